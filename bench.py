@@ -5,6 +5,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --config shard [--gpus N] [--utts-per-gpu 125000]   # BASELINE configs[4]
+    python bench.py --dump-outputs DIR                                   # + what the timed path computed, as DIR/*.npy
 
 Default workload (BASELINE.json configs[1]): ECAPA-TDNN C=1024, bf16 MFMA / fp32 accumulate, batch = 256 utterances of
 2 s @ 16 kHz per step, waveforms resident in HBM (8 distinct batches = 262 MB are rotated, so the timed loop does not
@@ -46,6 +47,8 @@ PEAK_F32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0
 SEED_STREAM = 20220829         # synthetic utterance stream of the embedding benches (yaml/configuration-voxceleb.yaml:15)
 SEED_SHARD = 5
+DUMP_MAX_BYTES = (64 << 20) - (64 << 10)   # --dump-outputs: 64 MB in all, less room for the .npy headers
+DUMP_SEED = 7                  # the fixed row sample of an output above DUMP_MAX_BYTES
 
 
 def parse():
@@ -71,7 +74,30 @@ def parse():
     ap.add_argument("--record-file", default=None,
                     help="JSON-lines file that receives every sub-record and the full (verbose) headline record; default "
                          "gpurun_out/bench_records.jsonl when gpurun_out/ exists, otherwise none.  stdout carries ONE compact line.")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed to DIR/embeddings.npy (float32): the last timed "
+                         "step's embeddings (every rank's, in rank order); --config shard: the gathered embeddings, a fixed seeded "
+                         "row sample when they exceed 64 MB (row indices in DIR/embeddings_rows.npy).  Inputs are seeded: two builds "
+                         "run with the same arguments can be compared output for output.")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def dump_outputs(dirpath, name, rows):
+    """--dump-outputs: the (N, D) float32 device matrix `rows` -> DIR/<name>.npy.  Above DUMP_MAX_BYTES a fixed, seeded sample of
+    rows is written instead (ascending; their indices, as float64, go to DIR/<name>_rows.npy)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    n, d = rows.shape
+    cap = DUMP_MAX_BYTES // (d * 4 + 8)
+    if n > cap:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+        np.save(os.path.join(dirpath, f"{name}_rows.npy"), idx.astype(np.float64))
+        rows = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+    np.save(os.path.join(dirpath, f"{name}.npy"), rows.to(torch.float32).cpu().numpy())
 
 
 HEADLINE_MAX_BYTES = 4096
@@ -876,7 +902,7 @@ def synth_batches(eng, n_batches, B, first_utt, dev, seed=SEED_STREAM):
     return wavs
 
 
-def shard_tail(eng, comm, ranks, shard, dev, n_local, do_scoring=True, carrier="", regen_embed=None):
+def shard_tail(eng, comm, ranks, shard, dev, n_local, do_scoring=True, carrier="", regen_embed=None, on_gathered=None):
     """after embedding: ONE all-gather of the (n_local, D) block per rank, then config-4-style scoring of the gathered matrix,
     row-sharded by enrol index: rank r scores the trials (i, pi(i)) with i in its block, and computes the AS-norm cohort
     statistics of its own rows (gathered with a second, small all-gather of (n_local, 2))."""
@@ -901,6 +927,8 @@ def shard_tail(eng, comm, ranks, shard, dev, n_local, do_scoring=True, carrier="
     rec["rccl_world"] = eng.comm_rank_world()[1] if comm is not None else 0
     if regen_embed is not None:
         rec.update(verify_gather(ranks, shard, gathered, n_local, regen_embed))
+    if on_gathered is not None:
+        on_gathered(gathered)                        # before the scoring below normalises `gathered` in place
     if not do_scoring:
         return rec, gathered
     N = world * n_local
@@ -961,6 +989,10 @@ def run_batch(args, ranks, dev):
     prof = eng.profile_results()
     eng.profile(False)
     check = verify_last_step(eng, wavs[(K - 1) % NBATCH], shard[(K - 1) * B:K * B], local, dev)
+    if args.dump_outputs and rank == 0:              # the last timed step of every rank, before shard_tail normalises `gathered`
+        dump_outputs(args.dump_outputs, "embeddings",
+                     torch.cat([gathered[r * K * B + (K - 1) * B:(r + 1) * K * B] for r in range(world)]) if ranks.launched
+                     else shard[(K - 1) * B:K * B])
     shard_rec = None
     if ranks.launched:
         def regen(r, n):          # the first n rows of rank r's block = its step 0 = utterances [r * NBATCH * B, ...) of the stream
@@ -1121,7 +1153,9 @@ def run_shard(args, ranks, dev, keep=False):
         eng.embed_wave(w, out=o, async_=True)
         torch.cuda.synchronize()
         return o
-    rec, _ = shard_tail(eng, comm, ranks, shard, dev, n_local, carrier=carrier, regen_embed=regen if ranks.launched else None)
+    dump_dir = getattr(args, "dump_outputs", None) if rank == 0 else None
+    rec, _ = shard_tail(eng, comm, ranks, shard, dev, n_local, carrier=carrier, regen_embed=regen if ranks.launched else None,
+                        on_gathered=(lambda g: dump_outputs(dump_dir, "embeddings", g)) if dump_dir else None)
     line = None
     if rank == 0:
         total = world * n_local

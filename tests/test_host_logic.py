@@ -76,7 +76,8 @@ def _make_handler(tmp_path, dim=16):
     net = sv_model.WrappedModel(enc)
     net.forward = lambda x, label=None: enc.forward(x)
     spec = {"sample_rate": 16000, "channels": 1, "sentence_len": 2.0, "win_len": 0.025, "hop_len": 0.01}
-    mh = sv_model.ModelHandling(net, audio_spec=spec, save_folder=str(tmp_path), embed_batch=5)
+    # device_feats=False: the host path, whose numpy blocks the CPU fakes can score, also when the box has a GPU
+    mh = sv_model.ModelHandling(net, audio_spec=spec, save_folder=str(tmp_path), embed_batch=5, device_feats=False)
     return mh, emb, spec
 
 
@@ -444,6 +445,25 @@ def test_bench_headline_is_one_compact_parsable_line(tmp_path, capsys):
     lines = [json.loads(ln) for ln in open(tmp_path / "r.jsonl")]
     assert [ln["record"] for ln in lines] == ["kernels", "rawnet2"] and len(lines[0]["kernels"]) == 60
     assert [json.loads(ln)["record"] for ln in cap.err.strip().splitlines()] == ["kernels", "rawnet2"]
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: a small output is written whole, in float32; one above the byte budget becomes a fixed, seeded,
+    ascending row sample (indices alongside) that is the same on every run and fits the budget."""
+    import bench
+    rows = torch.arange(300 * 8, dtype=torch.float32).reshape(300, 8)
+    bench.dump_outputs(str(tmp_path / "whole"), "embeddings", rows)
+    got = np.load(tmp_path / "whole" / "embeddings.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, rows.numpy())
+    assert not (tmp_path / "whole" / "embeddings_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40 * (8 * 4 + 8))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), "embeddings", rows)
+    got, idx = np.load(tmp_path / "a" / "embeddings.npy"), np.load(tmp_path / "a" / "embeddings_rows.npy")
+    assert got.shape == (40, 8) and idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got, rows.numpy()[idx.astype(np.int64)])
+    assert got.nbytes + idx.nbytes <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(got, np.load(tmp_path / "b" / "embeddings.npy")) and np.array_equal(idx, np.load(tmp_path / "b" / "embeddings_rows.npy"))
 
 
 def test_persistent_gemm_item_walk_covers_every_tile_once():
