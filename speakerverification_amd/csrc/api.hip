@@ -61,38 +61,32 @@ struct svhip_handle {
     hipStream_t lane_stream[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t lane_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};       // [lane] done events, [4] = fork point
     int lanes = 1;                            // > 1: the forward runs as that many batch slices on as many streams
-    // developer / test switches.  The SVHIP_* environment variables of the same names are read ONCE, in svhip_create (they are the
-    // defaults of a new handle); afterwards only svhip_set_option changes them: no getenv on any forward or scoring call
+    // developer / test switches: what the call sites read.  Defaults, environment variables and names: kDevOpts (below)
     struct DevOpts {
-        int layer_labels = 0;     // one profile row per GEMM shape
-        int x3_keep_f32 = 0;      // F32X3: keep the fp32 copies of the block outputs beside the split layout
-        int r2_big = 0;           // F32X3: Res2Net steps on the R2 form of the 256 x 256 kernel instead of r2_step
-        int asp_v1 = 0;           // bf16: asp_fused_kernel instead of asp_bf16_kernel
-        int rn_stop = -1;         // RawNet2: return after this many residual blocks (0: after the sinc front-end), unfused kernel sequence
-        int rn_snap = -1;         // RawNet2: keep block n's pre-activation as stage "rn_snap"
-        int rn_unfused = 0;       // RawNet2: the separate kernel sequence instead of rn_block128 / rn_tail / the folded shortcut
-        int asnorm_slab = 0;      // AS-norm statistics on the slab path
-        int asnorm_f32mfma = 0;   // AS-norm fused kernel on the exact fp32 MFMA instead of a split form
-        int score_f32mfma = 0;    // dense score GEMMs (svhip_score_matrix, the slab path's cohort GEMM) on the exact fp32 MFMA instead of the split form
-        int score_tiled = 0;      // dense score GEMMs on the tiled split kernel (gemm_pw) instead of the row-streaming one (score_h3w)
-        int asnorm_w32 = 0;       // AS-norm two-half-plane kernel on the 32-wide MFMA (round 4's first form) instead of 16x16x32
-        int asnorm_norefit = 0;   // AS-norm: embeddings the normal-quantile threshold does not fit go straight to the slab path (round 5's behaviour)
-        int asnorm_2s = 0;        // AS-norm split forms: candidate statistics of chunk c on a second stream under the matrix kernel of chunk c + 1
-        int asnorm_x6 = 0;        // AS-norm fused kernel on six bf16 MFMAs (three planes, round 3) instead of three fp16 MFMAs (two planes)
-        int rn_sinc_full = 0;     // RawNet2 fp16 handles: the 251-tap sinc kernel (round 5) instead of the symmetric 126-tap form
-        int fbank32 = 0;          // the 32-frame front-end kernel
-        int ff_abl = 0;           // tools only: fused front-end phase ablations (FbankTables::ff_abl)
-        int fbank_unfused = 0;    // bf16 handles: fbank -> prologue_stats -> prologue_apply (round 5) instead of the fused front-end
-        int pw3_cus = -1;         // cap of the persistent GEMM grids (0: persistent kernels off)
-        int pw4 = 0;              // plain pointwise bf16 layers with more tiles than workgroups on the four-wave kernel (gemm_pw4.hip)
-        int pw3_tail_off = 0;     // persistent 16-bit GEMMs: the last partial round as whole tiles (round 4) instead of column halves
-        int cv_off = 0;           // 16-bit handles: conv-gather GEMMs on the per-tile kernel instead of the persistent one
-        int n128_off = 0;         // bf16: asp.tdnn on gemm_pw instead of gemm_n128
-        int rn_pool_off = 0;      // F32X3 handles: conv2 of the long pooled blocks writes the un-pooled output, rn_maxpool3 pools it (tests)
-        int rn_step_off = 0;      // F32X3 handles: the 128 -> 128 blocks' convolutions on the tiled in-register-split kernel (tests)
-        int rn_sinc_f32 = 0;      // F32X3 handles: the sinc front-end on the exact fp32 MFMA (tests) instead of three fp16 MFMAs per product
-        int rn_tail_big = 0;      // RawNet2 block tail: one workgroup per utterance at every batch size (tests)
-        int r2_slices = -1;       // bf16 Res2Net chain: time slices per utterance (-1: by batch size, 0 / 1: whole utterances, n: forced)
+        int layer_labels;         // one profile row per GEMM shape
+        int x3_keep_f32;          // F32X3: keep the fp32 copies of the block outputs beside the split layout
+        int r2_big;               // F32X3: Res2Net steps on the R2 form of the 256 x 256 kernel instead of r2_step
+        int asp_v1;               // bf16: asp_fused_kernel instead of asp_bf16_kernel
+        int rn_stop;              // RawNet2: return after this many residual blocks (0: after the sinc front-end), unfused kernel sequence
+        int rn_snap;              // RawNet2: keep block n's pre-activation as stage "rn_snap"
+        int rn_unfused;           // RawNet2: the separate kernel sequence instead of rn_block128 / rn_tail / the folded shortcut
+        int asnorm_slab;          // AS-norm statistics on the slab path
+        int asnorm_f32mfma;       // AS-norm fused kernel on the exact fp32 MFMA instead of the split form
+        int score_f32mfma;        // dense score GEMMs (svhip_score_matrix, the slab path's cohort GEMM) on the exact fp32 MFMA instead of the split form
+        int score_tiled;          // dense score GEMMs on the tiled split kernel (gemm_pw) instead of the row-streaming one (score_h3w)
+        int asnorm_norefit;       // AS-norm: embeddings the normal-quantile threshold does not fit go straight to the slab path (round 5's behaviour)
+        int rn_sinc_full;         // RawNet2 fp16 handles: the 251-tap sinc kernel (round 5) instead of the symmetric 126-tap form
+        int fbank32;              // the 32-frame front-end kernel
+        int fbank_unfused;        // bf16 handles: fbank -> prologue_stats -> prologue_apply (round 5) instead of the fused front-end
+        int pw3_cus;              // cap of the persistent GEMM grids (0: persistent kernels off)
+        int pw3_tail_off;         // persistent 16-bit GEMMs: the last partial round as whole tiles (round 4) instead of column halves
+        int cv_off;               // 16-bit handles: conv-gather GEMMs on the per-tile kernel instead of the persistent one
+        int n128_off;             // bf16: asp.tdnn on gemm_pw instead of gemm_n128
+        int rn_pool_off;          // F32X3 handles: conv2 of the long pooled blocks writes the un-pooled output, rn_maxpool3 pools it (tests)
+        int rn_step_off;          // F32X3 handles: the 128 -> 128 blocks' convolutions on the tiled in-register-split kernel (tests)
+        int rn_sinc_f32;          // F32X3 handles: the sinc front-end on the exact fp32 MFMA (tests) instead of three fp16 MFMAs per product
+        int rn_tail_big;          // RawNet2 block tail: one workgroup per utterance at every batch size (tests)
+        int r2_slices;            // bf16 Res2Net chain: time slices per utterance (-1: by batch size, 0 / 1: whole utterances, n: forced)
     } opt;
     bool bf16 = false;                        // 16-bit storage handle: bf16, or fp16 when `f16` is set (the flag keeps its round-1 name)
     bool f16 = false;                         // SVHIP_F16: the 16-bit type is IEEE half (RawNet2)
@@ -222,6 +216,41 @@ struct svhip_handle {
 };
 
 namespace {
+
+// The developer / test options, one row each: svhip_set_option's names (include/svhip.h lists the same), the DevOpts field, the
+// SVHIP_* environment variable (nullptr: none) and the default.  svhip_create reads the variables ONCE, as a new handle's defaults;
+// afterwards only svhip_set_option changes the fields — no getenv on any forward or scoring call.  Each variable keeps its own parse:
+// OPT_SET: set at all -> 1 (SVHIP_LAYER_LABELS=0 turns labels on); OPT_IS1: a value starting with '1' -> 1; OPT_NUM: atoi.
+enum DevOptParse { OPT_NO_ENV, OPT_SET, OPT_IS1, OPT_NUM };
+struct DevOptRow { const char* name; int svhip_handle::DevOpts::*field; const char* env; DevOptParse parse; int dflt; };
+#define SV_OPT(name, env, parse, dflt) {#name, &svhip_handle::DevOpts::name, env, parse, dflt}
+const DevOptRow kDevOpts[] = {
+    SV_OPT(layer_labels, "SVHIP_LAYER_LABELS", OPT_SET, 0),
+    SV_OPT(x3_keep_f32, "SVHIP_X3_KEEP_F32", OPT_SET, 0),
+    SV_OPT(r2_big, "SVHIP_R2_BIG", OPT_IS1, 0),
+    SV_OPT(asp_v1, "SVHIP_ASP_V1", OPT_IS1, 0),
+    SV_OPT(rn_stop, "SVHIP_RN_STOP", OPT_NUM, -1),
+    SV_OPT(rn_snap, "SVHIP_RN_SNAP", OPT_NUM, -1),
+    SV_OPT(rn_unfused, "SVHIP_RN_UNFUSED", OPT_SET, 0),
+    SV_OPT(asnorm_slab, "SVHIP_ASNORM_SLAB", OPT_SET, 0),
+    SV_OPT(asnorm_f32mfma, "SVHIP_ASNORM_F32MFMA", OPT_SET, 0),
+    SV_OPT(score_f32mfma, "SVHIP_SCORE_F32MFMA", OPT_SET, 0),
+    SV_OPT(score_tiled, "SVHIP_SCORE_TILED", OPT_SET, 0),
+    SV_OPT(asnorm_norefit, nullptr, OPT_NO_ENV, 0),
+    SV_OPT(rn_sinc_full, "SVHIP_RN_SINC_FULL", OPT_IS1, 0),
+    SV_OPT(fbank32, "SVHIP_FBANK32", OPT_IS1, 0),
+    SV_OPT(fbank_unfused, "SVHIP_FBANK_UNFUSED", OPT_IS1, 0),
+    SV_OPT(pw3_cus, "SVHIP_PW3_CUS", OPT_NUM, -1),
+    SV_OPT(pw3_tail_off, "SVHIP_PW3_TAIL_OFF", OPT_IS1, 0),
+    SV_OPT(cv_off, "SVHIP_CV_OFF", OPT_IS1, 0),
+    SV_OPT(n128_off, "SVHIP_N128_OFF", OPT_IS1, 0),
+    SV_OPT(rn_pool_off, "SVHIP_RN_POOL_OFF", OPT_IS1, 0),
+    SV_OPT(rn_step_off, "SVHIP_RN_STEP_OFF", OPT_IS1, 0),
+    SV_OPT(rn_sinc_f32, "SVHIP_RN_SINC_F32", OPT_IS1, 0),
+    SV_OPT(rn_tail_big, "SVHIP_RN_TAIL_BIG", OPT_IS1, 0),
+    SV_OPT(r2_slices, "SVHIP_R2_SLICES", OPT_NUM, -1),
+};
+#undef SV_OPT
 
 #define SV_FAIL(h, code, ...)                                   \
     do {                                                        \
@@ -978,6 +1007,12 @@ int alloc_workspace(svhip_handle* h) {
     return SVHIP_OK;
 }
 
+// the handle's persistent-GEMM options (pw3_cus, pw3_tail_off) into the parameters of a GEMM launch
+static void gemm_options(const svhip_handle* h, GemmParams& p) {
+    p.pw3_cus = h->opt.pw3_cus;
+    p.tail_split = h->opt.pw3_tail_off ? 0 : 1;
+}
+
 // zero page of a conv-gather GEMM whose A operand starts at `A`: the zero tail of the RawNet2 activation buffer that holds A (behind
 // the operand, within 4 GiB: what gemm_pw3's 16-bit conv-gather form needs), else the handle's stand-alone zero page
 const void* zero_page_for(const svhip_handle* h, const void* A) {
@@ -1006,7 +1041,7 @@ int conv_gemm(svhip_handle* h, const char* label, const ConvLayer& L, const void
     p.lda = lda; p.lda2 = lda2; p.ldy = ldy; p.ld_bu = ld_bu;
     p.T = T > 0 ? T : h->T; p.taps = L.taps; p.dil = L.dil; p.cin = L.cin; p.pad_mode = pad_mode;
     p.act1 = act1; p.act2 = act2; p.out_f32 = out_f32 ? 1 : 0;
-    p.f16 = h->f16 ? 1 : 0; p.pw3_cus = h->opt.pw3_cus; p.tail_split = h->opt.pw3_tail_off ? 0 : 1; p.pw4 = h->opt.pw4;
+    p.f16 = h->f16 ? 1 : 0; gemm_options(h, p);
     const bool bf = h->bf16;
     hipStream_t st = h->cur;
     (void)label;
@@ -1041,7 +1076,7 @@ int conv_gemm(svhip_handle* h, const char* label, const ConvLayer& L, const void
     }
     // profile labels name the kernel instance (one label == one kernel symbol in a rocprofv3 trace)
     const GemmRoute route = gemm_route(p, bf);
-    const char* klabel = route == ROUTE_PW3 ? ((p.pw4 && gemm_pw4_supported(p, bf)) ? "gemm_pw4" : "gemm_pw3") : route == ROUTE_PW3CV ? "gemm_pw3cv16" : route == ROUTE_N128 ? "gemm_n128" : route == ROUTE_PW2 ? (L.taps > 1 ? "gemm_pw2_conv" : "gemm_pw2")
+    const char* klabel = route == ROUTE_PW3 ? "gemm_pw3" : route == ROUTE_PW3CV ? "gemm_pw3cv16" : route == ROUTE_N128 ? "gemm_n128" : route == ROUTE_PW2 ? (L.taps > 1 ? "gemm_pw2_conv" : "gemm_pw2")
                          : L.taps > 1 ? (A2 ? "gemm_conv_add" : "gemm_conv") : (route == ROUTE_GENERIC ? "gemm_generic" : "gemm_pw");
     char shaped[96];
     if (h->opt.layer_labels) {            // developer hook (SVHIP_LAYER_LABELS): one profile row per GEMM shape
@@ -1096,7 +1131,7 @@ int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, int B) 
         q.A = a32; q.lda = lda32; q.W = L.Ws32; q.x3 = 2; q.Y = MFA; q.ldy = L.N;
         q.bias = L.bias; q.scale = L.scale; q.shift = L.shift;
         q.M = M; q.N = L.N; q.K = L.K; q.Kp = L.Kp; q.Wrows = L.Np; q.T = T; q.taps = L.taps; q.act1 = ACT_GELU; q.num_cu = h->num_cu;
-        q.pw3_cus = h->opt.pw3_cus; q.tail_split = h->opt.pw3_tail_off ? 0 : 1;
+        gemm_options(h, q);
         if (cs) { q.colsum = cs_base; q.colsum_sq = 1; q.colsum_stride = h->colsum_region; }
         return gemm_pw3x3_supported(q);
     };
@@ -1114,7 +1149,7 @@ int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, int B) 
         q.A = h->s32_buf; q.lda = L.cv_cin; q.W = L.Wcv; q.Wrows = L.N; q.x3 = 2; q.Y = X0; q.ldy = C;
         q.bias = L.bias; q.scale = L.scale; q.shift = L.shift;
         q.M = M; q.N = L.N; q.K = L.taps * L.cv_cin; q.Kp = L.cv_Kp; q.T = T; q.taps = L.taps; q.dil = L.dil; q.cin = L.cv_cin; q.pad_mode = PAD_REFLECT;
-        q.act1 = ACT_GELU; q.act2 = ACT_NONE; q.num_cu = h->num_cu; q.pw3_cus = h->opt.pw3_cus; q.tail_split = h->opt.pw3_tail_off ? 0 : 1;
+        q.act1 = ACT_GELU; q.act2 = ACT_NONE; q.num_cu = h->num_cu; gemm_options(h, q);
         // (with s32_only and tdnn1 of the first block on the X3 kernel, X0 itself is written in the split layout: no conversion pass,
         //  block 1's residual is read as hi + lo, svhip_get_stage rebuilds the fp32 view)
         q.y_s32 = (s32_only && x3_route(h->tdnn1[0], X0, C, false)) ? 1 : 0;
@@ -1156,7 +1191,7 @@ int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, int B) 
             q.A = us[(j - 1) & 1]; q.lda = C8; q.W = L.Ws32; q.Wrows = L.N; q.x3 = 2;
             q.bias = L.bias; q.scale = L.scale; q.shift = L.shift;
             q.M = M; q.N = L.N; q.K = L.K; q.Kp = L.Kp; q.T = T; q.taps = 3; q.dil = L.dil; q.cin = L.cin; q.pad_mode = PAD_REFLECT;
-            q.act1 = ACT_RELU; q.act2 = ACT_NONE; q.num_cu = h->num_cu; q.pw3_cus = h->opt.pw3_cus; q.tail_split = h->opt.pw3_tail_off ? 0 : 1;
+            q.act1 = ACT_RELU; q.act2 = ACT_NONE; q.num_cu = h->num_cu; gemm_options(h, q);
             q.Y = h2s + (size_t)j * C8 * 4; q.ldy = C;
             if (j < 7) { q.R = static_cast<const float*>(H1) + (size_t)(j + 1) * C8; q.ldr = C; q.Y2 = us[j & 1]; q.lda2 = C8; }
             return q;
@@ -1315,7 +1350,7 @@ static GemmParams conv2sc_params(svhip_handle* h, const svhip_handle::RnBlock& K
     p.M = M; p.N = K.cout; p.K = K.conv2.K; p.Kp = K.conv2.K + K.cin; p.Wrows = K.conv2.Np;
     p.lda = K.cout; p.ldy = K.cout; p.T = T; p.taps = 3; p.dil = 1; p.cin = K.cout; p.pad_mode = PAD_ZERO;
     p.A3 = pre; p.lda3 = K.cin; p.K3 = K.cin;
-    p.num_cu = h->num_cu; p.f16 = h->f16 ? 1 : 0; p.pw3_cus = h->opt.pw3_cus; p.tail_split = h->opt.pw3_tail_off ? 0 : 1;
+    p.num_cu = h->num_cu; p.f16 = h->f16 ? 1 : 0; gemm_options(h, p);
     return p;
 }
 static bool conv2sc_fits(svhip_handle* h, const svhip_handle::RnBlock& K, const void* pre, const void* hb, void* o, int M, int T) {
@@ -1330,7 +1365,7 @@ static bool conv_cv_persistent(svhip_handle* h, const ConvLayer& L, const void* 
     p.bias = L.bias; p.scale = L.scale; p.shift = L.shift; p.zeros = h->d_zeros; p.ones = h->d_ones; p.zero_page = zero_page_for(h, A);
     p.M = M; p.N = L.N; p.K = L.K; p.Kp = L.Kp; p.Wrows = L.Np; p.lda = lda; p.ldy = L.N; p.T = T;
     p.taps = L.taps; p.dil = L.dil; p.cin = L.cin; p.pad_mode = pad_mode;
-    p.num_cu = h->num_cu; p.f16 = h->f16 ? 1 : 0; p.pw3_cus = h->opt.pw3_cus; p.tail_split = h->opt.pw3_tail_off ? 0 : 1; p.cv_off = h->opt.cv_off;
+    p.num_cu = h->num_cu; p.f16 = h->f16 ? 1 : 0; gemm_options(h, p); p.cv_off = h->opt.cv_off;
     return h->bf16 && gemm_route(p, true) == ROUTE_PW3CV;
 }
 
@@ -1708,15 +1743,9 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
     h->bf16 = cfg->compute == SVHIP_BF16 || h->f16;
     h->dt = h->f16 ? DT_F16 : h->bf16 ? DT_BF16 : DT_F32;
     h->x3 = cfg->compute == SVHIP_F32X3;
-    {   // the developer switches' defaults come from the environment, once
-        auto flag = [](const char* n) { return getenv(n) != nullptr ? 1 : 0; };
-        auto is1 = [](const char* n) { const char* e = getenv(n); return (e && e[0] == '1') ? 1 : 0; };
-        auto num = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
-        svhip_handle::DevOpts& o = h->opt;
-        o.layer_labels = flag("SVHIP_LAYER_LABELS"); o.x3_keep_f32 = flag("SVHIP_X3_KEEP_F32"); o.r2_big = is1("SVHIP_R2_BIG");
-        o.asp_v1 = is1("SVHIP_ASP_V1"); o.rn_stop = num("SVHIP_RN_STOP", -1); o.rn_snap = num("SVHIP_RN_SNAP", -1);
-        o.rn_unfused = flag("SVHIP_RN_UNFUSED"); o.asnorm_slab = flag("SVHIP_ASNORM_SLAB"); o.asnorm_f32mfma = flag("SVHIP_ASNORM_F32MFMA"); o.asnorm_x6 = flag("SVHIP_ASNORM_X6"); o.asnorm_w32 = flag("SVHIP_ASNORM_W32"); o.score_tiled = flag("SVHIP_SCORE_TILED"); o.score_f32mfma = flag("SVHIP_SCORE_F32MFMA");
-        o.fbank32 = is1("SVHIP_FBANK32"); o.rn_sinc_full = is1("SVHIP_RN_SINC_FULL"); o.fbank_unfused = is1("SVHIP_FBANK_UNFUSED"); o.pw3_cus = num("SVHIP_PW3_CUS", -1); o.pw3_tail_off = is1("SVHIP_PW3_TAIL_OFF"); o.pw4 = is1("SVHIP_PW4"); o.asnorm_2s = is1("SVHIP_ASNORM_2S"); o.cv_off = is1("SVHIP_CV_OFF"); o.n128_off = is1("SVHIP_N128_OFF"); o.r2_slices = num("SVHIP_R2_SLICES", -1); o.rn_tail_big = is1("SVHIP_RN_TAIL_BIG"); o.rn_sinc_f32 = is1("SVHIP_RN_SINC_F32"); o.rn_step_off = is1("SVHIP_RN_STEP_OFF"); o.rn_pool_off = is1("SVHIP_RN_POOL_OFF");
+    for (const DevOptRow& r : kDevOpts) {       // the developer switches' defaults come from the environment, once
+        const char* e = r.env ? getenv(r.env) : nullptr;
+        h->opt.*r.field = !e ? r.dflt : r.parse == OPT_SET ? 1 : r.parse == OPT_IS1 ? (e[0] == '1' ? 1 : 0) : atoi(e);
     }
     h->esz = h->bf16 ? 2 : 4;
     h->T = cfg->samples / cfg->hop_length + 1;
@@ -2284,16 +2313,14 @@ int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, co
         void *mb, *cand, *cnt, *flag;
         const size_t mb_bytes = (size_t)(D + 32) * D * 4;          // [MB | slice partials of its computation]
         const size_t cand_elems = (size_t)chunk * 2 * ASNORM_CAND_PER_LANE, cnt_elems = (size_t)chunk * 4;      // (2 or 4 candidate lists per embedding)
-        // (the exact default is the six-bf16-MFMA form where it is built: scores to fp32 rounding at 2.7 x the fp32 matrix rate)
-        // (the exact default is a split form where it is built: scores to fp32 rounding at several times the fp32 matrix rate — two half
-        //  planes / three fp16 MFMAs (D = 192, 256); option asnorm_x6: three bf16 planes / six bf16 MFMAs, round 3's form, D = 192)
-        const int nplanes = h->opt.asnorm_x6 ? 3 : 2;
-        const bool x6 = asnorm_fused6_supported(D, nplanes) && !h->opt.asnorm_f32mfma;
-        // (x6: the candidate kernel takes 1.7 ms of 17 on its own and 7 when it shares the CUs with the matrix kernel: one stream.
+        // (the exact default is the split form where it is built: scores to fp32 rounding at several times the fp32 matrix rate — two half
+        //  planes / three fp16 MFMAs, D = 192, 256)
+        const bool split = (D == 192 || D == 256) && !h->opt.asnorm_f32mfma;
+        // (split: the candidate kernel takes 1.7 ms of 17 on its own and 7 when it shares the CUs with the matrix kernel: one stream.
         //  The fp32-MFMA form keeps the second stream: 26.1 - 26.9 against 27.5 ms)
-        const int nbuf = (N > chunk && (!x6 || h->opt.asnorm_2s)) ? 2 : 1;
+        const int nbuf = (N > chunk && !split) ? 2 : 1;
         const size_t mom_bytes = (cohort_moments_scratch_bytes(D) + 255) & ~(size_t)255;
-        if ((rc = scratch(h, svhip_handle::SCR_MB, mb_bytes + mom_bytes + (x6 ? asnorm_planes_bytes(D, K) : 0), &mb))) return rc;
+        if ((rc = scratch(h, svhip_handle::SCR_MB, mb_bytes + mom_bytes + (split ? asnorm_planes_bytes(D, K) : 0), &mb))) return rc;
         if ((rc = scratch(h, svhip_handle::SCR_CAND, cand_elems * 4 * nbuf, &cand))) return rc;
         if ((rc = scratch(h, svhip_handle::SCR_CNT, (cnt_elems + (size_t)chunk) * 4 * nbuf, &cnt))) return rc;      // per buffer: [counts (chunk, 4) | row factors (chunk)]
         if ((rc = scratch(h, svhip_handle::SCR_FLAG, (size_t)(2 * N + 1) * 4, &flag))) return rc;        // [count | flagged ids (N) | their candidate counts (N)]
@@ -2306,14 +2333,14 @@ int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, co
         if ((rc = run(h, "asnorm_cohort_moments", 0, [&]() { return launch_cohort_moments((const float*)dC, K, D, (float*)mb, (float*)((char*)mb + mb_bytes), h->stream); }))) return rc;
         AsnormFusedParams fp;
         fp.cohort = (const float*)dC; fp.K = K; fp.MB = (const float*)mb; fp.z = asnorm_tail_z(K, top);
-        if (x6) {
+        if (split) {
             void* planes = (char*)mb + mb_bytes + mom_bytes;
-            fp.planes = planes; fp.nplanes = nplanes;
-            fp.nlists = (nplanes == 2 && !h->opt.asnorm_w32) ? 4 : 2;       // the 16-wide-MFMA kernel: four lists per embedding
-            // the default kernel scales its operands by exact powers of two (asnorm_fused.hip, "operand scaling"): the cohort's max |x| goes to
+            fp.planes = planes;
+            fp.nlists = 4;                  // the 16-wide-MFMA kernel: four lists per embedding
+            // the kernel scales its operands by exact powers of two (asnorm_fused.hip, "operand scaling"): the cohort's max |x| goes to
             // a device word behind the two planes (the buffer is sized for three)
-            uint32_t* pscale = fp.nlists == 4 ? reinterpret_cast<uint32_t*>((char*)planes + (size_t)2 * (D + 32 + K) * D * 2) : nullptr;
-            if ((rc = run(h, "asnorm_planes", 0, [&]() { return launch_asnorm_planes((const float*)mb, (const float*)dC, K, D, planes, h->stream, nplanes, pscale); }))) return rc;
+            uint32_t* pscale = reinterpret_cast<uint32_t*>((char*)planes + (size_t)2 * (D + 32 + K) * D * 2);
+            if ((rc = run(h, "asnorm_planes", 0, [&]() { return launch_asnorm_planes((const float*)mb, (const float*)dC, K, D, planes, h->stream, pscale); }))) return rc;
             fp.pscale = pscale;
         }
         int c = 0;
@@ -2351,7 +2378,7 @@ int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, co
         SV_HIP(h, hipStreamSynchronize(h->stream));
         int64_t refit_rows = 0;
         int refit_passes = 0;
-        if (nf > 0 && x6 && fp.nlists == 4 && !h->opt.asnorm_norefit) {
+        if (nf > 0 && split && !h->opt.asnorm_norefit) {
             // REFIT (round 6).  tau = mean + z sd with z the normal quantile fits isotropic embeddings; real cohorts are not isotropic
             // (speaker centroids cluster by gender / language: bimodal cohort scores), and a row whose threshold passes fewer than `top`
             // scores, or overflows a list, used to take the slab path — N x K scores through HBM.  Such rows now go through the SAME fused
@@ -2605,17 +2632,10 @@ double svhip_workload_flops(const svhip_handle* h) { return h ? h->flops_per_utt
 
 int svhip_set_option(svhip_handle* h, const char* name, int32_t value) {
     if (!h || !name) return SVHIP_ERR_INVALID;
-    const std::string n(name);
-    svhip_handle::DevOpts& o = h->opt;
-    struct { const char* key; int* slot; } table[] = {
-        {"layer_labels", &o.layer_labels}, {"x3_keep_f32", &o.x3_keep_f32}, {"r2_big", &o.r2_big}, {"asp_v1", &o.asp_v1},
-        {"rn_stop", &o.rn_stop}, {"rn_snap", &o.rn_snap}, {"rn_unfused", &o.rn_unfused}, {"asnorm_slab", &o.asnorm_slab},
-        {"asnorm_f32mfma", &o.asnorm_f32mfma}, {"asnorm_x6", &o.asnorm_x6}, {"asnorm_2s", &o.asnorm_2s}, {"asnorm_norefit", &o.asnorm_norefit}, {"asnorm_w32", &o.asnorm_w32}, {"score_tiled", &o.score_tiled}, {"score_f32mfma", &o.score_f32mfma}, {"fbank32", &o.fbank32}, {"rn_sinc_full", &o.rn_sinc_full}, {"fbank_unfused", &o.fbank_unfused}, {"ff_abl", &o.ff_abl}, {"pw3_cus", &o.pw3_cus}, {"pw3_tail_off", &o.pw3_tail_off}, {"pw4", &o.pw4}, {"cv_off", &o.cv_off},
-        {"r2_slices", &o.r2_slices}, {"rn_tail_big", &o.rn_tail_big}, {"rn_sinc_f32", &o.rn_sinc_f32}, {"rn_step_off", &o.rn_step_off}, {"rn_pool_off", &o.rn_pool_off}, {"n128_off", &o.n128_off}};
-    for (auto& t : table)
-        if (n == t.key) {
-            *t.slot = value;
-            h->fb.force32 = o.fbank32; h->fb.ff_abl = o.ff_abl;
+    for (const DevOptRow& r : kDevOpts)
+        if (strcmp(name, r.name) == 0) {
+            h->opt.*r.field = value;
+            h->fb.force32 = h->opt.fbank32;
             return SVHIP_OK;
         }
     SV_FAIL(h, SVHIP_ERR_INVALID, "unknown option %s", name);

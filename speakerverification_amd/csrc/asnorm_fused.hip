@@ -171,178 +171,6 @@ __global__ __launch_bounds__(256, 2) void asnorm_fused_kernel(AsnormFusedParams 
     if (valid) p.cnt[row * 2 + h] = cnt;
 }
 
-// ---- the same kernel on SIX bf16 MFMAs per product block ("x6"): fp32-grade scores at 2.7 x the fp32 matrix rate ----------------
-// An fp32 value splits EXACTLY into three bf16 parts, v = h + m + l (8 + 8 + 8 mantissa bits), so a product is the nine partial
-// products of the parts; the three smallest (m l, l m, l l: <= 2^-26 of |a b|) are dropped and the other six are bf16 MFMAs with
-// exact fp32 products and fp32 accumulation: h h, h m, m h, h l, l h, m m.  A score (|e| = |c| = 1) is then within 1.5e-8 of the
-// exact-fp32-MFMA kernel's plus the usual accumulation rounding — three orders below anything AS-norm can see (the 2^-17 of the
-// three-product form is NOT: 2e-4 on the normalised scores) — while v_mfma_f32_32x32x16_bf16 does 16 k values in the 32
-// cycles v_mfma_f32_32x32x2_f32 needs for one: six of them per 16 k against eight fp32 MFMAs of 64 cycles, 192 against 512 cycles.
-// Same structure as above (embeddings = B operand in registers, cohort blocks through LDS, lane-local selection, exact moments as
-// leading pseudo-cohort blocks); the cohort image (pseudo rows first, then the K cohort rows) is split into three bf16 planes once
-// per call (split3_planes_kernel).  D = 192 only: the B operand is 144 VGPRs.
-//
-// NPL = 2 ("h3", round 4, the default): TWO planes of IEEE half and THREE fp16 MFMAs per product block (hi.hi + hi.lo + lo.hi).  A half
-// plane carries 11 significant bits, so hi + lo holds 22 (2^-23 relative) while lo is a normal half, and below |v| = 2^-3 — where
-// the components of unit embeddings live — lo is a subnormal half with an ABSOLUTE quantum of 2^-24: a component is represented to
-// 3e-8 absolute, a score of unit vectors to ~4e-8 (measured against the float64 oracle: tests), the same class as x6, at half the MFMAs,
-// two thirds of the LDS bytes and 96 instead of 144 operand VGPRs (D = 256 fits as well).
-template <int D, int NPL>
-__global__ __launch_bounds__(256, 2) void asnorm_fused6_kernel(AsnormFusedParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int CH = D / 8;                       // 16-byte chunks (8 values) per row of a plane
-    constexpr int PL = 32 * D * 2;                  // one plane of a block of 32 rows
-    constexpr int BLK = NPL * PL;
-    constexpr int NDMA = NPL * 32 * CH / 256;       // DMA instructions per thread per block
-    constexpr int NP = D / 32 + 1;                  // pseudo-cohort blocks: rows of M, then cbar
-    constexpr int NS = D / 16;                      // MFMA k steps per block
-    static_assert(D % 64 == 0 && (NPL * 32 * CH) % 256 == 0 && CH % 8 == 0, "block image: whole DMA rounds, chunk groups of 8");
-    static_assert(NPL == 2 || NPL == 3, "two half planes or three bf16 planes");
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 31, h = lane >> 5;
-    const int64_t row = (int64_t)blockIdx.x * 128 + wave * 32 + j;
-    const bool valid = row < p.N;
-    // (per-lane addresses are kept as 32-bit offsets from the scalar bases: every VGPR counts here)
-    const uint32_t eoff = (uint32_t)((valid ? row : p.N - 1) * D);                  // < 2^31 elements per launch (host check)
-    const float* __restrict__ erow = p.E + eoff;
-
-    // B operand: embedding j, k = 16 s + 8 h .. + 7 for k step s, in three bf16 parts (or two half parts: bh, bm)
-    bf16x8 bh[NS], bm[NS], bl[NPL == 3 ? NS : 1];
-#pragma unroll
-    for (int s_ = 0; s_ < NS; ++s_) {
-        const f32x4 v0 = *reinterpret_cast<const f32x4*>(erow + 16 * s_ + 8 * h);
-        const f32x4 v1 = *reinterpret_cast<const f32x4*>(erow + 16 * s_ + 8 * h + 4);
-        if (NPL == 3) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float v = u < 4 ? v0[u] : v1[u - 4];
-                const bf16_t a = static_cast<bf16_t>(v);
-                const float r1 = v - static_cast<float>(a);
-                const bf16_t b = static_cast<bf16_t>(r1);
-                bh[s_][u] = a;
-                bm[s_][u] = b;
-                bl[s_][u] = static_cast<bf16_t>(r1 - static_cast<float>(b));
-            }
-        } else {
-            f16x8 a8, b8;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float v = u < 4 ? v0[u] : v1[u - 4];
-                const f16_t a = static_cast<f16_t>(v);
-                a8[u] = a;
-                b8[u] = static_cast<f16_t>(v - static_cast<float>(a));
-            }
-            bh[s_] = __builtin_bit_cast(bf16x8, a8);
-            bm[s_] = __builtin_bit_cast(bf16x8, b8);
-        }
-    }
-
-    const int rows_total = NP * 32 + p.K;
-    const int nb = (rows_total + 31) / 32;
-    const char* planes = reinterpret_cast<const char*>(p.planes);
-    const int64_t plane_bytes = (int64_t)rows_total * D * 2;
-    // the image is lane-linear (16 bytes per lane): position -> (plane, row, chunk slot); the swizzle goes on the source chunk
-    auto issue = [&](int b, int buf) {
-        const int r0 = b * 32;
-        const int limit = rows_total - 1 - r0;          // the last block clamps its rows
-#pragma unroll
-        for (int q = 0; q < NDMA; ++q) {
-            const int pidx = q * 256 + tid;
-            const int pl = pidx / (32 * CH), rem = pidx - pl * (32 * CH);
-            const int i = rem / CH, cs = rem - i * CH;
-            const int c = (cs & ~7) | ((cs ^ (i >> 1)) & 7);
-            const char* src = planes + pl * plane_bytes + ((int64_t)(r0 + min(i, limit)) * D + c * 8) * 2;
-            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(smem + buf * BLK + (q * 256 + wave * 64) * 16), 16, 0, 0);
-        }
-    };
-    auto rd = [&](int buf, int pl, int s_) {          // A fragment: cohort row j of the block, k = 16 s + 8 h .. + 7
-        const int cs = 2 * s_ + h;
-        return *reinterpret_cast<const bf16x8*>(smem + buf * BLK + pl * PL + j * (D * 2) + (((cs & ~7) | ((cs ^ (j >> 1)) & 7)) << 4));
-    };
-    auto mfma_block = [&](int buf) {
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-        // A fragments are read ONE k step ahead of their six MFMAs, fenced (left alone hipcc issues each ds_read right in front of
-        // the wait of the MFMAs that use it, and a wave then sits out the LDS latency every k step whenever its SIMD partner is
-        // not in its own MFMA phase: matrix pipe busy 0.58)
-        bf16x8 ah = rd(buf, 0, 0), am = rd(buf, 1, 0), al = NPL == 3 ? rd(buf, 2, 0) : ah;
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s_ = 0; s_ < NS; ++s_) {
-            bf16x8 nh = ah, nm = am, nl = al;
-            if (s_ + 1 < NS) { nh = rd(buf, 0, s_ + 1); nm = rd(buf, 1, s_ + 1); if (NPL == 3) nl = rd(buf, 2, s_ + 1); }
-            __builtin_amdgcn_sched_barrier(0);
-            if (NPL == 3) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[s_], acc, 0, 0, 0);      // small terms first
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[s_], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm[s_], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh[s_], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm[s_], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[s_], acc, 0, 0, 0);
-            } else {            // (planes: h = hi, m = lo)
-                acc = Half16<f16_t>::mfma32(am, bh[s_], acc);
-                acc = Half16<f16_t>::mfma32(ah, bm[s_], acc);
-                acc = Half16<f16_t>::mfma32(ah, bh[s_], acc);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            ah = nh; am = nm; al = nl;
-        }
-        __builtin_amdgcn_s_setprio(0);
-        return acc;
-    };
-
-    float second = 0.0f, tau = 0.0f;
-    int cnt = 0;
-    const uint32_t coff = (uint32_t)(((valid ? row : 0) * 2 + h) * AF_CAPL);
-    // acc[r] = score of image row 32 b + (r & 3) + 8 (r >> 2) + 4 h against embedding j
-    auto process = [&](const f32x16& a, int b) {
-        if (b < NP - 1) {               // rows of M: (M e)_i . e_i
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 ev = *reinterpret_cast<const f32x4*>(p.E + eoff + 32 * b + 8 * g + 4 * h);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) second = fmaf(a[4 * g + u], ev[u], second);
-            }
-        } else if (b == NP - 1) {       // row 0 of the last pseudo block is cbar: the mean lives in register 0 of the h = 0 lanes
-            const float m = __shfl(a[0], j, 64);
-            const float sec = second + __shfl_xor(second, 32, 64);
-            tau = m + (p.zrow ? p.zrow[valid ? row : 0] : p.z) * sqrtf(fmaxf(sec - m * m, 0.0f));
-        } else {
-            const int kb = (b - NP) * 32 + 4 * h;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = kb + (r & 3) + 8 * (r >> 2);
-                const float v = a[r];
-                if (i < p.K && v > tau) {
-                    if (cnt < AF_CAPL && valid) p.cand[coff + cnt] = v;
-                    ++cnt;
-                }
-            }
-        }
-    };
-
-    issue(0, 0);
-    f32x16 accp;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accp[r] = 0.0f;
-    for (int b = 0; b < nb; ++b) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // block b has landed (and the candidate stores of one block ago, long since)
-        __syncthreads();                                       // ... for every wave; nobody still reads the other buffer
-        if (b + 1 < nb) issue(b + 1, (b + 1) & 1);
-        // the selection of the PREVIOUS block goes first: its candidate stores are then a whole MFMA phase old at the next wait
-        // (issued after the MFMAs they sat right in front of that wait: 18.8 ms for 1.2 M embeddings)
-        if (b > 0) process(accp, b - 1);
-        __builtin_amdgcn_sched_barrier(0);
-        accp = mfma_block(b & 1);
-    }
-    process(accp, nb - 1);
-    if (valid) p.cnt[row * 2 + h] = cnt;
-}
-
 // ---- operand scaling of the half-plane forms (round 5) --------------------------------------------------------------------------
 // IEEE-half planes have fp16's exponent range: a component beyond 65504 overflows, one below 2^-14 loses bits of its hi part, and lo is a
 // subnormal (2^-24 absolute) below 2^-3.  Embeddings are not always unit vectors (the reference scores raw embeddings when `normalize` is
@@ -384,8 +212,15 @@ __device__ __forceinline__ uint32_t absmax_fold(const uint32_t* __restrict__ par
     return max(max(fm[0], fm[1]), max(fm[2], fm[3]));
 }
 
-// ---- the two-half-plane form on v_mfma_f32_16x16x32_f16 ("h3w", round 4, the default) -------------------------------------------------
-// Same arithmetic as asnorm_fused6_kernel<D, 2> (hi.hi + hi.lo + lo.hi on IEEE-half planes, fp32 accumulate), on the 16-wide MFMA: on random
+// ---- the same kernel on two IEEE-half planes and three fp16 MFMAs per product block ("h3w", round 4, the default) ----------------------
+// Same structure as asnorm_fused_kernel (embeddings = B operand in registers, cohort blocks through LDS, lane-local selection, exact moments as
+// leading pseudo-cohort blocks); the cohort image (pseudo rows first, then the K cohort rows) is split into two half planes once per call
+// (split2_planes_kernel), and a product block is hi.hi + hi.lo + lo.hi with fp32 accumulation.  A half plane carries 11 significant bits, so
+// hi + lo holds 22 (2^-23 relative) while lo is a normal half, and below |v| = 2^-3 — where the components of unit embeddings live — lo is a
+// subnormal half with an ABSOLUTE quantum of 2^-24: a component is represented to 3e-8 absolute, a score of unit vectors to ~4e-8 (measured
+// against the float64 oracle: tests).  That is the class of round 3's six-bf16-MFMA form (three exact bf16 parts per value, 1.5e-8 from the
+// exact-fp32-MFMA kernel) at half its MFMAs, two thirds of its LDS bytes and 96 instead of 144 operand VGPRs (D = 256 fits as well); the
+// 2^-17 of a three-product bf16 form is NOT enough (2e-4 on the normalised scores).  It runs on the 16-wide MFMA: on random
 // data the chip holds a higher clock under the 16x16x32 instruction than under 32x32x16 (bare loops: 1.87 against 1.63 PFLOP/s,
 // tools/mfma_rate.hip; MI355X_MICROARCH.md, DVFS give-back), and this kernel runs at the pace of its MFMAs.  A wave still owns 32 embeddings
 // and walks the cohort in blocks of 32 rows: 2 row groups x 2 embedding groups of 16 per k step of 32.  Accumulator layout: lane (c = lane & 15,
@@ -460,7 +295,7 @@ __global__ __launch_bounds__(256, 2) void asnorm_h3w_kernel(AsnormFusedParams p)
     const int nb = (rows_total + 31) / 32;
     const char* planes = reinterpret_cast<const char*>(p.planes);
     const int64_t plane_bytes = (int64_t)rows_total * D * 2;
-    // the block image is the one of asnorm_fused6_kernel: lane-linear DMA, the swizzle on the source chunk
+    // the image is lane-linear (16 bytes per lane): position -> (plane, row, chunk slot); the swizzle goes on the source chunk
     auto issue = [&](int b, int buf) {
         const int r0 = b * 32;
         const int limit = rows_total - 1 - r0;          // the last block clamps its rows
@@ -486,7 +321,9 @@ __global__ __launch_bounds__(256, 2) void asnorm_h3w_kernel(AsnormFusedParams p)
         for (int rg = 0; rg < 2; ++rg)
 #pragma unroll
             for (int eg = 0; eg < 2; ++eg) acc[rg][eg] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // A fragments one k step ahead of their MFMAs, fenced (see asnorm_fused6_kernel)
+        // A fragments are read ONE k step ahead of their MFMAs, fenced (left alone hipcc issues each ds_read right in front of the wait
+        // of the MFMAs that use it, and a wave then sits out the LDS latency every k step whenever its SIMD partner is not in its own MFMA
+        // phase: matrix pipe busy 0.58 in round 3's form)
         bf16x8 ah[2] = {rd(buf, 0, 0, 0), rd(buf, 0, 1, 0)}, al[2] = {rd(buf, 1, 0, 0), rd(buf, 1, 1, 0)};
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -596,7 +433,9 @@ __global__ __launch_bounds__(256, 2) void asnorm_h3w_kernel(AsnormFusedParams p)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // block b has landed (and the candidate stores of one block ago, long since)
         __syncthreads();                                       // ... for every wave; nobody still reads the other buffer
         if (b + 1 < nb) issue(b + 1, (b + 1) & 1);
-        if (b > 0) process(accp, b - 1);                       // the selection of the PREVIOUS block first (asnorm_fused6_kernel)
+        // the selection of the PREVIOUS block goes first: its candidate stores are then a whole MFMA phase old at the next wait
+        // (issued after the MFMAs they sat right in front of that wait: 18.8 ms for 1.2 M embeddings)
+        if (b > 0) process(accp, b - 1);
         __builtin_amdgcn_sched_barrier(0);
         mfma_block(b & 1, accp);
     }
@@ -810,22 +649,7 @@ __global__ __launch_bounds__(256, 2) void score_h3w_kernel(ScoreH3Params p) {
     }
 }
 
-// fp32 rows -> three bf16 planes [3][rows_total][D]: rows [0, n0) from A (the pseudo-cohort rows MB), the rest from B (the cohort)
-__global__ __launch_bounds__(256) void split3_planes_kernel(const float* __restrict__ A, int n0, const float* __restrict__ B, int n1, int D,
-                                                            bf16_t* __restrict__ planes) {
-    const int64_t n = (int64_t)(n0 + n1) * D;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int64_t r = i / D;
-        const float v = r < n0 ? A[i] : B[i - (int64_t)n0 * D];
-        const bf16_t a = static_cast<bf16_t>(v);
-        const float r1 = v - static_cast<float>(a);
-        const bf16_t b = static_cast<bf16_t>(r1);
-        planes[i] = a;
-        planes[n + i] = b;
-        planes[2 * n + i] = static_cast<bf16_t>(r1 - static_cast<float>(b));
-    }
-}
-// ... -> two half planes [2][rows_total][D] (hi, lo) for the three-fp16-MFMA form
+// fp32 rows -> two half planes [2][rows_total][D] (hi, lo): rows [0, n0) from A (the pseudo-cohort rows MB), the rest from B (the cohort)
 // `pscale` (optional): the max-|x| word of B (absmax_bits_kernel): every row is multiplied by s = pow2_scale_of_bits(*pscale), the first
 // `sq_rows` rows of A (second-moment rows: products of two cohort values) by s^2
 __global__ __launch_bounds__(256) void split2_planes_kernel(const float* __restrict__ A, int n0, const float* __restrict__ B, int n1, int D,
@@ -847,7 +671,7 @@ __global__ __launch_bounds__(256) void split2_planes_kernel(const float* __restr
 }
 
 // one wave per embedding: exact statistics of the top-`top` of its candidates; rows that cannot be decided are flagged.
-// NL candidate lists per embedding (2: one per half-wave lane of the 32-wide kernels; 4: the 16-wide kernel), 2 * AF_CAPL slots in all.
+// NL candidate lists per embedding (2: one per half-wave lane of the fp32-MFMA kernel; 4: the half-plane kernel), 2 * AF_CAPL slots in all.
 template <int NL>
 __global__ __launch_bounds__(256) void asnorm_cand_stats_kernel(const float* __restrict__ cand, const int32_t* __restrict__ cnt, int64_t rows,
                                                                 int top, float* __restrict__ mu, float* __restrict__ sigma,
@@ -1000,18 +824,16 @@ hipError_t launch_cohort_moments(const float* cohort, int K, int D, float* MB, f
     return hipGetLastError();
 }
 
-// planes = 2: two half planes, three fp16 MFMAs (D = 192 / 256); planes = 3: three bf16 planes, six bf16 MFMAs (D = 192)
-bool asnorm_fused6_supported(int D, int planes) { return planes == 2 ? (D == 192 || D == 256) : (planes == 3 && D == 192); }
+// two half planes and, in the room of a third, the cohort's max-|x| word and its partials
 size_t asnorm_planes_bytes(int D, int K) { return (size_t)3 * (D + 32 + K) * D * 2; }
 
-hipError_t launch_asnorm_planes(const float* MB, const float* cohort, int K, int D, void* planes, hipStream_t stream, int nplanes, uint32_t* pscale) {
-    if (!MB || !cohort || !planes || K <= 0 || D % 32 != 0 || !(nplanes == 2 || nplanes == 3) || (pscale && nplanes != 2)) return hipErrorInvalidValue;
+hipError_t launch_asnorm_planes(const float* MB, const float* cohort, int K, int D, void* planes, hipStream_t stream, uint32_t* pscale) {
+    if (!MB || !cohort || !planes || K <= 0 || D % 32 != 0) return hipErrorInvalidValue;
     const int64_t n = (int64_t)(D + 32 + K) * D;
     const int64_t g = (n + 255) / 256;
     if (pscale)             // the cohort's max |x| -> pscale[1 ..] (partials; the split pass folds them into pscale[0]); cohort rows and the mean row are scaled by s, the D moment rows by s^2
         hipLaunchKernelGGL(absmax_bits_kernel, dim3(ABSMAX_WGS), dim3(256), 0, stream, cohort, (int64_t)K * D, pscale + 1);
-    if (nplanes == 2) hipLaunchKernelGGL(split2_planes_kernel, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, stream, MB, D + 32, cohort, K, D, reinterpret_cast<f16_t*>(planes), pscale, D);
-    else hipLaunchKernelGGL(split3_planes_kernel, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, stream, MB, D + 32, cohort, K, D, reinterpret_cast<bf16_t*>(planes));
+    hipLaunchKernelGGL(split2_planes_kernel, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, stream, MB, D + 32, cohort, K, D, reinterpret_cast<f16_t*>(planes), pscale, D);
     return hipGetLastError();
 }
 
@@ -1019,37 +841,23 @@ hipError_t launch_asnorm_fused(const AsnormFusedParams& p, int D, hipStream_t st
     if (p.N <= 0) return hipSuccess;
     if (!asnorm_fused_supported(D, p.K, 1) || !p.E || !p.cohort || !p.MB || !p.cand || !p.cnt) return hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(p.E) | reinterpret_cast<uintptr_t>(p.cohort) | reinterpret_cast<uintptr_t>(p.MB)) & 15) return hipErrorInvalidValue;
-    if (p.nlists != 2 && !(p.nlists == 4 && p.planes && p.nplanes == 2)) return hipErrorInvalidValue;      // (four lists: the 16-wide half-plane kernel only)
-    if (p.planes) {                                       // the split forms: three fp16 MFMAs on two half planes / six bf16 MFMAs on three
-        if (!asnorm_fused6_supported(D, p.nplanes) || (reinterpret_cast<uintptr_t>(p.planes) & 15) || p.N > (int64_t)1 << 21) return hipErrorInvalidValue;      // (32-bit lane offsets)
-        if (p.nlists == 4 && p.N * 2 * ASNORM_CAND_PER_LANE * 4 >= (int64_t)1 << 32) return hipErrorInvalidValue;      // (32-bit byte offsets into the candidate lists)
-        if (p.pscale && (p.nlists != 4 || !p.rowscale)) return hipErrorInvalidValue;                                    // (scaled planes: the 16-wide kernel, with its row factors)
+    if (p.nlists != (p.planes ? 4 : 2)) return hipErrorInvalidValue;      // (four lists: the half-plane kernel; two: the fp32-MFMA kernel)
+    if (p.planes) {                                       // the split form: three fp16 MFMAs on two half planes
+        if ((D != 192 && D != 256) || (reinterpret_cast<uintptr_t>(p.planes) & 15) || p.N > (int64_t)1 << 21) return hipErrorInvalidValue;      // (32-bit lane offsets)
+        if (p.N * 2 * ASNORM_CAND_PER_LANE * 4 >= (int64_t)1 << 32) return hipErrorInvalidValue;      // (32-bit byte offsets into the candidate lists)
+        if (p.pscale && !p.rowscale) return hipErrorInvalidValue;                                       // (scaled planes: the row factors go with them)
         const dim3 grid((unsigned)((p.N + 127) / 128));
-#define SV_AF6(DD, NP)                                                                                                      \
+#define SV_H3W(DD)                                                                                                          \
         {                                                                                                                   \
-            static DeviceOnce attr6;                                                                                        \
-            constexpr int lds6 = 2 * NP * 32 * DD * 2;                                                                      \
-            if (hipError_t e = set_max_dynamic_lds(attr6, reinterpret_cast<const void*>(asnorm_fused6_kernel<DD, NP>), lds6)) return e; \
-            hipLaunchKernelGGL((asnorm_fused6_kernel<DD, NP>), grid, dim3(256), lds6, stream, p);                           \
+            static DeviceOnce attrw;                                                                                        \
+            constexpr int ldsw = 2 * 2 * 32 * DD * 2;                                                                       \
+            if (hipError_t e = set_max_dynamic_lds(attrw, reinterpret_cast<const void*>(asnorm_h3w_kernel<DD>), ldsw)) return e; \
+            hipLaunchKernelGGL((asnorm_h3w_kernel<DD>), grid, dim3(256), ldsw, stream, p);                                  \
             return hipGetLastError();                                                                                       \
         }
-        if (p.nplanes == 3) SV_AF6(192, 3)
-        if (p.nlists == 4) {            // two half planes on the 16-wide MFMA (the default)
-#define SV_H3W(DD)                                                                                                          \
-            {                                                                                                               \
-                static DeviceOnce attrw;                                                                                    \
-                constexpr int ldsw = 2 * 2 * 32 * DD * 2;                                                                   \
-                if (hipError_t e = set_max_dynamic_lds(attrw, reinterpret_cast<const void*>(asnorm_h3w_kernel<DD>), ldsw)) return e; \
-                hipLaunchKernelGGL((asnorm_h3w_kernel<DD>), grid, dim3(256), ldsw, stream, p);                              \
-                return hipGetLastError();                                                                                   \
-            }
-            if (D == 192) SV_H3W(192)
-            SV_H3W(256)
+        if (D == 192) SV_H3W(192)
+        SV_H3W(256)
 #undef SV_H3W
-        }
-        if (D == 192) SV_AF6(192, 2)
-        SV_AF6(256, 2)
-#undef SV_AF6
     }
     switch (D) {
         case 192: return launch_fused_d<192>(p, stream);

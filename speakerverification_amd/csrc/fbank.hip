@@ -435,7 +435,7 @@ __global__ __launch_bounds__(FF_THREADS, 4) void fbank_fused_kernel(FbankTables 
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
             const int q4 = tid + u * FF_THREADS;
-            const bool in = q4 < nv && !(tb.ff_abl & 1);
+            const bool in = q4 < nv;
             v[u] = in ? *reinterpret_cast<const f32x4*>(x + j0 + 4 * q4) : f32x4{0.f, 0.f, 0.f, 0.f};
             pv[u] = in ? x[j0 + 4 * q4 - 1] : 0.0f;
         }
@@ -463,7 +463,7 @@ __global__ __launch_bounds__(FF_THREADS, 4) void fbank_fused_kernel(FbankTables 
                 jj = jj >= L ? 2 * (L - 1) - jj : jj;
                 jj = max(0, min(jj, L - 1));
             }
-            const bool in = i < ns_pad && !(tb.ff_abl & 1);
+            const bool in = i < ns_pad;
             v[u] = in ? x[in ? jj : 0] : 0.0f;
             prev[u] = (in && coef >= 0.0f) ? x[jj == 0 ? 1 : jj - 1] : 0.0f;   // F.pad(reflect,(1,0)): x[-1] := x[1]
         }
@@ -481,7 +481,7 @@ __global__ __launch_bounds__(FF_THREADS, 4) void fbank_fused_kernel(FbankTables 
 
     // ---- 2. the symmetric operand: e | o of every frame, bf16 hi | lo ---------------------------------------------------------------
     const int half = tb.win_length >> 1;                           // 100: the tap the window is symmetric about
-    for (int wk = tid; wk < ((tb.ff_abl & 2) ? 0 : FF_FRAMES * (FF_K / 8)); wk += FF_THREADS) {
+    for (int wk = tid; wk < FF_FRAMES * (FF_K / 8); wk += FF_THREADS) {
         const int i = wk / (FF_K / 8), j = wk - i * (FF_K / 8);
         const int c = i * tb.hop + half;
         const f32x4 fa = *reinterpret_cast<const f32x4*>(ys + c + 8 * j), fb = *reinterpret_cast<const f32x4*>(ys + c + 8 * j + 4);
@@ -527,7 +527,6 @@ __global__ __launch_bounds__(FF_THREADS, 4) void fbank_fused_kernel(FbankTables 
         bf16x8 nh0 = bh[0], nh1 = bh[64], nl0 = bl[0], nl1 = bl[64];
 #pragma unroll
         for (int kk = 0; kk < FF_KSTEPS; ++kk) {
-            if (tb.ff_abl & 4) break;
             const bf16x8 ch = nh0, sh = nh1, cl = nl0, sl = nl1;
             const int kn = min(kk + 1, FF_KSTEPS - 1) * kstride;
             nh0 = bh[kn]; nh1 = bh[kn + 64]; nl0 = bl[kn]; nl1 = bl[kn + 64];
@@ -574,7 +573,7 @@ __global__ __launch_bounds__(FF_THREADS, 4) void fbank_fused_kernel(FbankTables 
 #pragma unroll
         for (int j = 0; j < FF_MAXOUT; ++j) {
             const int idx = tid + j * FF_THREADS;
-            if (idx >= 32 * tb.n_mels || (tb.ff_abl & 8)) break;
+            if (idx >= 32 * tb.n_mels) break;
             const int i = idx & 31, m = idx >> 5;
             const int st = mst[m], ln = mln[m];
             const float* w = melw + mof[m];
@@ -595,7 +594,7 @@ __global__ __launch_bounds__(FF_THREADS, 4) void fbank_fused_kernel(FbankTables 
         __syncthreads();
         for (int idx = tid; idx < 32 * tb.n_mels; idx += FF_THREADS) {
             const int f = idx / tb.n_mels, m = idx - f * tb.n_mels;
-            if (fbase + f < T && !(tb.ff_abl & 16)) logmel[((int64_t)b * T + fbase + f) * tb.n_mels + m] = lm[f * lms + m];
+            if (fbase + f < T) logmel[((int64_t)b * T + fbase + f) * tb.n_mels + m] = lm[f * lms + m];
         }
     }
     if ((tid & 31) == 0) {
@@ -771,9 +770,8 @@ hipError_t launch_fbank_fused(const FbankTables& tb, const float* wav, int B, in
     if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(fbank_fused_kernel), 80 * 1024)) return e;
     const int ntiles = (T + FF_FRAMES - 1) / FF_FRAMES;
     hipLaunchKernelGGL(fbank_fused_kernel, dim3(ntiles, B), dim3(FF_THREADS), lds, stream, tb, wav, L, T, log_input, logmel, partial);
-    if (!(tb.ff_abl & 32))
-        hipLaunchKernelGGL(fbank_norm_kernel<bf16_t>, dim3((T + 63) / 64, B), dim3(256), 0, stream, logmel, partial, reinterpret_cast<bf16_t*>(out), T,
-                           tb.n_mels, ntiles, log_input);
+    hipLaunchKernelGGL(fbank_norm_kernel<bf16_t>, dim3((T + 63) / 64, B), dim3(256), 0, stream, logmel, partial, reinterpret_cast<bf16_t*>(out), T,
+                       tb.n_mels, ntiles, log_input);
     return hipGetLastError();
 }
 

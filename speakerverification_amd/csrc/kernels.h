@@ -90,7 +90,6 @@ struct GemmParams {
                                     // many workgroups, so that a small test problem walks several tiles per workgroup; 0: persistent kernels off
     const float* in_scale = nullptr; // gemm_pw3's X3 conv-gather form: (device) [0] = s, [1] = 1 / (s sw), [2] = s sw — A holds s * x, W holds sw * w (launch_in_scale):
                                     // the accumulators start at s sw * bias and the epilogue multiplies by 1 / (s sw) before the activation
-    int pw4 = 0;                    // option pw4: plain pointwise bf16 layers with more tiles than workgroups run on the four-wave kernel (gemm_pw4.hip)
     int tail_split = 1;             // persistent 16-bit GEMMs: a last partial round of <= G / 2 tiles is walked as column halves (gemm_pw3.hip)
     void* ts = nullptr;             // developer builds (SVHIP_GEMM_DEBUG, debug bit 16384): per-workgroup stage timestamps
     int M = 0, N = 0, K = 0, Kp = 0;
@@ -140,9 +139,6 @@ hipError_t launch_gemm_pw2(const GemmParams& p, hipStream_t stream);
 bool gemm_pw3_supported(const GemmParams& p, bool bf16);
 hipError_t launch_gemm_pw3(const GemmParams& p, hipStream_t stream);
 int pw3_grid_cap(const GemmParams& p);
-// round 6: the same contract on four waves with 128 x 128 wave tiles (gemm_pw4.hip)
-bool gemm_pw4_supported(const GemmParams& p, bool bf16);
-hipError_t launch_gemm_pw4(const GemmParams& p, hipStream_t stream);
 // the X3 form of the persistent kernel (x3 == 2): A (M, K) and W (N, K) in the S32 split layout (per row, per 32 k: 32 hi bf16 |
 // 32 lo bf16), fp32 output, exact GELU + BN affine, optional column sums: the GELU layers of SVHIP_F32X3 handles
 bool gemm_pw3x3_supported(const GemmParams& p);
@@ -216,8 +212,6 @@ struct FbankTables {           // device pointers, built once per handle
     int n_q = 25;                      // win_length / 8
     int mel_max_bin = 256;             // highest bin with a non-zero mel weight
     int force32 = 0;                   // developer option fbank32: the 32-frame kernel whatever the bank
-    int ff_abl = 0;                    // developer option ff_abl (tools only; results are then wrong): fused front-end phases skipped: 1 sample loads,
-                                       // 2 operand build, 4 MFMAs, 8 mel / log, 16 row stores, 32 the normalisation launch
     float preemph = 0.97f;
 };
 // wav (B, L) fp32 -> mel power (B, n_mels, T) fp32
@@ -411,13 +405,13 @@ struct AsnormFusedParams {
                                     // normal quantile did not fit (round 6)
     float* cand = nullptr;          // (N, 2, ASNORM_CAND_PER_LANE) candidate scores
     int32_t* cnt = nullptr;         // (N, 2) scores above the threshold seen by each of the two lanes (may exceed the list size)
-    const void* planes = nullptr;   // optional: [nplanes][D + 32 + K][D] 16-bit parts of [MB ; cohort] (launch_asnorm_planes): the split forms
-    int nplanes = 2;                // 2: half hi | lo, three fp16 MFMAs per product block (default); 3: bf16 h | m | l, six bf16 MFMAs
+    const void* planes = nullptr;   // optional: [2][D + 32 + K][D] half hi | lo parts of [MB ; cohort] (launch_asnorm_planes): the split form,
+                                    // three fp16 MFMAs per product block
+    int nlists = 2;                 // candidate lists per embedding: 2 (cnt (N, 2), lists of ASNORM_CAND_PER_LANE), or 4 with planes: the
+                                    // 16-wide-MFMA kernel (cnt (N, 4), lists of ASNORM_CAND_PER_LANE / 2)
     float* rowscale = nullptr;      // the 16-wide half-plane kernel with pscale: (N) factor that takes a row's candidates (stored in the scaled
                                     // domain) back to scores: asnorm_cand_stats multiplies mu and sigma by it
     const uint32_t* pscale = nullptr;   // the 16-wide half-plane kernel: max-|x| word of the cohort the planes were scaled by (launch_asnorm_planes)
-    int nlists = 2;                 // candidate lists per embedding: 2 (cnt (N, 2), lists of ASNORM_CAND_PER_LANE), or 4 with nplanes = 2: the
-                                    // 16-wide-MFMA kernel (cnt (N, 4), lists of ASNORM_CAND_PER_LANE / 2)
 };
 // dense score matrix on half planes / 16x16x32 fp16 MFMAs (asnorm_fused.hip): out (Na, ldo) = A (Na, D) . B (Nb, D)^T, D = 192 / 256
 struct ScoreH3Params {
@@ -434,10 +428,9 @@ bool score_h3w_supported(int D, int64_t Na, int64_t Nb);
 size_t score_h3w_planes_bytes(int D, int64_t Nb);
 hipError_t launch_score_h3w(const float* A, int64_t Na, const float* B, int64_t Nb, int D, float* out, int64_t ldo, void* planes, int num_cu,
                             hipStream_t stream);
-bool asnorm_fused6_supported(int D, int planes);
 size_t asnorm_planes_bytes(int D, int K);
-// pscale (two half planes only): a device word that receives the cohort's max |x|; the planes are then scaled by an exact power of two
-hipError_t launch_asnorm_planes(const float* MB, const float* cohort, int K, int D, void* planes, hipStream_t stream, int nplanes = 2, uint32_t* pscale = nullptr);
+// pscale: a device word that receives the cohort's max |x|; the planes are then scaled by an exact power of two
+hipError_t launch_asnorm_planes(const float* MB, const float* cohort, int K, int D, void* planes, hipStream_t stream, uint32_t* pscale = nullptr);
 bool asnorm_fused_supported(int D, int K, int top);
 float asnorm_tail_z(int K, int top);
 // `part`: cohort_moments_scratch_bytes(D) of scratch (slice partials, summed in a fixed order)

@@ -382,15 +382,12 @@ __global__ __launch_bounds__(256, 2) void rn_sinc_kernel(const float* __restrict
         f32x16 acc[BF ? 1 : 2][BF ? 1 : 3];           // fp32 path: [position group][pool partner]
         // 16-bit path: the wave's 32 pooled frames are two groups of 16, multiplied and finished ONE AFTER THE OTHER (12 accumulators of
         // 16 x 16 live at a time: with all 24 the kernel needs 270 registers and spills its filter fragments into the tile loop)
-        const char* base[3] = {nullptr, nullptr, nullptr};
-        const char* bback[3] = {nullptr, nullptr, nullptr};       // SYM: the backward windows (descending with the k step)
+        const char* base[3] = {nullptr, nullptr, nullptr};       // 16-bit path without SYM: the window of each pool partner (SYM: formed in the tile body below)
         if (BF) {
+            if (!SYM) {
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int s = 3 * ((SYM ? 16 * wave : 32 * gw) + r16) + j;       // conv position inside the tile (frame group 0; group 1: + 48)
-                if (SYM) {
-                    // (slot k': forward sample s + 123 + k', backward sample s + 127 - k': formed per pool partner in the tile body below)
-                } else {
+                for (int j = 0; j < 3; ++j) {
+                    const int s = 3 * (32 * gw + r16) + j;       // conv position inside the tile (frame group 0; group 1: + 48)
                     base[j] = xbuf + (s & 7) * CF::COPY_BYTES + (((CF::COPY_SKEW >> (4 * (s & 7))) & 15) + (s >> 3) + q4) * 16;
                 }
             }
@@ -498,23 +495,14 @@ __global__ __launch_bounds__(256, 2) void rn_sinc_kernel(const float* __restrict
                 // 24 fragment reads are issued two ahead of their MFMAs through a ring of three, fenced (the compiler otherwise hoists them
                 // in bulk); frame group 1 starts 48 conv positions = 6 chunks of the SAME copy further on (+ 96 bytes)
                 auto xread = [&](int idx) { return *reinterpret_cast<const bf16x8*>(base[idx % 3] + g * 96 + (idx / 3) * 64); };
-                auto bread = [&](int idx) { return *reinterpret_cast<const bf16x8*>(bback[idx % 3] + g * 96 - (idx / 3) * 64); };
-                bf16x8 ring[3], rback[SYM ? 3 : 1];
+                bf16x8 ring[3];
                 ring[0] = xread(0);
                 ring[1] = xread(1);
-                if (SYM) { rback[0] = bread(0); rback[1] = bread(1); }
 #pragma unroll
                 for (int idx = 0; idx < 3 * NKS; ++idx) {
-                    if (idx + 2 < 3 * NKS) {
-                        ring[(idx + 2) % 3] = xread(idx + 2);
-                        if (SYM) rback[(idx + 2) % 3] = bread(idx + 2);
-                    }
+                    if (idx + 2 < 3 * NKS) ring[(idx + 2) % 3] = xread(idx + 2);
                     __builtin_amdgcn_sched_barrier(0);
-                    bf16x8 xf = ring[idx % 3];
-                    if (SYM) {          // e[u] = forward[u] + backward[7 - u]
-                        const f16x8 fw = __builtin_bit_cast(f16x8, ring[idx % 3]), bk = __builtin_bit_cast(f16x8, rback[idx % 3]);
-                        xf = __builtin_bit_cast(bf16x8, fw + __builtin_shufflevector(bk, bk, 7, 6, 5, 4, 3, 2, 1, 0));
-                    }
+                    const bf16x8 xf = ring[idx % 3];
 #pragma unroll
                     for (int fb = 0; fb < 4; ++fb) acc16[fb][idx % 3] = Half16<H>::mfma16(wfb[fb][idx / 3], xf, acc16[fb][idx % 3]);
                     __builtin_amdgcn_sched_barrier(0);

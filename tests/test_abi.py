@@ -21,6 +21,27 @@ def test_header_and_binding_agree():
     assert header_symbols() == _lib.exported_symbols()
 
 
+def header_option_names():
+    text = open(os.path.join(ROOT, "include", "svhip.h")).read()
+    start = text.index("Developer / test options")
+    names = text[text.index("Names:", start):text.index("Unknown names", start)]
+    return sorted(set(re.findall(r'"([a-z0-9_]+)"', names)))
+
+
+def table_option_names():
+    text = open(os.path.join(ROOT, "speakerverification_amd", "csrc", "api.hip")).read()
+    table = text[text.index("const DevOptRow kDevOpts[] = {"):]
+    table = table[:table.index("};")]
+    return sorted(set(re.findall(r"SV_OPT\((\w+),", table)))
+
+
+def test_header_lists_exactly_the_options_set_option_accepts():
+    """svhip_set_option and svhip_create walk ONE table (kDevOpts, csrc/api.hip); the name list of svhip.h must be that table."""
+    table = table_option_names()
+    assert len(table) >= 20
+    assert header_option_names() == table
+
+
 def test_library_exports_every_declared_symbol():
     lib = _lib.load()
     for name in header_symbols():

@@ -437,11 +437,11 @@ def test_pnorm_similarity_for_any_p_matches_the_reference(eng, golden_dir):
         eng.score_trials(F, ia, ib, "pnorm", p=float("nan"))
 
 
-def test_asnorm_six_bf16_mfma_form_agrees_with_the_fp32_mfma_form(monkeypatch):
-    """D = 192 runs the fused AS-norm kernel on SIX bf16 MFMAs per product block (every fp32 value split exactly into three bf16
-    parts; the three smallest of the nine partial products, <= 2^-26 relative, dropped): scores to fp32 rounding.  Against the
-    exact-fp32-MFMA form of the same kernel (option asnorm_f32mfma) and against the float64 oracle, on a cohort with ties and a
-    ragged last block; same bars as the fp32 form."""
+def test_asnorm_half_plane_form_agrees_with_the_fp32_mfma_form(monkeypatch):
+    """D = 192 runs the fused AS-norm kernel on the default split form ("h3"): every fp32 value split into two IEEE-half planes,
+    hi.hi + hi.lo + lo.hi on three fp16 MFMAs per product block (v_mfma_f32_16x16x32_f16, four candidate lists per embedding):
+    scores to fp32 rounding.  Against the exact-fp32-MFMA form of the same kernel (option asnorm_f32mfma) and against the float64
+    oracle, on a cohort with ties and a ragged last block; same bars as the fp32 form."""
     eng = Engine(model="none", max_batch=1)
     rng = np.random.Generator(np.random.PCG64(606))
     N, D, K, top = 1333, 192, 5994, 200
@@ -450,34 +450,16 @@ def test_asnorm_six_bf16_mfma_form_agrees_with_the_fp32_mfma_form(monkeypatch):
     cohort = rng.standard_normal((K, D)).astype(np.float32)
     cohort /= np.linalg.norm(cohort, axis=1, keepdims=True)
     cohort[7] = cohort[9]
-    # round 4: the default split form is TWO half planes / three fp16 MFMAs ("h3"); option asnorm_x6 selects round 3's three bf16 planes
     mu3, sd3 = eng.asnorm_stats(E, cohort, top)
-    assert eng.asnorm_last_fallback == 0
-    eng.set_option("asnorm_x6", 1)
-    mu6, sd6 = eng.asnorm_stats(E, cohort, top)
-    eng.set_option("asnorm_x6", 0)
     assert eng.asnorm_last_fallback == 0
     eng.set_option("asnorm_f32mfma", 1)
     mu1, sd1 = eng.asnorm_stats(E, cohort, top)
     eng.set_option("asnorm_f32mfma", 0)
     assert eng.asnorm_last_fallback == 0
     rmu, rsd = o_scoring.asnorm_stats(E, cohort, top)
-    print("x6 vs f64 oracle: mu", float(np.abs(mu6 - rmu).max()), "sd rel", float((np.abs(sd6 - rsd) / rsd).max()),
-          "| fp32 MFMA vs oracle: mu", float(np.abs(mu1 - rmu).max()), "| x6 vs fp32 MFMA: mu", float(np.abs(mu6 - mu1).max()))
-    assert float(np.abs(mu6 - rmu).max()) <= 1e-6 and float(np.abs(mu1 - rmu).max()) <= 1e-6
-    assert float((np.abs(sd6 - rsd) / rsd).max()) <= 1e-4
-    assert float(np.abs(mu6 - mu1).max()) <= 5e-7 and float(np.abs(sd6 - sd1).max()) <= 5e-7
     print("h3 (two half planes, three fp16 MFMAs) vs f64 oracle: mu", float(np.abs(mu3 - rmu).max()), "sd rel", float((np.abs(sd3 - rsd) / rsd).max()),
-          "| h3 vs fp32 MFMA: mu", float(np.abs(mu3 - mu1).max()))
+          "| fp32 MFMA vs oracle: mu", float(np.abs(mu1 - rmu).max()), "| h3 vs fp32 MFMA: mu", float(np.abs(mu3 - mu1).max()))
+    assert float(np.abs(mu1 - rmu).max()) <= 1e-6
     assert float(np.abs(mu3 - rmu).max()) <= 1e-6 and float((np.abs(sd3 - rsd) / rsd).max()) <= 1e-4
     assert float(np.abs(mu3 - mu1).max()) <= 5e-7 and float(np.abs(sd3 - sd1).max()) <= 5e-7
-    # round 4 (late): the default runs on v_mfma_f32_16x16x32_f16 (four candidate lists per embedding); option asnorm_w32 keeps the 32-wide
-    # form (two lists).  Same three products per block in the same order within a k step; the k steps are 32 wide instead of 16
-    eng.set_option("asnorm_w32", 1)
-    muw, sdw = eng.asnorm_stats(E, cohort, top)
-    eng.set_option("asnorm_w32", 0)
-    assert eng.asnorm_last_fallback == 0
-    print("16-wide vs 32-wide half-plane kernel: mu", float(np.abs(mu3 - muw).max()), "sd", float(np.abs(sd3 - sdw).max()))
-    assert float(np.abs(mu3 - muw).max()) <= 2e-7 and float(np.abs(sd3 - sdw).max()) <= 2e-7
-    assert float(np.abs(muw - rmu).max()) <= 1e-6
     eng.close()

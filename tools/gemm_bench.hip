@@ -167,14 +167,11 @@ int main(int argc, char** argv) {
             p.cv_off = (debug & 32768) ? 1 : 0;            // 32768: conv-gather shapes on the per-tile kernel
             p.tail_split = (debug & 65536) ? 0 : 1;        // 65536: the persistent kernel's last partial round as whole tiles (round 4)
             if (debug & 128) { p.colsum = csum; p.colsum_sq = (debug & 256) ? 1 : 0; p.colsum_stride = csr; } else { p.colsum = nullptr; }
-            const bool pw4 = (debug & (1 << 21)) && bf16 && gemm_pw4_supported(p, bf16) && gemm_route(p, bf16) == ROUTE_PW3;      // 2097152: the four-wave kernel
-            auto launch = [&]() { return pw4 ? launch_gemm_pw4(p, st) : launch_gemm(p, bf16, st); };
-            if ((debug & (1 << 21)) && !pw4) continue;
-            for (int i = 0; i < 2; ++i) CK(launch());
+            for (int i = 0; i < 2; ++i) CK(launch_gemm(p, bf16, st));
             CK(hipStreamSynchronize(st));
             const int it = 10;
             CK(hipEventRecord(e0, st));
-            for (int i = 0; i < it; ++i) CK(launch());
+            for (int i = 0; i < it; ++i) CK(launch_gemm(p, bf16, st));
             CK(hipEventRecord(e1, st));
             CK(hipEventSynchronize(e1));
             float ms; CK(hipEventElapsedTime(&ms, e0, e1)); ms /= it;
@@ -187,7 +184,7 @@ int main(int argc, char** argv) {
                 CK(hipMemcpyAsync(hcs, dcs, 16, hipMemcpyDeviceToHost, st)); CK(hipStreamSynchronize(st));
             }
             printf("%-36s dbg %5d %8.3f ms  %8.1f TFLOP/s  cs %.6e %.6e  [%s]\n", s.name, debug, ms, 2.0 * s.M * s.N * s.K / ms / 1e9, hcs[0], hcs[1],
-                   pw4 ? "pw4" : gemm_route(p, bf16) == ROUTE_PW3 ? "pw3" : gemm_route(p, bf16) == ROUTE_PW3CV ? "pw3cv16" : gemm_route(p, bf16) == ROUTE_PW2 ? "pw2" : "other");
+                   gemm_route(p, bf16) == ROUTE_PW3 ? "pw3" : gemm_route(p, bf16) == ROUTE_PW3CV ? "pw3cv16" : gemm_route(p, bf16) == ROUTE_PW2 ? "pw2" : "other");
             if ((debug & 128) && p.colsum && gemm_pw2_supported(p, bf16)) {
                 // per-utterance column sums from the partials (the arithmetic of colsum_finalize_kernel), as an order-sensitive checksum:
                 // the 8-row-group layout of pw2 and the 2-row-group layout of pw3 must agree to bf16 rounding of the summed values
