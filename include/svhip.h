@@ -47,7 +47,12 @@ typedef enum svhip_status {
                                    embeddings come out non-finite */
 } svhip_status;
 
-enum { SVHIP_MODEL_ECAPA = 0, SVHIP_MODEL_RAWNET2 = 1, SVHIP_MODEL_NONE = 2 /* fbank + scoring only */ };
+/* SVHIP_MODEL_RAWNET2: front_proc='sinc' (LayerNorm + sinc filters + first_bn; L fixed by the LayerNorm, >= 2438 samples).
+ * SVHIP_MODEL_RAWNET2_CONV (added under ABI v5): front_proc='conv' — conv1 = Conv1d(1, 128, 3, stride=3) with bias straight on the
+ * waveform (RawNet2_custom.py:45-52,166-169), the same residual stack and aggregate='asp', att_dim=128 behind it; any L >= 2187
+ * (floor(L / 3) frames pass six max_pool1d(3) stages), one handle per L like every model.  Weights: conv1.* instead of ln.*,
+ * first_conv.* and first_bn.* (140 tensors). */
+enum { SVHIP_MODEL_ECAPA = 0, SVHIP_MODEL_RAWNET2 = 1, SVHIP_MODEL_NONE = 2 /* fbank + scoring only */, SVHIP_MODEL_RAWNET2_CONV = 3 };
 enum { SVHIP_F32 = 0, SVHIP_BF16 = 1, SVHIP_I64 = 2, SVHIP_F32X3 = 3 /* compute only */, SVHIP_F16 = 4 /* compute only */ };
 enum { SVHIP_IN_DEVICE = 1, SVHIP_OUT_DEVICE = 2, SVHIP_ASYNC = 4 };
 
@@ -63,7 +68,9 @@ typedef struct svhip_config {
                                call (SVHIP_ERR_RANGE), the embeddings are checked for inf / NaN on every call (SVHIP_ERR_NONFINITE);
                                SVHIP_F16 (RawNet2 handles only): fp16 storage + fp16 MFMA, fp32 accumulate — the same speed as bf16 with
                                three more mantissa bits (RawNet2's un-normalised residual stack loses two digits to bf16 WEIGHT rounding);
-                               an fp16 value overflows at 65504: the input is LayerNorm'ed, so only the weights decide the activation scale */
+                               an fp16 value overflows at 65504: on SVHIP_MODEL_RAWNET2 the input is LayerNorm'ed, so only the weights decide
+                               the activation scale; on SVHIP_MODEL_RAWNET2_CONV the input is NOT LayerNorm'ed, so the waveform's scale and the
+                               weights both decide whether an fp16 activation overflows (reported as SVHIP_ERR_NONFINITE like any other) */
     int32_t device;         /* HIP device ordinal */
     int32_t channels;       /* ECAPA C (channels = [C,C,C,C,3C], ECAPA_TDNN.py:378) */
     int32_t n_mels;         /* 80 */
@@ -275,7 +282,7 @@ double svhip_workload_flops(const svhip_handle* h);
  * svhip_create, as a new handle's defaults; afterwards only this call changes them — no getenv on the hot path.  Names:
  * "pw3_cus" (cap of the persistent GEMM grids; 0: off), "rn_unfused", "rn_stop", "rn_snap", "asp_v1", "r2_big", "x3_keep_f32",
  * "asnorm_slab", "asnorm_f32mfma", "asnorm_norefit", "score_f32mfma", "score_tiled", "fbank32", "fbank_unfused", "rn_sinc_full", "cv_off",
- * "pw3_tail_off", "n128_off", "r2_slices", "rn_tail_big", "rn_sinc_f32", "rn_step_off", "rn_pool_off", "layer_labels".
+ * "pw3_tail_off", "n128_off", "r2_slices", "rn_tail_big", "rn_sinc_f32", "rn_step_off", "rn_pool_off", "layer_labels", "rn_conv_unfused".
  * Unknown names: SVHIP_ERR_INVALID. */
 int svhip_set_option(svhip_handle* h, const char* name, int32_t value);
 /* Free the scoring / metrics scratch slots of the handle (grown on demand, otherwise kept until svhip_destroy). */

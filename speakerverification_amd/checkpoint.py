@@ -23,7 +23,7 @@ from . import _lib
 
 MAGIC = b"SVHIPWB1"
 _MODEL_IDS = {"ECAPA_TDNN": _lib.MODEL_ECAPA, "ecapa": _lib.MODEL_ECAPA, "RawNet2_custom": _lib.MODEL_RAWNET2,
-              "rawnet2": _lib.MODEL_RAWNET2}
+              "rawnet2": _lib.MODEL_RAWNET2, "RawNet2_custom_conv": _lib.MODEL_RAWNET2_CONV, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV}
 
 
 def model_id(model) -> int:
@@ -132,7 +132,13 @@ def read_blob(path):
         lib.svhip_blob_close(b)
 
 
-FUSION_MODELS = {"Raw_ECAPA_sinc_asp": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom", ".rawnet2"))}
+# fusion model -> its branches: (state-dict prefix, blob model, blob suffix).  The RawNet2 blob's model id records the front-end
+# (SVHIP_MODEL_RAWNET2: 'sinc', SVHIP_MODEL_RAWNET2_CONV: 'conv'), so a pair cannot be loaded into the other model's module.
+FUSION_MODELS = {
+    "Raw_ECAPA_sinc_asp": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom", ".rawnet2")),
+    "Raw_ECAPA": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom", ".rawnet2")),
+    "Raw_ECAPA_conv_asp": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom_conv", ".rawnet2")),
+}
 
 
 def fusion_blob_paths(dst, model="Raw_ECAPA_sinc_asp"):
@@ -143,8 +149,8 @@ def fusion_blob_paths(dst, model="Raw_ECAPA_sinc_asp"):
 def convert_checkpoint(src, dst, model) -> int:
     """Reference checkpoint file (torch pickle) or state dict -> blob at ``dst``.  Returns the number of tensors written.
 
-    A fusion checkpoint (``model='Raw_ECAPA_sinc_asp'``: keys ``__S__.ECAPA_TDNN.*`` / ``__S__.rawnet2v2.*``,
-    Raw_ECAPA_sinc_asp.py:22-28) becomes one blob per branch, ``dst + '.ecapa'`` and ``dst + '.rawnet2'`` — a handle is one
+    A fusion checkpoint (``model`` one of FUSION_MODELS — ``Raw_ECAPA_sinc_asp``, ``Raw_ECAPA``, ``Raw_ECAPA_conv_asp``: keys
+    ``__S__.ECAPA_TDNN.*`` / ``__S__.rawnet2v2.*``, Raw_ECAPA*.py:22-28) becomes one blob per branch, ``dst + '.ecapa'`` and ``dst + '.rawnet2'`` — a handle is one
     network, and ``Raw_ECAPA.load_blob(dst)`` reads the pair back."""
     if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
         import torch  # host-side only: the one place a pickle is read
@@ -155,6 +161,11 @@ def convert_checkpoint(src, dst, model) -> int:
         state = src
     sd = embedding_state_dict(state)
     if model in FUSION_MODELS:
+        front = "conv" if FUSION_MODELS[model][1][1] == "RawNet2_custom_conv" else "sinc"
+        if front == "conv" and any(k.startswith("rawnet2v2.first_conv.") for k in sd):
+            raise ValueError(f"{model}: the checkpoint's RawNet2 branch has a sinc front-end (rawnet2v2.first_conv.*)")
+        if front == "sinc" and any(k.startswith("rawnet2v2.conv1.") for k in sd):
+            raise ValueError(f"{model}: the checkpoint's RawNet2 branch has a conv front-end (rawnet2v2.conv1.*)")
         total = 0
         for prefix, branch, suffix in FUSION_MODELS[model]:
             sub = OrderedDict((k[len(prefix):], v) for k, v in sd.items() if k.startswith(prefix))
@@ -165,7 +176,7 @@ def convert_checkpoint(src, dst, model) -> int:
         return total
     if any(k.startswith(("ECAPA_TDNN.", "rawnet2v2.")) for k in sd):
         raise ValueError("this is a fusion checkpoint (ECAPA_TDNN.* / rawnet2v2.* keys): convert it with "
-                         "model='Raw_ECAPA_sinc_asp' (one blob per branch)")
+                         f"model= one of {sorted(FUSION_MODELS)} (one blob per branch)")
     write_blob(dst, model, sd)
     return len(sd)
 
@@ -174,7 +185,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("src")
     ap.add_argument("dst")
-    ap.add_argument("--model", default="ECAPA_TDNN", help="reference model name (ECAPA_TDNN, RawNet2_custom, Raw_ECAPA_sinc_asp)")
+    ap.add_argument("--model", default="ECAPA_TDNN", help="reference model name (ECAPA_TDNN, RawNet2_custom, RawNet2_custom_conv, Raw_ECAPA_sinc_asp, Raw_ECAPA, "
+                    "Raw_ECAPA_conv_asp)")
     a = ap.parse_args(argv)
     n = convert_checkpoint(a.src, a.dst, a.model)
     print(f"{a.dst}: {n} tensors")

@@ -87,6 +87,7 @@ struct svhip_handle {
         int rn_sinc_f32;          // F32X3 handles: the sinc front-end on the exact fp32 MFMA (tests) instead of three fp16 MFMAs per product
         int rn_tail_big;          // RawNet2 block tail: one workgroup per utterance at every batch size (tests)
         int r2_slices;            // bf16 Res2Net chain: time slices per utterance (-1: by batch size, 0 / 1: whole utterances, n: forced)
+        int rn_conv_unfused;      // 16-bit RawNet2 'conv' handles: rn_conv3_front + plain rn_block128 instead of block 0 reading the waveform (tests, A/B)
     } opt;
     bool bf16 = false;                        // 16-bit storage handle: bf16, or fp16 when `f16` is set (the flag keeps its round-1 name)
     bool f16 = false;                         // SVHIP_F16: the 16-bit type is IEEE half (RawNet2)
@@ -112,7 +113,7 @@ struct svhip_handle {
     float *aspbn_scale = nullptr, *aspbn_shift = nullptr;
     float *in_w = nullptr, *in_b = nullptr;   // instance norm affine
 
-    // RawNet2 layers (front_proc='sinc', aggregate='asp'; RawNet2_custom.py:230-243)
+    // RawNet2 layers (front_proc='sinc' or 'conv', aggregate='asp'; RawNet2_custom.py:230-243)
     struct RnBlock {
         int cin = 0, cout = 0;
         bool downsample = false, has_shortcut = false;
@@ -128,6 +129,7 @@ struct svhip_handle {
     void* rn_filt = nullptr;
     void* rn_filt_sym = nullptr;              // fp16 handles: [128][128] slot-major table of the symmetric sinc form (round 6)
     void* rn_filt_x3 = nullptr;               // F32X3 handles: [2][128][256] half hi | lo parts of the sinc filters
+    float* rn_cw = nullptr;                   // 'conv' front-end (SVHIP_MODEL_RAWNET2_CONV): [w0 | w1 | w2 | bias] x 128 floats of conv1
     float *rn_agg_scale = nullptr, *rn_agg_shift = nullptr;
     ConvLayer rn_att0, rn_att3;
     LinearLayer rn_fc;
@@ -249,6 +251,7 @@ const DevOptRow kDevOpts[] = {
     SV_OPT(rn_sinc_f32, "SVHIP_RN_SINC_F32", OPT_IS1, 0),
     SV_OPT(rn_tail_big, "SVHIP_RN_TAIL_BIG", OPT_IS1, 0),
     SV_OPT(r2_slices, "SVHIP_R2_SLICES", OPT_NUM, -1),
+    SV_OPT(rn_conv_unfused, "SVHIP_RN_CONV_UNFUSED", OPT_IS1, 0),
 };
 #undef SV_OPT
 
@@ -549,6 +552,10 @@ void ecapa_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t
 }
 
 const int RN_LAYERS[6] = {1, 1, 1, 2, 1, 2};                   // RawNet2_custom.py:231
+
+inline bool is_rawnet2(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_CONV; }
+// RawNet2 needs six max_pool1d(3) stages behind the front-end to leave at least one frame: 3^6 front-end frames
+constexpr int RN_MIN_FRAMES = 3 * 3 * 3 * 3 * 3 * 3;
 const int RN_FILTERS[6] = {128, 128, 256, 256, 512, 512};      // RawNet2_custom.py:232
 
 void rawnet2_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec) {
@@ -556,9 +563,13 @@ void rawnet2_spec(const svhip_config& c, std::map<std::string, std::vector<int64
         spec[p + ".weight"] = {n}; spec[p + ".bias"] = {n}; spec[p + ".running_mean"] = {n};
         spec[p + ".running_var"] = {n}; spec[p + ".num_batches_tracked"] = {};
     };
-    spec["ln.gamma"] = {(int64_t)c.samples}; spec["ln.beta"] = {(int64_t)c.samples};
-    spec["first_conv.low_hz_"] = {128, 1}; spec["first_conv.band_hz_"] = {128, 1};
-    bn("first_bn", 128);
+    if (c.model == SVHIP_MODEL_RAWNET2_CONV) {          // conv1 = Conv1d(1, 128, 3, stride=3) with bias (RawNet2_custom.py:45-52)
+        spec["conv1.weight"] = {128, 1, 3}; spec["conv1.bias"] = {128};
+    } else {
+        spec["ln.gamma"] = {(int64_t)c.samples}; spec["ln.beta"] = {(int64_t)c.samples};
+        spec["first_conv.low_hz_"] = {128, 1}; spec["first_conv.band_hz_"] = {128, 1};
+        bn("first_bn", 128);
+    }
     int64_t inpl = 128;
     for (int li = 0; li < 6; ++li)
         for (int b = 0; b < RN_LAYERS[li]; ++b) {
@@ -582,7 +593,7 @@ void rawnet2_spec(const svhip_config& c, std::map<std::string, std::vector<int64
 
 void model_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec) {
     if (c.model == SVHIP_MODEL_ECAPA) ecapa_spec(c, spec);
-    else if (c.model == SVHIP_MODEL_RAWNET2) rawnet2_spec(c, spec);
+    else if (is_rawnet2(c.model)) rawnet2_spec(c, spec);
 }
 
 const HostTensor* getw(svhip_handle* h, const std::string& name) {
@@ -644,7 +655,7 @@ int make_conv(svhip_handle* h, ConvLayer& L, const std::string& wname, const std
             if ((taps == 1 && N % 256 == 0 && L.K == L.Kp && L.K % 64 == 0 && L.K >= 128) ||
                 (taps == 3 && N == cin && (cin == 64 || cin == 128) && L.K == L.Kp) ||
                 // RawNet2's convolutions and projection shortcuts (r2_step.hip, modes 1 / 2)
-                (h->cfg.model == SVHIP_MODEL_RAWNET2 && (taps == 1 || taps == 3) && N % 128 == 0 && cin % 32 == 0 && L.K == L.Kp && L.K == taps * cin)) {
+                (is_rawnet2(h->cfg.model) && (taps == 1 || taps == 3) && N % 128 == 0 && cin % 32 == 0 && L.K == L.Kp && L.K == taps * cin)) {
                 std::vector<uint16_t> s32((size_t)N * L.K * 2);
                 for (int n = 0; n < N; ++n)
                     for (int k = 0; k < L.K; ++k) {
@@ -857,15 +868,32 @@ int bake_sinc(svhip_handle* h) {
     return SVHIP_OK;
 }
 
+// the 'conv' front-end's constants: conv1.weight (128, 1, 3) and conv1.bias as [w0 | w1 | w2 | bias] x 128 floats
+int make_conv3_front(svhip_handle* h) {
+    const HostTensor *w = getw(h, "conv1.weight"), *b = getw(h, "conv1.bias");
+    if (!w || !b) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %s", !w ? "conv1.weight" : "conv1.bias");
+    std::vector<float> cw(4 * 128);
+    for (int c = 0; c < 128; ++c) {
+        for (int k = 0; k < 3; ++k) cw[k * 128 + c] = w->data[c * 3 + k];
+        cw[3 * 128 + c] = b->data[c];
+    }
+    return dev_upload(h, &h->rn_cw, cw);
+}
+
 int finalize_rawnet2(svhip_handle* h) {
     int rc;
-    if ((rc = upload_f32(h, "ln.gamma", &h->rn_gamma))) return rc;
-    if ((rc = upload_f32(h, "ln.beta", &h->rn_beta))) return rc;
-    if ((rc = bake_sinc(h))) return rc;
-    if ((rc = make_bn(h, "first_bn", 128, &h->rn_fbn_scale, &h->rn_fbn_shift))) return rc;
+    const bool conv = h->cfg.model == SVHIP_MODEL_RAWNET2_CONV;
+    if (conv) {
+        if ((rc = make_conv3_front(h))) return rc;
+    } else {
+        if ((rc = upload_f32(h, "ln.gamma", &h->rn_gamma))) return rc;
+        if ((rc = upload_f32(h, "ln.beta", &h->rn_beta))) return rc;
+        if ((rc = bake_sinc(h))) return rc;
+        if ((rc = make_bn(h, "first_bn", 128, &h->rn_fbn_scale, &h->rn_fbn_shift))) return rc;
+    }
     int inpl = 128, bi = 0;
     int T = h->rn_T1;
-    double fl = 2.0 * 128 * 251 * (double)(h->cfg.samples - 250);
+    double fl = conv ? 2.0 * 128 * 3 * (double)T : 2.0 * 128 * 251 * (double)(h->cfg.samples - 250);
     for (int li = 0; li < 6; ++li)
         for (int b = 0; b < RN_LAYERS[li]; ++b, ++bi) {
             svhip_handle::RnBlock& B = h->rn_blocks[bi];
@@ -939,8 +967,9 @@ int alloc_workspace(svhip_handle* h) {
     SV_HIP(h, hipHostMalloc((void**)&h->host_flag, 64, hipHostMallocMapped));
     *h->host_flag = 0;
     SV_HIP(h, hipHostGetDevicePointer((void**)&h->host_flag_dev, h->host_flag, 0));
-    if (c.model == SVHIP_MODEL_RAWNET2) {
-        h->rn_T1 = (c.samples - 250) / 3;
+    if (is_rawnet2(c.model)) {
+        const bool conv = c.model == SVHIP_MODEL_RAWNET2_CONV;
+        h->rn_T1 = conv ? (c.samples - 3) / 3 + 1 : (c.samples - 250) / 3;       // conv1 (kernel 3, stride 3) | sinc (251 taps) + max_pool1d(3)
         const size_t per_utt = (size_t)h->rn_T1 * 128;           // largest activation: (T1, 128); later stages shrink 3x per doubling
         h->rn_buf_bytes = B * per_utt * e;
         for (int i = 0; i < 6; ++i) {
@@ -949,8 +978,8 @@ int alloc_workspace(svhip_handle* h) {
             h->rn_buf[i] = q;
             SV_HIP(h, hipMemset(q + h->rn_buf_bytes, 0, 256));          // the zero tail (no kernel writes past the payload)
         }
-        if ((rc = dev_alloc(h, &h->rn_stats, B * 2))) return rc;
-        if (h->bf16 || h->x3) {                                  // LayerNorm output in 16 bits, zero-tailed rows (operand of the 16-bit / split sinc kernels)
+        if (!conv && (rc = dev_alloc(h, &h->rn_stats, B * 2))) return rc;
+        if (!conv && (h->bf16 || h->x3)) {                                  // LayerNorm output in 16 bits, zero-tailed rows (operand of the 16-bit / split sinc kernels)
             h->rn_Lp = (int)round_up(c.samples + RN_XN_TAIL, 64);
             uint16_t* q;
             if ((rc = dev_alloc(h, &q, (h->x3 ? 4 : 2) * B * (size_t)h->rn_Lp))) return rc;      // (F32X3: hi and lo parts of both copies)
@@ -1378,7 +1407,8 @@ int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0, int B)
     const int L = c.samples, e = h->esz;
     const size_t per_utt = (size_t)h->rn_T1 * 128;                 // elements of the largest activation of one utterance
     const float* d_wav = d_wav_all + (size_t)b0 * L;
-    float* rn_stats = h->rn_stats + (size_t)b0 * 2;
+    const bool conv = c.model == SVHIP_MODEL_RAWNET2_CONV;        // front_proc='conv': no LayerNorm, no sinc, no first_bn
+    float* rn_stats = conv ? nullptr : h->rn_stats + (size_t)b0 * 2;
     float* rn_mean = h->rn_mean + (size_t)b0 * 512;
     float* rn_scratch = h->rn_scratch + (size_t)b0 * 16 * 512;
     float* rn_part = h->rn_part + (size_t)b0 * (rn_block128_ntiles(h->rn_T1) + 1) * 4 * 128;
@@ -1386,10 +1416,10 @@ int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0, int B)
     float* rn_pooled = h->rn_pooled + (size_t)b0 * 1024;
     float* d_emb = h->d_emb + (size_t)b0 * c.embed_dim;
     int rc;
-    const bool sinc_x3 = h->x3 && h->rn_filt_x3 && !h->opt.rn_sinc_f32;            // F32X3: the front-end on three fp16 MFMAs per product
-    void* rn_xn = bf ? static_cast<char*>(h->rn_xn) + (size_t)b0 * 2 * h->rn_Lp * 2 : sinc_x3 ? static_cast<char*>(h->rn_xn) + (size_t)b0 * 4 * h->rn_Lp * 2 : nullptr;
+    const bool sinc_x3 = !conv && h->x3 && h->rn_filt_x3 && !h->opt.rn_sinc_f32;      // F32X3: the front-end on three fp16 MFMAs per product
+    void* rn_xn = conv ? nullptr : bf ? static_cast<char*>(h->rn_xn) + (size_t)b0 * 2 * h->rn_Lp * 2 : sinc_x3 ? static_cast<char*>(h->rn_xn) + (size_t)b0 * 4 * h->rn_Lp * 2 : nullptr;
     const int dt = h->dt;
-    if ((rc = run(h, "rn_ln_stats", 0, [&]() { return launch_rn_ln_stats(d_wav, B, L, rn_stats, st, rn_xn, h->rn_Lp, h->rn_gamma, h->rn_beta, dt, sinc_x3); }))) return rc;
+    if (!conv && (rc = run(h, "rn_ln_stats", 0, [&]() { return launch_rn_ln_stats(d_wav, B, L, rn_stats, st, rn_xn, h->rn_Lp, h->rn_gamma, h->rn_beta, dt, sinc_x3); }))) return rc;
     int T = h->rn_T1;
     void *x = off(h->rn_buf[0], b0 * per_utt, e), *pre = off(h->rn_buf[1], b0 * per_utt, e), *hb = off(h->rn_buf[2], b0 * per_utt, e),
          *o = off(h->rn_buf[3], b0 * per_utt, e), *sc = off(h->rn_buf[4], b0 * per_utt, e), *xn = off(h->rn_buf[5], b0 * per_utt, e);
@@ -1422,7 +1452,16 @@ int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0, int B)
     // (the split front-end writes block 0's pre-activation itself, in the S32 layout, when block 0 runs on the split convolution kernel)
     const bool sinc_pre = sinc_x3 && x3_step_block(0, T);
     if (sinc_pre) pre_is_s32 = true;
-    if ((rc = run(h, "rn_sinc", 2.0 * B * 128.0 * 251.0 * (L - 250), [&]() {
+    // bf16 / fp16 handles: the fused chain's first block computes the conv front-end itself from the waveform (rn_block128's CONV
+    // form) and x is never stored; option rn_conv_unfused stores x with rn_conv3_front and runs the plain block (bit-identical)
+    const bool fuse_ok = bf && stop_after < 0 && !h->opt.rn_unfused;
+    const svhip_handle::RnBlock& K0 = h->rn_blocks[0];
+    const bool conv_fused = conv && fuse_ok && !h->opt.rn_conv_unfused &&
+                            rn_block128_supported(K0.cin, K0.cout, T, K0.downsample, K0.has_shortcut, K0.conv1.Kp, K0.conv2.Kp);
+    if (conv) {
+        if (!conv_fused && (rc = run(h, "rn_conv3_front", 2.0 * B * 128.0 * 3.0 * T, [&]() { return launch_rn_conv3_front(d_wav, h->rn_cw, x, dt, B, L, T, st); })))
+            return rc;
+    } else if ((rc = run(h, "rn_sinc", 2.0 * B * 128.0 * 251.0 * (L - 250), [&]() {
              // (the kernel can also write block 0's pre-activation, but its 8-byte scattered stores make that as dear as the
              //  separate coalesced rn_bn_act pass: measured 0.85 + 0.29 ms either way)
              if (sinc_x3) return launch_rn_sinc_x3(h->rn_filt_x3, h->rn_fbn_scale, h->rn_fbn_shift, reinterpret_cast<float*>(x), B, L, T, rn_xn, h->rn_Lp, h->num_cu, st,
@@ -1437,7 +1476,6 @@ int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0, int B)
     // bf16: the 128 -> 128 pooled blocks (layer1, layer2) each run as ONE fused kernel + the AFMS gate kernel; the gate of
     // block i is applied by block i + 1 on the way in (or by the rn_afms_apply pass in front of the first GEMM block)
     int first = 0;
-    const bool fuse_ok = bf && stop_after < 0 && !h->opt.rn_unfused;
     const bool no_tail = h->opt.rn_unfused != 0;                        // (tests: the separate passes against the fused tail)
     const float *g_alpha = nullptr, *g_gate = nullptr;          // pending gate of the previous fused block
     const void* xin = x;
@@ -1454,8 +1492,10 @@ int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0, int B)
         bp.opool = reinterpret_cast<bf16_t*>(dst);
         bp.colsum = rn_part;
         bp.B = B; bp.T = T; bp.Tout = T / 3; bp.ntiles = rn_block128_ntiles(T); bp.f16 = h->f16 ? 1 : 0;
-        const double fl = (double)B * T * (K.conv1.flops_per_row + K.conv2.flops_per_row);
-        if ((rc = run(h, "rn_block128", fl, [&]() { return launch_rn_block128(bp, h->num_cu, st); }))) return rc;
+        const bool from_wave = first == 0 && conv_fused;
+        if (from_wave) { bp.xin = nullptr; bp.wav = d_wav; bp.cw = h->rn_cw; bp.L = L; }
+        const double fl = (double)B * T * (K.conv1.flops_per_row + K.conv2.flops_per_row + (from_wave ? 2.0 * 128 * 3 : 0.0));
+        if ((rc = run(h, from_wave ? "rn_block128_conv" : "rn_block128", fl, [&]() { return launch_rn_block128(bp, h->num_cu, st); }))) return rc;
         float* gate = rn_gate[first & 1];                        // two gate buffers: block i + 1 reads i's while writing its own
         if ((rc = run(h, "rn_afms_gate", 2.0 * B * K.cout * K.cout, [&]() {
                  return launch_rn_afms_gate(rn_part, rn_block128_nparts(B, bp.T, h->num_cu), B, K.cout, bp.Tout, K.afms_fcT, K.afms_fc.bias, gate, st);
@@ -1730,11 +1770,15 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) { g_create_error = std::string("no HIP device: ") + hipGetErrorString(e); return SVHIP_ERR_HIP; }
     if (cfg->device < 0 || cfg->device >= ndev) { g_create_error = "device ordinal out of range"; return SVHIP_ERR_INVALID; }
-    if (cfg->model != SVHIP_MODEL_ECAPA && cfg->model != SVHIP_MODEL_RAWNET2 && cfg->model != SVHIP_MODEL_NONE) { g_create_error = "unknown model"; return SVHIP_ERR_INVALID; }
+    if (cfg->model != SVHIP_MODEL_ECAPA && !is_rawnet2(cfg->model) && cfg->model != SVHIP_MODEL_NONE) { g_create_error = "unknown model"; return SVHIP_ERR_INVALID; }
     if (cfg->model == SVHIP_MODEL_ECAPA && (cfg->channels <= 0 || cfg->channels % 64 != 0)) { g_create_error = "ECAPA channels must be a positive multiple of 64"; return SVHIP_ERR_INVALID; }
     if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16 && cfg->compute != SVHIP_F32X3 && cfg->compute != SVHIP_F16) { g_create_error = "unknown compute mode"; return SVHIP_ERR_INVALID; }
-    if (cfg->compute == SVHIP_F16 && cfg->model != SVHIP_MODEL_RAWNET2) { g_create_error = "SVHIP_F16 is RawNet2's 16-bit mode (ECAPA's is SVHIP_BF16)"; return SVHIP_ERR_UNSUPPORTED; }
+    if (cfg->compute == SVHIP_F16 && !is_rawnet2(cfg->model)) { g_create_error = "SVHIP_F16 is RawNet2's 16-bit mode (ECAPA's is SVHIP_BF16)"; return SVHIP_ERR_UNSUPPORTED; }
     if (cfg->model == SVHIP_MODEL_RAWNET2 && cfg->samples < 251 + 3 * 3 * 3 * 3 * 3 * 3 * 3) { g_create_error = "RawNet2 needs at least 2438 samples"; return SVHIP_ERR_INVALID; }
+    if (cfg->model == SVHIP_MODEL_RAWNET2_CONV && cfg->samples < 3 * RN_MIN_FRAMES) {
+        g_create_error = "RawNet2 (front_proc='conv') needs at least 2187 samples: floor(L / 3) frames pass six max_pool1d(3) stages";
+        return SVHIP_ERR_INVALID;
+    }
     if (cfg->n_mels <= 0 || cfg->n_mels % 8 != 0 || cfg->max_batch <= 0 || cfg->samples < cfg->n_fft || cfg->hop_length <= 0) { g_create_error = "bad n_mels / max_batch / samples"; return SVHIP_ERR_INVALID; }
     if ((e = hipSetDevice(cfg->device)) != hipSuccess) { g_create_error = hipGetErrorString(e); return SVHIP_ERR_HIP; }
     svhip_handle* h = new svhip_handle();
@@ -1852,7 +1896,7 @@ int svhip_finalize_weights(svhip_handle* h) {
             SV_FAIL(h, SVHIP_ERR_MISSING, "tensor %s was never loaded", kv.first.c_str());
     int rc = SVHIP_ERR_UNSUPPORTED;
     if (h->cfg.model == SVHIP_MODEL_ECAPA) rc = finalize_ecapa(h);
-    else if (h->cfg.model == SVHIP_MODEL_RAWNET2) rc = finalize_rawnet2(h);
+    else if (is_rawnet2(h->cfg.model)) rc = finalize_rawnet2(h);
     else SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
     if (rc) return rc;
     SV_HIP(h, hipDeviceSynchronize());
@@ -1932,7 +1976,7 @@ int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, fl
     if (L != h->cfg.samples) SV_FAIL(h, SVHIP_ERR_INVALID, "L=%d but the handle was created for %d samples", L, h->cfg.samples);
     if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
         SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
-    if (h->cfg.model != SVHIP_MODEL_ECAPA && h->cfg.model != SVHIP_MODEL_RAWNET2)
+    if (h->cfg.model != SVHIP_MODEL_ECAPA && !is_rawnet2(h->cfg.model))
         SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
     SV_HIP(h, hipSetDevice(h->cfg.device));
     const float* d_in = wav;
@@ -1940,7 +1984,7 @@ int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, fl
         SV_HIP(h, hipMemcpyAsync(h->d_wav, wav, (size_t)B * L * 4, hipMemcpyHostToDevice, h->stream));
         d_in = h->d_wav;
     }
-    if (h->cfg.model == SVHIP_MODEL_RAWNET2) {
+    if (is_rawnet2(h->cfg.model)) {
         if ((rc = rawnet2_forward(h, d_in, B))) return rc;
     } else {
         const int T = h->T;

@@ -133,6 +133,12 @@ template <> struct Half16<f16_t> {
     }
 };
 
+// RawNet2's 'conv' front-end (RawNet2_custom.py:45-52,166-169: Conv1d(1, 128, kernel 3, stride 3) with bias): one output value in ONE fixed
+// fp32 order.  rn_conv3_front (rn_conv3.hip) and the fused block 0 of rn_block128 both call this, so their values agree bit for bit.
+__device__ __forceinline__ float rn_conv3_y(float w0, float w1, float w2, float bias, float s0, float s1, float s2) {
+    return fmaf(w2, s2, fmaf(w1, s1, fmaf(w0, s0, bias)));
+}
+
 // ---- the split ("X3") forms: fp32 values as hi | lo planes of a 16-bit type, a product as three MFMAs (hi.hi + hi.lo + lo.hi) ----------
 // Round 4: the planes are IEEE half, not bf16.  bf16 planes carry 8 + 8 significant bits (v - hi - lo ~ 2^-17 |v|: the error of rounds
 // 2 - 3's f32x3 mode); fp16 planes carry 11 + 11 (2^-23 |v| while lo is a normal half, i.e. |v| >= 2^-3; below that lo is a subnormal

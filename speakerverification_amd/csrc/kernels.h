@@ -329,6 +329,9 @@ hipError_t launch_rn_sinc(const float* wav, const float* stats, const float* gam
 // (sym, DT_F16 only: `filt` is the [128][128] slot-major table of the symmetric form — rawnet2.hip, rn_sinc_kernel<.., SYM>)
 // (dt: DT_F32 / DT_BF16 / DT_F16 — the storage type of the activations)
 // (y_s32 / pre_s32, fp32 only: that output in the S32 split layout — the operand of the split convolution kernels — instead of fp32)
+// RawNet2 'conv' front-end (rn_conv3.hip): x (B, T1, 128) in dt = Conv1d(1, 128, 3, stride 3) of wav (B, L) fp32, T1 = (L - 3) / 3 + 1;
+// cw = [w0 | w1 | w2 | bias] x 128 floats
+hipError_t launch_rn_conv3_front(const float* wav, const float* cw, void* x, int dt, int B, int L, int T1, hipStream_t stream);
 hipError_t launch_rn_bn_act(const void* x, void* y, int dt, const float* scale, const float* shift, int64_t rows, int C,
                             float slope, hipStream_t stream, bool y_s32 = false);
 hipError_t launch_rn_maxpool3(const void* x, void* y, int dt, int B, int Tin, int C, hipStream_t stream);
@@ -363,6 +366,11 @@ struct RnBlock128Params {
     unsigned long long* dbg = nullptr;   // tools/rb_bench: per-workgroup phase cycle totals (only read in -DSVHIP_GEMM_DEBUG builds)
     int debug = 0;                       // tools/rb_bench ablations (debug builds): 1 no fragment reads, 2 no MFMA, 4 no conversion, 8 no pool
     int f16 = 0;                         // the 16-bit tensors (xin, W1, W2, opool) hold fp16, not bf16
+    // RawNet2 'conv' front-end fused into block 0 (xin unused, no gate): the item's input rows are computed from the waveform
+    // (B, L) fp32 as rn_conv3_front would store them; cw = [w0 | w1 | w2 | bias] x 128 floats.  T = (L - 3) / 3 + 1.
+    const float* wav = nullptr;
+    const float* cw = nullptr;
+    int L = 0;
 };
 int rn_block128_ntiles(int T);
 int rn_block128_nparts(int B, int T, int num_cu);

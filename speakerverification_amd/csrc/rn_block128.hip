@@ -50,6 +50,11 @@ constexpr int RB_O = RB_Y + 2 * RB_YR * 256;
 constexpr int RB_CST = RB_O + RB_OR * 256;                       // 5 x 128 floats of per-channel constants
 constexpr int RB_GATE = RB_CST + 5 * 128 * 4;                    // 2 x 1 KiB: the item's AFMS gate row (one DMA piece: the 128 floats twice)
 constexpr int RB_LDS = RB_GATE + 2 * 1024;                       // 151 040 bytes
+// block 0 behind RawNet2's 'conv' front-end (CONV): the item's 246 waveform samples land in the two gate slots (block 0 has no gate),
+// the conv constants [w0 | w1 | w2 | bias] x 128 floats follow RB_LDS
+constexpr int RB_SMP = RB_GATE;
+constexpr int RB_CW = RB_LDS;
+constexpr int RB_LDS_CONV = RB_CW + 4 * 128 * 4;                 // 153 088 bytes
 
 typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
@@ -152,8 +157,9 @@ __device__ __forceinline__ void conv_k3(const char* src, const bf16x8 (&w)[2][12
     __builtin_amdgcn_s_setprio(0);
 }
 
-template <bool GATE, typename H>
+template <bool GATE, typename H, bool CONV>
 __global__ __launch_bounds__(512, 2) void rn_block128_kernel(RnBlock128Params p) {
+    static_assert(!(GATE && CONV), "the conv front-end feeds block 0, which has no gate");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -179,6 +185,8 @@ __global__ __launch_bounds__(512, 2) void rn_block128_kernel(RnBlock128Params p)
         const float* srcs[5] = {p.bn1_scale, p.bn1_shift, p.alpha, p.bn2_scale, p.bn2_shift};
         reinterpret_cast<float*>(smem + RB_CST)[i] = (which == 2 && !GATE) ? 0.0f : srcs[which][c];
     }
+    if (CONV)
+        for (int i = tid; i < 4 * 128; i += 512) reinterpret_cast<float*>(smem + RB_CW)[i] = p.cw[i];
     for (int i = tid; i < 2 * 2 * 16; i += 512)                   // H rows 80, 81 (both buffers) feed only the two discarded output rows
         *reinterpret_cast<u32x4*>(smem + RB_H + (i >> 5) * RB_HR * 256 + (80 + ((i >> 4) & 1)) * 256 + ((i & 15) << 4)) = u32x4{0u, 0u, 0u, 0u};
 
@@ -194,6 +202,13 @@ __global__ __launch_bounds__(512, 2) void rn_block128_kernel(RnBlock128Params p)
     auto issue_dma = [&](int k) {
         const int item = first + k;
         const int b = item / p.ntiles, t0 = (item - b * p.ntiles) * RB_TT;
+        if (CONV) {
+            // the samples of frames t0 - 2 .. t0 + 79: 3 (t0 - 2) + 0 .. 245 (wave w4 moves 64 of 256, one dword per lane), clamped to the
+            // utterance — frames in [0, T) read only samples < 3 T <= L; the others are zeroed or never stored
+            const int sidx = min(max(3 * (t0 - 2) + 64 * w4 + lane, 0), p.L - 1);
+            __builtin_amdgcn_global_load_lds((gbl_void*)(p.wav + (int64_t)b * p.L + sidx), (lds_void*)(smem + RB_SMP + (k & 1) * 1024 + w4 * 256), 4, 0, 0);
+            return;
+        }
         char* dst = smem + RB_P + (k & 1) * RB_RAWK * 1024;
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
@@ -326,10 +341,31 @@ __global__ __launch_bounds__(512, 2) void rn_block128_kernel(RnBlock128Params p)
             char* pbuf = smem + RB_P + (k & 1) * RB_RAWK * 1024;
             char* ybuf = smem + RB_Y + (k & 1) * RB_YR * 256;
             u32x4 xin[NI];
+            if (CONV) {
+                // x rows from the waveform, as rn_conv3_front stores them: row r <-> frame t0 - 2 + r <-> samples 3 r .. 3 r + 2 of the slot
+                f32x4 cw[4][2];
 #pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                const int row = min(row0 + rg + 16 * i, RB_PR - 1);
-                xin[i] = *reinterpret_cast<const u32x4*>(pbuf + row * 256 + ((c16 ^ RB_SWZ(row)) << 4));
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int hf = 0; hf < 2; ++hf) cw[j][hf] = *reinterpret_cast<const f32x4*>(smem + RB_CW + (j * 128 + 8 * c16 + 4 * hf) * 4);
+                const float* smp = reinterpret_cast<const float*>(smem + RB_SMP + (k & 1) * 1024);
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    const int row = min(row0 + rg + 16 * i, RB_PR - 1);
+                    const float s0 = smp[3 * row], s1 = smp[3 * row + 1], s2 = smp[3 * row + 2];
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        const int e0 = (2 * w) & 3, e1 = (2 * w + 1) & 3, hf = w >> 1;
+                        xin[i][w] = bf_pack(rn_conv3_y(cw[0][hf][e0], cw[1][hf][e0], cw[2][hf][e0], cw[3][hf][e0], s0, s1, s2),
+                                            rn_conv3_y(cw[0][hf][e1], cw[1][hf][e1], cw[2][hf][e1], cw[3][hf][e1], s0, s1, s2));
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    const int row = min(row0 + rg + 16 * i, RB_PR - 1);
+                    xin[i] = *reinterpret_cast<const u32x4*>(pbuf + row * 256 + ((c16 ^ RB_SWZ(row)) << 4));
+                }
             }
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
@@ -539,21 +575,25 @@ bool rn_block128_supported(int cin, int cout, int T, bool downsample, bool has_s
 
 hipError_t launch_rn_block128(const RnBlock128Params& p_in, int num_cu, hipStream_t stream) {
     RnBlock128Params p = p_in;
-    if (!p.xin || !p.W1 || !p.W2 || !p.opool || !p.colsum || p.B <= 0 || p.T < 3 || p.Tout != p.T / 3 || p.ntiles != rn_block128_ntiles(p.T))
+    const bool conv = p.wav != nullptr;
+    if ((!conv && !p.xin) || !p.W1 || !p.W2 || !p.opool || !p.colsum || p.B <= 0 || p.T < 3 || p.Tout != p.T / 3 || p.ntiles != rn_block128_ntiles(p.T))
         return hipErrorInvalidValue;
     if ((p.alpha == nullptr) != (p.gate == nullptr)) return hipErrorInvalidValue;
+    if (conv && (!p.cw || p.gate || p.T != (p.L - 3) / 3 + 1)) return hipErrorInvalidValue;
     int grid = 0;
     rn_block128_split(p.B, p.T, num_cu, &p.per_wg, &p.nseg, &grid);
     // the partial rows of segments an utterance does not have stay zero
     if (hipError_t e = hipMemsetAsync(p.colsum, 0, (size_t)p.B * p.nseg * 4 * 128 * sizeof(float), stream)) return e;
-#define SV_RB(G, HH)                                                                                                       \
+#define SV_RB(G, HH, CV)                                                                                                   \
     {                                                                                                                      \
         static DeviceOnce attr;                                                                                            \
-        if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(rn_block128_kernel<G, HH>), RB_LDS)) return e; \
-        hipLaunchKernelGGL((rn_block128_kernel<G, HH>), dim3(grid), dim3(512), RB_LDS, stream, p);                         \
+        constexpr int lds = CV ? RB_LDS_CONV : RB_LDS;                                                                     \
+        if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(rn_block128_kernel<G, HH, CV>), lds)) return e; \
+        hipLaunchKernelGGL((rn_block128_kernel<G, HH, CV>), dim3(grid), dim3(512), lds, stream, p);                        \
     }
-    if (p.f16) { if (p.gate) SV_RB(true, f16_t) else SV_RB(false, f16_t) }
-    else { if (p.gate) SV_RB(true, bf16_t) else SV_RB(false, bf16_t) }
+    if (conv) { if (p.f16) SV_RB(false, f16_t, true) else SV_RB(false, bf16_t, true) }
+    else if (p.f16) { if (p.gate) SV_RB(true, f16_t, false) else SV_RB(false, f16_t, false) }
+    else { if (p.gate) SV_RB(true, bf16_t, false) else SV_RB(false, bf16_t, false) }
 #undef SV_RB
     return hipGetLastError();
 }

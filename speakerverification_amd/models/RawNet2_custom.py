@@ -1,11 +1,15 @@
-"""Drop-in for the reference plug-in ``models/RawNet2_custom.py`` (MainModel :230-243) in the variant
-the fusion models instantiate (``front_proc='sinc'``, ``aggregate='asp'``, Raw_ECAPA_sinc_asp.py:26-28).
+"""Drop-in for the reference plug-in ``models/RawNet2_custom.py`` (MainModel :230-243) in the variants
+the fusion models instantiate: ``aggregate='asp'``, ``att_dim=128`` with ``front_proc='sinc'``
+(Raw_ECAPA_sinc_asp.py / Raw_ECAPA.py:26-28) or ``front_proc='conv'`` (Raw_ECAPA_conv_asp.py:26-28).
 
     model = MainModel(nOut=320, front_proc='sinc', aggregate='asp', att_dim=128, audio_spec={...})
     emb = model(wav)          # (B, 32000) waveform -> (B, nOut); (nOut,) for B == 1
 
-State-dict keys are the reference's (147 tensors); the sinc band-pass filters are rebuilt from
-``first_conv.low_hz_`` / ``band_hz_`` once per weight load instead of once per forward.
+State-dict keys are the reference's: 147 tensors for 'sinc' (the band-pass filters are rebuilt from
+``first_conv.low_hz_`` / ``band_hz_`` once per weight load instead of once per forward), 140 for 'conv'
+(``conv1.weight`` / ``conv1.bias``).  The sinc form's LayerNorm(nb_samp) fixes the input length; the conv
+form takes any length L >= 2187 (one library handle per length, the configured crop length with the
+full batch workspace).
 """
 from __future__ import annotations
 
@@ -13,18 +17,31 @@ from .. import synth
 from ._base import HipModule
 
 
+# the conv front-end's shortest input: floor(L / 3) frames must survive six max_pool1d(3) stages (the reference raises below it)
+CONV_MIN_SAMPLES = 3 * 3 ** 6
+
+
 class RawNet2(HipModule):
     model_kind = "rawnet2"
 
     def __init__(self, nOut=512, front_proc="sinc", aggregate="gru", att_dim=128, audio_spec=None, device=None,
                  compute=None, max_batch=None, **kwargs):
-        if front_proc != "sinc" or aggregate != "asp" or att_dim != 128:
-            raise NotImplementedError("only front_proc='sinc', aggregate='asp', att_dim=128 is built "
-                                      "(the variant of Raw_ECAPA_sinc_asp.py:26-28)")
-        audio_spec = audio_spec or {"sample_rate": 16000, "sentence_len": 2.0}
-        if int(audio_spec["sample_rate"]) != 16000:
-            raise NotImplementedError("the sinc front-end is built for sample_rate 16000 (RawNet2_custom.py:55-63)")
-        self.nb_samp = int(audio_spec["sentence_len"] * audio_spec["sample_rate"])      # LayerNorm(nb_samp), :58-60
+        if front_proc not in ("sinc", "conv") or aggregate != "asp" or att_dim != 128:
+            raise NotImplementedError("only front_proc='sinc' | 'conv', aggregate='asp', att_dim=128 are built "
+                                      "(the variants of Raw_ECAPA_sinc_asp.py / Raw_ECAPA_conv_asp.py:26-28)")
+        self.front_proc = front_proc
+        if front_proc == "conv":
+            self.model_kind = "rawnet2_conv"
+            # no LayerNorm(nb_samp): any length; the configured crop length (if the config gives one) gets the full workspace
+            spec_samples = int(audio_spec["sentence_len"] * audio_spec["sample_rate"]) if audio_spec else None
+            if spec_samples is not None and spec_samples < CONV_MIN_SAMPLES:
+                raise ValueError(f"audio_spec gives {spec_samples} samples; RawNet2 (front_proc='conv') needs at least {CONV_MIN_SAMPLES}")
+            self.nb_samp = spec_samples
+        else:
+            audio_spec = audio_spec or {"sample_rate": 16000, "sentence_len": 2.0}
+            if int(audio_spec["sample_rate"]) != 16000:
+                raise NotImplementedError("the sinc front-end is built for sample_rate 16000 (RawNet2_custom.py:55-63)")
+            self.nb_samp = int(audio_spec["sentence_len"] * audio_spec["sample_rate"])      # LayerNorm(nb_samp), :58-60
         # hip_compute: "f32" (exact fp32 MFMA) | "f32x3" | "f16" (fp16 storage + fp16 MFMA: RawNet2's fast mode) | "bf16" (the same
         # kernels on bf16: range-safe, but RawNet2 loses two digits to bf16 weight rounding) | "half" = this model's 16-bit mode (f16)
         compute = compute or kwargs.get("hip_compute", "f32")
@@ -35,18 +52,35 @@ class RawNet2(HipModule):
         # ill-scaled one of tests/test_gpu_rawnet2.py), so it is not the default
         self._range_fallback = kwargs.get("range_fallback", "f32")
         max_batch = int(max_batch or kwargs.get("embed_batch", 256))
-        super().__init__(synth.rawnet2_param_spec(nOut=nOut, nb_samp=self.nb_samp, att_dim=att_dim),
+        super().__init__(synth.rawnet2_param_spec(nOut=nOut, nb_samp=self.nb_samp or 0, att_dim=att_dim, front_proc=front_proc),
                          dict(embed_dim=nOut), device=device if device is not None else kwargs.get("device"),
                          compute=compute, max_batch=max_batch, primary_samples=self.nb_samp)
 
-    def forward(self, x):
+    def _check_input(self, x):
+        """-> the input length; raises ValueError (before any handle is made) for a shape this module cannot run"""
+        if self.front_proc == "conv":
+            if x.ndim != 2 or x.shape[1] < CONV_MIN_SAMPLES:
+                raise ValueError(f"RawNet2 (front_proc='conv') takes (batch, L >= {CONV_MIN_SAMPLES}) waveforms, got {tuple(x.shape)} "
+                                 "(floor(L / 3) frames pass six max_pool1d(3) stages)")
+            return int(x.shape[1])
         if x.ndim != 2 or x.shape[1] != self.nb_samp:
             raise ValueError(f"RawNet2 was built for (batch, {self.nb_samp}) waveforms, got {tuple(x.shape)} "
                              "(LayerNorm gamma/beta fix the length, RawNet_baseline.py:16-18)")
+        return self.nb_samp
+
+    def accepts_length(self, L):
+        """can a (batch, L) waveform run (the sinc form: L == nb_samp; the conv form: L >= 2187)"""
+        return L >= CONV_MIN_SAMPLES if self.front_proc == "conv" else L == self.nb_samp
+
+    def _engine_for(self, x):
+        L = self._check_input(x)
+        return self._get_engine(L) if self.front_proc == "sinc" else self._get_engine(L, batch=x.shape[0])
+
+    def forward(self, x):
         from .._lib import SvhipNumericError, ERR_NONFINITE
-        eng = self._get_engine(self.nb_samp)
+        eng = self._engine_for(x)
         try:
-            return self._squeeze(self._batched(eng.embed_wave, x))
+            return self._squeeze(self._batched(eng.embed_wave, x, eng.max_batch))
         except SvhipNumericError as e:
             if e.code != ERR_NONFINITE or self._compute != "f16" or not self._range_fallback:
                 raise
@@ -55,8 +89,8 @@ class RawNet2(HipModule):
                           "(every later forward runs in that mode)", RuntimeWarning, stacklevel=2)
             self._compute = self._range_fallback
             self._drop_engine()
-            eng = self._get_engine(self.nb_samp)
-            return self._squeeze(self._batched(eng.embed_wave, x))
+            eng = self._engine_for(x)
+            return self._squeeze(self._batched(eng.embed_wave, x, eng.max_batch))
 
 
 def MainModel(nOut=512, **kwargs):

@@ -6,7 +6,7 @@ source of truth for the *names and shapes* of the reference state dicts
 
   * ECAPA-TDNN  — reference ``src/models/ECAPA_TDNN.py:339-458`` (231 tensors),
   * RawNet2     — reference ``src/models/RawNet2_custom.py:18-135`` + ``RawNet_baseline.py``
-                  (147 tensors, ``front_proc='sinc'``, ``aggregate='asp'``),
+                  (``aggregate='asp'``: 147 tensors with ``front_proc='sinc'``, 140 with ``'conv'``),
 
 and generates values from a ``numpy`` PCG64 stream in state-dict order, so the CPU oracle and the
 HIP path see bit-identical weights on any machine.  ``tests/test_oracle_golden.py`` checks the
@@ -68,13 +68,19 @@ def ecapa_param_spec(C=1024, n_mels=80, nOut=192, input_norm=False):
     return spec
 
 
-def rawnet2_param_spec(nOut=320, nb_samp=32000, att_dim=128):
-    """Ordered (name, shape) list == ``RawNet2_custom.MainModel(front_proc='sinc',
-    aggregate='asp').state_dict()`` of the reference."""
+def rawnet2_param_spec(nOut=320, nb_samp=32000, att_dim=128, front_proc="sinc"):
+    """Ordered (name, shape) list == ``RawNet2_custom.MainModel(front_proc=front_proc,
+    aggregate='asp').state_dict()`` of the reference: 147 tensors for ``'sinc'`` (LayerNorm, sinc filters,
+    first_bn), 140 for ``'conv'`` (``conv1 = Conv1d(1, 128, 3, stride=3)`` with bias, RawNet2_custom.py:45-52)."""
     f = RAWNET2_FILTERS
-    spec = [("ln.gamma", (nb_samp,)), ("ln.beta", (nb_samp,)),
-            ("first_conv.low_hz_", (f[0], 1)), ("first_conv.band_hz_", (f[0], 1))]
-    spec += _bn("first_bn", f[0])
+    if front_proc == "sinc":
+        spec = [("ln.gamma", (nb_samp,)), ("ln.beta", (nb_samp,)),
+                ("first_conv.low_hz_", (f[0], 1)), ("first_conv.band_hz_", (f[0], 1))]
+        spec += _bn("first_bn", f[0])
+    elif front_proc == "conv":
+        spec = [("conv1.weight", (f[0], 1, 3)), ("conv1.bias", (f[0],))]
+    else:
+        raise ValueError(f"front_proc {front_proc!r}: 'sinc' or 'conv'")
     inpl = f[0]
     for li, (nblk, planes) in enumerate(zip(RAWNET2_LAYERS, f), start=1):
         for b in range(nblk):
