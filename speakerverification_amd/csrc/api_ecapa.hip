@@ -1,0 +1,238 @@
+// api_ecapa.hip — the ECAPA-TDNN forward of libsvhip.
+#include <algorithm>
+
+#include "handle.h"
+
+namespace svhip {
+
+// ECAPA_TDNN.forward (models/ECAPA_TDNN.py:460-502) on device-resident features (B, n_mels, T)
+// for the utterances [b0, b0 + B) of the call, enqueued on h->cur.  Every workspace buffer is frame-major, so a
+// batch slice is just a row offset: two slices can run concurrently on two streams (lanes).
+static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, int B) {
+    const svhip_config& c = h->cfg;
+    const int T = h->T, M = B * T, C = c.channels, C3 = 3 * C, C8 = C / 8, e = h->esz;
+    const bool bf = h->bf16;
+    hipStream_t st = h->cur;
+    const size_t r0 = (size_t)b0 * T;                       // first activation row of the slice
+    const float* d_feat = d_feat_all + (size_t)b0 * c.n_mels * T;
+    void* X_in = off(h->X_in, r0 * c.n_mels, e);
+    void* X0 = off(h->X0, r0 * C, e);
+    void* H1 = off(h->H1, r0 * C, e);
+    void* H2 = off(h->H2, r0 * C, e);
+    void* H3 = off(h->H3, r0 * C, e);
+    void* CAT = off(h->CAT, r0 * C3, e);
+    void* MFA = off(h->MFA, r0 * C3, e);
+    void* ATT = off(h->ATT, r0 * 128, e);
+    float* LOGITS = h->LOGITS + r0 * C3;
+    float* d_pstats = h->d_pstats + (size_t)b0 * c.n_mels * 2;
+    float* d_mean = h->d_mean + (size_t)b0 * C;
+    float* d_s2 = h->d_s2 + (size_t)b0 * C;
+    float* d_gstats = h->d_gstats + (size_t)b0 * 2 * C3;
+    float* d_ctx = h->d_ctx + (size_t)b0 * 128;
+    float* d_pool_raw = h->d_pool_raw + (size_t)b0 * 2 * C3;
+    float* d_pool_bn = h->d_pool_bn + (size_t)b0 * 2 * C3;
+    float* d_emb = h->d_emb + (size_t)b0 * c.embed_dim;
+    float* cs_base = ((bf || h->x3) && h->d_colsum) ? h->d_colsum + (b0 ? 2 * h->colsum_region : 0) : nullptr;
+    int rc;
+    // F32X3: se_apply also leaves each block output in the S32 split layout (CAT's twin), so tdnn1 of the next block and mfa read
+    // their A operand without a conversion pass
+    char* cat32 = h->cat_s32 ? static_cast<char*>(h->cat_s32) + r0 * C3 * 4 : nullptr;
+    // ... and when every consumer of a block output takes the split operand at this batch size (tdnn1 of the next block, mfa: the
+    // persistent X3 kernel; the next se_apply reads its residual as hi + lo), the fp32 copy is not written at all
+    auto x3_route = [&](const ConvLayer& L, const void* a32, int lda32, bool cs) {
+        if (!h->x3 || !L.Ws32 || !h->s32_buf || !a32) return false;
+        GemmParams q = conv_params(h, L, a32, lda32, MFA, L.N, M, T);
+        q.W = L.Ws32; q.x3 = 2; q.act1 = ACT_GELU;
+        if (cs) { q.colsum = cs_base; q.colsum_sq = 1; q.colsum_stride = h->colsum_region; }
+        return gemm_pw3x3_supported(q);
+    };
+    const bool s32_only = cat32 && x3_route(h->tdnn1[1], cat32, C3, false) && x3_route(h->tdnn1[2], cat32, C3, false) &&
+                          x3_route(h->mfa, cat32, C3, cs_base != nullptr) && !h->opt.x3_keep_f32;
+    if (s32_only) h->cat_f32_stale = true;
+    bool b0_done = false, x0_s32 = false, b0_cv = false;
+    GemmParams q0;
+    float* xscale = h->d_xscale ? h->d_xscale + (b0 ? 4 + 256 : 0) : nullptr;
+    if (h->x3 && h->blocks0.Wcv && h->s32_buf) {
+        // F32X3: blocks.0 on the persistent kernel's conv-gather form: the features go to the S32 layout with rows zero-padded to
+        // cv_cin channels (one small pass), the im2col view is formed by the operand DMAs
+        const ConvLayer& L = h->blocks0;
+        GemmParams& q = q0;
+        q = conv_params(h, L, h->s32_buf, L.cv_cin, X0, C, M, T);
+        q.W = L.Wcv; q.Wrows = L.N; q.x3 = 2; q.K = L.taps * L.cv_cin; q.Kp = L.cv_Kp; q.cin = L.cv_cin; q.act1 = ACT_GELU;
+        // (with s32_only and tdnn1 of the first block on the X3 kernel, X0 itself is written in the split layout: no conversion pass,
+        //  block 1's residual is read as hi + lo, svhip_get_stage rebuilds the fp32 view)
+        q.y_s32 = (s32_only && x3_route(h->tdnn1[0], X0, C, false)) ? 1 : 0;
+        q.in_scale = xscale;
+        b0_cv = gemm_pw3cv_supported(q);
+    }
+    // the prologue's range guard (F32X3: half-precision planes carry |x| <= 65504): with the scaled first convolution only a non-finite
+    // input is reported — a finite one of any magnitude is brought into the planes' range by an exact power of two (round 6)
+    if (!h->xin_ready && (rc = run(h, "prologue", 0, [&]() {
+             return launch_prologue(d_feat, X_in, bf, B, c.n_mels, T, c.log_input, h->in_w, h->in_b, d_pstats, st,
+                                    h->x3 ? h->d_status : nullptr, h->host_flag_dev, (b0_cv && xscale) ? 3.0e38f : 65504.0f);
+         }))) return rc;
+    if (b0_cv) {
+        const ConvLayer& L = h->blocks0;
+        if (xscale && (rc = run(h, "in_scale", 0, [&]() {
+                 return launch_in_scale(static_cast<const float*>(X_in), (int64_t)M * c.n_mels, reinterpret_cast<uint32_t*>(xscale + 4), xscale, st, L.cv_wscale);
+             }))) return rc;
+        if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(X_in), c.n_mels, h->s32_buf, M, L.cv_cin, st, L.cv_cin, c.n_mels, xscale); }))) return rc;
+        if ((rc = run(h, "gemm_pw3cv", (double)M * L.flops_per_row, [&]() { return launch_gemm_pw3cv(q0, st); }))) return rc;
+        b0_done = true;
+        x0_s32 = q0.y_s32 != 0;
+    }
+    if (!b0_done) {
+        GemmParams p = conv_params(h, h->blocks0, X_in, c.n_mels, X0, C, M, T);
+        p.act1 = ACT_GELU;
+        if ((rc = conv_gemm(h, h->blocks0, p))) return rc;
+    }
+    h->x0_is_s32 = x0_s32;
+    const void* xin = x0_s32 ? nullptr : X0;
+    int ldin = C;
+    const void* xin32 = x0_s32 ? X0 : nullptr;
+    int ldin32 = C;
+    for (int i = 0; i < 3; ++i) {
+        const void* h2_32 = nullptr;      // F32X3: the chain output in the S32 layout (tdnn2's A operand)
+        // F32X3: seven launches of gemm_pw3's Res2Net step form; step j reads U_j = c_j + y_{j-1} (S32) and writes y_j (S32, into the
+        // chain output) and U_{j+1}; no fp32 copy of the chain exists
+        char* h2s = h->h2_s32 ? static_cast<char*>(h->h2_s32) + r0 * C * 4 : nullptr;
+        char* us[2] = {h->u_s32[0] ? static_cast<char*>(h->u_s32[0]) + r0 * C8 * 4 : nullptr, h->u_s32[1] ? static_cast<char*>(h->u_s32[1]) + r0 * C8 * 4 : nullptr};
+        auto step_params = [&](int j) {
+            const ConvLayer& L = h->res2[i][j - 1];
+            GemmParams q = conv_params(h, L, us[(j - 1) & 1], C8, h2s + (size_t)j * C8 * 4, C, M, T);
+            q.W = L.Ws32; q.Wrows = L.N; q.x3 = 2; q.act1 = ACT_RELU;
+            if (j < 7) { q.R = static_cast<const float*>(H1) + (size_t)(j + 1) * C8; q.ldr = C; q.Y2 = us[j & 1]; q.lda2 = C8; }
+            return q;
+        };
+        // (C / 8 = 128: the dedicated 128 x 128 kernel, two workgroups per CU, any batch size; C / 8 = 64, or SVHIP_R2_BIG=1: the R2 form
+        //  of the persistent 256 x 256 kernel)
+        const bool r2_small = h->x3 && h2s && us[0] && us[1] && h->res2[i][0].Ws32 && !h->opt.r2_big && r2_step_supported(step_params(1)) &&
+                              x3_route(h->tdnn2[i], h2s, C, false);      // (tdnn2 must be able to read the chain output in the split layout)
+        const bool r2_plan = r2_small || (h->x3 && h2s && us[0] && us[1] && h->res2[i][0].Ws32 && gemm_pw3r2_supported(step_params(1)));
+        if (r2_plan) {      // tdnn1 writes the pass-through chunk and the first step's input in the split layout itself (when it takes the X3 kernel)
+            h->side_a = h2s; h->side_lda = C; h->side_b = us[0]; h->side_ldb = C8; h->side_c = C8;
+        }
+        GemmParams p1 = conv_params(h, h->tdnn1[i], (s32_only && (i > 0 || x0_s32)) ? nullptr : xin, ldin, H1, C, M, T);
+        p1.act1 = ACT_GELU;
+        if ((rc = conv_gemm(h, h->tdnn1[i], p1, xin32, ldin32))) return rc;
+        const bool side_done = h->side_done;
+        h->side_c = 0;
+        if (r2_plan) {
+            if (!side_done) {
+                if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(H1), C, h2s, M, C8, st, C); }))) return rc;
+                if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(H1) + C8, C, us[0], M, C8, st, C8); }))) return rc;
+            }
+            for (int j = 1; j < 8; ++j) {
+                const GemmParams q = step_params(j);
+                if (r2_small) {
+                    if ((rc = run(h, "r2_step", (double)M * h->res2[i][j - 1].flops_per_row, [&]() { return launch_r2_step(q, st); }))) return rc;
+                } else if ((rc = run(h, "gemm_pw3r2", (double)M * h->res2[i][j - 1].flops_per_row, [&]() { return launch_gemm_pw3r2(q, st); }))) return rc;
+            }
+            h2_32 = h2s;
+        } else if (bf && res2net_chain_supported(C, T, h->res2[i][0].dil, h->res2[i][0].Kp)) {
+            Res2Params rp;
+            rp.H1 = H1; rp.H2 = H2; rp.ld = C; rp.T = T; rp.dil = h->res2[i][0].dil; rp.Kp = h->res2[i][0].Kp;
+            // small batches (the reference's per-file calls: B = num_eval crops): time slices, so that the chip is not left to B workgroups
+            rp.slices = h->opt.r2_slices >= 0 ? std::max(1, h->opt.r2_slices) : res2net_chain_slices(B, C, T, rp.dil, h->num_cu);
+            double fl = 0;
+            for (int j = 0; j < 7; ++j) {
+                rp.W[j] = h->res2[i][j].W; rp.bias[j] = h->res2[i][j].bias;
+                rp.scale[j] = h->res2[i][j].scale; rp.shift[j] = h->res2[i][j].shift;
+                fl += (double)M * h->res2[i][j].flops_per_row;
+            }
+            if ((rc = run(h, rp.slices > 1 ? "res2net_slices" : "res2net_chain", fl, [&]() { return launch_res2net_chain(rp, B, C, st); }))) return rc;
+        } else {
+            if ((rc = run(h, "copy_cols", 0, [&]() { return launch_copy_cols(H1, C, H2, C, bf, M, C8, st); }))) return rc;
+            for (int j = 1; j < 8; ++j) {
+                GemmParams p = conv_params(h, h->res2[i][j - 1], off(H1, (size_t)j * C8, e), C, off(H2, (size_t)j * C8, e), C, M, T);
+                p.act1 = ACT_RELU;
+                p.A2 = j >= 2 ? off(H2, (size_t)(j - 1) * C8, e) : nullptr; p.lda2 = C;
+                if ((rc = conv_gemm(h, h->res2[i][j - 1], p))) return rc;
+            }
+        }
+        // tdnn2; its epilogue also leaves per-utterance column sums (the SE squeeze) when the pw2 kernel runs
+        GemmParams p2 = conv_params(h, h->tdnn2[i], r2_plan ? nullptr : H2, C, H3, C, M, T);
+        p2.act1 = ACT_GELU;
+        p2.colsum = cs_base; p2.colsum_stride = h->colsum_region;
+        if ((rc = conv_gemm(h, h->tdnn2[i], p2, h2_32, C))) return rc;
+        const bool from_part = h->last_colsum_done;      // the squeeze comes straight from the GEMM's column-sum partials
+        if (!from_part) {
+            if ((rc = run(h, "se_mean", 0, [&]() { return launch_colmean(H3, bf, C, B, T, C, d_mean, st); }))) return rc;
+        }
+        if ((rc = run(h, "se_mlp", 4.0 * B * 128 * C, [&]() {
+                 return launch_se_mlp(from_part ? nullptr : d_mean, from_part ? cs_base : nullptr, T,
+                                      bf ? (const void*)h->se1_bf[i] : (const void*)h->se1[i].W, h->se1[i].bias,
+                                      bf ? (const void*)h->se2T_bf[i] : (const void*)h->se2T[i], h->se2[i].bias, d_s2, bf, B, C, 128, st,
+                                      h->last_colsum_groups);
+             }))) return rc;
+        void* xout = off(CAT, (size_t)i * C, e);
+        void* xout32 = cat32 ? cat32 + (size_t)i * C * 4 : nullptr;
+        if ((rc = run(h, "se_apply", 0, [&]() {
+                 return launch_se_apply(H3, C, d_s2, xin, ldin, s32_only ? nullptr : xout, C3, bf, B, T, C, st, xout32, C3,
+                                        s32_only && (i > 0 || x0_s32) ? xin32 : nullptr, ldin32);
+             })))
+            return rc;
+        xin = xout;
+        xin32 = xout32;
+        ldin = C3;
+        ldin32 = C3;
+    }
+    GemmParams pm = conv_params(h, h->mfa, s32_only ? nullptr : CAT, C3, MFA, C3, M, T);
+    pm.act1 = ACT_GELU;
+    pm.colsum = cs_base; pm.colsum_sq = 1; pm.colsum_stride = h->colsum_region;
+    if ((rc = conv_gemm(h, h->mfa, pm, cat32, C3))) return rc;
+    if (h->last_colsum_done) {
+        if ((rc = run(h, "colsum_finalize", 0, [&]() { return launch_colsum_finalize(cs_base, h->colsum_region, true, B, T, C3, M, d_gstats, 1e-12f, st, h->last_colsum_groups); }))) return rc;
+    } else {
+        if ((rc = run(h, "asp_gstats", 0, [&]() { return launch_colstats(MFA, bf, C3, B, T, C3, d_gstats, 1e-12f, st); }))) return rc;
+    }
+    if ((rc = run(h, "asp_ctx", 2.0 * B * 128 * 2 * C3, [&]() {
+             return launch_rowvec_linear(d_gstats, 2 * C3, h->asp_ctx.W, h->asp_ctx.bias, d_ctx, 128, B, 128, 2 * C3, ACT_NONE, st, h->d_lin_part + (size_t)b0 * h->lin_part_per_utt);
+         }))) return rc;
+    GemmParams pa = conv_params(h, h->asp_tdnn, MFA, C3, ATT, 128, M, T);
+    pa.act1 = ACT_RELU; pa.act2 = ACT_TANH;
+    pa.bias_utt = d_ctx; pa.ld_bu = 128;
+    if ((rc = conv_gemm(h, h->asp_tdnn, pa))) return rc;
+    // bf16: 16 waves per CU, lane-local online softmax (asp_x3.hip's bf16 form: 0.195 against 0.264 ms at B = 256, any T); the
+    // one-wave-per-SIMD kernel keeps the channel counts that are not multiples of 256 (and SVHIP_ASP_V1=1: the tests compare the two)
+    const bool asp_v2 = bf && C3 % 256 == 0 && h->asp_tdnn.N == 128 && h->asp_conv.Kp == 128 && !h->opt.asp_v1;
+    if (asp_v2 || (bf && asp_fused_supported(T, C3, h->asp_tdnn.N, h->asp_conv.Kp))) {
+        AspFusedParams ap;
+        ap.att = ATT; ap.W = h->asp_conv.W; ap.Kp = h->asp_conv.Kp; ap.bias = h->asp_conv.bias;
+        ap.X = MFA; ap.ldx = C3; ap.T = T; ap.C = C3;
+        ap.bn_scale = h->aspbn_scale; ap.bn_shift = h->aspbn_shift;
+        ap.pooled_raw = d_pool_raw; ap.pooled_bn = d_pool_bn; ap.eps = 1e-12f;
+        if (asp_v2) {
+            if ((rc = run(h, "asp_bf16", (double)M * h->asp_conv.flops_per_row, [&]() { return launch_asp_bf16(ap, d_gstats, 2 * C3, B, st); }))) return rc;
+        } else
+        if ((rc = run(h, "asp_fused", (double)M * h->asp_conv.flops_per_row, [&]() { return launch_asp_fused(ap, B, st); }))) return rc;
+    } else if (h->x3 && h->asp_conv.Ws32 && asp_x3_supported(T, C3, h->asp_tdnn.N, h->asp_conv.K)) {
+        AspX3Params ap;
+        ap.att = (const float*)ATT; ap.Ws32 = h->asp_conv.Ws32; ap.X = (const float*)MFA; ap.ldx = C3; ap.T = T; ap.C = C3;
+        ap.mref = d_gstats; ap.mref_ld = 2 * C3;                  // [mean | std] per utterance: the means
+        ap.bn_scale = h->aspbn_scale; ap.bn_shift = h->aspbn_shift;
+        ap.pooled_raw = d_pool_raw; ap.pooled_bn = d_pool_bn; ap.eps = 1e-12f;
+        if ((rc = run(h, "asp_x3", (double)M * h->asp_conv.flops_per_row, [&]() { return launch_asp_x3(ap, B, st); }))) return rc;
+    } else {
+        GemmParams p = conv_params(h, h->asp_conv, ATT, 128, LOGITS, C3, M, T);
+        p.out_f32 = 1;
+        if ((rc = conv_gemm(h, h->asp_conv, p))) return rc;
+        if ((rc = run(h, "asp_pool", 0, [&]() {
+                 return launch_asp_pool(LOGITS, MFA, bf, C3, B, T, C3, h->aspbn_scale, h->aspbn_shift, d_pool_raw, d_pool_bn, 1e-12f, st);
+             }))) return rc;
+    }
+    if ((rc = run(h, "fc", 2.0 * B * h->fc.N * h->fc.K, [&]() {
+             return launch_rowvec_linear(d_pool_bn, 2 * C3, h->fc.W, h->fc.bias, d_emb, c.embed_dim, B, c.embed_dim, 2 * C3, ACT_NONE, st, h->d_lin_part + (size_t)b0 * h->lin_part_per_utt);
+         }))) return rc;
+    return SVHIP_OK;
+}
+
+// whole batch: one lane, or two half-batches on two streams so that kernel tails, launch gaps and the
+// small latency-bound kernels of one half overlap the big GEMMs of the other
+int ecapa_forward(svhip_handle* h, const float* d_feat, int B) {
+    h->cat_f32_stale = false;
+    const bool two = h->lanes == 2 && B >= 64 && !h->x3;      // (F32X3: the lanes would share the split-operand staging buffer)
+    return forward_lanes(h, ecapa_forward_part, d_feat, B, two ? 2 : 1, (B / 2 + 3) & ~3);
+}
+
+}  // namespace svhip

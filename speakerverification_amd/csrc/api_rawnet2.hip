@@ -1,0 +1,287 @@
+// api_rawnet2.hip — the RawNet2 forward of libsvhip.
+#include <algorithm>
+
+#include "handle.h"
+
+namespace svhip {
+
+// conv2 + 1 x 1 shortcut of a RawNet2 block as ONE conv-gather GEMM: K = 3 * cout conv columns of hb, then cin columns of `pre`
+static GemmParams conv2sc_params(svhip_handle* h, const svhip_handle::RnBlock& K, const void* pre, const void* hb, void* o, int M, int T) {
+    GemmParams p = conv_params(h, K.conv2, hb, K.cout, o, K.cout, M, T);
+    p.W = K.conv2sc_W; p.Kp = K.conv2.K + K.cin; p.zero_page = zero_page_for(h, hb); p.pad_mode = PAD_ZERO;
+    p.A3 = pre; p.lda3 = K.cin; p.K3 = K.cin;
+    return p;
+}
+static bool conv2sc_fits(svhip_handle* h, const svhip_handle::RnBlock& K, const void* pre, const void* hb, void* o, int M, int T) {
+    const GemmParams p = conv2sc_params(h, K, pre, hb, o, M, T);
+    return gemm_pw2_supported(p, true) && gemm_route(p, true) == ROUTE_PW2;
+}
+
+// would conv_gemm route this residual-free convolution to the persistent conv-gather kernel?
+static bool conv_cv_persistent(svhip_handle* h, const ConvLayer& L, const void* A, int lda, int M, int T, int pad_mode) {
+    GemmParams p = conv_params(h, L, A, lda, h->d_emb, L.N, M, T);      // (Y: any 16-byte aligned pointer; the route does not depend on it)
+    p.zero_page = zero_page_for(h, A); p.pad_mode = pad_mode;
+    return h->bf16 && gemm_route(p, true) == ROUTE_PW3CV;
+}
+
+// RawNet2.forward (models/RawNet2_custom.py:161-227) on device-resident waveforms (B, L), utterances [b0, b0 + B) of the call,
+// enqueued on h->cur.  Every workspace buffer is per-utterance contiguous, so a batch slice is an offset into each.
+static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0, int B) {
+    const svhip_config& c = h->cfg;
+    const bool bf = h->bf16;
+    hipStream_t st = h->cur;
+    const int L = c.samples, e = h->esz;
+    const size_t per_utt = (size_t)h->rn_T1 * 128;                 // elements of the largest activation of one utterance
+    const float* d_wav = d_wav_all + (size_t)b0 * L;
+    const bool conv = c.model == SVHIP_MODEL_RAWNET2_CONV;        // front_proc='conv': no LayerNorm, no sinc, no first_bn
+    float* rn_stats = conv ? nullptr : h->rn_stats + (size_t)b0 * 2;
+    float* rn_mean = h->rn_mean + (size_t)b0 * 512;
+    float* rn_scratch = h->rn_scratch + (size_t)b0 * 16 * 512;
+    float* rn_part = h->rn_part + (size_t)b0 * (rn_block128_ntiles(h->rn_T1) + 1) * 4 * 128;
+    float* rn_gate[2] = {h->rn_s + (size_t)b0 * 512, h->rn_s + ((size_t)c.max_batch + b0) * 512};
+    float* rn_pooled = h->rn_pooled + (size_t)b0 * 1024;
+    float* d_emb = h->d_emb + (size_t)b0 * c.embed_dim;
+    int rc;
+    const bool sinc_x3 = !conv && h->x3 && h->rn_filt_x3 && !h->opt.rn_sinc_f32;      // F32X3: the front-end on three fp16 MFMAs per product
+    void* rn_xn = conv ? nullptr : bf ? static_cast<char*>(h->rn_xn) + (size_t)b0 * 2 * h->rn_Lp * 2 : sinc_x3 ? static_cast<char*>(h->rn_xn) + (size_t)b0 * 4 * h->rn_Lp * 2 : nullptr;
+    const int dt = h->dt;
+    if (!conv && (rc = run(h, "rn_ln_stats", 0, [&]() { return launch_rn_ln_stats(d_wav, B, L, rn_stats, st, rn_xn, h->rn_Lp, h->rn_gamma, h->rn_beta, dt, sinc_x3); }))) return rc;
+    int T = h->rn_T1;
+    void *x = off(h->rn_buf[0], b0 * per_utt, e), *pre = off(h->rn_buf[1], b0 * per_utt, e), *hb = off(h->rn_buf[2], b0 * per_utt, e),
+         *o = off(h->rn_buf[3], b0 * per_utt, e), *sc = off(h->rn_buf[4], b0 * per_utt, e), *xn = off(h->rn_buf[5], b0 * per_utt, e);
+    // developer hook (option rn_stop): return after N residual blocks (0: after the front-end) with x exposed as stage "rn_x"; the
+    // unfused kernel sequence runs, whose storage points are those of the fused kernels
+    const int stop_after = h->opt.rn_stop;
+    // developer hook (tests): SVHIP_RN_SNAP=2 keeps a copy of lrelu(bn1(x)) as block 2 will read it — the first tensor that both the
+    // fused 128-channel blocks and the separate kernel sequence materialise — as stage "rn_snap"
+    const int snap_at = h->opt.rn_snap;
+    auto snapshot = [&](const void* src, int Tn, int Cn) -> int {
+        const size_t bytes = (size_t)B * Tn * Cn * e;
+        if (h->rn_snap_cap < bytes) {
+            void* q = nullptr;
+            SV_HIP(h, hipMalloc(&q, bytes));
+            h->allocs.push_back(q);
+            h->rn_snap = q; h->rn_snap_cap = bytes;
+        }
+        SV_HIP(h, hipMemcpyAsync(h->rn_snap, src, bytes, hipMemcpyDeviceToDevice, st));
+        h->rn_snap_T = Tn; h->rn_snap_C = Cn;
+        return SVHIP_OK;
+    };
+    // F32X3: will block `bn` (entered with Tn frames) run its convolutions on the 128 x 128 split kernel (r2_step.hip modes 1 / 2)?  Its
+    // producer then writes lrelu(bn1(x)) straight in the S32 layout (pre_is_s32) instead of fp32
+    auto x3_step_block = [&](int bn, int Tn) {
+        if (bn > 7 || !h->x3 || h->opt.rn_step_off || stop_after >= 0 || snap_at >= 0) return false;
+        const svhip_handle::RnBlock& Kn = h->rn_blocks[bn];
+        return Kn.cin % 32 == 0 && Kn.cout % 128 == 0 && Kn.conv1.Ws32 && Kn.conv2.Ws32 && (!Kn.has_shortcut || Kn.shortcut.Ws32) && Tn >= 2;
+    };
+    bool pre_is_s32 = false;
+    // (the split front-end writes block 0's pre-activation itself, in the S32 layout, when block 0 runs on the split convolution kernel)
+    const bool sinc_pre = sinc_x3 && x3_step_block(0, T);
+    if (sinc_pre) pre_is_s32 = true;
+    // bf16 / fp16 handles: the fused chain's first block computes the conv front-end itself from the waveform (rn_block128's CONV
+    // form) and x is never stored; option rn_conv_unfused stores x with rn_conv3_front and runs the plain block (bit-identical)
+    const bool fuse_ok = bf && stop_after < 0 && !h->opt.rn_unfused;
+    const svhip_handle::RnBlock& K0 = h->rn_blocks[0];
+    const bool conv_fused = conv && fuse_ok && !h->opt.rn_conv_unfused &&
+                            rn_block128_supported(K0.cin, K0.cout, T, K0.downsample, K0.has_shortcut, K0.conv1.Kp, K0.conv2.Kp);
+    if (conv) {
+        if (!conv_fused && (rc = run(h, "rn_conv3_front", 2.0 * B * 128.0 * 3.0 * T, [&]() { return launch_rn_conv3_front(d_wav, h->rn_cw, x, dt, B, L, T, st); })))
+            return rc;
+    } else if ((rc = run(h, "rn_sinc", 2.0 * B * 128.0 * 251.0 * (L - 250), [&]() {
+             // (the kernel can also write block 0's pre-activation, but its 8-byte scattered stores make that as dear as the
+             //  separate coalesced rn_bn_act pass: measured 0.85 + 0.29 ms either way)
+             if (sinc_x3) return launch_rn_sinc_x3(h->rn_filt_x3, h->rn_fbn_scale, h->rn_fbn_shift, reinterpret_cast<float*>(x), B, L, T, rn_xn, h->rn_Lp, h->num_cu, st,
+                                                   sinc_pre ? pre : nullptr, h->rn_blocks[0].bn1_scale, h->rn_blocks[0].bn1_shift);
+             // fp16 handles: the symmetric form of the sinc convolution (K = 126 instead of 251; option rn_sinc_full keeps round 5's kernel)
+             const bool sym = h->f16 && h->rn_filt_sym && !h->opt.rn_sinc_full;
+             return launch_rn_sinc(d_wav, rn_stats, h->rn_gamma, h->rn_beta, sym ? h->rn_filt_sym : h->rn_filt, h->rn_fbn_scale, h->rn_fbn_shift, x, dt, B, L, T, st,
+                                   nullptr, nullptr, nullptr, rn_xn, h->rn_Lp, h->num_cu, sym);
+         }))) return rc;
+    h->rn_dbg_x = x; h->rn_dbg_T = T; h->rn_dbg_C = 128;
+    if (stop_after == 0) return SVHIP_OK;
+    // bf16: the 128 -> 128 pooled blocks (layer1, layer2) each run as ONE fused kernel + the AFMS gate kernel; the gate of
+    // block i is applied by block i + 1 on the way in (or by the rn_afms_apply pass in front of the first GEMM block)
+    int first = 0;
+    const bool no_tail = h->opt.rn_unfused != 0;                        // (tests: the separate passes against the fused tail)
+    const float *g_alpha = nullptr, *g_gate = nullptr;          // pending gate of the previous fused block
+    const void* xin = x;
+    for (; fuse_ok && first < 8; ++first) {
+        svhip_handle::RnBlock& K = h->rn_blocks[first];
+        if (!rn_block128_supported(K.cin, K.cout, T, K.downsample, K.has_shortcut, K.conv1.Kp, K.conv2.Kp)) break;
+        RnBlock128Params bp;
+        bp.xin = reinterpret_cast<const bf16_t*>(xin);
+        bp.alpha = g_alpha; bp.gate = g_gate;
+        bp.bn1_scale = K.bn1_scale; bp.bn1_shift = K.bn1_shift;
+        bp.W1 = reinterpret_cast<const bf16_t*>(K.conv1.W); bp.bn2_scale = K.conv1.scale; bp.bn2_shift = K.conv1.shift;
+        bp.W2 = reinterpret_cast<const bf16_t*>(K.conv2.W);
+        void* dst = (first & 1) ? hb : o;                        // ping-pong: never the buffer being read
+        bp.opool = reinterpret_cast<bf16_t*>(dst);
+        bp.colsum = rn_part;
+        bp.B = B; bp.T = T; bp.Tout = T / 3; bp.ntiles = rn_block128_ntiles(T); bp.f16 = h->f16 ? 1 : 0;
+        const bool from_wave = first == 0 && conv_fused;
+        if (from_wave) { bp.xin = nullptr; bp.wav = d_wav; bp.cw = h->rn_cw; bp.L = L; }
+        const double fl = (double)B * T * (K.conv1.flops_per_row + K.conv2.flops_per_row + (from_wave ? 2.0 * 128 * 3 : 0.0));
+        if ((rc = run(h, from_wave ? "rn_block128_conv" : "rn_block128", fl, [&]() { return launch_rn_block128(bp, h->num_cu, st); }))) return rc;
+        float* gate = rn_gate[first & 1];                        // two gate buffers: block i + 1 reads i's while writing its own
+        if ((rc = run(h, "rn_afms_gate", 2.0 * B * K.cout * K.cout, [&]() {
+                 return launch_rn_afms_gate(rn_part, rn_block128_nparts(B, bp.T, h->num_cu), B, K.cout, bp.Tout, K.afms_fcT, K.afms_fc.bias, gate, st);
+             }))) return rc;
+        T /= 3;
+        xin = dst;
+        g_alpha = K.alpha; g_gate = gate;
+    }
+    if (first > 0) {
+        // x = (o + alpha) * gate and, in the same pass, the next consumer's lrelu(bn(x))
+        svhip_handle::RnBlock& Kp = h->rn_blocks[first - 1];
+        const float* nsc = first < 8 ? h->rn_blocks[first].bn1_scale : h->rn_agg_scale;
+        const float* nsh = first < 8 ? h->rn_blocks[first].bn1_shift : h->rn_agg_shift;
+        // x itself is read only as an identity shortcut (or as a debug stage): not written when the next block projects its input
+        void* xdst = (first < 8 && h->rn_blocks[first].has_shortcut && stop_after < 0) ? nullptr : x;
+        if ((rc = run(h, "rn_afms_apply", 0, [&]() { return launch_rn_afms_apply(xin, xdst, dt, Kp.alpha, g_gate, B, T, Kp.cout, st, nsc, nsh, pre, 0.3f); }))) return rc;
+        h->rn_dbg_x = x; h->rn_dbg_T = T; h->rn_dbg_C = Kp.cout;
+        if (snap_at == first && b0 == 0 && (rc = snapshot(pre, T, Kp.cout))) return rc;
+    }
+    for (int bi = first; bi < 8; ++bi) {
+        svhip_handle::RnBlock& K = h->rn_blocks[bi];
+        const int M = B * T;
+        // out = lrelu(bn1(x))                                                         RawNet_baseline.py:222
+        // (blocks 1..7 get it from the previous block's AFMS pass, which writes x and lrelu(bn1(x)) together)
+        if (((bi == 0 && first == 0) || stop_after >= 0) && !(bi == 0 && sinc_pre)) {
+            pre_is_s32 = x3_step_block(bi, T);
+            if ((rc = run(h, "rn_bn_act", 0, [&]() { return launch_rn_bn_act(x, pre, dt, K.bn1_scale, K.bn1_shift, M, K.cin, 0.3f, st, pre_is_s32); }))) return rc;
+        }
+        // conv1 -> bn2 -> lrelu (epilogue), conv2 + shortcut                            :224-226
+        // A 1 x 1 shortcut rides in conv2's GEMM as extra K columns when the 256 x 256 kernel takes it (no shortcut tensor in HBM)
+        const bool fold_sc = K.has_shortcut && K.conv2sc_W && !no_tail && conv2sc_fits(h, K, pre, hb, o, M, T);
+        const void* resid = x;                                                       // identity shortcut takes the pre-BN x (:223)
+        const void* resid_in_tail = nullptr;
+        const bool tail_fused = !no_tail && rn_tail_supported(dt, K.downsample ? T / 3 : T, K.cout);
+        // F32X3: the block's convolutions (and its projection shortcut) on the 128 x 128 split kernel (r2_step.hip, modes 1 / 2) — pre in the
+        // S32 layout, conv1's output stays S32 (conv2's operand), conv2 adds the shortcut on the way out.  (Otherwise they run on the tiled
+        // kernel that splits its fp32 operands in registers: 170 - 190 TFLOP/s.)
+        bool pooled_by_conv = false;
+        const bool x3_step = h->x3 && !h->opt.rn_step_off && K.cin % 32 == 0 && K.cout % 128 == 0 && K.conv1.Ws32 && K.conv2.Ws32 &&
+                             (!K.has_shortcut || K.shortcut.Ws32) && T >= 2;
+        auto project_shortcut = [&]() { return conv_gemm(h, K.shortcut, conv_params(h, K.shortcut, pre, K.cin, sc, K.cout, M, h->T)); };
+        if (K.has_shortcut && !fold_sc && !x3_step) {
+            if ((rc = project_shortcut())) return rc;
+            resid = sc;
+        }
+        if (pre_is_s32 && !x3_step) SV_FAIL(h, SVHIP_ERR_STATE, "RawNet2 block %d: split pre-activation without the split convolution route", bi);
+        if (x3_step) {
+            void* const split_dst = K.has_shortcut ? xn : sc;      // (fp32 pre: its S32 copy goes to a buffer that is free here — the next-x buffer when `sc` holds the projected shortcut)
+            GemmParams q1 = conv_params(h, K.conv1, pre_is_s32 ? pre : split_dst, K.cin, hb, K.cout, M, T);      // conv1: pre (S32) -> lrelu(bn2(.)) in S32
+            q1.W = K.conv1.Ws32; q1.x3 = 2; q1.pad_mode = PAD_ZERO; q1.zero_page = h->d_zeros;
+            GemmParams q2 = q1;                              // conv2: h (S32) -> fp32, + the shortcut (identity x, or the projected one)
+            q2.A = hb; q2.lda = K.cout; q2.cin = K.cout; q2.K = 3 * K.cout; q2.Kp = q2.K; q2.W = K.conv2.Ws32; q2.scale = nullptr; q2.shift = nullptr;
+            q2.Y = o; q2.out_f32 = 1; q2.R = reinterpret_cast<const float*>(K.has_shortcut ? sc : x); q2.ldr = K.cout;
+            GemmParams q0 = q1;                              // projection shortcut (k = 1) of pre -> fp32, into the spare activation buffer
+            q0.W = K.shortcut.Ws32; q0.taps = 1; q0.K = K.cin; q0.Kp = K.cin; q0.scale = nullptr; q0.shift = nullptr; q0.Y = sc; q0.out_f32 = 1;
+            const bool ok = rn_step_supported(q1, 1) && rn_step_supported(q2, 2) && (!K.has_shortcut || rn_step_supported(q0, 2));
+            if (ok) {
+                if (!pre_is_s32 && (rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(reinterpret_cast<const float*>(pre), K.cin, split_dst, M, K.cin, st); }))) return rc;
+                if (K.has_shortcut && (rc = run(h, "rn_step", (double)M * K.shortcut.flops_per_row, [&]() { return launch_rn_step(q0, 2, st); }))) return rc;
+                if ((rc = run(h, "rn_step", (double)M * K.conv1.flops_per_row, [&]() { return launch_rn_step(q1, 1, st); }))) return rc;
+                // (a pooled block whose tail is not the fused kernel — the long utterances of layers 1 - 3: conv2 pools on its way out)
+                pooled_by_conv = K.downsample && !tail_fused && T >= 3 && !h->opt.rn_pool_off && rn_step_supported(q2, 3);
+                if ((rc = run(h, "rn_step", (double)M * K.conv2.flops_per_row, [&]() { return launch_rn_step(q2, pooled_by_conv ? 3 : 2, st); }))) return rc;
+                goto convs_done;
+            }
+            if (pre_is_s32) SV_FAIL(h, SVHIP_ERR_STATE, "RawNet2 block %d: the split convolution kernel refused a shape its producer was told it takes", bi);
+            if (K.has_shortcut && !fold_sc) {               // (the tiled route after all: its projection shortcut)
+                if ((rc = project_shortcut())) return rc;
+                resid = sc;
+            }
+        }
+        {
+            GemmParams p1 = conv_params(h, K.conv1, pre, K.cin, hb, K.cout, M, T);
+            p1.act2 = ACT_LRELU03; p1.pad_mode = PAD_ZERO;
+            if ((rc = conv_gemm(h, K.conv1, p1))) return rc;
+        }
+        if (fold_sc) {
+            GemmParams p = conv2sc_params(h, K, pre, hb, o, M, T);
+            const char* lbl = "gemm_pw2_conv";
+            char shaped2[96];
+            if (h->opt.layer_labels) { snprintf(shaped2, sizeof(shaped2), "%s M%d N%d K%d+%d", lbl, M, K.cout, K.conv2.K, K.cin); lbl = shaped2; }
+            if ((rc = run(h, lbl, (double)M * (K.conv2.flops_per_row + K.shortcut.flops_per_row), [&]() { return launch_gemm(p, true, st); }))) return rc;
+        } else {
+            // identity shortcut: with the fused block tail and conv2 on the persistent conv-gather kernel (which has no residual
+            // operand) the tail adds the block input; otherwise conv2's epilogue does
+            if (!K.has_shortcut && tail_fused && bf && conv_cv_persistent(h, K.conv2, hb, K.cout, M, T, PAD_ZERO)) { resid_in_tail = x; resid = nullptr; }
+            GemmParams p2 = conv_params(h, K.conv2, hb, K.cout, o, K.cout, M, T);
+            p2.pad_mode = PAD_ZERO; p2.R = resid; p2.ldr = resid ? K.cout : 0;
+            if ((rc = conv_gemm(h, K.conv2, p2))) return rc;
+        }
+    convs_done:
+        // AFMS gate; the same pass writes the next consumer's lrelu(bn(.)): block bi+1's bn1, or the aggregation BN after block 7
+        const float* nsc = bi < 7 ? h->rn_blocks[bi + 1].bn1_scale : h->rn_agg_scale;
+        const float* nsh = bi < 7 ? h->rn_blocks[bi + 1].bn1_shift : h->rn_agg_shift;
+        void* npre = stop_after >= 0 ? nullptr : pre;           // (the developer hook keeps the unfused sequence)
+        // the block output itself is read only by an identity shortcut of the next block (or as a debug stage)
+        const bool x_dead = stop_after < 0 && npre && (bi == 7 || h->rn_blocks[bi + 1].has_shortcut);
+        const int Tn = K.downsample ? T / 3 : T;
+        if (tail_fused) {
+            // max-pool + AFMS + next pre-activation in one launch, the pooled activation held in registers      :228-229, :62-68
+            const bool tail_s32 = npre && x3_step_block(bi + 1, Tn);      // (F32X3: the next block's operand straight in the S32 layout)
+            char tl[48] = "rn_tail";
+            if (h->opt.layer_labels) snprintf(tl, sizeof(tl), "rn_tail T%d C%d", T, K.cout);
+            if ((rc = run(h, tl, 2.0 * B * K.cout * K.cout, [&]() {
+                     // (small batches: slice sums in rn_scratch, the gate in rn_gate[0]; option rn_tail_big keeps one workgroup per utterance)
+                     const bool sliced = !h->opt.rn_tail_big;
+                     return launch_rn_tail(o, x_dead ? nullptr : xn, npre, dt, K.downsample, K.alpha, K.afms_fcT, K.afms_fc.bias, nsc, nsh, B, T, K.cout, 0.3f, st,
+                                           resid_in_tail, sliced ? rn_scratch : nullptr, sliced ? rn_gate[0] : nullptr, h->num_cu, tail_s32);
+                 }))) return rc;
+            pre_is_s32 = tail_s32;
+            T = Tn;
+        } else {
+            void* y = o;
+            if (K.downsample && pooled_by_conv) {                                        // (F32X3: conv2 pooled on its way out, into o)
+                T /= 3;
+            } else if (K.downsample) {                                                   // :228-229
+                if ((rc = run(h, "rn_maxpool3", 0, [&]() { return launch_rn_maxpool3(o, hb, dt, B, T, K.cout, st); }))) return rc;
+                T /= 3;
+                y = hb;
+            }
+            // AFMS: (y + alpha) * sigmoid(fc(mean_t y))                                     :62-68
+            if ((rc = run(h, "rn_afms_mean", 0, [&]() { return launch_colmean(y, dt, K.cout, B, T, K.cout, rn_mean, st, rn_scratch, 16); }))) return rc;
+            if ((rc = run(h, "rn_afms_gate", 2.0 * B * K.cout * K.cout, [&]() {
+                     return launch_rn_afms_gate(rn_mean, 1, B, K.cout, 1, K.afms_fcT, K.afms_fc.bias, rn_gate[0], st);
+                 }))) return rc;
+            // (F32X3: when the next block runs on the split convolution kernel its pre-activation is written in the S32 layout right here)
+            const bool next_s32 = npre && x3_step_block(bi + 1, T);
+            if ((rc = run(h, "rn_afms_apply", 0, [&]() { return launch_rn_afms_apply(y, x_dead ? nullptr : xn, dt, K.alpha, rn_gate[0], B, T, K.cout, st, nsc, nsh, npre, 0.3f, next_s32); }))) return rc;
+            pre_is_s32 = next_s32;
+        }
+        std::swap(x, xn);
+        h->rn_dbg_x = x; h->rn_dbg_T = T; h->rn_dbg_C = K.cout;
+        if (stop_after == bi + 1) return SVHIP_OK;
+        if (snap_at == bi + 1 && b0 == 0 && npre && (rc = snapshot(npre, T, K.cout))) return rc;
+    }
+    // aggregation: attentive statistics pooling                                          RawNet2_custom.py:215-224
+    const int M = B * T;
+    // (pre = lrelu(bn_before_agg(x)) came out of block 7's AFMS pass)
+    // (1 x 1 layers, like the projection shortcut, are given the handle's T: no frame index enters a pointwise GEMM without column sums or bias_utt)
+    GemmParams pa = conv_params(h, h->rn_att0, pre, 512, hb, 128, M, h->T);
+    pa.act1 = ACT_LRELU001;
+    if ((rc = conv_gemm(h, h->rn_att0, pa))) return rc;
+    float* rn_logits = h->rn_logits + (size_t)b0 * T * 512;
+    GemmParams pl = conv_params(h, h->rn_att3, hb, 128, rn_logits, 512, M, h->T);
+    pl.out_f32 = 1;
+    if ((rc = conv_gemm(h, h->rn_att3, pl))) return rc;
+    if ((rc = run(h, "rn_attn_pool", 0, [&]() { return launch_rn_attn_pool(rn_logits, pre, dt, B, T, 512, rn_pooled, st); }))) return rc;
+    if ((rc = run(h, "rn_fc", 2.0 * B * h->rn_fc.N * h->rn_fc.K, [&]() {
+             // (16-bit handles, full batches: the K-split MFMA form — fp32-grade handles keep ONE kernel for every batch size here)
+             return launch_rowvec_linear(rn_pooled, 1024, h->rn_fc.W, h->rn_fc.bias, d_emb, c.embed_dim, B, c.embed_dim, 1024, ACT_NONE, st,
+                                         h->bf16 && h->d_lin_part ? h->d_lin_part + (size_t)b0 * h->lin_part_per_utt : nullptr, true);
+         }))) return rc;
+    return SVHIP_OK;
+}
+
+// whole batch: one slice, or `lanes` slices on as many streams, so that the small and under-filled kernels of one slice (the late
+// blocks are grids of 86 - 400 workgroups, the AFMS passes are latency-bound) run beside the big ones of another
+int rawnet2_forward(svhip_handle* h, const float* d_wav, int B) {
+    const int lanes = (h->lanes > 1 && B >= 16 * h->lanes && h->opt.rn_stop < 0) ? h->lanes : 1;
+    return forward_lanes(h, rawnet2_forward_part, d_wav, B, lanes, ((B + lanes - 1) / lanes + 3) & ~3);
+}
+
+}  // namespace svhip

@@ -1,0 +1,531 @@
+// api_scoring.hip — scoring, AS-norm and verification metrics entry points of libsvhip (see include/svhip.h).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "handle.h"
+
+using namespace svhip;
+
+extern "C" {
+
+// ---- scoring ------------------------------------------------------------------------------------------
+namespace {
+// a scratch slot of at least `bytes` (grown by half again; the old block is freed only after the stream has drained)
+int scratch(svhip_handle* h, int slot, size_t bytes, void** out) {
+    if (h->scr_cap[slot] < bytes || !h->scr[slot]) {
+        if (h->scr[slot]) { SV_HIP(h, hipStreamSynchronize(h->stream)); if (h->aux_stream) SV_HIP(h, hipStreamSynchronize(h->aux_stream)); (void)hipFree(h->scr[slot]); h->scr[slot] = nullptr; h->scr_cap[slot] = 0; }
+        const size_t cap = std::max<size_t>(bytes + bytes / 2, 256);
+        if (hipMalloc(&h->scr[slot], cap) != hipSuccess) {
+            if (hipMalloc(&h->scr[slot], std::max<size_t>(bytes, 256)) != hipSuccess) { h->scr[slot] = nullptr; SV_FAIL(h, SVHIP_ERR_NOMEM, "scratch slot %d: %zu bytes", slot, bytes); }
+            h->scr_cap[slot] = std::max<size_t>(bytes, 256);
+        } else {
+            h->scr_cap[slot] = cap;
+        }
+    }
+    *out = h->scr[slot];
+    return SVHIP_OK;
+}
+// Scratch retention policy: the slab of the AS-norm slab path (up to 2 GiB) and the staging copies of HOST-pointer calls
+// (N x D x 4 bytes for the embedding matrix) are released at the end of the call once they exceed 256 MiB — they would otherwise sit
+// beside the model engines' workspaces for the life of the process-wide scoring handle.  The slots of the device-resident fast path
+// (candidate lists, cohort planes: re-used every call) stay; svhip_trim_scratch frees everything.
+void release_big_scratch(svhip_handle* h, bool staged_host) {
+    const size_t cap = (size_t)256 << 20;
+    auto drop = [&](int slot) {
+        if (h->scr[slot] && h->scr_cap[slot] > cap) {
+            (void)hipStreamSynchronize(h->stream);
+            if (h->aux_stream) (void)hipStreamSynchronize(h->aux_stream);
+            (void)hipFree(h->scr[slot]);
+            h->scr[slot] = nullptr; h->scr_cap[slot] = 0;
+        }
+    };
+    drop(svhip_handle::SCR_SLAB);
+    if (staged_host)
+        for (int s_ : {svhip_handle::SCR_IN0, svhip_handle::SCR_IN1, svhip_handle::SCR_IN2, svhip_handle::SCR_IN3, svhip_handle::SCR_IN4,
+                       svhip_handle::SCR_OUT0, svhip_handle::SCR_OUT1, svhip_handle::SCR_OUT2, svhip_handle::SCR_SPLIT}) drop(s_);
+}
+struct TempBuf {      // device staging for host-pointer calls, in a scratch slot of the handle
+    svhip_handle* h; int slot;
+    int in(const void* src, size_t bytes, bool is_dev, const void** out) {
+        if (is_dev) { *out = src; return SVHIP_OK; }
+        void* d;
+        if (int rc = scratch(h, slot, bytes, &d)) return rc;
+        SV_HIP(h, hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, h->stream));
+        *out = d;
+        return SVHIP_OK;
+    }
+    int out(void* dst, size_t bytes, bool is_dev, void** o) {
+        if (is_dev) { *o = dst; return SVHIP_OK; }
+        return scratch(h, slot, bytes, o);
+    }
+};
+}  // namespace
+
+int svhip_l2norm(svhip_handle* h, float* E, int64_t N, int32_t D, int32_t flags) {
+    if (!h || !E || N < 0 || D <= 0) return SVHIP_ERR_INVALID;
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    const bool dev = flags & SVHIP_IN_DEVICE;
+    TempBuf t{h, svhip_handle::SCR_IN0};
+    const void* d;
+    int rc = t.in(E, (size_t)N * D * 4, dev, &d);
+    if (rc) return rc;
+    float* de = const_cast<float*>(reinterpret_cast<const float*>(d));
+    if ((rc = run(h, "l2norm", 0, [&]() { return launch_l2norm(de, N, D, h->stream); }))) return rc;
+    if (!dev) SV_HIP(h, hipMemcpyAsync(E, de, (size_t)N * D * 4, hipMemcpyDeviceToHost, h->stream));
+    if (!dev || !(flags & SVHIP_ASYNC)) SV_HIP(h, hipStreamSynchronize(h->stream));
+    return SVHIP_OK;
+}
+
+static int pairs_common(svhip_handle* h, int mode, const float* E, int64_t N, int32_t D, const float* mu, const float* sigma,
+                        const int32_t* ia, const int32_t* ib, int64_t P, float* out, int32_t flags) {
+    if (!h || !E || !ia || !ib || !out || N <= 0 || D <= 0 || P < 0) return SVHIP_ERR_INVALID;
+    if (mode == 1 && (!mu || !sigma)) return SVHIP_ERR_INVALID;
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
+    if (!din) {   // host indices are range-checked before they reach the GPU
+        for (int64_t p = 0; p < P; ++p)
+            if (ia[p] < 0 || ia[p] >= N || ib[p] < 0 || ib[p] >= N) SV_FAIL(h, SVHIP_ERR_INVALID, "pair %lld indexes outside [0, %lld)", (long long)p, (long long)N);
+    }
+    TempBuf tE{h, svhip_handle::SCR_IN0}, tA{h, svhip_handle::SCR_IN1}, tB{h, svhip_handle::SCR_IN2}, tM{h, svhip_handle::SCR_IN3},
+        tS{h, svhip_handle::SCR_IN4}, tO{h, svhip_handle::SCR_OUT0};
+    const void *dE, *dA, *dB, *dM = nullptr, *dS = nullptr;
+    void* dO;
+    int rc;
+    if ((rc = tE.in(E, (size_t)N * D * 4, din, &dE))) return rc;
+    if ((rc = tA.in(ia, (size_t)P * 4, din, &dA))) return rc;
+    if ((rc = tB.in(ib, (size_t)P * 4, din, &dB))) return rc;
+    if (mode == 1) {
+        if ((rc = tM.in(mu, (size_t)N * 4, din, &dM))) return rc;
+        if ((rc = tS.in(sigma, (size_t)N * 4, din, &dS))) return rc;
+    }
+    if ((rc = tO.out(out, (size_t)P * 4, dout, &dO))) return rc;
+    if (mode == 0)
+        rc = run(h, "score_pairs", 2.0 * P * D, [&]() { return launch_score_pairs((const float*)dE, D, (const int32_t*)dA, (const int32_t*)dB, P, (float*)dO, h->stream); });
+    else
+        rc = run(h, "asnorm_pairs", 2.0 * P * D, [&]() { return launch_asnorm_pairs((const float*)dE, D, (const float*)dM, (const float*)dS, (const int32_t*)dA, (const int32_t*)dB, P, (float*)dO, h->stream); });
+    if (rc) return rc;
+    if (!dout) SV_HIP(h, hipMemcpyAsync(out, dO, (size_t)P * 4, hipMemcpyDeviceToHost, h->stream));
+    if (!(din && dout && (flags & SVHIP_ASYNC))) SV_HIP(h, hipStreamSynchronize(h->stream));
+    return SVHIP_OK;
+}
+
+int svhip_score_pairs(svhip_handle* h, const float* E, int64_t N, int32_t D, const int32_t* ia, const int32_t* ib, int64_t P,
+                      float* out, int32_t flags) {
+    return pairs_common(h, 0, E, N, D, nullptr, nullptr, ia, ib, P, out, flags);
+}
+
+int svhip_asnorm_pairs(svhip_handle* h, const float* E, int64_t N, int32_t D, const float* mu, const float* sigma,
+                       const int32_t* ia, const int32_t* ib, int64_t P, float* out, int32_t flags) {
+    return pairs_common(h, 1, E, N, D, mu, sigma, ia, ib, P, out, flags);
+}
+
+static int score_trials_impl(svhip_handle* h, int32_t mode, float pexp, const float* F, int64_t n_files, int32_t n_crops, int32_t D, const int32_t* ia,
+                       const int32_t* ib, int64_t P, float* out, int32_t flags) {
+    if (!h || !F || !ia || !ib || !out || n_files <= 0 || n_crops <= 0 || D <= 0 || P < 0) return SVHIP_ERR_INVALID;
+    if (mode < SVHIP_TRIAL_COSINE || mode > SVHIP_TRIAL_PDIST) SV_FAIL(h, SVHIP_ERR_INVALID, "unknown trial scoring mode %d", mode);
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
+    if (!din)
+        for (int64_t p = 0; p < P; ++p)
+            if (ia[p] < 0 || ia[p] >= n_files || ib[p] < 0 || ib[p] >= n_files) SV_FAIL(h, SVHIP_ERR_INVALID, "trial %lld indexes outside [0, %lld)", (long long)p, (long long)n_files);
+    TempBuf tF{h, svhip_handle::SCR_IN0}, tA{h, svhip_handle::SCR_IN1}, tB{h, svhip_handle::SCR_IN2}, tO{h, svhip_handle::SCR_OUT0};
+    const void *dF, *dA, *dB;
+    void* dO;
+    int rc;
+    if ((rc = tF.in(F, (size_t)n_files * n_crops * D * 4, din, &dF))) return rc;
+    if ((rc = tA.in(ia, (size_t)P * 4, din, &dA))) return rc;
+    if ((rc = tB.in(ib, (size_t)P * 4, din, &dB))) return rc;
+    if ((rc = tO.out(out, (size_t)P * 4, dout, &dO))) return rc;
+    if ((rc = run(h, "score_trials", 2.0 * P * n_crops * D, [&]() {
+             return launch_trial_crops(mode, pexp, (const float*)dF, n_crops, D, (const int32_t*)dA, (const int32_t*)dB, P, (float*)dO, h->stream);
+         }))) return rc;
+    if (!dout) SV_HIP(h, hipMemcpyAsync(out, dO, (size_t)P * 4, hipMemcpyDeviceToHost, h->stream));
+    if (!(din && dout && (flags & SVHIP_ASYNC))) SV_HIP(h, hipStreamSynchronize(h->stream));
+    return SVHIP_OK;
+}
+
+int svhip_score_trials(svhip_handle* h, int32_t mode, const float* F, int64_t n_files, int32_t n_crops, int32_t D, const int32_t* ia,
+                       const int32_t* ib, int64_t P, float* out, int32_t flags) {
+    return score_trials_impl(h, mode, 2.0f, F, n_files, n_crops, D, ia, ib, P, out, flags);
+}
+
+int svhip_score_trials_pnorm(svhip_handle* h, float p, const float* F, int64_t n_files, int32_t n_crops, int32_t D, const int32_t* ia,
+                             const int32_t* ib, int64_t P, float* out, int32_t flags) {
+    if (h && p != p) SV_FAIL(h, SVHIP_ERR_INVALID, "pnorm: p is NaN");
+    return score_trials_impl(h, SVHIP_TRIAL_PNORM, p, F, n_files, n_crops, D, ia, ib, P, out, flags);
+}
+
+int svhip_mean_crops(svhip_handle* h, const float* F, int64_t n_files, int32_t n_crops, int32_t D, float* out, int32_t flags) {
+    if (!h || !F || !out || n_files <= 0 || n_crops <= 0 || D <= 0) return SVHIP_ERR_INVALID;
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
+    TempBuf tF{h, svhip_handle::SCR_IN0}, tO{h, svhip_handle::SCR_OUT0};
+    const void* dF;
+    void* dO;
+    int rc;
+    if ((rc = tF.in(F, (size_t)n_files * n_crops * D * 4, din, &dF))) return rc;
+    if ((rc = tO.out(out, (size_t)n_files * D * 4, dout, &dO))) return rc;
+    if ((rc = run(h, "mean_crops", 0, [&]() { return launch_mean_crops((const float*)dF, n_files, n_crops, D, (float*)dO, h->stream); }))) return rc;
+    if (!dout) SV_HIP(h, hipMemcpyAsync(out, dO, (size_t)n_files * D * 4, hipMemcpyDeviceToHost, h->stream));
+    if (!(din && dout && (flags & SVHIP_ASYNC))) SV_HIP(h, hipStreamSynchronize(h->stream));
+    return SVHIP_OK;
+}
+
+// out (Na, Nb) = A @ B^T.  The route is decided ONCE (split_b and score_gemm used to re-derive it from different predicates):
+//   SCORE_H3W     rows of A in registers, B streamed past them as half planes (asnorm_fused.hip: score_h3w; D = 192 / 256, aligned operands);
+//                 the kernel's launcher fills the planes itself (and scales both operands by exact powers of two)
+//   SCORE_WORDS   the tiled GEMM with B as (hi half << 16 | lo half) words, A split in registers (gemm_pw's x3 form)
+//   SCORE_F32MFMA the exact fp32 MFMA GEMM (option score_f32mfma, or shapes gemm_pw's split form does not take)
+// The split forms run as three fp16 MFMAs per product on every handle since round 4 (a score of unit vectors within ~4e-8 of the float64
+// oracle, the exact fp32 MFMA 3.5e-8) at twice the fp32 matrix rate.
+enum ScoreRoute { SCORE_F32MFMA = 0, SCORE_WORDS = 1, SCORE_H3W = 2 };
+static ScoreRoute score_route(const svhip_handle* h, const float* dA, int64_t Na, const float* dB, int64_t Nb, int D) {
+    if (h->opt.score_f32mfma && !h->x3) return SCORE_F32MFMA;
+    if (!h->opt.score_tiled && score_h3w_supported(D, Na, Nb) && ((reinterpret_cast<uintptr_t>(dA) | reinterpret_cast<uintptr_t>(dB)) & 15) == 0) return SCORE_H3W;
+    return SCORE_WORDS;
+}
+
+static int score_gemm(svhip_handle* h, const char* label, const float* dA, int64_t Na, const float* dB, int64_t Nb, int D, float* dO, int64_t ldo,
+                      ScoreRoute route, const void* dBsplit) {
+    if (D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "embedding dim %d must be a multiple of 32", D);
+    if (Na > (1 << 30) / 1 || Nb > (1 << 30)) SV_FAIL(h, SVHIP_ERR_INVALID, "matrix too large");
+    hipStream_t st = h->stream;
+    if (route == SCORE_H3W) {
+        if (!dBsplit || (reinterpret_cast<uintptr_t>(dA) & 15)) SV_FAIL(h, SVHIP_ERR_STATE, "score route: the row-streaming kernel was chosen without its plane scratch");
+        return run(h, label, 2.0 * Na * Nb * D, [&]() { return launch_score_h3w(dA, Na, dB, Nb, D, dO, ldo, const_cast<void*>(dBsplit), h->num_cu, st); });
+    }
+    GemmParams p;
+    p.A = dA; p.W = dB; p.Y = dO;
+    p.M = (int)Na; p.N = (int)Nb; p.K = D; p.Kp = D; p.Wrows = (int)Nb;
+    p.lda = D; p.ldy = (int)ldo; p.T = 1;
+    if (route == SCORE_WORDS && dBsplit && gemm_pw_supported(p, false)) { p.W = dBsplit; p.x3 = 1; }      // (the words exist: split_b ran launch_split_words)
+    return run(h, label, 2.0 * Na * Nb * D, [&]() { return launch_gemm(p, false, st); });
+}
+
+// the split operand of the chosen route in a scratch slot of the handle: half planes (filled by the row-streaming kernel's own launcher:
+// [2][Nb][D] halves + its scale word) or split words (filled here)
+static int split_b(svhip_handle* h, ScoreRoute route, const float* dB, int64_t Nb, int D, void** out) {
+    *out = nullptr;
+    if (route == SCORE_F32MFMA) return SVHIP_OK;
+    if (int rc = scratch(h, svhip_handle::SCR_SPLIT, std::max((size_t)Nb * D * 4, score_h3w_planes_bytes(D, Nb)), out)) return rc;
+    if (route == SCORE_H3W) return SVHIP_OK;
+    return run(h, "split_words", 0, [&]() { return launch_split_words(dB, *out, Nb * D, h->stream); });
+}
+
+int svhip_score_matrix(svhip_handle* h, const float* A, int64_t Na, const float* B, int64_t Nb, int32_t D, float* out, int32_t flags) {
+    if (!h || !A || !B || !out || Na <= 0 || Nb <= 0 || D <= 0) return SVHIP_ERR_INVALID;
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
+    TempBuf tA{h, svhip_handle::SCR_IN0}, tB{h, svhip_handle::SCR_IN1}, tO{h, svhip_handle::SCR_OUT0};
+    const void *dA, *dB;
+    void* dO;
+    int rc;
+    if ((rc = tA.in(A, (size_t)Na * D * 4, din, &dA))) return rc;
+    if ((rc = tB.in(B, (size_t)Nb * D * 4, din, &dB))) return rc;
+    if ((rc = tO.out(out, (size_t)Na * Nb * 4, dout, &dO))) return rc;
+    void* bsplit = nullptr;
+    const ScoreRoute route = score_route(h, (const float*)dA, Na, (const float*)dB, Nb, D);
+    if ((rc = split_b(h, route, (const float*)dB, Nb, D, &bsplit))) return rc;
+    rc = score_gemm(h, "score_matrix", (const float*)dA, Na, (const float*)dB, Nb, D, (float*)dO, Nb, route, bsplit);
+    if (!rc && !dout) { const hipError_t e = hipMemcpyAsync(out, dO, (size_t)Na * Nb * 4, hipMemcpyDeviceToHost, h->stream); if (e != hipSuccess) rc = SVHIP_ERR_HIP; }
+    if (!(din && dout && (flags & SVHIP_ASYNC))) (void)hipStreamSynchronize(h->stream);
+    return rc;
+}
+
+// the slab path: cohort scores of `rows` embeddings into an HBM scratch (rows x K fp32), slab by slab, reduced per row.
+// Used for shapes the fused kernel does not take (small cohorts, top > 256, other embedding widths, F32X3 handles) and for
+// the embeddings the fused kernel flags.
+static int asnorm_stats_slab(svhip_handle* h, const float* dE, int64_t N, int D, const float* dC, int K, int top, float* dM, float* dS) {
+    const int64_t ldk = (K + 3) & ~3;                             // row stride of the slab (16-byte rows for the DMA GEMM)
+    const int64_t slab_rows = std::min<int64_t>(N, std::max<int64_t>(128, ((int64_t)1 << 31) / (ldk * 4)));
+    void* csplit = nullptr;
+    void* slab = nullptr;
+    int rc;
+    const ScoreRoute route = score_route(h, dE, slab_rows, dC, K, D);       // (every slab starts r0 * D * 4 bytes into E: the same alignment)
+    if ((rc = split_b(h, route, dC, K, D, &csplit))) return rc;
+    if ((rc = scratch(h, svhip_handle::SCR_SLAB, (size_t)slab_rows * ldk * 4, &slab))) return rc;
+    for (int64_t r0 = 0; r0 < N; r0 += slab_rows) {
+        const int64_t rows = std::min(slab_rows, N - r0);
+        rc = score_gemm(h, "asnorm_cohort_gemm", dE + r0 * D, rows, dC, K, D, (float*)slab, ldk, route, csplit);
+        if (!rc) rc = run(h, "asnorm_topk", 0, [&]() { return launch_topk_stats((const float*)slab, rows, K, (int)ldk, top, dM + r0, dS + r0, h->stream); });
+        if (rc) return rc;
+    }
+    return SVHIP_OK;
+}
+
+int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, const float* cohort, int32_t K, int32_t top,
+                       float* mu, float* sigma, int32_t flags) {
+    if (!h || !E || !cohort || !mu || !sigma || N <= 0 || D <= 0 || K <= 0) return SVHIP_ERR_INVALID;
+    if (top < 0) top = K + top;             // python slice semantics of S[:top] (utils.py:143); top=-1 drops the smallest
+    if (top > K) top = K;
+    if (top <= 0) SV_FAIL(h, SVHIP_ERR_INVALID, "top must select at least one cohort score");
+    if (N >= ((int64_t)1 << 31)) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "at most 2^31 - 1 embeddings per call");
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
+    TempBuf tE{h, svhip_handle::SCR_IN0}, tC{h, svhip_handle::SCR_IN1}, tM{h, svhip_handle::SCR_OUT0}, tS{h, svhip_handle::SCR_OUT1};
+    const void *dE, *dC;
+    void *dM, *dS;
+    int rc;
+    if ((rc = tE.in(E, (size_t)N * D * 4, din, &dE))) return rc;
+    if ((rc = tC.in(cohort, (size_t)K * D * 4, din, &dC))) return rc;
+    if ((rc = tM.out(mu, (size_t)N * 4, dout, &dM))) return rc;
+    if ((rc = tS.out(sigma, (size_t)N * 4, dout, &dS))) return rc;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(dE) | reinterpret_cast<uintptr_t>(dC)) & 15) == 0;
+    if (!h->x3 && aligned && asnorm_fused_supported(D, K, top) && !h->opt.asnorm_slab) {
+        // fused path: the scores never leave the MFMA accumulators (csrc/asnorm_fused.hip)
+        // chunks of 131 072 embeddings: the candidate statistics of chunk c run on a second stream under the MFMA kernel of
+        // chunk c + 1 (two candidate buffers; the kernels meet through events)
+        const int64_t chunk = std::min<int64_t>(N, 131072);
+        void *mb, *cand, *cnt, *flag;
+        const size_t mb_bytes = (size_t)(D + 32) * D * 4;          // [MB | slice partials of its computation]
+        const size_t cand_elems = (size_t)chunk * 2 * ASNORM_CAND_PER_LANE, cnt_elems = (size_t)chunk * 4;      // (2 or 4 candidate lists per embedding)
+        // (the exact default is the split form where it is built: scores to fp32 rounding at several times the fp32 matrix rate — two half
+        //  planes / three fp16 MFMAs, D = 192, 256)
+        const bool split = (D == 192 || D == 256) && !h->opt.asnorm_f32mfma;
+        // (split: the candidate kernel takes 1.7 ms of 17 on its own and 7 when it shares the CUs with the matrix kernel: one stream.
+        //  The fp32-MFMA form keeps the second stream: 26.1 - 26.9 against 27.5 ms)
+        const int nbuf = (N > chunk && !split) ? 2 : 1;
+        const size_t mom_bytes = (cohort_moments_scratch_bytes(D) + 255) & ~(size_t)255;
+        if ((rc = scratch(h, svhip_handle::SCR_MB, mb_bytes + mom_bytes + (split ? asnorm_planes_bytes(D, K) : 0), &mb))) return rc;
+        if ((rc = scratch(h, svhip_handle::SCR_CAND, cand_elems * 4 * nbuf, &cand))) return rc;
+        if ((rc = scratch(h, svhip_handle::SCR_CNT, (cnt_elems + (size_t)chunk) * 4 * nbuf, &cnt))) return rc;      // per buffer: [counts (chunk, 4) | row factors (chunk)]
+        if ((rc = scratch(h, svhip_handle::SCR_FLAG, (size_t)(2 * N + 1) * 4, &flag))) return rc;        // [count | flagged ids (N) | their candidate counts (N)]
+        if (nbuf == 2 && !h->aux_stream) {
+            SV_HIP(h, hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
+            for (int i = 0; i < 4; ++i) SV_HIP(h, hipEventCreateWithFlags(&h->aux_ev[i], hipEventDisableTiming));
+        }
+        int32_t* nflag = (int32_t*)flag;                    // [0] = number of flagged embeddings, [1 ..] their indices
+        SV_HIP(h, hipMemsetAsync(nflag, 0, 4, h->stream));
+        if ((rc = run(h, "asnorm_cohort_moments", 0, [&]() { return launch_cohort_moments((const float*)dC, K, D, (float*)mb, (float*)((char*)mb + mb_bytes), h->stream); }))) return rc;
+        AsnormFusedParams fp;
+        fp.cohort = (const float*)dC; fp.K = K; fp.MB = (const float*)mb; fp.z = asnorm_tail_z(K, top);
+        if (split) {
+            void* planes = (char*)mb + mb_bytes + mom_bytes;
+            fp.planes = planes;
+            fp.nlists = 4;                  // the 16-wide-MFMA kernel: four lists per embedding
+            // the kernel scales its operands by exact powers of two (asnorm_fused.hip, "operand scaling"): the cohort's max |x| goes to
+            // a device word behind the two planes (the buffer is sized for three)
+            uint32_t* pscale = reinterpret_cast<uint32_t*>((char*)planes + (size_t)2 * (D + 32 + K) * D * 2);
+            if ((rc = run(h, "asnorm_planes", 0, [&]() { return launch_asnorm_planes((const float*)mb, (const float*)dC, K, D, planes, h->stream, pscale); }))) return rc;
+            fp.pscale = pscale;
+        }
+        int c = 0;
+        for (int64_t r0 = 0; r0 < N; r0 += chunk, ++c) {
+            const int64_t rows = std::min(chunk, N - r0);
+            const int b = c & (nbuf - 1);
+            fp.E = (const float*)dE + r0 * D; fp.N = rows;
+            fp.cand = (float*)cand + b * cand_elems; fp.cnt = (int32_t*)cnt + b * (cnt_elems + (size_t)chunk);
+            fp.rowscale = fp.pscale ? reinterpret_cast<float*>(fp.cnt + cnt_elems) : nullptr;
+            if (nbuf == 2 && c >= 2) SV_HIP(h, hipStreamWaitEvent(h->stream, h->aux_ev[2 + b], 0));       // the statistics of chunk c - 2 have read this buffer
+            if ((rc = run(h, "asnorm_fused", 2.0 * rows * K * D, [&]() { return launch_asnorm_fused(fp, D, h->stream); }))) {
+                if (nbuf == 2 && h->aux_stream) (void)hipStreamSynchronize(h->aux_stream);
+                return rc;
+            }
+            hipStream_t st2 = h->stream;
+            if (nbuf == 2) {
+                SV_HIP(h, hipEventRecord(h->aux_ev[b], h->stream));
+                SV_HIP(h, hipStreamWaitEvent(h->aux_stream, h->aux_ev[b], 0));
+                st2 = h->aux_stream;
+            }
+            h->cur = st2;
+            rc = run(h, "asnorm_cand_stats", 0, [&]() {
+                return launch_asnorm_cand_stats(fp.cand, fp.cnt, rows, top, (float*)dM, (float*)dS, r0, nflag + 1, nflag, st2, fp.nlists, fp.rowscale, nflag + 1 + N);
+            });
+            h->cur = h->stream;
+            if (rc) {           // leave no aux-stream work pending behind a failed call
+                if (nbuf == 2) (void)hipStreamSynchronize(h->aux_stream);
+                return rc;
+            }
+            if (nbuf == 2) SV_HIP(h, hipEventRecord(h->aux_ev[2 + b], h->aux_stream));
+        }
+        if (nbuf == 2) for (int b = 0; b < std::min(c, 2); ++b) SV_HIP(h, hipStreamWaitEvent(h->stream, h->aux_ev[2 + b], 0));
+        int32_t nf = 0;
+        SV_HIP(h, hipMemcpyAsync(&nf, nflag, 4, hipMemcpyDeviceToHost, h->stream));
+        SV_HIP(h, hipStreamSynchronize(h->stream));
+        int64_t refit_rows = 0;
+        int refit_passes = 0;
+        if (nf > 0 && split && !h->opt.asnorm_norefit) {
+            // REFIT (round 6).  tau = mean + z sd with z the normal quantile fits isotropic embeddings; real cohorts are not isotropic
+            // (speaker centroids cluster by gender / language: bimodal cohort scores), and a row whose threshold passes fewer than `top`
+            // scores, or overflows a list, used to take the slab path — N x K scores through HBM.  Such rows now go through the SAME fused
+            // kernel again with a z of their own, derived from what the last pass counted (refit_next_z, asnorm_fused.hip).  At most ASNORM_REFIT_PASSES
+            // passes; what is still undecided after them takes the slab path as before.
+            constexpr int ASNORM_REFIT_PASSES = 3;
+            const float target = fminf(1.6f * (float)top, 0.7f * (float)(2 * ASNORM_CAND_PER_LANE));
+            // everything lives on the device: the state of the undecided rows (asnorm_fused.hip, "refit state": ids, z, the last measurement, the
+            // bracket), the gathered rows, their statistics and the flag list of the pass; the host reads ONE word per pass (how many are left)
+            void* g;
+            const size_t cap = (size_t)nf;
+            const size_t gbytes = cap * D * 4 + cap * 4 * (2 + 6 + 6 + 2) + 256;
+            if ((rc = scratch(h, svhip_handle::SCR_GATHER, gbytes, &g))) return rc;
+            float* gE = (float*)g;
+            float* gM = gE + cap * D;
+            float* gS = gM + cap;
+            float* soa[2] = {gS + cap, gS + cap + 6 * cap};
+            int32_t* gF = (int32_t*)(soa[1] + 6 * cap);      // [0] = count, [1 ..] positions within the gathered list
+            int32_t* gInfo = gF + 1 + cap;                   // (gbytes: + 256 covers the counter word)
+            if ((rc = run(h, "asnorm_refit_state", 0, [&]() { return launch_asnorm_refit_init(nflag + 1, nflag + 1 + N, nf, fp.z, target, soa[0], h->stream); }))) return rc;
+            int cur = nf, a = 0;
+            while (cur > 0 && refit_passes < ASNORM_REFIT_PASSES) {
+                ++refit_passes;
+                const int32_t* gI = reinterpret_cast<const int32_t*>(soa[a]);
+                const float* gZ = soa[a] + cur;
+                SV_HIP(h, hipMemsetAsync(gF, 0, 4, h->stream));
+                if ((rc = run(h, "asnorm_gather", 0, [&]() { return launch_gather_rows((const float*)dE, gI, cur, D, gE, h->stream); }))) return rc;
+                for (int64_t r0 = 0; r0 < cur; r0 += chunk) {
+                    const int64_t rows = std::min<int64_t>(chunk, cur - r0);
+                    fp.E = gE + r0 * D; fp.N = rows; fp.zrow = gZ + r0;
+                    fp.cand = (float*)cand; fp.cnt = (int32_t*)cnt;
+                    fp.rowscale = fp.pscale ? reinterpret_cast<float*>(fp.cnt + cnt_elems) : nullptr;
+                    if ((rc = run(h, "asnorm_fused_refit", 2.0 * rows * K * D, [&]() { return launch_asnorm_fused(fp, D, h->stream); }))) return rc;
+                    if ((rc = run(h, "asnorm_cand_stats", 0, [&]() {
+                            return launch_asnorm_cand_stats(fp.cand, fp.cnt, rows, top, gM, gS, r0, gF + 1, gF, h->stream, fp.nlists, fp.rowscale, gInfo);
+                        }))) return rc;
+                }
+                fp.zrow = nullptr;
+                // (rows that are still undecided scatter whatever their slots hold: a later pass or the slab path overwrites them)
+                if ((rc = run(h, "asnorm_scatter", 0, [&]() { return launch_scatter_stats(gM, gS, gI, cur, (float*)dM, (float*)dS, h->stream); }))) return rc;
+                int32_t left = 0;
+                SV_HIP(h, hipMemcpyAsync(&left, gF, 4, hipMemcpyDeviceToHost, h->stream));
+                SV_HIP(h, hipStreamSynchronize(h->stream));
+                refit_rows += cur - left;
+                // (the flag order is whatever the atomics gave; a row's result does not depend on where it sits in the gathered list)
+                if (left > 0 && (rc = run(h, "asnorm_refit_state", 0, [&]() {
+                                     return launch_asnorm_refit_next(soa[a], cur, gF + 1, gInfo, left, target, soa[a ^ 1], h->stream);
+                                 }))) return rc;
+                a ^= 1;
+                cur = left;
+            }
+            // what the refit passes could not decide: back into the flag list for the slab path
+            nf = cur;
+            if (nf > 0) SV_HIP(h, hipMemcpyAsync(nflag + 1, soa[a], (size_t)nf * 4, hipMemcpyDeviceToDevice, h->stream));
+        }
+        h->last_asnorm_refit = refit_rows;
+        h->last_asnorm_refit_passes = refit_passes;
+        if (nf > 0) {
+            // cohort scores too far from normal for the threshold (fewer than `top` candidates, or a list overflowed) even after the refit
+            // passes: these embeddings are gathered and take the slab path; results are scattered back
+            void* g;
+            const size_t gbytes = (size_t)nf * D * 4 + 2 * (size_t)nf * 4 + 64;
+            if ((rc = scratch(h, svhip_handle::SCR_GATHER, gbytes, &g))) return rc;
+            float* gE = (float*)g;
+            float* gM = gE + (size_t)nf * D;
+            float* gS = gM + nf;
+            if ((rc = run(h, "asnorm_gather", 0, [&]() { return launch_gather_rows((const float*)dE, nflag + 1, nf, D, gE, h->stream); }))) return rc;
+            if ((rc = asnorm_stats_slab(h, gE, nf, D, (const float*)dC, K, top, gM, gS))) return rc;
+            if ((rc = run(h, "asnorm_scatter", 0, [&]() { return launch_scatter_stats(gM, gS, nflag + 1, nf, (float*)dM, (float*)dS, h->stream); }))) return rc;
+        }
+        h->last_asnorm_flagged = nf;
+    } else {
+        if ((rc = asnorm_stats_slab(h, (const float*)dE, N, D, (const float*)dC, K, top, (float*)dM, (float*)dS))) return rc;
+        h->last_asnorm_flagged = -1;
+        h->last_asnorm_refit = 0; h->last_asnorm_refit_passes = 0;
+    }
+    if (!dout) {
+        SV_HIP(h, hipMemcpyAsync(mu, dM, (size_t)N * 4, hipMemcpyDeviceToHost, h->stream));
+        SV_HIP(h, hipMemcpyAsync(sigma, dS, (size_t)N * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (!(din && dout && (flags & SVHIP_ASYNC))) {
+        SV_HIP(h, hipStreamSynchronize(h->stream));
+        release_big_scratch(h, !din || !dout);
+    }
+    return SVHIP_OK;
+}
+
+int64_t svhip_asnorm_last_fallback(const svhip_handle* h) { return h ? h->last_asnorm_flagged : -1; }
+int64_t svhip_asnorm_last_refit(const svhip_handle* h, int32_t* passes) {
+    if (passes) *passes = h ? h->last_asnorm_refit_passes : 0;
+    return h ? h->last_asnorm_refit : 0;
+}
+
+// ---- verification metrics (metrics.hip) ------------------------------------------------------------------------------------
+namespace {
+// shared front half: stage scores / labels, sort, scan.  Labels must be 0 / 1 (host labels are checked).
+struct MetricsRun {
+    svhip_handle* h;
+    TempBuf tS{nullptr, svhip_handle::SCR_IN0}, tL{nullptr, svhip_handle::SCR_IN1};
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    explicit MetricsRun(svhip_handle* hh) : h(hh) { tS.h = hh; tL.h = hh; }
+    int start(const float* scores, const int32_t* labels, int64_t P, bool din, bool nan_to_num, const char* label) {
+        if (P >= ((int64_t)1 << 31)) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "trial lists are limited to 2^31 - 1 entries");
+        if (!din)
+            for (int64_t i = 0; i < P; ++i)
+                if (labels[i] != 0 && labels[i] != 1) SV_FAIL(h, SVHIP_ERR_INVALID, "label %lld of trial %lld is not 0 / 1", (long long)labels[i], (long long)i);
+        SV_HIP(h, hipSetDevice(h->cfg.device));
+        const void *dS, *dL;
+        int rc;
+        if ((rc = tS.in(scores, (size_t)P * 4, din, &dS))) return rc;
+        if ((rc = tL.in(labels, (size_t)P * 4, din, &dL))) return rc;
+        ws_bytes = metrics_workspace_bytes(P);
+        if ((rc = scratch(h, svhip_handle::SCR_WS, ws_bytes, &ws))) return rc;
+        return run(h, label, 0, [&]() { return metrics_sort_scan((const float*)dS, (const int32_t*)dL, P, nan_to_num, ws, ws_bytes, h->stream); });
+    }
+};
+}  // namespace
+
+int svhip_roc_points(svhip_handle* h, const float* scores, const int32_t* labels, int64_t P, int64_t* n_out, float* thr, int64_t* fps,
+                     int64_t* tps, int32_t flags) {
+    if (!h || !scores || !labels || !n_out || !thr || !fps || !tps || P <= 0) return SVHIP_ERR_INVALID;
+    const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
+    MetricsRun m(h);
+    int rc;
+    if ((rc = m.start(scores, labels, P, din, true, "metrics_sort"))) return rc;
+    TempBuf tT{h, svhip_handle::SCR_OUT0}, tF{h, svhip_handle::SCR_OUT1}, tP{h, svhip_handle::SCR_OUT2};
+    void *dT, *dF, *dP;
+    if ((rc = tT.out(thr, (size_t)P * 4, dout, &dT)) || (rc = tF.out(fps, (size_t)P * 8, dout, &dF)) || (rc = tP.out(tps, (size_t)P * 8, dout, &dP))) return rc;
+    int32_t* n_dev = nullptr;
+    if ((rc = run(h, "metrics_roc", 0, [&]() { return metrics_roc_points(P, m.ws, m.ws_bytes, (float*)dT, (int64_t*)dF, (int64_t*)dP, &n_dev, h->stream); }))) return rc;
+    int32_t n32 = 0;
+    SV_HIP(h, hipMemcpyAsync(&n32, n_dev, 4, hipMemcpyDeviceToHost, h->stream));
+    SV_HIP(h, hipStreamSynchronize(h->stream));
+    *n_out = n32;
+    if (!dout) {
+        SV_HIP(h, hipMemcpy(thr, dT, (size_t)n32 * 4, hipMemcpyDeviceToHost));
+        SV_HIP(h, hipMemcpy(fps, dF, (size_t)n32 * 8, hipMemcpyDeviceToHost));
+        SV_HIP(h, hipMemcpy(tps, dP, (size_t)n32 * 8, hipMemcpyDeviceToHost));
+    }
+    return SVHIP_OK;
+}
+
+int svhip_error_rates(svhip_handle* h, const float* scores, const int32_t* labels, int64_t P, double* fnrs, double* fprs, float* thresholds,
+                      int32_t flags) {
+    if (!h || !scores || !labels || !fnrs || !fprs || !thresholds || P <= 0) return SVHIP_ERR_INVALID;
+    const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
+    MetricsRun m(h);
+    int rc;
+    if ((rc = m.start(scores, labels, P, din, false, "metrics_sort"))) return rc;
+    TempBuf tA{h, svhip_handle::SCR_OUT0}, tB{h, svhip_handle::SCR_OUT1}, tC{h, svhip_handle::SCR_OUT2};
+    void *dA, *dB, *dC;
+    if ((rc = tA.out(fnrs, (size_t)P * 8, dout, &dA)) || (rc = tB.out(fprs, (size_t)P * 8, dout, &dB)) || (rc = tC.out(thresholds, (size_t)P * 4, dout, &dC))) return rc;
+    if ((rc = run(h, "metrics_rates", 0, [&]() { return metrics_error_rates(P, m.ws, m.ws_bytes, (double*)dA, (double*)dB, (float*)dC, h->stream); }))) return rc;
+    if (!dout) {
+        SV_HIP(h, hipMemcpyAsync(fnrs, dA, (size_t)P * 8, hipMemcpyDeviceToHost, h->stream));
+        SV_HIP(h, hipMemcpyAsync(fprs, dB, (size_t)P * 8, hipMemcpyDeviceToHost, h->stream));
+        SV_HIP(h, hipMemcpyAsync(thresholds, dC, (size_t)P * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    SV_HIP(h, hipStreamSynchronize(h->stream));
+    return SVHIP_OK;
+}
+
+int svhip_min_dcf(svhip_handle* h, const float* scores, const int32_t* labels, int64_t P, double p_target, double c_miss, double c_fa,
+                  double* min_dcf, float* threshold, int32_t flags) {
+    if (!h || !scores || !labels || !min_dcf || !threshold || P <= 0) return SVHIP_ERR_INVALID;
+    MetricsRun m(h);
+    int rc;
+    if ((rc = m.start(scores, labels, P, flags & SVHIP_IN_DEVICE, false, "metrics_sort"))) return rc;
+    void* res = nullptr;
+    if ((rc = scratch(h, svhip_handle::SCR_OUT0, 16, &res))) return rc;
+    rc = run(h, "metrics_min_dcf", 0, [&]() { return metrics_min_dcf(P, m.ws, m.ws_bytes, p_target, c_miss, c_fa, (double*)res, (float*)((char*)res + 8), h->stream); });
+    char host[16];
+    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(host, res, 16, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (rc) return rc;
+    SV_HIP(h, e);
+    memcpy(min_dcf, host, 8);
+    memcpy(threshold, host + 8, 4);
+    return SVHIP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,709 @@
+// api_weights.hip — weight loading of libsvhip: front-end tables, expected weight names / shapes, weight packing, the workspace.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "handle.h"
+
+namespace svhip {
+
+static inline uint16_t f32_to_f16_rne(float f) {      // IEEE half, round to nearest even (the host compiler's _Float16 conversion)
+    const _Float16 hv = static_cast<_Float16>(f);
+    uint16_t u;
+    memcpy(&u, &hv, 2);
+    return u;
+}
+
+static inline uint16_t f32_to_bf16_rne(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+// host twin of common.h's x3_hi / x3_lo: a weight as (hi << 16) | lo in the planes' type (IEEE half; bf16 under -DSVHIP_X3_BF16)
+static inline uint32_t x3_split_word(float v) {
+#ifdef SVHIP_X3_BF16
+    const uint16_t hi = f32_to_bf16_rne(v);
+    uint32_t hu = (uint32_t)hi << 16;
+    float hf; memcpy(&hf, &hu, 4);
+    return hu | f32_to_bf16_rne(v - hf);
+#else
+    const _Float16 h = static_cast<_Float16>(v);                 // (plain conversions: overflow -> inf, NaN stays NaN — common.h, RANGE)
+    const _Float16 l = static_cast<_Float16>(v - static_cast<float>(h));
+    uint16_t hb, lb;
+    memcpy(&hb, &h, 2); memcpy(&lb, &l, 2);
+    return ((uint32_t)hb << 16) | lb;
+#endif
+}
+
+// a weight in the handle's 16-bit storage type
+static inline uint16_t to_h16(const svhip_handle* h, float f) { return h->f16 ? f32_to_f16_rne(f) : f32_to_bf16_rne(f); }
+
+// ---- front-end tables (oracle/fbank.py restates the same constants) --------------------------------
+static double hz_to_mel(double f) {
+    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = std::log(6.4) / 27.0;
+    return f >= min_log_hz ? min_log_mel + std::log(f / min_log_hz) / logstep : f / f_sp;
+}
+static double mel_to_hz(double m) {
+    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = std::log(6.4) / 27.0;
+    return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m;
+}
+
+int build_fbank_tables(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    FbankTables& fb = h->fb;
+    fb.n_fft = c.n_fft; fb.win_length = c.win_length; fb.hop = c.hop_length; fb.n_mels = c.n_mels;
+    fb.n_bins = c.n_fft / 2 + 1;
+    fb.lpad = (c.n_fft - c.win_length) / 2;
+    fb.n_pairs = (fb.n_bins + 31) / 32;
+    fb.n_q = c.win_length / 8;
+    fb.preemph = c.preemph;
+    if (c.win_length % 8 != 0 || c.hop_length % 4 != 0 || fb.n_pairs > 9 || c.win_length > c.n_fft)
+        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "fbank geometry n_fft=%d win=%d hop=%d not supported", c.n_fft, c.win_length, c.hop_length);
+    const double PI = 3.14159265358979323846;
+    // periodic Hamming (scipy get_window('hamming', win, fftbins=True)), cast to float32
+    std::vector<float> win(c.win_length);
+    for (int k = 0; k < c.win_length; ++k) win[k] = (float)(0.54 - 0.46 * std::cos(2.0 * PI * k / c.win_length));
+    // basis[q][pair][part][lane] float4: tap = 8q + 4h + j, bin = 32*pair + r (lane = 32h + r); part 0 = cos, 1 = sin
+    std::vector<float> basis((size_t)fb.n_q * fb.n_pairs * 2 * 64 * 4, 0.0f);
+    for (int q = 0; q < fb.n_q; ++q)
+        for (int pr = 0; pr < fb.n_pairs; ++pr)
+            for (int part = 0; part < 2; ++part)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int j = 0; j < 4; ++j) {
+                        const int r = lane & 31, hh = lane >> 5;
+                        const int tap = 8 * q + 4 * hh + j, bin = 32 * pr + r;
+                        float v = 0.0f;
+                        if (bin < fb.n_bins) {
+                            const double ang = 2.0 * PI * (double)bin * (double)(fb.lpad + tap) / (double)c.n_fft;
+                            const float tr = (float)(part == 0 ? std::cos(ang) : std::sin(ang));
+                            v = tr * win[tap];                       // float32 product, as nnAudio's kernel * window mask
+                        }
+                        basis[((((size_t)q * fb.n_pairs + pr) * 2 + part) * 64 + lane) * 4 + j] = v;
+                    }
+    // bf16x3 tables: the same windowed taps split into bf16 hi + lo, k-steps of 16 (zero padded)
+    fb.n_k16 = (c.win_length + 15) / 16;
+    fb.split_bf16 = (h->bf16 && c.hop_length % 8 == 0) ? 1 : 0;
+    fb.split6 = (h->x3 && c.hop_length % 8 == 0) ? 1 : 0;          // F32X3 handles: the exact three-way split, six products
+    if (fb.split_bf16 || fb.split6) {
+        std::vector<uint16_t> bhi((size_t)fb.n_k16 * fb.n_pairs * 2 * 64 * 8, 0), blo(bhi.size(), 0), bl3(bhi.size(), 0);
+        for (int kk = 0; kk < fb.n_k16; ++kk)
+            for (int pr = 0; pr < fb.n_pairs; ++pr)
+                for (int part = 0; part < 2; ++part)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int j = 0; j < 8; ++j) {
+                            const int r = lane & 31, hh = lane >> 5;
+                            const int tap = 16 * kk + 8 * hh + j, bin = 32 * pr + r;
+                            float v = 0.0f;
+                            if (bin < fb.n_bins && tap < c.win_length) {
+                                const double ang = 2.0 * PI * (double)bin * (double)(fb.lpad + tap) / (double)c.n_fft;
+                                v = (float)(part == 0 ? std::cos(ang) : std::sin(ang)) * win[tap];
+                            }
+                            const uint16_t hi = f32_to_bf16_rne(v);
+                            uint32_t hu = (uint32_t)hi << 16;
+                            float hf; memcpy(&hf, &hu, 4);
+                            const size_t idx = ((((size_t)kk * fb.n_pairs + pr) * 2 + part) * 64 + lane) * 8 + j;
+                            bhi[idx] = hi;
+                            blo[idx] = f32_to_bf16_rne(v - hf);
+                            uint32_t mu = (uint32_t)blo[idx] << 16;
+                            float mf; memcpy(&mf, &mu, 4);
+                            bl3[idx] = f32_to_bf16_rne((v - hf) - mf);
+                        }
+        uint16_t *dh, *dl;
+        int rc2;
+        if ((rc2 = dev_upload(h, &dh, bhi))) return rc2;
+        if ((rc2 = dev_upload(h, &dl, blo))) return rc2;
+        fb.basis_hi = dh; fb.basis_lo = dl;
+        if (fb.split6) {
+            uint16_t* d3;
+            if ((rc2 = dev_upload(h, &d3, bl3))) return rc2;
+            fb.basis_l3 = d3;
+        }
+    }
+    // the fused front-end of bf16 handles (fbank.hip, round 6): the window is symmetric about tap win / 2, so Re X_k / Im X_k are products of
+    // K = win / 2 + 1 taps with w_m cos(2 pi k m / n_fft) / w_m sin(2 pi k m / n_fft), m = 0 .. win / 2 (slot win / 2 carries the unpaired tap 0)
+    if (h->bf16 && c.n_fft == 512 && c.win_length == 200 && c.hop_length == 80) {
+        const int half = c.win_length / 2, nks = 7, npr = 8;
+        std::vector<uint16_t> shi((size_t)nks * npr * 2 * 64 * 8, 0), slo(shi.size(), 0);
+        for (int kk = 0; kk < nks; ++kk)
+            for (int pr = 0; pr < npr; ++pr)
+                for (int part = 0; part < 2; ++part)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int j = 0; j < 8; ++j) {
+                            const int r = lane & 31, hh = lane >> 5;
+                            const int m = 16 * kk + 8 * hh + j, bin = 32 * pr + r;
+                            float v = 0.0f;
+                            if (m <= half && bin < fb.n_bins) {
+                                const float w = m < half ? win[half + m] : win[0];
+                                const double ang = 2.0 * PI * (double)bin * (double)m / (double)c.n_fft;
+                                v = (float)(part == 0 ? std::cos(ang) : std::sin(ang)) * w;
+                            }
+                            const uint16_t hi = f32_to_bf16_rne(v);
+                            uint32_t hu = (uint32_t)hi << 16;
+                            float hf; memcpy(&hf, &hu, 4);
+                            const size_t idx = ((((size_t)kk * npr + pr) * 2 + part) * 64 + lane) * 8 + j;
+                            shi[idx] = hi;
+                            slo[idx] = f32_to_bf16_rne(v - hf);
+                        }
+        uint16_t *dh, *dl;
+        int rc2;
+        if ((rc2 = dev_upload(h, &dh, shi))) return rc2;
+        if ((rc2 = dev_upload(h, &dl, slo))) return rc2;
+        fb.sym_hi = dh; fb.sym_lo = dl;
+    }
+    // Slaney mel bank (librosa 0.7 filters.mel(htk=False, norm=1)) in double, stored float32, sparse rows
+    const double sr = c.fb_sr;
+    const double fmax = c.fmax > 0 ? c.fmax : sr / 2;
+    const int nm = c.n_mels, nb = fb.n_bins;
+    std::vector<double> mel_f(nm + 2), fftf(nb);
+    for (int i = 0; i < nb; ++i) fftf[i] = (sr / 2) * i / (double)(nb - 1);
+    const double m0 = hz_to_mel(c.fmin), m1 = hz_to_mel(fmax);
+    for (int i = 0; i < nm + 2; ++i) mel_f[i] = mel_to_hz(m0 + (m1 - m0) * i / (double)(nm + 1));
+    std::vector<float> mw;
+    std::vector<int> mstart(nm), mlen(nm), moff(nm);
+    for (int i = 0; i < nm; ++i) {
+        const double fd0 = mel_f[i + 1] - mel_f[i], fd1 = mel_f[i + 2] - mel_f[i + 1];
+        const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
+        int first = -1, last = -1;
+        std::vector<float> row(nb);
+        for (int k = 0; k < nb; ++k) {
+            const double lower = -(mel_f[i] - fftf[k]) / fd0, upper = (mel_f[i + 2] - fftf[k]) / fd1;
+            const float w32 = (float)std::fmax(0.0, std::fmin(lower, upper));
+            row[k] = (float)((double)w32 * enorm);
+            if (row[k] != 0.0f) { if (first < 0) first = k; last = k; }
+        }
+        if (first < 0) { first = 0; last = -1; }
+        mstart[i] = first; mlen[i] = last - first + 1; moff[i] = (int)mw.size();
+        for (int k = first; k <= last; ++k) mw.push_back(row[k]);
+    }
+    if (mw.empty()) mw.push_back(0.0f);
+    float* d_basis; float* d_mw; int *d_ms, *d_ml, *d_mo;
+    int rc;
+    if ((rc = dev_upload(h, &d_basis, basis))) return rc;
+    if ((rc = dev_upload(h, &d_mw, mw))) return rc;
+    if ((rc = dev_upload(h, &d_ms, mstart))) return rc;
+    if ((rc = dev_upload(h, &d_ml, mlen))) return rc;
+    if ((rc = dev_upload(h, &d_mo, moff))) return rc;
+    fb.n_melw = (int)mw.size();
+    fb.mel_max_bin = 0;
+    for (int i = 0; i < nm; ++i) fb.mel_max_bin = std::max(fb.mel_max_bin, mstart[i] + mlen[i] - 1);
+    fb.basis = d_basis; fb.mel_w = d_mw; fb.mel_start = d_ms; fb.mel_len = d_ml; fb.mel_off = d_mo;
+    return SVHIP_OK;
+}
+
+// ---- expected weight names / shapes ----------------------------------------------------------------
+const int ECAPA_K[5] = {5, 3, 3, 3, 1};
+const int ECAPA_D[5] = {1, 2, 3, 4, 1};
+
+static void ecapa_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec) {
+    const int64_t C = c.channels, C3 = 3 * C, nm = c.n_mels;
+    auto bn = [&](const std::string& p, int64_t n) {
+        spec[p + ".weight"] = {n}; spec[p + ".bias"] = {n}; spec[p + ".running_mean"] = {n};
+        spec[p + ".running_var"] = {n}; spec[p + ".num_batches_tracked"] = {};
+    };
+    auto tdnn = [&](const std::string& p, int64_t cin, int64_t cout, int64_t k) {
+        spec[p + ".conv.conv.weight"] = {cout, cin, k}; spec[p + ".conv.conv.bias"] = {cout};
+        bn(p + ".norm.norm", cout);
+    };
+    if (c.input_norm) { spec["instance_norm.weight"] = {nm}; spec["instance_norm.bias"] = {nm}; }
+    tdnn("blocks.0", nm, C, ECAPA_K[0]);
+    for (int i = 1; i <= 3; ++i) {
+        const std::string p = "blocks." + std::to_string(i);
+        tdnn(p + ".tdnn1", C, C, 1);
+        for (int j = 0; j < 7; ++j) tdnn(p + ".res2net_block.blocks." + std::to_string(j), C / 8, C / 8, ECAPA_K[i]);
+        tdnn(p + ".tdnn2", C, C, 1);
+        spec[p + ".se_block.conv1.conv.weight"] = {128, C, 1}; spec[p + ".se_block.conv1.conv.bias"] = {128};
+        spec[p + ".se_block.conv2.conv.weight"] = {C, 128, 1}; spec[p + ".se_block.conv2.conv.bias"] = {C};
+    }
+    tdnn("mfa", C3, C3, 1);
+    tdnn("asp.tdnn", 3 * C3, 128, 1);
+    spec["asp.conv.conv.weight"] = {C3, 128, 1}; spec["asp.conv.conv.bias"] = {C3};
+    bn("asp_bn.norm", 2 * C3);
+    spec["fc.conv.weight"] = {(int64_t)c.embed_dim, 2 * C3, 1}; spec["fc.conv.bias"] = {(int64_t)c.embed_dim};
+}
+
+const int RN_LAYERS[6] = {1, 1, 1, 2, 1, 2};                   // RawNet2_custom.py:231
+
+const int RN_FILTERS[6] = {128, 128, 256, 256, 512, 512};      // RawNet2_custom.py:232
+
+static void rawnet2_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec) {
+    auto bn = [&](const std::string& p, int64_t n) {
+        spec[p + ".weight"] = {n}; spec[p + ".bias"] = {n}; spec[p + ".running_mean"] = {n};
+        spec[p + ".running_var"] = {n}; spec[p + ".num_batches_tracked"] = {};
+    };
+    if (c.model == SVHIP_MODEL_RAWNET2_CONV) {          // conv1 = Conv1d(1, 128, 3, stride=3) with bias (RawNet2_custom.py:45-52)
+        spec["conv1.weight"] = {128, 1, 3}; spec["conv1.bias"] = {128};
+    } else {
+        spec["ln.gamma"] = {(int64_t)c.samples}; spec["ln.beta"] = {(int64_t)c.samples};
+        spec["first_conv.low_hz_"] = {128, 1}; spec["first_conv.band_hz_"] = {128, 1};
+        bn("first_bn", 128);
+    }
+    int64_t inpl = 128;
+    for (int li = 0; li < 6; ++li)
+        for (int b = 0; b < RN_LAYERS[li]; ++b) {
+            const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
+            const int64_t planes = RN_FILTERS[li];
+            bn(p + ".bn1", inpl);
+            spec[p + ".conv1.weight"] = {planes, inpl, 3};
+            bn(p + ".bn2", planes);
+            spec[p + ".conv2.weight"] = {planes, planes, 3};
+            spec[p + ".afms.alpha"] = {planes, 1};
+            spec[p + ".afms.fc.weight"] = {planes, planes}; spec[p + ".afms.fc.bias"] = {planes};
+            if (inpl != planes) spec[p + ".shortcut.0.weight"] = {planes, inpl, 1};
+            inpl = planes;
+        }
+    bn("bn_before_agg", 512);
+    spec["attention.0.weight"] = {128, 512, 1}; spec["attention.0.bias"] = {128};
+    bn("attention.2", 128);
+    spec["attention.3.weight"] = {512, 128, 1}; spec["attention.3.bias"] = {512};
+    spec["fc.weight"] = {(int64_t)c.embed_dim, 1024}; spec["fc.bias"] = {(int64_t)c.embed_dim};
+}
+
+void model_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec) {
+    if (c.model == SVHIP_MODEL_ECAPA) ecapa_spec(c, spec);
+    else if (is_rawnet2(c.model)) rawnet2_spec(c, spec);
+}
+
+static const HostTensor* getw(svhip_handle* h, const std::string& name) {
+    auto it = h->host_w.find(name);
+    return it == h->host_w.end() ? nullptr : &it->second;
+}
+
+// fold BatchNorm1d(eval, eps=1e-5) into scale / shift (double arithmetic on the host)
+static int make_bn(svhip_handle* h, const std::string& p, int n, float** scale, float** shift) {
+    const HostTensor *w = getw(h, p + ".weight"), *b = getw(h, p + ".bias"), *rm = getw(h, p + ".running_mean"),
+                     *rv = getw(h, p + ".running_var");
+    if (!w || !b || !rm || !rv) SV_FAIL(h, SVHIP_ERR_MISSING, "missing BatchNorm tensors for %s", p.c_str());
+    std::vector<float> sc(n), sh(n);
+    for (int i = 0; i < n; ++i) {
+        const double s = (double)w->data[i] / std::sqrt((double)rv->data[i] + 1e-5);
+        sc[i] = (float)s;
+        sh[i] = (float)((double)b->data[i] - (double)rm->data[i] * s);
+    }
+    int rc;
+    if ((rc = dev_upload(h, scale, sc))) return rc;
+    return dev_upload(h, shift, sh);
+}
+
+// pack conv weight (N, cin, taps) columns [c_lo, c_hi) -> [Np][Kp], k = tap*cin' + c
+static int make_conv(svhip_handle* h, ConvLayer& L, const std::string& wname, const std::string& bname, const std::string& bnname,
+                     int dil, int c_lo = 0, int c_hi = -1) {
+    const HostTensor* w = getw(h, wname);
+    if (!w) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %s", wname.c_str());
+    const int N = (int)w->shape[0], cin_full = (int)w->shape[1], taps = (int)w->shape[2];
+    if (c_hi < 0) c_hi = cin_full;
+    const int cin = c_hi - c_lo;
+    const int bk = gemm_bk(h->bf16);
+    L.N = N; L.taps = taps; L.dil = dil; L.cin = cin; L.K = taps * cin;
+    L.Kp = round_up(L.K, bk); L.Np = round_up(N, GEMM_BN);
+    L.flops_per_row = 2.0 * N * L.K;
+    std::vector<float> packed((size_t)L.Np * L.Kp, 0.0f);
+    for (int n = 0; n < N; ++n)
+        for (int t = 0; t < taps; ++t)
+            for (int c = 0; c < cin; ++c)
+                packed[(size_t)n * L.Kp + t * cin + c] = w->data[((size_t)n * cin_full + (c_lo + c)) * taps + t];
+    int rc;
+    if (h->bf16) {
+        std::vector<uint16_t> pb(packed.size());
+        for (size_t i = 0; i < packed.size(); ++i) pb[i] = to_h16(h, packed[i]);
+        uint16_t* d;
+        if ((rc = dev_upload(h, &d, pb))) return rc;
+        L.W = d;
+    } else {
+        float* d;
+        if ((rc = dev_upload(h, &d, packed))) return rc;
+        L.W = d;
+        if (h->x3) {
+            std::vector<uint32_t> ws(packed.size());
+            for (size_t i = 0; i < packed.size(); ++i) ws[i] = x3_split_word(packed[i]);      // (hi plane << 16) | lo plane, x3_t of common.h
+            uint32_t* dsplit;
+            if ((rc = dev_upload(h, &dsplit, ws))) return rc;
+            L.Wsplit = dsplit;
+            // pointwise GELU layers (gemm_pw3's X3 form) and the Res2Net convolutions (its R2 form: N == cin, k = 3)
+            if ((taps == 1 && N % 256 == 0 && L.K == L.Kp && L.K % 64 == 0 && L.K >= 128) ||
+                (taps == 3 && N == cin && (cin == 64 || cin == 128) && L.K == L.Kp) ||
+                // RawNet2's convolutions and projection shortcuts (r2_step.hip, modes 1 / 2)
+                (is_rawnet2(h->cfg.model) && (taps == 1 || taps == 3) && N % 128 == 0 && cin % 32 == 0 && L.K == L.Kp && L.K == taps * cin)) {
+                std::vector<uint16_t> s32((size_t)N * L.K * 2);
+                for (int n = 0; n < N; ++n)
+                    for (int k = 0; k < L.K; ++k) {
+                        const uint32_t wv = ws[(size_t)n * L.Kp + k];
+                        const size_t o = (size_t)n * L.K * 2 + (size_t)(k >> 5) * 64 + (k & 31);
+                        s32[o] = (uint16_t)(wv >> 16);
+                        s32[o + 32] = (uint16_t)(wv & 0xffffu);
+                    }
+                uint16_t* d32;
+                if ((rc = dev_upload(h, &d32, s32))) return rc;
+                L.Ws32 = d32;
+            }
+            if (taps >= 3 && taps <= 7 && (taps & 1) && N % 256 == 0 && N != cin) {      // the conv-gather X3 form (gemm_pw3cv)
+                const int ccv = round_up(cin, 32), kcv = round_up(taps * ccv, 64);
+                // the first convolution of the network meets features of whatever magnitude the checkpoint was trained on: weights fitted to
+                // int16-scaled mel power are ~1e-10 — below the half planes' resolution.  Outside the ordinary range the planes hold sw * W,
+                // sw an exact power of two (max |w| -> [64, 128)); the kernel multiplies back together with the input's scale (GemmParams::in_scale)
+                float wmax = 0.0f;
+                for (int n = 0; n < N; ++n)
+                    for (int k = 0; k < L.K; ++k) { const float a = std::fabs(packed[(size_t)n * L.Kp + k]); if (std::isfinite(a) && a > wmax) wmax = a; }
+                float sw = 1.0f;
+                if (wmax > 0.0f && !(wmax >= 0x1p-8f && wmax < 0x1p13f)) { int e2; (void)std::frexp(wmax, &e2); sw = std::ldexp(1.0f, 7 - e2); }
+                L.cv_wscale = sw;
+                std::vector<uint16_t> s32((size_t)N * kcv * 2, 0);
+                for (int n = 0; n < N; ++n)
+                    for (int t = 0; t < taps; ++t)
+                        for (int c = 0; c < cin; ++c) {
+                            const uint32_t wv = sw == 1.0f ? ws[(size_t)n * L.Kp + t * cin + c] : x3_split_word(packed[(size_t)n * L.Kp + t * cin + c] * sw);
+                            const int k = t * ccv + c;
+                            const size_t o = (size_t)n * kcv * 2 + (size_t)(k >> 5) * 64 + (k & 31);
+                            s32[o] = (uint16_t)(wv >> 16);
+                            s32[o + 32] = (uint16_t)(wv & 0xffffu);
+                        }
+                uint16_t* dcv;
+                if ((rc = dev_upload(h, &dcv, s32))) return rc;
+                L.Wcv = dcv; L.cv_cin = ccv; L.cv_Kp = kcv;
+            }
+        }
+    }
+    if (!bname.empty()) {
+        const HostTensor* b = getw(h, bname);
+        if (!b) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %s", bname.c_str());
+        if ((rc = dev_upload(h, &L.bias, b->data))) return rc;
+    }
+    if (!bnname.empty()) return make_bn(h, bnname, N, &L.scale, &L.shift);
+    return SVHIP_OK;
+}
+
+static int make_tdnn(svhip_handle* h, ConvLayer& L, const std::string& p, int dil) {
+    return make_conv(h, L, p + ".conv.conv.weight", p + ".conv.conv.bias", p + ".norm.norm", dil);
+}
+
+// fp32 linear from a (N, K, 1) or (N, K) tensor, optional column range
+static int make_linear(svhip_handle* h, LinearLayer& L, const std::string& wname, const std::string& bname, int c_lo = 0, int c_hi = -1) {
+    const HostTensor* w = getw(h, wname);
+    if (!w) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %s", wname.c_str());
+    const int N = (int)w->shape[0], Kfull = (int)w->shape[1];
+    if (c_hi < 0) c_hi = Kfull;
+    L.N = N; L.K = c_hi - c_lo;
+    std::vector<float> m((size_t)N * L.K);
+    for (int n = 0; n < N; ++n)
+        for (int k = 0; k < L.K; ++k) m[(size_t)n * L.K + k] = w->data[(size_t)n * Kfull + c_lo + k];
+    int rc;
+    if ((rc = dev_upload(h, &L.W, m))) return rc;
+    if (!bname.empty()) {
+        const HostTensor* b = getw(h, bname);
+        if (!b) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %s", bname.c_str());
+        if ((rc = dev_upload(h, &L.bias, b->data))) return rc;
+    }
+    return SVHIP_OK;
+}
+
+int finalize_ecapa(svhip_handle* h) {
+    const int C = h->cfg.channels, C3 = 3 * C;
+    int rc;
+    if ((rc = make_tdnn(h, h->blocks0, "blocks.0", ECAPA_D[0]))) return rc;
+    for (int i = 1; i <= 3; ++i) {
+        const std::string p = "blocks." + std::to_string(i);
+        if ((rc = make_tdnn(h, h->tdnn1[i - 1], p + ".tdnn1", 1))) return rc;
+        for (int j = 0; j < 7; ++j)
+            if ((rc = make_tdnn(h, h->res2[i - 1][j], p + ".res2net_block.blocks." + std::to_string(j), ECAPA_D[i]))) return rc;
+        if ((rc = make_tdnn(h, h->tdnn2[i - 1], p + ".tdnn2", 1))) return rc;
+        if ((rc = make_linear(h, h->se1[i - 1], p + ".se_block.conv1.conv.weight", p + ".se_block.conv1.conv.bias"))) return rc;
+        if ((rc = make_linear(h, h->se2[i - 1], p + ".se_block.conv2.conv.weight", p + ".se_block.conv2.conv.bias"))) return rc;
+        {
+            const HostTensor* w2 = getw(h, p + ".se_block.conv2.conv.weight");      // (C, 128, 1)
+            std::vector<float> t((size_t)128 * C);
+            for (int c = 0; c < C; ++c)
+                for (int n = 0; n < 128; ++n) t[(size_t)n * C + c] = w2->data[(size_t)c * 128 + n];
+            if ((rc = dev_upload(h, &h->se2T[i - 1], t))) return rc;
+            if (h->bf16) {
+                const HostTensor* w1 = getw(h, p + ".se_block.conv1.conv.weight");  // (128, C, 1)
+                std::vector<uint16_t> b1v((size_t)128 * C), b2v((size_t)128 * C);
+                for (size_t k = 0; k < b1v.size(); ++k) { b1v[k] = f32_to_bf16_rne(w1->data[k]); b2v[k] = f32_to_bf16_rne(t[k]); }
+                for (int which = 0; which < 2; ++which) {
+                    void* d = nullptr;
+                    SV_HIP(h, hipMalloc(&d, b1v.size() * 2));
+                    h->allocs.push_back(d);
+                    SV_HIP(h, hipMemcpy(d, which ? b2v.data() : b1v.data(), b1v.size() * 2, hipMemcpyHostToDevice));
+                    (which ? h->se2T_bf[i - 1] : h->se1_bf[i - 1]) = d;
+                }
+            }
+        }
+    }
+    if ((rc = make_tdnn(h, h->mfa, "mfa", 1))) return rc;
+    // asp.tdnn over cat[x, mean, std]: the x columns go through the GEMM, the time-constant columns
+    // become a per-utterance bias (ctx) computed by a small linear layer.
+    if ((rc = make_conv(h, h->asp_tdnn, "asp.tdnn.conv.conv.weight", "", "asp.tdnn.norm.norm", 1, 0, C3))) return rc;
+    if ((rc = make_linear(h, h->asp_ctx, "asp.tdnn.conv.conv.weight", "asp.tdnn.conv.conv.bias", C3, 3 * C3))) return rc;
+    if ((rc = make_conv(h, h->asp_conv, "asp.conv.conv.weight", "asp.conv.conv.bias", "", 1))) return rc;
+    if ((rc = make_bn(h, "asp_bn.norm", 2 * C3, &h->aspbn_scale, &h->aspbn_shift))) return rc;
+    if ((rc = make_linear(h, h->fc, "fc.conv.weight", "fc.conv.bias"))) return rc;
+    if (h->cfg.input_norm) {
+        const HostTensor *w = getw(h, "instance_norm.weight"), *b = getw(h, "instance_norm.bias");
+        if (!w || !b) SV_FAIL(h, SVHIP_ERR_MISSING, "missing instance_norm tensors");
+        if ((rc = dev_upload(h, &h->in_w, w->data))) return rc;
+        if ((rc = dev_upload(h, &h->in_b, b->data))) return rc;
+    }
+    // algorithmic FLOPs per utterance: 2 x MACs of every conv / linear (SURVEY §8d counts the same)
+    const double T = h->T;
+    double f = T * h->blocks0.flops_per_row + T * h->mfa.flops_per_row + T * h->asp_conv.flops_per_row;
+    f += T * 2.0 * 128 * (3.0 * C3);                                  // asp.tdnn over the full 9C input, as the reference computes it
+    for (int i = 0; i < 3; ++i) {
+        f += T * (h->tdnn1[i].flops_per_row + h->tdnn2[i].flops_per_row);
+        for (int j = 0; j < 7; ++j) f += T * h->res2[i][j].flops_per_row;
+        f += 2.0 * h->se1[i].N * h->se1[i].K + 2.0 * h->se2[i].N * h->se2[i].K;
+    }
+    f += 2.0 * h->fc.N * h->fc.K;
+    h->flops_per_utt = f;
+    return SVHIP_OK;
+}
+
+static int upload_f32(svhip_handle* h, const std::string& name, float** dst) {
+    const HostTensor* t = getw(h, name);
+    if (!t) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %s", name.c_str());
+    return dev_upload(h, dst, t->data);
+}
+
+// sinc band-pass filters baked once per weight load (RawNet_baseline.py:313-318,339-357), float32 arithmetic
+static int bake_sinc(svhip_handle* h) {
+    const HostTensor *lo = getw(h, "first_conv.low_hz_"), *bd = getw(h, "first_conv.band_hz_");
+    if (!lo || !bd) SV_FAIL(h, SVHIP_ERR_MISSING, "missing sinc parameters");
+    const int NF = 128, KS = 251, HALF = 125;
+    const float sr = 16000.0f, min_low = 50.0f, min_band = 50.0f;
+    const float PI = 3.14159265358979323846f;
+    std::vector<float> win(HALF), n_(HALF);
+    for (int i = 0; i < HALF; ++i) {
+        const float n_lin = (float)(124.5 * i / 124.0);                         // torch.linspace(0, 124.5, 125)
+        win[i] = 0.54f - 0.46f * std::cos(2.0f * PI * n_lin / (float)KS);
+        n_[i] = 2.0f * PI * (float)(-125 + i) / sr;                             // 2*pi*arange(-125, 0)/16000
+    }
+    std::vector<float> filt((size_t)NF * KS);
+    for (int f = 0; f < NF; ++f) {
+        const float low = min_low + std::fabs(lo->data[f]);
+        float high = low + min_band + std::fabs(bd->data[f]);
+        high = std::fmin(std::fmax(high, min_low), sr / 2);
+        const float band = high - low;
+        for (int i = 0; i < HALF; ++i) {
+            const float left = ((std::sin(high * n_[i]) - std::sin(low * n_[i])) / (n_[i] / 2.0f)) * win[i];
+            filt[(size_t)f * KS + i] = left / (2.0f * band);
+            filt[(size_t)f * KS + (KS - 1 - i)] = left / (2.0f * band);
+        }
+        filt[(size_t)f * KS + HALF] = (2.0f * band) / (2.0f * band);
+    }
+    int rc;
+    if (h->bf16) {
+        std::vector<uint16_t> pk((size_t)NF * 256, 0);
+        for (int f = 0; f < NF; ++f)
+            for (int k = 0; k < KS; ++k) pk[(size_t)f * 256 + k] = to_h16(h, filt[(size_t)f * KS + k]);
+        uint16_t* d;
+        if ((rc = dev_upload(h, &d, pk))) return rc;
+        h->rn_filt = d;
+        if (h->f16) {
+            // the symmetric form (rawnet2.hip, SYM): slot k' = 2 + m carries h[125 + m] (the centre tap halved: its operand is x[c] + x[c]),
+            // slots 0 and 1 are zero; right and left halves of a filter are the same numbers by construction (checked here)
+            bool symmetric = true;
+            for (int f = 0; f < NF && symmetric; ++f)
+                for (int i = 0; i < HALF; ++i) symmetric = symmetric && filt[(size_t)f * KS + i] == filt[(size_t)f * KS + (KS - 1 - i)];
+            if (symmetric) {
+                std::vector<uint16_t> ps((size_t)NF * 128, 0);
+                for (int f = 0; f < NF; ++f) {
+                    ps[(size_t)f * 128 + 2] = to_h16(h, 0.5f * filt[(size_t)f * KS + HALF]);
+                    for (int m = 1; m <= HALF; ++m) ps[(size_t)f * 128 + 2 + m] = to_h16(h, filt[(size_t)f * KS + HALF + m]);
+                }
+                uint16_t* ds;
+                if ((rc = dev_upload(h, &ds, ps))) return rc;
+                h->rn_filt_sym = ds;
+            }
+        }
+    } else {
+        std::vector<float> pk((size_t)NF * 252, 0.0f);
+        for (int f = 0; f < NF; ++f)
+            for (int k = 0; k < KS; ++k) pk[(size_t)f * 252 + k] = filt[(size_t)f * KS + k];
+        float* d;
+        if ((rc = dev_upload(h, &d, pk))) return rc;
+        h->rn_filt = d;
+        if (h->x3) {        // the split front-end (rn_sinc_x3): hi and lo half planes, k contiguous, zero beyond the 251 taps
+            std::vector<uint16_t> pl((size_t)2 * NF * 256, 0);
+            for (int f = 0; f < NF; ++f)
+                for (int k = 0; k < KS; ++k) {
+                    const uint32_t w = x3_split_word(filt[(size_t)f * KS + k]);
+                    pl[(size_t)f * 256 + k] = (uint16_t)(w >> 16);
+                    pl[(size_t)(NF + f) * 256 + k] = (uint16_t)(w & 0xffffu);
+                }
+            uint16_t* dx;
+            if ((rc = dev_upload(h, &dx, pl))) return rc;
+            h->rn_filt_x3 = dx;
+        }
+    }
+    return SVHIP_OK;
+}
+
+// the 'conv' front-end's constants: conv1.weight (128, 1, 3) and conv1.bias as [w0 | w1 | w2 | bias] x 128 floats
+static int make_conv3_front(svhip_handle* h) {
+    const HostTensor *w = getw(h, "conv1.weight"), *b = getw(h, "conv1.bias");
+    if (!w || !b) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %s", !w ? "conv1.weight" : "conv1.bias");
+    std::vector<float> cw(4 * 128);
+    for (int c = 0; c < 128; ++c) {
+        for (int k = 0; k < 3; ++k) cw[k * 128 + c] = w->data[c * 3 + k];
+        cw[3 * 128 + c] = b->data[c];
+    }
+    return dev_upload(h, &h->rn_cw, cw);
+}
+
+int finalize_rawnet2(svhip_handle* h) {
+    int rc;
+    const bool conv = h->cfg.model == SVHIP_MODEL_RAWNET2_CONV;
+    if (conv) {
+        if ((rc = make_conv3_front(h))) return rc;
+    } else {
+        if ((rc = upload_f32(h, "ln.gamma", &h->rn_gamma))) return rc;
+        if ((rc = upload_f32(h, "ln.beta", &h->rn_beta))) return rc;
+        if ((rc = bake_sinc(h))) return rc;
+        if ((rc = make_bn(h, "first_bn", 128, &h->rn_fbn_scale, &h->rn_fbn_shift))) return rc;
+    }
+    int inpl = 128, bi = 0;
+    int T = h->rn_T1;
+    double fl = conv ? 2.0 * 128 * 3 * (double)T : 2.0 * 128 * 251 * (double)(h->cfg.samples - 250);
+    for (int li = 0; li < 6; ++li)
+        for (int b = 0; b < RN_LAYERS[li]; ++b, ++bi) {
+            svhip_handle::RnBlock& B = h->rn_blocks[bi];
+            const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
+            const int planes = RN_FILTERS[li];
+            B.cin = inpl; B.cout = planes; B.downsample = (b == RN_LAYERS[li] - 1); B.has_shortcut = inpl != planes;
+            if ((rc = make_bn(h, p + ".bn1", inpl, &B.bn1_scale, &B.bn1_shift))) return rc;
+            if ((rc = make_conv(h, B.conv1, p + ".conv1.weight", "", p + ".bn2", 1))) return rc;
+            if ((rc = make_conv(h, B.conv2, p + ".conv2.weight", "", "", 1))) return rc;
+            if (B.has_shortcut && (rc = make_conv(h, B.shortcut, p + ".shortcut.0.weight", "", "", 1))) return rc;
+            if (B.has_shortcut && h->bf16 && B.conv2.K % 64 == 0 && inpl % 64 == 0) {
+                // conv2 and the shortcut share their output: [conv2 columns (tap-major) | shortcut columns] as one K axis
+                const HostTensor* w2 = getw(h, p + ".conv2.weight");           // (planes, planes, 3)
+                const HostTensor* ws = getw(h, p + ".shortcut.0.weight");      // (planes, inpl, 1)
+                const int K2 = B.conv2.K, Kt = K2 + inpl, Np = B.conv2.Np;
+                std::vector<uint16_t> pk((size_t)Np * Kt, 0);
+                for (int n = 0; n < planes; ++n) {
+                    for (int t = 0; t < 3; ++t)
+                        for (int c = 0; c < planes; ++c) pk[(size_t)n * Kt + t * planes + c] = to_h16(h, w2->data[((size_t)n * planes + c) * 3 + t]);
+                    for (int c = 0; c < inpl; ++c) pk[(size_t)n * Kt + K2 + c] = to_h16(h, ws->data[(size_t)n * inpl + c]);
+                }
+                uint16_t* d;
+                if ((rc = dev_upload(h, &d, pk))) return rc;
+                B.conv2sc_W = d;
+            }
+            if ((rc = upload_f32(h, p + ".afms.alpha", &B.alpha))) return rc;
+            if ((rc = make_linear(h, B.afms_fc, p + ".afms.fc.weight", p + ".afms.fc.bias"))) return rc;
+            {
+                const HostTensor* fw = getw(h, p + ".afms.fc.weight");                  // (planes, planes)
+                std::vector<float> t((size_t)planes * planes);
+                for (int n = 0; n < planes; ++n)
+                    for (int c = 0; c < planes; ++c) t[(size_t)c * planes + n] = fw->data[(size_t)n * planes + c];
+                if ((rc = dev_upload(h, &B.afms_fcT, t))) return rc;
+            }
+            fl += (double)T * (B.conv1.flops_per_row + B.conv2.flops_per_row + (B.has_shortcut ? B.shortcut.flops_per_row : 0.0));
+            fl += 2.0 * planes * planes;
+            if (B.downsample) T /= 3;
+            inpl = planes;
+        }
+    if ((rc = make_bn(h, "bn_before_agg", 512, &h->rn_agg_scale, &h->rn_agg_shift))) return rc;
+    if ((rc = make_conv(h, h->rn_att0, "attention.0.weight", "attention.0.bias", "attention.2", 1))) return rc;
+    if ((rc = make_conv(h, h->rn_att3, "attention.3.weight", "attention.3.bias", "", 1))) return rc;
+    if ((rc = make_linear(h, h->rn_fc, "fc.weight", "fc.bias"))) return rc;
+    fl += (double)T * (h->rn_att0.flops_per_row + h->rn_att3.flops_per_row) + 2.0 * h->rn_fc.N * h->rn_fc.K;
+    h->flops_per_utt = fl;
+    return SVHIP_OK;
+}
+
+int alloc_workspace(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    const size_t B = c.max_batch, T = h->T, M = B * T, C = c.channels, C3 = 3 * C, e = h->esz;
+    int rc;
+    if ((rc = dev_alloc(h, &h->d_wav, B * (size_t)c.samples))) return rc;
+    if ((rc = dev_alloc(h, &h->d_feat, B * c.n_mels * T))) return rc;
+    if ((rc = dev_alloc(h, &h->d_pstats, B * c.n_mels * 2))) return rc;
+    if (h->x3 && (rc = dev_alloc(h, &h->d_xscale, 2 * (4 + 256)))) return rc;       // (one set per lane slice)
+    if (h->fb.sym_hi) {
+        if ((rc = dev_alloc(h, &h->d_logmel, B * c.n_mels * T))) return rc;
+        if ((rc = dev_alloc(h, &h->d_fpart, B * c.n_mels * ((T + 63) / 64)))) return rc;
+    }
+    if ((rc = dev_alloc(h, &h->d_zero, 64))) return rc;
+    SV_HIP(h, hipMemset(h->d_zero, 0, 256));
+    {
+        std::vector<float> one(4096, 1.0f), zero(4096, 0.0f);
+        if ((rc = dev_upload(h, &h->d_ones, one))) return rc;
+        if ((rc = dev_upload(h, &h->d_zeros, zero))) return rc;
+    }
+    if ((rc = dev_alloc(h, &h->d_emb, B * (size_t)c.embed_dim))) return rc;
+    if ((rc = dev_alloc(h, &h->d_status, 4))) return rc;
+    SV_HIP(h, hipMemset(h->d_status, 0, 16));
+    SV_HIP(h, hipHostMalloc((void**)&h->host_flag, 64, hipHostMallocMapped));
+    *h->host_flag = 0;
+    SV_HIP(h, hipHostGetDevicePointer((void**)&h->host_flag_dev, h->host_flag, 0));
+    if (is_rawnet2(c.model)) {
+        const bool conv = c.model == SVHIP_MODEL_RAWNET2_CONV;
+        h->rn_T1 = conv ? (c.samples - 3) / 3 + 1 : (c.samples - 250) / 3;       // conv1 (kernel 3, stride 3) | sinc (251 taps) + max_pool1d(3)
+        const size_t per_utt = (size_t)h->rn_T1 * 128;           // largest activation: (T1, 128); later stages shrink 3x per doubling
+        h->rn_buf_bytes = B * per_utt * e;
+        for (int i = 0; i < 6; ++i) {
+            char* q;
+            if ((rc = dev_alloc(h, &q, B * per_utt * e + 256))) return rc;
+            h->rn_buf[i] = q;
+            SV_HIP(h, hipMemset(q + h->rn_buf_bytes, 0, 256));          // the zero tail (no kernel writes past the payload)
+        }
+        if (!conv && (rc = dev_alloc(h, &h->rn_stats, B * 2))) return rc;
+        if (!conv && (h->bf16 || h->x3)) {                                  // LayerNorm output in 16 bits, zero-tailed rows (operand of the 16-bit / split sinc kernels)
+            h->rn_Lp = (int)round_up(c.samples + RN_XN_TAIL, 64);
+            uint16_t* q;
+            if ((rc = dev_alloc(h, &q, (h->x3 ? 4 : 2) * B * (size_t)h->rn_Lp))) return rc;      // (F32X3: hi and lo parts of both copies)
+            h->rn_xn = q;
+        }
+        if ((rc = dev_alloc(h, &h->rn_part, B * (size_t)(rn_block128_ntiles(h->rn_T1) + 1) * 4 * 128))) return rc;
+        if ((rc = dev_alloc(h, &h->rn_mean, B * 512))) return rc;
+        if ((rc = dev_alloc(h, &h->rn_scratch, B * 16 * 512))) return rc;
+        if ((rc = dev_alloc(h, &h->rn_s, B * 512 * 2))) return rc;
+        int tf = h->rn_T1;
+        for (int i = 0; i < 6; ++i) tf /= 3;                      // six max_pool1d(3) stages follow the front-end
+        if (tf < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance too short for RawNet2 (%d samples)", c.samples);
+        if ((rc = dev_alloc(h, &h->rn_logits, B * (size_t)tf * 512))) return rc;
+        if ((rc = dev_alloc(h, &h->rn_pooled, B * 1024))) return rc;
+        if (h->bf16) {          // K-slice partials of fc (K = 1 024: four slices of 256) at full batches, 16-bit handles
+            h->lin_part_per_utt = (size_t)4 * (size_t)std::max(128, c.embed_dim);
+            if ((rc = dev_alloc(h, &h->d_lin_part, B * h->lin_part_per_utt))) return rc;
+        }
+    }
+    if (c.model == SVHIP_MODEL_ECAPA) {
+        char* p;
+        auto actbuf = [&](void** dst, size_t elems) -> int {
+            int r = dev_alloc(h, &p, elems * e + 256);
+            *dst = p;
+            return r;
+        };
+        if ((rc = actbuf(&h->X_in, M * c.n_mels))) return rc;
+        if ((rc = actbuf(&h->X0, M * C))) return rc;
+        if ((rc = actbuf(&h->H1, M * C))) return rc;
+        if ((rc = actbuf(&h->H2, M * C))) return rc;
+        if ((rc = actbuf(&h->H3, M * C))) return rc;
+        if ((rc = actbuf(&h->CAT, M * C3))) return rc;
+        if ((rc = actbuf(&h->MFA, M * C3))) return rc;
+        if ((rc = actbuf(&h->ATT, M * 128))) return rc;
+        if ((rc = dev_alloc(h, &h->LOGITS, M * C3))) return rc;
+        if ((rc = dev_alloc(h, &h->d_mean, B * C))) return rc;
+        if ((rc = dev_alloc(h, &h->d_s1, B * 128))) return rc;
+        if ((rc = dev_alloc(h, &h->d_s2, B * C))) return rc;
+        if ((rc = dev_alloc(h, &h->d_gstats, B * 2 * C3))) return rc;
+        if ((rc = dev_alloc(h, &h->d_ctx, B * 128))) return rc;
+        h->lin_part_per_utt = (size_t)((2 * C3 + 383) / 384) * (size_t)std::max(128, c.embed_dim);
+        if ((rc = dev_alloc(h, &h->d_lin_part, B * h->lin_part_per_utt))) return rc;
+        if ((rc = dev_alloc(h, &h->d_pool_raw, B * 2 * C3))) return rc;
+        if ((rc = dev_alloc(h, &h->d_pool_bn, B * 2 * C3))) return rc;
+        if (h->x3 && (rc = dev_alloc(h, reinterpret_cast<char**>(&h->s32_buf), M * C3 * 4 + 256))) return rc;
+        if (h->x3 && C % 32 == 0 && (rc = dev_alloc(h, reinterpret_cast<char**>(&h->cat_s32), M * C3 * 4 + 256))) return rc;
+        if (h->x3 && (C == 512 || C == 1024)) {
+            if ((rc = dev_alloc(h, reinterpret_cast<char**>(&h->h2_s32), M * C * 4 + 256))) return rc;
+            for (int i = 0; i < 2; ++i) if ((rc = dev_alloc(h, reinterpret_cast<char**>(&h->u_s32[i]), M * (C / 8) * 4 + 256))) return rc;
+        }
+        h->colsum_region = (int64_t)((M + 255) / 256 + 2) * 16 * C3;
+        if ((rc = dev_alloc(h, &h->d_colsum, (size_t)4 * h->colsum_region))) return rc;
+    }
+    return SVHIP_OK;
+}
+
+}  // namespace svhip

@@ -19,7 +19,7 @@
 #include <mutex>
 #include <string>
 
-#include "kernels.h"
+#include "handle.h"
 
 namespace {
 
@@ -74,8 +74,19 @@ struct Comm {
 int fail(svhip_handle* h, int code, const char* what, const char* detail) {
     char b[512];
     snprintf(b, sizeof(b), "%s: %s", what, detail ? detail : "?");
-    svhip::handle_set_error(h, b);
+    h->err = b;
     return code;
+}
+
+// a launch on the handle's stream through svhip::run (the profiling bracket every launch gets); returns an svhip_status
+template <typename F>
+int run_on_stream(svhip_handle* h, const char* label, F&& launch) {
+    const std::string keep = h->err;             // a failing launch may have left a more specific message
+    h->err.clear();
+    h->cur = h->stream;
+    const int rc = svhip::run(h, label, 0, launch);
+    if (rc && !keep.empty() && h->err.empty()) h->err = keep;
+    return rc;
 }
 
 thread_local std::string g_id_error;
@@ -98,10 +109,10 @@ int svhip_comm_unique_id(void* id_out) {
 
 int svhip_comm_init(svhip_handle* h, const void* id_bytes, int32_t rank, int32_t world) {
     if (!h || !id_bytes || world <= 0 || rank < 0 || rank >= world) return SVHIP_ERR_INVALID;
-    if (svhip::handle_comm(h)) return fail(h, SVHIP_ERR_STATE, "svhip_comm_init", "the handle already owns a communicator");
+    if (h->comm) return fail(h, SVHIP_ERR_STATE, "svhip_comm_init", "the handle already owns a communicator");
     Rccl* r = rccl();
     if (!r->so) return fail(h, SVHIP_ERR_UNSUPPORTED, "svhip_comm_init", r->err.c_str());
-    hipError_t he = hipSetDevice(svhip::handle_device(h));
+    hipError_t he = hipSetDevice(h->cfg.device);
     if (he != hipSuccess) return fail(h, SVHIP_ERR_HIP, "hipSetDevice", hipGetErrorString(he));
     ncclUniqueId id;
     memcpy(&id, id_bytes, sizeof(id));
@@ -109,13 +120,13 @@ int svhip_comm_init(svhip_handle* h, const void* id_bytes, int32_t rank, int32_t
     c->rank = rank; c->world = world;
     const ncclResult_t e = r->CommInitRank(&c->comm, world, id, rank);
     if (e != ncclSuccess) { delete c; return fail(h, SVHIP_ERR_HIP, "ncclCommInitRank", r->GetErrorString(e)); }
-    svhip::handle_comm(h) = c;
+    h->comm = c;
     return SVHIP_OK;
 }
 
 int svhip_comm_rank(const svhip_handle* h, int32_t* rank, int32_t* world) {
     if (!h) return SVHIP_ERR_INVALID;
-    const Comm* c = static_cast<const Comm*>(svhip::handle_comm(const_cast<svhip_handle*>(h)));
+    const Comm* c = static_cast<const Comm*>(h->comm);
     if (rank) *rank = c ? c->rank : 0;
     if (world) *world = c ? c->world : 1;
     return c ? SVHIP_OK : SVHIP_ERR_STATE;
@@ -123,29 +134,29 @@ int svhip_comm_rank(const svhip_handle* h, int32_t* rank, int32_t* world) {
 
 int svhip_comm_destroy(svhip_handle* h) {
     if (!h) return SVHIP_ERR_INVALID;
-    Comm* c = static_cast<Comm*>(svhip::handle_comm(h));
+    Comm* c = static_cast<Comm*>(h->comm);
     if (!c) return SVHIP_OK;
-    (void)hipSetDevice(svhip::handle_device(h));
-    (void)hipStreamSynchronize(svhip::handle_stream(h));
+    (void)hipSetDevice(h->cfg.device);
+    (void)hipStreamSynchronize(h->stream);
     Rccl* r = rccl();
     if (r->so && c->comm) (void)r->CommDestroy(c->comm);
     if (c->stage_in) (void)hipFree(c->stage_in);
     if (c->stage_out) (void)hipFree(c->stage_out);
     delete c;
-    svhip::handle_comm(h) = nullptr;
+    h->comm = nullptr;
     return SVHIP_OK;
 }
 
 int svhip_allgather_rows(svhip_handle* h, const float* local, int64_t rows, int32_t D, float* out, int32_t flags) {
     if (!h || !local || !out || rows < 0 || D <= 0) return SVHIP_ERR_INVALID;
-    Comm* c = static_cast<Comm*>(svhip::handle_comm(h));
+    Comm* c = static_cast<Comm*>(h->comm);
     if (!c) return fail(h, SVHIP_ERR_STATE, "svhip_allgather_rows", "no communicator (call svhip_comm_init first)");
     const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
     if ((flags & SVHIP_ASYNC) && !(din && dout)) return fail(h, SVHIP_ERR_INVALID, "svhip_allgather_rows", "SVHIP_ASYNC needs device pointers");
     if (rows == 0) return SVHIP_OK;
-    hipError_t he = hipSetDevice(svhip::handle_device(h));
+    hipError_t he = hipSetDevice(h->cfg.device);
     if (he != hipSuccess) return fail(h, SVHIP_ERR_HIP, "hipSetDevice", hipGetErrorString(he));
-    hipStream_t st = svhip::handle_stream(h);
+    hipStream_t st = h->stream;
     const size_t n_in = (size_t)rows * D, n_out = n_in * c->world;
     const float* d_in = local;
     float* d_out = out;
@@ -169,9 +180,9 @@ int svhip_allgather_rows(svhip_handle* h, const float* local, int64_t rows, int3
         d_out = c->stage_out;
     }
     Rccl* r = rccl();
-    const int rc = svhip::handle_run(h, "allgather_rows", [&]() -> hipError_t {
+    const int rc = run_on_stream(h, "allgather_rows", [&]() -> hipError_t {
         const ncclResult_t e = r->AllGather(d_in, d_out, n_in, ncclFloat32, c->comm, st);
-        if (e != ncclSuccess) { svhip::handle_set_error(h, r->GetErrorString(e)); return hipErrorUnknown; }
+        if (e != ncclSuccess) { const char* m = r->GetErrorString(e); h->err = m ? m : ""; return hipErrorUnknown; }
         return hipSuccess;
     });
     if (rc) return rc;

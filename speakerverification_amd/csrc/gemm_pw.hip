@@ -122,7 +122,7 @@ __device__ __forceinline__ void split_hi_lo(const f32x4& a, const f32x4& b, bf16
 // X3 (T = float only): fp32 operands in memory and LDS, each product formed as THREE bf16 MFMAs on hi / lo-split fragments
 // (hi.hi + hi.lo + lo.hi, fp32 accumulate): ~2^-17 relative per product instead of 2^-24, at 3/16 of the fp32 MFMA's cycles.
 // The activations are split in registers after the fragment read; the packed weights hold (hi bf16 << 16) | lo bf16 per fp32
-// slot (api.hip make_conv, SVHIP_F32X3 handles), so their "split" is two byte permutes per pair.
+// slot (api_weights.hip make_conv, SVHIP_F32X3 handles), so their "split" is two byte permutes per pair.
 template <typename T, int EPI, bool OUT_F32, int PBN, bool CONV, bool X3 = false>
 __global__ __launch_bounds__(512, 2) void gemm_pw_kernel(GemmParams p) {
     static_assert(!X3 || sizeof(T) == 4, "the split path reads fp32 operands");

@@ -1,0 +1,302 @@
+// handle.h — the handle of libsvhip and what the host-side translation units of the C ABI share (api*.hip, comm.hip).
+// Internal: kernel translation units see kernels.h / common.h only.
+#pragma once
+#include "../../include/svhip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace svhip {
+
+struct HostTensor {
+    std::vector<float> data;
+    std::vector<int64_t> shape;
+    int64_t numel() const { int64_t n = 1; for (auto s : shape) n *= s; return n; }
+};
+
+struct ConvLayer {            // one conv1d as a GEMM operand set (device pointers)
+    int N = 0, K = 0, Kp = 0, Np = 0, taps = 1, dil = 1, cin = 0;
+    void* W = nullptr;        // packed [Np][Kp] in the compute dtype
+    void* Wsplit = nullptr;   // SVHIP_F32X3 handles: the same matrix as (hi bf16 << 16 | lo bf16) words, for gemm_pw's split path
+    float cv_wscale = 1.0f;   // ... whose planes hold cv_wscale * W (an exact power of two; 1 unless max |w| lies outside [2^-8, 2^13))
+    void* Wcv = nullptr;      // SVHIP_F32X3 handles, odd-tap convolutions with N % 256 == 0 (blocks.0): [N][cv_Kp] S32, k = tap * cv_cin + c with the
+    int cv_cin = 0, cv_Kp = 0; // input channels zero-padded to cv_cin (a multiple of 32) and cv_Kp = taps * cv_cin rounded up to 64: gemm_pw3's CV form
+    void* Ws32 = nullptr;     // SVHIP_F32X3 handles, pointwise layers with N % 256 == 0 and K % 64 == 0: the S32 split layout (per row, per
+                              // 32 k: 32 hi bf16 | 32 lo bf16) of gemm_pw3's X3 form
+    float* bias = nullptr;    // [N] or null
+    float* scale = nullptr;   // folded BatchNorm (eval): y = x*scale + shift, or null
+    float* shift = nullptr;
+    double flops_per_row = 0;
+};
+
+struct LinearLayer {          // small-M fp32 linear (rowvec kernel)
+    int N = 0, K = 0;
+    float* W = nullptr;       // [N][K]
+    float* bias = nullptr;
+};
+
+struct ProfEntry { std::string name; double ms = 0; int64_t launches = 0; double flops = 0; };
+struct PendingEvent { hipEvent_t e0, e1; int entry; };
+
+}  // namespace svhip
+
+struct svhip_handle {
+    svhip_config cfg{};
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    hipStream_t cur = nullptr;                // stream the launch helpers enqueue on (main stream or a lane)
+    hipStream_t lane_stream[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t lane_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};       // [lane] done events, [4] = fork point
+    int lanes = 1;                            // > 1: the forward runs as that many batch slices on as many streams
+    // developer / test switches: what the call sites read.  Defaults, environment variables and names: kDevOpts (api.hip)
+    struct DevOpts {
+        int layer_labels;         // one profile row per GEMM shape
+        int x3_keep_f32;          // F32X3: keep the fp32 copies of the block outputs beside the split layout
+        int r2_big;               // F32X3: Res2Net steps on the R2 form of the 256 x 256 kernel instead of r2_step
+        int asp_v1;               // bf16: asp_fused_kernel instead of asp_bf16_kernel
+        int rn_stop;              // RawNet2: return after this many residual blocks (0: after the sinc front-end), unfused kernel sequence
+        int rn_snap;              // RawNet2: keep block n's pre-activation as stage "rn_snap"
+        int rn_unfused;           // RawNet2: the separate kernel sequence instead of rn_block128 / rn_tail / the folded shortcut
+        int asnorm_slab;          // AS-norm statistics on the slab path
+        int asnorm_f32mfma;       // AS-norm fused kernel on the exact fp32 MFMA instead of the split form
+        int score_f32mfma;        // dense score GEMMs (svhip_score_matrix, the slab path's cohort GEMM) on the exact fp32 MFMA instead of the split form
+        int score_tiled;          // dense score GEMMs on the tiled split kernel (gemm_pw) instead of the row-streaming one (score_h3w)
+        int asnorm_norefit;       // AS-norm: embeddings the normal-quantile threshold does not fit go straight to the slab path (round 5's behaviour)
+        int rn_sinc_full;         // RawNet2 fp16 handles: the 251-tap sinc kernel (round 5) instead of the symmetric 126-tap form
+        int fbank32;              // the 32-frame front-end kernel
+        int fbank_unfused;        // bf16 handles: fbank -> prologue_stats -> prologue_apply (round 5) instead of the fused front-end
+        int pw3_cus;              // cap of the persistent GEMM grids (0: persistent kernels off)
+        int pw3_tail_off;         // persistent 16-bit GEMMs: the last partial round as whole tiles (round 4) instead of column halves
+        int cv_off;               // 16-bit handles: conv-gather GEMMs on the per-tile kernel instead of the persistent one
+        int n128_off;             // bf16: asp.tdnn on gemm_pw instead of gemm_n128
+        int rn_pool_off;          // F32X3 handles: conv2 of the long pooled blocks writes the un-pooled output, rn_maxpool3 pools it (tests)
+        int rn_step_off;          // F32X3 handles: the 128 -> 128 blocks' convolutions on the tiled in-register-split kernel (tests)
+        int rn_sinc_f32;          // F32X3 handles: the sinc front-end on the exact fp32 MFMA (tests) instead of three fp16 MFMAs per product
+        int rn_tail_big;          // RawNet2 block tail: one workgroup per utterance at every batch size (tests)
+        int r2_slices;            // bf16 Res2Net chain: time slices per utterance (-1: by batch size, 0 / 1: whole utterances, n: forced)
+        int rn_conv_unfused;      // 16-bit RawNet2 'conv' handles: rn_conv3_front + plain rn_block128 instead of block 0 reading the waveform (tests, A/B)
+    } opt;
+    bool bf16 = false;                        // 16-bit storage handle: bf16, or fp16 when `f16` is set (the flag keeps its round-1 name)
+    bool f16 = false;                         // SVHIP_F16: the 16-bit type is IEEE half (RawNet2)
+    int dt = svhip::DT_F32;                   // DT_F32 / DT_BF16 / DT_F16: what the element-wise launchers are told
+    bool x3 = false;                          // SVHIP_F32X3: fp32 handle whose conv GEMMs run as split-bf16 MFMA triples
+    bool finalized = false;
+    std::string err;
+    std::map<std::string, svhip::HostTensor> host_w;
+    std::vector<void*> allocs;               // everything hipMalloc'ed, freed in destroy
+
+    int T = 0;                                // frames per utterance
+    int esz = 4;                              // activation element size
+
+    // front-end tables
+    svhip::FbankTables fb;
+
+    // ECAPA layers
+    svhip::ConvLayer blocks0, mfa, asp_tdnn, asp_conv;
+    svhip::ConvLayer tdnn1[3], tdnn2[3], res2[3][7];
+    svhip::LinearLayer se1[3], se2[3], asp_ctx, fc;
+    float* se2T[3] = {};                      // se_block.conv2 weight transposed to [128][C]
+    void *se1_bf[3] = {}, *se2T_bf[3] = {};   // bf16 copies of both SE matrices (bf16 handles: half the L2 bytes per workgroup)
+    float *aspbn_scale = nullptr, *aspbn_shift = nullptr;
+    float *in_w = nullptr, *in_b = nullptr;   // instance norm affine
+
+    // RawNet2 layers (front_proc='sinc' or 'conv', aggregate='asp'; RawNet2_custom.py:230-243)
+    struct RnBlock {
+        int cin = 0, cout = 0;
+        bool downsample = false, has_shortcut = false;
+        float *bn1_scale = nullptr, *bn1_shift = nullptr;
+        svhip::ConvLayer conv1, conv2, shortcut;       // conv1 carries bn2 as its epilogue
+        void* conv2sc_W = nullptr;              // bf16 handles: [Np][conv2.K + cin] = conv2 | 1 x 1 shortcut, one GEMM for both (gemm_pw2 A3)
+        float* alpha = nullptr;
+        svhip::LinearLayer afms_fc;
+        float* afms_fcT = nullptr;              // fc weight transposed [cin][cout] (the gate kernel reads consecutive outputs per wave)
+    };
+    RnBlock rn_blocks[8];
+    float *rn_gamma = nullptr, *rn_beta = nullptr, *rn_fbn_scale = nullptr, *rn_fbn_shift = nullptr;
+    void* rn_filt = nullptr;
+    void* rn_filt_sym = nullptr;              // fp16 handles: [128][128] slot-major table of the symmetric sinc form (round 6)
+    void* rn_filt_x3 = nullptr;               // F32X3 handles: [2][128][256] half hi | lo parts of the sinc filters
+    float* rn_cw = nullptr;                   // 'conv' front-end (SVHIP_MODEL_RAWNET2_CONV): [w0 | w1 | w2 | bias] x 128 floats of conv1
+    float *rn_agg_scale = nullptr, *rn_agg_shift = nullptr;
+    svhip::ConvLayer rn_att0, rn_att3;
+    svhip::LinearLayer rn_fc;
+    void* rn_buf[6] = {};                 // activation ping-pong buffers
+    float* rn_scratch = nullptr;
+    void* rn_xn = nullptr;
+    int rn_Lp = 0;
+    float *rn_stats = nullptr, *rn_mean = nullptr, *rn_s = nullptr, *rn_logits = nullptr, *rn_pooled = nullptr;
+    float* rn_part = nullptr;             // fused 128-channel blocks: per-tile column sums (B, ntiles, 128)
+    int num_cu = 256;
+    int rn_T1 = 0;
+    const void* rn_dbg_x = nullptr; int rn_dbg_T = 0, rn_dbg_C = 0;   // SVHIP_RN_STOP developer hook (tests)
+    void* rn_snap = nullptr; size_t rn_snap_cap = 0; int rn_snap_T = 0, rn_snap_C = 0;      // SVHIP_RN_SNAP=2: copy of block 2's pre-activation (stage "rn_snap")
+
+    // workspace (device)
+    float* d_wav = nullptr;       // (Bmax, L)
+    float* d_feat = nullptr;      // (Bmax, n_mels, T) mel power
+    float* d_pstats = nullptr;    // (Bmax*n_mels*2)
+    float* d_xscale = nullptr;    // F32X3: [0] = s, [1] = 1 / s of the network input (launch_in_scale), then 256 partial max words
+    float* d_logmel = nullptr;    // fused front-end (bf16 handles): (Bmax, T, n_mels) log-mel rows before the mean is taken off
+    float* d_fpart = nullptr;     //   and their per-tile column sums (Bmax, ceil(T / 64), n_mels)
+    bool xin_ready = false;       // the fused front-end has written X_in: ecapa_forward_part skips its prologue
+    bool feat_is_stale = false;   // ... and d_feat does not hold this forward's mel power (svhip_get_stage "mel")
+    float* d_zero = nullptr;      // 256 zero bytes (DMA source for padded conv chunks)
+    float *d_ones = nullptr, *d_zeros = nullptr;      // 4096 ones / zeros: stand-ins for absent per-channel vectors (GemmParams::ones / zeros)
+    size_t rn_buf_bytes = 0;      // RawNet2: payload bytes of each activation buffer; a 256-byte zero tail follows (the zero page of the
+                                  // persistent conv-gather kernel must sit behind its A operand, within 4 GiB)
+    void* s32_buf = nullptr;      // SVHIP_F32X3: the A operand of the current big GEMM in the S32 split layout (M x 3C x 4 bytes)
+    void *side_a = nullptr, *side_b = nullptr;      // pending S32 side outputs of the next conv_gemm (GemmParams::side_*), consumed by it
+    int side_lda = 0, side_ldb = 0, side_c = 0;
+    bool side_done = false;       // ... and whether that GEMM wrote them
+    bool x0_is_s32 = false;       // SVHIP_F32X3: the last forward wrote blocks.0's output (X0) in the split layout
+    bool cat_f32_stale = false;   // SVHIP_F32X3: the last forward left the block outputs only in cat_s32 (svhip_get_stage converts on demand)
+    void* cat_s32 = nullptr;      // SVHIP_F32X3: the SE-Res2Net block outputs (the CAT buffer) in the S32 layout, written by se_apply
+    void* h2_s32 = nullptr;       // SVHIP_F32X3: the Res2Net chain output (H2's twin, S32 only) and the two step-input buffers (M x C/8)
+    void* u_s32[2] = {};
+    float* d_colsum = nullptr;    // pw2 column-sum partials, per lane: [sum | sumsq] x (tiles*4) x 3C floats
+    int64_t colsum_region = 0;    // floats per (lane, kind) region
+    bool last_colsum_done = false;
+    int last_colsum_groups = 8;   // row groups per tile in the partials the last GEMM wrote (8: pw2, 2: pw3)
+    void* X_in = nullptr;         // (M, n_mels)
+    void* X0 = nullptr;           // (M, C)
+    void *H1 = nullptr, *H2 = nullptr, *H3 = nullptr;   // (M, C)
+    void* CAT = nullptr;          // (M, 3C)
+    void* MFA = nullptr;          // (M, 3C)
+    void* ATT = nullptr;          // (M, 128)
+    float* LOGITS = nullptr;      // (M, 3C) fp32
+    float *d_mean = nullptr, *d_s1 = nullptr, *d_s2 = nullptr, *d_gstats = nullptr, *d_ctx = nullptr;
+    float* d_lin_part = nullptr;              // K-slice partials of the small-M linear layers (fc, asp_ctx) at full batches
+    size_t lin_part_per_utt = 0;
+    float *d_pool_raw = nullptr, *d_pool_bn = nullptr, *d_emb = nullptr;
+    int lastB = 0;
+    // numeric status of the forwards since the last reset: d_status[0] = SVHIP_STATUS_* bits, [1] = non-finite embedding values,
+    // [2] = input values beyond the split planes' range; host_flag (pinned, mapped) is set by the same kernels, so that a synchronous
+    // call learns of a problem without a copy
+    uint32_t* d_status = nullptr;
+    uint32_t* host_flag = nullptr;
+    uint32_t* host_flag_dev = nullptr;
+
+    // profiling: event pairs are recorded around every launch without blocking the host and
+    // resolved (hipEventElapsedTime) when results are read
+    bool prof = false;
+    std::string prof_filter;                  // non-empty: only launches with exactly this label are bracketed by events
+    std::vector<hipEvent_t> ev_free;
+    std::vector<svhip::PendingEvent> ev_pending;
+    std::vector<svhip::ProfEntry> prof_entries;
+    double flops_per_utt = 0;
+    void* comm = nullptr;                     // RCCL communicator state, owned by comm.hip
+    // svhip_crop_pcm16 staging (host-pointer calls): one grow-only device PCM buffer (copies and kernels are ordered on the
+    // handle's stream) and a ring of pinned host / device metadata slots, each guarded by an event, so that SVHIP_ASYNC calls
+    // can return before the copy has run
+    void* crop_pcm = nullptr; size_t crop_pcm_cap = 0;
+    // scoring / metrics scratch: handle-owned slots, grown on demand (no hipMalloc / hipFree per call once warm)
+    enum { SCR_IN0 = 0, SCR_IN1, SCR_IN2, SCR_IN3, SCR_IN4, SCR_OUT0, SCR_OUT1, SCR_OUT2, SCR_SLAB, SCR_SPLIT, SCR_CAND, SCR_CNT, SCR_MB,
+           SCR_FLAG, SCR_GATHER, SCR_WS, SCR_COUNT };
+    void* scr[SCR_COUNT] = {};
+    size_t scr_cap[SCR_COUNT] = {};
+    hipStream_t aux_stream = nullptr;         // second stream of the scoring entry points (candidate statistics under the next MFMA launch)
+    hipEvent_t aux_ev[4] = {};
+    int64_t last_asnorm_refit = 0;            // embeddings of the last call that the refit passes of the fused kernel decided (round 6)
+    int last_asnorm_refit_passes = 0;
+    int last_asnorm_flagged = -1;             // embeddings the fused AS-norm kernel handed to the slab path in the last call (-1: slab path)
+    struct CropSlot { char* host = nullptr; char* dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool busy = false; };
+    CropSlot crop_slot[4];
+    int crop_next = 0;
+};
+
+#define SV_FAIL(h, code, ...)                                   \
+    do {                                                        \
+        char _b[512];                                           \
+        snprintf(_b, sizeof(_b), __VA_ARGS__);                  \
+        (h)->err = _b;                                          \
+        return (code);                                          \
+    } while (0)
+
+#define SV_HIP(h, expr)                                                                            \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess) SV_FAIL(h, SVHIP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+namespace svhip {
+
+hipEvent_t prof_event(svhip_handle* h);
+void prof_collect(svhip_handle* h);
+
+template <typename T>
+int dev_alloc(svhip_handle* h, T** p, size_t count) {
+    void* q = nullptr;
+    size_t bytes = count * sizeof(T);
+    if (bytes == 0) bytes = 16;
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) SV_FAIL(h, SVHIP_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+    h->allocs.push_back(q);
+    *p = reinterpret_cast<T*>(q);
+    return SVHIP_OK;
+}
+
+template <typename T>
+int dev_upload(svhip_handle* h, T** p, const std::vector<T>& v) {
+    int rc = dev_alloc(h, p, v.size());
+    if (rc) return rc;
+    if (!v.empty()) SV_HIP(h, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return SVHIP_OK;
+}
+
+// the profiling-aware launch wrapper: every launch goes through it (event pairs around it while profiling is on)
+template <typename F>
+int run(svhip_handle* h, const char* label, double flops, F&& launch) {
+    PendingEvent pe{nullptr, nullptr, -1};
+    const bool prof = h->prof && (h->prof_filter.empty() || h->prof_filter == label);
+    if (prof) {
+        for (size_t i = 0; i < h->prof_entries.size(); ++i)
+            if (h->prof_entries[i].name == label) { pe.entry = (int)i; break; }
+        if (pe.entry < 0) { h->prof_entries.push_back(ProfEntry{label}); pe.entry = (int)h->prof_entries.size() - 1; }
+        pe.e0 = prof_event(h);
+        pe.e1 = prof_event(h);
+        (void)hipEventRecord(pe.e0, h->cur);
+    }
+    hipError_t e = launch();
+    if (e != hipSuccess) SV_FAIL(h, SVHIP_ERR_HIP, "launch %s failed: %s", label, hipGetErrorString(e));
+    if (prof) {
+        (void)hipEventRecord(pe.e1, h->cur);
+        h->prof_entries[pe.entry].launches += 1;
+        h->prof_entries[pe.entry].flops += flops;
+        h->ev_pending.push_back(pe);
+        if (h->ev_pending.size() >= 8192) prof_collect(h);
+    }
+    return SVHIP_OK;
+}
+
+inline bool is_rawnet2(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_CONV; }
+inline void* off(void* base, size_t elems, int esz) { return reinterpret_cast<char*>(base) + elems * esz; }
+inline const void* off(const void* base, size_t elems, int esz) { return reinterpret_cast<const char*>(base) + elems * esz; }
+
+// api_weights.hip: the front-end tables, the expected weight names / shapes, weight packing, the workspace
+int build_fbank_tables(svhip_handle* h);
+void model_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec);
+int finalize_ecapa(svhip_handle* h);
+int finalize_rawnet2(svhip_handle* h);
+int alloc_workspace(svhip_handle* h);
+
+// api_gemm.hip: the GEMM of one conv layer
+const void* zero_page_for(const svhip_handle* h, const void* A);
+GemmParams conv_params(const svhip_handle* h, const ConvLayer& L, const void* A, int lda, void* Y, int ldy, int M, int T);
+int conv_gemm(svhip_handle* h, const ConvLayer& L, GemmParams p, const void* A_s32 = nullptr, int lda_s32 = 0);
+
+// api.hip: a forward over the utterances [b0, b0 + B) of the call, enqueued on h->cur, as `lanes` batch slices
+using ForwardPart = int (*)(svhip_handle* h, const float* in, int b0, int B);
+int forward_lanes(svhip_handle* h, ForwardPart part, const float* in, int B, int lanes, int per);
+
+// api_ecapa.hip, api_rawnet2.hip: the whole-batch forwards
+int ecapa_forward(svhip_handle* h, const float* d_feat, int B);
+int rawnet2_forward(svhip_handle* h, const float* d_wav, int B);
+
+}  // namespace svhip

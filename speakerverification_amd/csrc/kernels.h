@@ -4,23 +4,10 @@
 #include <stdint.h>
 
 #include <atomic>
-#include <functional>
 
 #include "common.h"
 
-struct svhip_handle;
-
 namespace svhip {
-
-// ---------------------------------------------------------------------------------------------
-// Handle accessors for the translation units that do not see the handle's definition (api.hip owns it)
-// ---------------------------------------------------------------------------------------------
-hipStream_t handle_stream(svhip_handle* h);
-int handle_device(const svhip_handle* h);
-void handle_set_error(svhip_handle* h, const char* msg);
-void*& handle_comm(svhip_handle* h);            // opaque slot owned by comm.hip
-// profiling-aware launch (the same event bracketing api.hip's own launches get); returns an svhip_status
-int handle_run(svhip_handle* h, const char* label, const std::function<hipError_t()>& launch);
 
 // ---------------------------------------------------------------------------------------------
 // One-time per-DEVICE setup flag.  hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the function on the
@@ -116,7 +103,7 @@ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 hipError_t launch_gemm(const GemmParams& p, bool bf16, hipStream_t stream);
 // pointwise fast path (gemm_pw.hip): 256 x 128 tiles, LDS-DMA ring; launch_gemm routes to it when supported
-// Which kernel launch_gemm runs for a shape (the profile labels of api.hip name the same choice):
+// Which kernel launch_gemm runs for a shape (the profile labels of api_gemm.hip's conv_gemm name the same choice):
 //   PW2        256 x 256 role-staggered bf16 kernel (gemm_pw2.hip)
 //   PW_NARROW  gemm_pw's 256 x 128 tile: a pw2 grid of at most half the CUs finishes in one round either way, and the half-size
 //              tile takes about half as long (RawNet2 blocks 6 / 7, 86 tiles: 370 -> 470 - 510 TFLOP/s)
