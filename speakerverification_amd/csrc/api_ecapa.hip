@@ -37,17 +37,16 @@ static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, 
     // F32X3: se_apply also leaves each block output in the S32 split layout (CAT's twin), so tdnn1 of the next block and mfa read
     // their A operand without a conversion pass
     char* cat32 = h->cat_s32 ? static_cast<char*>(h->cat_s32) + r0 * C3 * 4 : nullptr;
-    // ... and when every consumer of a block output takes the split operand at this batch size (tdnn1 of the next block, mfa: the
-    // persistent X3 kernel; the next se_apply reads its residual as hi + lo), the fp32 copy is not written at all
-    auto x3_route = [&](const ConvLayer& L, const void* a32, int lda32, bool cs) {
-        if (!h->x3 || !L.Ws32 || !h->s32_buf || !a32) return false;
-        GemmParams q = conv_params(h, L, a32, lda32, MFA, L.N, M, T);
-        q.W = L.Ws32; q.x3 = 2; q.act1 = ACT_GELU;
-        if (cs) { q.colsum = cs_base; q.colsum_sq = 1; q.colsum_stride = h->colsum_region; }
-        return gemm_pw3x3_supported(q);
-    };
-    const bool s32_only = cat32 && x3_route(h->tdnn1[1], cat32, C3, false) && x3_route(h->tdnn1[2], cat32, C3, false) &&
-                          x3_route(h->mfa, cat32, C3, cs_base != nullptr) && !h->opt.x3_keep_f32;
+    // ... and when every consumer of a block output takes the split operand at this batch size (tdnn1 of the next block, mfa with its
+    // column sums: the persistent X3 kernel; the next se_apply reads its residual as hi + lo), the fp32 copy is not written at all
+    auto tdnn1_params = [&](int i, const void* a, int lda) { GemmParams p = conv_params(h, h->tdnn1[i], a, lda, H1, C, M, T); p.act1 = ACT_GELU; return p; };
+    GemmParams pm = conv_params(h, h->mfa, CAT, C3, MFA, C3, M, T);
+    pm.act1 = ACT_GELU;
+    pm.colsum = cs_base; pm.colsum_sq = 1; pm.colsum_stride = h->colsum_region;
+    GemmPlan gm = conv_plan(h, h->mfa, pm, cat32, C3);
+    const bool s32_only = cat32 && conv_plan(h, h->tdnn1[1], tdnn1_params(1, nullptr, C3), cat32, C3).x3 &&
+                          conv_plan(h, h->tdnn1[2], tdnn1_params(2, nullptr, C3), cat32 + (size_t)C * 4, C3).x3 && gm.x3 && (gm.colsum_groups || !pm.colsum) &&
+                          !h->opt.x3_keep_f32;
     if (s32_only) h->cat_f32_stale = true;
     bool b0_done = false, x0_s32 = false, b0_cv = false;
     GemmParams q0;
@@ -61,7 +60,7 @@ static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, 
         q.W = L.Wcv; q.Wrows = L.N; q.x3 = 2; q.K = L.taps * L.cv_cin; q.Kp = L.cv_Kp; q.cin = L.cv_cin; q.act1 = ACT_GELU;
         // (with s32_only and tdnn1 of the first block on the X3 kernel, X0 itself is written in the split layout: no conversion pass,
         //  block 1's residual is read as hi + lo, svhip_get_stage rebuilds the fp32 view)
-        q.y_s32 = (s32_only && x3_route(h->tdnn1[0], X0, C, false)) ? 1 : 0;
+        q.y_s32 = (s32_only && conv_plan(h, h->tdnn1[0], tdnn1_params(0, nullptr, C), X0, C).x3) ? 1 : 0;
         q.in_scale = xscale;
         b0_cv = gemm_pw3cv_supported(q);
     }
@@ -92,7 +91,6 @@ static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, 
     const void* xin32 = x0_s32 ? X0 : nullptr;
     int ldin32 = C;
     for (int i = 0; i < 3; ++i) {
-        const void* h2_32 = nullptr;      // F32X3: the chain output in the S32 layout (tdnn2's A operand)
         // F32X3: seven launches of gemm_pw3's Res2Net step form; step j reads U_j = c_j + y_{j-1} (S32) and writes y_j (S32, into the
         // chain output) and U_{j+1}; no fp32 copy of the chain exists
         char* h2s = h->h2_s32 ? static_cast<char*>(h->h2_s32) + r0 * C * 4 : nullptr;
@@ -104,21 +102,23 @@ static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, 
             if (j < 7) { q.R = static_cast<const float*>(H1) + (size_t)(j + 1) * C8; q.ldr = C; q.Y2 = us[j & 1]; q.lda2 = C8; }
             return q;
         };
+        // tdnn2; its epilogue also leaves per-utterance column sums (the SE squeeze) when the pw2 kernel runs
+        GemmParams p2 = conv_params(h, h->tdnn2[i], H2, C, H3, C, M, T);
+        p2.act1 = ACT_GELU;
+        p2.colsum = cs_base; p2.colsum_stride = h->colsum_region;
         // (C / 8 = 128: the dedicated 128 x 128 kernel, two workgroups per CU, any batch size; C / 8 = 64, or SVHIP_R2_BIG=1: the R2 form
         //  of the persistent 256 x 256 kernel)
         const bool r2_small = h->x3 && h2s && us[0] && us[1] && h->res2[i][0].Ws32 && !h->opt.r2_big && r2_step_supported(step_params(1)) &&
-                              x3_route(h->tdnn2[i], h2s, C, false);      // (tdnn2 must be able to read the chain output in the split layout)
+                              conv_plan(h, h->tdnn2[i], p2, h2s, C).x3;      // (tdnn2 must be able to read the chain output in the split layout)
         const bool r2_plan = r2_small || (h->x3 && h2s && us[0] && us[1] && h->res2[i][0].Ws32 && gemm_pw3r2_supported(step_params(1)));
+        GemmParams p1 = tdnn1_params(i, (s32_only && (i > 0 || x0_s32)) ? nullptr : xin, ldin);
         if (r2_plan) {      // tdnn1 writes the pass-through chunk and the first step's input in the split layout itself (when it takes the X3 kernel)
-            h->side_a = h2s; h->side_lda = C; h->side_b = us[0]; h->side_ldb = C8; h->side_c = C8;
+            p1.side_a = h2s; p1.side_lda = C; p1.side_b = us[0]; p1.side_ldb = C8; p1.side_c = C8;
         }
-        GemmParams p1 = conv_params(h, h->tdnn1[i], (s32_only && (i > 0 || x0_s32)) ? nullptr : xin, ldin, H1, C, M, T);
-        p1.act1 = ACT_GELU;
-        if ((rc = conv_gemm(h, h->tdnn1[i], p1, xin32, ldin32))) return rc;
-        const bool side_done = h->side_done;
-        h->side_c = 0;
+        GemmPlan g1;
+        if ((rc = conv_gemm(h, h->tdnn1[i], p1, xin32, ldin32, &g1))) return rc;
         if (r2_plan) {
-            if (!side_done) {
+            if (!g1.side) {
                 if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(H1), C, h2s, M, C8, st, C); }))) return rc;
                 if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(H1) + C8, C, us[0], M, C8, st, C8); }))) return rc;
             }
@@ -128,7 +128,7 @@ static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, 
                     if ((rc = run(h, "r2_step", (double)M * h->res2[i][j - 1].flops_per_row, [&]() { return launch_r2_step(q, st); }))) return rc;
                 } else if ((rc = run(h, "gemm_pw3r2", (double)M * h->res2[i][j - 1].flops_per_row, [&]() { return launch_gemm_pw3r2(q, st); }))) return rc;
             }
-            h2_32 = h2s;
+            p2.A = nullptr;      // (tdnn2 reads the chain output in the S32 layout only)
         } else if (bf && res2net_chain_supported(C, T, h->res2[i][0].dil, h->res2[i][0].Kp)) {
             Res2Params rp;
             rp.H1 = H1; rp.H2 = H2; rp.ld = C; rp.T = T; rp.dil = h->res2[i][0].dil; rp.Kp = h->res2[i][0].Kp;
@@ -150,12 +150,9 @@ static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, 
                 if ((rc = conv_gemm(h, h->res2[i][j - 1], p))) return rc;
             }
         }
-        // tdnn2; its epilogue also leaves per-utterance column sums (the SE squeeze) when the pw2 kernel runs
-        GemmParams p2 = conv_params(h, h->tdnn2[i], r2_plan ? nullptr : H2, C, H3, C, M, T);
-        p2.act1 = ACT_GELU;
-        p2.colsum = cs_base; p2.colsum_stride = h->colsum_region;
-        if ((rc = conv_gemm(h, h->tdnn2[i], p2, h2_32, C))) return rc;
-        const bool from_part = h->last_colsum_done;      // the squeeze comes straight from the GEMM's column-sum partials
+        GemmPlan g2;
+        if ((rc = conv_gemm(h, h->tdnn2[i], p2, r2_plan ? h2s : nullptr, C, &g2))) return rc;
+        const bool from_part = g2.colsum_groups != 0;      // the squeeze comes straight from the GEMM's column-sum partials
         if (!from_part) {
             if ((rc = run(h, "se_mean", 0, [&]() { return launch_colmean(H3, bf, C, B, T, C, d_mean, st); }))) return rc;
         }
@@ -163,7 +160,7 @@ static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, 
                  return launch_se_mlp(from_part ? nullptr : d_mean, from_part ? cs_base : nullptr, T,
                                       bf ? (const void*)h->se1_bf[i] : (const void*)h->se1[i].W, h->se1[i].bias,
                                       bf ? (const void*)h->se2T_bf[i] : (const void*)h->se2T[i], h->se2[i].bias, d_s2, bf, B, C, 128, st,
-                                      h->last_colsum_groups);
+                                      from_part ? g2.colsum_groups : 8);      // (8: any count the kernel takes; no partials are read)
              }))) return rc;
         void* xout = off(CAT, (size_t)i * C, e);
         void* xout32 = cat32 ? cat32 + (size_t)i * C * 4 : nullptr;
@@ -177,12 +174,10 @@ static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, 
         ldin = C3;
         ldin32 = C3;
     }
-    GemmParams pm = conv_params(h, h->mfa, s32_only ? nullptr : CAT, C3, MFA, C3, M, T);
-    pm.act1 = ACT_GELU;
-    pm.colsum = cs_base; pm.colsum_sq = 1; pm.colsum_stride = h->colsum_region;
-    if ((rc = conv_gemm(h, h->mfa, pm, cat32, C3))) return rc;
-    if (h->last_colsum_done) {
-        if ((rc = run(h, "colsum_finalize", 0, [&]() { return launch_colsum_finalize(cs_base, h->colsum_region, true, B, T, C3, M, d_gstats, 1e-12f, st, h->last_colsum_groups); }))) return rc;
+    if (s32_only) pm.A = nullptr;
+    if ((rc = conv_gemm(h, h->mfa, pm, cat32, C3, &gm))) return rc;
+    if (gm.colsum_groups) {
+        if ((rc = run(h, "colsum_finalize", 0, [&]() { return launch_colsum_finalize(cs_base, h->colsum_region, true, B, T, C3, M, d_gstats, 1e-12f, st, gm.colsum_groups); }))) return rc;
     } else {
         if ((rc = run(h, "asp_gstats", 0, [&]() { return launch_colstats(MFA, bf, C3, B, T, C3, d_gstats, 1e-12f, st); }))) return rc;
     }

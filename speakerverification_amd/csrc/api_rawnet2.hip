@@ -8,20 +8,9 @@ namespace svhip {
 // conv2 + 1 x 1 shortcut of a RawNet2 block as ONE conv-gather GEMM: K = 3 * cout conv columns of hb, then cin columns of `pre`
 static GemmParams conv2sc_params(svhip_handle* h, const svhip_handle::RnBlock& K, const void* pre, const void* hb, void* o, int M, int T) {
     GemmParams p = conv_params(h, K.conv2, hb, K.cout, o, K.cout, M, T);
-    p.W = K.conv2sc_W; p.Kp = K.conv2.K + K.cin; p.zero_page = zero_page_for(h, hb); p.pad_mode = PAD_ZERO;
+    p.W = K.conv2sc_W; p.Kp = K.conv2.K + K.cin; p.pad_mode = PAD_ZERO;
     p.A3 = pre; p.lda3 = K.cin; p.K3 = K.cin;
     return p;
-}
-static bool conv2sc_fits(svhip_handle* h, const svhip_handle::RnBlock& K, const void* pre, const void* hb, void* o, int M, int T) {
-    const GemmParams p = conv2sc_params(h, K, pre, hb, o, M, T);
-    return gemm_pw2_supported(p, true) && gemm_route(p, true) == ROUTE_PW2;
-}
-
-// would conv_gemm route this residual-free convolution to the persistent conv-gather kernel?
-static bool conv_cv_persistent(svhip_handle* h, const ConvLayer& L, const void* A, int lda, int M, int T, int pad_mode) {
-    GemmParams p = conv_params(h, L, A, lda, h->d_emb, L.N, M, T);      // (Y: any 16-byte aligned pointer; the route does not depend on it)
-    p.zero_page = zero_page_for(h, A); p.pad_mode = pad_mode;
-    return h->bf16 && gemm_route(p, true) == ROUTE_PW3CV;
 }
 
 // RawNet2.forward (models/RawNet2_custom.py:161-227) on device-resident waveforms (B, L), utterances [b0, b0 + B) of the call,
@@ -67,16 +56,32 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         h->rn_snap_T = Tn; h->rn_snap_C = Cn;
         return SVHIP_OK;
     };
-    // F32X3: will block `bn` (entered with Tn frames) run its convolutions on the 128 x 128 split kernel (r2_step.hip modes 1 / 2)?  Its
-    // producer then writes lrelu(bn1(x)) straight in the S32 layout (pre_is_s32) instead of fp32
-    auto x3_step_block = [&](int bn, int Tn) {
-        if (bn > 7 || !h->x3 || h->opt.rn_step_off || stop_after >= 0 || snap_at >= 0) return false;
-        const svhip_handle::RnBlock& Kn = h->rn_blocks[bn];
-        return Kn.cin % 32 == 0 && Kn.cout % 128 == 0 && Kn.conv1.Ws32 && Kn.conv2.Ws32 && (!Kn.has_shortcut || Kn.shortcut.Ws32) && Tn >= 2;
+    // F32X3: does block `bn`, entered with Tn frames, run its convolutions (and its projection shortcut) on the 128 x 128 split kernel
+    // (r2_step.hip, modes 1 / 2)?  a1: its pre-activation lrelu(bn1(x)) in the S32 layout; xb: its input x.  (Otherwise they run on the
+    // tiled kernel that splits its fp32 operands in registers: 170 - 190 TFLOP/s.)
+    struct RnStep { bool ok = false; GemmParams q0, q1, q2; };
+    auto rn_step_plan = [&](int bn, int Tn, const void* a1, const void* xb) {
+        RnStep s;
+        if (bn > 7 || !h->x3 || h->opt.rn_step_off) return s;
+        const svhip_handle::RnBlock& K = h->rn_blocks[bn];
+        GemmParams& q1 = s.q1;                           // conv1: pre (S32) -> lrelu(bn2(.)) in S32, conv2's operand
+        q1 = conv_params(h, K.conv1, a1, K.cin, hb, K.cout, B * Tn, Tn);
+        q1.W = K.conv1.Ws32; q1.x3 = 2; q1.pad_mode = PAD_ZERO; q1.zero_page = h->d_zeros;
+        GemmParams& q2 = s.q2 = q1;                      // conv2: h (S32) -> fp32, + the shortcut (identity x, or the projected one)
+        q2.A = hb; q2.lda = K.cout; q2.cin = K.cout; q2.K = 3 * K.cout; q2.Kp = q2.K; q2.W = K.conv2.Ws32; q2.scale = nullptr; q2.shift = nullptr;
+        q2.Y = o; q2.out_f32 = 1; q2.R = reinterpret_cast<const float*>(K.has_shortcut ? sc : xb); q2.ldr = K.cout;
+        GemmParams& q0 = s.q0 = q1;                      // projection shortcut (k = 1) of pre -> fp32, into the spare activation buffer
+        q0.W = K.shortcut.Ws32; q0.taps = 1; q0.K = K.cin; q0.Kp = K.cin; q0.scale = nullptr; q0.shift = nullptr; q0.Y = sc; q0.out_f32 = 1;
+        // (rn_step_supported also asks for the split weights and the shapes: cin % 32 == 0, cout % 128 == 0, Tn >= 2)
+        s.ok = rn_step_supported(q1, 1) && rn_step_supported(q2, 2) && (!K.has_shortcut || rn_step_supported(q0, 2));
+        return s;
     };
+    // a producer writes block bn's pre-activation straight in the S32 layout when the block takes the split kernel and neither developer
+    // hook is set (the block itself honours only rn_step_off: it splits an fp32 pre-activation first)
+    auto pre_s32_for = [&](int bn, int Tn, const void* xb) { return stop_after < 0 && snap_at < 0 && rn_step_plan(bn, Tn, pre, xb).ok; };
     bool pre_is_s32 = false;
     // (the split front-end writes block 0's pre-activation itself, in the S32 layout, when block 0 runs on the split convolution kernel)
-    const bool sinc_pre = sinc_x3 && x3_step_block(0, T);
+    const bool sinc_pre = sinc_x3 && pre_s32_for(0, T, x);
     if (sinc_pre) pre_is_s32 = true;
     // bf16 / fp16 handles: the fused chain's first block computes the conv front-end itself from the waveform (rn_block128's CONV
     // form) and x is never stored; option rn_conv_unfused stores x with rn_conv3_front and runs the plain block (bit-identical)
@@ -147,72 +152,47 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         // out = lrelu(bn1(x))                                                         RawNet_baseline.py:222
         // (blocks 1..7 get it from the previous block's AFMS pass, which writes x and lrelu(bn1(x)) together)
         if (((bi == 0 && first == 0) || stop_after >= 0) && !(bi == 0 && sinc_pre)) {
-            pre_is_s32 = x3_step_block(bi, T);
+            pre_is_s32 = pre_s32_for(bi, T, x);
             if ((rc = run(h, "rn_bn_act", 0, [&]() { return launch_rn_bn_act(x, pre, dt, K.bn1_scale, K.bn1_shift, M, K.cin, 0.3f, st, pre_is_s32); }))) return rc;
         }
-        // conv1 -> bn2 -> lrelu (epilogue), conv2 + shortcut                            :224-226
-        // A 1 x 1 shortcut rides in conv2's GEMM as extra K columns when the 256 x 256 kernel takes it (no shortcut tensor in HBM)
-        const bool fold_sc = K.has_shortcut && K.conv2sc_W && !no_tail && conv2sc_fits(h, K, pre, hb, o, M, T);
-        const void* resid = x;                                                       // identity shortcut takes the pre-BN x (:223)
-        const void* resid_in_tail = nullptr;
+        // (an fp32 pre-activation is split into a buffer that is free here: the next-x buffer when `sc` holds the projected shortcut)
+        void* const split_dst = K.has_shortcut ? xn : sc;
+        const RnStep s = rn_step_plan(bi, T, pre_is_s32 ? pre : split_dst, x);
+        if (pre_is_s32 && !s.ok) SV_FAIL(h, SVHIP_ERR_STATE, "RawNet2 block %d: split pre-activation without the split convolution route", bi);
         const bool tail_fused = !no_tail && rn_tail_supported(dt, K.downsample ? T / 3 : T, K.cout);
-        // F32X3: the block's convolutions (and its projection shortcut) on the 128 x 128 split kernel (r2_step.hip, modes 1 / 2) — pre in the
-        // S32 layout, conv1's output stays S32 (conv2's operand), conv2 adds the shortcut on the way out.  (Otherwise they run on the tiled
-        // kernel that splits its fp32 operands in registers: 170 - 190 TFLOP/s.)
         bool pooled_by_conv = false;
-        const bool x3_step = h->x3 && !h->opt.rn_step_off && K.cin % 32 == 0 && K.cout % 128 == 0 && K.conv1.Ws32 && K.conv2.Ws32 &&
-                             (!K.has_shortcut || K.shortcut.Ws32) && T >= 2;
-        auto project_shortcut = [&]() { return conv_gemm(h, K.shortcut, conv_params(h, K.shortcut, pre, K.cin, sc, K.cout, M, h->T)); };
-        if (K.has_shortcut && !fold_sc && !x3_step) {
-            if ((rc = project_shortcut())) return rc;
-            resid = sc;
-        }
-        if (pre_is_s32 && !x3_step) SV_FAIL(h, SVHIP_ERR_STATE, "RawNet2 block %d: split pre-activation without the split convolution route", bi);
-        if (x3_step) {
-            void* const split_dst = K.has_shortcut ? xn : sc;      // (fp32 pre: its S32 copy goes to a buffer that is free here — the next-x buffer when `sc` holds the projected shortcut)
-            GemmParams q1 = conv_params(h, K.conv1, pre_is_s32 ? pre : split_dst, K.cin, hb, K.cout, M, T);      // conv1: pre (S32) -> lrelu(bn2(.)) in S32
-            q1.W = K.conv1.Ws32; q1.x3 = 2; q1.pad_mode = PAD_ZERO; q1.zero_page = h->d_zeros;
-            GemmParams q2 = q1;                              // conv2: h (S32) -> fp32, + the shortcut (identity x, or the projected one)
-            q2.A = hb; q2.lda = K.cout; q2.cin = K.cout; q2.K = 3 * K.cout; q2.Kp = q2.K; q2.W = K.conv2.Ws32; q2.scale = nullptr; q2.shift = nullptr;
-            q2.Y = o; q2.out_f32 = 1; q2.R = reinterpret_cast<const float*>(K.has_shortcut ? sc : x); q2.ldr = K.cout;
-            GemmParams q0 = q1;                              // projection shortcut (k = 1) of pre -> fp32, into the spare activation buffer
-            q0.W = K.shortcut.Ws32; q0.taps = 1; q0.K = K.cin; q0.Kp = K.cin; q0.scale = nullptr; q0.shift = nullptr; q0.Y = sc; q0.out_f32 = 1;
-            const bool ok = rn_step_supported(q1, 1) && rn_step_supported(q2, 2) && (!K.has_shortcut || rn_step_supported(q0, 2));
-            if (ok) {
+        const void* resid_in_tail = nullptr;
+        // conv1 -> bn2 -> lrelu (epilogue), conv2 + shortcut                            :224-226
+        auto convs = [&]() -> int {
+            if (s.ok) {
                 if (!pre_is_s32 && (rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(reinterpret_cast<const float*>(pre), K.cin, split_dst, M, K.cin, st); }))) return rc;
-                if (K.has_shortcut && (rc = run(h, "rn_step", (double)M * K.shortcut.flops_per_row, [&]() { return launch_rn_step(q0, 2, st); }))) return rc;
-                if ((rc = run(h, "rn_step", (double)M * K.conv1.flops_per_row, [&]() { return launch_rn_step(q1, 1, st); }))) return rc;
+                if (K.has_shortcut && (rc = run(h, "rn_step", (double)M * K.shortcut.flops_per_row, [&]() { return launch_rn_step(s.q0, 2, st); }))) return rc;
+                if ((rc = run(h, "rn_step", (double)M * K.conv1.flops_per_row, [&]() { return launch_rn_step(s.q1, 1, st); }))) return rc;
                 // (a pooled block whose tail is not the fused kernel — the long utterances of layers 1 - 3: conv2 pools on its way out)
-                pooled_by_conv = K.downsample && !tail_fused && T >= 3 && !h->opt.rn_pool_off && rn_step_supported(q2, 3);
-                if ((rc = run(h, "rn_step", (double)M * K.conv2.flops_per_row, [&]() { return launch_rn_step(q2, pooled_by_conv ? 3 : 2, st); }))) return rc;
-                goto convs_done;
+                pooled_by_conv = K.downsample && !tail_fused && T >= 3 && !h->opt.rn_pool_off && rn_step_supported(s.q2, 3);
+                return run(h, "rn_step", (double)M * K.conv2.flops_per_row, [&]() { return launch_rn_step(s.q2, pooled_by_conv ? 3 : 2, st); });
             }
-            if (pre_is_s32) SV_FAIL(h, SVHIP_ERR_STATE, "RawNet2 block %d: the split convolution kernel refused a shape its producer was told it takes", bi);
-            if (K.has_shortcut && !fold_sc) {               // (the tiled route after all: its projection shortcut)
-                if ((rc = project_shortcut())) return rc;
+            // A 1 x 1 shortcut rides in conv2's GEMM as extra K columns when the 256 x 256 kernel takes it (no shortcut tensor in HBM)
+            const GemmParams psc = conv2sc_params(h, K, pre, hb, o, M, T);
+            const bool fold_sc = K.has_shortcut && K.conv2sc_W && !no_tail && conv_plan(h, K.conv2, psc).route == ROUTE_PW2;
+            const void* resid = x;                                                   // identity shortcut takes the pre-BN x (:223)
+            if (K.has_shortcut && !fold_sc) {
+                if ((rc = conv_gemm(h, K.shortcut, conv_params(h, K.shortcut, pre, K.cin, sc, K.cout, M, h->T)))) return rc;
                 resid = sc;
             }
-        }
-        {
             GemmParams p1 = conv_params(h, K.conv1, pre, K.cin, hb, K.cout, M, T);
             p1.act2 = ACT_LRELU03; p1.pad_mode = PAD_ZERO;
             if ((rc = conv_gemm(h, K.conv1, p1))) return rc;
-        }
-        if (fold_sc) {
-            GemmParams p = conv2sc_params(h, K, pre, hb, o, M, T);
-            const char* lbl = "gemm_pw2_conv";
-            char shaped2[96];
-            if (h->opt.layer_labels) { snprintf(shaped2, sizeof(shaped2), "%s M%d N%d K%d+%d", lbl, M, K.cout, K.conv2.K, K.cin); lbl = shaped2; }
-            if ((rc = run(h, lbl, (double)M * (K.conv2.flops_per_row + K.shortcut.flops_per_row), [&]() { return launch_gemm(p, true, st); }))) return rc;
-        } else {
+            if (fold_sc) return conv_gemm(h, K.conv2, psc);
+            GemmParams p2 = conv_params(h, K.conv2, hb, K.cout, o, K.cout, M, T);
+            p2.pad_mode = PAD_ZERO;
             // identity shortcut: with the fused block tail and conv2 on the persistent conv-gather kernel (which has no residual
             // operand) the tail adds the block input; otherwise conv2's epilogue does
-            if (!K.has_shortcut && tail_fused && bf && conv_cv_persistent(h, K.conv2, hb, K.cout, M, T, PAD_ZERO)) { resid_in_tail = x; resid = nullptr; }
-            GemmParams p2 = conv_params(h, K.conv2, hb, K.cout, o, K.cout, M, T);
-            p2.pad_mode = PAD_ZERO; p2.R = resid; p2.ldr = resid ? K.cout : 0;
-            if ((rc = conv_gemm(h, K.conv2, p2))) return rc;
-        }
-    convs_done:
+            if (!K.has_shortcut && tail_fused && conv_plan(h, K.conv2, p2).route == ROUTE_PW3CV) resid_in_tail = x;
+            else p2.R = resid, p2.ldr = K.cout;
+            return conv_gemm(h, K.conv2, p2);
+        };
+        if ((rc = convs())) return rc;
         // AFMS gate; the same pass writes the next consumer's lrelu(bn(.)): block bi+1's bn1, or the aggregation BN after block 7
         const float* nsc = bi < 7 ? h->rn_blocks[bi + 1].bn1_scale : h->rn_agg_scale;
         const float* nsh = bi < 7 ? h->rn_blocks[bi + 1].bn1_shift : h->rn_agg_shift;
@@ -222,7 +202,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         const int Tn = K.downsample ? T / 3 : T;
         if (tail_fused) {
             // max-pool + AFMS + next pre-activation in one launch, the pooled activation held in registers      :228-229, :62-68
-            const bool tail_s32 = npre && x3_step_block(bi + 1, Tn);      // (F32X3: the next block's operand straight in the S32 layout)
+            const bool tail_s32 = npre && pre_s32_for(bi + 1, Tn, xn);      // (F32X3: the next block's operand straight in the S32 layout)
             char tl[48] = "rn_tail";
             if (h->opt.layer_labels) snprintf(tl, sizeof(tl), "rn_tail T%d C%d", T, K.cout);
             if ((rc = run(h, tl, 2.0 * B * K.cout * K.cout, [&]() {
@@ -248,7 +228,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
                      return launch_rn_afms_gate(rn_mean, 1, B, K.cout, 1, K.afms_fcT, K.afms_fc.bias, rn_gate[0], st);
                  }))) return rc;
             // (F32X3: when the next block runs on the split convolution kernel its pre-activation is written in the S32 layout right here)
-            const bool next_s32 = npre && x3_step_block(bi + 1, T);
+            const bool next_s32 = npre && pre_s32_for(bi + 1, T, xn);
             if ((rc = run(h, "rn_afms_apply", 0, [&]() { return launch_rn_afms_apply(y, x_dead ? nullptr : xn, dt, K.alpha, rn_gate[0], B, T, K.cout, st, nsc, nsh, npre, 0.3f, next_s32); }))) return rc;
             pre_is_s32 = next_s32;
         }

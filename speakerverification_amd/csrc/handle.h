@@ -152,9 +152,6 @@ struct svhip_handle {
     size_t rn_buf_bytes = 0;      // RawNet2: payload bytes of each activation buffer; a 256-byte zero tail follows (the zero page of the
                                   // persistent conv-gather kernel must sit behind its A operand, within 4 GiB)
     void* s32_buf = nullptr;      // SVHIP_F32X3: the A operand of the current big GEMM in the S32 split layout (M x 3C x 4 bytes)
-    void *side_a = nullptr, *side_b = nullptr;      // pending S32 side outputs of the next conv_gemm (GemmParams::side_*), consumed by it
-    int side_lda = 0, side_ldb = 0, side_c = 0;
-    bool side_done = false;       // ... and whether that GEMM wrote them
     bool x0_is_s32 = false;       // SVHIP_F32X3: the last forward wrote blocks.0's output (X0) in the split layout
     bool cat_f32_stale = false;   // SVHIP_F32X3: the last forward left the block outputs only in cat_s32 (svhip_get_stage converts on demand)
     void* cat_s32 = nullptr;      // SVHIP_F32X3: the SE-Res2Net block outputs (the CAT buffer) in the S32 layout, written by se_apply
@@ -162,8 +159,6 @@ struct svhip_handle {
     void* u_s32[2] = {};
     float* d_colsum = nullptr;    // pw2 column-sum partials, per lane: [sum | sumsq] x (tiles*4) x 3C floats
     int64_t colsum_region = 0;    // floats per (lane, kind) region
-    bool last_colsum_done = false;
-    int last_colsum_groups = 8;   // row groups per tile in the partials the last GEMM wrote (8: pw2, 2: pw3)
     void* X_in = nullptr;         // (M, n_mels)
     void* X0 = nullptr;           // (M, C)
     void *H1 = nullptr, *H2 = nullptr, *H3 = nullptr;   // (M, C)
@@ -286,10 +281,20 @@ int finalize_ecapa(svhip_handle* h);
 int finalize_rawnet2(svhip_handle* h);
 int alloc_workspace(svhip_handle* h);
 
-// api_gemm.hip: the GEMM of one conv layer
-const void* zero_page_for(const svhip_handle* h, const void* A);
+// api_gemm.hip: the GEMM of one conv layer.  conv_plan is the one place that decides its kernel: conv_gemm launches what it returns,
+// and the producers of an operand ask it too, so that they write the layout that kernel reads.
+struct GemmPlan {
+    GemmParams q;                     // the parameters of the launch
+    bool x3 = false;                  // gemm_pw3x3 (F32X3, S32 operands); otherwise launch_gemm, which takes `route`
+    GemmRoute route = ROUTE_GENERIC;
+    bool side = false;                // the launch writes the side outputs (GemmParams::side_*)
+    int colsum_groups = 0;            // ... and column-sum partials with this many row groups per tile (0: none)
+    double flops = 0;
+    char label[96] = "";              // profile label: names the kernel instance (one label == one kernel symbol in a rocprofv3 trace)
+};
 GemmParams conv_params(const svhip_handle* h, const ConvLayer& L, const void* A, int lda, void* Y, int ldy, int M, int T);
-int conv_gemm(svhip_handle* h, const ConvLayer& L, GemmParams p, const void* A_s32 = nullptr, int lda_s32 = 0);
+GemmPlan conv_plan(const svhip_handle* h, const ConvLayer& L, GemmParams p, const void* A_s32 = nullptr, int lda_s32 = 0);
+int conv_gemm(svhip_handle* h, const ConvLayer& L, const GemmParams& p, const void* A_s32 = nullptr, int lda_s32 = 0, GemmPlan* plan = nullptr);
 
 // api.hip: a forward over the utterances [b0, b0 + B) of the call, enqueued on h->cur, as `lanes` batch slices
 using ForwardPart = int (*)(svhip_handle* h, const float* in, int b0, int B);
