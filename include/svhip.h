@@ -51,8 +51,16 @@ typedef enum svhip_status {
  * SVHIP_MODEL_RAWNET2_CONV (added under ABI v5): front_proc='conv' — conv1 = Conv1d(1, 128, 3, stride=3) with bias straight on the
  * waveform (RawNet2_custom.py:45-52,166-169), the same residual stack and aggregate='asp', att_dim=128 behind it; any L >= 2187
  * (floor(L / 3) frames pass six max_pool1d(3) stages), one handle per L like every model.  Weights: conv1.* instead of ln.*,
- * first_conv.* and first_bn.* (140 tensors). */
-enum { SVHIP_MODEL_ECAPA = 0, SVHIP_MODEL_RAWNET2 = 1, SVHIP_MODEL_NONE = 2 /* fbank + scoring only */, SVHIP_MODEL_RAWNET2_CONV = 3 };
+ * first_conv.* and first_bn.* (140 tensors).
+ * SVHIP_MODEL_RAWNET3 (added under ABI v5): RawNet3.MainModel with its defaults, the RawNet3 branch of Raw3_ECAPA (models/RawNet3.py,
+ * RawNet_baseline.py:27-159): pre-emphasis + InstanceNorm1d(1) + ParamSincFB(256, 251, stride 10) + log + time-mean front-end, three
+ * Bottle2neck layers (C = 1024, scale 8, dilations 2 / 3 / 4, max-pools 5 / 3 / none), layer4 (3072 -> 1536), context attentive
+ * statistics pooling with one attention logit per frame, bn5 and fc6.  embed_dim = nOut, samples = L (any L >= 541: T0 = (L - 251) / 10 + 1
+ * frames, T0 / 5 / 3 >= 2 frames reach the pooling, whose unbiased variance needs two); channels 0 or 1024; compute SVHIP_F32 (the
+ * filterbank sums in fp64) or SVHIP_BF16 only.  Weights: the 234 names of its state dict (bn1.*, bn6.* and preprocess.0.flipped_filter
+ * included; bn1 and bn6 are not used by the forward, the filters are built from conv1.filterbank.{low_hz_, band_hz_, window_, n_}). */
+enum { SVHIP_MODEL_ECAPA = 0, SVHIP_MODEL_RAWNET2 = 1, SVHIP_MODEL_NONE = 2 /* fbank + scoring only */, SVHIP_MODEL_RAWNET2_CONV = 3,
+       SVHIP_MODEL_RAWNET3 = 4 };
 enum { SVHIP_F32 = 0, SVHIP_BF16 = 1, SVHIP_I64 = 2, SVHIP_F32X3 = 3 /* compute only */, SVHIP_F16 = 4 /* compute only */ };
 enum { SVHIP_IN_DEVICE = 1, SVHIP_OUT_DEVICE = 2, SVHIP_ASYNC = 4 };
 

@@ -23,7 +23,8 @@ from . import _lib
 
 MAGIC = b"SVHIPWB1"
 _MODEL_IDS = {"ECAPA_TDNN": _lib.MODEL_ECAPA, "ecapa": _lib.MODEL_ECAPA, "RawNet2_custom": _lib.MODEL_RAWNET2,
-              "rawnet2": _lib.MODEL_RAWNET2, "RawNet2_custom_conv": _lib.MODEL_RAWNET2_CONV, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV}
+              "rawnet2": _lib.MODEL_RAWNET2, "RawNet2_custom_conv": _lib.MODEL_RAWNET2_CONV, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV,
+              "RawNet3": _lib.MODEL_RAWNET3, "rawnet3": _lib.MODEL_RAWNET3}
 
 
 def model_id(model) -> int:
@@ -138,6 +139,8 @@ FUSION_MODELS = {
     "Raw_ECAPA_sinc_asp": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom", ".rawnet2")),
     "Raw_ECAPA": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom", ".rawnet2")),
     "Raw_ECAPA_conv_asp": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom_conv", ".rawnet2")),
+    # Raw3_ECAPA.py: the raw-waveform branch is RawNet3, attribute `rawnet`; its blob's model id is SVHIP_MODEL_RAWNET3
+    "Raw3_ECAPA": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet.", "RawNet3", ".rawnet3")),
 }
 
 
@@ -151,7 +154,8 @@ def convert_checkpoint(src, dst, model) -> int:
 
     A fusion checkpoint (``model`` one of FUSION_MODELS — ``Raw_ECAPA_sinc_asp``, ``Raw_ECAPA``, ``Raw_ECAPA_conv_asp``: keys
     ``__S__.ECAPA_TDNN.*`` / ``__S__.rawnet2v2.*``, Raw_ECAPA*.py:22-28) becomes one blob per branch, ``dst + '.ecapa'`` and ``dst + '.rawnet2'`` — a handle is one
-    network, and ``Raw_ECAPA.load_blob(dst)`` reads the pair back."""
+    network, and ``Raw_ECAPA.load_blob(dst)`` reads the pair back.  ``Raw3_ECAPA`` (keys ``__S__.ECAPA_TDNN.*`` / ``__S__.rawnet.*``)
+    writes ``dst + '.ecapa'`` and ``dst + '.rawnet3'``."""
     if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
         import torch  # host-side only: the one place a pickle is read
         state = torch.load(src, map_location="cpu")     # the reference's 'cpu:0' is rejected by current torch (DESIGN.md §2)
@@ -161,6 +165,11 @@ def convert_checkpoint(src, dst, model) -> int:
         state = src
     sd = embedding_state_dict(state)
     if model in FUSION_MODELS:
+        raw_prefix = FUSION_MODELS[model][1][0]
+        other = "rawnet2v2." if raw_prefix == "rawnet." else "rawnet."
+        if any(k.startswith(other) for k in sd):          # a RawNet2 fusion checkpoint as Raw3_ECAPA, or the other way round
+            raise ValueError(f"{model}: the checkpoint's raw-waveform branch is '{other}*' ("
+                             f"{'RawNet2' if other == 'rawnet2v2.' else 'RawNet3'}), not this model's '{raw_prefix}*'")
         front = "conv" if FUSION_MODELS[model][1][1] == "RawNet2_custom_conv" else "sinc"
         if front == "conv" and any(k.startswith("rawnet2v2.first_conv.") for k in sd):
             raise ValueError(f"{model}: the checkpoint's RawNet2 branch has a sinc front-end (rawnet2v2.first_conv.*)")
@@ -174,8 +183,8 @@ def convert_checkpoint(src, dst, model) -> int:
             write_blob(str(dst) + suffix, branch, sub)
             total += len(sub)
         return total
-    if any(k.startswith(("ECAPA_TDNN.", "rawnet2v2.")) for k in sd):
-        raise ValueError("this is a fusion checkpoint (ECAPA_TDNN.* / rawnet2v2.* keys): convert it with "
+    if any(k.startswith(("ECAPA_TDNN.", "rawnet2v2.", "rawnet.")) for k in sd):
+        raise ValueError("this is a fusion checkpoint (ECAPA_TDNN.* / rawnet2v2.* / rawnet.* keys): convert it with "
                          f"model= one of {sorted(FUSION_MODELS)} (one blob per branch)")
     write_blob(dst, model, sd)
     return len(sd)
@@ -185,8 +194,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("src")
     ap.add_argument("dst")
-    ap.add_argument("--model", default="ECAPA_TDNN", help="reference model name (ECAPA_TDNN, RawNet2_custom, RawNet2_custom_conv, Raw_ECAPA_sinc_asp, Raw_ECAPA, "
-                    "Raw_ECAPA_conv_asp)")
+    ap.add_argument("--model", default="ECAPA_TDNN", help="reference model name (ECAPA_TDNN, RawNet2_custom, RawNet2_custom_conv, RawNet3, Raw_ECAPA_sinc_asp, "
+                    "Raw_ECAPA, Raw_ECAPA_conv_asp, Raw3_ECAPA)")
     a = ap.parse_args(argv)
     n = convert_checkpoint(a.src, a.dst, a.model)
     print(f"{a.dst}: {n} tensors")

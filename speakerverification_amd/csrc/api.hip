@@ -192,7 +192,18 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) { g_create_error = std::string("no HIP device: ") + hipGetErrorString(e); return SVHIP_ERR_HIP; }
     if (cfg->device < 0 || cfg->device >= ndev) { g_create_error = "device ordinal out of range"; return SVHIP_ERR_INVALID; }
-    if (cfg->model != SVHIP_MODEL_ECAPA && !is_rawnet2(cfg->model) && cfg->model != SVHIP_MODEL_NONE) { g_create_error = "unknown model"; return SVHIP_ERR_INVALID; }
+    if (cfg->model != SVHIP_MODEL_ECAPA && !is_rawnet2(cfg->model) && cfg->model != SVHIP_MODEL_RAWNET3 && cfg->model != SVHIP_MODEL_NONE) {
+        g_create_error = "unknown model";
+        return SVHIP_ERR_INVALID;
+    }
+    if (cfg->model == SVHIP_MODEL_RAWNET3) {
+        if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16) { g_create_error = "RawNet3 runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_INVALID; }
+        if (cfg->channels != 0 && cfg->channels != 1024) { g_create_error = "RawNet3 is built for C = 1024 (channels 0 or 1024)"; return SVHIP_ERR_INVALID; }
+        if (cfg->samples < RN3_MIN_SAMPLES) {
+            g_create_error = "RawNet3 needs at least 541 samples: (L - 251) / 10 + 1 frames pooled by 5 and 3 must leave two (the unbiased variance)";
+            return SVHIP_ERR_INVALID;
+        }
+    }
     if (cfg->model == SVHIP_MODEL_ECAPA && (cfg->channels <= 0 || cfg->channels % 64 != 0)) { g_create_error = "ECAPA channels must be a positive multiple of 64"; return SVHIP_ERR_INVALID; }
     if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16 && cfg->compute != SVHIP_F32X3 && cfg->compute != SVHIP_F16) { g_create_error = "unknown compute mode"; return SVHIP_ERR_INVALID; }
     if (cfg->compute == SVHIP_F16 && !is_rawnet2(cfg->model)) { g_create_error = "SVHIP_F16 is RawNet2's 16-bit mode (ECAPA's is SVHIP_BF16)"; return SVHIP_ERR_UNSUPPORTED; }
@@ -319,6 +330,7 @@ int svhip_finalize_weights(svhip_handle* h) {
     int rc = SVHIP_ERR_UNSUPPORTED;
     if (h->cfg.model == SVHIP_MODEL_ECAPA) rc = finalize_ecapa(h);
     else if (is_rawnet2(h->cfg.model)) rc = finalize_rawnet2(h);
+    else if (h->cfg.model == SVHIP_MODEL_RAWNET3) rc = finalize_rawnet3(h);
     else SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
     if (rc) return rc;
     SV_HIP(h, hipDeviceSynchronize());
@@ -398,7 +410,7 @@ int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, fl
     if (L != h->cfg.samples) SV_FAIL(h, SVHIP_ERR_INVALID, "L=%d but the handle was created for %d samples", L, h->cfg.samples);
     if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
         SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
-    if (h->cfg.model != SVHIP_MODEL_ECAPA && !is_rawnet2(h->cfg.model))
+    if (h->cfg.model != SVHIP_MODEL_ECAPA && !is_rawnet2(h->cfg.model) && h->cfg.model != SVHIP_MODEL_RAWNET3)
         SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
     SV_HIP(h, hipSetDevice(h->cfg.device));
     const float* d_in = wav;
@@ -408,6 +420,8 @@ int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, fl
     }
     if (is_rawnet2(h->cfg.model)) {
         if ((rc = rawnet2_forward(h, d_in, B))) return rc;
+    } else if (h->cfg.model == SVHIP_MODEL_RAWNET3) {
+        if ((rc = rawnet3_forward(h, d_in, B))) return rc;
     } else {
         const int T = h->T;
         // bf16 handles without the instance-norm prologue: waveform -> the 16-bit operand of blocks.0 in two launches (fbank.hip, round 6)
@@ -540,6 +554,14 @@ int svhip_get_stage(svhip_handle* h, const char* name, float* out, int64_t* coun
     else if (n == "rn_x") { src = h->rn_dbg_x; rows = (size_t)B * h->rn_dbg_T; cols = ld = h->rn_dbg_C; }
     else if (n == "rn_snap") { src = h->rn_snap; rows = (size_t)B * h->rn_snap_T; cols = ld = h->rn_snap_C; }
     else if (n == "rn_pooled") { src = h->rn_pooled; rows = B; cols = ld = 1024; f32 = true; }
+    else if (n.rfind("rn3_", 0) == 0 && h->cfg.model == SVHIP_MODEL_RAWNET3) {      // RawNet3: rn3_front, rn3_layer1 .. 3, rn3_layer4, rn3_pooled
+        static const char* kStages[5] = {"rn3_front", "rn3_layer1", "rn3_layer2", "rn3_layer3", "rn3_layer4"};
+        int i = 0;
+        while (i < 5 && n != kStages[i]) ++i;
+        if (n == "rn3_pooled") { src = h->rn3_pooled; rows = B; cols = ld = 3072; f32 = true; }
+        else if (i == 5) SV_FAIL(h, SVHIP_ERR_INVALID, "unknown stage %s", name);
+        else { src = h->rn3_stage[i]; rows = (size_t)B * h->rn3_stage_T[i]; cols = h->rn3_stage_C[i]; ld = h->rn3_stage_ld[i]; }
+    }
     else if (n == "mel") {
         if (h->feat_is_stale) SV_FAIL(h, SVHIP_ERR_STATE, "stage mel: the last forward ran the fused front-end, which never forms the mel power "
                                       "tensor (option fbank_unfused = 1 keeps the separate kernels)");

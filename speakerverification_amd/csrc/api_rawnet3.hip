@@ -1,0 +1,127 @@
+// api_rawnet3.hip — the RawNet3 forward of libsvhip (reference models/RawNet3.py:88-150, Bottle2neck: RawNet_baseline.py:71-159).
+//
+// Buffers (alloc_workspace): three (B T0, 1024) activations P0 .. P2 and CAT (B T2, 3072), whose column thirds are the three stage
+// outputs [mp3(x1) | x2 | x3], so that layer4 reads the concatenation as one operand.
+//   front-end   y (fp32) in P1, x0 in its own buffer (kept for svhip_get_stage)
+//   layer1      residual(x0) -> P0, conv1(x0) -> P1, Res2Net steps P1 -> P2, conv3(P2) + P0 -> P1, pool 5 -> P2, AFMS -> x1 in P0
+//   layer2      conv1(x1) -> P1, steps -> P2, conv3(P2) + x1 -> P1, mp3(x1) -> CAT[0], pool 3 -> P2, AFMS -> x2 in CAT[1] and
+//               mp3(x1) + x2 -> P1 (layer3's input and its identity residual)
+//   layer3      conv1(P1) and conv3 -> the head of P2, steps -> the next (B T2, 1024) of P2, AFMS -> x3 in CAT[2] (x1 stays in P0)
+//   layer4      relu(W4 CAT + b4) -> P1; context pooling (attention activation in P2) -> pooled; fc6 -> embeddings
+#include "handle.h"
+
+namespace svhip {
+
+namespace {
+
+constexpr int C = 1024, W = 128, D = 1536;
+
+// One Bottle2neck on x (B T, cin) at row stride ldx, T frames in; its output y = AFMS(pool(.)) goes to (ydst, ldy), and with `add` the
+// same pass writes y + add to `sum`.  res: the identity residual (null: the layer's 1 x 1 residual conv of x into `rbuf`).
+// h1, h2, o: scratch (B T, 1024) buffers (o may be h1); pooled: (B T / P, 1024) scratch when P > 1.
+int bottle2neck(svhip_handle* h, const svhip_handle::Rn3Layer& Ly, const void* x, int ldx, int cin, int B, int T, int P, const void* res, void* rbuf,
+                void* h1, void* h2, void* o, void* pooled, void* ydst, int ldy, const void* add, int ldadd, void* sum, int ldsum) {
+    const int M = B * T, e = h->esz, dt = h->dt;
+    hipStream_t st = h->cur;
+    int rc;
+    if (!res) {                                                                      // residual = Conv1d(cin, C, 1, bias=False)(x)
+        if ((rc = conv_gemm(h, Ly.residual, conv_params(h, Ly.residual, x, ldx, rbuf, C, M, T)))) return rc;
+        res = rbuf;
+    }
+    GemmParams p1 = conv_params(h, Ly.conv1, x, ldx, h1, C, M, T);                   // bn1(relu(conv1(x)))
+    p1.act1 = ACT_RELU;
+    if ((rc = conv_gemm(h, Ly.conv1, p1))) return rc;
+    for (int i = 0; i < 7; ++i) {                                                    // sp = bns[i](relu(convs[i](sp + spx[i])))
+        const ConvLayer& K = Ly.convs[i];
+        const void* a = i == 0 ? h1 : off(h2, (size_t)(i - 1) * W, e);
+        GemmParams q = conv_params(h, K, a, C, off(h2, (size_t)i * W, e), C, M, T);
+        q.act1 = ACT_RELU; q.pad_mode = PAD_ZERO;
+        if (i > 0) { q.A2 = off(h1, (size_t)i * W, e); q.lda2 = C; }
+        if ((rc = conv_gemm(h, K, q))) return rc;
+    }
+    if ((rc = run(h, "rn3_copy_chunk", 0, [&]() { return launch_copy_cols(off(h1, (size_t)7 * W, e), C, off(h2, (size_t)7 * W, e), C, h->bf16, M, W, st); })))
+        return rc;                                                                   // the eighth chunk passes unchanged
+    GemmParams p3 = conv_params(h, Ly.conv3, h2, C, o, C, M, T);                     // bn3(relu(conv3(.))) + residual
+    p3.act1 = ACT_RELU; p3.R = res; p3.ldr = C;
+    if ((rc = conv_gemm(h, Ly.conv3, p3))) return rc;
+    const void* z = o;
+    const int Tn = T / P;
+    if (P > 1) {
+        if ((rc = run(h, "rn3_maxpool", 0, [&]() { return launch_rn3_maxpool(o, C, pooled, C, dt, B, T, C, P, st); }))) return rc;
+        z = pooled;
+    }
+    // AFMS: (z + alpha) * sigmoid(fc(mean_t z))                                        RawNet_baseline.py:58-65
+    if ((rc = run(h, "rn3_afms_mean", 0, [&]() { return launch_colmean(z, dt, C, B, Tn, C, h->rn3_mean, st); }))) return rc;
+    if ((rc = run(h, "rn3_afms_gate", 2.0 * B * C * C, [&]() {
+             return launch_rowvec_linear(h->rn3_mean, C, Ly.afms_fc.W, Ly.afms_fc.bias, h->rn3_gate, C, B, C, C, ACT_SIGMOID, st);
+         }))) return rc;
+    return run(h, "rn3_afms", 0, [&]() { return launch_rn3_afms(z, C, Ly.alpha, h->rn3_gate, ydst, ldy, add, ldadd, sum, ldsum, dt, B, Tn, C, st); });
+}
+
+}  // namespace
+
+// RawNet3.forward on device-resident waveforms (B, L), enqueued on h->cur (one slice: b0 is 0)
+static int rawnet3_forward_part(svhip_handle* h, const float* d_wav, int b0, int B) {
+    (void)b0;
+    const svhip_config& c = h->cfg;
+    const int L = c.samples, e = h->esz, dt = h->dt;
+    const int T0 = h->rn3_T0, T1 = T0 / 5, T2 = T1 / 3;
+    hipStream_t st = h->cur;
+    void *P0 = h->rn3_buf[0], *P1 = h->rn3_buf[1], *P2 = h->rn3_buf[2], *CAT = h->rn3_cat;
+    int rc;
+    auto stage = [&](int i, const void* src, int T, int Cn, int ld) { h->rn3_stage[i] = src; h->rn3_stage_T[i] = T; h->rn3_stage_C[i] = Cn; h->rn3_stage_ld[i] = ld; };
+
+    // front-end: log(|sinc(in_norm(pre_emph(x)))| + 1e-6) - mean_t                  RawNet3.py:88-99
+    float* y = static_cast<float*>(P1);
+    void* x0 = h->rn3_x0;
+    if ((rc = run(h, "rn3_sinc", 2.0 * B * RN3_FILTERS * RN3_TAPS * (double)T0, [&]() {
+             return launch_rn3_front(d_wav, B, L, T0, h->rn3_pre[0], h->rn3_pre[1], h->rn3_in_w, h->rn3_in_b, h->rn3_filt, !h->bf16, h->rn3_stats, y, st);
+         }))) return rc;
+    if ((rc = run(h, "rn3_front_mean", 0, [&]() { return launch_colmean(y, DT_F32, RN3_FILTERS, B, T0, RN3_FILTERS, h->rn3_mean, st); }))) return rc;
+    if ((rc = run(h, "rn3_center", 0, [&]() { return launch_rn3_center(y, h->rn3_mean, x0, dt, B, T0, st); }))) return rc;
+    stage(0, x0, T0, RN3_FILTERS, RN3_FILTERS);
+
+    // layer1 = Bottle2neck(256, 1024, dilation 2, pool 5): x1 -> P0
+    if ((rc = bottle2neck(h, h->rn3[0], x0, RN3_FILTERS, RN3_FILTERS, B, T0, 5, nullptr, P0, P1, P2, P1, P2, P0, C, nullptr, 0, nullptr, 0)))
+        return rc;
+    stage(1, P0, T1, C, C);
+    // mp3(x1) -> CAT[:, 0:1024), written once
+    if ((rc = run(h, "rn3_maxpool", 0, [&]() { return launch_rn3_maxpool(P0, C, CAT, 3 * C, dt, B, T1, C, 3, st); }))) return rc;
+    // layer2 = Bottle2neck(1024, 1024, dilation 3, pool 3), identity residual x1: x2 -> CAT[:, 1024:2048), mp3(x1) + x2 -> P1
+    if ((rc = bottle2neck(h, h->rn3[1], P0, C, C, B, T1, 3, P0, nullptr, P1, P2, P1, P2, off(CAT, C, e), 3 * C, CAT, 3 * C, P1, C)))
+        return rc;
+    stage(2, off(CAT, C, e), T2, C, 3 * C);
+    // layer3 = Bottle2neck(1024, 1024, dilation 4) on mp3(x1) + x2, which is also its residual: x3 -> CAT[:, 2048:3072)
+    void* h1 = P2;
+    void* h2 = off(P2, (size_t)B * T2 * C, e);
+    if ((rc = bottle2neck(h, h->rn3[2], P1, C, C, B, T2, 1, P1, nullptr, h1, h2, h1, nullptr, off(CAT, 2 * C, e), 3 * C, nullptr, 0, nullptr, 0))) return rc;
+    stage(3, off(CAT, 2 * C, e), T2, C, 3 * C);
+
+    // layer4: relu(Conv1d(3072, 1536, 1)(cat(mp3(x1), x2, x3)))                       RawNet3.py:107-108
+    const int M2 = B * T2;
+    GemmParams p4 = conv_params(h, h->rn3_l4, CAT, 3 * C, P1, D, M2, T2);
+    p4.act1 = ACT_RELU;
+    if ((rc = conv_gemm(h, h->rn3_l4, p4))) return rc;
+    stage(4, P1, T2, D, D);
+
+    // context attentive statistics pooling                                            RawNet3.py:112-142
+    // attention.0 on cat(x, mean_t x, std_t x): the time-constant two thirds are a per-utterance bias
+    if ((rc = run(h, "rn3_tstats", 0, [&]() { return launch_rn3_tstats(P1, D, dt, B, T2, D, h->rn3_tstat, st); }))) return rc;
+    if ((rc = run(h, "rn3_att_ctx", 2.0 * B * 128 * 2 * D, [&]() {
+             return launch_rowvec_linear(h->rn3_tstat, 2 * D, h->rn3_att_ctx.W, h->rn3_att_ctx.bias, h->rn3_ctx, 128, B, 128, 2 * D, ACT_NONE, st);
+         }))) return rc;
+    GemmParams pa = conv_params(h, h->rn3_att, P1, D, P2, 128, M2, T2);              // attention.2(relu(attention.0(.)))
+    pa.act1 = ACT_RELU; pa.bias_utt = h->rn3_ctx; pa.ld_bu = 128;
+    if ((rc = conv_gemm(h, h->rn3_att, pa))) return rc;
+    if ((rc = run(h, "rn3_pool", 0, [&]() {
+             return launch_rn3_ctx_pool(P2, 128, h->rn3_w2, h->rn3_b2, h->rn3_logit, P1, D, dt, B, T2, D, h->rn3_bn5_scale, h->rn3_bn5_shift, h->rn3_pooled, st);
+         }))) return rc;
+    // fc6 (out_bn=False: bn6 is not applied)                                         RawNet3.py:144-148
+    return run(h, "rn3_fc6", 2.0 * B * h->rn3_fc6.N * h->rn3_fc6.K, [&]() {
+        return launch_rowvec_linear(h->rn3_pooled, 2 * D, h->rn3_fc6.W, h->rn3_fc6.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * D, ACT_NONE, st);
+    });
+}
+
+int rawnet3_forward(svhip_handle* h, const float* d_wav, int B) { return forward_lanes(h, rawnet3_forward_part, d_wav, B, 1, B); }
+
+}  // namespace svhip

@@ -261,9 +261,45 @@ static void rawnet2_spec(const svhip_config& c, std::map<std::string, std::vecto
     spec["fc.weight"] = {(int64_t)c.embed_dim, 1024}; spec["fc.bias"] = {(int64_t)c.embed_dim};
 }
 
+// RawNet3.MainModel's defaults (RawNet3.py:172-186): the 234 names of its state dict, the unused bn1.*, bn6.* and the pre-emphasis
+// buffer included (the filterbank's window_ / n_ buffers are read: the checkpoint's values are the ones the filters are built from)
+static void rawnet3_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec) {
+    auto bn = [&](const std::string& p, int64_t n) {
+        spec[p + ".weight"] = {n}; spec[p + ".bias"] = {n}; spec[p + ".running_mean"] = {n};
+        spec[p + ".running_var"] = {n}; spec[p + ".num_batches_tracked"] = {};
+    };
+    const int64_t C = 1024, W = C / 8, D = 1536, nOut = c.embed_dim;
+    spec["preprocess.0.flipped_filter"] = {1, 1, 2}; spec["preprocess.1.weight"] = {1}; spec["preprocess.1.bias"] = {1};
+    spec["conv1.filterbank.low_hz_"] = {C / 8, 1}; spec["conv1.filterbank.band_hz_"] = {C / 8, 1};
+    spec["conv1.filterbank.window_"] = {125}; spec["conv1.filterbank.n_"] = {1, 125};
+    bn("bn1", C / 4);
+    for (int li = 1; li <= 3; ++li) {
+        const std::string p = "layer" + std::to_string(li);
+        const int64_t cin = li == 1 ? C / 4 : C;
+        spec[p + ".conv1.weight"] = {C, cin, 1}; spec[p + ".conv1.bias"] = {C};
+        bn(p + ".bn1", C);
+        for (int i = 0; i < 7; ++i) {
+            spec[p + ".convs." + std::to_string(i) + ".weight"] = {W, W, 3}; spec[p + ".convs." + std::to_string(i) + ".bias"] = {W};
+            bn(p + ".bns." + std::to_string(i), W);
+        }
+        spec[p + ".conv3.weight"] = {C, C, 1}; spec[p + ".conv3.bias"] = {C};
+        bn(p + ".bn3", C);
+        spec[p + ".afms.alpha"] = {C, 1}; spec[p + ".afms.fc.weight"] = {C, C}; spec[p + ".afms.fc.bias"] = {C};
+        if (cin != C) spec[p + ".residual.0.weight"] = {C, cin, 1};
+    }
+    spec["layer4.weight"] = {D, 3 * C, 1}; spec["layer4.bias"] = {D};
+    spec["attention.0.weight"] = {128, 3 * D, 1}; spec["attention.0.bias"] = {128};
+    bn("attention.2", 128);
+    spec["attention.3.weight"] = {1, 128, 1}; spec["attention.3.bias"] = {1};
+    bn("bn5", 2 * D);
+    spec["fc6.weight"] = {nOut, 2 * D}; spec["fc6.bias"] = {nOut};
+    bn("bn6", nOut);
+}
+
 void model_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec) {
     if (c.model == SVHIP_MODEL_ECAPA) ecapa_spec(c, spec);
     else if (is_rawnet2(c.model)) rawnet2_spec(c, spec);
+    else if (c.model == SVHIP_MODEL_RAWNET3) rawnet3_spec(c, spec);
 }
 
 static const HostTensor* getw(svhip_handle* h, const std::string& name) {
@@ -612,6 +648,83 @@ int finalize_rawnet2(svhip_handle* h) {
     return SVHIP_OK;
 }
 
+// ParamSincFB(256, 251).filters() (asteroid-filterbanks 0.4; its cos half is RawNet_baseline.py:339-357's formula) from the
+// checkpoint's low_hz_, band_hz_, window_ and n_, in fp64, stored tap-major [251][256]: cos filters 0..127, sin filters 128..255
+static int bake_sinc3(svhip_handle* h) {
+    const HostTensor *lo = getw(h, "conv1.filterbank.low_hz_"), *bd = getw(h, "conv1.filterbank.band_hz_"),
+                     *win = getw(h, "conv1.filterbank.window_"), *nn = getw(h, "conv1.filterbank.n_");
+    if (!lo || !bd || !win || !nn) SV_FAIL(h, SVHIP_ERR_MISSING, "missing conv1.filterbank tensors");
+    const int NF = RN3_FILTERS / 2, HK = 125;
+    std::vector<double> f((size_t)RN3_TAPS * RN3_FILTERS);
+    for (int i = 0; i < NF; ++i) {
+        const double low = 50.0 + std::fabs((double)lo->data[i]);
+        const double high = std::min(std::max(low + 50.0 + std::fabs((double)bd->data[i]), 50.0), 8000.0);
+        const double band = high - low;
+        for (int k = 0; k < HK; ++k) {
+            const double n = nn->data[k], w = win->data[k];
+            const double c = (std::sin(high * n) - std::sin(low * n)) / (n / 2) * w;     // cos half, left side
+            const double s = (std::cos(low * n) - std::cos(high * n)) / (n / 2) * w;     // sin half, left side
+            f[(size_t)k * RN3_FILTERS + i] = c / (2 * band);
+            f[(size_t)(RN3_TAPS - 1 - k) * RN3_FILTERS + i] = c / (2 * band);
+            f[(size_t)k * RN3_FILTERS + NF + i] = s / (2 * band);
+            f[(size_t)(RN3_TAPS - 1 - k) * RN3_FILTERS + NF + i] = -s / (2 * band);
+        }
+        f[(size_t)HK * RN3_FILTERS + i] = 2 * band / (2 * band);
+        f[(size_t)HK * RN3_FILTERS + NF + i] = 0.0;
+    }
+    if (!h->bf16) {
+        double* d;
+        int rc = dev_upload(h, &d, f);
+        h->rn3_filt = d;
+        return rc;
+    }
+    std::vector<float> ff(f.begin(), f.end());
+    float* d;
+    int rc = dev_upload(h, &d, ff);
+    h->rn3_filt = d;
+    return rc;
+}
+
+int finalize_rawnet3(svhip_handle* h) {
+    int rc;
+    const HostTensor* pf = getw(h, "preprocess.0.flipped_filter");
+    if (!pf) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor preprocess.0.flipped_filter");
+    h->rn3_pre[0] = pf->data[0]; h->rn3_pre[1] = pf->data[1];
+    if ((rc = upload_f32(h, "preprocess.1.weight", &h->rn3_in_w))) return rc;
+    if ((rc = upload_f32(h, "preprocess.1.bias", &h->rn3_in_b))) return rc;
+    if ((rc = bake_sinc3(h))) return rc;
+    const int T0 = h->rn3_T0;
+    double fl = 2.0 * RN3_FILTERS * RN3_TAPS * T0;
+    const int dil[3] = {2, 3, 4}, pool[3] = {5, 3, 1};
+    int T = T0;
+    for (int li = 0; li < 3; ++li) {
+        svhip_handle::Rn3Layer& Ly = h->rn3[li];
+        const std::string p = "layer" + std::to_string(li + 1);
+        if ((rc = make_conv(h, Ly.conv1, p + ".conv1.weight", p + ".conv1.bias", p + ".bn1", 1))) return rc;
+        for (int i = 0; i < 7; ++i)
+            if ((rc = make_conv(h, Ly.convs[i], p + ".convs." + std::to_string(i) + ".weight", p + ".convs." + std::to_string(i) + ".bias",
+                                p + ".bns." + std::to_string(i), dil[li]))) return rc;
+        if ((rc = make_conv(h, Ly.conv3, p + ".conv3.weight", p + ".conv3.bias", p + ".bn3", 1))) return rc;
+        Ly.has_residual = li == 0;
+        if (Ly.has_residual && (rc = make_conv(h, Ly.residual, p + ".residual.0.weight", "", "", 1))) return rc;
+        if ((rc = upload_f32(h, p + ".afms.alpha", &Ly.alpha))) return rc;
+        if ((rc = make_linear(h, Ly.afms_fc, p + ".afms.fc.weight", p + ".afms.fc.bias"))) return rc;
+        double per_row = Ly.conv1.flops_per_row + 7 * Ly.convs[0].flops_per_row + Ly.conv3.flops_per_row + (Ly.has_residual ? Ly.residual.flops_per_row : 0.0);
+        fl += (double)T * per_row + 2.0 * 1024 * 1024;
+        T /= pool[li];
+    }
+    if ((rc = make_conv(h, h->rn3_l4, "layer4.weight", "layer4.bias", "", 1))) return rc;
+    if ((rc = make_conv(h, h->rn3_att, "attention.0.weight", "", "attention.2", 1, 0, 1536))) return rc;
+    if ((rc = make_linear(h, h->rn3_att_ctx, "attention.0.weight", "attention.0.bias", 1536, 3 * 1536))) return rc;
+    if ((rc = upload_f32(h, "attention.3.weight", &h->rn3_w2))) return rc;
+    if ((rc = upload_f32(h, "attention.3.bias", &h->rn3_b2))) return rc;
+    if ((rc = make_bn(h, "bn5", 2 * 1536, &h->rn3_bn5_scale, &h->rn3_bn5_shift))) return rc;
+    if ((rc = make_linear(h, h->rn3_fc6, "fc6.weight", "fc6.bias"))) return rc;
+    fl += (double)T * (h->rn3_l4.flops_per_row + h->rn3_att.flops_per_row + 2.0 * 128) + 2.0 * 128 * 3072 + 2.0 * h->rn3_fc6.N * h->rn3_fc6.K;
+    h->flops_per_utt = fl;
+    return SVHIP_OK;
+}
+
 int alloc_workspace(svhip_handle* h) {
     const svhip_config& c = h->cfg;
     const size_t B = c.max_batch, T = h->T, M = B * T, C = c.channels, C3 = 3 * C, e = h->esz;
@@ -668,6 +781,29 @@ int alloc_workspace(svhip_handle* h) {
             h->lin_part_per_utt = (size_t)4 * (size_t)std::max(128, c.embed_dim);
             if ((rc = dev_alloc(h, &h->d_lin_part, B * h->lin_part_per_utt))) return rc;
         }
+    }
+    if (c.model == SVHIP_MODEL_RAWNET3) {
+        // three (B T0, 1024) activation buffers carry layer1 (RawNet3 forward, api_rawnet3.hip); the later stages reuse them
+        h->rn3_T0 = rn3_frames(c.samples);
+        const size_t M0 = B * (size_t)h->rn3_T0, T2 = (size_t)(h->rn3_T0 / 5 / 3);
+        if (T2 < 2) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance too short for RawNet3 (%d samples)", c.samples);
+        for (int i = 0; i < 3; ++i) {
+            char* q;
+            if ((rc = dev_alloc(h, &q, M0 * 1024 * e + 256))) return rc;
+            h->rn3_buf[i] = q;
+        }
+        char* q;
+        if ((rc = dev_alloc(h, &q, B * T2 * 3072 * e + 256))) return rc;
+        h->rn3_cat = q;
+        if ((rc = dev_alloc(h, &q, M0 * RN3_FILTERS * e + 256))) return rc;
+        h->rn3_x0 = q;
+        if ((rc = dev_alloc(h, &h->rn3_stats, B * 2))) return rc;
+        if ((rc = dev_alloc(h, &h->rn3_mean, B * 1024))) return rc;
+        if ((rc = dev_alloc(h, &h->rn3_gate, B * 1024))) return rc;
+        if ((rc = dev_alloc(h, &h->rn3_tstat, B * 3072))) return rc;
+        if ((rc = dev_alloc(h, &h->rn3_ctx, B * 128))) return rc;
+        if ((rc = dev_alloc(h, &h->rn3_logit, B * T2))) return rc;
+        if ((rc = dev_alloc(h, &h->rn3_pooled, B * 3072))) return rc;
     }
     if (c.model == SVHIP_MODEL_ECAPA) {
         char* p;

@@ -138,6 +138,32 @@ struct svhip_handle {
     const void* rn_dbg_x = nullptr; int rn_dbg_T = 0, rn_dbg_C = 0;   // SVHIP_RN_STOP developer hook (tests)
     void* rn_snap = nullptr; size_t rn_snap_cap = 0; int rn_snap_T = 0, rn_snap_C = 0;      // SVHIP_RN_SNAP=2: copy of block 2's pre-activation (stage "rn_snap")
 
+    // RawNet3 layers (SVHIP_MODEL_RAWNET3: RawNet3.py with the defaults of its MainModel, RawNet_baseline.py:71-159)
+    struct Rn3Layer {                         // Bottle2neck(k = 3, scale = 8): every BatchNorm follows a ReLU, so it is its conv's epilogue affine
+        svhip::ConvLayer conv1, convs[7], conv3, residual;      // conv1 + bn1, convs[i] + bns[i], conv3 + bn3; residual: 1 x 1, no bias (layer1)
+        bool has_residual = false;
+        float* alpha = nullptr;               // AFMS
+        svhip::LinearLayer afms_fc;
+    };
+    Rn3Layer rn3[3];
+    svhip::ConvLayer rn3_l4, rn3_att;         // layer4 (3072 -> 1536, bias, ReLU); attention.0 columns [0, 1536) with attention.2 as epilogue
+    svhip::LinearLayer rn3_att_ctx, rn3_fc6;  // attention.0 columns [1536, 4608) + its bias: the per-utterance bias of the time-constant inputs; fc6
+    float *rn3_w2 = nullptr, *rn3_b2 = nullptr;                 // attention.3: the per-frame logit
+    float *rn3_bn5_scale = nullptr, *rn3_bn5_shift = nullptr;
+    float *rn3_in_w = nullptr, *rn3_in_b = nullptr;             // preprocess.1 (InstanceNorm1d affine)
+    double rn3_pre[2] = {-0.97, 1.0};                           // preprocess.0.flipped_filter: y[i] = pre[0] x[i - 1] + pre[1] x[i]
+    void* rn3_filt = nullptr;                 // [251][256] tap-major sinc filters: fp64 on fp32 handles, fp32 on bf16 handles
+    int rn3_T0 = 0;                           // front-end frames; layer1 pools to T0 / 5, layer2 to T0 / 5 / 3
+    void* rn3_buf[3] = {};                    // (Bmax * T0, 1024) activations each (the front-end's fp32 output passes through rn3_buf[1])
+    void* rn3_x0 = nullptr;                   // (Bmax * T0, 256): the front-end output, layer1's operand
+    void* rn3_cat = nullptr;                  // (Bmax * T2, 3072): [mp3(x1) | x2 | x3], layer4's operand
+    double* rn3_stats = nullptr;              // (Bmax, 2) pre-emphasis / InstanceNorm statistics
+    float *rn3_mean = nullptr, *rn3_gate = nullptr;             // (Bmax, 1024): time means, AFMS gates
+    float *rn3_tstat = nullptr, *rn3_ctx = nullptr;             // (Bmax, 3072) [mean | std] of layer4's output; (Bmax, 128) attention bias
+    float *rn3_logit = nullptr, *rn3_pooled = nullptr;          // (Bmax * T2) per-frame logits; (Bmax, 3072) bn5(pooled)
+    const void* rn3_stage[5] = {};            // svhip_get_stage: front-end, layer1, layer2, layer3, layer4 outputs of the last forward
+    int rn3_stage_T[5] = {}, rn3_stage_C[5] = {}, rn3_stage_ld[5] = {};
+
     // workspace (device)
     float* d_wav = nullptr;       // (Bmax, L)
     float* d_feat = nullptr;      // (Bmax, n_mels, T) mel power
@@ -271,6 +297,7 @@ int run(svhip_handle* h, const char* label, double flops, F&& launch) {
 }
 
 inline bool is_rawnet2(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_CONV; }
+inline int rn3_frames(int L) { return (L - RN3_TAPS) / RN3_STRIDE + 1; }      // T0 of RawNet3's front-end
 inline void* off(void* base, size_t elems, int esz) { return reinterpret_cast<char*>(base) + elems * esz; }
 inline const void* off(const void* base, size_t elems, int esz) { return reinterpret_cast<const char*>(base) + elems * esz; }
 
@@ -279,6 +306,7 @@ int build_fbank_tables(svhip_handle* h);
 void model_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec);
 int finalize_ecapa(svhip_handle* h);
 int finalize_rawnet2(svhip_handle* h);
+int finalize_rawnet3(svhip_handle* h);
 int alloc_workspace(svhip_handle* h);
 
 // api_gemm.hip: the GEMM of one conv layer.  conv_plan is the one place that decides its kernel: conv_gemm launches what it returns,
@@ -300,8 +328,9 @@ int conv_gemm(svhip_handle* h, const ConvLayer& L, const GemmParams& p, const vo
 using ForwardPart = int (*)(svhip_handle* h, const float* in, int b0, int B);
 int forward_lanes(svhip_handle* h, ForwardPart part, const float* in, int B, int lanes, int per);
 
-// api_ecapa.hip, api_rawnet2.hip: the whole-batch forwards
+// api_ecapa.hip, api_rawnet2.hip, api_rawnet3.hip: the whole-batch forwards
 int ecapa_forward(svhip_handle* h, const float* d_feat, int B);
 int rawnet2_forward(svhip_handle* h, const float* d_wav, int B);
+int rawnet3_forward(svhip_handle* h, const float* d_wav, int B);
 
 }  // namespace svhip

@@ -368,6 +368,30 @@ hipError_t launch_rn_afms_gate(const float* part, int nparts, int B, int C, int 
                                hipStream_t stream);
 hipError_t launch_rn_attn_pool(const float* logits, const void* x, int dt, int B, int T, int C, float* out, hipStream_t stream);
 
+// ---------------------------------------------------------------------------------------------
+// RawNet3 (rawnet3.hip)
+// ---------------------------------------------------------------------------------------------
+constexpr int RN3_FILTERS = 256, RN3_TAPS = 251, RN3_STRIDE = 10;     // ParamSincFB(256, 251, stride=10) (RawNet3.py:35-41)
+constexpr int RN3_MIN_SAMPLES = 541;       // T0 = 30 frames -> 6 -> 2: the shortest input whose pooled statistics are finite
+// pre-emphasis [f0, f1] (the checkpoint's preprocess.0.flipped_filter) + InstanceNorm1d(1, eps 1e-4, affine in_w / in_b) + the
+// sinc filterbank (filt: [251][256] tap-major, fp64 when filt_f64, else fp32) + log(|.| + 1e-6): wav (B, L) -> y (B, T0, 256) fp32,
+// T0 = (L - 251) / 10 + 1; stats: (B, 2) doubles of scratch
+hipError_t launch_rn3_front(const float* wav, int B, int L, int T0, double f0, double f1, const float* in_w, const float* in_b, const void* filt,
+                            bool filt_f64, double* stats, float* y, hipStream_t stream);
+// x0 (B, T0, 256) in dt = y - mean[b, :] (the time mean, colmean of y); y and x0 may alias (fp32)
+hipError_t launch_rn3_center(const float* y, const float* mean, void* x0, int dt, int B, int T0, hipStream_t stream);
+// MaxPool1d(P) over frames: x (B * Tin, ldx) -> y (B * (Tin / P), ldy), columns [0, C)
+hipError_t launch_rn3_maxpool(const void* x, int ldx, void* y, int ldy, int dt, int B, int Tin, int C, int P, hipStream_t stream);
+// AFMS apply: y = (x + alpha) * gate[b] (gate (B, C) fp32); with `sum`: sum = y + add in the same pass
+hipError_t launch_rn3_afms(const void* x, int ldx, const float* alpha, const float* gate, void* y, int ldy, const void* add, int ldadd, void* sum, int ldsum,
+                           int dt, int B, int Tn, int C, hipStream_t stream);
+// stats (B, 2C) fp32 = [mean_t x | sqrt(clamp(unbiased var_t x, 1e-4, 1e4))]
+hipError_t launch_rn3_tstats(const void* x, int ldx, int dt, int B, int Tn, int C, float* stats, hipStream_t stream);
+// single-head context pooling: logit (B * Tn) = hatt . w2 + b2 (hatt (B * Tn, 128)), softmax over Tn, weighted mean / std of x, bn5 affine
+// -> pooled (B, 2C) fp32
+hipError_t launch_rn3_ctx_pool(const void* hatt, int ldh, const float* w2, const float* b2, float* logit, const void* x, int ldx, int dt, int B, int Tn, int C,
+                               const float* bn_scale, const float* bn_shift, float* pooled, hipStream_t stream);
+
 // synthetic waveforms from a counter-based RNG (synth.hip): out (B, L) fp32 = utterances [first_utt, first_utt + B) of the stream `seed`
 hipError_t launch_synth_wave(float* out, uint64_t seed, int64_t first_utt, int B, int L, hipStream_t stream);
 

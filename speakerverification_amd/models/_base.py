@@ -100,7 +100,8 @@ class HipModule:
         """Weights from a packed checkpoint blob (checkpoint.convert_checkpoint); tensors of other networks are ignored."""
         from .. import checkpoint, _lib
         mid, sd = checkpoint.read_blob(path)
-        want = {"ecapa": _lib.MODEL_ECAPA, "rawnet2": _lib.MODEL_RAWNET2, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV}.get(self.model_kind)
+        want = {"ecapa": _lib.MODEL_ECAPA, "rawnet2": _lib.MODEL_RAWNET2, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV,
+                "rawnet3": _lib.MODEL_RAWNET3}.get(self.model_kind)
         if want is not None and mid != want:
             raise ValueError(f"{path} holds weights of model {mid}, this module is {self.model_kind}")
         return self.load_state_dict(sd, strict=False)

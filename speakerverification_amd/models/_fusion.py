@@ -1,18 +1,22 @@
-"""Shared body of the RawNet2 + ECAPA fusion plug-ins (reference ``models/Raw_ECAPA.py``, ``Raw_ECAPA_sinc_asp.py``,
-``Raw_ECAPA_conv_asp.py``, each :22-52): ECAPA-TDNN (C = 512, 192-d) on the mel spectrogram of the waveform, concatenated
-with RawNet2 (``aggregate='asp'``, nOut - 192 dims) on the raw waveform.  The three differ only in two switches:
+"""Shared body of the raw-waveform + ECAPA fusion plug-ins (reference ``models/Raw_ECAPA.py``, ``Raw_ECAPA_sinc_asp.py``,
+``Raw_ECAPA_conv_asp.py``, each :22-52, and ``Raw3_ECAPA.py``): ECAPA-TDNN (C = 512, 192-d) on the mel spectrogram of the
+waveform, concatenated with a raw-waveform network (nOut - 192 dims).  They differ in three switches:
 
-    model                 ECAPA input_norm   RawNet2 front_proc
-    Raw_ECAPA             True               'sinc'
-    Raw_ECAPA_sinc_asp    False              'sinc'
-    Raw_ECAPA_conv_asp    True               'conv'
+    model                 ECAPA input_norm   raw branch (attribute)
+    Raw_ECAPA             True               RawNet2 'sinc' / asp (rawnet2v2)
+    Raw_ECAPA_sinc_asp    False              RawNet2 'sinc' / asp (rawnet2v2)
+    Raw_ECAPA_conv_asp    True               RawNet2 'conv' / asp (rawnet2v2)
+    Raw3_ECAPA            True               RawNet3 (rawnet)
 
 As in the reference the ECAPA branch inherits ``features`` from the config: with ``features: raw`` (what every fusion YAML
 sets) it consumes the mel POWER without log / mean normalisation (ECAPA_TDNN.py:473).  Both branches read the same waveform;
-the mel front-end and the ECAPA body run as one fused library call.  State-dict keys: ``ECAPA_TDNN.*``, ``rawnet2v2.*``
-(``compute_features.*`` buffers of nnAudio are accepted and ignored: the front-end tables are rebuilt from the config).
+the mel front-end and the ECAPA body run as one fused library call.  State-dict keys: ``ECAPA_TDNN.*`` and the raw branch's
+attribute (``rawnet2v2.*`` or ``rawnet.*``); ``compute_features.*`` buffers of nnAudio are accepted and ignored (the front-end
+tables are rebuilt from the config).
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 
@@ -31,19 +35,27 @@ class RawECAPAFusion:
     INPUT_NORM = False              # ECAPA branch: InstanceNorm1d on its input (ECAPA_TDNN.py:406-409,477-478)
     FRONT_PROC = "sinc"             # RawNet2 branch front-end (RawNet2_custom.py:45-63)
     MODEL_NAME = "Raw_ECAPA_sinc_asp"
+    RAW_ATTR = "rawnet2v2"          # the raw branch's attribute: the prefix of its state-dict keys
 
     def __init__(self, nOut=512, **kwargs):
         kw = dict(kwargs)
         kw.pop("channels", None)
         kw.pop("input_norm", None)
         self.ECAPA_TDNN = _ecapa.MainModel(nOut=192, channels=[512, 512, 512, 512, 1536], input_norm=self.INPUT_NORM, **kw)
-        self.rawnet2v2 = _rawnet2.MainModel(nOut=nOut - 192, front_proc=self.FRONT_PROC, aggregate="asp", att_dim=128, **kw)
+        setattr(self, self.RAW_ATTR, self._make_raw_branch(nOut, kw))
         self.training = False
+
+    def _make_raw_branch(self, nOut, kw):
+        return _rawnet2.MainModel(nOut=nOut - 192, front_proc=self.FRONT_PROC, aggregate="asp", att_dim=128, **kw)
+
+    @property
+    def _raw(self):
+        return getattr(self, self.RAW_ATTR)
 
     # nn.Module look-alikes --------------------------------------------------------------------------
     def to(self, device=None, *a, **k):
         self.ECAPA_TDNN.to(device)
-        self.rawnet2v2.to(device)
+        self._raw.to(device)
         return self
 
     def eval(self):
@@ -56,41 +68,46 @@ class RawECAPAFusion:
 
     def parameters(self):
         yield from self.ECAPA_TDNN.parameters()
-        yield from self.rawnet2v2.parameters()
+        yield from self._raw.parameters()
 
     def state_dict(self):
         sd = {"ECAPA_TDNN." + k: v for k, v in self.ECAPA_TDNN.state_dict().items()}
-        sd.update({"rawnet2v2." + k: v for k, v in self.rawnet2v2.state_dict().items()})
+        sd.update({self.RAW_ATTR + "." + k: v for k, v in self._raw.state_dict().items()})
         return sd
 
     def load_state_dict(self, sd, strict=True):
         e = {k[len("ECAPA_TDNN."):]: v for k, v in sd.items() if k.startswith("ECAPA_TDNN.")}
-        r = {k[len("rawnet2v2."):]: v for k, v in sd.items() if k.startswith("rawnet2v2.")}
-        other = [k for k in sd if not k.startswith(("ECAPA_TDNN.", "rawnet2v2.", "compute_features."))]
+        pre = self.RAW_ATTR + "."
+        r = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
+        other = [k for k in sd if not k.startswith(("ECAPA_TDNN.", pre, "compute_features."))]
         if strict and other:
             raise KeyError(f"unexpected keys {other[:4]}")
         m1 = self.ECAPA_TDNN.load_state_dict(e, strict=strict)
-        m2 = self.rawnet2v2.load_state_dict(r, strict=strict)
+        m2 = self._raw.load_state_dict(r, strict=strict)
         return m1, m2
 
     def load_blob(self, path):
-        """the pair of branch blobs checkpoint.convert_checkpoint(..., model=MODEL_NAME) wrote for `path`.  A blob of the other
-        RawNet2 front-end raises ValueError; a blob that lacks a tensor this module needs (an ECAPA blob without instance_norm.*
-        for a model with input_norm) raises the library's SVHIP_ERR_MISSING instead of running on the initial values."""
+        """the pair of branch blobs checkpoint.convert_checkpoint(..., model=MODEL_NAME) wrote for `path`.  A blob of another
+        raw-waveform network (the other RawNet2 front-end, RawNet2 for RawNet3 or the other way round) raises ValueError; a blob that
+        lacks a tensor this module needs (an ECAPA blob without instance_norm.* for a model with input_norm) raises the library's
+        SVHIP_ERR_MISSING instead of running on the initial values."""
         from .. import checkpoint, _lib
-        p_ecapa, p_rawnet2 = checkpoint.fusion_blob_paths(path, self.MODEL_NAME)
-        done = self.ECAPA_TDNN.load_blob(p_ecapa), self.rawnet2v2.load_blob(p_rawnet2)
-        for branch, (missing, _) in zip(("ECAPA_TDNN", "rawnet2v2"), done):
+        p_ecapa, p_raw = checkpoint.fusion_blob_paths(path, self.MODEL_NAME)
+        if not os.path.exists(p_raw):
+            raise ValueError(f"{self.MODEL_NAME}: no {p_raw} beside {path}: the pair was converted for another fusion model "
+                             "(RawNet2 and RawNet3 branches are written as .rawnet2 / .rawnet3)")
+        done = self.ECAPA_TDNN.load_blob(p_ecapa), self._raw.load_blob(p_raw)
+        for branch, (missing, _) in zip(("ECAPA_TDNN", self.RAW_ATTR), done):
             if missing:
                 raise _lib.SvhipError(_lib.ERR_MISSING, f"{self.MODEL_NAME}: the {branch} blob lacks {missing[:4]} ({len(missing)} tensors)")
         return done
 
     def forward(self, x):
-        if _is_torch(x) and x.is_cuda and x.ndim == 2 and self.rawnet2v2.accepts_length(x.shape[1]):
+        if _is_torch(x) and x.is_cuda and x.ndim == 2 and self._raw.accepts_length(x.shape[1]):
             # device-resident batch: the two branches run CONCURRENTLY, each on its handle's own stream (RawNet2's small late
             # kernels beside ECAPA's GEMMs: 61 k instead of 55 k utt/s at B = 256)
             e1 = self.ECAPA_TDNN._get_engine(x.shape[1], batch=x.shape[0])
-            e2 = self.rawnet2v2._engine_for(x)
+            e2 = self._raw._engine_for(x)
             if x.shape[0] <= min(e1.max_batch, e2.max_batch) and x.dtype == torch.float32 and x.is_contiguous():
                 torch.cuda.current_stream(x.device).synchronize()          # x is complete before either handle reads it
                 out = torch.empty((x.shape[0], e1.embed_dim + e2.embed_dim), device=x.device, dtype=torch.float32)
@@ -104,7 +121,7 @@ class RawECAPAFusion:
                 out[:, e1.embed_dim:] = o2
                 return out.squeeze()
         out1 = self.ECAPA_TDNN.embed_wave(x)          # compute_features + ECAPA_TDNN (Raw_ECAPA_sinc_asp.py:41-44)
-        out2 = self.rawnet2v2(x)                      # :48
+        out2 = self._raw(x)                           # :48
         if _is_torch(out1):
             return torch.cat([out1, out2], dim=-1)    # :50
         return np.concatenate([out1, out2], axis=-1)

@@ -7,6 +7,8 @@ source of truth for the *names and shapes* of the reference state dicts
   * ECAPA-TDNN  — reference ``src/models/ECAPA_TDNN.py:339-458`` (231 tensors),
   * RawNet2     — reference ``src/models/RawNet2_custom.py:18-135`` + ``RawNet_baseline.py``
                   (``aggregate='asp'``: 147 tensors with ``front_proc='sinc'``, 140 with ``'conv'``),
+  * RawNet3     — reference ``src/models/RawNet3.py`` + ``RawNet_baseline.py`` (the defaults of its
+                  ``MainModel``: 234 tensors),
 
 and generates values from a ``numpy`` PCG64 stream in state-dict order, so the CPU oracle and the
 HIP path see bit-identical weights on any machine.  ``tests/test_oracle_golden.py`` checks the
@@ -28,6 +30,12 @@ ATT_CHANNELS = 128                        # ECAPA_TDNN.py:381
 RAWNET2_LAYERS = (1, 1, 1, 2, 1, 2)                    # RawNet2_custom.py:231
 RAWNET2_FILTERS = (128, 128, 256, 256, 512, 512)       # RawNet2_custom.py:232
 RAWNET2_SINC_K = 251                                   # RawNet2_custom.py:36
+
+RAWNET3_C = 1024                                       # RawNet3.py:10 (C; no config sets it)
+RAWNET3_SCALE = 8                                      # model_scale (RawNet3.py:178)
+RAWNET3_DILATIONS = (2, 3, 4)                          # RawNet3.py:46-52
+RAWNET3_CONTEXT = 1536                                 # RawNet3.py:31
+RAWNET3_SINC_HALF = 125                                # ParamSincFB(256, 251): taps on each side of the centre
 
 
 def _bn(prefix, c):
@@ -102,6 +110,65 @@ def rawnet2_param_spec(nOut=320, nb_samp=32000, att_dim=128, front_proc="sinc"):
     return spec
 
 
+def rawnet3_param_spec(nOut=512):
+    """Ordered (name, shape) list == ``RawNet3.MainModel(nOut=nOut).state_dict()`` of the reference (defaults: model_scale=8,
+    context=True, summed=True, encoder_type='ASP', C = 1024): 234 tensors.  ``bn1.*`` and ``bn6.*`` exist but the forward never
+    uses them (RawNet3.py:88-99, out_bn=False); ``conv1.filterbank.*`` are the parameters and persistent buffers of the sinc
+    filterbank ``ParamSincFB(256, 251, stride=10)``."""
+    C, W = RAWNET3_C, RAWNET3_C // RAWNET3_SCALE
+    spec = [("preprocess.0.flipped_filter", (1, 1, 2)), ("preprocess.1.weight", (1,)), ("preprocess.1.bias", (1,)),
+            ("conv1.filterbank.low_hz_", (C // 8, 1)), ("conv1.filterbank.band_hz_", (C // 8, 1)),
+            ("conv1.filterbank.window_", (RAWNET3_SINC_HALF,)), ("conv1.filterbank.n_", (1, RAWNET3_SINC_HALF))]
+    spec += _bn("bn1", C // 4)
+    for li, cin in enumerate((C // 4, C, C), start=1):
+        p = f"layer{li}"
+        spec += [(p + ".conv1.weight", (C, cin, 1)), (p + ".conv1.bias", (C,))]
+        spec += _bn(p + ".bn1", C)
+        for i in range(RAWNET3_SCALE - 1):
+            spec += [(p + f".convs.{i}.weight", (W, W, 3)), (p + f".convs.{i}.bias", (W,))]
+        for i in range(RAWNET3_SCALE - 1):
+            spec += _bn(p + f".bns.{i}", W)
+        spec += [(p + ".conv3.weight", (C, C, 1)), (p + ".conv3.bias", (C,))]
+        spec += _bn(p + ".bn3", C)
+        spec += [(p + ".afms.alpha", (C, 1)), (p + ".afms.fc.weight", (C, C)), (p + ".afms.fc.bias", (C,))]
+        if cin != C:
+            spec += [(p + ".residual.0.weight", (C, cin, 1))]
+    D = RAWNET3_CONTEXT
+    spec += [("layer4.weight", (D, 3 * C, 1)), ("layer4.bias", (D,)),
+             ("attention.0.weight", (128, 3 * D, 1)), ("attention.0.bias", (128,))]
+    spec += _bn("attention.2", 128)
+    spec += [("attention.3.weight", (1, 128, 1)), ("attention.3.bias", (1,))]
+    spec += _bn("bn5", 2 * D)
+    spec += [("fc6.weight", (nOut, 2 * D)), ("fc6.bias", (nOut,))]
+    spec += _bn("bn6", nOut)
+    return spec
+
+
+def rawnet3_sinc_buffers():
+    """the persistent buffers of ParamSincFB(256, 251) at sample_rate 16000: window_ (125,), n_ (1, 125)"""
+    n_lin = np.linspace(0.0, 251 / 2 - 1, RAWNET3_SINC_HALF)
+    window = (0.54 - 0.46 * np.cos(2 * math.pi * n_lin / 251)).astype(np.float32)
+    n = (2 * math.pi * np.arange(-RAWNET3_SINC_HALF, 0) / 16000.0).reshape(1, -1).astype(np.float32)
+    return window, n
+
+
+def rawnet3_sinc_filters(low_hz_, band_hz_, window_, n_, sample_rate=16000.0, min_low_hz=50.0, min_band_hz=50.0):
+    """ParamSincFB.filters() (asteroid-filterbanks 0.4.x, the filterbank RawNet3.py:35-41 instantiates) in float64 numpy: the
+    (256, 251) band-pass bank, 128 cos filters then 128 sin filters.  The cos half is RawNet_baseline.py:339-357's formula; the
+    library bakes the same arithmetic at finalize (api_weights.hip)."""
+    low = min_low_hz + np.abs(np.asarray(low_hz_, np.float64).reshape(-1, 1))
+    high = np.clip(low + min_band_hz + np.abs(np.asarray(band_hz_, np.float64).reshape(-1, 1)), min_low_hz, sample_rate / 2)
+    band = (high - low)[:, 0]
+    n = np.asarray(n_, np.float64).reshape(1, -1)
+    w = np.asarray(window_, np.float64).reshape(1, -1)
+    ft_low, ft_high = low @ n, high @ n
+    cos_left = (np.sin(ft_high) - np.sin(ft_low)) / (n / 2) * w
+    sin_left = (np.cos(ft_low) - np.cos(ft_high)) / (n / 2) * w
+    cos = np.concatenate([cos_left, 2 * band[:, None], cos_left[:, ::-1]], axis=1)
+    sin = np.concatenate([sin_left, np.zeros((len(band), 1)), -sin_left[:, ::-1]], axis=1)
+    return np.concatenate([cos / (2 * band[:, None]), sin / (2 * band[:, None])], axis=0)
+
+
 def _sinc_init(n_filt, sample_rate=16000, min_low_hz=50, min_band_hz=50):
     # same initial values as RawNet_baseline.py:296-310 (mel-spaced band edges)
     to_mel = lambda hz: 2595 * np.log10(1 + hz / 700)
@@ -134,6 +201,10 @@ def synth_state_dict(spec, seed=1):
             sd[name] = (0.01 * rng.standard_normal(shape)).astype(np.float32)
         elif leaf == "alpha":                                  # AFMS
             sd[name] = rng.uniform(0.5, 1.5, shape).astype(np.float32)
+        elif leaf == "flipped_filter":                        # PreEmphasis(0.97), RawNet_baseline.py:27-38
+            sd[name] = np.array([-0.97, 1.0], dtype=np.float32).reshape(shape)
+        elif leaf in ("window_", "n_"):                        # ParamSincFB's persistent buffers
+            sd[name] = rawnet3_sinc_buffers()[0 if leaf == "window_" else 1].reshape(shape)
         elif leaf in ("low_hz_", "band_hz_"):
             lo, band = _sinc_init(shape[0])
             base = lo if leaf == "low_hz_" else band
