@@ -114,7 +114,7 @@ static int rawnet3_forward_part(svhip_handle* h, const float* d_wav, int b0, int
     pa.act1 = ACT_RELU; pa.bias_utt = h->rn3_ctx; pa.ld_bu = 128;
     if ((rc = conv_gemm(h, h->rn3_att, pa))) return rc;
     if ((rc = run(h, "rn3_pool", 0, [&]() {
-             return launch_rn3_ctx_pool(P2, 128, h->rn3_w2, h->rn3_b2, h->rn3_logit, P1, D, dt, B, T2, D, h->rn3_bn5_scale, h->rn3_bn5_shift, h->rn3_pooled, st);
+             return launch_rn3_ctx_pool(P2, 128, h->rn3_w2, h->rn3_b2, h->rn3_logit, P1, D, dt, B, T2, D, h->rn3_bn5_scale, h->rn3_bn5_shift, h->rn3_stats, h->rn3_pooled, st);
          }))) return rc;
     // fc6 (out_bn=False: bn6 is not applied)                                         RawNet3.py:144-148
     return run(h, "rn3_fc6", 2.0 * B * h->rn3_fc6.N * h->rn3_fc6.K, [&]() {

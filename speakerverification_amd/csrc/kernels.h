@@ -388,9 +388,9 @@ hipError_t launch_rn3_afms(const void* x, int ldx, const float* alpha, const flo
 // stats (B, 2C) fp32 = [mean_t x | sqrt(clamp(unbiased var_t x, 1e-4, 1e4))]
 hipError_t launch_rn3_tstats(const void* x, int ldx, int dt, int B, int Tn, int C, float* stats, hipStream_t stream);
 // single-head context pooling: logit (B * Tn) = hatt . w2 + b2 (hatt (B * Tn, 128)), softmax over Tn, weighted mean / std of x, bn5 affine
-// -> pooled (B, 2C) fp32
+// -> pooled (B, 2C) fp32; NaN for an utterance whose in_stats (rn3_prenorm's (B, 2) statistics of the waveform) are not finite
 hipError_t launch_rn3_ctx_pool(const void* hatt, int ldh, const float* w2, const float* b2, float* logit, const void* x, int ldx, int dt, int B, int Tn, int C,
-                               const float* bn_scale, const float* bn_shift, float* pooled, hipStream_t stream);
+                               const float* bn_scale, const float* bn_shift, const double* in_stats, float* pooled, hipStream_t stream);
 
 // synthetic waveforms from a counter-based RNG (synth.hip): out (B, L) fp32 = utterances [first_utt, first_utt + B) of the stream `seed`
 hipError_t launch_synth_wave(float* out, uint64_t seed, int64_t first_utt, int B, int L, hipStream_t stream);

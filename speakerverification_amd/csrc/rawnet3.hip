@@ -18,8 +18,12 @@
 // Context pooling (RawNet3.py:110-142):
 //   rn3_tstats   [mean_t x | sqrt(clamp(var_t x, 1e-4, 1e4))] with the UNBIASED variance (torch.var), fp64 sums
 //   rn3_logit    the per-frame logit w2 . h_t + b2 of the 128-wide attention activation (one logit per frame, all channels share it)
-//   rn3_pool     softmax over T, mu = sum w x, sg = sqrt(clamp(sum w x^2 - mu^2, 1e-4, 1e4)), then the bn5 affine -> pooled (B, 3072)
+//   rn3_pool     softmax over T, mu = sum w x, sg = sqrt(clamp(sum w x^2 - mu^2, 1e-4, 1e4)), then the bn5 affine -> pooled (B, 3072).
+//                The moments are fp64 sums on fp32 handles: sum w x^2 - mu^2 cancels, and fp32 sums leave ~1e-5 of scale in sg.
+//                An utterance whose waveform is not finite (its rn3_prenorm statistics are not) pools to NaN, as in the reference: the
+//                ReLU epilogues (fmaxf) map a NaN to 0 where torch.relu keeps it, so layer4's output would be finite and meaningless
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
@@ -192,7 +196,9 @@ __global__ __launch_bounds__(R3_THREADS) void rn3_logit_kernel(const T* __restri
 // grid (ceil(C / 256), B), one thread per channel: softmax over the utterance's Tn logits, weighted moments, clamp, bn5 affine
 template <typename T>
 __global__ __launch_bounds__(R3_THREADS) void rn3_pool_kernel(const float* __restrict__ logit, const T* __restrict__ x, int ldx, int Tn, int C,
-                                                              const float* __restrict__ sc, const float* __restrict__ sh, float* __restrict__ pooled) {
+                                                              const float* __restrict__ sc, const float* __restrict__ sh, const double* __restrict__ in_stats,
+                                                              float* __restrict__ pooled) {
+    typedef typename std::conditional<sizeof(T) == 4, double, float>::type A;       // (fp64 moments on fp32 handles)
     __shared__ float red[R3_THREADS / 64];
     const int b = blockIdx.y, c = blockIdx.x * R3_THREADS + threadIdx.x;
     const float* lg = logit + (int64_t)b * Tn;
@@ -204,14 +210,15 @@ __global__ __launch_bounds__(R3_THREADS) void rn3_pool_kernel(const float* __res
     const float inv = 1.0f / block_sum(se, red);
     if (c >= C) return;
     const T* p = x + (int64_t)b * Tn * ldx + c;
-    float mu = 0.0f, m2 = 0.0f;
+    A mu = 0, m2 = 0;
     for (int t = 0; t < Tn; ++t) {
-        const float w = expf(lg[t] - mx) * inv, v = to_f32(p[(int64_t)t * ldx]);
-        mu = fmaf(v, w, mu);
-        m2 = fmaf(v * v, w, m2);
+        const A w = (A)(expf(lg[t] - mx) * inv), v = (A)to_f32(p[(int64_t)t * ldx]);
+        mu = fma(v, w, mu);
+        m2 = fma(v * v, w, m2);
     }
-    const float sg = sqrtf(fminf(fmaxf(m2 - mu * mu, 1e-4f), 1e4f));
-    pooled[(int64_t)b * 2 * C + c] = mu * sc[c] + sh[c];
+    float sg = sqrtf(fminf(fmaxf((float)(m2 - mu * mu), 1e-4f), 1e4f)), m = (float)mu;
+    if (!isfinite(in_stats[2 * b]) || !isfinite(in_stats[2 * b + 1])) m = sg = NAN;
+    pooled[(int64_t)b * 2 * C + c] = m * sc[c] + sh[c];
     pooled[(int64_t)b * 2 * C + C + c] = sg * sc[C + c] + sh[C + c];
 }
 
@@ -273,16 +280,16 @@ hipError_t launch_rn3_tstats(const void* x, int ldx, int dt, int B, int Tn, int 
 }
 
 hipError_t launch_rn3_ctx_pool(const void* hatt, int ldh, const float* w2, const float* b2, float* logit, const void* x, int ldx, int dt, int B, int Tn, int C,
-                               const float* bn_scale, const float* bn_shift, float* pooled, hipStream_t stream) {
-    if (!hatt || !w2 || !b2 || !logit || !x || !bn_scale || !bn_shift || !pooled || B <= 0 || Tn <= 0 || ldh < 128) return hipErrorInvalidValue;
+                               const float* bn_scale, const float* bn_shift, const double* in_stats, float* pooled, hipStream_t stream) {
+    if (!hatt || !w2 || !b2 || !logit || !x || !bn_scale || !bn_shift || !in_stats || !pooled || B <= 0 || Tn <= 0 || ldh < 128) return hipErrorInvalidValue;
     const int64_t M = (int64_t)B * Tn;
     const dim3 lgrid((unsigned)((M + 3) / 4)), pgrid((C + R3_THREADS - 1) / R3_THREADS, B);
     if (dt == DT_F32) {
         hipLaunchKernelGGL(rn3_logit_kernel<float>, lgrid, dim3(R3_THREADS), 0, stream, (const float*)hatt, ldh, w2, b2, logit, M);
-        hipLaunchKernelGGL(rn3_pool_kernel<float>, pgrid, dim3(R3_THREADS), 0, stream, logit, (const float*)x, ldx, Tn, C, bn_scale, bn_shift, pooled);
+        hipLaunchKernelGGL(rn3_pool_kernel<float>, pgrid, dim3(R3_THREADS), 0, stream, logit, (const float*)x, ldx, Tn, C, bn_scale, bn_shift, in_stats, pooled);
     } else if (dt == DT_BF16) {
         hipLaunchKernelGGL(rn3_logit_kernel<bf16_t>, lgrid, dim3(R3_THREADS), 0, stream, (const bf16_t*)hatt, ldh, w2, b2, logit, M);
-        hipLaunchKernelGGL(rn3_pool_kernel<bf16_t>, pgrid, dim3(R3_THREADS), 0, stream, logit, (const bf16_t*)x, ldx, Tn, C, bn_scale, bn_shift, pooled);
+        hipLaunchKernelGGL(rn3_pool_kernel<bf16_t>, pgrid, dim3(R3_THREADS), 0, stream, logit, (const bf16_t*)x, ldx, Tn, C, bn_scale, bn_shift, in_stats, pooled);
     } else {
         return hipErrorInvalidValue;
     }

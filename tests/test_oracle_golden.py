@@ -1,6 +1,7 @@
 """CPU: the oracle restatement vs fixtures captured from the imported reference (oracle/make_golden.py)."""
 import json
 import os
+import warnings
 
 import numpy as np
 import pytest
@@ -9,6 +10,7 @@ import torch
 from oracle import ecapa as o_ecapa
 from oracle import fbank as o_fbank
 from oracle import rawnet2 as o_rawnet2
+from oracle import rawnet3 as o_rawnet3
 from oracle import scoring as o_scoring
 from speakerverification_amd import synth
 
@@ -89,6 +91,70 @@ def test_rawnet2(golden_dir):
     for n in ("layer1", "layer6"):
         cs, ref = checksum(st[n]), g["cs_" + n]
         assert abs(cs[0] - ref[0]) <= 1e-5 * ref[1] + 1e-3
+
+
+def _rawnet3_sd(seed):
+    return o_rawnet3.torch_sd(synth.synth_state_dict(synth.rawnet3_param_spec(nOut=320), seed=seed))
+
+
+def test_rawnet3_float64_at_every_length(golden_dir):
+    """oracle/rawnet3.py in float64 against the reference module run in float64 (out64_*): both are exact arithmetic in different
+    summation orders, 3e-14 .. 9e-14 of scale apart (measured), so the bar is 1e-12"""
+    g = np.load(os.path.join(golden_dir, "rawnet3.npz"))
+    sd = _rawnet3_sd(int(g["seed_w"]))
+    for L in g["lengths"]:
+        L = int(L)
+        x = torch.from_numpy(synth.synth_waveforms(int(g["B"]), L, seed=int(g["seed_x"]))).double()
+        with torch.no_grad():
+            out = o_rawnet3.rawnet3_forward(x, sd).numpy()
+        ref = g[f"out64_{L}"]
+        assert out.shape == ref.shape == (2, 320)
+        assert float(np.abs(out - ref).max()) <= 1e-12 * float(np.abs(ref).max()), L
+
+
+def test_rawnet3_stage_checksums(golden_dir):
+    """the oracle's stages (frame-major, svhip_get_stage's names and shapes) at L = 32000 against the reference's fp32 forward hooks,
+    with the 1e-4 bar of test_gpu_rawnet3.py::test_rawnet3_layer_checksums (measured: 6e-10 .. 1.1e-5 of the |sum|)"""
+    g = np.load(os.path.join(golden_dir, "rawnet3.npz"))
+    sd = _rawnet3_sd(int(g["seed_w"]))
+    x = torch.from_numpy(synth.synth_waveforms(2, 32000, seed=int(g["seed_x"]))).double()
+    st = {}
+    with torch.no_grad():
+        o_rawnet3.rawnet3_forward(x, sd, stages=st)
+    T0, T1, T2 = o_rawnet3.frames(32000)
+    assert (T0, T1, T2) == (3175, 635, 211)
+    shapes = {"rn3_front": (2, T0, 256), "rn3_layer1": (2, T1, 1024), "rn3_layer2": (2, T2, 1024), "rn3_layer3": (2, T2, 1024),
+              "rn3_layer4": (2, T2, 1536), "rn3_pooled": (2, 3072)}
+    for name, shape in shapes.items():
+        assert tuple(st[name].shape) == shape, name
+        t = st[name].flatten().numpy()
+        cs = g["cs_" + name[4:]]
+        d_sum, d_abs = abs(t.sum() - cs[0]) / cs[1], abs(np.abs(t).sum() - cs[1]) / cs[1]
+        d_head = float(np.abs(t[:8] - cs[2:]).max()) / max(1.0, float(np.abs(cs[2:]).max()))
+        assert d_sum <= 1e-4 and d_abs <= 1e-4 and d_head <= 1e-3, (name, d_sum, d_abs, d_head)
+
+
+def test_rawnet3_is_not_finite_below_541_samples(golden_dir):
+    """L = 540 leaves one frame after the pools: torch.var's unbiased estimate is NaN there, in the reference (finite_540) and here"""
+    g = np.load(os.path.join(golden_dir, "rawnet3.npz"))
+    sd = _rawnet3_sd(int(g["seed_w"]))
+    assert o_rawnet3.frames(540)[2] == 1 and o_rawnet3.frames(541)[2] == 2
+    x = torch.from_numpy(synth.synth_waveforms(2, 540, seed=int(g["seed_x"]))).double()
+    with torch.no_grad(), warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)        # (torch.var's "degrees of freedom <= 0")
+        out = o_rawnet3.rawnet3_forward(x, sd)
+    assert bool(torch.isfinite(out).all()) == bool(g["finite_540"]) is False
+
+
+def test_rawnet3_columns_of_the_raw3_ecapa_fixture(golden_dir):
+    """Raw3_ECAPA's output is cat(ECAPA (192), RawNet3 (320)): columns 192: of the reference's float64 fusion output"""
+    g = np.load(os.path.join(golden_dir, "fusion_raw3_ecapa.npz"))
+    sd = _rawnet3_sd(int(g["seed_w_rawnet3"]))
+    x = torch.from_numpy(synth.synth_waveforms(int(g["B"]), 32000, seed=int(g["seed_x"]))).double()
+    with torch.no_grad():
+        out = o_rawnet3.rawnet3_forward(x, sd).numpy()
+    ref = g["out64_32000"][:, 192:]
+    assert float(np.abs(out - ref).max()) <= 1e-12 * float(np.abs(ref).max())
 
 
 def test_preemphasis(golden_dir):
