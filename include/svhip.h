@@ -58,9 +58,13 @@ typedef enum svhip_status {
  * statistics pooling with one attention logit per frame, bn5 and fc6.  embed_dim = nOut, samples = L (any L >= 541: T0 = (L - 251) / 10 + 1
  * frames, T0 / 5 / 3 >= 2 frames reach the pooling, whose unbiased variance needs two); channels 0 or 1024; compute SVHIP_F32 (the
  * filterbank sums in fp64) or SVHIP_BF16 only.  Weights: the 234 names of its state dict (bn1.*, bn6.* and preprocess.0.flipped_filter
- * included; bn1 and bn6 are not used by the forward, the filters are built from conv1.filterbank.{low_hz_, band_hz_, window_, n_}). */
+ * included; bn1 and bn6 are not used by the forward, the filters are built from conv1.filterbank.{low_hz_, band_hz_, window_, n_}).
+ * SVHIP_MODEL_RAWNET2_GRU (added under ABI v5): front_proc='sinc', aggregate='gru' — RawNet2_custom.MainModel's defaults and the RawNet2
+ * branch of Raw_ECAPA_sinc_gru: the sinc front-end and residual stack of SVHIP_MODEL_RAWNET2, then lrelu(bn_before_gru(x)), a one-layer
+ * GRU (input 512, hidden 1024, h0 = 0; RawNet2_custom.py:196-207) whose last state feeds fc_after_gru.  L >= 2438 samples; compute
+ * SVHIP_F32, SVHIP_F32X3, SVHIP_F16 or SVHIP_BF16.  Weights: the 144 names of its state dict (fc.* is part of it and is not used). */
 enum { SVHIP_MODEL_ECAPA = 0, SVHIP_MODEL_RAWNET2 = 1, SVHIP_MODEL_NONE = 2 /* fbank + scoring only */, SVHIP_MODEL_RAWNET2_CONV = 3,
-       SVHIP_MODEL_RAWNET3 = 4 };
+       SVHIP_MODEL_RAWNET3 = 4, SVHIP_MODEL_RAWNET2_GRU = 5 };
 enum { SVHIP_F32 = 0, SVHIP_BF16 = 1, SVHIP_I64 = 2, SVHIP_F32X3 = 3 /* compute only */, SVHIP_F16 = 4 /* compute only */ };
 enum { SVHIP_IN_DEVICE = 1, SVHIP_OUT_DEVICE = 2, SVHIP_ASYNC = 4 };
 
@@ -274,7 +278,8 @@ int svhip_synth_waveforms(svhip_handle* h, uint64_t seed, int64_t first_utt, int
 
 /* Introspection used by tests and bench.py (not part of the reference's surface).
  *   get_stage    : copy an intermediate activation of the LAST forward to host as fp32, frame-major
- *                  (B, T, C).  Names: "input","blocks.0".."blocks.3","mfa","asp","asp_bn" (ECAPA).
+ *                  (B, T, C).  Names: "input","blocks.0".."blocks.3","mfa","asp","asp_bn" (ECAPA); "rn_gru_in" (the (B T, 512) GRU
+ *                  input of a one-slice forward) and "rn_gru_h" (the (B, 1024) fp32 last GRU state) of SVHIP_MODEL_RAWNET2_GRU.
  *                  Returns the element count through *count (out may be NULL to query).
  *   profile_*    : when enabled every kernel launch is bracketed by HIP events on the handle's
  *                  stream; profile_get returns accumulated milliseconds / launch count per kernel

@@ -24,6 +24,7 @@ from . import _lib
 MAGIC = b"SVHIPWB1"
 _MODEL_IDS = {"ECAPA_TDNN": _lib.MODEL_ECAPA, "ecapa": _lib.MODEL_ECAPA, "RawNet2_custom": _lib.MODEL_RAWNET2,
               "rawnet2": _lib.MODEL_RAWNET2, "RawNet2_custom_conv": _lib.MODEL_RAWNET2_CONV, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV,
+              "RawNet2_custom_gru": _lib.MODEL_RAWNET2_GRU, "rawnet2_gru": _lib.MODEL_RAWNET2_GRU,
               "RawNet3": _lib.MODEL_RAWNET3, "rawnet3": _lib.MODEL_RAWNET3}
 
 
@@ -134,9 +135,11 @@ def read_blob(path):
 
 
 # fusion model -> its branches: (state-dict prefix, blob model, blob suffix).  The RawNet2 blob's model id records the front-end
-# (SVHIP_MODEL_RAWNET2: 'sinc', SVHIP_MODEL_RAWNET2_CONV: 'conv'), so a pair cannot be loaded into the other model's module.
+# and the aggregation (SVHIP_MODEL_RAWNET2: 'sinc' / asp, SVHIP_MODEL_RAWNET2_CONV: 'conv' / asp, SVHIP_MODEL_RAWNET2_GRU: 'sinc' / gru),
+# so a pair cannot be loaded into the other model's module.
 FUSION_MODELS = {
     "Raw_ECAPA_sinc_asp": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom", ".rawnet2")),
+    "Raw_ECAPA_sinc_gru": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom_gru", ".rawnet2")),
     "Raw_ECAPA": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom", ".rawnet2")),
     "Raw_ECAPA_conv_asp": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom_conv", ".rawnet2")),
     # Raw3_ECAPA.py: the raw-waveform branch is RawNet3, attribute `rawnet`; its blob's model id is SVHIP_MODEL_RAWNET3
@@ -175,6 +178,14 @@ def convert_checkpoint(src, dst, model) -> int:
             raise ValueError(f"{model}: the checkpoint's RawNet2 branch has a sinc front-end (rawnet2v2.first_conv.*)")
         if front == "sinc" and any(k.startswith("rawnet2v2.conv1.") for k in sd):
             raise ValueError(f"{model}: the checkpoint's RawNet2 branch has a conv front-end (rawnet2v2.conv1.*)")
+        if raw_prefix == "rawnet2v2.":
+            agg = "gru" if FUSION_MODELS[model][1][1] == "RawNet2_custom_gru" else "asp"
+            if agg == "asp" and any(k.startswith("rawnet2v2.gru.") for k in sd):
+                raise ValueError(f"{model}: the checkpoint's RawNet2 branch aggregates with a GRU (rawnet2v2.gru.*), not attentive "
+                                 "statistics pooling: convert it as Raw_ECAPA_sinc_gru")
+            if agg == "gru" and any(k.startswith("rawnet2v2.attention.") for k in sd):
+                raise ValueError(f"{model}: the checkpoint's RawNet2 branch aggregates with attentive statistics pooling "
+                                 "(rawnet2v2.attention.*), not a GRU")
         total = 0
         for prefix, branch, suffix in FUSION_MODELS[model]:
             sub = OrderedDict((k[len(prefix):], v) for k, v in sd.items() if k.startswith(prefix))
@@ -186,6 +197,11 @@ def convert_checkpoint(src, dst, model) -> int:
     if any(k.startswith(("ECAPA_TDNN.", "rawnet2v2.", "rawnet.")) for k in sd):
         raise ValueError("this is a fusion checkpoint (ECAPA_TDNN.* / rawnet2v2.* / rawnet.* keys): convert it with "
                          f"model= one of {sorted(FUSION_MODELS)} (one blob per branch)")
+    mid = model_id(model)
+    if mid in (_lib.MODEL_RAWNET2, _lib.MODEL_RAWNET2_CONV) and any(k.startswith("gru.") for k in sd):
+        raise ValueError(f"{model}: the checkpoint aggregates with a GRU (gru.*): convert it as RawNet2_custom_gru")
+    if mid == _lib.MODEL_RAWNET2_GRU and any(k.startswith("attention.") for k in sd):
+        raise ValueError(f"{model}: the checkpoint aggregates with attentive statistics pooling (attention.*), not a GRU")
     write_blob(dst, model, sd)
     return len(sd)
 
@@ -194,8 +210,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("src")
     ap.add_argument("dst")
-    ap.add_argument("--model", default="ECAPA_TDNN", help="reference model name (ECAPA_TDNN, RawNet2_custom, RawNet2_custom_conv, RawNet3, Raw_ECAPA_sinc_asp, "
-                    "Raw_ECAPA, Raw_ECAPA_conv_asp, Raw3_ECAPA)")
+    ap.add_argument("--model", default="ECAPA_TDNN", help="reference model name (ECAPA_TDNN, RawNet2_custom, RawNet2_custom_conv, RawNet2_custom_gru, "
+                    "RawNet3, Raw_ECAPA_sinc_asp, Raw_ECAPA_sinc_gru, Raw_ECAPA, Raw_ECAPA_conv_asp, Raw3_ECAPA)")
     a = ap.parse_args(argv)
     n = convert_checkpoint(a.src, a.dst, a.model)
     print(f"{a.dst}: {n} tensors")

@@ -207,7 +207,7 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
     if (cfg->model == SVHIP_MODEL_ECAPA && (cfg->channels <= 0 || cfg->channels % 64 != 0)) { g_create_error = "ECAPA channels must be a positive multiple of 64"; return SVHIP_ERR_INVALID; }
     if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16 && cfg->compute != SVHIP_F32X3 && cfg->compute != SVHIP_F16) { g_create_error = "unknown compute mode"; return SVHIP_ERR_INVALID; }
     if (cfg->compute == SVHIP_F16 && !is_rawnet2(cfg->model)) { g_create_error = "SVHIP_F16 is RawNet2's 16-bit mode (ECAPA's is SVHIP_BF16)"; return SVHIP_ERR_UNSUPPORTED; }
-    if (cfg->model == SVHIP_MODEL_RAWNET2 && cfg->samples < 251 + 3 * 3 * 3 * 3 * 3 * 3 * 3) { g_create_error = "RawNet2 needs at least 2438 samples"; return SVHIP_ERR_INVALID; }
+    if (rn_is_sinc(cfg->model) && cfg->samples < 251 + 3 * 3 * 3 * 3 * 3 * 3 * 3) { g_create_error = "RawNet2 needs at least 2438 samples"; return SVHIP_ERR_INVALID; }
     if (cfg->model == SVHIP_MODEL_RAWNET2_CONV && cfg->samples < 3 * RN_MIN_FRAMES) {
         g_create_error = "RawNet2 (front_proc='conv') needs at least 2187 samples: floor(L / 3) frames pass six max_pool1d(3) stages";
         return SVHIP_ERR_INVALID;
@@ -554,6 +554,11 @@ int svhip_get_stage(svhip_handle* h, const char* name, float* out, int64_t* coun
     else if (n == "rn_x") { src = h->rn_dbg_x; rows = (size_t)B * h->rn_dbg_T; cols = ld = h->rn_dbg_C; }
     else if (n == "rn_snap") { src = h->rn_snap; rows = (size_t)B * h->rn_snap_T; cols = ld = h->rn_snap_C; }
     else if (n == "rn_pooled") { src = h->rn_pooled; rows = B; cols = ld = 1024; f32 = true; }
+    else if ((n == "rn_gru_in" || n == "rn_gru_h") && rn_is_gru(h->cfg.model)) {
+        if (n == "rn_gru_h") { src = h->rn_gru_h; rows = B; cols = ld = RN_GRU_HIDDEN; f32 = true; }
+        else if (!h->rn_gru_in) SV_FAIL(h, SVHIP_ERR_STATE, "stage rn_gru_in: the last forward ran as several batch slices (SVHIP_LANES)");
+        else { src = h->rn_gru_in; rows = (size_t)B * h->rn_gru_T; cols = ld = 512; }
+    }
     else if (n.rfind("rn3_", 0) == 0 && h->cfg.model == SVHIP_MODEL_RAWNET3) {      // RawNet3: rn3_front, rn3_layer1 .. 3, rn3_layer4, rn3_pooled
         static const char* kStages[5] = {"rn3_front", "rn3_layer1", "rn3_layer2", "rn3_layer3", "rn3_layer4"};
         int i = 0;

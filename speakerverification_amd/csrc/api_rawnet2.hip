@@ -237,8 +237,30 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         if (stop_after == bi + 1) return SVHIP_OK;
         if (snap_at == bi + 1 && b0 == 0 && npre && (rc = snapshot(npre, T, K.cout))) return rc;
     }
-    // aggregation: attentive statistics pooling                                          RawNet2_custom.py:215-224
     const int M = B * T;
+    if (rn_is_gru(c.model)) {
+        // aggregation: GRU over the T frames, its last state through fc_after_gru          RawNet2_custom.py:196-207
+        // (pre = lrelu(bn_before_gru(x)), (B T, 512) frame-major, came out of block 7's AFMS pass)
+        const int G = 3 * RN_GRU_HIDDEN;
+        float* gi = h->rn_gru_gi + (size_t)b0 * T * G;
+        GemmParams pg = conv_params(h, h->rn_gru_ih, pre, 512, gi, G, M, h->T);
+        pg.out_f32 = 1;
+        const GemmPlan plan = conv_plan(h, h->rn_gru_ih, pg);          // (an fp32 output never takes the S32 form: plan.x3 is false)
+        if (plan.x3) SV_FAIL(h, SVHIP_ERR_STATE, "rn_gru_proj: unexpected split-operand route");
+        if ((rc = run(h, "rn_gru_proj", plan.flops, [&]() { return launch_gemm(plan.q, h->bf16, st); }))) return rc;
+        float* hb[2] = {h->rn_gru_hbuf[0] + (size_t)b0 * RN_GRU_HIDDEN, h->rn_gru_hbuf[1] + (size_t)b0 * RN_GRU_HIDDEN};
+        for (int t = 0; t < T; ++t)          // step t reads hb[t & 1] (h0 = 0: nothing) and writes hb[(t + 1) & 1]
+            if ((rc = run(h, "rn_gru_step", 2.0 * B * G * RN_GRU_HIDDEN, [&]() {
+                     return launch_rn_gru_step(h->rn_gru_whh, dt, gi, h->rn_gru_bhn, t ? hb[t & 1] : nullptr, hb[(t + 1) & 1], B, T, t, st);
+                 }))) return rc;
+        if (b0 == 0) h->rn_gru_in = pre;                                 // (rawnet2_forward forgets it after a sliced forward)
+        h->rn_gru_h = h->rn_gru_hbuf[T & 1];
+        return run(h, "rn_gru_fc", 2.0 * B * h->rn_gru_fc.N * h->rn_gru_fc.K, [&]() {
+            return launch_rowvec_linear(hb[T & 1], RN_GRU_HIDDEN, h->rn_gru_fc.W, h->rn_gru_fc.bias, d_emb, c.embed_dim, B, c.embed_dim, RN_GRU_HIDDEN, ACT_NONE, st,
+                                        h->bf16 && h->d_lin_part ? h->d_lin_part + (size_t)b0 * h->lin_part_per_utt : nullptr, true);
+        });
+    }
+    // aggregation: attentive statistics pooling                                          RawNet2_custom.py:215-224
     // (pre = lrelu(bn_before_agg(x)) came out of block 7's AFMS pass)
     // (1 x 1 layers, like the projection shortcut, are given the handle's T: no frame index enters a pointwise GEMM without column sums or bias_utt)
     GemmParams pa = conv_params(h, h->rn_att0, pre, 512, hb, 128, M, h->T);
@@ -261,7 +283,9 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
 // blocks are grids of 86 - 400 workgroups, the AFMS passes are latency-bound) run beside the big ones of another
 int rawnet2_forward(svhip_handle* h, const float* d_wav, int B) {
     const int lanes = (h->lanes > 1 && B >= 16 * h->lanes && h->opt.rn_stop < 0) ? h->lanes : 1;
-    return forward_lanes(h, rawnet2_forward_part, d_wav, B, lanes, ((B + lanes - 1) / lanes + 3) & ~3);
+    const int rc = forward_lanes(h, rawnet2_forward_part, d_wav, B, lanes, ((B + lanes - 1) / lanes + 3) & ~3);
+    if (lanes > 1) h->rn_gru_in = nullptr;          // the slices' GRU inputs are not one (B T, 512) block
+    return rc;
 }
 
 }  // namespace svhip

@@ -254,10 +254,18 @@ static void rawnet2_spec(const svhip_config& c, std::map<std::string, std::vecto
             if (inpl != planes) spec[p + ".shortcut.0.weight"] = {planes, inpl, 1};
             inpl = planes;
         }
-    bn("bn_before_agg", 512);
-    spec["attention.0.weight"] = {128, 512, 1}; spec["attention.0.bias"] = {128};
-    bn("attention.2", 128);
-    spec["attention.3.weight"] = {512, 128, 1}; spec["attention.3.bias"] = {512};
+    if (rn_is_gru(c.model)) {                        // aggregate='gru' (RawNet2_custom.py:84-95): fc is built too, and never used (:196-207)
+        const int64_t G = 3 * RN_GRU_HIDDEN;
+        bn("bn_before_gru", 512);
+        spec["gru.weight_ih_l0"] = {G, 512}; spec["gru.weight_hh_l0"] = {G, RN_GRU_HIDDEN};
+        spec["gru.bias_ih_l0"] = {G}; spec["gru.bias_hh_l0"] = {G};
+        spec["fc_after_gru.weight"] = {(int64_t)c.embed_dim, RN_GRU_HIDDEN}; spec["fc_after_gru.bias"] = {(int64_t)c.embed_dim};
+    } else {
+        bn("bn_before_agg", 512);
+        spec["attention.0.weight"] = {128, 512, 1}; spec["attention.0.bias"] = {128};
+        bn("attention.2", 128);
+        spec["attention.3.weight"] = {512, 128, 1}; spec["attention.3.bias"] = {512};
+    }
     spec["fc.weight"] = {(int64_t)c.embed_dim, 1024}; spec["fc.bias"] = {(int64_t)c.embed_dim};
 }
 
@@ -328,7 +336,7 @@ static int make_conv(svhip_handle* h, ConvLayer& L, const std::string& wname, co
                      int dil, int c_lo = 0, int c_hi = -1) {
     const HostTensor* w = getw(h, wname);
     if (!w) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %s", wname.c_str());
-    const int N = (int)w->shape[0], cin_full = (int)w->shape[1], taps = (int)w->shape[2];
+    const int N = (int)w->shape[0], cin_full = (int)w->shape[1], taps = w->shape.size() > 2 ? (int)w->shape[2] : 1;      // (a Linear: 1 tap)
     if (c_hi < 0) c_hi = cin_full;
     const int cin = c_hi - c_lo;
     const int bk = gemm_bk(h->bf16);
@@ -586,6 +594,41 @@ static int make_conv3_front(svhip_handle* h) {
     return dev_upload(h, &h->rn_cw, cw);
 }
 
+// aggregate='gru' (RawNet2_custom.py:84-95,196-207): bn_before_gru is the pass block 7's AFMS pass applies (rn_agg_scale / shift); the input
+// projection W_ih is a 1 x 1 conv layer whose bias folds b_ih + [b_hr | b_hz | 0] (b_hn stays inside r * (W_hn h + b_hn)); W_hh is packed
+// gate-interleaved (gru.hip) in the compute type; fc_after_gru is a small linear.  fc.* is loaded and not used, as in the reference.
+static int finalize_rawnet2_gru(svhip_handle* h) {
+    const int H = RN_GRU_HIDDEN, G = 3 * H;
+    int rc;
+    if ((rc = make_bn(h, "bn_before_gru", 512, &h->rn_agg_scale, &h->rn_agg_shift))) return rc;
+    const HostTensor *whh = getw(h, "gru.weight_hh_l0"), *bih = getw(h, "gru.bias_ih_l0"), *bhh = getw(h, "gru.bias_hh_l0");
+    if (!whh || !bih || !bhh) SV_FAIL(h, SVHIP_ERR_MISSING, "missing GRU tensors (gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0)");
+    if ((rc = make_conv(h, h->rn_gru_ih, "gru.weight_ih_l0", "", "", 1))) return rc;
+    std::vector<float> bias(G), bhn(H);
+    for (int j = 0; j < G; ++j) bias[j] = j < 2 * H ? (float)((double)bih->data[j] + (double)bhh->data[j]) : bih->data[j];
+    for (int j = 0; j < H; ++j) bhn[j] = bhh->data[2 * H + j];
+    if ((rc = dev_upload(h, &h->rn_gru_ih.bias, bias))) return rc;
+    if ((rc = dev_upload(h, &h->rn_gru_bhn, bhn))) return rc;
+    // packed row ut * 48 + g * 16 + j = W_hh row g * H + ut * 16 + j
+    std::vector<float> pk((size_t)G * H);
+    for (int ut = 0; ut < H / 16; ++ut)
+        for (int g = 0; g < 3; ++g)
+            for (int j = 0; j < 16; ++j)
+                memcpy(&pk[((size_t)ut * 48 + g * 16 + j) * H], &whh->data[((size_t)g * H + ut * 16 + j) * H], (size_t)H * 4);
+    if (h->bf16) {
+        std::vector<uint16_t> pb(pk.size());
+        for (size_t i = 0; i < pk.size(); ++i) pb[i] = to_h16(h, pk[i]);
+        uint16_t* d;
+        if ((rc = dev_upload(h, &d, pb))) return rc;
+        h->rn_gru_whh = d;
+    } else {
+        float* d;
+        if ((rc = dev_upload(h, &d, pk))) return rc;
+        h->rn_gru_whh = d;
+    }
+    return make_linear(h, h->rn_gru_fc, "fc_after_gru.weight", "fc_after_gru.bias");
+}
+
 int finalize_rawnet2(svhip_handle* h) {
     int rc;
     const bool conv = h->cfg.model == SVHIP_MODEL_RAWNET2_CONV;
@@ -639,6 +682,12 @@ int finalize_rawnet2(svhip_handle* h) {
             if (B.downsample) T /= 3;
             inpl = planes;
         }
+    if (rn_is_gru(h->cfg.model)) {
+        if ((rc = finalize_rawnet2_gru(h))) return rc;
+        fl += (double)T * (h->rn_gru_ih.flops_per_row + 2.0 * 3 * RN_GRU_HIDDEN * RN_GRU_HIDDEN) + 2.0 * h->rn_gru_fc.N * h->rn_gru_fc.K;
+        h->flops_per_utt = fl;
+        return SVHIP_OK;
+    }
     if ((rc = make_bn(h, "bn_before_agg", 512, &h->rn_agg_scale, &h->rn_agg_shift))) return rc;
     if ((rc = make_conv(h, h->rn_att0, "attention.0.weight", "attention.0.bias", "attention.2", 1))) return rc;
     if ((rc = make_conv(h, h->rn_att3, "attention.3.weight", "attention.3.bias", "", 1))) return rc;
@@ -776,6 +825,11 @@ int alloc_workspace(svhip_handle* h) {
         for (int i = 0; i < 6; ++i) tf /= 3;                      // six max_pool1d(3) stages follow the front-end
         if (tf < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance too short for RawNet2 (%d samples)", c.samples);
         if ((rc = dev_alloc(h, &h->rn_logits, B * (size_t)tf * 512))) return rc;
+        if (rn_is_gru(c.model)) {                                 // (256 x 14 frames: 11 MB of gate inputs)
+            h->rn_gru_T = tf;
+            if ((rc = dev_alloc(h, &h->rn_gru_gi, B * (size_t)tf * 3 * RN_GRU_HIDDEN))) return rc;
+            for (int i = 0; i < 2; ++i) if ((rc = dev_alloc(h, &h->rn_gru_hbuf[i], B * (size_t)RN_GRU_HIDDEN))) return rc;
+        }
         if ((rc = dev_alloc(h, &h->rn_pooled, B * 1024))) return rc;
         if (h->bf16) {          // K-slice partials of fc (K = 1 024: four slices of 256) at full batches, 16-bit handles
             h->lin_part_per_utt = (size_t)4 * (size_t)std::max(128, c.embed_dim);

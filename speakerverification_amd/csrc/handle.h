@@ -127,6 +127,17 @@ struct svhip_handle {
     float *rn_agg_scale = nullptr, *rn_agg_shift = nullptr;
     svhip::ConvLayer rn_att0, rn_att3;
     svhip::LinearLayer rn_fc;
+    // aggregate='gru' (SVHIP_MODEL_RAWNET2_GRU): bn_before_gru is rn_agg_scale / rn_agg_shift; W_ih a 1 x 1 conv layer whose bias is
+    // b_ih + [b_hr | b_hz | 0]; W_hh packed gate-interleaved (gru.hip) in the compute type; b_hn; fc_after_gru
+    svhip::ConvLayer rn_gru_ih;
+    void* rn_gru_whh = nullptr;
+    float* rn_gru_bhn = nullptr;
+    svhip::LinearLayer rn_gru_fc;
+    float* rn_gru_gi = nullptr;           // (Bmax, T, 3072) fp32 gate inputs
+    float* rn_gru_hbuf[2] = {};           // (Bmax, 1024) fp32 state, ping-pong
+    int rn_gru_T = 0;                     // frames that reach the GRU
+    const void* rn_gru_in = nullptr;      // svhip_get_stage "rn_gru_in": the GRU input of the last forward (one slice only)
+    const float* rn_gru_h = nullptr;      //                 "rn_gru_h": the buffer that holds the last state
     void* rn_buf[6] = {};                 // activation ping-pong buffers
     float* rn_scratch = nullptr;
     void* rn_xn = nullptr;
@@ -296,7 +307,9 @@ int run(svhip_handle* h, const char* label, double flops, F&& launch) {
     return SVHIP_OK;
 }
 
-inline bool is_rawnet2(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_CONV; }
+inline bool is_rawnet2(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_CONV || model == SVHIP_MODEL_RAWNET2_GRU; }
+inline bool rn_is_sinc(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_GRU; }     // front_proc='sinc'
+inline bool rn_is_gru(int model) { return model == SVHIP_MODEL_RAWNET2_GRU; }                                       // aggregate='gru'
 inline int rn3_frames(int L) { return (L - RN3_TAPS) / RN3_STRIDE + 1; }      // T0 of RawNet3's front-end
 inline void* off(void* base, size_t elems, int esz) { return reinterpret_cast<char*>(base) + elems * esz; }
 inline const void* off(const void* base, size_t elems, int esz) { return reinterpret_cast<const char*>(base) + elems * esz; }

@@ -369,6 +369,15 @@ hipError_t launch_rn_afms_gate(const float* part, int nparts, int B, int C, int 
 hipError_t launch_rn_attn_pool(const float* logits, const void* x, int dt, int B, int T, int C, float* out, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
+// RawNet2's GRU aggregation (gru.hip): one launch per time step of h' = GRU(gi_t, h), hidden size 1024
+// ---------------------------------------------------------------------------------------------
+constexpr int RN_GRU_HIDDEN = 1024;
+// Wp: W_hh (3072, 1024) in the gate-interleaved packing of gru.hip, element type by dt (DT_F32 / DT_BF16 / DT_F16); gi: (B, T, 3072) fp32
+// input projections (b_ih, b_hr, b_hz folded in); b_hn (1024); h_in (B, 1024) fp32 or null (h = 0); h_out (B, 1024) fp32, not h_in
+hipError_t launch_rn_gru_step(const void* Wp, int dt, const float* gi, const float* b_hn, const float* h_in, float* h_out, int B, int T, int t,
+                              hipStream_t stream);
+
+// ---------------------------------------------------------------------------------------------
 // RawNet3 (rawnet3.hip)
 // ---------------------------------------------------------------------------------------------
 constexpr int RN3_FILTERS = 256, RN3_TAPS = 251, RN3_STRIDE = 10;     // ParamSincFB(256, 251, stride=10) (RawNet3.py:35-41)

@@ -1,13 +1,15 @@
 """Drop-in for the reference plug-in ``models/RawNet2_custom.py`` (MainModel :230-243) in the variants
-the fusion models instantiate: ``aggregate='asp'``, ``att_dim=128`` with ``front_proc='sinc'``
-(Raw_ECAPA_sinc_asp.py / Raw_ECAPA.py:26-28) or ``front_proc='conv'`` (Raw_ECAPA_conv_asp.py:26-28).
+the fusion models and configs instantiate: ``aggregate='asp'``, ``att_dim=128`` with ``front_proc='sinc'``
+(Raw_ECAPA_sinc_asp.py / Raw_ECAPA.py:26-28) or ``front_proc='conv'`` (Raw_ECAPA_conv_asp.py:26-28), and
+``aggregate='gru'`` with ``front_proc='sinc'`` — the reference's defaults (RawNet2_custom.py:18-31; Raw_ECAPA_sinc_gru.py).
 
     model = MainModel(nOut=320, front_proc='sinc', aggregate='asp', att_dim=128, audio_spec={...})
     emb = model(wav)          # (B, 32000) waveform -> (B, nOut); (nOut,) for B == 1
 
 State-dict keys are the reference's: 147 tensors for 'sinc' (the band-pass filters are rebuilt from
 ``first_conv.low_hz_`` / ``band_hz_`` once per weight load instead of once per forward), 140 for 'conv'
-(``conv1.weight`` / ``conv1.bias``).  The sinc form's LayerNorm(nb_samp) fixes the input length; the conv
+(``conv1.weight`` / ``conv1.bias``), 144 for 'sinc' + 'gru' (``bn_before_gru``, ``gru.*``, ``fc_after_gru``;
+``fc`` is built and never used, as in the reference).  The sinc form's LayerNorm(nb_samp) fixes the input length; the conv
 form takes any length L >= 2187 (one library handle per length, the configured crop length with the
 full batch workspace).
 """
@@ -25,11 +27,17 @@ class RawNet2(HipModule):
     model_kind = "rawnet2"
 
     def __init__(self, nOut=512, front_proc="sinc", aggregate="gru", att_dim=128, audio_spec=None, device=None,
-                 compute=None, max_batch=None, **kwargs):
-        if front_proc not in ("sinc", "conv") or aggregate != "asp" or att_dim != 128:
-            raise NotImplementedError("only front_proc='sinc' | 'conv', aggregate='asp', att_dim=128 are built "
-                                      "(the variants of Raw_ECAPA_sinc_asp.py / Raw_ECAPA_conv_asp.py:26-28)")
+                 compute=None, max_batch=None, nb_gru_layers=1, gru_node=1024, **kwargs):
+        if front_proc not in ("sinc", "conv") or aggregate not in ("asp", "gru") or (aggregate == "asp" and att_dim != 128):
+            raise NotImplementedError("only front_proc='sinc' | 'conv' with aggregate='asp', att_dim=128, and front_proc='sinc' with "
+                                      "aggregate='gru' are built (Raw_ECAPA_sinc_asp.py / Raw_ECAPA_conv_asp.py / Raw_ECAPA_sinc_gru.py)")
+        if aggregate == "gru" and (front_proc != "sinc" or gru_node != 1024 or nb_gru_layers != 1):
+            raise NotImplementedError("aggregate='gru' is built with front_proc='sinc', gru_node=1024 and nb_gru_layers=1 "
+                                      "(RawNet2_custom.py:18-31 defaults)")
         self.front_proc = front_proc
+        self.aggregate = aggregate
+        if aggregate == "gru":
+            self.model_kind = "rawnet2_gru"
         if front_proc == "conv":
             self.model_kind = "rawnet2_conv"
             # no LayerNorm(nb_samp): any length; the configured crop length (if the config gives one) gets the full workspace
@@ -52,7 +60,8 @@ class RawNet2(HipModule):
         # ill-scaled one of tests/test_gpu_rawnet2.py), so it is not the default
         self._range_fallback = kwargs.get("range_fallback", "f32")
         max_batch = int(max_batch or kwargs.get("embed_batch", 256))
-        super().__init__(synth.rawnet2_param_spec(nOut=nOut, nb_samp=self.nb_samp or 0, att_dim=att_dim, front_proc=front_proc),
+        super().__init__(synth.rawnet2_param_spec(nOut=nOut, nb_samp=self.nb_samp or 0, att_dim=att_dim, front_proc=front_proc,
+                                                  aggregate=aggregate),
                          dict(embed_dim=nOut), device=device if device is not None else kwargs.get("device"),
                          compute=compute, max_batch=max_batch, primary_samples=self.nb_samp)
 

@@ -101,7 +101,7 @@ class HipModule:
         from .. import checkpoint, _lib
         mid, sd = checkpoint.read_blob(path)
         want = {"ecapa": _lib.MODEL_ECAPA, "rawnet2": _lib.MODEL_RAWNET2, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV,
-                "rawnet3": _lib.MODEL_RAWNET3}.get(self.model_kind)
+                "rawnet2_gru": _lib.MODEL_RAWNET2_GRU, "rawnet3": _lib.MODEL_RAWNET3}.get(self.model_kind)
         if want is not None and mid != want:
             raise ValueError(f"{path} holds weights of model {mid}, this module is {self.model_kind}")
         return self.load_state_dict(sd, strict=False)
@@ -148,7 +148,7 @@ class HipModule:
 
     def _is_f16_handle(self):
         """the handle stores activations as IEEE half (RawNet2's 16-bit mode: compute 'f16', or 'half' on a RawNet2 model)"""
-        return self._compute in ("f16", "fp16") or (self._compute == "half" and self.model_kind in ("rawnet2", "rawnet2_conv"))
+        return self._compute in ("f16", "fp16") or (self._compute == "half" and self.model_kind in ("rawnet2", "rawnet2_conv", "rawnet2_gru"))
 
     @staticmethod
     def _squeeze(out):

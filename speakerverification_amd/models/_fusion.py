@@ -1,10 +1,11 @@
 """Shared body of the raw-waveform + ECAPA fusion plug-ins (reference ``models/Raw_ECAPA.py``, ``Raw_ECAPA_sinc_asp.py``,
 ``Raw_ECAPA_conv_asp.py``, each :22-52, and ``Raw3_ECAPA.py``): ECAPA-TDNN (C = 512, 192-d) on the mel spectrogram of the
-waveform, concatenated with a raw-waveform network (nOut - 192 dims).  They differ in three switches:
+waveform, concatenated with a raw-waveform network (nOut - 192 dims).  They differ in four switches:
 
     model                 ECAPA input_norm   raw branch (attribute)
     Raw_ECAPA             True               RawNet2 'sinc' / asp (rawnet2v2)
     Raw_ECAPA_sinc_asp    False              RawNet2 'sinc' / asp (rawnet2v2)
+    Raw_ECAPA_sinc_gru    False              RawNet2 'sinc' / gru (rawnet2v2)
     Raw_ECAPA_conv_asp    True               RawNet2 'conv' / asp (rawnet2v2)
     Raw3_ECAPA            True               RawNet3 (rawnet)
 
@@ -34,6 +35,7 @@ class RawECAPAFusion:
     accepts_device_wave = True      # both branches take CUDA tensors as raw device pointers
     INPUT_NORM = False              # ECAPA branch: InstanceNorm1d on its input (ECAPA_TDNN.py:406-409,477-478)
     FRONT_PROC = "sinc"             # RawNet2 branch front-end (RawNet2_custom.py:45-63)
+    AGGREGATE = "asp"               # RawNet2 branch aggregation (RawNet2_custom.py:84-111)
     MODEL_NAME = "Raw_ECAPA_sinc_asp"
     RAW_ATTR = "rawnet2v2"          # the raw branch's attribute: the prefix of its state-dict keys
 
@@ -46,7 +48,7 @@ class RawECAPAFusion:
         self.training = False
 
     def _make_raw_branch(self, nOut, kw):
-        return _rawnet2.MainModel(nOut=nOut - 192, front_proc=self.FRONT_PROC, aggregate="asp", att_dim=128, **kw)
+        return _rawnet2.MainModel(nOut=nOut - 192, front_proc=self.FRONT_PROC, aggregate=self.AGGREGATE, att_dim=128, **kw)
 
     @property
     def _raw(self):

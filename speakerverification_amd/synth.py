@@ -30,6 +30,7 @@ ATT_CHANNELS = 128                        # ECAPA_TDNN.py:381
 RAWNET2_LAYERS = (1, 1, 1, 2, 1, 2)                    # RawNet2_custom.py:231
 RAWNET2_FILTERS = (128, 128, 256, 256, 512, 512)       # RawNet2_custom.py:232
 RAWNET2_SINC_K = 251                                   # RawNet2_custom.py:36
+RAWNET2_GRU_NODE = 1024                                # gru_node (RawNet2_custom.py:31)
 
 RAWNET3_C = 1024                                       # RawNet3.py:10 (C; no config sets it)
 RAWNET3_SCALE = 8                                      # model_scale (RawNet3.py:178)
@@ -76,10 +77,14 @@ def ecapa_param_spec(C=1024, n_mels=80, nOut=192, input_norm=False):
     return spec
 
 
-def rawnet2_param_spec(nOut=320, nb_samp=32000, att_dim=128, front_proc="sinc"):
+def rawnet2_param_spec(nOut=320, nb_samp=32000, att_dim=128, front_proc="sinc", aggregate="asp"):
     """Ordered (name, shape) list == ``RawNet2_custom.MainModel(front_proc=front_proc,
-    aggregate='asp').state_dict()`` of the reference: 147 tensors for ``'sinc'`` (LayerNorm, sinc filters,
-    first_bn), 140 for ``'conv'`` (``conv1 = Conv1d(1, 128, 3, stride=3)`` with bias, RawNet2_custom.py:45-52)."""
+    aggregate=aggregate).state_dict()`` of the reference: 147 tensors for ``'sinc'`` (LayerNorm, sinc filters,
+    first_bn), 140 for ``'conv'`` (``conv1 = Conv1d(1, 128, 3, stride=3)`` with bias, RawNet2_custom.py:45-52);
+    ``aggregate='gru'`` (RawNet2_custom.py:84-95) replaces bn_before_agg / attention with bn_before_gru, the GRU
+    (512 -> 1024, one layer) and fc_after_gru, and keeps the unused fc: 144 tensors with 'sinc'."""
+    if aggregate not in ("asp", "gru"):
+        raise ValueError(f"aggregate {aggregate!r}: 'asp' or 'gru'")
     f = RAWNET2_FILTERS
     if front_proc == "sinc":
         spec = [("ln.gamma", (nb_samp,)), ("ln.beta", (nb_samp,)),
@@ -102,6 +107,13 @@ def rawnet2_param_spec(nOut=320, nb_samp=32000, att_dim=128, front_proc="sinc"):
             if inpl != planes:
                 spec += [(p + ".shortcut.0.weight", (planes, inpl, 1))]
             inpl = planes
+    if aggregate == "gru":
+        G, H = 3 * RAWNET2_GRU_NODE, RAWNET2_GRU_NODE
+        spec += _bn("bn_before_gru", f[5])
+        spec += [("gru.weight_ih_l0", (G, f[5])), ("gru.weight_hh_l0", (G, H)), ("gru.bias_ih_l0", (G,)), ("gru.bias_hh_l0", (G,)),
+                 ("fc_after_gru.weight", (nOut, H)), ("fc_after_gru.bias", (nOut,)),
+                 ("fc.weight", (nOut, 2 * f[5])), ("fc.bias", (nOut,))]
+        return spec
     spec += _bn("bn_before_agg", f[5])
     spec += [("attention.0.weight", (att_dim, f[5], 1)), ("attention.0.bias", (att_dim,))]
     spec += _bn("attention.2", att_dim)
@@ -210,6 +222,9 @@ def synth_state_dict(spec, seed=1):
             base = lo if leaf == "low_hz_" else band
             jitter = rng.uniform(-3.0, 3.0, shape[0]).astype(np.float32)
             sd[name] = (base + jitter).reshape(shape).astype(np.float32)
+        elif leaf in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):      # nn.GRU's own init: U(+-1 / sqrt(hidden))
+            k = 1.0 / math.sqrt(RAWNET2_GRU_NODE)
+            sd[name] = rng.uniform(-k, k, shape).astype(np.float32)
         elif leaf == "weight" and len(shape) == 1:             # BN / InstanceNorm affine weight
             sd[name] = rng.uniform(0.5, 1.5, shape).astype(np.float32)
         elif leaf == "bias":
