@@ -6,6 +6,7 @@
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --config shard [--gpus N] [--utts-per-gpu 125000]   # BASELINE configs[4]
     python bench.py --dump-outputs DIR                                   # + what the timed path computed, as DIR/*.npy
+    python bench.py --full [--steps K] [--warmup W]                      # + every check and side measurement (below)
 
 Default workload (BASELINE.json configs[1]): ECAPA-TDNN C=1024, bf16 MFMA / fp32 accumulate, batch = 256 utterances of
 2 s @ 16 kHz per step, waveforms resident in HBM (8 distinct batches = 262 MB are rotated, so the timed loop does not
@@ -16,13 +17,18 @@ issued through the C ABI (svhip_allgather_rows) on the library's stream; torch.d
 128-byte RCCL id, the barriers and the max-over-ranks of the wall time.
 
 stdout carries exactly ONE JSON line on rank 0, compact (<= 4 KB: `compact_headline`; the driver keeps a bounded tail of stdout and
-round 4's 20 KB line did not parse): the contract's fields; `roofline` = the dominant kernel (the pointwise-conv MFMA GEMM) timed with HIP
-events on the launch stream inside the timed region; `cpu_baseline` = the CPU oracle timed on this box's host cores on a bounded sample
-(rank 0, N = 1 only); `check` (the last timed step's embeddings verified against the fp32-parity path and a bitwise re-run); `sustained`;
-`sub` = {record name: embeddings/s} and `scoring` = the BASELINE configs[3] summary (trial pairs/s).  The sub-records themselves — `kernels`
-(per-kernel table), `scoring` (+ CPU baselines), `rawnet2` (configs[2]), `ecapa_f32` / `ecapa_f32x3` / `rawnet2_f32x3` (the 1e-4-parity
-paths), `latency` (B = 1 .. 32 per call), `fusion`, `pcie`, `headline_full` — are written one JSON line each, tagged {"record": name}, to
-stderr as they are measured and to --record-file (default gpurun_out/bench_records.jsonl).
+round 4's 20 KB line did not parse): the contract's fields and `roofline` = the dominant kernel (the pointwise-conv MFMA GEMM) timed with
+HIP events on the launch stream inside the timed region.  A plain run does only that: set up, warm up, time the K steps, dump the outputs
+if asked, print the line.
+
+--full adds, after the timed steps (the timed steps themselves are the same): `check` (the last timed step's embeddings verified against
+the fp32-parity path and a bitwise re-run); `sustained`; `cpu_baseline` = the CPU oracle timed on this box's host cores on a bounded sample
+(rank 0, N = 1 only); `sub` = {record name: embeddings/s} and `scoring` = the BASELINE configs[3] summary (trial pairs/s); with N > 1 the
+`shard` record (cross-rank verification of the gathered matrix, row-sharded scoring).  --no-cpu-baseline / --no-scoring / --no-extras /
+--sustain-seconds trim a --full run.  (--config shard is a workload of its own: its all-gather and scoring are its record, --full or not.)  The sub-records themselves — `kernels` (per-kernel table), `scoring` (+ CPU baselines), `rawnet2`
+(configs[2]), `ecapa_f32` / `ecapa_f32x3` / `rawnet2_f32x3` (the 1e-4-parity paths), `latency` (B = 1 .. 32 per call), `fusion`, `pcie` —
+and `headline_full` (every run) are written one JSON line each, tagged {"record": name}, to stderr as they are measured and to the
+record file (see --record-file).
 """
 from __future__ import annotations
 
@@ -64,13 +70,18 @@ def parse():
                     help="batch = K steps of one batch per GPU (configs[1]/[2]); shard = configs[4]: a sharded utterance list, "
                          "one all-gather, row-sharded scoring")
     ap.add_argument("--utts-per-gpu", type=int, default=125000, help="--config shard: utterances per GPU (1 M / 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-scoring", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the rawnet2 / ecapa_f32 / pcie / latency sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every check and side measurement: the last step's verification, `sustained`, "
+                         "the per-kernel table, CPU baselines, scoring, the other models and precisions, latency, fusion, PCIe; with "
+                         "N > 1 the cross-rank verification and row-sharded scoring of the gathered embeddings.  Off: the headline only.")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-scoring", action="store_true", help="--full: skip the configs[3] scoring records")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the rawnet2 / ecapa_f32 / pcie / latency sub-records")
     ap.add_argument("--allow-gloo", action="store_true",
                     help="N > 1: if the RCCL communicator cannot be created, carry the all-gather over gloo (host round trip) instead of "
                          "failing; the record then says so.  Without this flag a multi-GPU run that is not on RCCL exits non-zero.")
-    ap.add_argument("--sustain-seconds", type=float, default=2.0, help="length of the extra back-to-back run reported as `sustained` (0: skip)")
+    ap.add_argument("--sustain-seconds", type=float, default=2.0,
+                    help="--full: length of the extra back-to-back run reported as `sustained` (0: skip)")
     ap.add_argument("--record-file", default=None,
                     help="JSON-lines file that receives every sub-record and the full (verbose) headline record; default "
                          "gpurun_out/bench_records.jsonl when gpurun_out/ exists, otherwise none.  stdout carries ONE compact line.")
@@ -988,13 +999,13 @@ def run_batch(args, ranks, dev):
     dt = ranks.max(time.perf_counter() - t0)
     prof = eng.profile_results()
     eng.profile(False)
-    check = verify_last_step(eng, wavs[(K - 1) % NBATCH], shard[(K - 1) * B:K * B], local, dev)
+    check = verify_last_step(eng, wavs[(K - 1) % NBATCH], shard[(K - 1) * B:K * B], local, dev) if args.full else None
     if args.dump_outputs and rank == 0:              # the last timed step of every rank, before shard_tail normalises `gathered`
         dump_outputs(args.dump_outputs, "embeddings",
                      torch.cat([gathered[r * K * B + (K - 1) * B:(r + 1) * K * B] for r in range(world)]) if ranks.launched
                      else shard[(K - 1) * B:K * B])
     shard_rec = None
-    if ranks.launched:
+    if ranks.launched and args.full:
         def regen(r, n):          # the first n rows of rank r's block = its step 0 = utterances [r * NBATCH * B, ...) of the stream
             w = torch.empty((n, SAMPLES), device=dev, dtype=torch.float32)
             eng.synth_waveforms(SEED_STREAM, r * NBATCH * B, n, SAMPLES, out=w, async_=True)
@@ -1004,7 +1015,7 @@ def run_batch(args, ranks, dev):
             return o
         shard_rec, _ = shard_tail(eng, comm, ranks, shard, dev, K * B, carrier=carrier, regen_embed=regen)
     sustained = None
-    if args.sustain_seconds > 0 and rank == 0 and world == 1:
+    if args.full and args.sustain_seconds > 0 and rank == 0 and world == 1:
         # the K timed steps above are ~0.1 s on a clock-limited chip: the same loop back to back for >= 2 s, reported next to it
         n_s = max(K, int(args.sustain_seconds / max(dt / K, 1e-6)) + 1)
         scratch = torch.empty((B, embed), device=dev, dtype=torch.float32)
@@ -1016,7 +1027,7 @@ def run_batch(args, ranks, dev):
         d_s = time.perf_counter() - ts
         sustained = {"seconds": d_s, "steps": n_s, "value": n_s * B / d_s, "unit": "embeddings/s", "ms_per_step": d_s / n_s * 1e3}
     n_all = min(K, 10)
-    kern = kernel_table(eng, wavs, B, n_all, dev) if rank == 0 else {}
+    kern = kernel_table(eng, wavs, B, n_all, dev) if args.full and rank == 0 else None
 
     if rank == 0:
         recs = Records(getattr(args, "record_file", None))
@@ -1033,20 +1044,22 @@ def run_batch(args, ranks, dev):
                        "batch_per_gpu": B, "samples": SAMPLES, "frames": eng.frames, "embed_dim": embed,
                        "waveform_batches_rotated": NBATCH, "waveform_bytes_resident": NBATCH * B * SAMPLES * 4,
                        "collective": ("one all-gather of the shard embeddings inside the timed region: " + carrier) if ranks.launched else "none"},
-            "finite": check["finite"], "check": check,
             "whole_path_TFLOPs": eng.flops_per_utterance * total_utts / dt / 1e12,
             "flops_per_utterance": eng.flops_per_utterance,
             "roofline": roofline_of(prof, label, args.compute),
         }
-        recs.emit("kernels", {"kernels": kern,
-                              "note": "per-kernel table from a separate profiled pass of %d steps (every launch bracketed); "
-                                      "the roofline kernel is timed live inside the timed region" % n_all})
+        if check is not None:
+            line["finite"], line["check"] = check["finite"], check
+        if kern is not None:
+            recs.emit("kernels", {"kernels": kern,
+                                  "note": "per-kernel table from a separate profiled pass of %d steps (every launch bracketed); "
+                                          "the roofline kernel is timed live inside the timed region" % n_all})
         if shard_rec is not None:
             line["shard"] = shard_rec
         line["sustained"] = sustained
-        line["cpu_baseline"] = cpu_baseline() if (world == 1 and not args.no_cpu_baseline and args.model == "ecapa") else None
+        line["cpu_baseline"] = cpu_baseline() if (args.full and world == 1 and not args.no_cpu_baseline and args.model == "ecapa") else None
         sub, scoring = {}, None
-        if world == 1 and not args.no_scoring and args.model == "ecapa":
+        if args.full and world == 1 and not args.no_scoring and args.model == "ecapa":
             try:
                 sc = scoring_bench(dev, with_cpu=not args.no_cpu_baseline)
                 recs.emit("scoring", sc)
@@ -1071,7 +1084,7 @@ def run_batch(args, ranks, dev):
             except Exception as e:  # scoring is reported next to, not inside, the headline
                 recs.emit("scoring", {"error": repr(e)})
                 scoring = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_extras and args.model == "ecapa" and args.compute == "bf16":
+        if args.full and world == 1 and not args.no_extras and args.model == "ecapa" and args.compute == "bf16":
             for name, fn in (("rawnet2", lambda: sub_bench("rawnet2", "f16", B, local, dev, wavs)),
                              ("rawnet2_3_streams", lambda: multi_stream_bench("rawnet2", "f16", B, local, dev, wavs)),
                              ("rawnet2_bf16", lambda: sub_bench("rawnet2", "bf16", B, local, dev, wavs, steps=5, warmup=1)),

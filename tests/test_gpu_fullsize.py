@@ -179,14 +179,14 @@ def test_bench_shard_path_at_world_one(capsys):
 def test_bench_stdout_is_one_compact_json_line(tmp_path):
     """`python bench.py` as the driver runs it (a child process): stdout is exactly ONE line, <= 4 KB, that
     json.loads and carries the contract's fields, `roofline` and (with the CPU leg on) `cpu_baseline`; the sub-records went to the
-    record file.  Short legs only (2 steps, no extras / scoring / CPU leg) — the full default run is the driver's."""
+    record file.  A --full run with its short legs only (2 steps, no extras / scoring / CPU leg)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     rf = tmp_path / "records.jsonl"
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-extras", "--no-scoring",
-                        "--no-cpu-baseline", "--sustain-seconds", "0", "--record-file", str(rf)],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-extras",
+                        "--no-scoring", "--no-cpu-baseline", "--sustain-seconds", "0", "--record-file", str(rf)],
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     out_lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -200,6 +200,32 @@ def test_bench_stdout_is_one_compact_json_line(tmp_path):
     assert line["check"]["ok"] and line["cpu_baseline"] is None
     recs = [json.loads(ln) for ln in open(rf)]
     assert [x["record"] for x in recs] == ["kernels", "headline_full"] and "gemm_pw3" in recs[0]["kernels"]
+
+
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """`python bench.py` without --full: the same one-line headline (contract fields, the live roofline) and the timed path's outputs
+    with --dump-outputs, but none of the checks or side measurements that --full adds."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rf, dump = tmp_path / "records.jsonl", tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--record-file", str(rf),
+                        "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out_lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(out_lines) == 1 and len(out_lines[0]) <= 4096
+    line = json.loads(out_lines[0])
+    assert line["metric"].startswith("embeddings/sec") and line["unit"] == "embeddings/s" and line["higher_is_better"] is True
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "bf16" and line["value"] > 0
+    assert abs(line["value"] - 256 * 2 / (line["ms_per_step"] * 2e-3)) < 1e-3 * line["value"]
+    assert line["roofline"]["kernel"] == "gemm_pw3" and line["roofline"]["launches"] == 14
+    assert line["cpu_baseline"] is None
+    assert not {"check", "sustained", "sub", "scoring", "shard"} & set(line)
+    assert [json.loads(ln)["record"] for ln in open(rf)] == ["headline_full"]
+    emb = np.load(dump / "embeddings.npy")
+    assert emb.shape == (256, 192) and emb.dtype == np.float32 and np.isfinite(emb).all()
 
 
 def test_c_abi_error_behaviour():

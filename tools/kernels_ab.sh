@@ -5,7 +5,7 @@ var=$1; shift
 for on in 1 0; do
   if [ $on = 1 ]; then export $var=1; else unset $var; fi
   rm -f /tmp/_kab.jsonl
-  python bench.py --no-extras --no-scoring --no-cpu-baseline --sustain-seconds 0 --record-file /tmp/_kab.jsonl "$@" > /tmp/_kab.out 2>/dev/null
+  python bench.py --full --no-extras --no-scoring --no-cpu-baseline --sustain-seconds 0 --record-file /tmp/_kab.jsonl "$@" > /tmp/_kab.out 2>/dev/null
   python - <<PY
 import json
 d=json.loads(open('/tmp/_kab.out').read().strip().splitlines()[-1])

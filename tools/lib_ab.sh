@@ -7,7 +7,7 @@ for rep in 1 2; do
 for v in A B; do
   if [ $v = A ]; then export SVHIP_LIB_PATH=$PWD/tools/_ab/libsvhip_A.so; else unset SVHIP_LIB_PATH; fi
   rm -f /tmp/_lab.jsonl
-  python bench.py --no-extras --no-scoring --no-cpu-baseline --sustain-seconds 0 --record-file /tmp/_lab.jsonl "$@" > /tmp/_lab.out 2>/dev/null
+  python bench.py --full --no-extras --no-scoring --no-cpu-baseline --sustain-seconds 0 --record-file /tmp/_lab.jsonl "$@" > /tmp/_lab.out 2>/dev/null
   V=$v FILT=$filt python - <<'PY'
 import json, os, re
 d = json.loads(open('/tmp/_lab.out').read().strip().splitlines()[-1])

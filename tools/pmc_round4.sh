@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 2 --warmup 2 --no-cpu-baseline --no-scoring --no-extras --sustain-seconds 0"
+B="python3 $R/bench.py --full --steps 2 --warmup 2 --no-cpu-baseline --no-scoring --no-extras --sustain-seconds 0"
 LAT="TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_LEVEL_sum"
 for m in ecapa rawnet2 f32x3; do
   case $m in ecapa) X="";; rawnet2) X="--model rawnet2 --compute f16";; f32x3) X="--compute f32x3";; esac

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="--no-cpu-baseline --no-scoring --no-extras --sustain-seconds 0"
+B="--full --no-cpu-baseline --no-scoring --no-extras --sustain-seconds 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ecapa_bf16 -o p -- python3 $R/bench.py --steps 10 --warmup 3 $B > $OUT/ecapa_bf16_bench.json 2> $OUT/ecapa_bf16.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/rawnet2_f16 -o p -- python3 $R/bench.py --model rawnet2 --compute f16 --steps 10 --warmup 3 $B > $OUT/rawnet2_f16_bench.json 2> $OUT/rawnet2_f16.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ecapa_f32 -o p -- python3 $R/bench.py --compute f32 --steps 3 --warmup 1 $B > $OUT/ecapa_f32_bench.json 2> $OUT/ecapa_f32.err
