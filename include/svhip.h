@@ -62,9 +62,19 @@ typedef enum svhip_status {
  * SVHIP_MODEL_RAWNET2_GRU (added under ABI v5): front_proc='sinc', aggregate='gru' — RawNet2_custom.MainModel's defaults and the RawNet2
  * branch of Raw_ECAPA_sinc_gru: the sinc front-end and residual stack of SVHIP_MODEL_RAWNET2, then lrelu(bn_before_gru(x)), a one-layer
  * GRU (input 512, hidden 1024, h0 = 0; RawNet2_custom.py:196-207) whose last state feeds fc_after_gru.  L >= 2438 samples; compute
- * SVHIP_F32, SVHIP_F32X3, SVHIP_F16 or SVHIP_BF16.  Weights: the 144 names of its state dict (fc.* is part of it and is not used). */
+ * SVHIP_F32, SVHIP_F32X3, SVHIP_F16 or SVHIP_BF16.  Weights: the 144 names of its state dict (fc.* is part of it and is not used).
+ * SVHIP_MODEL_TITANET (added under ABI v5): TitaNet.MainModel (models/TitaNet.py, blocks/titanet_blocks.py), the spectral branch of
+ * Tita_ECAPA and Raw_tita: on the mel POWER spectrogram (no log, no normalisation), prolog Conv1d(n_mels, H, 3) + BN + ReLU, n mega-blocks
+ * of three depthwise-separable sub-blocks (depthwise k, pointwise H -> H, BN, ReLU) + squeeze-excitation (H / 16) + a 1 x 1 BN'd skip,
+ * epilog 1 x 1 H -> 1536 + BN + ReLU, attentive statistics pooling (hidden 128, eps 1e-6) + BN(3072), Linear(3072, nOut) + BN(nOut).
+ * channels = H in {256, 512, 1024}, which fixes the depthwise kernel at 3, 7 and 11 (sizes s / m / l); embed_dim = nOut; log_input =
+ * input_norm = 0; compute SVHIP_F32 or SVHIP_BF16 (others: SVHIP_ERR_UNSUPPORTED).  Weights: the reference state-dict names (encoder.prolog.*,
+ * encoder.mega_blocks.<i>.*, encoder.epilog.*, decoder.*) for block indices 0 .. SVHIP_TITANET_MAX_BLOCKS - 1; svhip_finalize_weights takes
+ * the block count from the indices loaded contiguously from 0 (a gap or a missing tensor of a present block: SVHIP_ERR_MISSING; a depthwise
+ * weight whose kernel size is not H's: SVHIP_ERR_INVALID).  Both svhip_embed_wave (mel front-end, then the net) and svhip_embed_features. */
+#define SVHIP_TITANET_MAX_BLOCKS 32
 enum { SVHIP_MODEL_ECAPA = 0, SVHIP_MODEL_RAWNET2 = 1, SVHIP_MODEL_NONE = 2 /* fbank + scoring only */, SVHIP_MODEL_RAWNET2_CONV = 3,
-       SVHIP_MODEL_RAWNET3 = 4, SVHIP_MODEL_RAWNET2_GRU = 5 };
+       SVHIP_MODEL_RAWNET3 = 4, SVHIP_MODEL_RAWNET2_GRU = 5, SVHIP_MODEL_TITANET = 6 };
 enum { SVHIP_F32 = 0, SVHIP_BF16 = 1, SVHIP_I64 = 2, SVHIP_F32X3 = 3 /* compute only */, SVHIP_F16 = 4 /* compute only */ };
 enum { SVHIP_IN_DEVICE = 1, SVHIP_OUT_DEVICE = 2, SVHIP_ASYNC = 4 };
 
@@ -279,7 +289,9 @@ int svhip_synth_waveforms(svhip_handle* h, uint64_t seed, int64_t first_utt, int
 /* Introspection used by tests and bench.py (not part of the reference's surface).
  *   get_stage    : copy an intermediate activation of the LAST forward to host as fp32, frame-major
  *                  (B, T, C).  Names: "input","blocks.0".."blocks.3","mfa","asp","asp_bn" (ECAPA); "rn_gru_in" (the (B T, 512) GRU
- *                  input of a one-slice forward) and "rn_gru_h" (the (B, 1024) fp32 last GRU state) of SVHIP_MODEL_RAWNET2_GRU.
+ *                  input of a one-slice forward) and "rn_gru_h" (the (B, 1024) fp32 last GRU state) of SVHIP_MODEL_RAWNET2_GRU;
+ *                  "tn_prolog" (B T, H), "tn_dw0" (block 0's first depthwise output, its bias included), "tn_mega_last" (the last
+ *                  mega-block's output), "tn_enc" (B T, 1536) and "tn_pool" (B, 3072, after BN) of SVHIP_MODEL_TITANET.
  *                  Returns the element count through *count (out may be NULL to query).
  *   profile_*    : when enabled every kernel launch is bracketed by HIP events on the handle's
  *                  stream; profile_get returns accumulated milliseconds / launch count per kernel

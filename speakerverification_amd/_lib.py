@@ -19,6 +19,7 @@ MODEL_ECAPA, MODEL_RAWNET2, MODEL_NONE = 0, 1, 2
 MODEL_RAWNET2_CONV = 3                     # RawNet2 with front_proc='conv' (include/svhip.h, added under ABI v5)
 MODEL_RAWNET3 = 4                          # RawNet3, the raw-waveform branch of Raw3_ECAPA (include/svhip.h, added under ABI v5)
 MODEL_RAWNET2_GRU = 5                      # RawNet2 with front_proc='sinc', aggregate='gru' (include/svhip.h, added under ABI v5)
+MODEL_TITANET = 6                          # TitaNet, the spectral branch of Tita_ECAPA / Raw_tita (include/svhip.h, added under ABI v5)
 F32, BF16, I64, F32X3, F16 = 0, 1, 2, 3, 4
 IN_DEVICE, OUT_DEVICE, ASYNC = 1, 2, 4
 TRIAL_COSINE, TRIAL_PNORM, TRIAL_PDIST = 0, 1, 2

@@ -25,7 +25,7 @@ MAGIC = b"SVHIPWB1"
 _MODEL_IDS = {"ECAPA_TDNN": _lib.MODEL_ECAPA, "ecapa": _lib.MODEL_ECAPA, "RawNet2_custom": _lib.MODEL_RAWNET2,
               "rawnet2": _lib.MODEL_RAWNET2, "RawNet2_custom_conv": _lib.MODEL_RAWNET2_CONV, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV,
               "RawNet2_custom_gru": _lib.MODEL_RAWNET2_GRU, "rawnet2_gru": _lib.MODEL_RAWNET2_GRU,
-              "RawNet3": _lib.MODEL_RAWNET3, "rawnet3": _lib.MODEL_RAWNET3}
+              "RawNet3": _lib.MODEL_RAWNET3, "rawnet3": _lib.MODEL_RAWNET3, "TitaNet": _lib.MODEL_TITANET, "titanet": _lib.MODEL_TITANET}
 
 
 def model_id(model) -> int:
@@ -144,7 +144,11 @@ FUSION_MODELS = {
     "Raw_ECAPA_conv_asp": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom_conv", ".rawnet2")),
     # Raw3_ECAPA.py: the raw-waveform branch is RawNet3, attribute `rawnet`; its blob's model id is SVHIP_MODEL_RAWNET3
     "Raw3_ECAPA": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet.", "RawNet3", ".rawnet3")),
+    # Tita_ECAPA.py: ECAPA + TitaNet-M (attribute `titaNet`); Raw_tita.py: TitaNet-M, then RawNet2 'sinc' / asp (attribute `RawNet`)
+    "Tita_ECAPA": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("titaNet.", "TitaNet", ".titanet")),
+    "Raw_tita": (("titaNet.", "TitaNet", ".titanet"), ("RawNet.", "RawNet2_custom", ".rawnet2")),
 }
+_BRANCH_PREFIXES = ("ECAPA_TDNN.", "rawnet2v2.", "rawnet.", "titaNet.", "RawNet.")
 
 
 def fusion_blob_paths(dst, model="Raw_ECAPA_sinc_asp"):
@@ -168,6 +172,12 @@ def convert_checkpoint(src, dst, model) -> int:
         state = src
     sd = embedding_state_dict(state)
     if model in FUSION_MODELS:
+        mine = tuple(prefix for prefix, _, _ in FUSION_MODELS[model])
+        foreign = sorted({p for p in _BRANCH_PREFIXES if p not in mine and any(k.startswith(p) for k in sd)})
+        if foreign and ("titaNet." in mine or "titaNet." in foreign):    # a TitaNet fusion checkpoint as another fusion model, or the other way round
+            raise ValueError(f"{model}: the checkpoint holds {foreign[0]}* tensors, a branch this model does not have (its branches: {list(mine)})")
+        if any(k.startswith(("RawNet.conv1.", "RawNet.gru.")) for k in sd):         # Raw_tita's RawNet2 is 'sinc' / asp (Raw_tita.py:22-24)
+            raise ValueError(f"{model}: the checkpoint's RawNet2 branch is not front_proc='sinc', aggregate='asp'")
         raw_prefix = FUSION_MODELS[model][1][0]
         other = "rawnet2v2." if raw_prefix == "rawnet." else "rawnet."
         if any(k.startswith(other) for k in sd):          # a RawNet2 fusion checkpoint as Raw3_ECAPA, or the other way round
@@ -194,8 +204,8 @@ def convert_checkpoint(src, dst, model) -> int:
             write_blob(str(dst) + suffix, branch, sub)
             total += len(sub)
         return total
-    if any(k.startswith(("ECAPA_TDNN.", "rawnet2v2.", "rawnet.")) for k in sd):
-        raise ValueError("this is a fusion checkpoint (ECAPA_TDNN.* / rawnet2v2.* / rawnet.* keys): convert it with "
+    if any(k.startswith(_BRANCH_PREFIXES) for k in sd):
+        raise ValueError("this is a fusion checkpoint (ECAPA_TDNN.* / rawnet2v2.* / rawnet.* / titaNet.* / RawNet.* keys): convert it with "
                          f"model= one of {sorted(FUSION_MODELS)} (one blob per branch)")
     mid = model_id(model)
     if mid in (_lib.MODEL_RAWNET2, _lib.MODEL_RAWNET2_CONV) and any(k.startswith("gru.") for k in sd):
@@ -211,7 +221,7 @@ def main(argv=None):
     ap.add_argument("src")
     ap.add_argument("dst")
     ap.add_argument("--model", default="ECAPA_TDNN", help="reference model name (ECAPA_TDNN, RawNet2_custom, RawNet2_custom_conv, RawNet2_custom_gru, "
-                    "RawNet3, Raw_ECAPA_sinc_asp, Raw_ECAPA_sinc_gru, Raw_ECAPA, Raw_ECAPA_conv_asp, Raw3_ECAPA)")
+                    "RawNet3, TitaNet, Raw_ECAPA_sinc_asp, Raw_ECAPA_sinc_gru, Raw_ECAPA, Raw_ECAPA_conv_asp, Raw3_ECAPA, Tita_ECAPA, Raw_tita)")
     a = ap.parse_args(argv)
     n = convert_checkpoint(a.src, a.dst, a.model)
     print(f"{a.dst}: {n} tensors")

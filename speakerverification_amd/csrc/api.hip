@@ -192,7 +192,8 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) { g_create_error = std::string("no HIP device: ") + hipGetErrorString(e); return SVHIP_ERR_HIP; }
     if (cfg->device < 0 || cfg->device >= ndev) { g_create_error = "device ordinal out of range"; return SVHIP_ERR_INVALID; }
-    if (cfg->model != SVHIP_MODEL_ECAPA && !is_rawnet2(cfg->model) && cfg->model != SVHIP_MODEL_RAWNET3 && cfg->model != SVHIP_MODEL_NONE) {
+    if (cfg->model != SVHIP_MODEL_ECAPA && !is_rawnet2(cfg->model) && cfg->model != SVHIP_MODEL_RAWNET3 && cfg->model != SVHIP_MODEL_TITANET &&
+        cfg->model != SVHIP_MODEL_NONE) {
         g_create_error = "unknown model";
         return SVHIP_ERR_INVALID;
     }
@@ -203,6 +204,12 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
             g_create_error = "RawNet3 needs at least 541 samples: (L - 251) / 10 + 1 frames pooled by 5 and 3 must leave two (the unbiased variance)";
             return SVHIP_ERR_INVALID;
         }
+    }
+    if (cfg->model == SVHIP_MODEL_TITANET) {
+        if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16) { g_create_error = "TitaNet runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_UNSUPPORTED; }
+        if (!tn_kernel_size(cfg->channels)) { g_create_error = "TitaNet is built for H = 256 / 512 / 1024 (sizes s / m / l: channels)"; return SVHIP_ERR_INVALID; }
+        if (cfg->log_input || cfg->input_norm) { g_create_error = "TitaNet reads the mel power as it is: log_input and input_norm must be 0"; return SVHIP_ERR_INVALID; }
+        if (cfg->embed_dim <= 0) { g_create_error = "TitaNet needs embed_dim > 0"; return SVHIP_ERR_INVALID; }
     }
     if (cfg->model == SVHIP_MODEL_ECAPA && (cfg->channels <= 0 || cfg->channels % 64 != 0)) { g_create_error = "ECAPA channels must be a positive multiple of 64"; return SVHIP_ERR_INVALID; }
     if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16 && cfg->compute != SVHIP_F32X3 && cfg->compute != SVHIP_F16) { g_create_error = "unknown compute mode"; return SVHIP_ERR_INVALID; }
@@ -324,13 +331,15 @@ int svhip_finalize_weights(svhip_handle* h) {
     SV_HIP(h, hipSetDevice(h->cfg.device));
     std::map<std::string, std::vector<int64_t>> spec;
     model_spec(h->cfg, spec);
-    for (auto& kv : spec)
-        if (!h->host_w.count(kv.first) && kv.first.find("num_batches_tracked") == std::string::npos)
+    for (auto& kv : spec)       // (TitaNet: the block count follows from what was loaded; finalize_titanet checks its blocks)
+        if (!h->host_w.count(kv.first) && kv.first.find("num_batches_tracked") == std::string::npos &&
+            !(h->cfg.model == SVHIP_MODEL_TITANET && kv.first.rfind("encoder.mega_blocks.", 0) == 0))
             SV_FAIL(h, SVHIP_ERR_MISSING, "tensor %s was never loaded", kv.first.c_str());
     int rc = SVHIP_ERR_UNSUPPORTED;
     if (h->cfg.model == SVHIP_MODEL_ECAPA) rc = finalize_ecapa(h);
     else if (is_rawnet2(h->cfg.model)) rc = finalize_rawnet2(h);
     else if (h->cfg.model == SVHIP_MODEL_RAWNET3) rc = finalize_rawnet3(h);
+    else if (h->cfg.model == SVHIP_MODEL_TITANET) rc = finalize_titanet(h);
     else SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
     if (rc) return rc;
     SV_HIP(h, hipDeviceSynchronize());
@@ -387,7 +396,8 @@ int svhip_embed_features(svhip_handle* h, const float* feat, int32_t B, int32_t 
     int rc = check_ready(h, B);
     if (rc) return rc;
     if (!feat || !emb_out) SV_FAIL(h, SVHIP_ERR_INVALID, "null pointer");
-    if (h->cfg.model != SVHIP_MODEL_ECAPA) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "embed_features needs a spectral model (ECAPA)");
+    if (h->cfg.model != SVHIP_MODEL_ECAPA && h->cfg.model != SVHIP_MODEL_TITANET)
+        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "embed_features needs a spectral model (ECAPA, TitaNet)");
     if (T != h->T) SV_FAIL(h, SVHIP_ERR_INVALID, "T=%d but the handle was created for T=%d frames", T, h->T);
     if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
         SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
@@ -398,7 +408,7 @@ int svhip_embed_features(svhip_handle* h, const float* feat, int32_t B, int32_t 
         d_in = h->d_feat;
     }
     h->feat_is_stale = false;
-    if ((rc = ecapa_forward(h, d_in, B))) return rc;
+    if ((rc = h->cfg.model == SVHIP_MODEL_TITANET ? titanet_forward(h, d_in, B) : ecapa_forward(h, d_in, B))) return rc;
     if ((rc = emit_embeddings(h, B, emb_out, flags))) return rc;
     return finish(h, flags);
 }
@@ -410,7 +420,7 @@ int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, fl
     if (L != h->cfg.samples) SV_FAIL(h, SVHIP_ERR_INVALID, "L=%d but the handle was created for %d samples", L, h->cfg.samples);
     if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
         SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
-    if (h->cfg.model != SVHIP_MODEL_ECAPA && !is_rawnet2(h->cfg.model) && h->cfg.model != SVHIP_MODEL_RAWNET3)
+    if (h->cfg.model != SVHIP_MODEL_ECAPA && !is_rawnet2(h->cfg.model) && h->cfg.model != SVHIP_MODEL_RAWNET3 && h->cfg.model != SVHIP_MODEL_TITANET)
         SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
     SV_HIP(h, hipSetDevice(h->cfg.device));
     const float* d_in = wav;
@@ -422,6 +432,10 @@ int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, fl
         if ((rc = rawnet2_forward(h, d_in, B))) return rc;
     } else if (h->cfg.model == SVHIP_MODEL_RAWNET3) {
         if ((rc = rawnet3_forward(h, d_in, B))) return rc;
+    } else if (h->cfg.model == SVHIP_MODEL_TITANET) {        // the mel power in fp32, then the net (its prologue casts to bf16 on bf16 handles)
+        if ((rc = run(h, "fbank", 0, [&]() { return launch_fbank(h->fb, d_in, B, L, h->T, h->d_feat, h->stream); }))) return rc;
+        h->feat_is_stale = false;
+        if ((rc = titanet_forward(h, h->d_feat, B))) return rc;
     } else {
         const int T = h->T;
         // bf16 handles without the instance-norm prologue: waveform -> the 16-bit operand of blocks.0 in two launches (fbank.hip, round 6)
@@ -566,6 +580,15 @@ int svhip_get_stage(svhip_handle* h, const char* name, float* out, int64_t* coun
         if (n == "rn3_pooled") { src = h->rn3_pooled; rows = B; cols = ld = 3072; f32 = true; }
         else if (i == 5) SV_FAIL(h, SVHIP_ERR_INVALID, "unknown stage %s", name);
         else { src = h->rn3_stage[i]; rows = (size_t)B * h->rn3_stage_T[i]; cols = h->rn3_stage_C[i]; ld = h->rn3_stage_ld[i]; }
+    }
+    else if (n.rfind("tn_", 0) == 0 && h->cfg.model == SVHIP_MODEL_TITANET) {      // TitaNet: tn_prolog, tn_dw0, tn_mega_last, tn_enc, tn_pool
+        const int H = C;
+        if (n == "tn_prolog") { src = h->tn_buf[0]; cols = ld = H; }
+        else if (n == "tn_mega_last") { src = h->tn_buf[1]; cols = ld = H; }
+        else if (n == "tn_dw0") { src = h->tn_buf[2]; cols = ld = H; }
+        else if (n == "tn_enc") { src = h->tn_enc; cols = ld = 1536; }
+        else if (n == "tn_pool") { src = h->tn_pool; rows = B; cols = ld = 3072; f32 = true; }
+        else SV_FAIL(h, SVHIP_ERR_INVALID, "unknown stage %s", name);
     }
     else if (n == "mel") {
         if (h->feat_is_stale) SV_FAIL(h, SVHIP_ERR_STATE, "stage mel: the last forward ran the fused front-end, which never forms the mel power "

@@ -304,10 +304,47 @@ static void rawnet3_spec(const svhip_config& c, std::map<std::string, std::vecto
     bn("bn6", nOut);
 }
 
+// TitaNet.MainModel (TitaNet.py:124-159,202-318,321-431): the names of its state dict for SVHIP_TITANET_MAX_BLOCKS mega-blocks; a checkpoint
+// holds the first n of them (finalize_titanet)
+static void tn_block_spec(int64_t H, int64_t k, const std::string& p, std::map<std::string, std::vector<int64_t>>& spec);
+static void titanet_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec) {
+    auto bn = [&](const std::string& p, int64_t n) {
+        spec[p + ".weight"] = {n}; spec[p + ".bias"] = {n}; spec[p + ".running_mean"] = {n};
+        spec[p + ".running_var"] = {n}; spec[p + ".num_batches_tracked"] = {};
+    };
+    const int64_t H = c.channels, k = tn_kernel_size(c.channels), D = 1536, nOut = c.embed_dim;
+    spec["encoder.prolog.conv_block.0.weight"] = {H, (int64_t)c.n_mels, 3}; spec["encoder.prolog.conv_block.0.bias"] = {H};
+    bn("encoder.prolog.conv_block.1", H);
+    for (int i = 0; i < SVHIP_TITANET_MAX_BLOCKS; ++i) tn_block_spec(H, k, "encoder.mega_blocks." + std::to_string(i) + ".", spec);
+    spec["encoder.epilog.conv_block.0.weight"] = {D, H, 1}; spec["encoder.epilog.conv_block.0.bias"] = {D};
+    bn("encoder.epilog.conv_block.1", D);
+    spec["decoder.pool.0.in_linear.weight"] = {128, D}; spec["decoder.pool.0.in_linear.bias"] = {128};
+    spec["decoder.pool.0.out_linear.weight"] = {D, 128}; spec["decoder.pool.0.out_linear.bias"] = {D};
+    bn("decoder.pool.1", 2 * D);
+    spec["decoder.linear.0.weight"] = {nOut, 2 * D}; spec["decoder.linear.0.bias"] = {nOut};
+    bn("decoder.linear.1", nOut);
+}
+static void tn_block_spec(int64_t H, int64_t k, const std::string& p, std::map<std::string, std::vector<int64_t>>& spec) {
+    auto bn = [&](const std::string& q, int64_t n) {
+        spec[q + ".weight"] = {n}; spec[q + ".bias"] = {n}; spec[q + ".running_mean"] = {n};
+        spec[q + ".running_var"] = {n}; spec[q + ".num_batches_tracked"] = {};
+    };
+    for (int j = 0; j < 3; ++j) {
+        const std::string q = p + "sub_blocks." + std::to_string(j) + ".conv_block.";
+        spec[q + "0.conv.0.weight"] = {H, 1, k}; spec[q + "0.conv.0.bias"] = {H};
+        spec[q + "0.conv.1.weight"] = {H, H, 1}; spec[q + "0.conv.1.bias"] = {H};
+        bn(q + "1", H);
+    }
+    spec[p + "sub_blocks.3.excitation.0.weight"] = {H / 16, H}; spec[p + "sub_blocks.3.excitation.2.weight"] = {H, H / 16};
+    spec[p + "skip_connection.0.weight"] = {H, H, 1}; spec[p + "skip_connection.0.bias"] = {H};
+    bn(p + "skip_connection.1", H);
+}
+
 void model_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec) {
     if (c.model == SVHIP_MODEL_ECAPA) ecapa_spec(c, spec);
     else if (is_rawnet2(c.model)) rawnet2_spec(c, spec);
     else if (c.model == SVHIP_MODEL_RAWNET3) rawnet3_spec(c, spec);
+    else if (c.model == SVHIP_MODEL_TITANET) titanet_spec(c, spec);
 }
 
 static const HostTensor* getw(svhip_handle* h, const std::string& name) {
@@ -774,6 +811,125 @@ int finalize_rawnet3(svhip_handle* h) {
     return SVHIP_OK;
 }
 
+// ---- TitaNet ---------------------------------------------------------------------------------------------
+int titanet_blocks_loaded(const svhip_handle* h) {
+    int n = 0;
+    while (n < SVHIP_TITANET_MAX_BLOCKS) {
+        const std::string p = "encoder.mega_blocks." + std::to_string(n) + ".";
+        auto it = h->host_w.lower_bound(p);
+        if (it == h->host_w.end() || it->first.compare(0, p.size(), p) != 0) break;
+        ++n;
+    }
+    return n;
+}
+
+// conv (N, cin, taps) + bias followed directly by BatchNorm1d(eval, eps 1e-5): the BN folded into the conv, W' = s W, b' = s b + t (double
+// arithmetic on the host), packed as a plain conv layer
+static int make_conv_bn(svhip_handle* h, ConvLayer& L, const std::string& conv, const std::string& bnp) {
+    const HostTensor *w = getw(h, conv + ".weight"), *b = getw(h, conv + ".bias");
+    const HostTensor *g = getw(h, bnp + ".weight"), *be = getw(h, bnp + ".bias"), *rm = getw(h, bnp + ".running_mean"), *rv = getw(h, bnp + ".running_var");
+    if (!w || !b) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %s.%s", conv.c_str(), !w ? "weight" : "bias");
+    if (!g || !be || !rm || !rv) SV_FAIL(h, SVHIP_ERR_MISSING, "missing BatchNorm tensors for %s", bnp.c_str());
+    const int64_t N = w->shape[0], per = w->numel() / N;
+    HostTensor fw = *w, fb = *b;
+    for (int64_t n = 0; n < N; ++n) {
+        const double sc = (double)g->data[n] / std::sqrt((double)rv->data[n] + 1e-5);
+        for (int64_t i = 0; i < per; ++i) fw.data[n * per + i] = (float)(sc * (double)w->data[n * per + i]);
+        fb.data[n] = (float)(sc * (double)b->data[n] + ((double)be->data[n] - (double)rm->data[n] * sc));
+    }
+    const std::string fwn = "#fold." + conv + ".weight", fbn = "#fold." + conv + ".bias";
+    h->host_w[fwn] = std::move(fw);
+    h->host_w[fbn] = std::move(fb);
+    int rc = make_conv(h, L, fwn, fbn, "", 1);
+    h->host_w.erase(fwn);
+    h->host_w.erase(fbn);
+    L.scale = h->d_ones;          // (an identity affine: the persistent 16-bit GEMM takes layers that carry all three vectors)
+    L.shift = h->d_zeros;
+    return rc;
+}
+
+// a [rows][cols] fp32 matrix in the handle's storage type (bf16 handles: bf16, else null)
+static int upload_h16(svhip_handle* h, const std::vector<float>& m, void** dst) {
+    std::vector<uint16_t> v(m.size());
+    for (size_t i = 0; i < m.size(); ++i) v[i] = f32_to_bf16_rne(m[i]);
+    uint16_t* d;
+    int rc = dev_upload(h, &d, v);
+    *dst = d;
+    return rc;
+}
+
+int finalize_titanet(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    const int H = c.channels, k = tn_kernel_size(H), Hh = H / 16, D = 1536, nOut = c.embed_dim, T = h->T;
+    const int nb = titanet_blocks_loaded(h);
+    if (nb == 0) SV_FAIL(h, SVHIP_ERR_MISSING, "no mega-block was loaded (encoder.mega_blocks.0.*)");
+    for (auto& kv : h->host_w)          // a gap: tensors of a block beyond the contiguous run
+        if (kv.first.rfind("encoder.mega_blocks.", 0) == 0 && atoi(kv.first.c_str() + 20) >= nb)
+            SV_FAIL(h, SVHIP_ERR_MISSING, "%s is loaded but mega-block %d is missing (blocks are counted contiguously from 0)", kv.first.c_str(), nb);
+    {
+        std::map<std::string, std::vector<int64_t>> bspec;
+        for (int i = 0; i < nb; ++i) tn_block_spec(H, k, "encoder.mega_blocks." + std::to_string(i) + ".", bspec);
+        for (auto& kv : bspec)
+            if (!h->host_w.count(kv.first) && kv.first.find("num_batches_tracked") == std::string::npos)
+                SV_FAIL(h, SVHIP_ERR_MISSING, "tensor %s was never loaded (mega-block count %d)", kv.first.c_str(), nb);
+    }
+    h->tn_k = k;
+    h->tn.assign(nb, svhip_handle::TnBlock{});
+    int rc;
+    if ((rc = make_conv_bn(h, h->tn_prolog, "encoder.prolog.conv_block.0", "encoder.prolog.conv_block.1"))) return rc;
+    double fl = h->tn_prolog.flops_per_row;
+    for (int i = 0; i < nb; ++i) {
+        svhip_handle::TnBlock& Bk = h->tn[i];
+        const std::string p = "encoder.mega_blocks." + std::to_string(i) + ".";
+        for (int j = 0; j < 3; ++j) {
+            const std::string q = p + "sub_blocks." + std::to_string(j) + ".conv_block.";
+            const HostTensor* dw = getw(h, q + "0.conv.0.weight");            // (H, 1, k)
+            if (!dw || dw->shape.size() != 3 || dw->shape[2] != k) SV_FAIL(h, SVHIP_ERR_INVALID, "%s0.conv.0.weight: depthwise kernel size must be %d", q.c_str(), k);
+            std::vector<float> tw((size_t)k * H);
+            for (int cch = 0; cch < H; ++cch)
+                for (int t = 0; t < k; ++t) tw[(size_t)t * H + cch] = dw->data[(size_t)cch * k + t];
+            if ((rc = dev_upload(h, &Bk.dw_w[j], tw))) return rc;
+            if ((rc = upload_f32(h, q + "0.conv.0.bias", &Bk.dw_b[j]))) return rc;
+            if ((rc = make_conv_bn(h, Bk.pw[j], q + "0.conv.1", q + "1"))) return rc;
+            fl += Bk.pw[j].flops_per_row + 2.0 * k * H;
+        }
+        if ((rc = make_conv_bn(h, Bk.skip, p + "skip_connection.0", p + "skip_connection.1"))) return rc;
+        fl += Bk.skip.flops_per_row;
+        const HostTensor *w1 = getw(h, p + "sub_blocks.3.excitation.0.weight"), *w2 = getw(h, p + "sub_blocks.3.excitation.2.weight");
+        std::vector<float> m1(w1->data), m2((size_t)Hh * H);
+        for (int cch = 0; cch < H; ++cch)
+            for (int n = 0; n < Hh; ++n) m2[(size_t)n * H + cch] = w2->data[(size_t)cch * Hh + n];
+        if ((rc = dev_upload(h, &Bk.se1, m1))) return rc;
+        if ((rc = dev_upload(h, &Bk.se2T, m2))) return rc;
+        if (h->bf16) {
+            if ((rc = upload_h16(h, m1, &Bk.se1_bf))) return rc;
+            if ((rc = upload_h16(h, m2, &Bk.se2T_bf))) return rc;
+        }
+    }
+    if ((rc = make_conv_bn(h, h->tn_epilog, "encoder.epilog.conv_block.0", "encoder.epilog.conv_block.1"))) return rc;
+    if ((rc = make_conv(h, h->tn_att_in, "decoder.pool.0.in_linear.weight", "decoder.pool.0.in_linear.bias", "", 1))) return rc;
+    if ((rc = make_conv(h, h->tn_att_out, "decoder.pool.0.out_linear.weight", "decoder.pool.0.out_linear.bias", "", 1))) return rc;
+    if ((rc = make_bn(h, "decoder.pool.1", 2 * D, &h->tn_pbn_scale, &h->tn_pbn_shift))) return rc;
+    {
+        // decoder.linear = Linear(3072, nOut) + BatchNorm1d(nOut): folded into one fp32 linear
+        const HostTensor *w = getw(h, "decoder.linear.0.weight"), *b = getw(h, "decoder.linear.0.bias");
+        const HostTensor *g = getw(h, "decoder.linear.1.weight"), *be = getw(h, "decoder.linear.1.bias");
+        const HostTensor *rm = getw(h, "decoder.linear.1.running_mean"), *rv = getw(h, "decoder.linear.1.running_var");
+        std::vector<float> fw((size_t)nOut * 2 * D), fb(nOut);
+        for (int n = 0; n < nOut; ++n) {
+            const double sc = (double)g->data[n] / std::sqrt((double)rv->data[n] + 1e-5);
+            for (int i = 0; i < 2 * D; ++i) fw[(size_t)n * 2 * D + i] = (float)(sc * (double)w->data[(size_t)n * 2 * D + i]);
+            fb[n] = (float)(sc * (double)b->data[n] + ((double)be->data[n] - (double)rm->data[n] * sc));
+        }
+        h->tn_fc.N = nOut; h->tn_fc.K = 2 * D;
+        if ((rc = dev_upload(h, &h->tn_fc.W, fw))) return rc;
+        if ((rc = dev_upload(h, &h->tn_fc.bias, fb))) return rc;
+    }
+    fl += h->tn_epilog.flops_per_row + h->tn_att_in.flops_per_row + h->tn_att_out.flops_per_row;
+    h->flops_per_utt = (double)T * fl + 2.0 * nOut * 2 * D;
+    return SVHIP_OK;
+}
+
 int alloc_workspace(svhip_handle* h) {
     const svhip_config& c = h->cfg;
     const size_t B = c.max_batch, T = h->T, M = B * T, C = c.channels, C3 = 3 * C, e = h->esz;
@@ -858,6 +1014,29 @@ int alloc_workspace(svhip_handle* h) {
         if ((rc = dev_alloc(h, &h->rn3_ctx, B * 128))) return rc;
         if ((rc = dev_alloc(h, &h->rn3_logit, B * T2))) return rc;
         if ((rc = dev_alloc(h, &h->rn3_pooled, B * 3072))) return rc;
+    }
+    if (c.model == SVHIP_MODEL_TITANET) {
+        // (TitaNet forward, api_titanet.hip): six (B T, H) activation buffers, the encoder output, the attention activation and energies
+        const size_t H = C;
+        char* p;
+        auto actbuf = [&](void** dst, size_t elems) -> int {
+            int r = dev_alloc(h, &p, elems * e + 256);
+            *dst = p;
+            return r;
+        };
+        if ((rc = actbuf(&h->X_in, M * c.n_mels))) return rc;
+        for (int i = 0; i < 6; ++i) if ((rc = actbuf(&h->tn_buf[i], M * H))) return rc;
+        if ((rc = actbuf(&h->tn_enc, M * 1536))) return rc;
+        if ((rc = actbuf(&h->tn_att, M * 128))) return rc;
+        if ((rc = dev_alloc(h, &h->tn_logits, M * 1536))) return rc;
+        if ((rc = dev_alloc(h, &h->tn_mean, B * H))) return rc;
+        if ((rc = dev_alloc(h, &h->tn_gate, B * H))) return rc;
+        if ((rc = dev_alloc(h, &h->tn_pool_raw, B * 3072))) return rc;
+        if ((rc = dev_alloc(h, &h->tn_pool, B * 3072))) return rc;
+        if (h->bf16) {          // the third pointwise GEMM's column-sum partials (the SE squeeze)
+            h->colsum_region = (int64_t)((M + 255) / 256 + 2) * 16 * H;
+            if ((rc = dev_alloc(h, &h->d_colsum, (size_t)2 * h->colsum_region))) return rc;
+        }
     }
     if (c.model == SVHIP_MODEL_ECAPA) {
         char* p;

@@ -86,7 +86,8 @@ template <> struct MmaTraits<f16_t> {         // SVHIP_F16 handles (RawNet2)
 
 // activation pairs used by the models, fixed at compile time (a runtime switch inlined 128 times
 // made the epilogue 30k instructions long and blew the instruction cache)
-enum Epi : int { EPI_NONE = 0, EPI_RELU = 1, EPI_GELU = 2, EPI_RELU_TANH = 3, EPI_LRELU03 = 4, EPI_BN_LRELU03 = 5, EPI_LRELU001 = 6 };
+enum Epi : int { EPI_NONE = 0, EPI_RELU = 1, EPI_GELU = 2, EPI_RELU_TANH = 3, EPI_LRELU03 = 4, EPI_BN_LRELU03 = 5, EPI_LRELU001 = 6,
+                 EPI_TANH = 7 /* act1 none, act2 tanh: TitaNet's attention in_linear */ };
 
 // erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7) on the fast exp / rcp units: bf16 path only
 __device__ __forceinline__ float gelu_fast(float x) {
@@ -301,7 +302,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
                     if (p.bias_utt) v += p.bias_utt[(int64_t)(m / p.T) * p.ld_bu + n];
                     v = epilogue_act1<T, EPI>(v);
                     v = fmaf(v, sc, sh);
-                    if (EPI == EPI_RELU_TANH) v = tanhf(v);
+                    if (EPI == EPI_RELU_TANH || EPI == EPI_TANH) v = tanhf(v);
                     if (EPI == EPI_BN_LRELU03) v = v > 0.0f ? v : 0.3f * v;
                     if (p.R) v += to_f32<T>(reinterpret_cast<const T*>(p.R)[(int64_t)m * p.ldr + n]);
                     if (out_f32) reinterpret_cast<float*>(p.Y)[(int64_t)m * p.ldy + n] = v;
@@ -349,6 +350,7 @@ hipError_t launch_t(const GemmParams& p, hipStream_t stream) {
     if (p.act1 == ACT_RELU && p.act2 == ACT_NONE) return launch_epi<T, EPI_RELU>(p, stream);
     if (p.act1 == ACT_GELU && p.act2 == ACT_NONE) return launch_epi<T, EPI_GELU>(p, stream);
     if (p.act1 == ACT_RELU && p.act2 == ACT_TANH) return launch_epi<T, EPI_RELU_TANH>(p, stream);
+    if (p.act1 == ACT_NONE && p.act2 == ACT_TANH) return launch_epi<T, EPI_TANH>(p, stream);
     }
     if (p.act1 == ACT_LRELU03 && p.act2 == ACT_NONE) return launch_epi<T, EPI_LRELU03>(p, stream);
     if (p.act1 == ACT_NONE && p.act2 == ACT_LRELU03) return launch_epi<T, EPI_BN_LRELU03>(p, stream);

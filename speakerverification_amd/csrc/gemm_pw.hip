@@ -52,7 +52,8 @@ template <int BN> struct TileCfg {
     static constexpr int LOADS = (PBM + BN) / 64;              // global_load_lds per thread per K-step: 6 / 8
 };
 
-enum Epi : int { EPI_NONE = 0, EPI_RELU = 1, EPI_GELU = 2, EPI_RELU_TANH = 3, EPI_LRELU03 = 4, EPI_BN_LRELU03 = 5, EPI_LRELU001 = 6 };
+enum Epi : int { EPI_NONE = 0, EPI_RELU = 1, EPI_GELU = 2, EPI_RELU_TANH = 3, EPI_LRELU03 = 4, EPI_BN_LRELU03 = 5, EPI_LRELU001 = 6,
+                 EPI_TANH = 7 /* act1 none, act2 tanh: TitaNet's attention in_linear */ };
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * ROWB + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
@@ -337,7 +338,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pw_kernel(GemmParams p) {
                     float t = acc[i][j][4 * g + e] + b4[e] + bu[e];
                     t = act1<T, EPI>(t);
                     t = fmaf(t, sc4[e], sh4[e]);
-                    if (EPI == EPI_RELU_TANH) t = tanhf(t);
+                    if (EPI == EPI_RELU_TANH || EPI == EPI_TANH) t = tanhf(t);
                     if (EPI == EPI_BN_LRELU03) t = t > 0.0f ? t : 0.3f * t;
                     v[e] = t;
                 }
@@ -413,6 +414,7 @@ hipError_t launch_epi(const GemmParams& p, hipStream_t stream) {
     if (p.act1 == ACT_RELU && p.act2 == ACT_NONE) return launch_inst<T, EPI_RELU, OUT_F32, BN>(p, stream);
     if (p.act1 == ACT_GELU && p.act2 == ACT_NONE) return launch_inst<T, EPI_GELU, OUT_F32, BN>(p, stream);
     if (p.act1 == ACT_RELU && p.act2 == ACT_TANH) return launch_inst<T, EPI_RELU_TANH, OUT_F32, BN>(p, stream);
+    if (p.act1 == ACT_NONE && p.act2 == ACT_TANH) return launch_inst<T, EPI_TANH, OUT_F32, BN>(p, stream);
     }
     if (p.act1 == ACT_LRELU03 && p.act2 == ACT_NONE) return launch_inst<T, EPI_LRELU03, OUT_F32, BN>(p, stream);
     if (p.act1 == ACT_NONE && p.act2 == ACT_LRELU03) return launch_inst<T, EPI_BN_LRELU03, OUT_F32, BN>(p, stream);

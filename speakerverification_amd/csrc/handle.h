@@ -175,6 +175,29 @@ struct svhip_handle {
     const void* rn3_stage[5] = {};            // svhip_get_stage: front-end, layer1, layer2, layer3, layer4 outputs of the last forward
     int rn3_stage_T[5] = {}, rn3_stage_C[5] = {}, rn3_stage_ld[5] = {};
 
+    // TitaNet layers (SVHIP_MODEL_TITANET: models/TitaNet.py).  Every BatchNorm follows its conv directly, so it is folded into that
+    // conv's weights and bias at finalize (the GEMM epilogues apply at most the ReLU)
+    struct TnBlock {
+        float* dw_w[3] = {};                  // depthwise weights, tap-major [k][H] fp32
+        float* dw_b[3] = {};                  // depthwise biases [H]
+        svhip::ConvLayer pw[3], skip;         // pointwise convs + BN (ReLU in the epilogue); the 1 x 1 skip + BN
+        float* se1 = nullptr;                 // excitation.0 [H / 16][H] (bf16 handles: bf16 copy in se1_bf)
+        float* se2T = nullptr;                // excitation.2 transposed [H / 16][H]
+        void *se1_bf = nullptr, *se2T_bf = nullptr;
+    };
+    std::vector<TnBlock> tn;                  // one per mega-block
+    int tn_k = 0;                             // depthwise kernel size (3 / 7 / 11 for H = 256 / 512 / 1024)
+    svhip::ConvLayer tn_prolog, tn_epilog, tn_att_in, tn_att_out;     // prolog (k = 3, zero padding), epilog, attention in_linear / out_linear
+    float *tn_pbn_scale = nullptr, *tn_pbn_shift = nullptr;        // decoder.pool.1 (BatchNorm1d(3072))
+    svhip::LinearLayer tn_fc;                 // decoder.linear.0 with decoder.linear.1 (BatchNorm1d(nOut)) folded in
+    void* tn_buf[6] = {};                     // (Bmax T, H) each: prolog output, block output, block 0's first depthwise output, depthwise
+                                              // output, sub-block output, skip (the first three are the stages tn_prolog / tn_mega_last / tn_dw0)
+    void* tn_enc = nullptr;                   // (Bmax T, 1536) epilog output
+    void* tn_att = nullptr;                   // (Bmax T, 128) tanh(in_linear(.))
+    float* tn_logits = nullptr;               // (Bmax T, 1536) fp32 attention energies
+    float *tn_mean = nullptr, *tn_gate = nullptr;                  // (Bmax, H) SE squeeze, SE gate
+    float *tn_pool_raw = nullptr, *tn_pool = nullptr;              // (Bmax, 3072) pooled [mean | std], after BN
+
     // workspace (device)
     float* d_wav = nullptr;       // (Bmax, L)
     float* d_feat = nullptr;      // (Bmax, n_mels, T) mel power
@@ -310,6 +333,7 @@ int run(svhip_handle* h, const char* label, double flops, F&& launch) {
 inline bool is_rawnet2(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_CONV || model == SVHIP_MODEL_RAWNET2_GRU; }
 inline bool rn_is_sinc(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_GRU; }     // front_proc='sinc'
 inline bool rn_is_gru(int model) { return model == SVHIP_MODEL_RAWNET2_GRU; }                                       // aggregate='gru'
+inline int tn_kernel_size(int H) { return H == 256 ? 3 : H == 512 ? 7 : H == 1024 ? 11 : 0; }      // TitaNet s / m / l (TitaNet.py:152-157)
 inline int rn3_frames(int L) { return (L - RN3_TAPS) / RN3_STRIDE + 1; }      // T0 of RawNet3's front-end
 inline void* off(void* base, size_t elems, int esz) { return reinterpret_cast<char*>(base) + elems * esz; }
 inline const void* off(const void* base, size_t elems, int esz) { return reinterpret_cast<const char*>(base) + elems * esz; }
@@ -320,6 +344,8 @@ void model_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t
 int finalize_ecapa(svhip_handle* h);
 int finalize_rawnet2(svhip_handle* h);
 int finalize_rawnet3(svhip_handle* h);
+int finalize_titanet(svhip_handle* h);
+int titanet_blocks_loaded(const svhip_handle* h);      // contiguous mega-block indices loaded from 0
 int alloc_workspace(svhip_handle* h);
 
 // api_gemm.hip: the GEMM of one conv layer.  conv_plan is the one place that decides its kernel: conv_gemm launches what it returns,
@@ -341,9 +367,10 @@ int conv_gemm(svhip_handle* h, const ConvLayer& L, const GemmParams& p, const vo
 using ForwardPart = int (*)(svhip_handle* h, const float* in, int b0, int B);
 int forward_lanes(svhip_handle* h, ForwardPart part, const float* in, int B, int lanes, int per);
 
-// api_ecapa.hip, api_rawnet2.hip, api_rawnet3.hip: the whole-batch forwards
+// api_ecapa.hip, api_rawnet2.hip, api_rawnet3.hip, api_titanet.hip: the whole-batch forwards
 int ecapa_forward(svhip_handle* h, const float* d_feat, int B);
 int rawnet2_forward(svhip_handle* h, const float* d_wav, int B);
 int rawnet3_forward(svhip_handle* h, const float* d_wav, int B);
+int titanet_forward(svhip_handle* h, const float* d_feat, int B);      // from the mel power (B, n_mels, T)
 
 }  // namespace svhip

@@ -401,6 +401,21 @@ hipError_t launch_rn3_tstats(const void* x, int ldx, int dt, int B, int Tn, int 
 hipError_t launch_rn3_ctx_pool(const void* hatt, int ldh, const float* w2, const float* b2, float* logit, const void* x, int ldx, int dt, int B, int Tn, int C,
                                const float* bn_scale, const float* bn_shift, const double* in_stats, float* pooled, hipStream_t stream);
 
+// ---------------------------------------------------------------------------------------------
+// TitaNet (titanet.hip): the depthwise 1-D convolution over frame-major (B T, C) activations, odd k in {3, 7, 11}, zero "same" padding
+// at each utterance's edges, fp32 accumulation in a fixed tap order; fp32 or bf16 storage (dt), C % 8 == 0, 16-byte aligned pointers.
+// w: tap-major [k][C] fp32; bias [C] fp32.
+// ---------------------------------------------------------------------------------------------
+// d = dwconv(x) + bias
+hipError_t launch_tn_dw(const void* x, void* d, const float* w, const float* bias, int dt, int k, int B, int Tn, int C, hipStream_t stream);
+// y = relu(skip + gate[b, :] * h3) (gate (B, C) fp32); with d != null also d = dwconv(y) + bias (w, bias, k: the next block's first
+// depthwise layer) in the same pass, y recomputed on the halo rows
+hipError_t launch_tn_mega_tail(const void* skip, const void* h3, const float* gate, void* y, const float* w, const float* bias, void* d, int dt, int k,
+                               int B, int Tn, int C, hipStream_t stream);
+
+// rows[b, 0:n) (row stride ld) = NaN for every utterance b whose input x[b * per_utt .. (b + 1) * per_utt) holds an inf / NaN
+hipError_t launch_tn_nonfinite_rows(const float* x, int64_t per_utt, int B, float* rows, int ld, int n, hipStream_t stream);
+
 // synthetic waveforms from a counter-based RNG (synth.hip): out (B, L) fp32 = utterances [first_utt, first_utt + B) of the stream `seed`
 hipError_t launch_synth_wave(float* out, uint64_t seed, int64_t first_utt, int B, int L, hipStream_t stream);
 

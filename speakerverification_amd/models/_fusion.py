@@ -8,6 +8,10 @@ waveform, concatenated with a raw-waveform network (nOut - 192 dims).  They diff
     Raw_ECAPA_sinc_gru    False              RawNet2 'sinc' / gru (rawnet2v2)
     Raw_ECAPA_conv_asp    True               RawNet2 'conv' / asp (rawnet2v2)
     Raw3_ECAPA            True               RawNet3 (rawnet)
+    Tita_ECAPA            True               TitaNet-M on the same mel spectrogram (titaNet)
+
+``Raw_tita`` uses the same body with TitaNet-M (``titaNet``, 192-d) in place of the ECAPA branch and RawNet2 'sinc' / asp
+(``RawNet``) as the second: FIRST_ATTR names the first branch and ``_make_first_branch`` builds it.
 
 As in the reference the ECAPA branch inherits ``features`` from the config: with ``features: raw`` (what every fusion YAML
 sets) it consumes the mel POWER without log / mean normalisation (ECAPA_TDNN.py:473).  Both branches read the same waveform;
@@ -38,25 +42,37 @@ class RawECAPAFusion:
     AGGREGATE = "asp"               # RawNet2 branch aggregation (RawNet2_custom.py:84-111)
     MODEL_NAME = "Raw_ECAPA_sinc_asp"
     RAW_ATTR = "rawnet2v2"          # the raw branch's attribute: the prefix of its state-dict keys
+    FIRST_ATTR = "ECAPA_TDNN"       # the first (mel-spectrogram) branch's attribute
 
     def __init__(self, nOut=512, **kwargs):
         kw = dict(kwargs)
         kw.pop("channels", None)
         kw.pop("input_norm", None)
-        self.ECAPA_TDNN = _ecapa.MainModel(nOut=192, channels=[512, 512, 512, 512, 1536], input_norm=self.INPUT_NORM, **kw)
+        setattr(self, self.FIRST_ATTR, self._make_first_branch(kw))
         setattr(self, self.RAW_ATTR, self._make_raw_branch(nOut, kw))
         self.training = False
+
+    def _make_first_branch(self, kw):
+        return _ecapa.MainModel(nOut=192, channels=[512, 512, 512, 512, 1536], input_norm=self.INPUT_NORM, **kw)
 
     def _make_raw_branch(self, nOut, kw):
         return _rawnet2.MainModel(nOut=nOut - 192, front_proc=self.FRONT_PROC, aggregate=self.AGGREGATE, att_dim=128, **kw)
 
     @property
+    def _first(self):
+        return getattr(self, self.FIRST_ATTR)
+
+    @property
     def _raw(self):
         return getattr(self, self.RAW_ATTR)
 
+    def _raw_forward(self, x):
+        """the second branch on the waveform batch"""
+        return self._raw(x)
+
     # nn.Module look-alikes --------------------------------------------------------------------------
     def to(self, device=None, *a, **k):
-        self.ECAPA_TDNN.to(device)
+        self._first.to(device)
         self._raw.to(device)
         return self
 
@@ -69,22 +85,23 @@ class RawECAPAFusion:
         return self
 
     def parameters(self):
-        yield from self.ECAPA_TDNN.parameters()
+        yield from self._first.parameters()
         yield from self._raw.parameters()
 
     def state_dict(self):
-        sd = {"ECAPA_TDNN." + k: v for k, v in self.ECAPA_TDNN.state_dict().items()}
+        sd = {self.FIRST_ATTR + "." + k: v for k, v in self._first.state_dict().items()}
         sd.update({self.RAW_ATTR + "." + k: v for k, v in self._raw.state_dict().items()})
         return sd
 
     def load_state_dict(self, sd, strict=True):
-        e = {k[len("ECAPA_TDNN."):]: v for k, v in sd.items() if k.startswith("ECAPA_TDNN.")}
+        pre1 = self.FIRST_ATTR + "."
+        e = {k[len(pre1):]: v for k, v in sd.items() if k.startswith(pre1)}
         pre = self.RAW_ATTR + "."
         r = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
-        other = [k for k in sd if not k.startswith(("ECAPA_TDNN.", pre, "compute_features."))]
+        other = [k for k in sd if not k.startswith((pre1, pre, "compute_features."))]
         if strict and other:
             raise KeyError(f"unexpected keys {other[:4]}")
-        m1 = self.ECAPA_TDNN.load_state_dict(e, strict=strict)
+        m1 = self._first.load_state_dict(e, strict=strict)
         m2 = self._raw.load_state_dict(r, strict=strict)
         return m1, m2
 
@@ -98,8 +115,8 @@ class RawECAPAFusion:
         if not os.path.exists(p_raw):
             raise ValueError(f"{self.MODEL_NAME}: no {p_raw} beside {path}: the pair was converted for another fusion model "
                              "(RawNet2 and RawNet3 branches are written as .rawnet2 / .rawnet3)")
-        done = self.ECAPA_TDNN.load_blob(p_ecapa), self._raw.load_blob(p_raw)
-        for branch, (missing, _) in zip(("ECAPA_TDNN", self.RAW_ATTR), done):
+        done = self._first.load_blob(p_ecapa), self._raw.load_blob(p_raw)
+        for branch, (missing, _) in zip((self.FIRST_ATTR, self.RAW_ATTR), done):
             if missing:
                 raise _lib.SvhipError(_lib.ERR_MISSING, f"{self.MODEL_NAME}: the {branch} blob lacks {missing[:4]} ({len(missing)} tensors)")
         return done
@@ -108,7 +125,7 @@ class RawECAPAFusion:
         if _is_torch(x) and x.is_cuda and x.ndim == 2 and self._raw.accepts_length(x.shape[1]):
             # device-resident batch: the two branches run CONCURRENTLY, each on its handle's own stream (RawNet2's small late
             # kernels beside ECAPA's GEMMs: 61 k instead of 55 k utt/s at B = 256)
-            e1 = self.ECAPA_TDNN._get_engine(x.shape[1], batch=x.shape[0])
+            e1 = self._first._get_engine(x.shape[1], batch=x.shape[0])
             e2 = self._raw._engine_for(x)
             if x.shape[0] <= min(e1.max_batch, e2.max_batch) and x.dtype == torch.float32 and x.is_contiguous():
                 torch.cuda.current_stream(x.device).synchronize()          # x is complete before either handle reads it
@@ -122,8 +139,8 @@ class RawECAPAFusion:
                 out[:, :e1.embed_dim] = o1                                 # torch.cat([out1, out2], dim=-1)   :50
                 out[:, e1.embed_dim:] = o2
                 return out.squeeze()
-        out1 = self.ECAPA_TDNN.embed_wave(x)          # compute_features + ECAPA_TDNN (Raw_ECAPA_sinc_asp.py:41-44)
-        out2 = self._raw(x)                           # :48
+        out1 = self._first.embed_wave(x)              # compute_features + ECAPA_TDNN (Raw_ECAPA_sinc_asp.py:41-44)
+        out2 = self._raw_forward(x)                   # :48
         if _is_torch(out1):
             return torch.cat([out1, out2], dim=-1)    # :50
         return np.concatenate([out1, out2], axis=-1)

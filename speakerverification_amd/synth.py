@@ -9,6 +9,7 @@ source of truth for the *names and shapes* of the reference state dicts
                   (``aggregate='asp'``: 147 tensors with ``front_proc='sinc'``, 140 with ``'conv'``),
   * RawNet3     — reference ``src/models/RawNet3.py`` + ``RawNet_baseline.py`` (the defaults of its
                   ``MainModel``: 234 tensors),
+  * TitaNet     — reference ``src/models/TitaNet.py`` + ``blocks/titanet_blocks.py`` (sizes s / m / l, any block count),
 
 and generates values from a ``numpy`` PCG64 stream in state-dict order, so the CPU oracle and the
 HIP path see bit-identical weights on any machine.  ``tests/test_oracle_golden.py`` checks the
@@ -156,6 +157,67 @@ def rawnet3_param_spec(nOut=512):
     return spec
 
 
+TITANET_SIZES = {"s": (256, 3), "m": (512, 7), "l": (1024, 11)}      # hidden size H, depthwise kernel (TitaNet.py:152-157)
+TITANET_TARGET_PARAMS = {"s": 6.4, "m": 13.4, "l": 25.3}             # TitaNet.TARGET_PARAMS (millions)
+TITANET_ENC = 1536                                                   # encoder_output_size (TitaNet.py:145)
+TITANET_ATT = 128                                                    # attention_hidden_size
+TITANET_SE_REDUCTION = 16
+
+
+def titanet_n_params(size, nOut, n_blocks, n_mels=80):
+    """trainable parameters of ``TitaNet.get_titanet(nOut, n_mels, n_blocks, size)`` (get_n_params: BatchNorm running statistics are
+    buffers, not parameters), in closed form"""
+    H, k = TITANET_SIZES[size]
+    D, A = TITANET_ENC, TITANET_ATT
+    prolog = H * n_mels * 3 + H + 2 * H
+    block = 3 * (H * k + H + H * H + H + 2 * H) + 2 * H * (H // TITANET_SE_REDUCTION) + H * H + H + 2 * H
+    epilog = D * H + D + 2 * D
+    decoder = D * A + A + A * D + D + 2 * 2 * D + 2 * D * nOut + nOut + 2 * nOut
+    return prolog + n_blocks * block + epilog + decoder
+
+
+def titanet_n_mega_blocks(size, nOut, n_mels=80):
+    """``TitaNet.find_n_mega_blocks`` (TitaNet.py:82-109): the count in 1 .. 19 whose parameter total (in millions) is closest to
+    TARGET_PARAMS[size], the first one on a tie"""
+    target = TITANET_TARGET_PARAMS[size]
+    best, dist = None, math.inf
+    for n in range(1, 20):
+        d = abs(target - titanet_n_params(size, nOut, n, n_mels) / 1e6)
+        if d < dist:
+            best, dist = n, d
+    return best
+
+
+def titanet_param_spec(size="l", nOut=512, n_blocks=None, n_mels=80):
+    """Ordered (name, shape) list == ``TitaNet.MainModel(nOut, model_size=size, n_mega_blocks=n_blocks).state_dict()`` of the reference
+    (TitaNet.py:202-431, blocks/titanet_blocks.py); n_blocks None: find_n_mega_blocks' choice"""
+    H, k = TITANET_SIZES[size]
+    D = TITANET_ENC
+    if n_blocks is None:
+        n_blocks = titanet_n_mega_blocks(size, nOut, n_mels)
+    spec = [("encoder.prolog.conv_block.0.weight", (H, n_mels, 3)), ("encoder.prolog.conv_block.0.bias", (H,))]
+    spec += _bn("encoder.prolog.conv_block.1", H)
+    for i in range(n_blocks):
+        p = f"encoder.mega_blocks.{i}."
+        for j in range(3):
+            q = p + f"sub_blocks.{j}.conv_block."
+            spec += [(q + "0.conv.0.weight", (H, 1, k)), (q + "0.conv.0.bias", (H,)),
+                     (q + "0.conv.1.weight", (H, H, 1)), (q + "0.conv.1.bias", (H,))]
+            spec += _bn(q + "1", H)
+        Hh = H // TITANET_SE_REDUCTION
+        spec += [(p + "sub_blocks.3.excitation.0.weight", (Hh, H)), (p + "sub_blocks.3.excitation.2.weight", (H, Hh)),
+                 (p + "skip_connection.0.weight", (H, H, 1)), (p + "skip_connection.0.bias", (H,))]
+        spec += _bn(p + "skip_connection.1", H)
+    spec += [("encoder.epilog.conv_block.0.weight", (D, H, 1)), ("encoder.epilog.conv_block.0.bias", (D,))]
+    spec += _bn("encoder.epilog.conv_block.1", D)
+    spec += [("decoder.pool.0.in_linear.weight", (TITANET_ATT, D)), ("decoder.pool.0.in_linear.bias", (TITANET_ATT,)),
+             ("decoder.pool.0.out_linear.weight", (D, TITANET_ATT)), ("decoder.pool.0.out_linear.bias", (D,))]
+    spec += _bn("decoder.pool.1", 2 * D)
+    spec += [("decoder.linear.0.weight", (nOut, 2 * D)), ("decoder.linear.0.bias", (nOut,))]
+    spec += _bn("decoder.linear.1", nOut)
+    return spec
+
+
 def rawnet3_sinc_buffers():
     """the persistent buffers of ParamSincFB(256, 251) at sample_rate 16000: window_ (125,), n_ (1, 125)"""
     n_lin = np.linspace(0.0, 251 / 2 - 1, RAWNET3_SINC_HALF)
@@ -237,6 +299,13 @@ def synth_state_dict(spec, seed=1):
             # (fp32 vs fp64 oracle).  Gain 0.7 keeps outputs at the O(20) the reference shows with its
             # default init and the fp32 noise floor at ~1e-5, so that a 1e-4 parity bar means something.
             if name.startswith("layer") and (".conv" in name or "shortcut" in name):
+                std *= 0.7
+            # TitaNet's mega-blocks add the BN'd skip to the gated sub-block path without a normalisation after the sum: with full He
+            # gain the block outputs grow ~2x per block (TitaNet-S: 1e7 after 18 blocks).  Gains 0.5 (skip) and 0.7 (pointwise convs)
+            # keep every block output O(1) for s / m / l.
+            if "mega_blocks." in name and ".skip_connection.0." in name:
+                std *= 0.5
+            elif "mega_blocks." in name and ".conv.1." in name:
                 std *= 0.7
             sd[name] = (std * rng.standard_normal(shape)).astype(np.float32)
         else:  # pragma: no cover
