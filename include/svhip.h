@@ -73,8 +73,20 @@ typedef enum svhip_status {
  * the block count from the indices loaded contiguously from 0 (a gap or a missing tensor of a present block: SVHIP_ERR_MISSING; a depthwise
  * weight whose kernel size is not H's: SVHIP_ERR_INVALID).  Both svhip_embed_wave (mel front-end, then the net) and svhip_embed_features. */
 #define SVHIP_TITANET_MAX_BLOCKS 32
+/* SVHIP_MODEL_CONFORMER (added under ABI v5): Conformer.MainModel (models/Conformer.py with models/conformer/conformer/*), the model of
+ * yaml/model_plot.yaml: on the mel power, log(x + 1e-6) - mean_t (log_input = 1 for features='melspectrogram', else 0) and
+ * InstanceNorm1d(n_mels, affine) (input_norm must be 1); Conv2dSubampling (two Conv2d(3 x 3, stride 2) + ReLU, 256 channels) and
+ * Linear(256 F2, 256); six Conformer blocks (d_model 256, 4 heads, FF x 4, depthwise kernel 15; eval: dropouts are identities); attentive
+ * statistics pooling with the variance clamped to [1e-4, 1e4], attention_norm, fc = Conv1d(512, nOut, 1).  Multi-head attention uses
+ * Transformer-XL relative positions, and the reference's _relative_shift (cat / view, attention.py:110-118) is reproduced exactly:
+ * key j of query i takes the positional score of query row i + 1 when j >= i + 2, zero when j == i + 1.
+ * channels 0 or 256; embed_dim = nOut; n_mels >= 7 (a multiple of 8, as for every model); compute SVHIP_F32 or SVHIP_BF16 (others:
+ * SVHIP_ERR_UNSUPPORTED).  Length: T = L / hop + 1 >= 7 frames (T' = ((T - 3) / 2 + 1 - 3) / 2 + 1 >= 1) and T' <= 10000, the length of the
+ * positional-encoding buffer (svhip_create refuses longer inputs); L >= n_fft as for every model.  Weights: the 278 reference state-dict
+ * names, positional_encoding.pe (1, 10000, 256) of every layer included; asp.* / asp_bn.* are required and ignored (the reference never
+ * calls them).  Both svhip_embed_wave and svhip_embed_features. */
 enum { SVHIP_MODEL_ECAPA = 0, SVHIP_MODEL_RAWNET2 = 1, SVHIP_MODEL_NONE = 2 /* fbank + scoring only */, SVHIP_MODEL_RAWNET2_CONV = 3,
-       SVHIP_MODEL_RAWNET3 = 4, SVHIP_MODEL_RAWNET2_GRU = 5, SVHIP_MODEL_TITANET = 6 };
+       SVHIP_MODEL_RAWNET3 = 4, SVHIP_MODEL_RAWNET2_GRU = 5, SVHIP_MODEL_TITANET = 6, SVHIP_MODEL_CONFORMER = 7 };
 enum { SVHIP_F32 = 0, SVHIP_BF16 = 1, SVHIP_I64 = 2, SVHIP_F32X3 = 3 /* compute only */, SVHIP_F16 = 4 /* compute only */ };
 enum { SVHIP_IN_DEVICE = 1, SVHIP_OUT_DEVICE = 2, SVHIP_ASYNC = 4 };
 
@@ -291,7 +303,9 @@ int svhip_synth_waveforms(svhip_handle* h, uint64_t seed, int64_t first_utt, int
  *                  (B, T, C).  Names: "input","blocks.0".."blocks.3","mfa","asp","asp_bn" (ECAPA); "rn_gru_in" (the (B T, 512) GRU
  *                  input of a one-slice forward) and "rn_gru_h" (the (B, 1024) fp32 last GRU state) of SVHIP_MODEL_RAWNET2_GRU;
  *                  "tn_prolog" (B T, H), "tn_dw0" (block 0's first depthwise output, its bias included), "tn_mega_last" (the last
- *                  mega-block's output), "tn_enc" (B T, 1536) and "tn_pool" (B, 3072, after BN) of SVHIP_MODEL_TITANET.
+ *                  mega-block's output), "tn_enc" (B T, 1536) and "tn_pool" (B, 3072, after BN) of SVHIP_MODEL_TITANET;
+ *                  "cf_in" (B T', 256: the input projection), "cf_block0", "cf_attn0" (block 0's per-head attention context before
+ *                  out_proj), "cf_last" (the last block's output) and "cf_pool" (B, 512, after attention_norm) of SVHIP_MODEL_CONFORMER.
  *                  Returns the element count through *count (out may be NULL to query).
  *   profile_*    : when enabled every kernel launch is bracketed by HIP events on the handle's
  *                  stream; profile_get returns accumulated milliseconds / launch count per kernel
@@ -313,6 +327,12 @@ int svhip_set_option(svhip_handle* h, const char* name, int32_t value);
 /* Free the scoring / metrics scratch slots of the handle (grown on demand, otherwise kept until svhip_destroy). */
 int svhip_trim_scratch(svhip_handle* h);
 int svhip_selftest(void);   /* host-only self checks (per-device launch-attribute bookkeeping); 0 = ok, no GPU needed */
+/* Conformer's relative-position attention kernel on its own (tests): device pointers, enqueued on `stream` (NULL: the null stream),
+ * not synchronised.  qkv (B T', 768) in the compute type (SVHIP_F32 / SVHIP_BF16) holds q | k | v; P (T', 256) fp32; u_bias, v_bias
+ * [4][64] fp32; ctx (B T', 256) in the compute type receives the four heads' contexts.  1 <= T' <= 10000.  SVHIP_OK,
+ * SVHIP_ERR_INVALID (arguments) or SVHIP_ERR_HIP (launch). */
+int svhip_conformer_attention(const void* qkv, const float* P, const float* u_bias, const float* v_bias, void* ctx, int32_t compute,
+                              int32_t B, int32_t T_sub, void* stream);
 
 #ifdef __cplusplus
 }

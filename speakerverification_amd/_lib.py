@@ -20,6 +20,7 @@ MODEL_RAWNET2_CONV = 3                     # RawNet2 with front_proc='conv' (inc
 MODEL_RAWNET3 = 4                          # RawNet3, the raw-waveform branch of Raw3_ECAPA (include/svhip.h, added under ABI v5)
 MODEL_RAWNET2_GRU = 5                      # RawNet2 with front_proc='sinc', aggregate='gru' (include/svhip.h, added under ABI v5)
 MODEL_TITANET = 6                          # TitaNet, the spectral branch of Tita_ECAPA / Raw_tita (include/svhip.h, added under ABI v5)
+MODEL_CONFORMER = 7                        # Conformer, the model of yaml/model_plot.yaml (include/svhip.h, added under ABI v5)
 F32, BF16, I64, F32X3, F16 = 0, 1, 2, 3, 4
 IN_DEVICE, OUT_DEVICE, ASYNC = 1, 2, 4
 TRIAL_COSINE, TRIAL_PNORM, TRIAL_PDIST = 0, 1, 2
@@ -109,6 +110,7 @@ _SIGNATURES = {
     "svhip_set_option": (C.c_int, [_P, C.c_char_p, C.c_int32]),
     "svhip_trim_scratch": (C.c_int, [_P]),
     "svhip_selftest": (C.c_int, []),
+    "svhip_conformer_attention": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
 }
 
 _lib = None

@@ -193,7 +193,7 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
     if (e != hipSuccess || ndev <= 0) { g_create_error = std::string("no HIP device: ") + hipGetErrorString(e); return SVHIP_ERR_HIP; }
     if (cfg->device < 0 || cfg->device >= ndev) { g_create_error = "device ordinal out of range"; return SVHIP_ERR_INVALID; }
     if (cfg->model != SVHIP_MODEL_ECAPA && !is_rawnet2(cfg->model) && cfg->model != SVHIP_MODEL_RAWNET3 && cfg->model != SVHIP_MODEL_TITANET &&
-        cfg->model != SVHIP_MODEL_NONE) {
+        cfg->model != SVHIP_MODEL_CONFORMER && cfg->model != SVHIP_MODEL_NONE) {
         g_create_error = "unknown model";
         return SVHIP_ERR_INVALID;
     }
@@ -210,6 +210,21 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
         if (!tn_kernel_size(cfg->channels)) { g_create_error = "TitaNet is built for H = 256 / 512 / 1024 (sizes s / m / l: channels)"; return SVHIP_ERR_INVALID; }
         if (cfg->log_input || cfg->input_norm) { g_create_error = "TitaNet reads the mel power as it is: log_input and input_norm must be 0"; return SVHIP_ERR_INVALID; }
         if (cfg->embed_dim <= 0) { g_create_error = "TitaNet needs embed_dim > 0"; return SVHIP_ERR_INVALID; }
+    }
+    if (cfg->model == SVHIP_MODEL_CONFORMER) {
+        if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16) { g_create_error = "Conformer runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_UNSUPPORTED; }
+        if (cfg->channels != 0 && cfg->channels != CF_D) { g_create_error = "Conformer is built for d_model = 256 (channels 0 or 256)"; return SVHIP_ERR_INVALID; }
+        if (!cfg->input_norm) { g_create_error = "Conformer always applies its InstanceNorm1d: input_norm must be 1"; return SVHIP_ERR_INVALID; }
+        if (cfg->embed_dim <= 0) { g_create_error = "Conformer needs embed_dim > 0"; return SVHIP_ERR_INVALID; }
+        if (cfg->n_mels < 7) { g_create_error = "Conformer needs n_mels >= 7 (two 3 x 3 stride-2 convolutions)"; return SVHIP_ERR_INVALID; }
+        if (cfg->hop_length > 0) {
+            const int T = cfg->samples / cfg->hop_length + 1;
+            if (T < 7) { g_create_error = "Conformer needs at least 7 frames (T' = ((T - 3) / 2 + 1 - 3) / 2 + 1 >= 1)"; return SVHIP_ERR_INVALID; }
+            if (cf_sub(cf_sub(T)) > CF_MAX_T) {
+                g_create_error = "Conformer's positional encoding holds 10000 positions: T' = ((T - 3) / 2 + 1 - 3) / 2 + 1 must be <= 10000";
+                return SVHIP_ERR_INVALID;
+            }
+        }
     }
     if (cfg->model == SVHIP_MODEL_ECAPA && (cfg->channels <= 0 || cfg->channels % 64 != 0)) { g_create_error = "ECAPA channels must be a positive multiple of 64"; return SVHIP_ERR_INVALID; }
     if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16 && cfg->compute != SVHIP_F32X3 && cfg->compute != SVHIP_F16) { g_create_error = "unknown compute mode"; return SVHIP_ERR_INVALID; }
@@ -340,6 +355,7 @@ int svhip_finalize_weights(svhip_handle* h) {
     else if (is_rawnet2(h->cfg.model)) rc = finalize_rawnet2(h);
     else if (h->cfg.model == SVHIP_MODEL_RAWNET3) rc = finalize_rawnet3(h);
     else if (h->cfg.model == SVHIP_MODEL_TITANET) rc = finalize_titanet(h);
+    else if (h->cfg.model == SVHIP_MODEL_CONFORMER) rc = finalize_conformer(h);
     else SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
     if (rc) return rc;
     SV_HIP(h, hipDeviceSynchronize());
@@ -396,8 +412,8 @@ int svhip_embed_features(svhip_handle* h, const float* feat, int32_t B, int32_t 
     int rc = check_ready(h, B);
     if (rc) return rc;
     if (!feat || !emb_out) SV_FAIL(h, SVHIP_ERR_INVALID, "null pointer");
-    if (h->cfg.model != SVHIP_MODEL_ECAPA && h->cfg.model != SVHIP_MODEL_TITANET)
-        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "embed_features needs a spectral model (ECAPA, TitaNet)");
+    if (h->cfg.model != SVHIP_MODEL_ECAPA && h->cfg.model != SVHIP_MODEL_TITANET && h->cfg.model != SVHIP_MODEL_CONFORMER)
+        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "embed_features needs a spectral model (ECAPA, TitaNet, Conformer)");
     if (T != h->T) SV_FAIL(h, SVHIP_ERR_INVALID, "T=%d but the handle was created for T=%d frames", T, h->T);
     if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
         SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
@@ -408,7 +424,8 @@ int svhip_embed_features(svhip_handle* h, const float* feat, int32_t B, int32_t 
         d_in = h->d_feat;
     }
     h->feat_is_stale = false;
-    if ((rc = h->cfg.model == SVHIP_MODEL_TITANET ? titanet_forward(h, d_in, B) : ecapa_forward(h, d_in, B))) return rc;
+    if ((rc = h->cfg.model == SVHIP_MODEL_TITANET ? titanet_forward(h, d_in, B)
+            : h->cfg.model == SVHIP_MODEL_CONFORMER ? conformer_forward(h, d_in, B) : ecapa_forward(h, d_in, B))) return rc;
     if ((rc = emit_embeddings(h, B, emb_out, flags))) return rc;
     return finish(h, flags);
 }
@@ -420,7 +437,8 @@ int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, fl
     if (L != h->cfg.samples) SV_FAIL(h, SVHIP_ERR_INVALID, "L=%d but the handle was created for %d samples", L, h->cfg.samples);
     if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
         SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
-    if (h->cfg.model != SVHIP_MODEL_ECAPA && !is_rawnet2(h->cfg.model) && h->cfg.model != SVHIP_MODEL_RAWNET3 && h->cfg.model != SVHIP_MODEL_TITANET)
+    if (h->cfg.model != SVHIP_MODEL_ECAPA && !is_rawnet2(h->cfg.model) && h->cfg.model != SVHIP_MODEL_RAWNET3 && h->cfg.model != SVHIP_MODEL_TITANET &&
+        h->cfg.model != SVHIP_MODEL_CONFORMER)
         SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
     SV_HIP(h, hipSetDevice(h->cfg.device));
     const float* d_in = wav;
@@ -432,10 +450,10 @@ int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, fl
         if ((rc = rawnet2_forward(h, d_in, B))) return rc;
     } else if (h->cfg.model == SVHIP_MODEL_RAWNET3) {
         if ((rc = rawnet3_forward(h, d_in, B))) return rc;
-    } else if (h->cfg.model == SVHIP_MODEL_TITANET) {        // the mel power in fp32, then the net (its prologue casts to bf16 on bf16 handles)
+    } else if (h->cfg.model == SVHIP_MODEL_TITANET || h->cfg.model == SVHIP_MODEL_CONFORMER) {   // the mel power in fp32, then the net
         if ((rc = run(h, "fbank", 0, [&]() { return launch_fbank(h->fb, d_in, B, L, h->T, h->d_feat, h->stream); }))) return rc;
         h->feat_is_stale = false;
-        if ((rc = titanet_forward(h, h->d_feat, B))) return rc;
+        if ((rc = h->cfg.model == SVHIP_MODEL_TITANET ? titanet_forward(h, h->d_feat, B) : conformer_forward(h, h->d_feat, B))) return rc;
     } else {
         const int T = h->T;
         // bf16 handles without the instance-norm prologue: waveform -> the 16-bit operand of blocks.0 in two launches (fbank.hip, round 6)
@@ -588,6 +606,15 @@ int svhip_get_stage(svhip_handle* h, const char* name, float* out, int64_t* coun
         else if (n == "tn_dw0") { src = h->tn_buf[2]; cols = ld = H; }
         else if (n == "tn_enc") { src = h->tn_enc; cols = ld = 1536; }
         else if (n == "tn_pool") { src = h->tn_pool; rows = B; cols = ld = 3072; f32 = true; }
+        else SV_FAIL(h, SVHIP_ERR_INVALID, "unknown stage %s", name);
+    }
+    else if (n.rfind("cf_", 0) == 0 && h->cfg.model == SVHIP_MODEL_CONFORMER) {  // Conformer: cf_in, cf_block0, cf_attn0, cf_last, cf_pool
+        rows = (size_t)B * h->cf_Tp; cols = ld = CF_D;
+        if (n == "cf_in") src = h->cf_in;
+        else if (n == "cf_block0") src = h->cf_b0;
+        else if (n == "cf_attn0") src = h->cf_attn0;
+        else if (n == "cf_last") src = h->cf_last;
+        else if (n == "cf_pool") { src = h->cf_pool; rows = B; cols = ld = 2 * CF_D; f32 = true; }
         else SV_FAIL(h, SVHIP_ERR_INVALID, "unknown stage %s", name);
     }
     else if (n == "mel") {

@@ -213,7 +213,7 @@ static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, 
         p.out_f32 = 1;
         if ((rc = conv_gemm(h, h->asp_conv, p))) return rc;
         if ((rc = run(h, "asp_pool", 0, [&]() {
-                 return launch_asp_pool(LOGITS, MFA, bf, C3, B, T, C3, h->aspbn_scale, h->aspbn_shift, d_pool_raw, d_pool_bn, 1e-12f, st);
+                 return launch_asp_pool(LOGITS, MFA, bf, C3, B, T, C3, h->aspbn_scale, h->aspbn_shift, d_pool_raw, d_pool_bn, 1e-12f, 0.0f, st);
              }))) return rc;
     }
     if ((rc = run(h, "fc", 2.0 * B * h->fc.N * h->fc.K, [&]() {

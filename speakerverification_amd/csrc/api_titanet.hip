@@ -80,7 +80,7 @@ static int titanet_forward_part(svhip_handle* h, const float* d_feat, int b0, in
     pl.out_f32 = 1;
     if ((rc = conv_gemm(h, h->tn_att_out, pl))) return rc;
     if ((rc = run(h, "tn_asp_pool", 0, [&]() {
-             return launch_asp_pool(h->tn_logits, h->tn_enc, bf, E, B, T, E, h->tn_pbn_scale, h->tn_pbn_shift, h->tn_pool_raw, h->tn_pool, 1e-6f, st);
+             return launch_asp_pool(h->tn_logits, h->tn_enc, bf, E, B, T, E, h->tn_pbn_scale, h->tn_pbn_shift, h->tn_pool_raw, h->tn_pool, 1e-6f, 0.0f, st);
          }))) return rc;
     // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the ReLU epilogues would have dropped it)
     if ((rc = run(h, "tn_in_check", 0, [&]() {

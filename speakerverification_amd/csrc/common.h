@@ -22,7 +22,8 @@ constexpr int WAVE = 64;
 // storage / MFMA operand type of a launch: the launchers' `dt` argument (a plain `bool bf16` converts to DT_F32 / DT_BF16)
 enum DType : int { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2 };
 
-enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_TANH = 3, ACT_SIGMOID = 4, ACT_LRELU03 = 5, ACT_LRELU001 = 6 };
+enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_TANH = 3, ACT_SIGMOID = 4, ACT_LRELU03 = 5, ACT_LRELU001 = 6,
+                 ACT_SWISH = 7 /* x * sigmoid(x): Conformer's feed-forward modules */ };
 enum Pad : int { PAD_REFLECT = 0, PAD_ZERO = 1 };
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return static_cast<float>(v); }
@@ -45,6 +46,7 @@ __device__ __forceinline__ float apply_act(float x, int act) {
         case ACT_SIGMOID: return 1.0f / (1.0f + expf(-x));
         case ACT_LRELU03: return x > 0.0f ? x : 0.3f * x;
         case ACT_LRELU001: return x > 0.0f ? x : 0.01f * x;
+        case ACT_SWISH: return x / (1.0f + expf(-x));
         default: return x;
     }
 }

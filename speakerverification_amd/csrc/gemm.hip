@@ -87,7 +87,7 @@ template <> struct MmaTraits<f16_t> {         // SVHIP_F16 handles (RawNet2)
 // activation pairs used by the models, fixed at compile time (a runtime switch inlined 128 times
 // made the epilogue 30k instructions long and blew the instruction cache)
 enum Epi : int { EPI_NONE = 0, EPI_RELU = 1, EPI_GELU = 2, EPI_RELU_TANH = 3, EPI_LRELU03 = 4, EPI_BN_LRELU03 = 5, EPI_LRELU001 = 6,
-                 EPI_TANH = 7 /* act1 none, act2 tanh: TitaNet's attention in_linear */ };
+                 EPI_TANH = 7 /* act1 none, act2 tanh: TitaNet's attention in_linear */, EPI_SWISH = 8 /* Conformer's FF1 */ };
 
 // erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7) on the fast exp / rcp units: bf16 path only
 __device__ __forceinline__ float gelu_fast(float x) {
@@ -110,6 +110,7 @@ __device__ __forceinline__ float epilogue_act1(float v) {
     if (EPI == EPI_GELU) return sizeof(T) == 2 ? gelu_fast(v) : 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
     if (EPI == EPI_LRELU03) return v > 0.0f ? v : 0.3f * v;
     if (EPI == EPI_LRELU001) return v > 0.0f ? v : 0.01f * v;
+    if (EPI == EPI_SWISH) return v / (1.0f + expf(-v));
     return v;
 }
 
@@ -129,7 +130,7 @@ __device__ __forceinline__ void split_hi_lo(const f32x4& a, const f32x4& b, bf16
 }
 
 // X3 (T = float only, SVHIP_F32X3 handles): every product as three bf16 MFMAs on hi / lo-split fragments (see gemm_pw.hip)
-template <typename T, bool CONV, bool HAS_A2, int EPI, bool X3 = false>
+template <typename T, bool CONV, bool HAS_A2, int EPI, bool X3 = false, bool SEG = false>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
     typedef MmaTraits<T> TR;
     typedef typename TR::chunk_t chunk_t;
@@ -176,6 +177,14 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
             tA[i] = m - b * p.T;
         }
     }
+    int64_t segbase[4];  // SEG: the row's offset in A
+    if (SEG) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int u = rowA[i] / p.seg_rows;
+            segbase[i] = (int64_t)u * p.seg_utt + p.seg_off[rowA[i] - u * p.seg_rows];
+        }
+    }
     int64_t wrow[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) wrow[i] = (int64_t)min(n0 + lr + 32 * i, p.Wrows - 1) * p.Kp;
@@ -186,6 +195,11 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
         const int k = kt * BK + lc * EPC;
         const bool kvalid = k < p.K;
         int tap_off = 0, cc = k;
+        int64_t seg_k = 0;
+        if (SEG) {
+            const int s = k / p.seg_len;
+            seg_k = (int64_t)s * p.seg_stride + (k - s * p.seg_len);
+        }
         if (CONV) {
             const int tap = k / p.cin;
             cc = k - tap * p.cin;
@@ -195,7 +209,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
         for (int i = 0; i < 4; ++i) {
             chunk_t v = TR::zero();
             if (kvalid) {
-                if (CONV) {
+                if (SEG) {
+                    v = *reinterpret_cast<const chunk_t*>(Ap + segbase[i] + seg_k);
+                } else if (CONV) {
                     int tt = tA[i] + tap_off;
                     bool ok = true;
                     if (p.pad_mode == PAD_REFLECT) tt = reflect_idx(tt, p.T);
@@ -316,14 +332,14 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
     }
 }
 
-template <typename T, bool CONV, bool HAS_A2, int EPI, bool X3>
+template <typename T, bool CONV, bool HAS_A2, int EPI, bool X3, bool SEG = false>
 hipError_t launch_inst_x(const GemmParams& p, hipStream_t stream) {
     const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
     dim3 grid(ntm * ntn), block(256);
     const size_t lds = 4 * TILE_BYTES;
     static DeviceOnce attr;         // 64 KiB of dynamic LDS per workgroup, raised once per device
-    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(gemm_kernel<T, CONV, HAS_A2, EPI, X3>), (int)lds)) return e;
-    hipLaunchKernelGGL((gemm_kernel<T, CONV, HAS_A2, EPI, X3>), grid, block, lds, stream, p);
+    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(gemm_kernel<T, CONV, HAS_A2, EPI, X3, SEG>), (int)lds)) return e;
+    hipLaunchKernelGGL((gemm_kernel<T, CONV, HAS_A2, EPI, X3, SEG>), grid, block, lds, stream, p);
     return hipGetLastError();
 }
 
@@ -345,12 +361,20 @@ hipError_t launch_epi(const GemmParams& p, hipStream_t stream) {
 
 template <typename T>
 hipError_t launch_t(const GemmParams& p, hipStream_t stream) {
+    if (p.seg_off) {          // the segmented row gather: Conformer's subsampling conv (bias + ReLU), fp32 / bf16 only
+        if constexpr (std::is_same<T, f16_t>::value) return hipErrorInvalidValue;
+        else {
+            if (p.act1 != ACT_RELU || p.act2 != ACT_NONE || p.taps != 1 || p.A2 || p.x3) return hipErrorInvalidValue;
+            return launch_inst_x<T, false, false, EPI_RELU, false, true>(p, stream);
+        }
+    }
     if (p.act1 == ACT_NONE && p.act2 == ACT_NONE) return launch_epi<T, EPI_NONE>(p, stream);
     if constexpr (!std::is_same<T, f16_t>::value) {      // (fp16: RawNet2's epilogues only)
     if (p.act1 == ACT_RELU && p.act2 == ACT_NONE) return launch_epi<T, EPI_RELU>(p, stream);
     if (p.act1 == ACT_GELU && p.act2 == ACT_NONE) return launch_epi<T, EPI_GELU>(p, stream);
     if (p.act1 == ACT_RELU && p.act2 == ACT_TANH) return launch_epi<T, EPI_RELU_TANH>(p, stream);
     if (p.act1 == ACT_NONE && p.act2 == ACT_TANH) return launch_epi<T, EPI_TANH>(p, stream);
+    if (p.act1 == ACT_SWISH && p.act2 == ACT_NONE) return launch_epi<T, EPI_SWISH>(p, stream);
     }
     if (p.act1 == ACT_LRELU03 && p.act2 == ACT_NONE) return launch_epi<T, EPI_LRELU03>(p, stream);
     if (p.act1 == ACT_NONE && p.act2 == ACT_LRELU03) return launch_epi<T, EPI_BN_LRELU03>(p, stream);
@@ -368,6 +392,7 @@ GemmRoute gemm_route(const GemmParams& p, bool bf16) {
 #else
     const bool skip_pw2 = false, no_narrow = false, no_pw3 = false;
 #endif
+    if (p.seg_off) return ROUTE_GENERIC;          // (only the generic kernel gathers segmented rows)
     const bool pw = gemm_pw_supported(p, bf16);
     if (bf16 && p.taps > 1 && !p.cv_off && gemm_pw3cv16_supported(p)) return ROUTE_PW3CV;
     if (bf16 && !p.n128_off && gemm_n128_supported(p)) return ROUTE_N128;
@@ -398,6 +423,8 @@ hipError_t launch_gemm(const GemmParams& p, bool bf16, hipStream_t stream) {
         return hipErrorInvalidValue;
     }
     if (p.bias_utt && (p.T <= 0)) return hipErrorInvalidValue;
+    if (p.seg_off && (p.seg_rows <= 0 || p.seg_len <= 0 || p.seg_len % epc != 0 || p.K % p.seg_len != 0 || p.seg_utt % epc != 0 ||
+                      p.seg_stride % epc != 0)) return hipErrorInvalidValue;
     if (p.A3 && gemm_route(p, bf16) != ROUTE_PW2) return hipErrorInvalidValue;       // (only the 256 x 256 kernel reads a second K segment)
     switch (gemm_route(p, bf16)) {
         case ROUTE_PW2: return launch_gemm_pw2(p, stream);

@@ -53,7 +53,7 @@ template <int BN> struct TileCfg {
 };
 
 enum Epi : int { EPI_NONE = 0, EPI_RELU = 1, EPI_GELU = 2, EPI_RELU_TANH = 3, EPI_LRELU03 = 4, EPI_BN_LRELU03 = 5, EPI_LRELU001 = 6,
-                 EPI_TANH = 7 /* act1 none, act2 tanh: TitaNet's attention in_linear */ };
+                 EPI_TANH = 7 /* act1 none, act2 tanh: TitaNet's attention in_linear */, EPI_SWISH = 8 /* Conformer's FF1 */ };
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * ROWB + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
@@ -75,6 +75,7 @@ __device__ __forceinline__ float act1(float v) {
     if (EPI == EPI_GELU) return sizeof(T) == 2 ? gelu_fast(v) : 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
     if (EPI == EPI_LRELU03) return v > 0.0f ? v : 0.3f * v;
     if (EPI == EPI_LRELU001) return v > 0.0f ? v : 0.01f * v;
+    if (EPI == EPI_SWISH) return v / (1.0f + expf(-v));
     return v;
 }
 
@@ -415,6 +416,7 @@ hipError_t launch_epi(const GemmParams& p, hipStream_t stream) {
     if (p.act1 == ACT_GELU && p.act2 == ACT_NONE) return launch_inst<T, EPI_GELU, OUT_F32, BN>(p, stream);
     if (p.act1 == ACT_RELU && p.act2 == ACT_TANH) return launch_inst<T, EPI_RELU_TANH, OUT_F32, BN>(p, stream);
     if (p.act1 == ACT_NONE && p.act2 == ACT_TANH) return launch_inst<T, EPI_TANH, OUT_F32, BN>(p, stream);
+    if (p.act1 == ACT_SWISH && p.act2 == ACT_NONE) return launch_inst<T, EPI_SWISH, OUT_F32, BN>(p, stream);
     }
     if (p.act1 == ACT_LRELU03 && p.act2 == ACT_NONE) return launch_inst<T, EPI_LRELU03, OUT_F32, BN>(p, stream);
     if (p.act1 == ACT_NONE && p.act2 == ACT_LRELU03) return launch_inst<T, EPI_BN_LRELU03, OUT_F32, BN>(p, stream);

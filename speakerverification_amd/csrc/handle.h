@@ -198,6 +198,40 @@ struct svhip_handle {
     float *tn_mean = nullptr, *tn_gate = nullptr;                  // (Bmax, H) SE squeeze, SE gate
     float *tn_pool_raw = nullptr, *tn_pool = nullptr;              // (Bmax, 3072) pooled [mean | std], after BN
 
+    // Conformer layers (SVHIP_MODEL_CONFORMER: models/Conformer.py, models/conformer/conformer/*).  d_model 256, 4 heads of 64, six blocks
+    struct CfBlock {
+        float *ff_g[2] = {}, *ff_b[2] = {};   // the two feed-forward modules' LayerNorms (FF, FF')
+        svhip::ConvLayer ff1[2], ff2[2];      // Linear(256, 1024) (Swish in the epilogue), Linear(1024, 256)
+        float *att_g = nullptr, *att_b = nullptr;
+        svhip::ConvLayer qkv, out;            // query | key | value projections as one 256 -> 768 layer; out_proj
+        float* P = nullptr;                   // (T', 256) fp32: pe[:T'] pos_proj^T (the same for every utterance: formed at finalize)
+        float *u = nullptr, *v = nullptr;     // u_bias, v_bias [4][64]
+        float *cv_g = nullptr, *cv_b = nullptr;
+        svhip::ConvLayer pw1, pw2;            // pointwise 256 -> 512 (GLU follows), 256 -> 256
+        float *dw_w = nullptr, *dw_b = nullptr;   // depthwise k = 15, tap-major [15][256], with BatchNorm(256) folded in
+        float *fin_g = nullptr, *fin_b = nullptr; // the block's final LayerNorm
+    };
+    std::vector<CfBlock> cf;
+    int cf_T1 = 0, cf_F1 = 0, cf_Tp = 0, cf_F2 = 0;   // conv1 / conv2 output sizes: T1 x F1, T' x F2
+    int cf_chunk = 0;                         // utterances per subsampling slice (bounds the conv1 output buffer)
+    float *cf_c1_w = nullptr, *cf_c1_b = nullptr;   // conv_subsample.sequential.0: tap-major [9][256], bias
+    svhip::ConvLayer cf_c2;                   // conv_subsample.sequential.2 as a GEMM, k = dt * 768 + df * 256 + c (the segmented gather)
+    int* cf_seg_off = nullptr;                // (T' F2) row offsets of that gather within an utterance's conv1 output
+    svhip::ConvLayer cf_proj;                 // input_projection, columns permuted from c * F2 + f to f * 256 + c
+    svhip::ConvLayer cf_att0, cf_att3;        // attention.0 (+ ReLU, attention.2 as the epilogue affine), attention.3 (fp32 logits)
+    float *cf_pbn_scale = nullptr, *cf_pbn_shift = nullptr;   // attention_norm (BatchNorm1d(512))
+    svhip::LinearLayer cf_fc;                 // fc (Conv1d(512, nOut, 1))
+    float* cf_half = nullptr;                 // 256 x 0.5: the half-step residual as the epilogue scale
+    void *cf_c1 = nullptr, *cf_s2 = nullptr;  // per slice: conv1 output (chunk, T1, F1, 256); conv2 output (chunk T' F2, 256)
+    void *cf_in = nullptr, *cf_b0 = nullptr, *cf_x[2] = {}, *cf_r = nullptr;   // (Bmax T', 256): input projection, block 0's output,
+                                              // later blocks' outputs (ping-pong), the residual stream inside a block
+    void *cf_ln = nullptr, *cf_ln2 = nullptr; // (Bmax T', 256) LayerNorm outputs
+    void* cf_hid = nullptr;                   // (Bmax T', 1024): FF hidden / q | k | v / pointwise-conv output
+    void *cf_ctx = nullptr, *cf_attn0 = nullptr;   // (Bmax T', 256): attention context (block 0's is kept: stage cf_attn0); GLU-dw output
+    void* cf_last = nullptr;                  // the last block's output
+    float* cf_logits = nullptr;               // (Bmax T', 256) fp32 attention logits of the pooling
+    float *cf_pool_raw = nullptr, *cf_pool = nullptr;         // (Bmax, 512) [mean | std], after attention_norm
+
     // workspace (device)
     float* d_wav = nullptr;       // (Bmax, L)
     float* d_feat = nullptr;      // (Bmax, n_mels, T) mel power
@@ -334,6 +368,8 @@ inline bool is_rawnet2(int model) { return model == SVHIP_MODEL_RAWNET2 || model
 inline bool rn_is_sinc(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_GRU; }     // front_proc='sinc'
 inline bool rn_is_gru(int model) { return model == SVHIP_MODEL_RAWNET2_GRU; }                                       // aggregate='gru'
 inline int tn_kernel_size(int H) { return H == 256 ? 3 : H == 512 ? 7 : H == 1024 ? 11 : 0; }      // TitaNet s / m / l (TitaNet.py:152-157)
+inline int cf_sub(int n) { return (n - 3) / 2 + 1; }                  // one Conv2d(3, stride 2) of Conformer's subsampling (n >= 3)
+constexpr int CF_D = 256, CF_LAYERS = 6, CF_MAX_T = 10000;           // d_model, blocks, the length of the pe buffer
 inline int rn3_frames(int L) { return (L - RN3_TAPS) / RN3_STRIDE + 1; }      // T0 of RawNet3's front-end
 inline void* off(void* base, size_t elems, int esz) { return reinterpret_cast<char*>(base) + elems * esz; }
 inline const void* off(const void* base, size_t elems, int esz) { return reinterpret_cast<const char*>(base) + elems * esz; }
@@ -346,6 +382,7 @@ int finalize_rawnet2(svhip_handle* h);
 int finalize_rawnet3(svhip_handle* h);
 int finalize_titanet(svhip_handle* h);
 int titanet_blocks_loaded(const svhip_handle* h);      // contiguous mega-block indices loaded from 0
+int finalize_conformer(svhip_handle* h);
 int alloc_workspace(svhip_handle* h);
 
 // api_gemm.hip: the GEMM of one conv layer.  conv_plan is the one place that decides its kernel: conv_gemm launches what it returns,
@@ -367,10 +404,11 @@ int conv_gemm(svhip_handle* h, const ConvLayer& L, const GemmParams& p, const vo
 using ForwardPart = int (*)(svhip_handle* h, const float* in, int b0, int B);
 int forward_lanes(svhip_handle* h, ForwardPart part, const float* in, int B, int lanes, int per);
 
-// api_ecapa.hip, api_rawnet2.hip, api_rawnet3.hip, api_titanet.hip: the whole-batch forwards
+// api_ecapa.hip, api_rawnet2.hip, api_rawnet3.hip, api_titanet.hip, api_conformer.hip: the whole-batch forwards
 int ecapa_forward(svhip_handle* h, const float* d_feat, int B);
 int rawnet2_forward(svhip_handle* h, const float* d_wav, int B);
 int rawnet3_forward(svhip_handle* h, const float* d_wav, int B);
 int titanet_forward(svhip_handle* h, const float* d_feat, int B);      // from the mel power (B, n_mels, T)
+int conformer_forward(svhip_handle* h, const float* d_feat, int B);    // from the mel power (B, n_mels, T)
 
 }  // namespace svhip

@@ -92,6 +92,12 @@ struct GemmParams {
                               // 2: A and W are both in the S32 split layout (gemm_pw3's X3 form, launch_gemm_pw3x3)
     int debug = 0;            // developer ablations (tools/gemm_bench): 1 no loads in the loop, 2 no MFMA, 4 no epilogue
     int Wrows = 0;            // allocated rows of W (loads clamp to Wrows-1); packed weights: N rounded up to 128
+    // segmented row gather (the generic kernel only; gemm_route sends such a GEMM there): with seg_off != null the operand is
+    //   A'[m, k] = A[(m / seg_rows) * seg_utt + seg_off[m % seg_rows] + (k / seg_len) * seg_stride + k % seg_len]
+    // — per utterance a table of row offsets and K made of K / seg_len contiguous runs (Conformer's strided 3 x 3 conv, conformer.hip)
+    const int* seg_off = nullptr;
+    int seg_rows = 0, seg_len = 0;
+    int64_t seg_utt = 0, seg_stride = 0;
 };
 
 constexpr int GEMM_BM = 128;
@@ -254,9 +260,10 @@ hipError_t launch_crop_pcm16(const int16_t* pcm, const int64_t* off, const int32
 hipError_t launch_copy_cols(const void* src, int lds, void* dst, int ldd, bool bf16, int M, int C, hipStream_t stream);
 // attentive statistics: softmax over T of logits (fp32, ld = C), weighted mean / std of X, then
 // BatchNorm affine over the 2C pooled values -> pooled (B, 2C) fp32   (ECAPA_TDNN.py:252-259,496)
+// The variance is clamped below at eps and, with var_max > 0, above at var_max (Conformer's [1e-4, 1e4]; 0: no upper clamp)
 hipError_t launch_asp_pool(const float* logits, const void* X, bool bf16, int ldx, int B, int T, int C,
                            const float* bn_scale, const float* bn_shift, float* pooled_raw, float* pooled_bn,
-                           float eps, hipStream_t stream);
+                           float eps, float var_max, hipStream_t stream);
 
 // Fused attention tail (bf16 path, asp_fused.hip): logits = conv1x1(att) + b, softmax over T, weighted
 // mean / std of X, BatchNorm affine -> pooled (B, 2C).  The logits never reach memory.
@@ -415,6 +422,23 @@ hipError_t launch_tn_mega_tail(const void* skip, const void* h3, const float* ga
 
 // rows[b, 0:n) (row stride ld) = NaN for every utterance b whose input x[b * per_utt .. (b + 1) * per_utt) holds an inf / NaN
 hipError_t launch_tn_nonfinite_rows(const float* x, int64_t per_utt, int B, float* rows, int ld, int n, hipStream_t stream);
+
+// ---------------------------------------------------------------------------------------------
+// Conformer (conformer.hip): d_model = 256, frame-major (B T', 256) activations, fp32 or bf16 storage (dt), 16-byte aligned pointers.
+// ---------------------------------------------------------------------------------------------
+// Conv2d(1, 256, 3, stride 2) + ReLU over the (T, F) image of each utterance (x: (B T, F)): y (B, T1, F1, 256), T1 = (T - 3) / 2 + 1,
+// F1 = (F - 3) / 2 + 1; w tap-major [9][256] fp32 (tap = 3 dt + df), bias [256]
+hipError_t launch_cf_conv1(const void* x, const float* w, const float* bias, void* y, int dt, int B, int Tn, int F, hipStream_t stream);
+// y = LayerNorm(x) (g1, b1; eps 1e-5, fp32 statistics); with y2 != null also y2 = LayerNorm(y as stored) (g2, b2)
+hipError_t launch_cf_ln(const void* x, void* y, const float* g1, const float* b1, void* y2, const float* g2, const float* b2, int dt, int64_t M,
+                        hipStream_t stream);
+// u (B T', 512) -> y (B T', 256) = swish(dw15(u[:, :256] * sigmoid(u[:, 256:])) + bias), zero padding 7 per utterance;
+// w tap-major [15][256] fp32 with the BatchNorm scale folded in, bias = the BatchNorm shift
+hipError_t launch_cf_glu_dw(const void* u, const float* w, const float* bias, void* y, int dt, int B, int Tn, hipStream_t stream);
+// relative-position self-attention, 4 heads of 64: qkv (B T', ldq) holds q | k | v in columns [0, 768); P (T', ldp) fp32 = pe[:T'] W_pos^T;
+// u_bias, v_bias [4][64] fp32; ctx (B T', ldc) = the heads' contexts concatenated (before out_proj).  Any T' >= 1.
+hipError_t launch_cf_attn(const void* qkv, int ldq, const float* P, int ldp, const float* u_bias, const float* v_bias, void* ctx, int ldc, int dt,
+                          int B, int Tn, hipStream_t stream);
 
 // synthetic waveforms from a counter-based RNG (synth.hip): out (B, L) fp32 = utterances [first_utt, first_utt + B) of the stream `seed`
 hipError_t launch_synth_wave(float* out, uint64_t seed, int64_t first_utt, int B, int L, hipStream_t stream);

@@ -10,6 +10,7 @@ source of truth for the *names and shapes* of the reference state dicts
   * RawNet3     — reference ``src/models/RawNet3.py`` + ``RawNet_baseline.py`` (the defaults of its
                   ``MainModel``: 234 tensors),
   * TitaNet     — reference ``src/models/TitaNet.py`` + ``blocks/titanet_blocks.py`` (sizes s / m / l, any block count),
+  * Conformer   — reference ``src/models/Conformer.py`` + ``models/conformer/conformer/*`` (278 tensors at n_mels 80),
 
 and generates values from a ``numpy`` PCG64 stream in state-dict order, so the CPU oracle and the
 HIP path see bit-identical weights on any machine.  ``tests/test_oracle_golden.py`` checks the
@@ -218,6 +219,87 @@ def titanet_param_spec(size="l", nOut=512, n_blocks=None, n_mels=80):
     return spec
 
 
+CONFORMER_D = 256                                    # encoder_dim (Conformer.py:43)
+CONFORMER_LAYERS = 6                                 # num_layers (Conformer.py:48)
+CONFORMER_HEADS = 4
+CONFORMER_MAX_T = 10000                              # PositionalEncoding's max_len (embedding.py:31)
+
+
+def conformer_f2(n_mels):
+    """frequency bins after Conv2dSubampling's two 3 x 3 stride-2 convolutions"""
+    f1 = (n_mels - 3) // 2 + 1
+    return (f1 - 3) // 2 + 1
+
+
+def conformer_frames(T):
+    """T' of Conv2dSubampling for T input frames (0 when T < 7: the reference refuses such inputs)"""
+    if T < 7:
+        return 0
+    return ((T - 3) // 2 + 1 - 3) // 2 + 1
+
+
+def conformer_pe(d_model=CONFORMER_D, max_len=CONFORMER_MAX_T):
+    """PositionalEncoding.pe (embedding.py:30-38) in torch's float32 arithmetic: div_term = exp(float32), position * div_term rounded to
+    float32, then sin / cos.  torch evaluates it when it is importable (its float32 exp is not correctly rounded: three of the 128
+    div_term values differ by an ulp from the rounded exact value, which moves the arguments near position 10^4 by 1e-3); otherwise the
+    same steps in numpy with correctly rounded exp / sin / cos"""
+    try:
+        import torch
+    except Exception:  # pragma: no cover
+        torch = None
+    if torch is not None:
+        pe = torch.zeros(max_len, d_model)
+        position = torch.arange(0, max_len, dtype=torch.float).unsqueeze(1)
+        div_term = torch.exp(torch.arange(0, d_model, 2).float() * -(math.log(10000.0) / d_model))
+        pe[:, 0::2] = torch.sin(position * div_term)
+        pe[:, 1::2] = torch.cos(position * div_term)
+        return pe.numpy().reshape(1, max_len, d_model)
+    div = np.exp((np.arange(0, d_model, 2, dtype=np.float32) * np.float32(-(math.log(10000.0) / d_model))).astype(np.float64)).astype(np.float32)
+    arg = (np.arange(max_len, dtype=np.float32)[:, None] * div[None, :]).astype(np.float32)
+    pe = np.zeros((max_len, d_model), np.float32)
+    pe[:, 0::2] = np.sin(arg.astype(np.float64)).astype(np.float32)
+    pe[:, 1::2] = np.cos(arg.astype(np.float64)).astype(np.float32)
+    return pe.reshape(1, max_len, d_model)
+
+
+def conformer_param_spec(nOut=512, n_mels=80, attention_dim=128):
+    """Ordered (name, shape) list == ``Conformer.MainModel(nOut, n_mels=n_mels).state_dict()`` of the reference (Conformer.py:13-97,
+    conformer/encoder.py, attention.py, convolution.py, feed_forward.py)"""
+    D, F2 = CONFORMER_D, conformer_f2(n_mels)
+    ln = lambda p: [(p + ".weight", (D,)), (p + ".bias", (D,))]
+    spec = [("instance_norm.weight", (n_mels,)), ("instance_norm.bias", (n_mels,))]
+    s = "conformer_block.conv_subsample.sequential."
+    spec += [(s + "0.weight", (D, 1, 3, 3)), (s + "0.bias", (D,)), (s + "2.weight", (D, D, 3, 3)), (s + "2.bias", (D,))]
+    spec += [("conformer_block.input_projection.0.linear.weight", (D, D * F2)), ("conformer_block.input_projection.0.linear.bias", (D,))]
+
+    def ff(q):
+        return ln(q + "module.sequential.0") + [
+            (q + "module.sequential.1.linear.weight", (4 * D, D)), (q + "module.sequential.1.linear.bias", (4 * D,)),
+            (q + "module.sequential.4.linear.weight", (D, 4 * D)), (q + "module.sequential.4.linear.bias", (D,))]
+    for i in range(CONFORMER_LAYERS):
+        p = f"conformer_block.layers.{i}."
+        spec += ff(p + "sequential.0.")
+        a = p + "sequential.1.module."
+        spec += [(a + "positional_encoding.pe", (1, CONFORMER_MAX_T, D))] + ln(a + "layer_norm")
+        dh = D // CONFORMER_HEADS
+        spec += [(a + "attention.u_bias", (CONFORMER_HEADS, dh)), (a + "attention.v_bias", (CONFORMER_HEADS, dh))]
+        for q in ("query_proj", "key_proj", "value_proj"):
+            spec += [(a + f"attention.{q}.linear.weight", (D, D)), (a + f"attention.{q}.linear.bias", (D,))]
+        spec += [(a + "attention.pos_proj.linear.weight", (D, D)),
+                 (a + "attention.out_proj.linear.weight", (D, D)), (a + "attention.out_proj.linear.bias", (D,))]
+        c = p + "sequential.2.module.sequential."
+        spec += ln(c + "0") + [(c + "2.conv.weight", (2 * D, D, 1)), (c + "2.conv.bias", (2 * D,)), (c + "4.conv.weight", (D, 1, 15))]
+        spec += _bn(c + "5", D) + [(c + "7.conv.weight", (D, D, 1)), (c + "7.conv.bias", (D,))]
+        spec += ff(p + "sequential.3.") + ln(p + "sequential.4")
+    spec += [("asp.tdnn.conv.conv.weight", (attention_dim, 3 * D, 1)), ("asp.tdnn.conv.conv.bias", (attention_dim,))]
+    spec += _bn("asp.tdnn.norm.norm", attention_dim)
+    spec += [("asp.conv.weight", (D, attention_dim, 1)), ("asp.conv.bias", (D,))] + _bn("asp_bn.norm", 2 * D)
+    spec += [("attention.0.weight", (attention_dim, D, 1)), ("attention.0.bias", (attention_dim,))] + _bn("attention.2", attention_dim)
+    spec += [("attention.3.weight", (D, attention_dim, 1)), ("attention.3.bias", (D,))] + _bn("attention_norm", 2 * D)
+    spec += [("fc.conv.weight", (nOut, 2 * D, 1)), ("fc.conv.bias", (nOut,))]
+    return spec
+
+
 def rawnet3_sinc_buffers():
     """the persistent buffers of ParamSincFB(256, 251) at sample_rate 16000: window_ (125,), n_ (1, 125)"""
     n_lin = np.linspace(0.0, 251 / 2 - 1, RAWNET3_SINC_HALF)
@@ -277,6 +359,10 @@ def synth_state_dict(spec, seed=1):
             sd[name] = rng.uniform(0.5, 1.5, shape).astype(np.float32)
         elif leaf == "flipped_filter":                        # PreEmphasis(0.97), RawNet_baseline.py:27-38
             sd[name] = np.array([-0.97, 1.0], dtype=np.float32).reshape(shape)
+        elif leaf == "pe":                                     # Conformer's PositionalEncoding buffer: the formula, not random
+            sd[name] = conformer_pe(shape[2], shape[1])
+        elif leaf in ("u_bias", "v_bias"):                     # Conformer's per-head position biases
+            sd[name] = (0.1 * rng.standard_normal(shape)).astype(np.float32)
         elif leaf in ("window_", "n_"):                        # ParamSincFB's persistent buffers
             sd[name] = rawnet3_sinc_buffers()[0 if leaf == "window_" else 1].reshape(shape)
         elif leaf in ("low_hz_", "band_hz_"):

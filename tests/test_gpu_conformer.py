@@ -1,0 +1,248 @@
+"""GPU parity of the Conformer (tests/golden/conformer.npz; tools/make_golden_conformer.py): the embeddings against the REFERENCE's own
+module in fp32 and float64 at T' = 1, 2, 99, 129 and 499 (the attention kernel's key tiling and its shortest inputs), the stages against
+the reference's float64 values, the relative shift (the reference's shift reproduces block 0's attention context, the standard
+Transformer-XL shift does not), the pooling clamp at both ends, batch-order invariance, a NaN utterance, the refusals and the
+SpeakerEncoder / ModelHandling path with a CUDA tensor.
+
+Bars follow test_gpu_titanet.py: f32 <= 1e-5 of scale to float64 and <= 1e-4 + (reference fp32 to float64) to the reference's fp32;
+bf16 at the shared 16-bit bars (cosine >= 0.999, <= 3e-2 of scale)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import fbank as o_fbank
+from speakerverification_amd import _lib, synth
+from speakerverification_amd.engine import Engine
+from speakerverification_amd.models import Conformer
+
+pytestmark = pytest.mark.gpu
+
+KW = dict(n_mels=80, augment=False, augment_options={"augment_chain": []}, features="melspectrogram")
+BF16_BARS = (0.999, 3e-2)
+ERR_INVALID, ERR_UNSUPPORTED = -1, -5         # include/svhip.h
+
+
+def _cos(a, b):
+    return np.sum(a * b, axis=1) / (np.linalg.norm(a, axis=1) * np.linalg.norm(b, axis=1))
+
+
+def _rel(out, ref):
+    return float(np.abs(out - ref).max()) / float(np.abs(ref).max())
+
+
+def _check(out, ref32, ref64, compute, tag):
+    out = np.atleast_2d(out)
+    assert out.shape == ref32.shape and np.isfinite(out).all()
+    r64, r32, own = _rel(out, ref64), _rel(out, ref32), _rel(ref32, ref64)
+    cos = _cos(out, ref64)
+    print(f"{tag} {compute}: to float64 {r64:.2e}, to fp32 {r32:.2e} (reference fp32 to float64 {own:.2e}), min cos {cos.min():.7f}")
+    if compute == "f32":
+        assert r64 <= 1e-5, r64
+        assert r32 <= 1e-4 + own, (r32, own)
+    else:
+        c_min, r_max = BF16_BARS
+        assert r64 <= r_max and float(cos.min()) >= c_min, (r64, cos)
+
+
+def _sd(seed=1, nOut=512):
+    return synth.synth_state_dict(synth.conformer_param_spec(nOut, 80), seed=seed)
+
+
+def _mel(L, B=2, seed=20220829):
+    return o_fbank.melspectrogram(torch.from_numpy(synth.synth_waveforms(B, L, seed=seed))).numpy()
+
+
+def _engine(compute, B, L, sd=None, nOut=512):
+    eng = Engine(model="conformer", compute=compute, channels=256, embed_dim=nOut, max_batch=B, samples=L, log_input=True, input_norm=True)
+    eng.load_state_dict(sd if sd is not None else _sd(nOut=nOut))
+    eng.finalize()
+    return eng
+
+
+@pytest.mark.parametrize("compute", ["f32", "bf16"])
+def test_conformer_matches_reference_at_every_length(golden_dir, compute):
+    g = np.load(os.path.join(golden_dir, "conformer.npz"))
+    B = int(g["B"])
+    sd = _sd(int(g["seed_w"]))
+    for L in (int(v) for v in g["lengths"]):
+        mel = _mel(L, B, int(g["seed_x"]))
+        assert np.allclose(np.array([mel.astype(np.float64).sum(), np.abs(mel).astype(np.float64).sum()]), g[f"mel_L{L}"][:2], rtol=1e-5)
+        eng = _engine(compute, B, L, sd)
+        _check(eng.embed_features(mel), g[f"out32_L{L}"], g[f"out64_L{L}"], compute, f"conformer L={L} T'={synth.conformer_frames(mel.shape[2])}")
+        if L == 512:       # the mel front-end + net path (svhip_embed_wave) at the shortest length
+            wav = synth.synth_waveforms(B, L, seed=int(g["seed_x"]))
+            _check(eng.embed_wave(wav), g[f"out32_L{L}"], g[f"out64_L{L}"], compute, f"conformer wave L={L}")
+        eng.close()
+
+
+@pytest.mark.parametrize("compute", ["f32", "bf16"])
+def test_conformer_stages_against_float64(golden_dir, compute):
+    """input projection (the subsampling GEMM with its segmented row gather, then the permuted projection), block 0's attention
+    context, block 0's output, the last block's output and the pooled vector, utterance 0, against the reference in float64"""
+    g = np.load(os.path.join(golden_dir, "conformer.npz"))
+    L, B = 32000, 2
+    mel = _mel(L, B, int(g["seed_x"]))
+    eng = _engine(compute, B, L, _sd(int(g["seed_w"])))
+    eng.embed_features(mel)
+    Tp = 99
+    for stage, key in (("cf_in", "cf_in"), ("cf_attn0", "cf_attn0"), ("cf_block0", "block0"), ("cf_last", "block5"), ("cf_pool", "cf_pool")):
+        got = eng.get_stage(stage)
+        got = got.reshape(B, -1)[0] if stage == "cf_pool" else got.reshape(B, Tp, -1)[0]
+        want = g[f"val_{key}"]
+        r = _rel(got, want)
+        print(f"{compute} {stage}: {r:.2e} of scale")
+        assert got.shape == want.shape and r <= (1e-5 if compute == "f32" else 3e-2), (stage, r)
+    eng.close()
+
+
+def _attn64(x, t, i, T, shift):
+    """block i's attention context (before out_proj) from its MHSA input x (T, 256), float64; shift 'reference' or 'standard'"""
+    p = f"conformer_block.layers.{i}.sequential.1.module."
+    ln = torch.nn.functional.layer_norm(x, (256,), t[p + "layer_norm.weight"], t[p + "layer_norm.bias"], 1e-5)
+    lin = lambda y, n: y @ t[p + f"attention.{n}.linear.weight"].T + t[p + f"attention.{n}.linear.bias"]
+    q, k, v = (lin(ln, n).view(T, 4, 64).transpose(0, 1) for n in ("query_proj", "key_proj", "value_proj"))
+    pe = t[p + "positional_encoding.pe"][0, :T] @ t[p + "attention.pos_proj.linear.weight"].T
+    pe = pe.view(T, 4, 64).transpose(0, 1)
+    u, vb = t[p + "attention.u_bias"][:, None], t[p + "attention.v_bias"][:, None]
+    content = (q + u) @ k.transpose(1, 2)
+    pos = (q + vb) @ pe.transpose(1, 2)
+    out = torch.zeros_like(pos)
+    for a in range(T):
+        for b in range(T):
+            if b <= a:
+                out[:, a, b] = pos[:, a, T - 1 - (a - b)]
+            elif shift == "reference" and b >= a + 2:
+                out[:, a, b] = pos[:, a + 1, b - a - 2]
+    att = torch.softmax((content + out) / 16.0, -1)
+    return (att @ v).transpose(0, 1).reshape(T, 256)
+
+
+def test_relative_shift_uses_the_next_query_row(golden_dir):
+    """block 0 in float64 from the reference's cf_in: the feed-forward half step, then attention with the reference's shift reproduces
+    the reference's context (which the handle matches, test above) and the standard Transformer-XL shift does not"""
+    g = np.load(os.path.join(golden_dir, "conformer.npz"))
+    sd = _sd(int(g["seed_w"]))
+    t = {k: torch.from_numpy(np.asarray(v)).double() for k, v in sd.items() if np.asarray(v).dtype != np.int64}
+    x = torch.from_numpy(g["val_cf_in"]).double()
+    p = "conformer_block.layers.0.sequential.0.module.sequential."
+    h = torch.nn.functional.layer_norm(x, (256,), t[p + "0.weight"], t[p + "0.bias"], 1e-5)
+    h = h @ t[p + "1.linear.weight"].T + t[p + "1.linear.bias"]
+    h = (h * torch.sigmoid(h)) @ t[p + "4.linear.weight"].T + t[p + "4.linear.bias"]
+    x = x + 0.5 * h
+    want = g["val_cf_attn0"]
+    r_ref = _rel(_attn64(x, t, 0, 99, "reference").numpy(), want)
+    r_std = _rel(_attn64(x, t, 0, 99, "standard").numpy(), want)
+    print(f"reference shift {r_ref:.2e}, standard shift {r_std:.2e}")
+    assert r_ref <= 1e-6 and r_std > 1e-2
+    eng = _engine("f32", 2, 32000, sd)
+    eng.embed_features(_mel(32000, 2, int(g["seed_x"])))
+    got = eng.get_stage("cf_attn0").reshape(2, 99, 256)[0]
+    assert _rel(got, want) <= 1e-5 and _rel(got, _attn64(x, t, 0, 99, "standard").numpy()) > 1e-2
+    eng.close()
+
+
+@pytest.mark.parametrize("compute", ["f32", "bf16"])
+def test_pooling_clamp_at_both_ends(compute):
+    """the last block's LayerNorm scaled up (variance > 1e4) and down (variance < 1e-4), the attention logits constant over time: the
+    pooled std sits at 100 / 0.01 where the reference's clamp(1e-4, 1e4) holds it"""
+    L, B = 32000, 2
+    mel = _mel(L, B, seed=5)
+    p = "conformer_block.layers.5.sequential.4."
+    for gain, bias, lo, hi in ((1e5, 0.0, 99.99, 100.01), (1e-4, 0.0, 0.0099999, 0.0100001)):
+        sd = _sd()
+        sd[p + "weight"] = (sd[p + "weight"] * gain).astype(np.float32)
+        sd[p + "bias"] = np.full_like(sd[p + "bias"], bias)
+        sd["attention.3.weight"] = np.zeros_like(sd["attention.3.weight"])        # constant logits: uniform weights, the plain variance
+        eng = _engine(compute, B, L, sd)
+        eng.embed_features(mel)
+        pool = eng.get_stage("cf_pool").reshape(B, 512)
+        g_, b_, rm, rv = (sd["attention_norm." + k].astype(np.float64) for k in ("weight", "bias", "running_mean", "running_var"))
+        s = g_ / np.sqrt(rv + 1e-5)
+        sdv = (pool[:, 256:] - (b_ - rm * s)[256:]) / s[256:]
+        frac = float(((sdv >= lo) & (sdv <= hi)).mean())
+        print(f"{compute} gain {gain}: std in [{sdv.min():.6g}, {sdv.max():.6g}], {frac:.2f} at the clamp")
+        assert sdv.max() <= hi and sdv.min() >= (lo if gain < 1 else 0.0)
+        assert frac >= (1.0 if gain < 1 else 0.5), frac
+        eng.close()
+
+
+@pytest.mark.parametrize("compute", ["f32", "bf16"])
+def test_batch_permutation_is_bit_identical(compute):
+    """nothing crosses utterances: permuting the batch permutes the embeddings bit for bit"""
+    L, B = 32000, 5
+    mel = _mel(L, B, seed=11)
+    eng = _engine(compute, B, L)
+    a = eng.embed_features(mel)
+    perm = np.array([3, 0, 4, 1, 2])
+    b = eng.embed_features(np.ascontiguousarray(mel[perm]))
+    assert np.array_equal(a[perm], b)
+    eng.close()
+
+
+@pytest.mark.parametrize("compute", ["f32", "bf16"])
+def test_nan_utterance_stays_in_its_row(compute):
+    L, B = 32000, 3
+    mel = _mel(L, B, seed=9)
+    eng = _engine(compute, B, L)
+    clean = eng.embed_features(mel)
+    bad = mel.copy()
+    bad[1, 3, 100] = np.nan
+    eng.on_numeric = "ignore"
+    out = eng.embed_features(bad)
+    assert np.isnan(out[1]).all()
+    assert np.array_equal(out[[0, 2]], clean[[0, 2]])
+    eng.on_numeric = "raise"
+    with pytest.raises(_lib.SvhipError) as ei:
+        eng.embed_features(bad)
+    assert ei.value.code == _lib.ERR_NONFINITE
+    eng.close()
+
+
+def test_refusals_at_create_and_finalize():
+    def make(**kw):
+        a = dict(model="conformer", compute="f32", channels=256, embed_dim=512, max_batch=1, samples=32000, log_input=True, input_norm=True)
+        a.update(kw)
+        return Engine(**a)
+    for compute in ("f32x3", "f16"):
+        with pytest.raises(_lib.SvhipError) as ei:
+            make(compute=compute)
+        assert ei.value.code == ERR_UNSUPPORTED
+    for kw in (dict(channels=512), dict(input_norm=False), dict(samples=40006 * 80)):       # T' = 10001: refused before any allocation
+        with pytest.raises(_lib.SvhipError) as ei:
+            make(**kw)
+        assert ei.value.code == ERR_INVALID
+    make(samples=40005 * 80, channels=0).close()                                           # T' = 10000 is served
+    sd = _sd()
+    for drop in ("conformer_block.layers.3.sequential.1.module.positional_encoding.pe", "asp.conv.weight", "attention.2.running_var"):
+        eng = make()
+        eng.load_state_dict({k: v for k, v in sd.items() if k != drop})
+        with pytest.raises(_lib.SvhipError) as ei:
+            eng.finalize()
+        assert ei.value.code == _lib.ERR_MISSING, drop
+        eng.close()
+
+
+def test_conformer_device_tensor_and_speaker_encoder(golden_dir):
+    """Conformer takes CUDA tensors; SpeakerEncoder / ModelHandling serve a model_plot.yaml-shaped config (name: Conformer)"""
+    from speakerverification_amd.model import ModelHandling, SpeakerEncoder, WrappedModel
+    from tests.test_gpu_e2e import ARGS
+    g = np.load(os.path.join(golden_dir, "conformer.npz"))
+    m = Conformer.MainModel(nOut=512, device="cuda", **KW)
+    m.load_state_dict(_sd(int(g["seed_w"])))
+    mel = _mel(32000, 2, int(g["seed_x"]))
+    out = m(torch.from_numpy(mel).cuda())
+    assert out.is_cuda
+    assert _rel(out.cpu().numpy(), g["out64_L32000"]) <= 1e-5
+    args = dict(ARGS, model={"name": "Conformer", "nOut": 512}, features="melspectrogram", classifier={"input_size": 512, "out_neurons": 10})
+    enc = SpeakerEncoder(**args)
+    enc.load_state_dict({"__S__." + k: v for k, v in _sd(int(g["seed_w"])).items()})
+    x = torch.from_numpy(synth.synth_waveforms(2, 32000, seed=int(g["seed_x"]))).cuda()
+    o = enc(x)
+    o = o.detach().cpu().numpy() if hasattr(o, "detach") else np.asarray(o)
+    assert o.shape == (2, 512) and np.isfinite(o).all()
+    mh = ModelHandling(WrappedModel(enc), **args)
+    emb = mh.embed_utterance(x[0].cpu().numpy(), num_eval=2, normalize=True)
+    emb = emb.numpy() if hasattr(emb, "numpy") else np.asarray(emb)
+    assert np.isfinite(emb).all()
