@@ -1,6 +1,7 @@
 // api.hip — C ABI of libsvhip: handle lifetime, developer options, weight loading, embedding, staging, stages and profiling
-// (see include/svhip.h).  The handle is in handle.h; weight packing in api_weights.hip, the conv-layer GEMM in api_gemm.hip, the
-// forwards in api_ecapa.hip / api_rawnet2.hip, scoring and metrics in api_scoring.hip.
+// (see include/svhip.h).  The handle is in handle.h; what the models share when weights are loaded in api_weights.hip, the conv-layer
+// GEMM in api_gemm.hip, each model's own host code in its api_<model>.hip (kModels below lists them), scoring and metrics in
+// api_scoring.hip.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -49,8 +50,45 @@ const DevOptRow kDevOpts[] = {
 };
 #undef SV_OPT
 
-// RawNet2 needs six max_pool1d(3) stages behind the front-end to leave at least one frame: 3^6 front-end frames
-constexpr int RN_MIN_FRAMES = 3 * 3 * 3 * 3 * 3 * 3;
+int none_check(const svhip_config& c, const char*& err) {
+    if (c.compute == SVHIP_F16) { err = "SVHIP_F16 is RawNet2's 16-bit mode (ECAPA's is SVHIP_BF16)"; return SVHIP_ERR_UNSUPPORTED; }
+    return SVHIP_OK;
+}
+int fbank_then_features(svhip_handle* h, const float* d_wav, int B);
+
+// The models, one row per model id.  The three RawNet2 models share their functions (front_proc / aggregate follow cfg.model).
+const ModelOps kModels[] = {
+    // model                   check            spec            finalize            alloc            embed_wave           embed_feat         stage            lanes
+    {SVHIP_MODEL_ECAPA,        ecapa_check,     ecapa_spec,     ecapa_finalize,     ecapa_alloc,     ecapa_embed_wave,    ecapa_forward,     ecapa_stage,     2},
+    {SVHIP_MODEL_RAWNET2,      rawnet2_check,   rawnet2_spec,   rawnet2_finalize,   rawnet2_alloc,   rawnet2_forward,     nullptr,           rawnet2_stage,   4},
+    {SVHIP_MODEL_RAWNET2_CONV, rawnet2_check,   rawnet2_spec,   rawnet2_finalize,   rawnet2_alloc,   rawnet2_forward,     nullptr,           rawnet2_stage,   4},
+    {SVHIP_MODEL_RAWNET2_GRU,  rawnet2_check,   rawnet2_spec,   rawnet2_finalize,   rawnet2_alloc,   rawnet2_forward,     nullptr,           rawnet2_stage,   4},
+    {SVHIP_MODEL_RAWNET3,      rawnet3_check,   rawnet3_spec,   rawnet3_finalize,   rawnet3_alloc,   rawnet3_forward,     nullptr,           rawnet3_stage,   4},
+    {SVHIP_MODEL_TITANET,      titanet_check,   titanet_spec,   titanet_finalize,   titanet_alloc,   fbank_then_features, titanet_forward,   titanet_stage,   4,
+     "encoder.mega_blocks."},       // (the block count follows from what was loaded: titanet_finalize checks its blocks)
+    {SVHIP_MODEL_CONFORMER,    conformer_check, conformer_spec, conformer_finalize, conformer_alloc, fbank_then_features, conformer_forward, conformer_stage, 4},
+    {SVHIP_MODEL_NONE,         none_check,      nullptr,        nullptr,            nullptr,         nullptr,             nullptr,           nullptr,         1},   // fbank + scoring
+};
+
+const ModelOps* model_ops(int model) {
+    for (const ModelOps& m : kModels)
+        if (m.model == model) return &m;
+    return nullptr;
+}
+
+WeightSpec model_spec(const svhip_handle* h) {
+    WeightSpec spec;
+    if (const ModelOps* m = model_ops(h->cfg.model); m->spec) m->spec(h->cfg, spec);
+    return spec;
+}
+
+// the spectral models' waveform path: the mel power in fp32, then the net
+int fbank_then_features(svhip_handle* h, const float* d_wav, int B) {
+    int rc;
+    if ((rc = run(h, "fbank", 0, [&]() { return launch_fbank(h->fb, d_wav, B, h->cfg.samples, h->T, h->d_feat, h->stream); }))) return rc;
+    h->feat_is_stale = false;
+    return model_ops(h->cfg.model)->embed_feat(h, h->d_feat, B);
+}
 
 }  // namespace
 
@@ -76,6 +114,8 @@ void prof_collect(svhip_handle* h) {
     }
     h->ev_pending.clear();
 }
+
+int unknown_stage(svhip_handle* h, const std::string& name) { SV_FAIL(h, SVHIP_ERR_INVALID, "unknown stage %s", name.c_str()); }
 
 // A whole-batch forward: one slice on the handle's stream, or `lanes` slices of `per` utterances (the last one takes the rest) on the
 // lane streams, forked from and joined back into the handle's stream.
@@ -192,48 +232,11 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) { g_create_error = std::string("no HIP device: ") + hipGetErrorString(e); return SVHIP_ERR_HIP; }
     if (cfg->device < 0 || cfg->device >= ndev) { g_create_error = "device ordinal out of range"; return SVHIP_ERR_INVALID; }
-    if (cfg->model != SVHIP_MODEL_ECAPA && !is_rawnet2(cfg->model) && cfg->model != SVHIP_MODEL_RAWNET3 && cfg->model != SVHIP_MODEL_TITANET &&
-        cfg->model != SVHIP_MODEL_CONFORMER && cfg->model != SVHIP_MODEL_NONE) {
-        g_create_error = "unknown model";
-        return SVHIP_ERR_INVALID;
-    }
-    if (cfg->model == SVHIP_MODEL_RAWNET3) {
-        if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16) { g_create_error = "RawNet3 runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_INVALID; }
-        if (cfg->channels != 0 && cfg->channels != 1024) { g_create_error = "RawNet3 is built for C = 1024 (channels 0 or 1024)"; return SVHIP_ERR_INVALID; }
-        if (cfg->samples < RN3_MIN_SAMPLES) {
-            g_create_error = "RawNet3 needs at least 541 samples: (L - 251) / 10 + 1 frames pooled by 5 and 3 must leave two (the unbiased variance)";
-            return SVHIP_ERR_INVALID;
-        }
-    }
-    if (cfg->model == SVHIP_MODEL_TITANET) {
-        if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16) { g_create_error = "TitaNet runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_UNSUPPORTED; }
-        if (!tn_kernel_size(cfg->channels)) { g_create_error = "TitaNet is built for H = 256 / 512 / 1024 (sizes s / m / l: channels)"; return SVHIP_ERR_INVALID; }
-        if (cfg->log_input || cfg->input_norm) { g_create_error = "TitaNet reads the mel power as it is: log_input and input_norm must be 0"; return SVHIP_ERR_INVALID; }
-        if (cfg->embed_dim <= 0) { g_create_error = "TitaNet needs embed_dim > 0"; return SVHIP_ERR_INVALID; }
-    }
-    if (cfg->model == SVHIP_MODEL_CONFORMER) {
-        if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16) { g_create_error = "Conformer runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_UNSUPPORTED; }
-        if (cfg->channels != 0 && cfg->channels != CF_D) { g_create_error = "Conformer is built for d_model = 256 (channels 0 or 256)"; return SVHIP_ERR_INVALID; }
-        if (!cfg->input_norm) { g_create_error = "Conformer always applies its InstanceNorm1d: input_norm must be 1"; return SVHIP_ERR_INVALID; }
-        if (cfg->embed_dim <= 0) { g_create_error = "Conformer needs embed_dim > 0"; return SVHIP_ERR_INVALID; }
-        if (cfg->n_mels < 7) { g_create_error = "Conformer needs n_mels >= 7 (two 3 x 3 stride-2 convolutions)"; return SVHIP_ERR_INVALID; }
-        if (cfg->hop_length > 0) {
-            const int T = cfg->samples / cfg->hop_length + 1;
-            if (T < 7) { g_create_error = "Conformer needs at least 7 frames (T' = ((T - 3) / 2 + 1 - 3) / 2 + 1 >= 1)"; return SVHIP_ERR_INVALID; }
-            if (cf_sub(cf_sub(T)) > CF_MAX_T) {
-                g_create_error = "Conformer's positional encoding holds 10000 positions: T' = ((T - 3) / 2 + 1 - 3) / 2 + 1 must be <= 10000";
-                return SVHIP_ERR_INVALID;
-            }
-        }
-    }
-    if (cfg->model == SVHIP_MODEL_ECAPA && (cfg->channels <= 0 || cfg->channels % 64 != 0)) { g_create_error = "ECAPA channels must be a positive multiple of 64"; return SVHIP_ERR_INVALID; }
+    const ModelOps* m = model_ops(cfg->model);
+    if (!m) { g_create_error = "unknown model"; return SVHIP_ERR_INVALID; }
+    const char* msg = "";
+    if (int rc = m->check(*cfg, msg)) { g_create_error = msg; return rc; }
     if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16 && cfg->compute != SVHIP_F32X3 && cfg->compute != SVHIP_F16) { g_create_error = "unknown compute mode"; return SVHIP_ERR_INVALID; }
-    if (cfg->compute == SVHIP_F16 && !is_rawnet2(cfg->model)) { g_create_error = "SVHIP_F16 is RawNet2's 16-bit mode (ECAPA's is SVHIP_BF16)"; return SVHIP_ERR_UNSUPPORTED; }
-    if (rn_is_sinc(cfg->model) && cfg->samples < 251 + 3 * 3 * 3 * 3 * 3 * 3 * 3) { g_create_error = "RawNet2 needs at least 2438 samples"; return SVHIP_ERR_INVALID; }
-    if (cfg->model == SVHIP_MODEL_RAWNET2_CONV && cfg->samples < 3 * RN_MIN_FRAMES) {
-        g_create_error = "RawNet2 (front_proc='conv') needs at least 2187 samples: floor(L / 3) frames pass six max_pool1d(3) stages";
-        return SVHIP_ERR_INVALID;
-    }
     if (cfg->n_mels <= 0 || cfg->n_mels % 8 != 0 || cfg->max_batch <= 0 || cfg->samples < cfg->n_fft || cfg->hop_length <= 0) { g_create_error = "bad n_mels / max_batch / samples"; return SVHIP_ERR_INVALID; }
     if ((e = hipSetDevice(cfg->device)) != hipSuccess) { g_create_error = hipGetErrorString(e); return SVHIP_ERR_HIP; }
     svhip_handle* h = new svhip_handle();
@@ -265,8 +268,8 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
         // separate handles / streams (+12 .. 21 %, bench.py `rawnet2_3_streams`): a serving-loop choice, not a library default.
         const char* le = getenv("SVHIP_LANES");
         h->lanes = le ? atoi(le) : 1;
-        if (h->lanes < 1 || h->lanes > 4 || cfg->model == SVHIP_MODEL_NONE) h->lanes = 1;
-        if (cfg->model == SVHIP_MODEL_ECAPA && h->lanes > 2) h->lanes = 2;
+        if (h->lanes < 1 || h->lanes > 4) h->lanes = 1;
+        h->lanes = std::min(h->lanes, m->max_lanes);
         if (h->lanes > 1) {
             for (int i = 0; i < h->lanes; ++i) (void)hipStreamCreateWithFlags(&h->lane_stream[i], hipStreamNonBlocking);
             for (int i = 0; i < 5; ++i) (void)hipEventCreateWithFlags(&h->lane_ev[i], hipEventDisableTiming);
@@ -275,8 +278,9 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
     int rc = build_fbank_tables(h);
     h->fb.force32 = h->opt.fbank32;
     if (rc == SVHIP_OK) rc = alloc_workspace(h);
+    if (rc == SVHIP_OK && m->alloc) rc = m->alloc(h);
     if (rc != SVHIP_OK) { g_create_error = h->err; svhip_destroy(h); return rc; }
-    if (cfg->model == SVHIP_MODEL_NONE) h->finalized = true;
+    if (!m->finalize) h->finalized = true;         // (no weights to load)
     *out = h;
     return SVHIP_OK;
 }
@@ -323,8 +327,7 @@ int svhip_load_tensor(svhip_handle* h, const char* name, const void* data, const
     if (!h || !name || !shape || ndim < 0 || ndim > 4) return SVHIP_ERR_INVALID;
     if (!data) SV_FAIL(h, SVHIP_ERR_INVALID, "null data for %s (a 0-d tensor still holds one element)", name);
     if (h->finalized) SV_FAIL(h, SVHIP_ERR_STATE, "weights already finalized");
-    std::map<std::string, std::vector<int64_t>> spec;
-    model_spec(h->cfg, spec);
+    const WeightSpec spec = model_spec(h);
     auto it = spec.find(name);
     if (it == spec.end()) SV_FAIL(h, SVHIP_ERR_INVALID, "%s is not in the model.", name);
     std::vector<int64_t> shp(shape, shape + ndim);
@@ -344,20 +347,13 @@ int svhip_finalize_weights(svhip_handle* h) {
     if (!h) return SVHIP_ERR_INVALID;
     if (h->finalized) SV_FAIL(h, SVHIP_ERR_STATE, "weights already finalized");
     SV_HIP(h, hipSetDevice(h->cfg.device));
-    std::map<std::string, std::vector<int64_t>> spec;
-    model_spec(h->cfg, spec);
-    for (auto& kv : spec)       // (TitaNet: the block count follows from what was loaded; finalize_titanet checks its blocks)
+    const ModelOps* m = model_ops(h->cfg.model);
+    for (auto& kv : model_spec(h))
         if (!h->host_w.count(kv.first) && kv.first.find("num_batches_tracked") == std::string::npos &&
-            !(h->cfg.model == SVHIP_MODEL_TITANET && kv.first.rfind("encoder.mega_blocks.", 0) == 0))
+            !(m->optional_prefix && kv.first.rfind(m->optional_prefix, 0) == 0))
             SV_FAIL(h, SVHIP_ERR_MISSING, "tensor %s was never loaded", kv.first.c_str());
-    int rc = SVHIP_ERR_UNSUPPORTED;
-    if (h->cfg.model == SVHIP_MODEL_ECAPA) rc = finalize_ecapa(h);
-    else if (is_rawnet2(h->cfg.model)) rc = finalize_rawnet2(h);
-    else if (h->cfg.model == SVHIP_MODEL_RAWNET3) rc = finalize_rawnet3(h);
-    else if (h->cfg.model == SVHIP_MODEL_TITANET) rc = finalize_titanet(h);
-    else if (h->cfg.model == SVHIP_MODEL_CONFORMER) rc = finalize_conformer(h);
-    else SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
-    if (rc) return rc;
+    if (!m->finalize) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
+    if (int rc = m->finalize(h)) return rc;
     SV_HIP(h, hipDeviceSynchronize());
     h->host_w.clear();
     h->finalized = true;
@@ -374,8 +370,7 @@ int svhip_load_blob(svhip_handle* h, const char* path) {
         svhip_blob_close(b);
         SV_FAIL(h, SVHIP_ERR_INVALID, "%s holds weights of model %d, this handle is model %d", path, m, h->cfg.model);
     }
-    std::map<std::string, std::vector<int64_t>> spec;
-    model_spec(h->cfg, spec);
+    const WeightSpec spec = model_spec(h);
     const int32_t n = svhip_blob_count(b);
     for (int32_t i = 0; i < n; ++i) {
         const char* name; const void* data; int64_t shape[4]; int32_t ndim, dtype;
@@ -412,8 +407,8 @@ int svhip_embed_features(svhip_handle* h, const float* feat, int32_t B, int32_t 
     int rc = check_ready(h, B);
     if (rc) return rc;
     if (!feat || !emb_out) SV_FAIL(h, SVHIP_ERR_INVALID, "null pointer");
-    if (h->cfg.model != SVHIP_MODEL_ECAPA && h->cfg.model != SVHIP_MODEL_TITANET && h->cfg.model != SVHIP_MODEL_CONFORMER)
-        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "embed_features needs a spectral model (ECAPA, TitaNet, Conformer)");
+    const ModelOps* m = model_ops(h->cfg.model);
+    if (!m->embed_feat) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "embed_features needs a spectral model (ECAPA, TitaNet, Conformer)");
     if (T != h->T) SV_FAIL(h, SVHIP_ERR_INVALID, "T=%d but the handle was created for T=%d frames", T, h->T);
     if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
         SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
@@ -424,8 +419,7 @@ int svhip_embed_features(svhip_handle* h, const float* feat, int32_t B, int32_t 
         d_in = h->d_feat;
     }
     h->feat_is_stale = false;
-    if ((rc = h->cfg.model == SVHIP_MODEL_TITANET ? titanet_forward(h, d_in, B)
-            : h->cfg.model == SVHIP_MODEL_CONFORMER ? conformer_forward(h, d_in, B) : ecapa_forward(h, d_in, B))) return rc;
+    if ((rc = m->embed_feat(h, d_in, B))) return rc;
     if ((rc = emit_embeddings(h, B, emb_out, flags))) return rc;
     return finish(h, flags);
 }
@@ -437,38 +431,15 @@ int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, fl
     if (L != h->cfg.samples) SV_FAIL(h, SVHIP_ERR_INVALID, "L=%d but the handle was created for %d samples", L, h->cfg.samples);
     if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
         SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
-    if (h->cfg.model != SVHIP_MODEL_ECAPA && !is_rawnet2(h->cfg.model) && h->cfg.model != SVHIP_MODEL_RAWNET3 && h->cfg.model != SVHIP_MODEL_TITANET &&
-        h->cfg.model != SVHIP_MODEL_CONFORMER)
-        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
+    const ModelOps* m = model_ops(h->cfg.model);
+    if (!m->embed_wave) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "model %d has no forward path in this build", h->cfg.model);
     SV_HIP(h, hipSetDevice(h->cfg.device));
     const float* d_in = wav;
     if (!(flags & SVHIP_IN_DEVICE)) {
         SV_HIP(h, hipMemcpyAsync(h->d_wav, wav, (size_t)B * L * 4, hipMemcpyHostToDevice, h->stream));
         d_in = h->d_wav;
     }
-    if (is_rawnet2(h->cfg.model)) {
-        if ((rc = rawnet2_forward(h, d_in, B))) return rc;
-    } else if (h->cfg.model == SVHIP_MODEL_RAWNET3) {
-        if ((rc = rawnet3_forward(h, d_in, B))) return rc;
-    } else if (h->cfg.model == SVHIP_MODEL_TITANET || h->cfg.model == SVHIP_MODEL_CONFORMER) {   // the mel power in fp32, then the net
-        if ((rc = run(h, "fbank", 0, [&]() { return launch_fbank(h->fb, d_in, B, L, h->T, h->d_feat, h->stream); }))) return rc;
-        h->feat_is_stale = false;
-        if ((rc = h->cfg.model == SVHIP_MODEL_TITANET ? titanet_forward(h, h->d_feat, B) : conformer_forward(h, h->d_feat, B))) return rc;
-    } else {
-        const int T = h->T;
-        // bf16 handles without the instance-norm prologue: waveform -> the 16-bit operand of blocks.0 in two launches (fbank.hip, round 6)
-        const bool fused = h->bf16 && !h->in_w && h->d_logmel && !h->opt.fbank_unfused && !h->opt.fbank32 && fbank_fused_supported(h->fb, L);
-        if (fused) {
-            if ((rc = run(h, "fbank_fused", 0, [&]() {
-                     return launch_fbank_fused(h->fb, d_in, B, L, T, h->cfg.log_input, h->d_logmel, h->d_fpart, h->X_in, h->stream);
-                 }))) return rc;
-        } else if ((rc = run(h, "fbank", 0, [&]() { return launch_fbank(h->fb, d_in, B, L, T, h->d_feat, h->stream); }))) return rc;
-        h->xin_ready = fused;
-        h->feat_is_stale = fused;
-        rc = ecapa_forward(h, h->d_feat, B);
-        h->xin_ready = false;
-        if (rc) return rc;
-    }
+    if ((rc = m->embed_wave(h, d_in, B))) return rc;
     if ((rc = emit_embeddings(h, B, emb_out, flags))) return rc;
     return finish(h, flags);
 }
@@ -558,78 +529,28 @@ int svhip_synth_waveforms(svhip_handle* h, uint64_t seed, int64_t first_utt, int
 int svhip_get_stage(svhip_handle* h, const char* name, float* out, int64_t* count) {
     if (!h || !name || !count) return SVHIP_ERR_INVALID;
     if (h->lastB <= 0) SV_FAIL(h, SVHIP_ERR_STATE, "no forward has run yet");
-    const int B = h->lastB, T = h->T, C = h->cfg.channels, C3 = 3 * C, e = h->esz;
-    const size_t M = (size_t)B * T;
-    const void* src = nullptr;
-    size_t rows = M, cols = 0, ld = 0;
-    bool f32 = !h->bf16;
+    const int B = h->lastB;
+    StageView v{nullptr, (size_t)B * h->T, 0, 0, !h->bf16};
     const std::string n(name);
-    if (n == "input") { src = h->X_in; cols = ld = h->cfg.n_mels; }
-    else if (n == "blocks.0") {
-        src = h->X0; cols = ld = C;
-        if (h->x0_is_s32 && out) {            // F32X3: X0 holds hi | lo planes; the fp32 view goes to the (idle) operand staging buffer
-            SV_HIP(h, launch_unsplit_s32(h->X0, C, static_cast<float*>(h->s32_buf), C, (int64_t)M, C, h->stream));
-            src = h->s32_buf;
-        }
-    }
-    else if (n == "blocks.1" || n == "blocks.2" || n == "blocks.3") {
-        const int i = n.back() - '1';
-        src = off(h->CAT, (size_t)i * C, e); cols = C; ld = C3;
-        if (h->cat_f32_stale && out) {        // F32X3: the block outputs exist only in the split layout; rebuild the fp32 view
-            SV_HIP(h, launch_unsplit_s32(h->cat_s32, C3, static_cast<float*>(h->CAT), C3, (int64_t)M, C3, h->stream));
-            h->cat_f32_stale = false;
-        }
-    }
-    else if (n == "mfa") { src = h->MFA; cols = ld = C3; }
-    else if (n == "asp") { src = h->d_pool_raw; rows = B; cols = ld = 2 * C3; f32 = true; }
-    else if (n == "asp_bn") { src = h->d_pool_bn; rows = B; cols = ld = 2 * C3; f32 = true; }
-    else if (n == "rn_x") { src = h->rn_dbg_x; rows = (size_t)B * h->rn_dbg_T; cols = ld = h->rn_dbg_C; }
-    else if (n == "rn_snap") { src = h->rn_snap; rows = (size_t)B * h->rn_snap_T; cols = ld = h->rn_snap_C; }
-    else if (n == "rn_pooled") { src = h->rn_pooled; rows = B; cols = ld = 1024; f32 = true; }
-    else if ((n == "rn_gru_in" || n == "rn_gru_h") && rn_is_gru(h->cfg.model)) {
-        if (n == "rn_gru_h") { src = h->rn_gru_h; rows = B; cols = ld = RN_GRU_HIDDEN; f32 = true; }
-        else if (!h->rn_gru_in) SV_FAIL(h, SVHIP_ERR_STATE, "stage rn_gru_in: the last forward ran as several batch slices (SVHIP_LANES)");
-        else { src = h->rn_gru_in; rows = (size_t)B * h->rn_gru_T; cols = ld = 512; }
-    }
-    else if (n.rfind("rn3_", 0) == 0 && h->cfg.model == SVHIP_MODEL_RAWNET3) {      // RawNet3: rn3_front, rn3_layer1 .. 3, rn3_layer4, rn3_pooled
-        static const char* kStages[5] = {"rn3_front", "rn3_layer1", "rn3_layer2", "rn3_layer3", "rn3_layer4"};
-        int i = 0;
-        while (i < 5 && n != kStages[i]) ++i;
-        if (n == "rn3_pooled") { src = h->rn3_pooled; rows = B; cols = ld = 3072; f32 = true; }
-        else if (i == 5) SV_FAIL(h, SVHIP_ERR_INVALID, "unknown stage %s", name);
-        else { src = h->rn3_stage[i]; rows = (size_t)B * h->rn3_stage_T[i]; cols = h->rn3_stage_C[i]; ld = h->rn3_stage_ld[i]; }
-    }
-    else if (n.rfind("tn_", 0) == 0 && h->cfg.model == SVHIP_MODEL_TITANET) {      // TitaNet: tn_prolog, tn_dw0, tn_mega_last, tn_enc, tn_pool
-        const int H = C;
-        if (n == "tn_prolog") { src = h->tn_buf[0]; cols = ld = H; }
-        else if (n == "tn_mega_last") { src = h->tn_buf[1]; cols = ld = H; }
-        else if (n == "tn_dw0") { src = h->tn_buf[2]; cols = ld = H; }
-        else if (n == "tn_enc") { src = h->tn_enc; cols = ld = 1536; }
-        else if (n == "tn_pool") { src = h->tn_pool; rows = B; cols = ld = 3072; f32 = true; }
-        else SV_FAIL(h, SVHIP_ERR_INVALID, "unknown stage %s", name);
-    }
-    else if (n.rfind("cf_", 0) == 0 && h->cfg.model == SVHIP_MODEL_CONFORMER) {  // Conformer: cf_in, cf_block0, cf_attn0, cf_last, cf_pool
-        rows = (size_t)B * h->cf_Tp; cols = ld = CF_D;
-        if (n == "cf_in") src = h->cf_in;
-        else if (n == "cf_block0") src = h->cf_b0;
-        else if (n == "cf_attn0") src = h->cf_attn0;
-        else if (n == "cf_last") src = h->cf_last;
-        else if (n == "cf_pool") { src = h->cf_pool; rows = B; cols = ld = 2 * CF_D; f32 = true; }
-        else SV_FAIL(h, SVHIP_ERR_INVALID, "unknown stage %s", name);
-    }
+    if (n == "input" && h->X_in) { v.src = h->X_in; v.cols = v.ld = h->cfg.n_mels; }
     else if (n == "mel") {
         if (h->feat_is_stale) SV_FAIL(h, SVHIP_ERR_STATE, "stage mel: the last forward ran the fused front-end, which never forms the mel power "
                                       "tensor (option fbank_unfused = 1 keeps the separate kernels)");
-        src = h->d_feat; rows = (size_t)B * h->cfg.n_mels; cols = ld = T; f32 = true;
+        v.src = h->d_feat; v.rows = (size_t)B * h->cfg.n_mels; v.cols = v.ld = h->T; v.f32 = true;
     }
-    else SV_FAIL(h, SVHIP_ERR_INVALID, "unknown stage %s", name);
+    else {                                    // every other name is the model's
+        const ModelOps* m = model_ops(h->cfg.model);
+        if (!m->stage) return unknown_stage(h, n);
+        if (int rc = m->stage(h, n, out != nullptr, v)) return rc;
+    }
+    const size_t rows = v.rows, cols = v.cols;
     *count = (int64_t)(rows * cols);
     if (!out) return SVHIP_OK;
     SV_HIP(h, hipStreamSynchronize(h->stream));
-    const size_t es = f32 ? 4 : 2;
+    const size_t es = v.f32 ? 4 : 2;
     std::vector<char> tmp(rows * cols * es);
-    SV_HIP(h, hipMemcpy2D(tmp.data(), cols * es, src, ld * es, cols * es, rows, hipMemcpyDeviceToHost));
-    if (f32) memcpy(out, tmp.data(), tmp.size());
+    SV_HIP(h, hipMemcpy2D(tmp.data(), cols * es, v.src, v.ld * es, cols * es, rows, hipMemcpyDeviceToHost));
+    if (v.f32) memcpy(out, tmp.data(), tmp.size());
     else {
         const uint16_t* s = reinterpret_cast<const uint16_t*>(tmp.data());
         if (h->f16) for (size_t i = 0; i < rows * cols; ++i) { _Float16 hv; memcpy(&hv, &s[i], 2); out[i] = static_cast<float>(hv); }

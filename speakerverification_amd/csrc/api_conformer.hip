@@ -1,4 +1,5 @@
-// api_conformer.hip — the Conformer forward of libsvhip (reference models/Conformer.py:100-154, models/conformer/conformer/*.py).
+// api_conformer.hip — the Conformer in libsvhip (reference models/Conformer.py:100-154, models/conformer/conformer/*.py): its create
+// rules, weight names and packing, workspace, forward and stages.
 //
 // From the mel power (B, n_mels, T):
 //   front-end   log(x + 1e-6) - mean_t (log_input), InstanceNorm1d(n_mels, affine) -> X_in (B T, n_mels)        prologue
@@ -10,9 +11,228 @@
 //   pooling     w = softmax_T(attention.3(BN(relu(attention.0 x)))); [mu | sqrt(clamp(var, 1e-4, 1e4))]; attention_norm; fc
 // Every Linear / pointwise conv goes through conv_plan / conv_gemm.  The half-step residuals are the GEMM epilogue's scale (0.5) and
 // residual R; the residual stream stays in the handle's storage type.
+#include <algorithm>
+#include <thread>
+
 #include "handle.h"
 
 namespace svhip {
+
+int conformer_check(const svhip_config& c, const char*& err) {
+    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "Conformer runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_UNSUPPORTED; }
+    if (c.channels != 0 && c.channels != CF_D) { err = "Conformer is built for d_model = 256 (channels 0 or 256)"; return SVHIP_ERR_INVALID; }
+    if (!c.input_norm) { err = "Conformer always applies its InstanceNorm1d: input_norm must be 1"; return SVHIP_ERR_INVALID; }
+    if (c.embed_dim <= 0) { err = "Conformer needs embed_dim > 0"; return SVHIP_ERR_INVALID; }
+    if (c.n_mels < 7) { err = "Conformer needs n_mels >= 7 (two 3 x 3 stride-2 convolutions)"; return SVHIP_ERR_INVALID; }
+    if (c.hop_length > 0) {
+        const int T = c.samples / c.hop_length + 1;
+        if (T < 7) { err = "Conformer needs at least 7 frames (T' = ((T - 3) / 2 + 1 - 3) / 2 + 1 >= 1)"; return SVHIP_ERR_INVALID; }
+        if (cf_sub(cf_sub(T)) > CF_MAX_T) {
+            err = "Conformer's positional encoding holds 10000 positions: T' = ((T - 3) / 2 + 1 - 3) / 2 + 1 must be <= 10000";
+            return SVHIP_ERR_INVALID;
+        }
+    }
+    return SVHIP_OK;
+}
+
+// Conformer.MainModel (models/Conformer.py:13-97 with models/conformer/conformer/encoder.py's ConformerEncoder(n_mels, 256, 6 layers,
+// 4 heads, FF x 4, conv kernel 15)): the 278 names of its state dict.  asp.* / asp_bn.* are in it but never called (Conformer.py:144-148)
+static void cf_block_spec(const std::string& p, WeightSpec& spec) {
+    const int64_t D = CF_D;
+    auto ln = [&](const std::string& q) { spec[q + ".weight"] = {D}; spec[q + ".bias"] = {D}; };
+    auto ff = [&](const std::string& q) {
+        ln(q + "module.sequential.0");
+        spec[q + "module.sequential.1.linear.weight"] = {4 * D, D}; spec[q + "module.sequential.1.linear.bias"] = {4 * D};
+        spec[q + "module.sequential.4.linear.weight"] = {D, 4 * D}; spec[q + "module.sequential.4.linear.bias"] = {D};
+    };
+    ff(p + "sequential.0.");
+    const std::string a = p + "sequential.1.module.";
+    spec[a + "positional_encoding.pe"] = {1, CF_MAX_T, D};
+    ln(a + "layer_norm");
+    spec[a + "attention.u_bias"] = {4, 64}; spec[a + "attention.v_bias"] = {4, 64};
+    for (const char* q : {"query_proj", "key_proj", "value_proj", "out_proj"}) {
+        spec[a + "attention." + q + ".linear.weight"] = {D, D}; spec[a + "attention." + q + ".linear.bias"] = {D};
+    }
+    spec[a + "attention.pos_proj.linear.weight"] = {D, D};
+    const std::string cv = p + "sequential.2.module.sequential.";
+    ln(cv + "0");
+    spec[cv + "2.conv.weight"] = {2 * D, D, 1}; spec[cv + "2.conv.bias"] = {2 * D};
+    spec[cv + "4.conv.weight"] = {D, 1, 15};
+    spec_bn(spec, cv + "5", D);
+    spec[cv + "7.conv.weight"] = {D, D, 1}; spec[cv + "7.conv.bias"] = {D};
+    ff(p + "sequential.3.");
+    ln(p + "sequential.4");
+}
+void conformer_spec(const svhip_config& c, WeightSpec& spec) {
+    const int64_t D = CF_D, nm = c.n_mels, F2 = cf_sub(cf_sub((int)nm)), nOut = c.embed_dim;
+    spec["instance_norm.weight"] = {nm}; spec["instance_norm.bias"] = {nm};
+    const std::string s = "conformer_block.conv_subsample.sequential.";
+    spec[s + "0.weight"] = {D, 1, 3, 3}; spec[s + "0.bias"] = {D};
+    spec[s + "2.weight"] = {D, D, 3, 3}; spec[s + "2.bias"] = {D};
+    spec["conformer_block.input_projection.0.linear.weight"] = {D, D * F2}; spec["conformer_block.input_projection.0.linear.bias"] = {D};
+    for (int i = 0; i < CF_LAYERS; ++i) cf_block_spec("conformer_block.layers." + std::to_string(i) + ".", spec);
+    spec["asp.tdnn.conv.conv.weight"] = {128, 3 * D, 1}; spec["asp.tdnn.conv.conv.bias"] = {128};
+    spec_bn(spec, "asp.tdnn.norm.norm", 128);
+    spec["asp.conv.weight"] = {D, 128, 1}; spec["asp.conv.bias"] = {D};
+    spec_bn(spec, "asp_bn.norm", 2 * D);
+    spec["attention.0.weight"] = {128, D, 1}; spec["attention.0.bias"] = {128};
+    spec_bn(spec, "attention.2", 128);
+    spec["attention.3.weight"] = {D, 128, 1}; spec["attention.3.bias"] = {D};
+    spec_bn(spec, "attention_norm", 2 * D);
+    spec["fc.conv.weight"] = {nOut, 2 * D, 1}; spec["fc.conv.bias"] = {nOut};
+}
+
+int conformer_finalize(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    const int D = CF_D, Tp = h->cf_Tp, F2 = h->cf_F2, nOut = c.embed_dim;
+    int rc;
+    if ((rc = upload_f32(h, "instance_norm.weight", &h->in_w))) return rc;
+    if ((rc = upload_f32(h, "instance_norm.bias", &h->in_b))) return rc;
+    const std::string s = "conformer_block.conv_subsample.sequential.";
+    {
+        const HostTensor* w;                                   // (256, 1, 3, 3) -> tap-major [9][256]
+        if ((rc = needw(h, s + "0.weight", w))) return rc;
+        std::vector<float> tw(9 * D);
+        for (int ch = 0; ch < D; ++ch)
+            for (int t = 0; t < 9; ++t) tw[(size_t)t * D + ch] = w->data[(size_t)ch * 9 + t];
+        if ((rc = dev_upload(h, &h->cf_c1_w, tw))) return rc;
+        if ((rc = upload_f32(h, s + "0.bias", &h->cf_c1_b))) return rc;
+    }
+    {
+        const HostTensor *w, *b;                               // (256, 256, 3, 3) [n][c][dt][df] -> [n][dt * 768 + df * 256 + c]
+        if ((rc = needw(h, s + "2.weight", w))) return rc;
+        std::vector<float> pw((size_t)D * 9 * D);
+        for (int n = 0; n < D; ++n)
+            for (int ch = 0; ch < D; ++ch)
+                for (int t = 0; t < 9; ++t) pw[(size_t)n * 9 * D + (size_t)(t / 3) * 3 * D + (t % 3) * D + ch] = w->data[((size_t)n * D + ch) * 9 + t];
+        if ((rc = needw(h, s + "2.bias", b)) || (rc = make_conv(h, h->cf_c2, HostTensor{std::move(pw), {D, 9 * D, 1}}, &b->data, 1))) return rc;
+        std::vector<int> so((size_t)Tp * F2);
+        for (int t = 0; t < Tp; ++t)
+            for (int f = 0; f < F2; ++f) so[(size_t)t * F2 + f] = ((2 * t) * h->cf_F1 + 2 * f) * D;
+        if ((rc = dev_upload(h, &h->cf_seg_off, so))) return rc;
+    }
+    {
+        const std::string p = "conformer_block.input_projection.0.linear.";
+        const HostTensor *w, *b;                               // (256, 256 F2), column c F2 + f -> f 256 + c (the GEMM writes (b, t, f) rows)
+        if ((rc = needw(h, p + "weight", w))) return rc;
+        std::vector<float> pw((size_t)D * D * F2);
+        for (int n = 0; n < D; ++n)
+            for (int ch = 0; ch < D; ++ch)
+                for (int f = 0; f < F2; ++f) pw[(size_t)n * D * F2 + (size_t)f * D + ch] = w->data[(size_t)n * D * F2 + (size_t)ch * F2 + f];
+        if ((rc = needw(h, p + "bias", b)) || (rc = make_conv(h, h->cf_proj, HostTensor{std::move(pw), {D, D * F2}}, &b->data, 1))) return rc;
+    }
+    double fl = 2.0 * 9 * D * h->cf_T1 * h->cf_F1 + (double)Tp * F2 * h->cf_c2.flops_per_row + (double)Tp * h->cf_proj.flops_per_row;
+    h->cf.assign(CF_LAYERS, svhip_handle::CfBlock{});
+    for (int i = 0; i < CF_LAYERS; ++i) {
+        svhip_handle::CfBlock& K = h->cf[i];
+        const std::string p = "conformer_block.layers." + std::to_string(i) + ".";
+        for (int j = 0; j < 2; ++j) {
+            const std::string q = p + (j == 0 ? "sequential.0." : "sequential.3.") + "module.sequential.";
+            if ((rc = upload_f32(h, q + "0.weight", &K.ff_g[j]))) return rc;
+            if ((rc = upload_f32(h, q + "0.bias", &K.ff_b[j]))) return rc;
+            if ((rc = make_conv(h, K.ff1[j], q + "1.linear.weight", q + "1.linear.bias", "", 1))) return rc;
+            if ((rc = make_conv(h, K.ff2[j], q + "4.linear.weight", q + "4.linear.bias", "", 1))) return rc;
+            fl += (double)Tp * (K.ff1[j].flops_per_row + K.ff2[j].flops_per_row);
+        }
+        const std::string a = p + "sequential.1.module.";
+        if ((rc = upload_f32(h, a + "layer_norm.weight", &K.att_g))) return rc;
+        if ((rc = upload_f32(h, a + "layer_norm.bias", &K.att_b))) return rc;
+        {
+            std::vector<float> w, b;
+            for (const char* q : {"query_proj", "key_proj", "value_proj"}) {
+                const HostTensor *wq = getw(h, a + "attention." + q + ".linear.weight"), *bq = getw(h, a + "attention." + q + ".linear.bias");
+                if (!wq || !bq) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %sattention.%s.linear.*", a.c_str(), q);
+                w.insert(w.end(), wq->data.begin(), wq->data.end());
+                b.insert(b.end(), bq->data.begin(), bq->data.end());
+            }
+            if ((rc = make_conv(h, K.qkv, HostTensor{std::move(w), {3 * D, D}}, &b, 1))) return rc;
+        }
+        if ((rc = make_conv(h, K.out, a + "attention.out_proj.linear.weight", a + "attention.out_proj.linear.bias", "", 1))) return rc;
+        if ((rc = upload_f32(h, a + "attention.u_bias", &K.u))) return rc;
+        if ((rc = upload_f32(h, a + "attention.v_bias", &K.v))) return rc;
+        {
+            // P = pe[:T'] pos_proj^T in double: the positional term depends on T' only
+            const HostTensor *pe = getw(h, a + "positional_encoding.pe"), *wp = getw(h, a + "attention.pos_proj.linear.weight");
+            if (!pe || !wp) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %s%s", a.c_str(), !pe ? "positional_encoding.pe" : "attention.pos_proj.linear.weight");
+            std::vector<float> P((size_t)Tp * D);
+            auto rows = [&](int t0, int t1) {
+                for (int t = t0; t < t1; ++t) {
+                    const float* pr = pe->data.data() + (size_t)t * D;
+                    for (int n = 0; n < D; ++n) {
+                        const float* wr = wp->data.data() + (size_t)n * D;
+                        double acc = 0.0;
+                        for (int k = 0; k < D; ++k) acc += (double)pr[k] * (double)wr[k];
+                        P[(size_t)t * D + n] = (float)acc;
+                    }
+                }
+            };
+            // (rows split over up to 16 host threads: 6 x 655 M multiply-adds at T' = 10^4; every row is the same sum whatever the split)
+            const int nt = std::max(1, std::min({16, (int)std::thread::hardware_concurrency(), (Tp + 63) / 64}));
+            std::vector<std::thread> pool;
+            for (int q = 1; q < nt; ++q) pool.emplace_back(rows, (int)((int64_t)Tp * q / nt), (int)((int64_t)Tp * (q + 1) / nt));
+            rows(0, Tp / nt);
+            for (auto& th : pool) th.join();
+            if ((rc = dev_upload(h, &K.P, P))) return rc;
+        }
+        fl += (double)Tp * (K.qkv.flops_per_row + K.out.flops_per_row) + 4.0 * Tp * (double)Tp * 3 * 2 * 64;
+        const std::string cv = p + "sequential.2.module.sequential.";
+        if ((rc = upload_f32(h, cv + "0.weight", &K.cv_g))) return rc;
+        if ((rc = upload_f32(h, cv + "0.bias", &K.cv_b))) return rc;
+        if ((rc = make_conv(h, K.pw1, cv + "2.conv.weight", cv + "2.conv.bias", "", 1))) return rc;
+        if ((rc = make_conv(h, K.pw2, cv + "7.conv.weight", cv + "7.conv.bias", "", 1))) return rc;
+        {
+            // depthwise (256, 1, 15), no bias, then BatchNorm(256) (eval, eps 1e-5): w' = s w, b' = t (double on the host)
+            const HostTensor* dw;
+            std::vector<double> bs, bt;
+            if ((rc = needw(h, cv + "4.conv.weight", dw)) || (rc = bn_fold(h, cv + "5", D, bs, bt))) return rc;
+            std::vector<float> tw((size_t)15 * D), tb(D);
+            for (int ch = 0; ch < D; ++ch) {
+                for (int t = 0; t < 15; ++t) tw[(size_t)t * D + ch] = (float)(bs[ch] * (double)dw->data[(size_t)ch * 15 + t]);
+                tb[ch] = (float)bt[ch];
+            }
+            if ((rc = dev_upload(h, &K.dw_w, tw))) return rc;
+            if ((rc = dev_upload(h, &K.dw_b, tb))) return rc;
+        }
+        fl += (double)Tp * (K.pw1.flops_per_row + K.pw2.flops_per_row + 2.0 * 15 * D);
+        if ((rc = upload_f32(h, p + "sequential.4.weight", &K.fin_g))) return rc;
+        if ((rc = upload_f32(h, p + "sequential.4.bias", &K.fin_b))) return rc;
+    }
+    // pooling: attention.0 + ReLU with attention.2 (BatchNorm1d(128)) as the epilogue affine, attention.3 to fp32 logits
+    if ((rc = make_conv(h, h->cf_att0, "attention.0.weight", "attention.0.bias", "attention.2", 1))) return rc;
+    if ((rc = make_conv(h, h->cf_att3, "attention.3.weight", "attention.3.bias", "", 1))) return rc;
+    if ((rc = make_bn(h, "attention_norm", 2 * D, &h->cf_pbn_scale, &h->cf_pbn_shift))) return rc;
+    if ((rc = make_linear(h, h->cf_fc, "fc.conv.weight", "fc.conv.bias"))) return rc;
+    if (h->cf_fc.N != nOut || h->cf_fc.K != 2 * D) SV_FAIL(h, SVHIP_ERR_INVALID, "fc.conv.weight must be (%d, %d, 1)", nOut, 2 * D);
+    {
+        std::vector<float> half(D, 0.5f);
+        if ((rc = dev_upload(h, &h->cf_half, half))) return rc;
+    }
+    fl += (double)Tp * (h->cf_att0.flops_per_row + h->cf_att3.flops_per_row) + 2.0 * nOut * 2 * D;
+    h->flops_per_utt = fl;
+    return SVHIP_OK;
+}
+
+int conformer_alloc(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    const size_t B = c.max_batch, M = B * h->T, e = h->esz;
+    int rc;
+    // the subsampling slice buffers, eleven (B T', <= 1024) activations, logits, pooled rows
+    h->cf_T1 = cf_sub(h->T); h->cf_F1 = cf_sub(c.n_mels);
+    h->cf_Tp = cf_sub(h->cf_T1); h->cf_F2 = cf_sub(h->cf_F1);
+    const size_t Tp = h->cf_Tp, Mp = B * Tp, D = CF_D;
+    const size_t per_utt = (size_t)h->cf_T1 * h->cf_F1 * D * e;          // conv1 output bytes of one utterance
+    h->cf_chunk = (int)std::max<size_t>(1, std::min<size_t>(B, ((size_t)256 << 20) / per_utt));
+    if ((rc = actbuf(h, &h->X_in, M * c.n_mels))) return rc;
+    if ((rc = actbuf(h, &h->cf_c1, (size_t)h->cf_chunk * h->cf_T1 * h->cf_F1 * D))) return rc;
+    if ((rc = actbuf(h, &h->cf_s2, (size_t)h->cf_chunk * Tp * h->cf_F2 * D))) return rc;
+    void** bufs[] = {&h->cf_in, &h->cf_b0, &h->cf_x[0], &h->cf_x[1], &h->cf_r, &h->cf_ln, &h->cf_ln2, &h->cf_ctx, &h->cf_attn0, &h->cf_last};
+    for (void** b : bufs) if ((rc = actbuf(h, b, Mp * D))) return rc;
+    if ((rc = actbuf(h, &h->cf_hid, Mp * 4 * D))) return rc;
+    if ((rc = dev_alloc(h, &h->cf_logits, Mp * D))) return rc;
+    if ((rc = dev_alloc(h, &h->cf_pool_raw, B * 2 * D))) return rc;
+    if ((rc = dev_alloc(h, &h->cf_pool, B * 2 * D))) return rc;
+    return SVHIP_OK;
+}
 
 static int cf_ln(svhip_handle* h, const void* x, void* y, const float* g, const float* b, int64_t M, void* y2 = nullptr,
                  const float* g2 = nullptr, const float* b2 = nullptr) {
@@ -109,6 +329,17 @@ static int conformer_forward_part(svhip_handle* h, const float* d_feat, int b0, 
 }
 
 int conformer_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, conformer_forward_part, d_feat, B, 1, B); }
+
+int conformer_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // cf_in, cf_block0, cf_attn0, cf_last, cf_pool
+    v.rows = (size_t)h->lastB * h->cf_Tp; v.cols = v.ld = CF_D;
+    if (n == "cf_in") v.src = h->cf_in;
+    else if (n == "cf_block0") v.src = h->cf_b0;
+    else if (n == "cf_attn0") v.src = h->cf_attn0;
+    else if (n == "cf_last") v.src = h->cf_last;
+    else if (n == "cf_pool") { v.src = h->cf_pool; v.rows = h->lastB; v.cols = v.ld = 2 * CF_D; v.f32 = true; }
+    else return unknown_stage(h, n);
+    return SVHIP_OK;
+}
 
 }  // namespace svhip
 

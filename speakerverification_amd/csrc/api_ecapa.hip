@@ -1,9 +1,131 @@
-// api_ecapa.hip — the ECAPA-TDNN forward of libsvhip.
+// api_ecapa.hip — ECAPA-TDNN in libsvhip: its create rules, weight names and packing, workspace, forward and stages.
 #include <algorithm>
 
 #include "handle.h"
 
 namespace svhip {
+
+int ecapa_check(const svhip_config& c, const char*& err) {
+    if (c.channels <= 0 || c.channels % 64 != 0) { err = "ECAPA channels must be a positive multiple of 64"; return SVHIP_ERR_INVALID; }
+    if (c.compute == SVHIP_F16) { err = "SVHIP_F16 is RawNet2's 16-bit mode (ECAPA's is SVHIP_BF16)"; return SVHIP_ERR_UNSUPPORTED; }
+    return SVHIP_OK;
+}
+
+// ---- expected weight names / shapes ----------------------------------------------------------------
+const int ECAPA_K[5] = {5, 3, 3, 3, 1};
+const int ECAPA_D[5] = {1, 2, 3, 4, 1};
+
+void ecapa_spec(const svhip_config& c, WeightSpec& spec) {
+    const int64_t C = c.channels, C3 = 3 * C, nm = c.n_mels;
+    auto tdnn = [&](const std::string& p, int64_t cin, int64_t cout, int64_t k) {
+        spec[p + ".conv.conv.weight"] = {cout, cin, k}; spec[p + ".conv.conv.bias"] = {cout};
+        spec_bn(spec, p + ".norm.norm", cout);
+    };
+    if (c.input_norm) { spec["instance_norm.weight"] = {nm}; spec["instance_norm.bias"] = {nm}; }
+    tdnn("blocks.0", nm, C, ECAPA_K[0]);
+    for (int i = 1; i <= 3; ++i) {
+        const std::string p = "blocks." + std::to_string(i);
+        tdnn(p + ".tdnn1", C, C, 1);
+        for (int j = 0; j < 7; ++j) tdnn(p + ".res2net_block.blocks." + std::to_string(j), C / 8, C / 8, ECAPA_K[i]);
+        tdnn(p + ".tdnn2", C, C, 1);
+        spec[p + ".se_block.conv1.conv.weight"] = {128, C, 1}; spec[p + ".se_block.conv1.conv.bias"] = {128};
+        spec[p + ".se_block.conv2.conv.weight"] = {C, 128, 1}; spec[p + ".se_block.conv2.conv.bias"] = {C};
+    }
+    tdnn("mfa", C3, C3, 1);
+    tdnn("asp.tdnn", 3 * C3, 128, 1);
+    spec["asp.conv.conv.weight"] = {C3, 128, 1}; spec["asp.conv.conv.bias"] = {C3};
+    spec_bn(spec, "asp_bn.norm", 2 * C3);
+    spec["fc.conv.weight"] = {(int64_t)c.embed_dim, 2 * C3, 1}; spec["fc.conv.bias"] = {(int64_t)c.embed_dim};
+}
+
+static int make_tdnn(svhip_handle* h, ConvLayer& L, const std::string& p, int dil) {
+    return make_conv(h, L, p + ".conv.conv.weight", p + ".conv.conv.bias", p + ".norm.norm", dil);
+}
+
+int ecapa_finalize(svhip_handle* h) {
+    const int C = h->cfg.channels, C3 = 3 * C;
+    int rc;
+    if ((rc = make_tdnn(h, h->blocks0, "blocks.0", ECAPA_D[0]))) return rc;
+    for (int i = 1; i <= 3; ++i) {
+        const std::string p = "blocks." + std::to_string(i);
+        if ((rc = make_tdnn(h, h->tdnn1[i - 1], p + ".tdnn1", 1))) return rc;
+        for (int j = 0; j < 7; ++j)
+            if ((rc = make_tdnn(h, h->res2[i - 1][j], p + ".res2net_block.blocks." + std::to_string(j), ECAPA_D[i]))) return rc;
+        if ((rc = make_tdnn(h, h->tdnn2[i - 1], p + ".tdnn2", 1))) return rc;
+        if ((rc = make_linear(h, h->se1[i - 1], p + ".se_block.conv1.conv.weight", p + ".se_block.conv1.conv.bias"))) return rc;
+        if ((rc = make_linear(h, h->se2[i - 1], p + ".se_block.conv2.conv.weight", p + ".se_block.conv2.conv.bias"))) return rc;
+        {
+            const HostTensor* w2 = getw(h, p + ".se_block.conv2.conv.weight");      // (C, 128, 1)
+            std::vector<float> t((size_t)128 * C);
+            for (int c = 0; c < C; ++c)
+                for (int n = 0; n < 128; ++n) t[(size_t)n * C + c] = w2->data[(size_t)c * 128 + n];
+            if ((rc = dev_upload(h, &h->se2T[i - 1], t))) return rc;
+            if (h->bf16) {
+                const HostTensor* w1 = getw(h, p + ".se_block.conv1.conv.weight");  // (128, C, 1)
+                if ((rc = upload_h16(h, w1->data, &h->se1_bf[i - 1])) || (rc = upload_h16(h, t, &h->se2T_bf[i - 1]))) return rc;
+            }
+        }
+    }
+    if ((rc = make_tdnn(h, h->mfa, "mfa", 1))) return rc;
+    // asp.tdnn over cat[x, mean, std]: the x columns go through the GEMM, the time-constant columns
+    // become a per-utterance bias (ctx) computed by a small linear layer.
+    if ((rc = make_conv(h, h->asp_tdnn, "asp.tdnn.conv.conv.weight", "", "asp.tdnn.norm.norm", 1, 0, C3))) return rc;
+    if ((rc = make_linear(h, h->asp_ctx, "asp.tdnn.conv.conv.weight", "asp.tdnn.conv.conv.bias", C3, 3 * C3))) return rc;
+    if ((rc = make_conv(h, h->asp_conv, "asp.conv.conv.weight", "asp.conv.conv.bias", "", 1))) return rc;
+    if ((rc = make_bn(h, "asp_bn.norm", 2 * C3, &h->aspbn_scale, &h->aspbn_shift))) return rc;
+    if ((rc = make_linear(h, h->fc, "fc.conv.weight", "fc.conv.bias"))) return rc;
+    if (h->cfg.input_norm) {
+        const HostTensor *w = getw(h, "instance_norm.weight"), *b = getw(h, "instance_norm.bias");
+        if (!w || !b) SV_FAIL(h, SVHIP_ERR_MISSING, "missing instance_norm tensors");
+        if ((rc = dev_upload(h, &h->in_w, w->data))) return rc;
+        if ((rc = dev_upload(h, &h->in_b, b->data))) return rc;
+    }
+    // algorithmic FLOPs per utterance: 2 x MACs of every conv / linear (SURVEY §8d counts the same)
+    const double T = h->T;
+    double f = T * h->blocks0.flops_per_row + T * h->mfa.flops_per_row + T * h->asp_conv.flops_per_row;
+    f += T * 2.0 * 128 * (3.0 * C3);                                  // asp.tdnn over the full 9C input, as the reference computes it
+    for (int i = 0; i < 3; ++i) {
+        f += T * (h->tdnn1[i].flops_per_row + h->tdnn2[i].flops_per_row);
+        for (int j = 0; j < 7; ++j) f += T * h->res2[i][j].flops_per_row;
+        f += 2.0 * h->se1[i].N * h->se1[i].K + 2.0 * h->se2[i].N * h->se2[i].K;
+    }
+    f += 2.0 * h->fc.N * h->fc.K;
+    h->flops_per_utt = f;
+    return SVHIP_OK;
+}
+
+int ecapa_alloc(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    const size_t B = c.max_batch, T = h->T, M = B * T, C = c.channels, C3 = 3 * C;
+    int rc;
+    if ((rc = actbuf(h, &h->X_in, M * c.n_mels))) return rc;
+    if ((rc = actbuf(h, &h->X0, M * C))) return rc;
+    if ((rc = actbuf(h, &h->H1, M * C))) return rc;
+    if ((rc = actbuf(h, &h->H2, M * C))) return rc;
+    if ((rc = actbuf(h, &h->H3, M * C))) return rc;
+    if ((rc = actbuf(h, &h->CAT, M * C3))) return rc;
+    if ((rc = actbuf(h, &h->MFA, M * C3))) return rc;
+    if ((rc = actbuf(h, &h->ATT, M * 128))) return rc;
+    if ((rc = dev_alloc(h, &h->LOGITS, M * C3))) return rc;
+    if ((rc = dev_alloc(h, &h->d_mean, B * C))) return rc;
+    if ((rc = dev_alloc(h, &h->d_s1, B * 128))) return rc;
+    if ((rc = dev_alloc(h, &h->d_s2, B * C))) return rc;
+    if ((rc = dev_alloc(h, &h->d_gstats, B * 2 * C3))) return rc;
+    if ((rc = dev_alloc(h, &h->d_ctx, B * 128))) return rc;
+    h->lin_part_per_utt = (size_t)((2 * C3 + 383) / 384) * (size_t)std::max(128, c.embed_dim);
+    if ((rc = dev_alloc(h, &h->d_lin_part, B * h->lin_part_per_utt))) return rc;
+    if ((rc = dev_alloc(h, &h->d_pool_raw, B * 2 * C3))) return rc;
+    if ((rc = dev_alloc(h, &h->d_pool_bn, B * 2 * C3))) return rc;
+    if (h->x3 && (rc = dev_alloc(h, reinterpret_cast<char**>(&h->s32_buf), M * C3 * 4 + 256))) return rc;
+    if (h->x3 && C % 32 == 0 && (rc = dev_alloc(h, reinterpret_cast<char**>(&h->cat_s32), M * C3 * 4 + 256))) return rc;
+    if (h->x3 && (C == 512 || C == 1024)) {
+        if ((rc = dev_alloc(h, reinterpret_cast<char**>(&h->h2_s32), M * C * 4 + 256))) return rc;
+        for (int i = 0; i < 2; ++i) if ((rc = dev_alloc(h, reinterpret_cast<char**>(&h->u_s32[i]), M * (C / 8) * 4 + 256))) return rc;
+    }
+    h->colsum_region = (int64_t)((M + 255) / 256 + 2) * 16 * C3;
+    if ((rc = dev_alloc(h, &h->d_colsum, (size_t)4 * h->colsum_region))) return rc;
+    return SVHIP_OK;
+}
 
 // ECAPA_TDNN.forward (models/ECAPA_TDNN.py:460-502) on device-resident features (B, n_mels, T)
 // for the utterances [b0, b0 + B) of the call, enqueued on h->cur.  Every workspace buffer is frame-major, so a
@@ -228,6 +350,48 @@ int ecapa_forward(svhip_handle* h, const float* d_feat, int B) {
     h->cat_f32_stale = false;
     const bool two = h->lanes == 2 && B >= 64 && !h->x3;      // (F32X3: the lanes would share the split-operand staging buffer)
     return forward_lanes(h, ecapa_forward_part, d_feat, B, two ? 2 : 1, (B / 2 + 3) & ~3);
+}
+
+// the waveform path: bf16 handles without the instance-norm prologue go from the waveform to the 16-bit operand of blocks.0 in two
+// launches (fbank.hip, round 6); the others run the fbank, then the forward from the mel power
+int ecapa_embed_wave(svhip_handle* h, const float* d_wav, int B) {
+    const int L = h->cfg.samples, T = h->T;
+    const bool fused = h->bf16 && !h->in_w && h->d_logmel && !h->opt.fbank_unfused && !h->opt.fbank32 && fbank_fused_supported(h->fb, L);
+    int rc;
+    if (fused) {
+        if ((rc = run(h, "fbank_fused", 0, [&]() {
+                 return launch_fbank_fused(h->fb, d_wav, B, L, T, h->cfg.log_input, h->d_logmel, h->d_fpart, h->X_in, h->stream);
+             }))) return rc;
+    } else if ((rc = run(h, "fbank", 0, [&]() { return launch_fbank(h->fb, d_wav, B, L, T, h->d_feat, h->stream); }))) return rc;
+    h->xin_ready = fused;
+    h->feat_is_stale = fused;
+    rc = ecapa_forward(h, h->d_feat, B);
+    h->xin_ready = false;
+    return rc;
+}
+
+int ecapa_stage(svhip_handle* h, const std::string& n, bool fill, StageView& v) {
+    const int C = h->cfg.channels, C3 = 3 * C, B = h->lastB;
+    const int64_t M = (int64_t)B * h->T;
+    if (n == "blocks.0") {
+        v.src = h->X0; v.cols = v.ld = C;
+        if (h->x0_is_s32 && fill) {           // F32X3: X0 holds hi | lo planes; the fp32 view goes to the (idle) operand staging buffer
+            SV_HIP(h, launch_unsplit_s32(h->X0, C, static_cast<float*>(h->s32_buf), C, M, C, h->stream));
+            v.src = h->s32_buf;
+        }
+    } else if (n == "blocks.1" || n == "blocks.2" || n == "blocks.3") {
+        const int i = n.back() - '1';
+        v.src = off(h->CAT, (size_t)i * C, h->esz); v.cols = C; v.ld = C3;
+        if (h->cat_f32_stale && fill) {       // F32X3: the block outputs exist only in the split layout; rebuild the fp32 view
+            SV_HIP(h, launch_unsplit_s32(h->cat_s32, C3, static_cast<float*>(h->CAT), C3, M, C3, h->stream));
+            h->cat_f32_stale = false;
+        }
+    }
+    else if (n == "mfa") { v.src = h->MFA; v.cols = v.ld = C3; }
+    else if (n == "asp") { v.src = h->d_pool_raw; v.rows = B; v.cols = v.ld = 2 * C3; v.f32 = true; }
+    else if (n == "asp_bn") { v.src = h->d_pool_bn; v.rows = B; v.cols = v.ld = 2 * C3; v.f32 = true; }
+    else return unknown_stage(h, n);
+    return SVHIP_OK;
 }
 
 }  // namespace svhip

@@ -1,9 +1,315 @@
-// api_rawnet2.hip — the RawNet2 forward of libsvhip.
+// api_rawnet2.hip — RawNet2 in libsvhip (the 'sinc' and 'conv' front-ends, the 'asp' and 'gru' aggregations): its create rules, weight
+// names and packing, workspace, forward and stages.
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 
 #include "handle.h"
 
 namespace svhip {
+
+// RawNet2 needs six max_pool1d(3) stages behind the front-end to leave at least one frame: 3^6 front-end frames
+constexpr int RN_MIN_FRAMES = 3 * 3 * 3 * 3 * 3 * 3;
+
+int rawnet2_check(const svhip_config& c, const char*& err) {
+    if (rn_is_sinc(c.model) && c.samples < 251 + 3 * RN_MIN_FRAMES) { err = "RawNet2 needs at least 2438 samples"; return SVHIP_ERR_INVALID; }
+    if (!rn_is_sinc(c.model) && c.samples < 3 * RN_MIN_FRAMES) {
+        err = "RawNet2 (front_proc='conv') needs at least 2187 samples: floor(L / 3) frames pass six max_pool1d(3) stages";
+        return SVHIP_ERR_INVALID;
+    }
+    return SVHIP_OK;
+}
+
+// ---- expected weight names / shapes ----------------------------------------------------------------
+const int RN_LAYERS[6] = {1, 1, 1, 2, 1, 2};                   // RawNet2_custom.py:231
+
+const int RN_FILTERS[6] = {128, 128, 256, 256, 512, 512};      // RawNet2_custom.py:232
+
+void rawnet2_spec(const svhip_config& c, WeightSpec& spec) {
+    if (c.model == SVHIP_MODEL_RAWNET2_CONV) {          // conv1 = Conv1d(1, 128, 3, stride=3) with bias (RawNet2_custom.py:45-52)
+        spec["conv1.weight"] = {128, 1, 3}; spec["conv1.bias"] = {128};
+    } else {
+        spec["ln.gamma"] = {(int64_t)c.samples}; spec["ln.beta"] = {(int64_t)c.samples};
+        spec["first_conv.low_hz_"] = {128, 1}; spec["first_conv.band_hz_"] = {128, 1};
+        spec_bn(spec, "first_bn", 128);
+    }
+    int64_t inpl = 128;
+    for (int li = 0; li < 6; ++li)
+        for (int b = 0; b < RN_LAYERS[li]; ++b) {
+            const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
+            const int64_t planes = RN_FILTERS[li];
+            spec_bn(spec, p + ".bn1", inpl);
+            spec[p + ".conv1.weight"] = {planes, inpl, 3};
+            spec_bn(spec, p + ".bn2", planes);
+            spec[p + ".conv2.weight"] = {planes, planes, 3};
+            spec[p + ".afms.alpha"] = {planes, 1};
+            spec[p + ".afms.fc.weight"] = {planes, planes}; spec[p + ".afms.fc.bias"] = {planes};
+            if (inpl != planes) spec[p + ".shortcut.0.weight"] = {planes, inpl, 1};
+            inpl = planes;
+        }
+    if (rn_is_gru(c.model)) {                        // aggregate='gru' (RawNet2_custom.py:84-95): fc is built too, and never used (:196-207)
+        const int64_t G = 3 * RN_GRU_HIDDEN;
+        spec_bn(spec, "bn_before_gru", 512);
+        spec["gru.weight_ih_l0"] = {G, 512}; spec["gru.weight_hh_l0"] = {G, RN_GRU_HIDDEN};
+        spec["gru.bias_ih_l0"] = {G}; spec["gru.bias_hh_l0"] = {G};
+        spec["fc_after_gru.weight"] = {(int64_t)c.embed_dim, RN_GRU_HIDDEN}; spec["fc_after_gru.bias"] = {(int64_t)c.embed_dim};
+    } else {
+        spec_bn(spec, "bn_before_agg", 512);
+        spec["attention.0.weight"] = {128, 512, 1}; spec["attention.0.bias"] = {128};
+        spec_bn(spec, "attention.2", 128);
+        spec["attention.3.weight"] = {512, 128, 1}; spec["attention.3.bias"] = {512};
+    }
+    spec["fc.weight"] = {(int64_t)c.embed_dim, 1024}; spec["fc.bias"] = {(int64_t)c.embed_dim};
+}
+
+// a conv layer of a RawNet2 handle: F32X3 handles also get the S32 split layout of r2_step.hip's modes 1 / 2 where its shape fits
+static int rn_conv(svhip_handle* h, ConvLayer& L, const std::string& w, const std::string& b, const std::string& bn) {
+    return make_conv(h, L, w, b, bn, 1, 0, -1, true);
+}
+
+// sinc band-pass filters baked once per weight load (RawNet_baseline.py:313-318,339-357), float32 arithmetic
+static int bake_sinc(svhip_handle* h) {
+    const HostTensor *lo = getw(h, "first_conv.low_hz_"), *bd = getw(h, "first_conv.band_hz_");
+    if (!lo || !bd) SV_FAIL(h, SVHIP_ERR_MISSING, "missing sinc parameters");
+    const int NF = 128, KS = 251, HALF = 125;
+    const float sr = 16000.0f, min_low = 50.0f, min_band = 50.0f;
+    const float PI = 3.14159265358979323846f;
+    std::vector<float> win(HALF), n_(HALF);
+    for (int i = 0; i < HALF; ++i) {
+        const float n_lin = (float)(124.5 * i / 124.0);                         // torch.linspace(0, 124.5, 125)
+        win[i] = 0.54f - 0.46f * std::cos(2.0f * PI * n_lin / (float)KS);
+        n_[i] = 2.0f * PI * (float)(-125 + i) / sr;                             // 2*pi*arange(-125, 0)/16000
+    }
+    std::vector<float> filt((size_t)NF * KS);
+    for (int f = 0; f < NF; ++f) {
+        const float low = min_low + std::fabs(lo->data[f]);
+        float high = low + min_band + std::fabs(bd->data[f]);
+        high = std::fmin(std::fmax(high, min_low), sr / 2);
+        const float band = high - low;
+        for (int i = 0; i < HALF; ++i) {
+            const float left = ((std::sin(high * n_[i]) - std::sin(low * n_[i])) / (n_[i] / 2.0f)) * win[i];
+            filt[(size_t)f * KS + i] = left / (2.0f * band);
+            filt[(size_t)f * KS + (KS - 1 - i)] = left / (2.0f * band);
+        }
+        filt[(size_t)f * KS + HALF] = (2.0f * band) / (2.0f * band);
+    }
+    int rc;
+    if (h->bf16) {
+        std::vector<uint16_t> pk((size_t)NF * 256, 0);
+        for (int f = 0; f < NF; ++f)
+            for (int k = 0; k < KS; ++k) pk[(size_t)f * 256 + k] = to_h16(h, filt[(size_t)f * KS + k]);
+        uint16_t* d;
+        if ((rc = dev_upload(h, &d, pk))) return rc;
+        h->rn_filt = d;
+        if (h->f16) {
+            // the symmetric form (rawnet2.hip, SYM): slot k' = 2 + m carries h[125 + m] (the centre tap halved: its operand is x[c] + x[c]),
+            // slots 0 and 1 are zero; right and left halves of a filter are the same numbers by construction (checked here)
+            bool symmetric = true;
+            for (int f = 0; f < NF && symmetric; ++f)
+                for (int i = 0; i < HALF; ++i) symmetric = symmetric && filt[(size_t)f * KS + i] == filt[(size_t)f * KS + (KS - 1 - i)];
+            if (symmetric) {
+                std::vector<uint16_t> ps((size_t)NF * 128, 0);
+                for (int f = 0; f < NF; ++f) {
+                    ps[(size_t)f * 128 + 2] = to_h16(h, 0.5f * filt[(size_t)f * KS + HALF]);
+                    for (int m = 1; m <= HALF; ++m) ps[(size_t)f * 128 + 2 + m] = to_h16(h, filt[(size_t)f * KS + HALF + m]);
+                }
+                uint16_t* ds;
+                if ((rc = dev_upload(h, &ds, ps))) return rc;
+                h->rn_filt_sym = ds;
+            }
+        }
+    } else {
+        std::vector<float> pk((size_t)NF * 252, 0.0f);
+        for (int f = 0; f < NF; ++f)
+            for (int k = 0; k < KS; ++k) pk[(size_t)f * 252 + k] = filt[(size_t)f * KS + k];
+        float* d;
+        if ((rc = dev_upload(h, &d, pk))) return rc;
+        h->rn_filt = d;
+        if (h->x3) {        // the split front-end (rn_sinc_x3): hi and lo half planes, k contiguous, zero beyond the 251 taps
+            std::vector<uint16_t> pl((size_t)2 * NF * 256, 0);
+            for (int f = 0; f < NF; ++f)
+                for (int k = 0; k < KS; ++k) {
+                    const uint32_t w = x3_split_word(filt[(size_t)f * KS + k]);
+                    pl[(size_t)f * 256 + k] = (uint16_t)(w >> 16);
+                    pl[(size_t)(NF + f) * 256 + k] = (uint16_t)(w & 0xffffu);
+                }
+            uint16_t* dx;
+            if ((rc = dev_upload(h, &dx, pl))) return rc;
+            h->rn_filt_x3 = dx;
+        }
+    }
+    return SVHIP_OK;
+}
+
+// the 'conv' front-end's constants: conv1.weight (128, 1, 3) and conv1.bias as [w0 | w1 | w2 | bias] x 128 floats
+static int make_conv3_front(svhip_handle* h) {
+    const HostTensor *w, *b;
+    int rc;
+    if ((rc = needw(h, "conv1.weight", w)) || (rc = needw(h, "conv1.bias", b))) return rc;
+    std::vector<float> cw(4 * 128);
+    for (int c = 0; c < 128; ++c) {
+        for (int k = 0; k < 3; ++k) cw[k * 128 + c] = w->data[c * 3 + k];
+        cw[3 * 128 + c] = b->data[c];
+    }
+    return dev_upload(h, &h->rn_cw, cw);
+}
+
+// aggregate='gru' (RawNet2_custom.py:84-95,196-207): bn_before_gru is the pass block 7's AFMS pass applies (rn_agg_scale / shift); the input
+// projection W_ih is a 1 x 1 conv layer whose bias folds b_ih + [b_hr | b_hz | 0] (b_hn stays inside r * (W_hn h + b_hn)); W_hh is packed
+// gate-interleaved (gru.hip) in the compute type; fc_after_gru is a small linear.  fc.* is loaded and not used, as in the reference.
+static int rawnet2_finalize_gru(svhip_handle* h) {
+    const int H = RN_GRU_HIDDEN, G = 3 * H;
+    int rc;
+    if ((rc = make_bn(h, "bn_before_gru", 512, &h->rn_agg_scale, &h->rn_agg_shift))) return rc;
+    const HostTensor *whh = getw(h, "gru.weight_hh_l0"), *bih = getw(h, "gru.bias_ih_l0"), *bhh = getw(h, "gru.bias_hh_l0");
+    if (!whh || !bih || !bhh) SV_FAIL(h, SVHIP_ERR_MISSING, "missing GRU tensors (gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0)");
+    if ((rc = rn_conv(h, h->rn_gru_ih, "gru.weight_ih_l0", "", ""))) return rc;
+    std::vector<float> bias(G), bhn(H);
+    for (int j = 0; j < G; ++j) bias[j] = j < 2 * H ? (float)((double)bih->data[j] + (double)bhh->data[j]) : bih->data[j];
+    for (int j = 0; j < H; ++j) bhn[j] = bhh->data[2 * H + j];
+    if ((rc = dev_upload(h, &h->rn_gru_ih.bias, bias))) return rc;
+    if ((rc = dev_upload(h, &h->rn_gru_bhn, bhn))) return rc;
+    // packed row ut * 48 + g * 16 + j = W_hh row g * H + ut * 16 + j
+    std::vector<float> pk((size_t)G * H);
+    for (int ut = 0; ut < H / 16; ++ut)
+        for (int g = 0; g < 3; ++g)
+            for (int j = 0; j < 16; ++j)
+                memcpy(&pk[((size_t)ut * 48 + g * 16 + j) * H], &whh->data[((size_t)g * H + ut * 16 + j) * H], (size_t)H * 4);
+    if (h->bf16) {
+        std::vector<uint16_t> pb(pk.size());
+        for (size_t i = 0; i < pk.size(); ++i) pb[i] = to_h16(h, pk[i]);
+        uint16_t* d;
+        if ((rc = dev_upload(h, &d, pb))) return rc;
+        h->rn_gru_whh = d;
+    } else {
+        float* d;
+        if ((rc = dev_upload(h, &d, pk))) return rc;
+        h->rn_gru_whh = d;
+    }
+    return make_linear(h, h->rn_gru_fc, "fc_after_gru.weight", "fc_after_gru.bias");
+}
+
+int rawnet2_finalize(svhip_handle* h) {
+    int rc;
+    const bool conv = h->cfg.model == SVHIP_MODEL_RAWNET2_CONV;
+    if (conv) {
+        if ((rc = make_conv3_front(h))) return rc;
+    } else {
+        if ((rc = upload_f32(h, "ln.gamma", &h->rn_gamma))) return rc;
+        if ((rc = upload_f32(h, "ln.beta", &h->rn_beta))) return rc;
+        if ((rc = bake_sinc(h))) return rc;
+        if ((rc = make_bn(h, "first_bn", 128, &h->rn_fbn_scale, &h->rn_fbn_shift))) return rc;
+    }
+    int inpl = 128, bi = 0;
+    int T = h->rn_T1;
+    double fl = conv ? 2.0 * 128 * 3 * (double)T : 2.0 * 128 * 251 * (double)(h->cfg.samples - 250);
+    for (int li = 0; li < 6; ++li)
+        for (int b = 0; b < RN_LAYERS[li]; ++b, ++bi) {
+            svhip_handle::RnBlock& B = h->rn_blocks[bi];
+            const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
+            const int planes = RN_FILTERS[li];
+            B.cin = inpl; B.cout = planes; B.downsample = (b == RN_LAYERS[li] - 1); B.has_shortcut = inpl != planes;
+            if ((rc = make_bn(h, p + ".bn1", inpl, &B.bn1_scale, &B.bn1_shift))) return rc;
+            if ((rc = rn_conv(h, B.conv1, p + ".conv1.weight", "", p + ".bn2"))) return rc;
+            if ((rc = rn_conv(h, B.conv2, p + ".conv2.weight", "", ""))) return rc;
+            if (B.has_shortcut && (rc = rn_conv(h, B.shortcut, p + ".shortcut.0.weight", "", ""))) return rc;
+            if (B.has_shortcut && h->bf16 && B.conv2.K % 64 == 0 && inpl % 64 == 0) {
+                // conv2 and the shortcut share their output: [conv2 columns (tap-major) | shortcut columns] as one K axis
+                const HostTensor* w2 = getw(h, p + ".conv2.weight");           // (planes, planes, 3)
+                const HostTensor* ws = getw(h, p + ".shortcut.0.weight");      // (planes, inpl, 1)
+                const int K2 = B.conv2.K, Kt = K2 + inpl, Np = B.conv2.Np;
+                std::vector<uint16_t> pk((size_t)Np * Kt, 0);
+                for (int n = 0; n < planes; ++n) {
+                    for (int t = 0; t < 3; ++t)
+                        for (int c = 0; c < planes; ++c) pk[(size_t)n * Kt + t * planes + c] = to_h16(h, w2->data[((size_t)n * planes + c) * 3 + t]);
+                    for (int c = 0; c < inpl; ++c) pk[(size_t)n * Kt + K2 + c] = to_h16(h, ws->data[(size_t)n * inpl + c]);
+                }
+                uint16_t* d;
+                if ((rc = dev_upload(h, &d, pk))) return rc;
+                B.conv2sc_W = d;
+            }
+            if ((rc = upload_f32(h, p + ".afms.alpha", &B.alpha))) return rc;
+            if ((rc = make_linear(h, B.afms_fc, p + ".afms.fc.weight", p + ".afms.fc.bias"))) return rc;
+            {
+                const HostTensor* fw = getw(h, p + ".afms.fc.weight");                  // (planes, planes)
+                std::vector<float> t((size_t)planes * planes);
+                for (int n = 0; n < planes; ++n)
+                    for (int c = 0; c < planes; ++c) t[(size_t)c * planes + n] = fw->data[(size_t)n * planes + c];
+                if ((rc = dev_upload(h, &B.afms_fcT, t))) return rc;
+            }
+            fl += (double)T * (B.conv1.flops_per_row + B.conv2.flops_per_row + (B.has_shortcut ? B.shortcut.flops_per_row : 0.0));
+            fl += 2.0 * planes * planes;
+            if (B.downsample) T /= 3;
+            inpl = planes;
+        }
+    if (rn_is_gru(h->cfg.model)) {
+        if ((rc = rawnet2_finalize_gru(h))) return rc;
+        fl += (double)T * (h->rn_gru_ih.flops_per_row + 2.0 * 3 * RN_GRU_HIDDEN * RN_GRU_HIDDEN) + 2.0 * h->rn_gru_fc.N * h->rn_gru_fc.K;
+        h->flops_per_utt = fl;
+        return SVHIP_OK;
+    }
+    if ((rc = make_bn(h, "bn_before_agg", 512, &h->rn_agg_scale, &h->rn_agg_shift))) return rc;
+    if ((rc = rn_conv(h, h->rn_att0, "attention.0.weight", "attention.0.bias", "attention.2"))) return rc;
+    if ((rc = rn_conv(h, h->rn_att3, "attention.3.weight", "attention.3.bias", ""))) return rc;
+    if ((rc = make_linear(h, h->rn_fc, "fc.weight", "fc.bias"))) return rc;
+    fl += (double)T * (h->rn_att0.flops_per_row + h->rn_att3.flops_per_row) + 2.0 * h->rn_fc.N * h->rn_fc.K;
+    h->flops_per_utt = fl;
+    return SVHIP_OK;
+}
+
+int rawnet2_alloc(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    const size_t B = c.max_batch, e = h->esz;
+    int rc;
+    const bool conv = c.model == SVHIP_MODEL_RAWNET2_CONV;
+    h->rn_T1 = conv ? (c.samples - 3) / 3 + 1 : (c.samples - 250) / 3;       // conv1 (kernel 3, stride 3) | sinc (251 taps) + max_pool1d(3)
+    const size_t per_utt = (size_t)h->rn_T1 * 128;           // largest activation: (T1, 128); later stages shrink 3x per doubling
+    h->rn_buf_bytes = B * per_utt * e;
+    for (int i = 0; i < 6; ++i) {
+        if ((rc = actbuf(h, &h->rn_buf[i], B * per_utt))) return rc;
+        SV_HIP(h, hipMemset(off(h->rn_buf[i], h->rn_buf_bytes, 1), 0, 256));      // the zero tail (no kernel writes past the payload)
+    }
+    if (!conv && (rc = dev_alloc(h, &h->rn_stats, B * 2))) return rc;
+    if (!conv && (h->bf16 || h->x3)) {                                  // LayerNorm output in 16 bits, zero-tailed rows (operand of the 16-bit / split sinc kernels)
+        h->rn_Lp = (int)round_up(c.samples + RN_XN_TAIL, 64);
+        uint16_t* q;
+        if ((rc = dev_alloc(h, &q, (h->x3 ? 4 : 2) * B * (size_t)h->rn_Lp))) return rc;      // (F32X3: hi and lo parts of both copies)
+        h->rn_xn = q;
+    }
+    if ((rc = dev_alloc(h, &h->rn_part, B * (size_t)(rn_block128_ntiles(h->rn_T1) + 1) * 4 * 128))) return rc;
+    if ((rc = dev_alloc(h, &h->rn_mean, B * 512))) return rc;
+    if ((rc = dev_alloc(h, &h->rn_scratch, B * 16 * 512))) return rc;
+    if ((rc = dev_alloc(h, &h->rn_s, B * 512 * 2))) return rc;
+    int tf = h->rn_T1;
+    for (int i = 0; i < 6; ++i) tf /= 3;                      // six max_pool1d(3) stages follow the front-end
+    if (tf < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance too short for RawNet2 (%d samples)", c.samples);
+    if ((rc = dev_alloc(h, &h->rn_logits, B * (size_t)tf * 512))) return rc;
+    if (rn_is_gru(c.model)) {                                 // (256 x 14 frames: 11 MB of gate inputs)
+        h->rn_gru_T = tf;
+        if ((rc = dev_alloc(h, &h->rn_gru_gi, B * (size_t)tf * 3 * RN_GRU_HIDDEN))) return rc;
+        for (int i = 0; i < 2; ++i) if ((rc = dev_alloc(h, &h->rn_gru_hbuf[i], B * (size_t)RN_GRU_HIDDEN))) return rc;
+    }
+    if ((rc = dev_alloc(h, &h->rn_pooled, B * 1024))) return rc;
+    if (h->bf16) {          // K-slice partials of fc (K = 1 024: four slices of 256) at full batches, 16-bit handles
+        h->lin_part_per_utt = (size_t)4 * (size_t)std::max(128, c.embed_dim);
+        if ((rc = dev_alloc(h, &h->d_lin_part, B * h->lin_part_per_utt))) return rc;
+    }
+    return SVHIP_OK;
+}
+
+int rawnet2_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {
+    const int B = h->lastB;
+    if (n == "rn_x") { v.src = h->rn_dbg_x; v.rows = (size_t)B * h->rn_dbg_T; v.cols = v.ld = h->rn_dbg_C; }
+    else if (n == "rn_snap") { v.src = h->rn_snap; v.rows = (size_t)B * h->rn_snap_T; v.cols = v.ld = h->rn_snap_C; }
+    else if (n == "rn_pooled") { v.src = h->rn_pooled; v.rows = B; v.cols = v.ld = 1024; v.f32 = true; }
+    else if (n == "rn_gru_h" && rn_is_gru(h->cfg.model)) { v.src = h->rn_gru_h; v.rows = B; v.cols = v.ld = RN_GRU_HIDDEN; v.f32 = true; }
+    else if (n == "rn_gru_in" && rn_is_gru(h->cfg.model)) {
+        if (!h->rn_gru_in) SV_FAIL(h, SVHIP_ERR_STATE, "stage rn_gru_in: the last forward ran as several batch slices (SVHIP_LANES)");
+        v.src = h->rn_gru_in; v.rows = (size_t)B * h->rn_gru_T; v.cols = v.ld = 512;
+    }
+    else return unknown_stage(h, n);
+    return SVHIP_OK;
+}
 
 // conv2 + 1 x 1 shortcut of a RawNet2 block as ONE conv-gather GEMM: K = 3 * cout conv columns of hb, then cin columns of `pre`
 static GemmParams conv2sc_params(svhip_handle* h, const svhip_handle::RnBlock& K, const void* pre, const void* hb, void* o, int M, int T) {

@@ -1,6 +1,7 @@
-// api_rawnet3.hip — the RawNet3 forward of libsvhip (reference models/RawNet3.py:88-150, Bottle2neck: RawNet_baseline.py:71-159).
+// api_rawnet3.hip — RawNet3 in libsvhip (reference models/RawNet3.py:88-150, Bottle2neck: RawNet_baseline.py:71-159): its create rules,
+// weight names and packing, workspace, forward and stages.
 //
-// Buffers (alloc_workspace): three (B T0, 1024) activations P0 .. P2 and CAT (B T2, 3072), whose column thirds are the three stage
+// Buffers (rawnet3_alloc): three (B T0, 1024) activations P0 .. P2 and CAT (B T2, 3072), whose column thirds are the three stage
 // outputs [mp3(x1) | x2 | x3], so that layer4 reads the concatenation as one operand.
 //   front-end   y (fp32) in P1, x0 in its own buffer (kept for svhip_get_stage)
 //   layer1      residual(x0) -> P0, conv1(x0) -> P1, Res2Net steps P1 -> P2, conv3(P2) + P0 -> P1, pool 5 -> P2, AFMS -> x1 in P0
@@ -8,6 +9,9 @@
 //               mp3(x1) + x2 -> P1 (layer3's input and its identity residual)
 //   layer3      conv1(P1) and conv3 -> the head of P2, steps -> the next (B T2, 1024) of P2, AFMS -> x3 in CAT[2] (x1 stays in P0)
 //   layer4      relu(W4 CAT + b4) -> P1; context pooling (attention activation in P2) -> pooled; fc6 -> embeddings
+#include <algorithm>
+#include <cmath>
+
 #include "handle.h"
 
 namespace svhip {
@@ -59,6 +63,155 @@ int bottle2neck(svhip_handle* h, const svhip_handle::Rn3Layer& Ly, const void* x
 }
 
 }  // namespace
+
+int rawnet3_check(const svhip_config& c, const char*& err) {
+    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "RawNet3 runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_INVALID; }
+    if (c.channels != 0 && c.channels != 1024) { err = "RawNet3 is built for C = 1024 (channels 0 or 1024)"; return SVHIP_ERR_INVALID; }
+    if (c.samples < RN3_MIN_SAMPLES) {
+        err = "RawNet3 needs at least 541 samples: (L - 251) / 10 + 1 frames pooled by 5 and 3 must leave two (the unbiased variance)";
+        return SVHIP_ERR_INVALID;
+    }
+    return SVHIP_OK;
+}
+
+// RawNet3.MainModel's defaults (RawNet3.py:172-186): the 234 names of its state dict, the unused bn1.*, bn6.* and the pre-emphasis
+// buffer included (the filterbank's window_ / n_ buffers are read: the checkpoint's values are the ones the filters are built from)
+void rawnet3_spec(const svhip_config& c, WeightSpec& spec) {
+    const int64_t nOut = c.embed_dim;
+    spec["preprocess.0.flipped_filter"] = {1, 1, 2}; spec["preprocess.1.weight"] = {1}; spec["preprocess.1.bias"] = {1};
+    spec["conv1.filterbank.low_hz_"] = {C / 8, 1}; spec["conv1.filterbank.band_hz_"] = {C / 8, 1};
+    spec["conv1.filterbank.window_"] = {125}; spec["conv1.filterbank.n_"] = {1, 125};
+    spec_bn(spec, "bn1", C / 4);
+    for (int li = 1; li <= 3; ++li) {
+        const std::string p = "layer" + std::to_string(li);
+        const int64_t cin = li == 1 ? C / 4 : C;
+        spec[p + ".conv1.weight"] = {C, cin, 1}; spec[p + ".conv1.bias"] = {C};
+        spec_bn(spec, p + ".bn1", C);
+        for (int i = 0; i < 7; ++i) {
+            spec[p + ".convs." + std::to_string(i) + ".weight"] = {W, W, 3}; spec[p + ".convs." + std::to_string(i) + ".bias"] = {W};
+            spec_bn(spec, p + ".bns." + std::to_string(i), W);
+        }
+        spec[p + ".conv3.weight"] = {C, C, 1}; spec[p + ".conv3.bias"] = {C};
+        spec_bn(spec, p + ".bn3", C);
+        spec[p + ".afms.alpha"] = {C, 1}; spec[p + ".afms.fc.weight"] = {C, C}; spec[p + ".afms.fc.bias"] = {C};
+        if (cin != C) spec[p + ".residual.0.weight"] = {C, cin, 1};
+    }
+    spec["layer4.weight"] = {D, 3 * C, 1}; spec["layer4.bias"] = {D};
+    spec["attention.0.weight"] = {128, 3 * D, 1}; spec["attention.0.bias"] = {128};
+    spec_bn(spec, "attention.2", 128);
+    spec["attention.3.weight"] = {1, 128, 1}; spec["attention.3.bias"] = {1};
+    spec_bn(spec, "bn5", 2 * D);
+    spec["fc6.weight"] = {nOut, 2 * D}; spec["fc6.bias"] = {nOut};
+    spec_bn(spec, "bn6", nOut);
+}
+
+// ParamSincFB(256, 251).filters() (asteroid-filterbanks 0.4; its cos half is RawNet_baseline.py:339-357's formula) from the
+// checkpoint's low_hz_, band_hz_, window_ and n_, in fp64, stored tap-major [251][256]: cos filters 0..127, sin filters 128..255
+static int bake_sinc3(svhip_handle* h) {
+    const HostTensor *lo = getw(h, "conv1.filterbank.low_hz_"), *bd = getw(h, "conv1.filterbank.band_hz_"),
+                     *win = getw(h, "conv1.filterbank.window_"), *nn = getw(h, "conv1.filterbank.n_");
+    if (!lo || !bd || !win || !nn) SV_FAIL(h, SVHIP_ERR_MISSING, "missing conv1.filterbank tensors");
+    const int NF = RN3_FILTERS / 2, HK = 125;
+    std::vector<double> f((size_t)RN3_TAPS * RN3_FILTERS);
+    for (int i = 0; i < NF; ++i) {
+        const double low = 50.0 + std::fabs((double)lo->data[i]);
+        const double high = std::min(std::max(low + 50.0 + std::fabs((double)bd->data[i]), 50.0), 8000.0);
+        const double band = high - low;
+        for (int k = 0; k < HK; ++k) {
+            const double n = nn->data[k], w = win->data[k];
+            const double c = (std::sin(high * n) - std::sin(low * n)) / (n / 2) * w;     // cos half, left side
+            const double s = (std::cos(low * n) - std::cos(high * n)) / (n / 2) * w;     // sin half, left side
+            f[(size_t)k * RN3_FILTERS + i] = c / (2 * band);
+            f[(size_t)(RN3_TAPS - 1 - k) * RN3_FILTERS + i] = c / (2 * band);
+            f[(size_t)k * RN3_FILTERS + NF + i] = s / (2 * band);
+            f[(size_t)(RN3_TAPS - 1 - k) * RN3_FILTERS + NF + i] = -s / (2 * band);
+        }
+        f[(size_t)HK * RN3_FILTERS + i] = 2 * band / (2 * band);
+        f[(size_t)HK * RN3_FILTERS + NF + i] = 0.0;
+    }
+    if (!h->bf16) {
+        double* d;
+        int rc = dev_upload(h, &d, f);
+        h->rn3_filt = d;
+        return rc;
+    }
+    std::vector<float> ff(f.begin(), f.end());
+    float* d;
+    int rc = dev_upload(h, &d, ff);
+    h->rn3_filt = d;
+    return rc;
+}
+
+int rawnet3_finalize(svhip_handle* h) {
+    int rc;
+    const HostTensor* pf;
+    if ((rc = needw(h, "preprocess.0.flipped_filter", pf))) return rc;
+    h->rn3_pre[0] = pf->data[0]; h->rn3_pre[1] = pf->data[1];
+    if ((rc = upload_f32(h, "preprocess.1.weight", &h->rn3_in_w))) return rc;
+    if ((rc = upload_f32(h, "preprocess.1.bias", &h->rn3_in_b))) return rc;
+    if ((rc = bake_sinc3(h))) return rc;
+    const int T0 = h->rn3_T0;
+    double fl = 2.0 * RN3_FILTERS * RN3_TAPS * T0;
+    const int dil[3] = {2, 3, 4}, pool[3] = {5, 3, 1};
+    int T = T0;
+    for (int li = 0; li < 3; ++li) {
+        svhip_handle::Rn3Layer& Ly = h->rn3[li];
+        const std::string p = "layer" + std::to_string(li + 1);
+        if ((rc = make_conv(h, Ly.conv1, p + ".conv1.weight", p + ".conv1.bias", p + ".bn1", 1))) return rc;
+        for (int i = 0; i < 7; ++i)
+            if ((rc = make_conv(h, Ly.convs[i], p + ".convs." + std::to_string(i) + ".weight", p + ".convs." + std::to_string(i) + ".bias",
+                                p + ".bns." + std::to_string(i), dil[li]))) return rc;
+        if ((rc = make_conv(h, Ly.conv3, p + ".conv3.weight", p + ".conv3.bias", p + ".bn3", 1))) return rc;
+        Ly.has_residual = li == 0;
+        if (Ly.has_residual && (rc = make_conv(h, Ly.residual, p + ".residual.0.weight", "", "", 1))) return rc;
+        if ((rc = upload_f32(h, p + ".afms.alpha", &Ly.alpha))) return rc;
+        if ((rc = make_linear(h, Ly.afms_fc, p + ".afms.fc.weight", p + ".afms.fc.bias"))) return rc;
+        double per_row = Ly.conv1.flops_per_row + 7 * Ly.convs[0].flops_per_row + Ly.conv3.flops_per_row + (Ly.has_residual ? Ly.residual.flops_per_row : 0.0);
+        fl += (double)T * per_row + 2.0 * 1024 * 1024;
+        T /= pool[li];
+    }
+    if ((rc = make_conv(h, h->rn3_l4, "layer4.weight", "layer4.bias", "", 1))) return rc;
+    if ((rc = make_conv(h, h->rn3_att, "attention.0.weight", "", "attention.2", 1, 0, 1536))) return rc;
+    if ((rc = make_linear(h, h->rn3_att_ctx, "attention.0.weight", "attention.0.bias", 1536, 3 * 1536))) return rc;
+    if ((rc = upload_f32(h, "attention.3.weight", &h->rn3_w2))) return rc;
+    if ((rc = upload_f32(h, "attention.3.bias", &h->rn3_b2))) return rc;
+    if ((rc = make_bn(h, "bn5", 2 * 1536, &h->rn3_bn5_scale, &h->rn3_bn5_shift))) return rc;
+    if ((rc = make_linear(h, h->rn3_fc6, "fc6.weight", "fc6.bias"))) return rc;
+    fl += (double)T * (h->rn3_l4.flops_per_row + h->rn3_att.flops_per_row + 2.0 * 128) + 2.0 * 128 * 3072 + 2.0 * h->rn3_fc6.N * h->rn3_fc6.K;
+    h->flops_per_utt = fl;
+    return SVHIP_OK;
+}
+
+int rawnet3_alloc(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    const size_t B = c.max_batch;
+    int rc;
+    // three (B T0, 1024) activation buffers carry layer1 (rawnet3_forward_part); the later stages reuse them
+    h->rn3_T0 = rn3_frames(c.samples);
+    const size_t M0 = B * (size_t)h->rn3_T0, T2 = (size_t)(h->rn3_T0 / 5 / 3);
+    if (T2 < 2) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance too short for RawNet3 (%d samples)", c.samples);
+    for (int i = 0; i < 3; ++i) if ((rc = actbuf(h, &h->rn3_buf[i], M0 * C))) return rc;
+    if ((rc = actbuf(h, &h->rn3_cat, B * T2 * 3 * C))) return rc;
+    if ((rc = actbuf(h, &h->rn3_x0, M0 * RN3_FILTERS))) return rc;
+    if ((rc = dev_alloc(h, &h->rn3_stats, B * 2))) return rc;
+    if ((rc = dev_alloc(h, &h->rn3_mean, B * 1024))) return rc;
+    if ((rc = dev_alloc(h, &h->rn3_gate, B * 1024))) return rc;
+    if ((rc = dev_alloc(h, &h->rn3_tstat, B * 3072))) return rc;
+    if ((rc = dev_alloc(h, &h->rn3_ctx, B * 128))) return rc;
+    if ((rc = dev_alloc(h, &h->rn3_logit, B * T2))) return rc;
+    if ((rc = dev_alloc(h, &h->rn3_pooled, B * 3072))) return rc;
+    return SVHIP_OK;
+}
+
+int rawnet3_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // rn3_front, rn3_layer1 .. 3, rn3_layer4, rn3_pooled
+    static const char* kStages[5] = {"rn3_front", "rn3_layer1", "rn3_layer2", "rn3_layer3", "rn3_layer4"};
+    int i = 0;
+    while (i < 5 && n != kStages[i]) ++i;
+    if (n == "rn3_pooled") { v.src = h->rn3_pooled; v.rows = h->lastB; v.cols = v.ld = 3072; v.f32 = true; }
+    else if (i == 5) return unknown_stage(h, n);
+    else { v.src = h->rn3_stage[i]; v.rows = (size_t)h->lastB * h->rn3_stage_T[i]; v.cols = h->rn3_stage_C[i]; v.ld = h->rn3_stage_ld[i]; }
+    return SVHIP_OK;
+}
 
 // RawNet3.forward on device-resident waveforms (B, L), enqueued on h->cur (one slice: b0 is 0)
 static int rawnet3_forward_part(svhip_handle* h, const float* d_wav, int b0, int B) {

@@ -1,8 +1,9 @@
-// api_titanet.hip — the TitaNet forward of libsvhip (reference models/TitaNet.py:184-431, blocks/titanet_blocks.py).
+// api_titanet.hip — TitaNet in libsvhip (reference models/TitaNet.py:184-431, blocks/titanet_blocks.py): its create rules, weight names
+// and packing, workspace, forward and stages.
 //
-// Buffers (alloc_workspace): six (B T, H) activations — PRO (prolog output), X (block output), D0 (block 0's first depthwise output),
+// Buffers (titanet_alloc): six (B T, H) activations — PRO (prolog output), X (block output), D0 (block 0's first depthwise output),
 // D (depthwise outputs), S (pointwise outputs), K (skip) — then ENC (B T, 1536), ATT (B T, 128) and the fp32 energies (B T, 1536).
-// Every BatchNorm is folded into the conv before it (finalize_titanet), so the GEMM epilogues apply at most a ReLU.
+// Every BatchNorm is folded into the conv before it (titanet_finalize), so the GEMM epilogues apply at most a ReLU.
 //
 // One mega-block (TitaNet.py:293-318) on x:
 //   skip     K = BN(conv1x1(x))                                  conv_gemm
@@ -12,10 +13,172 @@
 //                                                              when its kernel writes them; otherwise colmean)
 //   SE       g = sigmoid(W2 relu(W1 mean_t S))                   se_mlp (zero biases)
 //   tail     X = relu(K + g S) and D = dw_1'(X) + b' of the next block in the same pass      tn_mega_tail
+#include <cmath>
+#include <cstdlib>
+
 #include "handle.h"
 
 namespace svhip {
 
+int titanet_check(const svhip_config& c, const char*& err) {
+    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "TitaNet runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_UNSUPPORTED; }
+    if (!tn_kernel_size(c.channels)) { err = "TitaNet is built for H = 256 / 512 / 1024 (sizes s / m / l: channels)"; return SVHIP_ERR_INVALID; }
+    if (c.log_input || c.input_norm) { err = "TitaNet reads the mel power as it is: log_input and input_norm must be 0"; return SVHIP_ERR_INVALID; }
+    if (c.embed_dim <= 0) { err = "TitaNet needs embed_dim > 0"; return SVHIP_ERR_INVALID; }
+    return SVHIP_OK;
+}
+
+// TitaNet.MainModel (TitaNet.py:124-159,202-318,321-431): the names of its state dict for SVHIP_TITANET_MAX_BLOCKS mega-blocks; a checkpoint
+// holds the first n of them (titanet_finalize)
+static void tn_block_spec(int64_t H, int64_t k, const std::string& p, WeightSpec& spec) {
+    for (int j = 0; j < 3; ++j) {
+        const std::string q = p + "sub_blocks." + std::to_string(j) + ".conv_block.";
+        spec[q + "0.conv.0.weight"] = {H, 1, k}; spec[q + "0.conv.0.bias"] = {H};
+        spec[q + "0.conv.1.weight"] = {H, H, 1}; spec[q + "0.conv.1.bias"] = {H};
+        spec_bn(spec, q + "1", H);
+    }
+    spec[p + "sub_blocks.3.excitation.0.weight"] = {H / 16, H}; spec[p + "sub_blocks.3.excitation.2.weight"] = {H, H / 16};
+    spec[p + "skip_connection.0.weight"] = {H, H, 1}; spec[p + "skip_connection.0.bias"] = {H};
+    spec_bn(spec, p + "skip_connection.1", H);
+}
+
+void titanet_spec(const svhip_config& c, WeightSpec& spec) {
+    const int64_t H = c.channels, k = tn_kernel_size(c.channels), D = 1536, nOut = c.embed_dim;
+    spec["encoder.prolog.conv_block.0.weight"] = {H, (int64_t)c.n_mels, 3}; spec["encoder.prolog.conv_block.0.bias"] = {H};
+    spec_bn(spec, "encoder.prolog.conv_block.1", H);
+    for (int i = 0; i < SVHIP_TITANET_MAX_BLOCKS; ++i) tn_block_spec(H, k, "encoder.mega_blocks." + std::to_string(i) + ".", spec);
+    spec["encoder.epilog.conv_block.0.weight"] = {D, H, 1}; spec["encoder.epilog.conv_block.0.bias"] = {D};
+    spec_bn(spec, "encoder.epilog.conv_block.1", D);
+    spec["decoder.pool.0.in_linear.weight"] = {128, D}; spec["decoder.pool.0.in_linear.bias"] = {128};
+    spec["decoder.pool.0.out_linear.weight"] = {D, 128}; spec["decoder.pool.0.out_linear.bias"] = {D};
+    spec_bn(spec, "decoder.pool.1", 2 * D);
+    spec["decoder.linear.0.weight"] = {nOut, 2 * D}; spec["decoder.linear.0.bias"] = {nOut};
+    spec_bn(spec, "decoder.linear.1", nOut);
+}
+
+// contiguous mega-block indices loaded from 0
+static int titanet_blocks_loaded(const svhip_handle* h) {
+    int n = 0;
+    while (n < SVHIP_TITANET_MAX_BLOCKS) {
+        const std::string p = "encoder.mega_blocks." + std::to_string(n) + ".";
+        auto it = h->host_w.lower_bound(p);
+        if (it == h->host_w.end() || it->first.compare(0, p.size(), p) != 0) break;
+        ++n;
+    }
+    return n;
+}
+
+// conv (N, cin, taps) + bias followed directly by BatchNorm1d(eval, eps 1e-5): the BN folded into the conv, W' = s W, b' = s b + t (double
+// arithmetic on the host), packed as a plain conv layer
+static int make_conv_bn(svhip_handle* h, ConvLayer& L, const std::string& conv, const std::string& bnp) {
+    const HostTensor *w, *b;
+    std::vector<double> s, t;
+    int rc;
+    if ((rc = needw(h, conv + ".weight", w)) || (rc = needw(h, conv + ".bias", b)) || (rc = bn_fold(h, bnp, (int)w->shape[0], s, t))) return rc;
+    const int64_t N = w->shape[0], per = w->numel() / N;
+    HostTensor fw = *w;
+    std::vector<float> fb(N);
+    for (int64_t n = 0; n < N; ++n) {
+        for (int64_t i = 0; i < per; ++i) fw.data[n * per + i] = (float)(s[n] * (double)w->data[n * per + i]);
+        fb[n] = (float)(s[n] * (double)b->data[n] + t[n]);
+    }
+    if ((rc = make_conv(h, L, fw, &fb, 1))) return rc;
+    L.scale = h->d_ones;          // (an identity affine: the persistent 16-bit GEMM takes layers that carry all three vectors)
+    L.shift = h->d_zeros;
+    return SVHIP_OK;
+}
+
+int titanet_finalize(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    const int H = c.channels, k = tn_kernel_size(H), Hh = H / 16, D = 1536, nOut = c.embed_dim, T = h->T;
+    const int nb = titanet_blocks_loaded(h);
+    if (nb == 0) SV_FAIL(h, SVHIP_ERR_MISSING, "no mega-block was loaded (encoder.mega_blocks.0.*)");
+    for (auto& kv : h->host_w)          // a gap: tensors of a block beyond the contiguous run
+        if (kv.first.rfind("encoder.mega_blocks.", 0) == 0 && atoi(kv.first.c_str() + 20) >= nb)
+            SV_FAIL(h, SVHIP_ERR_MISSING, "%s is loaded but mega-block %d is missing (blocks are counted contiguously from 0)", kv.first.c_str(), nb);
+    {
+        WeightSpec bspec;
+        for (int i = 0; i < nb; ++i) tn_block_spec(H, k, "encoder.mega_blocks." + std::to_string(i) + ".", bspec);
+        for (auto& kv : bspec)
+            if (!h->host_w.count(kv.first) && kv.first.find("num_batches_tracked") == std::string::npos)
+                SV_FAIL(h, SVHIP_ERR_MISSING, "tensor %s was never loaded (mega-block count %d)", kv.first.c_str(), nb);
+    }
+    h->tn_k = k;
+    h->tn.assign(nb, svhip_handle::TnBlock{});
+    int rc;
+    if ((rc = make_conv_bn(h, h->tn_prolog, "encoder.prolog.conv_block.0", "encoder.prolog.conv_block.1"))) return rc;
+    double fl = h->tn_prolog.flops_per_row;
+    for (int i = 0; i < nb; ++i) {
+        svhip_handle::TnBlock& Bk = h->tn[i];
+        const std::string p = "encoder.mega_blocks." + std::to_string(i) + ".";
+        for (int j = 0; j < 3; ++j) {
+            const std::string q = p + "sub_blocks." + std::to_string(j) + ".conv_block.";
+            const HostTensor* dw = getw(h, q + "0.conv.0.weight");            // (H, 1, k)
+            if (!dw || dw->shape.size() != 3 || dw->shape[2] != k) SV_FAIL(h, SVHIP_ERR_INVALID, "%s0.conv.0.weight: depthwise kernel size must be %d", q.c_str(), k);
+            std::vector<float> tw((size_t)k * H);
+            for (int cch = 0; cch < H; ++cch)
+                for (int t = 0; t < k; ++t) tw[(size_t)t * H + cch] = dw->data[(size_t)cch * k + t];
+            if ((rc = dev_upload(h, &Bk.dw_w[j], tw))) return rc;
+            if ((rc = upload_f32(h, q + "0.conv.0.bias", &Bk.dw_b[j]))) return rc;
+            if ((rc = make_conv_bn(h, Bk.pw[j], q + "0.conv.1", q + "1"))) return rc;
+            fl += Bk.pw[j].flops_per_row + 2.0 * k * H;
+        }
+        if ((rc = make_conv_bn(h, Bk.skip, p + "skip_connection.0", p + "skip_connection.1"))) return rc;
+        fl += Bk.skip.flops_per_row;
+        const HostTensor *w1 = getw(h, p + "sub_blocks.3.excitation.0.weight"), *w2 = getw(h, p + "sub_blocks.3.excitation.2.weight");
+        std::vector<float> m1(w1->data), m2((size_t)Hh * H);
+        for (int cch = 0; cch < H; ++cch)
+            for (int n = 0; n < Hh; ++n) m2[(size_t)n * H + cch] = w2->data[(size_t)cch * Hh + n];
+        if ((rc = dev_upload(h, &Bk.se1, m1))) return rc;
+        if ((rc = dev_upload(h, &Bk.se2T, m2))) return rc;
+        if (h->bf16) {
+            if ((rc = upload_h16(h, m1, &Bk.se1_bf))) return rc;
+            if ((rc = upload_h16(h, m2, &Bk.se2T_bf))) return rc;
+        }
+    }
+    if ((rc = make_conv_bn(h, h->tn_epilog, "encoder.epilog.conv_block.0", "encoder.epilog.conv_block.1"))) return rc;
+    if ((rc = make_conv(h, h->tn_att_in, "decoder.pool.0.in_linear.weight", "decoder.pool.0.in_linear.bias", "", 1))) return rc;
+    if ((rc = make_conv(h, h->tn_att_out, "decoder.pool.0.out_linear.weight", "decoder.pool.0.out_linear.bias", "", 1))) return rc;
+    if ((rc = make_bn(h, "decoder.pool.1", 2 * D, &h->tn_pbn_scale, &h->tn_pbn_shift))) return rc;
+    {
+        // decoder.linear = Linear(3072, nOut) + BatchNorm1d(nOut): folded into one fp32 linear
+        const HostTensor *w = getw(h, "decoder.linear.0.weight"), *b = getw(h, "decoder.linear.0.bias");
+        std::vector<double> s, t;
+        if ((rc = bn_fold(h, "decoder.linear.1", nOut, s, t))) return rc;
+        std::vector<float> fw((size_t)nOut * 2 * D), fb(nOut);
+        for (int n = 0; n < nOut; ++n) {
+            for (int i = 0; i < 2 * D; ++i) fw[(size_t)n * 2 * D + i] = (float)(s[n] * (double)w->data[(size_t)n * 2 * D + i]);
+            fb[n] = (float)(s[n] * (double)b->data[n] + t[n]);
+        }
+        h->tn_fc.N = nOut; h->tn_fc.K = 2 * D;
+        if ((rc = dev_upload(h, &h->tn_fc.W, fw))) return rc;
+        if ((rc = dev_upload(h, &h->tn_fc.bias, fb))) return rc;
+    }
+    fl += h->tn_epilog.flops_per_row + h->tn_att_in.flops_per_row + h->tn_att_out.flops_per_row;
+    h->flops_per_utt = (double)T * fl + 2.0 * nOut * 2 * D;
+    return SVHIP_OK;
+}
+
+int titanet_alloc(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    const size_t B = c.max_batch, M = B * h->T, H = c.channels;
+    int rc;
+    // six (B T, H) activation buffers, the encoder output, the attention activation and energies
+    if ((rc = actbuf(h, &h->X_in, M * c.n_mels))) return rc;
+    for (int i = 0; i < 6; ++i) if ((rc = actbuf(h, &h->tn_buf[i], M * H))) return rc;
+    if ((rc = actbuf(h, &h->tn_enc, M * 1536))) return rc;
+    if ((rc = actbuf(h, &h->tn_att, M * 128))) return rc;
+    if ((rc = dev_alloc(h, &h->tn_logits, M * 1536))) return rc;
+    if ((rc = dev_alloc(h, &h->tn_mean, B * H))) return rc;
+    if ((rc = dev_alloc(h, &h->tn_gate, B * H))) return rc;
+    if ((rc = dev_alloc(h, &h->tn_pool_raw, B * 3072))) return rc;
+    if ((rc = dev_alloc(h, &h->tn_pool, B * 3072))) return rc;
+    if (h->bf16) {          // the third pointwise GEMM's column-sum partials (the SE squeeze)
+        h->colsum_region = (int64_t)((M + 255) / 256 + 2) * 16 * H;
+        if ((rc = dev_alloc(h, &h->d_colsum, (size_t)2 * h->colsum_region))) return rc;
+    }
+    return SVHIP_OK;
+}
 static int titanet_forward_part(svhip_handle* h, const float* d_feat, int b0, int B) {
     (void)b0;
     const svhip_config& c = h->cfg;
@@ -93,5 +256,16 @@ static int titanet_forward_part(svhip_handle* h, const float* d_feat, int b0, in
 }
 
 int titanet_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, titanet_forward_part, d_feat, B, 1, B); }
+
+int titanet_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // tn_prolog, tn_dw0, tn_mega_last, tn_enc, tn_pool
+    const int H = h->cfg.channels;
+    if (n == "tn_prolog") { v.src = h->tn_buf[0]; v.cols = v.ld = H; }
+    else if (n == "tn_mega_last") { v.src = h->tn_buf[1]; v.cols = v.ld = H; }
+    else if (n == "tn_dw0") { v.src = h->tn_buf[2]; v.cols = v.ld = H; }
+    else if (n == "tn_enc") { v.src = h->tn_enc; v.cols = v.ld = 1536; }
+    else if (n == "tn_pool") { v.src = h->tn_pool; v.rows = h->lastB; v.cols = v.ld = 3072; v.f32 = true; }
+    else return unknown_stage(h, n);
+    return SVHIP_OK;
+}
 
 }  // namespace svhip

@@ -6,7 +6,7 @@
 //
 //   r = sigmoid(gi_r + W_hr h),  z = sigmoid(gi_z + W_hz h),  n = tanh(gi_n + r (W_hn h + b_hn)),  h' = (1 - z) n + z h
 //
-// W_hh is packed at load time (api_weights.hip) with the gates interleaved per tile of 16 hidden units: row ut * 48 + g * 16 + j holds
+// W_hh is packed at load time (api_rawnet2.hip) with the gates interleaved per tile of 16 hidden units: row ut * 48 + g * 16 + j holds
 // W_hh row g * 1024 + ut * 16 + j.  A workgroup owns one tile of 16 units and 32 batch rows and keeps r, z and n of the same units in its
 // accumulators, so the epilogue needs nothing from another workgroup.  Its four waves split K (256 each): a wave's chain of dependent
 // L2 loads is a quarter as long, and eight waves per CU hide their latency (one wave over the whole K: 26.6 us per step at B = 256, f16);

@@ -364,7 +364,6 @@ int run(svhip_handle* h, const char* label, double flops, F&& launch) {
     return SVHIP_OK;
 }
 
-inline bool is_rawnet2(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_CONV || model == SVHIP_MODEL_RAWNET2_GRU; }
 inline bool rn_is_sinc(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_GRU; }     // front_proc='sinc'
 inline bool rn_is_gru(int model) { return model == SVHIP_MODEL_RAWNET2_GRU; }                                       // aggregate='gru'
 inline int tn_kernel_size(int H) { return H == 256 ? 3 : H == 512 ? 7 : H == 1024 ? 11 : 0; }      // TitaNet s / m / l (TitaNet.py:152-157)
@@ -374,16 +373,50 @@ inline int rn3_frames(int L) { return (L - RN3_TAPS) / RN3_STRIDE + 1; }      //
 inline void* off(void* base, size_t elems, int esz) { return reinterpret_cast<char*>(base) + elems * esz; }
 inline const void* off(const void* base, size_t elems, int esz) { return reinterpret_cast<const char*>(base) + elems * esz; }
 
-// api_weights.hip: the front-end tables, the expected weight names / shapes, weight packing, the workspace
+// api_weights.hip: what several models share when a handle is created and its weights are loaded — the front-end tables, the 16-bit
+// and split conversions, the weight packers and the common workspace (d_wav, d_feat, status, ones / zeros)
+using WeightSpec = std::map<std::string, std::vector<int64_t>>;      // the expected weight names and shapes of a model
 int build_fbank_tables(svhip_handle* h);
-void model_spec(const svhip_config& c, std::map<std::string, std::vector<int64_t>>& spec);
-int finalize_ecapa(svhip_handle* h);
-int finalize_rawnet2(svhip_handle* h);
-int finalize_rawnet3(svhip_handle* h);
-int finalize_titanet(svhip_handle* h);
-int titanet_blocks_loaded(const svhip_handle* h);      // contiguous mega-block indices loaded from 0
-int finalize_conformer(svhip_handle* h);
 int alloc_workspace(svhip_handle* h);
+uint16_t f32_to_bf16_rne(float f);
+uint32_t x3_split_word(float v);                                     // (hi plane << 16) | lo plane, x3_t of common.h
+uint16_t to_h16(const svhip_handle* h, float f);                     // a weight in the handle's 16-bit storage type
+const HostTensor* getw(svhip_handle* h, const std::string& name);    // a loaded tensor, or null
+int needw(svhip_handle* h, const std::string& name, const HostTensor*& t);   // ... or SVHIP_ERR_MISSING "missing tensor <name>"
+void spec_bn(WeightSpec& spec, const std::string& p, int64_t n);     // the five tensors of BatchNorm1d(n) `p`
+// BatchNorm1d(eval, eps 1e-5) `p` as y = s x + t per channel, in double: s = gamma / sqrt(var + eps), t = beta - mean s
+int bn_fold(svhip_handle* h, const std::string& p, int n, std::vector<double>& s, std::vector<double>& t);
+int make_bn(svhip_handle* h, const std::string& p, int n, float** scale, float** shift);        // bn_fold as fp32 device vectors
+// conv weight (N, cin, taps) columns [c_lo, c_hi) packed to [Np][Kp], k = tap * cin' + c, in the compute type (F32X3: and its split
+// layouts); rn_s32: RawNet2's rule for the S32 layout of r2_step.hip's modes 1 / 2
+int make_conv(svhip_handle* h, ConvLayer& L, const HostTensor& w, const std::vector<float>* bias, int dil, int c_lo = 0, int c_hi = -1,
+              bool rn_s32 = false);
+int make_conv(svhip_handle* h, ConvLayer& L, const std::string& wname, const std::string& bname, const std::string& bnname, int dil,
+              int c_lo = 0, int c_hi = -1, bool rn_s32 = false);        // by name; bname / bnname empty: no bias / no BatchNorm epilogue
+int make_linear(svhip_handle* h, LinearLayer& L, const std::string& wname, const std::string& bname, int c_lo = 0, int c_hi = -1);
+int upload_f32(svhip_handle* h, const std::string& name, float** dst);
+int upload_h16(svhip_handle* h, const std::vector<float>& m, void** dst);      // as bf16
+int actbuf(svhip_handle* h, void** dst, size_t elems);               // an activation buffer: elems in the storage type, 256 spare bytes
+
+// One row per model id (kModels, api.hip): everything outside a model's own file needs to know about it.  Null entries: the model has
+// no such step.
+struct StageView { const void* src; size_t rows, cols, ld; bool f32; };   // svhip_get_stage: rows x cols at row stride ld
+using CheckFn = int(const svhip_config& c, const char*& err);       // svhip_create's rules for the model: SVHIP_OK, or a code and err
+using SpecFn = void(const svhip_config& c, WeightSpec& spec);
+using HandleFn = int(svhip_handle* h);
+using EmbedFn = int(svhip_handle* h, const float* in, int B);       // device input (B, L) or (B, n_mels, T) -> h->d_emb
+using StageFn = int(svhip_handle* h, const std::string& name, bool fill, StageView& v);     // fill: the caller reads the data next
+struct ModelOps {
+    int model;
+    CheckFn* check;
+    SpecFn* spec;
+    HandleFn *finalize, *alloc;              // alloc: the model's part of the workspace
+    EmbedFn *embed_wave, *embed_feat;        // embed_feat: from the mel power; null for a waveform model
+    StageFn* stage;
+    int max_lanes;                           // cap of SVHIP_LANES
+    const char* optional_prefix;             // spec names that finalize may find absent (it checks them itself)
+};
+int unknown_stage(svhip_handle* h, const std::string& name);         // SVHIP_ERR_INVALID "unknown stage <name>"
 
 // api_gemm.hip: the GEMM of one conv layer.  conv_plan is the one place that decides its kernel: conv_gemm launches what it returns,
 // and the producers of an operand ask it too, so that they write the layout that kernel reads.
@@ -404,11 +437,13 @@ int conv_gemm(svhip_handle* h, const ConvLayer& L, const GemmParams& p, const vo
 using ForwardPart = int (*)(svhip_handle* h, const float* in, int b0, int B);
 int forward_lanes(svhip_handle* h, ForwardPart part, const float* in, int B, int lanes, int per);
 
-// api_ecapa.hip, api_rawnet2.hip, api_rawnet3.hip, api_titanet.hip, api_conformer.hip: the whole-batch forwards
-int ecapa_forward(svhip_handle* h, const float* d_feat, int B);
-int rawnet2_forward(svhip_handle* h, const float* d_wav, int B);
-int rawnet3_forward(svhip_handle* h, const float* d_wav, int B);
-int titanet_forward(svhip_handle* h, const float* d_feat, int B);      // from the mel power (B, n_mels, T)
-int conformer_forward(svhip_handle* h, const float* d_feat, int B);    // from the mel power (B, n_mels, T)
+// api_ecapa.hip, api_rawnet2.hip (the three RawNet2 models), api_rawnet3.hip, api_titanet.hip, api_conformer.hip: each model's functions
+CheckFn ecapa_check, rawnet2_check, rawnet3_check, titanet_check, conformer_check;
+SpecFn ecapa_spec, rawnet2_spec, rawnet3_spec, titanet_spec, conformer_spec;
+HandleFn ecapa_finalize, rawnet2_finalize, rawnet3_finalize, titanet_finalize, conformer_finalize;
+HandleFn ecapa_alloc, rawnet2_alloc, rawnet3_alloc, titanet_alloc, conformer_alloc;
+EmbedFn ecapa_embed_wave, rawnet2_forward, rawnet3_forward;                    // from the waveform
+EmbedFn ecapa_forward, titanet_forward, conformer_forward;                     // from the mel power
+StageFn ecapa_stage, rawnet2_stage, rawnet3_stage, titanet_stage, conformer_stage;
 
 }  // namespace svhip

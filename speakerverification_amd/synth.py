@@ -311,7 +311,7 @@ def rawnet3_sinc_buffers():
 def rawnet3_sinc_filters(low_hz_, band_hz_, window_, n_, sample_rate=16000.0, min_low_hz=50.0, min_band_hz=50.0):
     """ParamSincFB.filters() (asteroid-filterbanks 0.4.x, the filterbank RawNet3.py:35-41 instantiates) in float64 numpy: the
     (256, 251) band-pass bank, 128 cos filters then 128 sin filters.  The cos half is RawNet_baseline.py:339-357's formula; the
-    library bakes the same arithmetic at finalize (api_weights.hip)."""
+    library bakes the same arithmetic at finalize (api_rawnet2.hip)."""
     low = min_low_hz + np.abs(np.asarray(low_hz_, np.float64).reshape(-1, 1))
     high = np.clip(low + min_band_hz + np.abs(np.asarray(band_hz_, np.float64).reshape(-1, 1)), min_low_hz, sample_rate / 2)
     band = (high - low)[:, 0]

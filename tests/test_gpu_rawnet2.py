@@ -565,7 +565,7 @@ def test_symmetric_sinc_form_matches_the_251_tap_kernel():
     of 251, the operand formed in registers from a forward and a (half-reversed) backward fragment read, one extra fp16 rounding per sum —
     (rn_sinc_kernel<f16, SYM>; option rn_sinc_full keeps the 251-tap kernel).  Front-end output (stage rn_x) and embeddings of the two forms
     on the same handle; both against the exact-fp32 handle at the fp16 bars; the symmetric table exists only if every baked filter IS
-    symmetric bit for bit (api_weights.hip, bake_sinc)."""
+    symmetric bit for bit (api_rawnet2.hip, bake_sinc)."""
     B, L = 5, 32000
     sd = synth.synth_state_dict(synth.rawnet2_param_spec(nOut=320), seed=3)
     wav = synth.synth_waveforms(B, L, seed=9)

@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from speakerverification_amd import synth
+from speakerverification_amd import _lib, synth
 from speakerverification_amd.engine import Engine
 from speakerverification_amd.models import RawNet2_custom, Raw_ECAPA_sinc_gru
 
@@ -68,6 +68,10 @@ def test_recurrence_against_float64(compute, L):
     eng.embed_wave(synth.synth_waveforms(B, L, seed=3))
     x = eng.get_stage("rn_gru_in").reshape(B, -1, 512)
     h = eng.get_stage("rn_gru_h").reshape(B, 1024)
+    for other in ("blocks.1", "mfa", "asp", "input", "rn3_pooled", "tn_pool", "cf_pool"):     # other models' stages: not this handle's
+        with pytest.raises(_lib.SvhipError, match="unknown stage") as ei:
+            eng.get_stage(other)
+        assert ei.value.code == -1, other                                                  # SVHIP_ERR_INVALID
     T = x.shape[1]
     assert T == {2438: 1, 32000: 14, 96000: 43}[L]
     want = gru_f64(x, _sd(L, 2))
