@@ -158,7 +158,8 @@ int svhip_finalize_weights(svhip_handle* h);
 int svhip_fbank(svhip_handle* h, const float* wav, int32_t B, int32_t L, float* mel_out, int32_t flags);
 
 /* Model forward.  Replaces: self.__S__.forward(inp) (src/model.py:119-121) ==
- * ECAPA_TDNN.forward (models/ECAPA_TDNN.py:460-502) on features (B, n_mels, T), or
+ * ECAPA_TDNN.forward (models/ECAPA_TDNN.py:460-502) on features (B, n_mels, T) — T >= 5: block 3 reflect-pads 4 frames (a shorter
+ * L is refused at svhip_create with SVHIP_ERR_INVALID) — or
  * RawNet2.forward (models/RawNet2_custom.py:161-227) on waveforms (B, L).  emb_out (B, nOut) fp32
  * (the Python shim applies the reference's squeeze()). */
 int svhip_embed_features(svhip_handle* h, const float* feat, int32_t B, int32_t T, float* emb_out, int32_t flags);
@@ -300,7 +301,11 @@ int svhip_synth_waveforms(svhip_handle* h, uint64_t seed, int64_t first_utt, int
 
 /* Introspection used by tests and bench.py (not part of the reference's surface).
  *   get_stage    : copy an intermediate activation of the LAST forward to host as fp32, frame-major
- *                  (B, T, C).  Names: "input","blocks.0".."blocks.3","mfa","asp","asp_bn" (ECAPA); "rn_gru_in" (the (B T, 512) GRU
+ *                  (B, T, C).  Names: "input","blocks.0".."blocks.3","mfa","asp","asp_bn" (ECAPA), and of block 3 "blocks.3.tdnn1",
+ *                  "blocks.3.res2net", "blocks.3.tdnn2" (B T, C), "blocks.3.se_gate" (B, C), then "asp_gstats" (B, 6C: mean | std)
+ *                  and "asp_att" (B T, 128: asp.tdnn after tanh) — SVHIP_ERR_STATE where the last forward's route did not keep the
+ *                  value (blocks.3.tdnn1 of SVHIP_F32X3 handles whose tdnn1 wrote its first chunks in the split layout only; "mel"
+ *                  after the fused front-end); "rn_gru_in" (the (B T, 512) GRU
  *                  input of a one-slice forward) and "rn_gru_h" (the (B, 1024) fp32 last GRU state) of SVHIP_MODEL_RAWNET2_GRU;
  *                  "tn_prolog" (B T, H), "tn_dw0" (block 0's first depthwise output, its bias included), "tn_mega_last" (the last
  *                  mega-block's output), "tn_enc" (B T, 1536) and "tn_pool" (B, 3072, after BN) of SVHIP_MODEL_TITANET;

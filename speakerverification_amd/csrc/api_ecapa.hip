@@ -8,6 +8,10 @@ namespace svhip {
 int ecapa_check(const svhip_config& c, const char*& err) {
     if (c.channels <= 0 || c.channels % 64 != 0) { err = "ECAPA channels must be a positive multiple of 64"; return SVHIP_ERR_INVALID; }
     if (c.compute == SVHIP_F16) { err = "SVHIP_F16 is RawNet2's 16-bit mode (ECAPA's is SVHIP_BF16)"; return SVHIP_ERR_UNSUPPORTED; }
+    if (c.hop_length > 0 && c.samples / c.hop_length + 1 <= 4) {
+        err = "ECAPA needs T = L / hop + 1 >= 5 frames: block 3 reflect-pads 4 frames on each side of every utterance";
+        return SVHIP_ERR_INVALID;
+    }
     return SVHIP_OK;
 }
 
@@ -239,6 +243,7 @@ static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, 
         }
         GemmPlan g1;
         if ((rc = conv_gemm(h, h->tdnn1[i], p1, xin32, ldin32, &g1))) return rc;
+        if (i == 2) { h->h2_is_s32 = r2_plan; h->h1_split = r2_plan && g1.side; }      // (what svhip_get_stage can read back of block 3)
         if (r2_plan) {
             if (!g1.side) {
                 if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(H1), C, h2s, M, C8, st, C); }))) return rc;
@@ -387,6 +392,25 @@ int ecapa_stage(svhip_handle* h, const std::string& n, bool fill, StageView& v) 
             h->cat_f32_stale = false;
         }
     }
+    // block 3's inner tensors, the SE gate, the ASP statistics and attention: the forward leaves them in buffers that no later kernel of
+    // it writes (H1 / H2 / H3 / ATT and the per-utterance vectors are indexed by the lane's first row or utterance, so the two lanes of a
+    // B >= 64 batch fill disjoint parts of them)
+    else if (n == "blocks.3.tdnn1") {
+        if (h->h1_split)
+            SV_FAIL(h, SVHIP_ERR_STATE, "stage blocks.3.tdnn1: the last forward wrote its first two chunks only in the split layout of the "
+                                        "Res2Net step kernels, which the chain then overwrote");
+        v.src = h->H1; v.cols = v.ld = C;
+    } else if (n == "blocks.3.res2net") {
+        v.src = h->H2; v.cols = v.ld = C;
+        if (h->h2_is_s32 && fill) {           // F32X3 R2 steps: the chain output exists only in h2_s32; the fp32 view goes to the staging buffer
+            SV_HIP(h, launch_unsplit_s32(h->h2_s32, C, static_cast<float*>(h->s32_buf), C, M, C, h->stream));
+            v.src = h->s32_buf;
+        }
+    }
+    else if (n == "blocks.3.tdnn2") { v.src = h->H3; v.cols = v.ld = C; }
+    else if (n == "blocks.3.se_gate") { v.src = h->d_s2; v.rows = B; v.cols = v.ld = C; v.f32 = true; }
+    else if (n == "asp_gstats") { v.src = h->d_gstats; v.rows = B; v.cols = v.ld = 2 * C3; v.f32 = true; }      // [mean | std]
+    else if (n == "asp_att") { v.src = h->ATT; v.cols = v.ld = 128; }
     else if (n == "mfa") { v.src = h->MFA; v.cols = v.ld = C3; }
     else if (n == "asp") { v.src = h->d_pool_raw; v.rows = B; v.cols = v.ld = 2 * C3; v.f32 = true; }
     else if (n == "asp_bn") { v.src = h->d_pool_bn; v.rows = B; v.cols = v.ld = 2 * C3; v.f32 = true; }

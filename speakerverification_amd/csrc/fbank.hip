@@ -751,9 +751,18 @@ hipError_t launch_fbank(const FbankTables& tb, const float* wav, int B, int L, i
     return hipGetLastError();
 }
 
+static size_t fbank_fused_lds(const FbankTables& tb) {
+    const int ns = (FF_FRAMES - 1) * tb.hop + tb.win_length;
+    const int ns_pad = ((ns + 15) & ~15) + 16;
+    return (size_t)FF_ABYTES + (size_t)(ns_pad + tb.n_melw + 16 + 3 * tb.n_mels) * sizeof(float);
+}
+
+// (the kernel's limits on the bank: at most FF_MAXOUT outputs per thread and pass — 80 mels — and its LDS; a bank it cannot take goes
+//  to the separate kernels instead of failing at launch)
 bool fbank_fused_supported(const FbankTables& tb, int L) {
     return tb.sym_hi && tb.sym_lo && tb.n_fft == 512 && tb.win_length == 200 && tb.hop == 80 && tb.lpad == 156 && tb.mel_max_bin < 256 &&
-           tb.n_mels % 4 == 0 && tb.n_mels <= 128 && tb.n_pairs >= 8 && L >= tb.n_fft;
+           tb.n_mels % 4 == 0 && 32 * tb.n_mels <= 5 * FF_THREADS && tb.n_pairs >= 8 && L >= tb.n_fft && fbank_fused_lds(tb) <= 80 * 1024 &&
+           (size_t)(32 * FF_PT_STRIDE + 32 * (tb.n_mels + 1)) * 4 <= (size_t)4 * FF_PLANE;
 }
 
 // wav (B, L) -> out (B * T, n_mels) bf16 rows = log(mel + 1e-6) - time mean (log_input) or the mel power itself; `logmel` (B, T, n_mels)
@@ -761,11 +770,7 @@ bool fbank_fused_supported(const FbankTables& tb, int L) {
 hipError_t launch_fbank_fused(const FbankTables& tb, const float* wav, int B, int L, int T, int log_input, float* logmel, float* partial,
                               void* out, hipStream_t stream) {
     if (!fbank_fused_supported(tb, L) || B <= 0) return hipErrorInvalidValue;
-    const int ns = (FF_FRAMES - 1) * tb.hop + tb.win_length;
-    const int ns_pad = ((ns + 15) & ~15) + 16;
-    const size_t lds = (size_t)FF_ABYTES + (size_t)(ns_pad + tb.n_melw + 16 + 3 * tb.n_mels) * sizeof(float);
-    if (32 * tb.n_mels > 5 * FF_THREADS) return hipErrorInvalidValue;                 // (FF_MAXOUT outputs per thread and pass)
-    if (lds > 80 * 1024 || (size_t)(32 * FF_PT_STRIDE + 32 * (tb.n_mels + 1)) * 4 > (size_t)4 * FF_PLANE) return hipErrorInvalidValue;
+    const size_t lds = fbank_fused_lds(tb);
     static DeviceOnce attr;
     if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(fbank_fused_kernel), 80 * 1024)) return e;
     const int ntiles = (T + FF_FRAMES - 1) / FF_FRAMES;

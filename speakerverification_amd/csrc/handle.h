@@ -248,6 +248,8 @@ struct svhip_handle {
     void* s32_buf = nullptr;      // SVHIP_F32X3: the A operand of the current big GEMM in the S32 split layout (M x 3C x 4 bytes)
     bool x0_is_s32 = false;       // SVHIP_F32X3: the last forward wrote blocks.0's output (X0) in the split layout
     bool cat_f32_stale = false;   // SVHIP_F32X3: the last forward left the block outputs only in cat_s32 (svhip_get_stage converts on demand)
+    bool h2_is_s32 = false;       // SVHIP_F32X3: the last forward's block-3 Res2Net chain output exists only in h2_s32 (the R2 step kernels)
+    bool h1_split = false;        // ... and block 3's tdnn1 wrote its first two chunks in the split layout only (H1 does not hold them)
     void* cat_s32 = nullptr;      // SVHIP_F32X3: the SE-Res2Net block outputs (the CAT buffer) in the S32 layout, written by se_apply
     void* h2_s32 = nullptr;       // SVHIP_F32X3: the Res2Net chain output (H2's twin, S32 only) and the two step-input buffers (M x C/8)
     void* u_s32[2] = {};
