@@ -84,9 +84,18 @@ typedef enum svhip_status {
  * SVHIP_ERR_UNSUPPORTED).  Length: T = L / hop + 1 >= 7 frames (T' = ((T - 3) / 2 + 1 - 3) / 2 + 1 >= 1) and T' <= 10000, the length of the
  * positional-encoding buffer (svhip_create refuses longer inputs); L >= n_fft as for every model.  Weights: the 278 reference state-dict
  * names, positional_encoding.pe (1, 10000, 256) of every layer included; asp.* / asp_bn.* are required and ignored (the reference never
- * calls them).  Both svhip_embed_wave and svhip_embed_features. */
+ * calls them).  Both svhip_embed_wave and svhip_embed_features.
+ * SVHIP_MODEL_RESNETSE (added under ABI v5): ResNetSE34V2.MainModel (models/ResNetSE34V2.py, ResNetBaseline.py:141-301, ResNetBlocks.py), the
+ * 2-D "Fast ResNet" baseline: on the mel power, log(x + 1e-6) - mean_t (log_input = 1 for features='melspectrogram', else 0) and
+ * InstanceNorm1d(n_mels) without affine (input_norm must be 1); Conv2d(1, 32, 3) with bias -> ReLU -> BatchNorm; four stages of 3 / 4 / 6 / 3
+ * SEBasicBlockV2 at 32 / 64 / 128 / 256 channels, stages 2 - 4 opening with stride (2, 2) and a 1 x 1 BN'd downsample (the block's in-place
+ * ReLU makes the residual relu(x)); squeeze-excitation with 16 hidden units; attention Conv1d(256 n_mels / 8, 128) -> ReLU -> BN ->
+ * Conv1d(128, 256 n_mels / 8) -> softmax over frames; weighted mean and sqrt(clamp(weighted variance, 1e-5)); fc.  channels selects the
+ * pooling: 0 or 2 = encoder_type 'ASP' (mean | std, fc reads 512 n_mels / 8 values), 1 = 'SAP' (mean only); embed_dim = nOut; n_mels a
+ * multiple of 8 (as for every model); compute SVHIP_F32 or SVHIP_BF16 (others: SVHIP_ERR_UNSUPPORTED).  Length: T = L / hop + 1 >= 2 frames
+ * and L >= n_fft as for every model.  Weights: the 292 reference state-dict names.  Both svhip_embed_wave and svhip_embed_features. */
 enum { SVHIP_MODEL_ECAPA = 0, SVHIP_MODEL_RAWNET2 = 1, SVHIP_MODEL_NONE = 2 /* fbank + scoring only */, SVHIP_MODEL_RAWNET2_CONV = 3,
-       SVHIP_MODEL_RAWNET3 = 4, SVHIP_MODEL_RAWNET2_GRU = 5, SVHIP_MODEL_TITANET = 6, SVHIP_MODEL_CONFORMER = 7 };
+       SVHIP_MODEL_RAWNET3 = 4, SVHIP_MODEL_RAWNET2_GRU = 5, SVHIP_MODEL_TITANET = 6, SVHIP_MODEL_CONFORMER = 7, SVHIP_MODEL_RESNETSE = 8 };
 enum { SVHIP_F32 = 0, SVHIP_BF16 = 1, SVHIP_I64 = 2, SVHIP_F32X3 = 3 /* compute only */, SVHIP_F16 = 4 /* compute only */ };
 enum { SVHIP_IN_DEVICE = 1, SVHIP_OUT_DEVICE = 2, SVHIP_ASYNC = 4 };
 
@@ -310,7 +319,9 @@ int svhip_synth_waveforms(svhip_handle* h, uint64_t seed, int64_t first_utt, int
  *                  "tn_prolog" (B T, H), "tn_dw0" (block 0's first depthwise output, its bias included), "tn_mega_last" (the last
  *                  mega-block's output), "tn_enc" (B T, 1536) and "tn_pool" (B, 3072, after BN) of SVHIP_MODEL_TITANET;
  *                  "cf_in" (B T', 256: the input projection), "cf_block0", "cf_attn0" (block 0's per-head attention context before
- *                  out_proj), "cf_last" (the last block's output) and "cf_pool" (B, 512, after attention_norm) of SVHIP_MODEL_CONFORMER.
+ *                  out_proj), "cf_last" (the last block's output) and "cf_pool" (B, 512, after attention_norm) of SVHIP_MODEL_CONFORMER;
+ *                  "rs_stem" (B P Q, 32: channels-last, P frames x Q mel rows), "rs_layer1" .. "rs_layer4" (each stage's output, B P' Q' x C)
+ *                  and "rs_pool" (B, 512 n_mels / 8 fp32: [mean | std], feature q 256 + c) of SVHIP_MODEL_RESNETSE.
  *                  Returns the element count through *count (out may be NULL to query).
  *   profile_*    : when enabled every kernel launch is bracketed by HIP events on the handle's
  *                  stream; profile_get returns accumulated milliseconds / launch count per kernel
@@ -338,6 +349,14 @@ int svhip_selftest(void);   /* host-only self checks (per-device launch-attribut
  * SVHIP_ERR_INVALID (arguments) or SVHIP_ERR_HIP (launch). */
 int svhip_conformer_attention(const void* qkv, const float* P, const float* u_bias, const float* v_bias, void* ctx, int32_t compute,
                               int32_t B, int32_t T_sub, void* stream);
+
+/* ResNetSE's 3 x 3 convolution kernel on its own (tests): y = [relu](scale[n] conv3x3_stride([relu](x)) + shift[n]) with zero padding 1.
+ * x (B, P, Q, Cin) and y (B, Po, Qo, Cout), Po = (P - 1) / stride + 1, are DEVICE pointers, channels-last, in the compute type (SVHIP_F32 /
+ * SVHIP_BF16); scale / shift are device fp32 [Cout]; w is the HOST weight (Cout, Cin, 3, 3) in the reference's layout, whose [kh][kw] run
+ * over Q and P.  Cin a multiple of 32, Cout 32 or a multiple of 64, stride 1 or 2.  Enqueued on `stream` (NULL: the null stream) and
+ * synchronised.  SVHIP_OK, SVHIP_ERR_INVALID (arguments), SVHIP_ERR_NOMEM or SVHIP_ERR_HIP. */
+int svhip_resnetse_conv3x3(const void* x, const float* w, const float* scale, const float* shift, void* y, int32_t compute, int32_t B,
+                           int32_t P, int32_t Q, int32_t Cin, int32_t Cout, int32_t stride, int32_t relu_in, int32_t relu_out, void* stream);
 
 #ifdef __cplusplus
 }

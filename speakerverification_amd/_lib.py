@@ -21,6 +21,7 @@ MODEL_RAWNET3 = 4                          # RawNet3, the raw-waveform branch of
 MODEL_RAWNET2_GRU = 5                      # RawNet2 with front_proc='sinc', aggregate='gru' (include/svhip.h, added under ABI v5)
 MODEL_TITANET = 6                          # TitaNet, the spectral branch of Tita_ECAPA / Raw_tita (include/svhip.h, added under ABI v5)
 MODEL_CONFORMER = 7                        # Conformer, the model of yaml/model_plot.yaml (include/svhip.h, added under ABI v5)
+MODEL_RESNETSE = 8                         # ResNetSE34V2, the 2-D SE-ResNet baseline (include/svhip.h, added under ABI v5)
 F32, BF16, I64, F32X3, F16 = 0, 1, 2, 3, 4
 IN_DEVICE, OUT_DEVICE, ASYNC = 1, 2, 4
 TRIAL_COSINE, TRIAL_PNORM, TRIAL_PDIST = 0, 1, 2
@@ -111,6 +112,7 @@ _SIGNATURES = {
     "svhip_trim_scratch": (C.c_int, [_P]),
     "svhip_selftest": (C.c_int, []),
     "svhip_conformer_attention": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "svhip_resnetse_conv3x3": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 9 + [_P]),
 }
 
 _lib = None

@@ -26,7 +26,8 @@ _MODEL_IDS = {"ECAPA_TDNN": _lib.MODEL_ECAPA, "ecapa": _lib.MODEL_ECAPA, "RawNet
               "rawnet2": _lib.MODEL_RAWNET2, "RawNet2_custom_conv": _lib.MODEL_RAWNET2_CONV, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV,
               "RawNet2_custom_gru": _lib.MODEL_RAWNET2_GRU, "rawnet2_gru": _lib.MODEL_RAWNET2_GRU,
               "RawNet3": _lib.MODEL_RAWNET3, "rawnet3": _lib.MODEL_RAWNET3, "TitaNet": _lib.MODEL_TITANET, "titanet": _lib.MODEL_TITANET,
-              "Conformer": _lib.MODEL_CONFORMER, "conformer": _lib.MODEL_CONFORMER}
+              "Conformer": _lib.MODEL_CONFORMER, "conformer": _lib.MODEL_CONFORMER,
+              "ResNetSE34V2": _lib.MODEL_RESNETSE, "resnetse": _lib.MODEL_RESNETSE}
 
 
 def model_id(model) -> int:
@@ -222,7 +223,7 @@ def main(argv=None):
     ap.add_argument("src")
     ap.add_argument("dst")
     ap.add_argument("--model", default="ECAPA_TDNN", help="reference model name (ECAPA_TDNN, RawNet2_custom, RawNet2_custom_conv, RawNet2_custom_gru, "
-                    "RawNet3, TitaNet, Conformer, Raw_ECAPA_sinc_asp, Raw_ECAPA_sinc_gru, Raw_ECAPA, Raw_ECAPA_conv_asp, Raw3_ECAPA, Tita_ECAPA, Raw_tita)")
+                    "RawNet3, TitaNet, Conformer, ResNetSE34V2, Raw_ECAPA_sinc_asp, Raw_ECAPA_sinc_gru, Raw_ECAPA, Raw_ECAPA_conv_asp, Raw3_ECAPA, Tita_ECAPA, Raw_tita)")
     a = ap.parse_args(argv)
     n = convert_checkpoint(a.src, a.dst, a.model)
     print(f"{a.dst}: {n} tensors")

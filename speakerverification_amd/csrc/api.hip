@@ -67,6 +67,7 @@ const ModelOps kModels[] = {
     {SVHIP_MODEL_TITANET,      titanet_check,   titanet_spec,   titanet_finalize,   titanet_alloc,   fbank_then_features, titanet_forward,   titanet_stage,   4,
      "encoder.mega_blocks."},       // (the block count follows from what was loaded: titanet_finalize checks its blocks)
     {SVHIP_MODEL_CONFORMER,    conformer_check, conformer_spec, conformer_finalize, conformer_alloc, fbank_then_features, conformer_forward, conformer_stage, 4},
+    {SVHIP_MODEL_RESNETSE,     resnetse_check,  resnetse_spec,  resnetse_finalize,  resnetse_alloc,  fbank_then_features, resnetse_forward,  resnetse_stage,  4},
     {SVHIP_MODEL_NONE,         none_check,      nullptr,        nullptr,            nullptr,         nullptr,             nullptr,           nullptr,         1},   // fbank + scoring
 };
 
@@ -408,7 +409,7 @@ int svhip_embed_features(svhip_handle* h, const float* feat, int32_t B, int32_t 
     if (rc) return rc;
     if (!feat || !emb_out) SV_FAIL(h, SVHIP_ERR_INVALID, "null pointer");
     const ModelOps* m = model_ops(h->cfg.model);
-    if (!m->embed_feat) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "embed_features needs a spectral model (ECAPA, TitaNet, Conformer)");
+    if (!m->embed_feat) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "embed_features needs a spectral model (ECAPA, TitaNet, Conformer, ResNetSE)");
     if (T != h->T) SV_FAIL(h, SVHIP_ERR_INVALID, "T=%d but the handle was created for T=%d frames", T, h->T);
     if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
         SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");

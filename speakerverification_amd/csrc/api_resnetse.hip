@@ -1,0 +1,323 @@
+// api_resnetse.hip — ResNetSE34V2 in libsvhip (reference models/ResNetSE34V2.py, ResNetBaseline.py:141-301, ResNetBlocks.py:211-246,292-307): its
+// create rules, weight names and packing, workspace, forward and stages.
+//
+// Activations are channels-last (B, P, Q, C): P = frames (the reference's W), Q = mel rows (its H).  A reference weight (Cout, Cin, kh, kw)
+// has kh over mel rows and kw over frames, so the kernels' tap (dp, dq) is its element [dq][dp].
+//
+// Buffers (resnetse_alloc): XIN (B, P, Q) fp32 normalised input; OUT[0] the stem output, OUT[1 .. 4] the stages' outputs; TMP[0 / 1] block
+// outputs inside a stage, TMP[2] conv1's output, TMP[3] conv2's output, TMP[4] the downsample output; PART / GATE the SE squeeze and gates.
+//
+// One SEBasicBlockV2 on x (ResNetBlocks.py:229-246; `self.relu` is in place, so the residual is relu(x)):
+//   conv1   u = relu(bn1(conv3x3_s(relu(x))))                     rs_conv (ReLU on the operand, BN + ReLU in the epilogue)
+//   conv2   v = bn2(conv3x3(u)), tile sums of v                   rs_conv
+//   SE      g = sigmoid(W2 relu(W1 mean(v) + b1) + b2)            rs_se_gate (the tile sums in tile order)
+//   down    d = bn(conv1x1_s(relu(x)))   (first block of stages 2 - 4)      rs_conv, KS = 1
+//   tail    out = relu((d | relu(x)) + g v)                       rs_se_apply
+#include <cmath>
+#include <cstring>
+
+#include "handle.h"
+
+namespace svhip {
+
+namespace {
+
+// The 2-D ResNet family as data: blocks per stage, widths, block kind.  A sibling depth is another row.
+enum RsBlockKind { RS_SE_BASIC_V2 = 0 };
+struct RsArch { int blocks[4]; int widths[4]; RsBlockKind kind; int se_hidden; int att_dim; };
+const RsArch kResNetSE34V2 = {{3, 4, 6, 3}, {32, 64, 128, 256}, RS_SE_BASIC_V2, 16, 128};
+
+const RsArch& arch_of(const svhip_config&) { return kResNetSE34V2; }
+bool rs_is_sap(const svhip_config& c) { return c.channels == 1; }
+
+// (Cout, Cin, ks, ks) -> [Cin / CK][ks ks][Cout][CK], tap = ks dp + dq = the reference's element [dq][dp], in fp32
+std::vector<float> rs_pack(const float* w, int cout, int cin, int ks, int ck) {
+    std::vector<float> out((size_t)cout * cin * ks * ks);
+    const int taps = ks * ks;
+    for (int n = 0; n < cout; ++n)
+        for (int c = 0; c < cin; ++c)
+            for (int dp = 0; dp < ks; ++dp)
+                for (int dq = 0; dq < ks; ++dq)
+                    out[((((size_t)(c / ck) * taps) + dp * ks + dq) * cout + n) * ck + c % ck] = w[(((size_t)n * cin + c) * ks + dq) * ks + dp];
+    return out;
+}
+
+int rs_upload_packed(svhip_handle* h, const std::vector<float>& m, void** dst) {
+    if (h->bf16) return upload_h16(h, m, dst);
+    float* d;
+    int rc = dev_upload(h, &d, m);
+    *dst = d;
+    return rc;
+}
+
+int make_rs_conv(svhip_handle* h, svhip_handle::RsConv& L, const std::string& wname, const std::string& bnname, int cin, int cout, int ks, int stride) {
+    const HostTensor* w;
+    int rc;
+    if ((rc = needw(h, wname, w))) return rc;
+    L.cin = cin; L.cout = cout; L.ks = ks; L.stride = stride;
+    if ((rc = rs_upload_packed(h, rs_pack(w->data.data(), cout, cin, ks, h->bf16 ? 32 : 16), &L.W))) return rc;
+    return make_bn(h, bnname, cout, &L.scale, &L.shift);
+}
+
+RsConvParams rs_params(const svhip_handle::RsConv& L, const void* x, void* y, int B, int P, int Q, bool relu_in, bool relu_out, float* part) {
+    RsConvParams p;
+    p.X = x; p.Y = y; p.W = L.W; p.scale = L.scale; p.shift = L.shift; p.part = part;
+    p.B = B; p.P = P; p.Q = Q; p.Cin = L.cin; p.Cout = L.cout; p.stride = L.stride; p.ks = L.ks;
+    p.relu_in = relu_in; p.relu_out = relu_out;
+    rs_conv_plan(p);
+    return p;
+}
+
+}  // namespace
+
+int resnetse_check(const svhip_config& c, const char*& err) {
+    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "ResNetSE runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_UNSUPPORTED; }
+    if (c.channels < 0 || c.channels > 2) { err = "ResNetSE: channels selects the pooling, 0 / 2 = 'ASP' (mean | std), 1 = 'SAP' (mean)"; return SVHIP_ERR_INVALID; }
+    if (!c.input_norm) { err = "ResNetSE applies InstanceNorm1d(n_mels): input_norm must be 1"; return SVHIP_ERR_INVALID; }
+    if (c.embed_dim <= 0) { err = "ResNetSE needs embed_dim > 0"; return SVHIP_ERR_INVALID; }
+    if (c.hop_length > 0 && c.samples / c.hop_length + 1 < 2) { err = "ResNetSE needs T >= 2 frames (InstanceNorm1d over one frame is undefined)"; return SVHIP_ERR_INVALID; }
+    return SVHIP_OK;
+}
+
+void resnetse_spec(const svhip_config& c, WeightSpec& spec) {
+    const RsArch& a = arch_of(c);
+    spec["conv1.weight"] = {a.widths[0], 1, 3, 3}; spec["conv1.bias"] = {a.widths[0]};
+    spec_bn(spec, "bn1", a.widths[0]);
+    int inpl = a.widths[0];
+    for (int s = 0; s < 4; ++s) {
+        const int64_t C = a.widths[s];
+        for (int j = 0; j < a.blocks[s]; ++j) {
+            const std::string p = "layer" + std::to_string(s + 1) + "." + std::to_string(j) + ".";
+            spec[p + "conv1.weight"] = {C, inpl, 3, 3}; spec_bn(spec, p + "bn1", C);
+            spec[p + "conv2.weight"] = {C, C, 3, 3}; spec_bn(spec, p + "bn2", C);
+            spec[p + "se.fc.0.weight"] = {a.se_hidden, C}; spec[p + "se.fc.0.bias"] = {a.se_hidden};
+            spec[p + "se.fc.2.weight"] = {C, a.se_hidden}; spec[p + "se.fc.2.bias"] = {C};
+            if (j == 0 && s > 0) { spec[p + "downsample.0.weight"] = {C, inpl, 1, 1}; spec_bn(spec, p + "downsample.1", C); }
+            inpl = (int)C;
+        }
+    }
+    const int64_t F = (int64_t)a.widths[3] * (c.n_mels / 8), nOut = c.embed_dim;
+    spec["attention.0.weight"] = {a.att_dim, F, 1}; spec["attention.0.bias"] = {a.att_dim};
+    spec_bn(spec, "attention.2", a.att_dim);
+    spec["attention.3.weight"] = {F, a.att_dim, 1}; spec["attention.3.bias"] = {F};
+    spec["fc.weight"] = {nOut, rs_is_sap(c) ? F : 2 * F}; spec["fc.bias"] = {nOut};
+}
+
+int resnetse_finalize(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    const RsArch& a = arch_of(c);
+    int rc;
+    {
+        // stem: conv1 (32, 1, 3, 3) tap-major [3 dp + dq][32], bias, bn1
+        const HostTensor* w;
+        if ((rc = needw(h, "conv1.weight", w))) return rc;
+        const int C0 = a.widths[0];
+        std::vector<float> tw((size_t)9 * C0);
+        for (int n = 0; n < C0; ++n)
+            for (int dp = 0; dp < 3; ++dp)
+                for (int dq = 0; dq < 3; ++dq) tw[(size_t)(dp * 3 + dq) * C0 + n] = w->data[(size_t)n * 9 + dq * 3 + dp];
+        if ((rc = dev_upload(h, &h->rs_stem_w, tw)) || (rc = upload_f32(h, "conv1.bias", &h->rs_stem_b)) ||
+            (rc = make_bn(h, "bn1", C0, &h->rs_stem_scale, &h->rs_stem_shift))) return rc;
+    }
+    double fl = 2.0 * 9 * a.widths[0] * h->rs_P[0] * h->rs_Q[0];
+    h->rs.clear();
+    int inpl = a.widths[0];
+    for (int s = 0; s < 4; ++s) {
+        const int C = a.widths[s];
+        const double pos = (double)h->rs_P[s + 1] * h->rs_Q[s + 1];
+        for (int j = 0; j < a.blocks[s]; ++j) {
+            const std::string p = "layer" + std::to_string(s + 1) + "." + std::to_string(j) + ".";
+            svhip_handle::RsBlock K;
+            const int stride = (j == 0 && s > 0) ? 2 : 1;
+            if ((rc = make_rs_conv(h, K.c1, p + "conv1.weight", p + "bn1", inpl, C, 3, stride)) ||
+                (rc = make_rs_conv(h, K.c2, p + "conv2.weight", p + "bn2", C, C, 3, 1))) return rc;
+            K.has_down = j == 0 && s > 0;
+            if (K.has_down && (rc = make_rs_conv(h, K.down, p + "downsample.0.weight", p + "downsample.1", inpl, C, 1, 2))) return rc;
+            if ((rc = upload_f32(h, p + "se.fc.0.weight", &K.se_w1)) || (rc = upload_f32(h, p + "se.fc.0.bias", &K.se_b1)) ||
+                (rc = upload_f32(h, p + "se.fc.2.weight", &K.se_w2)) || (rc = upload_f32(h, p + "se.fc.2.bias", &K.se_b2))) return rc;
+            fl += pos * (2.0 * 9 * inpl * C + 2.0 * 9 * C * C + (K.has_down ? 2.0 * inpl * C : 0.0));
+            h->rs.push_back(K);
+            inpl = C;
+        }
+        h->rs_stage_end[s] = (int)h->rs.size();
+    }
+    // The reference flattens (B, C, Q, P) to rows c Q + q; the channels-last rows here run q C + c.  The permutation goes once into the
+    // K axis of attention.0 and fc and the N axis of attention.3, never into activations.
+    const int C4 = a.widths[3], Q4 = h->rs_Q[4], F = C4 * Q4, A = a.att_dim, nOut = c.embed_dim;
+    auto perm = [&](int k) { return (k % C4) * Q4 + k / C4; };        // column q C + c of this layout -> the reference's c Q + q
+    {
+        const HostTensor *w, *b;
+        if ((rc = needw(h, "attention.0.weight", w)) || (rc = needw(h, "attention.0.bias", b))) return rc;
+        HostTensor pw; pw.shape = {A, F}; pw.data.resize((size_t)A * F);
+        for (int n = 0; n < A; ++n)
+            for (int k = 0; k < F; ++k) pw.data[(size_t)n * F + k] = w->data[(size_t)n * F + perm(k)];
+        if ((rc = make_conv(h, h->rs_att0, pw, &b->data, 1)) || (rc = make_bn(h, "attention.2", A, &h->rs_att0.scale, &h->rs_att0.shift))) return rc;
+        if ((rc = needw(h, "attention.3.weight", w)) || (rc = needw(h, "attention.3.bias", b))) return rc;
+        HostTensor pw3; pw3.shape = {F, A}; pw3.data.resize((size_t)F * A);
+        std::vector<float> pb(F);
+        for (int k = 0; k < F; ++k) {
+            memcpy(&pw3.data[(size_t)k * A], &w->data[(size_t)perm(k) * A], (size_t)A * 4);
+            pb[k] = b->data[perm(k)];
+        }
+        if ((rc = make_conv(h, h->rs_att3, pw3, &pb, 1))) return rc;
+        if ((rc = needw(h, "fc.weight", w))) return rc;
+        const int halves = h->rs_sap ? 1 : 2, K = halves * F;
+        std::vector<float> fw((size_t)nOut * K);
+        for (int n = 0; n < nOut; ++n)
+            for (int hf = 0; hf < halves; ++hf)
+                for (int k = 0; k < F; ++k) fw[(size_t)n * K + hf * F + k] = w->data[(size_t)n * K + hf * F + perm(k)];
+        h->rs_fc.N = nOut; h->rs_fc.K = K;
+        if ((rc = dev_upload(h, &h->rs_fc.W, fw)) || (rc = upload_f32(h, "fc.bias", &h->rs_fc.bias))) return rc;
+    }
+    fl += (double)h->rs_P[4] * (h->rs_att0.flops_per_row + h->rs_att3.flops_per_row) + 2.0 * nOut * h->rs_fc.K;
+    h->flops_per_utt = fl;
+    return SVHIP_OK;
+}
+
+int resnetse_alloc(svhip_handle* h) {
+    const svhip_config& c = h->cfg;
+    const RsArch& a = arch_of(c);
+    const size_t B = c.max_batch;
+    h->rs_sap = rs_is_sap(c);
+    h->rs_P[0] = h->T; h->rs_Q[0] = c.n_mels; h->rs_C[0] = a.widths[0];
+    for (int s = 0; s < 4; ++s) {
+        const int st = s == 0 ? 1 : 2;
+        h->rs_P[s + 1] = rs_out_size(h->rs_P[s], st);
+        h->rs_Q[s + 1] = rs_out_size(h->rs_Q[s], st);
+        h->rs_C[s + 1] = a.widths[s];
+    }
+    int rc;
+    if ((rc = dev_alloc(h, &h->rs_xin, B * h->rs_P[0] * h->rs_Q[0]))) return rc;
+    size_t big = 0, part = 0;
+    for (int s = 0; s <= 4; ++s) {
+        const size_t n = (size_t)h->rs_P[s] * h->rs_Q[s] * h->rs_C[s];
+        if (n > big) big = n;
+        if ((rc = actbuf(h, &h->rs_out[s], B * n))) return rc;
+        if (s > 0) {          // the SE tile sums of conv2 in this stage
+            RsConvParams p;
+            p.P = h->rs_P[s]; p.Q = h->rs_Q[s]; p.stride = 1; p.ks = 3;
+            rs_conv_plan(p);
+            const size_t m = (size_t)p.ntp * p.ntq * h->rs_C[s];
+            if (m > part) part = m;
+        }
+    }
+    for (int i = 0; i < 5; ++i) if ((rc = actbuf(h, &h->rs_tmp[i], B * big))) return rc;
+    if ((rc = dev_alloc(h, &h->rs_part, B * part)) || (rc = dev_alloc(h, &h->rs_gate, B * 256))) return rc;
+    const size_t F = (size_t)h->rs_C[4] * h->rs_Q[4], M = B * h->rs_P[4];
+    if ((rc = actbuf(h, &h->rs_att, M * a.att_dim)) || (rc = dev_alloc(h, &h->rs_logits, M * F)) ||
+        (rc = dev_alloc(h, &h->rs_pool_raw, B * 2 * F)) || (rc = dev_alloc(h, &h->rs_pool, B * 2 * F))) return rc;
+    std::vector<float> one(2 * F, 1.0f), zero(2 * F, 0.0f);
+    if ((rc = dev_upload(h, &h->rs_pool_one, one)) || (rc = dev_upload(h, &h->rs_pool_zero, zero))) return rc;
+    return SVHIP_OK;
+}
+
+static int resnetse_forward_part(svhip_handle* h, const float* d_feat, int b0, int B) {
+    (void)b0;
+    const svhip_config& c = h->cfg;
+    const int dt = h->dt;
+    const bool bf = h->bf16;
+    hipStream_t st = h->cur;
+    int rc;
+    // log(x + 1e-6) - mean_t for features == 'melspectrogram', then InstanceNorm1d(n_mels) without affine: (B, n_mels, T) -> (B, T, n_mels) fp32
+    if ((rc = run(h, "prologue", 0, [&]() {
+             return launch_prologue(d_feat, h->rs_xin, false, B, c.n_mels, h->T, c.log_input, h->d_ones, h->d_zeros, h->d_pstats, st);
+         }))) return rc;
+    // conv1 (with bias) -> ReLU -> bn1                                                       ResNetBaseline.py:260-262
+    if ((rc = run(h, "rs_stem", 2.0 * 9 * h->rs_C[0] * B * h->rs_P[0] * h->rs_Q[0], [&]() {
+             return launch_rs_stem(h->rs_xin, h->rs_stem_w, h->rs_stem_b, h->rs_stem_scale, h->rs_stem_shift, h->rs_out[0], dt, B, h->rs_P[0], h->rs_Q[0], st);
+         }))) return rc;
+    const void* x = h->rs_out[0];
+    int P = h->rs_P[0], Q = h->rs_Q[0], stage = 0, pp = 0;
+    static const char* const kConvLabel[4] = {"rs_conv3x3_s1", "rs_conv3x3_s2", "rs_conv3x3_s3", "rs_conv3x3_s4"};
+    for (size_t i = 0; i < h->rs.size(); ++i) {
+        const svhip_handle::RsBlock& K = h->rs[i];
+        while ((int)i >= h->rs_stage_end[stage]) ++stage;
+        const bool last = (int)i + 1 == h->rs_stage_end[stage];
+        void* out = last ? h->rs_out[stage + 1] : h->rs_tmp[pp];
+        const RsConvParams p1 = rs_params(K.c1, x, h->rs_tmp[2], B, P, Q, true, true, nullptr);
+        const RsConvParams p2 = rs_params(K.c2, h->rs_tmp[2], h->rs_tmp[3], B, p1.Po, p1.Qo, false, false, h->rs_part);
+        const double pos = (double)B * p1.Po * p1.Qo;
+        if ((rc = run(h, kConvLabel[stage], 2.0 * 9 * K.c1.cin * K.c1.cout * pos, [&]() { return launch_rs_conv(p1, dt, st); }))) return rc;
+        if ((rc = run(h, kConvLabel[stage], 2.0 * 9 * K.c2.cin * K.c2.cout * pos, [&]() { return launch_rs_conv(p2, dt, st); }))) return rc;
+        if ((rc = run(h, "rs_se_gate", 0, [&]() {
+                 return launch_rs_se_gate(h->rs_part, p2.ntp * p2.ntq, B, K.c2.cout, p2.Po * p2.Qo, K.se_w1, K.se_b1, K.se_w2, K.se_b2, h->rs_gate, st);
+             }))) return rc;
+        const void* res = x;
+        if (K.has_down) {
+            const RsConvParams pd = rs_params(K.down, x, h->rs_tmp[4], B, P, Q, true, false, nullptr);
+            if ((rc = run(h, "rs_down", 2.0 * K.down.cin * K.down.cout * pos, [&]() { return launch_rs_conv(pd, dt, st); }))) return rc;
+            res = h->rs_tmp[4];
+        }
+        if ((rc = run(h, "rs_se_apply", 0, [&]() {
+                 return launch_rs_se_apply(h->rs_tmp[3], res, h->rs_gate, out, dt, B, p2.Po * p2.Qo, K.c2.cout, !K.has_down, st);
+             }))) return rc;
+        x = out;
+        P = p1.Po; Q = p1.Qo;
+        if (!last) pp ^= 1;
+    }
+    // attention (ResNetBaseline.py:186-194,269-279) on rows (B P4, Q4 C4): Conv1d -> ReLU -> BN -> Conv1d -> softmax over frames, then the
+    // weighted mean and sqrt(clamp(weighted variance, 1e-5))
+    const int F = h->rs_C[4] * h->rs_Q[4], M = B * P;
+    GemmParams pa = conv_params(h, h->rs_att0, x, F, h->rs_att, 128, M, P);
+    pa.act1 = ACT_RELU;
+    if ((rc = conv_gemm(h, h->rs_att0, pa))) return rc;
+    GemmParams pl = conv_params(h, h->rs_att3, h->rs_att, 128, h->rs_logits, F, M, P);
+    pl.out_f32 = 1;
+    if ((rc = conv_gemm(h, h->rs_att3, pl))) return rc;
+    if ((rc = run(h, "rs_asp_pool", 0, [&]() {
+             return launch_asp_pool(h->rs_logits, x, bf, F, B, P, F, h->rs_pool_one, h->rs_pool_zero, h->rs_pool_raw, h->rs_pool, 1e-5f, 0.0f, st);
+         }))) return rc;
+    // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the GEMM's ReLU epilogue would have dropped it)
+    if ((rc = run(h, "rs_in_check", 0, [&]() {
+             return launch_tn_nonfinite_rows(d_feat, (int64_t)c.n_mels * h->T, B, h->rs_pool, 2 * F, 2 * F, st);
+         }))) return rc;
+    return run(h, "rs_fc", 2.0 * B * h->rs_fc.N * h->rs_fc.K, [&]() {
+        return launch_rowvec_linear(h->rs_pool, 2 * F, h->rs_fc.W, h->rs_fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, h->rs_fc.K, ACT_NONE, st);
+    });
+}
+
+int resnetse_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, resnetse_forward_part, d_feat, B, 1, B); }
+
+int resnetse_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // rs_stem, rs_layer1 .. rs_layer4 (B P Q, C), rs_pool (B, 2 F)
+    int s = -1;
+    if (n == "rs_stem") s = 0;
+    else if (n.size() == 9 && n.compare(0, 8, "rs_layer") == 0 && n[8] >= '1' && n[8] <= '4') s = n[8] - '0';
+    if (s >= 0) { v.src = h->rs_out[s]; v.rows = (size_t)h->lastB * h->rs_P[s] * h->rs_Q[s]; v.cols = v.ld = h->rs_C[s]; }
+    else if (n == "rs_pool") { v.src = h->rs_pool; v.rows = h->lastB; v.cols = v.ld = 2 * (size_t)h->rs_C[4] * h->rs_Q[4]; v.f32 = true; }
+    else return unknown_stage(h, n);
+    return SVHIP_OK;
+}
+
+}  // namespace svhip
+
+// The 3 x 3 convolution kernel on its own (tests): x (B, P, Q, Cin) and y (B, Po, Qo, Cout) are device pointers in the compute type, scale /
+// shift device fp32 [Cout]; w is the HOST weight (Cout, Cin, 3, 3) in the reference's layout, packed and uploaded here.  Synchronises.
+extern "C" int svhip_resnetse_conv3x3(const void* x, const float* w, const float* scale, const float* shift, void* y, int32_t compute, int32_t B,
+                                      int32_t P, int32_t Q, int32_t Cin, int32_t Cout, int32_t stride, int32_t relu_in, int32_t relu_out, void* stream) {
+    using namespace svhip;
+    if ((compute != SVHIP_F32 && compute != SVHIP_BF16) || !x || !w || !scale || !shift || !y) return SVHIP_ERR_INVALID;
+    if (B <= 0 || P <= 0 || Q <= 0 || Cin <= 0 || Cin % 32 != 0 || Cout <= 0 || (stride != 1 && stride != 2)) return SVHIP_ERR_INVALID;
+    const bool bf = compute == SVHIP_BF16;
+    const std::vector<float> packed = rs_pack(w, Cout, Cin, 3, bf ? 32 : 16);
+    std::vector<uint16_t> pb;
+    if (bf) {
+        pb.resize(packed.size());
+        for (size_t i = 0; i < packed.size(); ++i) pb[i] = f32_to_bf16_rne(packed[i]);
+    }
+    void* dW = nullptr;
+    const size_t bytes = packed.size() * (bf ? 2 : 4);
+    if (hipMalloc(&dW, bytes) != hipSuccess) return SVHIP_ERR_NOMEM;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipError_t e = hipMemcpy(dW, bf ? (const void*)pb.data() : (const void*)packed.data(), bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        RsConvParams p;
+        p.X = x; p.Y = y; p.W = dW; p.scale = scale; p.shift = shift;
+        p.B = B; p.P = P; p.Q = Q; p.Cin = Cin; p.Cout = Cout; p.stride = stride; p.ks = 3; p.relu_in = relu_in != 0; p.relu_out = relu_out != 0;
+        rs_conv_plan(p);
+        e = launch_rs_conv(p, bf ? DT_BF16 : DT_F32, st);
+        if (e == hipErrorInvalidValue) { (void)hipFree(dW); return SVHIP_ERR_INVALID; }
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(dW);
+    return (e == hipSuccess && e2 == hipSuccess) ? SVHIP_OK : SVHIP_ERR_HIP;
+}

@@ -232,6 +232,33 @@ struct svhip_handle {
     float* cf_logits = nullptr;               // (Bmax T', 256) fp32 attention logits of the pooling
     float *cf_pool_raw = nullptr, *cf_pool = nullptr;         // (Bmax, 512) [mean | std], after attention_norm
 
+    // ResNetSE layers (SVHIP_MODEL_RESNETSE: models/ResNetSE34V2.py).  Activations are channels-last (B, P, Q, C), P frames x Q mel rows; every
+    // BatchNorm is the scale / shift of the convolution before it
+    struct RsConv {
+        void* W = nullptr;                    // [cin / CK][taps][cout][CK] in the compute type (resnetse.hip)
+        float *scale = nullptr, *shift = nullptr;
+        int cin = 0, cout = 0, stride = 1, ks = 3;
+    };
+    struct RsBlock {
+        RsConv c1, c2, down;                  // conv1 + bn1, conv2 + bn2, downsample.0 + downsample.1 (the first block of stages 2 - 4)
+        bool has_down = false;
+        float *se_w1 = nullptr, *se_b1 = nullptr, *se_w2 = nullptr, *se_b2 = nullptr;      // se.fc.0 [16][C], se.fc.2 [C][16]
+    };
+    std::vector<RsBlock> rs;                  // the blocks of all stages in order
+    int rs_stage_end[4] = {};                 // index one past the last block of each stage
+    int rs_P[5] = {}, rs_Q[5] = {}, rs_C[5] = {};     // image size and channels of the stem output [0] and of each stage's output [1 .. 4]
+    float *rs_stem_w = nullptr, *rs_stem_b = nullptr, *rs_stem_scale = nullptr, *rs_stem_shift = nullptr;     // conv1 tap-major [9][32], bn1
+    svhip::ConvLayer rs_att0, rs_att3;        // attention.0 (+ ReLU, attention.2 as the epilogue affine), attention.3; K permuted to q C + c
+    svhip::LinearLayer rs_fc;                 // fc, columns permuted the same way
+    bool rs_sap = false;                      // encoder_type 'SAP': fc reads the weighted means only
+    float* rs_xin = nullptr;                  // (Bmax, P, Q) fp32: the normalised input
+    void* rs_out[5] = {};                     // the stem output and each stage's output (stages rs_stem, rs_layer1 .. rs_layer4)
+    void* rs_tmp[5] = {};                     // block outputs inside a stage (ping-pong), conv1 output, conv2 output, downsample output
+    float *rs_part = nullptr, *rs_gate = nullptr;      // SE: per-tile channel sums of conv2's output, (Bmax, C) gates
+    void* rs_att = nullptr;                   // (Bmax P4, 128)
+    float* rs_logits = nullptr;               // (Bmax P4, Q4 C4) fp32
+    float *rs_pool_raw = nullptr, *rs_pool = nullptr, *rs_pool_one = nullptr, *rs_pool_zero = nullptr;     // (Bmax, 2 Q4 C4) [mu | sg]
+
     // workspace (device)
     float* d_wav = nullptr;       // (Bmax, L)
     float* d_feat = nullptr;      // (Bmax, n_mels, T) mel power
@@ -439,13 +466,14 @@ int conv_gemm(svhip_handle* h, const ConvLayer& L, const GemmParams& p, const vo
 using ForwardPart = int (*)(svhip_handle* h, const float* in, int b0, int B);
 int forward_lanes(svhip_handle* h, ForwardPart part, const float* in, int B, int lanes, int per);
 
-// api_ecapa.hip, api_rawnet2.hip (the three RawNet2 models), api_rawnet3.hip, api_titanet.hip, api_conformer.hip: each model's functions
-CheckFn ecapa_check, rawnet2_check, rawnet3_check, titanet_check, conformer_check;
-SpecFn ecapa_spec, rawnet2_spec, rawnet3_spec, titanet_spec, conformer_spec;
-HandleFn ecapa_finalize, rawnet2_finalize, rawnet3_finalize, titanet_finalize, conformer_finalize;
-HandleFn ecapa_alloc, rawnet2_alloc, rawnet3_alloc, titanet_alloc, conformer_alloc;
+// api_ecapa.hip, api_rawnet2.hip (the three RawNet2 models), api_rawnet3.hip, api_titanet.hip, api_conformer.hip, api_resnetse.hip: each
+// model's functions
+CheckFn ecapa_check, rawnet2_check, rawnet3_check, titanet_check, conformer_check, resnetse_check;
+SpecFn ecapa_spec, rawnet2_spec, rawnet3_spec, titanet_spec, conformer_spec, resnetse_spec;
+HandleFn ecapa_finalize, rawnet2_finalize, rawnet3_finalize, titanet_finalize, conformer_finalize, resnetse_finalize;
+HandleFn ecapa_alloc, rawnet2_alloc, rawnet3_alloc, titanet_alloc, conformer_alloc, resnetse_alloc;
 EmbedFn ecapa_embed_wave, rawnet2_forward, rawnet3_forward;                    // from the waveform
-EmbedFn ecapa_forward, titanet_forward, conformer_forward;                     // from the mel power
-StageFn ecapa_stage, rawnet2_stage, rawnet3_stage, titanet_stage, conformer_stage;
+EmbedFn ecapa_forward, titanet_forward, conformer_forward, resnetse_forward;   // from the mel power
+StageFn ecapa_stage, rawnet2_stage, rawnet3_stage, titanet_stage, conformer_stage, resnetse_stage;
 
 }  // namespace svhip

@@ -440,6 +440,35 @@ hipError_t launch_cf_glu_dw(const void* u, const float* w, const float* bias, vo
 hipError_t launch_cf_attn(const void* qkv, int ldq, const float* P, int ldp, const float* u_bias, const float* v_bias, void* ctx, int ldc, int dt,
                           int B, int Tn, hipStream_t stream);
 
+// ---------------------------------------------------------------------------------------------
+// ResNetSE (resnetse.hip): channels-last (B, P, Q, C) activations — P frames, Q mel rows — fp32 or bf16 storage (dt), 16-byte aligned.
+// ---------------------------------------------------------------------------------------------
+inline int rs_out_size(int n, int stride) { return (n - 1) / stride + 1; }      // Conv2d(3, stride, padding 1) and Conv2d(1, stride)
+// y (B, Po, Qo, Cout) = [relu](scale[n] conv(x) + shift[n]), conv = ks x ks (3: zero padding 1; 1: none) at stride 1 / 2 over
+// [relu](x) (B, P, Q, Cin); W packed [Cin / CK][ks ks taps][Cout][CK] in the compute type, CK = 32 (bf16) / 16 (fp32) channels, tap =
+// 3 dp + dq.  Cin % CK == 0; Cout 32 or a multiple of 64.  part (optional): (B, ntp ntq, Cout) fp32 sums of y over each tile's positions.
+struct RsConvParams {
+    const void* X = nullptr;
+    void* Y = nullptr;
+    const void* W = nullptr;
+    const float* scale = nullptr;
+    const float* shift = nullptr;
+    float* part = nullptr;
+    int B = 0, P = 0, Q = 0, Cin = 0, Cout = 0, stride = 1, ks = 3, relu_in = 0, relu_out = 0;
+    int Po = 0, Qo = 0, TP = 0, TQ = 0, ntp = 0, ntq = 0;      // rs_conv_plan: output size, tile (TP x TQ <= 128 positions), tiles per utterance
+};
+void rs_conv_plan(RsConvParams& p);
+hipError_t launch_rs_conv(const RsConvParams& p, int dt, hipStream_t stream);
+// stem: y (B, P, Q, 32) = scale relu(conv3x3(x) + bias) + shift on the fp32 (B, P, Q) input; w tap-major [9][32]
+hipError_t launch_rs_stem(const float* x, const float* w, const float* bias, const float* scale, const float* shift, void* y, int dt, int B, int P, int Q,
+                          hipStream_t stream);
+// gate (B, C) = sigmoid(w2 relu(w1 mean + b1) + b2), mean = the tile sums of rs_conv added in tile order / positions; w1 [16][C], w2 [C][16]
+hipError_t launch_rs_se_gate(const float* part, int ntiles, int B, int C, int positions, const float* w1, const float* b1, const float* w2, const float* b2,
+                             float* gate, hipStream_t stream);
+// out = relu(res' + y gate[b, :]); res' = relu(res) (identity residual) or res (downsample output)
+hipError_t launch_rs_se_apply(const void* y, const void* res, const float* gate, void* out, int dt, int B, int positions, int C, bool res_relu,
+                              hipStream_t stream);
+
 // synthetic waveforms from a counter-based RNG (synth.hip): out (B, L) fp32 = utterances [first_utt, first_utt + B) of the stream `seed`
 hipError_t launch_synth_wave(float* out, uint64_t seed, int64_t first_utt, int B, int L, hipStream_t stream);
 

@@ -1,0 +1,360 @@
+// resnetse.hip — the 2-D kernels of ResNetSE34V2 (reference models/ResNetBaseline.py:141-301, ResNetBlocks.py:211-246) for gfx950.
+//
+// Activations are channels-last (B, P, Q, C): P = frames (the reference's W), Q = mel rows (its H), C innermost, fp32 or bf16.
+//
+// rs_conv_kernel: a KS x KS convolution (KS = 3, zero padding 1; KS = 1, no padding: the downsample), stride 1 or 2, as an implicit GEMM
+// on MFMA.  M = output positions, N = Cout, K = KS KS Cin.
+//   tile    one workgroup = TP x TQ <= 128 output positions of ONE utterance (rs_conv_plan picks TP, TQ for the image) x BN = 32 / 64
+//           output channels; four waves of 32 positions each, NT = BN / 32 accumulators of 32 x 32 per wave.  N = 32 gets the tall tile
+//           (128 x 32), N >= 64 runs 128 x 64 tiles, Cout / 64 of them per position tile (the halo is then re-read from L2).
+//   K loop  the input channels in chunks of 64 bytes (32 bf16 / 16 fp32).  Per chunk the workgroup stages the HALO of its tile —
+//           ((TP - 1) s + KS) x ((TQ - 1) s + KS) positions, zero outside the image, the block's opening ReLU applied on the way — and the
+//           KS KS x BN weight rows of the chunk in LDS once; the nine taps then read their A fragments from the halo at shifted positions.
+//           An utterance's tile never reads another utterance's rows: the halo is addressed by (b, p, q), not by a flat row index.
+//   LDS     64 bytes per position / weight row, its four 16-byte slots XOR-ed with (row >> 2) & 3: sixteen consecutive rows cover the sixteen
+//           slots of a 256-byte bank row, so the ds_read_b128 fragment reads of stride-1 tiles are conflict-free (stride 2: two-way).
+//   MFMA    bf16: v_mfma_f32_32x32x16_bf16, fp32 accumulation; fp32: v_mfma_f32_32x32x2_f32 (exact products, the parity path).
+//   out     y = scale[n] acc + shift[n] (the folded BatchNorm), optional ReLU, stored in the activation type; with `part` also the
+//           per-(tile, channel) sums of y over the tile's valid positions (fp32, fixed order) — the SE squeeze, finished by rs_se_gate in
+//           tile order.  No atomics: permuting the batch permutes every value bit for bit.
+// Every ReLU here is x < 0 ? 0 : x, which keeps a NaN (fmaxf would drop it): a NaN input reaches the embedding of its own utterance.
+#include "common.h"
+#include "kernels.h"
+
+namespace svhip {
+
+namespace {
+
+constexpr int RS_ROWB = 64;            // bytes of one position's channel chunk / one weight row in LDS
+constexpr int RS_HALO_MAX = 56 * 1024; // LDS bytes the halo may take (the weights of a 64-channel tile take 36 KiB)
+
+template <typename T> struct RsMma;
+template <> struct RsMma<float> {
+    static constexpr int EPC = 4, CK = 16;
+    typedef f32x4 chunk_t;
+    static __device__ __forceinline__ void mma(const chunk_t& a, const chunk_t& b, f32x16& c) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ chunk_t zero() { return chunk_t{0.f, 0.f, 0.f, 0.f}; }
+    static __device__ __forceinline__ chunk_t relu(chunk_t v) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = v[j] < 0.0f ? 0.0f : v[j];
+        return v;
+    }
+};
+template <> struct RsMma<bf16_t> {
+    static constexpr int EPC = 8, CK = 32;
+    typedef bf16x8 chunk_t;
+    static __device__ __forceinline__ void mma(const chunk_t& a, const chunk_t& b, f32x16& c) {
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ chunk_t zero() {
+        chunk_t z;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) z[j] = static_cast<bf16_t>(0.0f);
+        return z;
+    }
+    static __device__ __forceinline__ chunk_t relu(chunk_t v) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = static_cast<float>(v[j]) < 0.0f ? static_cast<bf16_t>(0.0f) : v[j];
+        return v;
+    }
+};
+
+__device__ __forceinline__ int rs_slot(int row, int ch) { return row * RS_ROWB + ((ch ^ ((row >> 2) & 3)) << 4); }
+
+template <typename T, int BN, int KS>
+__global__ __launch_bounds__(256) void rs_conv_kernel(RsConvParams p) {
+    typedef RsMma<T> TR;
+    typedef typename TR::chunk_t chunk_t;
+    constexpr int EPC = TR::EPC, CK = TR::CK, NT = BN / 32, NTAPS = KS * KS, PAD = KS / 2;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    const int HP = (p.TP - 1) * p.stride + KS, HQ = (p.TQ - 1) * p.stride + KS;
+    char* halo = smem;
+    char* wl = smem + HP * HQ * RS_ROWB;
+
+    const int nn = p.Cout / BN;         // the channel tiles of one position tile are neighbours in the grid: they share the halo in L2
+    const int tile = blockIdx.x / nn;
+    const int tq_i = tile % p.ntq, t2 = tile / p.ntq;
+    const int tp_i = t2 % p.ntp, b = t2 / p.ntp;
+    const int p0 = tp_i * p.TP, q0 = tq_i * p.TQ;
+    const int ip0 = p0 * p.stride - PAD, iq0 = q0 * p.stride - PAD;
+    const int n0 = (blockIdx.x - tile * nn) * BN;
+    const T* __restrict__ X = reinterpret_cast<const T*>(p.X) + (int64_t)b * p.P * p.Q * p.Cin;
+    const T* __restrict__ W = reinterpret_cast<const T*>(p.W);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 31, fh = lane >> 5;
+    const int mt = p.TP * p.TQ;
+    int abase;                          // this lane's A row: the halo position of its output position at tap (0, 0)
+    {
+        int m = wave * 32 + fr;
+        if (m >= mt) m = 0;             // (rows beyond the tile compute position 0 again; the epilogue drops them)
+        const int tp = m / p.TQ, tq = m - tp * p.TQ;
+        abase = tp * p.stride * HQ + tq * p.stride;
+    }
+
+    f32x16 acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+
+    const int nchunks = p.Cin / CK;
+    const int nhalo = HP * HQ * 4, nw = NTAPS * BN * 4;
+    for (int c = 0; c < nchunks; ++c) {
+        if (c) __syncthreads();         // the previous chunk's fragments have been read
+        for (int idx = tid; idx < nhalo; idx += 256) {
+            const int pos = idx >> 2, ch = idx & 3;
+            const int hp = pos / HQ, hq = pos - hp * HQ;
+            const int ip = ip0 + hp, iq = iq0 + hq;
+            chunk_t v = TR::zero();
+            if (ip >= 0 && ip < p.P && iq >= 0 && iq < p.Q) {
+                v = *reinterpret_cast<const chunk_t*>(X + ((int64_t)ip * p.Q + iq) * p.Cin + c * CK + ch * EPC);
+                if (p.relu_in) v = TR::relu(v);
+            }
+            *reinterpret_cast<chunk_t*>(halo + rs_slot(pos, ch)) = v;
+        }
+        for (int idx = tid; idx < nw; idx += 256) {
+            const int row = idx >> 2, ch = idx & 3;
+            const int tap = row / BN, n = row - tap * BN;
+            *reinterpret_cast<chunk_t*>(wl + rs_slot(row, ch)) =
+                *reinterpret_cast<const chunk_t*>(W + (((int64_t)c * NTAPS + tap) * p.Cout + n0 + n) * CK + ch * EPC);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int tap = 0; tap < NTAPS; ++tap) {
+            const int pos = abase + (tap / KS) * HQ + (tap % KS);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int ch = 2 * s + fh;
+                const chunk_t a = *reinterpret_cast<const chunk_t*>(halo + rs_slot(pos, ch));
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    const chunk_t w = *reinterpret_cast<const chunk_t*>(wl + rs_slot(tap * BN + j * 32 + fr, ch));
+                    TR::mma(a, w, acc[j]);
+                }
+            }
+        }
+    }
+
+    // ---- epilogue: BN affine, optional ReLU, store; per-tile channel sums -------------------------------------------
+    T* __restrict__ Y = reinterpret_cast<T*>(p.Y) + (int64_t)b * p.Po * p.Qo * p.Cout;
+    float csum[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) csum[j] = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+        const int tp = m / p.TQ, tq = m - tp * p.TQ;
+        const int po = p0 + tp, qo = q0 + tq;
+        const bool ok = m < mt && po < p.Po && qo < p.Qo;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int n = n0 + j * 32 + fr;
+            float v = fmaf(acc[j][r], p.scale[n], p.shift[n]);
+            if (p.relu_out) v = v < 0.0f ? 0.0f : v;
+            if (ok) {
+                Y[((int64_t)po * p.Qo + qo) * p.Cout + n] = from_f32<T>(v);
+                csum[j] += v;
+            }
+        }
+    }
+    if (p.part) {
+        __syncthreads();                // (the LDS is free: every wave has left the K loop)
+        float* red = reinterpret_cast<float*>(smem);          // [4 waves][BN]
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const float other = __shfl_xor(csum[j], 32, 64);
+            if (fh == 0) red[wave * BN + j * 32 + fr] = csum[j] + other;
+        }
+        __syncthreads();
+        if (tid < BN) {
+            const float s = ((red[tid] + red[BN + tid]) + red[2 * BN + tid]) + red[3 * BN + tid];
+            p.part[(int64_t)tile * p.Cout + n0 + tid] = s;
+        }
+    }
+}
+
+template <typename T, int BN, int KS>
+hipError_t rs_conv_launch(const RsConvParams& p, hipStream_t stream) {
+    const int HP = (p.TP - 1) * p.stride + KS, HQ = (p.TQ - 1) * p.stride + KS;
+    const size_t lds = (size_t)HP * HQ * RS_ROWB + (size_t)KS * KS * BN * RS_ROWB;
+    static DeviceOnce attr;
+    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(rs_conv_kernel<T, BN, KS>), RS_HALO_MAX + 9 * 64 * RS_ROWB)) return e;
+    dim3 grid((unsigned)(p.B * p.ntp * p.ntq * (p.Cout / BN))), block(256);
+    hipLaunchKernelGGL((rs_conv_kernel<T, BN, KS>), grid, block, lds, stream, p);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t rs_conv_t(const RsConvParams& p, hipStream_t stream) {
+    if (p.Cout == 32) return p.ks == 3 ? rs_conv_launch<T, 32, 3>(p, stream) : rs_conv_launch<T, 32, 1>(p, stream);
+    return p.ks == 3 ? rs_conv_launch<T, 64, 3>(p, stream) : rs_conv_launch<T, 64, 1>(p, stream);
+}
+
+// ---- stem: Conv2d(1, 32, 3, padding 1) + bias -> ReLU -> BatchNorm on the normalised (B, P, Q) fp32 input ------------------------
+// One thread = one position x 8 channels (four threads per position write 16 / 32 consecutive bytes each); w tap-major [9][32].
+template <typename T>
+__global__ __launch_bounds__(256) void rs_stem_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                      const float* __restrict__ scale, const float* __restrict__ shift, T* __restrict__ y,
+                                                      int B, int P, int Q) {
+    __shared__ float sw[9 * 32 + 3 * 32];
+    for (int i = threadIdx.x; i < 9 * 32; i += 256) sw[i] = w[i];
+    if (threadIdx.x < 32) {
+        sw[288 + threadIdx.x] = bias[threadIdx.x];
+        sw[320 + threadIdx.x] = scale[threadIdx.x];
+        sw[352 + threadIdx.x] = shift[threadIdx.x];
+    }
+    __syncthreads();
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t pos = idx >> 2;
+    if (pos >= (int64_t)B * P * Q) return;
+    const int cg = (int)(idx & 3) * 8;
+    const int q = (int)(pos % Q);
+    const int64_t bp = pos / Q;
+    const int pp = (int)(bp % P);
+    const float* __restrict__ xb = x + (bp - pp) * Q;          // the utterance's (P, Q) image
+    float in[9];
+#pragma unroll
+    for (int dp = 0; dp < 3; ++dp)
+#pragma unroll
+        for (int dq = 0; dq < 3; ++dq) {
+            const int ip = pp + dp - 1, iq = q + dq - 1;
+            in[dp * 3 + dq] = (ip >= 0 && ip < P && iq >= 0 && iq < Q) ? xb[(int64_t)ip * Q + iq] : 0.0f;
+        }
+    T* __restrict__ yo = y + pos * 32 + cg;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int c = cg + k;
+        float v = sw[288 + c];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) v = fmaf(sw[t * 32 + c], in[t], v);
+        v = v < 0.0f ? 0.0f : v;
+        yo[k] = from_f32<T>(fmaf(v, sw[320 + c], sw[352 + c]));
+    }
+}
+
+// ---- SE gate from the per-tile sums: gate[b, c] = sigmoid(W2 relu(W1 mean + b1) + b2), 16 hidden units ---------------------------
+// One workgroup per utterance; the tiles are added in index order.  w1 [16][C], w2 [C][16], fp32.
+__global__ __launch_bounds__(256) void rs_se_gate_kernel(const float* __restrict__ part, int ntiles, int C, float inv_n, const float* __restrict__ w1,
+                                                         const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
+                                                         float* __restrict__ gate) {
+    __shared__ float mean[256], hid[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < C) {
+        const float* __restrict__ pp = part + (int64_t)b * ntiles * C + tid;
+        float s = 0.0f;
+        for (int t = 0; t < ntiles; ++t) s += pp[(int64_t)t * C];
+        mean[tid] = s * inv_n;
+    }
+    __syncthreads();
+    for (int j = wave * 4; j < wave * 4 + 4; ++j) {
+        float s = 0.0f;
+        for (int c = lane; c < C; c += 64) s = fmaf(w1[j * C + c], mean[c], s);
+        s = wave_sum(s) + b1[j];
+        if (lane == 0) hid[j] = s < 0.0f ? 0.0f : s;
+    }
+    __syncthreads();
+    if (tid < C) {
+        float s = b2[tid];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) s = fmaf(w2[tid * 16 + j], hid[j], s);
+        gate[(int64_t)b * C + tid] = 1.0f / (1.0f + expf(-s));
+    }
+}
+
+// ---- out = relu(res + y * gate[b, :]); res = relu(x) (the identity residual: the block's in-place ReLU has already overwritten x,
+// ResNetBlocks.py:230-231) or the downsample output as it is ---------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void rs_se_apply_kernel(const T* __restrict__ y, const T* __restrict__ res, const float* __restrict__ gate,
+                                                          T* __restrict__ out, int64_t nvec, int per_utt_vec, int cvec, int res_relu) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nvec) return;
+    constexpr int N = Vec16<T>::N;
+    const int b = (int)(i / per_utt_vec);
+    const int c0 = (int)(i % cvec) * N;
+    const Vec16<T> yv = ld_nt(y + i * N), rv = ld_nt(res + i * N);
+    const float* __restrict__ g = gate + (int64_t)b * cvec * N + c0;
+    Vec16<T> o;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        float r = rv.get(k);
+        if (res_relu) r = r < 0.0f ? 0.0f : r;
+        const float v = fmaf(yv.get(k), g[k], r);
+        o.set(k, v < 0.0f ? 0.0f : v);
+    }
+    *reinterpret_cast<decltype(o.v)*>(out + i * N) = o.v;
+}
+
+}  // namespace
+
+void rs_conv_plan(RsConvParams& p) {
+    p.Po = rs_out_size(p.P, p.stride);
+    p.Qo = rs_out_size(p.Q, p.stride);
+    double best = -1.0;
+    p.TP = p.TQ = 1;
+    for (int tq = 1; tq <= 32 && tq <= p.Qo; ++tq) {
+        const int tp = 128 / tq < p.Po ? 128 / tq : p.Po;
+        const int64_t halo = (int64_t)((tp - 1) * p.stride + p.ks) * ((tq - 1) * p.stride + p.ks);
+        if (halo * RS_ROWB > RS_HALO_MAX) continue;
+        const double cover = (double)((p.Po + tp - 1) / tp * tp) * ((p.Qo + tq - 1) / tq * tq);
+        // MFMA rows that carry an output, then (a tie-breaker) the halo positions staged per output
+        const double score = ((double)p.Po * p.Qo / cover) * (tp * tq / 128.0) - 0.01 * (double)halo / ((double)tp * tq * p.stride * p.stride);
+        if (score > best) { best = score; p.TP = tp; p.TQ = tq; }
+    }
+    p.ntp = (p.Po + p.TP - 1) / p.TP;
+    p.ntq = (p.Qo + p.TQ - 1) / p.TQ;
+}
+
+hipError_t launch_rs_conv(const RsConvParams& p, int dt, hipStream_t stream) {
+    const int ck = dt == DT_F32 ? 16 : 32;
+    if (dt != DT_F32 && dt != DT_BF16) return hipErrorInvalidValue;
+    if (p.B <= 0 || p.P <= 0 || p.Q <= 0 || p.Cin <= 0 || p.Cin % ck != 0 || p.Cout <= 0 || p.Cout % 32 != 0 || (p.Cout != 32 && p.Cout % 64 != 0))
+        return hipErrorInvalidValue;
+    if ((p.ks != 3 && p.ks != 1) || (p.stride != 1 && p.stride != 2) || !p.X || !p.Y || !p.W || !p.scale || !p.shift) return hipErrorInvalidValue;
+    if (p.Po != rs_out_size(p.P, p.stride) || p.Qo != rs_out_size(p.Q, p.stride) || p.TP < 1 || p.TQ < 1 || p.TP * p.TQ > 128 ||
+        p.ntp != (p.Po + p.TP - 1) / p.TP || p.ntq != (p.Qo + p.TQ - 1) / p.TQ ||
+        (int64_t)((p.TP - 1) * p.stride + p.ks) * ((p.TQ - 1) * p.stride + p.ks) * RS_ROWB > RS_HALO_MAX)
+        return hipErrorInvalidValue;
+    if ((int64_t)p.B * p.ntp * p.ntq * (p.Cout / 32) > 0x7fffffffLL) return hipErrorInvalidValue;
+    return dt == DT_F32 ? rs_conv_t<float>(p, stream) : rs_conv_t<bf16_t>(p, stream);
+}
+
+hipError_t launch_rs_stem(const float* x, const float* w, const float* bias, const float* scale, const float* shift, void* y, int dt, int B, int P, int Q,
+                          hipStream_t stream) {
+    if (dt != DT_F32 && dt != DT_BF16) return hipErrorInvalidValue;
+    const int64_t n = (int64_t)B * P * Q * 4;
+    dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (dt == DT_F32) hipLaunchKernelGGL(rs_stem_kernel<float>, grid, block, 0, stream, x, w, bias, scale, shift, (float*)y, B, P, Q);
+    else hipLaunchKernelGGL(rs_stem_kernel<bf16_t>, grid, block, 0, stream, x, w, bias, scale, shift, (bf16_t*)y, B, P, Q);
+    return hipGetLastError();
+}
+
+hipError_t launch_rs_se_gate(const float* part, int ntiles, int B, int C, int positions, const float* w1, const float* b1, const float* w2, const float* b2,
+                             float* gate, hipStream_t stream) {
+    if (C > 256 || C % 32 != 0 || ntiles <= 0 || positions <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rs_se_gate_kernel, dim3(B), dim3(256), 0, stream, part, ntiles, C, 1.0f / (float)positions, w1, b1, w2, b2, gate);
+    return hipGetLastError();
+}
+
+hipError_t launch_rs_se_apply(const void* y, const void* res, const float* gate, void* out, int dt, int B, int positions, int C, bool res_relu,
+                              hipStream_t stream) {
+    if (dt != DT_F32 && dt != DT_BF16) return hipErrorInvalidValue;
+    const int nv = dt == DT_F32 ? 4 : 8;
+    if (C % nv != 0) return hipErrorInvalidValue;
+    const int cvec = C / nv;
+    const int64_t per = (int64_t)positions * cvec, nvec = per * B;
+    if (per > 0x7fffffffLL) return hipErrorInvalidValue;
+    dim3 grid((unsigned)((nvec + 255) / 256)), block(256);
+    if (dt == DT_F32)
+        hipLaunchKernelGGL(rs_se_apply_kernel<float>, grid, block, 0, stream, (const float*)y, (const float*)res, gate, (float*)out, nvec, (int)per, cvec, res_relu ? 1 : 0);
+    else
+        hipLaunchKernelGGL(rs_se_apply_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)y, (const bf16_t*)res, gate, (bf16_t*)out, nvec, (int)per, cvec,
+                           res_relu ? 1 : 0);
+    return hipGetLastError();
+}
+
+}  // namespace svhip

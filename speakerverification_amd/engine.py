@@ -93,7 +93,7 @@ class Engine:
         cfg = _lib.default_config()
         cfg.model = {"ecapa": _lib.MODEL_ECAPA, "rawnet2": _lib.MODEL_RAWNET2, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV,
                      "rawnet2_gru": _lib.MODEL_RAWNET2_GRU, "rawnet3": _lib.MODEL_RAWNET3, "titanet": _lib.MODEL_TITANET,
-                     "conformer": _lib.MODEL_CONFORMER, "none": _lib.MODEL_NONE}[model]
+                     "conformer": _lib.MODEL_CONFORMER, "resnetse": _lib.MODEL_RESNETSE, "none": _lib.MODEL_NONE}[model]
         cfg.compute = {"f32": _lib.F32, "fp32": _lib.F32, "bf16": _lib.BF16, "f32x3": _lib.F32X3, "bf16x3": _lib.F32X3,
                        "f16": _lib.F16, "fp16": _lib.F16}[compute]
         cfg.device = int(device)

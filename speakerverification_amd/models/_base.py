@@ -102,7 +102,8 @@ class HipModule:
         mid, sd = checkpoint.read_blob(path)
         want = {"ecapa": _lib.MODEL_ECAPA, "rawnet2": _lib.MODEL_RAWNET2, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV,
                 "rawnet2_gru": _lib.MODEL_RAWNET2_GRU, "rawnet3": _lib.MODEL_RAWNET3,
-                "titanet": _lib.MODEL_TITANET, "conformer": _lib.MODEL_CONFORMER}.get(self.model_kind)
+                "titanet": _lib.MODEL_TITANET, "conformer": _lib.MODEL_CONFORMER,
+                "resnetse": _lib.MODEL_RESNETSE}.get(self.model_kind)
         if want is not None and mid != want:
             raise ValueError(f"{path} holds weights of model {mid}, this module is {self.model_kind}")
         return self.load_state_dict(sd, strict=False)

@@ -11,6 +11,7 @@ source of truth for the *names and shapes* of the reference state dicts
                   ``MainModel``: 234 tensors),
   * TitaNet     — reference ``src/models/TitaNet.py`` + ``blocks/titanet_blocks.py`` (sizes s / m / l, any block count),
   * Conformer   — reference ``src/models/Conformer.py`` + ``models/conformer/conformer/*`` (278 tensors at n_mels 80),
+  * ResNetSE34V2 — reference ``src/models/ResNetSE34V2.py`` + ``ResNetBaseline.py`` + ``ResNetBlocks.py`` (292 tensors),
 
 and generates values from a ``numpy`` PCG64 stream in state-dict order, so the CPU oracle and the
 HIP path see bit-identical weights on any machine.  ``tests/test_oracle_golden.py`` checks the
@@ -297,6 +298,41 @@ def conformer_param_spec(nOut=512, n_mels=80, attention_dim=128):
     spec += [("attention.0.weight", (attention_dim, D, 1)), ("attention.0.bias", (attention_dim,))] + _bn("attention.2", attention_dim)
     spec += [("attention.3.weight", (D, attention_dim, 1)), ("attention.3.bias", (D,))] + _bn("attention_norm", 2 * D)
     spec += [("fc.conv.weight", (nOut, 2 * D, 1)), ("fc.conv.bias", (nOut,))]
+    return spec
+
+
+RESNETSE_BLOCKS = {"ResNetSE34V2": ((3, 4, 6, 3), (32, 64, 128, 256))}     # blocks per stage, widths (ResNetSE34V2.py:5-9)
+RESNETSE_SE_HIDDEN = 16                              # SEBasicBlockV2's `reduction`, which SELayer takes as its hidden width
+RESNETSE_ATT = 128                                   # att_dim
+
+
+def resnetse_frames(T, n_mels=80):
+    """(frames, mel rows) that reach the pooling: three Conv2d(3, stride 2, padding 1)"""
+    for _ in range(3):
+        T, n_mels = (T - 1) // 2 + 1, (n_mels - 1) // 2 + 1
+    return T, n_mels
+
+
+def resnetse_param_spec(nOut=256, n_mels=80, encoder_type="ASP", arch="ResNetSE34V2"):
+    """Ordered (name, shape) list == ``ResNetSE34V2.MainModel(nOut, n_mels=n_mels, encoder_type=...).state_dict()`` of the reference
+    (ResNetBaseline.py:141-243, ResNetBlocks.py:211-246,292-307): 292 tensors"""
+    blocks, widths = RESNETSE_BLOCKS[arch]
+    spec = [("conv1.weight", (widths[0], 1, 3, 3)), ("conv1.bias", (widths[0],))] + _bn("bn1", widths[0])
+    inpl = widths[0]
+    for s, (n, C) in enumerate(zip(blocks, widths)):
+        for j in range(n):
+            p = f"layer{s + 1}.{j}."
+            spec += [(p + "conv1.weight", (C, inpl, 3, 3))] + _bn(p + "bn1", C)
+            spec += [(p + "conv2.weight", (C, C, 3, 3))] + _bn(p + "bn2", C)
+            spec += [(p + "se.fc.0.weight", (RESNETSE_SE_HIDDEN, C)), (p + "se.fc.0.bias", (RESNETSE_SE_HIDDEN,)),
+                     (p + "se.fc.2.weight", (C, RESNETSE_SE_HIDDEN)), (p + "se.fc.2.bias", (C,))]
+            if j == 0 and s > 0:
+                spec += [(p + "downsample.0.weight", (C, inpl, 1, 1))] + _bn(p + "downsample.1", C)
+            inpl = C
+    F = widths[3] * (n_mels // 8)
+    spec += [("attention.0.weight", (RESNETSE_ATT, F, 1)), ("attention.0.bias", (RESNETSE_ATT,))] + _bn("attention.2", RESNETSE_ATT)
+    spec += [("attention.3.weight", (F, RESNETSE_ATT, 1)), ("attention.3.bias", (F,))]
+    spec += [("fc.weight", (nOut, F if encoder_type == "SAP" else 2 * F)), ("fc.bias", (nOut,))]
     return spec
 
 
