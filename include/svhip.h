@@ -119,7 +119,7 @@ typedef struct svhip_config {
     int32_t n_mels;         /* 80 */
     int32_t embed_dim;      /* nOut: 192 (ECAPA) / 320 (RawNet2) */
     int32_t max_batch;      /* workspace is sized for max_batch utterances per call */
-    int32_t samples;        /* L: samples per utterance (32000); fixes T = L/hop + 1 */
+    int32_t samples;        /* L: samples per utterance (32000); fixes T = L/hop + 1 of the fixed-length calls and the row capacity max_batch * T of the ragged ones */
     int32_t log_input;      /* ECAPA: 1 = features=='melspectrogram' -> log(x+1e-6) - mean_t (ECAPA_TDNN.py:473-476) */
     int32_t input_norm;     /* ECAPA: InstanceNorm1d(n_mels, affine) (ECAPA_TDNN.py:406-409,477-478) */
     /* mel front-end — defaults of models/FeatureExtraction/feature.py:66-71 */
@@ -175,6 +175,35 @@ int svhip_embed_features(svhip_handle* h, const float* feat, int32_t B, int32_t 
 /* Fused waveform -> embedding: SpeakerEncoder.forward with label=None (src/model.py:104-125):
  * compute_features then __S__.forward (ECAPA), or __S__.forward directly (RawNet2). */
 int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, float* emb_out, int32_t flags);
+
+/* Ragged batches (added under ABI v5): n utterances of DIFFERENT lengths, packed back to back, embedded by one call on one handle, each
+ * exactly as if it had been forwarded alone at its own length — whole-file evaluation (num_eval = 0: loadWAV returns the entire file,
+ * src/processing/audio_loader.py:144-145, and evaluateFromList runs one forward per file, src/model.py:386-394) without a handle per length.
+ *   wave     : utterance i is wav[offsets[i] .. offsets[i] + lengths[i]); T_i = lengths[i] / hop + 1 frames.
+ *   features : utterance i is an (n_mels, frames[i]) fp32 block (mel power, as svhip_fbank writes it) at feat + n_mels * frame_offsets[i].
+ * offsets / lengths (frame_offsets / frames) are HOST arrays, copied before the call returns; wav / feat / emb_out follow `flags` like
+ * svhip_embed_wave (SVHIP_ASYNC needs device pointers).  emb_out is (n, nOut) fp32.
+ * CAPACITY, checked on the host before anything is enqueued (svhip_ragged_check is the same test without a handle):
+ *   1 <= n <= max_batch;  sum_i T_i <= max_batch * T, the rows of the workspace the handle owns (T = samples / hop + 1);  every
+ *   T_i >= 5 (block 3 reflect-pads 4 frames);  wave: every lengths[i] >= n_fft;  offsets >= 0.
+ * Anything else is SVHIP_ERR_INVALID with a message that names the utterance and the limit.  SVHIP_MODEL_ECAPA with compute SVHIP_F32 or
+ * SVHIP_BF16 only: every other model and SVHIP_F32X3 return SVHIP_ERR_UNSUPPORTED.  The first ragged call of a handle allocates the
+ * segment tables and a waveform staging buffer (once; nothing is allocated per call).
+ * BATCH INVARIANCE: an utterance's embedding and stages are bit-for-bit the same whatever it is packed with and wherever it sits in the
+ * pack — every reduction over time walks the utterance's own frames in an order fixed by the frame index, and every GEMM of the ragged
+ * forward runs on one kernel whatever the row count.  Against a fixed-length call of the same utterance the values agree to the
+ * precision of the compute type (the two forwards take different kernels), not bit for bit.
+ * STAGES after a ragged call (svhip_get_stage): the names of the ECAPA forward; per-frame tensors come back with the rows packed,
+ * (sum_i T_i, channels) in utterance order, per-utterance vectors as (n, .); "mel" is the utterances' (n_mels, T_i) blocks back to back.
+ * The numeric status (SVHIP_ERR_NONFINITE) is reported as after any forward. */
+int svhip_embed_wave_ragged(svhip_handle* h, const float* wav, const int64_t* offsets, const int32_t* lengths,
+                            int32_t n, float* emb_out, int32_t flags);
+int svhip_embed_features_ragged(svhip_handle* h, const float* feat, const int64_t* frame_offsets, const int32_t* frames,
+                                int32_t n, float* emb_out, int32_t flags);
+/* The capacity and scope rules of the two calls above for a handle of configuration *cfg, on the host alone (no GPU is touched):
+ * lengths[i] are samples (is_wave != 0) or frames.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is
+ * svhip_last_error(NULL). */
+int svhip_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave);
 
 /* Eval-mode cropping on device.  Replaces, for decoded 16-bit PCM, the cropping half of loadWAV
  * (src/processing/audio_loader.py:110-150): wrap-pad files not longer than L to L+1 samples, take num_eval

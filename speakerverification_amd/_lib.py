@@ -69,6 +69,9 @@ _SIGNATURES = {
     "svhip_fbank": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "svhip_embed_features": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "svhip_embed_wave": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "svhip_embed_wave_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32]),
+    "svhip_embed_features_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32]),
+    "svhip_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),
     "svhip_crop_pcm16": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     "svhip_l2norm": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32]),
     "svhip_score_pairs": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32]),

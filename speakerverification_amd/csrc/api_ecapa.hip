@@ -375,6 +375,188 @@ int ecapa_embed_wave(svhip_handle* h, const float* d_wav, int B) {
     return rc;
 }
 
+// ---- ragged batches ------------------------------------------------------------------------------------
+// The scope and capacity rules of svhip_embed_wave_ragged / svhip_embed_features_ragged (include/svhip.h), on the host alone.
+int ecapa_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
+    char b[256];
+    if (c.model != SVHIP_MODEL_ECAPA) { err = "ragged batches: SVHIP_MODEL_ECAPA only (the other models embed one length per handle)"; return SVHIP_ERR_UNSUPPORTED; }
+    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "ragged batches: compute SVHIP_F32 or SVHIP_BF16 only"; return SVHIP_ERR_UNSUPPORTED; }
+    if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft) { err = "bad hop_length / max_batch / samples"; return SVHIP_ERR_INVALID; }
+    if (n < 1 || n > c.max_batch) {
+        snprintf(b, sizeof(b), "ragged batch of %d utterances outside [1, max_batch=%d]", n, c.max_batch);
+        err = b; return SVHIP_ERR_INVALID;
+    }
+    const int64_t cap = (int64_t)c.max_batch * (c.samples / c.hop_length + 1);
+    int64_t rows = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t len = lengths[i];
+        if (is_wave && len < c.n_fft) {
+            snprintf(b, sizeof(b), "utterance %d: %lld samples, fewer than n_fft=%d", i, (long long)len, c.n_fft);
+            err = b; return SVHIP_ERR_INVALID;
+        }
+        const int64_t T = is_wave ? len / c.hop_length + 1 : len;
+        if (T < 5) {
+            snprintf(b, sizeof(b), "utterance %d: %lld frames, fewer than 5 (block 3 reflect-pads 4 frames on each side)", i, (long long)T);
+            err = b; return SVHIP_ERR_INVALID;
+        }
+        rows += T;
+        if (rows > cap) {
+            snprintf(b, sizeof(b), "utterance %d: the pack reaches %lld frames, over the handle's capacity of max_batch * T = %lld rows", i,
+                     (long long)rows, (long long)cap);
+            err = b; return SVHIP_ERR_INVALID;
+        }
+    }
+    return SVHIP_OK;
+}
+
+// the segment tables, the waveform staging buffer and the pinned table slots: once per handle
+static int ecapa_ragged_alloc(svhip_handle* h) {
+    if (h->rag_utt) return SVHIP_OK;
+    const svhip_config& c = h->cfg;
+    const size_t B = c.max_batch;
+    int rc;
+    char* tab = nullptr;
+    if ((rc = dev_alloc(h, &tab, B * 8 + (B + 1) * 4))) return rc;
+    h->rag_feat_off = reinterpret_cast<int64_t*>(tab);
+    h->rag_row0 = reinterpret_cast<int*>(tab + B * 8);
+    if ((rc = dev_alloc(h, &h->rag_wav, B * ((size_t)c.samples + c.hop_length)))) return rc;
+    if ((rc = dev_alloc(h, &h->rag_stats, B * c.n_mels * 2))) return rc;
+    for (auto& sl : h->rag_slot) {
+        SV_HIP(h, hipHostMalloc((void**)&sl.host, B * 8 + (B + 1) * 4, hipHostMallocDefault));
+        SV_HIP(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    }
+    return dev_alloc(h, &h->rag_utt, B * (size_t)h->T);
+}
+
+// ECAPA_TDNN.forward over the packed rows of a ragged batch (features at d_feat + rag_feat_off[u]; tables on the device).  One slice on
+// the handle's stream.  Every GEMM goes to the generic kernel (launch_gemm_ragged: one kernel at every row count, so that a row's sums
+// do not depend on the pack); the convolutions gather through the segment table; the reductions over time are ragged.hip's.
+static int ecapa_forward_ragged(svhip_handle* h, const float* d_feat, int n, int M, int maxT) {
+    const svhip_config& c = h->cfg;
+    const int C = c.channels, C3 = 3 * C, C8 = C / 8, e = h->esz;
+    const bool bf = h->bf16;
+    hipStream_t st = h->cur = h->stream;
+    const int *row0 = h->rag_row0, *utt = h->rag_utt;
+    int rc;
+    auto gemm = [&](const ConvLayer& L, GemmParams p, const char* label) {
+        p.rag_utt = utt; p.rag_row0 = row0;
+        return run(h, label, (double)M * L.flops_per_row, [&]() { return launch_gemm_ragged(p, bf, st); });
+    };
+    if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(row0, n, maxT, h->rag_utt, st); }))) return rc;
+    if ((rc = run(h, "rag_prologue", 0, [&]() {
+             return launch_rag_prologue(d_feat, h->rag_feat_off, row0, n, maxT, h->X_in, bf, c.n_mels, c.log_input, h->in_w, h->in_b, h->rag_stats, st);
+         }))) return rc;
+    {
+        GemmParams p = conv_params(h, h->blocks0, h->X_in, c.n_mels, h->X0, C, M, 1);
+        p.act1 = ACT_GELU;
+        if ((rc = gemm(h->blocks0, p, "rag_gemm_conv"))) return rc;
+    }
+    const void* xin = h->X0;
+    int ldin = C;
+    for (int i = 0; i < 3; ++i) {
+        GemmParams p1 = conv_params(h, h->tdnn1[i], xin, ldin, h->H1, C, M, 1);
+        p1.act1 = ACT_GELU;
+        if ((rc = gemm(h->tdnn1[i], p1, "rag_gemm"))) return rc;
+        if ((rc = run(h, "copy_cols", 0, [&]() { return launch_copy_cols(h->H1, C, h->H2, C, bf, M, C8, st); }))) return rc;
+        for (int j = 1; j < 8; ++j) {
+            GemmParams p = conv_params(h, h->res2[i][j - 1], off(h->H1, (size_t)j * C8, e), C, off(h->H2, (size_t)j * C8, e), C, M, 1);
+            p.act1 = ACT_RELU;
+            p.A2 = j >= 2 ? off(h->H2, (size_t)(j - 1) * C8, e) : nullptr; p.lda2 = C;
+            if ((rc = gemm(h->res2[i][j - 1], p, j >= 2 ? "rag_gemm_conv_add" : "rag_gemm_conv"))) return rc;
+        }
+        GemmParams p2 = conv_params(h, h->tdnn2[i], h->H2, C, h->H3, C, M, 1);
+        p2.act1 = ACT_GELU;
+        if ((rc = gemm(h->tdnn2[i], p2, "rag_gemm"))) return rc;
+        if ((rc = run(h, "rag_se_mean", 0, [&]() { return launch_rag_colstats(h->H3, bf, C, row0, n, C, h->d_mean, false, 0.0f, st); }))) return rc;
+        if ((rc = run(h, "se_mlp", 4.0 * n * 128 * C, [&]() {
+                 return launch_se_mlp(h->d_mean, nullptr, 1, bf ? (const void*)h->se1_bf[i] : (const void*)h->se1[i].W, h->se1[i].bias,
+                                      bf ? (const void*)h->se2T_bf[i] : (const void*)h->se2T[i], h->se2[i].bias, h->d_s2, bf, n, C, 128, st, 8);
+             }))) return rc;
+        void* xout = off(h->CAT, (size_t)i * C, e);
+        if ((rc = run(h, "rag_se_apply", 0, [&]() { return launch_rag_se_apply(h->H3, C, h->d_s2, xin, ldin, xout, C3, bf, utt, M, C, st); }))) return rc;
+        xin = xout;
+        ldin = C3;
+    }
+    GemmParams pm = conv_params(h, h->mfa, h->CAT, C3, h->MFA, C3, M, 1);
+    pm.act1 = ACT_GELU;
+    if ((rc = gemm(h->mfa, pm, "rag_gemm"))) return rc;
+    if ((rc = run(h, "rag_asp_gstats", 0, [&]() { return launch_rag_colstats(h->MFA, bf, C3, row0, n, C3, h->d_gstats, true, 1e-12f, st); }))) return rc;
+    if ((rc = run(h, "rag_asp_ctx", 2.0 * n * 128 * 2 * C3, [&]() {
+             return launch_rag_linear(h->d_gstats, 2 * C3, h->asp_ctx.W, h->asp_ctx.bias, h->d_ctx, 128, n, 128, 2 * C3, ACT_NONE, st);
+         }))) return rc;
+    GemmParams pa = conv_params(h, h->asp_tdnn, h->MFA, C3, h->ATT, 128, M, 1);
+    pa.act1 = ACT_RELU; pa.act2 = ACT_TANH;
+    pa.bias_utt = h->d_ctx; pa.ld_bu = 128;
+    if ((rc = gemm(h->asp_tdnn, pa, "rag_gemm_ctx"))) return rc;
+    GemmParams pl = conv_params(h, h->asp_conv, h->ATT, 128, h->LOGITS, C3, M, 1);
+    pl.out_f32 = 1;
+    if ((rc = gemm(h->asp_conv, pl, "rag_gemm"))) return rc;
+    if ((rc = run(h, "rag_asp_pool", 0, [&]() {
+             return launch_rag_asp_pool(h->LOGITS, h->MFA, bf, C3, row0, n, C3, h->aspbn_scale, h->aspbn_shift, h->d_pool_raw, h->d_pool_bn, 1e-12f, st);
+         }))) return rc;
+    return run(h, "rag_fc", 2.0 * n * h->fc.N * h->fc.K, [&]() {
+        return launch_rag_linear(h->d_pool_bn, 2 * C3, h->fc.W, h->fc.bias, h->d_emb, c.embed_dim, n, c.embed_dim, 2 * C3, ACT_NONE, st);
+    });
+}
+
+int ecapa_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n) {
+    const svhip_config& c = h->cfg;
+    int rc = ecapa_ragged_alloc(h);
+    if (rc) return rc;
+    // the tables of this call, in a pinned slot of the handle: the caller's arrays are free on return
+    svhip_handle::RagSlot& slot = h->rag_slot[h->rag_next];
+    h->rag_next = (h->rag_next + 1) & 3;
+    if (slot.busy) { SV_HIP(h, hipEventSynchronize(slot.done)); slot.busy = false; }
+    const size_t B = c.max_batch;
+    int64_t* feat_off = reinterpret_cast<int64_t*>(slot.host);
+    int* row0 = reinterpret_cast<int*>(slot.host + B * 8);
+    int M = 0, maxT = 0;
+    for (int u = 0; u < n; ++u) {
+        const int T = is_wave ? lengths[u] / c.hop_length + 1 : lengths[u];
+        row0[u] = M;
+        M += T;
+        maxT = std::max(maxT, T);
+    }
+    row0[n] = M;
+    h->cur = h->stream;
+    const float* d_feat = h->d_feat;
+    h->feat_is_stale = false;
+    if (is_wave) {
+        // the mel power of every utterance, (n_mels, T_u) blocks back to back in d_feat.  The DFT kernel is launched once per utterance
+        // (a workgroup of it sees one utterance's samples only, so its values do not depend on the pack)
+        int64_t pos = 0;
+        for (int u = 0; u < n; ++u) {
+            const int L = lengths[u], T = row0[u + 1] - row0[u];
+            const float* w = in + in_off[u];
+            if (in_host) {
+                SV_HIP(h, hipMemcpyAsync(h->rag_wav + pos, w, (size_t)L * 4, hipMemcpyHostToDevice, h->stream));
+                w = h->rag_wav + pos;
+                pos += L;
+            }
+            float* mel = h->d_feat + (size_t)row0[u] * c.n_mels;
+            if ((rc = run(h, "fbank", 0, [&]() { return launch_fbank(h->fb, w, 1, L, T, mel, h->stream); }))) return rc;
+            feat_off[u] = (int64_t)row0[u] * c.n_mels;
+        }
+    } else if (in_host) {
+        for (int u = 0; u < n; ++u) {
+            feat_off[u] = (int64_t)row0[u] * c.n_mels;
+            SV_HIP(h, hipMemcpyAsync(h->d_feat + feat_off[u], in + in_off[u] * c.n_mels, (size_t)lengths[u] * c.n_mels * 4, hipMemcpyHostToDevice, h->stream));
+        }
+    } else {
+        for (int u = 0; u < n; ++u) feat_off[u] = in_off[u] * c.n_mels;
+        d_feat = in;
+        h->feat_is_stale = true;            // (d_feat does not hold this forward's mel power)
+    }
+    SV_HIP(h, hipMemcpyAsync(h->rag_feat_off, slot.host, B * 8 + (size_t)(n + 1) * 4, hipMemcpyHostToDevice, h->stream));
+    SV_HIP(h, hipEventRecord(slot.done, h->stream));
+    slot.busy = true;
+    if ((rc = ecapa_forward_ragged(h, d_feat, n, M, maxT))) return rc;
+    h->lastB = n;
+    h->rag_rows = M;
+    h->x0_is_s32 = h->cat_f32_stale = h->h2_is_s32 = h->h1_split = false;
+    return SVHIP_OK;
+}
+
 int ecapa_stage(svhip_handle* h, const std::string& n, bool fill, StageView& v) {
     const int C = h->cfg.channels, C3 = 3 * C, B = h->lastB;
     const int64_t M = (int64_t)B * h->T;

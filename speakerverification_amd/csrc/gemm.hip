@@ -130,7 +130,8 @@ __device__ __forceinline__ void split_hi_lo(const f32x4& a, const f32x4& b, bf16
 }
 
 // X3 (T = float only, SVHIP_F32X3 handles): every product as three bf16 MFMAs on hi / lo-split fragments (see gemm_pw.hip)
-template <typename T, bool CONV, bool HAS_A2, int EPI, bool X3 = false, bool SEG = false>
+// RAG: a ragged batch (GemmParams::rag_utt / rag_row0) — an utterance's rows and length come from the segment table
+template <typename T, bool CONV, bool HAS_A2, int EPI, bool X3 = false, bool SEG = false, bool RAG = false>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
     typedef MmaTraits<T> TR;
     typedef typename TR::chunk_t chunk_t;
@@ -167,14 +168,22 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
 
     int rowA[4];        // clamped global row
     int uttA[4], tA[4]; // utterance base row and frame index (CONV only)
+    int lenA[4];        // RAG: frames of the row's utterance
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         int m = min(m0 + lr + 32 * i, p.M - 1);
         rowA[i] = m;
         if (CONV) {
+            if (RAG) {
+                const int u = p.rag_utt[m];
+                uttA[i] = p.rag_row0[u];
+                lenA[i] = p.rag_row0[u + 1] - uttA[i];
+                tA[i] = m - uttA[i];
+            } else {
             int b = m / p.T;
             uttA[i] = b * p.T;
             tA[i] = m - b * p.T;
+            }
         }
     }
     int64_t segbase[4];  // SEG: the row's offset in A
@@ -214,8 +223,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
                 } else if (CONV) {
                     int tt = tA[i] + tap_off;
                     bool ok = true;
-                    if (p.pad_mode == PAD_REFLECT) tt = reflect_idx(tt, p.T);
-                    else ok = (tt >= 0) && (tt < p.T);
+                    const int Tn = RAG ? lenA[i] : p.T;
+                    if (p.pad_mode == PAD_REFLECT) tt = reflect_idx(tt, Tn);
+                    else ok = (tt >= 0) && (tt < Tn);
                     if (ok) {
                         const int64_t src = (int64_t)(uttA[i] + tt);
                         v = *reinterpret_cast<const chunk_t*>(Ap + src * p.lda + cc);
@@ -315,7 +325,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
                 const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
                 if (nok && m < p.M) {
                     float v = acc[i][j][r] + bias;
-                    if (p.bias_utt) v += p.bias_utt[(int64_t)(m / p.T) * p.ld_bu + n];
+                    if (p.bias_utt) v += p.bias_utt[(int64_t)(RAG ? p.rag_utt[m] : m / p.T) * p.ld_bu + n];
                     v = epilogue_act1<T, EPI>(v);
                     v = fmaf(v, sc, sh);
                     if (EPI == EPI_RELU_TANH || EPI == EPI_TANH) v = tanhf(v);
@@ -332,14 +342,14 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
     }
 }
 
-template <typename T, bool CONV, bool HAS_A2, int EPI, bool X3, bool SEG = false>
+template <typename T, bool CONV, bool HAS_A2, int EPI, bool X3, bool SEG = false, bool RAG = false>
 hipError_t launch_inst_x(const GemmParams& p, hipStream_t stream) {
     const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
     dim3 grid(ntm * ntn), block(256);
     const size_t lds = 4 * TILE_BYTES;
     static DeviceOnce attr;         // 64 KiB of dynamic LDS per workgroup, raised once per device
-    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(gemm_kernel<T, CONV, HAS_A2, EPI, X3, SEG>), (int)lds)) return e;
-    hipLaunchKernelGGL((gemm_kernel<T, CONV, HAS_A2, EPI, X3, SEG>), grid, block, lds, stream, p);
+    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(gemm_kernel<T, CONV, HAS_A2, EPI, X3, SEG, RAG>), (int)lds)) return e;
+    hipLaunchKernelGGL((gemm_kernel<T, CONV, HAS_A2, EPI, X3, SEG, RAG>), grid, block, lds, stream, p);
     return hipGetLastError();
 }
 
@@ -382,7 +392,42 @@ hipError_t launch_t(const GemmParams& p, hipStream_t stream) {
     return hipErrorInvalidValue;
 }
 
+// the ragged forms ECAPA's forward needs: the k = 5 first convolution (GELU), the Res2Net steps (ReLU, with and without the running
+// sum A2) and asp.tdnn (pointwise, ReLU -> BN -> tanh, bias per utterance)
+template <typename T>
+hipError_t launch_rag_t(const GemmParams& p, hipStream_t stream) {
+    if (p.taps > 1) {
+        if (p.act2 != ACT_NONE) return hipErrorInvalidValue;
+        if (p.act1 == ACT_GELU && !p.A2) return launch_inst_x<T, true, false, EPI_GELU, false, false, true>(p, stream);
+        if (p.act1 == ACT_RELU) return p.A2 ? launch_inst_x<T, true, true, EPI_RELU, false, false, true>(p, stream)
+                                            : launch_inst_x<T, true, false, EPI_RELU, false, false, true>(p, stream);
+        return hipErrorInvalidValue;
+    }
+    if (p.bias_utt && p.act1 == ACT_RELU && p.act2 == ACT_TANH && !p.A2) return launch_inst_x<T, false, false, EPI_RELU_TANH, false, false, true>(p, stream);
+    return hipErrorInvalidValue;
+}
+
 }  // namespace
+
+hipError_t launch_gemm_ragged(const GemmParams& p, bool bf16, hipStream_t stream) {
+    const int epc = bf16 ? 8 : 4;
+    const int bk = gemm_bk(bf16);
+    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.Kp % bk != 0 || p.Kp < p.K || p.Wrows < p.N) return hipErrorInvalidValue;
+    if (p.lda % epc != 0 || (p.A2 && p.lda2 % epc != 0)) return hipErrorInvalidValue;
+    if (p.x3 || p.f16 || p.seg_off || p.A3 || p.colsum || p.y_s32 || p.side_c) return hipErrorInvalidValue;
+    if (p.taps > 1) {
+        if (p.cin % epc != 0 || p.taps * p.cin != p.K) return hipErrorInvalidValue;
+    } else if (p.K % epc != 0) {
+        return hipErrorInvalidValue;
+    }
+    if (p.taps > 1 || p.bias_utt) {          // (what needs the segment table; the caller has checked (taps / 2) dil < T_u for every utterance)
+        if (!p.rag_utt || !p.rag_row0) return hipErrorInvalidValue;
+        return bf16 ? launch_rag_t<bf16_t>(p, stream) : launch_rag_t<float>(p, stream);
+    }
+    GemmParams q = p;                        // plain pointwise layers see M rows and nothing else
+    q.rag_utt = q.rag_row0 = nullptr;
+    return bf16 ? launch_t<bf16_t>(q, stream) : launch_t<float>(q, stream);
+}
 
 GemmRoute gemm_route(const GemmParams& p, bool bf16) {
 #ifdef SVHIP_GEMM_DEBUG

@@ -294,6 +294,16 @@ struct svhip_handle {
     size_t lin_part_per_utt = 0;
     float *d_pool_raw = nullptr, *d_pool_bn = nullptr, *d_emb = nullptr;
     int lastB = 0;
+    // ragged batches (svhip_embed_wave_ragged / svhip_embed_features_ragged; api_ecapa.hip): allocated by the handle's first ragged call
+    int64_t* rag_feat_off = nullptr;          // (max_batch) element offset of every utterance's (n_mels, T_u) block in the feature array
+    int* rag_row0 = nullptr;                  // (max_batch + 1) first workspace row of every utterance, then the row count (behind rag_feat_off)
+    int* rag_utt = nullptr;                   // (max_batch * T) utterance of every row
+    float* rag_wav = nullptr;                 // host-pointer calls: max_batch * (samples + hop) floats, the utterances back to back
+    float* rag_stats = nullptr;               // (max_batch * n_mels * 2) shift / scale of the front-end normalisation
+    struct RagSlot { char* host = nullptr; hipEvent_t done = nullptr; bool busy = false; };
+    RagSlot rag_slot[4];                      // pinned copies of the tables of the calls in flight (SVHIP_ASYNC returns before the copy has run)
+    int rag_next = 0;
+    int64_t rag_rows = 0;                     // rows of the last forward when it was a ragged one (svhip_get_stage), else 0
     // numeric status of the forwards since the last reset: d_status[0] = SVHIP_STATUS_* bits, [1] = non-finite embedding values,
     // [2] = input values beyond the split planes' range; host_flag (pinned, mapped) is set by the same kernels, so that a synchronous
     // call learns of a problem without a copy
@@ -473,6 +483,10 @@ SpecFn ecapa_spec, rawnet2_spec, rawnet3_spec, titanet_spec, conformer_spec, res
 HandleFn ecapa_finalize, rawnet2_finalize, rawnet3_finalize, titanet_finalize, conformer_finalize, resnetse_finalize;
 HandleFn ecapa_alloc, rawnet2_alloc, rawnet3_alloc, titanet_alloc, conformer_alloc, resnetse_alloc;
 EmbedFn ecapa_embed_wave, rawnet2_forward, rawnet3_forward;                    // from the waveform
+// a ragged ECAPA batch: utterance u is `frames[u]` frames long; in_off[u] is where it starts in `in` (samples of a device waveform array,
+// wave; elements of a device feature array, features) or, with in_host, in the host array `in`
+int ecapa_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err);
+int ecapa_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n);
 EmbedFn ecapa_forward, titanet_forward, conformer_forward, resnetse_forward;   // from the mel power
 StageFn ecapa_stage, rawnet2_stage, rawnet3_stage, titanet_stage, conformer_stage, resnetse_stage;
 

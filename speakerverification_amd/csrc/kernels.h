@@ -98,6 +98,11 @@ struct GemmParams {
     const int* seg_off = nullptr;
     int seg_rows = 0, seg_len = 0;
     int64_t seg_utt = 0, seg_stride = 0;
+    // ragged batch (the generic kernel only, through launch_gemm_ragged): utterance u owns the rows [rag_row0[u], rag_row0[u + 1]) and
+    // rag_utt[m] is the utterance of row m.  The conv gather reflects at each utterance's own ends and bias_utt is read at rag_utt[m];
+    // T is not used.  Null (the default): every utterance has T rows.
+    const int* rag_utt = nullptr;
+    const int* rag_row0 = nullptr;
 };
 
 constexpr int GEMM_BM = 128;
@@ -159,6 +164,33 @@ hipError_t launch_in_scale(const float* X, int64_t n, uint32_t* part256, float* 
 hipError_t launch_unsplit_s32(const void* src, int lds32, float* dst, int ld, int64_t M, int K, hipStream_t stream);   // v = hi + lo
 // row groups per 256-row tile in the column-sum partials the routed kernel writes (8: pw2, 2: pw3)
 int gemm_colsum_groups(const GemmParams& p, bool bf16);
+// a GEMM of a ragged batch (fp32 / bf16): ALWAYS the generic kernel, whatever M is — gemm_route picks its kernel by the size of the
+// problem, and the kernels add a row's K products in different orders, so a routed GEMM would make an utterance's values depend on
+// what it is packed with.  With rag_utt / rag_row0 the conv gather and bias_utt follow the segment table (GemmParams).
+hipError_t launch_gemm_ragged(const GemmParams& p, bool bf16, hipStream_t stream);
+
+// ---------------------------------------------------------------------------------------------
+// Ragged batches (ragged.hip): n utterances of T_u frames packed back to back; row0 (n + 1 ints) holds each utterance's first row
+// and the total, utt (M ints) the utterance of every row.  Every reduction over time is one workgroup per (utterance, channel
+// block) that walks the utterance's own frames in an order fixed by the frame index: a value never depends on the neighbours.
+// ---------------------------------------------------------------------------------------------
+hipError_t launch_rag_rows(const int* row0, int n, int maxT, int* utt, hipStream_t stream);
+// features: utterance u is a (n_mels, T_u) fp32 block at feat + feat_off[u] -> rows row0[u] .. of out (M, n_mels) in the compute type:
+// log(x + 1e-6) minus its time mean (log_input), InstanceNorm1d with affine (in_w != null); stats: n * n_mels * 2 floats of scratch
+hipError_t launch_rag_prologue(const float* feat, const int64_t* feat_off, const int* row0, int n, int maxT, void* out, bool out_bf16,
+                               int n_mels, int log_input, const float* in_w, const float* in_b, float* stats, hipStream_t stream);
+// out (n, ld_out) = mean over each utterance's frames of X[:, 0:C) [| population std, two passes, variance clamped below at eps]
+hipError_t launch_rag_colstats(const void* X, bool bf16, int ldx, const int* row0, int n, int C, float* out, bool with_std, float eps,
+                               hipStream_t stream);
+// out[m, c] = h[m, c] * s[utt[m], c] + x[m, c]
+hipError_t launch_rag_se_apply(const void* h, int ldh, const float* s, const void* x, int ldx, void* out, int ldo, bool bf16,
+                               const int* utt, int M, int C, hipStream_t stream);
+// launch_asp_pool's arithmetic over each utterance's own frames
+hipError_t launch_rag_asp_pool(const float* logits, const void* X, bool bf16, int ldx, const int* row0, int n, int C, const float* bn_scale,
+                               const float* bn_shift, float* pooled_raw, float* pooled_bn, float eps, hipStream_t stream);
+// launch_rowvec_linear on ONE kernel at every batch size (a row's sum does not depend on how many rows ride along)
+hipError_t launch_rag_linear(const float* in, int ld_in, const float* W, const float* bias, float* out, int ld_out, int n, int N, int K,
+                             int act, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // Fused Res2Net chain (bf16 path): one workgroup per utterance runs the 7 dependent dilated convs

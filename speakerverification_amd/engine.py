@@ -244,6 +244,64 @@ class Engine:
         self._ck(self.lib.svhip_embed_wave(self.h, i.ptr, B, L, o.ptr, self._flags(i, o, async_)))
         return out
 
+    # ---- ragged batches: utterances of different lengths in one call (svhip_embed_wave_ragged / svhip_embed_features_ragged) ----
+    @property
+    def row_capacity(self):
+        """frames one ragged call can hold: the rows of the handle's workspace, max_batch * T"""
+        return self.max_batch * self.frames
+
+    def frames_of(self, n_samples):
+        return int(n_samples) // int(self.cfg.hop_length) + 1
+
+    def _pack(self, items, offsets, lengths, is_wave):
+        """a list of arrays -> (packed array, int64 offsets, int32 lengths); a packed array with its tables passes through.
+        Offsets and lengths count samples (waveforms) or frames (features: each item (n_mels, T_i), packed as blocks back to back)."""
+        if offsets is not None:
+            if lengths is None:
+                raise ValueError("a packed array needs offsets and lengths")
+            return items, np.ascontiguousarray(offsets, dtype=np.int64), np.ascontiguousarray(lengths, dtype=np.int32)
+        items = list(items)
+        if not items:
+            raise ValueError("empty batch")
+        if not is_wave:
+            for a in items:
+                if a.ndim != 2 or a.shape[0] != self.n_mels:
+                    raise ValueError(f"expected ({self.n_mels}, T) features, got {tuple(a.shape)}")
+        lens = np.asarray([a.shape[-1] for a in items], dtype=np.int32)
+        offs = np.zeros(len(items), dtype=np.int64)
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+        if _is_torch(items[0]):
+            packed = torch.cat([a.to(torch.float32).reshape(-1) for a in items])
+        else:
+            packed = np.concatenate([np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in items])
+        return packed, offs, lens
+
+    def _embed_ragged(self, fn, items, offsets, lengths, out, async_, is_wave):
+        packed, offs, lens = self._pack(items, offsets, lengths, is_wave)
+        n = int(lens.shape[0])
+        if out is None:
+            out = self._out(packed, (n, self.embed_dim))
+        i, o = _Buf(packed, np.float32), _Buf(out, np.float32, writable=True)
+        self._order_after_torch(i, o, async_=async_)
+        _count([i], [o])
+        self._ck(fn(self.h, i.ptr, offs.ctypes.data, lens.ctypes.data, n, o.ptr, self._flags(i, o, async_)))
+        return out
+
+    def embed_wave_ragged(self, wavs, offsets=None, lengths=None, out=None, async_=False):
+        """utterances of different lengths -> (n, embed_dim), each as if forwarded alone at its own length.  ``wavs``: a list of 1-D
+        arrays, or ONE packed array with ``offsets`` / ``lengths`` in samples; numpy or CUDA tensors, like embed_wave."""
+        return self._embed_ragged(self.lib.svhip_embed_wave_ragged, wavs, offsets, lengths, out, async_, True)
+
+    def embed_features_ragged(self, feats, offsets=None, lengths=None, out=None, async_=False):
+        """``feats``: a list of (n_mels, T_i) mel-power arrays, or one packed array of such blocks with frame ``offsets`` / ``lengths``."""
+        return self._embed_ragged(self.lib.svhip_embed_features_ragged, feats, offsets, lengths, out, async_, False)
+
+    def ragged_check(self, lengths, is_wave=True):
+        """the library's own capacity test for a pack (svhip_ragged_check, host only): None, or the refusal's text"""
+        lens = np.ascontiguousarray(lengths, dtype=np.int32)
+        rc = self.lib.svhip_ragged_check(C.byref(self.cfg), lens.ctypes.data, int(lens.shape[0]), 1 if is_wave else 0)
+        return None if rc == _lib.OK else (self.lib.svhip_last_error(None) or b"?").decode()
+
     def crop_pcm16(self, pcm_list, num_eval, L=32000, out=None, async_=False):
         """list of 1-D int16 arrays (decoded files) -> (len(list) * num_eval, L) fp32 eval-mode crops, cropped on
         the device (int16 travels over PCIe; reference semantics of loadWAV for 16-bit files).  With ``out`` a CUDA

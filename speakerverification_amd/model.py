@@ -161,6 +161,7 @@ class ModelHandling:
         self.embed_batch = int(kwargs.get("embed_batch", 256))     # crops per device call (cross-file batching)
         self.device_crop = bool(kwargs.get("device_crop", True))   # 16-bit PCM files: crop on the device (svhip_crop_pcm16)
         self.device_feats = bool(kwargs.get("device_feats", True)) # keep enrol -> score on the device when a GPU is there
+        self.ragged_eval = bool(kwargs.get("ragged_eval", True))   # num_eval == 0: whole files of different lengths share library calls
 
     # ---- training-only surface ---------------------------------------------------------------------------
     def fit(self, *a, **k):
@@ -190,6 +191,14 @@ class ModelHandling:
         if enc.features == "raw":
             return callable(getattr(S, "forward", None)) and getattr(S, "accepts_device_wave", False)
         return hasattr(S, "embed_wave") and enc._fusable()
+
+    def _ragged_ok(self, num_eval):
+        """whole-file evaluation as ragged batches: the model offers embed_ragged and the front-end is the one its handle bakes in"""
+        if num_eval != 0 or not self.ragged_eval:
+            return False
+        enc = self.__model__.module
+        S = getattr(enc, "__S__", None)
+        return S is not None and enc.features != "raw" and hasattr(S, "embed_ragged") and enc._fusable()
 
     def _feats_on_device(self):
         """evaluateFromList / testFromList keep the (n_files, num_eval, nOut) block in HBM from the embed calls to the scoring
@@ -253,6 +262,19 @@ class ModelHandling:
             pcm_pending.clear()
             pcm_owners.clear()
 
+        # num_eval == 0 on a model with embed_ragged: whole files of different lengths are collected up to the capacity of the model's
+        # primary handle and embedded in ONE call per group; a file that fits no call keeps the per-file path below
+        S = getattr(self.__model__.module, "__S__", None) if self._ragged_ok(num_eval) else None
+        packer = S.ragged_packer() if S is not None else None
+        rag_pending, rag_owners = [], []
+
+        def flush_ragged():
+            if rag_pending:
+                store(list(rag_owners), S.embed_ragged(list(rag_pending)))
+                rag_pending.clear()
+                rag_owners.clear()
+                packer.reset()
+
         for idx, f in enumerate(files):
             pcm = read_pcm16(f, self.audio_spec["sample_rate"]) if (use_dev and isinstance(f, (str, Path))) else None
             if pcm is not None:
@@ -263,6 +285,16 @@ class ModelHandling:
                 continue
             audio = loadWAV(f, self.audio_spec, evalmode=True, augment=False, augment_options=[], num_eval=num_eval,
                             random_chunk=False)
+            if packer is not None:
+                wav = np.ascontiguousarray(np.asarray(audio, np.float32).reshape(-1))
+                frames = S.ragged_frames(wav.shape[0])
+                if packer.fits_alone(frames):
+                    if not packer.add(frames):
+                        flush_ragged()
+                        packer.add(frames)
+                    rag_pending.append(wav)
+                    rag_owners.append((idx, 1))
+                    continue
             if num_eval == 0:                       # whole file: variable length, one forward per file
                 flush()
                 store([(idx, 1)], self._embed_crops(audio))
@@ -273,6 +305,7 @@ class ModelHandling:
                 flush()
         flush()
         flush_pcm()
+        flush_ragged()
         return feats
 
     def embed_utterance(self, source, num_eval=20, normalize=False):

@@ -1,0 +1,134 @@
+"""Whole-file evaluation (num_eval = 0) on the MI355X: files/s of `ModelHandling._embed_files` over seeded files of 2 - 20 s.
+
+    python tools/ragged_bench.py [--per-file] [--files 512] [--runs 5] [--compute bf16,f32] [--out profiles/ragged_bench.json]
+
+Default mode: the ragged path of this tree (files of different lengths share calls of the model's primary handle), plus, without a
+bar, the frames/s of the ragged call relative to the fixed-length B = 256 call of the same handle and the library's per-label event
+times of the ragged forward (which ragged kernel to fuse first).
+--per-file: one forward per file on a handle of that file's length — `ragged_eval=False` where the tree knows the keyword, and the
+only path of a tree that does not: the mode uses nothing newer than `_embed_files` and is meant to be run against a checkout of the
+parent commit (put that checkout first on PYTHONPATH), whose files/s are the yardstick.
+
+Own process; every figure is the median of `--runs` timed passes over the whole file list (after one untimed pass), with the spread
+(min, max); wall time and HIP-event time around the whole pass are both given.  ECAPA-TDNN C = 1024, nOut 192."""
+from __future__ import annotations
+
+import argparse
+import inspect
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+if not os.environ.get("RAGGED_BENCH_NO_PATH"):
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch             # noqa: E402
+
+from speakerverification_amd import synth                                                   # noqa: E402
+from speakerverification_amd.model import ModelHandling, SpeakerEncoder, WrappedModel      # noqa: E402
+
+SEED = 20220829
+ARGS = dict(
+    device="cuda", gpu=0, model={"name": "ECAPA_TDNN", "nOut": 192}, criterion={"name": "AAmSoftmaxAP"}, features="melspectrogram",
+    include_top=False, n_mels=80, channels=[1024] * 4 + [3072],
+    audio_spec={"sample_rate": 16000, "channels": 1, "sentence_len": 2.0, "win_len": 0.025, "hop_len": 0.01},
+    augment=False, augment_options={"augment_chain": []},
+)
+
+
+def make_files(n):
+    """n seeded waveforms of 2 - 20 s at 16 kHz (401 - 4001 frames), every length distinct from its neighbours"""
+    rng = np.random.Generator(np.random.PCG64(SEED))
+    lens = rng.integers(32000, 320001, size=n)
+    return [np.clip(0.1 * rng.standard_normal(int(L), dtype=np.float32), -1.0, 1.0) for L in lens]
+
+
+def handler(compute, per_file):
+    kw = dict(ARGS, hip_compute=compute)
+    net = WrappedModel(SpeakerEncoder(**kw))
+    extra = {}
+    if per_file and "ragged_eval" in inspect.getsource(ModelHandling.__init__):
+        extra["ragged_eval"] = False
+    mh = ModelHandling(net, **dict(kw, save_folder=".", device_feats=False, **extra))
+    net.module.load_state_dict({"__S__." + k: v for k, v in synth.synth_state_dict(synth.ecapa_param_spec(C=1024), seed=5).items()})
+    return mh, getattr(net.module, "__S__")
+
+
+def timed(fn, runs):
+    fn()                                                        # untimed: handles, allocations, first launches
+    wall, dev = [], []
+    for _ in range(runs):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        wall.append(time.perf_counter() - t0)
+        dev.append(e0.elapsed_time(e1) * 1e-3)
+    return wall, dev
+
+
+def stats(xs):
+    return {"median": float(np.median(xs)), "min": float(min(xs)), "max": float(max(xs))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--per-file", action="store_true")
+    ap.add_argument("--files", type=int, default=512)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--compute", default="bf16,f32")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    files = make_files(a.files)
+    frames = int(sum(len(f) // 80 + 1 for f in files))
+    res = {"mode": "per_file" if a.per_file else "ragged", "files": a.files, "frames": frames, "runs": a.runs, "model": "ECAPA_TDNN C=1024 nOut=192",
+           "device": torch.cuda.get_device_name(0), "tree_has_ragged_calls": hasattr(ModelHandling, "_ragged_ok")}
+    for compute in a.compute.split(","):
+        mh, S = handler(compute, a.per_file)
+        wall, dev = timed(lambda: mh._embed_files(files, 0), a.runs)
+        r = {"wall_s": stats(wall), "hip_event_s": stats(dev),
+             "files_per_s": {"median": a.files / float(np.median(wall)), "min": a.files / max(wall), "max": a.files / min(wall)},
+             "frames_per_s": frames / float(np.median(wall)), "engines_alive": len(S._engines)}
+        if not a.per_file:
+            eng = S.ragged_engine()
+            # the ragged call against the fixed-length call of the same handle, device-resident input, frames/s of each
+            x = torch.from_numpy(synth.synth_waveforms(eng.max_batch, eng.samples, seed=1)).cuda()
+            pack = [torch.from_numpy(f).cuda() for f in files[:40]]
+            while sum(len(p) // 80 + 1 for p in pack) > eng.row_capacity:
+                pack.pop()
+            packed = torch.cat(pack)
+            lens = [len(p) for p in pack]
+            offs = np.concatenate([[0], np.cumsum(lens)[:-1]])
+            w_fix, _ = timed(lambda: eng.embed_wave(x), a.runs)
+            w_rag, _ = timed(lambda: eng.embed_wave_ragged(packed, offsets=offs, lengths=lens), a.runs)
+            f_fix = eng.max_batch * eng.frames / float(np.median(w_fix))
+            f_rag = sum(n // 80 + 1 for n in lens) / float(np.median(w_rag))
+            r["fixed_B256_frames_per_s"] = f_fix
+            r["ragged_call_frames_per_s"] = f_rag
+            r["ragged_over_fixed"] = f_rag / f_fix
+            eng.profile(True)
+            eng.embed_wave_ragged(packed, offsets=offs, lengths=lens)
+            prof = eng.profile_results()
+            eng.profile(False)
+            r["ragged_forward_kernels_ms"] = {k: {"ms": round(v["ms"], 4), "launches": v["launches"]}
+                                              for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])}
+            r["ragged_forward_pack"] = {"utterances": len(lens), "frames": int(sum(n // 80 + 1 for n in lens))}
+        res[compute] = r
+        print(compute, json.dumps(r["files_per_s"]), flush=True)
+        S._drop_engine()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
