@@ -1,6 +1,6 @@
 // api.hip — C ABI of libsvhip: handle lifetime, developer options, weight loading, embedding, staging, stages and profiling
 // (see include/svhip.h).  The handle is in handle.h; what the models share when weights are loaded in api_weights.hip, the conv-layer
-// GEMM in api_gemm.hip, each model's own host code in its api_<model>.hip (kModels below lists them), scoring and metrics in
+// GEMM in api_gemm.hip, each model's own host code and state in its api_<model>.hip (kModels below lists them), scoring and metrics in
 // api_scoring.hip.
 #include <algorithm>
 #include <cstdlib>
@@ -295,10 +295,7 @@ int svhip_destroy(svhip_handle* h) {
     if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
     for (hipEvent_t e : h->aux_ev) if (e) (void)hipEventDestroy(e);
     for (void* q : h->scr) if (q) (void)hipFree(q);
-    for (auto& sl : h->rag_slot) {
-        if (sl.host) (void)hipHostFree(sl.host);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
+    h->model.reset();          // (ECAPA's releases the pinned slots and events of its ragged calls)
     for (auto& sl : h->crop_slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.dev) (void)hipFree(sl.dev);

@@ -18,6 +18,53 @@
 
 namespace svhip {
 
+namespace {
+
+int cf_sub(int n) { return (n - 3) / 2 + 1; }                         // one Conv2d(3, stride 2) of Conformer's subsampling (n >= 3)
+constexpr int CF_D = 256, CF_LAYERS = 6, CF_MAX_T = 10000;           // d_model, blocks, the length of the pe buffer
+
+struct CfBlock {
+    float *ff_g[2] = {}, *ff_b[2] = {};   // the two feed-forward modules' LayerNorms (FF, FF')
+    ConvLayer ff1[2], ff2[2];             // Linear(256, 1024) (Swish in the epilogue), Linear(1024, 256)
+    float *att_g = nullptr, *att_b = nullptr;
+    ConvLayer qkv, out;                   // query | key | value projections as one 256 -> 768 layer; out_proj
+    float* P = nullptr;                   // (T', 256) fp32: pe[:T'] pos_proj^T (the same for every utterance: formed at finalize)
+    float *u = nullptr, *v = nullptr;     // u_bias, v_bias [4][64]
+    float *cv_g = nullptr, *cv_b = nullptr;
+    ConvLayer pw1, pw2;                   // pointwise 256 -> 512 (GLU follows), 256 -> 256
+    float *dw_w = nullptr, *dw_b = nullptr;   // depthwise k = 15, tap-major [15][256], with BatchNorm(256) folded in
+    float *fin_g = nullptr, *fin_b = nullptr; // the block's final LayerNorm
+};
+
+// Conformer layers (SVHIP_MODEL_CONFORMER: models/Conformer.py, models/conformer/conformer/*).  d_model 256, 4 heads of 64, six blocks.
+// The InstanceNorm affine of the front-end is the handle's in_w / in_b
+struct ConformerState : ModelState {
+    std::vector<CfBlock> blocks;
+    int T1 = 0, F1 = 0, Tp = 0, F2 = 0;   // conv1 / conv2 output sizes: T1 x F1, T' x F2
+    int chunk = 0;                        // utterances per subsampling slice (bounds the conv1 output buffer)
+    float *c1_w = nullptr, *c1_b = nullptr;   // conv_subsample.sequential.0: tap-major [9][256], bias
+    ConvLayer c2;                         // conv_subsample.sequential.2 as a GEMM, k = dt * 768 + df * 256 + c (the segmented gather)
+    int* seg_off = nullptr;               // (T' F2) row offsets of that gather within an utterance's conv1 output
+    ConvLayer proj;                       // input_projection, columns permuted from c * F2 + f to f * 256 + c
+    ConvLayer att0, att3;                 // attention.0 (+ ReLU, attention.2 as the epilogue affine), attention.3 (fp32 logits)
+    float *pbn_scale = nullptr, *pbn_shift = nullptr;   // attention_norm (BatchNorm1d(512))
+    LinearLayer fc;                       // fc (Conv1d(512, nOut, 1))
+    float* half = nullptr;                // 256 x 0.5: the half-step residual as the epilogue scale
+    void *c1 = nullptr, *s2 = nullptr;    // per slice: conv1 output (chunk, T1, F1, 256); conv2 output (chunk T' F2, 256)
+    void *in = nullptr, *b0 = nullptr, *x[2] = {}, *r = nullptr;   // (Bmax T', 256): input projection, block 0's output,
+                                          // later blocks' outputs (ping-pong), the residual stream inside a block
+    void *ln = nullptr, *ln2 = nullptr;   // (Bmax T', 256) LayerNorm outputs
+    void* hid = nullptr;                  // (Bmax T', 1024): FF hidden / q | k | v / pointwise-conv output
+    void *ctx = nullptr, *attn0 = nullptr;   // (Bmax T', 256): attention context (block 0's is kept: stage cf_attn0); GLU-dw output
+    void* last = nullptr;                 // the last block's output
+    float* logits = nullptr;              // (Bmax T', 256) fp32 attention logits of the pooling
+    float *pool_raw = nullptr, *pool = nullptr;         // (Bmax, 512) [mean | std], after attention_norm
+};
+
+ConformerState& S(svhip_handle* h) { return static_cast<ConformerState&>(*h->model); }
+
+}  // namespace
+
 int conformer_check(const svhip_config& c, const char*& err) {
     if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "Conformer runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_UNSUPPORTED; }
     if (c.channels != 0 && c.channels != CF_D) { err = "Conformer is built for d_model = 256 (channels 0 or 256)"; return SVHIP_ERR_INVALID; }
@@ -83,33 +130,34 @@ void conformer_spec(const svhip_config& c, WeightSpec& spec) {
 }
 
 int conformer_finalize(svhip_handle* h) {
+    auto& s = S(h);
     const svhip_config& c = h->cfg;
-    const int D = CF_D, Tp = h->cf_Tp, F2 = h->cf_F2, nOut = c.embed_dim;
+    const int D = CF_D, Tp = s.Tp, F2 = s.F2, nOut = c.embed_dim;
     int rc;
     if ((rc = upload_f32(h, "instance_norm.weight", &h->in_w))) return rc;
     if ((rc = upload_f32(h, "instance_norm.bias", &h->in_b))) return rc;
-    const std::string s = "conformer_block.conv_subsample.sequential.";
+    const std::string sub = "conformer_block.conv_subsample.sequential.";
     {
         const HostTensor* w;                                   // (256, 1, 3, 3) -> tap-major [9][256]
-        if ((rc = needw(h, s + "0.weight", w))) return rc;
+        if ((rc = needw(h, sub + "0.weight", w))) return rc;
         std::vector<float> tw(9 * D);
         for (int ch = 0; ch < D; ++ch)
             for (int t = 0; t < 9; ++t) tw[(size_t)t * D + ch] = w->data[(size_t)ch * 9 + t];
-        if ((rc = dev_upload(h, &h->cf_c1_w, tw))) return rc;
-        if ((rc = upload_f32(h, s + "0.bias", &h->cf_c1_b))) return rc;
+        if ((rc = dev_upload(h, &s.c1_w, tw))) return rc;
+        if ((rc = upload_f32(h, sub + "0.bias", &s.c1_b))) return rc;
     }
     {
         const HostTensor *w, *b;                               // (256, 256, 3, 3) [n][c][dt][df] -> [n][dt * 768 + df * 256 + c]
-        if ((rc = needw(h, s + "2.weight", w))) return rc;
+        if ((rc = needw(h, sub + "2.weight", w))) return rc;
         std::vector<float> pw((size_t)D * 9 * D);
         for (int n = 0; n < D; ++n)
             for (int ch = 0; ch < D; ++ch)
                 for (int t = 0; t < 9; ++t) pw[(size_t)n * 9 * D + (size_t)(t / 3) * 3 * D + (t % 3) * D + ch] = w->data[((size_t)n * D + ch) * 9 + t];
-        if ((rc = needw(h, s + "2.bias", b)) || (rc = make_conv(h, h->cf_c2, HostTensor{std::move(pw), {D, 9 * D, 1}}, &b->data, 1))) return rc;
+        if ((rc = needw(h, sub + "2.bias", b)) || (rc = make_conv(h, s.c2, HostTensor{std::move(pw), {D, 9 * D, 1}}, &b->data, 1))) return rc;
         std::vector<int> so((size_t)Tp * F2);
         for (int t = 0; t < Tp; ++t)
-            for (int f = 0; f < F2; ++f) so[(size_t)t * F2 + f] = ((2 * t) * h->cf_F1 + 2 * f) * D;
-        if ((rc = dev_upload(h, &h->cf_seg_off, so))) return rc;
+            for (int f = 0; f < F2; ++f) so[(size_t)t * F2 + f] = ((2 * t) * s.F1 + 2 * f) * D;
+        if ((rc = dev_upload(h, &s.seg_off, so))) return rc;
     }
     {
         const std::string p = "conformer_block.input_projection.0.linear.";
@@ -119,12 +167,12 @@ int conformer_finalize(svhip_handle* h) {
         for (int n = 0; n < D; ++n)
             for (int ch = 0; ch < D; ++ch)
                 for (int f = 0; f < F2; ++f) pw[(size_t)n * D * F2 + (size_t)f * D + ch] = w->data[(size_t)n * D * F2 + (size_t)ch * F2 + f];
-        if ((rc = needw(h, p + "bias", b)) || (rc = make_conv(h, h->cf_proj, HostTensor{std::move(pw), {D, D * F2}}, &b->data, 1))) return rc;
+        if ((rc = needw(h, p + "bias", b)) || (rc = make_conv(h, s.proj, HostTensor{std::move(pw), {D, D * F2}}, &b->data, 1))) return rc;
     }
-    double fl = 2.0 * 9 * D * h->cf_T1 * h->cf_F1 + (double)Tp * F2 * h->cf_c2.flops_per_row + (double)Tp * h->cf_proj.flops_per_row;
-    h->cf.assign(CF_LAYERS, svhip_handle::CfBlock{});
+    double fl = 2.0 * 9 * D * s.T1 * s.F1 + (double)Tp * F2 * s.c2.flops_per_row + (double)Tp * s.proj.flops_per_row;
+    s.blocks.assign(CF_LAYERS, CfBlock{});
     for (int i = 0; i < CF_LAYERS; ++i) {
-        svhip_handle::CfBlock& K = h->cf[i];
+        CfBlock& K = s.blocks[i];
         const std::string p = "conformer_block.layers." + std::to_string(i) + ".";
         for (int j = 0; j < 2; ++j) {
             const std::string q = p + (j == 0 ? "sequential.0." : "sequential.3.") + "module.sequential.";
@@ -198,39 +246,41 @@ int conformer_finalize(svhip_handle* h) {
         if ((rc = upload_f32(h, p + "sequential.4.bias", &K.fin_b))) return rc;
     }
     // pooling: attention.0 + ReLU with attention.2 (BatchNorm1d(128)) as the epilogue affine, attention.3 to fp32 logits
-    if ((rc = make_conv(h, h->cf_att0, "attention.0.weight", "attention.0.bias", "attention.2", 1))) return rc;
-    if ((rc = make_conv(h, h->cf_att3, "attention.3.weight", "attention.3.bias", "", 1))) return rc;
-    if ((rc = make_bn(h, "attention_norm", 2 * D, &h->cf_pbn_scale, &h->cf_pbn_shift))) return rc;
-    if ((rc = make_linear(h, h->cf_fc, "fc.conv.weight", "fc.conv.bias"))) return rc;
-    if (h->cf_fc.N != nOut || h->cf_fc.K != 2 * D) SV_FAIL(h, SVHIP_ERR_INVALID, "fc.conv.weight must be (%d, %d, 1)", nOut, 2 * D);
+    if ((rc = make_conv(h, s.att0, "attention.0.weight", "attention.0.bias", "attention.2", 1))) return rc;
+    if ((rc = make_conv(h, s.att3, "attention.3.weight", "attention.3.bias", "", 1))) return rc;
+    if ((rc = make_bn(h, "attention_norm", 2 * D, &s.pbn_scale, &s.pbn_shift))) return rc;
+    if ((rc = make_linear(h, s.fc, "fc.conv.weight", "fc.conv.bias"))) return rc;
+    if (s.fc.N != nOut || s.fc.K != 2 * D) SV_FAIL(h, SVHIP_ERR_INVALID, "fc.conv.weight must be (%d, %d, 1)", nOut, 2 * D);
     {
         std::vector<float> half(D, 0.5f);
-        if ((rc = dev_upload(h, &h->cf_half, half))) return rc;
+        if ((rc = dev_upload(h, &s.half, half))) return rc;
     }
-    fl += (double)Tp * (h->cf_att0.flops_per_row + h->cf_att3.flops_per_row) + 2.0 * nOut * 2 * D;
+    fl += (double)Tp * (s.att0.flops_per_row + s.att3.flops_per_row) + 2.0 * nOut * 2 * D;
     h->flops_per_utt = fl;
     return SVHIP_OK;
 }
 
 int conformer_alloc(svhip_handle* h) {
+    h->model = std::make_unique<ConformerState>();
+    auto& s = S(h);
     const svhip_config& c = h->cfg;
     const size_t B = c.max_batch, M = B * h->T, e = h->esz;
     int rc;
     // the subsampling slice buffers, eleven (B T', <= 1024) activations, logits, pooled rows
-    h->cf_T1 = cf_sub(h->T); h->cf_F1 = cf_sub(c.n_mels);
-    h->cf_Tp = cf_sub(h->cf_T1); h->cf_F2 = cf_sub(h->cf_F1);
-    const size_t Tp = h->cf_Tp, Mp = B * Tp, D = CF_D;
-    const size_t per_utt = (size_t)h->cf_T1 * h->cf_F1 * D * e;          // conv1 output bytes of one utterance
-    h->cf_chunk = (int)std::max<size_t>(1, std::min<size_t>(B, ((size_t)256 << 20) / per_utt));
+    s.T1 = cf_sub(h->T); s.F1 = cf_sub(c.n_mels);
+    s.Tp = cf_sub(s.T1); s.F2 = cf_sub(s.F1);
+    const size_t Tp = s.Tp, Mp = B * Tp, D = CF_D;
+    const size_t per_utt = (size_t)s.T1 * s.F1 * D * e;          // conv1 output bytes of one utterance
+    s.chunk = (int)std::max<size_t>(1, std::min<size_t>(B, ((size_t)256 << 20) / per_utt));
     if ((rc = actbuf(h, &h->X_in, M * c.n_mels))) return rc;
-    if ((rc = actbuf(h, &h->cf_c1, (size_t)h->cf_chunk * h->cf_T1 * h->cf_F1 * D))) return rc;
-    if ((rc = actbuf(h, &h->cf_s2, (size_t)h->cf_chunk * Tp * h->cf_F2 * D))) return rc;
-    void** bufs[] = {&h->cf_in, &h->cf_b0, &h->cf_x[0], &h->cf_x[1], &h->cf_r, &h->cf_ln, &h->cf_ln2, &h->cf_ctx, &h->cf_attn0, &h->cf_last};
+    if ((rc = actbuf(h, &s.c1, (size_t)s.chunk * s.T1 * s.F1 * D))) return rc;
+    if ((rc = actbuf(h, &s.s2, (size_t)s.chunk * Tp * s.F2 * D))) return rc;
+    void** bufs[] = {&s.in, &s.b0, &s.x[0], &s.x[1], &s.r, &s.ln, &s.ln2, &s.ctx, &s.attn0, &s.last};
     for (void** b : bufs) if ((rc = actbuf(h, b, Mp * D))) return rc;
-    if ((rc = actbuf(h, &h->cf_hid, Mp * 4 * D))) return rc;
-    if ((rc = dev_alloc(h, &h->cf_logits, Mp * D))) return rc;
-    if ((rc = dev_alloc(h, &h->cf_pool_raw, B * 2 * D))) return rc;
-    if ((rc = dev_alloc(h, &h->cf_pool, B * 2 * D))) return rc;
+    if ((rc = actbuf(h, &s.hid, Mp * 4 * D))) return rc;
+    if ((rc = dev_alloc(h, &s.logits, Mp * D))) return rc;
+    if ((rc = dev_alloc(h, &s.pool_raw, B * 2 * D))) return rc;
+    if ((rc = dev_alloc(h, &s.pool, B * 2 * D))) return rc;
     return SVHIP_OK;
 }
 
@@ -240,9 +290,10 @@ static int cf_ln(svhip_handle* h, const void* x, void* y, const float* g, const 
 }
 
 static int conformer_forward_part(svhip_handle* h, const float* d_feat, int b0, int B) {
+    auto& s = S(h);
     (void)b0;
     const svhip_config& c = h->cfg;
-    const int T = h->T, Tp = h->cf_Tp, F = c.n_mels, T1 = h->cf_T1, F1 = h->cf_F1, F2 = h->cf_F2, e = h->esz, D = CF_D;
+    const int T = h->T, Tp = s.Tp, F = c.n_mels, T1 = s.T1, F1 = s.F1, F2 = s.F2, e = h->esz, D = CF_D;
     const int M = B * Tp;
     const bool bf = h->bf16;
     hipStream_t st = h->cur;
@@ -251,92 +302,93 @@ static int conformer_forward_part(svhip_handle* h, const float* d_feat, int b0, 
              return launch_prologue(d_feat, h->X_in, bf, B, F, T, c.log_input, h->in_w, h->in_b, h->d_pstats, st);
          }))) return rc;
     // Conv2dSubampling + input_projection (convolution.py:152-185, encoder.py:160-163), cf_chunk utterances at a time
-    for (int s0 = 0; s0 < B; s0 += h->cf_chunk) {
-        const int n = std::min(h->cf_chunk, B - s0);
+    for (int s0 = 0; s0 < B; s0 += s.chunk) {
+        const int n = std::min(s.chunk, B - s0);
         if ((rc = run(h, "cf_conv1", 2.0 * 9 * D * n * T1 * F1, [&]() {
-                 return launch_cf_conv1(off(h->X_in, (size_t)s0 * T * F, e), h->cf_c1_w, h->cf_c1_b, h->cf_c1, h->dt, n, T, F, st);
+                 return launch_cf_conv1(off(h->X_in, (size_t)s0 * T * F, e), s.c1_w, s.c1_b, s.c1, h->dt, n, T, F, st);
              }))) return rc;
-        GemmParams p2 = conv_params(h, h->cf_c2, h->cf_c1, D, h->cf_s2, D, n * Tp * F2, Tp * F2);
+        GemmParams p2 = conv_params(h, s.c2, s.c1, D, s.s2, D, n * Tp * F2, Tp * F2);
         p2.act1 = ACT_RELU;
-        p2.seg_off = h->cf_seg_off; p2.seg_rows = Tp * F2; p2.seg_len = 3 * D;
+        p2.seg_off = s.seg_off; p2.seg_rows = Tp * F2; p2.seg_len = 3 * D;
         p2.seg_stride = (int64_t)F1 * D; p2.seg_utt = (int64_t)T1 * F1 * D;
-        if ((rc = conv_gemm(h, h->cf_c2, p2))) return rc;
-        GemmParams pp = conv_params(h, h->cf_proj, h->cf_s2, F2 * D, off(h->cf_in, (size_t)s0 * Tp * D, e), D, n * Tp, Tp);
-        if ((rc = conv_gemm(h, h->cf_proj, pp))) return rc;
+        if ((rc = conv_gemm(h, s.c2, p2))) return rc;
+        GemmParams pp = conv_params(h, s.proj, s.s2, F2 * D, off(s.in, (size_t)s0 * Tp * D, e), D, n * Tp, Tp);
+        if ((rc = conv_gemm(h, s.proj, pp))) return rc;
     }
     // the blocks (encoder.py:32-110).  Buffers: x (block input) -> r -> xo -> r -> ln2 -> xo = LN(.) (+ the next block's FF LayerNorm)
-    const void* x = h->cf_in;
-    const int nb = (int)h->cf.size();
-    if ((rc = cf_ln(h, x, h->cf_ln, h->cf[0].ff_g[0], h->cf[0].ff_b[0], M))) return rc;
+    const void* x = s.in;
+    const int nb = (int)s.blocks.size();
+    if ((rc = cf_ln(h, x, s.ln, s.blocks[0].ff_g[0], s.blocks[0].ff_b[0], M))) return rc;
     for (int i = 0; i < nb; ++i) {
-        const svhip_handle::CfBlock& K = h->cf[i];
-        void* xo = i == 0 ? h->cf_b0 : i == nb - 1 ? h->cf_last : h->cf_x[i & 1];
-        void* ctx = i == 0 ? h->cf_attn0 : h->cf_ctx;
+        const CfBlock& K = s.blocks[i];
+        void* xo = i == 0 ? s.b0 : i == nb - 1 ? s.last : s.x[i & 1];
+        void* ctx = i == 0 ? s.attn0 : s.ctx;
         // r = x + 0.5 FF(x); cf_ln already holds LN(x)                                                 feed_forward.py:23-57
-        GemmParams f1 = conv_params(h, K.ff1[0], h->cf_ln, D, h->cf_hid, 4 * D, M, Tp);
+        GemmParams f1 = conv_params(h, K.ff1[0], s.ln, D, s.hid, 4 * D, M, Tp);
         f1.act1 = ACT_SWISH;
         if ((rc = conv_gemm(h, K.ff1[0], f1))) return rc;
-        GemmParams f2 = conv_params(h, K.ff2[0], h->cf_hid, 4 * D, h->cf_r, D, M, Tp);
-        f2.scale = h->cf_half; f2.shift = h->d_zeros; f2.R = x; f2.ldr = D;
+        GemmParams f2 = conv_params(h, K.ff2[0], s.hid, 4 * D, s.r, D, M, Tp);
+        f2.scale = s.half; f2.shift = h->d_zeros; f2.R = x; f2.ldr = D;
         if ((rc = conv_gemm(h, K.ff2[0], f2))) return rc;
         // xo = r + out_proj(attention(LN(r)))                                                        attention.py:75-159
-        if ((rc = cf_ln(h, h->cf_r, h->cf_ln, K.att_g, K.att_b, M))) return rc;
-        if ((rc = conv_gemm(h, K.qkv, conv_params(h, K.qkv, h->cf_ln, D, h->cf_hid, 3 * D, M, Tp)))) return rc;
+        if ((rc = cf_ln(h, s.r, s.ln, K.att_g, K.att_b, M))) return rc;
+        if ((rc = conv_gemm(h, K.qkv, conv_params(h, K.qkv, s.ln, D, s.hid, 3 * D, M, Tp)))) return rc;
         if ((rc = run(h, "cf_attn", 4.0 * B * Tp * (double)Tp * 3 * 2 * 64, [&]() {
-                 return launch_cf_attn(h->cf_hid, 3 * D, K.P, D, K.u, K.v, ctx, D, h->dt, B, Tp, st);
+                 return launch_cf_attn(s.hid, 3 * D, K.P, D, K.u, K.v, ctx, D, h->dt, B, Tp, st);
              }))) return rc;
         GemmParams po = conv_params(h, K.out, ctx, D, xo, D, M, Tp);
-        po.R = h->cf_r; po.ldr = D;
+        po.R = s.r; po.ldr = D;
         if ((rc = conv_gemm(h, K.out, po))) return rc;
         // r = xo + pw2(swish(BN(dw15(GLU(pw1(LN(xo)))))))                                             convolution.py:108-149
-        if ((rc = cf_ln(h, xo, h->cf_ln, K.cv_g, K.cv_b, M))) return rc;
-        if ((rc = conv_gemm(h, K.pw1, conv_params(h, K.pw1, h->cf_ln, D, h->cf_hid, 2 * D, M, Tp)))) return rc;
-        if ((rc = run(h, "cf_glu_dw", 2.0 * 15 * D * M, [&]() { return launch_cf_glu_dw(h->cf_hid, K.dw_w, K.dw_b, h->cf_ctx, h->dt, B, Tp, st); })))
+        if ((rc = cf_ln(h, xo, s.ln, K.cv_g, K.cv_b, M))) return rc;
+        if ((rc = conv_gemm(h, K.pw1, conv_params(h, K.pw1, s.ln, D, s.hid, 2 * D, M, Tp)))) return rc;
+        if ((rc = run(h, "cf_glu_dw", 2.0 * 15 * D * M, [&]() { return launch_cf_glu_dw(s.hid, K.dw_w, K.dw_b, s.ctx, h->dt, B, Tp, st); })))
             return rc;
-        GemmParams pw = conv_params(h, K.pw2, h->cf_ctx, D, h->cf_r, D, M, Tp);
+        GemmParams pw = conv_params(h, K.pw2, s.ctx, D, s.r, D, M, Tp);
         pw.R = xo; pw.ldr = D;
         if ((rc = conv_gemm(h, K.pw2, pw))) return rc;
         // ln2 = r + 0.5 FF'(r); xo = LN(ln2), and the next block's LN(xo) in the same pass
-        if ((rc = cf_ln(h, h->cf_r, h->cf_ln, K.ff_g[1], K.ff_b[1], M))) return rc;
-        GemmParams g1 = conv_params(h, K.ff1[1], h->cf_ln, D, h->cf_hid, 4 * D, M, Tp);
+        if ((rc = cf_ln(h, s.r, s.ln, K.ff_g[1], K.ff_b[1], M))) return rc;
+        GemmParams g1 = conv_params(h, K.ff1[1], s.ln, D, s.hid, 4 * D, M, Tp);
         g1.act1 = ACT_SWISH;
         if ((rc = conv_gemm(h, K.ff1[1], g1))) return rc;
-        GemmParams g2 = conv_params(h, K.ff2[1], h->cf_hid, 4 * D, h->cf_ln2, D, M, Tp);
-        g2.scale = h->cf_half; g2.shift = h->d_zeros; g2.R = h->cf_r; g2.ldr = D;
+        GemmParams g2 = conv_params(h, K.ff2[1], s.hid, 4 * D, s.ln2, D, M, Tp);
+        g2.scale = s.half; g2.shift = h->d_zeros; g2.R = s.r; g2.ldr = D;
         if ((rc = conv_gemm(h, K.ff2[1], g2))) return rc;
-        const svhip_handle::CfBlock* nx = i + 1 < nb ? &h->cf[i + 1] : nullptr;
-        if ((rc = cf_ln(h, h->cf_ln2, xo, K.fin_g, K.fin_b, M, nx ? h->cf_ln : nullptr, nx ? nx->ff_g[0] : nullptr, nx ? nx->ff_b[0] : nullptr)))
+        const CfBlock* nx = i + 1 < nb ? &s.blocks[i + 1] : nullptr;
+        if ((rc = cf_ln(h, s.ln2, xo, K.fin_g, K.fin_b, M, nx ? s.ln : nullptr, nx ? nx->ff_g[0] : nullptr, nx ? nx->ff_b[0] : nullptr)))
             return rc;
         x = xo;
     }
     // attentive statistics pooling (Conformer.py:130-142)
-    GemmParams pa = conv_params(h, h->cf_att0, x, D, h->cf_hid, 128, M, Tp);
+    GemmParams pa = conv_params(h, s.att0, x, D, s.hid, 128, M, Tp);
     pa.act1 = ACT_RELU;
-    if ((rc = conv_gemm(h, h->cf_att0, pa))) return rc;
-    GemmParams pl = conv_params(h, h->cf_att3, h->cf_hid, 128, h->cf_logits, D, M, Tp);
+    if ((rc = conv_gemm(h, s.att0, pa))) return rc;
+    GemmParams pl = conv_params(h, s.att3, s.hid, 128, s.logits, D, M, Tp);
     pl.out_f32 = 1;
-    if ((rc = conv_gemm(h, h->cf_att3, pl))) return rc;
+    if ((rc = conv_gemm(h, s.att3, pl))) return rc;
     if ((rc = run(h, "cf_asp_pool", 0, [&]() {
-             return launch_asp_pool(h->cf_logits, x, bf, D, B, Tp, D, h->cf_pbn_scale, h->cf_pbn_shift, h->cf_pool_raw, h->cf_pool, 1e-4f, 1e4f, st);
+             return launch_asp_pool(s.logits, x, bf, D, B, Tp, D, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-4f, 1e4f, st);
          }))) return rc;
     // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the ReLU epilogues would have dropped it)
     if ((rc = run(h, "cf_in_check", 0, [&]() {
-             return launch_tn_nonfinite_rows(d_feat, (int64_t)F * T, B, h->cf_pool, 2 * D, 2 * D, st);
+             return launch_tn_nonfinite_rows(d_feat, (int64_t)F * T, B, s.pool, 2 * D, 2 * D, st);
          }))) return rc;
-    return run(h, "cf_fc", 2.0 * B * h->cf_fc.N * h->cf_fc.K, [&]() {
-        return launch_rowvec_linear(h->cf_pool, 2 * D, h->cf_fc.W, h->cf_fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * D, ACT_NONE, st);
+    return run(h, "cf_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
+        return launch_rowvec_linear(s.pool, 2 * D, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * D, ACT_NONE, st);
     });
 }
 
 int conformer_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, conformer_forward_part, d_feat, B, 1, B); }
 
 int conformer_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // cf_in, cf_block0, cf_attn0, cf_last, cf_pool
-    v.rows = (size_t)h->lastB * h->cf_Tp; v.cols = v.ld = CF_D;
-    if (n == "cf_in") v.src = h->cf_in;
-    else if (n == "cf_block0") v.src = h->cf_b0;
-    else if (n == "cf_attn0") v.src = h->cf_attn0;
-    else if (n == "cf_last") v.src = h->cf_last;
-    else if (n == "cf_pool") { v.src = h->cf_pool; v.rows = h->lastB; v.cols = v.ld = 2 * CF_D; v.f32 = true; }
+    auto& s = S(h);
+    v.rows = (size_t)h->lastB * s.Tp; v.cols = v.ld = CF_D;
+    if (n == "cf_in") v.src = s.in;
+    else if (n == "cf_block0") v.src = s.b0;
+    else if (n == "cf_attn0") v.src = s.attn0;
+    else if (n == "cf_last") v.src = s.last;
+    else if (n == "cf_pool") { v.src = s.pool; v.rows = h->lastB; v.cols = v.ld = 2 * CF_D; v.f32 = true; }
     else return unknown_stage(h, n);
     return SVHIP_OK;
 }

@@ -3,14 +3,12 @@
 
 namespace svhip {
 
-// zero page of a conv-gather GEMM whose A operand starts at `A`: the zero tail of the RawNet2 activation buffer that holds A (behind
+// zero page of a conv-gather GEMM whose A operand starts at `A`: the zero tail of the zero-tailed activation buffer that holds A (behind
 // the operand, within 4 GiB: what gemm_pw3's 16-bit conv-gather form needs), else the handle's stand-alone zero page
 static const void* zero_page_for(const svhip_handle* h, const void* A) {
     const char* a = static_cast<const char*>(A);
-    for (int i = 0; i < 6; ++i) {
-        const char* b = static_cast<const char*>(h->rn_buf[i]);
-        if (b && a >= b && a < b + h->rn_buf_bytes) return b + h->rn_buf_bytes;
-    }
+    for (const TailedBuf& b : h->tailed)
+        if (a >= b.base && a < b.base + b.bytes) return b.base + b.bytes;
     return h->d_zero;
 }
 

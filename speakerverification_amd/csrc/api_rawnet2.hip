@@ -8,6 +8,59 @@
 
 namespace svhip {
 
+namespace {
+
+bool rn_is_sinc(int model) { return model == SVHIP_MODEL_RAWNET2 || model == SVHIP_MODEL_RAWNET2_GRU; }     // front_proc='sinc'
+bool rn_is_gru(int model) { return model == SVHIP_MODEL_RAWNET2_GRU; }                                       // aggregate='gru'
+
+struct RnBlock {
+    int cin = 0, cout = 0;
+    bool downsample = false, has_shortcut = false;
+    float *bn1_scale = nullptr, *bn1_shift = nullptr;
+    ConvLayer conv1, conv2, shortcut;       // conv1 carries bn2 as its epilogue
+    void* conv2sc_W = nullptr;              // bf16 handles: [Np][conv2.K + cin] = conv2 | 1 x 1 shortcut, one GEMM for both (gemm_pw2 A3)
+    float* alpha = nullptr;
+    LinearLayer afms_fc;
+    float* afms_fcT = nullptr;              // fc weight transposed [cin][cout] (the gate kernel reads consecutive outputs per wave)
+};
+
+// RawNet2 layers (front_proc='sinc' or 'conv', aggregate='asp'; RawNet2_custom.py:230-243)
+struct RawNet2State : ModelState {
+    RnBlock blocks[8];
+    float *gamma = nullptr, *beta = nullptr, *fbn_scale = nullptr, *fbn_shift = nullptr;
+    void* filt = nullptr;
+    void* filt_sym = nullptr;              // fp16 handles: [128][128] slot-major table of the symmetric sinc form (round 6)
+    void* filt_x3 = nullptr;               // F32X3 handles: [2][128][256] half hi | lo parts of the sinc filters
+    float* cw = nullptr;                   // 'conv' front-end (SVHIP_MODEL_RAWNET2_CONV): [w0 | w1 | w2 | bias] x 128 floats of conv1
+    float *agg_scale = nullptr, *agg_shift = nullptr;
+    ConvLayer att0, att3;
+    LinearLayer fc;
+    // aggregate='gru' (SVHIP_MODEL_RAWNET2_GRU): bn_before_gru is agg_scale / agg_shift; W_ih a 1 x 1 conv layer whose bias is
+    // b_ih + [b_hr | b_hz | 0]; W_hh packed gate-interleaved (gru.hip) in the compute type; b_hn; fc_after_gru
+    ConvLayer gru_ih;
+    void* gru_whh = nullptr;
+    float* gru_bhn = nullptr;
+    LinearLayer gru_fc;
+    float* gru_gi = nullptr;           // (Bmax, T, 3072) fp32 gate inputs
+    float* gru_hbuf[2] = {};           // (Bmax, 1024) fp32 state, ping-pong
+    int gru_T = 0;                     // frames that reach the GRU
+    const void* gru_in = nullptr;      // svhip_get_stage "rn_gru_in": the GRU input of the last forward (one slice only)
+    const float* gru_h = nullptr;      //                 "rn_gru_h": the buffer that holds the last state
+    void* buf[6] = {};                 // activation ping-pong buffers; a 256-byte zero tail follows each payload (h->tailed lists them)
+    float* scratch = nullptr;
+    void* xn = nullptr;
+    int Lp = 0;
+    float *stats = nullptr, *mean = nullptr, *gate = nullptr, *logits = nullptr, *pooled = nullptr;
+    float* part = nullptr;             // fused 128-channel blocks: per-tile column sums (B, ntiles, 128)
+    int T1 = 0;
+    const void* dbg_x = nullptr; int dbg_T = 0, dbg_C = 0;   // SVHIP_RN_STOP developer hook (tests)
+    void* snap = nullptr; size_t snap_cap = 0; int snap_T = 0, snap_C = 0;      // SVHIP_RN_SNAP=2: copy of block 2's pre-activation (stage "rn_snap")
+};
+
+RawNet2State& S(svhip_handle* h) { return static_cast<RawNet2State&>(*h->model); }
+
+}  // namespace
+
 // RawNet2 needs six max_pool1d(3) stages behind the front-end to leave at least one frame: 3^6 front-end frames
 constexpr int RN_MIN_FRAMES = 3 * 3 * 3 * 3 * 3 * 3;
 
@@ -69,6 +122,7 @@ static int rn_conv(svhip_handle* h, ConvLayer& L, const std::string& w, const st
 
 // sinc band-pass filters baked once per weight load (RawNet_baseline.py:313-318,339-357), float32 arithmetic
 static int bake_sinc(svhip_handle* h) {
+    auto& s = S(h);
     const HostTensor *lo = getw(h, "first_conv.low_hz_"), *bd = getw(h, "first_conv.band_hz_");
     if (!lo || !bd) SV_FAIL(h, SVHIP_ERR_MISSING, "missing sinc parameters");
     const int NF = 128, KS = 251, HALF = 125;
@@ -100,7 +154,7 @@ static int bake_sinc(svhip_handle* h) {
             for (int k = 0; k < KS; ++k) pk[(size_t)f * 256 + k] = to_h16(h, filt[(size_t)f * KS + k]);
         uint16_t* d;
         if ((rc = dev_upload(h, &d, pk))) return rc;
-        h->rn_filt = d;
+        s.filt = d;
         if (h->f16) {
             // the symmetric form (rawnet2.hip, SYM): slot k' = 2 + m carries h[125 + m] (the centre tap halved: its operand is x[c] + x[c]),
             // slots 0 and 1 are zero; right and left halves of a filter are the same numbers by construction (checked here)
@@ -115,7 +169,7 @@ static int bake_sinc(svhip_handle* h) {
                 }
                 uint16_t* ds;
                 if ((rc = dev_upload(h, &ds, ps))) return rc;
-                h->rn_filt_sym = ds;
+                s.filt_sym = ds;
             }
         }
     } else {
@@ -124,7 +178,7 @@ static int bake_sinc(svhip_handle* h) {
             for (int k = 0; k < KS; ++k) pk[(size_t)f * 252 + k] = filt[(size_t)f * KS + k];
         float* d;
         if ((rc = dev_upload(h, &d, pk))) return rc;
-        h->rn_filt = d;
+        s.filt = d;
         if (h->x3) {        // the split front-end (rn_sinc_x3): hi and lo half planes, k contiguous, zero beyond the 251 taps
             std::vector<uint16_t> pl((size_t)2 * NF * 256, 0);
             for (int f = 0; f < NF; ++f)
@@ -135,7 +189,7 @@ static int bake_sinc(svhip_handle* h) {
                 }
             uint16_t* dx;
             if ((rc = dev_upload(h, &dx, pl))) return rc;
-            h->rn_filt_x3 = dx;
+            s.filt_x3 = dx;
         }
     }
     return SVHIP_OK;
@@ -151,24 +205,25 @@ static int make_conv3_front(svhip_handle* h) {
         for (int k = 0; k < 3; ++k) cw[k * 128 + c] = w->data[c * 3 + k];
         cw[3 * 128 + c] = b->data[c];
     }
-    return dev_upload(h, &h->rn_cw, cw);
+    return dev_upload(h, &S(h).cw, cw);
 }
 
-// aggregate='gru' (RawNet2_custom.py:84-95,196-207): bn_before_gru is the pass block 7's AFMS pass applies (rn_agg_scale / shift); the input
+// aggregate='gru' (RawNet2_custom.py:84-95,196-207): bn_before_gru is the pass block 7's AFMS pass applies (agg_scale / agg_shift); the input
 // projection W_ih is a 1 x 1 conv layer whose bias folds b_ih + [b_hr | b_hz | 0] (b_hn stays inside r * (W_hn h + b_hn)); W_hh is packed
 // gate-interleaved (gru.hip) in the compute type; fc_after_gru is a small linear.  fc.* is loaded and not used, as in the reference.
 static int rawnet2_finalize_gru(svhip_handle* h) {
+    auto& s = S(h);
     const int H = RN_GRU_HIDDEN, G = 3 * H;
     int rc;
-    if ((rc = make_bn(h, "bn_before_gru", 512, &h->rn_agg_scale, &h->rn_agg_shift))) return rc;
+    if ((rc = make_bn(h, "bn_before_gru", 512, &s.agg_scale, &s.agg_shift))) return rc;
     const HostTensor *whh = getw(h, "gru.weight_hh_l0"), *bih = getw(h, "gru.bias_ih_l0"), *bhh = getw(h, "gru.bias_hh_l0");
     if (!whh || !bih || !bhh) SV_FAIL(h, SVHIP_ERR_MISSING, "missing GRU tensors (gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0)");
-    if ((rc = rn_conv(h, h->rn_gru_ih, "gru.weight_ih_l0", "", ""))) return rc;
+    if ((rc = rn_conv(h, s.gru_ih, "gru.weight_ih_l0", "", ""))) return rc;
     std::vector<float> bias(G), bhn(H);
     for (int j = 0; j < G; ++j) bias[j] = j < 2 * H ? (float)((double)bih->data[j] + (double)bhh->data[j]) : bih->data[j];
     for (int j = 0; j < H; ++j) bhn[j] = bhh->data[2 * H + j];
-    if ((rc = dev_upload(h, &h->rn_gru_ih.bias, bias))) return rc;
-    if ((rc = dev_upload(h, &h->rn_gru_bhn, bhn))) return rc;
+    if ((rc = dev_upload(h, &s.gru_ih.bias, bias))) return rc;
+    if ((rc = dev_upload(h, &s.gru_bhn, bhn))) return rc;
     // packed row ut * 48 + g * 16 + j = W_hh row g * H + ut * 16 + j
     std::vector<float> pk((size_t)G * H);
     for (int ut = 0; ut < H / 16; ++ut)
@@ -180,32 +235,33 @@ static int rawnet2_finalize_gru(svhip_handle* h) {
         for (size_t i = 0; i < pk.size(); ++i) pb[i] = to_h16(h, pk[i]);
         uint16_t* d;
         if ((rc = dev_upload(h, &d, pb))) return rc;
-        h->rn_gru_whh = d;
+        s.gru_whh = d;
     } else {
         float* d;
         if ((rc = dev_upload(h, &d, pk))) return rc;
-        h->rn_gru_whh = d;
+        s.gru_whh = d;
     }
-    return make_linear(h, h->rn_gru_fc, "fc_after_gru.weight", "fc_after_gru.bias");
+    return make_linear(h, s.gru_fc, "fc_after_gru.weight", "fc_after_gru.bias");
 }
 
 int rawnet2_finalize(svhip_handle* h) {
+    auto& s = S(h);
     int rc;
     const bool conv = h->cfg.model == SVHIP_MODEL_RAWNET2_CONV;
     if (conv) {
         if ((rc = make_conv3_front(h))) return rc;
     } else {
-        if ((rc = upload_f32(h, "ln.gamma", &h->rn_gamma))) return rc;
-        if ((rc = upload_f32(h, "ln.beta", &h->rn_beta))) return rc;
+        if ((rc = upload_f32(h, "ln.gamma", &s.gamma))) return rc;
+        if ((rc = upload_f32(h, "ln.beta", &s.beta))) return rc;
         if ((rc = bake_sinc(h))) return rc;
-        if ((rc = make_bn(h, "first_bn", 128, &h->rn_fbn_scale, &h->rn_fbn_shift))) return rc;
+        if ((rc = make_bn(h, "first_bn", 128, &s.fbn_scale, &s.fbn_shift))) return rc;
     }
     int inpl = 128, bi = 0;
-    int T = h->rn_T1;
+    int T = s.T1;
     double fl = conv ? 2.0 * 128 * 3 * (double)T : 2.0 * 128 * 251 * (double)(h->cfg.samples - 250);
     for (int li = 0; li < 6; ++li)
         for (int b = 0; b < RN_LAYERS[li]; ++b, ++bi) {
-            svhip_handle::RnBlock& B = h->rn_blocks[bi];
+            RnBlock& B = s.blocks[bi];
             const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
             const int planes = RN_FILTERS[li];
             B.cin = inpl; B.cout = planes; B.downsample = (b == RN_LAYERS[li] - 1); B.has_shortcut = inpl != planes;
@@ -244,52 +300,55 @@ int rawnet2_finalize(svhip_handle* h) {
         }
     if (rn_is_gru(h->cfg.model)) {
         if ((rc = rawnet2_finalize_gru(h))) return rc;
-        fl += (double)T * (h->rn_gru_ih.flops_per_row + 2.0 * 3 * RN_GRU_HIDDEN * RN_GRU_HIDDEN) + 2.0 * h->rn_gru_fc.N * h->rn_gru_fc.K;
+        fl += (double)T * (s.gru_ih.flops_per_row + 2.0 * 3 * RN_GRU_HIDDEN * RN_GRU_HIDDEN) + 2.0 * s.gru_fc.N * s.gru_fc.K;
         h->flops_per_utt = fl;
         return SVHIP_OK;
     }
-    if ((rc = make_bn(h, "bn_before_agg", 512, &h->rn_agg_scale, &h->rn_agg_shift))) return rc;
-    if ((rc = rn_conv(h, h->rn_att0, "attention.0.weight", "attention.0.bias", "attention.2"))) return rc;
-    if ((rc = rn_conv(h, h->rn_att3, "attention.3.weight", "attention.3.bias", ""))) return rc;
-    if ((rc = make_linear(h, h->rn_fc, "fc.weight", "fc.bias"))) return rc;
-    fl += (double)T * (h->rn_att0.flops_per_row + h->rn_att3.flops_per_row) + 2.0 * h->rn_fc.N * h->rn_fc.K;
+    if ((rc = make_bn(h, "bn_before_agg", 512, &s.agg_scale, &s.agg_shift))) return rc;
+    if ((rc = rn_conv(h, s.att0, "attention.0.weight", "attention.0.bias", "attention.2"))) return rc;
+    if ((rc = rn_conv(h, s.att3, "attention.3.weight", "attention.3.bias", ""))) return rc;
+    if ((rc = make_linear(h, s.fc, "fc.weight", "fc.bias"))) return rc;
+    fl += (double)T * (s.att0.flops_per_row + s.att3.flops_per_row) + 2.0 * s.fc.N * s.fc.K;
     h->flops_per_utt = fl;
     return SVHIP_OK;
 }
 
 int rawnet2_alloc(svhip_handle* h) {
+    h->model = std::make_unique<RawNet2State>();
+    auto& s = S(h);
     const svhip_config& c = h->cfg;
     const size_t B = c.max_batch, e = h->esz;
     int rc;
     const bool conv = c.model == SVHIP_MODEL_RAWNET2_CONV;
-    h->rn_T1 = conv ? (c.samples - 3) / 3 + 1 : (c.samples - 250) / 3;       // conv1 (kernel 3, stride 3) | sinc (251 taps) + max_pool1d(3)
-    const size_t per_utt = (size_t)h->rn_T1 * 128;           // largest activation: (T1, 128); later stages shrink 3x per doubling
-    h->rn_buf_bytes = B * per_utt * e;
+    s.T1 = conv ? (c.samples - 3) / 3 + 1 : (c.samples - 250) / 3;       // conv1 (kernel 3, stride 3) | sinc (251 taps) + max_pool1d(3)
+    const size_t per_utt = (size_t)s.T1 * 128;           // largest activation: (T1, 128); later stages shrink 3x per doubling
+    const size_t buf_bytes = B * per_utt * e;                // payload bytes of each activation buffer; a 256-byte zero tail follows
     for (int i = 0; i < 6; ++i) {
-        if ((rc = actbuf(h, &h->rn_buf[i], B * per_utt))) return rc;
-        SV_HIP(h, hipMemset(off(h->rn_buf[i], h->rn_buf_bytes, 1), 0, 256));      // the zero tail (no kernel writes past the payload)
+        if ((rc = actbuf(h, &s.buf[i], B * per_utt))) return rc;
+        SV_HIP(h, hipMemset(off(s.buf[i], buf_bytes, 1), 0, 256));      // the zero tail (no kernel writes past the payload)
+        h->tailed.push_back({static_cast<const char*>(s.buf[i]), buf_bytes});
     }
-    if (!conv && (rc = dev_alloc(h, &h->rn_stats, B * 2))) return rc;
+    if (!conv && (rc = dev_alloc(h, &s.stats, B * 2))) return rc;
     if (!conv && (h->bf16 || h->x3)) {                                  // LayerNorm output in 16 bits, zero-tailed rows (operand of the 16-bit / split sinc kernels)
-        h->rn_Lp = (int)round_up(c.samples + RN_XN_TAIL, 64);
+        s.Lp = (int)round_up(c.samples + RN_XN_TAIL, 64);
         uint16_t* q;
-        if ((rc = dev_alloc(h, &q, (h->x3 ? 4 : 2) * B * (size_t)h->rn_Lp))) return rc;      // (F32X3: hi and lo parts of both copies)
-        h->rn_xn = q;
+        if ((rc = dev_alloc(h, &q, (h->x3 ? 4 : 2) * B * (size_t)s.Lp))) return rc;      // (F32X3: hi and lo parts of both copies)
+        s.xn = q;
     }
-    if ((rc = dev_alloc(h, &h->rn_part, B * (size_t)(rn_block128_ntiles(h->rn_T1) + 1) * 4 * 128))) return rc;
-    if ((rc = dev_alloc(h, &h->rn_mean, B * 512))) return rc;
-    if ((rc = dev_alloc(h, &h->rn_scratch, B * 16 * 512))) return rc;
-    if ((rc = dev_alloc(h, &h->rn_s, B * 512 * 2))) return rc;
-    int tf = h->rn_T1;
+    if ((rc = dev_alloc(h, &s.part, B * (size_t)(rn_block128_ntiles(s.T1) + 1) * 4 * 128))) return rc;
+    if ((rc = dev_alloc(h, &s.mean, B * 512))) return rc;
+    if ((rc = dev_alloc(h, &s.scratch, B * 16 * 512))) return rc;
+    if ((rc = dev_alloc(h, &s.gate, B * 512 * 2))) return rc;
+    int tf = s.T1;
     for (int i = 0; i < 6; ++i) tf /= 3;                      // six max_pool1d(3) stages follow the front-end
     if (tf < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance too short for RawNet2 (%d samples)", c.samples);
-    if ((rc = dev_alloc(h, &h->rn_logits, B * (size_t)tf * 512))) return rc;
+    if ((rc = dev_alloc(h, &s.logits, B * (size_t)tf * 512))) return rc;
     if (rn_is_gru(c.model)) {                                 // (256 x 14 frames: 11 MB of gate inputs)
-        h->rn_gru_T = tf;
-        if ((rc = dev_alloc(h, &h->rn_gru_gi, B * (size_t)tf * 3 * RN_GRU_HIDDEN))) return rc;
-        for (int i = 0; i < 2; ++i) if ((rc = dev_alloc(h, &h->rn_gru_hbuf[i], B * (size_t)RN_GRU_HIDDEN))) return rc;
+        s.gru_T = tf;
+        if ((rc = dev_alloc(h, &s.gru_gi, B * (size_t)tf * 3 * RN_GRU_HIDDEN))) return rc;
+        for (int i = 0; i < 2; ++i) if ((rc = dev_alloc(h, &s.gru_hbuf[i], B * (size_t)RN_GRU_HIDDEN))) return rc;
     }
-    if ((rc = dev_alloc(h, &h->rn_pooled, B * 1024))) return rc;
+    if ((rc = dev_alloc(h, &s.pooled, B * 1024))) return rc;
     if (h->bf16) {          // K-slice partials of fc (K = 1 024: four slices of 256) at full batches, 16-bit handles
         h->lin_part_per_utt = (size_t)4 * (size_t)std::max(128, c.embed_dim);
         if ((rc = dev_alloc(h, &h->d_lin_part, B * h->lin_part_per_utt))) return rc;
@@ -298,21 +357,22 @@ int rawnet2_alloc(svhip_handle* h) {
 }
 
 int rawnet2_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {
+    auto& s = S(h);
     const int B = h->lastB;
-    if (n == "rn_x") { v.src = h->rn_dbg_x; v.rows = (size_t)B * h->rn_dbg_T; v.cols = v.ld = h->rn_dbg_C; }
-    else if (n == "rn_snap") { v.src = h->rn_snap; v.rows = (size_t)B * h->rn_snap_T; v.cols = v.ld = h->rn_snap_C; }
-    else if (n == "rn_pooled") { v.src = h->rn_pooled; v.rows = B; v.cols = v.ld = 1024; v.f32 = true; }
-    else if (n == "rn_gru_h" && rn_is_gru(h->cfg.model)) { v.src = h->rn_gru_h; v.rows = B; v.cols = v.ld = RN_GRU_HIDDEN; v.f32 = true; }
+    if (n == "rn_x") { v.src = s.dbg_x; v.rows = (size_t)B * s.dbg_T; v.cols = v.ld = s.dbg_C; }
+    else if (n == "rn_snap") { v.src = s.snap; v.rows = (size_t)B * s.snap_T; v.cols = v.ld = s.snap_C; }
+    else if (n == "rn_pooled") { v.src = s.pooled; v.rows = B; v.cols = v.ld = 1024; v.f32 = true; }
+    else if (n == "rn_gru_h" && rn_is_gru(h->cfg.model)) { v.src = s.gru_h; v.rows = B; v.cols = v.ld = RN_GRU_HIDDEN; v.f32 = true; }
     else if (n == "rn_gru_in" && rn_is_gru(h->cfg.model)) {
-        if (!h->rn_gru_in) SV_FAIL(h, SVHIP_ERR_STATE, "stage rn_gru_in: the last forward ran as several batch slices (SVHIP_LANES)");
-        v.src = h->rn_gru_in; v.rows = (size_t)B * h->rn_gru_T; v.cols = v.ld = 512;
+        if (!s.gru_in) SV_FAIL(h, SVHIP_ERR_STATE, "stage rn_gru_in: the last forward ran as several batch slices (SVHIP_LANES)");
+        v.src = s.gru_in; v.rows = (size_t)B * s.gru_T; v.cols = v.ld = 512;
     }
     else return unknown_stage(h, n);
     return SVHIP_OK;
 }
 
 // conv2 + 1 x 1 shortcut of a RawNet2 block as ONE conv-gather GEMM: K = 3 * cout conv columns of hb, then cin columns of `pre`
-static GemmParams conv2sc_params(svhip_handle* h, const svhip_handle::RnBlock& K, const void* pre, const void* hb, void* o, int M, int T) {
+static GemmParams conv2sc_params(svhip_handle* h, const RnBlock& K, const void* pre, const void* hb, void* o, int M, int T) {
     GemmParams p = conv_params(h, K.conv2, hb, K.cout, o, K.cout, M, T);
     p.W = K.conv2sc_W; p.Kp = K.conv2.K + K.cin; p.pad_mode = PAD_ZERO;
     p.A3 = pre; p.lda3 = K.cin; p.K3 = K.cin;
@@ -322,28 +382,29 @@ static GemmParams conv2sc_params(svhip_handle* h, const svhip_handle::RnBlock& K
 // RawNet2.forward (models/RawNet2_custom.py:161-227) on device-resident waveforms (B, L), utterances [b0, b0 + B) of the call,
 // enqueued on h->cur.  Every workspace buffer is per-utterance contiguous, so a batch slice is an offset into each.
 static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0, int B) {
+    auto& s = S(h);
     const svhip_config& c = h->cfg;
     const bool bf = h->bf16;
     hipStream_t st = h->cur;
     const int L = c.samples, e = h->esz;
-    const size_t per_utt = (size_t)h->rn_T1 * 128;                 // elements of the largest activation of one utterance
+    const size_t per_utt = (size_t)s.T1 * 128;                 // elements of the largest activation of one utterance
     const float* d_wav = d_wav_all + (size_t)b0 * L;
     const bool conv = c.model == SVHIP_MODEL_RAWNET2_CONV;        // front_proc='conv': no LayerNorm, no sinc, no first_bn
-    float* rn_stats = conv ? nullptr : h->rn_stats + (size_t)b0 * 2;
-    float* rn_mean = h->rn_mean + (size_t)b0 * 512;
-    float* rn_scratch = h->rn_scratch + (size_t)b0 * 16 * 512;
-    float* rn_part = h->rn_part + (size_t)b0 * (rn_block128_ntiles(h->rn_T1) + 1) * 4 * 128;
-    float* rn_gate[2] = {h->rn_s + (size_t)b0 * 512, h->rn_s + ((size_t)c.max_batch + b0) * 512};
-    float* rn_pooled = h->rn_pooled + (size_t)b0 * 1024;
+    float* rn_stats = conv ? nullptr : s.stats + (size_t)b0 * 2;
+    float* rn_mean = s.mean + (size_t)b0 * 512;
+    float* rn_scratch = s.scratch + (size_t)b0 * 16 * 512;
+    float* rn_part = s.part + (size_t)b0 * (rn_block128_ntiles(s.T1) + 1) * 4 * 128;
+    float* rn_gate[2] = {s.gate + (size_t)b0 * 512, s.gate + ((size_t)c.max_batch + b0) * 512};
+    float* rn_pooled = s.pooled + (size_t)b0 * 1024;
     float* d_emb = h->d_emb + (size_t)b0 * c.embed_dim;
     int rc;
-    const bool sinc_x3 = !conv && h->x3 && h->rn_filt_x3 && !h->opt.rn_sinc_f32;      // F32X3: the front-end on three fp16 MFMAs per product
-    void* rn_xn = conv ? nullptr : bf ? static_cast<char*>(h->rn_xn) + (size_t)b0 * 2 * h->rn_Lp * 2 : sinc_x3 ? static_cast<char*>(h->rn_xn) + (size_t)b0 * 4 * h->rn_Lp * 2 : nullptr;
+    const bool sinc_x3 = !conv && h->x3 && s.filt_x3 && !h->opt.rn_sinc_f32;      // F32X3: the front-end on three fp16 MFMAs per product
+    void* rn_xn = conv ? nullptr : bf ? static_cast<char*>(s.xn) + (size_t)b0 * 2 * s.Lp * 2 : sinc_x3 ? static_cast<char*>(s.xn) + (size_t)b0 * 4 * s.Lp * 2 : nullptr;
     const int dt = h->dt;
-    if (!conv && (rc = run(h, "rn_ln_stats", 0, [&]() { return launch_rn_ln_stats(d_wav, B, L, rn_stats, st, rn_xn, h->rn_Lp, h->rn_gamma, h->rn_beta, dt, sinc_x3); }))) return rc;
-    int T = h->rn_T1;
-    void *x = off(h->rn_buf[0], b0 * per_utt, e), *pre = off(h->rn_buf[1], b0 * per_utt, e), *hb = off(h->rn_buf[2], b0 * per_utt, e),
-         *o = off(h->rn_buf[3], b0 * per_utt, e), *sc = off(h->rn_buf[4], b0 * per_utt, e), *xn = off(h->rn_buf[5], b0 * per_utt, e);
+    if (!conv && (rc = run(h, "rn_ln_stats", 0, [&]() { return launch_rn_ln_stats(d_wav, B, L, rn_stats, st, rn_xn, s.Lp, s.gamma, s.beta, dt, sinc_x3); }))) return rc;
+    int T = s.T1;
+    void *x = off(s.buf[0], b0 * per_utt, e), *pre = off(s.buf[1], b0 * per_utt, e), *hb = off(s.buf[2], b0 * per_utt, e),
+         *o = off(s.buf[3], b0 * per_utt, e), *sc = off(s.buf[4], b0 * per_utt, e), *xn = off(s.buf[5], b0 * per_utt, e);
     // developer hook (option rn_stop): return after N residual blocks (0: after the front-end) with x exposed as stage "rn_x"; the
     // unfused kernel sequence runs, whose storage points are those of the fused kernels
     const int stop_after = h->opt.rn_stop;
@@ -352,14 +413,14 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
     const int snap_at = h->opt.rn_snap;
     auto snapshot = [&](const void* src, int Tn, int Cn) -> int {
         const size_t bytes = (size_t)B * Tn * Cn * e;
-        if (h->rn_snap_cap < bytes) {
+        if (s.snap_cap < bytes) {
             void* q = nullptr;
             SV_HIP(h, hipMalloc(&q, bytes));
             h->allocs.push_back(q);
-            h->rn_snap = q; h->rn_snap_cap = bytes;
+            s.snap = q; s.snap_cap = bytes;
         }
-        SV_HIP(h, hipMemcpyAsync(h->rn_snap, src, bytes, hipMemcpyDeviceToDevice, st));
-        h->rn_snap_T = Tn; h->rn_snap_C = Cn;
+        SV_HIP(h, hipMemcpyAsync(s.snap, src, bytes, hipMemcpyDeviceToDevice, st));
+        s.snap_T = Tn; s.snap_C = Cn;
         return SVHIP_OK;
     };
     // F32X3: does block `bn`, entered with Tn frames, run its convolutions (and its projection shortcut) on the 128 x 128 split kernel
@@ -367,20 +428,20 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
     // tiled kernel that splits its fp32 operands in registers: 170 - 190 TFLOP/s.)
     struct RnStep { bool ok = false; GemmParams q0, q1, q2; };
     auto rn_step_plan = [&](int bn, int Tn, const void* a1, const void* xb) {
-        RnStep s;
-        if (bn > 7 || !h->x3 || h->opt.rn_step_off) return s;
-        const svhip_handle::RnBlock& K = h->rn_blocks[bn];
-        GemmParams& q1 = s.q1;                           // conv1: pre (S32) -> lrelu(bn2(.)) in S32, conv2's operand
+        RnStep sp;
+        if (bn > 7 || !h->x3 || h->opt.rn_step_off) return sp;
+        const RnBlock& K = s.blocks[bn];
+        GemmParams& q1 = sp.q1;                           // conv1: pre (S32) -> lrelu(bn2(.)) in S32, conv2's operand
         q1 = conv_params(h, K.conv1, a1, K.cin, hb, K.cout, B * Tn, Tn);
         q1.W = K.conv1.Ws32; q1.x3 = 2; q1.pad_mode = PAD_ZERO; q1.zero_page = h->d_zeros;
-        GemmParams& q2 = s.q2 = q1;                      // conv2: h (S32) -> fp32, + the shortcut (identity x, or the projected one)
+        GemmParams& q2 = sp.q2 = q1;                      // conv2: h (S32) -> fp32, + the shortcut (identity x, or the projected one)
         q2.A = hb; q2.lda = K.cout; q2.cin = K.cout; q2.K = 3 * K.cout; q2.Kp = q2.K; q2.W = K.conv2.Ws32; q2.scale = nullptr; q2.shift = nullptr;
         q2.Y = o; q2.out_f32 = 1; q2.R = reinterpret_cast<const float*>(K.has_shortcut ? sc : xb); q2.ldr = K.cout;
-        GemmParams& q0 = s.q0 = q1;                      // projection shortcut (k = 1) of pre -> fp32, into the spare activation buffer
+        GemmParams& q0 = sp.q0 = q1;                      // projection shortcut (k = 1) of pre -> fp32, into the spare activation buffer
         q0.W = K.shortcut.Ws32; q0.taps = 1; q0.K = K.cin; q0.Kp = K.cin; q0.scale = nullptr; q0.shift = nullptr; q0.Y = sc; q0.out_f32 = 1;
         // (rn_step_supported also asks for the split weights and the shapes: cin % 32 == 0, cout % 128 == 0, Tn >= 2)
-        s.ok = rn_step_supported(q1, 1) && rn_step_supported(q2, 2) && (!K.has_shortcut || rn_step_supported(q0, 2));
-        return s;
+        sp.ok = rn_step_supported(q1, 1) && rn_step_supported(q2, 2) && (!K.has_shortcut || rn_step_supported(q0, 2));
+        return sp;
     };
     // a producer writes block bn's pre-activation straight in the S32 layout when the block takes the split kernel and neither developer
     // hook is set (the block itself honours only rn_step_off: it splits an fp32 pre-activation first)
@@ -392,23 +453,23 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
     // bf16 / fp16 handles: the fused chain's first block computes the conv front-end itself from the waveform (rn_block128's CONV
     // form) and x is never stored; option rn_conv_unfused stores x with rn_conv3_front and runs the plain block (bit-identical)
     const bool fuse_ok = bf && stop_after < 0 && !h->opt.rn_unfused;
-    const svhip_handle::RnBlock& K0 = h->rn_blocks[0];
+    const RnBlock& K0 = s.blocks[0];
     const bool conv_fused = conv && fuse_ok && !h->opt.rn_conv_unfused &&
                             rn_block128_supported(K0.cin, K0.cout, T, K0.downsample, K0.has_shortcut, K0.conv1.Kp, K0.conv2.Kp);
     if (conv) {
-        if (!conv_fused && (rc = run(h, "rn_conv3_front", 2.0 * B * 128.0 * 3.0 * T, [&]() { return launch_rn_conv3_front(d_wav, h->rn_cw, x, dt, B, L, T, st); })))
+        if (!conv_fused && (rc = run(h, "rn_conv3_front", 2.0 * B * 128.0 * 3.0 * T, [&]() { return launch_rn_conv3_front(d_wav, s.cw, x, dt, B, L, T, st); })))
             return rc;
     } else if ((rc = run(h, "rn_sinc", 2.0 * B * 128.0 * 251.0 * (L - 250), [&]() {
              // (the kernel can also write block 0's pre-activation, but its 8-byte scattered stores make that as dear as the
              //  separate coalesced rn_bn_act pass: measured 0.85 + 0.29 ms either way)
-             if (sinc_x3) return launch_rn_sinc_x3(h->rn_filt_x3, h->rn_fbn_scale, h->rn_fbn_shift, reinterpret_cast<float*>(x), B, L, T, rn_xn, h->rn_Lp, h->num_cu, st,
-                                                   sinc_pre ? pre : nullptr, h->rn_blocks[0].bn1_scale, h->rn_blocks[0].bn1_shift);
+             if (sinc_x3) return launch_rn_sinc_x3(s.filt_x3, s.fbn_scale, s.fbn_shift, reinterpret_cast<float*>(x), B, L, T, rn_xn, s.Lp, h->num_cu, st,
+                                                   sinc_pre ? pre : nullptr, s.blocks[0].bn1_scale, s.blocks[0].bn1_shift);
              // fp16 handles: the symmetric form of the sinc convolution (K = 126 instead of 251; option rn_sinc_full keeps round 5's kernel)
-             const bool sym = h->f16 && h->rn_filt_sym && !h->opt.rn_sinc_full;
-             return launch_rn_sinc(d_wav, rn_stats, h->rn_gamma, h->rn_beta, sym ? h->rn_filt_sym : h->rn_filt, h->rn_fbn_scale, h->rn_fbn_shift, x, dt, B, L, T, st,
-                                   nullptr, nullptr, nullptr, rn_xn, h->rn_Lp, h->num_cu, sym);
+             const bool sym = h->f16 && s.filt_sym && !h->opt.rn_sinc_full;
+             return launch_rn_sinc(d_wav, rn_stats, s.gamma, s.beta, sym ? s.filt_sym : s.filt, s.fbn_scale, s.fbn_shift, x, dt, B, L, T, st,
+                                   nullptr, nullptr, nullptr, rn_xn, s.Lp, h->num_cu, sym);
          }))) return rc;
-    h->rn_dbg_x = x; h->rn_dbg_T = T; h->rn_dbg_C = 128;
+    s.dbg_x = x; s.dbg_T = T; s.dbg_C = 128;
     if (stop_after == 0) return SVHIP_OK;
     // bf16: the 128 -> 128 pooled blocks (layer1, layer2) each run as ONE fused kernel + the AFMS gate kernel; the gate of
     // block i is applied by block i + 1 on the way in (or by the rn_afms_apply pass in front of the first GEMM block)
@@ -417,7 +478,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
     const float *g_alpha = nullptr, *g_gate = nullptr;          // pending gate of the previous fused block
     const void* xin = x;
     for (; fuse_ok && first < 8; ++first) {
-        svhip_handle::RnBlock& K = h->rn_blocks[first];
+        RnBlock& K = s.blocks[first];
         if (!rn_block128_supported(K.cin, K.cout, T, K.downsample, K.has_shortcut, K.conv1.Kp, K.conv2.Kp)) break;
         RnBlock128Params bp;
         bp.xin = reinterpret_cast<const bf16_t*>(xin);
@@ -430,7 +491,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         bp.colsum = rn_part;
         bp.B = B; bp.T = T; bp.Tout = T / 3; bp.ntiles = rn_block128_ntiles(T); bp.f16 = h->f16 ? 1 : 0;
         const bool from_wave = first == 0 && conv_fused;
-        if (from_wave) { bp.xin = nullptr; bp.wav = d_wav; bp.cw = h->rn_cw; bp.L = L; }
+        if (from_wave) { bp.xin = nullptr; bp.wav = d_wav; bp.cw = s.cw; bp.L = L; }
         const double fl = (double)B * T * (K.conv1.flops_per_row + K.conv2.flops_per_row + (from_wave ? 2.0 * 128 * 3 : 0.0));
         if ((rc = run(h, from_wave ? "rn_block128_conv" : "rn_block128", fl, [&]() { return launch_rn_block128(bp, h->num_cu, st); }))) return rc;
         float* gate = rn_gate[first & 1];                        // two gate buffers: block i + 1 reads i's while writing its own
@@ -443,17 +504,17 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
     }
     if (first > 0) {
         // x = (o + alpha) * gate and, in the same pass, the next consumer's lrelu(bn(x))
-        svhip_handle::RnBlock& Kp = h->rn_blocks[first - 1];
-        const float* nsc = first < 8 ? h->rn_blocks[first].bn1_scale : h->rn_agg_scale;
-        const float* nsh = first < 8 ? h->rn_blocks[first].bn1_shift : h->rn_agg_shift;
+        RnBlock& Kp = s.blocks[first - 1];
+        const float* nsc = first < 8 ? s.blocks[first].bn1_scale : s.agg_scale;
+        const float* nsh = first < 8 ? s.blocks[first].bn1_shift : s.agg_shift;
         // x itself is read only as an identity shortcut (or as a debug stage): not written when the next block projects its input
-        void* xdst = (first < 8 && h->rn_blocks[first].has_shortcut && stop_after < 0) ? nullptr : x;
+        void* xdst = (first < 8 && s.blocks[first].has_shortcut && stop_after < 0) ? nullptr : x;
         if ((rc = run(h, "rn_afms_apply", 0, [&]() { return launch_rn_afms_apply(xin, xdst, dt, Kp.alpha, g_gate, B, T, Kp.cout, st, nsc, nsh, pre, 0.3f); }))) return rc;
-        h->rn_dbg_x = x; h->rn_dbg_T = T; h->rn_dbg_C = Kp.cout;
+        s.dbg_x = x; s.dbg_T = T; s.dbg_C = Kp.cout;
         if (snap_at == first && b0 == 0 && (rc = snapshot(pre, T, Kp.cout))) return rc;
     }
     for (int bi = first; bi < 8; ++bi) {
-        svhip_handle::RnBlock& K = h->rn_blocks[bi];
+        RnBlock& K = s.blocks[bi];
         const int M = B * T;
         // out = lrelu(bn1(x))                                                         RawNet_baseline.py:222
         // (blocks 1..7 get it from the previous block's AFMS pass, which writes x and lrelu(bn1(x)) together)
@@ -463,20 +524,20 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         }
         // (an fp32 pre-activation is split into a buffer that is free here: the next-x buffer when `sc` holds the projected shortcut)
         void* const split_dst = K.has_shortcut ? xn : sc;
-        const RnStep s = rn_step_plan(bi, T, pre_is_s32 ? pre : split_dst, x);
-        if (pre_is_s32 && !s.ok) SV_FAIL(h, SVHIP_ERR_STATE, "RawNet2 block %d: split pre-activation without the split convolution route", bi);
+        const RnStep sp = rn_step_plan(bi, T, pre_is_s32 ? pre : split_dst, x);
+        if (pre_is_s32 && !sp.ok) SV_FAIL(h, SVHIP_ERR_STATE, "RawNet2 block %d: split pre-activation without the split convolution route", bi);
         const bool tail_fused = !no_tail && rn_tail_supported(dt, K.downsample ? T / 3 : T, K.cout);
         bool pooled_by_conv = false;
         const void* resid_in_tail = nullptr;
         // conv1 -> bn2 -> lrelu (epilogue), conv2 + shortcut                            :224-226
         auto convs = [&]() -> int {
-            if (s.ok) {
+            if (sp.ok) {
                 if (!pre_is_s32 && (rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(reinterpret_cast<const float*>(pre), K.cin, split_dst, M, K.cin, st); }))) return rc;
-                if (K.has_shortcut && (rc = run(h, "rn_step", (double)M * K.shortcut.flops_per_row, [&]() { return launch_rn_step(s.q0, 2, st); }))) return rc;
-                if ((rc = run(h, "rn_step", (double)M * K.conv1.flops_per_row, [&]() { return launch_rn_step(s.q1, 1, st); }))) return rc;
+                if (K.has_shortcut && (rc = run(h, "rn_step", (double)M * K.shortcut.flops_per_row, [&]() { return launch_rn_step(sp.q0, 2, st); }))) return rc;
+                if ((rc = run(h, "rn_step", (double)M * K.conv1.flops_per_row, [&]() { return launch_rn_step(sp.q1, 1, st); }))) return rc;
                 // (a pooled block whose tail is not the fused kernel — the long utterances of layers 1 - 3: conv2 pools on its way out)
-                pooled_by_conv = K.downsample && !tail_fused && T >= 3 && !h->opt.rn_pool_off && rn_step_supported(s.q2, 3);
-                return run(h, "rn_step", (double)M * K.conv2.flops_per_row, [&]() { return launch_rn_step(s.q2, pooled_by_conv ? 3 : 2, st); });
+                pooled_by_conv = K.downsample && !tail_fused && T >= 3 && !h->opt.rn_pool_off && rn_step_supported(sp.q2, 3);
+                return run(h, "rn_step", (double)M * K.conv2.flops_per_row, [&]() { return launch_rn_step(sp.q2, pooled_by_conv ? 3 : 2, st); });
             }
             // A 1 x 1 shortcut rides in conv2's GEMM as extra K columns when the 256 x 256 kernel takes it (no shortcut tensor in HBM)
             const GemmParams psc = conv2sc_params(h, K, pre, hb, o, M, T);
@@ -500,11 +561,11 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         };
         if ((rc = convs())) return rc;
         // AFMS gate; the same pass writes the next consumer's lrelu(bn(.)): block bi+1's bn1, or the aggregation BN after block 7
-        const float* nsc = bi < 7 ? h->rn_blocks[bi + 1].bn1_scale : h->rn_agg_scale;
-        const float* nsh = bi < 7 ? h->rn_blocks[bi + 1].bn1_shift : h->rn_agg_shift;
+        const float* nsc = bi < 7 ? s.blocks[bi + 1].bn1_scale : s.agg_scale;
+        const float* nsh = bi < 7 ? s.blocks[bi + 1].bn1_shift : s.agg_shift;
         void* npre = stop_after >= 0 ? nullptr : pre;           // (the developer hook keeps the unfused sequence)
         // the block output itself is read only by an identity shortcut of the next block (or as a debug stage)
-        const bool x_dead = stop_after < 0 && npre && (bi == 7 || h->rn_blocks[bi + 1].has_shortcut);
+        const bool x_dead = stop_after < 0 && npre && (bi == 7 || s.blocks[bi + 1].has_shortcut);
         const int Tn = K.downsample ? T / 3 : T;
         if (tail_fused) {
             // max-pool + AFMS + next pre-activation in one launch, the pooled activation held in registers      :228-229, :62-68
@@ -539,7 +600,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
             pre_is_s32 = next_s32;
         }
         std::swap(x, xn);
-        h->rn_dbg_x = x; h->rn_dbg_T = T; h->rn_dbg_C = K.cout;
+        s.dbg_x = x; s.dbg_T = T; s.dbg_C = K.cout;
         if (stop_after == bi + 1) return SVHIP_OK;
         if (snap_at == bi + 1 && b0 == 0 && npre && (rc = snapshot(npre, T, K.cout))) return rc;
     }
@@ -548,38 +609,38 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         // aggregation: GRU over the T frames, its last state through fc_after_gru          RawNet2_custom.py:196-207
         // (pre = lrelu(bn_before_gru(x)), (B T, 512) frame-major, came out of block 7's AFMS pass)
         const int G = 3 * RN_GRU_HIDDEN;
-        float* gi = h->rn_gru_gi + (size_t)b0 * T * G;
-        GemmParams pg = conv_params(h, h->rn_gru_ih, pre, 512, gi, G, M, h->T);
+        float* gi = s.gru_gi + (size_t)b0 * T * G;
+        GemmParams pg = conv_params(h, s.gru_ih, pre, 512, gi, G, M, h->T);
         pg.out_f32 = 1;
-        const GemmPlan plan = conv_plan(h, h->rn_gru_ih, pg);          // (an fp32 output never takes the S32 form: plan.x3 is false)
+        const GemmPlan plan = conv_plan(h, s.gru_ih, pg);          // (an fp32 output never takes the S32 form: plan.x3 is false)
         if (plan.x3) SV_FAIL(h, SVHIP_ERR_STATE, "rn_gru_proj: unexpected split-operand route");
         if ((rc = run(h, "rn_gru_proj", plan.flops, [&]() { return launch_gemm(plan.q, h->bf16, st); }))) return rc;
-        float* hb[2] = {h->rn_gru_hbuf[0] + (size_t)b0 * RN_GRU_HIDDEN, h->rn_gru_hbuf[1] + (size_t)b0 * RN_GRU_HIDDEN};
+        float* hb[2] = {s.gru_hbuf[0] + (size_t)b0 * RN_GRU_HIDDEN, s.gru_hbuf[1] + (size_t)b0 * RN_GRU_HIDDEN};
         for (int t = 0; t < T; ++t)          // step t reads hb[t & 1] (h0 = 0: nothing) and writes hb[(t + 1) & 1]
             if ((rc = run(h, "rn_gru_step", 2.0 * B * G * RN_GRU_HIDDEN, [&]() {
-                     return launch_rn_gru_step(h->rn_gru_whh, dt, gi, h->rn_gru_bhn, t ? hb[t & 1] : nullptr, hb[(t + 1) & 1], B, T, t, st);
+                     return launch_rn_gru_step(s.gru_whh, dt, gi, s.gru_bhn, t ? hb[t & 1] : nullptr, hb[(t + 1) & 1], B, T, t, st);
                  }))) return rc;
-        if (b0 == 0) h->rn_gru_in = pre;                                 // (rawnet2_forward forgets it after a sliced forward)
-        h->rn_gru_h = h->rn_gru_hbuf[T & 1];
-        return run(h, "rn_gru_fc", 2.0 * B * h->rn_gru_fc.N * h->rn_gru_fc.K, [&]() {
-            return launch_rowvec_linear(hb[T & 1], RN_GRU_HIDDEN, h->rn_gru_fc.W, h->rn_gru_fc.bias, d_emb, c.embed_dim, B, c.embed_dim, RN_GRU_HIDDEN, ACT_NONE, st,
+        if (b0 == 0) s.gru_in = pre;                                 // (rawnet2_forward forgets it after a sliced forward)
+        s.gru_h = s.gru_hbuf[T & 1];
+        return run(h, "rn_gru_fc", 2.0 * B * s.gru_fc.N * s.gru_fc.K, [&]() {
+            return launch_rowvec_linear(hb[T & 1], RN_GRU_HIDDEN, s.gru_fc.W, s.gru_fc.bias, d_emb, c.embed_dim, B, c.embed_dim, RN_GRU_HIDDEN, ACT_NONE, st,
                                         h->bf16 && h->d_lin_part ? h->d_lin_part + (size_t)b0 * h->lin_part_per_utt : nullptr, true);
         });
     }
     // aggregation: attentive statistics pooling                                          RawNet2_custom.py:215-224
     // (pre = lrelu(bn_before_agg(x)) came out of block 7's AFMS pass)
     // (1 x 1 layers, like the projection shortcut, are given the handle's T: no frame index enters a pointwise GEMM without column sums or bias_utt)
-    GemmParams pa = conv_params(h, h->rn_att0, pre, 512, hb, 128, M, h->T);
+    GemmParams pa = conv_params(h, s.att0, pre, 512, hb, 128, M, h->T);
     pa.act1 = ACT_LRELU001;
-    if ((rc = conv_gemm(h, h->rn_att0, pa))) return rc;
-    float* rn_logits = h->rn_logits + (size_t)b0 * T * 512;
-    GemmParams pl = conv_params(h, h->rn_att3, hb, 128, rn_logits, 512, M, h->T);
+    if ((rc = conv_gemm(h, s.att0, pa))) return rc;
+    float* rn_logits = s.logits + (size_t)b0 * T * 512;
+    GemmParams pl = conv_params(h, s.att3, hb, 128, rn_logits, 512, M, h->T);
     pl.out_f32 = 1;
-    if ((rc = conv_gemm(h, h->rn_att3, pl))) return rc;
+    if ((rc = conv_gemm(h, s.att3, pl))) return rc;
     if ((rc = run(h, "rn_attn_pool", 0, [&]() { return launch_rn_attn_pool(rn_logits, pre, dt, B, T, 512, rn_pooled, st); }))) return rc;
-    if ((rc = run(h, "rn_fc", 2.0 * B * h->rn_fc.N * h->rn_fc.K, [&]() {
+    if ((rc = run(h, "rn_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
              // (16-bit handles, full batches: the K-split MFMA form — fp32-grade handles keep ONE kernel for every batch size here)
-             return launch_rowvec_linear(rn_pooled, 1024, h->rn_fc.W, h->rn_fc.bias, d_emb, c.embed_dim, B, c.embed_dim, 1024, ACT_NONE, st,
+             return launch_rowvec_linear(rn_pooled, 1024, s.fc.W, s.fc.bias, d_emb, c.embed_dim, B, c.embed_dim, 1024, ACT_NONE, st,
                                          h->bf16 && h->d_lin_part ? h->d_lin_part + (size_t)b0 * h->lin_part_per_utt : nullptr, true);
          }))) return rc;
     return SVHIP_OK;
@@ -590,7 +651,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
 int rawnet2_forward(svhip_handle* h, const float* d_wav, int B) {
     const int lanes = (h->lanes > 1 && B >= 16 * h->lanes && h->opt.rn_stop < 0) ? h->lanes : 1;
     const int rc = forward_lanes(h, rawnet2_forward_part, d_wav, B, lanes, ((B + lanes - 1) / lanes + 3) & ~3);
-    if (lanes > 1) h->rn_gru_in = nullptr;          // the slices' GRU inputs are not one (B T, 512) block
+    if (lanes > 1) S(h).gru_in = nullptr;          // the slices' GRU inputs are not one (B T, 512) block
     return rc;
 }
 

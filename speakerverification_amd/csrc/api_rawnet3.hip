@@ -20,11 +20,45 @@ namespace {
 
 constexpr int C = 1024, W = 128, D = 1536;
 
+int rn3_frames(int L) { return (L - RN3_TAPS) / RN3_STRIDE + 1; }      // T0 of RawNet3's front-end
+
+struct Rn3Layer {                         // Bottle2neck(k = 3, scale = 8): every BatchNorm follows a ReLU, so it is its conv's epilogue affine
+    ConvLayer conv1, convs[7], conv3, residual;      // conv1 + bn1, convs[i] + bns[i], conv3 + bn3; residual: 1 x 1, no bias (layer1)
+    bool has_residual = false;
+    float* alpha = nullptr;               // AFMS
+    LinearLayer afms_fc;
+};
+
+// RawNet3 layers (SVHIP_MODEL_RAWNET3: RawNet3.py with the defaults of its MainModel, RawNet_baseline.py:71-159)
+struct RawNet3State : ModelState {
+    Rn3Layer layers[3];
+    ConvLayer l4, att;                    // layer4 (3072 -> 1536, bias, ReLU); attention.0 columns [0, 1536) with attention.2 as epilogue
+    LinearLayer att_ctx, fc6;             // attention.0 columns [1536, 4608) + its bias: the per-utterance bias of the time-constant inputs; fc6
+    float *w2 = nullptr, *b2 = nullptr;                 // attention.3: the per-frame logit
+    float *bn5_scale = nullptr, *bn5_shift = nullptr;
+    float *in_w = nullptr, *in_b = nullptr;             // preprocess.1 (InstanceNorm1d affine)
+    double pre[2] = {-0.97, 1.0};                       // preprocess.0.flipped_filter: y[i] = pre[0] x[i - 1] + pre[1] x[i]
+    void* filt = nullptr;                 // [251][256] tap-major sinc filters: fp64 on fp32 handles, fp32 on bf16 handles
+    int T0 = 0;                           // front-end frames; layer1 pools to T0 / 5, layer2 to T0 / 5 / 3
+    void* buf[3] = {};                    // (Bmax * T0, 1024) activations each (the front-end's fp32 output passes through buf[1])
+    void* x0 = nullptr;                   // (Bmax * T0, 256): the front-end output, layer1's operand
+    void* cat = nullptr;                  // (Bmax * T2, 3072): [mp3(x1) | x2 | x3], layer4's operand
+    double* stats = nullptr;              // (Bmax, 2) pre-emphasis / InstanceNorm statistics
+    float *mean = nullptr, *gate = nullptr;             // (Bmax, 1024): time means, AFMS gates
+    float *tstat = nullptr, *ctx = nullptr;             // (Bmax, 3072) [mean | std] of layer4's output; (Bmax, 128) attention bias
+    float *logit = nullptr, *pooled = nullptr;          // (Bmax * T2) per-frame logits; (Bmax, 3072) bn5(pooled)
+    const void* stage[5] = {};            // svhip_get_stage: front-end, layer1, layer2, layer3, layer4 outputs of the last forward
+    int stage_T[5] = {}, stage_C[5] = {}, stage_ld[5] = {};
+};
+
+RawNet3State& S(svhip_handle* h) { return static_cast<RawNet3State&>(*h->model); }
+
 // One Bottle2neck on x (B T, cin) at row stride ldx, T frames in; its output y = AFMS(pool(.)) goes to (ydst, ldy), and with `add` the
 // same pass writes y + add to `sum`.  res: the identity residual (null: the layer's 1 x 1 residual conv of x into `rbuf`).
 // h1, h2, o: scratch (B T, 1024) buffers (o may be h1); pooled: (B T / P, 1024) scratch when P > 1.
-int bottle2neck(svhip_handle* h, const svhip_handle::Rn3Layer& Ly, const void* x, int ldx, int cin, int B, int T, int P, const void* res, void* rbuf,
+int bottle2neck(svhip_handle* h, const Rn3Layer& Ly, const void* x, int ldx, int cin, int B, int T, int P, const void* res, void* rbuf,
                 void* h1, void* h2, void* o, void* pooled, void* ydst, int ldy, const void* add, int ldadd, void* sum, int ldsum) {
+    auto& s = S(h);
     const int M = B * T, e = h->esz, dt = h->dt;
     hipStream_t st = h->cur;
     int rc;
@@ -55,11 +89,11 @@ int bottle2neck(svhip_handle* h, const svhip_handle::Rn3Layer& Ly, const void* x
         z = pooled;
     }
     // AFMS: (z + alpha) * sigmoid(fc(mean_t z))                                        RawNet_baseline.py:58-65
-    if ((rc = run(h, "rn3_afms_mean", 0, [&]() { return launch_colmean(z, dt, C, B, Tn, C, h->rn3_mean, st); }))) return rc;
+    if ((rc = run(h, "rn3_afms_mean", 0, [&]() { return launch_colmean(z, dt, C, B, Tn, C, s.mean, st); }))) return rc;
     if ((rc = run(h, "rn3_afms_gate", 2.0 * B * C * C, [&]() {
-             return launch_rowvec_linear(h->rn3_mean, C, Ly.afms_fc.W, Ly.afms_fc.bias, h->rn3_gate, C, B, C, C, ACT_SIGMOID, st);
+             return launch_rowvec_linear(s.mean, C, Ly.afms_fc.W, Ly.afms_fc.bias, s.gate, C, B, C, C, ACT_SIGMOID, st);
          }))) return rc;
-    return run(h, "rn3_afms", 0, [&]() { return launch_rn3_afms(z, C, Ly.alpha, h->rn3_gate, ydst, ldy, add, ldadd, sum, ldsum, dt, B, Tn, C, st); });
+    return run(h, "rn3_afms", 0, [&]() { return launch_rn3_afms(z, C, Ly.alpha, s.gate, ydst, ldy, add, ldadd, sum, ldsum, dt, B, Tn, C, st); });
 }
 
 }  // namespace
@@ -108,6 +142,7 @@ void rawnet3_spec(const svhip_config& c, WeightSpec& spec) {
 // ParamSincFB(256, 251).filters() (asteroid-filterbanks 0.4; its cos half is RawNet_baseline.py:339-357's formula) from the
 // checkpoint's low_hz_, band_hz_, window_ and n_, in fp64, stored tap-major [251][256]: cos filters 0..127, sin filters 128..255
 static int bake_sinc3(svhip_handle* h) {
+    auto& s = S(h);
     const HostTensor *lo = getw(h, "conv1.filterbank.low_hz_"), *bd = getw(h, "conv1.filterbank.band_hz_"),
                      *win = getw(h, "conv1.filterbank.window_"), *nn = getw(h, "conv1.filterbank.n_");
     if (!lo || !bd || !win || !nn) SV_FAIL(h, SVHIP_ERR_MISSING, "missing conv1.filterbank tensors");
@@ -132,30 +167,31 @@ static int bake_sinc3(svhip_handle* h) {
     if (!h->bf16) {
         double* d;
         int rc = dev_upload(h, &d, f);
-        h->rn3_filt = d;
+        s.filt = d;
         return rc;
     }
     std::vector<float> ff(f.begin(), f.end());
     float* d;
     int rc = dev_upload(h, &d, ff);
-    h->rn3_filt = d;
+    s.filt = d;
     return rc;
 }
 
 int rawnet3_finalize(svhip_handle* h) {
+    auto& s = S(h);
     int rc;
     const HostTensor* pf;
     if ((rc = needw(h, "preprocess.0.flipped_filter", pf))) return rc;
-    h->rn3_pre[0] = pf->data[0]; h->rn3_pre[1] = pf->data[1];
-    if ((rc = upload_f32(h, "preprocess.1.weight", &h->rn3_in_w))) return rc;
-    if ((rc = upload_f32(h, "preprocess.1.bias", &h->rn3_in_b))) return rc;
+    s.pre[0] = pf->data[0]; s.pre[1] = pf->data[1];
+    if ((rc = upload_f32(h, "preprocess.1.weight", &s.in_w))) return rc;
+    if ((rc = upload_f32(h, "preprocess.1.bias", &s.in_b))) return rc;
     if ((rc = bake_sinc3(h))) return rc;
-    const int T0 = h->rn3_T0;
+    const int T0 = s.T0;
     double fl = 2.0 * RN3_FILTERS * RN3_TAPS * T0;
     const int dil[3] = {2, 3, 4}, pool[3] = {5, 3, 1};
     int T = T0;
     for (int li = 0; li < 3; ++li) {
-        svhip_handle::Rn3Layer& Ly = h->rn3[li];
+        Rn3Layer& Ly = s.layers[li];
         const std::string p = "layer" + std::to_string(li + 1);
         if ((rc = make_conv(h, Ly.conv1, p + ".conv1.weight", p + ".conv1.bias", p + ".bn1", 1))) return rc;
         for (int i = 0; i < 7; ++i)
@@ -170,108 +206,112 @@ int rawnet3_finalize(svhip_handle* h) {
         fl += (double)T * per_row + 2.0 * 1024 * 1024;
         T /= pool[li];
     }
-    if ((rc = make_conv(h, h->rn3_l4, "layer4.weight", "layer4.bias", "", 1))) return rc;
-    if ((rc = make_conv(h, h->rn3_att, "attention.0.weight", "", "attention.2", 1, 0, 1536))) return rc;
-    if ((rc = make_linear(h, h->rn3_att_ctx, "attention.0.weight", "attention.0.bias", 1536, 3 * 1536))) return rc;
-    if ((rc = upload_f32(h, "attention.3.weight", &h->rn3_w2))) return rc;
-    if ((rc = upload_f32(h, "attention.3.bias", &h->rn3_b2))) return rc;
-    if ((rc = make_bn(h, "bn5", 2 * 1536, &h->rn3_bn5_scale, &h->rn3_bn5_shift))) return rc;
-    if ((rc = make_linear(h, h->rn3_fc6, "fc6.weight", "fc6.bias"))) return rc;
-    fl += (double)T * (h->rn3_l4.flops_per_row + h->rn3_att.flops_per_row + 2.0 * 128) + 2.0 * 128 * 3072 + 2.0 * h->rn3_fc6.N * h->rn3_fc6.K;
+    if ((rc = make_conv(h, s.l4, "layer4.weight", "layer4.bias", "", 1))) return rc;
+    if ((rc = make_conv(h, s.att, "attention.0.weight", "", "attention.2", 1, 0, 1536))) return rc;
+    if ((rc = make_linear(h, s.att_ctx, "attention.0.weight", "attention.0.bias", 1536, 3 * 1536))) return rc;
+    if ((rc = upload_f32(h, "attention.3.weight", &s.w2))) return rc;
+    if ((rc = upload_f32(h, "attention.3.bias", &s.b2))) return rc;
+    if ((rc = make_bn(h, "bn5", 2 * 1536, &s.bn5_scale, &s.bn5_shift))) return rc;
+    if ((rc = make_linear(h, s.fc6, "fc6.weight", "fc6.bias"))) return rc;
+    fl += (double)T * (s.l4.flops_per_row + s.att.flops_per_row + 2.0 * 128) + 2.0 * 128 * 3072 + 2.0 * s.fc6.N * s.fc6.K;
     h->flops_per_utt = fl;
     return SVHIP_OK;
 }
 
 int rawnet3_alloc(svhip_handle* h) {
+    h->model = std::make_unique<RawNet3State>();
+    auto& s = S(h);
     const svhip_config& c = h->cfg;
     const size_t B = c.max_batch;
     int rc;
     // three (B T0, 1024) activation buffers carry layer1 (rawnet3_forward_part); the later stages reuse them
-    h->rn3_T0 = rn3_frames(c.samples);
-    const size_t M0 = B * (size_t)h->rn3_T0, T2 = (size_t)(h->rn3_T0 / 5 / 3);
+    s.T0 = rn3_frames(c.samples);
+    const size_t M0 = B * (size_t)s.T0, T2 = (size_t)(s.T0 / 5 / 3);
     if (T2 < 2) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance too short for RawNet3 (%d samples)", c.samples);
-    for (int i = 0; i < 3; ++i) if ((rc = actbuf(h, &h->rn3_buf[i], M0 * C))) return rc;
-    if ((rc = actbuf(h, &h->rn3_cat, B * T2 * 3 * C))) return rc;
-    if ((rc = actbuf(h, &h->rn3_x0, M0 * RN3_FILTERS))) return rc;
-    if ((rc = dev_alloc(h, &h->rn3_stats, B * 2))) return rc;
-    if ((rc = dev_alloc(h, &h->rn3_mean, B * 1024))) return rc;
-    if ((rc = dev_alloc(h, &h->rn3_gate, B * 1024))) return rc;
-    if ((rc = dev_alloc(h, &h->rn3_tstat, B * 3072))) return rc;
-    if ((rc = dev_alloc(h, &h->rn3_ctx, B * 128))) return rc;
-    if ((rc = dev_alloc(h, &h->rn3_logit, B * T2))) return rc;
-    if ((rc = dev_alloc(h, &h->rn3_pooled, B * 3072))) return rc;
+    for (int i = 0; i < 3; ++i) if ((rc = actbuf(h, &s.buf[i], M0 * C))) return rc;
+    if ((rc = actbuf(h, &s.cat, B * T2 * 3 * C))) return rc;
+    if ((rc = actbuf(h, &s.x0, M0 * RN3_FILTERS))) return rc;
+    if ((rc = dev_alloc(h, &s.stats, B * 2))) return rc;
+    if ((rc = dev_alloc(h, &s.mean, B * 1024))) return rc;
+    if ((rc = dev_alloc(h, &s.gate, B * 1024))) return rc;
+    if ((rc = dev_alloc(h, &s.tstat, B * 3072))) return rc;
+    if ((rc = dev_alloc(h, &s.ctx, B * 128))) return rc;
+    if ((rc = dev_alloc(h, &s.logit, B * T2))) return rc;
+    if ((rc = dev_alloc(h, &s.pooled, B * 3072))) return rc;
     return SVHIP_OK;
 }
 
 int rawnet3_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // rn3_front, rn3_layer1 .. 3, rn3_layer4, rn3_pooled
+    auto& s = S(h);
     static const char* kStages[5] = {"rn3_front", "rn3_layer1", "rn3_layer2", "rn3_layer3", "rn3_layer4"};
     int i = 0;
     while (i < 5 && n != kStages[i]) ++i;
-    if (n == "rn3_pooled") { v.src = h->rn3_pooled; v.rows = h->lastB; v.cols = v.ld = 3072; v.f32 = true; }
+    if (n == "rn3_pooled") { v.src = s.pooled; v.rows = h->lastB; v.cols = v.ld = 3072; v.f32 = true; }
     else if (i == 5) return unknown_stage(h, n);
-    else { v.src = h->rn3_stage[i]; v.rows = (size_t)h->lastB * h->rn3_stage_T[i]; v.cols = h->rn3_stage_C[i]; v.ld = h->rn3_stage_ld[i]; }
+    else { v.src = s.stage[i]; v.rows = (size_t)h->lastB * s.stage_T[i]; v.cols = s.stage_C[i]; v.ld = s.stage_ld[i]; }
     return SVHIP_OK;
 }
 
 // RawNet3.forward on device-resident waveforms (B, L), enqueued on h->cur (one slice: b0 is 0)
 static int rawnet3_forward_part(svhip_handle* h, const float* d_wav, int b0, int B) {
+    auto& s = S(h);
     (void)b0;
     const svhip_config& c = h->cfg;
     const int L = c.samples, e = h->esz, dt = h->dt;
-    const int T0 = h->rn3_T0, T1 = T0 / 5, T2 = T1 / 3;
+    const int T0 = s.T0, T1 = T0 / 5, T2 = T1 / 3;
     hipStream_t st = h->cur;
-    void *P0 = h->rn3_buf[0], *P1 = h->rn3_buf[1], *P2 = h->rn3_buf[2], *CAT = h->rn3_cat;
+    void *P0 = s.buf[0], *P1 = s.buf[1], *P2 = s.buf[2], *CAT = s.cat;
     int rc;
-    auto stage = [&](int i, const void* src, int T, int Cn, int ld) { h->rn3_stage[i] = src; h->rn3_stage_T[i] = T; h->rn3_stage_C[i] = Cn; h->rn3_stage_ld[i] = ld; };
+    auto stage = [&](int i, const void* src, int T, int Cn, int ld) { s.stage[i] = src; s.stage_T[i] = T; s.stage_C[i] = Cn; s.stage_ld[i] = ld; };
 
     // front-end: log(|sinc(in_norm(pre_emph(x)))| + 1e-6) - mean_t                  RawNet3.py:88-99
     float* y = static_cast<float*>(P1);
-    void* x0 = h->rn3_x0;
+    void* x0 = s.x0;
     if ((rc = run(h, "rn3_sinc", 2.0 * B * RN3_FILTERS * RN3_TAPS * (double)T0, [&]() {
-             return launch_rn3_front(d_wav, B, L, T0, h->rn3_pre[0], h->rn3_pre[1], h->rn3_in_w, h->rn3_in_b, h->rn3_filt, !h->bf16, h->rn3_stats, y, st);
+             return launch_rn3_front(d_wav, B, L, T0, s.pre[0], s.pre[1], s.in_w, s.in_b, s.filt, !h->bf16, s.stats, y, st);
          }))) return rc;
-    if ((rc = run(h, "rn3_front_mean", 0, [&]() { return launch_colmean(y, DT_F32, RN3_FILTERS, B, T0, RN3_FILTERS, h->rn3_mean, st); }))) return rc;
-    if ((rc = run(h, "rn3_center", 0, [&]() { return launch_rn3_center(y, h->rn3_mean, x0, dt, B, T0, st); }))) return rc;
+    if ((rc = run(h, "rn3_front_mean", 0, [&]() { return launch_colmean(y, DT_F32, RN3_FILTERS, B, T0, RN3_FILTERS, s.mean, st); }))) return rc;
+    if ((rc = run(h, "rn3_center", 0, [&]() { return launch_rn3_center(y, s.mean, x0, dt, B, T0, st); }))) return rc;
     stage(0, x0, T0, RN3_FILTERS, RN3_FILTERS);
 
     // layer1 = Bottle2neck(256, 1024, dilation 2, pool 5): x1 -> P0
-    if ((rc = bottle2neck(h, h->rn3[0], x0, RN3_FILTERS, RN3_FILTERS, B, T0, 5, nullptr, P0, P1, P2, P1, P2, P0, C, nullptr, 0, nullptr, 0)))
+    if ((rc = bottle2neck(h, s.layers[0], x0, RN3_FILTERS, RN3_FILTERS, B, T0, 5, nullptr, P0, P1, P2, P1, P2, P0, C, nullptr, 0, nullptr, 0)))
         return rc;
     stage(1, P0, T1, C, C);
     // mp3(x1) -> CAT[:, 0:1024), written once
     if ((rc = run(h, "rn3_maxpool", 0, [&]() { return launch_rn3_maxpool(P0, C, CAT, 3 * C, dt, B, T1, C, 3, st); }))) return rc;
     // layer2 = Bottle2neck(1024, 1024, dilation 3, pool 3), identity residual x1: x2 -> CAT[:, 1024:2048), mp3(x1) + x2 -> P1
-    if ((rc = bottle2neck(h, h->rn3[1], P0, C, C, B, T1, 3, P0, nullptr, P1, P2, P1, P2, off(CAT, C, e), 3 * C, CAT, 3 * C, P1, C)))
+    if ((rc = bottle2neck(h, s.layers[1], P0, C, C, B, T1, 3, P0, nullptr, P1, P2, P1, P2, off(CAT, C, e), 3 * C, CAT, 3 * C, P1, C)))
         return rc;
     stage(2, off(CAT, C, e), T2, C, 3 * C);
     // layer3 = Bottle2neck(1024, 1024, dilation 4) on mp3(x1) + x2, which is also its residual: x3 -> CAT[:, 2048:3072)
     void* h1 = P2;
     void* h2 = off(P2, (size_t)B * T2 * C, e);
-    if ((rc = bottle2neck(h, h->rn3[2], P1, C, C, B, T2, 1, P1, nullptr, h1, h2, h1, nullptr, off(CAT, 2 * C, e), 3 * C, nullptr, 0, nullptr, 0))) return rc;
+    if ((rc = bottle2neck(h, s.layers[2], P1, C, C, B, T2, 1, P1, nullptr, h1, h2, h1, nullptr, off(CAT, 2 * C, e), 3 * C, nullptr, 0, nullptr, 0))) return rc;
     stage(3, off(CAT, 2 * C, e), T2, C, 3 * C);
 
     // layer4: relu(Conv1d(3072, 1536, 1)(cat(mp3(x1), x2, x3)))                       RawNet3.py:107-108
     const int M2 = B * T2;
-    GemmParams p4 = conv_params(h, h->rn3_l4, CAT, 3 * C, P1, D, M2, T2);
+    GemmParams p4 = conv_params(h, s.l4, CAT, 3 * C, P1, D, M2, T2);
     p4.act1 = ACT_RELU;
-    if ((rc = conv_gemm(h, h->rn3_l4, p4))) return rc;
+    if ((rc = conv_gemm(h, s.l4, p4))) return rc;
     stage(4, P1, T2, D, D);
 
     // context attentive statistics pooling                                            RawNet3.py:112-142
     // attention.0 on cat(x, mean_t x, std_t x): the time-constant two thirds are a per-utterance bias
-    if ((rc = run(h, "rn3_tstats", 0, [&]() { return launch_rn3_tstats(P1, D, dt, B, T2, D, h->rn3_tstat, st); }))) return rc;
+    if ((rc = run(h, "rn3_tstats", 0, [&]() { return launch_rn3_tstats(P1, D, dt, B, T2, D, s.tstat, st); }))) return rc;
     if ((rc = run(h, "rn3_att_ctx", 2.0 * B * 128 * 2 * D, [&]() {
-             return launch_rowvec_linear(h->rn3_tstat, 2 * D, h->rn3_att_ctx.W, h->rn3_att_ctx.bias, h->rn3_ctx, 128, B, 128, 2 * D, ACT_NONE, st);
+             return launch_rowvec_linear(s.tstat, 2 * D, s.att_ctx.W, s.att_ctx.bias, s.ctx, 128, B, 128, 2 * D, ACT_NONE, st);
          }))) return rc;
-    GemmParams pa = conv_params(h, h->rn3_att, P1, D, P2, 128, M2, T2);              // attention.2(relu(attention.0(.)))
-    pa.act1 = ACT_RELU; pa.bias_utt = h->rn3_ctx; pa.ld_bu = 128;
-    if ((rc = conv_gemm(h, h->rn3_att, pa))) return rc;
+    GemmParams pa = conv_params(h, s.att, P1, D, P2, 128, M2, T2);              // attention.2(relu(attention.0(.)))
+    pa.act1 = ACT_RELU; pa.bias_utt = s.ctx; pa.ld_bu = 128;
+    if ((rc = conv_gemm(h, s.att, pa))) return rc;
     if ((rc = run(h, "rn3_pool", 0, [&]() {
-             return launch_rn3_ctx_pool(P2, 128, h->rn3_w2, h->rn3_b2, h->rn3_logit, P1, D, dt, B, T2, D, h->rn3_bn5_scale, h->rn3_bn5_shift, h->rn3_stats, h->rn3_pooled, st);
+             return launch_rn3_ctx_pool(P2, 128, s.w2, s.b2, s.logit, P1, D, dt, B, T2, D, s.bn5_scale, s.bn5_shift, s.stats, s.pooled, st);
          }))) return rc;
     // fc6 (out_bn=False: bn6 is not applied)                                         RawNet3.py:144-148
-    return run(h, "rn3_fc6", 2.0 * B * h->rn3_fc6.N * h->rn3_fc6.K, [&]() {
-        return launch_rowvec_linear(h->rn3_pooled, 2 * D, h->rn3_fc6.W, h->rn3_fc6.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * D, ACT_NONE, st);
+    return run(h, "rn3_fc6", 2.0 * B * s.fc6.N * s.fc6.K, [&]() {
+        return launch_rowvec_linear(s.pooled, 2 * D, s.fc6.W, s.fc6.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * D, ACT_NONE, st);
     });
 }
 

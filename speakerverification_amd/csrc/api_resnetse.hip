@@ -22,6 +22,38 @@ namespace svhip {
 
 namespace {
 
+struct RsConv {
+    void* W = nullptr;                    // [cin / CK][taps][cout][CK] in the compute type (resnetse.hip)
+    float *scale = nullptr, *shift = nullptr;
+    int cin = 0, cout = 0, stride = 1, ks = 3;
+};
+struct RsBlock {
+    RsConv c1, c2, down;                  // conv1 + bn1, conv2 + bn2, downsample.0 + downsample.1 (the first block of stages 2 - 4)
+    bool has_down = false;
+    float *se_w1 = nullptr, *se_b1 = nullptr, *se_w2 = nullptr, *se_b2 = nullptr;      // se.fc.0 [16][C], se.fc.2 [C][16]
+};
+
+// ResNetSE layers (SVHIP_MODEL_RESNETSE: models/ResNetSE34V2.py).  Activations are channels-last (B, P, Q, C), P frames x Q mel rows; every
+// BatchNorm is the scale / shift of the convolution before it
+struct ResNetSEState : ModelState {
+    std::vector<RsBlock> blocks;          // the blocks of all stages in order
+    int stage_end[4] = {};                // index one past the last block of each stage
+    int P[5] = {}, Q[5] = {}, C[5] = {};  // image size and channels of the stem output [0] and of each stage's output [1 .. 4]
+    float *stem_w = nullptr, *stem_b = nullptr, *stem_scale = nullptr, *stem_shift = nullptr;     // conv1 tap-major [9][32], bn1
+    ConvLayer att0, att3;                 // attention.0 (+ ReLU, attention.2 as the epilogue affine), attention.3; K permuted to q C + c
+    LinearLayer fc;                       // fc, columns permuted the same way
+    bool sap = false;                     // encoder_type 'SAP': fc reads the weighted means only
+    float* xin = nullptr;                 // (Bmax, P, Q) fp32: the normalised input
+    void* out[5] = {};                    // the stem output and each stage's output (stages rs_stem, rs_layer1 .. rs_layer4)
+    void* tmp[5] = {};                    // block outputs inside a stage (ping-pong), conv1 output, conv2 output, downsample output
+    float *part = nullptr, *gate = nullptr;      // SE: per-tile channel sums of conv2's output, (Bmax, C) gates
+    void* att = nullptr;                  // (Bmax P4, 128)
+    float* logits = nullptr;              // (Bmax P4, Q4 C4) fp32
+    float *pool_raw = nullptr, *pool = nullptr, *pool_one = nullptr, *pool_zero = nullptr;     // (Bmax, 2 Q4 C4) [mu | sg]
+};
+
+ResNetSEState& S(svhip_handle* h) { return static_cast<ResNetSEState&>(*h->model); }
+
 // The 2-D ResNet family as data: blocks per stage, widths, block kind.  A sibling depth is another row.
 enum RsBlockKind { RS_SE_BASIC_V2 = 0 };
 struct RsArch { int blocks[4]; int widths[4]; RsBlockKind kind; int se_hidden; int att_dim; };
@@ -50,7 +82,7 @@ int rs_upload_packed(svhip_handle* h, const std::vector<float>& m, void** dst) {
     return rc;
 }
 
-int make_rs_conv(svhip_handle* h, svhip_handle::RsConv& L, const std::string& wname, const std::string& bnname, int cin, int cout, int ks, int stride) {
+int make_rs_conv(svhip_handle* h, RsConv& L, const std::string& wname, const std::string& bnname, int cin, int cout, int ks, int stride) {
     const HostTensor* w;
     int rc;
     if ((rc = needw(h, wname, w))) return rc;
@@ -59,7 +91,7 @@ int make_rs_conv(svhip_handle* h, svhip_handle::RsConv& L, const std::string& wn
     return make_bn(h, bnname, cout, &L.scale, &L.shift);
 }
 
-RsConvParams rs_params(const svhip_handle::RsConv& L, const void* x, void* y, int B, int P, int Q, bool relu_in, bool relu_out, float* part) {
+RsConvParams rs_params(const RsConv& L, const void* x, void* y, int B, int P, int Q, bool relu_in, bool relu_out, float* part) {
     RsConvParams p;
     p.X = x; p.Y = y; p.W = L.W; p.scale = L.scale; p.shift = L.shift; p.part = part;
     p.B = B; p.P = P; p.Q = Q; p.Cin = L.cin; p.Cout = L.cout; p.stride = L.stride; p.ks = L.ks;
@@ -104,6 +136,7 @@ void resnetse_spec(const svhip_config& c, WeightSpec& spec) {
 }
 
 int resnetse_finalize(svhip_handle* h) {
+    auto& s = S(h);
     const svhip_config& c = h->cfg;
     const RsArch& a = arch_of(c);
     int rc;
@@ -116,34 +149,34 @@ int resnetse_finalize(svhip_handle* h) {
         for (int n = 0; n < C0; ++n)
             for (int dp = 0; dp < 3; ++dp)
                 for (int dq = 0; dq < 3; ++dq) tw[(size_t)(dp * 3 + dq) * C0 + n] = w->data[(size_t)n * 9 + dq * 3 + dp];
-        if ((rc = dev_upload(h, &h->rs_stem_w, tw)) || (rc = upload_f32(h, "conv1.bias", &h->rs_stem_b)) ||
-            (rc = make_bn(h, "bn1", C0, &h->rs_stem_scale, &h->rs_stem_shift))) return rc;
+        if ((rc = dev_upload(h, &s.stem_w, tw)) || (rc = upload_f32(h, "conv1.bias", &s.stem_b)) ||
+            (rc = make_bn(h, "bn1", C0, &s.stem_scale, &s.stem_shift))) return rc;
     }
-    double fl = 2.0 * 9 * a.widths[0] * h->rs_P[0] * h->rs_Q[0];
-    h->rs.clear();
+    double fl = 2.0 * 9 * a.widths[0] * s.P[0] * s.Q[0];
+    s.blocks.clear();
     int inpl = a.widths[0];
-    for (int s = 0; s < 4; ++s) {
-        const int C = a.widths[s];
-        const double pos = (double)h->rs_P[s + 1] * h->rs_Q[s + 1];
-        for (int j = 0; j < a.blocks[s]; ++j) {
-            const std::string p = "layer" + std::to_string(s + 1) + "." + std::to_string(j) + ".";
-            svhip_handle::RsBlock K;
-            const int stride = (j == 0 && s > 0) ? 2 : 1;
+    for (int sg = 0; sg < 4; ++sg) {
+        const int C = a.widths[sg];
+        const double pos = (double)s.P[sg + 1] * s.Q[sg + 1];
+        for (int j = 0; j < a.blocks[sg]; ++j) {
+            const std::string p = "layer" + std::to_string(sg + 1) + "." + std::to_string(j) + ".";
+            RsBlock K;
+            const int stride = (j == 0 && sg > 0) ? 2 : 1;
             if ((rc = make_rs_conv(h, K.c1, p + "conv1.weight", p + "bn1", inpl, C, 3, stride)) ||
                 (rc = make_rs_conv(h, K.c2, p + "conv2.weight", p + "bn2", C, C, 3, 1))) return rc;
-            K.has_down = j == 0 && s > 0;
+            K.has_down = j == 0 && sg > 0;
             if (K.has_down && (rc = make_rs_conv(h, K.down, p + "downsample.0.weight", p + "downsample.1", inpl, C, 1, 2))) return rc;
             if ((rc = upload_f32(h, p + "se.fc.0.weight", &K.se_w1)) || (rc = upload_f32(h, p + "se.fc.0.bias", &K.se_b1)) ||
                 (rc = upload_f32(h, p + "se.fc.2.weight", &K.se_w2)) || (rc = upload_f32(h, p + "se.fc.2.bias", &K.se_b2))) return rc;
             fl += pos * (2.0 * 9 * inpl * C + 2.0 * 9 * C * C + (K.has_down ? 2.0 * inpl * C : 0.0));
-            h->rs.push_back(K);
+            s.blocks.push_back(K);
             inpl = C;
         }
-        h->rs_stage_end[s] = (int)h->rs.size();
+        s.stage_end[sg] = (int)s.blocks.size();
     }
     // The reference flattens (B, C, Q, P) to rows c Q + q; the channels-last rows here run q C + c.  The permutation goes once into the
     // K axis of attention.0 and fc and the N axis of attention.3, never into activations.
-    const int C4 = a.widths[3], Q4 = h->rs_Q[4], F = C4 * Q4, A = a.att_dim, nOut = c.embed_dim;
+    const int C4 = a.widths[3], Q4 = s.Q[4], F = C4 * Q4, A = a.att_dim, nOut = c.embed_dim;
     auto perm = [&](int k) { return (k % C4) * Q4 + k / C4; };        // column q C + c of this layout -> the reference's c Q + q
     {
         const HostTensor *w, *b;
@@ -151,7 +184,7 @@ int resnetse_finalize(svhip_handle* h) {
         HostTensor pw; pw.shape = {A, F}; pw.data.resize((size_t)A * F);
         for (int n = 0; n < A; ++n)
             for (int k = 0; k < F; ++k) pw.data[(size_t)n * F + k] = w->data[(size_t)n * F + perm(k)];
-        if ((rc = make_conv(h, h->rs_att0, pw, &b->data, 1)) || (rc = make_bn(h, "attention.2", A, &h->rs_att0.scale, &h->rs_att0.shift))) return rc;
+        if ((rc = make_conv(h, s.att0, pw, &b->data, 1)) || (rc = make_bn(h, "attention.2", A, &s.att0.scale, &s.att0.shift))) return rc;
         if ((rc = needw(h, "attention.3.weight", w)) || (rc = needw(h, "attention.3.bias", b))) return rc;
         HostTensor pw3; pw3.shape = {F, A}; pw3.data.resize((size_t)F * A);
         std::vector<float> pb(F);
@@ -159,59 +192,62 @@ int resnetse_finalize(svhip_handle* h) {
             memcpy(&pw3.data[(size_t)k * A], &w->data[(size_t)perm(k) * A], (size_t)A * 4);
             pb[k] = b->data[perm(k)];
         }
-        if ((rc = make_conv(h, h->rs_att3, pw3, &pb, 1))) return rc;
+        if ((rc = make_conv(h, s.att3, pw3, &pb, 1))) return rc;
         if ((rc = needw(h, "fc.weight", w))) return rc;
-        const int halves = h->rs_sap ? 1 : 2, K = halves * F;
+        const int halves = s.sap ? 1 : 2, K = halves * F;
         std::vector<float> fw((size_t)nOut * K);
         for (int n = 0; n < nOut; ++n)
             for (int hf = 0; hf < halves; ++hf)
                 for (int k = 0; k < F; ++k) fw[(size_t)n * K + hf * F + k] = w->data[(size_t)n * K + hf * F + perm(k)];
-        h->rs_fc.N = nOut; h->rs_fc.K = K;
-        if ((rc = dev_upload(h, &h->rs_fc.W, fw)) || (rc = upload_f32(h, "fc.bias", &h->rs_fc.bias))) return rc;
+        s.fc.N = nOut; s.fc.K = K;
+        if ((rc = dev_upload(h, &s.fc.W, fw)) || (rc = upload_f32(h, "fc.bias", &s.fc.bias))) return rc;
     }
-    fl += (double)h->rs_P[4] * (h->rs_att0.flops_per_row + h->rs_att3.flops_per_row) + 2.0 * nOut * h->rs_fc.K;
+    fl += (double)s.P[4] * (s.att0.flops_per_row + s.att3.flops_per_row) + 2.0 * nOut * s.fc.K;
     h->flops_per_utt = fl;
     return SVHIP_OK;
 }
 
 int resnetse_alloc(svhip_handle* h) {
+    h->model = std::make_unique<ResNetSEState>();
+    auto& s = S(h);
     const svhip_config& c = h->cfg;
     const RsArch& a = arch_of(c);
     const size_t B = c.max_batch;
-    h->rs_sap = rs_is_sap(c);
-    h->rs_P[0] = h->T; h->rs_Q[0] = c.n_mels; h->rs_C[0] = a.widths[0];
-    for (int s = 0; s < 4; ++s) {
-        const int st = s == 0 ? 1 : 2;
-        h->rs_P[s + 1] = rs_out_size(h->rs_P[s], st);
-        h->rs_Q[s + 1] = rs_out_size(h->rs_Q[s], st);
-        h->rs_C[s + 1] = a.widths[s];
+    s.sap = rs_is_sap(c);
+    s.P[0] = h->T; s.Q[0] = c.n_mels; s.C[0] = a.widths[0];
+    for (int sg = 0; sg < 4; ++sg) {
+        const int st = sg == 0 ? 1 : 2;
+        s.P[sg + 1] = rs_out_size(s.P[sg], st);
+        s.Q[sg + 1] = rs_out_size(s.Q[sg], st);
+        s.C[sg + 1] = a.widths[sg];
     }
     int rc;
-    if ((rc = dev_alloc(h, &h->rs_xin, B * h->rs_P[0] * h->rs_Q[0]))) return rc;
+    if ((rc = dev_alloc(h, &s.xin, B * s.P[0] * s.Q[0]))) return rc;
     size_t big = 0, part = 0;
-    for (int s = 0; s <= 4; ++s) {
-        const size_t n = (size_t)h->rs_P[s] * h->rs_Q[s] * h->rs_C[s];
+    for (int sg = 0; sg <= 4; ++sg) {
+        const size_t n = (size_t)s.P[sg] * s.Q[sg] * s.C[sg];
         if (n > big) big = n;
-        if ((rc = actbuf(h, &h->rs_out[s], B * n))) return rc;
-        if (s > 0) {          // the SE tile sums of conv2 in this stage
+        if ((rc = actbuf(h, &s.out[sg], B * n))) return rc;
+        if (sg > 0) {          // the SE tile sums of conv2 in this stage
             RsConvParams p;
-            p.P = h->rs_P[s]; p.Q = h->rs_Q[s]; p.stride = 1; p.ks = 3;
+            p.P = s.P[sg]; p.Q = s.Q[sg]; p.stride = 1; p.ks = 3;
             rs_conv_plan(p);
-            const size_t m = (size_t)p.ntp * p.ntq * h->rs_C[s];
+            const size_t m = (size_t)p.ntp * p.ntq * s.C[sg];
             if (m > part) part = m;
         }
     }
-    for (int i = 0; i < 5; ++i) if ((rc = actbuf(h, &h->rs_tmp[i], B * big))) return rc;
-    if ((rc = dev_alloc(h, &h->rs_part, B * part)) || (rc = dev_alloc(h, &h->rs_gate, B * 256))) return rc;
-    const size_t F = (size_t)h->rs_C[4] * h->rs_Q[4], M = B * h->rs_P[4];
-    if ((rc = actbuf(h, &h->rs_att, M * a.att_dim)) || (rc = dev_alloc(h, &h->rs_logits, M * F)) ||
-        (rc = dev_alloc(h, &h->rs_pool_raw, B * 2 * F)) || (rc = dev_alloc(h, &h->rs_pool, B * 2 * F))) return rc;
+    for (int i = 0; i < 5; ++i) if ((rc = actbuf(h, &s.tmp[i], B * big))) return rc;
+    if ((rc = dev_alloc(h, &s.part, B * part)) || (rc = dev_alloc(h, &s.gate, B * 256))) return rc;
+    const size_t F = (size_t)s.C[4] * s.Q[4], M = B * s.P[4];
+    if ((rc = actbuf(h, &s.att, M * a.att_dim)) || (rc = dev_alloc(h, &s.logits, M * F)) ||
+        (rc = dev_alloc(h, &s.pool_raw, B * 2 * F)) || (rc = dev_alloc(h, &s.pool, B * 2 * F))) return rc;
     std::vector<float> one(2 * F, 1.0f), zero(2 * F, 0.0f);
-    if ((rc = dev_upload(h, &h->rs_pool_one, one)) || (rc = dev_upload(h, &h->rs_pool_zero, zero))) return rc;
+    if ((rc = dev_upload(h, &s.pool_one, one)) || (rc = dev_upload(h, &s.pool_zero, zero))) return rc;
     return SVHIP_OK;
 }
 
 static int resnetse_forward_part(svhip_handle* h, const float* d_feat, int b0, int B) {
+    auto& s = S(h);
     (void)b0;
     const svhip_config& c = h->cfg;
     const int dt = h->dt;
@@ -220,36 +256,36 @@ static int resnetse_forward_part(svhip_handle* h, const float* d_feat, int b0, i
     int rc;
     // log(x + 1e-6) - mean_t for features == 'melspectrogram', then InstanceNorm1d(n_mels) without affine: (B, n_mels, T) -> (B, T, n_mels) fp32
     if ((rc = run(h, "prologue", 0, [&]() {
-             return launch_prologue(d_feat, h->rs_xin, false, B, c.n_mels, h->T, c.log_input, h->d_ones, h->d_zeros, h->d_pstats, st);
+             return launch_prologue(d_feat, s.xin, false, B, c.n_mels, h->T, c.log_input, h->d_ones, h->d_zeros, h->d_pstats, st);
          }))) return rc;
     // conv1 (with bias) -> ReLU -> bn1                                                       ResNetBaseline.py:260-262
-    if ((rc = run(h, "rs_stem", 2.0 * 9 * h->rs_C[0] * B * h->rs_P[0] * h->rs_Q[0], [&]() {
-             return launch_rs_stem(h->rs_xin, h->rs_stem_w, h->rs_stem_b, h->rs_stem_scale, h->rs_stem_shift, h->rs_out[0], dt, B, h->rs_P[0], h->rs_Q[0], st);
+    if ((rc = run(h, "rs_stem", 2.0 * 9 * s.C[0] * B * s.P[0] * s.Q[0], [&]() {
+             return launch_rs_stem(s.xin, s.stem_w, s.stem_b, s.stem_scale, s.stem_shift, s.out[0], dt, B, s.P[0], s.Q[0], st);
          }))) return rc;
-    const void* x = h->rs_out[0];
-    int P = h->rs_P[0], Q = h->rs_Q[0], stage = 0, pp = 0;
+    const void* x = s.out[0];
+    int P = s.P[0], Q = s.Q[0], stage = 0, pp = 0;
     static const char* const kConvLabel[4] = {"rs_conv3x3_s1", "rs_conv3x3_s2", "rs_conv3x3_s3", "rs_conv3x3_s4"};
-    for (size_t i = 0; i < h->rs.size(); ++i) {
-        const svhip_handle::RsBlock& K = h->rs[i];
-        while ((int)i >= h->rs_stage_end[stage]) ++stage;
-        const bool last = (int)i + 1 == h->rs_stage_end[stage];
-        void* out = last ? h->rs_out[stage + 1] : h->rs_tmp[pp];
-        const RsConvParams p1 = rs_params(K.c1, x, h->rs_tmp[2], B, P, Q, true, true, nullptr);
-        const RsConvParams p2 = rs_params(K.c2, h->rs_tmp[2], h->rs_tmp[3], B, p1.Po, p1.Qo, false, false, h->rs_part);
+    for (size_t i = 0; i < s.blocks.size(); ++i) {
+        const RsBlock& K = s.blocks[i];
+        while ((int)i >= s.stage_end[stage]) ++stage;
+        const bool last = (int)i + 1 == s.stage_end[stage];
+        void* out = last ? s.out[stage + 1] : s.tmp[pp];
+        const RsConvParams p1 = rs_params(K.c1, x, s.tmp[2], B, P, Q, true, true, nullptr);
+        const RsConvParams p2 = rs_params(K.c2, s.tmp[2], s.tmp[3], B, p1.Po, p1.Qo, false, false, s.part);
         const double pos = (double)B * p1.Po * p1.Qo;
         if ((rc = run(h, kConvLabel[stage], 2.0 * 9 * K.c1.cin * K.c1.cout * pos, [&]() { return launch_rs_conv(p1, dt, st); }))) return rc;
         if ((rc = run(h, kConvLabel[stage], 2.0 * 9 * K.c2.cin * K.c2.cout * pos, [&]() { return launch_rs_conv(p2, dt, st); }))) return rc;
         if ((rc = run(h, "rs_se_gate", 0, [&]() {
-                 return launch_rs_se_gate(h->rs_part, p2.ntp * p2.ntq, B, K.c2.cout, p2.Po * p2.Qo, K.se_w1, K.se_b1, K.se_w2, K.se_b2, h->rs_gate, st);
+                 return launch_rs_se_gate(s.part, p2.ntp * p2.ntq, B, K.c2.cout, p2.Po * p2.Qo, K.se_w1, K.se_b1, K.se_w2, K.se_b2, s.gate, st);
              }))) return rc;
         const void* res = x;
         if (K.has_down) {
-            const RsConvParams pd = rs_params(K.down, x, h->rs_tmp[4], B, P, Q, true, false, nullptr);
+            const RsConvParams pd = rs_params(K.down, x, s.tmp[4], B, P, Q, true, false, nullptr);
             if ((rc = run(h, "rs_down", 2.0 * K.down.cin * K.down.cout * pos, [&]() { return launch_rs_conv(pd, dt, st); }))) return rc;
-            res = h->rs_tmp[4];
+            res = s.tmp[4];
         }
         if ((rc = run(h, "rs_se_apply", 0, [&]() {
-                 return launch_rs_se_apply(h->rs_tmp[3], res, h->rs_gate, out, dt, B, p2.Po * p2.Qo, K.c2.cout, !K.has_down, st);
+                 return launch_rs_se_apply(s.tmp[3], res, s.gate, out, dt, B, p2.Po * p2.Qo, K.c2.cout, !K.has_down, st);
              }))) return rc;
         x = out;
         P = p1.Po; Q = p1.Qo;
@@ -257,33 +293,34 @@ static int resnetse_forward_part(svhip_handle* h, const float* d_feat, int b0, i
     }
     // attention (ResNetBaseline.py:186-194,269-279) on rows (B P4, Q4 C4): Conv1d -> ReLU -> BN -> Conv1d -> softmax over frames, then the
     // weighted mean and sqrt(clamp(weighted variance, 1e-5))
-    const int F = h->rs_C[4] * h->rs_Q[4], M = B * P;
-    GemmParams pa = conv_params(h, h->rs_att0, x, F, h->rs_att, 128, M, P);
+    const int F = s.C[4] * s.Q[4], M = B * P;
+    GemmParams pa = conv_params(h, s.att0, x, F, s.att, 128, M, P);
     pa.act1 = ACT_RELU;
-    if ((rc = conv_gemm(h, h->rs_att0, pa))) return rc;
-    GemmParams pl = conv_params(h, h->rs_att3, h->rs_att, 128, h->rs_logits, F, M, P);
+    if ((rc = conv_gemm(h, s.att0, pa))) return rc;
+    GemmParams pl = conv_params(h, s.att3, s.att, 128, s.logits, F, M, P);
     pl.out_f32 = 1;
-    if ((rc = conv_gemm(h, h->rs_att3, pl))) return rc;
+    if ((rc = conv_gemm(h, s.att3, pl))) return rc;
     if ((rc = run(h, "rs_asp_pool", 0, [&]() {
-             return launch_asp_pool(h->rs_logits, x, bf, F, B, P, F, h->rs_pool_one, h->rs_pool_zero, h->rs_pool_raw, h->rs_pool, 1e-5f, 0.0f, st);
+             return launch_asp_pool(s.logits, x, bf, F, B, P, F, s.pool_one, s.pool_zero, s.pool_raw, s.pool, 1e-5f, 0.0f, st);
          }))) return rc;
     // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the GEMM's ReLU epilogue would have dropped it)
     if ((rc = run(h, "rs_in_check", 0, [&]() {
-             return launch_tn_nonfinite_rows(d_feat, (int64_t)c.n_mels * h->T, B, h->rs_pool, 2 * F, 2 * F, st);
+             return launch_tn_nonfinite_rows(d_feat, (int64_t)c.n_mels * h->T, B, s.pool, 2 * F, 2 * F, st);
          }))) return rc;
-    return run(h, "rs_fc", 2.0 * B * h->rs_fc.N * h->rs_fc.K, [&]() {
-        return launch_rowvec_linear(h->rs_pool, 2 * F, h->rs_fc.W, h->rs_fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, h->rs_fc.K, ACT_NONE, st);
+    return run(h, "rs_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
+        return launch_rowvec_linear(s.pool, 2 * F, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, s.fc.K, ACT_NONE, st);
     });
 }
 
 int resnetse_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, resnetse_forward_part, d_feat, B, 1, B); }
 
 int resnetse_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // rs_stem, rs_layer1 .. rs_layer4 (B P Q, C), rs_pool (B, 2 F)
-    int s = -1;
-    if (n == "rs_stem") s = 0;
-    else if (n.size() == 9 && n.compare(0, 8, "rs_layer") == 0 && n[8] >= '1' && n[8] <= '4') s = n[8] - '0';
-    if (s >= 0) { v.src = h->rs_out[s]; v.rows = (size_t)h->lastB * h->rs_P[s] * h->rs_Q[s]; v.cols = v.ld = h->rs_C[s]; }
-    else if (n == "rs_pool") { v.src = h->rs_pool; v.rows = h->lastB; v.cols = v.ld = 2 * (size_t)h->rs_C[4] * h->rs_Q[4]; v.f32 = true; }
+    auto& s = S(h);
+    int sg = -1;
+    if (n == "rs_stem") sg = 0;
+    else if (n.size() == 9 && n.compare(0, 8, "rs_layer") == 0 && n[8] >= '1' && n[8] <= '4') sg = n[8] - '0';
+    if (sg >= 0) { v.src = s.out[sg]; v.rows = (size_t)h->lastB * s.P[sg] * s.Q[sg]; v.cols = v.ld = s.C[sg]; }
+    else if (n == "rs_pool") { v.src = s.pool; v.rows = h->lastB; v.cols = v.ld = 2 * (size_t)s.C[4] * s.Q[4]; v.f32 = true; }
     else return unknown_stage(h, n);
     return SVHIP_OK;
 }

@@ -20,6 +20,40 @@
 
 namespace svhip {
 
+namespace {
+
+int tn_kernel_size(int H) { return H == 256 ? 3 : H == 512 ? 7 : H == 1024 ? 11 : 0; }      // TitaNet s / m / l (TitaNet.py:152-157)
+
+struct TnBlock {
+    float* dw_w[3] = {};                  // depthwise weights, tap-major [k][H] fp32
+    float* dw_b[3] = {};                  // depthwise biases [H]
+    ConvLayer pw[3], skip;                // pointwise convs + BN (ReLU in the epilogue); the 1 x 1 skip + BN
+    float* se1 = nullptr;                 // excitation.0 [H / 16][H] (bf16 handles: bf16 copy in se1_bf)
+    float* se2T = nullptr;                // excitation.2 transposed [H / 16][H]
+    void *se1_bf = nullptr, *se2T_bf = nullptr;
+};
+
+// TitaNet layers (SVHIP_MODEL_TITANET: models/TitaNet.py).  Every BatchNorm follows its conv directly, so it is folded into that
+// conv's weights and bias at finalize (the GEMM epilogues apply at most the ReLU)
+struct TitaNetState : ModelState {
+    std::vector<TnBlock> blocks;          // one per mega-block
+    int k = 0;                            // depthwise kernel size (3 / 7 / 11 for H = 256 / 512 / 1024)
+    ConvLayer prolog, epilog, att_in, att_out;     // prolog (k = 3, zero padding), epilog, attention in_linear / out_linear
+    float *pbn_scale = nullptr, *pbn_shift = nullptr;        // decoder.pool.1 (BatchNorm1d(3072))
+    LinearLayer fc;                       // decoder.linear.0 with decoder.linear.1 (BatchNorm1d(nOut)) folded in
+    void* buf[6] = {};                    // (Bmax T, H) each: prolog output, block output, block 0's first depthwise output, depthwise
+                                          // output, sub-block output, skip (the first three are the stages tn_prolog / tn_mega_last / tn_dw0)
+    void* enc = nullptr;                  // (Bmax T, 1536) epilog output
+    void* att = nullptr;                  // (Bmax T, 128) tanh(in_linear(.))
+    float* logits = nullptr;              // (Bmax T, 1536) fp32 attention energies
+    float *mean = nullptr, *gate = nullptr;                  // (Bmax, H) SE squeeze, SE gate
+    float *pool_raw = nullptr, *pool = nullptr;              // (Bmax, 3072) pooled [mean | std], after BN
+};
+
+TitaNetState& S(svhip_handle* h) { return static_cast<TitaNetState&>(*h->model); }
+
+}  // namespace
+
 int titanet_check(const svhip_config& c, const char*& err) {
     if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "TitaNet runs on SVHIP_F32 and SVHIP_BF16 handles only"; return SVHIP_ERR_UNSUPPORTED; }
     if (!tn_kernel_size(c.channels)) { err = "TitaNet is built for H = 256 / 512 / 1024 (sizes s / m / l: channels)"; return SVHIP_ERR_INVALID; }
@@ -89,6 +123,7 @@ static int make_conv_bn(svhip_handle* h, ConvLayer& L, const std::string& conv, 
 }
 
 int titanet_finalize(svhip_handle* h) {
+    auto& s = S(h);
     const svhip_config& c = h->cfg;
     const int H = c.channels, k = tn_kernel_size(H), Hh = H / 16, D = 1536, nOut = c.embed_dim, T = h->T;
     const int nb = titanet_blocks_loaded(h);
@@ -103,13 +138,13 @@ int titanet_finalize(svhip_handle* h) {
             if (!h->host_w.count(kv.first) && kv.first.find("num_batches_tracked") == std::string::npos)
                 SV_FAIL(h, SVHIP_ERR_MISSING, "tensor %s was never loaded (mega-block count %d)", kv.first.c_str(), nb);
     }
-    h->tn_k = k;
-    h->tn.assign(nb, svhip_handle::TnBlock{});
+    s.k = k;
+    s.blocks.assign(nb, TnBlock{});
     int rc;
-    if ((rc = make_conv_bn(h, h->tn_prolog, "encoder.prolog.conv_block.0", "encoder.prolog.conv_block.1"))) return rc;
-    double fl = h->tn_prolog.flops_per_row;
+    if ((rc = make_conv_bn(h, s.prolog, "encoder.prolog.conv_block.0", "encoder.prolog.conv_block.1"))) return rc;
+    double fl = s.prolog.flops_per_row;
     for (int i = 0; i < nb; ++i) {
-        svhip_handle::TnBlock& Bk = h->tn[i];
+        TnBlock& Bk = s.blocks[i];
         const std::string p = "encoder.mega_blocks." + std::to_string(i) + ".";
         for (int j = 0; j < 3; ++j) {
             const std::string q = p + "sub_blocks." + std::to_string(j) + ".conv_block.";
@@ -136,43 +171,45 @@ int titanet_finalize(svhip_handle* h) {
             if ((rc = upload_h16(h, m2, &Bk.se2T_bf))) return rc;
         }
     }
-    if ((rc = make_conv_bn(h, h->tn_epilog, "encoder.epilog.conv_block.0", "encoder.epilog.conv_block.1"))) return rc;
-    if ((rc = make_conv(h, h->tn_att_in, "decoder.pool.0.in_linear.weight", "decoder.pool.0.in_linear.bias", "", 1))) return rc;
-    if ((rc = make_conv(h, h->tn_att_out, "decoder.pool.0.out_linear.weight", "decoder.pool.0.out_linear.bias", "", 1))) return rc;
-    if ((rc = make_bn(h, "decoder.pool.1", 2 * D, &h->tn_pbn_scale, &h->tn_pbn_shift))) return rc;
+    if ((rc = make_conv_bn(h, s.epilog, "encoder.epilog.conv_block.0", "encoder.epilog.conv_block.1"))) return rc;
+    if ((rc = make_conv(h, s.att_in, "decoder.pool.0.in_linear.weight", "decoder.pool.0.in_linear.bias", "", 1))) return rc;
+    if ((rc = make_conv(h, s.att_out, "decoder.pool.0.out_linear.weight", "decoder.pool.0.out_linear.bias", "", 1))) return rc;
+    if ((rc = make_bn(h, "decoder.pool.1", 2 * D, &s.pbn_scale, &s.pbn_shift))) return rc;
     {
         // decoder.linear = Linear(3072, nOut) + BatchNorm1d(nOut): folded into one fp32 linear
         const HostTensor *w = getw(h, "decoder.linear.0.weight"), *b = getw(h, "decoder.linear.0.bias");
-        std::vector<double> s, t;
-        if ((rc = bn_fold(h, "decoder.linear.1", nOut, s, t))) return rc;
+        std::vector<double> bs, bt;
+        if ((rc = bn_fold(h, "decoder.linear.1", nOut, bs, bt))) return rc;
         std::vector<float> fw((size_t)nOut * 2 * D), fb(nOut);
         for (int n = 0; n < nOut; ++n) {
-            for (int i = 0; i < 2 * D; ++i) fw[(size_t)n * 2 * D + i] = (float)(s[n] * (double)w->data[(size_t)n * 2 * D + i]);
-            fb[n] = (float)(s[n] * (double)b->data[n] + t[n]);
+            for (int i = 0; i < 2 * D; ++i) fw[(size_t)n * 2 * D + i] = (float)(bs[n] * (double)w->data[(size_t)n * 2 * D + i]);
+            fb[n] = (float)(bs[n] * (double)b->data[n] + bt[n]);
         }
-        h->tn_fc.N = nOut; h->tn_fc.K = 2 * D;
-        if ((rc = dev_upload(h, &h->tn_fc.W, fw))) return rc;
-        if ((rc = dev_upload(h, &h->tn_fc.bias, fb))) return rc;
+        s.fc.N = nOut; s.fc.K = 2 * D;
+        if ((rc = dev_upload(h, &s.fc.W, fw))) return rc;
+        if ((rc = dev_upload(h, &s.fc.bias, fb))) return rc;
     }
-    fl += h->tn_epilog.flops_per_row + h->tn_att_in.flops_per_row + h->tn_att_out.flops_per_row;
+    fl += s.epilog.flops_per_row + s.att_in.flops_per_row + s.att_out.flops_per_row;
     h->flops_per_utt = (double)T * fl + 2.0 * nOut * 2 * D;
     return SVHIP_OK;
 }
 
 int titanet_alloc(svhip_handle* h) {
+    h->model = std::make_unique<TitaNetState>();
+    auto& s = S(h);
     const svhip_config& c = h->cfg;
     const size_t B = c.max_batch, M = B * h->T, H = c.channels;
     int rc;
     // six (B T, H) activation buffers, the encoder output, the attention activation and energies
     if ((rc = actbuf(h, &h->X_in, M * c.n_mels))) return rc;
-    for (int i = 0; i < 6; ++i) if ((rc = actbuf(h, &h->tn_buf[i], M * H))) return rc;
-    if ((rc = actbuf(h, &h->tn_enc, M * 1536))) return rc;
-    if ((rc = actbuf(h, &h->tn_att, M * 128))) return rc;
-    if ((rc = dev_alloc(h, &h->tn_logits, M * 1536))) return rc;
-    if ((rc = dev_alloc(h, &h->tn_mean, B * H))) return rc;
-    if ((rc = dev_alloc(h, &h->tn_gate, B * H))) return rc;
-    if ((rc = dev_alloc(h, &h->tn_pool_raw, B * 3072))) return rc;
-    if ((rc = dev_alloc(h, &h->tn_pool, B * 3072))) return rc;
+    for (int i = 0; i < 6; ++i) if ((rc = actbuf(h, &s.buf[i], M * H))) return rc;
+    if ((rc = actbuf(h, &s.enc, M * 1536))) return rc;
+    if ((rc = actbuf(h, &s.att, M * 128))) return rc;
+    if ((rc = dev_alloc(h, &s.logits, M * 1536))) return rc;
+    if ((rc = dev_alloc(h, &s.mean, B * H))) return rc;
+    if ((rc = dev_alloc(h, &s.gate, B * H))) return rc;
+    if ((rc = dev_alloc(h, &s.pool_raw, B * 3072))) return rc;
+    if ((rc = dev_alloc(h, &s.pool, B * 3072))) return rc;
     if (h->bf16) {          // the third pointwise GEMM's column-sum partials (the SE squeeze)
         h->colsum_region = (int64_t)((M + 255) / 256 + 2) * 16 * H;
         if ((rc = dev_alloc(h, &h->d_colsum, (size_t)2 * h->colsum_region))) return rc;
@@ -180,12 +217,13 @@ int titanet_alloc(svhip_handle* h) {
     return SVHIP_OK;
 }
 static int titanet_forward_part(svhip_handle* h, const float* d_feat, int b0, int B) {
+    auto& s = S(h);
     (void)b0;
     const svhip_config& c = h->cfg;
-    const int T = h->T, M = B * T, H = c.channels, E = 1536, k = h->tn_k, dt = h->dt;
+    const int T = h->T, M = B * T, H = c.channels, E = 1536, k = s.k, dt = h->dt;
     const bool bf = h->bf16;
     hipStream_t st = h->cur;
-    void *PRO = h->tn_buf[0], *X = h->tn_buf[1], *D0 = h->tn_buf[2], *D = h->tn_buf[3], *S = h->tn_buf[4], *K = h->tn_buf[5];
+    void *PRO = s.buf[0], *X = s.buf[1], *D0 = s.buf[2], *D = s.buf[3], *S = s.buf[4], *K = s.buf[5];
     float* cs = bf ? h->d_colsum : nullptr;
     int rc;
     // the mel power (B, n_mels, T) as it is (no log, no normalisation) -> frame-major (B T, n_mels) in the compute type
@@ -193,13 +231,13 @@ static int titanet_forward_part(svhip_handle* h, const float* d_feat, int b0, in
              return launch_prologue(d_feat, h->X_in, bf, B, c.n_mels, T, 0, nullptr, nullptr, h->d_pstats, st);
          }))) return rc;
     // prolog: relu(BN(Conv1dSamePadding(n_mels, H, 3)))                          TitaNet.py:226-227, titanet_blocks.py:123-139
-    GemmParams pp = conv_params(h, h->tn_prolog, h->X_in, c.n_mels, PRO, H, M, T);
+    GemmParams pp = conv_params(h, s.prolog, h->X_in, c.n_mels, PRO, H, M, T);
     pp.act1 = ACT_RELU; pp.pad_mode = PAD_ZERO;
-    if ((rc = conv_gemm(h, h->tn_prolog, pp))) return rc;
-    const int nb = (int)h->tn.size();
+    if ((rc = conv_gemm(h, s.prolog, pp))) return rc;
+    const int nb = (int)s.blocks.size();
     const void* x = PRO;
     for (int i = 0; i < nb; ++i) {
-        const svhip_handle::TnBlock& Bk = h->tn[i];
+        const TnBlock& Bk = s.blocks[i];
         if ((rc = conv_gemm(h, Bk.skip, conv_params(h, Bk.skip, x, H, K, H, M, T)))) return rc;
         if (i == 0 && (rc = run(h, "tn_dw", 2.0 * k * H * M, [&]() { return launch_tn_dw(x, D0, Bk.dw_w[0], Bk.dw_b[0], dt, k, B, T, H, st); })))
             return rc;
@@ -218,52 +256,53 @@ static int titanet_forward_part(svhip_handle* h, const float* d_feat, int b0, in
         }
         // squeeze-excitation (titanet_blocks.py:162-192): the squeeze from the GEMM's column sums when its kernel wrote them
         const bool from_part = g3.colsum_groups != 0;
-        if (!from_part && (rc = run(h, "tn_se_mean", 0, [&]() { return launch_colmean(S, dt, H, B, T, H, h->tn_mean, st); }))) return rc;
+        if (!from_part && (rc = run(h, "tn_se_mean", 0, [&]() { return launch_colmean(S, dt, H, B, T, H, s.mean, st); }))) return rc;
         if ((rc = run(h, "tn_se_mlp", 4.0 * B * (H / 16) * H, [&]() {
-                 return launch_se_mlp(from_part ? nullptr : h->tn_mean, from_part ? cs : nullptr, T, bf ? Bk.se1_bf : (const void*)Bk.se1, h->d_zeros,
-                                      bf ? Bk.se2T_bf : (const void*)Bk.se2T, h->d_zeros, h->tn_gate, bf, B, H, H / 16, st, from_part ? g3.colsum_groups : 8);
+                 return launch_se_mlp(from_part ? nullptr : s.mean, from_part ? cs : nullptr, T, bf ? Bk.se1_bf : (const void*)Bk.se1, h->d_zeros,
+                                      bf ? Bk.se2T_bf : (const void*)Bk.se2T, h->d_zeros, s.gate, bf, B, H, H / 16, st, from_part ? g3.colsum_groups : 8);
              }))) return rc;
         // relu(skip + SE(sub_blocks(x))) and the next block's first depthwise conv                     TitaNet.py:306-318
-        const svhip_handle::TnBlock* nx = i + 1 < nb ? &h->tn[i + 1] : nullptr;
+        const TnBlock* nx = i + 1 < nb ? &s.blocks[i + 1] : nullptr;
         if ((rc = run(h, "tn_mega_tail", nx ? 2.0 * k * H * M : 0.0, [&]() {
-                 return launch_tn_mega_tail(K, S, h->tn_gate, X, nx ? nx->dw_w[0] : nullptr, nx ? nx->dw_b[0] : nullptr, nx ? D : nullptr, dt, k, B, T, H, st);
+                 return launch_tn_mega_tail(K, S, s.gate, X, nx ? nx->dw_w[0] : nullptr, nx ? nx->dw_b[0] : nullptr, nx ? D : nullptr, dt, k, B, T, H, st);
              }))) return rc;
         x = X;
     }
     // epilog: relu(BN(conv1x1(x)))                                                   TitaNet.py:244-245
-    GemmParams pe = conv_params(h, h->tn_epilog, x, H, h->tn_enc, E, M, T);
+    GemmParams pe = conv_params(h, s.epilog, x, H, s.enc, E, M, T);
     pe.act1 = ACT_RELU;
-    if ((rc = conv_gemm(h, h->tn_epilog, pe))) return rc;
+    if ((rc = conv_gemm(h, s.epilog, pe))) return rc;
     // attentive statistics pooling (TitaNet.py:389-431): energies = out_linear(tanh(in_linear(x))), softmax over T, mean and
     // sqrt(clamp(var, 1e-6)) (the variance in the centred form), then decoder.pool.1
-    GemmParams pa = conv_params(h, h->tn_att_in, h->tn_enc, E, h->tn_att, 128, M, T);
+    GemmParams pa = conv_params(h, s.att_in, s.enc, E, s.att, 128, M, T);
     pa.act2 = ACT_TANH;
-    if ((rc = conv_gemm(h, h->tn_att_in, pa))) return rc;
-    GemmParams pl = conv_params(h, h->tn_att_out, h->tn_att, 128, h->tn_logits, E, M, T);
+    if ((rc = conv_gemm(h, s.att_in, pa))) return rc;
+    GemmParams pl = conv_params(h, s.att_out, s.att, 128, s.logits, E, M, T);
     pl.out_f32 = 1;
-    if ((rc = conv_gemm(h, h->tn_att_out, pl))) return rc;
+    if ((rc = conv_gemm(h, s.att_out, pl))) return rc;
     if ((rc = run(h, "tn_asp_pool", 0, [&]() {
-             return launch_asp_pool(h->tn_logits, h->tn_enc, bf, E, B, T, E, h->tn_pbn_scale, h->tn_pbn_shift, h->tn_pool_raw, h->tn_pool, 1e-6f, 0.0f, st);
+             return launch_asp_pool(s.logits, s.enc, bf, E, B, T, E, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-6f, 0.0f, st);
          }))) return rc;
     // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the ReLU epilogues would have dropped it)
     if ((rc = run(h, "tn_in_check", 0, [&]() {
-             return launch_tn_nonfinite_rows(d_feat, (int64_t)c.n_mels * T, B, h->tn_pool, 2 * E, 2 * E, st);
+             return launch_tn_nonfinite_rows(d_feat, (int64_t)c.n_mels * T, B, s.pool, 2 * E, 2 * E, st);
          }))) return rc;
     // decoder.linear: Linear(3072, nOut) with BatchNorm1d(nOut) folded in                                     TitaNet.py:355-358
-    return run(h, "tn_fc", 2.0 * B * h->tn_fc.N * h->tn_fc.K, [&]() {
-        return launch_rowvec_linear(h->tn_pool, 2 * E, h->tn_fc.W, h->tn_fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * E, ACT_NONE, st);
+    return run(h, "tn_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
+        return launch_rowvec_linear(s.pool, 2 * E, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * E, ACT_NONE, st);
     });
 }
 
 int titanet_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, titanet_forward_part, d_feat, B, 1, B); }
 
 int titanet_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // tn_prolog, tn_dw0, tn_mega_last, tn_enc, tn_pool
+    auto& s = S(h);
     const int H = h->cfg.channels;
-    if (n == "tn_prolog") { v.src = h->tn_buf[0]; v.cols = v.ld = H; }
-    else if (n == "tn_mega_last") { v.src = h->tn_buf[1]; v.cols = v.ld = H; }
-    else if (n == "tn_dw0") { v.src = h->tn_buf[2]; v.cols = v.ld = H; }
-    else if (n == "tn_enc") { v.src = h->tn_enc; v.cols = v.ld = 1536; }
-    else if (n == "tn_pool") { v.src = h->tn_pool; v.rows = h->lastB; v.cols = v.ld = 3072; v.f32 = true; }
+    if (n == "tn_prolog") { v.src = s.buf[0]; v.cols = v.ld = H; }
+    else if (n == "tn_mega_last") { v.src = s.buf[1]; v.cols = v.ld = H; }
+    else if (n == "tn_dw0") { v.src = s.buf[2]; v.cols = v.ld = H; }
+    else if (n == "tn_enc") { v.src = s.enc; v.cols = v.ld = 1536; }
+    else if (n == "tn_pool") { v.src = s.pool; v.rows = h->lastB; v.cols = v.ld = 3072; v.f32 = true; }
     else return unknown_stage(h, n);
     return SVHIP_OK;
 }
