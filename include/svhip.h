@@ -205,6 +205,28 @@ int svhip_embed_features_ragged(svhip_handle* h, const float* feat, const int64_
  * svhip_last_error(NULL). */
 int svhip_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave);
 
+/* Ragged RawNet3 packs (added under ABI v5): the same call for SVHIP_MODEL_RAWNET3, the raw-waveform branch of Raw3_ECAPA.  The two
+ * calls above are specified in mel frames and stay ECAPA's; they refuse a RawNet3 handle with SVHIP_ERR_UNSUPPORTED.
+ *   utterance i is wav[offsets[i] .. offsets[i] + lengths[i]) and has T0_i = (lengths[i] - 251) / 10 + 1 frames after the sinc
+ *   filterbank, T0_i / 5 after layer1's pool and T0_i / 5 / 3 after layer2's; the pack is laid out back to back at each of the three
+ *   levels (an utterance's T % 5 / T % 3 left-over frames are dropped per utterance, as its own forward would drop them).
+ * wav / offsets / lengths / emb_out / flags: the rules of svhip_embed_wave_ragged.
+ * CAPACITY, checked on the host before anything is enqueued (svhip_rawnet3_ragged_check is the same test without a handle):
+ *   1 <= n <= max_batch;  every lengths[i] >= 541;  offsets >= 0;  sum_i T0_i <= max_batch * T0, the level-0 rows of the workspace the
+ *   handle owns (T0 = (samples - 251) / 10 + 1).  That one rule bounds the other levels: the level-2 buffers hold
+ *   floor(max_batch * T0 / 15) + 1 rows (the sum of T0_i / 5 / 3 can pass max_batch * (T0 / 5 / 3) by a few rows).
+ * Anything else is SVHIP_ERR_INVALID with a message that names the utterance and the limit.  Compute SVHIP_F32 or SVHIP_BF16 only:
+ * every other model and compute type return SVHIP_ERR_UNSUPPORTED.  The first ragged call of a handle allocates the segment tables
+ * and a waveform staging buffer (once; nothing is allocated per call).
+ * BATCH INVARIANCE as above: bit-for-bit the same embedding and stages whatever the pack; to the precision of the compute type against
+ * a fixed-length call.  A non-finite waveform gives NaN for its own utterance only, and SVHIP_ERR_NONFINITE.
+ * STAGES after a ragged call: rn3_front (sum T0_i, 256), rn3_layer1 (sum T0_i / 5, 1024), rn3_layer2 / rn3_layer3 (sum T0_i / 5 / 3, 1024),
+ * rn3_layer4 (sum T0_i / 5 / 3, 1536), rows packed in utterance order; rn3_pooled (n, 3072). */
+int svhip_rawnet3_embed_ragged(svhip_handle* h, const float* wav, const int64_t* offsets, const int32_t* lengths,
+                               int32_t n, float* emb_out, int32_t flags);
+/* lengths[i] are samples.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is svhip_last_error(NULL). */
+int svhip_rawnet3_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n);
+
 /* Eval-mode cropping on device.  Replaces, for decoded 16-bit PCM, the cropping half of loadWAV
  * (src/processing/audio_loader.py:110-150): wrap-pad files not longer than L to L+1 samples, take num_eval
  * crops of L samples at int(linspace(0, len - L, num_eval)), scale by 1/32768 (soundfile float32).  pcm holds

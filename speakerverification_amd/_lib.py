@@ -72,6 +72,8 @@ _SIGNATURES = {
     "svhip_embed_wave_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32]),
     "svhip_embed_features_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32]),
     "svhip_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),
+    "svhip_rawnet3_embed_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32]),
+    "svhip_rawnet3_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32]),
     "svhip_crop_pcm16": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     "svhip_l2norm": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32]),
     "svhip_score_pairs": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32]),

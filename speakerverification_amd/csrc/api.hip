@@ -295,7 +295,7 @@ int svhip_destroy(svhip_handle* h) {
     if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
     for (hipEvent_t e : h->aux_ev) if (e) (void)hipEventDestroy(e);
     for (void* q : h->scr) if (q) (void)hipFree(q);
-    h->model.reset();          // (ECAPA's releases the pinned slots and events of its ragged calls)
+    h->model.reset();          // (ECAPA's and RawNet3's release the pinned slots and events of their ragged calls)
     for (auto& sl : h->crop_slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.dev) (void)hipFree(sl.dev);
@@ -480,6 +480,33 @@ int svhip_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t 
     if (!lengths) { g_create_error = "null pointer"; return SVHIP_ERR_INVALID; }
     std::string msg;
     const int rc = ecapa_ragged_check(*cfg, lengths, n, is_wave != 0, msg);
+    if (rc) g_create_error = msg;
+    return rc;
+}
+
+int svhip_rawnet3_embed_ragged(svhip_handle* h, const float* wav, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
+                               int32_t flags) {
+    if (!h) return SVHIP_ERR_INVALID;
+    if (!h->finalized) SV_FAIL(h, SVHIP_ERR_STATE, "weights not finalized (call svhip_finalize_weights first)");
+    if (!wav || !offsets || !lengths || !emb_out) SV_FAIL(h, SVHIP_ERR_INVALID, "null pointer");
+    std::string msg;
+    if (int rc = rawnet3_ragged_check(h->cfg, lengths, n, msg)) SV_FAIL(h, rc, "%s", msg.c_str());
+    for (int i = 0; i < n; ++i)
+        if (offsets[i] < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance %d: negative offset (the limit is 0)", i);
+    if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
+        SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    int rc = rawnet3_embed_ragged(h, wav, !(flags & SVHIP_IN_DEVICE), offsets, lengths, n);
+    if (rc) return rc;
+    if ((rc = emit_embeddings(h, n, emb_out, flags))) return rc;
+    return finish(h, flags);
+}
+
+int svhip_rawnet3_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n) {
+    if (!cfg || cfg->struct_size != (int32_t)sizeof(svhip_config)) { g_create_error = "bad config / struct_size"; return SVHIP_ERR_INVALID; }
+    if (!lengths) { g_create_error = "null pointer"; return SVHIP_ERR_INVALID; }
+    std::string msg;
+    const int rc = rawnet3_ragged_check(*cfg, lengths, n, msg);
     if (rc) g_create_error = msg;
     return rc;
 }

@@ -435,7 +435,7 @@ int ecapa_embed_wave(svhip_handle* h, const float* d_wav, int B) {
 // The scope and capacity rules of svhip_embed_wave_ragged / svhip_embed_features_ragged (include/svhip.h), on the host alone.
 int ecapa_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
     char b[256];
-    if (c.model != SVHIP_MODEL_ECAPA) { err = "ragged batches: SVHIP_MODEL_ECAPA only (the other models embed one length per handle)"; return SVHIP_ERR_UNSUPPORTED; }
+    if (c.model != SVHIP_MODEL_ECAPA) { err = "ragged batches: SVHIP_MODEL_ECAPA only (RawNet3 packs go through svhip_rawnet3_embed_ragged; the other models embed one length per handle)"; return SVHIP_ERR_UNSUPPORTED; }
     if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "ragged batches: compute SVHIP_F32 or SVHIP_BF16 only"; return SVHIP_ERR_UNSUPPORTED; }
     if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft) { err = "bad hop_length / max_batch / samples"; return SVHIP_ERR_INVALID; }
     if (n < 1 || n > c.max_batch) {

@@ -9,6 +9,14 @@
 //               mp3(x1) + x2 -> P1 (layer3's input and its identity residual)
 //   layer3      conv1(P1) and conv3 -> the head of P2, steps -> the next (B T2, 1024) of P2, AFMS -> x3 in CAT[2] (x1 stays in P0)
 //   layer4      relu(W4 CAT + b4) -> P1; context pooling (attention activation in P2) -> pooled; fc6 -> embeddings
+//
+// A ragged pack (svhip_rawnet3_embed_ragged) runs the same plan over n utterances of different lengths packed back to back: level 0
+// holds the sum of T0_u rows, level 1 the sum of T0_u / 5, level 2 the sum of T0_u / 5 / 3, each with its segment table (Seg).  The
+// buffers are the fixed-length ones: a pack holds at most max_batch * T0 level-0 rows, hence at most a fifth of that at level 1 and
+// floor(max_batch * T0 / 15) at level 2, which is what CAT and the logits are sized for (the sum of T0_u / 15 can pass max_batch * T2
+// by a few rows).  Every GEMM goes to launch_gemm_ragged and every small linear to launch_rag_linear — one kernel at every row count —
+// and the reductions over time are the per-utterance kernels of rawnet3.hip / ragged.hip, so an utterance's values do not depend on
+// the pack.
 #include <algorithm>
 #include <cmath>
 
@@ -21,6 +29,8 @@ namespace {
 constexpr int C = 1024, W = 128, D = 1536;
 
 int rn3_frames(int L) { return (L - RN3_TAPS) / RN3_STRIDE + 1; }      // T0 of RawNet3's front-end
+
+struct RagSlot { char* host = nullptr; hipEvent_t done = nullptr; bool busy = false; };
 
 struct Rn3Layer {                         // Bottle2neck(k = 3, scale = 8): every BatchNorm follows a ReLU, so it is its conv's epilogue affine
     ConvLayer conv1, convs[7], conv3, residual;      // conv1 + bn1, convs[i] + bns[i], conv3 + bn3; residual: 1 x 1, no bias (layer1)
@@ -49,46 +59,85 @@ struct RawNet3State : ModelState {
     float *logit = nullptr, *pooled = nullptr;          // (Bmax * T2) per-frame logits; (Bmax, 3072) bn5(pooled)
     const void* stage[5] = {};            // svhip_get_stage: front-end, layer1, layer2, layer3, layer4 outputs of the last forward
     int stage_T[5] = {}, stage_C[5] = {}, stage_ld[5] = {};
+    // ragged packs (allocated by the first ragged call)
+    char* rag_tab = nullptr;              // device tables of the call: sample offsets (Bmax int64), lengths (Bmax int), three row0 (Bmax + 1 each)
+    int* rag_utt[3] = {};                 // utterance of every row, per level
+    float* rag_wav = nullptr;             // host-pointer calls: the utterances back to back, Bmax * (samples + 16) floats
+    RagSlot rag_slot[4];                  // pinned copies of the tables of the calls in flight (SVHIP_ASYNC returns before the copy has run)
+    int rag_next = 0;
+    int64_t rag_rows[3] = {};             // rows per level of the last forward when it was a ragged one (svhip_get_stage), else 0
+
+    ~RawNet3State() override {
+        for (auto& sl : rag_slot) {
+            if (sl.host) (void)hipHostFree(sl.host);
+            if (sl.done) (void)hipEventDestroy(sl.done);
+        }
+    }
 };
+
+// one frame level of a ragged pack: utterance u owns the rows [row0[u], row0[u + 1]), utt[m] is the utterance of row m, M rows in all
+struct Seg { const int* row0 = nullptr; const int* utt = nullptr; int M = 0; };
+
+size_t rag_tab_bytes(size_t B) { return B * 8 + B * 4 + 3 * (B + 1) * 4; }
 
 RawNet3State& S(svhip_handle* h) { return static_cast<RawNet3State&>(*h->model); }
 
 // One Bottle2neck on x (B T, cin) at row stride ldx, T frames in; its output y = AFMS(pool(.)) goes to (ydst, ldy), and with `add` the
 // same pass writes y + add to `sum`.  res: the identity residual (null: the layer's 1 x 1 residual conv of x into `rbuf`).
 // h1, h2, o: scratch (B T, 1024) buffers (o may be h1); pooled: (B T / P, 1024) scratch when P > 1.
+// in / out (ragged packs; B = n, T unused): the segment tables of the input rows and of the rows after the pool (out == in when P == 1).
 int bottle2neck(svhip_handle* h, const Rn3Layer& Ly, const void* x, int ldx, int cin, int B, int T, int P, const void* res, void* rbuf,
-                void* h1, void* h2, void* o, void* pooled, void* ydst, int ldy, const void* add, int ldadd, void* sum, int ldsum) {
+                void* h1, void* h2, void* o, void* pooled, void* ydst, int ldy, const void* add, int ldadd, void* sum, int ldsum,
+                const Seg* in = nullptr, const Seg* out = nullptr) {
     auto& s = S(h);
-    const int M = B * T, e = h->esz, dt = h->dt;
+    const int M = in ? in->M : B * T, e = h->esz, dt = h->dt;
     hipStream_t st = h->cur;
     int rc;
+    auto gemm = [&](const ConvLayer& K, GemmParams p) {
+        if (!in) return conv_gemm(h, K, p);
+        p.rag_utt = in->utt; p.rag_row0 = in->row0;
+        return run(h, K.taps > 1 ? (p.A2 ? "rag_gemm_conv_add" : "rag_gemm_conv") : "rag_gemm", (double)M * K.flops_per_row,
+                   [&]() { return launch_gemm_ragged(p, h->bf16, st); });
+    };
     if (!res) {                                                                      // residual = Conv1d(cin, C, 1, bias=False)(x)
-        if ((rc = conv_gemm(h, Ly.residual, conv_params(h, Ly.residual, x, ldx, rbuf, C, M, T)))) return rc;
+        if ((rc = gemm(Ly.residual, conv_params(h, Ly.residual, x, ldx, rbuf, C, M, T)))) return rc;
         res = rbuf;
     }
     GemmParams p1 = conv_params(h, Ly.conv1, x, ldx, h1, C, M, T);                   // bn1(relu(conv1(x)))
     p1.act1 = ACT_RELU;
-    if ((rc = conv_gemm(h, Ly.conv1, p1))) return rc;
+    if ((rc = gemm(Ly.conv1, p1))) return rc;
     for (int i = 0; i < 7; ++i) {                                                    // sp = bns[i](relu(convs[i](sp + spx[i])))
         const ConvLayer& K = Ly.convs[i];
         const void* a = i == 0 ? h1 : off(h2, (size_t)(i - 1) * W, e);
         GemmParams q = conv_params(h, K, a, C, off(h2, (size_t)i * W, e), C, M, T);
         q.act1 = ACT_RELU; q.pad_mode = PAD_ZERO;
         if (i > 0) { q.A2 = off(h1, (size_t)i * W, e); q.lda2 = C; }
-        if ((rc = conv_gemm(h, K, q))) return rc;
+        if ((rc = gemm(K, q))) return rc;
     }
     if ((rc = run(h, "rn3_copy_chunk", 0, [&]() { return launch_copy_cols(off(h1, (size_t)7 * W, e), C, off(h2, (size_t)7 * W, e), C, h->bf16, M, W, st); })))
         return rc;                                                                   // the eighth chunk passes unchanged
     GemmParams p3 = conv_params(h, Ly.conv3, h2, C, o, C, M, T);                     // bn3(relu(conv3(.))) + residual
     p3.act1 = ACT_RELU; p3.R = res; p3.ldr = C;
-    if ((rc = conv_gemm(h, Ly.conv3, p3))) return rc;
+    if ((rc = gemm(Ly.conv3, p3))) return rc;
     const void* z = o;
     const int Tn = T / P;
     if (P > 1) {
-        if ((rc = run(h, "rn3_maxpool", 0, [&]() { return launch_rn3_maxpool(o, C, pooled, C, dt, B, T, C, P, st); }))) return rc;
+        if ((rc = run(h, "rn3_maxpool", 0, [&]() {
+                 return in ? launch_rn3_rag_maxpool(o, C, pooled, C, dt, in->row0, out->row0, out->utt, out->M, C, P, st)
+                           : launch_rn3_maxpool(o, C, pooled, C, dt, B, T, C, P, st);
+             }))) return rc;
         z = pooled;
     }
     // AFMS: (z + alpha) * sigmoid(fc(mean_t z))                                        RawNet_baseline.py:58-65
+    if (in) {
+        if ((rc = run(h, "rn3_afms_mean", 0, [&]() { return launch_rag_colstats(z, h->bf16, C, out->row0, B, C, s.mean, false, 0.0f, st); }))) return rc;
+        if ((rc = run(h, "rn3_afms_gate", 2.0 * B * C * C, [&]() {
+                 return launch_rag_linear(s.mean, C, Ly.afms_fc.W, Ly.afms_fc.bias, s.gate, C, B, C, C, ACT_SIGMOID, st);
+             }))) return rc;
+        return run(h, "rn3_afms", 0, [&]() {
+            return launch_rn3_rag_afms(z, C, Ly.alpha, s.gate, ydst, ldy, add, ldadd, sum, ldsum, dt, out->utt, out->M, C, st);
+        });
+    }
     if ((rc = run(h, "rn3_afms_mean", 0, [&]() { return launch_colmean(z, dt, C, B, Tn, C, s.mean, st); }))) return rc;
     if ((rc = run(h, "rn3_afms_gate", 2.0 * B * C * C, [&]() {
              return launch_rowvec_linear(s.mean, C, Ly.afms_fc.W, Ly.afms_fc.bias, s.gate, C, B, C, C, ACT_SIGMOID, st);
@@ -228,15 +277,17 @@ int rawnet3_alloc(svhip_handle* h) {
     s.T0 = rn3_frames(c.samples);
     const size_t M0 = B * (size_t)s.T0, T2 = (size_t)(s.T0 / 5 / 3);
     if (T2 < 2) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance too short for RawNet3 (%d samples)", c.samples);
+    // level-2 rows: B * T2 of a fixed-length batch; a ragged pack that fills the M0 level-0 rows can hold up to M0 / 15
+    const size_t M2 = M0 / 15 + 1;
     for (int i = 0; i < 3; ++i) if ((rc = actbuf(h, &s.buf[i], M0 * C))) return rc;
-    if ((rc = actbuf(h, &s.cat, B * T2 * 3 * C))) return rc;
+    if ((rc = actbuf(h, &s.cat, M2 * 3 * C))) return rc;
     if ((rc = actbuf(h, &s.x0, M0 * RN3_FILTERS))) return rc;
     if ((rc = dev_alloc(h, &s.stats, B * 2))) return rc;
     if ((rc = dev_alloc(h, &s.mean, B * 1024))) return rc;
     if ((rc = dev_alloc(h, &s.gate, B * 1024))) return rc;
     if ((rc = dev_alloc(h, &s.tstat, B * 3072))) return rc;
     if ((rc = dev_alloc(h, &s.ctx, B * 128))) return rc;
-    if ((rc = dev_alloc(h, &s.logit, B * T2))) return rc;
+    if ((rc = dev_alloc(h, &s.logit, M2))) return rc;
     if ((rc = dev_alloc(h, &s.pooled, B * 3072))) return rc;
     return SVHIP_OK;
 }
@@ -248,7 +299,11 @@ int rawnet3_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {  
     while (i < 5 && n != kStages[i]) ++i;
     if (n == "rn3_pooled") { v.src = s.pooled; v.rows = h->lastB; v.cols = v.ld = 3072; v.f32 = true; }
     else if (i == 5) return unknown_stage(h, n);
-    else { v.src = s.stage[i]; v.rows = (size_t)h->lastB * s.stage_T[i]; v.cols = s.stage_C[i]; v.ld = s.stage_ld[i]; }
+    else {
+        static const int kLevel[5] = {0, 1, 2, 2, 2};       // after a ragged forward: the packed rows of the stage's level, in utterance order
+        v.src = s.stage[i]; v.cols = s.stage_C[i]; v.ld = s.stage_ld[i];
+        v.rows = h->rag_rows ? (size_t)s.rag_rows[kLevel[i]] : (size_t)h->lastB * s.stage_T[i];
+    }
     return SVHIP_OK;
 }
 
@@ -316,5 +371,171 @@ static int rawnet3_forward_part(svhip_handle* h, const float* d_wav, int b0, int
 }
 
 int rawnet3_forward(svhip_handle* h, const float* d_wav, int B) { return forward_lanes(h, rawnet3_forward_part, d_wav, B, 1, B); }
+
+// ---- ragged packs ------------------------------------------------------------------------------------------
+// The scope and capacity rules of svhip_rawnet3_embed_ragged (include/svhip.h), on the host alone.
+int rawnet3_ragged_check(const svhip_config& c, const int32_t* lengths, int n, std::string& err) {
+    char b[256];
+    if (c.model != SVHIP_MODEL_RAWNET3) { err = "svhip_rawnet3_embed_ragged: SVHIP_MODEL_RAWNET3 only (ECAPA packs go through svhip_embed_wave_ragged)"; return SVHIP_ERR_UNSUPPORTED; }
+    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "ragged RawNet3 packs: compute SVHIP_F32 or SVHIP_BF16 only"; return SVHIP_ERR_UNSUPPORTED; }
+    if (c.max_batch <= 0 || c.samples < RN3_MIN_SAMPLES) { err = "bad max_batch / samples"; return SVHIP_ERR_INVALID; }
+    if (n < 1 || n > c.max_batch) {
+        snprintf(b, sizeof(b), "ragged pack of %d utterances outside [1, max_batch=%d]", n, c.max_batch);
+        err = b; return SVHIP_ERR_INVALID;
+    }
+    const int64_t cap = (int64_t)c.max_batch * rn3_frames(c.samples);
+    int64_t rows = 0;
+    for (int i = 0; i < n; ++i) {
+        if (lengths[i] < RN3_MIN_SAMPLES) {
+            snprintf(b, sizeof(b), "utterance %d: %d samples, fewer than RawNet3's minimum of %d", i, lengths[i], RN3_MIN_SAMPLES);
+            err = b; return SVHIP_ERR_INVALID;
+        }
+        rows += rn3_frames(lengths[i]);
+        if (rows > cap) {
+            snprintf(b, sizeof(b), "utterance %d: the pack reaches %lld frames, over the handle's capacity of max_batch * T0 = %lld rows", i,
+                     (long long)rows, (long long)cap);
+            err = b; return SVHIP_ERR_INVALID;
+        }
+    }
+    return SVHIP_OK;
+}
+
+// the device tables, the waveform staging buffer and the pinned table slots: once per handle
+static int rawnet3_ragged_alloc(svhip_handle* h) {
+    auto& s = S(h);
+    if (s.rag_tab) return SVHIP_OK;
+    const svhip_config& c = h->cfg;
+    const size_t B = c.max_batch, M0 = B * (size_t)s.T0;
+    int rc;
+    int* utt = nullptr;
+    if ((rc = dev_alloc(h, &utt, M0 + (M0 / 5 + 1) + (M0 / 15 + 1)))) return rc;
+    s.rag_utt[0] = utt; s.rag_utt[1] = utt + M0; s.rag_utt[2] = utt + M0 + M0 / 5 + 1;
+    // (a pack of n <= B utterances within M0 frames holds at most 10 M0 + 250 n <= B (samples + 9) samples)
+    if ((rc = dev_alloc(h, &s.rag_wav, B * ((size_t)c.samples + 16)))) return rc;
+    for (auto& sl : s.rag_slot) {
+        SV_HIP(h, hipHostMalloc((void**)&sl.host, rag_tab_bytes(B), hipHostMallocDefault));
+        SV_HIP(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    }
+    return dev_alloc(h, &s.rag_tab, rag_tab_bytes(B));
+}
+
+// RawNet3.forward over a ragged pack (utterance u: len[u] samples at d_wav + off[u]; the tables are on the device), on the handle's
+// stream: rawnet3_forward_part's plan with the segment-table form of every step
+static int rawnet3_forward_ragged(svhip_handle* h, const float* d_wav, int n, const Seg lv[3], const int maxT[3]) {
+    auto& s = S(h);
+    const svhip_config& c = h->cfg;
+    const int e = h->esz, dt = h->dt;
+    const bool bf = h->bf16;
+    hipStream_t st = h->cur = h->stream;
+    const size_t B = c.max_batch;
+    const int64_t* d_off = reinterpret_cast<const int64_t*>(s.rag_tab);
+    const int* d_len = reinterpret_cast<const int*>(s.rag_tab + B * 8);
+    void *P0 = s.buf[0], *P1 = s.buf[1], *P2 = s.buf[2], *CAT = s.cat;
+    int rc;
+    auto stage = [&](int i, const void* src, int Cn, int ld) { s.stage[i] = src; s.stage_T[i] = 0; s.stage_C[i] = Cn; s.stage_ld[i] = ld; };
+    auto gemm = [&](const ConvLayer& L, GemmParams p, const Seg& g, const char* label) {
+        p.rag_utt = g.utt; p.rag_row0 = g.row0;
+        return run(h, label, (double)g.M * L.flops_per_row, [&]() { return launch_gemm_ragged(p, bf, st); });
+    };
+    for (int l = 0; l < 3; ++l)
+        if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(lv[l].row0, n, maxT[l], s.rag_utt[l], st); }))) return rc;
+
+    // front-end
+    float* y = static_cast<float*>(P1);
+    void* x0 = s.x0;
+    if ((rc = run(h, "rn3_sinc", 2.0 * RN3_FILTERS * RN3_TAPS * (double)lv[0].M, [&]() {
+             return launch_rn3_rag_front(d_wav, d_off, d_len, lv[0].row0, n, maxT[0], s.pre[0], s.pre[1], s.in_w, s.in_b, s.filt, !bf, s.stats, y, st);
+         }))) return rc;
+    if ((rc = run(h, "rn3_front_mean", 0, [&]() { return launch_rag_colstats(y, false, RN3_FILTERS, lv[0].row0, n, RN3_FILTERS, s.mean, false, 0.0f, st); }))) return rc;
+    if ((rc = run(h, "rn3_center", 0, [&]() { return launch_rn3_rag_center(y, s.mean, x0, dt, lv[0].utt, lv[0].M, st); }))) return rc;
+    stage(0, x0, RN3_FILTERS, RN3_FILTERS);
+
+    // layer1: x1 -> P0 (level 1)
+    if ((rc = bottle2neck(h, s.layers[0], x0, RN3_FILTERS, RN3_FILTERS, n, 1, 5, nullptr, P0, P1, P2, P1, P2, P0, C, nullptr, 0, nullptr, 0, &lv[0], &lv[1])))
+        return rc;
+    stage(1, P0, C, C);
+    // mp3(x1) -> CAT[:, 0:1024)
+    if ((rc = run(h, "rn3_maxpool", 0, [&]() { return launch_rn3_rag_maxpool(P0, C, CAT, 3 * C, dt, lv[1].row0, lv[2].row0, lv[2].utt, lv[2].M, C, 3, st); })))
+        return rc;
+    // layer2: x2 -> CAT[:, 1024:2048), mp3(x1) + x2 -> P1 (level 2)
+    if ((rc = bottle2neck(h, s.layers[1], P0, C, C, n, 1, 3, P0, nullptr, P1, P2, P1, P2, off(CAT, C, e), 3 * C, CAT, 3 * C, P1, C, &lv[1], &lv[2])))
+        return rc;
+    stage(2, off(CAT, C, e), C, 3 * C);
+    // layer3 on mp3(x1) + x2: x3 -> CAT[:, 2048:3072)
+    void* h1 = P2;
+    void* h2 = off(P2, (size_t)lv[2].M * C, e);
+    if ((rc = bottle2neck(h, s.layers[2], P1, C, C, n, 1, 1, P1, nullptr, h1, h2, h1, nullptr, off(CAT, 2 * C, e), 3 * C, nullptr, 0, nullptr, 0, &lv[2], &lv[2])))
+        return rc;
+    stage(3, off(CAT, 2 * C, e), C, 3 * C);
+
+    // layer4
+    const int M2 = lv[2].M;
+    GemmParams p4 = conv_params(h, s.l4, CAT, 3 * C, P1, D, M2, 1);
+    p4.act1 = ACT_RELU;
+    if ((rc = gemm(s.l4, p4, lv[2], "rag_gemm"))) return rc;
+    stage(4, P1, D, D);
+
+    // context attentive statistics pooling, per utterance from the level-2 table
+    if ((rc = run(h, "rn3_tstats", 0, [&]() { return launch_rn3_tstats(P1, D, dt, n, 1, D, s.tstat, st, lv[2].row0); }))) return rc;
+    if ((rc = run(h, "rn3_att_ctx", 2.0 * n * 128 * 2 * D, [&]() {
+             return launch_rag_linear(s.tstat, 2 * D, s.att_ctx.W, s.att_ctx.bias, s.ctx, 128, n, 128, 2 * D, ACT_NONE, st);
+         }))) return rc;
+    GemmParams pa = conv_params(h, s.att, P1, D, P2, 128, M2, 1);
+    pa.act1 = ACT_RELU; pa.bias_utt = s.ctx; pa.ld_bu = 128;
+    if ((rc = gemm(s.att, pa, lv[2], "rag_gemm_ctx"))) return rc;
+    if ((rc = run(h, "rn3_pool", 0, [&]() {
+             return launch_rn3_ctx_pool(P2, 128, s.w2, s.b2, s.logit, P1, D, dt, n, 1, D, s.bn5_scale, s.bn5_shift, s.stats, s.pooled, st, lv[2].row0, M2);
+         }))) return rc;
+    return run(h, "rn3_fc6", 2.0 * n * s.fc6.N * s.fc6.K, [&]() {
+        return launch_rag_linear(s.pooled, 2 * D, s.fc6.W, s.fc6.bias, h->d_emb, c.embed_dim, n, c.embed_dim, 2 * D, ACT_NONE, st);
+    });
+}
+
+// the caller (svhip_rawnet3_embed_ragged) has run rawnet3_ragged_check
+int rawnet3_embed_ragged(svhip_handle* h, const float* in, bool in_host, const int64_t* in_off, const int32_t* lengths, int n) {
+    auto& s = S(h);
+    int rc = rawnet3_ragged_alloc(h);
+    if (rc) return rc;
+    // the tables of this call, in a pinned slot of the handle: the caller's arrays are free on return
+    RagSlot& slot = s.rag_slot[s.rag_next];
+    s.rag_next = (s.rag_next + 1) & 3;
+    if (slot.busy) { SV_HIP(h, hipEventSynchronize(slot.done)); slot.busy = false; }
+    const size_t B = h->cfg.max_batch;
+    int64_t* t_off = reinterpret_cast<int64_t*>(slot.host);
+    int* t_len = reinterpret_cast<int*>(slot.host + B * 8);
+    int* t_row0[3];
+    for (int l = 0; l < 3; ++l) t_row0[l] = t_len + B + l * (B + 1);
+    int M[3] = {0, 0, 0}, maxT[3] = {0, 0, 0};
+    int64_t pos = 0;
+    h->cur = h->stream;
+    for (int u = 0; u < n; ++u) {
+        const int T0 = rn3_frames(lengths[u]);
+        const int T[3] = {T0, T0 / 5, T0 / 5 / 3};
+        for (int l = 0; l < 3; ++l) {
+            t_row0[l][u] = M[l];
+            M[l] += T[l];
+            maxT[l] = std::max(maxT[l], T[l]);
+        }
+        t_len[u] = lengths[u];
+        t_off[u] = in_off[u];
+        if (in_host) {
+            SV_HIP(h, hipMemcpyAsync(s.rag_wav + pos, in + in_off[u], (size_t)lengths[u] * 4, hipMemcpyHostToDevice, h->stream));
+            t_off[u] = pos;
+            pos += lengths[u];
+        }
+    }
+    for (int l = 0; l < 3; ++l) t_row0[l][n] = M[l];
+    SV_HIP(h, hipMemcpyAsync(s.rag_tab, slot.host, rag_tab_bytes(B), hipMemcpyHostToDevice, h->stream));
+    SV_HIP(h, hipEventRecord(slot.done, h->stream));
+    slot.busy = true;
+    Seg lv[3];
+    const int* d_row0 = reinterpret_cast<const int*>(s.rag_tab + B * 12);
+    for (int l = 0; l < 3; ++l) { lv[l].row0 = d_row0 + l * (B + 1); lv[l].utt = s.rag_utt[l]; lv[l].M = M[l]; }
+    if ((rc = rawnet3_forward_ragged(h, in_host ? s.rag_wav : in, n, lv, maxT))) return rc;
+    h->lastB = n;
+    h->rag_rows = M[0];
+    for (int l = 0; l < 3; ++l) s.rag_rows[l] = M[l];
+    return SVHIP_OK;
+}
 
 }  // namespace svhip

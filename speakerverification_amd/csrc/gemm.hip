@@ -392,8 +392,9 @@ hipError_t launch_t(const GemmParams& p, hipStream_t stream) {
     return hipErrorInvalidValue;
 }
 
-// the ragged forms ECAPA's forward needs: the k = 5 first convolution (GELU), the Res2Net steps (ReLU, with and without the running
-// sum A2) and asp.tdnn (pointwise, ReLU -> BN -> tanh, bias per utterance)
+// the ragged forms ECAPA's and RawNet3's forwards need: the k = 5 first convolution (GELU), the Res2Net steps (ReLU, with and without the
+// running sum A2; reflect or zero padding: pad_mode is a runtime field) and the attention layer with its bias per utterance (pointwise;
+// ECAPA's asp.tdnn: ReLU -> BN -> tanh, RawNet3's attention.0 -> attention.2: ReLU -> BN)
 template <typename T>
 hipError_t launch_rag_t(const GemmParams& p, hipStream_t stream) {
     if (p.taps > 1) {
@@ -404,6 +405,7 @@ hipError_t launch_rag_t(const GemmParams& p, hipStream_t stream) {
         return hipErrorInvalidValue;
     }
     if (p.bias_utt && p.act1 == ACT_RELU && p.act2 == ACT_TANH && !p.A2) return launch_inst_x<T, false, false, EPI_RELU_TANH, false, false, true>(p, stream);
+    if (p.bias_utt && p.act1 == ACT_RELU && p.act2 == ACT_NONE && !p.A2) return launch_inst_x<T, false, false, EPI_RELU, false, false, true>(p, stream);
     return hipErrorInvalidValue;
 }
 

@@ -313,6 +313,9 @@ EmbedFn ecapa_embed_wave, rawnet2_forward, rawnet3_forward;                    /
 // wave; elements of a device feature array, features) or, with in_host, in the host array `in`
 int ecapa_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err);
 int ecapa_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n);
+// a ragged RawNet3 pack: utterance u is lengths[u] samples at in + in_off[u] (a device waveform array, or with in_host a host one)
+int rawnet3_ragged_check(const svhip_config& c, const int32_t* lengths, int n, std::string& err);
+int rawnet3_embed_ragged(svhip_handle* h, const float* in, bool in_host, const int64_t* in_off, const int32_t* lengths, int n);
 EmbedFn ecapa_forward, titanet_forward, conformer_forward, resnetse_forward;   // from the mel power
 StageFn ecapa_stage, rawnet2_stage, rawnet3_stage, titanet_stage, conformer_stage, resnetse_stage;
 

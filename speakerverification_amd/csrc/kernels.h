@@ -434,11 +434,27 @@ hipError_t launch_rn3_maxpool(const void* x, int ldx, void* y, int ldy, int dt, 
 hipError_t launch_rn3_afms(const void* x, int ldx, const float* alpha, const float* gate, void* y, int ldy, const void* add, int ldadd, void* sum, int ldsum,
                            int dt, int B, int Tn, int C, hipStream_t stream);
 // stats (B, 2C) fp32 = [mean_t x | sqrt(clamp(unbiased var_t x, 1e-4, 1e4))]
-hipError_t launch_rn3_tstats(const void* x, int ldx, int dt, int B, int Tn, int C, float* stats, hipStream_t stream);
+hipError_t launch_rn3_tstats(const void* x, int ldx, int dt, int B, int Tn, int C, float* stats, hipStream_t stream, const int* row0 = nullptr);
 // single-head context pooling: logit (B * Tn) = hatt . w2 + b2 (hatt (B * Tn, 128)), softmax over Tn, weighted mean / std of x, bn5 affine
 // -> pooled (B, 2C) fp32; NaN for an utterance whose in_stats (rn3_prenorm's (B, 2) statistics of the waveform) are not finite
 hipError_t launch_rn3_ctx_pool(const void* hatt, int ldh, const float* w2, const float* b2, float* logit, const void* x, int ldx, int dt, int B, int Tn, int C,
-                               const float* bn_scale, const float* bn_shift, const double* in_stats, float* pooled, hipStream_t stream);
+                               const float* bn_scale, const float* bn_shift, const double* in_stats, float* pooled, hipStream_t stream,
+                               const int* row0 = nullptr, int64_t rows = 0);
+// The same kernels over a ragged pack: n utterances packed back to back at each frame level, a level's rows described by its row0
+// (n + 1) / utt (M) tables (ragged.hip).  launch_rn3_tstats / launch_rn3_ctx_pool take the level-2 row0 (B = n; Tn: any positive
+// value, unused; rows: the level's row count); the others have their own entry:
+//   front     utterance u = len[u] samples at wav + off[u] (device tables) -> y rows row0[u] .. (two launches for the whole pack)
+//   center    x0[m] = y[m] - mean[utt[m]]
+//   maxpool   output row m (utterance u = utt_out[m], frame t = m - row0_out[u]) = max of the input rows row0_in[u] + P t .. + P - 1:
+//             an utterance's T_u % P left-over frames are dropped
+//   afms      the gate row is utt[m]
+hipError_t launch_rn3_rag_front(const float* wav, const int64_t* off, const int* len, const int* row0, int n, int maxT0, double f0, double f1,
+                                const float* in_w, const float* in_b, const void* filt, bool filt_f64, double* stats, float* y, hipStream_t stream);
+hipError_t launch_rn3_rag_center(const float* y, const float* mean, void* x0, int dt, const int* utt, int M, hipStream_t stream);
+hipError_t launch_rn3_rag_maxpool(const void* x, int ldx, void* y, int ldy, int dt, const int* row0_in, const int* row0_out, const int* utt_out, int M_out,
+                                  int C, int P, hipStream_t stream);
+hipError_t launch_rn3_rag_afms(const void* x, int ldx, const float* alpha, const float* gate, void* y, int ldy, const void* add, int ldadd, void* sum, int ldsum,
+                               int dt, const int* utt, int M, int C, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // TitaNet (titanet.hip): the depthwise 1-D convolution over frame-major (B T, C) activations, odd k in {3, 7, 11}, zero "same" padding

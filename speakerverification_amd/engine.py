@@ -247,10 +247,14 @@ class Engine:
     # ---- ragged batches: utterances of different lengths in one call (svhip_embed_wave_ragged / svhip_embed_features_ragged) ----
     @property
     def row_capacity(self):
-        """frames one ragged call can hold: the rows of the handle's workspace, max_batch * T"""
-        return self.max_batch * self.frames
+        """frames one ragged call can hold: the rows of the handle's workspace, max_batch * T (RawNet3: max_batch * T0)"""
+        return self.max_batch * self.frames_of(self.samples)
 
     def frames_of(self, n_samples):
+        """frames of an utterance of n_samples in the unit of row_capacity: mel frames, or on a RawNet3 handle the frames after
+        its sinc filterbank (251 taps, stride 10)"""
+        if self.model == "rawnet3":
+            return (int(n_samples) - 251) // 10 + 1
         return int(n_samples) // int(self.cfg.hop_length) + 1
 
     def _pack(self, items, offsets, lengths, is_wave):
@@ -276,21 +280,23 @@ class Engine:
             packed = np.concatenate([np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in items])
         return packed, offs, lens
 
-    def _embed_ragged(self, fn, items, offsets, lengths, out, async_, is_wave):
+    def _embed_ragged(self, fn, items, offsets, lengths, out, async_, is_wave, ordered=False):
         packed, offs, lens = self._pack(items, offsets, lengths, is_wave)
         n = int(lens.shape[0])
         if out is None:
             out = self._out(packed, (n, self.embed_dim))
         i, o = _Buf(packed, np.float32), _Buf(out, np.float32, writable=True)
-        self._order_after_torch(i, o, async_=async_)
+        self._order_after_torch(i, o, async_=async_, ordered=ordered)
         _count([i], [o])
         self._ck(fn(self.h, i.ptr, offs.ctypes.data, lens.ctypes.data, n, o.ptr, self._flags(i, o, async_)))
         return out
 
-    def embed_wave_ragged(self, wavs, offsets=None, lengths=None, out=None, async_=False):
+    def embed_wave_ragged(self, wavs, offsets=None, lengths=None, out=None, async_=False, ordered=False):
         """utterances of different lengths -> (n, embed_dim), each as if forwarded alone at its own length.  ``wavs``: a list of 1-D
-        arrays, or ONE packed array with ``offsets`` / ``lengths`` in samples; numpy or CUDA tensors, like embed_wave."""
-        return self._embed_ragged(self.lib.svhip_embed_wave_ragged, wavs, offsets, lengths, out, async_, True)
+        arrays, or ONE packed array with ``offsets`` / ``lengths`` in samples; numpy or CUDA tensors, like embed_wave.  A RawNet3
+        handle takes the pack through svhip_rawnet3_embed_ragged."""
+        fn = self.lib.svhip_rawnet3_embed_ragged if self.model == "rawnet3" else self.lib.svhip_embed_wave_ragged
+        return self._embed_ragged(fn, wavs, offsets, lengths, out, async_, True, ordered)
 
     def embed_features_ragged(self, feats, offsets=None, lengths=None, out=None, async_=False):
         """``feats``: a list of (n_mels, T_i) mel-power arrays, or one packed array of such blocks with frame ``offsets`` / ``lengths``."""
@@ -299,7 +305,10 @@ class Engine:
     def ragged_check(self, lengths, is_wave=True):
         """the library's own capacity test for a pack (svhip_ragged_check, host only): None, or the refusal's text"""
         lens = np.ascontiguousarray(lengths, dtype=np.int32)
-        rc = self.lib.svhip_ragged_check(C.byref(self.cfg), lens.ctypes.data, int(lens.shape[0]), 1 if is_wave else 0)
+        if self.model == "rawnet3":
+            rc = self.lib.svhip_rawnet3_ragged_check(C.byref(self.cfg), lens.ctypes.data, int(lens.shape[0]))
+        else:
+            rc = self.lib.svhip_ragged_check(C.byref(self.cfg), lens.ctypes.data, int(lens.shape[0]), 1 if is_wave else 0)
         return None if rc == _lib.OK else (self.lib.svhip_last_error(None) or b"?").decode()
 
     def crop_pcm16(self, pcm_list, num_eval, L=32000, out=None, async_=False):

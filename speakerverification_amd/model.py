@@ -193,12 +193,15 @@ class ModelHandling:
         return hasattr(S, "embed_wave") and enc._fusable()
 
     def _ragged_ok(self, num_eval):
-        """whole-file evaluation as ragged batches: the model offers embed_ragged and the front-end is the one its handle bakes in"""
+        """whole-file evaluation as ragged batches: the model offers embed_ragged and the front-end is the one its handle bakes in
+        (a ``features: raw`` model reads the waveform and bakes its own front-end: the mel extractor's settings do not apply)"""
         if num_eval != 0 or not self.ragged_eval:
             return False
         enc = self.__model__.module
         S = getattr(enc, "__S__", None)
-        return S is not None and enc.features != "raw" and hasattr(S, "embed_ragged") and enc._fusable()
+        if S is None or not hasattr(S, "embed_ragged"):
+            return False
+        return enc.features == "raw" or enc._fusable()
 
     def _feats_on_device(self):
         """evaluateFromList / testFromList keep the (n_files, num_eval, nOut) block in HBM from the embed calls to the scoring

@@ -146,3 +146,56 @@ class RawECAPAFusion:
         return np.concatenate([out1, out2], axis=-1)
 
     __call__ = forward
+
+    # ---- ragged batches: whole files of different lengths in shared calls of BOTH branches' primary handles ---------------
+    # Offered only when both branches have embed_ragged (ECAPA-TDNN + RawNet3: Raw3_ECAPA); on the RawNet2 and TitaNet fusions
+    # these attributes do not exist (__getattr__), so whole-file evaluation keeps the per-file path there.
+    _RAGGED = ("ragged_packer", "ragged_frames", "embed_ragged")
+
+    def __getattr__(self, name):
+        if name in RawECAPAFusion._RAGGED:
+            d = self.__dict__
+            if all(hasattr(d.get(a), "embed_ragged") for a in (self.FIRST_ATTR, self.RAW_ATTR)):
+                return getattr(self, "_fusion_" + name)
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    def _fusion_ragged_packer(self):
+        from ..ragged import FusionPacker
+        return FusionPacker(self._first.ragged_packer(), self._raw.ragged_packer())
+
+    def _fusion_ragged_frames(self, n_samples):
+        """the packer's unit: (frames of the first branch, frames of the raw branch); a 0 fits no ragged call"""
+        return self._first.ragged_frames(n_samples), self._raw.ragged_frames(n_samples)
+
+    def _fusion_embed_ragged(self, wavs):
+        """list of 1-D waveforms of any lengths -> (n, nOut): one plan for both branches, [first | raw] per utterance.  CUDA
+        waveforms keep forward's two-stream overlap (each branch on its handle's own stream); otherwise the branches run one
+        after the other.  Raises ValueError for utterances that fit no call of either branch."""
+        from ..ragged import plan_packed
+        calls, alone = plan_packed([self._fusion_ragged_frames(w.shape[-1]) for w in wavs], self._fusion_ragged_packer())
+        if alone:
+            raise ValueError(f"utterances {alone[:8]} fit no ragged call of both branches")
+        e1, e2 = self._first.ragged_engine(), self._raw.ragged_engine()
+        outs = []
+        for call in calls:
+            group = [wavs[i].reshape(-1) for i in call]
+            if _is_torch(group[0]) and group[0].is_cuda:
+                lens = np.asarray([g.shape[0] for g in group], dtype=np.int32)
+                offs = np.zeros(len(group), dtype=np.int64)
+                offs[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+                packed = torch.cat([g.to(torch.float32) for g in group])
+                torch.cuda.current_stream(packed.device).synchronize()     # the pack is complete before either handle reads it
+                o1 = torch.empty((len(group), e1.embed_dim), device=packed.device, dtype=torch.float32)
+                o2 = torch.empty((len(group), e2.embed_dim), device=packed.device, dtype=torch.float32)
+                e1.embed_wave_ragged(packed, offs, lens, out=o1, async_=True, ordered=True)
+                e2.embed_wave_ragged(packed, offs, lens, out=o2, async_=True, ordered=True)
+                e1.synchronize()
+                e2.synchronize()
+                outs.append(torch.cat([o1, o2], dim=-1))
+            else:
+                packed, offs, lens = e1._pack(group, None, None, True)      # packed once, read by both branches
+                o1, o2 = e1.embed_wave_ragged(packed, offs, lens), e2.embed_wave_ragged(packed, offs, lens)
+                outs.append(torch.cat([o1, o2], dim=-1) if _is_torch(o1) else np.concatenate([o1, o2], axis=-1))
+        if len(outs) == 1:
+            return outs[0]
+        return torch.cat(outs, 0) if _is_torch(outs[0]) else np.concatenate(outs, 0)

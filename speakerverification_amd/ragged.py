@@ -3,7 +3,8 @@
 Pure host logic (no GPU, no library): a ragged call of a handle holds at most ``max_batch`` utterances and at most
 ``row_capacity`` frames in all (the rows of the workspace the handle owns, ``max_batch * T``); an utterance needs at least
 ``MIN_FRAMES`` frames (block 3 of ECAPA-TDNN reflect-pads 4).  An utterance that cannot ride in ANY call (longer than the whole
-capacity, or too short) is handed back to the caller, which keeps the per-length handle for it.
+capacity, or too short) is handed back to the caller, which keeps the per-length handle for it.  RawNet3 counts the frames after its
+sinc filterbank (at least 30); a fusion model plans both of its branches at once (FusionPacker).
 """
 from __future__ import annotations
 
@@ -54,4 +55,46 @@ def plan_ragged(frames, max_batch, row_capacity, min_frames=MIN_FRAMES):
         cur.append(i)
     if cur:
         calls.append(cur)
+    return calls, alone
+
+
+class FusionPacker:
+    """One plan for the two branches of a fusion model, which read the same waveforms: the unit is the pair (frames of the first
+    branch, frames of the second), and a call is closed when EITHER branch's utterance count or row capacity would overflow."""
+
+    def __init__(self, first, second):
+        self.packers = (first, second)
+
+    def reset(self):
+        for p in self.packers:
+            p.reset()
+
+    def fits_alone(self, frames):
+        return all(p.fits_alone(f) for p, f in zip(self.packers, frames))
+
+    def add(self, frames):
+        a, b = self.packers
+        if not self.fits_alone(frames) or a.count + 1 > a.max_batch or a.rows + frames[0] > a.row_capacity \
+                or b.count + 1 > b.max_batch or b.rows + frames[1] > b.row_capacity:
+            return False
+        return a.add(frames[0]) and b.add(frames[1])
+
+
+def plan_packed(units, packer):
+    """plan_ragged with a packer of any unit (RaggedPacker: frame counts; FusionPacker: pairs): -> (calls, alone)"""
+    packer.reset()
+    calls, alone, cur = [], [], []
+    for i, t in enumerate(units):
+        if not packer.fits_alone(t):
+            alone.append(i)
+            continue
+        if not packer.add(t):
+            calls.append(cur)
+            cur = []
+            packer.reset()
+            packer.add(t)
+        cur.append(i)
+    if cur:
+        calls.append(cur)
+    packer.reset()
     return calls, alone

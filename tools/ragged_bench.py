@@ -1,6 +1,7 @@
 """Whole-file evaluation (num_eval = 0) on the MI355X: files/s of `ModelHandling._embed_files` over seeded files of 2 - 20 s.
 
-    python tools/ragged_bench.py [--per-file] [--files 512] [--runs 5] [--compute bf16,f32] [--out profiles/ragged_bench.json]
+    python tools/ragged_bench.py [--model ECAPA_TDNN|RawNet3|Raw3_ECAPA] [--per-file] [--files 512] [--runs 5] [--compute bf16,f32]
+                                 [--out profiles/ragged_bench.json]
 
 Default mode: the ragged path of this tree (files of different lengths share calls of the model's primary handle), plus, without a
 bar, the frames/s of the ragged call relative to the fixed-length B = 256 call of the same handle and the library's per-label event
@@ -10,7 +11,9 @@ only path of a tree that does not: the mode uses nothing newer than `_embed_file
 parent commit (put that checkout first on PYTHONPATH), whose files/s are the yardstick.
 
 Own process; every figure is the median of `--runs` timed passes over the whole file list (after one untimed pass), with the spread
-(min, max); wall time and HIP-event time around the whole pass are both given.  ECAPA-TDNN C = 1024, nOut 192."""
+(min, max); wall time and HIP-event time around the whole pass are both given.  ECAPA-TDNN C = 1024, nOut 192; with --model RawNet3
+(nOut 320) or Raw3_ECAPA (nOut 512, the model of the reference's default configs: ECAPA-TDNN C = 512 + RawNet3), `features: raw`,
+written to profiles/rawnet3_ragged_bench.json by convention.  The single-call comparison and the kernel table are ECAPA-TDNN's."""
 from __future__ import annotations
 
 import argparse
@@ -46,15 +49,44 @@ def make_files(n):
     return [np.clip(0.1 * rng.standard_normal(int(L), dtype=np.float32), -1.0, 1.0) for L in lens]
 
 
-def handler(compute, per_file):
+MODELS = {"ECAPA_TDNN": "ECAPA_TDNN C=1024 nOut=192", "RawNet3": "RawNet3 nOut=320", "Raw3_ECAPA": "Raw3_ECAPA nOut=512 (ECAPA-TDNN C=512 + RawNet3)"}
+
+
+def state_dict(model):
+    if model == "ECAPA_TDNN":
+        return synth.synth_state_dict(synth.ecapa_param_spec(C=1024), seed=5)
+    rn3 = synth.synth_state_dict(synth.rawnet3_param_spec(nOut=320), seed=5)
+    if model == "RawNet3":
+        return rn3
+    sd = {"ECAPA_TDNN." + k: v for k, v in synth.synth_state_dict(synth.ecapa_param_spec(C=512, input_norm=True), seed=5).items()}
+    sd.update({"rawnet." + k: v for k, v in rn3.items()})
+    return sd
+
+
+def handler(compute, per_file, model="ECAPA_TDNN"):
     kw = dict(ARGS, hip_compute=compute)
+    if model != "ECAPA_TDNN":
+        kw.update(model={"name": model, "nOut": 320 if model == "RawNet3" else 512}, features="raw")
+        kw.pop("channels")
     net = WrappedModel(SpeakerEncoder(**kw))
     extra = {}
     if per_file and "ragged_eval" in inspect.getsource(ModelHandling.__init__):
         extra["ragged_eval"] = False
     mh = ModelHandling(net, **dict(kw, save_folder=".", device_feats=False, **extra))
-    net.module.load_state_dict({"__S__." + k: v for k, v in synth.synth_state_dict(synth.ecapa_param_spec(C=1024), seed=5).items()})
+    net.module.load_state_dict({"__S__." + k: v for k, v in state_dict(model).items()})
     return mh, getattr(net.module, "__S__")
+
+
+def engines_alive(S):
+    """handles the model keeps alive: of the module itself, or of each branch of a fusion model"""
+    if hasattr(S, "_engines"):
+        return len(S._engines)
+    return {a: len(getattr(S, a)._engines) for a in (S.FIRST_ATTR, S.RAW_ATTR)}
+
+
+def drop_engines(S):
+    for m in ([S] if hasattr(S, "_drop_engine") else [getattr(S, S.FIRST_ATTR), getattr(S, S.RAW_ATTR)]):
+        m._drop_engine()
 
 
 def timed(fn, runs):
@@ -79,6 +111,7 @@ def stats(xs):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="ECAPA_TDNN", choices=sorted(MODELS))
     ap.add_argument("--per-file", action="store_true")
     ap.add_argument("--files", type=int, default=512)
     ap.add_argument("--runs", type=int, default=5)
@@ -87,15 +120,15 @@ def main():
     a = ap.parse_args()
     files = make_files(a.files)
     frames = int(sum(len(f) // 80 + 1 for f in files))
-    res = {"mode": "per_file" if a.per_file else "ragged", "files": a.files, "frames": frames, "runs": a.runs, "model": "ECAPA_TDNN C=1024 nOut=192",
+    res = {"mode": "per_file" if a.per_file else "ragged", "files": a.files, "frames": frames, "runs": a.runs, "model": MODELS[a.model],
            "device": torch.cuda.get_device_name(0), "tree_has_ragged_calls": hasattr(ModelHandling, "_ragged_ok")}
     for compute in a.compute.split(","):
-        mh, S = handler(compute, a.per_file)
+        mh, S = handler(compute, a.per_file, a.model)
         wall, dev = timed(lambda: mh._embed_files(files, 0), a.runs)
         r = {"wall_s": stats(wall), "hip_event_s": stats(dev),
              "files_per_s": {"median": a.files / float(np.median(wall)), "min": a.files / max(wall), "max": a.files / min(wall)},
-             "frames_per_s": frames / float(np.median(wall)), "engines_alive": len(S._engines)}
-        if not a.per_file:
+             "frames_per_s": frames / float(np.median(wall)), "engines_alive": engines_alive(S)}
+        if not a.per_file and a.model == "ECAPA_TDNN":
             eng = S.ragged_engine()
             # the ragged call against the fixed-length call of the same handle, device-resident input, frames/s of each
             x = torch.from_numpy(synth.synth_waveforms(eng.max_batch, eng.samples, seed=1)).cuda()
@@ -121,7 +154,7 @@ def main():
             r["ragged_forward_pack"] = {"utterances": len(lens), "frames": int(sum(n // 80 + 1 for n in lens))}
         res[compute] = r
         print(compute, json.dumps(r["files_per_s"]), flush=True)
-        S._drop_engine()
+        drop_engines(S)
     line = json.dumps(res)
     print(line)
     if a.out:
