@@ -227,6 +227,31 @@ int svhip_rawnet3_embed_ragged(svhip_handle* h, const float* wav, const int64_t*
 /* lengths[i] are samples.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is svhip_last_error(NULL). */
 int svhip_rawnet3_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n);
 
+/* Ragged Conformer packs (added under ABI v5): the same calls for SVHIP_MODEL_CONFORMER.  The ECAPA and RawNet3 calls above keep
+ * refusing a Conformer handle with SVHIP_ERR_UNSUPPORTED.
+ *   in / offsets / lengths / emb_out / flags: the rules of svhip_embed_wave_ragged (is_wave != 0: lengths and offsets in samples) and of
+ *   svhip_embed_features_ragged (is_wave == 0: lengths are frames, offsets frame offsets).  Utterance i has T_i mel frames and
+ *   T'_i = (T_i - 3) / 4 subsampled frames; the pack is laid out back to back at both levels.
+ * CAPACITY, checked on the host before anything is enqueued (svhip_conformer_ragged_check is the same test without a handle):
+ *   1 <= n <= max_batch;  every T_i >= 7;  wave: every lengths[i] >= n_fft;  offsets >= 0;  every T'_i <= 10000 (the positional
+ *   encoding);  every T'_i <= chunk * T', what one subsampling slice of the handle holds (T' of the handle's own length; chunk =
+ *   min(max_batch, 256 MiB / the conv1 output of one utterance of that length): an utterance's conv1 image must fit the slice buffer);
+ *   sum_i T_i <= max_batch * T, the mel rows of the workspace the handle owns.  That one sum rule bounds the subsampled level: the row
+ *   buffers of the blocks hold floor((max_batch * T - 3) / 4) rows (the sum of T'_i can pass max_batch * T' by about 1.5 max_batch rows).
+ * Anything else is SVHIP_ERR_INVALID with a message that names the utterance and the limit.  Compute SVHIP_F32 or SVHIP_BF16 only: every
+ * other model and SVHIP_F32X3 return SVHIP_ERR_UNSUPPORTED.  The first ragged call of a handle allocates the segment tables and a
+ * waveform staging buffer (once); P = pe W_pos^T is formed for rows 0 .. the longest T'_i seen so far (the double-precision row sums of
+ * svhip_finalize_weights, so its first T' rows are the handle's own), on the first ragged call and again only when a longer utterance
+ * arrives.  Nothing else is allocated per call, and a handle that never sees a ragged call pays nothing.
+ * BATCH INVARIANCE as above: bit-for-bit the same embedding and stages whatever the pack; to the precision of the compute type against
+ * a fixed-length call.  A non-finite input gives NaN for its own utterance only, and SVHIP_ERR_NONFINITE.
+ * STAGES after a ragged call: cf_in, cf_attn0, cf_block0, cf_last (sum T'_i, 256), rows packed in utterance order; cf_pool (n, 512);
+ * "input" (sum T_i, n_mels). */
+int svhip_conformer_embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
+                                 int32_t flags, int32_t is_wave);
+/* lengths[i] are samples (is_wave != 0) or frames.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is svhip_last_error(NULL). */
+int svhip_conformer_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave);
+
 /* Eval-mode cropping on device.  Replaces, for decoded 16-bit PCM, the cropping half of loadWAV
  * (src/processing/audio_loader.py:110-150): wrap-pad files not longer than L to L+1 samples, take num_eval
  * crops of L samples at int(linspace(0, len - L, num_eval)), scale by 1/32768 (soundfile float32).  pcm holds
@@ -400,6 +425,13 @@ int svhip_selftest(void);   /* host-only self checks (per-device launch-attribut
  * SVHIP_ERR_INVALID (arguments) or SVHIP_ERR_HIP (launch). */
 int svhip_conformer_attention(const void* qkv, const float* P, const float* u_bias, const float* v_bias, void* ctx, int32_t compute,
                               int32_t B, int32_t T_sub, void* stream);
+
+/* The attention kernel over a pack (tests), the counterpart of svhip_conformer_attention: utterance u owns the rows
+ * [row0_dev[u], row0_dev[u + 1]) of qkv and ctx (row0_dev: a DEVICE table of n + 1 ints) and is attended exactly as
+ * svhip_conformer_attention attends it alone (B = 1, T_sub = its length), bit for bit; P holds at least max_T_sub rows and
+ * max_T_sub >= every utterance's length. */
+int svhip_conformer_attention_ragged(const void* qkv, const float* P, const float* u_bias, const float* v_bias, void* ctx, int32_t compute,
+                                     const int32_t* row0_dev, int32_t n, int32_t max_T_sub, void* stream);
 
 /* ResNetSE's 3 x 3 convolution kernel on its own (tests): y = [relu](scale[n] conv3x3_stride([relu](x)) + shift[n]) with zero padding 1.
  * x (B, P, Q, Cin) and y (B, Po, Qo, Cout), Po = (P - 1) / stride + 1, are DEVICE pointers, channels-last, in the compute type (SVHIP_F32 /

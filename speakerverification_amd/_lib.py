@@ -74,6 +74,8 @@ _SIGNATURES = {
     "svhip_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),
     "svhip_rawnet3_embed_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32]),
     "svhip_rawnet3_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32]),
+    "svhip_conformer_embed_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32]),
+    "svhip_conformer_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),
     "svhip_crop_pcm16": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     "svhip_l2norm": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32]),
     "svhip_score_pairs": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32]),
@@ -117,6 +119,7 @@ _SIGNATURES = {
     "svhip_trim_scratch": (C.c_int, [_P]),
     "svhip_selftest": (C.c_int, []),
     "svhip_conformer_attention": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "svhip_conformer_attention_ragged": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P]),
     "svhip_resnetse_conv3x3": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 9 + [_P]),
 }
 

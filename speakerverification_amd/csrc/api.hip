@@ -511,6 +511,33 @@ int svhip_rawnet3_ragged_check(const svhip_config* cfg, const int32_t* lengths, 
     return rc;
 }
 
+int svhip_conformer_embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
+                                 int32_t flags, int32_t is_wave) {
+    if (!h) return SVHIP_ERR_INVALID;
+    if (!h->finalized) SV_FAIL(h, SVHIP_ERR_STATE, "weights not finalized (call svhip_finalize_weights first)");
+    if (!in || !offsets || !lengths || !emb_out) SV_FAIL(h, SVHIP_ERR_INVALID, "null pointer");
+    std::string msg;
+    if (int rc = conformer_ragged_check(h->cfg, lengths, n, is_wave != 0, msg)) SV_FAIL(h, rc, "%s", msg.c_str());
+    for (int i = 0; i < n; ++i)
+        if (offsets[i] < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance %d: negative offset (the limit is 0)", i);
+    if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
+        SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    int rc = conformer_embed_ragged(h, in, !(flags & SVHIP_IN_DEVICE), is_wave != 0, offsets, lengths, n);
+    if (rc) return rc;
+    if ((rc = emit_embeddings(h, n, emb_out, flags))) return rc;
+    return finish(h, flags);
+}
+
+int svhip_conformer_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave) {
+    if (!cfg || cfg->struct_size != (int32_t)sizeof(svhip_config)) { g_create_error = "bad config / struct_size"; return SVHIP_ERR_INVALID; }
+    if (!lengths) { g_create_error = "null pointer"; return SVHIP_ERR_INVALID; }
+    std::string msg;
+    const int rc = conformer_ragged_check(*cfg, lengths, n, is_wave != 0, msg);
+    if (rc) g_create_error = msg;
+    return rc;
+}
+
 int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, const int64_t* offsets, const int32_t* lengths,
                      int32_t n_files, int32_t num_eval, int32_t L, float* crops_out, int32_t flags) {
     if (!h || !pcm || !offsets || !lengths || !crops_out || n_files <= 0 || num_eval <= 0 || L <= 0 || n_samples <= 0) return SVHIP_ERR_INVALID;
@@ -597,14 +624,15 @@ int svhip_get_stage(svhip_handle* h, const char* name, float* out, int64_t* coun
     if (!h || !name || !count) return SVHIP_ERR_INVALID;
     if (h->lastB <= 0) SV_FAIL(h, SVHIP_ERR_STATE, "no forward has run yet");
     const int B = h->lastB;
-    StageView v{nullptr, h->rag_rows ? (size_t)h->rag_rows : (size_t)B * h->T, 0, 0, !h->bf16};      // (a ragged forward: the packed rows)
+    const size_t rag_in = h->rag_rows && h->rag_in_rows ? (size_t)h->rag_in_rows : (size_t)h->rag_rows;      // packed mel frames of a ragged forward
+    StageView v{nullptr, h->rag_rows ? rag_in : (size_t)B * h->T, 0, 0, !h->bf16};      // (a ragged forward: the packed rows)
     const std::string n(name);
     if (n == "input" && h->X_in) { v.src = h->X_in; v.cols = v.ld = h->cfg.n_mels; }
     else if (n == "mel") {
         if (h->feat_is_stale) SV_FAIL(h, SVHIP_ERR_STATE, "stage mel: the last forward ran the fused front-end, which never forms the mel power "
                                       "tensor (option fbank_unfused = 1 keeps the separate kernels)");
         v.src = h->d_feat; v.rows = (size_t)B * h->cfg.n_mels; v.cols = v.ld = h->T; v.f32 = true;
-        if (h->rag_rows) { v.rows = 1; v.cols = v.ld = (size_t)h->rag_rows * h->cfg.n_mels; }      // the (n_mels, T_u) blocks back to back
+        if (h->rag_rows) { v.rows = 1; v.cols = v.ld = rag_in * h->cfg.n_mels; }      // the (n_mels, T_u) blocks back to back
     }
     else {                                    // every other name is the model's
         const ModelOps* m = model_ops(h->cfg.model);

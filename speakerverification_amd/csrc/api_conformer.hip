@@ -11,7 +11,15 @@
 //   pooling     w = softmax_T(attention.3(BN(relu(attention.0 x)))); [mu | sqrt(clamp(var, 1e-4, 1e4))]; attention_norm; fc
 // Every Linear / pointwise conv goes through conv_plan / conv_gemm.  The half-step residuals are the GEMM epilogue's scale (0.5) and
 // residual R; the residual stream stays in the handle's storage type.
+//
+// A ragged pack (conformer_embed_ragged): n utterances of T_u mel frames, packed back to back at the mel level and, T'_u rows each, at
+// the subsampled level (row0 / utt tables, as ECAPA's and RawNet3's packs).  The same layers over the packed rows: every GEMM through
+// launch_gemm_ragged, LayerNorm unchanged (row-wise), and the five steps that know where an utterance begins and ends in their
+// segment-table forms — the input normalisation (launch_rag_prologue), the subsampling (conv1 keeps only the 2 T'_u + 1 rows conv2
+// reads, utterance u's at conv1 row 2 row0[u] + u; conv2's operand gather adds that per-utterance offset), the attention, the GLU +
+// depthwise conv and the pooling.  P = pe W_pos^T is kept for rows 0 .. the longest T'_u seen (row c depends on c only).
 #include <algorithm>
+#include <cstring>
 #include <thread>
 
 #include "handle.h"
@@ -22,6 +30,8 @@ namespace {
 
 int cf_sub(int n) { return (n - 3) / 2 + 1; }                         // one Conv2d(3, stride 2) of Conformer's subsampling (n >= 3)
 constexpr int CF_D = 256, CF_LAYERS = 6, CF_MAX_T = 10000;           // d_model, blocks, the length of the pe buffer
+
+struct RagSlot { char* host = nullptr; hipEvent_t done = nullptr; bool busy = false; };
 
 struct CfBlock {
     float *ff_g[2] = {}, *ff_b[2] = {};   // the two feed-forward modules' LayerNorms (FF, FF')
@@ -59,9 +69,59 @@ struct ConformerState : ModelState {
     void* last = nullptr;                 // the last block's output
     float* logits = nullptr;              // (Bmax T', 256) fp32 attention logits of the pooling
     float *pool_raw = nullptr, *pool = nullptr;         // (Bmax, 512) [mean | std], after attention_norm
+    // ragged packs (allocated by the first ragged call; the row buffers above hold rows_cap >= floor((Bmax T - 3) / 4) rows for them)
+    size_t rows_cap = 0;
+    std::vector<std::vector<float>> pe_host, wpos_host;   // kept from finalize: each layer's pos_proj weight; pe_host[pe_of[i]] is layer
+    std::vector<int> pe_of;                               // i's positional encoding (layers whose buffers are equal share one copy)
+    float* rag_P = nullptr;               // (layers, rag_P_rows, 256): P for rows 0 .. rag_P_rows - 1, grown to the longest T'_u seen
+    int rag_P_rows = 0;
+    char* rag_tab = nullptr;              // device tables of the call: feature offsets (Bmax int64), mel row0, subsampled row0 (Bmax + 1 each)
+    int64_t* rag_feat_off = nullptr;
+    int *rag_mel0 = nullptr, *rag_row0 = nullptr;
+    int* rag_utt = nullptr;               // (rows_cap) utterance of every subsampled row
+    float *rag_wav = nullptr, *rag_stats = nullptr;   // host-pointer waveform staging; (Bmax n_mels 2) shift / scale of the front-end
+    RagSlot rag_slot[4];                  // pinned copies of the tables of the calls in flight (SVHIP_ASYNC returns before the copy has run)
+    int rag_next = 0;
+
+    ~ConformerState() override {
+        for (auto& sl : rag_slot) {
+            if (sl.host) (void)hipHostFree(sl.host);
+            if (sl.done) (void)hipEventDestroy(sl.done);
+        }
+        if (rag_P) (void)hipFree(rag_P);
+    }
 };
 
 ConformerState& S(svhip_handle* h) { return static_cast<ConformerState&>(*h->model); }
+
+// utterances per subsampling slice: what keeps the conv1 output of a slice within 256 MiB
+int cf_chunk(const svhip_config& c, int T) {
+    const size_t e = c.compute == SVHIP_BF16 ? 2 : 4;
+    const size_t per_utt = (size_t)cf_sub(T) * cf_sub(c.n_mels) * CF_D * e;          // conv1 output bytes of one utterance
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)c.max_batch, ((size_t)256 << 20) / per_utt));
+}
+
+// rows [0, rows) of P = pe W_pos^T, every element a double-precision sum over k in order: a row depends on its index only
+// (rows split over up to 16 host threads: 6 x 655 M multiply-adds at T' = 10^4; every row is the same sum whatever the split)
+void cf_pos_rows(const float* pe, const float* wp, int rows, float* P) {
+    const int D = CF_D;
+    auto part = [&](int t0, int t1) {
+        for (int t = t0; t < t1; ++t) {
+            const float* pr = pe + (size_t)t * D;
+            for (int n = 0; n < D; ++n) {
+                const float* wr = wp + (size_t)n * D;
+                double acc = 0.0;
+                for (int k = 0; k < D; ++k) acc += (double)pr[k] * (double)wr[k];
+                P[(size_t)t * D + n] = (float)acc;
+            }
+        }
+    };
+    const int nt = std::max(1, std::min({16, (int)std::thread::hardware_concurrency(), (rows + 63) / 64}));
+    std::vector<std::thread> pool;
+    for (int q = 1; q < nt; ++q) pool.emplace_back(part, (int)((int64_t)rows * q / nt), (int)((int64_t)rows * (q + 1) / nt));
+    part(0, rows / nt);
+    for (auto& th : pool) th.join();
+}
 
 }  // namespace
 
@@ -171,6 +231,7 @@ int conformer_finalize(svhip_handle* h) {
     }
     double fl = 2.0 * 9 * D * s.T1 * s.F1 + (double)Tp * F2 * s.c2.flops_per_row + (double)Tp * s.proj.flops_per_row;
     s.blocks.assign(CF_LAYERS, CfBlock{});
+    s.pe_host.assign(CF_LAYERS, {}); s.wpos_host.assign(CF_LAYERS, {}); s.pe_of.assign(CF_LAYERS, 0);
     for (int i = 0; i < CF_LAYERS; ++i) {
         CfBlock& K = s.blocks[i];
         const std::string p = "conformer_block.layers." + std::to_string(i) + ".";
@@ -202,25 +263,18 @@ int conformer_finalize(svhip_handle* h) {
             // P = pe[:T'] pos_proj^T in double: the positional term depends on T' only
             const HostTensor *pe = getw(h, a + "positional_encoding.pe"), *wp = getw(h, a + "attention.pos_proj.linear.weight");
             if (!pe || !wp) SV_FAIL(h, SVHIP_ERR_MISSING, "missing tensor %s%s", a.c_str(), !pe ? "positional_encoding.pe" : "attention.pos_proj.linear.weight");
+            if (pe->numel() < (int64_t)CF_MAX_T * D || wp->numel() != (int64_t)D * D)
+                SV_FAIL(h, SVHIP_ERR_INVALID, "%spositional_encoding.pe must be (1, %d, %d) and pos_proj (%d, %d)", a.c_str(), CF_MAX_T, D, D, D);
             std::vector<float> P((size_t)Tp * D);
-            auto rows = [&](int t0, int t1) {
-                for (int t = t0; t < t1; ++t) {
-                    const float* pr = pe->data.data() + (size_t)t * D;
-                    for (int n = 0; n < D; ++n) {
-                        const float* wr = wp->data.data() + (size_t)n * D;
-                        double acc = 0.0;
-                        for (int k = 0; k < D; ++k) acc += (double)pr[k] * (double)wr[k];
-                        P[(size_t)t * D + n] = (float)acc;
-                    }
-                }
-            };
-            // (rows split over up to 16 host threads: 6 x 655 M multiply-adds at T' = 10^4; every row is the same sum whatever the split)
-            const int nt = std::max(1, std::min({16, (int)std::thread::hardware_concurrency(), (Tp + 63) / 64}));
-            std::vector<std::thread> pool;
-            for (int q = 1; q < nt; ++q) pool.emplace_back(rows, (int)((int64_t)Tp * q / nt), (int)((int64_t)Tp * (q + 1) / nt));
-            rows(0, Tp / nt);
-            for (auto& th : pool) th.join();
+            cf_pos_rows(pe->data.data(), wp->data.data(), Tp, P.data());
             if ((rc = dev_upload(h, &K.P, P))) return rc;
+            // a ragged call forms P for its own lengths: the two host tensors outlive finalize (the loaded weights are dropped after it)
+            s.wpos_host[i] = wp->data;
+            int same = -1;
+            for (int j = 0; j < i && same < 0; ++j)
+                if (s.pe_of[j] == j && !memcmp(s.pe_host[j].data(), pe->data.data(), (size_t)CF_MAX_T * D * 4)) same = j;
+            s.pe_of[i] = same < 0 ? i : same;
+            if (same < 0) s.pe_host[i] = std::move(const_cast<HostTensor*>(pe)->data);
         }
         fl += (double)Tp * (K.qkv.flops_per_row + K.out.flops_per_row) + 4.0 * Tp * (double)Tp * 3 * 2 * 64;
         const std::string cv = p + "sequential.2.module.sequential.";
@@ -264,14 +318,15 @@ int conformer_alloc(svhip_handle* h) {
     h->model = std::make_unique<ConformerState>();
     auto& s = S(h);
     const svhip_config& c = h->cfg;
-    const size_t B = c.max_batch, M = B * h->T, e = h->esz;
+    const size_t B = c.max_batch, M = B * h->T;
     int rc;
     // the subsampling slice buffers, eleven (B T', <= 1024) activations, logits, pooled rows
     s.T1 = cf_sub(h->T); s.F1 = cf_sub(c.n_mels);
     s.Tp = cf_sub(s.T1); s.F2 = cf_sub(s.F1);
-    const size_t Tp = s.Tp, Mp = B * Tp, D = CF_D;
-    const size_t per_utt = (size_t)s.T1 * s.F1 * D * e;          // conv1 output bytes of one utterance
-    s.chunk = (int)std::max<size_t>(1, std::min<size_t>(B, ((size_t)256 << 20) / per_utt));
+    // (the row buffers: a ragged pack of sum T_i <= B T mel frames has up to floor((B T - 3) / 4) subsampled rows, a few more than B T')
+    const size_t Tp = s.Tp, Mp = std::max(B * Tp, (B * (size_t)h->T - 3) / 4), D = CF_D;
+    s.rows_cap = Mp;
+    s.chunk = cf_chunk(c, h->T);
     if ((rc = actbuf(h, &h->X_in, M * c.n_mels))) return rc;
     if ((rc = actbuf(h, &s.c1, (size_t)s.chunk * s.T1 * s.F1 * D))) return rc;
     if ((rc = actbuf(h, &s.s2, (size_t)s.chunk * Tp * s.F2 * D))) return rc;
@@ -381,9 +436,261 @@ static int conformer_forward_part(svhip_handle* h, const float* d_feat, int b0, 
 
 int conformer_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, conformer_forward_part, d_feat, B, 1, B); }
 
+// ---- ragged packs ------------------------------------------------------------------------------------------
+// The scope and capacity rules of svhip_conformer_embed_ragged (include/svhip.h), on the host alone.
+int conformer_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
+    char b[320];
+    if (c.model != SVHIP_MODEL_CONFORMER) { err = "ragged Conformer packs: SVHIP_MODEL_CONFORMER only (ECAPA and RawNet3 packs have their own calls)"; return SVHIP_ERR_UNSUPPORTED; }
+    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "ragged Conformer packs: compute SVHIP_F32 or SVHIP_BF16 only"; return SVHIP_ERR_UNSUPPORTED; }
+    if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft || c.n_mels < 7 || c.samples / c.hop_length + 1 < 7) {
+        err = "bad hop_length / max_batch / samples / n_mels"; return SVHIP_ERR_INVALID;
+    }
+    if (n < 1 || n > c.max_batch) {
+        snprintf(b, sizeof(b), "ragged batch of %d utterances outside [1, max_batch=%d]", n, c.max_batch);
+        err = b; return SVHIP_ERR_INVALID;
+    }
+    const int Th = c.samples / c.hop_length + 1;
+    const int64_t cap = (int64_t)c.max_batch * Th;
+    const int64_t slice = (int64_t)cf_chunk(c, Th) * cf_sub(cf_sub(Th));      // subsampled frames one subsampling slice holds
+    int64_t rows = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t len = lengths[i];
+        if (is_wave && len < c.n_fft) {
+            snprintf(b, sizeof(b), "utterance %d: %lld samples, fewer than n_fft=%d", i, (long long)len, c.n_fft);
+            err = b; return SVHIP_ERR_INVALID;
+        }
+        const int64_t T = is_wave ? len / c.hop_length + 1 : len;
+        if (T < 7) {
+            snprintf(b, sizeof(b), "utterance %d: %lld frames, fewer than 7 (two 3 x 3 stride-2 convolutions leave T' = (T - 3) / 4 >= 1)", i, (long long)T);
+            err = b; return SVHIP_ERR_INVALID;
+        }
+        const int64_t Tp = (T - 3) / 4;
+        if (Tp > CF_MAX_T) {
+            snprintf(b, sizeof(b), "utterance %d: T' = %lld subsampled frames, over the %d positions of the positional encoding", i, (long long)Tp, CF_MAX_T);
+            err = b; return SVHIP_ERR_INVALID;
+        }
+        if (Tp > slice) {
+            snprintf(b, sizeof(b), "utterance %d: T' = %lld subsampled frames, over the %lld one subsampling slice of this handle holds (its conv1 image "
+                                   "must fit the slice buffer)", i, (long long)Tp, (long long)slice);
+            err = b; return SVHIP_ERR_INVALID;
+        }
+        rows += T;
+        if (rows > cap) {
+            snprintf(b, sizeof(b), "utterance %d: the pack reaches %lld frames, over the handle's capacity of max_batch * T = %lld rows", i,
+                     (long long)rows, (long long)cap);
+            err = b; return SVHIP_ERR_INVALID;
+        }
+    }
+    return SVHIP_OK;
+}
+
+static size_t cf_tab_bytes(size_t B) { return B * 8 + 2 * (B + 1) * 4; }
+
+// the segment tables, the waveform staging buffer and the pinned table slots: once per handle
+static int conformer_ragged_alloc(svhip_handle* h) {
+    auto& s = S(h);
+    if (s.rag_utt) return SVHIP_OK;
+    const svhip_config& c = h->cfg;
+    const size_t B = c.max_batch;
+    int rc;
+    if ((rc = dev_alloc(h, &s.rag_tab, cf_tab_bytes(B)))) return rc;
+    s.rag_feat_off = reinterpret_cast<int64_t*>(s.rag_tab);
+    s.rag_mel0 = reinterpret_cast<int*>(s.rag_tab + B * 8);
+    s.rag_row0 = s.rag_mel0 + (B + 1);
+    if ((rc = dev_alloc(h, &s.rag_wav, B * ((size_t)c.samples + c.hop_length)))) return rc;
+    if ((rc = dev_alloc(h, &s.rag_stats, B * c.n_mels * 2))) return rc;
+    for (auto& sl : s.rag_slot) {
+        SV_HIP(h, hipHostMalloc((void**)&sl.host, cf_tab_bytes(B), hipHostMallocDefault));
+        SV_HIP(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    }
+    return dev_alloc(h, &s.rag_utt, s.rows_cap);
+}
+
+// P of every layer for rows [0, rows): the double-precision row sums of finalize, so the first T' rows are the handle's own P bit for
+// bit.  Grown (in steps of 256 rows) when a pack brings a longer utterance than any before it; a handle without ragged calls never
+// gets here.
+static int conformer_ragged_pos(svhip_handle* h, int rows) {
+    auto& s = S(h);
+    if (rows <= s.rag_P_rows) return SVHIP_OK;
+    rows = std::min(CF_MAX_T, (rows + 255) & ~255);
+    SV_HIP(h, hipStreamSynchronize(h->stream));        // (earlier calls may still read the old table)
+    if (s.rag_P) (void)hipFree(s.rag_P);
+    s.rag_P = nullptr; s.rag_P_rows = 0;
+    const size_t per = (size_t)rows * CF_D;
+    hipError_t e = hipMalloc((void**)&s.rag_P, CF_LAYERS * per * 4);
+    if (e != hipSuccess) SV_FAIL(h, SVHIP_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", CF_LAYERS * per * 4, hipGetErrorString(e));
+    std::vector<float> P(CF_LAYERS * per);
+    for (int i = 0; i < CF_LAYERS; ++i) cf_pos_rows(s.pe_host[s.pe_of[i]].data(), s.wpos_host[i].data(), rows, P.data() + i * per);
+    SV_HIP(h, hipMemcpy(s.rag_P, P.data(), P.size() * 4, hipMemcpyHostToDevice));
+    s.rag_P_rows = rows;
+    return SVHIP_OK;
+}
+
+// Conformer_.forward over the packed rows of a ragged batch (features at d_feat + rag_feat_off[u]; tables on the device; hrow0: the
+// subsampled row0 on the host).  One stream; nothing but the per-slice subsampling is launched more than once per layer.
+static int conformer_forward_ragged(svhip_handle* h, const float* d_feat, int n, int maxT, const int* hrow0, int maxTp) {
+    auto& s = S(h);
+    const svhip_config& c = h->cfg;
+    const int F = c.n_mels, F1 = s.F1, F2 = s.F2, e = h->esz, D = CF_D;
+    const int M = hrow0[n];
+    const bool bf = h->bf16;
+    hipStream_t st = h->cur = h->stream;
+    const int *row0 = s.rag_row0, *utt = s.rag_utt;
+    int rc;
+    auto gemm = [&](const ConvLayer& L, const GemmParams& p) {
+        return run(h, "rag_gemm", (double)p.M * L.flops_per_row, [&]() { return launch_gemm_ragged(p, bf, st); });
+    };
+    if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(row0, n, maxTp, s.rag_utt, st); }))) return rc;
+    if ((rc = run(h, "rag_prologue", 0, [&]() {
+             return launch_rag_prologue(d_feat, s.rag_feat_off, s.rag_mel0, n, maxT, h->X_in, bf, F, c.log_input, h->in_w, h->in_b, s.rag_stats, st);
+         }))) return rc;
+    // the subsampling, whole utterances at a time: a slice holds at most `chunk` utterances and chunk * T' subsampled frames, so that
+    // its conv1 image (2 T'_u + 1 <= T1 rows per utterance) and its conv2 output fit the buffers of the fixed-length slices
+    const int64_t slice_rows = (int64_t)s.chunk * s.Tp;
+    for (int u0 = 0; u0 < n;) {
+        int u1 = u0, mt = 0;
+        while (u1 < n && u1 - u0 < s.chunk && hrow0[u1 + 1] - hrow0[u0] <= slice_rows) { mt = std::max(mt, hrow0[u1 + 1] - hrow0[u1]); ++u1; }
+        const int rows = hrow0[u1] - hrow0[u0];
+        if ((rc = run(h, "cf_conv1_rag", 2.0 * 9 * D * (2.0 * rows + (u1 - u0)) * F1, [&]() {
+                 return launch_cf_conv1_ragged(h->X_in, s.c1_w, s.c1_b, s.c1, h->dt, s.rag_mel0, row0, u0, u1 - u0, mt, F, st);
+             }))) return rc;
+        GemmParams p2 = conv_params(h, s.c2, s.c1, D, s.s2, D, rows * F2, 1);
+        p2.act1 = ACT_RELU;
+        p2.seg_off = s.seg_off; p2.seg_rows = F2; p2.seg_len = 3 * D;          // (seg_off[f] = 2 f D: its first F2 entries, frame 0's)
+        p2.seg_stride = (int64_t)F1 * D; p2.seg_utt = 2 * (int64_t)F1 * D; p2.seg_u0 = u0;
+        p2.rag_utt = utt + hrow0[u0]; p2.rag_row0 = row0;
+        if ((rc = gemm(s.c2, p2))) return rc;
+        if ((rc = gemm(s.proj, conv_params(h, s.proj, s.s2, F2 * D, off(s.in, (size_t)hrow0[u0] * D, e), D, rows, 1)))) return rc;
+        u0 = u1;
+    }
+    const void* x = s.in;
+    const int nb = (int)s.blocks.size();
+    if ((rc = cf_ln(h, x, s.ln, s.blocks[0].ff_g[0], s.blocks[0].ff_b[0], M))) return rc;
+    for (int i = 0; i < nb; ++i) {
+        const CfBlock& K = s.blocks[i];
+        void* xo = i == 0 ? s.b0 : i == nb - 1 ? s.last : s.x[i & 1];
+        void* ctx = i == 0 ? s.attn0 : s.ctx;
+        GemmParams f1 = conv_params(h, K.ff1[0], s.ln, D, s.hid, 4 * D, M, 1);
+        f1.act1 = ACT_SWISH;
+        if ((rc = gemm(K.ff1[0], f1))) return rc;
+        GemmParams f2 = conv_params(h, K.ff2[0], s.hid, 4 * D, s.r, D, M, 1);
+        f2.scale = s.half; f2.shift = h->d_zeros; f2.R = x; f2.ldr = D;
+        if ((rc = gemm(K.ff2[0], f2))) return rc;
+        if ((rc = cf_ln(h, s.r, s.ln, K.att_g, K.att_b, M))) return rc;
+        if ((rc = gemm(K.qkv, conv_params(h, K.qkv, s.ln, D, s.hid, 3 * D, M, 1)))) return rc;
+        const float* P = s.rag_P + (size_t)i * s.rag_P_rows * D;
+        if ((rc = run(h, "cf_attn_rag", 0, [&]() {
+                 return launch_cf_attn_ragged(s.hid, 3 * D, P, D, K.u, K.v, ctx, D, h->dt, row0, n, maxTp, st);
+             }))) return rc;
+        GemmParams po = conv_params(h, K.out, ctx, D, xo, D, M, 1);
+        po.R = s.r; po.ldr = D;
+        if ((rc = gemm(K.out, po))) return rc;
+        if ((rc = cf_ln(h, xo, s.ln, K.cv_g, K.cv_b, M))) return rc;
+        if ((rc = gemm(K.pw1, conv_params(h, K.pw1, s.ln, D, s.hid, 2 * D, M, 1)))) return rc;
+        if ((rc = run(h, "cf_glu_dw_rag", 2.0 * 15 * D * M, [&]() {
+                 return launch_cf_glu_dw_ragged(s.hid, K.dw_w, K.dw_b, s.ctx, h->dt, row0, n, maxTp, st);
+             }))) return rc;
+        GemmParams pw = conv_params(h, K.pw2, s.ctx, D, s.r, D, M, 1);
+        pw.R = xo; pw.ldr = D;
+        if ((rc = gemm(K.pw2, pw))) return rc;
+        if ((rc = cf_ln(h, s.r, s.ln, K.ff_g[1], K.ff_b[1], M))) return rc;
+        GemmParams g1 = conv_params(h, K.ff1[1], s.ln, D, s.hid, 4 * D, M, 1);
+        g1.act1 = ACT_SWISH;
+        if ((rc = gemm(K.ff1[1], g1))) return rc;
+        GemmParams g2 = conv_params(h, K.ff2[1], s.hid, 4 * D, s.ln2, D, M, 1);
+        g2.scale = s.half; g2.shift = h->d_zeros; g2.R = s.r; g2.ldr = D;
+        if ((rc = gemm(K.ff2[1], g2))) return rc;
+        const CfBlock* nx = i + 1 < nb ? &s.blocks[i + 1] : nullptr;
+        if ((rc = cf_ln(h, s.ln2, xo, K.fin_g, K.fin_b, M, nx ? s.ln : nullptr, nx ? nx->ff_g[0] : nullptr, nx ? nx->ff_b[0] : nullptr)))
+            return rc;
+        x = xo;
+    }
+    GemmParams pa = conv_params(h, s.att0, x, D, s.hid, 128, M, 1);
+    pa.act1 = ACT_RELU;
+    if ((rc = gemm(s.att0, pa))) return rc;
+    GemmParams pl = conv_params(h, s.att3, s.hid, 128, s.logits, D, M, 1);
+    pl.out_f32 = 1;
+    if ((rc = gemm(s.att3, pl))) return rc;
+    if ((rc = run(h, "rag_asp_pool", 0, [&]() {
+             return launch_rag_asp_pool(s.logits, x, bf, D, row0, n, D, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-4f, st, 1e4f);
+         }))) return rc;
+    // an utterance with a non-finite input value gets a NaN embedding: its own row only
+    if ((rc = run(h, "cf_in_check", 0, [&]() {
+             return launch_tn_nonfinite_rows_ragged(d_feat, s.rag_feat_off, s.rag_mel0, F, n, s.pool, 2 * D, 2 * D, st);
+         }))) return rc;
+    return run(h, "rag_fc", 2.0 * n * s.fc.N * s.fc.K, [&]() {
+        return launch_rag_linear(s.pool, 2 * D, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, n, c.embed_dim, 2 * D, ACT_NONE, st);
+    });
+}
+
+int conformer_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n) {
+    auto& s = S(h);
+    const svhip_config& c = h->cfg;
+    int rc = conformer_ragged_alloc(h);
+    if (rc) return rc;
+    int maxTp = 0;
+    for (int u = 0; u < n; ++u) maxTp = std::max(maxTp, ((is_wave ? lengths[u] / c.hop_length + 1 : lengths[u]) - 3) / 4);
+    if ((rc = conformer_ragged_pos(h, maxTp))) return rc;
+    // the tables of this call, in a pinned slot of the handle: the caller's arrays are free on return
+    RagSlot& slot = s.rag_slot[s.rag_next];
+    s.rag_next = (s.rag_next + 1) & 3;
+    if (slot.busy) { SV_HIP(h, hipEventSynchronize(slot.done)); slot.busy = false; }
+    const size_t B = c.max_batch;
+    int64_t* feat_off = reinterpret_cast<int64_t*>(slot.host);
+    int* mel0 = reinterpret_cast<int*>(slot.host + B * 8);
+    int* row0 = mel0 + (B + 1);
+    int M = 0, Mp = 0, maxT = 0;
+    for (int u = 0; u < n; ++u) {
+        const int T = is_wave ? lengths[u] / c.hop_length + 1 : lengths[u];
+        mel0[u] = M; row0[u] = Mp;
+        M += T; Mp += cf_sub(cf_sub(T));
+        maxT = std::max(maxT, T);
+    }
+    mel0[n] = M; row0[n] = Mp;
+    if ((size_t)Mp > s.rows_cap) SV_FAIL(h, SVHIP_ERR_INVALID, "the pack has %d subsampled rows, over the %zu the handle holds", Mp, s.rows_cap);
+    h->cur = h->stream;
+    const float* d_feat = h->d_feat;
+    h->feat_is_stale = false;
+    if (is_wave) {
+        // the mel power of every utterance, (n_mels, T_u) blocks back to back in d_feat.  The DFT kernel is launched once per utterance
+        // (a workgroup of it sees one utterance's samples only, so its values do not depend on the pack)
+        int64_t pos = 0;
+        for (int u = 0; u < n; ++u) {
+            const int L = lengths[u], T = mel0[u + 1] - mel0[u];
+            const float* w = in + in_off[u];
+            if (in_host) {
+                SV_HIP(h, hipMemcpyAsync(s.rag_wav + pos, w, (size_t)L * 4, hipMemcpyHostToDevice, h->stream));
+                w = s.rag_wav + pos;
+                pos += L;
+            }
+            float* mel = h->d_feat + (size_t)mel0[u] * c.n_mels;
+            if ((rc = run(h, "fbank", 0, [&]() { return launch_fbank(h->fb, w, 1, L, T, mel, h->stream); }))) return rc;
+            feat_off[u] = (int64_t)mel0[u] * c.n_mels;
+        }
+    } else if (in_host) {
+        for (int u = 0; u < n; ++u) {
+            feat_off[u] = (int64_t)mel0[u] * c.n_mels;
+            SV_HIP(h, hipMemcpyAsync(h->d_feat + feat_off[u], in + in_off[u] * c.n_mels, (size_t)lengths[u] * c.n_mels * 4, hipMemcpyHostToDevice, h->stream));
+        }
+    } else {
+        for (int u = 0; u < n; ++u) feat_off[u] = in_off[u] * c.n_mels;
+        d_feat = in;
+        h->feat_is_stale = true;            // (d_feat does not hold this forward's mel power)
+    }
+    SV_HIP(h, hipMemcpyAsync(s.rag_tab, slot.host, cf_tab_bytes(B), hipMemcpyHostToDevice, h->stream));
+    SV_HIP(h, hipEventRecord(slot.done, h->stream));
+    slot.busy = true;
+    // (row0 is read on the host while the launches are enqueued; the slot is not reused before its event)
+    if ((rc = conformer_forward_ragged(h, d_feat, n, maxT, row0, maxTp))) return rc;
+    h->lastB = n;
+    h->rag_rows = Mp;
+    h->rag_in_rows = M;
+    return SVHIP_OK;
+}
+
 int conformer_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // cf_in, cf_block0, cf_attn0, cf_last, cf_pool
     auto& s = S(h);
-    v.rows = (size_t)h->lastB * s.Tp; v.cols = v.ld = CF_D;
+    v.rows = h->rag_rows ? (size_t)h->rag_rows : (size_t)h->lastB * s.Tp; v.cols = v.ld = CF_D;      // (a ragged forward: the packed rows)
     if (n == "cf_in") v.src = s.in;
     else if (n == "cf_block0") v.src = s.b0;
     else if (n == "cf_attn0") v.src = s.attn0;
@@ -401,5 +708,14 @@ extern "C" int svhip_conformer_attention(const void* qkv, const float* P, const 
     if ((compute != SVHIP_F32 && compute != SVHIP_BF16) || T_sub < 1 || T_sub > CF_MAX_T) return SVHIP_ERR_INVALID;
     const hipError_t e = launch_cf_attn(qkv, 3 * CF_D, P, CF_D, u_bias, v_bias, ctx, CF_D, compute == SVHIP_BF16 ? DT_BF16 : DT_F32, B, T_sub,
                                         reinterpret_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SVHIP_OK : e == hipErrorInvalidValue ? SVHIP_ERR_INVALID : SVHIP_ERR_HIP;
+}
+
+extern "C" int svhip_conformer_attention_ragged(const void* qkv, const float* P, const float* u_bias, const float* v_bias, void* ctx,
+                                                int32_t compute, const int32_t* row0_dev, int32_t n, int32_t max_T_sub, void* stream) {
+    using namespace svhip;
+    if ((compute != SVHIP_F32 && compute != SVHIP_BF16) || max_T_sub < 1 || max_T_sub > CF_MAX_T) return SVHIP_ERR_INVALID;
+    const hipError_t e = launch_cf_attn_ragged(qkv, 3 * CF_D, P, CF_D, u_bias, v_bias, ctx, CF_D, compute == SVHIP_BF16 ? DT_BF16 : DT_F32, row0_dev,
+                                               n, max_T_sub, reinterpret_cast<hipStream_t>(stream));
     return e == hipSuccess ? SVHIP_OK : e == hipErrorInvalidValue ? SVHIP_ERR_INVALID : SVHIP_ERR_HIP;
 }

@@ -42,6 +42,27 @@ template <> struct V4<bf16_t> {
 constexpr int CF_D = 256;         // d_model
 
 // ---- cf_conv1: one thread per (b, t1, f1, 4 channels); 9 taps in the order (dt, df) row-major, bias first, then ReLU ----------------
+// one output position: xp = the top-left input value of its 3 x 3 window (input rows F apart), yp = its 256 channels
+template <typename T>
+__device__ __forceinline__ void cf_conv1_point(const T* __restrict__ xp, int F, const float* __restrict__ w, const float* __restrict__ bias,
+                                               T* __restrict__ yp, int c0) {
+    float acc[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = bias[c0 + e];
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+        for (int df = 0; df < 3; ++df) {
+            const float xv = to_f32<T>(xp[(int64_t)dt * F + df]);
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(w + (dt * 3 + df) * CF_D + c0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = fmaf(wv[e], xv, acc[e]);
+        }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = fmaxf(acc[e], 0.0f);
+    V4<T>::store(yp + c0, acc);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void cf_conv1_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                        T* __restrict__ y, int B, int Tn, int F, int T1, int F1) {
@@ -53,22 +74,27 @@ __global__ __launch_bounds__(256) void cf_conv1_kernel(const T* __restrict__ x, 
         const int64_t bt = pos / F1;
         const int t1 = (int)(bt % T1);
         const int b = (int)(bt / T1);
-        const T* __restrict__ xp = x + ((int64_t)b * Tn + 2 * t1) * F + 2 * f1;
-        float acc[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = bias[c0 + e];
-#pragma unroll
-        for (int dt = 0; dt < 3; ++dt)
-#pragma unroll
-            for (int df = 0; df < 3; ++df) {
-                const float xv = to_f32<T>(xp[(int64_t)dt * F + df]);
-                const f32x4 wv = *reinterpret_cast<const f32x4*>(w + (dt * 3 + df) * CF_D + c0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[e] = fmaf(wv[e], xv, acc[e]);
-            }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = fmaxf(acc[e], 0.0f);
-        V4<T>::store(y + pos * CF_D + c0, acc);
+        cf_conv1_point<T>(x + ((int64_t)b * Tn + 2 * t1) * F + 2 * f1, F, w, bias, y + pos * CF_D, c0);
+    }
+}
+
+// The same over a pack, grid (x, utterances of the slice): utterance u = u0 + blockIdx.y reads its mel rows mel0[u] .. of x and writes
+// only the 2 T'_u + 1 conv1 rows that conv2 reads (T'_u = row0[u + 1] - row0[u]), at conv1 row 2 (row0[u] - row0[u0]) + (u - u0) of y
+template <typename T>
+__global__ __launch_bounds__(256) void cf_conv1_rag_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                           T* __restrict__ y, const int* __restrict__ mel0, const int* __restrict__ row0, int u0,
+                                                           int F, int F1) {
+    const int u = u0 + blockIdx.y;
+    const int r0 = row0[u], rows = 2 * (row0[u + 1] - r0) + 1;
+    const int64_t total = (int64_t)rows * F1 * (CF_D / 4);
+    const int64_t out0 = 2 * (int64_t)(r0 - row0[u0]) + (u - u0);
+    const T* __restrict__ xu = x + (int64_t)mel0[u] * F;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+        const int c0 = (int)(g % (CF_D / 4)) * 4;
+        const int64_t pos = g / (CF_D / 4);
+        const int f1 = (int)(pos % F1);
+        const int t1 = (int)(pos / F1);
+        cf_conv1_point<T>(xu + (int64_t)(2 * t1) * F + 2 * f1, F, w, bias, y + (out0 * F1 + pos) * CF_D, c0);
     }
 }
 
@@ -116,17 +142,28 @@ __global__ __launch_bounds__(256) void cf_ln_kernel(const T* __restrict__ x, T* 
 // y = swish(b' + sum_j w'_j g(t - 7 + j)) with the taps added in the order j = 0 .. 14 (BatchNorm folded: w' = s w, b' = shift)
 constexpr int GDW_TT = 16, GDW_K = 15, GDW_R = 7;
 
-template <typename T>
+// RAG (a pack, grid (x, n)): utterance blockIdx.y owns the rows [rag_row0[b], rag_row0[b + 1]); the tile and its halo are zero outside them
+template <typename T, bool RAG>
 __global__ __launch_bounds__(256) void cf_glu_dw_kernel(const T* __restrict__ u, const float* __restrict__ w, const float* __restrict__ bias,
-                                                        T* __restrict__ y, int B, int Tn) {
-    const int ntile = (Tn + GDW_TT - 1) / GDW_TT;
+                                                        T* __restrict__ y, int B, int Tn, const int* __restrict__ rag_row0) {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int c0 = (int)(g % (CF_D / 4)) * 4;
     const int64_t q = g / (CF_D / 4);
-    if (q >= (int64_t)B * ntile) return;
-    const int b = (int)(q / ntile);
-    const int t0 = (int)(q - (int64_t)b * ntile) * GDW_TT;
-    const int64_t row0 = (int64_t)b * Tn;
+    int b, t0;
+    int64_t row0;
+    if (RAG) {
+        b = blockIdx.y;
+        row0 = rag_row0[b];
+        Tn = rag_row0[b + 1] - (int)row0;
+        if (q >= (Tn + GDW_TT - 1) / GDW_TT) return;
+        t0 = (int)q * GDW_TT;
+    } else {
+        const int ntile = (Tn + GDW_TT - 1) / GDW_TT;
+        if (q >= (int64_t)B * ntile) return;
+        b = (int)(q / ntile);
+        t0 = (int)(q - (int64_t)b * ntile) * GDW_TT;
+        row0 = (int64_t)b * Tn;
+    }
     float acc[GDW_TT][4];
     const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + c0);
 #pragma unroll
@@ -183,6 +220,15 @@ __global__ __launch_bounds__(256) void cf_glu_dw_kernel(const T* __restrict__ u,
 //   pos(i, j) = (d >= 2 ? G1 : G0)[i][d - (j0 - i_w - 15)]   read back along the shifted diagonal from LDS
 //   O += softmax-weights V        (the weights through LDS into the A-operand layout)
 // Scores and the softmax are fp32; keys past T' score -inf; rows past T' are computed from zero queries and not written.
+//
+// RAG, a pack of n utterances laid out back to back (row0: n + 1 device ints): the grid is (ceil(max T' / 64), 4, n) and a workgroup
+// takes its first row and its T' from row0[blockIdx.z]; a query tile past its utterance's end leaves at once (the test is uniform over
+// the workgroup and comes before the first barrier).  Everything else is the fixed kernel: every operand load — q' and q'' (row i + 1
+// included), k, v, the band of P — is already masked by T' where it is loaded, so the rows behind an utterance's end, which in a pack
+// are the next utterance's, never enter a product (a weight of 0 would not stop a NaN); P is read from row 0 for every utterance.
+// The plain grid was chosen over a device-built tile table: an idle workgroup costs one table read, and the whole-file packs this
+// serves (2 - 20 s files, T' within a factor of ten) leave at most as many idle tiles as working ones, against a second launch and a
+// prefix sum per block for the table.  LDS footprint and MFMA operand layouts are those of the fixed kernel (one body).
 constexpr int AQ = 64, AK = 64, DH = 64, NBAND = AQ + AK, GW = 80, LDG = GW + 1;
 
 template <typename E> struct AttnMma;
@@ -210,10 +256,10 @@ constexpr size_t attn_lds_bytes() {
     return (size_t)(AQ + (AQ + 1) + AK + DH + NBAND) * AttnMma<T>::LDE * sizeof(T) + (size_t)4 * 2 * 16 * LDG * sizeof(float);
 }
 
-template <typename T>
+template <typename T, bool RAG>
 __global__ __launch_bounds__(256) void cf_attn_kernel(const T* __restrict__ qkv, int ldq, const float* __restrict__ P, int ldp,
                                                       const float* __restrict__ ub, const float* __restrict__ vb, T* __restrict__ ctx,
-                                                      int ldc, int Tn) {
+                                                      int ldc, int Tn, const int* __restrict__ rag_row0) {
     typedef AttnMma<T> M;
     constexpr int LDE = M::LDE, KS = M::KS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -225,7 +271,14 @@ __global__ __launch_bounds__(256) void cf_attn_kernel(const T* __restrict__ qkv,
     float* sG = reinterpret_cast<float*>(sB + NBAND * LDE);       // per wave: [G0 | G1] 2 x 16 x LDG; then the wave's weights
     const int hh = blockIdx.y, b = blockIdx.z;
     const int i0 = blockIdx.x * AQ;
-    const int64_t rb = (int64_t)b * Tn;
+    int64_t rb;
+    if (RAG) {
+        rb = rag_row0[b];
+        Tn = rag_row0[b + 1] - (int)rb;
+        if (i0 >= Tn) return;
+    } else {
+        rb = (int64_t)b * Tn;
+    }
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int qcol = hh * DH, kcol = CF_D + hh * DH, vcol = 2 * CF_D + hh * DH;
     float* gw = sG + w * (2 * 16 * LDG);
@@ -358,6 +411,19 @@ hipError_t launch_cf_conv1(const void* x, const float* w, const float* bias, voi
     return hipGetLastError();
 }
 
+hipError_t launch_cf_conv1_ragged(const void* x, const float* w, const float* bias, void* y, int dt, const int* mel0, const int* row0, int u0,
+                                  int n, int max_T_sub, int F, hipStream_t stream) {
+    const int F1 = (F - 3) / 2 + 1;
+    if (!x || !w || !bias || !y || !mel0 || !row0 || u0 < 0 || n <= 0 || n > 65535 || max_T_sub <= 0 || F < 3 || (dt != DT_F32 && dt != DT_BF16))
+        return hipErrorInvalidValue;
+    if (!al16(w) || !al16(bias) || !al16(y)) return hipErrorInvalidValue;
+    const dim3 grid(grid_of((int64_t)(2 * max_T_sub + 1) * F1 * (CF_D / 4)), (unsigned)n);
+    if (dt == DT_BF16)
+        hipLaunchKernelGGL(cf_conv1_rag_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)x, w, bias, (bf16_t*)y, mel0, row0, u0, F, F1);
+    else hipLaunchKernelGGL(cf_conv1_rag_kernel<float>, grid, dim3(256), 0, stream, (const float*)x, w, bias, (float*)y, mel0, row0, u0, F, F1);
+    return hipGetLastError();
+}
+
 hipError_t launch_cf_ln(const void* x, void* y, const float* g1, const float* b1, void* y2, const float* g2, const float* b2, int dt, int64_t M,
                         hipStream_t stream) {
     if (!x || !y || !g1 || !b1 || M <= 0 || (y2 && (!g2 || !b2)) || (dt != DT_F32 && dt != DT_BF16)) return hipErrorInvalidValue;
@@ -376,27 +442,54 @@ hipError_t launch_cf_glu_dw(const void* u, const float* w, const float* bias, vo
     const int64_t threads = (int64_t)B * ((Tn + GDW_TT - 1) / GDW_TT) * (CF_D / 4);
     if (threads >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((threads + 255) / 256));
-    if (dt == DT_BF16) hipLaunchKernelGGL(cf_glu_dw_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)u, w, bias, (bf16_t*)y, B, Tn);
-    else hipLaunchKernelGGL(cf_glu_dw_kernel<float>, grid, dim3(256), 0, stream, (const float*)u, w, bias, (float*)y, B, Tn);
+    if (dt == DT_BF16)
+        hipLaunchKernelGGL((cf_glu_dw_kernel<bf16_t, false>), grid, dim3(256), 0, stream, (const bf16_t*)u, w, bias, (bf16_t*)y, B, Tn, nullptr);
+    else hipLaunchKernelGGL((cf_glu_dw_kernel<float, false>), grid, dim3(256), 0, stream, (const float*)u, w, bias, (float*)y, B, Tn, nullptr);
     return hipGetLastError();
 }
+
+hipError_t launch_cf_glu_dw_ragged(const void* u, const float* w, const float* bias, void* y, int dt, const int* row0, int n, int max_T_sub,
+                                   hipStream_t stream) {
+    if (!u || !w || !bias || !y || !row0 || n <= 0 || n > 65535 || max_T_sub <= 0 || (dt != DT_F32 && dt != DT_BF16)) return hipErrorInvalidValue;
+    if (!al16(u) || !al16(w) || !al16(bias) || !al16(y)) return hipErrorInvalidValue;
+    const int64_t threads = (int64_t)((max_T_sub + GDW_TT - 1) / GDW_TT) * (CF_D / 4);
+    const dim3 grid((unsigned)((threads + 255) / 256), (unsigned)n);
+    if (dt == DT_BF16)
+        hipLaunchKernelGGL((cf_glu_dw_kernel<bf16_t, true>), grid, dim3(256), 0, stream, (const bf16_t*)u, w, bias, (bf16_t*)y, n, 0, row0);
+    else hipLaunchKernelGGL((cf_glu_dw_kernel<float, true>), grid, dim3(256), 0, stream, (const float*)u, w, bias, (float*)y, n, 0, row0);
+    return hipGetLastError();
+}
+
+namespace {
+
+template <typename T, bool RAG>
+hipError_t attn_launch(const void* qkv, int ldq, const float* P, int ldp, const float* u_bias, const float* v_bias, void* ctx, int ldc, int B, int Tn,
+                       const int* row0, hipStream_t stream) {
+    const size_t lds = attn_lds_bytes<T>();
+    const dim3 grid((unsigned)((Tn + AQ - 1) / AQ), CF_D / DH, (unsigned)B);
+    static DeviceOnce attr;
+    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(cf_attn_kernel<T, RAG>), (int)lds)) return e;
+    hipLaunchKernelGGL((cf_attn_kernel<T, RAG>), grid, dim3(256), lds, stream, (const T*)qkv, ldq, P, ldp, u_bias, v_bias, (T*)ctx, ldc, Tn, row0);
+    return hipGetLastError();
+}
+
+}  // namespace
 
 hipError_t launch_cf_attn(const void* qkv, int ldq, const float* P, int ldp, const float* u_bias, const float* v_bias, void* ctx, int ldc, int dt,
                           int B, int Tn, hipStream_t stream) {
     if (!qkv || !P || !u_bias || !v_bias || !ctx || B <= 0 || B > 65535 || Tn <= 0 || (dt != DT_F32 && dt != DT_BF16)) return hipErrorInvalidValue;
     if (ldq < 3 * CF_D || ldp < CF_D || ldc < CF_D) return hipErrorInvalidValue;
-    const size_t lds = dt == DT_BF16 ? attn_lds_bytes<bf16_t>() : attn_lds_bytes<float>();
-    const dim3 grid((unsigned)((Tn + AQ - 1) / AQ), CF_D / DH, (unsigned)B);
-    if (dt == DT_BF16) {
-        static DeviceOnce attr;
-        if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(cf_attn_kernel<bf16_t>), (int)lds)) return e;
-        hipLaunchKernelGGL(cf_attn_kernel<bf16_t>, grid, dim3(256), lds, stream, (const bf16_t*)qkv, ldq, P, ldp, u_bias, v_bias, (bf16_t*)ctx, ldc, Tn);
-    } else {
-        static DeviceOnce attr;
-        if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(cf_attn_kernel<float>), (int)lds)) return e;
-        hipLaunchKernelGGL(cf_attn_kernel<float>, grid, dim3(256), lds, stream, (const float*)qkv, ldq, P, ldp, u_bias, v_bias, (float*)ctx, ldc, Tn);
-    }
-    return hipGetLastError();
+    if (dt == DT_BF16) return attn_launch<bf16_t, false>(qkv, ldq, P, ldp, u_bias, v_bias, ctx, ldc, B, Tn, nullptr, stream);
+    return attn_launch<float, false>(qkv, ldq, P, ldp, u_bias, v_bias, ctx, ldc, B, Tn, nullptr, stream);
+}
+
+hipError_t launch_cf_attn_ragged(const void* qkv, int ldq, const float* P, int ldp, const float* u_bias, const float* v_bias, void* ctx, int ldc,
+                                 int dt, const int* row0, int n, int max_T_sub, hipStream_t stream) {
+    if (!qkv || !P || !u_bias || !v_bias || !ctx || !row0 || n <= 0 || n > 65535 || max_T_sub <= 0 || (dt != DT_F32 && dt != DT_BF16))
+        return hipErrorInvalidValue;
+    if (ldq < 3 * CF_D || ldp < CF_D || ldc < CF_D) return hipErrorInvalidValue;
+    if (dt == DT_BF16) return attn_launch<bf16_t, true>(qkv, ldq, P, ldp, u_bias, v_bias, ctx, ldc, n, max_T_sub, row0, stream);
+    return attn_launch<float, true>(qkv, ldq, P, ldp, u_bias, v_bias, ctx, ldc, n, max_T_sub, row0, stream);
 }
 
 }  // namespace svhip

@@ -192,6 +192,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
         for (int i = 0; i < 4; ++i) {
             const int u = rowA[i] / p.seg_rows;
             segbase[i] = (int64_t)u * p.seg_utt + p.seg_off[rowA[i] - u * p.seg_rows];
+            // a pack: u is the packed frame of the row and the frame's utterance adds its own offset (GemmParams::seg_u0)
+            if (RAG) segbase[i] += (int64_t)(p.rag_utt[u] - p.seg_u0) * p.seg_stride;
         }
     }
     int64_t wrow[4];
@@ -397,6 +399,10 @@ hipError_t launch_t(const GemmParams& p, hipStream_t stream) {
 // ECAPA's asp.tdnn: ReLU -> BN -> tanh, RawNet3's attention.0 -> attention.2: ReLU -> BN)
 template <typename T>
 hipError_t launch_rag_t(const GemmParams& p, hipStream_t stream) {
+    if (p.seg_off) {          // Conformer's subsampling conv over a pack: launch_t's segmented instance with the per-utterance offset
+        if (p.act1 != ACT_RELU || p.act2 != ACT_NONE || p.taps != 1 || p.A2 || p.bias_utt) return hipErrorInvalidValue;
+        return launch_inst_x<T, false, false, EPI_RELU, false, true, true>(p, stream);
+    }
     if (p.taps > 1) {
         if (p.act2 != ACT_NONE) return hipErrorInvalidValue;
         if (p.act1 == ACT_GELU && !p.A2) return launch_inst_x<T, true, false, EPI_GELU, false, false, true>(p, stream);
@@ -416,13 +422,15 @@ hipError_t launch_gemm_ragged(const GemmParams& p, bool bf16, hipStream_t stream
     const int bk = gemm_bk(bf16);
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.Kp % bk != 0 || p.Kp < p.K || p.Wrows < p.N) return hipErrorInvalidValue;
     if (p.lda % epc != 0 || (p.A2 && p.lda2 % epc != 0)) return hipErrorInvalidValue;
-    if (p.x3 || p.f16 || p.seg_off || p.A3 || p.colsum || p.y_s32 || p.side_c) return hipErrorInvalidValue;
+    if (p.x3 || p.f16 || p.A3 || p.colsum || p.y_s32 || p.side_c) return hipErrorInvalidValue;
     if (p.taps > 1) {
         if (p.cin % epc != 0 || p.taps * p.cin != p.K) return hipErrorInvalidValue;
     } else if (p.K % epc != 0) {
         return hipErrorInvalidValue;
     }
-    if (p.taps > 1 || p.bias_utt) {          // (what needs the segment table; the caller has checked (taps / 2) dil < T_u for every utterance)
+    if (p.seg_off && (p.seg_rows <= 0 || p.seg_len <= 0 || p.seg_len % epc != 0 || p.K % p.seg_len != 0 || p.seg_utt % epc != 0 ||
+                      p.seg_stride % epc != 0)) return hipErrorInvalidValue;
+    if (p.taps > 1 || p.bias_utt || p.seg_off) {          // (what needs the segment table; the caller has checked (taps / 2) dil < T_u for every utterance)
         if (!p.rag_utt || !p.rag_row0) return hipErrorInvalidValue;
         return bf16 ? launch_rag_t<bf16_t>(p, stream) : launch_rag_t<float>(p, stream);
     }

@@ -125,6 +125,7 @@ struct svhip_handle {
     float* d_emb = nullptr;
     int lastB = 0;
     int64_t rag_rows = 0;                     // rows of the last forward when it was a ragged one (svhip_get_stage), else 0
+    int64_t rag_in_rows = 0;                  // ... and its mel frames where they are not those rows (Conformer: rag_rows counts subsampled frames)
     // shared by several models: each is allocated by the alloc / finalize hook of the models named, and null on the others' handles
     void* X_in = nullptr;         // (M, n_mels): the network input (ECAPA, TitaNet, Conformer; svhip_get_stage "input")
     float *in_w = nullptr, *in_b = nullptr;   // instance norm affine (ECAPA, Conformer)
@@ -316,6 +317,9 @@ int ecapa_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_w
 // a ragged RawNet3 pack: utterance u is lengths[u] samples at in + in_off[u] (a device waveform array, or with in_host a host one)
 int rawnet3_ragged_check(const svhip_config& c, const int32_t* lengths, int n, std::string& err);
 int rawnet3_embed_ragged(svhip_handle* h, const float* in, bool in_host, const int64_t* in_off, const int32_t* lengths, int n);
+// a ragged Conformer pack: ecapa_embed_ragged's arguments (lengths in samples, wave, or mel frames)
+int conformer_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err);
+int conformer_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n);
 EmbedFn ecapa_forward, titanet_forward, conformer_forward, resnetse_forward;   // from the mel power
 StageFn ecapa_stage, rawnet2_stage, rawnet3_stage, titanet_stage, conformer_stage, resnetse_stage;
 

@@ -98,6 +98,10 @@ struct GemmParams {
     const int* seg_off = nullptr;
     int seg_rows = 0, seg_len = 0;
     int64_t seg_utt = 0, seg_stride = 0;
+    // ... over a ragged batch (launch_gemm_ragged with rag_utt): m / seg_rows is a packed frame m' instead of an utterance, and the
+    // frame's utterance shifts the row by whole runs:  A'[m, k] = A[m' * seg_utt + (rag_utt[m'] - seg_u0) * seg_stride +
+    // seg_off[m % seg_rows] + (k / seg_len) * seg_stride + k % seg_len]  (Conformer: utterance u's conv1 rows start at 2 row0[u] + u)
+    int seg_u0 = 0;
     // ragged batch (the generic kernel only, through launch_gemm_ragged): utterance u owns the rows [rag_row0[u], rag_row0[u + 1]) and
     // rag_utt[m] is the utterance of row m.  The conv gather reflects at each utterance's own ends and bias_utt is read at rag_utt[m];
     // T is not used.  Null (the default): every utterance has T rows.
@@ -186,8 +190,9 @@ hipError_t launch_rag_colstats(const void* X, bool bf16, int ldx, const int* row
 hipError_t launch_rag_se_apply(const void* h, int ldh, const float* s, const void* x, int ldx, void* out, int ldo, bool bf16,
                                const int* utt, int M, int C, hipStream_t stream);
 // launch_asp_pool's arithmetic over each utterance's own frames
+// (var_max > 0: the variance is also clamped above, as launch_asp_pool's — the Conformer's clamp(1e-4, 1e4))
 hipError_t launch_rag_asp_pool(const float* logits, const void* X, bool bf16, int ldx, const int* row0, int n, int C, const float* bn_scale,
-                               const float* bn_shift, float* pooled_raw, float* pooled_bn, float eps, hipStream_t stream);
+                               const float* bn_shift, float* pooled_raw, float* pooled_bn, float eps, hipStream_t stream, float var_max = 0.0f);
 // launch_rowvec_linear on ONE kernel at every batch size (a row's sum does not depend on how many rows ride along)
 hipError_t launch_rag_linear(const float* in, int ld_in, const float* W, const float* bias, float* out, int ld_out, int n, int N, int K,
                              int act, hipStream_t stream);
@@ -470,6 +475,9 @@ hipError_t launch_tn_mega_tail(const void* skip, const void* h3, const float* ga
 
 // rows[b, 0:n) (row stride ld) = NaN for every utterance b whose input x[b * per_utt .. (b + 1) * per_utt) holds an inf / NaN
 hipError_t launch_tn_nonfinite_rows(const float* x, int64_t per_utt, int B, float* rows, int ld, int n, hipStream_t stream);
+// the same over a pack: utterance b is the (row0[b + 1] - row0[b]) * per_row values at x + off[b] (off, row0: device tables)
+hipError_t launch_tn_nonfinite_rows_ragged(const float* x, const int64_t* off, const int* row0, int per_row, int B, float* rows, int ld, int n,
+                                           hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // Conformer (conformer.hip): d_model = 256, frame-major (B T', 256) activations, fp32 or bf16 storage (dt), 16-byte aligned pointers.
@@ -477,16 +485,28 @@ hipError_t launch_tn_nonfinite_rows(const float* x, int64_t per_utt, int B, floa
 // Conv2d(1, 256, 3, stride 2) + ReLU over the (T, F) image of each utterance (x: (B T, F)): y (B, T1, F1, 256), T1 = (T - 3) / 2 + 1,
 // F1 = (F - 3) / 2 + 1; w tap-major [9][256] fp32 (tap = 3 dt + df), bias [256]
 hipError_t launch_cf_conv1(const void* x, const float* w, const float* bias, void* y, int dt, int B, int Tn, int F, hipStream_t stream);
+// ... over the utterances [u0, u0 + n) of a pack: utterance u's mel rows start at row mel0[u] of x (packed (sum T_u, F)); row0 is the
+// table of the SUBSAMPLED level (T'_u = row0[u + 1] - row0[u]).  Only the 2 T'_u + 1 conv1 rows conv2 reads are written, utterance u's at
+// conv1 row 2 (row0[u] - row0[u0]) + (u - u0) of y; max_T_sub >= every T'_u of the slice
+hipError_t launch_cf_conv1_ragged(const void* x, const float* w, const float* bias, void* y, int dt, const int* mel0, const int* row0, int u0,
+                                  int n, int max_T_sub, int F, hipStream_t stream);
 // y = LayerNorm(x) (g1, b1; eps 1e-5, fp32 statistics); with y2 != null also y2 = LayerNorm(y as stored) (g2, b2)
 hipError_t launch_cf_ln(const void* x, void* y, const float* g1, const float* b1, void* y2, const float* g2, const float* b2, int dt, int64_t M,
                         hipStream_t stream);
 // u (B T', 512) -> y (B T', 256) = swish(dw15(u[:, :256] * sigmoid(u[:, 256:])) + bias), zero padding 7 per utterance;
 // w tap-major [15][256] fp32 with the BatchNorm scale folded in, bias = the BatchNorm shift
 hipError_t launch_cf_glu_dw(const void* u, const float* w, const float* bias, void* y, int dt, int B, int Tn, hipStream_t stream);
+// ... over a pack (row0: n + 1 device ints, max_T_sub >= every T'_u): the zero padding sits at each utterance's own edges
+hipError_t launch_cf_glu_dw_ragged(const void* u, const float* w, const float* bias, void* y, int dt, const int* row0, int n, int max_T_sub,
+                                   hipStream_t stream);
 // relative-position self-attention, 4 heads of 64: qkv (B T', ldq) holds q | k | v in columns [0, 768); P (T', ldp) fp32 = pe[:T'] W_pos^T;
 // u_bias, v_bias [4][64] fp32; ctx (B T', ldc) = the heads' contexts concatenated (before out_proj).  Any T' >= 1.
 hipError_t launch_cf_attn(const void* qkv, int ldq, const float* P, int ldp, const float* u_bias, const float* v_bias, void* ctx, int ldc, int dt,
                           int B, int Tn, hipStream_t stream);
+// ... over a pack: utterance u owns the rows [row0[u], row0[u + 1]) of qkv and ctx (row0: n + 1 device ints) and is attended exactly as
+// launch_cf_attn attends it alone (B = 1, Tn = T'_u), bit for bit; P holds at least max_T_sub >= every T'_u rows
+hipError_t launch_cf_attn_ragged(const void* qkv, int ldq, const float* P, int ldp, const float* u_bias, const float* v_bias, void* ctx, int ldc,
+                                 int dt, const int* row0, int n, int max_T_sub, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // ResNetSE (resnetse.hip): channels-last (B, P, Q, C) activations — P frames, Q mel rows — fp32 or bf16 storage (dt), 16-byte aligned.

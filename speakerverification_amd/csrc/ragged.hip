@@ -196,7 +196,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void rag_asp_pool_kernel(const float* __restrict__ logits, const T* __restrict__ X, int ldx,
                                                            const int* __restrict__ row0, int C, const float* __restrict__ bn_scale,
                                                            const float* __restrict__ bn_shift, float* __restrict__ pooled_raw,
-                                                           float* __restrict__ pooled_bn, float eps) {
+                                                           float* __restrict__ pooled_bn, float eps, float var_max) {
     __shared__ float smx[4][64], sse[4][64], smean[4][64], sm2[4][64];
     const int b = blockIdx.y;
     const int r0 = row0[b], Tn = row0[b + 1] - r0;
@@ -249,7 +249,9 @@ __global__ __launch_bounds__(256) void rag_asp_pool_kernel(const float* __restri
                 SE = tot;
             }
         }
-        const float sd = sqrtf(fmaxf(M2 / SE, eps));
+        float var = fmaxf(M2 / SE, eps);
+        if (var_max > 0.0f && var > var_max) var = var_max;      // (Conformer: clamp(min = 1e-4, max = 1e4))
+        const float sd = sqrtf(var);
         if (pooled_raw) {
             pooled_raw[(int64_t)b * 2 * C + c] = MEAN;
             pooled_raw[(int64_t)b * 2 * C + C + c] = sd;
@@ -368,11 +370,11 @@ hipError_t launch_rag_se_apply(const void* h, int ldh, const float* s, const voi
 }
 
 hipError_t launch_rag_asp_pool(const float* logits, const void* X, bool bf16, int ldx, const int* row0, int n, int C, const float* bn_scale,
-                               const float* bn_shift, float* pooled_raw, float* pooled_bn, float eps, hipStream_t stream) {
+                               const float* bn_shift, float* pooled_raw, float* pooled_bn, float eps, hipStream_t stream, float var_max) {
     if (!logits || !X || !row0 || !bn_scale || !bn_shift || !pooled_bn || n <= 0 || C <= 0) return hipErrorInvalidValue;
     const dim3 grid((C + 63) / 64, n), block(256);
-    if (bf16) hipLaunchKernelGGL(rag_asp_pool_kernel<bf16_t>, grid, block, 0, stream, logits, (const bf16_t*)X, ldx, row0, C, bn_scale, bn_shift, pooled_raw, pooled_bn, eps);
-    else hipLaunchKernelGGL(rag_asp_pool_kernel<float>, grid, block, 0, stream, logits, (const float*)X, ldx, row0, C, bn_scale, bn_shift, pooled_raw, pooled_bn, eps);
+    if (bf16) hipLaunchKernelGGL(rag_asp_pool_kernel<bf16_t>, grid, block, 0, stream, logits, (const bf16_t*)X, ldx, row0, C, bn_scale, bn_shift, pooled_raw, pooled_bn, eps, var_max);
+    else hipLaunchKernelGGL(rag_asp_pool_kernel<float>, grid, block, 0, stream, logits, (const float*)X, ldx, row0, C, bn_scale, bn_shift, pooled_raw, pooled_bn, eps, var_max);
     return hipGetLastError();
 }
 

@@ -294,19 +294,27 @@ class Engine:
     def embed_wave_ragged(self, wavs, offsets=None, lengths=None, out=None, async_=False, ordered=False):
         """utterances of different lengths -> (n, embed_dim), each as if forwarded alone at its own length.  ``wavs``: a list of 1-D
         arrays, or ONE packed array with ``offsets`` / ``lengths`` in samples; numpy or CUDA tensors, like embed_wave.  A RawNet3
-        handle takes the pack through svhip_rawnet3_embed_ragged."""
-        fn = self.lib.svhip_rawnet3_embed_ragged if self.model == "rawnet3" else self.lib.svhip_embed_wave_ragged
+        handle takes the pack through svhip_rawnet3_embed_ragged, a Conformer handle through svhip_conformer_embed_ragged."""
+        fn = (self.lib.svhip_rawnet3_embed_ragged if self.model == "rawnet3" else
+              self._conformer_ragged(1) if self.model == "conformer" else self.lib.svhip_embed_wave_ragged)
         return self._embed_ragged(fn, wavs, offsets, lengths, out, async_, True, ordered)
+
+    def _conformer_ragged(self, is_wave):
+        """svhip_conformer_embed_ragged with the call shape of the two ECAPA exports"""
+        return lambda *args: self.lib.svhip_conformer_embed_ragged(*args, is_wave)
 
     def embed_features_ragged(self, feats, offsets=None, lengths=None, out=None, async_=False):
         """``feats``: a list of (n_mels, T_i) mel-power arrays, or one packed array of such blocks with frame ``offsets`` / ``lengths``."""
-        return self._embed_ragged(self.lib.svhip_embed_features_ragged, feats, offsets, lengths, out, async_, False)
+        fn = self._conformer_ragged(0) if self.model == "conformer" else self.lib.svhip_embed_features_ragged
+        return self._embed_ragged(fn, feats, offsets, lengths, out, async_, False)
 
     def ragged_check(self, lengths, is_wave=True):
         """the library's own capacity test for a pack (svhip_ragged_check, host only): None, or the refusal's text"""
         lens = np.ascontiguousarray(lengths, dtype=np.int32)
         if self.model == "rawnet3":
             rc = self.lib.svhip_rawnet3_ragged_check(C.byref(self.cfg), lens.ctypes.data, int(lens.shape[0]))
+        elif self.model == "conformer":
+            rc = self.lib.svhip_conformer_ragged_check(C.byref(self.cfg), lens.ctypes.data, int(lens.shape[0]), 1 if is_wave else 0)
         else:
             rc = self.lib.svhip_ragged_check(C.byref(self.cfg), lens.ctypes.data, int(lens.shape[0]), 1 if is_wave else 0)
         return None if rc == _lib.OK else (self.lib.svhip_last_error(None) or b"?").decode()

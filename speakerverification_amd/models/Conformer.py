@@ -10,6 +10,7 @@ the reference.  Six Conformer blocks (d_model 256, 4 heads, relative positions w
 pooling with the variance clamped to [1e-4, 1e4], attention_norm and fc.  State-dict keys are the reference's (asp.* / asp_bn.* are
 loaded and ignored, as the reference never calls them).  Computes: "f32" and "bf16" ("half" means bf16 here).  Lengths: L >= 512
 samples (the library's front-end; the reference needs T >= 7 frames) and T' <= 10000 (the positional-encoding buffer).
+``embed_ragged`` embeds utterances of different lengths in shared calls of the primary handle (whole-file evaluation).
 SpecAugment (``augment=True`` with 'spec_domain') is not built.
 """
 from __future__ import annotations
@@ -18,6 +19,23 @@ from .. import synth
 from ._base import HipModule
 
 MIN_SAMPLES = 512           # the mel front-end's n_fft (one frame of the library's front-end)
+
+
+def slice_frames(max_batch, frames, n_mels, compute):
+    """subsampled frames one subsampling slice of a handle of `frames` mel frames holds (csrc/api_conformer.hip: cf_chunk utterances
+    of the handle's own T'): the longest utterance a ragged call of that handle takes"""
+    sub = lambda n: (n - 3) // 2 + 1
+    per_utt = sub(frames) * sub(n_mels) * synth.CONFORMER_D * (2 if compute == "bf16" else 4)      # conv1 output bytes of one utterance
+    return max(1, min(int(max_batch), (256 << 20) // per_utt)) * synth.conformer_frames(frames)
+
+
+def ragged_frames_of(n_samples, hop, n_fft, slice_limit):
+    """mel frames of an utterance of n_samples, or 0 when it fits no ragged call: shorter than one FFT window or 7 frames, more than
+    10000 subsampled frames, or more of them than one subsampling slice holds"""
+    if n_samples < n_fft:
+        return 0
+    T = int(n_samples) // int(hop) + 1
+    return T if 1 <= synth.conformer_frames(T) <= min(synth.CONFORMER_MAX_T, slice_limit) else 0
 
 
 def _crop_samples(audio_spec):
@@ -86,6 +104,47 @@ class Conformer(HipModule):
         """fused waveform -> embedding (mel front-end + forward in one library call)"""
         eng = self._engine_for(wav)
         return self._squeeze(self._batched(eng.embed_wave, wav, eng.max_batch))
+
+    # ---- ragged batches: utterances of different lengths on the PRIMARY handle (whole-file evaluation) ----------------
+    DEFAULT_PRIMARY = 32000         # the primary geometry when no audio_spec names one: the reference's 2 s crop at 16 kHz
+    MIN_FRAMES = 7                  # T' = (T - 3) // 4 >= 1
+
+    def ragged_engine(self):
+        """the handle with the full max_batch workspace: its mel rows are the capacity of a ragged call"""
+        return self._get_engine(self._primary or self.DEFAULT_PRIMARY)
+
+    def _ragged_geometry(self):
+        """(max_batch, row capacity, slice limit) of the primary handle, from the module's own settings (no handle is built)"""
+        frames = (self._primary or self.DEFAULT_PRIMARY) // self._hop + 1
+        return self._max_batch, self._max_batch * frames, slice_frames(self._max_batch, frames, self.n_mels, self._compute)
+
+    def ragged_packer(self):
+        from ..ragged import RaggedPacker
+        mb, cap, _ = self._ragged_geometry()
+        return RaggedPacker(mb, cap, min_frames=self.MIN_FRAMES)
+
+    def ragged_frames(self, n_samples):
+        """mel frames of an utterance of n_samples; 0 for one that fits no ragged call (ragged_frames_of)"""
+        return ragged_frames_of(n_samples, self._hop, self._min_samples, self._ragged_geometry()[2])
+
+    def embed_ragged(self, wavs):
+        """list of 1-D waveforms of any lengths -> (n, nOut), each embedded as if alone at its own length, in as few library calls
+        as the primary handle's capacity allows (ragged.plan_ragged).  Raises ValueError for utterances that fit no call: the
+        caller embeds those through embed_wave, which builds a handle for their length."""
+        from ..ragged import plan_ragged
+        mb, cap, _ = self._ragged_geometry()
+        calls, alone = plan_ragged([self.ragged_frames(w.shape[-1]) for w in wavs], mb, cap, min_frames=self.MIN_FRAMES)
+        if alone:
+            raise ValueError(f"utterances {alone[:8]} fit no ragged call of this handle ({cap} frames; at least {self._min_samples} "
+                             f"samples and 7 frames each, at most {self._ragged_geometry()[2]} subsampled frames)")
+        eng = self.ragged_engine()
+        outs = [eng.embed_wave_ragged([wavs[i].reshape(-1) for i in call]) for call in calls]
+        if len(outs) == 1:
+            return outs[0]
+        import numpy as np
+        from ..engine import _is_torch
+        import torch
+        return torch.cat(outs, 0) if _is_torch(outs[0]) else np.concatenate(outs, 0)
 
 
 def MainModel(nOut=512, **kwargs):

@@ -1,6 +1,6 @@
 """Whole-file evaluation (num_eval = 0) on the MI355X: files/s of `ModelHandling._embed_files` over seeded files of 2 - 20 s.
 
-    python tools/ragged_bench.py [--model ECAPA_TDNN|RawNet3|Raw3_ECAPA] [--per-file] [--files 512] [--runs 5] [--compute bf16,f32]
+    python tools/ragged_bench.py [--model ECAPA_TDNN|RawNet3|Raw3_ECAPA|Conformer] [--per-file] [--files 512] [--runs 5] [--compute bf16,f32]
                                  [--out profiles/ragged_bench.json]
 
 Default mode: the ragged path of this tree (files of different lengths share calls of the model's primary handle), plus, without a
@@ -13,7 +13,8 @@ parent commit (put that checkout first on PYTHONPATH), whose files/s are the yar
 Own process; every figure is the median of `--runs` timed passes over the whole file list (after one untimed pass), with the spread
 (min, max); wall time and HIP-event time around the whole pass are both given.  ECAPA-TDNN C = 1024, nOut 192; with --model RawNet3
 (nOut 320) or Raw3_ECAPA (nOut 512, the model of the reference's default configs: ECAPA-TDNN C = 512 + RawNet3), `features: raw`,
-written to profiles/rawnet3_ragged_bench.json by convention.  The single-call comparison and the kernel table are ECAPA-TDNN's."""
+written to profiles/rawnet3_ragged_bench.json by convention; --model Conformer (nOut 512, the model of yaml/model_plot.yaml, mel features)
+to profiles/conformer_ragged_bench.json.  The single-call comparison and the kernel table are given for ECAPA-TDNN and the Conformer."""
 from __future__ import annotations
 
 import argparse
@@ -49,12 +50,15 @@ def make_files(n):
     return [np.clip(0.1 * rng.standard_normal(int(L), dtype=np.float32), -1.0, 1.0) for L in lens]
 
 
-MODELS = {"ECAPA_TDNN": "ECAPA_TDNN C=1024 nOut=192", "RawNet3": "RawNet3 nOut=320", "Raw3_ECAPA": "Raw3_ECAPA nOut=512 (ECAPA-TDNN C=512 + RawNet3)"}
+MODELS = {"ECAPA_TDNN": "ECAPA_TDNN C=1024 nOut=192", "RawNet3": "RawNet3 nOut=320", "Raw3_ECAPA": "Raw3_ECAPA nOut=512 (ECAPA-TDNN C=512 + RawNet3)",
+          "Conformer": "Conformer nOut=512"}
 
 
 def state_dict(model):
     if model == "ECAPA_TDNN":
         return synth.synth_state_dict(synth.ecapa_param_spec(C=1024), seed=5)
+    if model == "Conformer":
+        return synth.synth_state_dict(synth.conformer_param_spec(512, 80), seed=5)
     rn3 = synth.synth_state_dict(synth.rawnet3_param_spec(nOut=320), seed=5)
     if model == "RawNet3":
         return rn3
@@ -65,7 +69,10 @@ def state_dict(model):
 
 def handler(compute, per_file, model="ECAPA_TDNN"):
     kw = dict(ARGS, hip_compute=compute)
-    if model != "ECAPA_TDNN":
+    if model == "Conformer":
+        kw.update(model={"name": model, "nOut": 512})
+        kw.pop("channels")
+    elif model != "ECAPA_TDNN":
         kw.update(model={"name": model, "nOut": 320 if model == "RawNet3" else 512}, features="raw")
         kw.pop("channels")
     net = WrappedModel(SpeakerEncoder(**kw))
@@ -128,7 +135,7 @@ def main():
         r = {"wall_s": stats(wall), "hip_event_s": stats(dev),
              "files_per_s": {"median": a.files / float(np.median(wall)), "min": a.files / max(wall), "max": a.files / min(wall)},
              "frames_per_s": frames / float(np.median(wall)), "engines_alive": engines_alive(S)}
-        if not a.per_file and a.model == "ECAPA_TDNN":
+        if not a.per_file and a.model in ("ECAPA_TDNN", "Conformer"):
             eng = S.ragged_engine()
             # the ragged call against the fixed-length call of the same handle, device-resident input, frames/s of each
             x = torch.from_numpy(synth.synth_waveforms(eng.max_batch, eng.samples, seed=1)).cuda()
