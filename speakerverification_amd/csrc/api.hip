@@ -1,7 +1,7 @@
 // api.hip — C ABI of libsvhip: handle lifetime, developer options, weight loading, embedding, staging, stages and profiling
 // (see include/svhip.h).  The handle is in handle.h; what the models share when weights are loaded in api_weights.hip, the conv-layer
-// GEMM in api_gemm.hip, each model's own host code and state in its api_<model>.hip (kModels below lists them), scoring and metrics in
-// api_scoring.hip.
+// GEMM in api_gemm.hip, what the ragged calls share in api_ragged.hip, each model's own host code and state in its api_<model>.hip
+// (kModels below lists them), scoring and metrics in api_scoring.hip.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -9,6 +9,11 @@
 #include "handle.h"
 
 using namespace svhip;
+
+namespace svhip {      // the ragged hooks of the models that have them: only kModels names them
+RaggedCheckFn ecapa_ragged_check, rawnet3_ragged_check, conformer_ragged_check;
+RaggedEmbedFn ecapa_embed_ragged, rawnet3_embed_ragged, conformer_embed_ragged;          // (RawNet3: waveforms only, is_wave is true)
+}
 
 namespace {
 
@@ -59,14 +64,17 @@ int fbank_then_features(svhip_handle* h, const float* d_wav, int B);
 // The models, one row per model id.  The three RawNet2 models share their functions (front_proc / aggregate follow cfg.model).
 const ModelOps kModels[] = {
     // model                   check            spec            finalize            alloc            embed_wave           embed_feat         stage            lanes
-    {SVHIP_MODEL_ECAPA,        ecapa_check,     ecapa_spec,     ecapa_finalize,     ecapa_alloc,     ecapa_embed_wave,    ecapa_forward,     ecapa_stage,     2},
+    {SVHIP_MODEL_ECAPA,        ecapa_check,     ecapa_spec,     ecapa_finalize,     ecapa_alloc,     ecapa_embed_wave,    ecapa_forward,     ecapa_stage,     2,
+     nullptr, ecapa_ragged_check, ecapa_embed_ragged},
     {SVHIP_MODEL_RAWNET2,      rawnet2_check,   rawnet2_spec,   rawnet2_finalize,   rawnet2_alloc,   rawnet2_forward,     nullptr,           rawnet2_stage,   4},
     {SVHIP_MODEL_RAWNET2_CONV, rawnet2_check,   rawnet2_spec,   rawnet2_finalize,   rawnet2_alloc,   rawnet2_forward,     nullptr,           rawnet2_stage,   4},
     {SVHIP_MODEL_RAWNET2_GRU,  rawnet2_check,   rawnet2_spec,   rawnet2_finalize,   rawnet2_alloc,   rawnet2_forward,     nullptr,           rawnet2_stage,   4},
-    {SVHIP_MODEL_RAWNET3,      rawnet3_check,   rawnet3_spec,   rawnet3_finalize,   rawnet3_alloc,   rawnet3_forward,     nullptr,           rawnet3_stage,   4},
+    {SVHIP_MODEL_RAWNET3,      rawnet3_check,   rawnet3_spec,   rawnet3_finalize,   rawnet3_alloc,   rawnet3_forward,     nullptr,           rawnet3_stage,   4,
+     nullptr, rawnet3_ragged_check, rawnet3_embed_ragged},
     {SVHIP_MODEL_TITANET,      titanet_check,   titanet_spec,   titanet_finalize,   titanet_alloc,   fbank_then_features, titanet_forward,   titanet_stage,   4,
      "encoder.mega_blocks."},       // (the block count follows from what was loaded: titanet_finalize checks its blocks)
-    {SVHIP_MODEL_CONFORMER,    conformer_check, conformer_spec, conformer_finalize, conformer_alloc, fbank_then_features, conformer_forward, conformer_stage, 4},
+    {SVHIP_MODEL_CONFORMER,    conformer_check, conformer_spec, conformer_finalize, conformer_alloc, fbank_then_features, conformer_forward, conformer_stage, 4,
+     nullptr, conformer_ragged_check, conformer_embed_ragged},
     {SVHIP_MODEL_RESNETSE,     resnetse_check,  resnetse_spec,  resnetse_finalize,  resnetse_alloc,  fbank_then_features, resnetse_forward,  resnetse_stage,  4},
     {SVHIP_MODEL_NONE,         none_check,      nullptr,        nullptr,            nullptr,         nullptr,             nullptr,           nullptr,         1},   // fbank + scoring
 };
@@ -139,7 +147,7 @@ int forward_lanes(svhip_handle* h, ForwardPart part, const float* in, int B, int
         h->cur = h->stream;
         rc = part(h, in, 0, B);
     }
-    if (!rc) { h->lastB = B; h->rag_rows = 0; }
+    if (!rc) { h->lastB = B; h->rag_levels = 0; }
     return rc;
 }
 
@@ -197,6 +205,53 @@ int emit_embeddings(svhip_handle* h, int B, float* emb_out, int flags) {
     if (rc) return rc;
     if (!(flags & SVHIP_OUT_DEVICE)) SV_HIP(h, hipMemcpyAsync(emb_out, h->d_emb, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     return SVHIP_OK;
+}
+
+// ---- ragged calls: utterances of different lengths in one call --------------------------------------------------
+// Each ragged export serves one model (kModels names its check and its forward) and refuses the others by its name
+struct RaggedExport { int model; const char* name; };
+constexpr RaggedExport kRagEcapa{SVHIP_MODEL_ECAPA, "ECAPA"}, kRagRawnet3{SVHIP_MODEL_RAWNET3, "RAWNET3"},
+                       kRagConformer{SVHIP_MODEL_CONFORMER, "CONFORMER"};
+
+// the rules of a pack, on the host alone, in this order: the scope, the model's rules on the configuration, the pack size, the model's
+// rules on every utterance in index order
+int ragged_rules(const RaggedExport& x, const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
+    if (c.model != x.model)
+        return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: SVHIP_MODEL_%s only (ECAPA, RawNet3 and Conformer packs have their own calls; the "
+                      "other models embed one length per handle)", x.name, x.name);
+    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16)
+        return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: compute SVHIP_F32 or SVHIP_BF16 only", x.name);
+    // The pack size is tested between the model's two kinds of rules, as it always was, so that the first failing rule stays the same
+    // one.  A RaggedCheckFn looks at no utterance when it is given n = 0, so the first call is its rules on the configuration alone
+    // (they also make max_batch and the divisions of the second call safe); the second adds every utterance in index order.
+    RaggedCheckFn* check = model_ops(x.model)->ragged_check;
+    if (int rc = check(c, lengths, 0, is_wave, err)) return rc;
+    if (n < 1 || n > c.max_batch) return refuse(err, SVHIP_ERR_INVALID, "ragged batch of %d utterances outside [1, max_batch=%d]", n, c.max_batch);
+    return check(c, lengths, n, is_wave, err);
+}
+
+int ragged_check(const RaggedExport& x, const svhip_config* cfg, const int32_t* lengths, int32_t n, bool is_wave) {
+    if (!cfg || cfg->struct_size != (int32_t)sizeof(svhip_config)) { g_create_error = "bad config / struct_size"; return SVHIP_ERR_INVALID; }
+    if (!lengths) { g_create_error = "null pointer"; return SVHIP_ERR_INVALID; }
+    return ragged_rules(x, *cfg, lengths, n, is_wave, g_create_error);
+}
+
+// argument and capacity checks on the host, then the model's ragged forward
+int embed_ragged(const RaggedExport& x, svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
+                 int32_t flags, bool is_wave) {
+    if (!h) return SVHIP_ERR_INVALID;
+    if (!h->finalized) SV_FAIL(h, SVHIP_ERR_STATE, "weights not finalized (call svhip_finalize_weights first)");
+    if (!in || !offsets || !lengths || !emb_out) SV_FAIL(h, SVHIP_ERR_INVALID, "null pointer");
+    if (int rc = ragged_rules(x, h->cfg, lengths, n, is_wave, h->err)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (offsets[i] < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance %d: negative offset (the limit is 0)", i);
+    if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
+        SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    int rc = model_ops(x.model)->embed_ragged(h, in, !(flags & SVHIP_IN_DEVICE), is_wave, offsets, lengths, n);
+    if (rc) return rc;
+    if ((rc = emit_embeddings(h, n, emb_out, flags))) return rc;
+    return finish(h, flags);
 }
 
 }  // namespace
@@ -295,7 +350,7 @@ int svhip_destroy(svhip_handle* h) {
     if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
     for (hipEvent_t e : h->aux_ev) if (e) (void)hipEventDestroy(e);
     for (void* q : h->scr) if (q) (void)hipFree(q);
-    h->model.reset();          // (ECAPA's and RawNet3's release the pinned slots and events of their ragged calls)
+    h->model.reset();          // (a model with ragged calls releases the pinned slots and events of its RagTables)
     for (auto& sl : h->crop_slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.dev) (void)hipFree(sl.dev);
@@ -446,96 +501,36 @@ int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, fl
     return finish(h, flags);
 }
 
-// the two ragged calls: argument and capacity checks on the host, then the model's ragged forward
-static int embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out, int32_t flags,
-                        bool is_wave) {
-    if (!h) return SVHIP_ERR_INVALID;
-    if (!h->finalized) SV_FAIL(h, SVHIP_ERR_STATE, "weights not finalized (call svhip_finalize_weights first)");
-    if (!in || !offsets || !lengths || !emb_out) SV_FAIL(h, SVHIP_ERR_INVALID, "null pointer");
-    std::string msg;
-    if (int rc = ecapa_ragged_check(h->cfg, lengths, n, is_wave, msg)) SV_FAIL(h, rc, "%s", msg.c_str());
-    for (int i = 0; i < n; ++i)
-        if (offsets[i] < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance %d: negative offset", i);
-    if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
-        SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
-    SV_HIP(h, hipSetDevice(h->cfg.device));
-    int rc = ecapa_embed_ragged(h, in, !(flags & SVHIP_IN_DEVICE), is_wave, offsets, lengths, n);
-    if (rc) return rc;
-    if ((rc = emit_embeddings(h, n, emb_out, flags))) return rc;
-    return finish(h, flags);
-}
-
 int svhip_embed_wave_ragged(svhip_handle* h, const float* wav, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
                             int32_t flags) {
-    return embed_ragged(h, wav, offsets, lengths, n, emb_out, flags, true);
+    return embed_ragged(kRagEcapa, h, wav, offsets, lengths, n, emb_out, flags, true);
 }
 
 int svhip_embed_features_ragged(svhip_handle* h, const float* feat, const int64_t* frame_offsets, const int32_t* frames, int32_t n,
                                 float* emb_out, int32_t flags) {
-    return embed_ragged(h, feat, frame_offsets, frames, n, emb_out, flags, false);
+    return embed_ragged(kRagEcapa, h, feat, frame_offsets, frames, n, emb_out, flags, false);
 }
 
 int svhip_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave) {
-    if (!cfg || cfg->struct_size != (int32_t)sizeof(svhip_config)) { g_create_error = "bad config / struct_size"; return SVHIP_ERR_INVALID; }
-    if (!lengths) { g_create_error = "null pointer"; return SVHIP_ERR_INVALID; }
-    std::string msg;
-    const int rc = ecapa_ragged_check(*cfg, lengths, n, is_wave != 0, msg);
-    if (rc) g_create_error = msg;
-    return rc;
+    return ragged_check(kRagEcapa, cfg, lengths, n, is_wave != 0);
 }
 
 int svhip_rawnet3_embed_ragged(svhip_handle* h, const float* wav, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
                                int32_t flags) {
-    if (!h) return SVHIP_ERR_INVALID;
-    if (!h->finalized) SV_FAIL(h, SVHIP_ERR_STATE, "weights not finalized (call svhip_finalize_weights first)");
-    if (!wav || !offsets || !lengths || !emb_out) SV_FAIL(h, SVHIP_ERR_INVALID, "null pointer");
-    std::string msg;
-    if (int rc = rawnet3_ragged_check(h->cfg, lengths, n, msg)) SV_FAIL(h, rc, "%s", msg.c_str());
-    for (int i = 0; i < n; ++i)
-        if (offsets[i] < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance %d: negative offset (the limit is 0)", i);
-    if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
-        SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
-    SV_HIP(h, hipSetDevice(h->cfg.device));
-    int rc = rawnet3_embed_ragged(h, wav, !(flags & SVHIP_IN_DEVICE), offsets, lengths, n);
-    if (rc) return rc;
-    if ((rc = emit_embeddings(h, n, emb_out, flags))) return rc;
-    return finish(h, flags);
+    return embed_ragged(kRagRawnet3, h, wav, offsets, lengths, n, emb_out, flags, true);
 }
 
 int svhip_rawnet3_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n) {
-    if (!cfg || cfg->struct_size != (int32_t)sizeof(svhip_config)) { g_create_error = "bad config / struct_size"; return SVHIP_ERR_INVALID; }
-    if (!lengths) { g_create_error = "null pointer"; return SVHIP_ERR_INVALID; }
-    std::string msg;
-    const int rc = rawnet3_ragged_check(*cfg, lengths, n, msg);
-    if (rc) g_create_error = msg;
-    return rc;
+    return ragged_check(kRagRawnet3, cfg, lengths, n, true);
 }
 
 int svhip_conformer_embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
                                  int32_t flags, int32_t is_wave) {
-    if (!h) return SVHIP_ERR_INVALID;
-    if (!h->finalized) SV_FAIL(h, SVHIP_ERR_STATE, "weights not finalized (call svhip_finalize_weights first)");
-    if (!in || !offsets || !lengths || !emb_out) SV_FAIL(h, SVHIP_ERR_INVALID, "null pointer");
-    std::string msg;
-    if (int rc = conformer_ragged_check(h->cfg, lengths, n, is_wave != 0, msg)) SV_FAIL(h, rc, "%s", msg.c_str());
-    for (int i = 0; i < n; ++i)
-        if (offsets[i] < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "utterance %d: negative offset (the limit is 0)", i);
-    if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
-        SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
-    SV_HIP(h, hipSetDevice(h->cfg.device));
-    int rc = conformer_embed_ragged(h, in, !(flags & SVHIP_IN_DEVICE), is_wave != 0, offsets, lengths, n);
-    if (rc) return rc;
-    if ((rc = emit_embeddings(h, n, emb_out, flags))) return rc;
-    return finish(h, flags);
+    return embed_ragged(kRagConformer, h, in, offsets, lengths, n, emb_out, flags, is_wave != 0);
 }
 
 int svhip_conformer_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave) {
-    if (!cfg || cfg->struct_size != (int32_t)sizeof(svhip_config)) { g_create_error = "bad config / struct_size"; return SVHIP_ERR_INVALID; }
-    if (!lengths) { g_create_error = "null pointer"; return SVHIP_ERR_INVALID; }
-    std::string msg;
-    const int rc = conformer_ragged_check(*cfg, lengths, n, is_wave != 0, msg);
-    if (rc) g_create_error = msg;
-    return rc;
+    return ragged_check(kRagConformer, cfg, lengths, n, is_wave != 0);
 }
 
 int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, const int64_t* offsets, const int32_t* lengths,
@@ -624,15 +619,15 @@ int svhip_get_stage(svhip_handle* h, const char* name, float* out, int64_t* coun
     if (!h || !name || !count) return SVHIP_ERR_INVALID;
     if (h->lastB <= 0) SV_FAIL(h, SVHIP_ERR_STATE, "no forward has run yet");
     const int B = h->lastB;
-    const size_t rag_in = h->rag_rows && h->rag_in_rows ? (size_t)h->rag_in_rows : (size_t)h->rag_rows;      // packed mel frames of a ragged forward
-    StageView v{nullptr, h->rag_rows ? rag_in : (size_t)B * h->T, 0, 0, !h->bf16};      // (a ragged forward: the packed rows)
+    const size_t rag_in = h->rag_levels ? (size_t)h->rag_rows[0] : 0;      // a ragged forward: the packed rows of its input level
+    StageView v{nullptr, rag_in ? rag_in : (size_t)B * h->T, 0, 0, !h->bf16};
     const std::string n(name);
     if (n == "input" && h->X_in) { v.src = h->X_in; v.cols = v.ld = h->cfg.n_mels; }
     else if (n == "mel") {
         if (h->feat_is_stale) SV_FAIL(h, SVHIP_ERR_STATE, "stage mel: the last forward ran the fused front-end, which never forms the mel power "
                                       "tensor (option fbank_unfused = 1 keeps the separate kernels)");
         v.src = h->d_feat; v.rows = (size_t)B * h->cfg.n_mels; v.cols = v.ld = h->T; v.f32 = true;
-        if (h->rag_rows) { v.rows = 1; v.cols = v.ld = rag_in * h->cfg.n_mels; }      // the (n_mels, T_u) blocks back to back
+        if (rag_in) { v.rows = 1; v.cols = v.ld = rag_in * h->cfg.n_mels; }      // the (n_mels, T_u) blocks back to back
     }
     else {                                    // every other name is the model's
         const ModelOps* m = model_ops(h->cfg.model);

@@ -31,8 +31,6 @@ namespace {
 int cf_sub(int n) { return (n - 3) / 2 + 1; }                         // one Conv2d(3, stride 2) of Conformer's subsampling (n >= 3)
 constexpr int CF_D = 256, CF_LAYERS = 6, CF_MAX_T = 10000;           // d_model, blocks, the length of the pe buffer
 
-struct RagSlot { char* host = nullptr; hipEvent_t done = nullptr; bool busy = false; };
-
 struct CfBlock {
     float *ff_g[2] = {}, *ff_b[2] = {};   // the two feed-forward modules' LayerNorms (FF, FF')
     ConvLayer ff1[2], ff2[2];             // Linear(256, 1024) (Swish in the epilogue), Linear(1024, 256)
@@ -75,21 +73,13 @@ struct ConformerState : ModelState {
     std::vector<int> pe_of;                               // i's positional encoding (layers whose buffers are equal share one copy)
     float* rag_P = nullptr;               // (layers, rag_P_rows, 256): P for rows 0 .. rag_P_rows - 1, grown to the longest T'_u seen
     int rag_P_rows = 0;
-    char* rag_tab = nullptr;              // device tables of the call: feature offsets (Bmax int64), mel row0, subsampled row0 (Bmax + 1 each)
+    RagTables rag;                        // the tables of a call: feature offsets (Bmax int64), mel row0, subsampled row0 (Bmax + 1 each)
     int64_t* rag_feat_off = nullptr;
     int *rag_mel0 = nullptr, *rag_row0 = nullptr;
     int* rag_utt = nullptr;               // (rows_cap) utterance of every subsampled row
-    float *rag_wav = nullptr, *rag_stats = nullptr;   // host-pointer waveform staging; (Bmax n_mels 2) shift / scale of the front-end
-    RagSlot rag_slot[4];                  // pinned copies of the tables of the calls in flight (SVHIP_ASYNC returns before the copy has run)
-    int rag_next = 0;
+    float* rag_stats = nullptr;           // (Bmax n_mels 2) shift / scale of the front-end
 
-    ~ConformerState() override {
-        for (auto& sl : rag_slot) {
-            if (sl.host) (void)hipHostFree(sl.host);
-            if (sl.done) (void)hipEventDestroy(sl.done);
-        }
-        if (rag_P) (void)hipFree(rag_P);
-    }
+    ~ConformerState() override { if (rag_P) (void)hipFree(rag_P); }
 };
 
 ConformerState& S(svhip_handle* h) { return static_cast<ConformerState&>(*h->model); }
@@ -437,49 +427,29 @@ static int conformer_forward_part(svhip_handle* h, const float* d_feat, int b0, 
 int conformer_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, conformer_forward_part, d_feat, B, 1, B); }
 
 // ---- ragged packs ------------------------------------------------------------------------------------------
-// The scope and capacity rules of svhip_conformer_embed_ragged (include/svhip.h), on the host alone.
+// The Conformer's rules for a pack (RaggedCheckFn; include/svhip.h), on the host alone
 int conformer_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
-    char b[320];
-    if (c.model != SVHIP_MODEL_CONFORMER) { err = "ragged Conformer packs: SVHIP_MODEL_CONFORMER only (ECAPA and RawNet3 packs have their own calls)"; return SVHIP_ERR_UNSUPPORTED; }
-    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "ragged Conformer packs: compute SVHIP_F32 or SVHIP_BF16 only"; return SVHIP_ERR_UNSUPPORTED; }
-    if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft || c.n_mels < 7 || c.samples / c.hop_length + 1 < 7) {
-        err = "bad hop_length / max_batch / samples / n_mels"; return SVHIP_ERR_INVALID;
-    }
-    if (n < 1 || n > c.max_batch) {
-        snprintf(b, sizeof(b), "ragged batch of %d utterances outside [1, max_batch=%d]", n, c.max_batch);
-        err = b; return SVHIP_ERR_INVALID;
-    }
-    const int Th = c.samples / c.hop_length + 1;
+    if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft || c.n_mels < 7 || c.samples / c.hop_length + 1 < 7)
+        return refuse(err, SVHIP_ERR_INVALID, "bad hop_length / max_batch / samples / n_mels");
+    const int Th = (int)mel_frames(c, c.samples, true);
     const int64_t cap = (int64_t)c.max_batch * Th;
     const int64_t slice = (int64_t)cf_chunk(c, Th) * cf_sub(cf_sub(Th));      // subsampled frames one subsampling slice holds
     int64_t rows = 0;
     for (int i = 0; i < n; ++i) {
-        const int64_t len = lengths[i];
-        if (is_wave && len < c.n_fft) {
-            snprintf(b, sizeof(b), "utterance %d: %lld samples, fewer than n_fft=%d", i, (long long)len, c.n_fft);
-            err = b; return SVHIP_ERR_INVALID;
-        }
-        const int64_t T = is_wave ? len / c.hop_length + 1 : len;
-        if (T < 7) {
-            snprintf(b, sizeof(b), "utterance %d: %lld frames, fewer than 7 (two 3 x 3 stride-2 convolutions leave T' = (T - 3) / 4 >= 1)", i, (long long)T);
-            err = b; return SVHIP_ERR_INVALID;
-        }
+        if (is_wave && lengths[i] < c.n_fft)
+            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld samples, fewer than n_fft=%d", i, (long long)lengths[i], c.n_fft);
+        const int64_t T = mel_frames(c, lengths[i], is_wave);
+        if (T < 7)
+            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld frames, fewer than 7 (two 3 x 3 stride-2 convolutions leave T' = (T - 3) / 4 >= 1)",
+                          i, (long long)T);
         const int64_t Tp = (T - 3) / 4;
-        if (Tp > CF_MAX_T) {
-            snprintf(b, sizeof(b), "utterance %d: T' = %lld subsampled frames, over the %d positions of the positional encoding", i, (long long)Tp, CF_MAX_T);
-            err = b; return SVHIP_ERR_INVALID;
-        }
-        if (Tp > slice) {
-            snprintf(b, sizeof(b), "utterance %d: T' = %lld subsampled frames, over the %lld one subsampling slice of this handle holds (its conv1 image "
-                                   "must fit the slice buffer)", i, (long long)Tp, (long long)slice);
-            err = b; return SVHIP_ERR_INVALID;
-        }
-        rows += T;
-        if (rows > cap) {
-            snprintf(b, sizeof(b), "utterance %d: the pack reaches %lld frames, over the handle's capacity of max_batch * T = %lld rows", i,
-                     (long long)rows, (long long)cap);
-            err = b; return SVHIP_ERR_INVALID;
-        }
+        if (Tp > CF_MAX_T)
+            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: T' = %lld subsampled frames, over the %d positions of the positional encoding", i,
+                          (long long)Tp, CF_MAX_T);
+        if (Tp > slice)
+            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: T' = %lld subsampled frames, over the %lld one subsampling slice of this handle holds (its "
+                          "conv1 image must fit the slice buffer)", i, (long long)Tp, (long long)slice);
+        if (int rc = rag_rows_fit(err, i, rows += T, cap, "T")) return rc;
     }
     return SVHIP_OK;
 }
@@ -489,21 +459,17 @@ static size_t cf_tab_bytes(size_t B) { return B * 8 + 2 * (B + 1) * 4; }
 // the segment tables, the waveform staging buffer and the pinned table slots: once per handle
 static int conformer_ragged_alloc(svhip_handle* h) {
     auto& s = S(h);
-    if (s.rag_utt) return SVHIP_OK;
+    if (s.rag.dev) return SVHIP_OK;
     const svhip_config& c = h->cfg;
     const size_t B = c.max_batch;
     int rc;
-    if ((rc = dev_alloc(h, &s.rag_tab, cf_tab_bytes(B)))) return rc;
-    s.rag_feat_off = reinterpret_cast<int64_t*>(s.rag_tab);
-    s.rag_mel0 = reinterpret_cast<int*>(s.rag_tab + B * 8);
+    if (!s.rag_stats && (rc = dev_alloc(h, &s.rag_stats, B * c.n_mels * 2))) return rc;
+    if (!s.rag_utt && (rc = dev_alloc(h, &s.rag_utt, s.rows_cap))) return rc;
+    if ((rc = s.rag.alloc(h, cf_tab_bytes(B), B * ((size_t)c.samples + c.hop_length)))) return rc;
+    s.rag_feat_off = reinterpret_cast<int64_t*>(s.rag.dev);
+    s.rag_mel0 = reinterpret_cast<int*>(s.rag.dev + B * 8);
     s.rag_row0 = s.rag_mel0 + (B + 1);
-    if ((rc = dev_alloc(h, &s.rag_wav, B * ((size_t)c.samples + c.hop_length)))) return rc;
-    if ((rc = dev_alloc(h, &s.rag_stats, B * c.n_mels * 2))) return rc;
-    for (auto& sl : s.rag_slot) {
-        SV_HIP(h, hipHostMalloc((void**)&sl.host, cf_tab_bytes(B), hipHostMallocDefault));
-        SV_HIP(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    }
-    return dev_alloc(h, &s.rag_utt, s.rows_cap);
+    return SVHIP_OK;
 }
 
 // P of every layer for rows [0, rows): the double-precision row sums of finalize, so the first T' rows are the handle's own P bit for
@@ -629,68 +595,35 @@ int conformer_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool 
     int rc = conformer_ragged_alloc(h);
     if (rc) return rc;
     int maxTp = 0;
-    for (int u = 0; u < n; ++u) maxTp = std::max(maxTp, ((is_wave ? lengths[u] / c.hop_length + 1 : lengths[u]) - 3) / 4);
+    for (int u = 0; u < n; ++u) maxTp = std::max(maxTp, (int)((mel_frames(c, lengths[u], is_wave) - 3) / 4));
     if ((rc = conformer_ragged_pos(h, maxTp))) return rc;
-    // the tables of this call, in a pinned slot of the handle: the caller's arrays are free on return
-    RagSlot& slot = s.rag_slot[s.rag_next];
-    s.rag_next = (s.rag_next + 1) & 3;
-    if (slot.busy) { SV_HIP(h, hipEventSynchronize(slot.done)); slot.busy = false; }
     const size_t B = c.max_batch;
-    int64_t* feat_off = reinterpret_cast<int64_t*>(slot.host);
-    int* mel0 = reinterpret_cast<int*>(slot.host + B * 8);
+    char* tab = nullptr;
+    if ((rc = s.rag.acquire(h, &tab))) return rc;
+    int64_t* feat_off = reinterpret_cast<int64_t*>(tab);
+    int* mel0 = reinterpret_cast<int*>(tab + B * 8);
     int* row0 = mel0 + (B + 1);
     int M = 0, Mp = 0, maxT = 0;
     for (int u = 0; u < n; ++u) {
-        const int T = is_wave ? lengths[u] / c.hop_length + 1 : lengths[u];
+        const int T = (int)mel_frames(c, lengths[u], is_wave);
         mel0[u] = M; row0[u] = Mp;
         M += T; Mp += cf_sub(cf_sub(T));
         maxT = std::max(maxT, T);
     }
     mel0[n] = M; row0[n] = Mp;
     if ((size_t)Mp > s.rows_cap) SV_FAIL(h, SVHIP_ERR_INVALID, "the pack has %d subsampled rows, over the %zu the handle holds", Mp, s.rows_cap);
-    h->cur = h->stream;
-    const float* d_feat = h->d_feat;
-    h->feat_is_stale = false;
-    if (is_wave) {
-        // the mel power of every utterance, (n_mels, T_u) blocks back to back in d_feat.  The DFT kernel is launched once per utterance
-        // (a workgroup of it sees one utterance's samples only, so its values do not depend on the pack)
-        int64_t pos = 0;
-        for (int u = 0; u < n; ++u) {
-            const int L = lengths[u], T = mel0[u + 1] - mel0[u];
-            const float* w = in + in_off[u];
-            if (in_host) {
-                SV_HIP(h, hipMemcpyAsync(s.rag_wav + pos, w, (size_t)L * 4, hipMemcpyHostToDevice, h->stream));
-                w = s.rag_wav + pos;
-                pos += L;
-            }
-            float* mel = h->d_feat + (size_t)mel0[u] * c.n_mels;
-            if ((rc = run(h, "fbank", 0, [&]() { return launch_fbank(h->fb, w, 1, L, T, mel, h->stream); }))) return rc;
-            feat_off[u] = (int64_t)mel0[u] * c.n_mels;
-        }
-    } else if (in_host) {
-        for (int u = 0; u < n; ++u) {
-            feat_off[u] = (int64_t)mel0[u] * c.n_mels;
-            SV_HIP(h, hipMemcpyAsync(h->d_feat + feat_off[u], in + in_off[u] * c.n_mels, (size_t)lengths[u] * c.n_mels * 4, hipMemcpyHostToDevice, h->stream));
-        }
-    } else {
-        for (int u = 0; u < n; ++u) feat_off[u] = in_off[u] * c.n_mels;
-        d_feat = in;
-        h->feat_is_stale = true;            // (d_feat does not hold this forward's mel power)
-    }
-    SV_HIP(h, hipMemcpyAsync(s.rag_tab, slot.host, cf_tab_bytes(B), hipMemcpyHostToDevice, h->stream));
-    SV_HIP(h, hipEventRecord(slot.done, h->stream));
-    slot.busy = true;
-    // (row0 is read on the host while the launches are enqueued; the slot is not reused before its event)
+    const float* d_feat = nullptr;
+    if ((rc = rag_mel_input(h, s.rag, in, in_host, is_wave, in_off, lengths, n, mel0, feat_off, &d_feat))) return rc;
+    if ((rc = s.rag.commit(h, cf_tab_bytes(B)))) return rc;
+    // (row0 is read on the host while the launches are enqueued; the slot is not taken again before the next call)
     if ((rc = conformer_forward_ragged(h, d_feat, n, maxT, row0, maxTp))) return rc;
-    h->lastB = n;
-    h->rag_rows = Mp;
-    h->rag_in_rows = M;
+    set_rag_rows(h, n, {M, Mp});
     return SVHIP_OK;
 }
 
 int conformer_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // cf_in, cf_block0, cf_attn0, cf_last, cf_pool
     auto& s = S(h);
-    v.rows = h->rag_rows ? (size_t)h->rag_rows : (size_t)h->lastB * s.Tp; v.cols = v.ld = CF_D;      // (a ragged forward: the packed rows)
+    v.rows = h->rag_levels ? (size_t)h->rag_rows[1] : (size_t)h->lastB * s.Tp; v.cols = v.ld = CF_D;      // (a ragged forward: the packed rows)
     if (n == "cf_in") v.src = s.in;
     else if (n == "cf_block0") v.src = s.b0;
     else if (n == "cf_attn0") v.src = s.attn0;

@@ -7,8 +7,6 @@ namespace svhip {
 
 namespace {
 
-struct RagSlot { char* host = nullptr; hipEvent_t done = nullptr; bool busy = false; };
-
 struct EcapaState : ModelState {
     // ECAPA layers
     ConvLayer blocks0, mfa, asp_tdnn, asp_conv;
@@ -36,20 +34,11 @@ struct EcapaState : ModelState {
     float *d_pool_raw = nullptr, *d_pool_bn = nullptr;
 
     // ragged batches (svhip_embed_wave_ragged / svhip_embed_features_ragged): allocated by the handle's first ragged call
+    RagTables rag;                            // the tables of a call, feat_off | row0; staging: max_batch * (samples + hop) floats, the utterances back to back
     int64_t* rag_feat_off = nullptr;          // (max_batch) element offset of every utterance's (n_mels, T_u) block in the feature array
     int* rag_row0 = nullptr;                  // (max_batch + 1) first workspace row of every utterance, then the row count (behind rag_feat_off)
     int* rag_utt = nullptr;                   // (max_batch * T) utterance of every row
-    float* rag_wav = nullptr;                 // host-pointer calls: max_batch * (samples + hop) floats, the utterances back to back
     float* rag_stats = nullptr;               // (max_batch * n_mels * 2) shift / scale of the front-end normalisation
-    RagSlot rag_slot[4];                      // pinned copies of the tables of the calls in flight (SVHIP_ASYNC returns before the copy has run)
-    int rag_next = 0;
-
-    ~EcapaState() override {
-        for (auto& sl : rag_slot) {
-            if (sl.host) (void)hipHostFree(sl.host);
-            if (sl.done) (void)hipEventDestroy(sl.done);
-        }
-    }
 };
 
 EcapaState& S(svhip_handle* h) { return static_cast<EcapaState&>(*h->model); }
@@ -432,35 +421,18 @@ int ecapa_embed_wave(svhip_handle* h, const float* d_wav, int B) {
 }
 
 // ---- ragged batches ------------------------------------------------------------------------------------
-// The scope and capacity rules of svhip_embed_wave_ragged / svhip_embed_features_ragged (include/svhip.h), on the host alone.
+// ECAPA's rules for a pack (RaggedCheckFn; include/svhip.h), on the host alone
 int ecapa_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
-    char b[256];
-    if (c.model != SVHIP_MODEL_ECAPA) { err = "ragged batches: SVHIP_MODEL_ECAPA only (RawNet3 packs go through svhip_rawnet3_embed_ragged; the other models embed one length per handle)"; return SVHIP_ERR_UNSUPPORTED; }
-    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "ragged batches: compute SVHIP_F32 or SVHIP_BF16 only"; return SVHIP_ERR_UNSUPPORTED; }
-    if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft) { err = "bad hop_length / max_batch / samples"; return SVHIP_ERR_INVALID; }
-    if (n < 1 || n > c.max_batch) {
-        snprintf(b, sizeof(b), "ragged batch of %d utterances outside [1, max_batch=%d]", n, c.max_batch);
-        err = b; return SVHIP_ERR_INVALID;
-    }
-    const int64_t cap = (int64_t)c.max_batch * (c.samples / c.hop_length + 1);
+    if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft) return refuse(err, SVHIP_ERR_INVALID, "bad hop_length / max_batch / samples");
+    const int64_t cap = (int64_t)c.max_batch * mel_frames(c, c.samples, true);
     int64_t rows = 0;
     for (int i = 0; i < n; ++i) {
-        const int64_t len = lengths[i];
-        if (is_wave && len < c.n_fft) {
-            snprintf(b, sizeof(b), "utterance %d: %lld samples, fewer than n_fft=%d", i, (long long)len, c.n_fft);
-            err = b; return SVHIP_ERR_INVALID;
-        }
-        const int64_t T = is_wave ? len / c.hop_length + 1 : len;
-        if (T < 5) {
-            snprintf(b, sizeof(b), "utterance %d: %lld frames, fewer than 5 (block 3 reflect-pads 4 frames on each side)", i, (long long)T);
-            err = b; return SVHIP_ERR_INVALID;
-        }
-        rows += T;
-        if (rows > cap) {
-            snprintf(b, sizeof(b), "utterance %d: the pack reaches %lld frames, over the handle's capacity of max_batch * T = %lld rows", i,
-                     (long long)rows, (long long)cap);
-            err = b; return SVHIP_ERR_INVALID;
-        }
+        if (is_wave && lengths[i] < c.n_fft)
+            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld samples, fewer than n_fft=%d", i, (long long)lengths[i], c.n_fft);
+        const int64_t T = mel_frames(c, lengths[i], is_wave);
+        if (T < 5)
+            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld frames, fewer than 5 (block 3 reflect-pads 4 frames on each side)", i, (long long)T);
+        if (int rc = rag_rows_fit(err, i, rows += T, cap, "T")) return rc;
     }
     return SVHIP_OK;
 }
@@ -468,21 +440,16 @@ int ecapa_ragged_check(const svhip_config& c, const int32_t* lengths, int n, boo
 // the segment tables, the waveform staging buffer and the pinned table slots: once per handle
 static int ecapa_ragged_alloc(svhip_handle* h) {
     auto& s = S(h);
-    if (s.rag_utt) return SVHIP_OK;
+    if (s.rag.dev) return SVHIP_OK;
     const svhip_config& c = h->cfg;
     const size_t B = c.max_batch;
     int rc;
-    char* tab = nullptr;
-    if ((rc = dev_alloc(h, &tab, B * 8 + (B + 1) * 4))) return rc;
-    s.rag_feat_off = reinterpret_cast<int64_t*>(tab);
-    s.rag_row0 = reinterpret_cast<int*>(tab + B * 8);
-    if ((rc = dev_alloc(h, &s.rag_wav, B * ((size_t)c.samples + c.hop_length)))) return rc;
-    if ((rc = dev_alloc(h, &s.rag_stats, B * c.n_mels * 2))) return rc;
-    for (auto& sl : s.rag_slot) {
-        SV_HIP(h, hipHostMalloc((void**)&sl.host, B * 8 + (B + 1) * 4, hipHostMallocDefault));
-        SV_HIP(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    }
-    return dev_alloc(h, &s.rag_utt, B * (size_t)h->T);
+    if (!s.rag_stats && (rc = dev_alloc(h, &s.rag_stats, B * c.n_mels * 2))) return rc;
+    if (!s.rag_utt && (rc = dev_alloc(h, &s.rag_utt, B * (size_t)h->T))) return rc;
+    if ((rc = s.rag.alloc(h, B * 8 + (B + 1) * 4, B * ((size_t)c.samples + c.hop_length)))) return rc;
+    s.rag_feat_off = reinterpret_cast<int64_t*>(s.rag.dev);
+    s.rag_row0 = reinterpret_cast<int*>(s.rag.dev + B * 8);
+    return SVHIP_OK;
 }
 
 // ECAPA_TDNN.forward over the packed rows of a ragged batch (features at d_feat + rag_feat_off[u]; tables on the device).  One slice on
@@ -562,56 +529,24 @@ int ecapa_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_w
     const svhip_config& c = h->cfg;
     int rc = ecapa_ragged_alloc(h);
     if (rc) return rc;
-    // the tables of this call, in a pinned slot of the handle: the caller's arrays are free on return
-    RagSlot& slot = s.rag_slot[s.rag_next];
-    s.rag_next = (s.rag_next + 1) & 3;
-    if (slot.busy) { SV_HIP(h, hipEventSynchronize(slot.done)); slot.busy = false; }
     const size_t B = c.max_batch;
-    int64_t* feat_off = reinterpret_cast<int64_t*>(slot.host);
-    int* row0 = reinterpret_cast<int*>(slot.host + B * 8);
+    char* tab = nullptr;
+    if ((rc = s.rag.acquire(h, &tab))) return rc;
+    int64_t* feat_off = reinterpret_cast<int64_t*>(tab);
+    int* row0 = reinterpret_cast<int*>(tab + B * 8);
     int M = 0, maxT = 0;
     for (int u = 0; u < n; ++u) {
-        const int T = is_wave ? lengths[u] / c.hop_length + 1 : lengths[u];
+        const int T = (int)mel_frames(c, lengths[u], is_wave);
         row0[u] = M;
         M += T;
         maxT = std::max(maxT, T);
     }
     row0[n] = M;
-    h->cur = h->stream;
-    const float* d_feat = h->d_feat;
-    h->feat_is_stale = false;
-    if (is_wave) {
-        // the mel power of every utterance, (n_mels, T_u) blocks back to back in d_feat.  The DFT kernel is launched once per utterance
-        // (a workgroup of it sees one utterance's samples only, so its values do not depend on the pack)
-        int64_t pos = 0;
-        for (int u = 0; u < n; ++u) {
-            const int L = lengths[u], T = row0[u + 1] - row0[u];
-            const float* w = in + in_off[u];
-            if (in_host) {
-                SV_HIP(h, hipMemcpyAsync(s.rag_wav + pos, w, (size_t)L * 4, hipMemcpyHostToDevice, h->stream));
-                w = s.rag_wav + pos;
-                pos += L;
-            }
-            float* mel = h->d_feat + (size_t)row0[u] * c.n_mels;
-            if ((rc = run(h, "fbank", 0, [&]() { return launch_fbank(h->fb, w, 1, L, T, mel, h->stream); }))) return rc;
-            feat_off[u] = (int64_t)row0[u] * c.n_mels;
-        }
-    } else if (in_host) {
-        for (int u = 0; u < n; ++u) {
-            feat_off[u] = (int64_t)row0[u] * c.n_mels;
-            SV_HIP(h, hipMemcpyAsync(h->d_feat + feat_off[u], in + in_off[u] * c.n_mels, (size_t)lengths[u] * c.n_mels * 4, hipMemcpyHostToDevice, h->stream));
-        }
-    } else {
-        for (int u = 0; u < n; ++u) feat_off[u] = in_off[u] * c.n_mels;
-        d_feat = in;
-        h->feat_is_stale = true;            // (d_feat does not hold this forward's mel power)
-    }
-    SV_HIP(h, hipMemcpyAsync(s.rag_feat_off, slot.host, B * 8 + (size_t)(n + 1) * 4, hipMemcpyHostToDevice, h->stream));
-    SV_HIP(h, hipEventRecord(slot.done, h->stream));
-    slot.busy = true;
+    const float* d_feat = nullptr;
+    if ((rc = rag_mel_input(h, s.rag, in, in_host, is_wave, in_off, lengths, n, row0, feat_off, &d_feat))) return rc;
+    if ((rc = s.rag.commit(h, B * 8 + (size_t)(n + 1) * 4))) return rc;
     if ((rc = ecapa_forward_ragged(h, d_feat, n, M, maxT))) return rc;
-    h->lastB = n;
-    h->rag_rows = M;
+    set_rag_rows(h, n, {M});
     s.x0_is_s32 = s.cat_f32_stale = s.h2_is_s32 = s.h1_split = false;
     return SVHIP_OK;
 }

@@ -30,8 +30,6 @@ constexpr int C = 1024, W = 128, D = 1536;
 
 int rn3_frames(int L) { return (L - RN3_TAPS) / RN3_STRIDE + 1; }      // T0 of RawNet3's front-end
 
-struct RagSlot { char* host = nullptr; hipEvent_t done = nullptr; bool busy = false; };
-
 struct Rn3Layer {                         // Bottle2neck(k = 3, scale = 8): every BatchNorm follows a ReLU, so it is its conv's epilogue affine
     ConvLayer conv1, convs[7], conv3, residual;      // conv1 + bn1, convs[i] + bns[i], conv3 + bn3; residual: 1 x 1, no bias (layer1)
     bool has_residual = false;
@@ -60,19 +58,9 @@ struct RawNet3State : ModelState {
     const void* stage[5] = {};            // svhip_get_stage: front-end, layer1, layer2, layer3, layer4 outputs of the last forward
     int stage_T[5] = {}, stage_C[5] = {}, stage_ld[5] = {};
     // ragged packs (allocated by the first ragged call)
-    char* rag_tab = nullptr;              // device tables of the call: sample offsets (Bmax int64), lengths (Bmax int), three row0 (Bmax + 1 each)
+    RagTables rag;                        // the tables of a call: sample offsets (Bmax int64), lengths (Bmax int), three row0 (Bmax + 1 each);
+                                          // staging: the utterances back to back, Bmax * (samples + 16) floats
     int* rag_utt[3] = {};                 // utterance of every row, per level
-    float* rag_wav = nullptr;             // host-pointer calls: the utterances back to back, Bmax * (samples + 16) floats
-    RagSlot rag_slot[4];                  // pinned copies of the tables of the calls in flight (SVHIP_ASYNC returns before the copy has run)
-    int rag_next = 0;
-    int64_t rag_rows[3] = {};             // rows per level of the last forward when it was a ragged one (svhip_get_stage), else 0
-
-    ~RawNet3State() override {
-        for (auto& sl : rag_slot) {
-            if (sl.host) (void)hipHostFree(sl.host);
-            if (sl.done) (void)hipEventDestroy(sl.done);
-        }
-    }
 };
 
 // one frame level of a ragged pack: utterance u owns the rows [row0[u], row0[u + 1]), utt[m] is the utterance of row m, M rows in all
@@ -302,7 +290,7 @@ int rawnet3_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {  
     else {
         static const int kLevel[5] = {0, 1, 2, 2, 2};       // after a ragged forward: the packed rows of the stage's level, in utterance order
         v.src = s.stage[i]; v.cols = s.stage_C[i]; v.ld = s.stage_ld[i];
-        v.rows = h->rag_rows ? (size_t)s.rag_rows[kLevel[i]] : (size_t)h->lastB * s.stage_T[i];
+        v.rows = h->rag_levels ? (size_t)h->rag_rows[kLevel[i]] : (size_t)h->lastB * s.stage_T[i];
     }
     return SVHIP_OK;
 }
@@ -373,29 +361,15 @@ static int rawnet3_forward_part(svhip_handle* h, const float* d_wav, int b0, int
 int rawnet3_forward(svhip_handle* h, const float* d_wav, int B) { return forward_lanes(h, rawnet3_forward_part, d_wav, B, 1, B); }
 
 // ---- ragged packs ------------------------------------------------------------------------------------------
-// The scope and capacity rules of svhip_rawnet3_embed_ragged (include/svhip.h), on the host alone.
-int rawnet3_ragged_check(const svhip_config& c, const int32_t* lengths, int n, std::string& err) {
-    char b[256];
-    if (c.model != SVHIP_MODEL_RAWNET3) { err = "svhip_rawnet3_embed_ragged: SVHIP_MODEL_RAWNET3 only (ECAPA packs go through svhip_embed_wave_ragged)"; return SVHIP_ERR_UNSUPPORTED; }
-    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16) { err = "ragged RawNet3 packs: compute SVHIP_F32 or SVHIP_BF16 only"; return SVHIP_ERR_UNSUPPORTED; }
-    if (c.max_batch <= 0 || c.samples < RN3_MIN_SAMPLES) { err = "bad max_batch / samples"; return SVHIP_ERR_INVALID; }
-    if (n < 1 || n > c.max_batch) {
-        snprintf(b, sizeof(b), "ragged pack of %d utterances outside [1, max_batch=%d]", n, c.max_batch);
-        err = b; return SVHIP_ERR_INVALID;
-    }
+// RawNet3's rules for a pack of waveforms (RaggedCheckFn; include/svhip.h), on the host alone
+int rawnet3_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool, std::string& err) {
+    if (c.max_batch <= 0 || c.samples < RN3_MIN_SAMPLES) return refuse(err, SVHIP_ERR_INVALID, "bad max_batch / samples");
     const int64_t cap = (int64_t)c.max_batch * rn3_frames(c.samples);
     int64_t rows = 0;
     for (int i = 0; i < n; ++i) {
-        if (lengths[i] < RN3_MIN_SAMPLES) {
-            snprintf(b, sizeof(b), "utterance %d: %d samples, fewer than RawNet3's minimum of %d", i, lengths[i], RN3_MIN_SAMPLES);
-            err = b; return SVHIP_ERR_INVALID;
-        }
-        rows += rn3_frames(lengths[i]);
-        if (rows > cap) {
-            snprintf(b, sizeof(b), "utterance %d: the pack reaches %lld frames, over the handle's capacity of max_batch * T0 = %lld rows", i,
-                     (long long)rows, (long long)cap);
-            err = b; return SVHIP_ERR_INVALID;
-        }
+        if (lengths[i] < RN3_MIN_SAMPLES)
+            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %d samples, fewer than RawNet3's minimum of %d", i, lengths[i], RN3_MIN_SAMPLES);
+        if (int rc = rag_rows_fit(err, i, rows += rn3_frames(lengths[i]), cap, "T0")) return rc;
     }
     return SVHIP_OK;
 }
@@ -403,20 +377,16 @@ int rawnet3_ragged_check(const svhip_config& c, const int32_t* lengths, int n, s
 // the device tables, the waveform staging buffer and the pinned table slots: once per handle
 static int rawnet3_ragged_alloc(svhip_handle* h) {
     auto& s = S(h);
-    if (s.rag_tab) return SVHIP_OK;
+    if (s.rag.dev) return SVHIP_OK;
     const svhip_config& c = h->cfg;
     const size_t B = c.max_batch, M0 = B * (size_t)s.T0;
     int rc;
-    int* utt = nullptr;
-    if ((rc = dev_alloc(h, &utt, M0 + (M0 / 5 + 1) + (M0 / 15 + 1)))) return rc;
-    s.rag_utt[0] = utt; s.rag_utt[1] = utt + M0; s.rag_utt[2] = utt + M0 + M0 / 5 + 1;
-    // (a pack of n <= B utterances within M0 frames holds at most 10 M0 + 250 n <= B (samples + 9) samples)
-    if ((rc = dev_alloc(h, &s.rag_wav, B * ((size_t)c.samples + 16)))) return rc;
-    for (auto& sl : s.rag_slot) {
-        SV_HIP(h, hipHostMalloc((void**)&sl.host, rag_tab_bytes(B), hipHostMallocDefault));
-        SV_HIP(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    if (!s.rag_utt[0]) {
+        if ((rc = dev_alloc(h, &s.rag_utt[0], M0 + (M0 / 5 + 1) + (M0 / 15 + 1)))) return rc;
+        s.rag_utt[1] = s.rag_utt[0] + M0; s.rag_utt[2] = s.rag_utt[1] + M0 / 5 + 1;
     }
-    return dev_alloc(h, &s.rag_tab, rag_tab_bytes(B));
+    // (a pack of n <= B utterances within M0 frames holds at most 10 M0 + 250 n <= B (samples + 9) samples)
+    return s.rag.alloc(h, rag_tab_bytes(B), B * ((size_t)c.samples + 16));
 }
 
 // RawNet3.forward over a ragged pack (utterance u: len[u] samples at d_wav + off[u]; the tables are on the device), on the handle's
@@ -428,8 +398,8 @@ static int rawnet3_forward_ragged(svhip_handle* h, const float* d_wav, int n, co
     const bool bf = h->bf16;
     hipStream_t st = h->cur = h->stream;
     const size_t B = c.max_batch;
-    const int64_t* d_off = reinterpret_cast<const int64_t*>(s.rag_tab);
-    const int* d_len = reinterpret_cast<const int*>(s.rag_tab + B * 8);
+    const int64_t* d_off = reinterpret_cast<const int64_t*>(s.rag.dev);
+    const int* d_len = reinterpret_cast<const int*>(s.rag.dev + B * 8);
     void *P0 = s.buf[0], *P1 = s.buf[1], *P2 = s.buf[2], *CAT = s.cat;
     int rc;
     auto stage = [&](int i, const void* src, int Cn, int ld) { s.stage[i] = src; s.stage_T[i] = 0; s.stage_C[i] = Cn; s.stage_ld[i] = ld; };
@@ -491,18 +461,15 @@ static int rawnet3_forward_ragged(svhip_handle* h, const float* d_wav, int n, co
     });
 }
 
-// the caller (svhip_rawnet3_embed_ragged) has run rawnet3_ragged_check
-int rawnet3_embed_ragged(svhip_handle* h, const float* in, bool in_host, const int64_t* in_off, const int32_t* lengths, int n) {
+int rawnet3_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool, const int64_t* in_off, const int32_t* lengths, int n) {
     auto& s = S(h);
     int rc = rawnet3_ragged_alloc(h);
     if (rc) return rc;
-    // the tables of this call, in a pinned slot of the handle: the caller's arrays are free on return
-    RagSlot& slot = s.rag_slot[s.rag_next];
-    s.rag_next = (s.rag_next + 1) & 3;
-    if (slot.busy) { SV_HIP(h, hipEventSynchronize(slot.done)); slot.busy = false; }
     const size_t B = h->cfg.max_batch;
-    int64_t* t_off = reinterpret_cast<int64_t*>(slot.host);
-    int* t_len = reinterpret_cast<int*>(slot.host + B * 8);
+    char* tab = nullptr;
+    if ((rc = s.rag.acquire(h, &tab))) return rc;
+    int64_t* t_off = reinterpret_cast<int64_t*>(tab);
+    int* t_len = reinterpret_cast<int*>(tab + B * 8);
     int* t_row0[3];
     for (int l = 0; l < 3; ++l) t_row0[l] = t_len + B + l * (B + 1);
     int M[3] = {0, 0, 0}, maxT[3] = {0, 0, 0};
@@ -519,22 +486,18 @@ int rawnet3_embed_ragged(svhip_handle* h, const float* in, bool in_host, const i
         t_len[u] = lengths[u];
         t_off[u] = in_off[u];
         if (in_host) {
-            SV_HIP(h, hipMemcpyAsync(s.rag_wav + pos, in + in_off[u], (size_t)lengths[u] * 4, hipMemcpyHostToDevice, h->stream));
+            SV_HIP(h, hipMemcpyAsync(s.rag.wav + pos, in + in_off[u], (size_t)lengths[u] * 4, hipMemcpyHostToDevice, h->stream));
             t_off[u] = pos;
             pos += lengths[u];
         }
     }
     for (int l = 0; l < 3; ++l) t_row0[l][n] = M[l];
-    SV_HIP(h, hipMemcpyAsync(s.rag_tab, slot.host, rag_tab_bytes(B), hipMemcpyHostToDevice, h->stream));
-    SV_HIP(h, hipEventRecord(slot.done, h->stream));
-    slot.busy = true;
+    if ((rc = s.rag.commit(h, rag_tab_bytes(B)))) return rc;
     Seg lv[3];
-    const int* d_row0 = reinterpret_cast<const int*>(s.rag_tab + B * 12);
+    const int* d_row0 = reinterpret_cast<const int*>(s.rag.dev + B * 12);
     for (int l = 0; l < 3; ++l) { lv[l].row0 = d_row0 + l * (B + 1); lv[l].utt = s.rag_utt[l]; lv[l].M = M[l]; }
-    if ((rc = rawnet3_forward_ragged(h, in_host ? s.rag_wav : in, n, lv, maxT))) return rc;
-    h->lastB = n;
-    h->rag_rows = M[0];
-    for (int l = 0; l < 3; ++l) s.rag_rows[l] = M[l];
+    if ((rc = rawnet3_forward_ragged(h, in_host ? s.rag.wav : in, n, lv, maxT))) return rc;
+    set_rag_rows(h, n, {M[0], M[1], M[2]});
     return SVHIP_OK;
 }
 

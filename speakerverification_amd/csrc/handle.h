@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <string>
@@ -124,8 +125,10 @@ struct svhip_handle {
     float *d_ones = nullptr, *d_zeros = nullptr;      // 4096 ones / zeros: stand-ins for absent per-channel vectors (GemmParams::ones / zeros)
     float* d_emb = nullptr;
     int lastB = 0;
-    int64_t rag_rows = 0;                     // rows of the last forward when it was a ragged one (svhip_get_stage), else 0
-    int64_t rag_in_rows = 0;                  // ... and its mel frames where they are not those rows (Conformer: rag_rows counts subsampled frames)
+    // the last forward when it was a ragged one (svhip_get_stage): the packed rows of each of its rag_levels frame levels, the input's first
+    // (ECAPA: mel frames; Conformer: mel frames, subsampled frames; RawNet3: its levels 0 .. 2).  rag_levels = 0: a fixed-length forward
+    int64_t rag_rows[3] = {};
+    int rag_levels = 0;
     // shared by several models: each is allocated by the alloc / finalize hook of the models named, and null on the others' handles
     void* X_in = nullptr;         // (M, n_mels): the network input (ECAPA, TitaNet, Conformer; svhip_get_stage "input")
     float *in_w = nullptr, *in_b = nullptr;   // instance norm affine (ECAPA, Conformer)
@@ -272,6 +275,12 @@ using SpecFn = void(const svhip_config& c, WeightSpec& spec);
 using HandleFn = int(svhip_handle* h);
 using EmbedFn = int(svhip_handle* h, const float* in, int B);       // device input (B, L) or (B, n_mels, T) -> h->d_emb
 using StageFn = int(svhip_handle* h, const std::string& name, bool fill, StageView& v);     // fill: the caller reads the data next
+// A ragged pack: utterance u is lengths[u] long (samples, is_wave; else mel frames).  RaggedCheckFn: the model's own rules — with n = 0 those on
+// the configuration alone, else also those on every utterance in index order and on the pack's rows; the caller has checked the scope and n.
+// RaggedEmbedFn: the forward -> h->d_emb after those rules passed; utterance u starts at in + in_off[u] (samples of a waveform array;
+// frames of a feature array of (n_mels, T_u) blocks), a device array or with in_host a host one
+using RaggedCheckFn = int(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err);
+using RaggedEmbedFn = int(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n);
 struct ModelOps {
     int model;
     CheckFn* check;
@@ -281,8 +290,42 @@ struct ModelOps {
     StageFn* stage;
     int max_lanes;                           // cap of SVHIP_LANES
     const char* optional_prefix;             // spec names that finalize may find absent (it checks them itself)
+    RaggedCheckFn* ragged_check;             // utterances of different lengths in one call: null for a model without a ragged forward
+    RaggedEmbedFn* embed_ragged;
 };
 int unknown_stage(svhip_handle* h, const std::string& name);         // SVHIP_ERR_INVALID "unknown stage <name>"
+
+// api_ragged.hip: what the ragged calls of the models share on the host
+int refuse(std::string& err, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));      // err = the text; returns code
+// the running row sum of a pack after utterance i against the handle's rows (frames_name: what max_batch multiplies in the text)
+int rag_rows_fit(std::string& err, int i, int64_t rows, int64_t cap, const char* frames_name);
+// in int64: a length near INT32_MAX at hop_length 1 must reach the capacity rule, not wrap
+inline int64_t mel_frames(const svhip_config& c, int64_t len, bool is_wave) { return is_wave ? len / c.hop_length + 1 : len; }
+// a ragged forward has run over n utterances: what svhip_get_stage needs of it
+inline void set_rag_rows(svhip_handle* h, int n, std::initializer_list<int> rows) {
+    h->lastB = n;
+    h->rag_levels = 0;
+    for (int r : rows) h->rag_rows[h->rag_levels++] = r;
+}
+// The tables of a ragged call: a device block in which the model lays out its tables, a ring of four pinned host copies of it, each
+// guarded by an event (an SVHIP_ASYNC call returns before the copy has run, and the caller's arrays are free on return), and the
+// device staging buffer of host-pointer waveforms.  One per model state; the device memory is the handle's (dev_alloc)
+struct RagSlot { char* host = nullptr; hipEvent_t done = nullptr; bool busy = false; };
+struct RagTables {
+    char* dev = nullptr;
+    float* wav = nullptr;
+    RagSlot slot[4], *cur = nullptr;
+    int next = 0;
+    int alloc(svhip_handle* h, size_t table_bytes, size_t wav_floats);      // once per handle (later calls do nothing)
+    int acquire(svhip_handle* h, char** host);          // the next pinned copy to fill, after a wait if its last call's copy has not run yet
+    int commit(svhip_handle* h, size_t bytes);          // its first `bytes` to `dev` on the handle's stream; it is busy until that copy has run
+    ~RagTables();
+};
+// the mel input of a pack (ECAPA, Conformer; mel0: the n + 1 first mel frames on the host): waveforms through the staging buffer and one
+// fbank launch per utterance into h->d_feat, host features copied there, device features read in place; fills feat_off, *d_feat is
+// the array they index
+int rag_mel_input(svhip_handle* h, RagTables& rag, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths,
+                  int n, const int* mel0, int64_t* feat_off, const float** d_feat);
 
 // api_gemm.hip: the GEMM of one conv layer.  conv_plan is the one place that decides its kernel: conv_gemm launches what it returns,
 // and the producers of an operand ask it too, so that they write the layout that kernel reads.
@@ -310,16 +353,6 @@ SpecFn ecapa_spec, rawnet2_spec, rawnet3_spec, titanet_spec, conformer_spec, res
 HandleFn ecapa_finalize, rawnet2_finalize, rawnet3_finalize, titanet_finalize, conformer_finalize, resnetse_finalize;
 HandleFn ecapa_alloc, rawnet2_alloc, rawnet3_alloc, titanet_alloc, conformer_alloc, resnetse_alloc;
 EmbedFn ecapa_embed_wave, rawnet2_forward, rawnet3_forward;                    // from the waveform
-// a ragged ECAPA batch: utterance u is `frames[u]` frames long; in_off[u] is where it starts in `in` (samples of a device waveform array,
-// wave; elements of a device feature array, features) or, with in_host, in the host array `in`
-int ecapa_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err);
-int ecapa_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n);
-// a ragged RawNet3 pack: utterance u is lengths[u] samples at in + in_off[u] (a device waveform array, or with in_host a host one)
-int rawnet3_ragged_check(const svhip_config& c, const int32_t* lengths, int n, std::string& err);
-int rawnet3_embed_ragged(svhip_handle* h, const float* in, bool in_host, const int64_t* in_off, const int32_t* lengths, int n);
-// a ragged Conformer pack: ecapa_embed_ragged's arguments (lengths in samples, wave, or mel frames)
-int conformer_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err);
-int conformer_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n);
 EmbedFn ecapa_forward, titanet_forward, conformer_forward, resnetse_forward;   // from the mel power
 StageFn ecapa_stage, rawnet2_stage, rawnet3_stage, titanet_stage, conformer_stage, resnetse_stage;
 

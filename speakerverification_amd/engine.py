@@ -6,6 +6,7 @@ Host-side plumbing only: every array that crosses into the library is passed as 
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from typing import Dict, Optional
 
 import numpy as np
@@ -77,6 +78,21 @@ class _Buf:
             self.device = False
             self.ptr = a.ctypes.data
             self.nbytes = a.nbytes
+
+
+# The ragged exports of the library per model kind, as data: the waveform export and the feature export (None: a waveform model), each a
+# name with the arguments that follow the common ones (svhip_embed_wave_ragged's); the host-only check export and whether it takes is_wave
+# after (cfg, lengths, n); and the frames of an utterance of n samples at the handle's hop, in the unit of row_capacity.  A model kind
+# without a row goes to ECAPA's exports, which refuse its handle by name.
+_RaggedCalls = namedtuple("_RaggedCalls", "wave features check check_takes_is_wave frames")
+_MEL_FRAMES = lambda n, hop: n // hop + 1
+_RAGGED = {
+    "ecapa": _RaggedCalls(("svhip_embed_wave_ragged",), ("svhip_embed_features_ragged",), "svhip_ragged_check", True, _MEL_FRAMES),
+    "rawnet3": _RaggedCalls(("svhip_rawnet3_embed_ragged",), None, "svhip_rawnet3_ragged_check", False,
+                            lambda n, hop: (n - 251) // 10 + 1),       # the frames after its sinc filterbank (251 taps, stride 10)
+    "conformer": _RaggedCalls(("svhip_conformer_embed_ragged", 1), ("svhip_conformer_embed_ragged", 0), "svhip_conformer_ragged_check", True,
+                              _MEL_FRAMES),
+}
 
 
 class Engine:
@@ -244,18 +260,19 @@ class Engine:
         self._ck(self.lib.svhip_embed_wave(self.h, i.ptr, B, L, o.ptr, self._flags(i, o, async_)))
         return out
 
-    # ---- ragged batches: utterances of different lengths in one call (svhip_embed_wave_ragged / svhip_embed_features_ragged) ----
+    # ---- ragged batches: utterances of different lengths in one call (_RAGGED names the model's exports) ----
+    @property
+    def _ragged(self):
+        return _RAGGED.get(self.model, _RAGGED["ecapa"])
+
     @property
     def row_capacity(self):
-        """frames one ragged call can hold: the rows of the handle's workspace, max_batch * T (RawNet3: max_batch * T0)"""
+        """frames one ragged call can hold: the rows of the handle's workspace, max_batch frames_of(samples)"""
         return self.max_batch * self.frames_of(self.samples)
 
     def frames_of(self, n_samples):
-        """frames of an utterance of n_samples in the unit of row_capacity: mel frames, or on a RawNet3 handle the frames after
-        its sinc filterbank (251 taps, stride 10)"""
-        if self.model == "rawnet3":
-            return (int(n_samples) - 251) // 10 + 1
-        return int(n_samples) // int(self.cfg.hop_length) + 1
+        """frames of an utterance of n_samples in the unit of row_capacity (_RAGGED: mel frames, or the model's own first frame level)"""
+        return self._ragged.frames(int(n_samples), int(self.cfg.hop_length))
 
     def _pack(self, items, offsets, lengths, is_wave):
         """a list of arrays -> (packed array, int64 offsets, int32 lengths); a packed array with its tables passes through.
@@ -280,7 +297,8 @@ class Engine:
             packed = np.concatenate([np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in items])
         return packed, offs, lens
 
-    def _embed_ragged(self, fn, items, offsets, lengths, out, async_, is_wave, ordered=False):
+    def _embed_ragged(self, export, items, offsets, lengths, out, async_, is_wave, ordered=False):
+        """export: a wave / features entry of _RAGGED, (name, trailing arguments ..)"""
         packed, offs, lens = self._pack(items, offsets, lengths, is_wave)
         n = int(lens.shape[0])
         if out is None:
@@ -288,35 +306,23 @@ class Engine:
         i, o = _Buf(packed, np.float32), _Buf(out, np.float32, writable=True)
         self._order_after_torch(i, o, async_=async_, ordered=ordered)
         _count([i], [o])
-        self._ck(fn(self.h, i.ptr, offs.ctypes.data, lens.ctypes.data, n, o.ptr, self._flags(i, o, async_)))
+        self._ck(getattr(self.lib, export[0])(self.h, i.ptr, offs.ctypes.data, lens.ctypes.data, n, o.ptr, self._flags(i, o, async_), *export[1:]))
         return out
 
     def embed_wave_ragged(self, wavs, offsets=None, lengths=None, out=None, async_=False, ordered=False):
         """utterances of different lengths -> (n, embed_dim), each as if forwarded alone at its own length.  ``wavs``: a list of 1-D
-        arrays, or ONE packed array with ``offsets`` / ``lengths`` in samples; numpy or CUDA tensors, like embed_wave.  A RawNet3
-        handle takes the pack through svhip_rawnet3_embed_ragged, a Conformer handle through svhip_conformer_embed_ragged."""
-        fn = (self.lib.svhip_rawnet3_embed_ragged if self.model == "rawnet3" else
-              self._conformer_ragged(1) if self.model == "conformer" else self.lib.svhip_embed_wave_ragged)
-        return self._embed_ragged(fn, wavs, offsets, lengths, out, async_, True, ordered)
-
-    def _conformer_ragged(self, is_wave):
-        """svhip_conformer_embed_ragged with the call shape of the two ECAPA exports"""
-        return lambda *args: self.lib.svhip_conformer_embed_ragged(*args, is_wave)
+        arrays, or ONE packed array with ``offsets`` / ``lengths`` in samples; numpy or CUDA tensors, like embed_wave."""
+        return self._embed_ragged(self._ragged.wave, wavs, offsets, lengths, out, async_, True, ordered)
 
     def embed_features_ragged(self, feats, offsets=None, lengths=None, out=None, async_=False):
         """``feats``: a list of (n_mels, T_i) mel-power arrays, or one packed array of such blocks with frame ``offsets`` / ``lengths``."""
-        fn = self._conformer_ragged(0) if self.model == "conformer" else self.lib.svhip_embed_features_ragged
-        return self._embed_ragged(fn, feats, offsets, lengths, out, async_, False)
+        return self._embed_ragged(self._ragged.features or _RAGGED["ecapa"].features, feats, offsets, lengths, out, async_, False)
 
     def ragged_check(self, lengths, is_wave=True):
-        """the library's own capacity test for a pack (svhip_ragged_check, host only): None, or the refusal's text"""
+        """the library's own capacity test for a pack (host only): None, or the refusal's text"""
         lens = np.ascontiguousarray(lengths, dtype=np.int32)
-        if self.model == "rawnet3":
-            rc = self.lib.svhip_rawnet3_ragged_check(C.byref(self.cfg), lens.ctypes.data, int(lens.shape[0]))
-        elif self.model == "conformer":
-            rc = self.lib.svhip_conformer_ragged_check(C.byref(self.cfg), lens.ctypes.data, int(lens.shape[0]), 1 if is_wave else 0)
-        else:
-            rc = self.lib.svhip_ragged_check(C.byref(self.cfg), lens.ctypes.data, int(lens.shape[0]), 1 if is_wave else 0)
+        r = self._ragged
+        rc = getattr(self.lib, r.check)(C.byref(self.cfg), lens.ctypes.data, int(lens.shape[0]), *([1 if is_wave else 0] if r.check_takes_is_wave else []))
         return None if rc == _lib.OK else (self.lib.svhip_last_error(None) or b"?").decode()
 
     def crop_pcm16(self, pcm_list, num_eval, L=32000, out=None, async_=False):

@@ -16,7 +16,7 @@ SpecAugment (``augment=True`` with 'spec_domain') is not built.
 from __future__ import annotations
 
 from .. import synth
-from ._base import HipModule
+from ._base import HipModule, RaggedMixin
 
 MIN_SAMPLES = 512           # the mel front-end's n_fft (one frame of the library's front-end)
 
@@ -45,7 +45,7 @@ def _crop_samples(audio_spec):
         return None
 
 
-class Conformer(HipModule):
+class Conformer(RaggedMixin, HipModule):
     model_kind = "conformer"
 
     def __init__(self, nOut=512, input_size=80, attention_dim=128, device=None, compute=None, max_batch=None, **kwargs):
@@ -105,46 +105,20 @@ class Conformer(HipModule):
         eng = self._engine_for(wav)
         return self._squeeze(self._batched(eng.embed_wave, wav, eng.max_batch))
 
-    # ---- ragged batches: utterances of different lengths on the PRIMARY handle (whole-file evaluation) ----------------
-    DEFAULT_PRIMARY = 32000         # the primary geometry when no audio_spec names one: the reference's 2 s crop at 16 kHz
+    # ---- ragged batches (RaggedMixin): the rows are mel frames ----------------------------------------------------------------
     MIN_FRAMES = 7                  # T' = (T - 3) // 4 >= 1
-
-    def ragged_engine(self):
-        """the handle with the full max_batch workspace: its mel rows are the capacity of a ragged call"""
-        return self._get_engine(self._primary or self.DEFAULT_PRIMARY)
 
     def _ragged_geometry(self):
         """(max_batch, row capacity, slice limit) of the primary handle, from the module's own settings (no handle is built)"""
         frames = (self._primary or self.DEFAULT_PRIMARY) // self._hop + 1
         return self._max_batch, self._max_batch * frames, slice_frames(self._max_batch, frames, self.n_mels, self._compute)
 
-    def ragged_packer(self):
-        from ..ragged import RaggedPacker
-        mb, cap, _ = self._ragged_geometry()
-        return RaggedPacker(mb, cap, min_frames=self.MIN_FRAMES)
-
     def ragged_frames(self, n_samples):
         """mel frames of an utterance of n_samples; 0 for one that fits no ragged call (ragged_frames_of)"""
         return ragged_frames_of(n_samples, self._hop, self._min_samples, self._ragged_geometry()[2])
 
-    def embed_ragged(self, wavs):
-        """list of 1-D waveforms of any lengths -> (n, nOut), each embedded as if alone at its own length, in as few library calls
-        as the primary handle's capacity allows (ragged.plan_ragged).  Raises ValueError for utterances that fit no call: the
-        caller embeds those through embed_wave, which builds a handle for their length."""
-        from ..ragged import plan_ragged
-        mb, cap, _ = self._ragged_geometry()
-        calls, alone = plan_ragged([self.ragged_frames(w.shape[-1]) for w in wavs], mb, cap, min_frames=self.MIN_FRAMES)
-        if alone:
-            raise ValueError(f"utterances {alone[:8]} fit no ragged call of this handle ({cap} frames; at least {self._min_samples} "
-                             f"samples and 7 frames each, at most {self._ragged_geometry()[2]} subsampled frames)")
-        eng = self.ragged_engine()
-        outs = [eng.embed_wave_ragged([wavs[i].reshape(-1) for i in call]) for call in calls]
-        if len(outs) == 1:
-            return outs[0]
-        import numpy as np
-        from ..engine import _is_torch
-        import torch
-        return torch.cat(outs, 0) if _is_torch(outs[0]) else np.concatenate(outs, 0)
+    def _ragged_limits(self):
+        return f"; at least {self._min_samples} samples and 7 frames each, at most {self._ragged_geometry()[2]} subsampled frames"
 
 
 def MainModel(nOut=512, **kwargs):

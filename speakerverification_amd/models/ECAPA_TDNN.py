@@ -8,7 +8,7 @@ The forward runs in libsvhip (HIP, gfx950).  State-dict keys are the reference's
 from __future__ import annotations
 
 from .. import synth
-from ._base import HipModule
+from ._base import HipModule, RaggedMixin
 
 
 def _crop_samples(audio_spec):
@@ -19,7 +19,7 @@ def _crop_samples(audio_spec):
         return None
 
 
-class ECAPA_TDNN(HipModule):
+class ECAPA_TDNN(RaggedMixin, HipModule):
     model_kind = "ecapa"
 
     def __init__(self, input_size=80, lin_neurons=192, activation=None, channels=(1024, 1024, 1024, 1024, 3072),
@@ -73,40 +73,14 @@ class ECAPA_TDNN(HipModule):
         eng = self._get_engine(wav.shape[1], batch=wav.shape[0])
         return self._squeeze(self._batched(eng.embed_wave, wav, eng.max_batch))
 
-
-    # ---- ragged batches: utterances of different lengths on the PRIMARY handle (whole-file evaluation) ----------------
-    DEFAULT_PRIMARY = 32000         # the primary geometry when no audio_spec names one: the reference's 2 s crop at 16 kHz
-
-    def ragged_engine(self):
-        """the handle with the full max_batch workspace: its rows are the capacity of a ragged call"""
-        return self._get_engine(self._primary or self.DEFAULT_PRIMARY)
-
-    def ragged_packer(self):
-        from ..ragged import RaggedPacker
-        eng = self.ragged_engine()
-        return RaggedPacker(eng.max_batch, eng.row_capacity)
-
+    # ---- ragged batches (RaggedMixin) ------------------------------------------------------------------------------------
     def ragged_frames(self, n_samples):
         """frames of an utterance of n_samples; 0 when it is shorter than one FFT window (it fits no ragged call)"""
         eng = self.ragged_engine()
         return eng.frames_of(n_samples) if n_samples >= int(eng.cfg.n_fft) else 0
 
-    def embed_ragged(self, wavs):
-        """list of 1-D waveforms of any lengths -> (n, nOut), each embedded as if alone at its own length, in as few library calls
-        as the primary handle's capacity allows (ragged.plan_ragged).  Raises ValueError for utterances that fit no call: the
-        caller embeds those through forward / embed_wave, which builds a handle for their length."""
-        from ..ragged import plan_ragged
-        eng = self.ragged_engine()
-        calls, alone = plan_ragged([self.ragged_frames(w.shape[-1]) for w in wavs], eng.max_batch, eng.row_capacity)
-        if alone:
-            raise ValueError(f"utterances {alone[:8]} fit no ragged call of this handle ({eng.row_capacity} frames, at least 5 each)")
-        outs = [eng.embed_wave_ragged([wavs[i].reshape(-1) for i in call]) for call in calls]
-        if len(outs) == 1:
-            return outs[0]
-        import numpy as np
-        from ..engine import _is_torch
-        import torch
-        return torch.cat(outs, 0) if _is_torch(outs[0]) else np.concatenate(outs, 0)
+    def _ragged_limits(self):
+        return ", at least 5 each"
 
 
 def MainModel(nOut=512, **kwargs):

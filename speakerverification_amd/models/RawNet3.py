@@ -14,7 +14,7 @@ sums in fp64) and "bf16" ("half" means bf16 here).
 from __future__ import annotations
 
 from .. import synth
-from ._base import HipModule
+from ._base import HipModule, RaggedMixin
 
 MIN_SAMPLES = 541
 
@@ -23,7 +23,7 @@ _BUILT = dict(model_scale=8, context=True, summed=True, out_bn=False, log_sinc=T
               encoder_type="ASP", sinc_stride=10)
 
 
-class RawNet3(HipModule):
+class RawNet3(RaggedMixin, HipModule):
     model_kind = "rawnet3"
 
     def __init__(self, nOut=512, device=None, compute=None, max_batch=None, audio_spec=None, **kwargs):
@@ -54,40 +54,15 @@ class RawNet3(HipModule):
         eng = self._engine_for(x)
         return self._squeeze(self._batched(eng.embed_wave, x, eng.max_batch))
 
-    # ---- ragged batches: utterances of different lengths on the PRIMARY handle (whole-file evaluation) ----------------
-    DEFAULT_PRIMARY = 32000         # the primary geometry when no audio_spec names one: the reference's 2 s crop at 16 kHz
-
-    def ragged_engine(self):
-        """the handle with the full max_batch workspace: its level-0 rows are the capacity of a ragged call"""
-        return self._get_engine(self._primary or self.DEFAULT_PRIMARY)
-
-    def ragged_packer(self):
-        from ..ragged import RaggedPacker
-        eng = self.ragged_engine()
-        return RaggedPacker(eng.max_batch, eng.row_capacity, min_frames=eng.frames_of(MIN_SAMPLES))
+    # ---- ragged batches (RaggedMixin): the rows are the frames after the sinc filterbank -------------------------------------
+    MIN_FRAMES = (MIN_SAMPLES - 251) // 10 + 1
 
     def ragged_frames(self, n_samples):
         """frames of an utterance of n_samples after the sinc filterbank; 0 below 541 samples (it fits no ragged call)"""
         return self.ragged_engine().frames_of(n_samples) if n_samples >= MIN_SAMPLES else 0
 
-    def embed_ragged(self, wavs):
-        """list of 1-D waveforms of any lengths -> (n, nOut), each embedded as if alone at its own length, in as few library calls
-        as the primary handle's capacity allows (ragged.plan_ragged).  Raises ValueError for utterances that fit no call: the
-        caller embeds those through forward, which builds a handle for their length."""
-        from ..ragged import plan_ragged
-        eng = self.ragged_engine()
-        calls, alone = plan_ragged([self.ragged_frames(w.shape[-1]) for w in wavs], eng.max_batch, eng.row_capacity,
-                                   min_frames=eng.frames_of(MIN_SAMPLES))
-        if alone:
-            raise ValueError(f"utterances {alone[:8]} fit no ragged call of this handle ({eng.row_capacity} frames, "
-                             f"at least {MIN_SAMPLES} samples each)")
-        outs = [eng.embed_wave_ragged([wavs[i].reshape(-1) for i in call]) for call in calls]
-        if len(outs) == 1:
-            return outs[0]
-        import numpy as np
-        from ..engine import _is_torch
-        import torch
-        return torch.cat(outs, 0) if _is_torch(outs[0]) else np.concatenate(outs, 0)
+    def _ragged_limits(self):
+        return f", at least {MIN_SAMPLES} samples each"
 
 
 def MainModel(nOut=512, model_scale=8, context=True, summed=True, out_bn=False, log_sinc=True, norm_sinc="mean", grad_mult=1,

@@ -8,6 +8,7 @@ from collections import OrderedDict
 import numpy as np
 
 from ..engine import Engine, _is_torch
+from ..ragged import MIN_FRAMES, RaggedPacker, plan_ragged
 
 try:
     import torch
@@ -168,3 +169,47 @@ class HipModule:
 
     def __call__(self, x, *a, **k):
         return self.forward(x, *a, **k)
+
+
+class RaggedMixin:
+    """Utterances of different lengths in shared calls of the PRIMARY handle (whole-file evaluation), for the HipModules whose library
+    model has a ragged forward.  A mix-in, so that the other models do not grow ``embed_ragged`` (model.py and _fusion.py look for it).
+    A model supplies ``ragged_frames``, ``MIN_FRAMES`` and ``_ragged_limits``."""
+
+    DEFAULT_PRIMARY = 32000         # the primary geometry when no audio_spec names one: the reference's 2 s crop at 16 kHz
+    MIN_FRAMES = MIN_FRAMES         # the fewest frames an utterance of a ragged call has
+
+    def ragged_engine(self):
+        """the handle with the full max_batch workspace: its rows are the capacity of a ragged call"""
+        return self._get_engine(self._primary or self.DEFAULT_PRIMARY)
+
+    def _ragged_geometry(self):
+        """(max_batch, row capacity) of the primary handle"""
+        eng = self.ragged_engine()
+        return eng.max_batch, eng.row_capacity
+
+    def ragged_packer(self):
+        mb, cap = self._ragged_geometry()[:2]
+        return RaggedPacker(mb, cap, min_frames=self.MIN_FRAMES)
+
+    def ragged_frames(self, n_samples):
+        """frames of an utterance of n_samples in the unit of the row capacity; 0 when it fits no ragged call"""
+        raise NotImplementedError
+
+    def _ragged_limits(self):
+        """what an utterance must meet to ride in a ragged call, for embed_ragged's ValueError"""
+        raise NotImplementedError
+
+    def embed_ragged(self, wavs):
+        """list of 1-D waveforms of any lengths -> (n, nOut), each embedded as if alone at its own length, in as few library calls
+        as the primary handle's capacity allows (ragged.plan_ragged).  Raises ValueError for utterances that fit no call: the
+        caller embeds those through forward / embed_wave, which builds a handle for their length."""
+        mb, cap = self._ragged_geometry()[:2]
+        calls, alone = plan_ragged([self.ragged_frames(w.shape[-1]) for w in wavs], mb, cap, min_frames=self.MIN_FRAMES)
+        if alone:
+            raise ValueError(f"utterances {alone[:8]} fit no ragged call of this handle ({cap} frames{self._ragged_limits()})")
+        eng = self.ragged_engine()
+        outs = [eng.embed_wave_ragged([wavs[i].reshape(-1) for i in call]) for call in calls]
+        if len(outs) == 1:
+            return outs[0]
+        return torch.cat(outs, 0) if _is_torch(outs[0]) else np.concatenate(outs, 0)

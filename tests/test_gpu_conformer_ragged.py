@@ -18,6 +18,7 @@ import torch
 
 from speakerverification_amd import _lib, synth
 from speakerverification_amd.models import Conformer
+from tests.ragged_ring_check import check_async_ring
 from tests.test_gpu_conformer import BF16_BARS, KW, _check, _cos, _engine, _mel, _rel, _sd
 
 pytestmark = pytest.mark.gpu
@@ -200,6 +201,16 @@ def test_a_nonfinite_input_stays_in_its_utterance(compute):
         assert np.isnan(got[1]).all(), name
         assert np.array_equal(got[[0, 2]], clean[[0, 2]]), name
         assert np.array_equal(fn(items), clean), name
+    eng.close()
+
+
+# ---- 6b. more asynchronous calls in flight than table slots ---------------------------------------------------------------------------
+@pytest.mark.parametrize("compute", ["f32", "bf16"])
+def test_six_async_calls_wrap_the_table_slot_ring(compute):
+    """six SVHIP_ASYNC calls in flight over the four pinned table slots of the handle (tests/ragged_ring_check.py)"""
+    eng = _engine(compute, 3, 32000)
+    Ls = [(600, 4000), (8000, 512, 2500), (1200, 5000), (3000, 700, 6100), (2000, 7000), (900, 4500, 1700)]
+    check_async_ring(eng, [[synth.synth_waveforms(1, L, seed=300 + 10 * k + i)[0] for i, L in enumerate(ls)] for k, ls in enumerate(Ls)])
     eng.close()
 
 

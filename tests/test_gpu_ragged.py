@@ -28,6 +28,7 @@ from speakerverification_amd.engine import Engine
 from speakerverification_amd.model import ModelHandling, SpeakerEncoder, WrappedModel
 from tests import ecapa_oracle_check as chk
 from tests.e2e_data import make_e2e_files
+from tests.ragged_ring_check import check_async_ring
 
 pytestmark = pytest.mark.gpu
 
@@ -240,6 +241,15 @@ def test_batch_invariance_bit_for_bit(compute):
             continue
         for n in ref:
             assert np.array_equal(got[n], ref[n]), (compute, name, n, float(np.abs(got[n] - ref[n]).max()))
+    e.close()
+
+
+@pytest.mark.parametrize("compute", ["f32", "bf16"])
+def test_six_async_calls_wrap_the_table_slot_ring(compute):
+    """six SVHIP_ASYNC calls in flight over the four pinned table slots of the handle (tests/ragged_ring_check.py)"""
+    e = _engine(compute, 64)
+    Ts = [(7, 33), (60, 9, 21), (12, 45), (30, 8, 17), (25, 50), (11, 40, 19)]
+    check_async_ring(e, [_waves([_len(T) for T in ts], first=700 + 10 * k) for k, ts in enumerate(Ts)])
     e.close()
 
 

@@ -18,6 +18,7 @@ from oracle import rawnet3 as o_rn3
 from speakerverification_amd import _lib, synth
 from speakerverification_amd.engine import Engine
 from tests.e2e_data import make_e2e_files
+from tests.ragged_ring_check import check_async_ring
 from tests.test_gpu_rawnet3_oracle import BF16_BARS, F32_BARS, SEED_W, STAGES, _layer_local, _rel, _sd_np
 
 pytestmark = pytest.mark.gpu
@@ -142,6 +143,15 @@ def test_batch_invariance_bit_for_bit(compute):
             continue
         for n in ref:
             assert np.array_equal(got[n], ref[n]), (compute, name, n, float(np.abs(got[n] - ref[n]).max()))
+    e.close()
+
+
+@pytest.mark.parametrize("compute", ["f32", "bf16"])
+def test_six_async_calls_wrap_the_table_slot_ring(compute):
+    """six SVHIP_ASYNC calls in flight over the four pinned table slots of the handle (tests/ragged_ring_check.py)"""
+    e = _engine(compute)
+    T0s = [(30, 45), (33, 61, 38), (52, 31), (40, 35, 47), (36, 70), (44, 32, 55)]
+    check_async_ring(e, [_waves(ts, first=700 + 10 * k) for k, ts in enumerate(T0s)])
     e.close()
 
 
