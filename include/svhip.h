@@ -252,6 +252,27 @@ int svhip_conformer_embed_ragged(svhip_handle* h, const float* in, const int64_t
 /* lengths[i] are samples (is_wave != 0) or frames.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is svhip_last_error(NULL). */
 int svhip_conformer_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave);
 
+/* Ragged TitaNet packs (added under ABI v5): the same calls for SVHIP_MODEL_TITANET, the spectral branch of Tita_ECAPA.  The ECAPA,
+ * RawNet3 and Conformer calls above keep refusing a TitaNet handle with SVHIP_ERR_UNSUPPORTED.
+ *   in / offsets / lengths / emb_out / flags / is_wave: the rules of svhip_conformer_embed_ragged.  TitaNet does not subsample, so the
+ *   pack has one frame level: utterance i owns T_i rows of every activation, back to back in utterance order.
+ * CAPACITY, checked on the host before anything is enqueued (svhip_titanet_ragged_check is the same test without a handle):
+ *   1 <= n <= max_batch;  every T_i >= 1;  wave: every lengths[i] >= n_fft;  offsets >= 0;  sum_i T_i <= max_batch * T, T = samples / hop + 1
+ *   (the rows of the workspace the handle owns).
+ * Anything else is SVHIP_ERR_INVALID with a message that names the utterance and the limit.  Compute SVHIP_F32 or SVHIP_BF16 only: every
+ * other model returns SVHIP_ERR_UNSUPPORTED.  The first ragged call of a handle allocates the segment tables and a waveform staging
+ * buffer (once); nothing is allocated per call, and a handle that never sees a ragged call pays nothing.
+ * BATCH INVARIANCE as above: bit-for-bit the same embedding and stages whatever the pack (every GEMM of the ragged forward runs on one
+ * kernel, the depthwise convolutions pad at each utterance's own edges, and the SE squeeze is taken over the utterance's own frames at
+ * both computes); to the precision of the compute type against a fixed-length call, which stays bit for bit what it was.  A non-finite
+ * input gives NaN for its own utterance only, and SVHIP_ERR_NONFINITE.
+ * STAGES after a ragged call: tn_prolog, tn_dw0, tn_mega_last (sum T_i, H) and tn_enc (sum T_i, 1536), rows packed in utterance order;
+ * tn_pool (n, 3072); "mel" the packed (n_mels, T_i) blocks. */
+int svhip_titanet_embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
+                               int32_t flags, int32_t is_wave);
+/* lengths[i] are samples (is_wave != 0) or frames.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is svhip_last_error(NULL). */
+int svhip_titanet_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave);
+
 /* Eval-mode cropping on device.  Replaces, for decoded 16-bit PCM, the cropping half of loadWAV
  * (src/processing/audio_loader.py:110-150): wrap-pad files not longer than L to L+1 samples, take num_eval
  * crops of L samples at int(linspace(0, len - L, num_eval)), scale by 1/32768 (soundfile float32).  pcm holds
@@ -432,6 +453,23 @@ int svhip_conformer_attention(const void* qkv, const float* P, const float* u_bi
  * max_T_sub >= every utterance's length. */
 int svhip_conformer_attention_ragged(const void* qkv, const float* P, const float* u_bias, const float* v_bias, void* ctx, int32_t compute,
                                      const int32_t* row0_dev, int32_t n, int32_t max_T_sub, void* stream);
+
+/* TitaNet's depthwise kernels on their own (tests): device pointers, enqueued on `stream` (NULL: the null stream), not synchronised.
+ * Activations are frame-major (B T, C) in the compute type (SVHIP_F32 / SVHIP_BF16), C % 8 == 0, 16-byte aligned; w is tap-major [k][C]
+ * fp32, bias [C] fp32, k is 3, 7 or 11; gate (B, C) fp32.
+ *   x != NULL:  d = dwconv(x) + bias, zero "same" padding at each utterance's edges (tn_dw; skip / h3 / gate / y are not read).
+ *   x == NULL:  y = relu(skip + gate[b] * h3), and with d != NULL also d = dwconv(y) + bias in the same pass (tn_mega_tail; without d,
+ *               w and bias may be NULL).
+ * SVHIP_OK, SVHIP_ERR_INVALID (arguments, NULL pointers included: nothing is launched) or SVHIP_ERR_HIP (launch). */
+int svhip_titanet_depthwise(const void* x, const void* skip, const void* h3, const float* gate, void* y, const float* w, const float* bias,
+                            void* d, int32_t compute, int32_t k, int32_t B, int32_t T, int32_t C, void* stream);
+
+/* The same kernels over a pack (tests): utterance u owns the rows [row0_dev[u], row0_dev[u + 1]) of every activation (row0_dev: a DEVICE
+ * table of n + 1 ints), gate is (n, C), max_T >= every utterance's length.  The padding sits at each utterance's own edges and no tap reads
+ * a neighbour's row; each utterance comes out exactly as svhip_titanet_depthwise gives it alone (B = 1, T = its length), bit for bit. */
+int svhip_titanet_depthwise_ragged(const void* x, const void* skip, const void* h3, const float* gate, void* y, const float* w,
+                                   const float* bias, void* d, int32_t compute, int32_t k, const int32_t* row0_dev, int32_t n, int32_t max_T,
+                                   int32_t C, void* stream);
 
 /* ResNetSE's 3 x 3 convolution kernel on its own (tests): y = [relu](scale[n] conv3x3_stride([relu](x)) + shift[n]) with zero padding 1.
  * x (B, P, Q, Cin) and y (B, Po, Qo, Cout), Po = (P - 1) / stride + 1, are DEVICE pointers, channels-last, in the compute type (SVHIP_F32 /

@@ -76,6 +76,8 @@ _SIGNATURES = {
     "svhip_rawnet3_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32]),
     "svhip_conformer_embed_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32]),
     "svhip_conformer_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),
+    "svhip_titanet_embed_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32]),
+    "svhip_titanet_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),
     "svhip_crop_pcm16": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     "svhip_l2norm": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32]),
     "svhip_score_pairs": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32]),
@@ -120,6 +122,8 @@ _SIGNATURES = {
     "svhip_selftest": (C.c_int, []),
     "svhip_conformer_attention": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "svhip_conformer_attention_ragged": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P]),
+    "svhip_titanet_depthwise": (C.c_int, [_P] * 8 + [C.c_int32] * 5 + [_P]),
+    "svhip_titanet_depthwise_ragged": (C.c_int, [_P] * 8 + [C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "svhip_resnetse_conv3x3": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 9 + [_P]),
 }
 

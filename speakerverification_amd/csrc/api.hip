@@ -11,8 +11,8 @@
 using namespace svhip;
 
 namespace svhip {      // the ragged hooks of the models that have them: only kModels names them
-RaggedCheckFn ecapa_ragged_check, rawnet3_ragged_check, conformer_ragged_check;
-RaggedEmbedFn ecapa_embed_ragged, rawnet3_embed_ragged, conformer_embed_ragged;          // (RawNet3: waveforms only, is_wave is true)
+RaggedCheckFn ecapa_ragged_check, rawnet3_ragged_check, conformer_ragged_check, titanet_ragged_check;
+RaggedEmbedFn ecapa_embed_ragged, rawnet3_embed_ragged, conformer_embed_ragged, titanet_embed_ragged;      // (RawNet3: waveforms only, is_wave is true)
 }
 
 namespace {
@@ -72,7 +72,7 @@ const ModelOps kModels[] = {
     {SVHIP_MODEL_RAWNET3,      rawnet3_check,   rawnet3_spec,   rawnet3_finalize,   rawnet3_alloc,   rawnet3_forward,     nullptr,           rawnet3_stage,   4,
      nullptr, rawnet3_ragged_check, rawnet3_embed_ragged},
     {SVHIP_MODEL_TITANET,      titanet_check,   titanet_spec,   titanet_finalize,   titanet_alloc,   fbank_then_features, titanet_forward,   titanet_stage,   4,
-     "encoder.mega_blocks."},       // (the block count follows from what was loaded: titanet_finalize checks its blocks)
+     "encoder.mega_blocks.", titanet_ragged_check, titanet_embed_ragged},      // (the block count follows from what was loaded: titanet_finalize checks its blocks)
     {SVHIP_MODEL_CONFORMER,    conformer_check, conformer_spec, conformer_finalize, conformer_alloc, fbank_then_features, conformer_forward, conformer_stage, 4,
      nullptr, conformer_ragged_check, conformer_embed_ragged},
     {SVHIP_MODEL_RESNETSE,     resnetse_check,  resnetse_spec,  resnetse_finalize,  resnetse_alloc,  fbank_then_features, resnetse_forward,  resnetse_stage,  4},
@@ -211,13 +211,13 @@ int emit_embeddings(svhip_handle* h, int B, float* emb_out, int flags) {
 // Each ragged export serves one model (kModels names its check and its forward) and refuses the others by its name
 struct RaggedExport { int model; const char* name; };
 constexpr RaggedExport kRagEcapa{SVHIP_MODEL_ECAPA, "ECAPA"}, kRagRawnet3{SVHIP_MODEL_RAWNET3, "RAWNET3"},
-                       kRagConformer{SVHIP_MODEL_CONFORMER, "CONFORMER"};
+                       kRagConformer{SVHIP_MODEL_CONFORMER, "CONFORMER"}, kRagTitanet{SVHIP_MODEL_TITANET, "TITANET"};
 
 // the rules of a pack, on the host alone, in this order: the scope, the model's rules on the configuration, the pack size, the model's
 // rules on every utterance in index order
 int ragged_rules(const RaggedExport& x, const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
     if (c.model != x.model)
-        return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: SVHIP_MODEL_%s only (ECAPA, RawNet3 and Conformer packs have their own calls; the "
+        return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: SVHIP_MODEL_%s only (ECAPA, RawNet3, Conformer and TitaNet packs have their own calls; the "
                       "other models embed one length per handle)", x.name, x.name);
     if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16)
         return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: compute SVHIP_F32 or SVHIP_BF16 only", x.name);
@@ -531,6 +531,15 @@ int svhip_conformer_embed_ragged(svhip_handle* h, const float* in, const int64_t
 
 int svhip_conformer_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave) {
     return ragged_check(kRagConformer, cfg, lengths, n, is_wave != 0);
+}
+
+int svhip_titanet_embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
+                               int32_t flags, int32_t is_wave) {
+    return embed_ragged(kRagTitanet, h, in, offsets, lengths, n, emb_out, flags, is_wave != 0);
+}
+
+int svhip_titanet_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave) {
+    return ragged_check(kRagTitanet, cfg, lengths, n, is_wave != 0);
 }
 
 int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, const int64_t* offsets, const int32_t* lengths,

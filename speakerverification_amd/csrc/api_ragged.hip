@@ -1,4 +1,4 @@
-// api_ragged.hip — what the ragged calls of ECAPA-TDNN, RawNet3 and the Conformer share on the host: the refusal texts, the table ring
+// api_ragged.hip — what the ragged calls of ECAPA-TDNN, RawNet3, the Conformer and TitaNet share on the host: the refusal texts, the table ring
 // (RagTables) and the mel input of a pack.  Each model's own rules, table layout and forward stay in its api_<model>.hip.
 #include <cstdarg>
 
@@ -58,7 +58,7 @@ RagTables::~RagTables() {
     }
 }
 
-// ---- the mel input of a pack (ECAPA-TDNN, Conformer) ---------------------------------------------------------
+// ---- the mel input of a pack (ECAPA-TDNN, Conformer, TitaNet) ---------------------------------------------------------
 int rag_mel_input(svhip_handle* h, RagTables& rag, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths,
                   int n, const int* mel0, int64_t* feat_off, const float** d_feat) {
     const svhip_config& c = h->cfg;

@@ -13,6 +13,12 @@
 //                                                              when its kernel writes them; otherwise colmean)
 //   SE       g = sigmoid(W2 relu(W1 mean_t S))                   se_mlp (zero biases)
 //   tail     X = relu(K + g S) and D = dw_1'(X) + b' of the next block in the same pass      tn_mega_tail
+//
+// A ragged pack (titanet_embed_ragged): n utterances of T_u mel frames back to back, sum T_u <= Bmax T rows of the same buffers.  The
+// network has no subsampling, so the pack has one frame level and one row0 table.  Every GEMM goes through launch_gemm_ragged (the
+// prolog's three taps zero-padded at each utterance's own ends), the depthwise convs and the block tail run in their segment-table
+// forms, and the SE squeeze, the pooling, the input test and the last linear layer are ragged.hip's: no value of an utterance depends on
+// what it is packed with.
 #include <cmath>
 #include <cstdlib>
 
@@ -48,6 +54,11 @@ struct TitaNetState : ModelState {
     float* logits = nullptr;              // (Bmax T, 1536) fp32 attention energies
     float *mean = nullptr, *gate = nullptr;                  // (Bmax, H) SE squeeze, SE gate
     float *pool_raw = nullptr, *pool = nullptr;              // (Bmax, 3072) pooled [mean | std], after BN
+    // ragged packs (allocated by the first ragged call; the buffers above already hold Bmax T rows)
+    RagTables rag;                        // the tables of a call: feature offsets (Bmax int64), row0 (Bmax + 1)
+    int64_t* rag_feat_off = nullptr;
+    int* rag_row0 = nullptr;
+    int* rag_utt = nullptr;               // (Bmax T) utterance of every row
 };
 
 TitaNetState& S(svhip_handle* h) { return static_cast<TitaNetState&>(*h->model); }
@@ -295,6 +306,139 @@ static int titanet_forward_part(svhip_handle* h, const float* d_feat, int b0, in
 
 int titanet_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, titanet_forward_part, d_feat, B, 1, B); }
 
+// ---- ragged packs ------------------------------------------------------------------------------------------
+// TitaNet's rules for a pack (RaggedCheckFn; include/svhip.h), on the host alone
+int titanet_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
+    if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft) return refuse(err, SVHIP_ERR_INVALID, "bad hop_length / max_batch / samples");
+    const int64_t cap = (int64_t)c.max_batch * mel_frames(c, c.samples, true);
+    int64_t rows = 0;
+    for (int i = 0; i < n; ++i) {
+        if (is_wave && lengths[i] < c.n_fft)
+            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld samples, fewer than n_fft=%d", i, (long long)lengths[i], c.n_fft);
+        const int64_t T = mel_frames(c, lengths[i], is_wave);
+        if (T < 1) return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld frames, fewer than 1", i, (long long)T);
+        if (int rc = rag_rows_fit(err, i, rows += T, cap, "T")) return rc;
+    }
+    return SVHIP_OK;
+}
+
+// the segment tables, the waveform staging buffer and the pinned table slots: once per handle
+static int titanet_ragged_alloc(svhip_handle* h) {
+    auto& s = S(h);
+    if (s.rag.dev) return SVHIP_OK;
+    const svhip_config& c = h->cfg;
+    const size_t B = c.max_batch;
+    int rc;
+    if (!s.rag_utt && (rc = dev_alloc(h, &s.rag_utt, B * (size_t)h->T))) return rc;
+    if ((rc = s.rag.alloc(h, B * 8 + (B + 1) * 4, B * ((size_t)c.samples + c.hop_length)))) return rc;
+    s.rag_feat_off = reinterpret_cast<int64_t*>(s.rag.dev);
+    s.rag_row0 = reinterpret_cast<int*>(s.rag.dev + B * 8);
+    return SVHIP_OK;
+}
+
+// TitaNet.forward over the packed rows of a ragged batch (features at d_feat + rag_feat_off[u]; tables on the device).  One slice on the
+// handle's stream.  Every GEMM goes to the generic kernel (launch_gemm_ragged: one kernel at every row count, so a row's sums do not depend
+// on the pack), which is why the bf16 handles' column-sum squeeze is not used here: the squeeze is launch_rag_colstats at both computes.
+static int titanet_forward_ragged(svhip_handle* h, const float* d_feat, int n, int M, int maxT) {
+    auto& s = S(h);
+    const svhip_config& c = h->cfg;
+    const int H = c.channels, E = 1536, k = s.k, dt = h->dt;
+    const bool bf = h->bf16;
+    hipStream_t st = h->cur = h->stream;
+    const int* row0 = s.rag_row0;
+    void *PRO = s.buf[0], *X = s.buf[1], *D0 = s.buf[2], *D = s.buf[3], *Sb = s.buf[4], *K = s.buf[5];
+    int rc;
+    auto gemm = [&](const ConvLayer& L, GemmParams p) {
+        p.rag_utt = s.rag_utt; p.rag_row0 = row0;
+        return run(h, "rag_gemm", (double)M * L.flops_per_row, [&]() { return launch_gemm_ragged(p, bf, st); });
+    };
+    auto dw = [&](const void* x, void* d, const float* w, const float* b) {
+        return run(h, "tn_dw_rag", 2.0 * k * H * M, [&]() { return launch_tn_dw_ragged(x, d, w, b, dt, k, row0, n, maxT, H, st); });
+    };
+    if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(row0, n, maxT, s.rag_utt, st); }))) return rc;
+    // the mel power as it is (no log, no normalisation) -> the packed rows (M, n_mels) in the compute type
+    if ((rc = run(h, "rag_prologue", 0, [&]() {
+             return launch_rag_prologue(d_feat, s.rag_feat_off, row0, n, maxT, h->X_in, bf, c.n_mels, 0, nullptr, nullptr, h->d_pstats, st);
+         }))) return rc;
+    GemmParams pp = conv_params(h, s.prolog, h->X_in, c.n_mels, PRO, H, M, 1);
+    pp.act1 = ACT_RELU; pp.pad_mode = PAD_ZERO;
+    if ((rc = gemm(s.prolog, pp))) return rc;
+    const int nb = (int)s.blocks.size();
+    const void* x = PRO;
+    for (int i = 0; i < nb; ++i) {
+        const TnBlock& Bk = s.blocks[i];
+        if ((rc = gemm(Bk.skip, conv_params(h, Bk.skip, x, H, K, H, M, 1)))) return rc;
+        if (i == 0 && (rc = dw(x, D0, Bk.dw_w[0], Bk.dw_b[0]))) return rc;
+        const void* d = i == 0 ? D0 : D;
+        for (int j = 0; j < 3; ++j) {
+            GemmParams p = conv_params(h, Bk.pw[j], d, H, Sb, H, M, 1);
+            p.act1 = ACT_RELU;
+            if ((rc = gemm(Bk.pw[j], p))) return rc;
+            if (j < 2) {
+                if ((rc = dw(Sb, D, Bk.dw_w[j + 1], Bk.dw_b[j + 1]))) return rc;
+                d = D;
+            }
+        }
+        if ((rc = run(h, "rag_se_mean", 0, [&]() { return launch_rag_colstats(Sb, bf, H, row0, n, H, s.mean, false, 0.0f, st); }))) return rc;
+        if ((rc = run(h, "tn_se_mlp", 4.0 * n * (H / 16) * H, [&]() {
+                 return launch_se_mlp(s.mean, nullptr, 1, bf ? Bk.se1_bf : (const void*)Bk.se1, h->d_zeros, bf ? Bk.se2T_bf : (const void*)Bk.se2T,
+                                      h->d_zeros, s.gate, bf, n, H, H / 16, st, 8);
+             }))) return rc;
+        const TnBlock* nx = i + 1 < nb ? &s.blocks[i + 1] : nullptr;
+        if ((rc = run(h, "tn_mega_tail_rag", nx ? 2.0 * k * H * M : 0.0, [&]() {
+                 return launch_tn_mega_tail_ragged(K, Sb, s.gate, X, nx ? nx->dw_w[0] : nullptr, nx ? nx->dw_b[0] : nullptr, nx ? D : nullptr, dt, k,
+                                                   row0, n, maxT, H, st);
+             }))) return rc;
+        x = X;
+    }
+    GemmParams pe = conv_params(h, s.epilog, x, H, s.enc, E, M, 1);
+    pe.act1 = ACT_RELU;
+    if ((rc = gemm(s.epilog, pe))) return rc;
+    GemmParams pa = conv_params(h, s.att_in, s.enc, E, s.att, 128, M, 1);
+    pa.act2 = ACT_TANH;
+    if ((rc = gemm(s.att_in, pa))) return rc;
+    GemmParams pl = conv_params(h, s.att_out, s.att, 128, s.logits, E, M, 1);
+    pl.out_f32 = 1;
+    if ((rc = gemm(s.att_out, pl))) return rc;
+    if ((rc = run(h, "rag_asp_pool", 0, [&]() {
+             return launch_rag_asp_pool(s.logits, s.enc, bf, E, row0, n, E, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-6f, st);
+         }))) return rc;
+    // an utterance with a non-finite input value gets a NaN embedding: its own row only
+    if ((rc = run(h, "tn_in_check", 0, [&]() {
+             return launch_tn_nonfinite_rows_ragged(d_feat, s.rag_feat_off, row0, c.n_mels, n, s.pool, 2 * E, 2 * E, st);
+         }))) return rc;
+    return run(h, "rag_fc", 2.0 * n * s.fc.N * s.fc.K, [&]() {
+        return launch_rag_linear(s.pool, 2 * E, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, n, c.embed_dim, 2 * E, ACT_NONE, st);
+    });
+}
+
+int titanet_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n) {
+    auto& s = S(h);
+    const svhip_config& c = h->cfg;
+    int rc = titanet_ragged_alloc(h);
+    if (rc) return rc;
+    const size_t B = c.max_batch;
+    char* tab = nullptr;
+    if ((rc = s.rag.acquire(h, &tab))) return rc;
+    int64_t* feat_off = reinterpret_cast<int64_t*>(tab);
+    int* row0 = reinterpret_cast<int*>(tab + B * 8);
+    int M = 0, maxT = 0;
+    for (int u = 0; u < n; ++u) {
+        const int T = (int)mel_frames(c, lengths[u], is_wave);
+        row0[u] = M;
+        M += T;
+        maxT = std::max(maxT, T);
+    }
+    row0[n] = M;
+    const float* d_feat = nullptr;
+    if ((rc = rag_mel_input(h, s.rag, in, in_host, is_wave, in_off, lengths, n, row0, feat_off, &d_feat))) return rc;
+    if ((rc = s.rag.commit(h, B * 8 + (size_t)(n + 1) * 4))) return rc;
+    if ((rc = titanet_forward_ragged(h, d_feat, n, M, maxT))) return rc;
+    set_rag_rows(h, n, {M});
+    return SVHIP_OK;
+}
+
+// (after a ragged forward the (rows, H) stages and tn_enc are the packed sum T_i rows: svhip_get_stage sets them from rag_rows)
 int titanet_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // tn_prolog, tn_dw0, tn_mega_last, tn_enc, tn_pool
     auto& s = S(h);
     const int H = h->cfg.channels;
@@ -308,3 +452,35 @@ int titanet_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {  
 }
 
 }  // namespace svhip
+
+// ---- test exports: the depthwise kernels alone (include/svhip.h) ---------------------------------------------------
+namespace {
+
+// x != null: tn_dw; x == null: the block tail (with d also the next depthwise conv).  ragged: the pack forms, B = n and T = max_T
+int tn_depthwise_export(const void* x, const void* skip, const void* h3, const float* gate, void* y, const float* w, const float* bias, void* d,
+                        int compute, int k, int B, int T, int C, const int* row0, bool ragged, void* stream) {
+    using namespace svhip;
+    if (compute != SVHIP_F32 && compute != SVHIP_BF16) return SVHIP_ERR_INVALID;
+    if (k != 3 && k != 7 && k != 11) return SVHIP_ERR_INVALID;
+    if (ragged && !row0) return SVHIP_ERR_INVALID;
+    const int dt = compute == SVHIP_BF16 ? DT_BF16 : DT_F32;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipError_t e;
+    if (x) e = ragged ? launch_tn_dw_ragged(x, d, w, bias, dt, k, row0, B, T, C, st) : launch_tn_dw(x, d, w, bias, dt, k, B, T, C, st);
+    else e = ragged ? launch_tn_mega_tail_ragged(skip, h3, gate, y, w, bias, d, dt, k, row0, B, T, C, st)
+                    : launch_tn_mega_tail(skip, h3, gate, y, w, bias, d, dt, k, B, T, C, st);
+    return e == hipSuccess ? SVHIP_OK : e == hipErrorInvalidValue ? SVHIP_ERR_INVALID : SVHIP_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" int svhip_titanet_depthwise(const void* x, const void* skip, const void* h3, const float* gate, void* y, const float* w, const float* bias,
+                                       void* d, int32_t compute, int32_t k, int32_t B, int32_t T, int32_t C, void* stream) {
+    return tn_depthwise_export(x, skip, h3, gate, y, w, bias, d, compute, k, B, T, C, nullptr, false, stream);
+}
+
+extern "C" int svhip_titanet_depthwise_ragged(const void* x, const void* skip, const void* h3, const float* gate, void* y, const float* w,
+                                              const float* bias, void* d, int32_t compute, int32_t k, const int32_t* row0_dev, int32_t n,
+                                              int32_t max_T, int32_t C, void* stream) {
+    return tn_depthwise_export(x, skip, h3, gate, y, w, bias, d, compute, k, n, max_T, C, row0_dev, true, stream);
+}

@@ -126,7 +126,7 @@ struct svhip_handle {
     float* d_emb = nullptr;
     int lastB = 0;
     // the last forward when it was a ragged one (svhip_get_stage): the packed rows of each of its rag_levels frame levels, the input's first
-    // (ECAPA: mel frames; Conformer: mel frames, subsampled frames; RawNet3: its levels 0 .. 2).  rag_levels = 0: a fixed-length forward
+    // (ECAPA, TitaNet: mel frames; Conformer: mel frames, subsampled frames; RawNet3: its levels 0 .. 2).  rag_levels = 0: a fixed-length forward
     int64_t rag_rows[3] = {};
     int rag_levels = 0;
     // shared by several models: each is allocated by the alloc / finalize hook of the models named, and null on the others' handles

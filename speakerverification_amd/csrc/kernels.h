@@ -472,6 +472,13 @@ hipError_t launch_tn_dw(const void* x, void* d, const float* w, const float* bia
 // depthwise layer) in the same pass, y recomputed on the halo rows
 hipError_t launch_tn_mega_tail(const void* skip, const void* h3, const float* gate, void* y, const float* w, const float* bias, void* d, int dt, int k,
                                int B, int Tn, int C, hipStream_t stream);
+// The same two over a ragged pack: utterance u owns the rows [row0[u], row0[u + 1]) (row0: n + 1 ints on the device), max_T >= every
+// T_u, gate (n, C).  The padding sits at each utterance's own edges and no tap reads a neighbour's row; an utterance's values are bit for
+// bit those of the fixed form at B = 1, Tn = T_u.  n <= 65535.
+hipError_t launch_tn_dw_ragged(const void* x, void* d, const float* w, const float* bias, int dt, int k, const int* row0, int n, int max_T, int C,
+                               hipStream_t stream);
+hipError_t launch_tn_mega_tail_ragged(const void* skip, const void* h3, const float* gate, void* y, const float* w, const float* bias, void* d, int dt,
+                                      int k, const int* row0, int n, int max_T, int C, hipStream_t stream);
 
 // rows[b, 0:n) (row stride ld) = NaN for every utterance b whose input x[b * per_utt .. (b + 1) * per_utt) holds an inf / NaN
 hipError_t launch_tn_nonfinite_rows(const float* x, int64_t per_utt, int B, float* rows, int ld, int n, hipStream_t stream);

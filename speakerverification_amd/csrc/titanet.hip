@@ -1,6 +1,8 @@
 // titanet.hip — TitaNet's depthwise time-context path (reference models/TitaNet.py:253-318, blocks/titanet_blocks.py:47-97).
 //
-// Activations are frame-major (B T, C): the rows of B utterances stacked.  Both kernels walk a tile of TT frames of ONE utterance for
+// Activations are frame-major (B T, C): the rows of B utterances stacked — or, in a ragged pack, n utterances of T_u rows each, back to
+// back, utterance u owning the rows [row0[u], row0[u + 1]) of a device table (the *_ragged forms).
+// Both kernels walk a tile of TT frames of ONE utterance for
 // one 16-byte vector of channels per thread (4 fp32 / 8 bf16): the TT + K - 1 input rows the tile needs are loaded into registers
 // first (every load of the thread in flight at once), rows outside [0, T) of the utterance are zero — the "same" zero padding of
 // Conv1dSamePadding at each utterance's own edges, so a tap never reads a neighbouring utterance — and the K taps are applied in a
@@ -22,24 +24,38 @@ namespace {
 // frame: half the tile keeps it at the depthwise kernel's register count
 template <int K, bool TAIL> struct TnTile { static constexpr int TT = TAIL && K > 1 ? 8 : 16; };
 
-template <typename T, int K, bool TAIL, bool DW>
+// RAG (a pack, grid (x, n)): utterance blockIdx.y owns the rows [rag_row0[b], rag_row0[b + 1]) and Tn is its own length; grid.x holds the
+// tiles of the longest utterance, and the threads past an utterance's last tile leave before they load anything.  From there on the
+// thread runs the fixed kernel's code on (row0, Tn, t0), so an utterance's values are those of the fixed kernel at B = 1, Tn = T_u.
+template <typename T, int K, bool TAIL, bool DW, bool RAG>
 __global__ __launch_bounds__(256) void tn_dw_kernel(const T* __restrict__ x, const T* __restrict__ skip, const T* __restrict__ h3,
                                                     const float* __restrict__ gate, T* __restrict__ y, const float* __restrict__ w,
-                                                    const float* __restrict__ bias, T* __restrict__ d, int B, int Tn, int C) {
+                                                    const float* __restrict__ bias, T* __restrict__ d, int B, int Tn, int C,
+                                                    const int* __restrict__ rag_row0) {
     constexpr int VEC = Vec16<T>::N;
     constexpr int R = K / 2;
     constexpr int TT = TnTile<K, TAIL>::TT;
     constexpr int NR = DW ? TT + 2 * R : TT;          // rows held in registers
     const int nvec = C / VEC;
-    const int ntile = (Tn + TT - 1) / TT;
     const int g = blockIdx.x * 256 + threadIdx.x;
     const int v = g % nvec;
     const int q = g / nvec;
-    const int b = q / ntile;
-    if (b >= B) return;
-    const int t0 = (q - b * ntile) * TT;
+    int b, t0;
+    int64_t row0;
+    if constexpr (RAG) {
+        b = blockIdx.y;
+        row0 = rag_row0[b];
+        Tn = rag_row0[b + 1] - (int)row0;
+        if (q >= (Tn + TT - 1) / TT) return;
+        t0 = q * TT;
+    } else {
+        const int ntile = (Tn + TT - 1) / TT;
+        b = q / ntile;
+        if (b >= B) return;
+        t0 = (q - b * ntile) * TT;
+        row0 = (int64_t)b * Tn;
+    }
     const int c0 = v * VEC;
-    const int64_t row0 = (int64_t)b * Tn;
     const int r0 = DW ? R : 0;                        // register row i holds frame t0 - r0 + i
 
     float gv[VEC];
@@ -110,25 +126,32 @@ __global__ __launch_bounds__(256) void tn_dw_kernel(const T* __restrict__ x, con
     }
 }
 
+// row0 == null: B utterances of Tn frames.  A pack: B = n utterances by the device table row0, Tn = the longest utterance's frames
 template <typename T, int K, bool TAIL, bool DW>
 hipError_t launch_k(const void* x, const void* skip, const void* h3, const float* gate, void* y, const float* w, const float* bias, void* d,
-                    int B, int Tn, int C, hipStream_t stream) {
+                    int B, int Tn, int C, const int* row0, hipStream_t stream) {
     constexpr int TT = TnTile<K, TAIL>::TT;
-    const int64_t threads = (int64_t)B * ((Tn + TT - 1) / TT) * (C / Vec16<T>::N);
-    if (threads >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((tn_dw_kernel<T, K, TAIL, DW>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, (const T*)x, (const T*)skip,
-                       (const T*)h3, gate, (T*)y, w, bias, (T*)d, B, Tn, C);
+    const int64_t per_utt = (int64_t)((Tn + TT - 1) / TT) * (C / Vec16<T>::N);
+    const int64_t threads = row0 ? per_utt : B * per_utt;
+    if (threads >= ((int64_t)1 << 31) || (row0 && B > 65535)) return hipErrorInvalidValue;
+    const unsigned gx = (unsigned)((threads + 255) / 256);
+    if (row0)
+        hipLaunchKernelGGL((tn_dw_kernel<T, K, TAIL, DW, true>), dim3(gx, (unsigned)B), dim3(256), 0, stream, (const T*)x, (const T*)skip,
+                           (const T*)h3, gate, (T*)y, w, bias, (T*)d, B, 0, C, row0);
+    else
+        hipLaunchKernelGGL((tn_dw_kernel<T, K, TAIL, DW, false>), dim3(gx), dim3(256), 0, stream, (const T*)x, (const T*)skip,
+                           (const T*)h3, gate, (T*)y, w, bias, (T*)d, B, Tn, C, nullptr);
     return hipGetLastError();
 }
 
 template <typename T, bool TAIL>
 hipError_t launch_by_k(int k, const void* x, const void* skip, const void* h3, const float* gate, void* y, const float* w, const float* bias, void* d,
-                       int B, int Tn, int C, hipStream_t stream) {
-    if (TAIL && !d) return launch_k<T, 1, true, false>(x, skip, h3, gate, y, w, bias, d, B, Tn, C, stream);
+                       int B, int Tn, int C, const int* row0, hipStream_t stream) {
+    if (TAIL && !d) return launch_k<T, 1, true, false>(x, skip, h3, gate, y, w, bias, d, B, Tn, C, row0, stream);
     switch (k) {
-        case 3: return launch_k<T, 3, TAIL, true>(x, skip, h3, gate, y, w, bias, d, B, Tn, C, stream);
-        case 7: return launch_k<T, 7, TAIL, true>(x, skip, h3, gate, y, w, bias, d, B, Tn, C, stream);
-        case 11: return launch_k<T, 11, TAIL, true>(x, skip, h3, gate, y, w, bias, d, B, Tn, C, stream);
+        case 3: return launch_k<T, 3, TAIL, true>(x, skip, h3, gate, y, w, bias, d, B, Tn, C, row0, stream);
+        case 7: return launch_k<T, 7, TAIL, true>(x, skip, h3, gate, y, w, bias, d, B, Tn, C, row0, stream);
+        case 11: return launch_k<T, 11, TAIL, true>(x, skip, h3, gate, y, w, bias, d, B, Tn, C, row0, stream);
         default: return hipErrorInvalidValue;
     }
 }
@@ -181,20 +204,41 @@ hipError_t launch_tn_nonfinite_rows_ragged(const float* x, const int64_t* off, c
     return hipGetLastError();
 }
 
-hipError_t launch_tn_dw(const void* x, void* d, const float* w, const float* bias, int dt, int k, int B, int Tn, int C, hipStream_t stream) {
-    if (!shape_ok(dt, k, B, Tn, C) || !x || !d || !w || !bias) return hipErrorInvalidValue;
+// (ragged != 0: the pack forms, which need their table)
+static hipError_t tn_dw_any(const void* x, void* d, const float* w, const float* bias, int dt, int k, int B, int Tn, int C, const int* row0, bool ragged,
+                            hipStream_t stream) {
+    if (!shape_ok(dt, k, B, Tn, C) || !x || !d || !w || !bias || (ragged && !row0)) return hipErrorInvalidValue;
     if (!aligned16(x) || !aligned16(d) || !aligned16(w) || !aligned16(bias)) return hipErrorInvalidValue;
-    if (dt == DT_BF16) return launch_by_k<bf16_t, false>(k, x, nullptr, nullptr, nullptr, nullptr, w, bias, d, B, Tn, C, stream);
-    return launch_by_k<float, false>(k, x, nullptr, nullptr, nullptr, nullptr, w, bias, d, B, Tn, C, stream);
+    if (dt == DT_BF16) return launch_by_k<bf16_t, false>(k, x, nullptr, nullptr, nullptr, nullptr, w, bias, d, B, Tn, C, row0, stream);
+    return launch_by_k<float, false>(k, x, nullptr, nullptr, nullptr, nullptr, w, bias, d, B, Tn, C, row0, stream);
+}
+
+static hipError_t tn_mega_tail_any(const void* skip, const void* h3, const float* gate, void* y, const float* w, const float* bias, void* d, int dt,
+                                   int k, int B, int Tn, int C, const int* row0, bool ragged, hipStream_t stream) {
+    if (!shape_ok(dt, d ? k : 3, B, Tn, C) || !skip || !h3 || !gate || !y || (d && (!w || !bias)) || (ragged && !row0)) return hipErrorInvalidValue;
+    if (!aligned16(skip) || !aligned16(h3) || !aligned16(gate) || !aligned16(y) || (d && (!aligned16(d) || !aligned16(w) || !aligned16(bias))))
+        return hipErrorInvalidValue;
+    if (dt == DT_BF16) return launch_by_k<bf16_t, true>(k, nullptr, skip, h3, gate, y, w, bias, d, B, Tn, C, row0, stream);
+    return launch_by_k<float, true>(k, nullptr, skip, h3, gate, y, w, bias, d, B, Tn, C, row0, stream);
+}
+
+hipError_t launch_tn_dw(const void* x, void* d, const float* w, const float* bias, int dt, int k, int B, int Tn, int C, hipStream_t stream) {
+    return tn_dw_any(x, d, w, bias, dt, k, B, Tn, C, nullptr, false, stream);
 }
 
 hipError_t launch_tn_mega_tail(const void* skip, const void* h3, const float* gate, void* y, const float* w, const float* bias, void* d, int dt, int k,
                                int B, int Tn, int C, hipStream_t stream) {
-    if (!shape_ok(dt, d ? k : 3, B, Tn, C) || !skip || !h3 || !gate || !y || (d && (!w || !bias))) return hipErrorInvalidValue;
-    if (!aligned16(skip) || !aligned16(h3) || !aligned16(gate) || !aligned16(y) || (d && (!aligned16(d) || !aligned16(w) || !aligned16(bias))))
-        return hipErrorInvalidValue;
-    if (dt == DT_BF16) return launch_by_k<bf16_t, true>(k, nullptr, skip, h3, gate, y, w, bias, d, B, Tn, C, stream);
-    return launch_by_k<float, true>(k, nullptr, skip, h3, gate, y, w, bias, d, B, Tn, C, stream);
+    return tn_mega_tail_any(skip, h3, gate, y, w, bias, d, dt, k, B, Tn, C, nullptr, false, stream);
+}
+
+hipError_t launch_tn_dw_ragged(const void* x, void* d, const float* w, const float* bias, int dt, int k, const int* row0, int n, int max_T, int C,
+                               hipStream_t stream) {
+    return tn_dw_any(x, d, w, bias, dt, k, n, max_T, C, row0, true, stream);
+}
+
+hipError_t launch_tn_mega_tail_ragged(const void* skip, const void* h3, const float* gate, void* y, const float* w, const float* bias, void* d, int dt,
+                                      int k, const int* row0, int n, int max_T, int C, hipStream_t stream) {
+    return tn_mega_tail_any(skip, h3, gate, y, w, bias, d, dt, k, n, max_T, C, row0, true, stream);
 }
 
 }  // namespace svhip

@@ -92,6 +92,7 @@ _RAGGED = {
                             lambda n, hop: (n - 251) // 10 + 1),       # the frames after its sinc filterbank (251 taps, stride 10)
     "conformer": _RaggedCalls(("svhip_conformer_embed_ragged", 1), ("svhip_conformer_embed_ragged", 0), "svhip_conformer_ragged_check", True,
                               _MEL_FRAMES),
+    "titanet": _RaggedCalls(("svhip_titanet_embed_ragged", 1), ("svhip_titanet_embed_ragged", 0), "svhip_titanet_ragged_check", True, _MEL_FRAMES),
 }
 
 

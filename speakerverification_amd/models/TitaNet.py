@@ -8,11 +8,12 @@
 TitaNet reads its input as it is (no log, no normalisation).  Sizes s / m / l are H = 256 / 512 / 1024 with depthwise kernels 3 / 7 /
 11; ``n_mega_blocks=None`` takes ``find_n_mega_blocks``' choice, restated in closed form (synth.titanet_n_mega_blocks).  State-dict keys
 are the reference's.  Computes: "f32" and "bf16" ("half" means bf16 here).  ``device`` is accepted as the reference requires it.
+``embed_ragged`` embeds utterances of different lengths in shared calls of the primary handle (whole-file evaluation).
 """
 from __future__ import annotations
 
 from .. import synth
-from ._base import HipModule
+from ._base import HipModule, RaggedMixin
 
 MIN_SAMPLES = 512           # the mel front-end's n_fft (one frame of the library's front-end)
 
@@ -24,7 +25,7 @@ def _crop_samples(audio_spec):
         return None
 
 
-class TitaNet(HipModule):
+class TitaNet(RaggedMixin, HipModule):
     model_kind = "titanet"
 
     def __init__(self, nOut=512, model_size="l", n_mega_blocks=None, device=None, compute=None, max_batch=None, **kwargs):
@@ -72,6 +73,21 @@ class TitaNet(HipModule):
         """fused waveform -> embedding (mel front-end + forward in one library call)"""
         eng = self._engine_for(wav)
         return self._squeeze(self._batched(eng.embed_wave, wav, eng.max_batch))
+
+    # ---- ragged batches (RaggedMixin): the rows are mel frames ----------------------------------------------------------------
+    MIN_FRAMES = 1                  # no subsampling and zero padding: one frame is an utterance
+
+    def _ragged_geometry(self):
+        """(max_batch, row capacity) of the primary handle, from the module's own settings (no handle is built)"""
+        frames = (self._primary or self.DEFAULT_PRIMARY) // self._hop + 1
+        return self._max_batch, self._max_batch * frames
+
+    def ragged_frames(self, n_samples):
+        """mel frames of an utterance of n_samples; 0 for one shorter than the front-end's FFT window, which fits no ragged call"""
+        return 0 if n_samples < self._min_samples else int(n_samples) // int(self._hop) + 1
+
+    def _ragged_limits(self):
+        return f"; at least {self._min_samples} samples each"
 
 
 def MainModel(nOut=512, model_size="l", n_mega_blocks=None, **kwargs):

@@ -5,7 +5,9 @@
     emb = model(wav)            # (B, 32000) -> (B, 512)
 
 State-dict keys: ``ECAPA_TDNN.*`` and ``titaNet.*``; ``compute_features.*`` is ignored.  Each branch runs its own mel front-end on its
-own handle (and, for device-resident batches, its own stream).  The shared body is models/_fusion.py.
+own handle (and, for device-resident batches, its own stream).  The shared body is models/_fusion.py.  Both branches have a ragged
+forward, so ``embed_ragged`` / ``ragged_packer`` / ``ragged_frames`` are offered: whole files of different lengths share calls of the two
+primary handles, one plan for both (ragged.FusionPacker).
 """
 from __future__ import annotations
 

@@ -148,8 +148,9 @@ class RawECAPAFusion:
     __call__ = forward
 
     # ---- ragged batches: whole files of different lengths in shared calls of BOTH branches' primary handles ---------------
-    # Offered only when both branches have embed_ragged (ECAPA-TDNN + RawNet3: Raw3_ECAPA); on the RawNet2 and TitaNet fusions
-    # these attributes do not exist (__getattr__), so whole-file evaluation keeps the per-file path there.
+    # Offered only when both branches have embed_ragged (ECAPA-TDNN + RawNet3: Raw3_ECAPA; ECAPA-TDNN + TitaNet: Tita_ECAPA); on the
+    # RawNet2 fusions (Raw_ECAPA*, Raw_tita) these attributes do not exist (__getattr__), so whole-file evaluation keeps the per-file
+    # path there.
     _RAGGED = ("ragged_packer", "ragged_frames", "embed_ragged")
 
     def __getattr__(self, name):

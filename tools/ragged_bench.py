@@ -1,6 +1,6 @@
 """Whole-file evaluation (num_eval = 0) on the MI355X: files/s of `ModelHandling._embed_files` over seeded files of 2 - 20 s.
 
-    python tools/ragged_bench.py [--model ECAPA_TDNN|RawNet3|Raw3_ECAPA|Conformer] [--per-file] [--files 512] [--runs 5] [--compute bf16,f32]
+    python tools/ragged_bench.py [--model ECAPA_TDNN|RawNet3|Raw3_ECAPA|Conformer|TitaNet|Tita_ECAPA] [--per-file] [--files 512] [--runs 5] [--compute bf16,f32]
                                  [--out profiles/ragged_bench.json]
 
 Default mode: the ragged path of this tree (files of different lengths share calls of the model's primary handle), plus, without a
@@ -14,7 +14,10 @@ Own process; every figure is the median of `--runs` timed passes over the whole 
 (min, max); wall time and HIP-event time around the whole pass are both given.  ECAPA-TDNN C = 1024, nOut 192; with --model RawNet3
 (nOut 320) or Raw3_ECAPA (nOut 512, the model of the reference's default configs: ECAPA-TDNN C = 512 + RawNet3), `features: raw`,
 written to profiles/rawnet3_ragged_bench.json by convention; --model Conformer (nOut 512, the model of yaml/model_plot.yaml, mel features)
-to profiles/conformer_ragged_bench.json.  The single-call comparison and the kernel table are given for ECAPA-TDNN and the Conformer."""
+to profiles/conformer_ragged_bench.json; --model TitaNet (TitaNet-M, nOut 320, mel features) and --model Tita_ECAPA (nOut 512: ECAPA-TDNN
+C = 512 + TitaNet-M, `features: raw`) to profiles/titanet_ragged_bench.json (one record per run: --out names the file).  The single-call
+comparison and the kernel table are given for ECAPA-TDNN, the Conformer and TitaNet; for TitaNet also the packed depthwise kernels
+(tn_dw, tn_mega_tail) beside the fixed ones over the same rows in the same process, in algorithmic bytes per second."""
 from __future__ import annotations
 
 import argparse
@@ -31,7 +34,7 @@ if not os.environ.get("RAGGED_BENCH_NO_PATH"):
 
 import torch             # noqa: E402
 
-from speakerverification_amd import synth                                                   # noqa: E402
+from speakerverification_amd import _lib, synth                                                # noqa: E402
 from speakerverification_amd.model import ModelHandling, SpeakerEncoder, WrappedModel      # noqa: E402
 
 SEED = 20220829
@@ -51,7 +54,8 @@ def make_files(n):
 
 
 MODELS = {"ECAPA_TDNN": "ECAPA_TDNN C=1024 nOut=192", "RawNet3": "RawNet3 nOut=320", "Raw3_ECAPA": "Raw3_ECAPA nOut=512 (ECAPA-TDNN C=512 + RawNet3)",
-          "Conformer": "Conformer nOut=512"}
+          "Conformer": "Conformer nOut=512", "TitaNet": "TitaNet-M nOut=320",
+          "Tita_ECAPA": "Tita_ECAPA nOut=512 (ECAPA-TDNN C=512 + TitaNet-M)"}
 
 
 def state_dict(model):
@@ -59,6 +63,12 @@ def state_dict(model):
         return synth.synth_state_dict(synth.ecapa_param_spec(C=1024), seed=5)
     if model == "Conformer":
         return synth.synth_state_dict(synth.conformer_param_spec(512, 80), seed=5)
+    if model == "TitaNet":
+        return synth.synth_state_dict(synth.titanet_param_spec("m", 320), seed=5)
+    if model == "Tita_ECAPA":
+        sd = {"ECAPA_TDNN." + k: v for k, v in synth.synth_state_dict(synth.ecapa_param_spec(C=512, input_norm=True), seed=5).items()}
+        sd.update({"titaNet." + k: v for k, v in synth.synth_state_dict(synth.titanet_param_spec("m", 320), seed=5).items()})
+        return sd
     rn3 = synth.synth_state_dict(synth.rawnet3_param_spec(nOut=320), seed=5)
     if model == "RawNet3":
         return rn3
@@ -71,6 +81,9 @@ def handler(compute, per_file, model="ECAPA_TDNN"):
     kw = dict(ARGS, hip_compute=compute)
     if model == "Conformer":
         kw.update(model={"name": model, "nOut": 512})
+        kw.pop("channels")
+    elif model == "TitaNet":
+        kw.update(model={"name": model, "nOut": 320}, model_size="m")
         kw.pop("channels")
     elif model != "ECAPA_TDNN":
         kw.update(model={"name": model, "nOut": 320 if model == "RawNet3" else 512}, features="raw")
@@ -94,6 +107,47 @@ def engines_alive(S):
 def drop_engines(S):
     for m in ([S] if hasattr(S, "_drop_engine") else [getattr(S, S.FIRST_ATTR), getattr(S, S.RAW_ATTR)]):
         m._drop_engine()
+
+
+def titanet_depthwise_rates(lens, H=512, k=7, compute="bf16", iters=20):
+    """TitaNet's two depthwise kernels over the pack `lens` (mel frames per utterance) through svhip_titanet_depthwise_ragged, beside the
+    fixed kernels (svhip_titanet_depthwise) over B x 401 frames with B = rows // 401 — the same rows but for the last < 401 — on the same
+    buffers: microseconds per launch (HIP events around `iters` launches) and algorithmic bytes per second (tn_dw: the input read once
+    and the output written once; tn_mega_tail with the next depthwise conv: skip and h3 read, y and d written)"""
+    lib = _lib.load()
+    dtype, code, esz = (torch.bfloat16, _lib.BF16, 2) if compute == "bf16" else (torch.float32, _lib.F32, 4)
+    n, M = len(lens), int(sum(lens))
+    B = M // 401
+    row0 = torch.tensor(np.concatenate([[0], np.cumsum(lens)]), dtype=torch.int32, device="cuda")
+    x, skip, h3, y, d = (torch.randn((M, H), device="cuda").to(dtype) for _ in range(5))
+    gate = torch.rand((max(n, B), H), device="cuda")
+    w, bias = torch.randn((k, H), device="cuda"), torch.randn(H, device="cuda")
+    P = lambda t: t.data_ptr()
+    forms = {
+        "tn_dw": (2, lambda rag: lib.svhip_titanet_depthwise_ragged(P(x), None, None, None, None, P(w), P(bias), P(d), code, k, P(row0), n, max(lens), H, None)
+                  if rag else lib.svhip_titanet_depthwise(P(x), None, None, None, None, P(w), P(bias), P(d), code, k, B, 401, H, None)),
+        "tn_mega_tail": (4, lambda rag: lib.svhip_titanet_depthwise_ragged(None, P(skip), P(h3), P(gate), P(y), P(w), P(bias), P(d), code, k, P(row0), n,
+                                                                           max(lens), H, None)
+                         if rag else lib.svhip_titanet_depthwise(None, P(skip), P(h3), P(gate), P(y), P(w), P(bias), P(d), code, k, B, 401, H, None)),
+    }
+    out = {"rows_packed": M, "rows_fixed": B * 401, "utterances": n, "H": H, "k": k, "compute": compute}
+    for name, (tensors, call) in forms.items():
+        for rag in (False, True):
+            rows = M if rag else B * 401
+            us = []
+            for _ in range(5):
+                assert call(rag) == 0
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    call(rag)
+                e1.record()
+                torch.cuda.synchronize()
+                us.append(e0.elapsed_time(e1) * 1e3 / iters)
+            med = float(np.median(us))
+            out[name + ("_packed" if rag else "_fixed")] = {"us_per_launch": stats(us), "TBps": round(tensors * rows * H * esz / (med * 1e-6) / 1e12, 3)}
+    return out
 
 
 def timed(fn, runs):
@@ -135,7 +189,7 @@ def main():
         r = {"wall_s": stats(wall), "hip_event_s": stats(dev),
              "files_per_s": {"median": a.files / float(np.median(wall)), "min": a.files / max(wall), "max": a.files / min(wall)},
              "frames_per_s": frames / float(np.median(wall)), "engines_alive": engines_alive(S)}
-        if not a.per_file and a.model in ("ECAPA_TDNN", "Conformer"):
+        if not a.per_file and a.model in ("ECAPA_TDNN", "Conformer", "TitaNet"):
             eng = S.ragged_engine()
             # the ragged call against the fixed-length call of the same handle, device-resident input, frames/s of each
             x = torch.from_numpy(synth.synth_waveforms(eng.max_batch, eng.samples, seed=1)).cuda()
@@ -159,6 +213,8 @@ def main():
             r["ragged_forward_kernels_ms"] = {k: {"ms": round(v["ms"], 4), "launches": v["launches"]}
                                               for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])}
             r["ragged_forward_pack"] = {"utterances": len(lens), "frames": int(sum(n // 80 + 1 for n in lens))}
+            if a.model == "TitaNet":
+                r["depthwise_kernels"] = titanet_depthwise_rates([n // 80 + 1 for n in lens], compute=compute)
         res[compute] = r
         print(compute, json.dumps(r["files_per_s"]), flush=True)
         drop_engines(S)
