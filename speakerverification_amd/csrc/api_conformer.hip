@@ -13,11 +13,12 @@
 // residual R; the residual stream stays in the handle's storage type.
 //
 // A ragged pack (conformer_embed_ragged): n utterances of T_u mel frames, packed back to back at the mel level and, T'_u rows each, at
-// the subsampled level (row0 / utt tables, as ECAPA's and RawNet3's packs).  The same layers over the packed rows: every GEMM through
-// launch_gemm_ragged, LayerNorm unchanged (row-wise), and the five steps that know where an utterance begins and ends in their
-// segment-table forms — the input normalisation (launch_rag_prologue), the subsampling (conv1 keeps only the 2 T'_u + 1 rows conv2
-// reads, utterance u's at conv1 row 2 row0[u] + u; conv2's operand gather adds that per-utterance offset), the attention, the GLU +
-// depthwise conv and the pooling.  P = pe W_pos^T is kept for rows 0 .. the longest T'_u seen (row c depends on c only).
+// the subsampled level (row0 / utt tables, as ECAPA's and RawNet3's packs).  The same layers over the packed rows, enqueued by the same
+// walk (conformer_walk): every GEMM through launch_gemm_ragged, LayerNorm unchanged (row-wise), and the five steps that know where an
+// utterance begins and ends in their segment-table forms — the input normalisation (launch_rag_prologue), the subsampling (conv1
+// keeps only the 2 T'_u + 1 rows conv2 reads, utterance u's at conv1 row 2 row0[u] + u; conv2's operand gather adds that
+// per-utterance offset), the attention, the GLU + depthwise conv and the pooling.  P = pe W_pos^T is kept for rows 0 .. the longest
+// T'_u seen (row c depends on c only).
 #include <algorithm>
 #include <cstring>
 #include <thread>
@@ -73,10 +74,7 @@ struct ConformerState : ModelState {
     std::vector<int> pe_of;                               // i's positional encoding (layers whose buffers are equal share one copy)
     float* rag_P = nullptr;               // (layers, rag_P_rows, 256): P for rows 0 .. rag_P_rows - 1, grown to the longest T'_u seen
     int rag_P_rows = 0;
-    RagTables rag;                        // the tables of a call: feature offsets (Bmax int64), mel row0, subsampled row0 (Bmax + 1 each)
-    int64_t* rag_feat_off = nullptr;
-    int *rag_mel0 = nullptr, *rag_row0 = nullptr;
-    int* rag_utt = nullptr;               // (rows_cap) utterance of every subsampled row
+    RagTables rag;                        // the tables of a call (two levels: mel frames, subsampled frames) and the waveform staging buffer
     float* rag_stats = nullptr;           // (Bmax n_mels 2) shift / scale of the front-end
 
     ~ConformerState() override { if (rag_P) (void)hipFree(rag_P); }
@@ -334,19 +332,24 @@ static int cf_ln(svhip_handle* h, const void* x, void* y, const float* g, const 
     return run(h, "cf_ln", 0, [&]() { return launch_cf_ln(x, y, g, b, y2, g2, b2, h->dt, M, h->cur); });
 }
 
-static int conformer_forward_part(svhip_handle* h, const float* d_feat, int b0, int B) {
+// A GEMM over the rows of a pack: the generic kernel, one label (the subsampling's conv2 brings its own rag_utt / rag_row0; the pointwise
+// layers need none)
+static int cf_rag_gemm(svhip_handle* h, const ConvLayer& L, const GemmParams& p) {
+    return run(h, "rag_gemm", (double)p.M * L.flops_per_row, [&]() { return launch_gemm_ragged(p, h->bf16, h->cur); });
+}
+
+// The front-end and the subsampling have a form each (fixed-length chunks and whole-utterance slices are different algorithms); both
+// leave the input projection in s.in.
+// Fixed: Conv2dSubampling + input_projection (convolution.py:152-185, encoder.py:160-163), cf_chunk utterances at a time
+static int cf_front_fixed(svhip_handle* h, const float* d_feat, int B) {
     auto& s = S(h);
-    (void)b0;
     const svhip_config& c = h->cfg;
     const int T = h->T, Tp = s.Tp, F = c.n_mels, T1 = s.T1, F1 = s.F1, F2 = s.F2, e = h->esz, D = CF_D;
-    const int M = B * Tp;
-    const bool bf = h->bf16;
     hipStream_t st = h->cur;
     int rc;
     if ((rc = run(h, "prologue", 0, [&]() {
-             return launch_prologue(d_feat, h->X_in, bf, B, F, T, c.log_input, h->in_w, h->in_b, h->d_pstats, st);
+             return launch_prologue(d_feat, h->X_in, h->bf16, B, F, T, c.log_input, h->in_w, h->in_b, h->d_pstats, st);
          }))) return rc;
-    // Conv2dSubampling + input_projection (convolution.py:152-185, encoder.py:160-163), cf_chunk utterances at a time
     for (int s0 = 0; s0 < B; s0 += s.chunk) {
         const int n = std::min(s.chunk, B - s0);
         if ((rc = run(h, "cf_conv1", 2.0 * 9 * D * n * T1 * F1, [&]() {
@@ -360,6 +363,75 @@ static int conformer_forward_part(svhip_handle* h, const float* d_feat, int b0, 
         GemmParams pp = conv_params(h, s.proj, s.s2, F2 * D, off(s.in, (size_t)s0 * Tp * D, e), D, n * Tp, Tp);
         if ((rc = conv_gemm(h, s.proj, pp))) return rc;
     }
+    return SVHIP_OK;
+}
+
+// A pack (features at pk.in + pk.off[u]; levels: mel frames, subsampled frames), whole utterances at a time: a slice holds at most
+// `chunk` utterances and chunk * T' subsampled frames, so that its conv1 image (2 T'_u + 1 <= T1 rows per utterance) and its conv2
+// output fit the buffers of the fixed-length slices
+static int cf_front_ragged(svhip_handle* h, const RagPack& pk) {
+    auto& s = S(h);
+    const svhip_config& c = h->cfg;
+    const int n = pk.n, F = c.n_mels, F1 = s.F1, F2 = s.F2, e = h->esz, D = CF_D;
+    const Seg &mel = pk.lv[0], &sub = pk.lv[1];
+    const int* hrow0 = sub.hrow0;
+    const bool bf = h->bf16;
+    hipStream_t st = h->cur;
+    int rc;
+    if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(sub.row0, n, sub.maxT, sub.utt, st); }))) return rc;
+    if ((rc = run(h, "rag_prologue", 0, [&]() {
+             return launch_rag_prologue(pk.in, pk.off, mel.row0, n, mel.maxT, h->X_in, bf, F, c.log_input, h->in_w, h->in_b, s.rag_stats, st);
+         }))) return rc;
+    const int64_t slice_rows = (int64_t)s.chunk * s.Tp;
+    for (int u0 = 0; u0 < n;) {
+        int u1 = u0, mt = 0;
+        while (u1 < n && u1 - u0 < s.chunk && hrow0[u1 + 1] - hrow0[u0] <= slice_rows) { mt = std::max(mt, hrow0[u1 + 1] - hrow0[u1]); ++u1; }
+        const int rows = hrow0[u1] - hrow0[u0];
+        if ((rc = run(h, "cf_conv1_rag", 2.0 * 9 * D * (2.0 * rows + (u1 - u0)) * F1, [&]() {
+                 return launch_cf_conv1_ragged(h->X_in, s.c1_w, s.c1_b, s.c1, h->dt, mel.row0, sub.row0, u0, u1 - u0, mt, F, st);
+             }))) return rc;
+        GemmParams p2 = conv_params(h, s.c2, s.c1, D, s.s2, D, rows * F2, 1);
+        p2.act1 = ACT_RELU;
+        p2.seg_off = s.seg_off; p2.seg_rows = F2; p2.seg_len = 3 * D;          // (seg_off[f] = 2 f D: its first F2 entries, frame 0's)
+        p2.seg_stride = (int64_t)F1 * D; p2.seg_utt = 2 * (int64_t)F1 * D; p2.seg_u0 = u0;
+        p2.rag_utt = sub.utt + hrow0[u0]; p2.rag_row0 = sub.row0;
+        if ((rc = cf_rag_gemm(h, s.c2, p2))) return rc;
+        if ((rc = cf_rag_gemm(h, s.proj, conv_params(h, s.proj, s.s2, F2 * D, off(s.in, (size_t)hrow0[u0] * D, e), D, rows, 1)))) return rc;
+        u0 = u1;
+    }
+    return SVHIP_OK;
+}
+
+// Conformer_.forward, written once for both forms.  pk null: a fixed-length batch of B utterances of h->T frames, (B, n_mels, T) at
+// d_feat, on h->cur; the GEMMs take their routes through conv_gemm.  pk set: its n = B utterances as packed rows, on the handle's stream;
+// every GEMM goes to the generic kernel (launch_gemm_ragged), LayerNorm is row-wise in both, and the steps that know where an utterance
+// begins and ends run in their segment-table forms.  The helpers pick the form; below them the network reads once.
+static int conformer_walk(svhip_handle* h, const float* d_feat, int B, const RagPack* pk) {
+    auto& s = S(h);
+    const svhip_config& c = h->cfg;
+    const Seg* g = pk ? &pk->lv[1] : nullptr;          // the subsampled level: the rows of everything behind the subsampling
+    const int T = g ? 1 : s.Tp, M = g ? g->M : B * T, F = c.n_mels, D = CF_D;      // (T: of the GEMMs; a pack's rows are their own frames)
+    const bool bf = h->bf16;
+    if (g) h->cur = h->stream;
+    hipStream_t st = h->cur;
+    int rc;
+    auto gemm = [&](const ConvLayer& L, const GemmParams& p) { return g ? cf_rag_gemm(h, L, p) : conv_gemm(h, L, p); };
+    // relative-position attention of block i over hid = q | k | v -> ctx; a pack's P: rows 0 .. the longest T'_u seen (conformer_ragged_pos)
+    auto attn = [&](int i, void* ctx) {
+        const CfBlock& K = s.blocks[i];
+        if (!g) return run(h, "cf_attn", 4.0 * B * T * (double)T * 3 * 2 * 64, [&]() {
+            return launch_cf_attn(s.hid, 3 * D, K.P, D, K.u, K.v, ctx, D, h->dt, B, T, st);
+        });
+        const float* P = s.rag_P + (size_t)i * s.rag_P_rows * D;
+        return run(h, "cf_attn_rag", 0, [&]() { return launch_cf_attn_ragged(s.hid, 3 * D, P, D, K.u, K.v, ctx, D, h->dt, g->row0, B, g->maxT, st); });
+    };
+    auto glu_dw = [&](const CfBlock& K) {          // BN(dw15(GLU(hid))) -> s.ctx
+        return run(h, g ? "cf_glu_dw_rag" : "cf_glu_dw", 2.0 * 15 * D * M, [&]() {
+            return g ? launch_cf_glu_dw_ragged(s.hid, K.dw_w, K.dw_b, s.ctx, h->dt, g->row0, B, g->maxT, st)
+                     : launch_cf_glu_dw(s.hid, K.dw_w, K.dw_b, s.ctx, h->dt, B, T, st);
+        });
+    };
+    if ((rc = g ? cf_front_ragged(h, *pk) : cf_front_fixed(h, d_feat, B))) return rc;
     // the blocks (encoder.py:32-110).  Buffers: x (block input) -> r -> xo -> r -> ln2 -> xo = LN(.) (+ the next block's FF LayerNorm)
     const void* x = s.in;
     const int nb = (int)s.blocks.size();
@@ -369,108 +441,97 @@ static int conformer_forward_part(svhip_handle* h, const float* d_feat, int b0, 
         void* xo = i == 0 ? s.b0 : i == nb - 1 ? s.last : s.x[i & 1];
         void* ctx = i == 0 ? s.attn0 : s.ctx;
         // r = x + 0.5 FF(x); cf_ln already holds LN(x)                                                 feed_forward.py:23-57
-        GemmParams f1 = conv_params(h, K.ff1[0], s.ln, D, s.hid, 4 * D, M, Tp);
+        GemmParams f1 = conv_params(h, K.ff1[0], s.ln, D, s.hid, 4 * D, M, T);
         f1.act1 = ACT_SWISH;
-        if ((rc = conv_gemm(h, K.ff1[0], f1))) return rc;
-        GemmParams f2 = conv_params(h, K.ff2[0], s.hid, 4 * D, s.r, D, M, Tp);
+        if ((rc = gemm(K.ff1[0], f1))) return rc;
+        GemmParams f2 = conv_params(h, K.ff2[0], s.hid, 4 * D, s.r, D, M, T);
         f2.scale = s.half; f2.shift = h->d_zeros; f2.R = x; f2.ldr = D;
-        if ((rc = conv_gemm(h, K.ff2[0], f2))) return rc;
+        if ((rc = gemm(K.ff2[0], f2))) return rc;
         // xo = r + out_proj(attention(LN(r)))                                                        attention.py:75-159
         if ((rc = cf_ln(h, s.r, s.ln, K.att_g, K.att_b, M))) return rc;
-        if ((rc = conv_gemm(h, K.qkv, conv_params(h, K.qkv, s.ln, D, s.hid, 3 * D, M, Tp)))) return rc;
-        if ((rc = run(h, "cf_attn", 4.0 * B * Tp * (double)Tp * 3 * 2 * 64, [&]() {
-                 return launch_cf_attn(s.hid, 3 * D, K.P, D, K.u, K.v, ctx, D, h->dt, B, Tp, st);
-             }))) return rc;
-        GemmParams po = conv_params(h, K.out, ctx, D, xo, D, M, Tp);
+        if ((rc = gemm(K.qkv, conv_params(h, K.qkv, s.ln, D, s.hid, 3 * D, M, T)))) return rc;
+        if ((rc = attn(i, ctx))) return rc;
+        GemmParams po = conv_params(h, K.out, ctx, D, xo, D, M, T);
         po.R = s.r; po.ldr = D;
-        if ((rc = conv_gemm(h, K.out, po))) return rc;
+        if ((rc = gemm(K.out, po))) return rc;
         // r = xo + pw2(swish(BN(dw15(GLU(pw1(LN(xo)))))))                                             convolution.py:108-149
         if ((rc = cf_ln(h, xo, s.ln, K.cv_g, K.cv_b, M))) return rc;
-        if ((rc = conv_gemm(h, K.pw1, conv_params(h, K.pw1, s.ln, D, s.hid, 2 * D, M, Tp)))) return rc;
-        if ((rc = run(h, "cf_glu_dw", 2.0 * 15 * D * M, [&]() { return launch_cf_glu_dw(s.hid, K.dw_w, K.dw_b, s.ctx, h->dt, B, Tp, st); })))
-            return rc;
-        GemmParams pw = conv_params(h, K.pw2, s.ctx, D, s.r, D, M, Tp);
+        if ((rc = gemm(K.pw1, conv_params(h, K.pw1, s.ln, D, s.hid, 2 * D, M, T)))) return rc;
+        if ((rc = glu_dw(K))) return rc;
+        GemmParams pw = conv_params(h, K.pw2, s.ctx, D, s.r, D, M, T);
         pw.R = xo; pw.ldr = D;
-        if ((rc = conv_gemm(h, K.pw2, pw))) return rc;
+        if ((rc = gemm(K.pw2, pw))) return rc;
         // ln2 = r + 0.5 FF'(r); xo = LN(ln2), and the next block's LN(xo) in the same pass
         if ((rc = cf_ln(h, s.r, s.ln, K.ff_g[1], K.ff_b[1], M))) return rc;
-        GemmParams g1 = conv_params(h, K.ff1[1], s.ln, D, s.hid, 4 * D, M, Tp);
+        GemmParams g1 = conv_params(h, K.ff1[1], s.ln, D, s.hid, 4 * D, M, T);
         g1.act1 = ACT_SWISH;
-        if ((rc = conv_gemm(h, K.ff1[1], g1))) return rc;
-        GemmParams g2 = conv_params(h, K.ff2[1], s.hid, 4 * D, s.ln2, D, M, Tp);
+        if ((rc = gemm(K.ff1[1], g1))) return rc;
+        GemmParams g2 = conv_params(h, K.ff2[1], s.hid, 4 * D, s.ln2, D, M, T);
         g2.scale = s.half; g2.shift = h->d_zeros; g2.R = s.r; g2.ldr = D;
-        if ((rc = conv_gemm(h, K.ff2[1], g2))) return rc;
+        if ((rc = gemm(K.ff2[1], g2))) return rc;
         const CfBlock* nx = i + 1 < nb ? &s.blocks[i + 1] : nullptr;
         if ((rc = cf_ln(h, s.ln2, xo, K.fin_g, K.fin_b, M, nx ? s.ln : nullptr, nx ? nx->ff_g[0] : nullptr, nx ? nx->ff_b[0] : nullptr)))
             return rc;
         x = xo;
     }
     // attentive statistics pooling (Conformer.py:130-142)
-    GemmParams pa = conv_params(h, s.att0, x, D, s.hid, 128, M, Tp);
+    GemmParams pa = conv_params(h, s.att0, x, D, s.hid, 128, M, T);
     pa.act1 = ACT_RELU;
-    if ((rc = conv_gemm(h, s.att0, pa))) return rc;
-    GemmParams pl = conv_params(h, s.att3, s.hid, 128, s.logits, D, M, Tp);
+    if ((rc = gemm(s.att0, pa))) return rc;
+    GemmParams pl = conv_params(h, s.att3, s.hid, 128, s.logits, D, M, T);
     pl.out_f32 = 1;
-    if ((rc = conv_gemm(h, s.att3, pl))) return rc;
-    if ((rc = run(h, "cf_asp_pool", 0, [&]() {
-             return launch_asp_pool(s.logits, x, bf, D, B, Tp, D, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-4f, 1e4f, st);
+    if ((rc = gemm(s.att3, pl))) return rc;
+    if ((rc = run(h, g ? "rag_asp_pool" : "cf_asp_pool", 0, [&]() {
+             return g ? launch_rag_asp_pool(s.logits, x, bf, D, g->row0, B, D, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-4f, st, 1e4f)
+                      : launch_asp_pool(s.logits, x, bf, D, B, T, D, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-4f, 1e4f, st);
          }))) return rc;
-    // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the ReLU epilogues would have dropped it)
+    // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the ReLU epilogues would have dropped it): its
+    // own row only
     if ((rc = run(h, "cf_in_check", 0, [&]() {
-             return launch_tn_nonfinite_rows(d_feat, (int64_t)F * T, B, s.pool, 2 * D, 2 * D, st);
+             return g ? launch_tn_nonfinite_rows_ragged(d_feat, pk->off, pk->lv[0].row0, F, B, s.pool, 2 * D, 2 * D, st)
+                      : launch_tn_nonfinite_rows(d_feat, (int64_t)F * h->T, B, s.pool, 2 * D, 2 * D, st);
          }))) return rc;
-    return run(h, "cf_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
-        return launch_rowvec_linear(s.pool, 2 * D, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * D, ACT_NONE, st);
+    return run(h, g ? "rag_fc" : "cf_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
+        return g ? launch_rag_linear(s.pool, 2 * D, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * D, ACT_NONE, st)
+                 : launch_rowvec_linear(s.pool, 2 * D, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * D, ACT_NONE, st);
     });
 }
 
+static int conformer_forward_part(svhip_handle* h, const float* d_feat, int, int B) { return conformer_walk(h, d_feat, B, nullptr); }
 int conformer_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, conformer_forward_part, d_feat, B, 1, B); }
 
 // ---- ragged packs ------------------------------------------------------------------------------------------
+// the Conformer's own rules on an utterance of T >= 7 frames: T' within the positional encoding and within one subsampling slice
+// (slice: the subsampled frames a slice of the handle holds)
+static int cf_ragged_utt_rule(int64_t slice, int i, int64_t T, std::string& err) {
+    const int64_t Tp = (T - 3) / 4;
+    if (Tp > CF_MAX_T)
+        return refuse(err, SVHIP_ERR_INVALID, "utterance %d: T' = %lld subsampled frames, over the %d positions of the positional encoding", i,
+                      (long long)Tp, CF_MAX_T);
+    if (Tp > slice)
+        return refuse(err, SVHIP_ERR_INVALID, "utterance %d: T' = %lld subsampled frames, over the %lld one subsampling slice of this handle holds (its "
+                      "conv1 image must fit the slice buffer)", i, (long long)Tp, (long long)slice);
+    return SVHIP_OK;
+}
+
 // The Conformer's rules for a pack (RaggedCheckFn; include/svhip.h), on the host alone
 int conformer_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
-    if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft || c.n_mels < 7 || c.samples / c.hop_length + 1 < 7)
-        return refuse(err, SVHIP_ERR_INVALID, "bad hop_length / max_batch / samples / n_mels");
-    const int Th = (int)mel_frames(c, c.samples, true);
-    const int64_t cap = (int64_t)c.max_batch * Th;
-    const int64_t slice = (int64_t)cf_chunk(c, Th) * cf_sub(cf_sub(Th));      // subsampled frames one subsampling slice holds
-    int64_t rows = 0;
-    for (int i = 0; i < n; ++i) {
-        if (is_wave && lengths[i] < c.n_fft)
-            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld samples, fewer than n_fft=%d", i, (long long)lengths[i], c.n_fft);
-        const int64_t T = mel_frames(c, lengths[i], is_wave);
-        if (T < 7)
-            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld frames, fewer than 7 (two 3 x 3 stride-2 convolutions leave T' = (T - 3) / 4 >= 1)",
-                          i, (long long)T);
-        const int64_t Tp = (T - 3) / 4;
-        if (Tp > CF_MAX_T)
-            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: T' = %lld subsampled frames, over the %d positions of the positional encoding", i,
-                          (long long)Tp, CF_MAX_T);
-        if (Tp > slice)
-            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: T' = %lld subsampled frames, over the %lld one subsampling slice of this handle holds (its "
-                          "conv1 image must fit the slice buffer)", i, (long long)Tp, (long long)slice);
-        if (int rc = rag_rows_fit(err, i, rows += T, cap, "T")) return rc;
+    const bool cfg_ok = c.n_mels >= 7 && (c.hop_length <= 0 || c.samples / c.hop_length + 1 >= 7);      // (hop_length <= 0: refused by the shared rules)
+    int64_t slice = 0;          // (of a configuration the shared rules take: cf_chunk divides by the conv1 image of T >= 7 frames)
+    if (cfg_ok && c.hop_length > 0) {
+        const int Th = (int)mel_frames(c, c.samples, true);
+        slice = (int64_t)cf_chunk(c, Th) * cf_sub(cf_sub(Th));
     }
-    return SVHIP_OK;
+    return rag_mel_check(c, lengths, n, is_wave, err, cfg_ok, "hop_length / max_batch / samples / n_mels", 7,
+                         " (two 3 x 3 stride-2 convolutions leave T' = (T - 3) / 4 >= 1)", cf_ragged_utt_rule, slice);
 }
 
-static size_t cf_tab_bytes(size_t B) { return B * 8 + 2 * (B + 1) * 4; }
-
-// the segment tables, the waveform staging buffer and the pinned table slots: once per handle
-static int conformer_ragged_alloc(svhip_handle* h) {
-    auto& s = S(h);
-    if (s.rag.dev) return SVHIP_OK;
-    const svhip_config& c = h->cfg;
-    const size_t B = c.max_batch;
-    int rc;
-    if (!s.rag_stats && (rc = dev_alloc(h, &s.rag_stats, B * c.n_mels * 2))) return rc;
-    if (!s.rag_utt && (rc = dev_alloc(h, &s.rag_utt, s.rows_cap))) return rc;
-    if ((rc = s.rag.alloc(h, cf_tab_bytes(B), B * ((size_t)c.samples + c.hop_length)))) return rc;
-    s.rag_feat_off = reinterpret_cast<int64_t*>(s.rag.dev);
-    s.rag_mel0 = reinterpret_cast<int*>(s.rag.dev + B * 8);
-    s.rag_row0 = s.rag_mel0 + (B + 1);
-    return SVHIP_OK;
+// two frame levels: the mel frames and the subsampled frames
+static void cf_rag_frames(const svhip_config& c, int64_t len, bool is_wave, int T[3]) {
+    T[0] = (int)mel_frames(c, len, is_wave);
+    T[1] = cf_sub(cf_sub(T[0]));
 }
+static const RagRule kConformerRag = {2, cf_rag_frames, true};
 
 // P of every layer for rows [0, rows): the double-precision row sums of finalize, so the first T' rows are the handle's own P bit for
 // bit.  Grown (in steps of 256 rows) when a pack brings a longer utterance than any before it; a handle without ragged calls never
@@ -492,132 +553,19 @@ static int conformer_ragged_pos(svhip_handle* h, int rows) {
     return SVHIP_OK;
 }
 
-// Conformer_.forward over the packed rows of a ragged batch (features at d_feat + rag_feat_off[u]; tables on the device; hrow0: the
-// subsampled row0 on the host).  One stream; nothing but the per-slice subsampling is launched more than once per layer.
-static int conformer_forward_ragged(svhip_handle* h, const float* d_feat, int n, int maxT, const int* hrow0, int maxTp) {
-    auto& s = S(h);
-    const svhip_config& c = h->cfg;
-    const int F = c.n_mels, F1 = s.F1, F2 = s.F2, e = h->esz, D = CF_D;
-    const int M = hrow0[n];
-    const bool bf = h->bf16;
-    hipStream_t st = h->cur = h->stream;
-    const int *row0 = s.rag_row0, *utt = s.rag_utt;
-    int rc;
-    auto gemm = [&](const ConvLayer& L, const GemmParams& p) {
-        return run(h, "rag_gemm", (double)p.M * L.flops_per_row, [&]() { return launch_gemm_ragged(p, bf, st); });
-    };
-    if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(row0, n, maxTp, s.rag_utt, st); }))) return rc;
-    if ((rc = run(h, "rag_prologue", 0, [&]() {
-             return launch_rag_prologue(d_feat, s.rag_feat_off, s.rag_mel0, n, maxT, h->X_in, bf, F, c.log_input, h->in_w, h->in_b, s.rag_stats, st);
-         }))) return rc;
-    // the subsampling, whole utterances at a time: a slice holds at most `chunk` utterances and chunk * T' subsampled frames, so that
-    // its conv1 image (2 T'_u + 1 <= T1 rows per utterance) and its conv2 output fit the buffers of the fixed-length slices
-    const int64_t slice_rows = (int64_t)s.chunk * s.Tp;
-    for (int u0 = 0; u0 < n;) {
-        int u1 = u0, mt = 0;
-        while (u1 < n && u1 - u0 < s.chunk && hrow0[u1 + 1] - hrow0[u0] <= slice_rows) { mt = std::max(mt, hrow0[u1 + 1] - hrow0[u1]); ++u1; }
-        const int rows = hrow0[u1] - hrow0[u0];
-        if ((rc = run(h, "cf_conv1_rag", 2.0 * 9 * D * (2.0 * rows + (u1 - u0)) * F1, [&]() {
-                 return launch_cf_conv1_ragged(h->X_in, s.c1_w, s.c1_b, s.c1, h->dt, s.rag_mel0, row0, u0, u1 - u0, mt, F, st);
-             }))) return rc;
-        GemmParams p2 = conv_params(h, s.c2, s.c1, D, s.s2, D, rows * F2, 1);
-        p2.act1 = ACT_RELU;
-        p2.seg_off = s.seg_off; p2.seg_rows = F2; p2.seg_len = 3 * D;          // (seg_off[f] = 2 f D: its first F2 entries, frame 0's)
-        p2.seg_stride = (int64_t)F1 * D; p2.seg_utt = 2 * (int64_t)F1 * D; p2.seg_u0 = u0;
-        p2.rag_utt = utt + hrow0[u0]; p2.rag_row0 = row0;
-        if ((rc = gemm(s.c2, p2))) return rc;
-        if ((rc = gemm(s.proj, conv_params(h, s.proj, s.s2, F2 * D, off(s.in, (size_t)hrow0[u0] * D, e), D, rows, 1)))) return rc;
-        u0 = u1;
-    }
-    const void* x = s.in;
-    const int nb = (int)s.blocks.size();
-    if ((rc = cf_ln(h, x, s.ln, s.blocks[0].ff_g[0], s.blocks[0].ff_b[0], M))) return rc;
-    for (int i = 0; i < nb; ++i) {
-        const CfBlock& K = s.blocks[i];
-        void* xo = i == 0 ? s.b0 : i == nb - 1 ? s.last : s.x[i & 1];
-        void* ctx = i == 0 ? s.attn0 : s.ctx;
-        GemmParams f1 = conv_params(h, K.ff1[0], s.ln, D, s.hid, 4 * D, M, 1);
-        f1.act1 = ACT_SWISH;
-        if ((rc = gemm(K.ff1[0], f1))) return rc;
-        GemmParams f2 = conv_params(h, K.ff2[0], s.hid, 4 * D, s.r, D, M, 1);
-        f2.scale = s.half; f2.shift = h->d_zeros; f2.R = x; f2.ldr = D;
-        if ((rc = gemm(K.ff2[0], f2))) return rc;
-        if ((rc = cf_ln(h, s.r, s.ln, K.att_g, K.att_b, M))) return rc;
-        if ((rc = gemm(K.qkv, conv_params(h, K.qkv, s.ln, D, s.hid, 3 * D, M, 1)))) return rc;
-        const float* P = s.rag_P + (size_t)i * s.rag_P_rows * D;
-        if ((rc = run(h, "cf_attn_rag", 0, [&]() {
-                 return launch_cf_attn_ragged(s.hid, 3 * D, P, D, K.u, K.v, ctx, D, h->dt, row0, n, maxTp, st);
-             }))) return rc;
-        GemmParams po = conv_params(h, K.out, ctx, D, xo, D, M, 1);
-        po.R = s.r; po.ldr = D;
-        if ((rc = gemm(K.out, po))) return rc;
-        if ((rc = cf_ln(h, xo, s.ln, K.cv_g, K.cv_b, M))) return rc;
-        if ((rc = gemm(K.pw1, conv_params(h, K.pw1, s.ln, D, s.hid, 2 * D, M, 1)))) return rc;
-        if ((rc = run(h, "cf_glu_dw_rag", 2.0 * 15 * D * M, [&]() {
-                 return launch_cf_glu_dw_ragged(s.hid, K.dw_w, K.dw_b, s.ctx, h->dt, row0, n, maxTp, st);
-             }))) return rc;
-        GemmParams pw = conv_params(h, K.pw2, s.ctx, D, s.r, D, M, 1);
-        pw.R = xo; pw.ldr = D;
-        if ((rc = gemm(K.pw2, pw))) return rc;
-        if ((rc = cf_ln(h, s.r, s.ln, K.ff_g[1], K.ff_b[1], M))) return rc;
-        GemmParams g1 = conv_params(h, K.ff1[1], s.ln, D, s.hid, 4 * D, M, 1);
-        g1.act1 = ACT_SWISH;
-        if ((rc = gemm(K.ff1[1], g1))) return rc;
-        GemmParams g2 = conv_params(h, K.ff2[1], s.hid, 4 * D, s.ln2, D, M, 1);
-        g2.scale = s.half; g2.shift = h->d_zeros; g2.R = s.r; g2.ldr = D;
-        if ((rc = gemm(K.ff2[1], g2))) return rc;
-        const CfBlock* nx = i + 1 < nb ? &s.blocks[i + 1] : nullptr;
-        if ((rc = cf_ln(h, s.ln2, xo, K.fin_g, K.fin_b, M, nx ? s.ln : nullptr, nx ? nx->ff_g[0] : nullptr, nx ? nx->ff_b[0] : nullptr)))
-            return rc;
-        x = xo;
-    }
-    GemmParams pa = conv_params(h, s.att0, x, D, s.hid, 128, M, 1);
-    pa.act1 = ACT_RELU;
-    if ((rc = gemm(s.att0, pa))) return rc;
-    GemmParams pl = conv_params(h, s.att3, s.hid, 128, s.logits, D, M, 1);
-    pl.out_f32 = 1;
-    if ((rc = gemm(s.att3, pl))) return rc;
-    if ((rc = run(h, "rag_asp_pool", 0, [&]() {
-             return launch_rag_asp_pool(s.logits, x, bf, D, row0, n, D, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-4f, st, 1e4f);
-         }))) return rc;
-    // an utterance with a non-finite input value gets a NaN embedding: its own row only
-    if ((rc = run(h, "cf_in_check", 0, [&]() {
-             return launch_tn_nonfinite_rows_ragged(d_feat, s.rag_feat_off, s.rag_mel0, F, n, s.pool, 2 * D, 2 * D, st);
-         }))) return rc;
-    return run(h, "rag_fc", 2.0 * n * s.fc.N * s.fc.K, [&]() {
-        return launch_rag_linear(s.pool, 2 * D, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, n, c.embed_dim, 2 * D, ACT_NONE, st);
-    });
-}
-
 int conformer_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n) {
     auto& s = S(h);
     const svhip_config& c = h->cfg;
-    int rc = conformer_ragged_alloc(h);
-    if (rc) return rc;
-    int maxTp = 0;
-    for (int u = 0; u < n; ++u) maxTp = std::max(maxTp, (int)((mel_frames(c, lengths[u], is_wave) - 3) / 4));
-    if ((rc = conformer_ragged_pos(h, maxTp))) return rc;
-    const size_t B = c.max_batch;
-    char* tab = nullptr;
-    if ((rc = s.rag.acquire(h, &tab))) return rc;
-    int64_t* feat_off = reinterpret_cast<int64_t*>(tab);
-    int* mel0 = reinterpret_cast<int*>(tab + B * 8);
-    int* row0 = mel0 + (B + 1);
-    int M = 0, Mp = 0, maxT = 0;
-    for (int u = 0; u < n; ++u) {
-        const int T = (int)mel_frames(c, lengths[u], is_wave);
-        mel0[u] = M; row0[u] = Mp;
-        M += T; Mp += cf_sub(cf_sub(T));
-        maxT = std::max(maxT, T);
-    }
-    mel0[n] = M; row0[n] = Mp;
-    if ((size_t)Mp > s.rows_cap) SV_FAIL(h, SVHIP_ERR_INVALID, "the pack has %d subsampled rows, over the %zu the handle holds", Mp, s.rows_cap);
-    const float* d_feat = nullptr;
-    if ((rc = rag_mel_input(h, s.rag, in, in_host, is_wave, in_off, lengths, n, mel0, feat_off, &d_feat))) return rc;
-    if ((rc = s.rag.commit(h, cf_tab_bytes(B)))) return rc;
-    // (row0 is read on the host while the launches are enqueued; the slot is not taken again before the next call)
-    if ((rc = conformer_forward_ragged(h, d_feat, n, maxT, row0, maxTp))) return rc;
-    set_rag_rows(h, n, {M, Mp});
+    const size_t utt_cap[3] = {0, s.rows_cap};          // (nothing reads the mel level's utt table)
+    RagPack pk;
+    int rc;
+    if (!s.rag_stats && (rc = dev_alloc(h, &s.rag_stats, (size_t)c.max_batch * c.n_mels * 2))) return rc;
+    if ((rc = rag_pack(h, s.rag, kConformerRag, utt_cap, in, in_host, is_wave, in_off, lengths, n, pk))) return rc;
+    // (a guard in front of the walk's writes: a pack that passed conformer_ragged_check has sum (T_u - 3) / 4 <= rows_cap rows)
+    const Seg& sub = pk.lv[1];
+    if ((size_t)sub.M > s.rows_cap) SV_FAIL(h, SVHIP_ERR_INVALID, "the pack has %d subsampled rows, over the %zu the handle holds", sub.M, s.rows_cap);
+    if ((rc = conformer_ragged_pos(h, sub.maxT)) || (rc = conformer_walk(h, pk.in, n, &pk))) return rc;
+    set_rag_rows(h, pk);
     return SVHIP_OK;
 }
 

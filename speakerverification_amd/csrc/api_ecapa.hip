@@ -34,10 +34,7 @@ struct EcapaState : ModelState {
     float *d_pool_raw = nullptr, *d_pool_bn = nullptr;
 
     // ragged batches (svhip_embed_wave_ragged / svhip_embed_features_ragged): allocated by the handle's first ragged call
-    RagTables rag;                            // the tables of a call, feat_off | row0; staging: max_batch * (samples + hop) floats, the utterances back to back
-    int64_t* rag_feat_off = nullptr;          // (max_batch) element offset of every utterance's (n_mels, T_u) block in the feature array
-    int* rag_row0 = nullptr;                  // (max_batch + 1) first workspace row of every utterance, then the row count (behind rag_feat_off)
-    int* rag_utt = nullptr;                   // (max_batch * T) utterance of every row
+    RagTables rag;                            // the tables of a call (one level: mel frames, max_batch * T rows) and the waveform staging buffer
     float* rag_stats = nullptr;               // (max_batch * n_mels * 2) shift / scale of the front-end normalisation
 };
 
@@ -423,53 +420,34 @@ int ecapa_embed_wave(svhip_handle* h, const float* d_wav, int B) {
 // ---- ragged batches ------------------------------------------------------------------------------------
 // ECAPA's rules for a pack (RaggedCheckFn; include/svhip.h), on the host alone
 int ecapa_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
-    if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft) return refuse(err, SVHIP_ERR_INVALID, "bad hop_length / max_batch / samples");
-    const int64_t cap = (int64_t)c.max_batch * mel_frames(c, c.samples, true);
-    int64_t rows = 0;
-    for (int i = 0; i < n; ++i) {
-        if (is_wave && lengths[i] < c.n_fft)
-            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld samples, fewer than n_fft=%d", i, (long long)lengths[i], c.n_fft);
-        const int64_t T = mel_frames(c, lengths[i], is_wave);
-        if (T < 5)
-            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld frames, fewer than 5 (block 3 reflect-pads 4 frames on each side)", i, (long long)T);
-        if (int rc = rag_rows_fit(err, i, rows += T, cap, "T")) return rc;
-    }
-    return SVHIP_OK;
+    return rag_mel_check(c, lengths, n, is_wave, err, true, "hop_length / max_batch / samples", 5, " (block 3 reflect-pads 4 frames on each side)");
 }
 
-// the segment tables, the waveform staging buffer and the pinned table slots: once per handle
-static int ecapa_ragged_alloc(svhip_handle* h) {
-    auto& s = S(h);
-    if (s.rag.dev) return SVHIP_OK;
-    const svhip_config& c = h->cfg;
-    const size_t B = c.max_batch;
-    int rc;
-    if (!s.rag_stats && (rc = dev_alloc(h, &s.rag_stats, B * c.n_mels * 2))) return rc;
-    if (!s.rag_utt && (rc = dev_alloc(h, &s.rag_utt, B * (size_t)h->T))) return rc;
-    if ((rc = s.rag.alloc(h, B * 8 + (B + 1) * 4, B * ((size_t)c.samples + c.hop_length)))) return rc;
-    s.rag_feat_off = reinterpret_cast<int64_t*>(s.rag.dev);
-    s.rag_row0 = reinterpret_cast<int*>(s.rag.dev + B * 8);
-    return SVHIP_OK;
-}
+// one frame level: the mel frames
+static void ecapa_rag_frames(const svhip_config& c, int64_t len, bool is_wave, int T[3]) { T[0] = (int)mel_frames(c, len, is_wave); }
+static const RagRule kEcapaRag = {1, ecapa_rag_frames, true};
 
-// ECAPA_TDNN.forward over the packed rows of a ragged batch (features at d_feat + rag_feat_off[u]; tables on the device).  One slice on
+// ECAPA_TDNN.forward over the packed rows of a ragged batch (features at pk.in + pk.off[u]; tables on the device).  One slice on
 // the handle's stream.  Every GEMM goes to the generic kernel (launch_gemm_ragged: one kernel at every row count, so that a row's sums
 // do not depend on the pack); the convolutions gather through the segment table; the reductions over time are ragged.hip's.
-static int ecapa_forward_ragged(svhip_handle* h, const float* d_feat, int n, int M, int maxT) {
+// It stays apart from ecapa_forward_part: that one is mostly route decisions (F32X3 planes, the Res2Net step kernels, fused attention
+// heads, two lanes) that this one has none of, and what the two share is too little to pay for one walk.
+static int ecapa_forward_ragged(svhip_handle* h, const RagPack& pk) {
     auto& s = S(h);
     const svhip_config& c = h->cfg;
     const int C = c.channels, C3 = 3 * C, C8 = C / 8, e = h->esz;
     const bool bf = h->bf16;
     hipStream_t st = h->cur = h->stream;
-    const int *row0 = s.rag_row0, *utt = s.rag_utt;
+    const int n = pk.n, M = pk.lv[0].M, maxT = pk.lv[0].maxT;
+    const int *row0 = pk.lv[0].row0, *utt = pk.lv[0].utt;
     int rc;
     auto gemm = [&](const ConvLayer& L, GemmParams p, const char* label) {
         p.rag_utt = utt; p.rag_row0 = row0;
         return run(h, label, (double)M * L.flops_per_row, [&]() { return launch_gemm_ragged(p, bf, st); });
     };
-    if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(row0, n, maxT, s.rag_utt, st); }))) return rc;
+    if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(row0, n, maxT, pk.lv[0].utt, st); }))) return rc;
     if ((rc = run(h, "rag_prologue", 0, [&]() {
-             return launch_rag_prologue(d_feat, s.rag_feat_off, row0, n, maxT, h->X_in, bf, c.n_mels, c.log_input, h->in_w, h->in_b, s.rag_stats, st);
+             return launch_rag_prologue(pk.in, pk.off, row0, n, maxT, h->X_in, bf, c.n_mels, c.log_input, h->in_w, h->in_b, s.rag_stats, st);
          }))) return rc;
     {
         GemmParams p = conv_params(h, s.blocks0, h->X_in, c.n_mels, s.X0, C, M, 1);
@@ -526,27 +504,12 @@ static int ecapa_forward_ragged(svhip_handle* h, const float* d_feat, int n, int
 
 int ecapa_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n) {
     auto& s = S(h);
-    const svhip_config& c = h->cfg;
-    int rc = ecapa_ragged_alloc(h);
-    if (rc) return rc;
-    const size_t B = c.max_batch;
-    char* tab = nullptr;
-    if ((rc = s.rag.acquire(h, &tab))) return rc;
-    int64_t* feat_off = reinterpret_cast<int64_t*>(tab);
-    int* row0 = reinterpret_cast<int*>(tab + B * 8);
-    int M = 0, maxT = 0;
-    for (int u = 0; u < n; ++u) {
-        const int T = (int)mel_frames(c, lengths[u], is_wave);
-        row0[u] = M;
-        M += T;
-        maxT = std::max(maxT, T);
-    }
-    row0[n] = M;
-    const float* d_feat = nullptr;
-    if ((rc = rag_mel_input(h, s.rag, in, in_host, is_wave, in_off, lengths, n, row0, feat_off, &d_feat))) return rc;
-    if ((rc = s.rag.commit(h, B * 8 + (size_t)(n + 1) * 4))) return rc;
-    if ((rc = ecapa_forward_ragged(h, d_feat, n, M, maxT))) return rc;
-    set_rag_rows(h, n, {M});
+    const size_t B = h->cfg.max_batch, utt_cap[3] = {B * (size_t)h->T};
+    RagPack pk;
+    int rc;
+    if (!s.rag_stats && (rc = dev_alloc(h, &s.rag_stats, B * h->cfg.n_mels * 2))) return rc;
+    if ((rc = rag_pack(h, s.rag, kEcapaRag, utt_cap, in, in_host, is_wave, in_off, lengths, n, pk)) || (rc = ecapa_forward_ragged(h, pk))) return rc;
+    set_rag_rows(h, pk);
     s.x0_is_s32 = s.cat_f32_stale = s.h2_is_s32 = s.h1_split = false;
     return SVHIP_OK;
 }

@@ -10,13 +10,13 @@
 //   layer3      conv1(P1) and conv3 -> the head of P2, steps -> the next (B T2, 1024) of P2, AFMS -> x3 in CAT[2] (x1 stays in P0)
 //   layer4      relu(W4 CAT + b4) -> P1; context pooling (attention activation in P2) -> pooled; fc6 -> embeddings
 //
-// A ragged pack (svhip_rawnet3_embed_ragged) runs the same plan over n utterances of different lengths packed back to back: level 0
-// holds the sum of T0_u rows, level 1 the sum of T0_u / 5, level 2 the sum of T0_u / 5 / 3, each with its segment table (Seg).  The
-// buffers are the fixed-length ones: a pack holds at most max_batch * T0 level-0 rows, hence at most a fifth of that at level 1 and
-// floor(max_batch * T0 / 15) at level 2, which is what CAT and the logits are sized for (the sum of T0_u / 15 can pass max_batch * T2
-// by a few rows).  Every GEMM goes to launch_gemm_ragged and every small linear to launch_rag_linear — one kernel at every row count —
-// and the reductions over time are the per-utterance kernels of rawnet3.hip / ragged.hip, so an utterance's values do not depend on
-// the pack.
+// A ragged pack (svhip_rawnet3_embed_ragged) runs the same walk (rawnet3_walk) over n utterances of different lengths packed back to
+// back: level 0 holds the sum of T0_u rows, level 1 the sum of T0_u / 5, level 2 the sum of T0_u / 5 / 3, each with its segment table
+// (Seg).  The buffers are the fixed-length ones: a pack holds at most max_batch * T0 level-0 rows, hence at most a fifth of that at
+// level 1 and floor(max_batch * T0 / 15) at level 2, which is what CAT and the logits are sized for (the sum of T0_u / 15 can pass
+// max_batch * T2 by a few rows).  Every GEMM goes to launch_gemm_ragged and every small linear to launch_rag_linear — one kernel at
+// every row count — and the reductions over time are the per-utterance kernels of rawnet3.hip / ragged.hip, so an utterance's values
+// do not depend on the pack.
 #include <algorithm>
 #include <cmath>
 
@@ -58,17 +58,19 @@ struct RawNet3State : ModelState {
     const void* stage[5] = {};            // svhip_get_stage: front-end, layer1, layer2, layer3, layer4 outputs of the last forward
     int stage_T[5] = {}, stage_C[5] = {}, stage_ld[5] = {};
     // ragged packs (allocated by the first ragged call)
-    RagTables rag;                        // the tables of a call: sample offsets (Bmax int64), lengths (Bmax int), three row0 (Bmax + 1 each);
-                                          // staging: the utterances back to back, Bmax * (samples + 16) floats
-    int* rag_utt[3] = {};                 // utterance of every row, per level
+    RagTables rag;                        // the tables of a call (three levels) and the staging buffer: the utterances back to back,
+                                          // Bmax * (samples + 16) floats
 };
 
-// one frame level of a ragged pack: utterance u owns the rows [row0[u], row0[u + 1]), utt[m] is the utterance of row m, M rows in all
-struct Seg { const int* row0 = nullptr; const int* utt = nullptr; int M = 0; };
-
-size_t rag_tab_bytes(size_t B) { return B * 8 + B * 4 + 3 * (B + 1) * 4; }
-
 RawNet3State& S(svhip_handle* h) { return static_cast<RawNet3State&>(*h->model); }
+
+// The GEMM of one layer in either form: fixed-length (g null) through conv_gemm and its routes; over a pack, whose level g holds its rows,
+// on the generic kernel under `label`
+int rn3_gemm(svhip_handle* h, const ConvLayer& K, GemmParams p, const Seg* g, const char* label) {
+    if (!g) return conv_gemm(h, K, p);
+    p.rag_utt = g->utt; p.rag_row0 = g->row0;
+    return run(h, label, (double)g->M * K.flops_per_row, [&]() { return launch_gemm_ragged(p, h->bf16, h->cur); });
+}
 
 // One Bottle2neck on x (B T, cin) at row stride ldx, T frames in; its output y = AFMS(pool(.)) goes to (ydst, ldy), and with `add` the
 // same pass writes y + add to `sum`.  res: the identity residual (null: the layer's 1 x 1 residual conv of x into `rbuf`).
@@ -81,11 +83,8 @@ int bottle2neck(svhip_handle* h, const Rn3Layer& Ly, const void* x, int ldx, int
     const int M = in ? in->M : B * T, e = h->esz, dt = h->dt;
     hipStream_t st = h->cur;
     int rc;
-    auto gemm = [&](const ConvLayer& K, GemmParams p) {
-        if (!in) return conv_gemm(h, K, p);
-        p.rag_utt = in->utt; p.rag_row0 = in->row0;
-        return run(h, K.taps > 1 ? (p.A2 ? "rag_gemm_conv_add" : "rag_gemm_conv") : "rag_gemm", (double)M * K.flops_per_row,
-                   [&]() { return launch_gemm_ragged(p, h->bf16, st); });
+    auto gemm = [&](const ConvLayer& K, const GemmParams& p) {
+        return rn3_gemm(h, K, p, in, K.taps > 1 ? (p.A2 ? "rag_gemm_conv_add" : "rag_gemm_conv") : "rag_gemm");
     };
     if (!res) {                                                                      // residual = Conv1d(cin, C, 1, bias=False)(x)
         if ((rc = gemm(Ly.residual, conv_params(h, Ly.residual, x, ldx, rbuf, C, M, T)))) return rc;
@@ -295,69 +294,98 @@ int rawnet3_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {  
     return SVHIP_OK;
 }
 
-// RawNet3.forward on device-resident waveforms (B, L), enqueued on h->cur (one slice: b0 is 0)
-static int rawnet3_forward_part(svhip_handle* h, const float* d_wav, int b0, int B) {
+// RawNet3.forward, written once for both forms.  pk null: a fixed-length batch of B waveforms (B, L) at d_wav, on h->cur (one slice).
+// pk set: its n = B utterances (utterance u: pk->len[u] samples at d_wav + pk->off[u]) as packed rows at three frame levels, on the
+// handle's stream, every step in its segment-table form.  T0 .. T2 are the frames per utterance of the fixed form (a pack's rows are their
+// own frames: 1) and M2 the level-2 rows.
+static int rawnet3_walk(svhip_handle* h, const float* d_wav, int B, const RagPack* pk) {
     auto& s = S(h);
-    (void)b0;
     const svhip_config& c = h->cfg;
+    const Seg *g0 = pk ? &pk->lv[0] : nullptr, *g1 = pk ? &pk->lv[1] : nullptr, *g2 = pk ? &pk->lv[2] : nullptr;
     const int L = c.samples, e = h->esz, dt = h->dt;
-    const int T0 = s.T0, T1 = T0 / 5, T2 = T1 / 3;
+    const int T0 = pk ? 1 : s.T0, T1 = pk ? 1 : T0 / 5, T2 = pk ? 1 : T1 / 3;
+    const int M0 = pk ? g0->M : B * T0, M2 = pk ? g2->M : B * T2;
+    const bool bf = h->bf16;
+    if (pk) h->cur = h->stream;
     hipStream_t st = h->cur;
     void *P0 = s.buf[0], *P1 = s.buf[1], *P2 = s.buf[2], *CAT = s.cat;
     int rc;
-    auto stage = [&](int i, const void* src, int T, int Cn, int ld) { s.stage[i] = src; s.stage_T[i] = T; s.stage_C[i] = Cn; s.stage_ld[i] = ld; };
+    // svhip_get_stage: (stage_T 0: a pack's rows are counted by the handle's rag_rows)
+    auto stage = [&](int i, const void* src, int T, int Cn, int ld) { s.stage[i] = src; s.stage_T[i] = pk ? 0 : T; s.stage_C[i] = Cn; s.stage_ld[i] = ld; };
+    auto colmean = [&](const char* label, const float* y) {          // mean_t of the fp32 front-end output -> s.mean
+        return run(h, label, 0, [&]() {
+            return pk ? launch_rag_colstats(y, false, RN3_FILTERS, g0->row0, B, RN3_FILTERS, s.mean, false, 0.0f, st)
+                      : launch_colmean(y, DT_F32, RN3_FILTERS, B, T0, RN3_FILTERS, s.mean, st);
+        });
+    };
+    auto mp3 = [&](const void* x, void* y, int ldy) {                // MaxPool1d(3) of the level-1 rows x -> the level-2 rows y
+        return run(h, "rn3_maxpool", 0, [&]() {
+            return pk ? launch_rn3_rag_maxpool(x, C, y, ldy, dt, g1->row0, g2->row0, g2->utt, g2->M, C, 3, st)
+                      : launch_rn3_maxpool(x, C, y, ldy, dt, B, T1, C, 3, st);
+        });
+    };
+    auto linear = [&](const char* label, const LinearLayer& K, const float* in, float* out, int ld_out) {      // per utterance, from 2 D inputs
+        return run(h, label, 2.0 * B * K.N * K.K, [&]() {
+            return pk ? launch_rag_linear(in, 2 * D, K.W, K.bias, out, ld_out, B, K.N, 2 * D, ACT_NONE, st)
+                      : launch_rowvec_linear(in, 2 * D, K.W, K.bias, out, ld_out, B, K.N, 2 * D, ACT_NONE, st);
+        });
+    };
+    if (pk)
+        for (int l = 0; l < 3; ++l)
+            if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(pk->lv[l].row0, B, pk->lv[l].maxT, pk->lv[l].utt, st); }))) return rc;
 
     // front-end: log(|sinc(in_norm(pre_emph(x)))| + 1e-6) - mean_t                  RawNet3.py:88-99
     float* y = static_cast<float*>(P1);
     void* x0 = s.x0;
-    if ((rc = run(h, "rn3_sinc", 2.0 * B * RN3_FILTERS * RN3_TAPS * (double)T0, [&]() {
-             return launch_rn3_front(d_wav, B, L, T0, s.pre[0], s.pre[1], s.in_w, s.in_b, s.filt, !h->bf16, s.stats, y, st);
+    if ((rc = run(h, "rn3_sinc", 2.0 * RN3_FILTERS * RN3_TAPS * (double)M0, [&]() {
+             return pk ? launch_rn3_rag_front(d_wav, pk->off, pk->len, g0->row0, B, g0->maxT, s.pre[0], s.pre[1], s.in_w, s.in_b, s.filt, !bf, s.stats, y, st)
+                       : launch_rn3_front(d_wav, B, L, T0, s.pre[0], s.pre[1], s.in_w, s.in_b, s.filt, !bf, s.stats, y, st);
          }))) return rc;
-    if ((rc = run(h, "rn3_front_mean", 0, [&]() { return launch_colmean(y, DT_F32, RN3_FILTERS, B, T0, RN3_FILTERS, s.mean, st); }))) return rc;
-    if ((rc = run(h, "rn3_center", 0, [&]() { return launch_rn3_center(y, s.mean, x0, dt, B, T0, st); }))) return rc;
+    if ((rc = colmean("rn3_front_mean", y))) return rc;
+    if ((rc = run(h, "rn3_center", 0, [&]() {
+             return pk ? launch_rn3_rag_center(y, s.mean, x0, dt, g0->utt, g0->M, st) : launch_rn3_center(y, s.mean, x0, dt, B, T0, st);
+         }))) return rc;
     stage(0, x0, T0, RN3_FILTERS, RN3_FILTERS);
 
-    // layer1 = Bottle2neck(256, 1024, dilation 2, pool 5): x1 -> P0
-    if ((rc = bottle2neck(h, s.layers[0], x0, RN3_FILTERS, RN3_FILTERS, B, T0, 5, nullptr, P0, P1, P2, P1, P2, P0, C, nullptr, 0, nullptr, 0)))
+    // layer1 = Bottle2neck(256, 1024, dilation 2, pool 5): x1 -> P0 (level 1)
+    if ((rc = bottle2neck(h, s.layers[0], x0, RN3_FILTERS, RN3_FILTERS, B, T0, 5, nullptr, P0, P1, P2, P1, P2, P0, C, nullptr, 0, nullptr, 0, g0, g1)))
         return rc;
     stage(1, P0, T1, C, C);
     // mp3(x1) -> CAT[:, 0:1024), written once
-    if ((rc = run(h, "rn3_maxpool", 0, [&]() { return launch_rn3_maxpool(P0, C, CAT, 3 * C, dt, B, T1, C, 3, st); }))) return rc;
-    // layer2 = Bottle2neck(1024, 1024, dilation 3, pool 3), identity residual x1: x2 -> CAT[:, 1024:2048), mp3(x1) + x2 -> P1
-    if ((rc = bottle2neck(h, s.layers[1], P0, C, C, B, T1, 3, P0, nullptr, P1, P2, P1, P2, off(CAT, C, e), 3 * C, CAT, 3 * C, P1, C)))
+    if ((rc = mp3(P0, CAT, 3 * C))) return rc;
+    // layer2 = Bottle2neck(1024, 1024, dilation 3, pool 3), identity residual x1: x2 -> CAT[:, 1024:2048), mp3(x1) + x2 -> P1 (level 2)
+    if ((rc = bottle2neck(h, s.layers[1], P0, C, C, B, T1, 3, P0, nullptr, P1, P2, P1, P2, off(CAT, C, e), 3 * C, CAT, 3 * C, P1, C, g1, g2)))
         return rc;
     stage(2, off(CAT, C, e), T2, C, 3 * C);
     // layer3 = Bottle2neck(1024, 1024, dilation 4) on mp3(x1) + x2, which is also its residual: x3 -> CAT[:, 2048:3072)
     void* h1 = P2;
-    void* h2 = off(P2, (size_t)B * T2 * C, e);
-    if ((rc = bottle2neck(h, s.layers[2], P1, C, C, B, T2, 1, P1, nullptr, h1, h2, h1, nullptr, off(CAT, 2 * C, e), 3 * C, nullptr, 0, nullptr, 0))) return rc;
+    void* h2 = off(P2, (size_t)M2 * C, e);
+    if ((rc = bottle2neck(h, s.layers[2], P1, C, C, B, T2, 1, P1, nullptr, h1, h2, h1, nullptr, off(CAT, 2 * C, e), 3 * C, nullptr, 0, nullptr, 0, g2, g2)))
+        return rc;
     stage(3, off(CAT, 2 * C, e), T2, C, 3 * C);
 
     // layer4: relu(Conv1d(3072, 1536, 1)(cat(mp3(x1), x2, x3)))                       RawNet3.py:107-108
-    const int M2 = B * T2;
     GemmParams p4 = conv_params(h, s.l4, CAT, 3 * C, P1, D, M2, T2);
     p4.act1 = ACT_RELU;
-    if ((rc = conv_gemm(h, s.l4, p4))) return rc;
+    if ((rc = rn3_gemm(h, s.l4, p4, g2, "rag_gemm"))) return rc;
     stage(4, P1, T2, D, D);
 
-    // context attentive statistics pooling                                            RawNet3.py:112-142
+    // context attentive statistics pooling (per utterance: a pack's from the level-2 table)            RawNet3.py:112-142
     // attention.0 on cat(x, mean_t x, std_t x): the time-constant two thirds are a per-utterance bias
-    if ((rc = run(h, "rn3_tstats", 0, [&]() { return launch_rn3_tstats(P1, D, dt, B, T2, D, s.tstat, st); }))) return rc;
-    if ((rc = run(h, "rn3_att_ctx", 2.0 * B * 128 * 2 * D, [&]() {
-             return launch_rowvec_linear(s.tstat, 2 * D, s.att_ctx.W, s.att_ctx.bias, s.ctx, 128, B, 128, 2 * D, ACT_NONE, st);
-         }))) return rc;
+    if ((rc = run(h, "rn3_tstats", 0, [&]() { return launch_rn3_tstats(P1, D, dt, B, T2, D, s.tstat, st, pk ? g2->row0 : nullptr); }))) return rc;
+    if ((rc = linear("rn3_att_ctx", s.att_ctx, s.tstat, s.ctx, 128))) return rc;
     GemmParams pa = conv_params(h, s.att, P1, D, P2, 128, M2, T2);              // attention.2(relu(attention.0(.)))
     pa.act1 = ACT_RELU; pa.bias_utt = s.ctx; pa.ld_bu = 128;
-    if ((rc = conv_gemm(h, s.att, pa))) return rc;
+    if ((rc = rn3_gemm(h, s.att, pa, g2, "rag_gemm_ctx"))) return rc;
     if ((rc = run(h, "rn3_pool", 0, [&]() {
-             return launch_rn3_ctx_pool(P2, 128, s.w2, s.b2, s.logit, P1, D, dt, B, T2, D, s.bn5_scale, s.bn5_shift, s.stats, s.pooled, st);
+             return launch_rn3_ctx_pool(P2, 128, s.w2, s.b2, s.logit, P1, D, dt, B, T2, D, s.bn5_scale, s.bn5_shift, s.stats, s.pooled, st,
+                                        pk ? g2->row0 : nullptr, pk ? M2 : 0);
          }))) return rc;
     // fc6 (out_bn=False: bn6 is not applied)                                         RawNet3.py:144-148
-    return run(h, "rn3_fc6", 2.0 * B * s.fc6.N * s.fc6.K, [&]() {
-        return launch_rowvec_linear(s.pooled, 2 * D, s.fc6.W, s.fc6.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * D, ACT_NONE, st);
-    });
+    return linear("rn3_fc6", s.fc6, s.pooled, h->d_emb, c.embed_dim);
 }
 
+static int rawnet3_forward_part(svhip_handle* h, const float* d_wav, int, int B) { return rawnet3_walk(h, d_wav, B, nullptr); }
 int rawnet3_forward(svhip_handle* h, const float* d_wav, int B) { return forward_lanes(h, rawnet3_forward_part, d_wav, B, 1, B); }
 
 // ---- ragged packs ------------------------------------------------------------------------------------------
@@ -374,130 +402,21 @@ int rawnet3_ragged_check(const svhip_config& c, const int32_t* lengths, int n, b
     return SVHIP_OK;
 }
 
-// the device tables, the waveform staging buffer and the pinned table slots: once per handle
-static int rawnet3_ragged_alloc(svhip_handle* h) {
-    auto& s = S(h);
-    if (s.rag.dev) return SVHIP_OK;
-    const svhip_config& c = h->cfg;
-    const size_t B = c.max_batch, M0 = B * (size_t)s.T0;
-    int rc;
-    if (!s.rag_utt[0]) {
-        if ((rc = dev_alloc(h, &s.rag_utt[0], M0 + (M0 / 5 + 1) + (M0 / 15 + 1)))) return rc;
-        s.rag_utt[1] = s.rag_utt[0] + M0; s.rag_utt[2] = s.rag_utt[1] + M0 / 5 + 1;
-    }
-    // (a pack of n <= B utterances within M0 frames holds at most 10 M0 + 250 n <= B (samples + 9) samples)
-    return s.rag.alloc(h, rag_tab_bytes(B), B * ((size_t)c.samples + 16));
+// three frame levels: the front-end's frames, then what layer1's and layer2's pools leave
+static void rn3_rag_frames(const svhip_config&, int64_t len, bool, int T[3]) {
+    T[0] = rn3_frames((int)len);
+    T[1] = T[0] / 5;
+    T[2] = T[1] / 3;
 }
-
-// RawNet3.forward over a ragged pack (utterance u: len[u] samples at d_wav + off[u]; the tables are on the device), on the handle's
-// stream: rawnet3_forward_part's plan with the segment-table form of every step
-static int rawnet3_forward_ragged(svhip_handle* h, const float* d_wav, int n, const Seg lv[3], const int maxT[3]) {
-    auto& s = S(h);
-    const svhip_config& c = h->cfg;
-    const int e = h->esz, dt = h->dt;
-    const bool bf = h->bf16;
-    hipStream_t st = h->cur = h->stream;
-    const size_t B = c.max_batch;
-    const int64_t* d_off = reinterpret_cast<const int64_t*>(s.rag.dev);
-    const int* d_len = reinterpret_cast<const int*>(s.rag.dev + B * 8);
-    void *P0 = s.buf[0], *P1 = s.buf[1], *P2 = s.buf[2], *CAT = s.cat;
-    int rc;
-    auto stage = [&](int i, const void* src, int Cn, int ld) { s.stage[i] = src; s.stage_T[i] = 0; s.stage_C[i] = Cn; s.stage_ld[i] = ld; };
-    auto gemm = [&](const ConvLayer& L, GemmParams p, const Seg& g, const char* label) {
-        p.rag_utt = g.utt; p.rag_row0 = g.row0;
-        return run(h, label, (double)g.M * L.flops_per_row, [&]() { return launch_gemm_ragged(p, bf, st); });
-    };
-    for (int l = 0; l < 3; ++l)
-        if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(lv[l].row0, n, maxT[l], s.rag_utt[l], st); }))) return rc;
-
-    // front-end
-    float* y = static_cast<float*>(P1);
-    void* x0 = s.x0;
-    if ((rc = run(h, "rn3_sinc", 2.0 * RN3_FILTERS * RN3_TAPS * (double)lv[0].M, [&]() {
-             return launch_rn3_rag_front(d_wav, d_off, d_len, lv[0].row0, n, maxT[0], s.pre[0], s.pre[1], s.in_w, s.in_b, s.filt, !bf, s.stats, y, st);
-         }))) return rc;
-    if ((rc = run(h, "rn3_front_mean", 0, [&]() { return launch_rag_colstats(y, false, RN3_FILTERS, lv[0].row0, n, RN3_FILTERS, s.mean, false, 0.0f, st); }))) return rc;
-    if ((rc = run(h, "rn3_center", 0, [&]() { return launch_rn3_rag_center(y, s.mean, x0, dt, lv[0].utt, lv[0].M, st); }))) return rc;
-    stage(0, x0, RN3_FILTERS, RN3_FILTERS);
-
-    // layer1: x1 -> P0 (level 1)
-    if ((rc = bottle2neck(h, s.layers[0], x0, RN3_FILTERS, RN3_FILTERS, n, 1, 5, nullptr, P0, P1, P2, P1, P2, P0, C, nullptr, 0, nullptr, 0, &lv[0], &lv[1])))
-        return rc;
-    stage(1, P0, C, C);
-    // mp3(x1) -> CAT[:, 0:1024)
-    if ((rc = run(h, "rn3_maxpool", 0, [&]() { return launch_rn3_rag_maxpool(P0, C, CAT, 3 * C, dt, lv[1].row0, lv[2].row0, lv[2].utt, lv[2].M, C, 3, st); })))
-        return rc;
-    // layer2: x2 -> CAT[:, 1024:2048), mp3(x1) + x2 -> P1 (level 2)
-    if ((rc = bottle2neck(h, s.layers[1], P0, C, C, n, 1, 3, P0, nullptr, P1, P2, P1, P2, off(CAT, C, e), 3 * C, CAT, 3 * C, P1, C, &lv[1], &lv[2])))
-        return rc;
-    stage(2, off(CAT, C, e), C, 3 * C);
-    // layer3 on mp3(x1) + x2: x3 -> CAT[:, 2048:3072)
-    void* h1 = P2;
-    void* h2 = off(P2, (size_t)lv[2].M * C, e);
-    if ((rc = bottle2neck(h, s.layers[2], P1, C, C, n, 1, 1, P1, nullptr, h1, h2, h1, nullptr, off(CAT, 2 * C, e), 3 * C, nullptr, 0, nullptr, 0, &lv[2], &lv[2])))
-        return rc;
-    stage(3, off(CAT, 2 * C, e), C, 3 * C);
-
-    // layer4
-    const int M2 = lv[2].M;
-    GemmParams p4 = conv_params(h, s.l4, CAT, 3 * C, P1, D, M2, 1);
-    p4.act1 = ACT_RELU;
-    if ((rc = gemm(s.l4, p4, lv[2], "rag_gemm"))) return rc;
-    stage(4, P1, D, D);
-
-    // context attentive statistics pooling, per utterance from the level-2 table
-    if ((rc = run(h, "rn3_tstats", 0, [&]() { return launch_rn3_tstats(P1, D, dt, n, 1, D, s.tstat, st, lv[2].row0); }))) return rc;
-    if ((rc = run(h, "rn3_att_ctx", 2.0 * n * 128 * 2 * D, [&]() {
-             return launch_rag_linear(s.tstat, 2 * D, s.att_ctx.W, s.att_ctx.bias, s.ctx, 128, n, 128, 2 * D, ACT_NONE, st);
-         }))) return rc;
-    GemmParams pa = conv_params(h, s.att, P1, D, P2, 128, M2, 1);
-    pa.act1 = ACT_RELU; pa.bias_utt = s.ctx; pa.ld_bu = 128;
-    if ((rc = gemm(s.att, pa, lv[2], "rag_gemm_ctx"))) return rc;
-    if ((rc = run(h, "rn3_pool", 0, [&]() {
-             return launch_rn3_ctx_pool(P2, 128, s.w2, s.b2, s.logit, P1, D, dt, n, 1, D, s.bn5_scale, s.bn5_shift, s.stats, s.pooled, st, lv[2].row0, M2);
-         }))) return rc;
-    return run(h, "rn3_fc6", 2.0 * n * s.fc6.N * s.fc6.K, [&]() {
-        return launch_rag_linear(s.pooled, 2 * D, s.fc6.W, s.fc6.bias, h->d_emb, c.embed_dim, n, c.embed_dim, 2 * D, ACT_NONE, st);
-    });
-}
+static const RagRule kRawnet3Rag = {3, rn3_rag_frames, false};
 
 int rawnet3_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool, const int64_t* in_off, const int32_t* lengths, int n) {
     auto& s = S(h);
-    int rc = rawnet3_ragged_alloc(h);
-    if (rc) return rc;
-    const size_t B = h->cfg.max_batch;
-    char* tab = nullptr;
-    if ((rc = s.rag.acquire(h, &tab))) return rc;
-    int64_t* t_off = reinterpret_cast<int64_t*>(tab);
-    int* t_len = reinterpret_cast<int*>(tab + B * 8);
-    int* t_row0[3];
-    for (int l = 0; l < 3; ++l) t_row0[l] = t_len + B + l * (B + 1);
-    int M[3] = {0, 0, 0}, maxT[3] = {0, 0, 0};
-    int64_t pos = 0;
-    h->cur = h->stream;
-    for (int u = 0; u < n; ++u) {
-        const int T0 = rn3_frames(lengths[u]);
-        const int T[3] = {T0, T0 / 5, T0 / 5 / 3};
-        for (int l = 0; l < 3; ++l) {
-            t_row0[l][u] = M[l];
-            M[l] += T[l];
-            maxT[l] = std::max(maxT[l], T[l]);
-        }
-        t_len[u] = lengths[u];
-        t_off[u] = in_off[u];
-        if (in_host) {
-            SV_HIP(h, hipMemcpyAsync(s.rag.wav + pos, in + in_off[u], (size_t)lengths[u] * 4, hipMemcpyHostToDevice, h->stream));
-            t_off[u] = pos;
-            pos += lengths[u];
-        }
-    }
-    for (int l = 0; l < 3; ++l) t_row0[l][n] = M[l];
-    if ((rc = s.rag.commit(h, rag_tab_bytes(B)))) return rc;
-    Seg lv[3];
-    const int* d_row0 = reinterpret_cast<const int*>(s.rag.dev + B * 12);
-    for (int l = 0; l < 3; ++l) { lv[l].row0 = d_row0 + l * (B + 1); lv[l].utt = s.rag_utt[l]; lv[l].M = M[l]; }
-    if ((rc = rawnet3_forward_ragged(h, in_host ? s.rag.wav : in, n, lv, maxT))) return rc;
-    set_rag_rows(h, n, {M[0], M[1], M[2]});
+    const size_t M0 = (size_t)h->cfg.max_batch * s.T0, utt_cap[3] = {M0, M0 / 5 + 1, M0 / 15 + 1};
+    RagPack pk;
+    int rc;
+    if ((rc = rag_pack(h, s.rag, kRawnet3Rag, utt_cap, in, in_host, true, in_off, lengths, n, pk)) || (rc = rawnet3_walk(h, pk.in, n, &pk))) return rc;
+    set_rag_rows(h, pk);
     return SVHIP_OK;
 }
 

@@ -15,10 +15,10 @@
 //   tail     X = relu(K + g S) and D = dw_1'(X) + b' of the next block in the same pass      tn_mega_tail
 //
 // A ragged pack (titanet_embed_ragged): n utterances of T_u mel frames back to back, sum T_u <= Bmax T rows of the same buffers.  The
-// network has no subsampling, so the pack has one frame level and one row0 table.  Every GEMM goes through launch_gemm_ragged (the
-// prolog's three taps zero-padded at each utterance's own ends), the depthwise convs and the block tail run in their segment-table
-// forms, and the SE squeeze, the pooling, the input test and the last linear layer are ragged.hip's: no value of an utterance depends on
-// what it is packed with.
+// network has no subsampling, so the pack has one frame level and one row0 table.  titanet_walk is the one walk of the layers: for a
+// pack every GEMM goes through launch_gemm_ragged (the prolog's three taps zero-padded at each utterance's own ends), the depthwise
+// convs and the block tail run in their segment-table forms, and the SE squeeze, the pooling, the input test and the last linear layer
+// are ragged.hip's: no value of an utterance depends on what it is packed with.
 #include <cmath>
 #include <cstdlib>
 
@@ -55,10 +55,7 @@ struct TitaNetState : ModelState {
     float *mean = nullptr, *gate = nullptr;                  // (Bmax, H) SE squeeze, SE gate
     float *pool_raw = nullptr, *pool = nullptr;              // (Bmax, 3072) pooled [mean | std], after BN
     // ragged packs (allocated by the first ragged call; the buffers above already hold Bmax T rows)
-    RagTables rag;                        // the tables of a call: feature offsets (Bmax int64), row0 (Bmax + 1)
-    int64_t* rag_feat_off = nullptr;
-    int* rag_row0 = nullptr;
-    int* rag_utt = nullptr;               // (Bmax T) utterance of every row
+    RagTables rag;                        // the tables of a call (one level: mel frames, Bmax T rows) and the waveform staging buffer
 };
 
 TitaNetState& S(svhip_handle* h) { return static_cast<TitaNetState&>(*h->model); }
@@ -227,214 +224,136 @@ int titanet_alloc(svhip_handle* h) {
     }
     return SVHIP_OK;
 }
-static int titanet_forward_part(svhip_handle* h, const float* d_feat, int b0, int B) {
+// TitaNet.forward, written once for both forms.  pk null: a fixed-length batch of B utterances of h->T frames, (B, n_mels, T) at d_feat,
+// on h->cur; the GEMMs take their routes through conv_gemm.  pk set: its n = B utterances as packed rows (features at d_feat + pk->off[u]),
+// on the handle's stream; every GEMM goes to the generic kernel (launch_gemm_ragged: one kernel at every row count, so a row's sums do not
+// depend on the pack), which is why the bf16 handles' column-sum squeeze is not used there.  The helpers pick the form; below them the
+// network reads once.
+static int titanet_walk(svhip_handle* h, const float* d_feat, int B, const RagPack* pk) {
     auto& s = S(h);
-    (void)b0;
     const svhip_config& c = h->cfg;
-    const int T = h->T, M = B * T, H = c.channels, E = 1536, k = s.k, dt = h->dt;
+    const Seg* g = pk ? &pk->lv[0] : nullptr;
+    const int T = g ? 1 : h->T, M = g ? g->M : B * T, H = c.channels, E = 1536, k = s.k, dt = h->dt;      // (T: of the GEMMs; a pack's rows are their own frames)
     const bool bf = h->bf16;
+    if (g) h->cur = h->stream;
     hipStream_t st = h->cur;
-    void *PRO = s.buf[0], *X = s.buf[1], *D0 = s.buf[2], *D = s.buf[3], *S = s.buf[4], *K = s.buf[5];
-    float* cs = bf ? h->d_colsum : nullptr;
-    int rc;
-    // the mel power (B, n_mels, T) as it is (no log, no normalisation) -> frame-major (B T, n_mels) in the compute type
-    if ((rc = run(h, "prologue", 0, [&]() {
-             return launch_prologue(d_feat, h->X_in, bf, B, c.n_mels, T, 0, nullptr, nullptr, h->d_pstats, st);
-         }))) return rc;
-    // prolog: relu(BN(Conv1dSamePadding(n_mels, H, 3)))                          TitaNet.py:226-227, titanet_blocks.py:123-139
-    GemmParams pp = conv_params(h, s.prolog, h->X_in, c.n_mels, PRO, H, M, T);
-    pp.act1 = ACT_RELU; pp.pad_mode = PAD_ZERO;
-    if ((rc = conv_gemm(h, s.prolog, pp))) return rc;
-    const int nb = (int)s.blocks.size();
-    const void* x = PRO;
-    for (int i = 0; i < nb; ++i) {
-        const TnBlock& Bk = s.blocks[i];
-        if ((rc = conv_gemm(h, Bk.skip, conv_params(h, Bk.skip, x, H, K, H, M, T)))) return rc;
-        if (i == 0 && (rc = run(h, "tn_dw", 2.0 * k * H * M, [&]() { return launch_tn_dw(x, D0, Bk.dw_w[0], Bk.dw_b[0], dt, k, B, T, H, st); })))
-            return rc;
-        const void* d = i == 0 ? D0 : D;
-        GemmPlan g3;
-        for (int j = 0; j < 3; ++j) {
-            GemmParams p = conv_params(h, Bk.pw[j], d, H, S, H, M, T);
-            p.act1 = ACT_RELU;
-            if (j == 2) { p.colsum = cs; p.colsum_stride = h->colsum_region; }
-            if ((rc = conv_gemm(h, Bk.pw[j], p, nullptr, 0, &g3))) return rc;
-            if (j < 2) {
-                if ((rc = run(h, "tn_dw", 2.0 * k * H * M, [&]() { return launch_tn_dw(S, D, Bk.dw_w[j + 1], Bk.dw_b[j + 1], dt, k, B, T, H, st); })))
-                    return rc;
-                d = D;
-            }
-        }
-        // squeeze-excitation (titanet_blocks.py:162-192): the squeeze from the GEMM's column sums when its kernel wrote them
-        const bool from_part = g3.colsum_groups != 0;
-        if (!from_part && (rc = run(h, "tn_se_mean", 0, [&]() { return launch_colmean(S, dt, H, B, T, H, s.mean, st); }))) return rc;
-        if ((rc = run(h, "tn_se_mlp", 4.0 * B * (H / 16) * H, [&]() {
-                 return launch_se_mlp(from_part ? nullptr : s.mean, from_part ? cs : nullptr, T, bf ? Bk.se1_bf : (const void*)Bk.se1, h->d_zeros,
-                                      bf ? Bk.se2T_bf : (const void*)Bk.se2T, h->d_zeros, s.gate, bf, B, H, H / 16, st, from_part ? g3.colsum_groups : 8);
-             }))) return rc;
-        // relu(skip + SE(sub_blocks(x))) and the next block's first depthwise conv                     TitaNet.py:306-318
-        const TnBlock* nx = i + 1 < nb ? &s.blocks[i + 1] : nullptr;
-        if ((rc = run(h, "tn_mega_tail", nx ? 2.0 * k * H * M : 0.0, [&]() {
-                 return launch_tn_mega_tail(K, S, s.gate, X, nx ? nx->dw_w[0] : nullptr, nx ? nx->dw_b[0] : nullptr, nx ? D : nullptr, dt, k, B, T, H, st);
-             }))) return rc;
-        x = X;
-    }
-    // epilog: relu(BN(conv1x1(x)))                                                   TitaNet.py:244-245
-    GemmParams pe = conv_params(h, s.epilog, x, H, s.enc, E, M, T);
-    pe.act1 = ACT_RELU;
-    if ((rc = conv_gemm(h, s.epilog, pe))) return rc;
-    // attentive statistics pooling (TitaNet.py:389-431): energies = out_linear(tanh(in_linear(x))), softmax over T, mean and
-    // sqrt(clamp(var, 1e-6)) (the variance in the centred form), then decoder.pool.1
-    GemmParams pa = conv_params(h, s.att_in, s.enc, E, s.att, 128, M, T);
-    pa.act2 = ACT_TANH;
-    if ((rc = conv_gemm(h, s.att_in, pa))) return rc;
-    GemmParams pl = conv_params(h, s.att_out, s.att, 128, s.logits, E, M, T);
-    pl.out_f32 = 1;
-    if ((rc = conv_gemm(h, s.att_out, pl))) return rc;
-    if ((rc = run(h, "tn_asp_pool", 0, [&]() {
-             return launch_asp_pool(s.logits, s.enc, bf, E, B, T, E, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-6f, 0.0f, st);
-         }))) return rc;
-    // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the ReLU epilogues would have dropped it)
-    if ((rc = run(h, "tn_in_check", 0, [&]() {
-             return launch_tn_nonfinite_rows(d_feat, (int64_t)c.n_mels * T, B, s.pool, 2 * E, 2 * E, st);
-         }))) return rc;
-    // decoder.linear: Linear(3072, nOut) with BatchNorm1d(nOut) folded in                                     TitaNet.py:355-358
-    return run(h, "tn_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
-        return launch_rowvec_linear(s.pool, 2 * E, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * E, ACT_NONE, st);
-    });
-}
-
-int titanet_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, titanet_forward_part, d_feat, B, 1, B); }
-
-// ---- ragged packs ------------------------------------------------------------------------------------------
-// TitaNet's rules for a pack (RaggedCheckFn; include/svhip.h), on the host alone
-int titanet_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
-    if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft) return refuse(err, SVHIP_ERR_INVALID, "bad hop_length / max_batch / samples");
-    const int64_t cap = (int64_t)c.max_batch * mel_frames(c, c.samples, true);
-    int64_t rows = 0;
-    for (int i = 0; i < n; ++i) {
-        if (is_wave && lengths[i] < c.n_fft)
-            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld samples, fewer than n_fft=%d", i, (long long)lengths[i], c.n_fft);
-        const int64_t T = mel_frames(c, lengths[i], is_wave);
-        if (T < 1) return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld frames, fewer than 1", i, (long long)T);
-        if (int rc = rag_rows_fit(err, i, rows += T, cap, "T")) return rc;
-    }
-    return SVHIP_OK;
-}
-
-// the segment tables, the waveform staging buffer and the pinned table slots: once per handle
-static int titanet_ragged_alloc(svhip_handle* h) {
-    auto& s = S(h);
-    if (s.rag.dev) return SVHIP_OK;
-    const svhip_config& c = h->cfg;
-    const size_t B = c.max_batch;
-    int rc;
-    if (!s.rag_utt && (rc = dev_alloc(h, &s.rag_utt, B * (size_t)h->T))) return rc;
-    if ((rc = s.rag.alloc(h, B * 8 + (B + 1) * 4, B * ((size_t)c.samples + c.hop_length)))) return rc;
-    s.rag_feat_off = reinterpret_cast<int64_t*>(s.rag.dev);
-    s.rag_row0 = reinterpret_cast<int*>(s.rag.dev + B * 8);
-    return SVHIP_OK;
-}
-
-// TitaNet.forward over the packed rows of a ragged batch (features at d_feat + rag_feat_off[u]; tables on the device).  One slice on the
-// handle's stream.  Every GEMM goes to the generic kernel (launch_gemm_ragged: one kernel at every row count, so a row's sums do not depend
-// on the pack), which is why the bf16 handles' column-sum squeeze is not used here: the squeeze is launch_rag_colstats at both computes.
-static int titanet_forward_ragged(svhip_handle* h, const float* d_feat, int n, int M, int maxT) {
-    auto& s = S(h);
-    const svhip_config& c = h->cfg;
-    const int H = c.channels, E = 1536, k = s.k, dt = h->dt;
-    const bool bf = h->bf16;
-    hipStream_t st = h->cur = h->stream;
-    const int* row0 = s.rag_row0;
     void *PRO = s.buf[0], *X = s.buf[1], *D0 = s.buf[2], *D = s.buf[3], *Sb = s.buf[4], *K = s.buf[5];
+    float* cs = !g && bf ? h->d_colsum : nullptr;       // the third pointwise GEMM's column-sum partials (fixed form, bf16)
     int rc;
-    auto gemm = [&](const ConvLayer& L, GemmParams p) {
-        p.rag_utt = s.rag_utt; p.rag_row0 = row0;
+    auto gemm = [&](const ConvLayer& L, GemmParams p, GemmPlan* plan = nullptr) {
+        if (!g) return conv_gemm(h, L, p, nullptr, 0, plan);
+        p.rag_utt = g->utt; p.rag_row0 = g->row0;
         return run(h, "rag_gemm", (double)M * L.flops_per_row, [&]() { return launch_gemm_ragged(p, bf, st); });
     };
     auto dw = [&](const void* x, void* d, const float* w, const float* b) {
-        return run(h, "tn_dw_rag", 2.0 * k * H * M, [&]() { return launch_tn_dw_ragged(x, d, w, b, dt, k, row0, n, maxT, H, st); });
+        return run(h, g ? "tn_dw_rag" : "tn_dw", 2.0 * k * H * M, [&]() {
+            return g ? launch_tn_dw_ragged(x, d, w, b, dt, k, g->row0, B, g->maxT, H, st) : launch_tn_dw(x, d, w, b, dt, k, B, T, H, st);
+        });
     };
-    if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(row0, n, maxT, s.rag_utt, st); }))) return rc;
-    // the mel power as it is (no log, no normalisation) -> the packed rows (M, n_mels) in the compute type
-    if ((rc = run(h, "rag_prologue", 0, [&]() {
-             return launch_rag_prologue(d_feat, s.rag_feat_off, row0, n, maxT, h->X_in, bf, c.n_mels, 0, nullptr, nullptr, h->d_pstats, st);
-         }))) return rc;
-    GemmParams pp = conv_params(h, s.prolog, h->X_in, c.n_mels, PRO, H, M, 1);
+    auto squeeze = [&]() {          // mean_t Sb -> s.mean
+        return g ? run(h, "rag_se_mean", 0, [&]() { return launch_rag_colstats(Sb, bf, H, g->row0, B, H, s.mean, false, 0.0f, st); })
+                 : run(h, "tn_se_mean", 0, [&]() { return launch_colmean(Sb, dt, H, B, T, H, s.mean, st); });
+    };
+    // relu(skip + gate * Sb) -> X and, with a next block, its first depthwise conv -> D
+    auto tail = [&](const TnBlock* nx) {
+        const float *w = nx ? nx->dw_w[0] : nullptr, *b = nx ? nx->dw_b[0] : nullptr;
+        void* d = nx ? D : nullptr;
+        return run(h, g ? "tn_mega_tail_rag" : "tn_mega_tail", nx ? 2.0 * k * H * M : 0.0, [&]() {
+            return g ? launch_tn_mega_tail_ragged(K, Sb, s.gate, X, w, b, d, dt, k, g->row0, B, g->maxT, H, st)
+                     : launch_tn_mega_tail(K, Sb, s.gate, X, w, b, d, dt, k, B, T, H, st);
+        });
+    };
+    // the mel power as it is (no log, no normalisation) -> frame-major rows (M, n_mels) in the compute type
+    if (g) {
+        if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(g->row0, B, g->maxT, g->utt, st); }))) return rc;
+        if ((rc = run(h, "rag_prologue", 0, [&]() {
+                 return launch_rag_prologue(d_feat, pk->off, g->row0, B, g->maxT, h->X_in, bf, c.n_mels, 0, nullptr, nullptr, h->d_pstats, st);
+             }))) return rc;
+    } else if ((rc = run(h, "prologue", 0, [&]() {
+                    return launch_prologue(d_feat, h->X_in, bf, B, c.n_mels, T, 0, nullptr, nullptr, h->d_pstats, st);
+                }))) return rc;
+    // prolog: relu(BN(Conv1dSamePadding(n_mels, H, 3))), zero-padded at each utterance's own ends      TitaNet.py:226-227, titanet_blocks.py:123-139
+    GemmParams pp = conv_params(h, s.prolog, h->X_in, c.n_mels, PRO, H, M, T);
     pp.act1 = ACT_RELU; pp.pad_mode = PAD_ZERO;
     if ((rc = gemm(s.prolog, pp))) return rc;
     const int nb = (int)s.blocks.size();
     const void* x = PRO;
     for (int i = 0; i < nb; ++i) {
         const TnBlock& Bk = s.blocks[i];
-        if ((rc = gemm(Bk.skip, conv_params(h, Bk.skip, x, H, K, H, M, 1)))) return rc;
+        if ((rc = gemm(Bk.skip, conv_params(h, Bk.skip, x, H, K, H, M, T)))) return rc;
         if (i == 0 && (rc = dw(x, D0, Bk.dw_w[0], Bk.dw_b[0]))) return rc;
         const void* d = i == 0 ? D0 : D;
+        GemmPlan g3;
         for (int j = 0; j < 3; ++j) {
-            GemmParams p = conv_params(h, Bk.pw[j], d, H, Sb, H, M, 1);
+            GemmParams p = conv_params(h, Bk.pw[j], d, H, Sb, H, M, T);
             p.act1 = ACT_RELU;
-            if ((rc = gemm(Bk.pw[j], p))) return rc;
+            if (j == 2 && !g) { p.colsum = cs; p.colsum_stride = h->colsum_region; }
+            if ((rc = gemm(Bk.pw[j], p, &g3))) return rc;
             if (j < 2) {
                 if ((rc = dw(Sb, D, Bk.dw_w[j + 1], Bk.dw_b[j + 1]))) return rc;
                 d = D;
             }
         }
-        if ((rc = run(h, "rag_se_mean", 0, [&]() { return launch_rag_colstats(Sb, bf, H, row0, n, H, s.mean, false, 0.0f, st); }))) return rc;
-        if ((rc = run(h, "tn_se_mlp", 4.0 * n * (H / 16) * H, [&]() {
-                 return launch_se_mlp(s.mean, nullptr, 1, bf ? Bk.se1_bf : (const void*)Bk.se1, h->d_zeros, bf ? Bk.se2T_bf : (const void*)Bk.se2T,
-                                      h->d_zeros, s.gate, bf, n, H, H / 16, st, 8);
+        // squeeze-excitation (titanet_blocks.py:162-192): the squeeze from the GEMM's column sums when its kernel wrote them (never for a
+        // pack: launch_gemm_ragged leaves g3 as it is)
+        const bool from_part = g3.colsum_groups != 0;
+        if (!from_part && (rc = squeeze())) return rc;
+        if ((rc = run(h, "tn_se_mlp", 4.0 * B * (H / 16) * H, [&]() {
+                 return launch_se_mlp(from_part ? nullptr : s.mean, from_part ? cs : nullptr, T, bf ? Bk.se1_bf : (const void*)Bk.se1, h->d_zeros,
+                                      bf ? Bk.se2T_bf : (const void*)Bk.se2T, h->d_zeros, s.gate, bf, B, H, H / 16, st, from_part ? g3.colsum_groups : 8);
              }))) return rc;
-        const TnBlock* nx = i + 1 < nb ? &s.blocks[i + 1] : nullptr;
-        if ((rc = run(h, "tn_mega_tail_rag", nx ? 2.0 * k * H * M : 0.0, [&]() {
-                 return launch_tn_mega_tail_ragged(K, Sb, s.gate, X, nx ? nx->dw_w[0] : nullptr, nx ? nx->dw_b[0] : nullptr, nx ? D : nullptr, dt, k,
-                                                   row0, n, maxT, H, st);
-             }))) return rc;
+        // relu(skip + SE(sub_blocks(x))) and the next block's first depthwise conv                     TitaNet.py:306-318
+        if ((rc = tail(i + 1 < nb ? &s.blocks[i + 1] : nullptr))) return rc;
         x = X;
     }
-    GemmParams pe = conv_params(h, s.epilog, x, H, s.enc, E, M, 1);
+    // epilog: relu(BN(conv1x1(x)))                                                   TitaNet.py:244-245
+    GemmParams pe = conv_params(h, s.epilog, x, H, s.enc, E, M, T);
     pe.act1 = ACT_RELU;
     if ((rc = gemm(s.epilog, pe))) return rc;
-    GemmParams pa = conv_params(h, s.att_in, s.enc, E, s.att, 128, M, 1);
+    // attentive statistics pooling (TitaNet.py:389-431): energies = out_linear(tanh(in_linear(x))), softmax over T, mean and
+    // sqrt(clamp(var, 1e-6)) (the variance in the centred form), then decoder.pool.1
+    GemmParams pa = conv_params(h, s.att_in, s.enc, E, s.att, 128, M, T);
     pa.act2 = ACT_TANH;
     if ((rc = gemm(s.att_in, pa))) return rc;
-    GemmParams pl = conv_params(h, s.att_out, s.att, 128, s.logits, E, M, 1);
+    GemmParams pl = conv_params(h, s.att_out, s.att, 128, s.logits, E, M, T);
     pl.out_f32 = 1;
     if ((rc = gemm(s.att_out, pl))) return rc;
-    if ((rc = run(h, "rag_asp_pool", 0, [&]() {
-             return launch_rag_asp_pool(s.logits, s.enc, bf, E, row0, n, E, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-6f, st);
+    if ((rc = run(h, g ? "rag_asp_pool" : "tn_asp_pool", 0, [&]() {
+             return g ? launch_rag_asp_pool(s.logits, s.enc, bf, E, g->row0, B, E, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-6f, st)
+                      : launch_asp_pool(s.logits, s.enc, bf, E, B, T, E, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-6f, 0.0f, st);
          }))) return rc;
-    // an utterance with a non-finite input value gets a NaN embedding: its own row only
+    // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the ReLU epilogues would have dropped it): its
+    // own row only
     if ((rc = run(h, "tn_in_check", 0, [&]() {
-             return launch_tn_nonfinite_rows_ragged(d_feat, s.rag_feat_off, row0, c.n_mels, n, s.pool, 2 * E, 2 * E, st);
+             return g ? launch_tn_nonfinite_rows_ragged(d_feat, pk->off, g->row0, c.n_mels, B, s.pool, 2 * E, 2 * E, st)
+                      : launch_tn_nonfinite_rows(d_feat, (int64_t)c.n_mels * T, B, s.pool, 2 * E, 2 * E, st);
          }))) return rc;
-    return run(h, "rag_fc", 2.0 * n * s.fc.N * s.fc.K, [&]() {
-        return launch_rag_linear(s.pool, 2 * E, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, n, c.embed_dim, 2 * E, ACT_NONE, st);
+    // decoder.linear: Linear(3072, nOut) with BatchNorm1d(nOut) folded in                                     TitaNet.py:355-358
+    return run(h, g ? "rag_fc" : "tn_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
+        return g ? launch_rag_linear(s.pool, 2 * E, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * E, ACT_NONE, st)
+                 : launch_rowvec_linear(s.pool, 2 * E, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, 2 * E, ACT_NONE, st);
     });
 }
 
+static int titanet_forward_part(svhip_handle* h, const float* d_feat, int, int B) { return titanet_walk(h, d_feat, B, nullptr); }
+int titanet_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, titanet_forward_part, d_feat, B, 1, B); }
+
+// ---- ragged packs ------------------------------------------------------------------------------------------
+// TitaNet's rules for a pack (RaggedCheckFn; include/svhip.h), on the host alone
+int titanet_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
+    return rag_mel_check(c, lengths, n, is_wave, err, true, "hop_length / max_batch / samples", 1, "");
+}
+
+// one frame level (the network has no subsampling): the mel frames
+static void titanet_rag_frames(const svhip_config& c, int64_t len, bool is_wave, int T[3]) { T[0] = (int)mel_frames(c, len, is_wave); }
+static const RagRule kTitanetRag = {1, titanet_rag_frames, true};
+
 int titanet_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n) {
-    auto& s = S(h);
-    const svhip_config& c = h->cfg;
-    int rc = titanet_ragged_alloc(h);
-    if (rc) return rc;
-    const size_t B = c.max_batch;
-    char* tab = nullptr;
-    if ((rc = s.rag.acquire(h, &tab))) return rc;
-    int64_t* feat_off = reinterpret_cast<int64_t*>(tab);
-    int* row0 = reinterpret_cast<int*>(tab + B * 8);
-    int M = 0, maxT = 0;
-    for (int u = 0; u < n; ++u) {
-        const int T = (int)mel_frames(c, lengths[u], is_wave);
-        row0[u] = M;
-        M += T;
-        maxT = std::max(maxT, T);
-    }
-    row0[n] = M;
-    const float* d_feat = nullptr;
-    if ((rc = rag_mel_input(h, s.rag, in, in_host, is_wave, in_off, lengths, n, row0, feat_off, &d_feat))) return rc;
-    if ((rc = s.rag.commit(h, B * 8 + (size_t)(n + 1) * 4))) return rc;
-    if ((rc = titanet_forward_ragged(h, d_feat, n, M, maxT))) return rc;
-    set_rag_rows(h, n, {M});
+    const size_t utt_cap[3] = {(size_t)h->cfg.max_batch * h->T};
+    RagPack pk;
+    int rc;
+    if ((rc = rag_pack(h, S(h).rag, kTitanetRag, utt_cap, in, in_host, is_wave, in_off, lengths, n, pk)) || (rc = titanet_walk(h, pk.in, n, &pk))) return rc;
+    set_rag_rows(h, pk);
     return SVHIP_OK;
 }
 

@@ -125,8 +125,8 @@ struct svhip_handle {
     float *d_ones = nullptr, *d_zeros = nullptr;      // 4096 ones / zeros: stand-ins for absent per-channel vectors (GemmParams::ones / zeros)
     float* d_emb = nullptr;
     int lastB = 0;
-    // the last forward when it was a ragged one (svhip_get_stage): the packed rows of each of its rag_levels frame levels, the input's first
-    // (ECAPA, TitaNet: mel frames; Conformer: mel frames, subsampled frames; RawNet3: its levels 0 .. 2).  rag_levels = 0: a fixed-length forward
+    // the last forward when it was a ragged one (svhip_get_stage): the packed rows of each of its rag_levels frame levels (RagPack), the
+    // input's first.  rag_levels = 0: a fixed-length forward
     int64_t rag_rows[3] = {};
     int rag_levels = 0;
     // shared by several models: each is allocated by the alloc / finalize hook of the models named, and null on the others' handles
@@ -301,19 +301,15 @@ int refuse(std::string& err, int code, const char* fmt, ...) __attribute__((form
 int rag_rows_fit(std::string& err, int i, int64_t rows, int64_t cap, const char* frames_name);
 // in int64: a length near INT32_MAX at hop_length 1 must reach the capacity rule, not wrap
 inline int64_t mel_frames(const svhip_config& c, int64_t len, bool is_wave) { return is_wave ? len / c.hop_length + 1 : len; }
-// a ragged forward has run over n utterances: what svhip_get_stage needs of it
-inline void set_rag_rows(svhip_handle* h, int n, std::initializer_list<int> rows) {
-    h->lastB = n;
-    h->rag_levels = 0;
-    for (int r : rows) h->rag_rows[h->rag_levels++] = r;
-}
-// The tables of a ragged call: a device block in which the model lays out its tables, a ring of four pinned host copies of it, each
-// guarded by an event (an SVHIP_ASYNC call returns before the copy has run, and the caller's arrays are free on return), and the
-// device staging buffer of host-pointer waveforms.  One per model state; the device memory is the handle's (dev_alloc)
+// The tables of a ragged call: one device block (layout: rag_view, api_ragged.hip), a ring of four pinned host copies of it, each
+// guarded by an event (an SVHIP_ASYNC call returns before the copy has run, and the caller's arrays are free on return), the device
+// utt table of every frame level and the device staging buffer of host-pointer waveforms.  One per model state; the device memory is
+// the handle's (dev_alloc)
 struct RagSlot { char* host = nullptr; hipEvent_t done = nullptr; bool busy = false; };
 struct RagTables {
     char* dev = nullptr;
     float* wav = nullptr;
+    int* utt[3] = {};
     RagSlot slot[4], *cur = nullptr;
     int next = 0;
     int alloc(svhip_handle* h, size_t table_bytes, size_t wav_floats);      // once per handle (later calls do nothing)
@@ -321,11 +317,35 @@ struct RagTables {
     int commit(svhip_handle* h, size_t bytes);          // its first `bytes` to `dev` on the handle's stream; it is busy until that copy has run
     ~RagTables();
 };
-// the mel input of a pack (ECAPA, Conformer; mel0: the n + 1 first mel frames on the host): waveforms through the staging buffer and one
-// fbank launch per utterance into h->d_feat, host features copied there, device features read in place; fills feat_off, *d_feat is
-// the array they index
-int rag_mel_input(svhip_handle* h, RagTables& rag, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths,
-                  int n, const int* mel0, int64_t* feat_off, const float** d_feat);
+// One frame level of a pack: utterance u owns the rows [row0[u], row0[u + 1]), utt[m] is the utterance of row m, M rows in all and maxT in
+// the longest utterance.  row0 / utt are device tables (utt: the forward fills it from row0, launch_rag_rows); hrow0 is row0 in the call's
+// pinned slot, for what slices the pack while enqueueing (readable until the ring hands the slot out again, four calls later)
+struct Seg { const int* row0 = nullptr; int* utt = nullptr; const int* hrow0 = nullptr; int M = 0, maxT = 0; };
+// A pack as a forward sees it: n utterances at `levels` frame levels, lv[0] the input's.  in + off[u] (device tables off / len) is
+// utterance u's first element — of its (n_mels, T_u) block of mel power, or of its len[u] samples for a waveform model
+struct RagPack { int n = 0, levels = 0; Seg lv[3]; const int64_t* off = nullptr; const int32_t* len = nullptr; const float* in = nullptr; };
+// How a model packs: the frames of one utterance at each of its levels, and whether its input is the mel power (rag_mel_input; staging
+// slack hop_length floats per utterance) or the waveform itself (staged as it is, off / len for the front-end kernel; slack 16 floats)
+struct RagRule { int levels; void (*frames)(const svhip_config& c, int64_t len, bool is_wave, int T[3]); bool mel; };
+// The host side of a ragged forward, after the model's check has passed: allocates on the handle's first ragged call (utt_cap: the
+// rows of each level's utt table; 0: nothing reads that level's), takes a table slot, lays out the pack (all four models: offsets
+// max_batch x int64 | lengths max_batch x int32 | one row0 of max_batch + 1 ints per level), stages the input, enqueues the table
+// upload and fills pk for the model's forward
+int rag_pack(svhip_handle* h, RagTables& rag, const RagRule& rule, const size_t utt_cap[3], const float* in, bool in_host, bool is_wave,
+             const int64_t* in_off, const int32_t* lengths, int n, RagPack& pk);
+// that forward has run: what svhip_get_stage needs of it
+inline void set_rag_rows(svhip_handle* h, const RagPack& pk) {
+    h->lastB = pk.n;
+    h->rag_levels = pk.levels;
+    for (int l = 0; l < pk.levels; ++l) h->rag_rows[l] = pk.lv[l].M;
+}
+// What the packs of the three mel models must all pass, in this order: the configuration (hop_length, max_batch, samples >= n_fft and
+// the model's cfg_extra_ok; cfg_names ends the text), every waveform n_fft samples, every utterance min_frames frames (why: the text's
+// explanation, "" or " (...)"), the model's further rules on an utterance of T frames (more with its own figure `bound`, or null), the
+// running row sum
+using RagUttRule = int(int64_t bound, int i, int64_t T, std::string& err);
+int rag_mel_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err, bool cfg_extra_ok, const char* cfg_names,
+                  int min_frames, const char* why, RagUttRule* more = nullptr, int64_t bound = 0);
 
 // api_gemm.hip: the GEMM of one conv layer.  conv_plan is the one place that decides its kernel: conv_gemm launches what it returns,
 // and the producers of an operand ask it too, so that they write the layout that kernel reads.
