@@ -413,6 +413,9 @@ int svhip_synth_waveforms(svhip_handle* h, uint64_t seed, int64_t first_utt, int
  *                  value (blocks.3.tdnn1 of SVHIP_F32X3 handles whose tdnn1 wrote its first chunks in the split layout only; "mel"
  *                  after the fused front-end); "rn_gru_in" (the (B T, 512) GRU
  *                  input of a one-slice forward) and "rn_gru_h" (the (B, 1024) fp32 last GRU state) of SVHIP_MODEL_RAWNET2_GRU;
+ *                  with option "rn_keep" what a RawNet2 forward stored on its way (INTEGRATION.md lists the names: "rn_front",
+ *                  "rn_b<i>_pre", "rn_b<i>_x", "rn_b<i>_o", "rn_b<i>_c2", "rn_b<i>_pool", "rn_b<i>_gate", "rn_agg_in", "rn_logits") — SVHIP_ERR_STATE
+ *                  where the route taken never stored the tensor;
  *                  "tn_prolog" (B T, H), "tn_dw0" (block 0's first depthwise output, its bias included), "tn_mega_last" (the last
  *                  mega-block's output), "tn_enc" (B T, 1536) and "tn_pool" (B, 3072, after BN) of SVHIP_MODEL_TITANET;
  *                  "cf_in" (B T', 256: the input projection), "cf_block0", "cf_attn0" (block 0's per-head attention context before
@@ -434,7 +437,8 @@ double svhip_workload_flops(const svhip_handle* h);
  * svhip_create, as a new handle's defaults; afterwards only this call changes them — no getenv on the hot path.  Names:
  * "pw3_cus" (cap of the persistent GEMM grids; 0: off), "rn_unfused", "rn_stop", "rn_snap", "asp_v1", "r2_big", "x3_keep_f32",
  * "asnorm_slab", "asnorm_f32mfma", "asnorm_norefit", "score_f32mfma", "score_tiled", "fbank32", "fbank_unfused", "rn_sinc_full", "cv_off",
- * "pw3_tail_off", "n128_off", "r2_slices", "rn_tail_big", "rn_sinc_f32", "rn_step_off", "rn_pool_off", "layer_labels", "rn_conv_unfused".
+ * "pw3_tail_off", "n128_off", "r2_slices", "rn_tail_big", "rn_sinc_f32", "rn_step_off", "rn_pool_off", "layer_labels", "rn_conv_unfused",
+ * "rn_keep".
  * Unknown names: SVHIP_ERR_INVALID. */
 int svhip_set_option(svhip_handle* h, const char* name, int32_t value);
 /* Free the scoring / metrics scratch slots of the handle (grown on demand, otherwise kept until svhip_destroy). */

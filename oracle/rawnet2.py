@@ -1,6 +1,7 @@
 """Oracle (TEST INFRASTRUCTURE) — functional restatement of the reference RawNet2 forward
 (``front_proc='sinc'``, ``aggregate='asp'``: the variant the fusion models build,
-``src/models/Raw_ECAPA_sinc_asp.py:26-28``).
+``src/models/Raw_ECAPA_sinc_asp.py:26-28``; ``front_proc='conv'`` replaces LayerNorm, the sinc
+filters, the pool and first_bn by one strided convolution, ``src/models/RawNet2_custom.py:166-169``).
 
 Follows ``src/models/RawNet2_custom.py:161-227`` and ``src/models/RawNet_baseline.py:13-24``
 (LayerNorm), ``:62-68`` (AFMS), ``:221-232`` (RawNetBasicBlock), ``:265-361`` (SincConv_fast).
@@ -67,15 +68,30 @@ def basic_block(x, sd, p, downsample):
     return afms(out, sd, p + ".afms")
 
 
-def rawnet2_forward(x, sd, stages=None):
-    """RawNet2.forward RawNet2_custom.py:161-227.  x: (B, 32000) waveform -> (B, nOut)."""
-    x = layer_norm(x, sd)                                                          # :171
-    filt = sinc_filters(sd["first_conv.low_hz_"], sd["first_conv.band_hz_"])       # RawNet_baseline.py:320-357
-    if stages is not None:
-        stages["sinc_filters"] = filt
+def front_sinc(x, sd, filt=None):
+    """RawNet2_custom.py:170-176 after the LayerNorm: sinc filters, |.|, max_pool1d(3), first_bn, LeakyReLU.  x: (B, L) normalised."""
+    if filt is None:
+        filt = sinc_filters(sd["first_conv.low_hz_"], sd["first_conv.band_hz_"])   # RawNet_baseline.py:320-357
     x = F.conv1d(x.unsqueeze(1), filt.unsqueeze(1))                                # :359-361 (valid)
     x = F.max_pool1d(torch.abs(x), 3)                                              # RawNet2_custom.py:174
-    x = F.leaky_relu(bn(x, sd, "first_bn"), 0.3)                                   # :175-176
+    return F.leaky_relu(bn(x, sd, "first_bn"), 0.3)                                # :175-176
+
+
+def front_conv(x, sd):
+    """RawNet2_custom.py:45-52,166-169: conv1 = Conv1d(1, 128, 3, stride=3) with bias, nothing else.  x: (B, L) waveform."""
+    return F.conv1d(x.unsqueeze(1), sd["conv1.weight"], sd["conv1.bias"], stride=3)
+
+
+def rawnet2_forward(x, sd, stages=None, front_proc="sinc"):
+    """RawNet2.forward RawNet2_custom.py:161-227.  x: (B, 32000) waveform -> (B, nOut)."""
+    if front_proc == "conv":
+        x = front_conv(x, sd)                                                      # :166-169
+    else:
+        x = layer_norm(x, sd)                                                      # :171
+        filt = sinc_filters(sd["first_conv.low_hz_"], sd["first_conv.band_hz_"])
+        if stages is not None:
+            stages["sinc_filters"] = filt
+        x = front_sinc(x, sd, filt)
     if stages is not None:
         stages["front"] = x
     for li, nblk in enumerate(LAYERS, start=1):

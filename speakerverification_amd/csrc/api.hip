@@ -52,6 +52,7 @@ const DevOptRow kDevOpts[] = {
     SV_OPT(rn_tail_big, "SVHIP_RN_TAIL_BIG", OPT_IS1, 0),
     SV_OPT(r2_slices, "SVHIP_R2_SLICES", OPT_NUM, -1),
     SV_OPT(rn_conv_unfused, "SVHIP_RN_CONV_UNFUSED", OPT_IS1, 0),
+    SV_OPT(rn_keep, "SVHIP_RN_KEEP", OPT_IS1, 0),
 };
 #undef SV_OPT
 

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 
 #include "handle.h"
 
@@ -55,6 +56,12 @@ struct RawNet2State : ModelState {
     int T1 = 0;
     const void* dbg_x = nullptr; int dbg_T = 0, dbg_C = 0;   // SVHIP_RN_STOP developer hook (tests)
     void* snap = nullptr; size_t snap_cap = 0; int snap_T = 0, snap_C = 0;      // SVHIP_RN_SNAP=2: copy of block 2's pre-activation (stage "rn_snap")
+    // option rn_keep: copies of what the forward stored, by stage name.  A buffer holds max_batch utterances (allocated when its stage is
+    // first kept), so the slices of a forward on several lanes fill it side by side; a stage counts as kept when every utterance of the
+    // last forward (`epoch`) wrote it.
+    struct Kept { void* buf = nullptr; size_t rows = 0, cols = 0; bool f32 = false; uint64_t epoch = 0; int utts = 0; };
+    std::map<std::string, Kept> kept;
+    uint64_t epoch = 0;
 };
 
 RawNet2State& S(svhip_handle* h) { return static_cast<RawNet2State&>(*h->model); }
@@ -356,6 +363,14 @@ int rawnet2_alloc(svhip_handle* h) {
     return SVHIP_OK;
 }
 
+// the stages of option rn_keep: rn_front, rn_agg_in, rn_logits, rn_b<block>_pre | _x | _o | _c2 | _pool | _gate
+static bool rn_keep_name(const std::string& n) {
+    if (n == "rn_front" || n == "rn_agg_in" || n == "rn_logits") return true;
+    if (n.size() < 7 || n.compare(0, 4, "rn_b") != 0 || n[4] < '0' || n[4] > '7' || n[5] != '_') return false;
+    const std::string w = n.substr(6);
+    return w == "pre" || w == "x" || w == "o" || w == "c2" || w == "pool" || w == "gate";
+}
+
 int rawnet2_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {
     auto& s = S(h);
     const int B = h->lastB;
@@ -366,6 +381,13 @@ int rawnet2_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {
     else if (n == "rn_gru_in" && rn_is_gru(h->cfg.model)) {
         if (!s.gru_in) SV_FAIL(h, SVHIP_ERR_STATE, "stage rn_gru_in: the last forward ran as several batch slices (SVHIP_LANES)");
         v.src = s.gru_in; v.rows = (size_t)B * s.gru_T; v.cols = v.ld = 512;
+    }
+    else if (rn_keep_name(n)) {
+        const auto it = s.kept.find(n);
+        if (it == s.kept.end() || it->second.epoch != s.epoch || it->second.utts != B)
+            SV_FAIL(h, SVHIP_ERR_STATE, "stage %s: %s", n.c_str(), h->opt.rn_keep ? "the route of the last forward never stored it" : "option rn_keep was not set");
+        const RawNet2State::Kept& k = it->second;
+        v.src = k.buf; v.rows = (size_t)B * k.rows; v.cols = v.ld = k.cols; v.f32 = k.f32;
     }
     else return unknown_stage(h, n);
     return SVHIP_OK;
@@ -423,6 +445,32 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         s.snap_T = Tn; s.snap_C = Cn;
         return SVHIP_OK;
     };
+    // developer hook (option rn_keep): copy a tensor the forward has just stored — `rows` x `cols` per utterance, in the handle's type, in
+    // fp32 (KEEP_F32) or in the S32 layout (KEEP_S32, kept as fp32) — on the forward's own stream.  Nothing else reads the option: the
+    // kernels enqueued, their operands and their routes are those of a forward without it.
+    enum { KEEP_DT, KEEP_F32, KEEP_S32 };
+    const bool keeping = h->opt.rn_keep != 0;
+    auto keep = [&](const std::string& name, const void* src, size_t rows, int cols, int kind) -> int {
+        if (!keeping) return SVHIP_OK;
+        const bool f32 = kind != KEEP_DT || !bf;
+        const size_t es = f32 ? 4 : 2;
+        RawNet2State::Kept& k = s.kept[name];
+        if (!k.buf || k.rows != rows || k.cols != (size_t)cols || k.f32 != f32) {
+            void* q = nullptr;
+            SV_HIP(h, hipMalloc(&q, (size_t)c.max_batch * rows * cols * es));
+            h->allocs.push_back(q);
+            k.buf = q; k.rows = rows; k.cols = cols; k.f32 = f32; k.epoch = 0;
+        }
+        if (k.epoch != s.epoch) { k.epoch = s.epoch; k.utts = 0; }
+        void* dst = static_cast<char*>(k.buf) + (size_t)b0 * rows * cols * es;
+        if (kind == KEEP_S32) SV_HIP(h, launch_unsplit_s32(src, cols, static_cast<float*>(dst), cols, (int64_t)B * rows, cols, st));
+        else SV_HIP(h, hipMemcpyAsync(dst, src, (size_t)B * rows * cols * es, hipMemcpyDeviceToDevice, st));
+        k.utts += B;
+        return SVHIP_OK;
+    };
+    auto blk = [](int i, const char* what) { return "rn_b" + std::to_string(i) + "_" + what; };
+    // (the pre-activation block `bn` will read, or after block 7 the aggregation's input; the input x of block `bn`)
+    auto keep_pre = [&](int bn, const void* src, int Tn, int Cn, bool s32) { return keep(bn < 8 ? blk(bn, "pre") : std::string("rn_agg_in"), src, Tn, Cn, s32 ? KEEP_S32 : KEEP_DT); };
     // F32X3: does block `bn`, entered with Tn frames, run its convolutions (and its projection shortcut) on the 128 x 128 split kernel
     // (r2_step.hip, modes 1 / 2)?  a1: its pre-activation lrelu(bn1(x)) in the S32 layout; xb: its input x.  (Otherwise they run on the
     // tiled kernel that splits its fp32 operands in registers: 170 - 190 TFLOP/s.)
@@ -470,6 +518,8 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
                                    nullptr, nullptr, nullptr, rn_xn, s.Lp, h->num_cu, sym);
          }))) return rc;
     s.dbg_x = x; s.dbg_T = T; s.dbg_C = 128;
+    if (!conv_fused && (rc = keep("rn_front", x, T, 128, KEEP_DT))) return rc;        // (the conv-fused block 0 reads the waveform: no front-end tensor)
+    if (sinc_pre && (rc = keep_pre(0, pre, T, 128, true))) return rc;
     if (stop_after == 0) return SVHIP_OK;
     // bf16: the 128 -> 128 pooled blocks (layer1, layer2) each run as ONE fused kernel + the AFMS gate kernel; the gate of
     // block i is applied by block i + 1 on the way in (or by the rn_afms_apply pass in front of the first GEMM block)
@@ -498,6 +548,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         if ((rc = run(h, "rn_afms_gate", 2.0 * B * K.cout * K.cout, [&]() {
                  return launch_rn_afms_gate(rn_part, rn_block128_nparts(B, bp.T, h->num_cu), B, K.cout, bp.Tout, K.afms_fcT, K.afms_fc.bias, gate, st);
              }))) return rc;
+        if ((rc = keep(blk(first, "pool"), dst, bp.Tout, K.cout, KEEP_DT)) || (rc = keep(blk(first, "gate"), gate, 1, K.cout, KEEP_F32))) return rc;
         T /= 3;
         xin = dst;
         g_alpha = K.alpha; g_gate = gate;
@@ -511,6 +562,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         void* xdst = (first < 8 && s.blocks[first].has_shortcut && stop_after < 0) ? nullptr : x;
         if ((rc = run(h, "rn_afms_apply", 0, [&]() { return launch_rn_afms_apply(xin, xdst, dt, Kp.alpha, g_gate, B, T, Kp.cout, st, nsc, nsh, pre, 0.3f); }))) return rc;
         s.dbg_x = x; s.dbg_T = T; s.dbg_C = Kp.cout;
+        if ((rc = keep_pre(first, pre, T, Kp.cout, false)) || (xdst && first < 8 && (rc = keep(blk(first, "x"), x, T, Kp.cout, KEEP_DT)))) return rc;
         if (snap_at == first && b0 == 0 && (rc = snapshot(pre, T, Kp.cout))) return rc;
     }
     for (int bi = first; bi < 8; ++bi) {
@@ -521,6 +573,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         if (((bi == 0 && first == 0) || stop_after >= 0) && !(bi == 0 && sinc_pre)) {
             pre_is_s32 = pre_s32_for(bi, T, x);
             if ((rc = run(h, "rn_bn_act", 0, [&]() { return launch_rn_bn_act(x, pre, dt, K.bn1_scale, K.bn1_shift, M, K.cin, 0.3f, st, pre_is_s32); }))) return rc;
+            if ((rc = keep_pre(bi, pre, T, K.cin, pre_is_s32))) return rc;
         }
         // (an fp32 pre-activation is split into a buffer that is free here: the next-x buffer when `sc` holds the projected shortcut)
         void* const split_dst = K.has_shortcut ? xn : sc;
@@ -560,6 +613,8 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
             return conv_gemm(h, K.conv2, p2);
         };
         if ((rc = convs())) return rc;
+        // conv2 + shortcut (F32X3: pooled where conv2 pools), or conv2 alone ("c2") where the tail adds the identity shortcut
+        if ((rc = keep(blk(bi, resid_in_tail ? "c2" : "o"), o, pooled_by_conv ? T / 3 : T, K.cout, KEEP_DT))) return rc;
         // AFMS gate; the same pass writes the next consumer's lrelu(bn(.)): block bi+1's bn1, or the aggregation BN after block 7
         const float* nsc = bi < 7 ? s.blocks[bi + 1].bn1_scale : s.agg_scale;
         const float* nsh = bi < 7 ? s.blocks[bi + 1].bn1_shift : s.agg_shift;
@@ -578,6 +633,8 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
                      return launch_rn_tail(o, x_dead ? nullptr : xn, npre, dt, K.downsample, K.alpha, K.afms_fcT, K.afms_fc.bias, nsc, nsh, B, T, K.cout, 0.3f, st,
                                            resid_in_tail, sliced ? rn_scratch : nullptr, sliced ? rn_gate[0] : nullptr, h->num_cu, tail_s32);
                  }))) return rc;
+            // (only the sliced form stores its gate; one workgroup per utterance keeps it on chip)
+            if (!h->opt.rn_tail_big && rn_tail_slices(dt, B, Tn, K.cout, h->num_cu) > 0 && (rc = keep(blk(bi, "gate"), rn_gate[0], 1, K.cout, KEEP_F32))) return rc;
             pre_is_s32 = tail_s32;
             T = Tn;
         } else {
@@ -597,10 +654,13 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
             // (F32X3: when the next block runs on the split convolution kernel its pre-activation is written in the S32 layout right here)
             const bool next_s32 = npre && pre_s32_for(bi + 1, T, xn);
             if ((rc = run(h, "rn_afms_apply", 0, [&]() { return launch_rn_afms_apply(y, x_dead ? nullptr : xn, dt, K.alpha, rn_gate[0], B, T, K.cout, st, nsc, nsh, npre, 0.3f, next_s32); }))) return rc;
+            if ((rc = keep(blk(bi, "gate"), rn_gate[0], 1, K.cout, KEEP_F32))) return rc;
             pre_is_s32 = next_s32;
         }
         std::swap(x, xn);
         s.dbg_x = x; s.dbg_T = T; s.dbg_C = K.cout;
+        if (npre && (rc = keep_pre(bi + 1, npre, T, K.cout, pre_is_s32))) return rc;
+        if (!x_dead && bi < 7 && (rc = keep(blk(bi + 1, "x"), x, T, K.cout, KEEP_DT))) return rc;
         if (stop_after == bi + 1) return SVHIP_OK;
         if (snap_at == bi + 1 && b0 == 0 && npre && (rc = snapshot(npre, T, K.cout))) return rc;
     }
@@ -637,6 +697,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
     GemmParams pl = conv_params(h, s.att3, hb, 128, rn_logits, 512, M, h->T);
     pl.out_f32 = 1;
     if ((rc = conv_gemm(h, s.att3, pl))) return rc;
+    if ((rc = keep("rn_logits", rn_logits, T, 512, KEEP_F32))) return rc;
     if ((rc = run(h, "rn_attn_pool", 0, [&]() { return launch_rn_attn_pool(rn_logits, pre, dt, B, T, 512, rn_pooled, st); }))) return rc;
     if ((rc = run(h, "rn_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
              // (16-bit handles, full batches: the K-split MFMA form — fp32-grade handles keep ONE kernel for every batch size here)
@@ -650,6 +711,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
 // blocks are grids of 86 - 400 workgroups, the AFMS passes are latency-bound) run beside the big ones of another
 int rawnet2_forward(svhip_handle* h, const float* d_wav, int B) {
     const int lanes = (h->lanes > 1 && B >= 16 * h->lanes && h->opt.rn_stop < 0) ? h->lanes : 1;
+    ++S(h).epoch;
     const int rc = forward_lanes(h, rawnet2_forward_part, d_wav, B, lanes, ((B + lanes - 1) / lanes + 3) & ~3);
     if (lanes > 1) S(h).gru_in = nullptr;          // the slices' GRU inputs are not one (B T, 512) block
     return rc;

@@ -93,6 +93,7 @@ struct svhip_handle {
         int rn_tail_big;          // RawNet2 block tail: one workgroup per utterance at every batch size (tests)
         int r2_slices;            // bf16 Res2Net chain: time slices per utterance (-1: by batch size, 0 / 1: whole utterances, n: forced)
         int rn_conv_unfused;      // 16-bit RawNet2 'conv' handles: rn_conv3_front + plain rn_block128 instead of block 0 reading the waveform (tests, A/B)
+        int rn_keep;              // RawNet2: copy what the forward stores (block inputs, outputs, gates, logits) for svhip_get_stage; the kernels enqueued stay the same (tests)
     } opt;
     bool bf16 = false;                        // 16-bit storage handle: bf16, or fp16 when `f16` is set (the flag keeps its round-1 name)
     bool f16 = false;                         // SVHIP_F16: the 16-bit type is IEEE half (RawNet2)

@@ -816,15 +816,18 @@ __global__ __launch_bounds__(256) void rn_attn_pool_kernel(const float* __restri
     for (int t = 0; t < Tn; ++t) mx = fmaxf(mx, lg[(int64_t)t * C]);
     float se = 0.0f;
     for (int t = 0; t < Tn; ++t) se += expf(lg[(int64_t)t * C] - mx);
-    float m = 0.0f, q = 0.0f;
+    float m = 0.0f;
+    for (int t = 0; t < Tn; ++t) m = fmaf(to_f32<T>(xp[(int64_t)t * C]), expf(lg[(int64_t)t * C] - mx) / se, m);
+    // the variance around the mean, not sum(w x^2) - m^2: in fp32 that difference keeps the rounding of x^2 (up to 2^-24 x^2, which passes
+    // the clamp from |x| = 13 on), so that one frame (utterances of up to 4 624 samples) gave a std of up to 1.5 times the reference's
+    // sqrt(1e-5) — found by tests/test_gpu_rawnet2_oracle.py (`pooled`, fp32-grade handles)
+    float v = 0.0f;
     for (int t = 0; t < Tn; ++t) {
-        const float w = expf(lg[(int64_t)t * C] - mx) / se;
-        const float xv = to_f32<T>(xp[(int64_t)t * C]);
-        m = fmaf(xv, w, m);
-        q = fmaf(xv * xv, w, q);
+        const float d = to_f32<T>(xp[(int64_t)t * C]) - m;
+        v = fmaf(d * d, expf(lg[(int64_t)t * C] - mx) / se, v);
     }
     out[(int64_t)b * 2 * C + c] = m;
-    out[(int64_t)b * 2 * C + C + c] = sqrtf(fmaxf(q - m * m, 1e-5f));
+    out[(int64_t)b * 2 * C + C + c] = sqrtf(fmaxf(v, 1e-5f));
 }
 
 
