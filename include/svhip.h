@@ -227,6 +227,32 @@ int svhip_rawnet3_embed_ragged(svhip_handle* h, const float* wav, const int64_t*
 /* lengths[i] are samples.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is svhip_last_error(NULL). */
 int svhip_rawnet3_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n);
 
+/* Ragged RawNet2 packs (added under ABI v5): the same call for SVHIP_MODEL_RAWNET2_CONV, the raw-waveform branch of Raw_ECAPA_conv_asp.
+ * The sinc models (SVHIP_MODEL_RAWNET2, SVHIP_MODEL_RAWNET2_GRU) are refused with SVHIP_ERR_UNSUPPORTED: their LayerNorm(nb_samp) fixes
+ * the input length by the weights.  The other ragged calls keep refusing every RawNet2 handle.
+ *   utterance i is wav[offsets[i] .. offsets[i] + lengths[i]) and has T1_i = lengths[i] / 3 frames after the conv front-end, then
+ *   T1_i / 3, / 9, .. / 729 after the six max_pool1d(3) stages; the pack is laid out back to back at each of the seven levels (an
+ *   utterance's left-over frames of a pool are dropped per utterance, as its own forward would drop them).
+ * wav / offsets / lengths / emb_out / flags: the rules of svhip_embed_wave_ragged.
+ * CAPACITY, checked on the host before anything is enqueued (svhip_rawnet2_ragged_check is the same test without a handle):
+ *   1 <= n <= max_batch;  every lengths[i] >= 2187 (729 front-end frames: one frame reaches the aggregation);  offsets >= 0;
+ *   sum_i T1_i <= max_batch * T1, the level-0 rows of the workspace the handle owns (T1 = samples / 3, samples >= 2187).  That one
+ *   rule bounds the other levels; what a pack can hold beyond max_batch * (T1 / 729) rows at the last level lives in buffers the
+ *   first ragged call allocates (once; nothing is allocated per call), with the segment tables and a waveform staging buffer.
+ * Anything else is SVHIP_ERR_INVALID with a message that names the utterance and the limit.  Compute SVHIP_F32, SVHIP_BF16 or SVHIP_F16
+ * (this model's 16-bit mode); SVHIP_F32X3 and every other model return SVHIP_ERR_UNSUPPORTED.
+ * BATCH INVARIANCE as above: bit-for-bit the same embedding and stages whatever the pack — no grid size, slice count or kernel
+ * choice of the ragged forward depends on n, on the neighbours or on the device's compute units; to the precision of the compute
+ * type against a fixed-length call.  A non-finite waveform (or an fp16 overflow) gives a non-finite embedding for its own utterance
+ * only, and SVHIP_ERR_NONFINITE.
+ * STAGES after a ragged call, rows packed in utterance order: rn_pooled (n, 1024) always; with option rn_keep also rn_front (sum T1_i,
+ * 128), rn_b<i>_pre / rn_b<i>_o (block i's level, its channels), rn_b<i>_x (where the next block's identity shortcut reads it),
+ * rn_b<i>_gate (n, channels), rn_agg_in and rn_logits (last level, 512). */
+int svhip_rawnet2_embed_ragged(svhip_handle* h, const float* wav, const int64_t* offsets, const int32_t* lengths,
+                               int32_t n, float* emb_out, int32_t flags);
+/* lengths[i] are samples.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is svhip_last_error(NULL). */
+int svhip_rawnet2_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n);
+
 /* Ragged Conformer packs (added under ABI v5): the same calls for SVHIP_MODEL_CONFORMER.  The ECAPA and RawNet3 calls above keep
  * refusing a Conformer handle with SVHIP_ERR_UNSUPPORTED.
  *   in / offsets / lengths / emb_out / flags: the rules of svhip_embed_wave_ragged (is_wave != 0: lengths and offsets in samples) and of

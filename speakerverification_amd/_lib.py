@@ -74,6 +74,8 @@ _SIGNATURES = {
     "svhip_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),
     "svhip_rawnet3_embed_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32]),
     "svhip_rawnet3_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32]),
+    "svhip_rawnet2_embed_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32]),
+    "svhip_rawnet2_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32]),
     "svhip_conformer_embed_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32]),
     "svhip_conformer_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),
     "svhip_titanet_embed_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32]),

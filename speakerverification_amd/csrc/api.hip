@@ -11,8 +11,8 @@
 using namespace svhip;
 
 namespace svhip {      // the ragged hooks of the models that have them: only kModels names them
-RaggedCheckFn ecapa_ragged_check, rawnet3_ragged_check, conformer_ragged_check, titanet_ragged_check;
-RaggedEmbedFn ecapa_embed_ragged, rawnet3_embed_ragged, conformer_embed_ragged, titanet_embed_ragged;      // (RawNet3: waveforms only, is_wave is true)
+RaggedCheckFn ecapa_ragged_check, rawnet2_ragged_check, rawnet3_ragged_check, conformer_ragged_check, titanet_ragged_check;
+RaggedEmbedFn ecapa_embed_ragged, rawnet2_embed_ragged, rawnet3_embed_ragged, conformer_embed_ragged, titanet_embed_ragged;      // (RawNet2 / RawNet3: waveforms only, is_wave is true)
 }
 
 namespace {
@@ -68,7 +68,8 @@ const ModelOps kModels[] = {
     {SVHIP_MODEL_ECAPA,        ecapa_check,     ecapa_spec,     ecapa_finalize,     ecapa_alloc,     ecapa_embed_wave,    ecapa_forward,     ecapa_stage,     2,
      nullptr, ecapa_ragged_check, ecapa_embed_ragged},
     {SVHIP_MODEL_RAWNET2,      rawnet2_check,   rawnet2_spec,   rawnet2_finalize,   rawnet2_alloc,   rawnet2_forward,     nullptr,           rawnet2_stage,   4},
-    {SVHIP_MODEL_RAWNET2_CONV, rawnet2_check,   rawnet2_spec,   rawnet2_finalize,   rawnet2_alloc,   rawnet2_forward,     nullptr,           rawnet2_stage,   4},
+    {SVHIP_MODEL_RAWNET2_CONV, rawnet2_check,   rawnet2_spec,   rawnet2_finalize,   rawnet2_alloc,   rawnet2_forward,     nullptr,           rawnet2_stage,   4,
+     nullptr, rawnet2_ragged_check, rawnet2_embed_ragged},       // (the sinc models' LayerNorm(nb_samp) fixes their length: no ragged forward)
     {SVHIP_MODEL_RAWNET2_GRU,  rawnet2_check,   rawnet2_spec,   rawnet2_finalize,   rawnet2_alloc,   rawnet2_forward,     nullptr,           rawnet2_stage,   4},
     {SVHIP_MODEL_RAWNET3,      rawnet3_check,   rawnet3_spec,   rawnet3_finalize,   rawnet3_alloc,   rawnet3_forward,     nullptr,           rawnet3_stage,   4,
      nullptr, rawnet3_ragged_check, rawnet3_embed_ragged},
@@ -209,19 +210,27 @@ int emit_embeddings(svhip_handle* h, int B, float* emb_out, int flags) {
 }
 
 // ---- ragged calls: utterances of different lengths in one call --------------------------------------------------
-// Each ragged export serves one model (kModels names its check and its forward) and refuses the others by its name
-struct RaggedExport { int model; const char* name; };
-constexpr RaggedExport kRagEcapa{SVHIP_MODEL_ECAPA, "ECAPA"}, kRagRawnet3{SVHIP_MODEL_RAWNET3, "RAWNET3"},
-                       kRagConformer{SVHIP_MODEL_CONFORMER, "CONFORMER"}, kRagTitanet{SVHIP_MODEL_TITANET, "TITANET"};
+// Each ragged export serves one model (kModels names its check and its forward) and refuses the others by its name; computes: the
+// compute types it accepts, as a mask of 1 << SVHIP_*, and their names for the refusal
+struct RaggedExport { int model; const char* name; unsigned computes; const char* compute_names; };
+constexpr unsigned kRagF32Bf16 = 1u << SVHIP_F32 | 1u << SVHIP_BF16;
+constexpr RaggedExport kRagEcapa{SVHIP_MODEL_ECAPA, "ECAPA", kRagF32Bf16, "SVHIP_F32 or SVHIP_BF16"},
+                       kRagRawnet2{SVHIP_MODEL_RAWNET2_CONV, "RAWNET2_CONV", kRagF32Bf16 | 1u << SVHIP_F16, "SVHIP_F32, SVHIP_BF16 or SVHIP_F16"},
+                       kRagRawnet3{SVHIP_MODEL_RAWNET3, "RAWNET3", kRagF32Bf16, "SVHIP_F32 or SVHIP_BF16"},
+                       kRagConformer{SVHIP_MODEL_CONFORMER, "CONFORMER", kRagF32Bf16, "SVHIP_F32 or SVHIP_BF16"},
+                       kRagTitanet{SVHIP_MODEL_TITANET, "TITANET", kRagF32Bf16, "SVHIP_F32 or SVHIP_BF16"};
 
 // the rules of a pack, on the host alone, in this order: the scope, the model's rules on the configuration, the pack size, the model's
 // rules on every utterance in index order
 int ragged_rules(const RaggedExport& x, const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
+    if (x.model == SVHIP_MODEL_RAWNET2_CONV && (c.model == SVHIP_MODEL_RAWNET2 || c.model == SVHIP_MODEL_RAWNET2_GRU))
+        return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: SVHIP_MODEL_%s only (the sinc front-end of SVHIP_MODEL_RAWNET2 and SVHIP_MODEL_RAWNET2_GRU "
+                      "starts with LayerNorm(nb_samp), whose weights fix the input length)", x.name, x.name);
     if (c.model != x.model)
-        return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: SVHIP_MODEL_%s only (ECAPA, RawNet3, Conformer and TitaNet packs have their own calls; the "
-                      "other models embed one length per handle)", x.name, x.name);
-    if (c.compute != SVHIP_F32 && c.compute != SVHIP_BF16)
-        return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: compute SVHIP_F32 or SVHIP_BF16 only", x.name);
+        return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: SVHIP_MODEL_%s only (ECAPA, RawNet2 'conv', RawNet3, Conformer and TitaNet packs have their own "
+                      "calls; the other models embed one length per handle)", x.name, x.name);
+    if (c.compute < 0 || c.compute >= 32 || !(x.computes >> c.compute & 1u))
+        return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: compute %s only", x.name, x.compute_names);
     // The pack size is tested between the model's two kinds of rules, as it always was, so that the first failing rule stays the same
     // one.  A RaggedCheckFn looks at no utterance when it is given n = 0, so the first call is its rules on the configuration alone
     // (they also make max_batch and the divisions of the second call safe); the second adds every utterance in index order.
@@ -523,6 +532,15 @@ int svhip_rawnet3_embed_ragged(svhip_handle* h, const float* wav, const int64_t*
 
 int svhip_rawnet3_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n) {
     return ragged_check(kRagRawnet3, cfg, lengths, n, true);
+}
+
+int svhip_rawnet2_embed_ragged(svhip_handle* h, const float* wav, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
+                               int32_t flags) {
+    return embed_ragged(kRagRawnet2, h, wav, offsets, lengths, n, emb_out, flags, true);
+}
+
+int svhip_rawnet2_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n) {
+    return ragged_check(kRagRawnet2, cfg, lengths, n, true);
 }
 
 int svhip_conformer_embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,

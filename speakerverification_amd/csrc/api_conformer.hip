@@ -527,7 +527,7 @@ int conformer_ragged_check(const svhip_config& c, const int32_t* lengths, int n,
 }
 
 // two frame levels: the mel frames and the subsampled frames
-static void cf_rag_frames(const svhip_config& c, int64_t len, bool is_wave, int T[3]) {
+static void cf_rag_frames(const svhip_config& c, int64_t len, bool is_wave, int T[RAG_LEVELS]) {
     T[0] = (int)mel_frames(c, len, is_wave);
     T[1] = cf_sub(cf_sub(T[0]));
 }
@@ -556,7 +556,7 @@ static int conformer_ragged_pos(svhip_handle* h, int rows) {
 int conformer_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n) {
     auto& s = S(h);
     const svhip_config& c = h->cfg;
-    const size_t utt_cap[3] = {0, s.rows_cap};          // (nothing reads the mel level's utt table)
+    const size_t utt_cap[RAG_LEVELS] = {0, s.rows_cap};          // (nothing reads the mel level's utt table)
     RagPack pk;
     int rc;
     if (!s.rag_stats && (rc = dev_alloc(h, &s.rag_stats, (size_t)c.max_batch * c.n_mels * 2))) return rc;

@@ -424,7 +424,7 @@ int ecapa_ragged_check(const svhip_config& c, const int32_t* lengths, int n, boo
 }
 
 // one frame level: the mel frames
-static void ecapa_rag_frames(const svhip_config& c, int64_t len, bool is_wave, int T[3]) { T[0] = (int)mel_frames(c, len, is_wave); }
+static void ecapa_rag_frames(const svhip_config& c, int64_t len, bool is_wave, int T[RAG_LEVELS]) { T[0] = (int)mel_frames(c, len, is_wave); }
 static const RagRule kEcapaRag = {1, ecapa_rag_frames, true};
 
 // ECAPA_TDNN.forward over the packed rows of a ragged batch (features at pk.in + pk.off[u]; tables on the device).  One slice on
@@ -504,7 +504,7 @@ static int ecapa_forward_ragged(svhip_handle* h, const RagPack& pk) {
 
 int ecapa_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n) {
     auto& s = S(h);
-    const size_t B = h->cfg.max_batch, utt_cap[3] = {B * (size_t)h->T};
+    const size_t B = h->cfg.max_batch, utt_cap[RAG_LEVELS] = {B * (size_t)h->T};
     RagPack pk;
     int rc;
     if (!s.rag_stats && (rc = dev_alloc(h, &s.rag_stats, B * h->cfg.n_mels * 2))) return rc;

@@ -1,4 +1,4 @@
-// api_ragged.hip — what the ragged calls of ECAPA-TDNN, RawNet3, the Conformer and TitaNet share on the host: the refusal texts and the
+// api_ragged.hip — what the ragged calls of ECAPA-TDNN, RawNet2 'conv', RawNet3, the Conformer and TitaNet share on the host: the refusal texts and the
 // rules of the mel models, the table ring (RagTables), the one table layout, and the driver that turns a call's arrays into a RagPack
 // (allocation, the row loop, the input, the upload).  A model's api_<model>.hip keeps its RagRule, its own rules and its forward.
 #include <algorithm>
@@ -118,7 +118,7 @@ static int rag_mel_input(svhip_handle* h, RagTables& rag, const float* in, bool 
 // ---- a call's arrays -> a pack ------------------------------------------------------------------------------------------
 namespace {
 
-struct RagView { int64_t* off; int32_t* len; int* row0[3]; };      // the typed tables of a block, on the device or in a pinned slot
+struct RagView { int64_t* off; int32_t* len; int* row0[RAG_LEVELS]; };      // the typed tables of a block, on the device or in a pinned slot
 
 size_t rag_tab_bytes(size_t B, int levels) { return B * 8 + B * 4 + (size_t)levels * (B + 1) * 4; }
 
@@ -130,7 +130,7 @@ RagView rag_view(char* base, size_t B, int levels) {
 
 }  // namespace
 
-int rag_pack(svhip_handle* h, RagTables& rag, const RagRule& rule, const size_t utt_cap[3], const float* in, bool in_host, bool is_wave,
+int rag_pack(svhip_handle* h, RagTables& rag, const RagRule& rule, const size_t utt_cap[RAG_LEVELS], const float* in, bool in_host, bool is_wave,
              const int64_t* in_off, const int32_t* lengths, int n, RagPack& pk) {
     const svhip_config& c = h->cfg;
     const size_t B = c.max_batch, bytes = rag_tab_bytes(B, rule.levels);
@@ -138,7 +138,8 @@ int rag_pack(svhip_handle* h, RagTables& rag, const RagRule& rule, const size_t 
     if (!rag.dev) {
         for (int l = 0; l < rule.levels; ++l)
             if (utt_cap[l] && !rag.utt[l] && (rc = dev_alloc(h, &rag.utt[l], utt_cap[l]))) return rc;
-        // (RawNet3: a pack of n <= B utterances within B T0 frames holds at most 10 B T0 + 250 n <= B (samples + 9) samples)
+        // (RawNet3: a pack of n <= B utterances within B T0 frames holds at most 10 B T0 + 250 n <= B (samples + 9) samples;
+        //  RawNet2 'conv': at most 3 sum T1_u + 2 n <= B (samples + 2) samples, since L_u <= 3 T1_u + 2 and sum T1_u <= B floor(samples / 3))
         if ((rc = rag.alloc(h, bytes, B * ((size_t)c.samples + (rule.mel ? c.hop_length : 16))))) return rc;
     }
     char* slot = nullptr;
@@ -148,7 +149,7 @@ int rag_pack(svhip_handle* h, RagTables& rag, const RagRule& rule, const size_t 
     pk.n = n; pk.levels = rule.levels;
     pk.off = dev.off; pk.len = dev.len;
     for (int u = 0; u < n; ++u) {
-        int T[3] = {};
+        int T[RAG_LEVELS] = {};
         rule.frames(c, lengths[u], is_wave, T);
         for (int l = 0; l < rule.levels; ++l) {
             Seg& g = pk.lv[l];

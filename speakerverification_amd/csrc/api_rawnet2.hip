@@ -1,5 +1,5 @@
 // api_rawnet2.hip — RawNet2 in libsvhip (the 'sinc' and 'conv' front-ends, the 'asp' and 'gru' aggregations): its create rules, weight
-// names and packing, workspace, forward and stages.
+// names and packing, workspace, forward and stages; for the 'conv' model also the forward over a ragged pack (rawnet2_rag_walk, at the end).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -59,9 +59,16 @@ struct RawNet2State : ModelState {
     // option rn_keep: copies of what the forward stored, by stage name.  A buffer holds max_batch utterances (allocated when its stage is
     // first kept), so the slices of a forward on several lanes fill it side by side; a stage counts as kept when every utterance of the
     // last forward (`epoch`) wrote it.
-    struct Kept { void* buf = nullptr; size_t rows = 0, cols = 0; bool f32 = false; uint64_t epoch = 0; int utts = 0; };
+    // (after a ragged forward `rows` counts the packed rows of all its utterances: `packed`)
+    struct Kept { void* buf = nullptr; size_t rows = 0, cols = 0; bool f32 = false; uint64_t epoch = 0; int utts = 0; bool packed = false; size_t cap = 0; };
     std::map<std::string, Kept> kept;
     uint64_t epoch = 0;
+    // ragged packs of the 'conv' model: all allocated by the first ragged call, each under its own null check
+    RagTables rag;                     // the tables of a call (seven levels) and the staging buffer of host waveforms
+    int* rag_slice0 = nullptr;         // (RAG_LEVELS, max_batch + 1): the first slice of every utterance at every level (rn_rag_slices)
+    float* rag_part = nullptr;         // the slice sums of one block tail, (slices of its out level, channels)
+    float* rag_gate = nullptr;         // (8 blocks, max_batch, 512): every block's gates stay until the next forward (stages)
+    float* rag_logits = nullptr;       // (last-level rows, 512) fp32
 };
 
 RawNet2State& S(svhip_handle* h) { return static_cast<RawNet2State&>(*h->model); }
@@ -387,7 +394,8 @@ int rawnet2_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {
         if (it == s.kept.end() || it->second.epoch != s.epoch || it->second.utts != B)
             SV_FAIL(h, SVHIP_ERR_STATE, "stage %s: %s", n.c_str(), h->opt.rn_keep ? "the route of the last forward never stored it" : "option rn_keep was not set");
         const RawNet2State::Kept& k = it->second;
-        v.src = k.buf; v.rows = (size_t)B * k.rows; v.cols = v.ld = k.cols; v.f32 = k.f32;
+        // (a pack's rows are those of the stage's level, counted when it was kept; a fixed-length forward has `rows` per utterance)
+        v.src = k.buf; v.rows = k.packed ? k.rows : (size_t)B * k.rows; v.cols = v.ld = k.cols; v.f32 = k.f32;
     }
     else return unknown_stage(h, n);
     return SVHIP_OK;
@@ -455,11 +463,11 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
         const bool f32 = kind != KEEP_DT || !bf;
         const size_t es = f32 ? 4 : 2;
         RawNet2State::Kept& k = s.kept[name];
-        if (!k.buf || k.rows != rows || k.cols != (size_t)cols || k.f32 != f32) {
+        if (!k.buf || k.packed || k.rows != rows || k.cols != (size_t)cols || k.f32 != f32) {
             void* q = nullptr;
             SV_HIP(h, hipMalloc(&q, (size_t)c.max_batch * rows * cols * es));
             h->allocs.push_back(q);
-            k.buf = q; k.rows = rows; k.cols = cols; k.f32 = f32; k.epoch = 0;
+            k.buf = q; k.rows = rows; k.cols = cols; k.f32 = f32; k.epoch = 0; k.packed = false; k.cap = (size_t)c.max_batch * rows * cols * es;
         }
         if (k.epoch != s.epoch) { k.epoch = s.epoch; k.utts = 0; }
         void* dst = static_cast<char*>(k.buf) + (size_t)b0 * rows * cols * es;
@@ -715,6 +723,185 @@ int rawnet2_forward(svhip_handle* h, const float* d_wav, int B) {
     const int rc = forward_lanes(h, rawnet2_forward_part, d_wav, B, lanes, ((B + lanes - 1) / lanes + 3) & ~3);
     if (lanes > 1) S(h).gru_in = nullptr;          // the slices' GRU inputs are not one (B T, 512) block
     return rc;
+}
+
+// ---- ragged packs of the 'conv' model --------------------------------------------------------------------------------------
+// RawNet2's rules for a pack of waveforms (RaggedCheckFn; include/svhip.h), on the host alone
+int rawnet2_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool, std::string& err) {
+    const int min_samples = 3 * RN_MIN_FRAMES;
+    if (c.max_batch <= 0 || c.samples < min_samples) return refuse(err, SVHIP_ERR_INVALID, "bad max_batch / samples (RawNet2 'conv' needs samples >= %d)", min_samples);
+    const int64_t cap = (int64_t)c.max_batch * (c.samples / 3);
+    int64_t rows = 0;
+    for (int i = 0; i < n; ++i) {
+        if (lengths[i] < min_samples)
+            return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %d samples, fewer than RawNet2's minimum of %d (729 front-end frames: one frame reaches the aggregation)",
+                          i, lengths[i], min_samples);
+        if (int rc = rag_rows_fit(err, i, rows += lengths[i] / 3, cap, "T1")) return rc;
+    }
+    return SVHIP_OK;
+}
+
+// seven frame levels: the front-end's T1 = floor(L / 3) frames, then what each of the six max_pool1d(3) stages leaves
+static void rn_rag_frames(const svhip_config&, int64_t len, bool, int T[RAG_LEVELS]) {
+    T[0] = (int)(len / 3);
+    for (int l = 1; l < RAG_LEVELS; ++l) T[l] = T[l - 1] / 3;
+}
+static const RagRule kRawnet2Rag = {7, rn_rag_frames, false};
+
+// RawNet2.forward over a pack: n utterances (utterance u: pk.len[u] samples at d_wav + pk.off[u]) as packed rows at seven frame levels,
+// on the handle's stream.  A walk of its own, not a `pk` threaded through rawnet2_forward_part: the fixed forward is a tree of routes
+// (the fused rn_block128 chain, rn_step, the conv2 + shortcut fold, three tail forms, lanes, the developer options that pick among
+// them), chosen by the batch size and the device, and a pack takes none of them — every GEMM is the generic kernel
+// (launch_gemm_ragged), every tail the segment-table form (rn_ragged.hip), so that nothing depends on n, on the neighbours or on
+// num_cu.  A pk pointer would double every branch of that tree for a path that shares only the layer order with it.  Of the
+// developer options it reads rn_keep and layer_labels alone.
+// Buffers: the six activation buffers of rawnet2_alloc, max_batch * T1 * 128 elements each, hold every tensor of every level: level l
+// has sum_u floor(T_u / 3^l) <= floor(M0 / 3^l) rows (M0 <= max_batch * T1 by the capacity rule) of at most 128 * 2^ceil(l / 2)
+// channels, so the rows shrink 3 x where the channels at most double.  What is sized per utterance in rawnet2_alloc does not fit a
+// pack (its last level can have more rows than max_batch * tf, its slices are not capped at 16): rawnet2_rag_alloc.
+static int rawnet2_rag_alloc(svhip_handle* h) {
+    auto& s = S(h);
+    const size_t B = h->cfg.max_batch, M0 = B * (size_t)s.T1;
+    int rc;
+    if (!s.rag_slice0 && (rc = dev_alloc(h, &s.rag_slice0, (size_t)RAG_LEVELS * (B + 1)))) return rc;
+    if (!s.rag_part) {          // a tail's slices: level l has at most M0 / 3^l / RN_RAG_SLICE + max_batch of them, of the block's channels
+        size_t need = 0, rows = M0;
+        for (int bi = 0; bi < 8; ++bi) {
+            const RnBlock& K = s.blocks[bi];
+            if (K.downsample) rows /= 3;
+            need = std::max(need, (rows / RN_RAG_SLICE + B + 1) * (size_t)K.cout);
+        }
+        if ((rc = dev_alloc(h, &s.rag_part, need))) return rc;
+    }
+    if (!s.rag_gate && (rc = dev_alloc(h, &s.rag_gate, 8 * B * 512))) return rc;
+    if (!s.rag_logits && (rc = dev_alloc(h, &s.rag_logits, (M0 / 729 + 1) * 512))) return rc;
+    return SVHIP_OK;
+}
+
+static int rawnet2_rag_walk(svhip_handle* h, const RagPack& pk) {
+    auto& s = S(h);
+    const svhip_config& c = h->cfg;
+    const int n = pk.n, dt = h->dt;
+    const size_t B = c.max_batch, M0cap = B * (size_t)s.T1;
+    h->cur = h->stream;
+    hipStream_t st = h->cur;
+    int rc;
+    ++s.epoch;
+    // option rn_keep: a copy of a packed tensor the forward has just stored (level `lvl` rows; lvl < 0: one row per utterance), on the
+    // forward's stream; nothing else reads the option
+    const bool keeping = h->opt.rn_keep != 0;
+    auto keep = [&](const std::string& name, const void* src, int lvl, int cols, bool f32) -> int {
+        if (!keeping) return SVHIP_OK;
+        const size_t es = f32 || !h->bf16 ? 4 : 2;
+        size_t cap_rows = lvl < 0 ? B : M0cap, rows = lvl < 0 ? (size_t)n : (size_t)pk.lv[lvl].M;
+        for (int l = 0; l < lvl; ++l) cap_rows /= 3;
+        RawNet2State::Kept& k = s.kept[name];
+        if (!k.buf || k.cap < cap_rows * cols * es) {
+            void* q = nullptr;
+            SV_HIP(h, hipMalloc(&q, cap_rows * cols * es));
+            h->allocs.push_back(q);
+            k.buf = q; k.cap = cap_rows * cols * es;
+        }
+        k.rows = rows; k.cols = cols; k.f32 = es == 4; k.packed = true; k.epoch = s.epoch; k.utts = n;
+        SV_HIP(h, hipMemcpyAsync(k.buf, src, rows * cols * es, hipMemcpyDeviceToDevice, st));
+        return SVHIP_OK;
+    };
+    auto blk = [](int i, const char* what) { return "rn_b" + std::to_string(i) + "_" + what; };
+    // a GEMM over the rows of level g on the generic kernel (pointwise layers need no table)
+    auto gemm = [&](const ConvLayer& K, GemmParams p, const Seg& g) {
+        p.rag_utt = g.utt; p.rag_row0 = g.row0;
+        char label[96];
+        const char* kl = K.taps > 1 ? "gemm_conv" : "gemm_pw";
+        if (h->opt.layer_labels) snprintf(label, sizeof(label), "%s M%d N%d K%d", kl, p.M, K.N, K.K);
+        else snprintf(label, sizeof(label), "%s", kl);
+        return run(h, label, (double)p.M * K.flops_per_row, [&]() { return launch_gemm_ragged(p, h->bf16, st); });
+    };
+    for (int l = 0; l < 6; ++l)          // the levels a k = 3 convolution reads
+        if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(pk.lv[l].row0, n, pk.lv[l].maxT, pk.lv[l].utt, st); }))) return rc;
+    const int ld = (int)(pk.lv[1].row0 - pk.lv[0].row0);          // the levels' row0 tables lie max_batch + 1 ints apart (rag_pack)
+    if ((rc = run(h, "rn_rag_slices", 0, [&]() { return launch_rn_rag_slices(pk.lv[0].row0, ld, RAG_LEVELS, n, s.rag_slice0, st); }))) return rc;
+
+    void *x = s.buf[0], *pre = s.buf[1], *hb = s.buf[2], *o = s.buf[3], *sc = s.buf[4], *xn = s.buf[5];
+    // front-end: x = conv1(wav) and block 0's pre-activation lrelu(bn1(x))                  RawNet2_custom.py:166-169, RawNet_baseline.py:222
+    if ((rc = run(h, "rn_rag_front", 2.0 * 128.0 * 3.0 * pk.lv[0].M, [&]() {
+             return launch_rn_rag_front(pk.in, pk.off, pk.len, pk.lv[0].row0, n, pk.lv[0].maxT, s.cw, s.blocks[0].bn1_scale, s.blocks[0].bn1_shift, 0.3f,
+                                        x, pre, dt, st);
+         }))) return rc;
+    if ((rc = keep("rn_front", x, 0, 128, false)) || (rc = keep(blk(0, "pre"), pre, 0, 128, false))) return rc;
+    int li = 0;
+    for (int bi = 0; bi < 8; ++bi) {
+        const RnBlock& K = s.blocks[bi];
+        const Seg& g = pk.lv[li];
+        const int M = g.M;
+        const void* resid = x;                                                    // identity shortcut takes the pre-BN x (:223)
+        if (K.has_shortcut) {
+            if ((rc = gemm(K.shortcut, conv_params(h, K.shortcut, pre, K.cin, sc, K.cout, M, 1), g))) return rc;
+            resid = sc;
+        }
+        GemmParams p1 = conv_params(h, K.conv1, pre, K.cin, hb, K.cout, M, 1);      // conv1 -> bn2 -> lrelu (epilogue)       :224-225
+        p1.act2 = ACT_LRELU03; p1.pad_mode = PAD_ZERO;
+        if ((rc = gemm(K.conv1, p1, g))) return rc;
+        GemmParams p2 = conv_params(h, K.conv2, hb, K.cout, o, K.cout, M, 1);       // conv2 + shortcut                       :226
+        p2.pad_mode = PAD_ZERO; p2.R = resid; p2.ldr = K.cout;
+        if ((rc = gemm(K.conv2, p2, g))) return rc;
+        if ((rc = keep(blk(bi, "o"), o, li, K.cout, false))) return rc;
+        // the tail: [max_pool1d(3)] -> AFMS -> the next consumer's lrelu(bn(.)), over the slices of the out level       :228-229, :62-68
+        const int lo = K.downsample ? li + 1 : li;
+        const Seg& go = pk.lv[lo];
+        int nslices = 0;
+        for (int u = 0; u < n; ++u) nslices += (go.hrow0[u + 1] - go.hrow0[u] + RN_RAG_SLICE - 1) / RN_RAG_SLICE;
+        const int* sl0 = s.rag_slice0 + (size_t)lo * ld;
+        float* gate = s.rag_gate + (size_t)bi * B * 512;
+        const float* nsc = bi < 7 ? s.blocks[bi + 1].bn1_scale : s.agg_scale;
+        const float* nsh = bi < 7 ? s.blocks[bi + 1].bn1_shift : s.agg_shift;
+        const bool x_dead = bi == 7 || s.blocks[bi + 1].has_shortcut;              // x is read only as an identity shortcut
+        // (layer_labels: one profile row per block, "<kernel> M<in rows> C<channels>")
+        auto tl = [&](const char* k) {
+            std::string l = k;
+            if (h->opt.layer_labels) l += " M" + std::to_string(M) + " C" + std::to_string(K.cout);
+            return l;
+        };
+        if ((rc = run(h, tl("rn_rag_tail_part").c_str(), 0, [&]() { return launch_rn_rag_tail_part(o, dt, K.downsample, g.row0, go.row0, sl0, n, nslices, K.cout, s.rag_part, st); })))
+            return rc;
+        if ((rc = run(h, tl("rn_rag_gate").c_str(), 2.0 * n * K.cout * K.cout, [&]() { return launch_rn_rag_gate(s.rag_part, go.row0, sl0, n, K.cout, K.afms_fcT, K.afms_fc.bias, gate, st); })))
+            return rc;
+        if ((rc = run(h, tl("rn_rag_tail_apply").c_str(), 0, [&]() {
+                 return launch_rn_rag_tail_apply(o, dt, K.downsample, g.row0, go.row0, sl0, n, nslices, K.cout, K.alpha, gate, nsc, nsh, 0.3f,
+                                                 x_dead ? nullptr : xn, pre, st);
+             }))) return rc;
+        std::swap(x, xn);
+        li = lo;
+        if ((rc = keep(blk(bi, "gate"), gate, -1, K.cout, true))) return rc;
+        if ((rc = keep(bi < 7 ? blk(bi + 1, "pre") : std::string("rn_agg_in"), pre, li, K.cout, false))) return rc;
+        if (!x_dead && (rc = keep(blk(bi + 1, "x"), x, li, K.cout, false))) return rc;
+    }
+    // aggregation: attentive statistics pooling over each utterance's own frames of the last level         RawNet2_custom.py:215-224
+    const Seg& g6 = pk.lv[6];
+    GemmParams pa = conv_params(h, s.att0, pre, 512, hb, 128, g6.M, 1);
+    pa.act1 = ACT_LRELU001;
+    if ((rc = gemm(s.att0, pa, g6))) return rc;
+    GemmParams pl = conv_params(h, s.att3, hb, 128, s.rag_logits, 512, g6.M, 1);
+    pl.out_f32 = 1;
+    if ((rc = gemm(s.att3, pl, g6))) return rc;
+    if ((rc = keep("rn_logits", s.rag_logits, 6, 512, true))) return rc;
+    if ((rc = run(h, "rn_rag_attn_pool", 0, [&]() { return launch_rn_rag_attn_pool(s.rag_logits, pre, dt, g6.row0, n, 512, s.pooled, st); }))) return rc;
+    return run(h, "rn_fc", 2.0 * n * s.fc.N * s.fc.K, [&]() {
+        return launch_rag_linear(s.pooled, 1024, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, n, c.embed_dim, 1024, ACT_NONE, st);
+    });
+}
+
+int rawnet2_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool, const int64_t* in_off, const int32_t* lengths, int n) {
+    auto& s = S(h);
+    // utt tables for the levels a k = 3 convolution reads (0 - 5); nothing reads the last level's
+    size_t utt_cap[RAG_LEVELS] = {};
+    size_t rows = (size_t)h->cfg.max_batch * s.T1;
+    for (int l = 0; l < 6; ++l, rows /= 3) utt_cap[l] = rows + 1;
+    RagPack pk;
+    int rc;
+    if ((rc = rawnet2_rag_alloc(h)) || (rc = rag_pack(h, s.rag, kRawnet2Rag, utt_cap, in, in_host, true, in_off, lengths, n, pk)) ||
+        (rc = rawnet2_rag_walk(h, pk))) return rc;
+    set_rag_rows(h, pk);
+    return SVHIP_OK;
 }
 
 }  // namespace svhip

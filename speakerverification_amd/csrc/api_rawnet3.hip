@@ -403,7 +403,7 @@ int rawnet3_ragged_check(const svhip_config& c, const int32_t* lengths, int n, b
 }
 
 // three frame levels: the front-end's frames, then what layer1's and layer2's pools leave
-static void rn3_rag_frames(const svhip_config&, int64_t len, bool, int T[3]) {
+static void rn3_rag_frames(const svhip_config&, int64_t len, bool, int T[RAG_LEVELS]) {
     T[0] = rn3_frames((int)len);
     T[1] = T[0] / 5;
     T[2] = T[1] / 3;
@@ -412,7 +412,7 @@ static const RagRule kRawnet3Rag = {3, rn3_rag_frames, false};
 
 int rawnet3_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool, const int64_t* in_off, const int32_t* lengths, int n) {
     auto& s = S(h);
-    const size_t M0 = (size_t)h->cfg.max_batch * s.T0, utt_cap[3] = {M0, M0 / 5 + 1, M0 / 15 + 1};
+    const size_t M0 = (size_t)h->cfg.max_batch * s.T0, utt_cap[RAG_LEVELS] = {M0, M0 / 5 + 1, M0 / 15 + 1};
     RagPack pk;
     int rc;
     if ((rc = rag_pack(h, s.rag, kRawnet3Rag, utt_cap, in, in_host, true, in_off, lengths, n, pk)) || (rc = rawnet3_walk(h, pk.in, n, &pk))) return rc;

@@ -345,11 +345,11 @@ int titanet_ragged_check(const svhip_config& c, const int32_t* lengths, int n, b
 }
 
 // one frame level (the network has no subsampling): the mel frames
-static void titanet_rag_frames(const svhip_config& c, int64_t len, bool is_wave, int T[3]) { T[0] = (int)mel_frames(c, len, is_wave); }
+static void titanet_rag_frames(const svhip_config& c, int64_t len, bool is_wave, int T[RAG_LEVELS]) { T[0] = (int)mel_frames(c, len, is_wave); }
 static const RagRule kTitanetRag = {1, titanet_rag_frames, true};
 
 int titanet_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n) {
-    const size_t utt_cap[3] = {(size_t)h->cfg.max_batch * h->T};
+    const size_t utt_cap[RAG_LEVELS] = {(size_t)h->cfg.max_batch * h->T};
     RagPack pk;
     int rc;
     if ((rc = rag_pack(h, S(h).rag, kTitanetRag, utt_cap, in, in_host, is_wave, in_off, lengths, n, pk)) || (rc = titanet_walk(h, pk.in, n, &pk))) return rc;

@@ -397,8 +397,16 @@ hipError_t launch_t(const GemmParams& p, hipStream_t stream) {
 // the ragged forms ECAPA's and RawNet3's forwards need: the k = 5 first convolution (GELU), the Res2Net steps (ReLU, with and without the
 // running sum A2; reflect or zero padding: pad_mode is a runtime field) and the attention layer with its bias per utterance (pointwise;
 // ECAPA's asp.tdnn: ReLU -> BN -> tanh, RawNet3's attention.0 -> attention.2: ReLU -> BN)
+// RawNet2's: the k = 3 convolutions of a block (zero padding; conv1 with bn2 -> LeakyReLU 0.3 as its epilogue, conv2 plain with the
+// residual operand R, a runtime field) — the only ragged forms an fp16 handle has
 template <typename T>
 hipError_t launch_rag_t(const GemmParams& p, hipStream_t stream) {
+    if (p.taps > 1 && !p.A2 && !p.seg_off && p.act1 == ACT_NONE) {
+        if (p.act2 == ACT_LRELU03) return launch_inst_x<T, true, false, EPI_BN_LRELU03, false, false, true>(p, stream);
+        if (p.act2 == ACT_NONE) return launch_inst_x<T, true, false, EPI_NONE, false, false, true>(p, stream);
+    }
+    if constexpr (std::is_same<T, f16_t>::value) return hipErrorInvalidValue;
+    else {
     if (p.seg_off) {          // Conformer's subsampling conv over a pack: launch_t's segmented instance with the per-utterance offset
         if (p.act1 != ACT_RELU || p.act2 != ACT_NONE || p.taps != 1 || p.A2 || p.bias_utt) return hipErrorInvalidValue;
         return launch_inst_x<T, false, false, EPI_RELU, false, true, true>(p, stream);
@@ -413,6 +421,7 @@ hipError_t launch_rag_t(const GemmParams& p, hipStream_t stream) {
     if (p.bias_utt && p.act1 == ACT_RELU && p.act2 == ACT_TANH && !p.A2) return launch_inst_x<T, false, false, EPI_RELU_TANH, false, false, true>(p, stream);
     if (p.bias_utt && p.act1 == ACT_RELU && p.act2 == ACT_NONE && !p.A2) return launch_inst_x<T, false, false, EPI_RELU, false, false, true>(p, stream);
     return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace
@@ -422,7 +431,7 @@ hipError_t launch_gemm_ragged(const GemmParams& p, bool bf16, hipStream_t stream
     const int bk = gemm_bk(bf16);
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.Kp % bk != 0 || p.Kp < p.K || p.Wrows < p.N) return hipErrorInvalidValue;
     if (p.lda % epc != 0 || (p.A2 && p.lda2 % epc != 0)) return hipErrorInvalidValue;
-    if (p.x3 || p.f16 || p.A3 || p.colsum || p.y_s32 || p.side_c) return hipErrorInvalidValue;
+    if (p.x3 || (p.f16 && !bf16) || p.A3 || p.colsum || p.y_s32 || p.side_c) return hipErrorInvalidValue;
     if (p.taps > 1) {
         if (p.cin % epc != 0 || p.taps * p.cin != p.K) return hipErrorInvalidValue;
     } else if (p.K % epc != 0) {
@@ -432,10 +441,12 @@ hipError_t launch_gemm_ragged(const GemmParams& p, bool bf16, hipStream_t stream
                       p.seg_stride % epc != 0)) return hipErrorInvalidValue;
     if (p.taps > 1 || p.bias_utt || p.seg_off) {          // (what needs the segment table; the caller has checked (taps / 2) dil < T_u for every utterance)
         if (!p.rag_utt || !p.rag_row0) return hipErrorInvalidValue;
+        if (bf16 && p.f16) return launch_rag_t<f16_t>(p, stream);
         return bf16 ? launch_rag_t<bf16_t>(p, stream) : launch_rag_t<float>(p, stream);
     }
     GemmParams q = p;                        // plain pointwise layers see M rows and nothing else
     q.rag_utt = q.rag_row0 = nullptr;
+    if (bf16 && p.f16) return launch_t<f16_t>(q, stream);
     return bf16 ? launch_t<bf16_t>(q, stream) : launch_t<float>(q, stream);
 }
 

@@ -53,6 +53,9 @@ struct ModelState { virtual ~ModelState() = default; };
 // an activation buffer whose `bytes` of payload are followed by a 256-byte zero tail (api_gemm.hip's zero_page_for)
 struct TailedBuf { const char* base; size_t bytes; };
 
+// the most frame levels a ragged pack has (RawNet2: the front-end's frames and what each of its six max_pool1d(3) stages leaves)
+constexpr int RAG_LEVELS = 7;
+
 struct ProfEntry { std::string name; double ms = 0; int64_t launches = 0; double flops = 0; };
 struct PendingEvent { hipEvent_t e0, e1; int entry; };
 
@@ -128,7 +131,7 @@ struct svhip_handle {
     int lastB = 0;
     // the last forward when it was a ragged one (svhip_get_stage): the packed rows of each of its rag_levels frame levels (RagPack), the
     // input's first.  rag_levels = 0: a fixed-length forward
-    int64_t rag_rows[3] = {};
+    int64_t rag_rows[svhip::RAG_LEVELS] = {};
     int rag_levels = 0;
     // shared by several models: each is allocated by the alloc / finalize hook of the models named, and null on the others' handles
     void* X_in = nullptr;         // (M, n_mels): the network input (ECAPA, TitaNet, Conformer; svhip_get_stage "input")
@@ -310,7 +313,7 @@ struct RagSlot { char* host = nullptr; hipEvent_t done = nullptr; bool busy = fa
 struct RagTables {
     char* dev = nullptr;
     float* wav = nullptr;
-    int* utt[3] = {};
+    int* utt[RAG_LEVELS] = {};
     RagSlot slot[4], *cur = nullptr;
     int next = 0;
     int alloc(svhip_handle* h, size_t table_bytes, size_t wav_floats);      // once per handle (later calls do nothing)
@@ -324,15 +327,15 @@ struct RagTables {
 struct Seg { const int* row0 = nullptr; int* utt = nullptr; const int* hrow0 = nullptr; int M = 0, maxT = 0; };
 // A pack as a forward sees it: n utterances at `levels` frame levels, lv[0] the input's.  in + off[u] (device tables off / len) is
 // utterance u's first element — of its (n_mels, T_u) block of mel power, or of its len[u] samples for a waveform model
-struct RagPack { int n = 0, levels = 0; Seg lv[3]; const int64_t* off = nullptr; const int32_t* len = nullptr; const float* in = nullptr; };
+struct RagPack { int n = 0, levels = 0; Seg lv[RAG_LEVELS]; const int64_t* off = nullptr; const int32_t* len = nullptr; const float* in = nullptr; };
 // How a model packs: the frames of one utterance at each of its levels, and whether its input is the mel power (rag_mel_input; staging
 // slack hop_length floats per utterance) or the waveform itself (staged as it is, off / len for the front-end kernel; slack 16 floats)
-struct RagRule { int levels; void (*frames)(const svhip_config& c, int64_t len, bool is_wave, int T[3]); bool mel; };
+struct RagRule { int levels; void (*frames)(const svhip_config& c, int64_t len, bool is_wave, int T[RAG_LEVELS]); bool mel; };
 // The host side of a ragged forward, after the model's check has passed: allocates on the handle's first ragged call (utt_cap: the
 // rows of each level's utt table; 0: nothing reads that level's), takes a table slot, lays out the pack (all four models: offsets
 // max_batch x int64 | lengths max_batch x int32 | one row0 of max_batch + 1 ints per level), stages the input, enqueues the table
 // upload and fills pk for the model's forward
-int rag_pack(svhip_handle* h, RagTables& rag, const RagRule& rule, const size_t utt_cap[3], const float* in, bool in_host, bool is_wave,
+int rag_pack(svhip_handle* h, RagTables& rag, const RagRule& rule, const size_t utt_cap[RAG_LEVELS], const float* in, bool in_host, bool is_wave,
              const int64_t* in_off, const int32_t* lengths, int n, RagPack& pk);
 // that forward has run: what svhip_get_stage needs of it
 inline void set_rag_rows(svhip_handle* h, const RagPack& pk) {
@@ -367,7 +370,7 @@ int conv_gemm(svhip_handle* h, const ConvLayer& L, const GemmParams& p, const vo
 using ForwardPart = int (*)(svhip_handle* h, const float* in, int b0, int B);
 int forward_lanes(svhip_handle* h, ForwardPart part, const float* in, int B, int lanes, int per);
 
-// api_ecapa.hip, api_rawnet2.hip (the three RawNet2 models), api_rawnet3.hip, api_titanet.hip, api_conformer.hip, api_resnetse.hip: each
+// api_ecapa.hip, api_rawnet2.hip (the three RawNet2 models; ragged packs of the 'conv' one), api_rawnet3.hip, api_titanet.hip, api_conformer.hip, api_resnetse.hip: each
 // model's functions (its state struct stays inside its file)
 CheckFn ecapa_check, rawnet2_check, rawnet3_check, titanet_check, conformer_check, resnetse_check;
 SpecFn ecapa_spec, rawnet2_spec, rawnet3_spec, titanet_spec, conformer_spec, resnetse_spec;

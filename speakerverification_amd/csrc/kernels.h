@@ -168,7 +168,7 @@ hipError_t launch_in_scale(const float* X, int64_t n, uint32_t* part256, float* 
 hipError_t launch_unsplit_s32(const void* src, int lds32, float* dst, int ld, int64_t M, int K, hipStream_t stream);   // v = hi + lo
 // row groups per 256-row tile in the column-sum partials the routed kernel writes (8: pw2, 2: pw3)
 int gemm_colsum_groups(const GemmParams& p, bool bf16);
-// a GEMM of a ragged batch (fp32 / bf16): ALWAYS the generic kernel, whatever M is — gemm_route picks its kernel by the size of the
+// a GEMM of a ragged batch (fp32 / bf16; fp16 with p.f16: RawNet2's instances): ALWAYS the generic kernel, whatever M is — gemm_route picks its kernel by the size of the
 // problem, and the kernels add a row's K products in different orders, so a routed GEMM would make an utterance's values depend on
 // what it is packed with.  With rag_utt / rag_row0 the conv gather and bias_utt follow the segment table (GemmParams).
 hipError_t launch_gemm_ragged(const GemmParams& p, bool bf16, hipStream_t stream);
@@ -411,6 +411,30 @@ hipError_t launch_rn_block128(const RnBlock128Params& p, int num_cu, hipStream_t
 hipError_t launch_rn_afms_gate(const float* part, int nparts, int B, int C, int Tn, const float* WT, const float* bias, float* s,
                                hipStream_t stream);
 hipError_t launch_rn_attn_pool(const float* logits, const void* x, int dt, int B, int T, int C, float* out, hipStream_t stream);
+// RawNet2 'conv' over a ragged pack (rn_ragged.hip): n utterances packed back to back at seven frame levels (T1_u = len_u / 3, then / 3
+// per pooled block), each level described by its row0 table (n + 1 device ints).  No grid, slice length or kernel choice depends on n,
+// on the neighbours or on the device: an utterance's values are bit for bit the same in every pack.
+//   front     utterance u = len[u] samples at wav + off[u] (device tables) -> x rows row0[u] .. (rn_conv3_front's value) and, from the
+//             value as stored, pre = lrelu(bn_scale x + bn_shift) (rn_bn_act's value); maxT1 >= every T1_u
+//   slices    slice0[l * ld + u] = the first slice of utterance u at level l when every utterance is cut into slices of
+//             RN_RAG_SLICE frames (slice0[l * ld + n]: the level's slice count); row0 + l * ld is level l's table
+//   tail      rn_tail_part / rn_afms_gate / rn_tail_apply over the slices of the OUT level (nslices of them, counted on the host):
+//             part (nslices, C) = the column sums of each slice of [max_pool1d(3) of] the utterance's in-level rows; gate (n, C) =
+//             sigmoid(fc(sum of the utterance's slice sums in slice order / Tn_u)); apply forms the pooled value again and writes
+//             y = (v + alpha) gate (null: nothing reads it) and pre = lrelu(nscale y + nshift) from y in fp32, before its rounding
+//   attn_pool softmax over the utterance's own frames of the fp32 logits, weighted mean and sqrt(max(sum w (x - m)^2, 1e-5)) -> out (n, 2 C)
+constexpr int RN_RAG_SLICE = 48;
+hipError_t launch_rn_rag_front(const float* wav, const int64_t* off, const int32_t* len, const int* row0, int n, int maxT1, const float* cw,
+                               const float* bn_scale, const float* bn_shift, float slope, void* x, void* pre, int dt, hipStream_t stream);
+hipError_t launch_rn_rag_slices(const int* row0, int ld, int levels, int n, int* slice0, hipStream_t stream);
+hipError_t launch_rn_rag_tail_part(const void* x, int dt, bool pool, const int* row0_in, const int* row0_out, const int* slice0, int n, int nslices,
+                                   int C, float* part, hipStream_t stream);
+hipError_t launch_rn_rag_gate(const float* part, const int* row0_out, const int* slice0, int n, int C, const float* WT, const float* bias, float* gate,
+                              hipStream_t stream);
+hipError_t launch_rn_rag_tail_apply(const void* x, int dt, bool pool, const int* row0_in, const int* row0_out, const int* slice0, int n, int nslices,
+                                    int C, const float* alpha, const float* gate, const float* nscale, const float* nshift, float slope, void* y,
+                                    void* pre, hipStream_t stream);
+hipError_t launch_rn_rag_attn_pool(const float* logits, const void* x, int dt, const int* row0, int n, int C, float* out, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // RawNet2's GRU aggregation (gru.hip): one launch per time step of h' = GRU(gi_t, h), hidden size 1024

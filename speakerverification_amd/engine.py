@@ -90,6 +90,8 @@ _RAGGED = {
     "ecapa": _RaggedCalls(("svhip_embed_wave_ragged",), ("svhip_embed_features_ragged",), "svhip_ragged_check", True, _MEL_FRAMES),
     "rawnet3": _RaggedCalls(("svhip_rawnet3_embed_ragged",), None, "svhip_rawnet3_ragged_check", False,
                             lambda n, hop: (n - 251) // 10 + 1),       # the frames after its sinc filterbank (251 taps, stride 10)
+    "rawnet2_conv": _RaggedCalls(("svhip_rawnet2_embed_ragged",), None, "svhip_rawnet2_ragged_check", False,
+                                 lambda n, hop: n // 3),                # the frames after its conv front-end (kernel 3, stride 3)
     "conformer": _RaggedCalls(("svhip_conformer_embed_ragged", 1), ("svhip_conformer_embed_ragged", 0), "svhip_conformer_ragged_check", True,
                               _MEL_FRAMES),
     "titanet": _RaggedCalls(("svhip_titanet_embed_ragged", 1), ("svhip_titanet_embed_ragged", 0), "svhip_titanet_ragged_check", True, _MEL_FRAMES),

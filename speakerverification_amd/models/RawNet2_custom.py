@@ -11,12 +11,14 @@ State-dict keys are the reference's: 147 tensors for 'sinc' (the band-pass filte
 (``conv1.weight`` / ``conv1.bias``), 144 for 'sinc' + 'gru' (``bn_before_gru``, ``gru.*``, ``fc_after_gru``;
 ``fc`` is built and never used, as in the reference).  The sinc form's LayerNorm(nb_samp) fixes the input length; the conv
 form takes any length L >= 2187 (one library handle per length, the configured crop length with the
-full batch workspace).
+full batch workspace) and, alone of the three, offers ``embed_ragged``: utterances of different lengths in shared calls of the
+primary handle (whole-file evaluation; ``RawNet2Conv``).
 """
 from __future__ import annotations
 
 from .. import synth
-from ._base import HipModule
+from ..engine import _RAGGED
+from ._base import HipModule, RaggedMixin
 
 
 # the conv front-end's shortest input: floor(L / 3) frames must survive six max_pool1d(3) stages (the reference raises below it)
@@ -85,22 +87,61 @@ class RawNet2(HipModule):
         L = self._check_input(x)
         return self._get_engine(L) if self.front_proc == "sinc" else self._get_engine(L, batch=x.shape[0])
 
-    def forward(self, x):
+    def _with_range_fallback(self, call):
+        """call() — which looks its handle up itself — and, when an fp16 handle reports an overflow (SVHIP_ERR_NONFINITE) and
+        range_fallback is set: a warning, this module's handles rebuilt in the fallback compute, and that call once more"""
         from .._lib import SvhipNumericError, ERR_NONFINITE
-        eng = self._engine_for(x)
         try:
-            return self._squeeze(self._batched(eng.embed_wave, x, eng.max_batch))
+            return call()
         except SvhipNumericError as e:
             if e.code != ERR_NONFINITE or self._compute != "f16" or not self._range_fallback:
                 raise
             import warnings
             warnings.warn(f"RawNet2 fp16 handle: {e}; rebuilding this module's handle with compute = {self._range_fallback!r} "
-                          "(every later forward runs in that mode)", RuntimeWarning, stacklevel=2)
+                          "(every later forward runs in that mode)", RuntimeWarning, stacklevel=3)
             self._compute = self._range_fallback
             self._drop_engine()
+            return call()
+
+    def forward(self, x):
+        def call():
             eng = self._engine_for(x)
             return self._squeeze(self._batched(eng.embed_wave, x, eng.max_batch))
+        return self._with_range_fallback(call)
 
 
-def MainModel(nOut=512, **kwargs):
-    return RawNet2(nOut=nOut, **kwargs)
+class RawNet2Conv(RaggedMixin, RawNet2):
+    """front_proc='conv': no LayerNorm(nb_samp) in front, so any length runs and files of different lengths ride in shared calls of
+    the primary handle (RaggedMixin).  The rows of a call are the frames after the conv front-end, floor(L / 3); the fp16 range
+    fallback of ``forward`` covers the ragged calls too, also when a fusion model drives this branch (``ragged_call``)."""
+
+    MIN_FRAMES = 3 ** 6             # 729 front-end frames: one frame reaches the aggregation
+
+    def ragged_frames(self, n_samples):
+        """frames of an utterance of n_samples after the conv front-end; 0 below 2187 samples (it fits no ragged call)"""
+        return _RAGGED["rawnet2_conv"].frames(int(n_samples), 0) if n_samples >= CONV_MIN_SAMPLES else 0
+
+    def _ragged_limits(self):
+        return f", at least {CONV_MIN_SAMPLES} samples each"
+
+    def _embed_ragged_call(self, group):
+        return self._with_range_fallback(lambda: self.ragged_engine().embed_wave_ragged(group))
+
+    def ragged_call(self, packed, offsets, lengths, out=None, ordered=False):
+        """one ragged call of the primary handle on a pack somebody else made (a fusion model's, shared with its other branch).
+        ``ordered``: the device buffers are complete (Engine.embed_wave_ragged) — the call is enqueued on the handle's own stream and
+        waited for here, so that an overflow is reported, and the call redone, before the caller reads ``out``."""
+        def call():
+            eng = self.ragged_engine()
+            if not ordered:
+                return eng.embed_wave_ragged(packed, offsets, lengths, out=out)
+            res = eng.embed_wave_ragged(packed, offsets, lengths, out=out, async_=True, ordered=True)
+            eng.synchronize()
+            return res
+        return self._with_range_fallback(call)
+
+
+def MainModel(nOut=512, front_proc="sinc", **kwargs):
+    """only the conv form has the ragged surface: hasattr(model, "embed_ragged") is how model.py and _fusion.py ask"""
+    cls = RawNet2Conv if front_proc == "conv" else RawNet2
+    return cls(nOut=nOut, front_proc=front_proc, **kwargs)

@@ -200,6 +200,10 @@ class RaggedMixin:
         """what an utterance must meet to ride in a ragged call, for embed_ragged's ValueError"""
         raise NotImplementedError
 
+    def _embed_ragged_call(self, group):
+        """one call of the primary handle on a list of 1-D waveforms that plan_ragged put together"""
+        return self.ragged_engine().embed_wave_ragged(group)
+
     def embed_ragged(self, wavs):
         """list of 1-D waveforms of any lengths -> (n, nOut), each embedded as if alone at its own length, in as few library calls
         as the primary handle's capacity allows (ragged.plan_ragged).  Raises ValueError for utterances that fit no call: the
@@ -208,8 +212,7 @@ class RaggedMixin:
         calls, alone = plan_ragged([self.ragged_frames(w.shape[-1]) for w in wavs], mb, cap, min_frames=self.MIN_FRAMES)
         if alone:
             raise ValueError(f"utterances {alone[:8]} fit no ragged call of this handle ({cap} frames{self._ragged_limits()})")
-        eng = self.ragged_engine()
-        outs = [eng.embed_wave_ragged([wavs[i].reshape(-1) for i in call]) for call in calls]
+        outs = [self._embed_ragged_call([wavs[i].reshape(-1) for i in call]) for call in calls]
         if len(outs) == 1:
             return outs[0]
         return torch.cat(outs, 0) if _is_torch(outs[0]) else np.concatenate(outs, 0)

@@ -148,9 +148,10 @@ class RawECAPAFusion:
     __call__ = forward
 
     # ---- ragged batches: whole files of different lengths in shared calls of BOTH branches' primary handles ---------------
-    # Offered only when both branches have embed_ragged (ECAPA-TDNN + RawNet3: Raw3_ECAPA; ECAPA-TDNN + TitaNet: Tita_ECAPA); on the
-    # RawNet2 fusions (Raw_ECAPA*, Raw_tita) these attributes do not exist (__getattr__), so whole-file evaluation keeps the per-file
-    # path there.
+    # Offered only when both branches have embed_ragged (ECAPA-TDNN + RawNet3: Raw3_ECAPA; ECAPA-TDNN + TitaNet: Tita_ECAPA; ECAPA-TDNN +
+    # RawNet2 'conv': Raw_ECAPA_conv_asp); on the fusions with a RawNet2 'sinc' branch (Raw_ECAPA, Raw_ECAPA_sinc_asp, Raw_ECAPA_sinc_gru,
+    # Raw_tita: LayerNorm(nb_samp) fixes that branch's length) these attributes do not exist (__getattr__), so whole-file evaluation
+    # keeps the per-file path there.
     _RAGGED = ("ragged_packer", "ragged_frames", "embed_ragged")
 
     def __getattr__(self, name):
@@ -177,6 +178,9 @@ class RawECAPAFusion:
         if alone:
             raise ValueError(f"utterances {alone[:8]} fit no ragged call of both branches")
         e1, e2 = self._first.ragged_engine(), self._raw.ragged_engine()
+        # a raw branch that owns a fallback (RawNet2 'conv': an fp16 handle that overflows is rebuilt in another compute) makes its own
+        # call on the shared pack, so that the fallback works here as in its embed_ragged
+        raw_call = getattr(self._raw, "ragged_call", None)
         outs = []
         for call in calls:
             group = [wavs[i].reshape(-1) for i in call]
@@ -189,13 +193,18 @@ class RawECAPAFusion:
                 o1 = torch.empty((len(group), e1.embed_dim), device=packed.device, dtype=torch.float32)
                 o2 = torch.empty((len(group), e2.embed_dim), device=packed.device, dtype=torch.float32)
                 e1.embed_wave_ragged(packed, offs, lens, out=o1, async_=True, ordered=True)
-                e2.embed_wave_ragged(packed, offs, lens, out=o2, async_=True, ordered=True)
+                if raw_call:
+                    raw_call(packed, offs, lens, out=o2, ordered=True)      # on its handle's own stream, beside e1's; waited for inside
+                else:
+                    e2.embed_wave_ragged(packed, offs, lens, out=o2, async_=True, ordered=True)
                 e1.synchronize()
-                e2.synchronize()
+                if not raw_call:
+                    e2.synchronize()
                 outs.append(torch.cat([o1, o2], dim=-1))
             else:
                 packed, offs, lens = e1._pack(group, None, None, True)      # packed once, read by both branches
-                o1, o2 = e1.embed_wave_ragged(packed, offs, lens), e2.embed_wave_ragged(packed, offs, lens)
+                o1 = e1.embed_wave_ragged(packed, offs, lens)
+                o2 = raw_call(packed, offs, lens) if raw_call else e2.embed_wave_ragged(packed, offs, lens)
                 outs.append(torch.cat([o1, o2], dim=-1) if _is_torch(o1) else np.concatenate([o1, o2], axis=-1))
         if len(outs) == 1:
             return outs[0]

@@ -1,6 +1,6 @@
 """Whole-file evaluation (num_eval = 0) on the MI355X: files/s of `ModelHandling._embed_files` over seeded files of 2 - 20 s.
 
-    python tools/ragged_bench.py [--model ECAPA_TDNN|RawNet3|Raw3_ECAPA|Conformer|TitaNet|Tita_ECAPA] [--per-file] [--files 512] [--runs 5] [--compute bf16,f32]
+    python tools/ragged_bench.py [--model ECAPA_TDNN|RawNet3|Raw3_ECAPA|Conformer|TitaNet|Tita_ECAPA|RawNet2_conv|Raw_ECAPA_conv_asp] [--per-file] [--files 512] [--runs 5] [--compute bf16,f32]
                                  [--out profiles/ragged_bench.json]
 
 Default mode: the ragged path of this tree (files of different lengths share calls of the model's primary handle), plus, without a
@@ -17,7 +17,12 @@ written to profiles/rawnet3_ragged_bench.json by convention; --model Conformer (
 to profiles/conformer_ragged_bench.json; --model TitaNet (TitaNet-M, nOut 320, mel features) and --model Tita_ECAPA (nOut 512: ECAPA-TDNN
 C = 512 + TitaNet-M, `features: raw`) to profiles/titanet_ragged_bench.json (one record per run: --out names the file).  The single-call
 comparison and the kernel table are given for ECAPA-TDNN, the Conformer and TitaNet; for TitaNet also the packed depthwise kernels
-(tn_dw, tn_mega_tail) beside the fixed ones over the same rows in the same process, in algorithmic bytes per second."""
+(tn_dw, tn_mega_tail) beside the fixed ones over the same rows in the same process, in algorithmic bytes per second.  --model
+RawNet2_conv (RawNet2 with front_proc='conv', nOut 320) and --model Raw_ECAPA_conv_asp (nOut 512: ECAPA-TDNN C = 512 + RawNet2 'conv',
+`features: raw`; --compute f32,bf16,f16 or half) go to profiles/rawnet2_ragged_bench.json; for RawNet2_conv also the packed block tail
+(rn_rag_tail_part + rn_rag_gate + rn_rag_tail_apply) per block beside the fixed sliced tail (rn_tail at B * 4 <= CUs) of the blocks where
+the fixed forward takes it, from the library's per-label event times of both forwards in the same process, in algorithmic bytes per
+second."""
 from __future__ import annotations
 
 import argparse
@@ -55,7 +60,8 @@ def make_files(n):
 
 MODELS = {"ECAPA_TDNN": "ECAPA_TDNN C=1024 nOut=192", "RawNet3": "RawNet3 nOut=320", "Raw3_ECAPA": "Raw3_ECAPA nOut=512 (ECAPA-TDNN C=512 + RawNet3)",
           "Conformer": "Conformer nOut=512", "TitaNet": "TitaNet-M nOut=320",
-          "Tita_ECAPA": "Tita_ECAPA nOut=512 (ECAPA-TDNN C=512 + TitaNet-M)"}
+          "Tita_ECAPA": "Tita_ECAPA nOut=512 (ECAPA-TDNN C=512 + TitaNet-M)", "RawNet2_conv": "RawNet2 front_proc='conv' nOut=320",
+          "Raw_ECAPA_conv_asp": "Raw_ECAPA_conv_asp nOut=512 (ECAPA-TDNN C=512 + RawNet2 'conv')"}
 
 
 def state_dict(model):
@@ -68,6 +74,13 @@ def state_dict(model):
     if model == "Tita_ECAPA":
         sd = {"ECAPA_TDNN." + k: v for k, v in synth.synth_state_dict(synth.ecapa_param_spec(C=512, input_norm=True), seed=5).items()}
         sd.update({"titaNet." + k: v for k, v in synth.synth_state_dict(synth.titanet_param_spec("m", 320), seed=5).items()})
+        return sd
+    if model in ("RawNet2_conv", "Raw_ECAPA_conv_asp"):
+        rn2 = synth.synth_state_dict(synth.rawnet2_param_spec(nOut=320, front_proc="conv"), seed=5)
+        if model == "RawNet2_conv":
+            return rn2
+        sd = {"ECAPA_TDNN." + k: v for k, v in synth.synth_state_dict(synth.ecapa_param_spec(C=512, input_norm=True), seed=5).items()}
+        sd.update({"rawnet2v2." + k: v for k, v in rn2.items()})
         return sd
     rn3 = synth.synth_state_dict(synth.rawnet3_param_spec(nOut=320), seed=5)
     if model == "RawNet3":
@@ -84,6 +97,9 @@ def handler(compute, per_file, model="ECAPA_TDNN"):
         kw.pop("channels")
     elif model == "TitaNet":
         kw.update(model={"name": model, "nOut": 320}, model_size="m")
+        kw.pop("channels")
+    elif model == "RawNet2_conv":
+        kw.update(model={"name": "RawNet2_custom", "nOut": 320}, features="raw", front_proc="conv", aggregate="asp", att_dim=128)
         kw.pop("channels")
     elif model != "ECAPA_TDNN":
         kw.update(model={"name": model, "nOut": 320 if model == "RawNet3" else 512}, features="raw")
@@ -150,6 +166,45 @@ def titanet_depthwise_rates(lens, H=512, k=7, compute="bf16", iters=20):
     return out
 
 
+RN2_BLOCKS = ((128, True), (128, True), (256, True), (256, False), (256, True), (512, True), (512, False), (512, True))      # (cout, pooled)
+
+
+def rawnet2_tail_rates(eng, pack, offs, lens, esz):
+    """RawNet2's block tail per block over the pack `lens` (samples per utterance): the three packed launches of a block, summed, beside
+    the fixed sliced tail (label rn_tail, a batch of B <= 64 primary-length utterances with about the pack's rows) where the fixed
+    forward takes it — milliseconds from the library's per-label events (option layer_labels: one label per block) and algorithmic
+    bytes per second: the block output read twice, the next pre-activation written once, and x where the next block reads it"""
+    def prof(call):
+        eng.set_option("layer_labels", 1)
+        eng.profile(True)
+        call()
+        p = eng.profile_results()
+        eng.profile(False)
+        eng.set_option("layer_labels", 0)
+        return p
+    T1s = [n // 3 for n in lens]
+    B = max(1, min(64, eng.max_batch, sum(T1s) // (eng.samples // 3)))
+    x = torch.from_numpy(synth.synth_waveforms(B, eng.samples, seed=1)).cuda()
+    p_rag = prof(lambda: eng.embed_wave_ragged(pack, offsets=offs, lengths=lens))
+    p_fix = prof(lambda: eng.embed_wave(x))
+    out = {"utterances": len(lens), "rows_packed": int(sum(T1s)), "fixed_B": B, "rows_fixed": B * (eng.samples // 3), "blocks": []}
+    Tu, Tf = list(T1s), eng.samples // 3
+    for i, (C, down) in enumerate(RN2_BLOCKS):
+        m_in, f_in = sum(Tu), B * Tf
+        if down:
+            Tu, Tf = [t // 3 for t in Tu], Tf // 3
+        writes = 1 if i == 7 or RN2_BLOCKS[i + 1][0] != C else 2
+        ms_r = sum(v["ms"] for k, v in p_rag.items() if k.startswith("rn_rag_") and k.endswith(f" M{m_in} C{C}"))
+        row = {"block": i, "C": C, "packed_ms": round(ms_r, 4),
+               "packed_TBps": round((2 * m_in + writes * sum(Tu)) * C * esz / (ms_r * 1e-3) / 1e12, 3) if ms_r else None}
+        fix = [v for k, v in p_fix.items() if k == f"rn_tail T{f_in // B} C{C}"]
+        if fix:
+            ms_f = sum(v["ms"] for v in fix)
+            row.update(fixed_ms=round(ms_f, 4), fixed_TBps=round((2 * f_in + writes * B * Tf) * C * esz / (ms_f * 1e-3) / 1e12, 3))
+        out["blocks"].append(row)
+    return out
+
+
 def timed(fn, runs):
     fn()                                                        # untimed: handles, allocations, first launches
     wall, dev = [], []
@@ -189,6 +244,27 @@ def main():
         r = {"wall_s": stats(wall), "hip_event_s": stats(dev),
              "files_per_s": {"median": a.files / float(np.median(wall)), "min": a.files / max(wall), "max": a.files / min(wall)},
              "frames_per_s": frames / float(np.median(wall)), "engines_alive": engines_alive(S)}
+        if not a.per_file and a.model == "RawNet2_conv":
+            eng = S.ragged_engine()
+            pack = [torch.from_numpy(f).cuda() for f in files[:40]]
+            while sum(len(p) // 3 for p in pack) > eng.row_capacity or len(pack) > eng.max_batch:
+                pack.pop()
+            lens = [len(p) for p in pack]
+            offs = np.concatenate([[0], np.cumsum(lens)[:-1]])
+            packed = torch.cat(pack)
+            x = torch.from_numpy(synth.synth_waveforms(eng.max_batch, eng.samples, seed=1)).cuda()
+            w_fix, _ = timed(lambda: eng.embed_wave(x), a.runs)
+            w_rag, _ = timed(lambda: eng.embed_wave_ragged(packed, offsets=offs, lengths=lens), a.runs)
+            r["fixed_B256_frames_per_s"] = eng.max_batch * (eng.samples // 3) / float(np.median(w_fix))
+            r["ragged_call_frames_per_s"] = sum(n // 3 for n in lens) / float(np.median(w_rag))
+            r["ragged_over_fixed"] = r["ragged_call_frames_per_s"] / r["fixed_B256_frames_per_s"]
+            eng.profile(True)
+            eng.embed_wave_ragged(packed, offsets=offs, lengths=lens)
+            prof = eng.profile_results()
+            eng.profile(False)
+            r["ragged_forward_kernels_ms"] = {k: {"ms": round(v["ms"], 4), "launches": v["launches"]}
+                                              for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])}
+            r["block_tail"] = rawnet2_tail_rates(eng, packed, offs, lens, 4 if compute in ("f32", "fp32") else 2)
         if not a.per_file and a.model in ("ECAPA_TDNN", "Conformer", "TitaNet"):
             eng = S.ragged_engine()
             # the ragged call against the fixed-length call of the same handle, device-resident input, frames/s of each
