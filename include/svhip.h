@@ -299,6 +299,33 @@ int svhip_titanet_embed_ragged(svhip_handle* h, const float* in, const int64_t* 
 /* lengths[i] are samples (is_wave != 0) or frames.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is svhip_last_error(NULL). */
 int svhip_titanet_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave);
 
+/* Ragged ResNetSE34V2 packs (added under ABI v5): the same calls for SVHIP_MODEL_RESNETSE.  The ECAPA, RawNet2, RawNet3, Conformer and
+ * TitaNet calls above keep refusing a ResNetSE handle with SVHIP_ERR_UNSUPPORTED, and these refuse every other model.
+ *   in / offsets / lengths / emb_out / flags / is_wave: the rules of svhip_titanet_embed_ragged.  Utterance i has T_i mel frames and is a
+ *   (P_l,i, Q_l, C_l) channels-last image at each of four frame levels: P_0,i = T_i (the stem and layer1), P_l+1,i = ceil(P_l,i / 2)
+ *   (layer2 .. layer4); Q_l and C_l are the handle's.  The images lie back to back in utterance order at every level.
+ * CAPACITY, checked on the host before anything is enqueued (svhip_resnetse_ragged_check is the same test without a handle):
+ *   1 <= n <= max_batch;  every T_i >= 2 (InstanceNorm1d over one frame is undefined);  wave: every lengths[i] >= n_fft;  offsets >= 0;
+ *   sum_i 8 ceil(T_i / 8) <= max_batch * T, T = samples / hop + 1.  An utterance counts as its frames rounded up to a multiple of 8 because
+ *   the subsampling rounds up: sum T_i <= max_batch * T alone would let a deeper level overflow (max_batch = 4, T = 40, frames 37 + 41 +
+ *   41 + 41 = 160, but 19 + 21 + 21 + 21 = 82 rows at level 1, over 4 * 20).  With the rounding, sum_i P_l,i <= max_batch * P_l at every
+ *   level, since ceil(T_i / 2^l) <= 8 ceil(T_i / 8) / 2^l for l <= 3.
+ * Anything else is SVHIP_ERR_INVALID with a message that names the utterance and the limit.  Compute SVHIP_F32 or SVHIP_BF16 only: every
+ * other model returns SVHIP_ERR_UNSUPPORTED.  The first ragged call of a handle allocates the segment tables, the tile tables of the
+ * convolutions, the SE tile sums of a pack and a waveform staging buffer (once); nothing is allocated per call, and a handle that never
+ * sees a ragged call pays nothing.
+ * BATCH INVARIANCE as above: bit-for-bit the same embedding and stages whatever the pack.  Every utterance is tiled by the convolution's
+ * plan for its own image and padded with zeros at its own first and last frame, its SE squeeze adds its own tiles in its own order, and
+ * the two attention convolutions run on one kernel; so rs_stem .. rs_layer4 of an utterance are also bit for bit those of a fixed-length
+ * handle of its length at B = 1, and the embedding agrees with it to the precision of the compute type.  The fixed-length call stays bit
+ * for bit what it was.  A non-finite input gives NaN for its own utterance only, and SVHIP_ERR_NONFINITE.
+ * STAGES after a ragged call: rs_stem, rs_layer1 .. rs_layer4 (sum_i P_l,i * Q_l, C_l), the images packed in utterance order; rs_pool
+ * (n, 2 F); "mel" the packed (n_mels, T_i) blocks. */
+int svhip_resnetse_embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
+                                int32_t flags, int32_t is_wave);
+/* lengths[i] are samples (is_wave != 0) or frames.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is svhip_last_error(NULL). */
+int svhip_resnetse_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave);
+
 /* Eval-mode cropping on device.  Replaces, for decoded 16-bit PCM, the cropping half of loadWAV
  * (src/processing/audio_loader.py:110-150): wrap-pad files not longer than L to L+1 samples, take num_eval
  * crops of L samples at int(linspace(0, len - L, num_eval)), scale by 1/32768 (soundfile float32).  pcm holds
@@ -508,6 +535,14 @@ int svhip_titanet_depthwise_ragged(const void* x, const void* skip, const void* 
  * synchronised.  SVHIP_OK, SVHIP_ERR_INVALID (arguments), SVHIP_ERR_NOMEM or SVHIP_ERR_HIP. */
 int svhip_resnetse_conv3x3(const void* x, const float* w, const float* scale, const float* shift, void* y, int32_t compute, int32_t B,
                            int32_t P, int32_t Q, int32_t Cin, int32_t Cout, int32_t stride, int32_t relu_in, int32_t relu_out, void* stream);
+
+/* The same kernel over a pack (tests): n utterances, utterance u a (P_host[u], Q, Cin) image; the images lie back to back in x, and their
+ * (Po_u, Qo, Cout) outputs back to back in y.  P_host holds n HOST int32 frame counts; the entry builds and uploads the segment tables,
+ * builds the tile tables on the device, launches the packed kernel and synchronises.  Every utterance comes out exactly as
+ * svhip_resnetse_conv3x3 gives it alone (B = 1, P = P_host[u]), bit for bit, and nothing outside the pack's rows is written. */
+int svhip_resnetse_conv3x3_ragged(const void* x, const float* w, const float* scale, const float* shift, void* y, int32_t compute,
+                                  const int32_t* P_host, int32_t n, int32_t Q, int32_t Cin, int32_t Cout, int32_t stride, int32_t relu_in,
+                                  int32_t relu_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,8 @@ _SIGNATURES = {
     "svhip_conformer_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),
     "svhip_titanet_embed_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32]),
     "svhip_titanet_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),
+    "svhip_resnetse_embed_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32]),
+    "svhip_resnetse_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),
     "svhip_crop_pcm16": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     "svhip_l2norm": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32]),
     "svhip_score_pairs": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32]),
@@ -127,6 +129,7 @@ _SIGNATURES = {
     "svhip_titanet_depthwise": (C.c_int, [_P] * 8 + [C.c_int32] * 5 + [_P]),
     "svhip_titanet_depthwise_ragged": (C.c_int, [_P] * 8 + [C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "svhip_resnetse_conv3x3": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 9 + [_P]),
+    "svhip_resnetse_conv3x3_ragged": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P] + [C.c_int32] * 7 + [_P]),
 }
 
 _lib = None

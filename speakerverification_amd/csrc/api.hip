@@ -11,8 +11,8 @@
 using namespace svhip;
 
 namespace svhip {      // the ragged hooks of the models that have them: only kModels names them
-RaggedCheckFn ecapa_ragged_check, rawnet2_ragged_check, rawnet3_ragged_check, conformer_ragged_check, titanet_ragged_check;
-RaggedEmbedFn ecapa_embed_ragged, rawnet2_embed_ragged, rawnet3_embed_ragged, conformer_embed_ragged, titanet_embed_ragged;      // (RawNet2 / RawNet3: waveforms only, is_wave is true)
+RaggedCheckFn ecapa_ragged_check, rawnet2_ragged_check, rawnet3_ragged_check, conformer_ragged_check, titanet_ragged_check, resnetse_ragged_check;
+RaggedEmbedFn ecapa_embed_ragged, rawnet2_embed_ragged, rawnet3_embed_ragged, conformer_embed_ragged, titanet_embed_ragged, resnetse_embed_ragged;      // (RawNet2 / RawNet3: waveforms only, is_wave is true)
 }
 
 namespace {
@@ -77,7 +77,8 @@ const ModelOps kModels[] = {
      "encoder.mega_blocks.", titanet_ragged_check, titanet_embed_ragged},      // (the block count follows from what was loaded: titanet_finalize checks its blocks)
     {SVHIP_MODEL_CONFORMER,    conformer_check, conformer_spec, conformer_finalize, conformer_alloc, fbank_then_features, conformer_forward, conformer_stage, 4,
      nullptr, conformer_ragged_check, conformer_embed_ragged},
-    {SVHIP_MODEL_RESNETSE,     resnetse_check,  resnetse_spec,  resnetse_finalize,  resnetse_alloc,  fbank_then_features, resnetse_forward,  resnetse_stage,  4},
+    {SVHIP_MODEL_RESNETSE,     resnetse_check,  resnetse_spec,  resnetse_finalize,  resnetse_alloc,  fbank_then_features, resnetse_forward,  resnetse_stage,  4,
+     nullptr, resnetse_ragged_check, resnetse_embed_ragged},
     {SVHIP_MODEL_NONE,         none_check,      nullptr,        nullptr,            nullptr,         nullptr,             nullptr,           nullptr,         1},   // fbank + scoring
 };
 
@@ -218,7 +219,8 @@ constexpr RaggedExport kRagEcapa{SVHIP_MODEL_ECAPA, "ECAPA", kRagF32Bf16, "SVHIP
                        kRagRawnet2{SVHIP_MODEL_RAWNET2_CONV, "RAWNET2_CONV", kRagF32Bf16 | 1u << SVHIP_F16, "SVHIP_F32, SVHIP_BF16 or SVHIP_F16"},
                        kRagRawnet3{SVHIP_MODEL_RAWNET3, "RAWNET3", kRagF32Bf16, "SVHIP_F32 or SVHIP_BF16"},
                        kRagConformer{SVHIP_MODEL_CONFORMER, "CONFORMER", kRagF32Bf16, "SVHIP_F32 or SVHIP_BF16"},
-                       kRagTitanet{SVHIP_MODEL_TITANET, "TITANET", kRagF32Bf16, "SVHIP_F32 or SVHIP_BF16"};
+                       kRagTitanet{SVHIP_MODEL_TITANET, "TITANET", kRagF32Bf16, "SVHIP_F32 or SVHIP_BF16"},
+                       kRagResnetse{SVHIP_MODEL_RESNETSE, "RESNETSE", kRagF32Bf16, "SVHIP_F32 or SVHIP_BF16"};
 
 // the rules of a pack, on the host alone, in this order: the scope, the model's rules on the configuration, the pack size, the model's
 // rules on every utterance in index order
@@ -227,7 +229,7 @@ int ragged_rules(const RaggedExport& x, const svhip_config& c, const int32_t* le
         return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: SVHIP_MODEL_%s only (the sinc front-end of SVHIP_MODEL_RAWNET2 and SVHIP_MODEL_RAWNET2_GRU "
                       "starts with LayerNorm(nb_samp), whose weights fix the input length)", x.name, x.name);
     if (c.model != x.model)
-        return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: SVHIP_MODEL_%s only (ECAPA, RawNet2 'conv', RawNet3, Conformer and TitaNet packs have their own "
+        return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: SVHIP_MODEL_%s only (ECAPA, RawNet2 'conv', RawNet3, Conformer, TitaNet and ResNetSE packs have their own "
                       "calls; the other models embed one length per handle)", x.name, x.name);
     if (c.compute < 0 || c.compute >= 32 || !(x.computes >> c.compute & 1u))
         return refuse(err, SVHIP_ERR_UNSUPPORTED, "ragged %s packs: compute %s only", x.name, x.compute_names);
@@ -559,6 +561,15 @@ int svhip_titanet_embed_ragged(svhip_handle* h, const float* in, const int64_t* 
 
 int svhip_titanet_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave) {
     return ragged_check(kRagTitanet, cfg, lengths, n, is_wave != 0);
+}
+
+int svhip_resnetse_embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
+                                int32_t flags, int32_t is_wave) {
+    return embed_ragged(kRagResnetse, h, in, offsets, lengths, n, emb_out, flags, is_wave != 0);
+}
+
+int svhip_resnetse_ragged_check(const svhip_config* cfg, const int32_t* lengths, int32_t n, int32_t is_wave) {
+    return ragged_check(kRagResnetse, cfg, lengths, n, is_wave != 0);
 }
 
 int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, const int64_t* offsets, const int32_t* lengths,

@@ -1,4 +1,4 @@
-// api_ragged.hip — what the ragged calls of ECAPA-TDNN, RawNet2 'conv', RawNet3, the Conformer and TitaNet share on the host: the refusal texts and the
+// api_ragged.hip — what the ragged calls of ECAPA-TDNN, RawNet2 'conv', RawNet3, the Conformer, TitaNet and ResNetSE34V2 share on the host: the refusal texts and the
 // rules of the mel models, the table ring (RagTables), the one table layout, and the driver that turns a call's arrays into a RagPack
 // (allocation, the row loop, the input, the upload).  A model's api_<model>.hip keeps its RagRule, its own rules and its forward.
 #include <algorithm>
@@ -25,7 +25,7 @@ int rag_rows_fit(std::string& err, int i, int64_t rows, int64_t cap, const char*
 }
 
 int rag_mel_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err, bool cfg_extra_ok, const char* cfg_names,
-                  int min_frames, const char* why, RagUttRule* more, int64_t bound) {
+                  int min_frames, const char* why, RagUttRule* more, int64_t bound, int row_unit) {
     if (c.hop_length <= 0 || c.max_batch <= 0 || c.samples < c.n_fft || !cfg_extra_ok) return refuse(err, SVHIP_ERR_INVALID, "bad %s", cfg_names);
     const int64_t cap = (int64_t)c.max_batch * mel_frames(c, c.samples, true);
     int64_t rows = 0;
@@ -36,7 +36,7 @@ int rag_mel_check(const svhip_config& c, const int32_t* lengths, int n, bool is_
         if (T < min_frames) return refuse(err, SVHIP_ERR_INVALID, "utterance %d: %lld frames, fewer than %d%s", i, (long long)T, min_frames, why);
         int rc;
         if (more && (rc = more(bound, i, T, err))) return rc;
-        if ((rc = rag_rows_fit(err, i, rows += T, cap, "T"))) return rc;
+        if ((rc = rag_rows_fit(err, i, rows += (T + row_unit - 1) / row_unit * row_unit, cap, "T"))) return rc;
     }
     return SVHIP_OK;
 }
@@ -77,7 +77,7 @@ RagTables::~RagTables() {
     }
 }
 
-// ---- the mel input of a pack (ECAPA-TDNN, Conformer, TitaNet) ---------------------------------------------------------
+// ---- the mel input of a pack (ECAPA-TDNN, Conformer, TitaNet, ResNetSE) ---------------------------------------------------------
 // mel0: the n + 1 first mel frames on the host.  Waveforms go through the staging buffer and one fbank launch per utterance into
 // h->d_feat, host features are copied there, device features are read in place; fills feat_off, *d_feat is the array they index
 static int rag_mel_input(svhip_handle* h, RagTables& rag, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths,

@@ -13,6 +13,19 @@
 //   SE      g = sigmoid(W2 relu(W1 mean(v) + b1) + b2)            rs_se_gate (the tile sums in tile order)
 //   down    d = bn(conv1x1_s(relu(x)))   (first block of stages 2 - 4)      rs_conv, KS = 1
 //   tail    out = relu((d | relu(x)) + g v)                       rs_se_apply
+//
+// A ragged pack (resnetse_embed_ragged): n utterances of T_u mel frames in ONE call.  Utterance u at frame level l is a (P_l,u, Q_l, C_l)
+// image, P_0,u = T_u (the stem and layer1) and P_l+1,u = rs_out_size(P_l,u, 2) = ceil(P_l,u / 2) (layer2 .. layer4); the images lie back to
+// back in utterance order in the buffers above, one row0 / utt table per level (RagRule: four levels).  resnetse_walk is the one walk of
+// the layers: for a pack the convolutions run on the packed form of rs_conv (every utterance tiled by rs_conv_plan of its own image, the
+// padding at its own first and last frame), the stem, the SE gate and the block tail in their segment-table forms, the two attention
+// convolutions on launch_gemm_ragged and the pooling, the input test and fc on ragged.hip's kernels, so no value of an utterance depends
+// on what it is packed with, and its stages are bit for bit those of a fixed-length handle of its length at B = 1.
+// CAPACITY of a pack: 1 <= n <= max_batch and sum_u 8 ceil(T_u / 8) <= max_batch T.  The subsampling rounds up, so sum T_u <= max_batch T
+// alone does not protect the deeper levels (max_batch = 4, T = 40, frames 37 + 41 + 41 + 41 = 160, but 19 + 21 + 21 + 21 = 82 > 4 * 20 rows
+// at level 1); counting an utterance as 8 ceil(T_u / 8) rows does, at every level: P_l,u = ceil(T_u / 2^l) <= 8 ceil(T_u / 8) / 2^l for
+// l <= 3 (the right side is an integer >= T_u / 2^l), and max_batch T / 2^l <= max_batch ceil(T / 2^l) = max_batch P_l.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -50,6 +63,11 @@ struct ResNetSEState : ModelState {
     void* att = nullptr;                  // (Bmax P4, 128)
     float* logits = nullptr;              // (Bmax P4, Q4 C4) fp32
     float *pool_raw = nullptr, *pool = nullptr, *pool_one = nullptr, *pool_zero = nullptr;     // (Bmax, 2 Q4 C4) [mu | sg]
+    // ragged packs (all allocated by the first ragged call; the buffers above already hold a pack's rows at every level)
+    RagTables rag;                        // the tables of a call (four frame levels) and the waveform staging buffer
+    int* rag_tiles = nullptr;             // RS_RAG_KINDS x (tile0 (Bmax + 1) | plan (Bmax)): the tile tables of a pack's convolutions
+    float* rag_part = nullptr;            // the SE tile sums of a pack: rag_part_floats (rs_rag_part_floats) of them
+    size_t rag_part_floats = 0;
 };
 
 ResNetSEState& S(svhip_handle* h) { return static_cast<ResNetSEState&>(*h->model); }
@@ -98,6 +116,37 @@ RsConvParams rs_params(const RsConv& L, const void* x, void* y, int B, int P, in
     p.relu_in = relu_in; p.relu_out = relu_out;
     rs_conv_plan(p);
     return p;
+}
+
+// ---- ragged packs: the tile tables of the convolutions ----------------------------------------------------------------------------
+// A pack's convolutions come in ten kinds, each with its own tiles: 3 x 3 stride 1 inside level l (kind l, 0 .. 3), 3 x 3 stride 2 into
+// level l (kind 3 + l, l = 1 .. 3) and the 1 x 1 stride-2 downsample into level l (kind 6 + l)
+constexpr int RS_RAG_KINDS = 10;
+struct RsRagKind { int l_in, l_out, stride, ks; };
+RsRagKind rs_rag_kind(int k) {
+    if (k < 4) return {k, k, 1, 3};
+    return k < 7 ? RsRagKind{k - 4, k - 3, 2, 3} : RsRagKind{k - 7, k - 6, 2, 1};
+}
+int rs_rag_kind_of(const RsConv& L, int l_out) { return L.stride == 1 ? l_out : L.ks == 3 ? 3 + l_out : 6 + l_out; }
+
+// The most SE tiles (of conv2: 3 x 3 stride 1 inside a level) a pack can have at level l, times C_l, maximised over the levels.  An
+// utterance is tiled on its own, so short utterances give more tiles per row than max_batch ntp ntq of the fixed image.  The bound follows
+// from the capacity rule: with w(T) = 8 ceil(T / 8) and rho_l = max over P of tiles_l(P) / w(the shortest T with P_l = P),
+//   sum_u tiles_l(P_l,u) <= rho_l sum_u w(T_u) <= rho_l max_batch T.
+size_t rs_rag_part_floats(const ResNetSEState& s, size_t cap) {
+    size_t best = 0;
+    for (int l = 0; l < 4; ++l) {
+        double rho = 0.0;
+        for (size_t P = 1; ((P - 1) << l) + 1 <= cap; ++P) {
+            RsConvParams p;
+            p.P = (int)P; p.Q = s.Q[l + 1]; p.stride = 1; p.ks = 3;
+            rs_conv_plan(p);
+            const size_t Tmin = ((P - 1) << l) + 1;
+            rho = std::max(rho, (double)p.ntp * p.ntq / (double)((Tmin + 7) / 8 * 8));
+        }
+        best = std::max(best, ((size_t)std::ceil(rho * (double)cap) + 1) * s.C[l + 1]);
+    }
+    return best;
 }
 
 }  // namespace
@@ -246,80 +295,168 @@ int resnetse_alloc(svhip_handle* h) {
     return SVHIP_OK;
 }
 
-static int resnetse_forward_part(svhip_handle* h, const float* d_feat, int b0, int B) {
+// ResNetSE.forward, written once for both forms.  pk null: a fixed-length batch of B utterances of h->T frames, (B, n_mels, T) at d_feat,
+// on h->cur; the two attention convolutions take their routes through conv_gemm.  pk set: its n = B utterances as packed images
+// (features at d_feat + pk->off[u]), on the handle's stream; lv[l] are the tables of frame level l, the convolutions read the tile
+// tables built here, and the attention convolutions go to the generic kernel (launch_gemm_ragged: one kernel at every row count).  The
+// helpers pick the form; below them the network reads once.
+static int resnetse_walk(svhip_handle* h, const float* d_feat, int B, const RagPack* pk) {
     auto& s = S(h);
-    (void)b0;
     const svhip_config& c = h->cfg;
-    const int dt = h->dt;
+    const Seg* g = pk ? pk->lv : nullptr;                 // g[l]: frame level l of the pack
+    const int dt = h->dt, Bmax = c.max_batch;
     const bool bf = h->bf16;
+    if (g) h->cur = h->stream;
     hipStream_t st = h->cur;
     int rc;
+    // a pack: the tile tables of its ten kinds of convolution — counted on the host for the grids and the LDS, built on the device from
+    // the row0 tables (the upload is already enqueued on this stream; nothing here waits for it)
+    RsRagConv rk[RS_RAG_KINDS];
+    if (g) {
+        for (int l = 0; l < 4; ++l)
+            if ((rc = run(h, "rag_rows", 0, [&]() { return launch_rag_rows(g[l].row0, B, g[l].maxT, g[l].utt, st); }))) return rc;
+        for (int k = 0; k < RS_RAG_KINDS; ++k) {
+            const RsRagKind kd = rs_rag_kind(k);
+            RsRagConv& r = rk[k];
+            int* tab = s.rag_tiles + (size_t)k * (2 * Bmax + 1);
+            r.row0_in = g[kd.l_in].row0; r.row0_out = g[kd.l_out].row0; r.tile0 = tab; r.plan = tab + Bmax + 1; r.n = B;
+            rs_rag_tiles_host(g[kd.l_in].hrow0, B, s.Q[kd.l_in + 1], kd.stride, kd.ks, &r.ntiles, &r.halo_bytes);
+            if ((rc = run(h, "rs_rag_tiles", 0, [&]() {
+                     return launch_rs_rag_tiles(r.row0_in, B, s.Q[kd.l_in + 1], kd.stride, kd.ks, tab, tab + Bmax + 1, st);
+                 }))) return rc;
+            if (r.ntiles <= 0 || (k < 4 && (size_t)r.ntiles * s.C[k + 1] > s.rag_part_floats))
+                SV_FAIL(h, SVHIP_ERR_STATE, "ragged ResNetSE: %d tiles at level %d are over the bound of the SE tile sums", r.ntiles, k);
+        }
+    }
+    float* part = g ? s.rag_part : s.part;
+    // one convolution L of the block that writes level `lv` (= its stage), x -> y
+    auto conv = [&](const char* label, const RsConv& L, const void* x, void* y, int P, int Q, int lv, bool relu_in, bool relu_out, float* pt,
+                    RsConvParams& p) {
+        p = rs_params(L, x, y, B, P, Q, relu_in, relu_out, pt);
+        const double taps = L.ks * L.ks, pos = g ? (double)g[lv].M * p.Qo : (double)B * p.Po * p.Qo;
+        return run(h, label, 2.0 * taps * L.cin * L.cout * pos, [&]() {
+            return g ? launch_rs_conv_ragged(p, rk[rs_rag_kind_of(L, lv)], dt, st) : launch_rs_conv(p, dt, st);
+        });
+    };
     // log(x + 1e-6) - mean_t for features == 'melspectrogram', then InstanceNorm1d(n_mels) without affine: (B, n_mels, T) -> (B, T, n_mels) fp32
-    if ((rc = run(h, "prologue", 0, [&]() {
-             return launch_prologue(d_feat, s.xin, false, B, c.n_mels, h->T, c.log_input, h->d_ones, h->d_zeros, h->d_pstats, st);
-         }))) return rc;
+    // (a pack: rag_prologue's arithmetic is launch_prologue's over each utterance's own frames; the identity affine selects the norm)
+    if (g) {
+        if ((rc = run(h, "rag_prologue", 0, [&]() {
+                 return launch_rag_prologue(d_feat, pk->off, g[0].row0, B, g[0].maxT, s.xin, false, c.n_mels, c.log_input, h->d_ones, h->d_zeros, h->d_pstats, st);
+             }))) return rc;
+    } else if ((rc = run(h, "prologue", 0, [&]() {
+                    return launch_prologue(d_feat, s.xin, false, B, c.n_mels, h->T, c.log_input, h->d_ones, h->d_zeros, h->d_pstats, st);
+                }))) return rc;
     // conv1 (with bias) -> ReLU -> bn1                                                       ResNetBaseline.py:260-262
-    if ((rc = run(h, "rs_stem", 2.0 * 9 * s.C[0] * B * s.P[0] * s.Q[0], [&]() {
-             return launch_rs_stem(s.xin, s.stem_w, s.stem_b, s.stem_scale, s.stem_shift, s.out[0], dt, B, s.P[0], s.Q[0], st);
+    if ((rc = run(h, g ? "rs_stem_rag" : "rs_stem", 2.0 * 9 * s.C[0] * (g ? (double)g[0].M : (double)B * s.P[0]) * s.Q[0], [&]() {
+             return g ? launch_rs_stem_ragged(s.xin, s.stem_w, s.stem_b, s.stem_scale, s.stem_shift, s.out[0], dt, g[0].row0, g[0].utt, g[0].M, s.Q[0], st)
+                      : launch_rs_stem(s.xin, s.stem_w, s.stem_b, s.stem_scale, s.stem_shift, s.out[0], dt, B, s.P[0], s.Q[0], st);
          }))) return rc;
     const void* x = s.out[0];
-    int P = s.P[0], Q = s.Q[0], stage = 0, pp = 0;
+    int P = s.P[0], Q = s.Q[0], stage = 0, pp = 0;      // (P: of the fixed form; a pack's frames are in its tables)
     static const char* const kConvLabel[4] = {"rs_conv3x3_s1", "rs_conv3x3_s2", "rs_conv3x3_s3", "rs_conv3x3_s4"};
     for (size_t i = 0; i < s.blocks.size(); ++i) {
         const RsBlock& K = s.blocks[i];
         while ((int)i >= s.stage_end[stage]) ++stage;
         const bool last = (int)i + 1 == s.stage_end[stage];
         void* out = last ? s.out[stage + 1] : s.tmp[pp];
-        const RsConvParams p1 = rs_params(K.c1, x, s.tmp[2], B, P, Q, true, true, nullptr);
-        const RsConvParams p2 = rs_params(K.c2, s.tmp[2], s.tmp[3], B, p1.Po, p1.Qo, false, false, s.part);
-        const double pos = (double)B * p1.Po * p1.Qo;
-        if ((rc = run(h, kConvLabel[stage], 2.0 * 9 * K.c1.cin * K.c1.cout * pos, [&]() { return launch_rs_conv(p1, dt, st); }))) return rc;
-        if ((rc = run(h, kConvLabel[stage], 2.0 * 9 * K.c2.cin * K.c2.cout * pos, [&]() { return launch_rs_conv(p2, dt, st); }))) return rc;
-        if ((rc = run(h, "rs_se_gate", 0, [&]() {
-                 return launch_rs_se_gate(s.part, p2.ntp * p2.ntq, B, K.c2.cout, p2.Po * p2.Qo, K.se_w1, K.se_b1, K.se_w2, K.se_b2, s.gate, st);
+        RsConvParams p1, p2, pd;
+        if ((rc = conv(kConvLabel[stage], K.c1, x, s.tmp[2], P, Q, stage, true, true, nullptr, p1))) return rc;
+        if ((rc = conv(kConvLabel[stage], K.c2, s.tmp[2], s.tmp[3], p1.Po, p1.Qo, stage, false, false, part, p2))) return rc;
+        if ((rc = run(h, g ? "rs_se_gate_rag" : "rs_se_gate", 0, [&]() {
+                 return g ? launch_rs_se_gate_ragged(part, rk[stage].tile0, g[stage].row0, B, K.c2.cout, p2.Qo, K.se_w1, K.se_b1, K.se_w2, K.se_b2, s.gate, st)
+                          : launch_rs_se_gate(part, p2.ntp * p2.ntq, B, K.c2.cout, p2.Po * p2.Qo, K.se_w1, K.se_b1, K.se_w2, K.se_b2, s.gate, st);
              }))) return rc;
         const void* res = x;
         if (K.has_down) {
-            const RsConvParams pd = rs_params(K.down, x, s.tmp[4], B, P, Q, true, false, nullptr);
-            if ((rc = run(h, "rs_down", 2.0 * K.down.cin * K.down.cout * pos, [&]() { return launch_rs_conv(pd, dt, st); }))) return rc;
+            if ((rc = conv("rs_down", K.down, x, s.tmp[4], P, Q, stage, true, false, nullptr, pd))) return rc;
             res = s.tmp[4];
         }
-        if ((rc = run(h, "rs_se_apply", 0, [&]() {
-                 return launch_rs_se_apply(s.tmp[3], res, s.gate, out, dt, B, p2.Po * p2.Qo, K.c2.cout, !K.has_down, st);
+        if ((rc = run(h, g ? "rs_se_apply_rag" : "rs_se_apply", 0, [&]() {
+                 return g ? launch_rs_se_apply_ragged(s.tmp[3], res, s.gate, out, dt, g[stage].utt, g[stage].M, p2.Qo, K.c2.cout, !K.has_down, st)
+                          : launch_rs_se_apply(s.tmp[3], res, s.gate, out, dt, B, p2.Po * p2.Qo, K.c2.cout, !K.has_down, st);
              }))) return rc;
         x = out;
         P = p1.Po; Q = p1.Qo;
         if (!last) pp ^= 1;
     }
     // attention (ResNetBaseline.py:186-194,269-279) on rows (B P4, Q4 C4): Conv1d -> ReLU -> BN -> Conv1d -> softmax over frames, then the
-    // weighted mean and sqrt(clamp(weighted variance, 1e-5))
-    const int F = s.C[4] * s.Q[4], M = B * P;
-    GemmParams pa = conv_params(h, s.att0, x, F, s.att, 128, M, P);
+    // weighted mean and sqrt(clamp(weighted variance, 1e-5)).  Both convolutions are 1 x 1: no tap crosses an utterance's edge
+    const int F = s.C[4] * s.Q[4], M = g ? g[3].M : B * P, Tg = g ? 1 : P;
+    auto gemm = [&](const ConvLayer& L, GemmParams p) {
+        if (!g) return conv_gemm(h, L, p);
+        p.rag_utt = g[3].utt; p.rag_row0 = g[3].row0;
+        return run(h, "rag_gemm", (double)M * L.flops_per_row, [&]() { return launch_gemm_ragged(p, bf, st); });
+    };
+    GemmParams pa = conv_params(h, s.att0, x, F, s.att, 128, M, Tg);
     pa.act1 = ACT_RELU;
-    if ((rc = conv_gemm(h, s.att0, pa))) return rc;
-    GemmParams pl = conv_params(h, s.att3, s.att, 128, s.logits, F, M, P);
+    if ((rc = gemm(s.att0, pa))) return rc;
+    GemmParams pl = conv_params(h, s.att3, s.att, 128, s.logits, F, M, Tg);
     pl.out_f32 = 1;
-    if ((rc = conv_gemm(h, s.att3, pl))) return rc;
-    if ((rc = run(h, "rs_asp_pool", 0, [&]() {
-             return launch_asp_pool(s.logits, x, bf, F, B, P, F, s.pool_one, s.pool_zero, s.pool_raw, s.pool, 1e-5f, 0.0f, st);
+    if ((rc = gemm(s.att3, pl))) return rc;
+    if ((rc = run(h, g ? "rag_asp_pool" : "rs_asp_pool", 0, [&]() {
+             return g ? launch_rag_asp_pool(s.logits, x, bf, F, g[3].row0, B, F, s.pool_one, s.pool_zero, s.pool_raw, s.pool, 1e-5f, st)
+                      : launch_asp_pool(s.logits, x, bf, F, B, P, F, s.pool_one, s.pool_zero, s.pool_raw, s.pool, 1e-5f, 0.0f, st);
          }))) return rc;
-    // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the GEMM's ReLU epilogue would have dropped it)
+    // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the GEMM's ReLU epilogue would have dropped it):
+    // its own row only
     if ((rc = run(h, "rs_in_check", 0, [&]() {
-             return launch_tn_nonfinite_rows(d_feat, (int64_t)c.n_mels * h->T, B, s.pool, 2 * F, 2 * F, st);
+             return g ? launch_tn_nonfinite_rows_ragged(d_feat, pk->off, g[0].row0, c.n_mels, B, s.pool, 2 * F, 2 * F, st)
+                      : launch_tn_nonfinite_rows(d_feat, (int64_t)c.n_mels * h->T, B, s.pool, 2 * F, 2 * F, st);
          }))) return rc;
-    return run(h, "rs_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
-        return launch_rowvec_linear(s.pool, 2 * F, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, s.fc.K, ACT_NONE, st);
+    // fc; 'SAP' reads the weighted means only (K = F of the 2 F columns)
+    return run(h, g ? "rag_fc" : "rs_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
+        return g ? launch_rag_linear(s.pool, 2 * F, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, s.fc.K, ACT_NONE, st)
+                 : launch_rowvec_linear(s.pool, 2 * F, s.fc.W, s.fc.bias, h->d_emb, c.embed_dim, B, c.embed_dim, s.fc.K, ACT_NONE, st);
     });
 }
 
+static int resnetse_forward_part(svhip_handle* h, const float* d_feat, int, int B) { return resnetse_walk(h, d_feat, B, nullptr); }
 int resnetse_forward(svhip_handle* h, const float* d_feat, int B) { return forward_lanes(h, resnetse_forward_part, d_feat, B, 1, B); }
 
-int resnetse_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // rs_stem, rs_layer1 .. rs_layer4 (B P Q, C), rs_pool (B, 2 F)
+// ---- ragged packs ------------------------------------------------------------------------------------------
+// ResNetSE's rules for a pack (RaggedCheckFn; include/svhip.h), on the host alone.  An utterance counts as 8 ceil(T_u / 8) rows against
+// max_batch T: then sum_u P_l,u <= max_batch P_l at every level, since P_l,u = ceil(T_u / 2^l) <= 8 ceil(T_u / 8) / 2^l (file header).
+// T_u >= 2: InstanceNorm1d over one frame is the reference's own ValueError
+int resnetse_ragged_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err) {
+    return rag_mel_check(c, lengths, n, is_wave, err, true, "hop_length / max_batch / samples", 2, " (InstanceNorm1d over one frame is undefined)", nullptr,
+                         0, 8);
+}
+
+// four frame levels: the mel frames (the stem, layer1), then what each stride-2 stage leaves
+static void resnetse_rag_frames(const svhip_config& c, int64_t len, bool is_wave, int T[RAG_LEVELS]) {
+    T[0] = (int)mel_frames(c, len, is_wave);
+    for (int l = 1; l < 4; ++l) T[l] = rs_out_size(T[l - 1], 2);
+}
+static const RagRule kResnetseRag = {4, resnetse_rag_frames, true};
+
+int resnetse_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is_wave, const int64_t* in_off, const int32_t* lengths, int n) {
+    auto& s = S(h);
+    const size_t B = h->cfg.max_batch;
+    const size_t utt_cap[RAG_LEVELS] = {B * s.P[1], B * s.P[2], B * s.P[3], B * s.P[4]};
+    RagPack pk;
+    int rc;
+    // the handle's first ragged call: the tile tables and the SE tile sums of a pack (rag_pack: the segment tables and the staging buffer)
+    if (!s.rag_tiles && (rc = dev_alloc(h, &s.rag_tiles, (size_t)RS_RAG_KINDS * (2 * B + 1)))) return rc;
+    if (!s.rag_part) {
+        s.rag_part_floats = rs_rag_part_floats(s, B * h->T);
+        if ((rc = dev_alloc(h, &s.rag_part, s.rag_part_floats))) return rc;
+    }
+    if ((rc = rag_pack(h, s.rag, kResnetseRag, utt_cap, in, in_host, is_wave, in_off, lengths, n, pk)) || (rc = resnetse_walk(h, pk.in, n, &pk))) return rc;
+    set_rag_rows(h, pk);
+    return SVHIP_OK;
+}
+
+// rs_stem, rs_layer1 .. rs_layer4 (B P Q, C), rs_pool (B, 2 F); after a ragged forward the packed rows (sum_u P_l,u Q_l, C_l) in utterance order
+int resnetse_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {
     auto& s = S(h);
     int sg = -1;
     if (n == "rs_stem") sg = 0;
     else if (n.size() == 9 && n.compare(0, 8, "rs_layer") == 0 && n[8] >= '1' && n[8] <= '4') sg = n[8] - '0';
-    if (sg >= 0) { v.src = s.out[sg]; v.rows = (size_t)h->lastB * s.P[sg] * s.Q[sg]; v.cols = v.ld = s.C[sg]; }
+    if (sg >= 0) {
+        const size_t frames = h->rag_levels ? (size_t)h->rag_rows[sg ? sg - 1 : 0] : (size_t)h->lastB * s.P[sg];
+        v.src = s.out[sg]; v.rows = frames * s.Q[sg]; v.cols = v.ld = s.C[sg];
+    }
     else if (n == "rs_pool") { v.src = s.pool; v.rows = h->lastB; v.cols = v.ld = 2 * (size_t)s.C[4] * s.Q[4]; v.f32 = true; }
     else return unknown_stage(h, n);
     return SVHIP_OK;
@@ -356,5 +493,52 @@ extern "C" int svhip_resnetse_conv3x3(const void* x, const float* w, const float
     }
     const hipError_t e2 = hipStreamSynchronize(st);
     (void)hipFree(dW);
+    return (e == hipSuccess && e2 == hipSuccess) ? SVHIP_OK : SVHIP_ERR_HIP;
+}
+
+// The same kernel over a pack (tests): n utterances, utterance u a (P_host[u], Q, Cin) image, the images back to back in x and (Po_u, Qo,
+// Cout) back to back in y.  Builds and uploads the row0 tables of the two levels, builds the tile tables on the device, launches the packed
+// kernel and synchronises.
+extern "C" int svhip_resnetse_conv3x3_ragged(const void* x, const float* w, const float* scale, const float* shift, void* y, int32_t compute,
+                                             const int32_t* P_host, int32_t n, int32_t Q, int32_t Cin, int32_t Cout, int32_t stride, int32_t relu_in,
+                                             int32_t relu_out, void* stream) {
+    using namespace svhip;
+    if ((compute != SVHIP_F32 && compute != SVHIP_BF16) || !x || !w || !scale || !shift || !y || !P_host) return SVHIP_ERR_INVALID;
+    if (n <= 0 || Q <= 0 || Cin <= 0 || Cin % 32 != 0 || Cout <= 0 || (stride != 1 && stride != 2)) return SVHIP_ERR_INVALID;
+    std::vector<int> tab(2 * (size_t)(n + 1), 0);          // row0 of the input level | row0 of the output level
+    for (int u = 0; u < n; ++u) {
+        if (P_host[u] <= 0 || (int64_t)tab[u] + P_host[u] > 0x7fffffffLL / Q) return SVHIP_ERR_INVALID;
+        tab[u + 1] = tab[u] + P_host[u];
+        tab[n + 1 + u + 1] = tab[n + 1 + u] + rs_out_size(P_host[u], stride);
+    }
+    const bool bf = compute == SVHIP_BF16;
+    const std::vector<float> packed = rs_pack(w, Cout, Cin, 3, bf ? 32 : 16);
+    std::vector<uint16_t> pb;
+    if (bf) {
+        pb.resize(packed.size());
+        for (size_t i = 0; i < packed.size(); ++i) pb[i] = f32_to_bf16_rne(packed[i]);
+    }
+    void* dW = nullptr;
+    int* dT = nullptr;                                     // the two row0 tables, then tile0 (n + 1) and plan (n)
+    const size_t bytes = packed.size() * (bf ? 2 : 4), tints = 4 * (size_t)(n + 1);
+    if (hipMalloc(&dW, bytes) != hipSuccess) return SVHIP_ERR_NOMEM;
+    if (hipMalloc((void**)&dT, tints * 4) != hipSuccess) { (void)hipFree(dW); return SVHIP_ERR_NOMEM; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipError_t e = hipMemcpy(dW, bf ? (const void*)pb.data() : (const void*)packed.data(), bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dT, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        RsRagConv r;
+        r.row0_in = dT; r.row0_out = dT + (n + 1); r.tile0 = dT + 2 * (n + 1); r.plan = dT + 3 * (n + 1); r.n = n;
+        rs_rag_tiles_host(tab.data(), n, Q, stride, 3, &r.ntiles, &r.halo_bytes);
+        RsConvParams p;
+        p.X = x; p.Y = y; p.W = dW; p.scale = scale; p.shift = shift;
+        p.B = n; p.Q = Q; p.Cin = Cin; p.Cout = Cout; p.stride = stride; p.ks = 3; p.relu_in = relu_in != 0; p.relu_out = relu_out != 0;
+        e = launch_rs_rag_tiles(r.row0_in, n, Q, stride, 3, dT + 2 * (n + 1), dT + 3 * (n + 1), st);
+        if (e == hipSuccess) e = launch_rs_conv_ragged(p, r, bf ? DT_BF16 : DT_F32, st);
+        if (e == hipErrorInvalidValue) { (void)hipFree(dW); (void)hipFree(dT); return SVHIP_ERR_INVALID; }
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(dW);
+    (void)hipFree(dT);
     return (e == hipSuccess && e2 == hipSuccess) ? SVHIP_OK : SVHIP_ERR_HIP;
 }

@@ -346,10 +346,11 @@ inline void set_rag_rows(svhip_handle* h, const RagPack& pk) {
 // What the packs of the three mel models must all pass, in this order: the configuration (hop_length, max_batch, samples >= n_fft and
 // the model's cfg_extra_ok; cfg_names ends the text), every waveform n_fft samples, every utterance min_frames frames (why: the text's
 // explanation, "" or " (...)"), the model's further rules on an utterance of T frames (more with its own figure `bound`, or null), the
-// running row sum
+// running row sum, in which an utterance counts as its frames rounded up to a multiple of row_unit (ResNetSE: 8, which keeps every
+// subsampled level of the pack within the handle's rows; the others: 1)
 using RagUttRule = int(int64_t bound, int i, int64_t T, std::string& err);
 int rag_mel_check(const svhip_config& c, const int32_t* lengths, int n, bool is_wave, std::string& err, bool cfg_extra_ok, const char* cfg_names,
-                  int min_frames, const char* why, RagUttRule* more = nullptr, int64_t bound = 0);
+                  int min_frames, const char* why, RagUttRule* more = nullptr, int64_t bound = 0, int row_unit = 1);
 
 // api_gemm.hip: the GEMM of one conv layer.  conv_plan is the one place that decides its kernel: conv_gemm launches what it returns,
 // and the producers of an operand ask it too, so that they write the layout that kernel reads.

@@ -546,6 +546,16 @@ inline int rs_out_size(int n, int stride) { return (n - 1) / stride + 1; }      
 // y (B, Po, Qo, Cout) = [relu](scale[n] conv(x) + shift[n]), conv = ks x ks (3: zero padding 1; 1: none) at stride 1 / 2 over
 // [relu](x) (B, P, Q, Cin); W packed [Cin / CK][ks ks taps][Cout][CK] in the compute type, CK = 32 (bf16) / 16 (fp32) channels, tap =
 // 3 dp + dq.  Cin % CK == 0; Cout 32 or a multiple of 64.  part (optional): (B, ntp ntq, Cout) fp32 sums of y over each tile's positions.
+// the tables of a convolution over a ragged pack (launch_rs_conv_ragged below)
+struct RsRagConv {
+    const int* row0_in = nullptr;
+    const int* row0_out = nullptr;
+    const int* tile0 = nullptr;
+    const int* plan = nullptr;
+    int n = 0;
+    int ntiles = 0;                      // host: tile0[n]
+    int halo_bytes = 0;                  // host: the largest halo of the pack, in LDS bytes
+};
 struct RsConvParams {
     const void* X = nullptr;
     void* Y = nullptr;
@@ -555,9 +565,21 @@ struct RsConvParams {
     float* part = nullptr;
     int B = 0, P = 0, Q = 0, Cin = 0, Cout = 0, stride = 1, ks = 3, relu_in = 0, relu_out = 0;
     int Po = 0, Qo = 0, TP = 0, TQ = 0, ntp = 0, ntq = 0;      // rs_conv_plan: output size, tile (TP x TQ <= 128 positions), tiles per utterance
+    RsRagConv rag;                       // launch_rs_conv_ragged fills it; the fixed form never reads it
 };
 void rs_conv_plan(RsConvParams& p);
 hipError_t launch_rs_conv(const RsConvParams& p, int dt, hipStream_t stream);
+// The same convolution over a ragged pack: n utterances, utterance u a (P_u, Q, Cin) image at the rows [row0_in[u], row0_in[u + 1]) of x and
+// a (Po_u, Qo, Cout) image at [row0_out[u], row0_out[u + 1]) of y, Po_u = rs_out_size(P_u, stride) (a row = one frame, Q C values).  Every
+// utterance is tiled by rs_conv_plan of its OWN image, so its values, and its rows of `part`, are bit for bit those of launch_rs_conv on it
+// alone (B = 1).  tile0 (n + 1) is the prefix of the utterances' tile counts and plan (n) their tiles, TP | TQ << 8: device tables that
+// launch_rs_rag_tiles builds from row0_in on the stream (no host synchronisation).  The host counts the same tiles from its copy of the
+// table (rs_rag_tiles_host: the grid, and the dynamic LDS of the pack's largest halo); one function serves both sides.
+void rs_rag_tiles_host(const int* hrow0_in, int n, int Q, int stride, int ks, int* ntiles, int* halo_bytes);
+hipError_t launch_rs_rag_tiles(const int* row0_in, int n, int Q, int stride, int ks, int* tile0, int* plan, hipStream_t stream);
+// p: X, Y, W, scale, shift, part, Q, Cin, Cout, stride, ks, relu_* as for launch_rs_conv; B / P / Po / TP / TQ / ntp / ntq are not read.
+// part (optional): (r.ntiles, Cout), the pack's tiles in utterance order, each utterance's in its own tile order
+hipError_t launch_rs_conv_ragged(RsConvParams p, const RsRagConv& r, int dt, hipStream_t stream);
 // stem: y (B, P, Q, 32) = scale relu(conv3x3(x) + bias) + shift on the fp32 (B, P, Q) input; w tap-major [9][32]
 hipError_t launch_rs_stem(const float* x, const float* w, const float* bias, const float* scale, const float* shift, void* y, int dt, int B, int P, int Q,
                           hipStream_t stream);
@@ -567,6 +589,16 @@ hipError_t launch_rs_se_gate(const float* part, int ntiles, int B, int C, int po
 // out = relu(res' + y gate[b, :]); res' = relu(res) (identity residual) or res (downsample output)
 hipError_t launch_rs_se_apply(const void* y, const void* res, const float* gate, void* out, int dt, int B, int positions, int C, bool res_relu,
                               hipStream_t stream);
+// The three over a pack (row0 / utt: one frame level's tables, ragged.hip; M = row0[n] frames of Q positions): the stem pads at each
+// utterance's own first and last frame; the gate of utterance u adds its own tiles part[tile0[u] .. tile0[u + 1]) in index order and divides
+// by its own P_u Q positions; the tail takes the gate row of its frame's utterance.  An utterance's values are those of the fixed forms at
+// B = 1, bit for bit.
+hipError_t launch_rs_stem_ragged(const float* x, const float* w, const float* bias, const float* scale, const float* shift, void* y, int dt,
+                                 const int* row0, const int* utt, int M, int Q, hipStream_t stream);
+hipError_t launch_rs_se_gate_ragged(const float* part, const int* tile0, const int* row0, int n, int C, int Q, const float* w1, const float* b1,
+                                    const float* w2, const float* b2, float* gate, hipStream_t stream);
+hipError_t launch_rs_se_apply_ragged(const void* y, const void* res, const float* gate, void* out, int dt, const int* utt, int M, int Q, int C,
+                                     bool res_relu, hipStream_t stream);
 
 // synthetic waveforms from a counter-based RNG (synth.hip): out (B, L) fp32 = utterances [first_utt, first_utt + B) of the stream `seed`
 hipError_t launch_synth_wave(float* out, uint64_t seed, int64_t first_utt, int B, int L, hipStream_t stream);

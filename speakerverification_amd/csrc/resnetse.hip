@@ -17,6 +17,11 @@
 //   out     y = scale[n] acc + shift[n] (the folded BatchNorm), optional ReLU, stored in the activation type; with `part` also the
 //           per-(tile, channel) sums of y over the tile's valid positions (fp32, fixed order) — the SE squeeze, finished by rs_se_gate in
 //           tile order.  No atomics: permuting the batch permutes every value bit for bit.
+//   packs   RAG = true: n utterances of different frame counts, their images back to back (launch_rs_conv_ragged).  A workgroup still owns
+//           TP x TQ <= 128 positions of one utterance; it finds the utterance in a tile prefix built on the device from the level's row0
+//           table (rs_rag_tiles_kernel), takes that utterance's own tile and frame counts, and runs the same body: an utterance's values
+//           and tile sums are those of the fixed form on it alone.  The grid is the pack's tiles, no more.  The stem, the SE gate and the
+//           block tail have segment-table forms next to their fixed ones.
 // Every ReLU here is x < 0 ? 0 : x, which keeps a NaN (fmaxf would drop it): a NaN input reaches the embedding of its own utterance.
 #include "common.h"
 #include "kernels.h"
@@ -62,10 +67,54 @@ template <> struct RsMma<bf16_t> {
     }
 };
 
+// The tile rs_conv_plan gives an output image of Po x Qo positions.  One function for the host (rs_conv_plan; the grid and the LDS of a
+// pack) and the device (rs_rag_tiles_kernel), which must agree on every image: the score is a few IEEE double operations, and contraction
+// into fused multiply-adds, which only the device has, is switched off, so both sides round alike.
+__host__ __device__ inline void rs_tile_of(int Po, int Qo, int stride, int ks, int& TP, int& TQ) {
+#pragma clang fp contract(off)
+    double best = -1.0;
+    TP = TQ = 1;
+    for (int tq = 1; tq <= 32 && tq <= Qo; ++tq) {
+        const int tp = 128 / tq < Po ? 128 / tq : Po;
+        const int64_t halo = (int64_t)((tp - 1) * stride + ks) * ((tq - 1) * stride + ks);
+        if (halo * RS_ROWB > RS_HALO_MAX) continue;
+        const double cover = (double)((Po + tp - 1) / tp * tp) * ((Qo + tq - 1) / tq * tq);
+        // MFMA rows that carry an output, then (a tie-breaker) the halo positions staged per output
+        const double score = ((double)Po * Qo / cover) * (tp * tq / 128.0) - 0.01 * (double)halo / ((double)tp * tq * stride * stride);
+        if (score > best) { best = score; TP = tp; TQ = tq; }
+    }
+}
+
 __device__ __forceinline__ int rs_slot(int row, int ch) { return row * RS_ROWB + ((ch ^ ((row >> 2) & 3)) << 4); }
 
-template <typename T, int BN, int KS>
+// RAG false: a fixed-length batch, the tile found from the grid index alone.  RAG true: a pack (p.rag) — the workgroup finds its utterance u
+// by a binary search of the tile prefix rag.tile0 (uniform over the workgroup, ceil(log2 n) <= 8 steps for n <= 256), then makes its copy
+// of p describe that utterance alone: its own tile (rag.plan[u], rs_tile_of of its own image), its own frame counts (the two levels' row0
+// tables) and X / Y at its first frame.  The K loop and the epilogue below are then the fixed form's on that image: the zero padding sits
+// at the utterance's own first and last frame, and `part` is indexed by the pack's tile number, which runs through an utterance's tiles in
+// its own tile order.
+template <typename T, int BN, int KS, bool RAG>
 __global__ __launch_bounds__(256) void rs_conv_kernel(RsConvParams p) {
+    int tile_first = 0;                 // RAG: the pack's tiles before this utterance's
+    if constexpr (RAG) {
+        const RsRagConv& r = p.rag;
+        const int t = blockIdx.x / (p.Cout / BN);
+        int lo = 0, hi = r.n;           // tile0[lo] <= t < tile0[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (r.tile0[mid] <= t) lo = mid; else hi = mid;
+        }
+        const int ri = r.row0_in[lo], ro = r.row0_out[lo], pl = r.plan[lo];
+        tile_first = r.tile0[lo];
+        p.P = r.row0_in[lo + 1] - ri;
+        p.Po = r.row0_out[lo + 1] - ro;
+        p.TP = pl & 255;
+        p.TQ = pl >> 8;
+        p.ntp = (p.Po + p.TP - 1) / p.TP;
+        p.ntq = (p.Qo + p.TQ - 1) / p.TQ;
+        p.X = reinterpret_cast<const T*>(p.X) + (int64_t)ri * p.Q * p.Cin;
+        p.Y = reinterpret_cast<T*>(p.Y) + (int64_t)ro * p.Qo * p.Cout;
+    }
     typedef RsMma<T> TR;
     typedef typename TR::chunk_t chunk_t;
     constexpr int EPC = TR::EPC, CK = TR::CK, NT = BN / 32, NTAPS = KS * KS, PAD = KS / 2;
@@ -77,8 +126,8 @@ __global__ __launch_bounds__(256) void rs_conv_kernel(RsConvParams p) {
 
     const int nn = p.Cout / BN;         // the channel tiles of one position tile are neighbours in the grid: they share the halo in L2
     const int tile = blockIdx.x / nn;
-    const int tq_i = tile % p.ntq, t2 = tile / p.ntq;
-    const int tp_i = t2 % p.ntp, b = t2 / p.ntp;
+    const int tq_i = (tile - tile_first) % p.ntq, t2 = (tile - tile_first) / p.ntq;
+    const int tp_i = t2 % p.ntp, b = t2 / p.ntp;      // (RAG: b = 0)
     const int p0 = tp_i * p.TP, q0 = tq_i * p.TQ;
     const int ip0 = p0 * p.stride - PAD, iq0 = q0 * p.stride - PAD;
     const int n0 = (blockIdx.x - tile * nn) * BN;
@@ -183,9 +232,9 @@ hipError_t rs_conv_launch(const RsConvParams& p, hipStream_t stream) {
     const int HP = (p.TP - 1) * p.stride + KS, HQ = (p.TQ - 1) * p.stride + KS;
     const size_t lds = (size_t)HP * HQ * RS_ROWB + (size_t)KS * KS * BN * RS_ROWB;
     static DeviceOnce attr;
-    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(rs_conv_kernel<T, BN, KS>), RS_HALO_MAX + 9 * 64 * RS_ROWB)) return e;
+    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(rs_conv_kernel<T, BN, KS, false>), RS_HALO_MAX + 9 * 64 * RS_ROWB)) return e;
     dim3 grid((unsigned)(p.B * p.ntp * p.ntq * (p.Cout / BN))), block(256);
-    hipLaunchKernelGGL((rs_conv_kernel<T, BN, KS>), grid, block, lds, stream, p);
+    hipLaunchKernelGGL((rs_conv_kernel<T, BN, KS, false>), grid, block, lds, stream, p);
     return hipGetLastError();
 }
 
@@ -289,22 +338,162 @@ __global__ __launch_bounds__(256) void rs_se_apply_kernel(const T* __restrict__ 
     *reinterpret_cast<decltype(o.v)*>(out + i * N) = o.v;
 }
 
+// ---- the same three over a ragged pack, and the tile tables of its convolutions -----------------------------------------------------
+// tile0 / plan of one convolution of a pack from the input level's row0: thread u plans utterance u's output image (rs_tile_of, the
+// function the host counts with), thread 0 adds the counts up in utterance order.  One workgroup; n > 256 runs in rounds of 256.
+__global__ __launch_bounds__(256) void rs_rag_tiles_kernel(const int* __restrict__ row0_in, int n, int Q, int stride, int ks, int* __restrict__ tile0,
+                                                           int* __restrict__ plan) {
+    __shared__ int cnt[256];
+    __shared__ int base;
+    if (threadIdx.x == 0) base = 0;
+    const int Qo = (Q - 1) / stride + 1;          // rs_out_size
+    for (int u0 = 0; u0 < n; u0 += 256) {
+        const int u = u0 + threadIdx.x;
+        if (u < n) {
+            const int Po = (row0_in[u + 1] - row0_in[u] - 1) / stride + 1;
+            int TP, TQ;
+            rs_tile_of(Po, Qo, stride, ks, TP, TQ);
+            plan[u] = TP | TQ << 8;
+            cnt[threadIdx.x] = ((Po + TP - 1) / TP) * ((Qo + TQ - 1) / TQ);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int t = base;
+            const int m = min(256, n - u0);
+            for (int i = 0; i < m; ++i) { tile0[u0 + i] = t; t += cnt[i]; }
+            base = t;
+            if (u0 + m == n) tile0[n] = t;
+        }
+        __syncthreads();
+    }
+}
+
+// rs_stem_kernel with the frame's utterance taken from the level's tables: M frames of Q positions
+template <typename T>
+__global__ __launch_bounds__(256) void rs_stem_rag_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                          const float* __restrict__ scale, const float* __restrict__ shift, T* __restrict__ y,
+                                                          const int* __restrict__ row0, const int* __restrict__ utt, int M, int Q) {
+    __shared__ float sw[9 * 32 + 3 * 32];
+    for (int i = threadIdx.x; i < 9 * 32; i += 256) sw[i] = w[i];
+    if (threadIdx.x < 32) {
+        sw[288 + threadIdx.x] = bias[threadIdx.x];
+        sw[320 + threadIdx.x] = scale[threadIdx.x];
+        sw[352 + threadIdx.x] = shift[threadIdx.x];
+    }
+    __syncthreads();
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t pos = idx >> 2;
+    if (pos >= (int64_t)M * Q) return;
+    const int cg = (int)(idx & 3) * 8;
+    const int q = (int)(pos % Q);
+    const int m = (int)(pos / Q);
+    const int u = utt[m];
+    const int r0 = row0[u], P = row0[u + 1] - r0;
+    const int pp = m - r0;
+    const float* __restrict__ xb = x + (int64_t)r0 * Q;        // the utterance's (P, Q) image
+    float in[9];
+#pragma unroll
+    for (int dp = 0; dp < 3; ++dp)
+#pragma unroll
+        for (int dq = 0; dq < 3; ++dq) {
+            const int ip = pp + dp - 1, iq = q + dq - 1;
+            in[dp * 3 + dq] = (ip >= 0 && ip < P && iq >= 0 && iq < Q) ? xb[(int64_t)ip * Q + iq] : 0.0f;
+        }
+    T* __restrict__ yo = y + pos * 32 + cg;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int c = cg + k;
+        float v = sw[288 + c];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) v = fmaf(sw[t * 32 + c], in[t], v);
+        v = v < 0.0f ? 0.0f : v;
+        yo[k] = from_f32<T>(fmaf(v, sw[320 + c], sw[352 + c]));
+    }
+}
+
+// rs_se_gate_kernel of utterance u = blockIdx.x over its own tiles [tile0[u], tile0[u + 1]) and its own P_u Q positions
+__global__ __launch_bounds__(256) void rs_se_gate_rag_kernel(const float* __restrict__ part, const int* __restrict__ tile0, const int* __restrict__ row0,
+                                                             int C, int Q, const float* __restrict__ w1, const float* __restrict__ b1,
+                                                             const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ gate) {
+    __shared__ float mean[256], hid[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t0 = tile0[b], ntiles = tile0[b + 1] - t0;
+    const float inv_n = 1.0f / (float)((row0[b + 1] - row0[b]) * Q);
+    if (tid < C) {
+        const float* __restrict__ pp = part + (int64_t)t0 * C + tid;
+        float s = 0.0f;
+        int t = 0;
+        for (; t + 8 <= ntiles; t += 8) {          // eight loads in flight, added in index order (a 20 s file has 2500 tiles at level 0)
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = pp[(int64_t)(t + k) * C];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s += v[k];
+        }
+        for (; t < ntiles; ++t) s += pp[(int64_t)t * C];
+        mean[tid] = s * inv_n;
+    }
+    __syncthreads();
+    for (int j = wave * 4; j < wave * 4 + 4; ++j) {
+        float s = 0.0f;
+        for (int c = lane; c < C; c += 64) s = fmaf(w1[j * C + c], mean[c], s);
+        s = wave_sum(s) + b1[j];
+        if (lane == 0) hid[j] = s < 0.0f ? 0.0f : s;
+    }
+    __syncthreads();
+    if (tid < C) {
+        float s = b2[tid];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) s = fmaf(w2[tid * 16 + j], hid[j], s);
+        gate[(int64_t)b * C + tid] = 1.0f / (1.0f + expf(-s));
+    }
+}
+
+// rs_se_apply_kernel with the gate row of the frame's utterance: per_frame_vec = Q C / N vectors in a frame
+template <typename T>
+__global__ __launch_bounds__(256) void rs_se_apply_rag_kernel(const T* __restrict__ y, const T* __restrict__ res, const float* __restrict__ gate,
+                                                              T* __restrict__ out, const int* __restrict__ utt, int64_t nvec, int per_frame_vec, int cvec,
+                                                              int res_relu) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nvec) return;
+    constexpr int N = Vec16<T>::N;
+    const int b = utt[(int)(i / per_frame_vec)];
+    const int c0 = (int)(i % cvec) * N;
+    const Vec16<T> yv = ld_nt(y + i * N), rv = ld_nt(res + i * N);
+    const float* __restrict__ g = gate + (int64_t)b * cvec * N + c0;
+    Vec16<T> o;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        float r = rv.get(k);
+        if (res_relu) r = r < 0.0f ? 0.0f : r;
+        const float v = fmaf(yv.get(k), g[k], r);
+        o.set(k, v < 0.0f ? 0.0f : v);
+    }
+    *reinterpret_cast<decltype(o.v)*>(out + i * N) = o.v;
+}
+
+template <typename T, int BN, int KS>
+hipError_t rs_conv_rag_launch(const RsConvParams& p, const RsRagConv& r, hipStream_t stream) {
+    const size_t lds = (size_t)r.halo_bytes + (size_t)KS * KS * BN * RS_ROWB;
+    static DeviceOnce attr;
+    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(rs_conv_kernel<T, BN, KS, true>), RS_HALO_MAX + 9 * 64 * RS_ROWB)) return e;
+    dim3 grid((unsigned)((int64_t)r.ntiles * (p.Cout / BN))), block(256);
+    hipLaunchKernelGGL((rs_conv_kernel<T, BN, KS, true>), grid, block, lds, stream, p);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t rs_conv_rag_t(const RsConvParams& p, const RsRagConv& r, hipStream_t stream) {
+    if (p.Cout == 32) return p.ks == 3 ? rs_conv_rag_launch<T, 32, 3>(p, r, stream) : rs_conv_rag_launch<T, 32, 1>(p, r, stream);
+    return p.ks == 3 ? rs_conv_rag_launch<T, 64, 3>(p, r, stream) : rs_conv_rag_launch<T, 64, 1>(p, r, stream);
+}
+
 }  // namespace
 
 void rs_conv_plan(RsConvParams& p) {
     p.Po = rs_out_size(p.P, p.stride);
     p.Qo = rs_out_size(p.Q, p.stride);
-    double best = -1.0;
-    p.TP = p.TQ = 1;
-    for (int tq = 1; tq <= 32 && tq <= p.Qo; ++tq) {
-        const int tp = 128 / tq < p.Po ? 128 / tq : p.Po;
-        const int64_t halo = (int64_t)((tp - 1) * p.stride + p.ks) * ((tq - 1) * p.stride + p.ks);
-        if (halo * RS_ROWB > RS_HALO_MAX) continue;
-        const double cover = (double)((p.Po + tp - 1) / tp * tp) * ((p.Qo + tq - 1) / tq * tq);
-        // MFMA rows that carry an output, then (a tie-breaker) the halo positions staged per output
-        const double score = ((double)p.Po * p.Qo / cover) * (tp * tq / 128.0) - 0.01 * (double)halo / ((double)tp * tq * p.stride * p.stride);
-        if (score > best) { best = score; p.TP = tp; p.TQ = tq; }
-    }
+    rs_tile_of(p.Po, p.Qo, p.stride, p.ks, p.TP, p.TQ);
     p.ntp = (p.Po + p.TP - 1) / p.TP;
     p.ntq = (p.Qo + p.TQ - 1) / p.TQ;
 }
@@ -354,6 +543,77 @@ hipError_t launch_rs_se_apply(const void* y, const void* res, const float* gate,
     else
         hipLaunchKernelGGL(rs_se_apply_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)y, (const bf16_t*)res, gate, (bf16_t*)out, nvec, (int)per, cvec,
                            res_relu ? 1 : 0);
+    return hipGetLastError();
+}
+
+// ---- ragged packs ----------------------------------------------------------------------------------------------------------------
+void rs_rag_tiles_host(const int* hrow0_in, int n, int Q, int stride, int ks, int* ntiles, int* halo_bytes) {
+    const int Qo = rs_out_size(Q, stride);
+    int64_t tiles = 0;
+    int halo = 0;
+    for (int u = 0; u < n; ++u) {
+        const int Po = rs_out_size(hrow0_in[u + 1] - hrow0_in[u], stride);
+        int TP, TQ;
+        rs_tile_of(Po, Qo, stride, ks, TP, TQ);
+        tiles += (int64_t)((Po + TP - 1) / TP) * ((Qo + TQ - 1) / TQ);
+        const int hb = ((TP - 1) * stride + ks) * ((TQ - 1) * stride + ks) * RS_ROWB;
+        if (hb > halo) halo = hb;
+    }
+    *ntiles = tiles > 0x7fffffffLL ? -1 : (int)tiles;
+    *halo_bytes = halo;
+}
+
+hipError_t launch_rs_rag_tiles(const int* row0_in, int n, int Q, int stride, int ks, int* tile0, int* plan, hipStream_t stream) {
+    if (!row0_in || !tile0 || !plan || n <= 0 || Q <= 0 || (stride != 1 && stride != 2) || (ks != 3 && ks != 1)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rs_rag_tiles_kernel, dim3(1), dim3(256), 0, stream, row0_in, n, Q, stride, ks, tile0, plan);
+    return hipGetLastError();
+}
+
+hipError_t launch_rs_conv_ragged(RsConvParams p, const RsRagConv& r, int dt, hipStream_t stream) {
+    const int ck = dt == DT_F32 ? 16 : 32;
+    if (dt != DT_F32 && dt != DT_BF16) return hipErrorInvalidValue;
+    if (p.Q <= 0 || p.Cin <= 0 || p.Cin % ck != 0 || p.Cout <= 0 || p.Cout % 32 != 0 || (p.Cout != 32 && p.Cout % 64 != 0)) return hipErrorInvalidValue;
+    if ((p.ks != 3 && p.ks != 1) || (p.stride != 1 && p.stride != 2) || !p.X || !p.Y || !p.W || !p.scale || !p.shift) return hipErrorInvalidValue;
+    if (!r.row0_in || !r.row0_out || !r.tile0 || !r.plan || r.n <= 0 || r.ntiles <= 0 || r.halo_bytes <= 0 || r.halo_bytes > RS_HALO_MAX)
+        return hipErrorInvalidValue;
+    if ((int64_t)r.ntiles * (p.Cout / 32) > 0x7fffffffLL) return hipErrorInvalidValue;
+    p.Qo = rs_out_size(p.Q, p.stride);
+    p.rag = r;
+    return dt == DT_F32 ? rs_conv_rag_t<float>(p, r, stream) : rs_conv_rag_t<bf16_t>(p, r, stream);
+}
+
+hipError_t launch_rs_stem_ragged(const float* x, const float* w, const float* bias, const float* scale, const float* shift, void* y, int dt,
+                                 const int* row0, const int* utt, int M, int Q, hipStream_t stream) {
+    if ((dt != DT_F32 && dt != DT_BF16) || !row0 || !utt || M <= 0 || Q <= 0) return hipErrorInvalidValue;
+    const int64_t n = (int64_t)M * Q * 4;
+    dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (dt == DT_F32) hipLaunchKernelGGL(rs_stem_rag_kernel<float>, grid, block, 0, stream, x, w, bias, scale, shift, (float*)y, row0, utt, M, Q);
+    else hipLaunchKernelGGL(rs_stem_rag_kernel<bf16_t>, grid, block, 0, stream, x, w, bias, scale, shift, (bf16_t*)y, row0, utt, M, Q);
+    return hipGetLastError();
+}
+
+hipError_t launch_rs_se_gate_ragged(const float* part, const int* tile0, const int* row0, int n, int C, int Q, const float* w1, const float* b1,
+                                    const float* w2, const float* b2, float* gate, hipStream_t stream) {
+    if (C > 256 || C % 32 != 0 || n <= 0 || Q <= 0 || !part || !tile0 || !row0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rs_se_gate_rag_kernel, dim3(n), dim3(256), 0, stream, part, tile0, row0, C, Q, w1, b1, w2, b2, gate);
+    return hipGetLastError();
+}
+
+hipError_t launch_rs_se_apply_ragged(const void* y, const void* res, const float* gate, void* out, int dt, const int* utt, int M, int Q, int C,
+                                     bool res_relu, hipStream_t stream) {
+    if ((dt != DT_F32 && dt != DT_BF16) || !utt || M <= 0 || Q <= 0) return hipErrorInvalidValue;
+    const int nv = dt == DT_F32 ? 4 : 8;
+    if (C % nv != 0) return hipErrorInvalidValue;
+    const int cvec = C / nv;
+    const int64_t per = (int64_t)Q * cvec, nvec = per * M;
+    if (per > 0x7fffffffLL) return hipErrorInvalidValue;
+    dim3 grid((unsigned)((nvec + 255) / 256)), block(256);
+    if (dt == DT_F32)
+        hipLaunchKernelGGL(rs_se_apply_rag_kernel<float>, grid, block, 0, stream, (const float*)y, (const float*)res, gate, (float*)out, utt, nvec, (int)per, cvec,
+                           res_relu ? 1 : 0);
+    else
+        hipLaunchKernelGGL(rs_se_apply_rag_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)y, (const bf16_t*)res, gate, (bf16_t*)out, utt, nvec, (int)per,
+                           cvec, res_relu ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -95,6 +95,8 @@ _RAGGED = {
     "conformer": _RaggedCalls(("svhip_conformer_embed_ragged", 1), ("svhip_conformer_embed_ragged", 0), "svhip_conformer_ragged_check", True,
                               _MEL_FRAMES),
     "titanet": _RaggedCalls(("svhip_titanet_embed_ragged", 1), ("svhip_titanet_embed_ragged", 0), "svhip_titanet_ragged_check", True, _MEL_FRAMES),
+    # (row_capacity counts mel frames; an utterance of a pack takes its frames rounded up to a multiple of 8: ResNetSE.ragged_frames)
+    "resnetse": _RaggedCalls(("svhip_resnetse_embed_ragged", 1), ("svhip_resnetse_embed_ragged", 0), "svhip_resnetse_ragged_check", True, _MEL_FRAMES),
 }
 
 

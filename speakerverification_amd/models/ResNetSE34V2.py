@@ -11,11 +11,12 @@ are the reference's (292 at nOut = 256; ``num_batches_tracked`` is kept and igno
 here).  Lengths: T = 1 is a ``ValueError`` as in the reference (InstanceNorm1d over one frame); a handle is made for L >= 512 samples, one
 frame of the library's front-end, so ``forward`` takes T >= 7 frames and ``embed_wave`` L >= 512 (T = 2 .. 6 raise ``ValueError`` here).  ``n_mels`` must be a multiple of 8: the reference's ``outmap_size = int(n_mels / 8)``
 agrees with its own convolution arithmetic only then.  SpecAugment (``augment=True`` with 'spec_domain') is training only and not built.
+``embed_ragged`` embeds utterances of different lengths in shared calls of the primary handle (whole-file evaluation).
 """
 from __future__ import annotations
 
 from .. import synth
-from ._base import HipModule
+from ._base import HipModule, RaggedMixin
 
 MIN_SAMPLES = 512           # the mel front-end's n_fft (one frame of the library's front-end)
 
@@ -27,7 +28,7 @@ def _crop_samples(audio_spec):
         return None
 
 
-class ResNetSE(HipModule):
+class ResNetSE(RaggedMixin, HipModule):
     model_kind = "resnetse"
 
     def __init__(self, nOut=256, encoder_type="ASP", att_dim=128, device=None, compute=None, max_batch=None, **kwargs):
@@ -85,6 +86,25 @@ class ResNetSE(HipModule):
         """fused waveform -> embedding (mel front-end + forward in one library call)"""
         eng = self._engine_for(wav)
         return self._batched(eng.embed_wave, wav, eng.max_batch)
+
+    # ---- ragged batches (RaggedMixin): the rows are mel frames, an utterance counted in whole groups of 8 ---------------------------
+    MIN_FRAMES = 2                  # InstanceNorm1d over one frame is the reference's own ValueError
+
+    def _ragged_geometry(self):
+        """(max_batch, row capacity) of the primary handle, from the module's own settings (no handle is built)"""
+        frames = (self._primary or self.DEFAULT_PRIMARY) // self._hop + 1
+        return self._max_batch, self._max_batch * frames
+
+    def ragged_frames(self, n_samples):
+        """rows an utterance of n_samples takes in a ragged call: its T mel frames rounded up to a multiple of 8 (the network halves the
+        frame axis three times, rounding up, so the library counts an utterance this way to keep every level within the handle's rows);
+        0 for one shorter than the front-end's FFT window, which fits no ragged call"""
+        if n_samples < self._min_samples:
+            return 0
+        return 8 * -(-(int(n_samples) // int(self._hop) + 1) // 8)
+
+    def _ragged_limits(self):
+        return f", an utterance counted as its frames rounded up to a multiple of 8; at least {self._min_samples} samples each"
 
 
 def MainModel(nOut=256, **kwargs):

@@ -1,6 +1,6 @@
 """Whole-file evaluation (num_eval = 0) on the MI355X: files/s of `ModelHandling._embed_files` over seeded files of 2 - 20 s.
 
-    python tools/ragged_bench.py [--model ECAPA_TDNN|RawNet3|Raw3_ECAPA|Conformer|TitaNet|Tita_ECAPA|RawNet2_conv|Raw_ECAPA_conv_asp] [--per-file] [--files 512] [--runs 5] [--compute bf16,f32]
+    python tools/ragged_bench.py [--model ECAPA_TDNN|RawNet3|Raw3_ECAPA|Conformer|TitaNet|Tita_ECAPA|RawNet2_conv|Raw_ECAPA_conv_asp|ResNetSE34V2] [--per-file] [--files 512] [--runs 5] [--compute bf16,f32]
                                  [--out profiles/ragged_bench.json]
 
 Default mode: the ragged path of this tree (files of different lengths share calls of the model's primary handle), plus, without a
@@ -22,7 +22,10 @@ RawNet2_conv (RawNet2 with front_proc='conv', nOut 320) and --model Raw_ECAPA_co
 `features: raw`; --compute f32,bf16,f16 or half) go to profiles/rawnet2_ragged_bench.json; for RawNet2_conv also the packed block tail
 (rn_rag_tail_part + rn_rag_gate + rn_rag_tail_apply) per block beside the fixed sliced tail (rn_tail at B * 4 <= CUs) of the blocks where
 the fixed forward takes it, from the library's per-label event times of both forwards in the same process, in algorithmic bytes per
-second."""
+second.  --model ResNetSE34V2 (nOut 256, mel features) goes to profiles/resnetse_ragged_bench.json; it has the single-call comparison and the
+kernel table too, and the packed rs_conv beside the fixed one per stage, in TFLOP/s, over the same rows in the same process: as many
+401-frame utterances as a pack of the handle holds (251 of max_batch = 256: a pack counts an utterance as 408 rows) against the
+fixed-length call at that batch size, from the library's per-label event times."""
 from __future__ import annotations
 
 import argparse
@@ -61,7 +64,7 @@ def make_files(n):
 MODELS = {"ECAPA_TDNN": "ECAPA_TDNN C=1024 nOut=192", "RawNet3": "RawNet3 nOut=320", "Raw3_ECAPA": "Raw3_ECAPA nOut=512 (ECAPA-TDNN C=512 + RawNet3)",
           "Conformer": "Conformer nOut=512", "TitaNet": "TitaNet-M nOut=320",
           "Tita_ECAPA": "Tita_ECAPA nOut=512 (ECAPA-TDNN C=512 + TitaNet-M)", "RawNet2_conv": "RawNet2 front_proc='conv' nOut=320",
-          "Raw_ECAPA_conv_asp": "Raw_ECAPA_conv_asp nOut=512 (ECAPA-TDNN C=512 + RawNet2 'conv')"}
+          "Raw_ECAPA_conv_asp": "Raw_ECAPA_conv_asp nOut=512 (ECAPA-TDNN C=512 + RawNet2 'conv')", "ResNetSE34V2": "ResNetSE34V2 nOut=256"}
 
 
 def state_dict(model):
@@ -71,6 +74,8 @@ def state_dict(model):
         return synth.synth_state_dict(synth.conformer_param_spec(512, 80), seed=5)
     if model == "TitaNet":
         return synth.synth_state_dict(synth.titanet_param_spec("m", 320), seed=5)
+    if model == "ResNetSE34V2":
+        return synth.synth_state_dict(synth.resnetse_param_spec(256, 80, "ASP"), seed=5)
     if model == "Tita_ECAPA":
         sd = {"ECAPA_TDNN." + k: v for k, v in synth.synth_state_dict(synth.ecapa_param_spec(C=512, input_norm=True), seed=5).items()}
         sd.update({"titaNet." + k: v for k, v in synth.synth_state_dict(synth.titanet_param_spec("m", 320), seed=5).items()})
@@ -97,6 +102,9 @@ def handler(compute, per_file, model="ECAPA_TDNN"):
         kw.pop("channels")
     elif model == "TitaNet":
         kw.update(model={"name": model, "nOut": 320}, model_size="m")
+        kw.pop("channels")
+    elif model == "ResNetSE34V2":
+        kw.update(model={"name": model, "nOut": 256})
         kw.pop("channels")
     elif model == "RawNet2_conv":
         kw.update(model={"name": "RawNet2_custom", "nOut": 320}, features="raw", front_proc="conv", aggregate="asp", att_dim=128)
@@ -205,6 +213,33 @@ def rawnet2_tail_rates(eng, pack, offs, lens, esz):
     return out
 
 
+def resnetse_conv_rates(eng, runs=3):
+    """rs_conv per stage, packed beside fixed, over the same rows in the same process: n utterances of the handle's own length (as many
+    as one pack holds: an utterance counts as its frames rounded up to a multiple of 8) as a features pack against the fixed-length call
+    at B = n.  Both forwards label their convolutions rs_conv3x3_s1 .. s4 and rs_down; ms and FLOP from the library's per-label events,
+    the median of `runs` profiled forwards each"""
+    T = eng.frames
+    n = min(eng.max_batch, eng.row_capacity // (8 * -(-T // 8)))
+    x = (torch.randn((n, eng.n_mels, T), device="cuda") ** 2 + 1e-3).contiguous()
+    offs, lens = np.arange(n, dtype=np.int64) * T, np.full(n, T, np.int32)
+    forms = {"fixed": lambda: eng.embed_features(x), "packed": lambda: eng.embed_features_ragged(x.reshape(-1), offsets=offs, lengths=lens)}
+    out = {"utterances": n, "frames_each": T, "stages": {}}
+    for form, call in forms.items():
+        call()
+        seen = []
+        for _ in range(runs):
+            eng.profile(True)
+            call()
+            seen.append(eng.profile_results())
+            eng.profile(False)
+        for label in ("rs_conv3x3_s1", "rs_conv3x3_s2", "rs_conv3x3_s3", "rs_conv3x3_s4", "rs_down"):
+            ms = [p[label]["ms"] for p in seen]
+            med = float(np.median(ms))
+            out["stages"].setdefault(label, {})[form] = {"ms": stats(ms), "launches": seen[0][label]["launches"],
+                                                        "TFLOPs": round(seen[0][label]["flops"] / (med * 1e-3) / 1e12, 2)}
+    return out
+
+
 def timed(fn, runs):
     fn()                                                        # untimed: handles, allocations, first launches
     wall, dev = [], []
@@ -265,12 +300,13 @@ def main():
             r["ragged_forward_kernels_ms"] = {k: {"ms": round(v["ms"], 4), "launches": v["launches"]}
                                               for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])}
             r["block_tail"] = rawnet2_tail_rates(eng, packed, offs, lens, 4 if compute in ("f32", "fp32") else 2)
-        if not a.per_file and a.model in ("ECAPA_TDNN", "Conformer", "TitaNet"):
+        if not a.per_file and a.model in ("ECAPA_TDNN", "Conformer", "TitaNet", "ResNetSE34V2"):
             eng = S.ragged_engine()
             # the ragged call against the fixed-length call of the same handle, device-resident input, frames/s of each
             x = torch.from_numpy(synth.synth_waveforms(eng.max_batch, eng.samples, seed=1)).cuda()
             pack = [torch.from_numpy(f).cuda() for f in files[:40]]
-            while sum(len(p) // 80 + 1 for p in pack) > eng.row_capacity:
+            rows_of = (lambda p: 8 * -(-(len(p) // 80 + 1) // 8)) if a.model == "ResNetSE34V2" else (lambda p: len(p) // 80 + 1)      # as a pack counts them
+            while sum(rows_of(p) for p in pack) > eng.row_capacity:
                 pack.pop()
             packed = torch.cat(pack)
             lens = [len(p) for p in pack]
@@ -291,6 +327,8 @@ def main():
             r["ragged_forward_pack"] = {"utterances": len(lens), "frames": int(sum(n // 80 + 1 for n in lens))}
             if a.model == "TitaNet":
                 r["depthwise_kernels"] = titanet_depthwise_rates([n // 80 + 1 for n in lens], compute=compute)
+            if a.model == "ResNetSE34V2":
+                r["rs_conv_packed_beside_fixed"] = resnetse_conv_rates(eng)
         res[compute] = r
         print(compute, json.dumps(r["files_per_s"]), flush=True)
         drop_engines(S)
