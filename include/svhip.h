@@ -93,9 +93,17 @@ typedef enum svhip_status {
  * Conv1d(128, 256 n_mels / 8) -> softmax over frames; weighted mean and sqrt(clamp(weighted variance, 1e-5)); fc.  channels selects the
  * pooling: 0 or 2 = encoder_type 'ASP' (mean | std, fc reads 512 n_mels / 8 values), 1 = 'SAP' (mean only); embed_dim = nOut; n_mels a
  * multiple of 8 (as for every model); compute SVHIP_F32 or SVHIP_BF16 (others: SVHIP_ERR_UNSUPPORTED).  Length: T = L / hop + 1 >= 2 frames
- * and L >= n_fft as for every model.  Weights: the 292 reference state-dict names.  Both svhip_embed_wave and svhip_embed_features. */
+ * and L >= n_fft as for every model.  Weights: the 292 reference state-dict names.  Both svhip_embed_wave and svhip_embed_features.
+ * SVHIP_MODEL_FUSION_HEAD (added under ABI v5): the attention head of Raw_ECAPA_hype (models/Raw_ECAPA_hype.py:34-45,65-86), which mixes the
+ * 704-d concatenation of its two branch embeddings: lrelu_0.3(bn_before_agg(.)), channel attention Conv1d(704, 128, 1) -> SiLU -> BatchNorm ->
+ * Conv1d(128, 704, 1) -> softmax over the 704 channels, weighted mean | std (variance clamped at 1e-9), bn_final, fc.  Like SVHIP_MODEL_NONE
+ * the handle has no waveform model: svhip_embed_* return SVHIP_ERR_UNSUPPORTED, its one forward is svhip_fusion_head.  channels = 704
+ * (anything else: SVHIP_ERR_INVALID); embed_dim = nOut >= 1; the arithmetic is fp32 whatever `compute` says.  Weights: the 21 reference
+ * state-dict names bn_before_agg.*, attention.0.{weight (128, 704, 1), bias}, attention.2.*, attention.3.{weight (704, 128, 1), bias},
+ * bn_final.* (1408), fc.{weight (nOut, 1408), bias}. */
 enum { SVHIP_MODEL_ECAPA = 0, SVHIP_MODEL_RAWNET2 = 1, SVHIP_MODEL_NONE = 2 /* fbank + scoring only */, SVHIP_MODEL_RAWNET2_CONV = 3,
-       SVHIP_MODEL_RAWNET3 = 4, SVHIP_MODEL_RAWNET2_GRU = 5, SVHIP_MODEL_TITANET = 6, SVHIP_MODEL_CONFORMER = 7, SVHIP_MODEL_RESNETSE = 8 };
+       SVHIP_MODEL_RAWNET3 = 4, SVHIP_MODEL_RAWNET2_GRU = 5, SVHIP_MODEL_TITANET = 6, SVHIP_MODEL_CONFORMER = 7, SVHIP_MODEL_RESNETSE = 8,
+       SVHIP_MODEL_FUSION_HEAD = 9 };
 enum { SVHIP_F32 = 0, SVHIP_BF16 = 1, SVHIP_I64 = 2, SVHIP_F32X3 = 3 /* compute only */, SVHIP_F16 = 4 /* compute only */ };
 enum { SVHIP_IN_DEVICE = 1, SVHIP_OUT_DEVICE = 2, SVHIP_ASYNC = 4 };
 
@@ -131,6 +139,9 @@ typedef struct svhip_config {
     float   fmax;           /* <=0 -> sr/2 */
     float   preemph;        /* 0.97; <0 disables pre-emphasis */
     void*   stream;         /* optional hipStream_t to enqueue on (NULL: the handle creates its own) */
+    int32_t sinc_sr;        /* added under ABI v5: the sample rate of RawNet2's sinc front-end (SincConv_fast's sample_rate, RawNet2_custom.py:55-67:
+                               n_ = 2 pi arange(-125, 0) / sinc_sr and the clamp high <= sinc_sr / 2); 16000 by default, 0 means 16000; svhip_create
+                               refuses a negative value and sinc_sr / 2 <= 100 (min_low_hz + min_band_hz) with SVHIP_ERR_INVALID */
 } svhip_config;
 
 /* Fill *cfg with the reference defaults (ECAPA C=1024, fp32, 80 mels, nOut 192, L=32000). */
@@ -175,6 +186,14 @@ int svhip_embed_features(svhip_handle* h, const float* feat, int32_t B, int32_t 
 /* Fused waveform -> embedding: SpeakerEncoder.forward with label=None (src/model.py:104-125):
  * compute_features then __S__.forward (ECAPA), or __S__.forward directly (RawNet2). */
 int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, float* emb_out, int32_t flags);
+
+/* The fusion head of Raw_ECAPA_hype (added under ABI v5; SVHIP_MODEL_FUSION_HEAD handles only, others: SVHIP_ERR_UNSUPPORTED).  Replaces
+ * models/Raw_ECAPA_hype.py:65-85 in eval mode: out (B, nOut) fp32 from the two branch embeddings e1 (B, d1) and e2 (B, d2), d1 + d2 == 704
+ * and 1 <= B <= max_batch (else SVHIP_ERR_INVALID).  The two inputs are separate pointers: no concatenated copy is made.  e1 / e2 / out
+ * follow `flags` like svhip_embed_wave (SVHIP_IN_DEVICE covers both inputs; SVHIP_ASYNC needs device pointers).  One kernel launch (profile
+ * label "hype_head"), fp32 on every handle; the kernel that writes `out` checks it for inf / NaN (SVHIP_ERR_NONFINITE, as after any forward).
+ * BATCH INVARIANCE: a row's output is bit for bit the same whatever B is and wherever the row sits in the batch. */
+int svhip_fusion_head(svhip_handle* h, const float* e1, int32_t d1, const float* e2, int32_t d2, int32_t B, float* out, int32_t flags);
 
 /* Ragged batches (added under ABI v5): n utterances of DIFFERENT lengths, packed back to back, embedded by one call on one handle, each
  * exactly as if it had been forwarded alone at its own length — whole-file evaluation (num_eval = 0: loadWAV returns the entire file,

@@ -22,6 +22,7 @@ MODEL_RAWNET2_GRU = 5                      # RawNet2 with front_proc='sinc', agg
 MODEL_TITANET = 6                          # TitaNet, the spectral branch of Tita_ECAPA / Raw_tita (include/svhip.h, added under ABI v5)
 MODEL_CONFORMER = 7                        # Conformer, the model of yaml/model_plot.yaml (include/svhip.h, added under ABI v5)
 MODEL_RESNETSE = 8                         # ResNetSE34V2, the 2-D SE-ResNet baseline (include/svhip.h, added under ABI v5)
+MODEL_FUSION_HEAD = 9                      # the attention head of Raw_ECAPA_hype: no waveform model, svhip_fusion_head (include/svhip.h, added under ABI v5)
 F32, BF16, I64, F32X3, F16 = 0, 1, 2, 3, 4
 IN_DEVICE, OUT_DEVICE, ASYNC = 1, 2, 4
 TRIAL_COSINE, TRIAL_PNORM, TRIAL_PDIST = 0, 1, 2
@@ -51,6 +52,7 @@ class Config(C.Structure):
         ("fb_sr", C.c_int32), ("n_fft", C.c_int32), ("win_length", C.c_int32), ("hop_length", C.c_int32),
         ("fmin", C.c_float), ("fmax", C.c_float), ("preemph", C.c_float),
         ("stream", C.c_void_p),
+        ("sinc_sr", C.c_int32),             # added under ABI v5: the sample rate of RawNet2's sinc front-end (16000; 0 means 16000)
     ]
 
 
@@ -69,6 +71,7 @@ _SIGNATURES = {
     "svhip_fbank": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "svhip_embed_features": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "svhip_embed_wave": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "svhip_fusion_head": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "svhip_embed_wave_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32]),
     "svhip_embed_features_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32]),
     "svhip_ragged_check": (C.c_int, [C.POINTER(Config), _P, C.c_int32, C.c_int32]),

@@ -27,7 +27,8 @@ _MODEL_IDS = {"ECAPA_TDNN": _lib.MODEL_ECAPA, "ecapa": _lib.MODEL_ECAPA, "RawNet
               "RawNet2_custom_gru": _lib.MODEL_RAWNET2_GRU, "rawnet2_gru": _lib.MODEL_RAWNET2_GRU,
               "RawNet3": _lib.MODEL_RAWNET3, "rawnet3": _lib.MODEL_RAWNET3, "TitaNet": _lib.MODEL_TITANET, "titanet": _lib.MODEL_TITANET,
               "Conformer": _lib.MODEL_CONFORMER, "conformer": _lib.MODEL_CONFORMER,
-              "ResNetSE34V2": _lib.MODEL_RESNETSE, "resnetse": _lib.MODEL_RESNETSE}
+              "ResNetSE34V2": _lib.MODEL_RESNETSE, "resnetse": _lib.MODEL_RESNETSE,
+              "Raw_ECAPA_hype_head": _lib.MODEL_FUSION_HEAD, "fusion_head": _lib.MODEL_FUSION_HEAD}
 
 
 def model_id(model) -> int:
@@ -149,12 +150,16 @@ FUSION_MODELS = {
     # Tita_ECAPA.py: ECAPA + TitaNet-M (attribute `titaNet`); Raw_tita.py: TitaNet-M, then RawNet2 'sinc' / asp (attribute `RawNet`)
     "Tita_ECAPA": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("titaNet.", "TitaNet", ".titanet")),
     "Raw_tita": (("titaNet.", "TitaNet", ".titanet"), ("RawNet.", "RawNet2_custom", ".rawnet2")),
+    # Raw_ECAPA_hype.py: ECAPA + RawNet2 'sinc' / gru (nOut 512), then the attention head whose 21 tensors sit at the top level of the
+    # state dict (prefix ""): a third blob, model id SVHIP_MODEL_FUSION_HEAD
+    "Raw_ECAPA_hype": (("ECAPA_TDNN.", "ECAPA_TDNN", ".ecapa"), ("rawnet2v2.", "RawNet2_custom_gru", ".rawnet2"),
+                       ("", "Raw_ECAPA_hype_head", ".head")),
 }
 _BRANCH_PREFIXES = ("ECAPA_TDNN.", "rawnet2v2.", "rawnet.", "titaNet.", "RawNet.")
 
 
 def fusion_blob_paths(dst, model="Raw_ECAPA_sinc_asp"):
-    """the two branch blobs a fusion checkpoint converts to: (ECAPA path, RawNet2 path)"""
+    """the branch blobs a fusion checkpoint converts to: (ECAPA path, RawNet2 path), and for Raw_ECAPA_hype the head's as a third"""
     return tuple(str(dst) + suffix for _, _, suffix in FUSION_MODELS[model])
 
 
@@ -164,7 +169,8 @@ def convert_checkpoint(src, dst, model) -> int:
     A fusion checkpoint (``model`` one of FUSION_MODELS — ``Raw_ECAPA_sinc_asp``, ``Raw_ECAPA``, ``Raw_ECAPA_conv_asp``: keys
     ``__S__.ECAPA_TDNN.*`` / ``__S__.rawnet2v2.*``, Raw_ECAPA*.py:22-28) becomes one blob per branch, ``dst + '.ecapa'`` and ``dst + '.rawnet2'`` — a handle is one
     network, and ``Raw_ECAPA.load_blob(dst)`` reads the pair back.  ``Raw3_ECAPA`` (keys ``__S__.ECAPA_TDNN.*`` / ``__S__.rawnet.*``)
-    writes ``dst + '.ecapa'`` and ``dst + '.rawnet3'``."""
+    writes ``dst + '.ecapa'`` and ``dst + '.rawnet3'``; ``Raw_ECAPA_hype`` writes ``dst + '.ecapa'``, ``dst + '.rawnet2'`` and, for the 21
+    tensors of its attention head, ``dst + '.head'``."""
     if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
         import torch  # host-side only: the one place a pickle is read
         state = torch.load(src, map_location="cpu")     # the reference's 'cpu:0' is rejected by current torch (DESIGN.md §2)
@@ -174,7 +180,7 @@ def convert_checkpoint(src, dst, model) -> int:
         state = src
     sd = embedding_state_dict(state)
     if model in FUSION_MODELS:
-        mine = tuple(prefix for prefix, _, _ in FUSION_MODELS[model])
+        mine = tuple(prefix for prefix, _, _ in FUSION_MODELS[model] if prefix)
         foreign = sorted({p for p in _BRANCH_PREFIXES if p not in mine and any(k.startswith(p) for k in sd)})
         if foreign and ("titaNet." in mine or "titaNet." in foreign):    # a TitaNet fusion checkpoint as another fusion model, or the other way round
             raise ValueError(f"{model}: the checkpoint holds {foreign[0]}* tensors, a branch this model does not have (its branches: {list(mine)})")
@@ -200,9 +206,13 @@ def convert_checkpoint(src, dst, model) -> int:
                                  "(rawnet2v2.attention.*), not a GRU")
         total = 0
         for prefix, branch, suffix in FUSION_MODELS[model]:
-            sub = OrderedDict((k[len(prefix):], v) for k, v in sd.items() if k.startswith(prefix))
+            if prefix:
+                sub = OrderedDict((k[len(prefix):], v) for k, v in sd.items() if k.startswith(prefix))
+            else:       # the head: what sits at the top level, beside the branches and the front-end's buffers
+                sub = OrderedDict((k, v) for k, v in sd.items() if not k.startswith(_BRANCH_PREFIXES + ("compute_features.",)))
             if not sub:
-                raise ValueError(f"{model}: the checkpoint holds no '{prefix}*' tensors")
+                raise ValueError(f"{model}: the checkpoint holds no '{prefix}*' tensors" if prefix else
+                                 f"{model}: the checkpoint holds no head tensors (bn_before_agg.*, attention.*, bn_final.*, fc.*)")
             write_blob(str(dst) + suffix, branch, sub)
             total += len(sub)
         return total
@@ -223,7 +233,7 @@ def main(argv=None):
     ap.add_argument("src")
     ap.add_argument("dst")
     ap.add_argument("--model", default="ECAPA_TDNN", help="reference model name (ECAPA_TDNN, RawNet2_custom, RawNet2_custom_conv, RawNet2_custom_gru, "
-                    "RawNet3, TitaNet, Conformer, ResNetSE34V2, Raw_ECAPA_sinc_asp, Raw_ECAPA_sinc_gru, Raw_ECAPA, Raw_ECAPA_conv_asp, Raw3_ECAPA, Tita_ECAPA, Raw_tita)")
+                    "RawNet3, TitaNet, Conformer, ResNetSE34V2, Raw_ECAPA_sinc_asp, Raw_ECAPA_sinc_gru, Raw_ECAPA, Raw_ECAPA_conv_asp, Raw_ECAPA_hype, Raw3_ECAPA, Tita_ECAPA, Raw_tita)")
     a = ap.parse_args(argv)
     n = convert_checkpoint(a.src, a.dst, a.model)
     print(f"{a.dst}: {n} tensors")

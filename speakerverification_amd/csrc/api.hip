@@ -80,6 +80,7 @@ const ModelOps kModels[] = {
     {SVHIP_MODEL_RESNETSE,     resnetse_check,  resnetse_spec,  resnetse_finalize,  resnetse_alloc,  fbank_then_features, resnetse_forward,  resnetse_stage,  4,
      nullptr, resnetse_ragged_check, resnetse_embed_ragged},
     {SVHIP_MODEL_NONE,         none_check,      nullptr,        nullptr,            nullptr,         nullptr,             nullptr,           nullptr,         1},   // fbank + scoring
+    {SVHIP_MODEL_FUSION_HEAD,  fusion_head_check, fusion_head_spec, fusion_head_finalize, fusion_head_alloc, nullptr,     nullptr,           nullptr,         1},   // svhip_fusion_head
 };
 
 const ModelOps* model_ops(int model) {
@@ -287,6 +288,7 @@ void svhip_default_config(svhip_config* c) {
     c->fb_sr = 8000; c->n_fft = 512; c->win_length = 200; c->hop_length = 80;
     c->fmin = 0.0f; c->fmax = -1.0f; c->preemph = 0.97f;
     c->stream = nullptr;
+    c->sinc_sr = 16000;
 }
 
 int svhip_abi_version(void) { return SVHIP_ABI_VERSION; }
@@ -305,6 +307,8 @@ int svhip_create(const svhip_config* cfg, svhip_handle** out) {
     const char* msg = "";
     if (int rc = m->check(*cfg, msg)) { g_create_error = msg; return rc; }
     if (cfg->compute != SVHIP_F32 && cfg->compute != SVHIP_BF16 && cfg->compute != SVHIP_F32X3 && cfg->compute != SVHIP_F16) { g_create_error = "unknown compute mode"; return SVHIP_ERR_INVALID; }
+    // the sinc front-end's sample rate (0: 16000): min_low_hz + min_band_hz = 100 Hz must lie below the clamp at sinc_sr / 2
+    if (cfg->sinc_sr < 0 || (cfg->sinc_sr ? cfg->sinc_sr : 16000) / 2 <= 100) { g_create_error = "bad sinc_sr: the sinc front-end needs sinc_sr / 2 > 100 Hz (0 means 16000)"; return SVHIP_ERR_INVALID; }
     if (cfg->n_mels <= 0 || cfg->n_mels % 8 != 0 || cfg->max_batch <= 0 || cfg->samples < cfg->n_fft || cfg->hop_length <= 0) { g_create_error = "bad n_mels / max_batch / samples"; return SVHIP_ERR_INVALID; }
     if ((e = hipSetDevice(cfg->device)) != hipSuccess) { g_create_error = hipGetErrorString(e); return SVHIP_ERR_HIP; }
     svhip_handle* h = new svhip_handle();
@@ -510,6 +514,22 @@ int svhip_embed_wave(svhip_handle* h, const float* wav, int32_t B, int32_t L, fl
     }
     if ((rc = m->embed_wave(h, d_in, B))) return rc;
     if ((rc = emit_embeddings(h, B, emb_out, flags))) return rc;
+    return finish(h, flags);
+}
+
+int svhip_fusion_head(svhip_handle* h, const float* e1, int32_t d1, const float* e2, int32_t d2, int32_t B, float* out, int32_t flags) {
+    int rc = check_ready(h, B);
+    if (rc) return rc;
+    if (h->cfg.model != SVHIP_MODEL_FUSION_HEAD) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "svhip_fusion_head needs a SVHIP_MODEL_FUSION_HEAD handle, this handle is model %d", h->cfg.model);
+    if (!e1 || !e2 || !out) SV_FAIL(h, SVHIP_ERR_INVALID, "null pointer");
+    if (d1 < 1 || d2 < 1 || d1 + d2 != HYPE_HEAD_C) SV_FAIL(h, SVHIP_ERR_INVALID, "d1 + d2 = %d + %d, the head mixes %d channels", d1, d2, HYPE_HEAD_C);
+    if ((flags & SVHIP_ASYNC) && (flags & (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE)) != (SVHIP_IN_DEVICE | SVHIP_OUT_DEVICE))
+        SV_FAIL(h, SVHIP_ERR_INVALID, "SVHIP_ASYNC needs device pointers");
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    float* d_out = (flags & SVHIP_OUT_DEVICE) ? out : h->d_emb;
+    if ((rc = fusion_head_forward(h, e1, d1, e2, d2, B, !(flags & SVHIP_IN_DEVICE), d_out))) return rc;
+    if (!(flags & SVHIP_OUT_DEVICE)) SV_HIP(h, hipMemcpyAsync(out, d_out, (size_t)B * h->cfg.embed_dim * 4, hipMemcpyDeviceToHost, h->stream));
+    h->lastB = 0;          // (no stages)
     return finish(h, flags);
 }
 

@@ -134,19 +134,20 @@ static int rn_conv(svhip_handle* h, ConvLayer& L, const std::string& w, const st
     return make_conv(h, L, w, b, bn, 1, 0, -1, true);
 }
 
-// sinc band-pass filters baked once per weight load (RawNet_baseline.py:313-318,339-357), float32 arithmetic
+// sinc band-pass filters baked once per weight load (RawNet_baseline.py:313-318,339-357), float32 arithmetic, at the handle's sample
+// rate (cfg.sinc_sr; SincConv_fast's sample_rate: the time axis n_ and the clamp of the upper band edge at sr / 2)
 static int bake_sinc(svhip_handle* h) {
     auto& s = S(h);
     const HostTensor *lo = getw(h, "first_conv.low_hz_"), *bd = getw(h, "first_conv.band_hz_");
     if (!lo || !bd) SV_FAIL(h, SVHIP_ERR_MISSING, "missing sinc parameters");
     const int NF = 128, KS = 251, HALF = 125;
-    const float sr = 16000.0f, min_low = 50.0f, min_band = 50.0f;
+    const float sr = (float)(h->cfg.sinc_sr ? h->cfg.sinc_sr : 16000), min_low = 50.0f, min_band = 50.0f;
     const float PI = 3.14159265358979323846f;
     std::vector<float> win(HALF), n_(HALF);
     for (int i = 0; i < HALF; ++i) {
         const float n_lin = (float)(124.5 * i / 124.0);                         // torch.linspace(0, 124.5, 125)
         win[i] = 0.54f - 0.46f * std::cos(2.0f * PI * n_lin / (float)KS);
-        n_[i] = 2.0f * PI * (float)(-125 + i) / sr;                             // 2*pi*arange(-125, 0)/16000
+        n_[i] = 2.0f * PI * (float)(-125 + i) / sr;                             // 2*pi*arange(-125, 0)/sample_rate
     }
     std::vector<float> filt((size_t)NF * KS);
     for (int f = 0; f < NF; ++f) {

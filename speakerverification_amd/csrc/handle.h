@@ -380,5 +380,10 @@ HandleFn ecapa_alloc, rawnet2_alloc, rawnet3_alloc, titanet_alloc, conformer_all
 EmbedFn ecapa_embed_wave, rawnet2_forward, rawnet3_forward;                    // from the waveform
 EmbedFn ecapa_forward, titanet_forward, conformer_forward, resnetse_forward;   // from the mel power
 StageFn ecapa_stage, rawnet2_stage, rawnet3_stage, titanet_stage, conformer_stage, resnetse_stage;
+// api_fusionhead.hip: the attention head of Raw_ECAPA_hype, a handle kind without a waveform model (no embed hooks, no stages)
+CheckFn fusion_head_check;
+SpecFn fusion_head_spec;
+HandleFn fusion_head_finalize, fusion_head_alloc;
+int fusion_head_forward(svhip_handle* h, const float* e1, int d1, const float* e2, int d2, int B, bool in_host, float* d_out);
 
 }  // namespace svhip

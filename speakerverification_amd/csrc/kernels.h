@@ -278,6 +278,22 @@ hipError_t launch_rowvec_linear(const float* in, int ld_in, const float* W, cons
 // the embeddings leave the workspace (dst == src: no copy) and the call's numeric status is recorded: a non-finite value raises bit 0 of
 // status[0], is counted in status[1] and sets *host_flag (mapped pinned memory).  SVHIP_STATUS_* bits: api.hip
 hipError_t launch_emb_out(const float* src, float* dst, int n, uint32_t* status, uint32_t* host_flag, hipStream_t stream);
+
+// The attention head of Raw_ECAPA_hype (fusion_head.hip): out (B, nOut) from the branch embeddings e1 (B, d1) | e2 (B, d2), d1 + d2 ==
+// HYPE_HEAD_C, in one launch, fp32.  s0 / t0, s2 / t2, sF / tF: bn_before_agg, attention.2 and bn_final folded to scale / shift; the
+// weights K-major: W0t [704][128] = attention.0, W3t [128][704] = attention.3, Wft [1408][nOutP] = fc with the rows padded with zeros to
+// nOutP = nOut rounded up to 4.  The kernel checks what it writes for inf / NaN (status / host_flag as launch_emb_out).  A row's output
+// does not depend on B or on its place in the batch, bit for bit.
+constexpr int HYPE_HEAD_C = 704, HYPE_HEAD_A = 128, HYPE_HEAD_UT = 4, HYPE_HEAD_COLS = 128;       // channels, attention width; utterances and output columns per workgroup
+struct HypeHeadParams {
+    const float *e1, *e2;
+    int d1, d2, B, nOut, nOutP;
+    const float *s0, *t0, *W0t, *b0, *s2, *t2, *W3t, *b3, *sF, *tF, *Wft, *bf;
+    float* out;
+    uint32_t* status;
+    volatile uint32_t* host_flag;
+};
+hipError_t launch_hype_head(const HypeHeadParams& p, hipStream_t stream);
 // s[b, :] = sigmoid(W2 relu(W1 mean[b, :] + b1) + b2); W1 [H][C], W2T = W2 transposed [H][C]
 hipError_t launch_se_mlp(const float* mean, const float* part, int T, const void* W1, const float* b1, const void* W2T,
                          const float* b2, float* s, bool w_bf16, int B, int C, int H, hipStream_t stream, int row_groups = 8);

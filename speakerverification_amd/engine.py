@@ -103,8 +103,11 @@ _RAGGED = {
 class Engine:
     def __init__(self, model="ecapa", compute="f32", channels=1024, n_mels=80, embed_dim=192, max_batch=8,
                  samples=32000, log_input=True, input_norm=False, device=0, stream=None,
-                 sr=8000, n_fft=512, win_length=200, hop_length=80, fmin=0.0, fmax=None, pre_emphasis=True, on_numeric="raise"):
-        """``on_numeric``: what a forward does when the library reports SVHIP_ERR_NONFINITE / SVHIP_ERR_RANGE (the outputs were written,
+                 sr=8000, n_fft=512, win_length=200, hop_length=80, fmin=0.0, fmax=None, pre_emphasis=True, on_numeric="raise",
+                 sinc_sr=16000):
+        """``sinc_sr``: the sample rate of RawNet2's sinc front-end (the reference's ``audio_spec['sample_rate']``, RawNet2_custom.py:55-67).
+        ``model="fusion_head"``: the attention head of Raw_ECAPA_hype (``channels=704``, ``embed_dim=nOut``; ``fusion_head`` is its forward).
+        ``on_numeric``: what a forward does when the library reports SVHIP_ERR_NONFINITE / SVHIP_ERR_RANGE (the outputs were written,
         but an fp16 activation overflowed / the input left an f32x3 handle's range / the input was not finite): "raise"
         (_lib.SvhipNumericError, default), "warn" (RuntimeWarning; the outputs are returned as computed, as the reference would) or "ignore"."""
         if on_numeric not in ("raise", "warn", "ignore"):
@@ -114,7 +117,8 @@ class Engine:
         cfg = _lib.default_config()
         cfg.model = {"ecapa": _lib.MODEL_ECAPA, "rawnet2": _lib.MODEL_RAWNET2, "rawnet2_conv": _lib.MODEL_RAWNET2_CONV,
                      "rawnet2_gru": _lib.MODEL_RAWNET2_GRU, "rawnet3": _lib.MODEL_RAWNET3, "titanet": _lib.MODEL_TITANET,
-                     "conformer": _lib.MODEL_CONFORMER, "resnetse": _lib.MODEL_RESNETSE, "none": _lib.MODEL_NONE}[model]
+                     "conformer": _lib.MODEL_CONFORMER, "resnetse": _lib.MODEL_RESNETSE, "none": _lib.MODEL_NONE,
+                     "fusion_head": _lib.MODEL_FUSION_HEAD}[model]
         cfg.compute = {"f32": _lib.F32, "fp32": _lib.F32, "bf16": _lib.BF16, "f32x3": _lib.F32X3, "bf16x3": _lib.F32X3,
                        "f16": _lib.F16, "fp16": _lib.F16}[compute]
         cfg.device = int(device)
@@ -130,6 +134,7 @@ class Engine:
         cfg.fmax = -1.0 if fmax is None else float(fmax)
         cfg.preemph = 0.97 if pre_emphasis is True else (-1.0 if pre_emphasis in (False, None) else float(pre_emphasis))
         cfg.stream = C.c_void_p(int(stream)) if stream else None
+        cfg.sinc_sr = int(sinc_sr)
         self.cfg = cfg
         self.model = model
         self.compute = {_lib.BF16: "bf16", _lib.F32X3: "f32x3", _lib.F16: "f16"}.get(cfg.compute, "f32")
@@ -263,6 +268,23 @@ class Engine:
         self._order_after_torch(i, o, async_=async_, ordered=ordered)
         _count([i], [o])
         self._ck(self.lib.svhip_embed_wave(self.h, i.ptr, B, L, o.ptr, self._flags(i, o, async_)))
+        return out
+
+    def fusion_head(self, e1, e2, out=None, async_=False, ordered=False):
+        """``model="fusion_head"`` handles: the two branch embeddings (B, d1) and (B, d2), d1 + d2 == 704, as separate arrays -> (B, embed_dim)
+        (svhip_fusion_head; numpy in -> numpy out, CUDA tensors in -> CUDA tensor out).  ``ordered``: as in embed_wave."""
+        B, d1 = e1.shape
+        B2, d2 = e2.shape
+        if B2 != B:
+            raise ValueError(f"the branch embeddings have {B} and {B2} rows")
+        if out is None:
+            out = self._out(e1, (B, self.embed_dim))
+        i1, i2, o = _Buf(e1, np.float32), _Buf(e2, np.float32), _Buf(out, np.float32, writable=True)
+        if i1.device != i2.device:
+            raise ValueError("both branch embeddings must live in the same memory space")
+        self._order_after_torch(i1, i2, o, async_=async_, ordered=ordered)
+        _count([i1, i2], [o])
+        self._ck(self.lib.svhip_fusion_head(self.h, i1.ptr, d1, i2.ptr, d2, B, o.ptr, self._flags(i1, o, async_)))
         return out
 
     # ---- ragged batches: utterances of different lengths in one call (_RAGGED names the model's exports) ----

@@ -9,7 +9,8 @@ the fusion models and configs instantiate: ``aggregate='asp'``, ``att_dim=128`` 
 State-dict keys are the reference's: 147 tensors for 'sinc' (the band-pass filters are rebuilt from
 ``first_conv.low_hz_`` / ``band_hz_`` once per weight load instead of once per forward), 140 for 'conv'
 (``conv1.weight`` / ``conv1.bias``), 144 for 'sinc' + 'gru' (``bn_before_gru``, ``gru.*``, ``fc_after_gru``;
-``fc`` is built and never used, as in the reference).  The sinc form's LayerNorm(nb_samp) fixes the input length; the conv
+``fc`` is built and never used, as in the reference).  The sinc filters are baked at ``audio_spec['sample_rate']``, as the
+reference's SincConv_fast builds them (RawNet2_custom.py:55-67; 8000 in every saved experiment).  The sinc form's LayerNorm(nb_samp) fixes the input length; the conv
 form takes any length L >= 2187 (one library handle per length, the configured crop length with the
 full batch workspace) and, alone of the three, offers ``embed_ragged``: utterances of different lengths in shared calls of the
 primary handle (whole-file evaluation; ``RawNet2Conv``).
@@ -49,8 +50,6 @@ class RawNet2(HipModule):
             self.nb_samp = spec_samples
         else:
             audio_spec = audio_spec or {"sample_rate": 16000, "sentence_len": 2.0}
-            if int(audio_spec["sample_rate"]) != 16000:
-                raise NotImplementedError("the sinc front-end is built for sample_rate 16000 (RawNet2_custom.py:55-63)")
             self.nb_samp = int(audio_spec["sentence_len"] * audio_spec["sample_rate"])      # LayerNorm(nb_samp), :58-60
         # hip_compute: "f32" (exact fp32 MFMA) | "f32x3" | "f16" (fp16 storage + fp16 MFMA: RawNet2's fast mode) | "bf16" (the same
         # kernels on bf16: range-safe, but RawNet2 loses two digits to bf16 weight rounding) | "half" = this model's 16-bit mode (f16)
@@ -62,10 +61,12 @@ class RawNet2(HipModule):
         # ill-scaled one of tests/test_gpu_rawnet2.py), so it is not the default
         self._range_fallback = kwargs.get("range_fallback", "f32")
         max_batch = int(max_batch or kwargs.get("embed_batch", 256))
+        # SincConv_fast takes audio_spec['sample_rate'] (RawNet2_custom.py:55-67): the handle bakes its filters at that rate
+        sinc_sr = int(audio_spec["sample_rate"]) if front_proc == "sinc" else 16000
         super().__init__(synth.rawnet2_param_spec(nOut=nOut, nb_samp=self.nb_samp or 0, att_dim=att_dim, front_proc=front_proc,
                                                   aggregate=aggregate),
-                         dict(embed_dim=nOut), device=device if device is not None else kwargs.get("device"),
-                         compute=compute, max_batch=max_batch, primary_samples=self.nb_samp)
+                         dict(embed_dim=nOut, sinc_sr=sinc_sr), device=device if device is not None else kwargs.get("device"),
+                         compute=compute, max_batch=max_batch, primary_samples=self.nb_samp, sample_rate=sinc_sr)
 
     def _check_input(self, x):
         """-> the input length; raises ValueError (before any handle is made) for a shape this module cannot run"""

@@ -33,10 +33,11 @@ class HipModule:
     accepts_device_wave = True      # forward / embed_wave take CUDA tensors as raw device pointers (no host copy)
     ENGINE_CACHE = 3                # handles kept alive at once (one per input geometry)
 
-    def __init__(self, spec, engine_kwargs, device=None, compute="f32", max_batch=256, seed=0, primary_samples=None):
+    def __init__(self, spec, engine_kwargs, device=None, compute="f32", max_batch=256, seed=0, primary_samples=None, sample_rate=16000):
         from .. import synth
         self._spec = OrderedDict((n, tuple(s)) for n, s in spec)
-        self._sd = synth.synth_state_dict(spec, seed=seed)        # random init, like a fresh nn.Module
+        # random init, like a fresh nn.Module (sample_rate: where a sinc front-end's band edges start, RawNet_baseline.py:296-310)
+        self._sd = synth.synth_state_dict(spec, seed=seed, sample_rate=sample_rate)
         self._engine_kwargs = dict(engine_kwargs)
         self._compute = compute
         self._max_batch = int(max_batch)

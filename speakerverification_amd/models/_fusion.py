@@ -6,6 +6,7 @@ waveform, concatenated with a raw-waveform network (nOut - 192 dims).  They diff
     Raw_ECAPA             True               RawNet2 'sinc' / asp (rawnet2v2)
     Raw_ECAPA_sinc_asp    False              RawNet2 'sinc' / asp (rawnet2v2)
     Raw_ECAPA_sinc_gru    False              RawNet2 'sinc' / gru (rawnet2v2)
+    Raw_ECAPA_hype        True               RawNet2 'sinc' / gru, 512-d (rawnet2v2); an attention head instead of the concatenation
     Raw_ECAPA_conv_asp    True               RawNet2 'conv' / asp (rawnet2v2)
     Raw3_ECAPA            True               RawNet3 (rawnet)
     Tita_ECAPA            True               TitaNet-M on the same mel spectrogram (titaNet)
@@ -111,7 +112,7 @@ class RawECAPAFusion:
         lacks a tensor this module needs (an ECAPA blob without instance_norm.* for a model with input_norm) raises the library's
         SVHIP_ERR_MISSING instead of running on the initial values."""
         from .. import checkpoint, _lib
-        p_ecapa, p_raw = checkpoint.fusion_blob_paths(path, self.MODEL_NAME)
+        p_ecapa, p_raw = checkpoint.fusion_blob_paths(path, self.MODEL_NAME)[:2]
         if not os.path.exists(p_raw):
             raise ValueError(f"{self.MODEL_NAME}: no {p_raw} beside {path}: the pair was converted for another fusion model "
                              "(RawNet2 and RawNet3 branches are written as .rawnet2 / .rawnet3)")
@@ -129,21 +130,23 @@ class RawECAPAFusion:
             e2 = self._raw._engine_for(x)
             if x.shape[0] <= min(e1.max_batch, e2.max_batch) and x.dtype == torch.float32 and x.is_contiguous():
                 torch.cuda.current_stream(x.device).synchronize()          # x is complete before either handle reads it
-                out = torch.empty((x.shape[0], e1.embed_dim + e2.embed_dim), device=x.device, dtype=torch.float32)
                 o1 = torch.empty((x.shape[0], e1.embed_dim), device=x.device, dtype=torch.float32)
                 o2 = torch.empty((x.shape[0], e2.embed_dim), device=x.device, dtype=torch.float32)
                 e1.embed_wave(x, out=o1, async_=True, ordered=True)       # compute_features + ECAPA_TDNN (Raw_ECAPA_sinc_asp.py:41-44)
                 e2.embed_wave(x, out=o2, async_=True, ordered=True)       # :48
                 e1.synchronize()
                 e2.synchronize()
-                out[:, :e1.embed_dim] = o1                                 # torch.cat([out1, out2], dim=-1)   :50
-                out[:, e1.embed_dim:] = o2
-                return out.squeeze()
+                return self._combine(o1, o2).squeeze()
         out1 = self._first.embed_wave(x)              # compute_features + ECAPA_TDNN (Raw_ECAPA_sinc_asp.py:41-44)
         out2 = self._raw_forward(x)                   # :48
-        if _is_torch(out1):
-            return torch.cat([out1, out2], dim=-1)    # :50
-        return np.concatenate([out1, out2], axis=-1)
+        return self._combine(out1, out2)
+
+    def _combine(self, o1, o2):
+        """what the model makes of its two branch outputs (CUDA tensors, complete, or numpy arrays; (B, d) or, squeezed, (d,)): the
+        concatenation, torch.cat([out1, out2], dim=-1) (Raw_ECAPA_sinc_asp.py:50).  Raw_ECAPA_hype puts its attention head here."""
+        if _is_torch(o1):
+            return torch.cat([o1, o2], dim=-1)
+        return np.concatenate([o1, o2], axis=-1)
 
     __call__ = forward
 

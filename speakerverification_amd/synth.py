@@ -35,6 +35,8 @@ RAWNET2_FILTERS = (128, 128, 256, 256, 512, 512)       # RawNet2_custom.py:232
 RAWNET2_SINC_K = 251                                   # RawNet2_custom.py:36
 RAWNET2_GRU_NODE = 1024                                # gru_node (RawNet2_custom.py:31)
 
+HYPE_CONTEXT = 512 + 192                               # Raw_ECAPA_hype.py:20: the RawNet2 and ECAPA-TDNN embeddings side by side
+
 RAWNET3_C = 1024                                       # RawNet3.py:10 (C; no config sets it)
 RAWNET3_SCALE = 8                                      # model_scale (RawNet3.py:178)
 RAWNET3_DILATIONS = (2, 3, 4)                          # RawNet3.py:46-52
@@ -122,6 +124,19 @@ def rawnet2_param_spec(nOut=320, nb_samp=32000, att_dim=128, front_proc="sinc", 
     spec += _bn("attention.2", att_dim)
     spec += [("attention.3.weight", (f[5], att_dim, 1)), ("attention.3.bias", (f[5],)),
              ("fc.weight", (nOut, 2 * f[5])), ("fc.bias", (nOut,))]
+    return spec
+
+
+def hype_head_param_spec(nOut=512):
+    """Ordered (name, shape) list of the attention head of the reference's ``Raw_ECAPA_hype`` (Raw_ECAPA_hype.py:34-44): the 21 tensors
+    its state dict holds beside ``ECAPA_TDNN.*``, ``rawnet2v2.*`` and ``compute_features.*``, in its key order"""
+    C, A = HYPE_CONTEXT, ATT_CHANNELS
+    spec = _bn("bn_before_agg", C)
+    spec += [("attention.0.weight", (A, C, 1)), ("attention.0.bias", (A,))]
+    spec += _bn("attention.2", A)
+    spec += [("attention.3.weight", (C, A, 1)), ("attention.3.bias", (C,))]
+    spec += _bn("bn_final", 2 * C)
+    spec += [("fc.weight", (nOut, 2 * C)), ("fc.bias", (nOut,))]
     return spec
 
 
@@ -370,12 +385,13 @@ def _sinc_init(n_filt, sample_rate=16000, min_low_hz=50, min_band_hz=50):
     return hz[:-1].astype(np.float32), np.diff(hz).astype(np.float32)
 
 
-def synth_state_dict(spec, seed=1):
+def synth_state_dict(spec, seed=1, sample_rate=16000):
     """Deterministic non-trivial weights (numpy float32 / int64) in ``spec`` order.
 
     Conv / linear weights are He-scaled so activations stay O(1) through the stack; BatchNorm
     running statistics and affine terms are randomised so that BN cannot be mistaken for the
-    identity; sinc band edges start from the reference initialisation plus jitter.
+    identity; sinc band edges start from the reference initialisation at ``sample_rate`` (SincConv_fast's argument,
+    RawNet_baseline.py:296-310) plus jitter.
     """
     rng = np.random.Generator(np.random.PCG64(seed))
     sd = OrderedDict()
@@ -402,7 +418,7 @@ def synth_state_dict(spec, seed=1):
         elif leaf in ("window_", "n_"):                        # ParamSincFB's persistent buffers
             sd[name] = rawnet3_sinc_buffers()[0 if leaf == "window_" else 1].reshape(shape)
         elif leaf in ("low_hz_", "band_hz_"):
-            lo, band = _sinc_init(shape[0])
+            lo, band = _sinc_init(shape[0], sample_rate)
             base = lo if leaf == "low_hz_" else band
             jitter = rng.uniform(-3.0, 3.0, shape[0]).astype(np.float32)
             sd[name] = (base + jitter).reshape(shape).astype(np.float32)
