@@ -507,7 +507,7 @@ int svhip_profile_get(svhip_handle* h, int32_t idx, char* name, int32_t name_cap
 double svhip_workload_flops(const svhip_handle* h);
 /* Developer / test options (not part of the reference's surface).  The SVHIP_<NAME> environment variables are read ONCE, by
  * svhip_create, as a new handle's defaults; afterwards only this call changes them — no getenv on the hot path.  Names:
- * "pw3_cus" (cap of the persistent GEMM grids; 0: off), "rn_unfused", "rn_stop", "rn_snap", "asp_v1", "r2_big", "x3_keep_f32",
+ * "pw3_cus" (cap of the persistent GEMM grids; 0: off), "rn_unfused", "asp_v1", "r2_big", "x3_keep_f32",
  * "asnorm_slab", "asnorm_f32mfma", "asnorm_norefit", "score_f32mfma", "score_tiled", "fbank32", "fbank_unfused", "rn_sinc_full", "cv_off",
  * "pw3_tail_off", "n128_off", "r2_slices", "rn_tail_big", "rn_sinc_f32", "rn_step_off", "rn_pool_off", "layer_labels", "rn_conv_unfused",
  * "rn_keep".

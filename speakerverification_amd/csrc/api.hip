@@ -31,8 +31,6 @@ const DevOptRow kDevOpts[] = {
     SV_OPT(x3_keep_f32, "SVHIP_X3_KEEP_F32", OPT_SET, 0),
     SV_OPT(r2_big, "SVHIP_R2_BIG", OPT_IS1, 0),
     SV_OPT(asp_v1, "SVHIP_ASP_V1", OPT_IS1, 0),
-    SV_OPT(rn_stop, "SVHIP_RN_STOP", OPT_NUM, -1),
-    SV_OPT(rn_snap, "SVHIP_RN_SNAP", OPT_NUM, -1),
     SV_OPT(rn_unfused, "SVHIP_RN_UNFUSED", OPT_SET, 0),
     SV_OPT(asnorm_slab, "SVHIP_ASNORM_SLAB", OPT_SET, 0),
     SV_OPT(asnorm_f32mfma, "SVHIP_ASNORM_F32MFMA", OPT_SET, 0),

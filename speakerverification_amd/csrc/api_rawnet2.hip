@@ -54,12 +54,9 @@ struct RawNet2State : ModelState {
     float *stats = nullptr, *mean = nullptr, *gate = nullptr, *logits = nullptr, *pooled = nullptr;
     float* part = nullptr;             // fused 128-channel blocks: per-tile column sums (B, ntiles, 128)
     int T1 = 0;
-    const void* dbg_x = nullptr; int dbg_T = 0, dbg_C = 0;   // SVHIP_RN_STOP developer hook (tests)
-    void* snap = nullptr; size_t snap_cap = 0; int snap_T = 0, snap_C = 0;      // SVHIP_RN_SNAP=2: copy of block 2's pre-activation (stage "rn_snap")
-    // option rn_keep: copies of what the forward stored, by stage name.  A buffer holds max_batch utterances (allocated when its stage is
-    // first kept), so the slices of a forward on several lanes fill it side by side; a stage counts as kept when every utterance of the
-    // last forward (`epoch`) wrote it.
-    // (after a ragged forward `rows` counts the packed rows of all its utterances: `packed`)
+    // option rn_keep (the helper of the same name fills them): copies of what the forward stored, by stage name, `rows` per utterance or,
+    // after a ragged forward, the packed rows of all its utterances (`packed`); `cap`: the buffer's bytes.  A stage counts as kept when
+    // every utterance of the last forward (`epoch`) wrote it.
     struct Kept { void* buf = nullptr; size_t rows = 0, cols = 0; bool f32 = false; uint64_t epoch = 0; int utts = 0; bool packed = false; size_t cap = 0; };
     std::map<std::string, Kept> kept;
     uint64_t epoch = 0;
@@ -382,9 +379,7 @@ static bool rn_keep_name(const std::string& n) {
 int rawnet2_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {
     auto& s = S(h);
     const int B = h->lastB;
-    if (n == "rn_x") { v.src = s.dbg_x; v.rows = (size_t)B * s.dbg_T; v.cols = v.ld = s.dbg_C; }
-    else if (n == "rn_snap") { v.src = s.snap; v.rows = (size_t)B * s.snap_T; v.cols = v.ld = s.snap_C; }
-    else if (n == "rn_pooled") { v.src = s.pooled; v.rows = B; v.cols = v.ld = 1024; v.f32 = true; }
+    if (n == "rn_pooled") { v.src = s.pooled; v.rows = B; v.cols = v.ld = 1024; v.f32 = true; }
     else if (n == "rn_gru_h" && rn_is_gru(h->cfg.model)) { v.src = s.gru_h; v.rows = B; v.cols = v.ld = RN_GRU_HIDDEN; v.f32 = true; }
     else if (n == "rn_gru_in" && rn_is_gru(h->cfg.model)) {
         if (!s.gru_in) SV_FAIL(h, SVHIP_ERR_STATE, "stage rn_gru_in: the last forward ran as several batch slices (SVHIP_LANES)");
@@ -410,321 +405,370 @@ static GemmParams conv2sc_params(svhip_handle* h, const RnBlock& K, const void* 
     return p;
 }
 
-// RawNet2.forward (models/RawNet2_custom.py:161-227) on device-resident waveforms (B, L), utterances [b0, b0 + B) of the call,
-// enqueued on h->cur.  Every workspace buffer is per-utterance contiguous, so a batch slice is an offset into each.
-static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0, int B) {
+// Option rn_keep, for both forwards: copy `nrows` x `cols` values the forward has just stored — in the handle's type, in fp32 (KEEP_F32)
+// or in the S32 layout (KEEP_S32, kept as fp32) — to rows [row0, row0 + nrows) of stage `name`, on the forward's stream, for `utts`
+// utterances.  A fixed-length forward counts `rows` per utterance and fills a buffer of max_batch utterances slice by slice; a ragged
+// one (`packed`) keeps the `rows` packed rows of a level at once.  The buffer holds `cap_rows` rows and grows when a call needs more.
+// Nothing else reads the option: the kernels enqueued, their operands and their routes are those of a forward without it.
+enum { KEEP_DT, KEEP_F32, KEEP_S32 };
+static int rn_keep(svhip_handle* h, hipStream_t st, const std::string& name, const void* src, int kind, size_t rows, bool packed, size_t cap_rows,
+                   int cols, size_t row0, size_t nrows, int utts) {
     auto& s = S(h);
-    const svhip_config& c = h->cfg;
-    const bool bf = h->bf16;
-    hipStream_t st = h->cur;
-    const int L = c.samples, e = h->esz;
-    const size_t per_utt = (size_t)s.T1 * 128;                 // elements of the largest activation of one utterance
-    const float* d_wav = d_wav_all + (size_t)b0 * L;
-    const bool conv = c.model == SVHIP_MODEL_RAWNET2_CONV;        // front_proc='conv': no LayerNorm, no sinc, no first_bn
-    float* rn_stats = conv ? nullptr : s.stats + (size_t)b0 * 2;
-    float* rn_mean = s.mean + (size_t)b0 * 512;
-    float* rn_scratch = s.scratch + (size_t)b0 * 16 * 512;
-    float* rn_part = s.part + (size_t)b0 * (rn_block128_ntiles(s.T1) + 1) * 4 * 128;
-    float* rn_gate[2] = {s.gate + (size_t)b0 * 512, s.gate + ((size_t)c.max_batch + b0) * 512};
-    float* rn_pooled = s.pooled + (size_t)b0 * 1024;
-    float* d_emb = h->d_emb + (size_t)b0 * c.embed_dim;
-    int rc;
-    const bool sinc_x3 = !conv && h->x3 && s.filt_x3 && !h->opt.rn_sinc_f32;      // F32X3: the front-end on three fp16 MFMAs per product
-    void* rn_xn = conv ? nullptr : bf ? static_cast<char*>(s.xn) + (size_t)b0 * 2 * s.Lp * 2 : sinc_x3 ? static_cast<char*>(s.xn) + (size_t)b0 * 4 * s.Lp * 2 : nullptr;
-    const int dt = h->dt;
-    if (!conv && (rc = run(h, "rn_ln_stats", 0, [&]() { return launch_rn_ln_stats(d_wav, B, L, rn_stats, st, rn_xn, s.Lp, s.gamma, s.beta, dt, sinc_x3); }))) return rc;
-    int T = s.T1;
-    void *x = off(s.buf[0], b0 * per_utt, e), *pre = off(s.buf[1], b0 * per_utt, e), *hb = off(s.buf[2], b0 * per_utt, e),
-         *o = off(s.buf[3], b0 * per_utt, e), *sc = off(s.buf[4], b0 * per_utt, e), *xn = off(s.buf[5], b0 * per_utt, e);
-    // developer hook (option rn_stop): return after N residual blocks (0: after the front-end) with x exposed as stage "rn_x"; the
-    // unfused kernel sequence runs, whose storage points are those of the fused kernels
-    const int stop_after = h->opt.rn_stop;
-    // developer hook (tests): SVHIP_RN_SNAP=2 keeps a copy of lrelu(bn1(x)) as block 2 will read it — the first tensor that both the
-    // fused 128-channel blocks and the separate kernel sequence materialise — as stage "rn_snap"
-    const int snap_at = h->opt.rn_snap;
-    auto snapshot = [&](const void* src, int Tn, int Cn) -> int {
-        const size_t bytes = (size_t)B * Tn * Cn * e;
-        if (s.snap_cap < bytes) {
-            void* q = nullptr;
-            SV_HIP(h, hipMalloc(&q, bytes));
-            h->allocs.push_back(q);
-            s.snap = q; s.snap_cap = bytes;
-        }
-        SV_HIP(h, hipMemcpyAsync(s.snap, src, bytes, hipMemcpyDeviceToDevice, st));
-        s.snap_T = Tn; s.snap_C = Cn;
-        return SVHIP_OK;
-    };
-    // developer hook (option rn_keep): copy a tensor the forward has just stored — `rows` x `cols` per utterance, in the handle's type, in
-    // fp32 (KEEP_F32) or in the S32 layout (KEEP_S32, kept as fp32) — on the forward's own stream.  Nothing else reads the option: the
-    // kernels enqueued, their operands and their routes are those of a forward without it.
-    enum { KEEP_DT, KEEP_F32, KEEP_S32 };
-    const bool keeping = h->opt.rn_keep != 0;
-    auto keep = [&](const std::string& name, const void* src, size_t rows, int cols, int kind) -> int {
-        if (!keeping) return SVHIP_OK;
-        const bool f32 = kind != KEEP_DT || !bf;
-        const size_t es = f32 ? 4 : 2;
-        RawNet2State::Kept& k = s.kept[name];
-        if (!k.buf || k.packed || k.rows != rows || k.cols != (size_t)cols || k.f32 != f32) {
-            void* q = nullptr;
-            SV_HIP(h, hipMalloc(&q, (size_t)c.max_batch * rows * cols * es));
-            h->allocs.push_back(q);
-            k.buf = q; k.rows = rows; k.cols = cols; k.f32 = f32; k.epoch = 0; k.packed = false; k.cap = (size_t)c.max_batch * rows * cols * es;
-        }
-        if (k.epoch != s.epoch) { k.epoch = s.epoch; k.utts = 0; }
-        void* dst = static_cast<char*>(k.buf) + (size_t)b0 * rows * cols * es;
-        if (kind == KEEP_S32) SV_HIP(h, launch_unsplit_s32(src, cols, static_cast<float*>(dst), cols, (int64_t)B * rows, cols, st));
-        else SV_HIP(h, hipMemcpyAsync(dst, src, (size_t)B * rows * cols * es, hipMemcpyDeviceToDevice, st));
-        k.utts += B;
-        return SVHIP_OK;
-    };
-    auto blk = [](int i, const char* what) { return "rn_b" + std::to_string(i) + "_" + what; };
-    // (the pre-activation block `bn` will read, or after block 7 the aggregation's input; the input x of block `bn`)
-    auto keep_pre = [&](int bn, const void* src, int Tn, int Cn, bool s32) { return keep(bn < 8 ? blk(bn, "pre") : std::string("rn_agg_in"), src, Tn, Cn, s32 ? KEEP_S32 : KEEP_DT); };
-    // F32X3: does block `bn`, entered with Tn frames, run its convolutions (and its projection shortcut) on the 128 x 128 split kernel
-    // (r2_step.hip, modes 1 / 2)?  a1: its pre-activation lrelu(bn1(x)) in the S32 layout; xb: its input x.  (Otherwise they run on the
-    // tiled kernel that splits its fp32 operands in registers: 170 - 190 TFLOP/s.)
-    struct RnStep { bool ok = false; GemmParams q0, q1, q2; };
-    auto rn_step_plan = [&](int bn, int Tn, const void* a1, const void* xb) {
-        RnStep sp;
-        if (bn > 7 || !h->x3 || h->opt.rn_step_off) return sp;
-        const RnBlock& K = s.blocks[bn];
-        GemmParams& q1 = sp.q1;                           // conv1: pre (S32) -> lrelu(bn2(.)) in S32, conv2's operand
-        q1 = conv_params(h, K.conv1, a1, K.cin, hb, K.cout, B * Tn, Tn);
-        q1.W = K.conv1.Ws32; q1.x3 = 2; q1.pad_mode = PAD_ZERO; q1.zero_page = h->d_zeros;
-        GemmParams& q2 = sp.q2 = q1;                      // conv2: h (S32) -> fp32, + the shortcut (identity x, or the projected one)
-        q2.A = hb; q2.lda = K.cout; q2.cin = K.cout; q2.K = 3 * K.cout; q2.Kp = q2.K; q2.W = K.conv2.Ws32; q2.scale = nullptr; q2.shift = nullptr;
-        q2.Y = o; q2.out_f32 = 1; q2.R = reinterpret_cast<const float*>(K.has_shortcut ? sc : xb); q2.ldr = K.cout;
-        GemmParams& q0 = sp.q0 = q1;                      // projection shortcut (k = 1) of pre -> fp32, into the spare activation buffer
-        q0.W = K.shortcut.Ws32; q0.taps = 1; q0.K = K.cin; q0.Kp = K.cin; q0.scale = nullptr; q0.shift = nullptr; q0.Y = sc; q0.out_f32 = 1;
-        // (rn_step_supported also asks for the split weights and the shapes: cin % 32 == 0, cout % 128 == 0, Tn >= 2)
-        sp.ok = rn_step_supported(q1, 1) && rn_step_supported(q2, 2) && (!K.has_shortcut || rn_step_supported(q0, 2));
-        return sp;
-    };
-    // a producer writes block bn's pre-activation straight in the S32 layout when the block takes the split kernel and neither developer
-    // hook is set (the block itself honours only rn_step_off: it splits an fp32 pre-activation first)
-    auto pre_s32_for = [&](int bn, int Tn, const void* xb) { return stop_after < 0 && snap_at < 0 && rn_step_plan(bn, Tn, pre, xb).ok; };
-    bool pre_is_s32 = false;
-    // (the split front-end writes block 0's pre-activation itself, in the S32 layout, when block 0 runs on the split convolution kernel)
-    const bool sinc_pre = sinc_x3 && pre_s32_for(0, T, x);
-    if (sinc_pre) pre_is_s32 = true;
-    // bf16 / fp16 handles: the fused chain's first block computes the conv front-end itself from the waveform (rn_block128's CONV
-    // form) and x is never stored; option rn_conv_unfused stores x with rn_conv3_front and runs the plain block (bit-identical)
-    const bool fuse_ok = bf && stop_after < 0 && !h->opt.rn_unfused;
+    const bool f32 = kind != KEEP_DT || !h->bf16;
+    const size_t es = f32 ? 4 : 2, need = cap_rows * cols * es;
+    RawNet2State::Kept& k = s.kept[name];
+    if (!k.buf || k.cap < need) {
+        void* q = nullptr;
+        SV_HIP(h, hipMalloc(&q, need));
+        h->allocs.push_back(q);
+        k.buf = q; k.cap = need; k.epoch = 0;
+    }
+    // (the first copy of a forward, or another shape than the earlier slices': what the buffer held does not count)
+    if (k.epoch != s.epoch || k.rows != rows || k.cols != (size_t)cols || k.f32 != f32 || k.packed != packed) {
+        k.rows = rows; k.cols = cols; k.f32 = f32; k.packed = packed; k.epoch = s.epoch; k.utts = 0;
+    }
+    void* dst = static_cast<char*>(k.buf) + row0 * cols * es;
+    if (kind == KEEP_S32) SV_HIP(h, launch_unsplit_s32(src, cols, static_cast<float*>(dst), cols, (int64_t)nrows, cols, st));
+    else SV_HIP(h, hipMemcpyAsync(dst, src, nrows * cols * es, hipMemcpyDeviceToDevice, st));
+    k.utts += utts;
+    return SVHIP_OK;
+}
+static std::string blk(int i, const char* what) { return "rn_b" + std::to_string(i) + "_" + what; }
+
+// RawNet2.forward (models/RawNet2_custom.py:161-227) on device-resident waveforms, as steps over one slice of the call: utterances
+// [b0, b0 + B), enqueued on `st`.  Every workspace buffer is per-utterance contiguous, so a slice's pointers are offsets into each.
+struct RnPass {
+    svhip_handle* h;
+    RawNet2State& s;
+    int b0 = 0, B = 0;
+    hipStream_t st = nullptr;
+    int dt = DT_F32;
+    const float* wav = nullptr;               // (B, L)
+    // activations: the block input x, its pre-activation lrelu(bn1(x)), conv1's output, conv2's, the projected shortcut, the next x
+    void *x = nullptr, *pre = nullptr, *hb = nullptr, *o = nullptr, *sc = nullptr, *xn = nullptr;
+    float* stats = nullptr;                   // LayerNorm statistics
+    void* ln = nullptr;                       // ... and its output in 16 bits / split halves (operand of the 16-bit / split sinc kernels)
+    float *mean = nullptr, *scratch = nullptr, *part = nullptr, *gate[2] = {}, *pooled = nullptr, *emb = nullptr;
+    float* lin_part = nullptr;                // K-slice partials of the last linear layer (16-bit handles), or null
+    int T = 0;                                // frames of x
+    bool pre_is_s32 = false;                  // F32X3: `pre` is in the S32 layout (its producer asked rn_step_plan for the block that reads it)
+    bool sinc_x3 = false;                     // F32X3: the sinc front-end on three fp16 MFMAs per product
+    bool fuse_ok = false;                     // 16-bit handles: 128 -> 128 pooled blocks run as the fused chain (rn_block128 + gate)
+    bool chain0 = false;                      // ... and block 0 opens it: it forms its pre-activation itself
+    bool conv_fused = false;                  // ... from the waveform ('conv' front-end): x is never stored
+
+    int keep(const std::string& name, const void* src, size_t rows, int cols, int kind) const {
+        if (!h->opt.rn_keep) return SVHIP_OK;
+        return rn_keep(h, st, name, src, kind, rows, false, (size_t)h->cfg.max_batch * rows, cols, (size_t)b0 * rows, (size_t)B * rows, B);
+    }
+    // (the pre-activation block `bn` will read, or after block 7 the aggregation's input)
+    int keep_pre(int bn, int Tn, int Cn) const { return keep(bn < 8 ? blk(bn, "pre") : std::string("rn_agg_in"), pre, Tn, Cn, pre_is_s32 ? KEEP_S32 : KEEP_DT); }
+};
+
+// F32X3: does block `bn`, entered with Tn frames, run its convolutions (and its projection shortcut) on the 128 x 128 split kernel
+// (r2_step.hip, modes 1 / 2)?  Its operand is `pre` in the S32 layout; xb: its input x.  (Otherwise they run on the tiled kernel
+// that splits its fp32 operands in registers: 170 - 190 TFLOP/s.)  The producer of `pre` asks, and writes the S32 layout where the
+// answer is yes; the block asks again with the same arguments.
+struct RnStep { bool ok = false; GemmParams q0, q1, q2; };
+static RnStep rn_step_plan(const RnPass& p, int bn, int Tn, const void* xb) {
+    svhip_handle* h = p.h;
+    RnStep sp;
+    if (bn > 7 || !h->x3 || h->opt.rn_step_off) return sp;
+    const RnBlock& K = p.s.blocks[bn];
+    GemmParams& q1 = sp.q1;                           // conv1: pre (S32) -> lrelu(bn2(.)) in S32, conv2's operand
+    q1 = conv_params(h, K.conv1, p.pre, K.cin, p.hb, K.cout, p.B * Tn, Tn);
+    q1.W = K.conv1.Ws32; q1.x3 = 2; q1.pad_mode = PAD_ZERO; q1.zero_page = h->d_zeros;
+    GemmParams& q2 = sp.q2 = q1;                      // conv2: h (S32) -> fp32, + the shortcut (identity x, or the projected one)
+    q2.A = p.hb; q2.lda = K.cout; q2.cin = K.cout; q2.K = 3 * K.cout; q2.Kp = q2.K; q2.W = K.conv2.Ws32; q2.scale = nullptr; q2.shift = nullptr;
+    q2.Y = p.o; q2.out_f32 = 1; q2.R = reinterpret_cast<const float*>(K.has_shortcut ? p.sc : xb); q2.ldr = K.cout;
+    GemmParams& q0 = sp.q0 = q1;                      // projection shortcut (k = 1) of pre -> fp32, into the spare activation buffer
+    q0.W = K.shortcut.Ws32; q0.taps = 1; q0.K = K.cin; q0.Kp = K.cin; q0.scale = nullptr; q0.shift = nullptr; q0.Y = p.sc; q0.out_f32 = 1;
+    // (rn_step_supported also asks for the split weights and the shapes: cin % 32 == 0, cout % 128 == 0, Tn >= 2)
+    sp.ok = rn_step_supported(q1, 1) && rn_step_supported(q2, 2) && (!K.has_shortcut || rn_step_supported(q0, 2));
+    return sp;
+}
+
+// the front-end: [LayerNorm statistics,] x = sinc | split sinc | conv1 of the waveform, and block 0's pre-activation lrelu(bn1(x))
+// unless block 0 opens the fused chain
+static int rn_front(RnPass& p) {
+    svhip_handle* h = p.h;
+    auto& s = p.s;
+    const int B = p.B, L = h->cfg.samples, T = p.T, dt = p.dt;
+    const bool conv = h->cfg.model == SVHIP_MODEL_RAWNET2_CONV;        // front_proc='conv': no LayerNorm, no sinc, no first_bn
     const RnBlock& K0 = s.blocks[0];
-    const bool conv_fused = conv && fuse_ok && !h->opt.rn_conv_unfused &&
-                            rn_block128_supported(K0.cin, K0.cout, T, K0.downsample, K0.has_shortcut, K0.conv1.Kp, K0.conv2.Kp);
+    int rc;
+    if (!conv && (rc = run(h, "rn_ln_stats", 0, [&]() { return launch_rn_ln_stats(p.wav, B, L, p.stats, p.st, p.ln, s.Lp, s.gamma, s.beta, dt, p.sinc_x3); }))) return rc;
+    // (the split front-end writes block 0's pre-activation itself, in the S32 layout, when block 0 runs on the split convolution kernel)
+    const bool pre_s32 = rn_step_plan(p, 0, T, p.x).ok, sinc_pre = p.sinc_x3 && pre_s32;
     if (conv) {
-        if (!conv_fused && (rc = run(h, "rn_conv3_front", 2.0 * B * 128.0 * 3.0 * T, [&]() { return launch_rn_conv3_front(d_wav, s.cw, x, dt, B, L, T, st); })))
+        // (16-bit handles: the fused chain's first block computes the conv front-end itself from the waveform — rn_block128's CONV
+        //  form; option rn_conv_unfused stores x with rn_conv3_front and runs the plain block, bit-identical)
+        if (!p.conv_fused && (rc = run(h, "rn_conv3_front", 2.0 * B * 128.0 * 3.0 * T, [&]() { return launch_rn_conv3_front(p.wav, s.cw, p.x, dt, B, L, T, p.st); })))
             return rc;
     } else if ((rc = run(h, "rn_sinc", 2.0 * B * 128.0 * 251.0 * (L - 250), [&]() {
              // (the kernel can also write block 0's pre-activation, but its 8-byte scattered stores make that as dear as the
              //  separate coalesced rn_bn_act pass: measured 0.85 + 0.29 ms either way)
-             if (sinc_x3) return launch_rn_sinc_x3(s.filt_x3, s.fbn_scale, s.fbn_shift, reinterpret_cast<float*>(x), B, L, T, rn_xn, s.Lp, h->num_cu, st,
-                                                   sinc_pre ? pre : nullptr, s.blocks[0].bn1_scale, s.blocks[0].bn1_shift);
+             if (p.sinc_x3) return launch_rn_sinc_x3(s.filt_x3, s.fbn_scale, s.fbn_shift, reinterpret_cast<float*>(p.x), B, L, T, p.ln, s.Lp, h->num_cu, p.st,
+                                                     sinc_pre ? p.pre : nullptr, K0.bn1_scale, K0.bn1_shift);
              // fp16 handles: the symmetric form of the sinc convolution (K = 126 instead of 251; option rn_sinc_full keeps round 5's kernel)
              const bool sym = h->f16 && s.filt_sym && !h->opt.rn_sinc_full;
-             return launch_rn_sinc(d_wav, rn_stats, s.gamma, s.beta, sym ? s.filt_sym : s.filt, s.fbn_scale, s.fbn_shift, x, dt, B, L, T, st,
-                                   nullptr, nullptr, nullptr, rn_xn, s.Lp, h->num_cu, sym);
+             return launch_rn_sinc(p.wav, p.stats, s.gamma, s.beta, sym ? s.filt_sym : s.filt, s.fbn_scale, s.fbn_shift, p.x, dt, B, L, T, p.st,
+                                   nullptr, nullptr, nullptr, p.ln, s.Lp, h->num_cu, sym);
          }))) return rc;
-    s.dbg_x = x; s.dbg_T = T; s.dbg_C = 128;
-    if (!conv_fused && (rc = keep("rn_front", x, T, 128, KEEP_DT))) return rc;        // (the conv-fused block 0 reads the waveform: no front-end tensor)
-    if (sinc_pre && (rc = keep_pre(0, pre, T, 128, true))) return rc;
-    if (stop_after == 0) return SVHIP_OK;
-    // bf16: the 128 -> 128 pooled blocks (layer1, layer2) each run as ONE fused kernel + the AFMS gate kernel; the gate of
-    // block i is applied by block i + 1 on the way in (or by the rn_afms_apply pass in front of the first GEMM block)
-    int first = 0;
-    const bool no_tail = h->opt.rn_unfused != 0;                        // (tests: the separate passes against the fused tail)
+    if (!p.conv_fused && (rc = p.keep("rn_front", p.x, T, 128, KEEP_DT))) return rc;        // (the conv-fused block 0 reads the waveform: no front-end tensor)
+    if (p.chain0) return SVHIP_OK;
+    // out = lrelu(bn1(x))                                                             RawNet_baseline.py:222
+    // (blocks 1..7 get it from the previous block's AFMS pass, which writes x and lrelu(bn1(x)) together)
+    p.pre_is_s32 = pre_s32;
+    if (!sinc_pre && (rc = run(h, "rn_bn_act", 0, [&]() { return launch_rn_bn_act(p.x, p.pre, dt, K0.bn1_scale, K0.bn1_shift, B * T, K0.cin, 0.3f, p.st, p.pre_is_s32); })))
+        return rc;
+    return p.keep_pre(0, T, K0.cin);
+}
+
+// 16-bit handles: the leading 128 -> 128 pooled blocks (layer1, layer2) each run as ONE fused kernel + the AFMS gate kernel; the gate
+// of block i is applied by block i + 1 on the way in, the last one's by the closing rn_afms_apply pass in front of the first GEMM
+// block.  first: the blocks taken
+static int rn_fused_chain(RnPass& p, int& first) {
+    svhip_handle* h = p.h;
+    auto& s = p.s;
+    const int B = p.B, dt = p.dt;
+    int rc;
     const float *g_alpha = nullptr, *g_gate = nullptr;          // pending gate of the previous fused block
-    const void* xin = x;
-    for (; fuse_ok && first < 8; ++first) {
-        RnBlock& K = s.blocks[first];
-        if (!rn_block128_supported(K.cin, K.cout, T, K.downsample, K.has_shortcut, K.conv1.Kp, K.conv2.Kp)) break;
+    const void* xin = p.x;
+    for (first = 0; p.fuse_ok && first < 8; ++first) {
+        const RnBlock& K = s.blocks[first];
+        if (!rn_block128_supported(K.cin, K.cout, p.T, K.downsample, K.has_shortcut, K.conv1.Kp, K.conv2.Kp)) break;
         RnBlock128Params bp;
         bp.xin = reinterpret_cast<const bf16_t*>(xin);
         bp.alpha = g_alpha; bp.gate = g_gate;
         bp.bn1_scale = K.bn1_scale; bp.bn1_shift = K.bn1_shift;
         bp.W1 = reinterpret_cast<const bf16_t*>(K.conv1.W); bp.bn2_scale = K.conv1.scale; bp.bn2_shift = K.conv1.shift;
         bp.W2 = reinterpret_cast<const bf16_t*>(K.conv2.W);
-        void* dst = (first & 1) ? hb : o;                        // ping-pong: never the buffer being read
+        void* dst = (first & 1) ? p.hb : p.o;                    // ping-pong: never the buffer being read
         bp.opool = reinterpret_cast<bf16_t*>(dst);
-        bp.colsum = rn_part;
-        bp.B = B; bp.T = T; bp.Tout = T / 3; bp.ntiles = rn_block128_ntiles(T); bp.f16 = h->f16 ? 1 : 0;
-        const bool from_wave = first == 0 && conv_fused;
-        if (from_wave) { bp.xin = nullptr; bp.wav = d_wav; bp.cw = s.cw; bp.L = L; }
-        const double fl = (double)B * T * (K.conv1.flops_per_row + K.conv2.flops_per_row + (from_wave ? 2.0 * 128 * 3 : 0.0));
-        if ((rc = run(h, from_wave ? "rn_block128_conv" : "rn_block128", fl, [&]() { return launch_rn_block128(bp, h->num_cu, st); }))) return rc;
-        float* gate = rn_gate[first & 1];                        // two gate buffers: block i + 1 reads i's while writing its own
+        bp.colsum = p.part;
+        bp.B = B; bp.T = p.T; bp.Tout = p.T / 3; bp.ntiles = rn_block128_ntiles(p.T); bp.f16 = h->f16 ? 1 : 0;
+        const bool from_wave = first == 0 && p.conv_fused;
+        if (from_wave) { bp.xin = nullptr; bp.wav = p.wav; bp.cw = s.cw; bp.L = h->cfg.samples; }
+        const double fl = (double)B * p.T * (K.conv1.flops_per_row + K.conv2.flops_per_row + (from_wave ? 2.0 * 128 * 3 : 0.0));
+        if ((rc = run(h, from_wave ? "rn_block128_conv" : "rn_block128", fl, [&]() { return launch_rn_block128(bp, h->num_cu, p.st); }))) return rc;
+        float* gate = p.gate[first & 1];                         // two gate buffers: block i + 1 reads i's while writing its own
         if ((rc = run(h, "rn_afms_gate", 2.0 * B * K.cout * K.cout, [&]() {
-                 return launch_rn_afms_gate(rn_part, rn_block128_nparts(B, bp.T, h->num_cu), B, K.cout, bp.Tout, K.afms_fcT, K.afms_fc.bias, gate, st);
+                 return launch_rn_afms_gate(p.part, rn_block128_nparts(B, bp.T, h->num_cu), B, K.cout, bp.Tout, K.afms_fcT, K.afms_fc.bias, gate, p.st);
              }))) return rc;
-        if ((rc = keep(blk(first, "pool"), dst, bp.Tout, K.cout, KEEP_DT)) || (rc = keep(blk(first, "gate"), gate, 1, K.cout, KEEP_F32))) return rc;
-        T /= 3;
+        if ((rc = p.keep(blk(first, "pool"), dst, bp.Tout, K.cout, KEEP_DT)) || (rc = p.keep(blk(first, "gate"), gate, 1, K.cout, KEEP_F32))) return rc;
+        p.T /= 3;
         xin = dst;
         g_alpha = K.alpha; g_gate = gate;
     }
-    if (first > 0) {
-        // x = (o + alpha) * gate and, in the same pass, the next consumer's lrelu(bn(x))
-        RnBlock& Kp = s.blocks[first - 1];
-        const float* nsc = first < 8 ? s.blocks[first].bn1_scale : s.agg_scale;
-        const float* nsh = first < 8 ? s.blocks[first].bn1_shift : s.agg_shift;
-        // x itself is read only as an identity shortcut (or as a debug stage): not written when the next block projects its input
-        void* xdst = (first < 8 && s.blocks[first].has_shortcut && stop_after < 0) ? nullptr : x;
-        if ((rc = run(h, "rn_afms_apply", 0, [&]() { return launch_rn_afms_apply(xin, xdst, dt, Kp.alpha, g_gate, B, T, Kp.cout, st, nsc, nsh, pre, 0.3f); }))) return rc;
-        s.dbg_x = x; s.dbg_T = T; s.dbg_C = Kp.cout;
-        if ((rc = keep_pre(first, pre, T, Kp.cout, false)) || (xdst && first < 8 && (rc = keep(blk(first, "x"), x, T, Kp.cout, KEEP_DT)))) return rc;
-        if (snap_at == first && b0 == 0 && (rc = snapshot(pre, T, Kp.cout))) return rc;
+    if (first == 0) return SVHIP_OK;
+    // x = (o + alpha) * gate and, in the same pass, the next consumer's lrelu(bn(x))
+    const RnBlock& Kp = s.blocks[first - 1];
+    const float* nsc = first < 8 ? s.blocks[first].bn1_scale : s.agg_scale;
+    const float* nsh = first < 8 ? s.blocks[first].bn1_shift : s.agg_shift;
+    // x itself is read only as an identity shortcut: not written when the next block projects its input
+    void* xdst = (first < 8 && s.blocks[first].has_shortcut) ? nullptr : p.x;
+    if ((rc = run(h, "rn_afms_apply", 0, [&]() { return launch_rn_afms_apply(xin, xdst, dt, Kp.alpha, g_gate, B, p.T, Kp.cout, p.st, nsc, nsh, p.pre, 0.3f); }))) return rc;
+    if ((rc = p.keep_pre(first, p.T, Kp.cout))) return rc;
+    return xdst && first < 8 ? p.keep(blk(first, "x"), p.x, p.T, Kp.cout, KEEP_DT) : SVHIP_OK;
+}
+
+// A block's convolutions on the split kernel (F32X3, `pre` in the S32 layout): [projection shortcut,] conv1 -> bn2 -> lrelu, conv2 +
+// shortcut.  pooled_by_conv: conv2 pooled on its way out (a pooled block whose tail is not the fused kernel — the long utterances
+// of layers 1 - 3)
+static int rn_convs_split(RnPass& p, const RnBlock& K, const RnStep& sp, bool tail_fused, bool& pooled_by_conv) {
+    svhip_handle* h = p.h;
+    const int M = p.B * p.T;
+    int rc;
+    if (K.has_shortcut && (rc = run(h, "rn_step", (double)M * K.shortcut.flops_per_row, [&]() { return launch_rn_step(sp.q0, 2, p.st); }))) return rc;
+    if ((rc = run(h, "rn_step", (double)M * K.conv1.flops_per_row, [&]() { return launch_rn_step(sp.q1, 1, p.st); }))) return rc;
+    pooled_by_conv = K.downsample && !tail_fused && p.T >= 3 && !h->opt.rn_pool_off && rn_step_supported(sp.q2, 3);
+    return run(h, "rn_step", (double)M * K.conv2.flops_per_row, [&]() { return launch_rn_step(sp.q2, pooled_by_conv ? 3 : 2, p.st); });
+}
+
+// ... and on the tiled GEMMs (conv_plan picks each kernel).  resid_in_tail: the block input, where the tail adds the identity shortcut
+static int rn_convs_tiled(RnPass& p, const RnBlock& K, bool tail_fused, const void*& resid_in_tail) {
+    svhip_handle* h = p.h;
+    const int T = p.T, M = p.B * T;
+    int rc;
+    // A 1 x 1 shortcut rides in conv2's GEMM as extra K columns when the 256 x 256 kernel takes it (no shortcut tensor in HBM)
+    const GemmParams psc = conv2sc_params(h, K, p.pre, p.hb, p.o, M, T);
+    const bool fold_sc = K.has_shortcut && K.conv2sc_W && !h->opt.rn_unfused && conv_plan(h, K.conv2, psc).route == ROUTE_PW2;
+    const void* resid = p.x;                                                 // identity shortcut takes the pre-BN x (:223)
+    if (K.has_shortcut && !fold_sc) {
+        if ((rc = conv_gemm(h, K.shortcut, conv_params(h, K.shortcut, p.pre, K.cin, p.sc, K.cout, M, h->T)))) return rc;
+        resid = p.sc;
     }
-    for (int bi = first; bi < 8; ++bi) {
-        RnBlock& K = s.blocks[bi];
-        const int M = B * T;
-        // out = lrelu(bn1(x))                                                         RawNet_baseline.py:222
-        // (blocks 1..7 get it from the previous block's AFMS pass, which writes x and lrelu(bn1(x)) together)
-        if (((bi == 0 && first == 0) || stop_after >= 0) && !(bi == 0 && sinc_pre)) {
-            pre_is_s32 = pre_s32_for(bi, T, x);
-            if ((rc = run(h, "rn_bn_act", 0, [&]() { return launch_rn_bn_act(x, pre, dt, K.bn1_scale, K.bn1_shift, M, K.cin, 0.3f, st, pre_is_s32); }))) return rc;
-            if ((rc = keep_pre(bi, pre, T, K.cin, pre_is_s32))) return rc;
+    GemmParams p1 = conv_params(h, K.conv1, p.pre, K.cin, p.hb, K.cout, M, T);
+    p1.act2 = ACT_LRELU03; p1.pad_mode = PAD_ZERO;
+    if ((rc = conv_gemm(h, K.conv1, p1))) return rc;
+    if (fold_sc) return conv_gemm(h, K.conv2, psc);
+    GemmParams p2 = conv_params(h, K.conv2, p.hb, K.cout, p.o, K.cout, M, T);
+    p2.pad_mode = PAD_ZERO;
+    // identity shortcut: with the fused block tail and conv2 on the persistent conv-gather kernel (which has no residual
+    // operand) the tail adds the block input; otherwise conv2's epilogue does
+    if (!K.has_shortcut && tail_fused && conv_plan(h, K.conv2, p2).route == ROUTE_PW3CV) resid_in_tail = p.x;
+    else p2.R = resid, p2.ldr = K.cout;
+    return conv_gemm(h, K.conv2, p2);
+}
+
+// A block's tail, as one rn_tail launch or as separate passes: [max_pool1d(3)] -> AFMS gate -> the next step's x and, in the same pass,
+// its pre-activation lrelu(bn(.)) (block bi + 1's bn1, or the aggregation BN after block 7); p.x / p.pre / p.T move on to them
+static int rn_block_tail(RnPass& p, int bi, bool tail_fused, bool pooled_by_conv, const void* resid_in_tail) {
+    svhip_handle* h = p.h;
+    const RnBlock& K = p.s.blocks[bi];
+    const int B = p.B, dt = p.dt, T = p.T, Tn = K.downsample ? T / 3 : T;
+    const float* nsc = bi < 7 ? p.s.blocks[bi + 1].bn1_scale : p.s.agg_scale;
+    const float* nsh = bi < 7 ? p.s.blocks[bi + 1].bn1_shift : p.s.agg_shift;
+    // the block output itself is read only by an identity shortcut of the next block
+    const bool x_dead = bi == 7 || p.s.blocks[bi + 1].has_shortcut;
+    // (F32X3: when the next block runs on the split convolution kernel its pre-activation is written in the S32 layout right here)
+    const bool next_s32 = rn_step_plan(p, bi + 1, Tn, p.xn).ok;
+    int rc;
+    if (tail_fused) {
+        // max-pool + AFMS + next pre-activation in one launch, the pooled activation held in registers      :228-229, :62-68
+        char tl[48] = "rn_tail";
+        if (h->opt.layer_labels) snprintf(tl, sizeof(tl), "rn_tail T%d C%d", T, K.cout);
+        // (small batches: slice sums in `scratch`, the gate in gate[0]; option rn_tail_big keeps one workgroup per utterance)
+        const bool sliced = !h->opt.rn_tail_big;
+        if ((rc = run(h, tl, 2.0 * B * K.cout * K.cout, [&]() {
+                 return launch_rn_tail(p.o, x_dead ? nullptr : p.xn, p.pre, dt, K.downsample, K.alpha, K.afms_fcT, K.afms_fc.bias, nsc, nsh, B, T, K.cout, 0.3f, p.st,
+                                       resid_in_tail, sliced ? p.scratch : nullptr, sliced ? p.gate[0] : nullptr, h->num_cu, next_s32);
+             }))) return rc;
+        // (only the sliced form stores its gate; one workgroup per utterance keeps it on chip)
+        if (sliced && rn_tail_slices(dt, B, Tn, K.cout, h->num_cu) > 0 && (rc = p.keep(blk(bi, "gate"), p.gate[0], 1, K.cout, KEEP_F32))) return rc;
+    } else {
+        const void* y = p.o;                                                          // (F32X3: or conv2 pooled on its way out, into o)
+        if (K.downsample && !pooled_by_conv) {                                        // :228-229
+            if ((rc = run(h, "rn_maxpool3", 0, [&]() { return launch_rn_maxpool3(p.o, p.hb, dt, B, T, K.cout, p.st); }))) return rc;
+            y = p.hb;
         }
-        // (an fp32 pre-activation is split into a buffer that is free here: the next-x buffer when `sc` holds the projected shortcut)
-        void* const split_dst = K.has_shortcut ? xn : sc;
-        const RnStep sp = rn_step_plan(bi, T, pre_is_s32 ? pre : split_dst, x);
-        if (pre_is_s32 && !sp.ok) SV_FAIL(h, SVHIP_ERR_STATE, "RawNet2 block %d: split pre-activation without the split convolution route", bi);
-        const bool tail_fused = !no_tail && rn_tail_supported(dt, K.downsample ? T / 3 : T, K.cout);
-        bool pooled_by_conv = false;
-        const void* resid_in_tail = nullptr;
-        // conv1 -> bn2 -> lrelu (epilogue), conv2 + shortcut                            :224-226
-        auto convs = [&]() -> int {
-            if (sp.ok) {
-                if (!pre_is_s32 && (rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(reinterpret_cast<const float*>(pre), K.cin, split_dst, M, K.cin, st); }))) return rc;
-                if (K.has_shortcut && (rc = run(h, "rn_step", (double)M * K.shortcut.flops_per_row, [&]() { return launch_rn_step(sp.q0, 2, st); }))) return rc;
-                if ((rc = run(h, "rn_step", (double)M * K.conv1.flops_per_row, [&]() { return launch_rn_step(sp.q1, 1, st); }))) return rc;
-                // (a pooled block whose tail is not the fused kernel — the long utterances of layers 1 - 3: conv2 pools on its way out)
-                pooled_by_conv = K.downsample && !tail_fused && T >= 3 && !h->opt.rn_pool_off && rn_step_supported(sp.q2, 3);
-                return run(h, "rn_step", (double)M * K.conv2.flops_per_row, [&]() { return launch_rn_step(sp.q2, pooled_by_conv ? 3 : 2, st); });
-            }
-            // A 1 x 1 shortcut rides in conv2's GEMM as extra K columns when the 256 x 256 kernel takes it (no shortcut tensor in HBM)
-            const GemmParams psc = conv2sc_params(h, K, pre, hb, o, M, T);
-            const bool fold_sc = K.has_shortcut && K.conv2sc_W && !no_tail && conv_plan(h, K.conv2, psc).route == ROUTE_PW2;
-            const void* resid = x;                                                   // identity shortcut takes the pre-BN x (:223)
-            if (K.has_shortcut && !fold_sc) {
-                if ((rc = conv_gemm(h, K.shortcut, conv_params(h, K.shortcut, pre, K.cin, sc, K.cout, M, h->T)))) return rc;
-                resid = sc;
-            }
-            GemmParams p1 = conv_params(h, K.conv1, pre, K.cin, hb, K.cout, M, T);
-            p1.act2 = ACT_LRELU03; p1.pad_mode = PAD_ZERO;
-            if ((rc = conv_gemm(h, K.conv1, p1))) return rc;
-            if (fold_sc) return conv_gemm(h, K.conv2, psc);
-            GemmParams p2 = conv_params(h, K.conv2, hb, K.cout, o, K.cout, M, T);
-            p2.pad_mode = PAD_ZERO;
-            // identity shortcut: with the fused block tail and conv2 on the persistent conv-gather kernel (which has no residual
-            // operand) the tail adds the block input; otherwise conv2's epilogue does
-            if (!K.has_shortcut && tail_fused && conv_plan(h, K.conv2, p2).route == ROUTE_PW3CV) resid_in_tail = x;
-            else p2.R = resid, p2.ldr = K.cout;
-            return conv_gemm(h, K.conv2, p2);
-        };
-        if ((rc = convs())) return rc;
-        // conv2 + shortcut (F32X3: pooled where conv2 pools), or conv2 alone ("c2") where the tail adds the identity shortcut
-        if ((rc = keep(blk(bi, resid_in_tail ? "c2" : "o"), o, pooled_by_conv ? T / 3 : T, K.cout, KEEP_DT))) return rc;
-        // AFMS gate; the same pass writes the next consumer's lrelu(bn(.)): block bi+1's bn1, or the aggregation BN after block 7
-        const float* nsc = bi < 7 ? s.blocks[bi + 1].bn1_scale : s.agg_scale;
-        const float* nsh = bi < 7 ? s.blocks[bi + 1].bn1_shift : s.agg_shift;
-        void* npre = stop_after >= 0 ? nullptr : pre;           // (the developer hook keeps the unfused sequence)
-        // the block output itself is read only by an identity shortcut of the next block (or as a debug stage)
-        const bool x_dead = stop_after < 0 && npre && (bi == 7 || s.blocks[bi + 1].has_shortcut);
-        const int Tn = K.downsample ? T / 3 : T;
-        if (tail_fused) {
-            // max-pool + AFMS + next pre-activation in one launch, the pooled activation held in registers      :228-229, :62-68
-            const bool tail_s32 = npre && pre_s32_for(bi + 1, Tn, xn);      // (F32X3: the next block's operand straight in the S32 layout)
-            char tl[48] = "rn_tail";
-            if (h->opt.layer_labels) snprintf(tl, sizeof(tl), "rn_tail T%d C%d", T, K.cout);
-            if ((rc = run(h, tl, 2.0 * B * K.cout * K.cout, [&]() {
-                     // (small batches: slice sums in rn_scratch, the gate in rn_gate[0]; option rn_tail_big keeps one workgroup per utterance)
-                     const bool sliced = !h->opt.rn_tail_big;
-                     return launch_rn_tail(o, x_dead ? nullptr : xn, npre, dt, K.downsample, K.alpha, K.afms_fcT, K.afms_fc.bias, nsc, nsh, B, T, K.cout, 0.3f, st,
-                                           resid_in_tail, sliced ? rn_scratch : nullptr, sliced ? rn_gate[0] : nullptr, h->num_cu, tail_s32);
-                 }))) return rc;
-            // (only the sliced form stores its gate; one workgroup per utterance keeps it on chip)
-            if (!h->opt.rn_tail_big && rn_tail_slices(dt, B, Tn, K.cout, h->num_cu) > 0 && (rc = keep(blk(bi, "gate"), rn_gate[0], 1, K.cout, KEEP_F32))) return rc;
-            pre_is_s32 = tail_s32;
-            T = Tn;
-        } else {
-            void* y = o;
-            if (K.downsample && pooled_by_conv) {                                        // (F32X3: conv2 pooled on its way out, into o)
-                T /= 3;
-            } else if (K.downsample) {                                                   // :228-229
-                if ((rc = run(h, "rn_maxpool3", 0, [&]() { return launch_rn_maxpool3(o, hb, dt, B, T, K.cout, st); }))) return rc;
-                T /= 3;
-                y = hb;
-            }
-            // AFMS: (y + alpha) * sigmoid(fc(mean_t y))                                     :62-68
-            if ((rc = run(h, "rn_afms_mean", 0, [&]() { return launch_colmean(y, dt, K.cout, B, T, K.cout, rn_mean, st, rn_scratch, 16); }))) return rc;
-            if ((rc = run(h, "rn_afms_gate", 2.0 * B * K.cout * K.cout, [&]() {
-                     return launch_rn_afms_gate(rn_mean, 1, B, K.cout, 1, K.afms_fcT, K.afms_fc.bias, rn_gate[0], st);
-                 }))) return rc;
-            // (F32X3: when the next block runs on the split convolution kernel its pre-activation is written in the S32 layout right here)
-            const bool next_s32 = npre && pre_s32_for(bi + 1, T, xn);
-            if ((rc = run(h, "rn_afms_apply", 0, [&]() { return launch_rn_afms_apply(y, x_dead ? nullptr : xn, dt, K.alpha, rn_gate[0], B, T, K.cout, st, nsc, nsh, npre, 0.3f, next_s32); }))) return rc;
-            if ((rc = keep(blk(bi, "gate"), rn_gate[0], 1, K.cout, KEEP_F32))) return rc;
-            pre_is_s32 = next_s32;
-        }
-        std::swap(x, xn);
-        s.dbg_x = x; s.dbg_T = T; s.dbg_C = K.cout;
-        if (npre && (rc = keep_pre(bi + 1, npre, T, K.cout, pre_is_s32))) return rc;
-        if (!x_dead && bi < 7 && (rc = keep(blk(bi + 1, "x"), x, T, K.cout, KEEP_DT))) return rc;
-        if (stop_after == bi + 1) return SVHIP_OK;
-        if (snap_at == bi + 1 && b0 == 0 && npre && (rc = snapshot(npre, T, K.cout))) return rc;
+        // AFMS: (y + alpha) * sigmoid(fc(mean_t y))                                     :62-68
+        if ((rc = run(h, "rn_afms_mean", 0, [&]() { return launch_colmean(y, dt, K.cout, B, Tn, K.cout, p.mean, p.st, p.scratch, 16); }))) return rc;
+        if ((rc = run(h, "rn_afms_gate", 2.0 * B * K.cout * K.cout, [&]() {
+                 return launch_rn_afms_gate(p.mean, 1, B, K.cout, 1, K.afms_fcT, K.afms_fc.bias, p.gate[0], p.st);
+             }))) return rc;
+        if ((rc = run(h, "rn_afms_apply", 0, [&]() { return launch_rn_afms_apply(y, x_dead ? nullptr : p.xn, dt, K.alpha, p.gate[0], B, Tn, K.cout, p.st, nsc, nsh, p.pre, 0.3f, next_s32); }))) return rc;
+        if ((rc = p.keep(blk(bi, "gate"), p.gate[0], 1, K.cout, KEEP_F32))) return rc;
     }
-    const int M = B * T;
-    if (rn_is_gru(c.model)) {
-        // aggregation: GRU over the T frames, its last state through fc_after_gru          RawNet2_custom.py:196-207
-        // (pre = lrelu(bn_before_gru(x)), (B T, 512) frame-major, came out of block 7's AFMS pass)
-        const int G = 3 * RN_GRU_HIDDEN;
-        float* gi = s.gru_gi + (size_t)b0 * T * G;
-        GemmParams pg = conv_params(h, s.gru_ih, pre, 512, gi, G, M, h->T);
-        pg.out_f32 = 1;
-        const GemmPlan plan = conv_plan(h, s.gru_ih, pg);          // (an fp32 output never takes the S32 form: plan.x3 is false)
-        if (plan.x3) SV_FAIL(h, SVHIP_ERR_STATE, "rn_gru_proj: unexpected split-operand route");
-        if ((rc = run(h, "rn_gru_proj", plan.flops, [&]() { return launch_gemm(plan.q, h->bf16, st); }))) return rc;
-        float* hb[2] = {s.gru_hbuf[0] + (size_t)b0 * RN_GRU_HIDDEN, s.gru_hbuf[1] + (size_t)b0 * RN_GRU_HIDDEN};
-        for (int t = 0; t < T; ++t)          // step t reads hb[t & 1] (h0 = 0: nothing) and writes hb[(t + 1) & 1]
-            if ((rc = run(h, "rn_gru_step", 2.0 * B * G * RN_GRU_HIDDEN, [&]() {
-                     return launch_rn_gru_step(s.gru_whh, dt, gi, s.gru_bhn, t ? hb[t & 1] : nullptr, hb[(t + 1) & 1], B, T, t, st);
-                 }))) return rc;
-        if (b0 == 0) s.gru_in = pre;                                 // (rawnet2_forward forgets it after a sliced forward)
-        s.gru_h = s.gru_hbuf[T & 1];
-        return run(h, "rn_gru_fc", 2.0 * B * s.gru_fc.N * s.gru_fc.K, [&]() {
-            return launch_rowvec_linear(hb[T & 1], RN_GRU_HIDDEN, s.gru_fc.W, s.gru_fc.bias, d_emb, c.embed_dim, B, c.embed_dim, RN_GRU_HIDDEN, ACT_NONE, st,
-                                        h->bf16 && h->d_lin_part ? h->d_lin_part + (size_t)b0 * h->lin_part_per_utt : nullptr, true);
-        });
-    }
-    // aggregation: attentive statistics pooling                                          RawNet2_custom.py:215-224
-    // (pre = lrelu(bn_before_agg(x)) came out of block 7's AFMS pass)
+    std::swap(p.x, p.xn);
+    p.T = Tn;
+    p.pre_is_s32 = next_s32;
+    if ((rc = p.keep_pre(bi + 1, Tn, K.cout))) return rc;
+    return x_dead ? SVHIP_OK : p.keep(blk(bi + 1, "x"), p.x, Tn, K.cout, KEEP_DT);
+}
+
+// residual block bi (RawNet_baseline.py:222-229) from x and its pre-activation: the convolutions, then the tail
+static int rn_block(RnPass& p, int bi) {
+    svhip_handle* h = p.h;
+    const RnBlock& K = p.s.blocks[bi];
+    const int T = p.T;
+    const RnStep sp = rn_step_plan(p, bi, T, p.x);
+    // (every producer of `pre` asked the same question with the same arguments)
+    if (p.pre_is_s32 != sp.ok) SV_FAIL(h, SVHIP_ERR_STATE, "RawNet2 block %d: the pre-activation's layout is not the one its convolution route reads", bi);
+    const bool tail_fused = !h->opt.rn_unfused && rn_tail_supported(p.dt, K.downsample ? T / 3 : T, K.cout);
+    bool pooled_by_conv = false;
+    const void* resid_in_tail = nullptr;
+    int rc;
+    // conv1 -> bn2 -> lrelu (epilogue), conv2 + shortcut                            :224-226
+    if ((rc = sp.ok ? rn_convs_split(p, K, sp, tail_fused, pooled_by_conv) : rn_convs_tiled(p, K, tail_fused, resid_in_tail))) return rc;
+    // conv2 + shortcut (F32X3: pooled where conv2 pools), or conv2 alone ("c2") where the tail adds the identity shortcut
+    if ((rc = p.keep(blk(bi, resid_in_tail ? "c2" : "o"), p.o, pooled_by_conv ? T / 3 : T, K.cout, KEEP_DT))) return rc;
+    return rn_block_tail(p, bi, tail_fused, pooled_by_conv, resid_in_tail);
+}
+
+// aggregation: attentive statistics pooling                                          RawNet2_custom.py:215-224
+// (pre = lrelu(bn_before_agg(x)) came out of block 7's AFMS pass)
+static int rn_aggregate_asp(RnPass& p) {
+    svhip_handle* h = p.h;
+    auto& s = p.s;
+    const int B = p.B, T = p.T, M = B * T, E = h->cfg.embed_dim;
+    int rc;
     // (1 x 1 layers, like the projection shortcut, are given the handle's T: no frame index enters a pointwise GEMM without column sums or bias_utt)
-    GemmParams pa = conv_params(h, s.att0, pre, 512, hb, 128, M, h->T);
+    GemmParams pa = conv_params(h, s.att0, p.pre, 512, p.hb, 128, M, h->T);
     pa.act1 = ACT_LRELU001;
     if ((rc = conv_gemm(h, s.att0, pa))) return rc;
-    float* rn_logits = s.logits + (size_t)b0 * T * 512;
-    GemmParams pl = conv_params(h, s.att3, hb, 128, rn_logits, 512, M, h->T);
+    float* logits = s.logits + (size_t)p.b0 * T * 512;
+    GemmParams pl = conv_params(h, s.att3, p.hb, 128, logits, 512, M, h->T);
     pl.out_f32 = 1;
     if ((rc = conv_gemm(h, s.att3, pl))) return rc;
-    if ((rc = keep("rn_logits", rn_logits, T, 512, KEEP_F32))) return rc;
-    if ((rc = run(h, "rn_attn_pool", 0, [&]() { return launch_rn_attn_pool(rn_logits, pre, dt, B, T, 512, rn_pooled, st); }))) return rc;
-    if ((rc = run(h, "rn_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
-             // (16-bit handles, full batches: the K-split MFMA form — fp32-grade handles keep ONE kernel for every batch size here)
-             return launch_rowvec_linear(rn_pooled, 1024, s.fc.W, s.fc.bias, d_emb, c.embed_dim, B, c.embed_dim, 1024, ACT_NONE, st,
-                                         h->bf16 && h->d_lin_part ? h->d_lin_part + (size_t)b0 * h->lin_part_per_utt : nullptr, true);
-         }))) return rc;
-    return SVHIP_OK;
+    if ((rc = p.keep("rn_logits", logits, T, 512, KEEP_F32))) return rc;
+    if ((rc = run(h, "rn_attn_pool", 0, [&]() { return launch_rn_attn_pool(logits, p.pre, p.dt, B, T, 512, p.pooled, p.st); }))) return rc;
+    return run(h, "rn_fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
+        // (16-bit handles, full batches: the K-split MFMA form — fp32-grade handles keep ONE kernel for every batch size here)
+        return launch_rowvec_linear(p.pooled, 1024, s.fc.W, s.fc.bias, p.emb, E, B, E, 1024, ACT_NONE, p.st, p.lin_part, true);
+    });
+}
+
+// aggregation: GRU over the T frames, its last state through fc_after_gru            RawNet2_custom.py:196-207
+// (pre = lrelu(bn_before_gru(x)), (B T, 512) frame-major, came out of block 7's AFMS pass)
+static int rn_aggregate_gru(RnPass& p) {
+    svhip_handle* h = p.h;
+    auto& s = p.s;
+    const int B = p.B, T = p.T, G = 3 * RN_GRU_HIDDEN, E = h->cfg.embed_dim;
+    int rc;
+    float* gi = s.gru_gi + (size_t)p.b0 * T * G;
+    GemmParams pg = conv_params(h, s.gru_ih, p.pre, 512, gi, G, B * T, h->T);
+    pg.out_f32 = 1;
+    const GemmPlan plan = conv_plan(h, s.gru_ih, pg);          // (an fp32 output never takes the S32 form: plan.x3 is false)
+    if (plan.x3) SV_FAIL(h, SVHIP_ERR_STATE, "rn_gru_proj: unexpected split-operand route");
+    if ((rc = run(h, "rn_gru_proj", plan.flops, [&]() { return launch_gemm(plan.q, h->bf16, p.st); }))) return rc;
+    float* hb[2] = {s.gru_hbuf[0] + (size_t)p.b0 * RN_GRU_HIDDEN, s.gru_hbuf[1] + (size_t)p.b0 * RN_GRU_HIDDEN};
+    for (int t = 0; t < T; ++t)          // step t reads hb[t & 1] (h0 = 0: nothing) and writes hb[(t + 1) & 1]
+        if ((rc = run(h, "rn_gru_step", 2.0 * B * G * RN_GRU_HIDDEN, [&]() {
+                 return launch_rn_gru_step(s.gru_whh, p.dt, gi, s.gru_bhn, t ? hb[t & 1] : nullptr, hb[(t + 1) & 1], B, T, t, p.st);
+             }))) return rc;
+    if (p.b0 == 0) s.gru_in = p.pre;                             // (rawnet2_forward forgets it after a sliced forward)
+    s.gru_h = s.gru_hbuf[T & 1];
+    return run(h, "rn_gru_fc", 2.0 * B * s.gru_fc.N * s.gru_fc.K, [&]() {
+        return launch_rowvec_linear(hb[T & 1], RN_GRU_HIDDEN, s.gru_fc.W, s.gru_fc.bias, p.emb, E, B, E, RN_GRU_HIDDEN, ACT_NONE, p.st, p.lin_part, true);
+    });
+}
+
+// utterances [b0, b0 + B) of the call, enqueued on h->cur: front-end, fused chain, the remaining blocks, aggregation
+static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0, int B) {
+    auto& s = S(h);
+    const svhip_config& c = h->cfg;
+    const int e = h->esz;
+    const size_t at = (size_t)b0 * s.T1 * 128;                   // the slice's offset into an activation buffer (T1 x 128: the largest activation)
+    const bool conv = c.model == SVHIP_MODEL_RAWNET2_CONV;
+    RnPass p{h, s};
+    p.b0 = b0; p.B = B; p.st = h->cur; p.dt = h->dt;
+    p.wav = d_wav_all + (size_t)b0 * c.samples;
+    p.x = off(s.buf[0], at, e); p.pre = off(s.buf[1], at, e); p.hb = off(s.buf[2], at, e);
+    p.o = off(s.buf[3], at, e); p.sc = off(s.buf[4], at, e); p.xn = off(s.buf[5], at, e);
+    p.sinc_x3 = !conv && h->x3 && s.filt_x3 && !h->opt.rn_sinc_f32;
+    p.stats = conv ? nullptr : s.stats + (size_t)b0 * 2;
+    p.ln = conv ? nullptr : h->bf16 ? static_cast<char*>(s.xn) + (size_t)b0 * 2 * s.Lp * 2 : p.sinc_x3 ? static_cast<char*>(s.xn) + (size_t)b0 * 4 * s.Lp * 2 : nullptr;
+    p.mean = s.mean + (size_t)b0 * 512;
+    p.scratch = s.scratch + (size_t)b0 * 16 * 512;
+    p.part = s.part + (size_t)b0 * (rn_block128_ntiles(s.T1) + 1) * 4 * 128;
+    p.gate[0] = s.gate + (size_t)b0 * 512; p.gate[1] = s.gate + ((size_t)c.max_batch + b0) * 512;
+    p.pooled = s.pooled + (size_t)b0 * 1024;
+    p.emb = h->d_emb + (size_t)b0 * c.embed_dim;
+    p.lin_part = h->bf16 && h->d_lin_part ? h->d_lin_part + (size_t)b0 * h->lin_part_per_utt : nullptr;
+    p.T = s.T1;
+    const RnBlock& K0 = s.blocks[0];
+    p.fuse_ok = h->bf16 && !h->opt.rn_unfused;
+    p.chain0 = p.fuse_ok && rn_block128_supported(K0.cin, K0.cout, p.T, K0.downsample, K0.has_shortcut, K0.conv1.Kp, K0.conv2.Kp);
+    p.conv_fused = conv && p.chain0 && !h->opt.rn_conv_unfused;
+    int rc, first = 0;
+    if ((rc = rn_front(p)) || (rc = rn_fused_chain(p, first))) return rc;
+    for (int bi = first; bi < 8; ++bi)
+        if ((rc = rn_block(p, bi))) return rc;
+    return rn_is_gru(c.model) ? rn_aggregate_gru(p) : rn_aggregate_asp(p);
 }
 
 // whole batch: one slice, or `lanes` slices on as many streams, so that the small and under-filled kernels of one slice (the late
 // blocks are grids of 86 - 400 workgroups, the AFMS passes are latency-bound) run beside the big ones of another
 int rawnet2_forward(svhip_handle* h, const float* d_wav, int B) {
-    const int lanes = (h->lanes > 1 && B >= 16 * h->lanes && h->opt.rn_stop < 0) ? h->lanes : 1;
+    const int lanes = (h->lanes > 1 && B >= 16 * h->lanes) ? h->lanes : 1;
     ++S(h).epoch;
     const int rc = forward_lanes(h, rawnet2_forward_part, d_wav, B, lanes, ((B + lanes - 1) / lanes + 3) & ~3);
     if (lanes > 1) S(h).gru_in = nullptr;          // the slices' GRU inputs are not one (B T, 512) block
     return rc;
 }
+
 
 // ---- ragged packs of the 'conv' model --------------------------------------------------------------------------------------
 // RawNet2's rules for a pack of waveforms (RaggedCheckFn; include/svhip.h), on the host alone
@@ -788,26 +832,13 @@ static int rawnet2_rag_walk(svhip_handle* h, const RagPack& pk) {
     hipStream_t st = h->cur;
     int rc;
     ++s.epoch;
-    // option rn_keep: a copy of a packed tensor the forward has just stored (level `lvl` rows; lvl < 0: one row per utterance), on the
-    // forward's stream; nothing else reads the option
-    const bool keeping = h->opt.rn_keep != 0;
+    // option rn_keep: a packed tensor the forward has just stored (level `lvl` rows; lvl < 0: one row per utterance)
     auto keep = [&](const std::string& name, const void* src, int lvl, int cols, bool f32) -> int {
-        if (!keeping) return SVHIP_OK;
-        const size_t es = f32 || !h->bf16 ? 4 : 2;
+        if (!h->opt.rn_keep) return SVHIP_OK;
         size_t cap_rows = lvl < 0 ? B : M0cap, rows = lvl < 0 ? (size_t)n : (size_t)pk.lv[lvl].M;
         for (int l = 0; l < lvl; ++l) cap_rows /= 3;
-        RawNet2State::Kept& k = s.kept[name];
-        if (!k.buf || k.cap < cap_rows * cols * es) {
-            void* q = nullptr;
-            SV_HIP(h, hipMalloc(&q, cap_rows * cols * es));
-            h->allocs.push_back(q);
-            k.buf = q; k.cap = cap_rows * cols * es;
-        }
-        k.rows = rows; k.cols = cols; k.f32 = es == 4; k.packed = true; k.epoch = s.epoch; k.utts = n;
-        SV_HIP(h, hipMemcpyAsync(k.buf, src, rows * cols * es, hipMemcpyDeviceToDevice, st));
-        return SVHIP_OK;
+        return rn_keep(h, st, name, src, f32 ? KEEP_F32 : KEEP_DT, rows, true, cap_rows, cols, 0, rows, n);
     };
-    auto blk = [](int i, const char* what) { return "rn_b" + std::to_string(i) + "_" + what; };
     // a GEMM over the rows of level g on the generic kernel (pointwise layers need no table)
     auto gemm = [&](const ConvLayer& K, GemmParams p, const Seg& g) {
         p.rag_utt = g.utt; p.rag_row0 = g.row0;

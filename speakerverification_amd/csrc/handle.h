@@ -75,8 +75,6 @@ struct svhip_handle {
         int x3_keep_f32;          // F32X3: keep the fp32 copies of the block outputs beside the split layout
         int r2_big;               // F32X3: Res2Net steps on the R2 form of the 256 x 256 kernel instead of r2_step
         int asp_v1;               // bf16: asp_fused_kernel instead of asp_bf16_kernel
-        int rn_stop;              // RawNet2: return after this many residual blocks (0: after the sinc front-end), unfused kernel sequence
-        int rn_snap;              // RawNet2: keep block n's pre-activation as stage "rn_snap"
         int rn_unfused;           // RawNet2: the separate kernel sequence instead of rn_block128 / rn_tail / the folded shortcut
         int asnorm_slab;          // AS-norm statistics on the slab path
         int asnorm_f32mfma;       // AS-norm fused kernel on the exact fp32 MFMA instead of the split form

@@ -164,24 +164,19 @@ def test_fused_tail_fp32_matches_separate_passes(L, B, monkeypatch):
 def test_f32x3_sinc_front_end_on_split_halves_matches_the_exact_fp32_mfma(L, B):
     """Round 4: on F32X3 handles the sinc front-end runs as three fp16 MFMAs per product on half hi | lo parts of the LayerNorm output and
     of the filters (csrc/rawnet2.hip: rn_sinc_x3_kernel; 22 + 22 significant bits); option rn_sinc_f32 keeps the exact-fp32-MFMA instance.
-    Front-end outputs (option rn_stop = 0) and embeddings against each other, sample counts that are not a multiple of 8 or of a tile."""
+    Front-end outputs (option rn_keep: stage rn_front of the same forward) and embeddings against each other, sample counts that are not a
+    multiple of 8 or of a tile."""
     sd = synth.synth_state_dict(synth.rawnet2_param_spec(nb_samp=L), seed=9)
     wav = synth.synth_waveforms(B, L, seed=17)
     eng = Engine(model="rawnet2", compute="f32x3", embed_dim=320, max_batch=B, samples=L)
     eng.load_state_dict(sd)
     eng.finalize()
+    eng.set_option("rn_keep", 1)
     res = {}
     for exact in (1, 0):
         eng.set_option("rn_sinc_f32", exact)
-        eng.set_option("rn_stop", 0)
-        eng.embed_wave(wav)
-        front = eng.get_stage("rn_x").copy()
-        eng.set_option("rn_stop", -1)
-        eng.profile(True)
         emb = eng.embed_wave(wav).reshape(B, -1).copy()
-        labels = set(eng.profile_results())
-        eng.profile(False)
-        res[exact] = (front, emb)
+        res[exact] = (eng.get_stage("rn_front").copy(), emb)
     eng.close()
     f1, f0 = res[1][0], res[0][0]
     assert f1.shape == f0.shape and np.isfinite(f0).all() and np.abs(f1).max() > 0
@@ -308,14 +303,14 @@ def _ulps_bf16(a, b, bits=8):
 @pytest.mark.parametrize("L,B", [(32000, 3), (32000, 40), (20000, 7)])
 def test_fused_blocks_agree_with_the_separate_kernels_at_the_first_shared_tensor(L, B, half, monkeypatch):
     """the embedding-level bars (cosine >= 0.9, 3 % of the scale) could hide a wrong halo row or a mis-swizzled channel
-    block in one tile.  SVHIP_RN_SNAP=2 keeps lrelu(bn1(x)) as block 2 reads it — the first tensor that both the fused
-    128-channel kernels (rn_block128 x 2 + gates) and the separate kernel sequence store — and the two must agree element for
+    block in one tile.  Option rn_keep's stage rn_b2_pre is lrelu(bn1(x)) as block 2 reads it — the first tensor that both the fused
+    128-channel kernels (rn_block128 x 2 + gates; their closing rn_afms_apply stores it) and the separate kernel sequence (block
+    1's tail) store — and the two must agree element for
     element to bf16 round-off: same storage points, only the summation order of the AFMS column means differs, which moves a gate
     by ~1e-6 and so flips the rounding of a few elements by one ulp.  Geometries: one utterance per several workgroups (first tile
     at t0 = 0, short last tile), 40 utterances (workgroups that span an utterance boundary), a length whose tiles do not divide."""
     sd = synth.synth_state_dict(synth.rawnet2_param_spec(nb_samp=L), seed=2)
     wav = synth.synth_waveforms(B, L, seed=5)
-    monkeypatch.setenv("SVHIP_RN_SNAP", "2")
     snaps = {}
     for name, unfused in (("unfused", True), ("fused", False)):
         if unfused:
@@ -325,12 +320,13 @@ def test_fused_blocks_agree_with_the_separate_kernels_at_the_first_shared_tensor
         eng = Engine(model="rawnet2", compute=half, embed_dim=320, max_batch=B, samples=L)
         eng.load_state_dict(sd)
         eng.finalize()
+        eng.set_option("rn_keep", 1)
         eng.profile(True)
         eng.embed_wave(wav)
         labels = set(eng.profile_results())
         eng.profile(False)
         assert ("rn_block128" in labels) == (not unfused), labels
-        snaps[name] = eng.get_stage("rn_snap").reshape(B, -1, 128)
+        snaps[name] = eng.get_stage("rn_b2_pre").reshape(B, -1, 128)
         eng.close()
     a, b = snaps["fused"], snaps["unfused"]
     assert a.shape == b.shape and a.shape[1] == ((L - 250) // 3) // 9
@@ -396,7 +392,9 @@ def test_persistent_conv_gather_matches_the_per_tile_kernel(L, B, cus, half):
     kernel, 64-channel K tiles inside one tap, zero padding through a zero page behind the operand) whenever a layer has more tiles
     than the grid; option pw3_cus caps the grid so that these small batches take the route (several tiles per workgroup, masked last
     tiles), option cv_off keeps the per-tile kernel.  Block 2's conv1 (BN + LeakyReLU epilogue) multiplies the same K tiles in the
-    same order and rounds once (its conv2 + folded shortcut stays on the per-tile kernel): the block output must agree BIT FOR BIT.  Blocks 3 / 4 have an identity shortcut, which the persistent route hands to the block tail (sum
+    same order and rounds once (its conv2 + folded shortcut stays on the per-tile kernel): the block output must agree BIT FOR BIT
+    (option rn_keep on the forward that ships, blocks 0 and 1 as the fused chain: stage rn_b2_o, conv2 + shortcut, and stage rn_b3_x, the
+    block's output as block 3 reads it).  Blocks 3 / 4 have an identity shortcut, which the persistent route hands to the block tail (sum
     in fp32, one rounding instead of two): the embeddings agree to 16-bit round-off."""
     sd = synth.synth_state_dict(synth.rawnet2_param_spec(nb_samp=L), seed=6)
     wav = synth.synth_waveforms(B, L, seed=12)
@@ -404,21 +402,19 @@ def test_persistent_conv_gather_matches_the_per_tile_kernel(L, B, cus, half):
     eng.load_state_dict(sd)
     eng.finalize()
     eng.set_option("pw3_cus", cus)
+    eng.set_option("rn_keep", 1)          # block 2's conv2 + shortcut (rn_b2_o) and its output as block 3's identity shortcut reads it (rn_b3_x)
     res = {}
     for off in (1, 0):
         eng.set_option("cv_off", off)
-        eng.set_option("rn_stop", 3)
-        eng.embed_wave(wav)
-        x3 = eng.get_stage("rn_x").copy()
-        eng.set_option("rn_stop", -1)
         eng.profile(True)
-        emb = eng.embed_wave(wav).reshape(B, -1)
+        emb = eng.embed_wave(wav).reshape(B, -1).copy()
         labels = eng.profile_results()
         eng.profile(False)
-        res[off] = (x3, emb, labels)
+        res[off] = (eng.get_stage("rn_b3_x").copy(), emb, labels, eng.get_stage("rn_b2_o").copy())
     eng.close()
     assert "gemm_pw3cv16" not in res[1][2] and res[0][2]["gemm_pw3cv16"]["launches"] >= 3, (sorted(res[0][2]), sorted(res[1][2]))
-    assert np.isfinite(res[0][1]).all() and np.abs(res[1][0]).max() > 0
+    assert np.isfinite(res[0][1]).all() and np.abs(res[1][0]).max() > 0 and np.abs(res[1][3]).max() > 0
+    np.testing.assert_array_equal(res[0][3], res[1][3])
     np.testing.assert_array_equal(res[0][0], res[1][0])
     a, b = res[0][1], res[1][1]
     cos = (a * b).sum(1) / (np.linalg.norm(a, axis=1) * np.linalg.norm(b, axis=1))
@@ -563,7 +559,7 @@ def test_an_utterance_embeds_alike_on_both_sides_of_the_batch_size_switches(comp
 def test_symmetric_sinc_form_matches_the_251_tap_kernel():
     """Round 6: fp16 handles run the sinc front-end on the filters' symmetry — y[s] = sum_m h[125 + m] (x[c + m] + x[c - m]), K = 126 instead
     of 251, the operand formed in registers from a forward and a (half-reversed) backward fragment read, one extra fp16 rounding per sum —
-    (rn_sinc_kernel<f16, SYM>; option rn_sinc_full keeps the 251-tap kernel).  Front-end output (stage rn_x) and embeddings of the two forms
+    (rn_sinc_kernel<f16, SYM>; option rn_sinc_full keeps the 251-tap kernel).  Front-end output (stage rn_front) and embeddings of the two forms
     on the same handle; both against the exact-fp32 handle at the fp16 bars; the symmetric table exists only if every baked filter IS
     symmetric bit for bit (api_rawnet2.hip, bake_sinc)."""
     B, L = 5, 32000
@@ -572,14 +568,12 @@ def test_symmetric_sinc_form_matches_the_251_tap_kernel():
     eng = Engine(model="rawnet2", compute="f16", embed_dim=320, max_batch=B, samples=L)
     eng.load_state_dict(sd)
     eng.finalize()
+    eng.set_option("rn_keep", 1)                                       # stage rn_front: the front-end output of the same forward
     out, x0 = {}, {}
     for mode in (0, 1):
         eng.set_option("rn_sinc_full", mode)
-        eng.set_option("rn_stop", 0)                                   # stop behind the front-end: stage rn_x = its output
-        eng.embed_wave(wav)
-        x0[mode] = eng.get_stage("rn_x").copy()
-        eng.set_option("rn_stop", -1)
         out[mode] = eng.embed_wave(wav).copy()
+        x0[mode] = eng.get_stage("rn_front").copy()
     eng.set_option("rn_sinc_full", 0)
     assert np.array_equal(eng.embed_wave(wav), out[0])                 # run to run: bitwise
     eng.close()
