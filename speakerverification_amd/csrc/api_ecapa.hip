@@ -16,7 +16,7 @@ struct EcapaState : ModelState {
     void *se1_bf[3] = {}, *se2T_bf[3] = {};   // bf16 copies of both SE matrices (bf16 handles: half the L2 bytes per workgroup)
     float *aspbn_scale = nullptr, *aspbn_shift = nullptr;
 
-    bool xin_ready = false;       // the fused front-end has written X_in: ecapa_forward_part skips its prologue
+    bool xin_ready = false;       // the fused front-end has written X_in: ec_front skips the prologue
     bool x0_is_s32 = false;       // SVHIP_F32X3: the last forward wrote blocks.0's output (X0) in the split layout
     bool cat_f32_stale = false;   // SVHIP_F32X3: the last forward left the block outputs only in cat_s32 (svhip_get_stage converts on demand)
     bool h2_is_s32 = false;       // SVHIP_F32X3: the last forward's block-3 Res2Net chain output exists only in h2_s32 (the R2 step kernels)
@@ -30,7 +30,7 @@ struct EcapaState : ModelState {
     void* MFA = nullptr;          // (M, 3C)
     void* ATT = nullptr;          // (M, 128)
     float* LOGITS = nullptr;      // (M, 3C) fp32
-    float *d_mean = nullptr, *d_s1 = nullptr, *d_s2 = nullptr, *d_gstats = nullptr, *d_ctx = nullptr;
+    float *d_mean = nullptr, *d_s2 = nullptr, *d_gstats = nullptr, *d_ctx = nullptr;
     float *d_pool_raw = nullptr, *d_pool_bn = nullptr;
 
     // ragged batches (svhip_embed_wave_ragged / svhip_embed_features_ragged): allocated by the handle's first ragged call
@@ -152,7 +152,6 @@ int ecapa_alloc(svhip_handle* h) {
     if ((rc = actbuf(h, &s.ATT, M * 128))) return rc;
     if ((rc = dev_alloc(h, &s.LOGITS, M * C3))) return rc;
     if ((rc = dev_alloc(h, &s.d_mean, B * C))) return rc;
-    if ((rc = dev_alloc(h, &s.d_s1, B * 128))) return rc;
     if ((rc = dev_alloc(h, &s.d_s2, B * C))) return rc;
     if ((rc = dev_alloc(h, &s.d_gstats, B * 2 * C3))) return rc;
     if ((rc = dev_alloc(h, &s.d_ctx, B * 128))) return rc;
@@ -171,223 +170,348 @@ int ecapa_alloc(svhip_handle* h) {
     return SVHIP_OK;
 }
 
-// ECAPA_TDNN.forward (models/ECAPA_TDNN.py:460-502) on device-resident features (B, n_mels, T)
-// for the utterances [b0, b0 + B) of the call, enqueued on h->cur.  Every workspace buffer is frame-major, so a
-// batch slice is just a row offset: two slices can run concurrently on two streams (lanes).
-static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, int B) {
-    auto& s = S(h);
-    const svhip_config& c = h->cfg;
-    const int T = h->T, M = B * T, C = c.channels, C3 = 3 * C, C8 = C / 8, e = h->esz;
-    const bool bf = h->bf16;
-    hipStream_t st = h->cur;
-    const size_t r0 = (size_t)b0 * T;                       // first activation row of the slice
-    const float* d_feat = d_feat_all + (size_t)b0 * c.n_mels * T;
-    void* X_in = off(h->X_in, r0 * c.n_mels, e);
-    void* X0 = off(s.X0, r0 * C, e);
-    void* H1 = off(s.H1, r0 * C, e);
-    void* H2 = off(s.H2, r0 * C, e);
-    void* H3 = off(s.H3, r0 * C, e);
-    void* CAT = off(s.CAT, r0 * C3, e);
-    void* MFA = off(s.MFA, r0 * C3, e);
-    void* ATT = off(s.ATT, r0 * 128, e);
-    float* LOGITS = s.LOGITS + r0 * C3;
-    float* d_pstats = h->d_pstats + (size_t)b0 * c.n_mels * 2;
-    float* d_mean = s.d_mean + (size_t)b0 * C;
-    float* d_s2 = s.d_s2 + (size_t)b0 * C;
-    float* d_gstats = s.d_gstats + (size_t)b0 * 2 * C3;
-    float* d_ctx = s.d_ctx + (size_t)b0 * 128;
-    float* d_pool_raw = s.d_pool_raw + (size_t)b0 * 2 * C3;
-    float* d_pool_bn = s.d_pool_bn + (size_t)b0 * 2 * C3;
-    float* d_emb = h->d_emb + (size_t)b0 * c.embed_dim;
-    float* cs_base = ((bf || h->x3) && h->d_colsum) ? h->d_colsum + (b0 ? 2 * h->colsum_region : 0) : nullptr;
-    int rc;
+// ECAPA_TDNN.forward (models/ECAPA_TDNN.py:460-502) on device-resident features (B, n_mels, T), as steps over one slice of the call:
+// utterances [b0, b0 + B), enqueued on `st`.  Every workspace buffer is frame-major, so a batch slice is just a row offset: two slices
+// can run concurrently on two streams (lanes).
+struct EcPass {
+    svhip_handle* h;
+    EcapaState& s;
+    int b0 = 0, B = 0, M = 0;
+    hipStream_t st = nullptr;
+    const float* feat = nullptr;              // (B, n_mels, T)
+    void *X_in = nullptr, *X0 = nullptr, *H1 = nullptr, *H2 = nullptr, *H3 = nullptr, *CAT = nullptr, *MFA = nullptr, *ATT = nullptr;
+    float *LOGITS = nullptr, *d_pstats = nullptr, *d_mean = nullptr, *d_s2 = nullptr, *d_gstats = nullptr, *d_ctx = nullptr;
+    float *d_pool_raw = nullptr, *d_pool_bn = nullptr, *d_emb = nullptr;
+    float* cs_base = nullptr;                 // the lane's column-sum partials (16-bit and F32X3 handles), or null
+    float* xscale = nullptr;                  // F32X3: the lane's scale of the network input and its partial max words, or null
+    float* lin_part = nullptr;                // K-slice partials of asp_ctx and fc
+    char *h2s = nullptr, *us[2] = {};         // F32X3: the Res2Net chain output and the two step-input buffers (S32 only), or null
     // F32X3: se_apply also leaves each block output in the S32 split layout (CAT's twin), so tdnn1 of the next block and mfa read
     // their A operand without a conversion pass
-    char* cat32 = s.cat_s32 ? static_cast<char*>(s.cat_s32) + r0 * C3 * 4 : nullptr;
+    char* cat32 = nullptr;
     // ... and when every consumer of a block output takes the split operand at this batch size (tdnn1 of the next block, mfa with its
     // column sums: the persistent X3 kernel; the next se_apply reads its residual as hi + lo), the fp32 copy is not written at all
-    auto tdnn1_params = [&](int i, const void* a, int lda) { GemmParams p = conv_params(h, s.tdnn1[i], a, lda, H1, C, M, T); p.act1 = ACT_GELU; return p; };
-    GemmParams pm = conv_params(h, s.mfa, CAT, C3, MFA, C3, M, T);
-    pm.act1 = ACT_GELU;
-    pm.colsum = cs_base; pm.colsum_sq = 1; pm.colsum_stride = h->colsum_region;
-    GemmPlan gm = conv_plan(h, s.mfa, pm, cat32, C3);
-    const bool s32_only = cat32 && conv_plan(h, s.tdnn1[1], tdnn1_params(1, nullptr, C3), cat32, C3).x3 &&
-                          conv_plan(h, s.tdnn1[2], tdnn1_params(2, nullptr, C3), cat32 + (size_t)C * 4, C3).x3 && gm.x3 && (gm.colsum_groups || !pm.colsum) &&
-                          !h->opt.x3_keep_f32;
-    if (s32_only) s.cat_f32_stale = true;
-    bool b0_done = false, x0_s32 = false, b0_cv = false;
-    GemmParams q0;
-    float* xscale = h->d_xscale ? h->d_xscale + (b0 ? 4 + 256 : 0) : nullptr;
-    if (h->x3 && s.blocks0.Wcv && h->s32_buf) {
+    bool s32_only = false;
+    bool x0_s32 = false;                      // ... nor that of blocks.0's output: X0 is written in the split layout
+    // the block loop's cursor, the input of the next block: xin in the handle's type (null where only the split layout holds it),
+    // xin32 its S32 twin (null where there is none)
+    const void *xin = nullptr, *xin32 = nullptr;
+    int ldin = 0, ldin32 = 0;
+};
+
+static GemmParams ec_tdnn1_params(const EcPass& p, int i, const void* a, int lda) {
+    GemmParams q = conv_params(p.h, p.s.tdnn1[i], a, lda, p.H1, p.h->cfg.channels, p.M, p.h->T);
+    q.act1 = ACT_GELU;
+    return q;
+}
+
+// tdnn2; its epilogue also leaves per-utterance column sums (the SE squeeze) when the pw2 kernel runs
+static GemmParams ec_tdnn2_params(const EcPass& p, int i) {
+    const int C = p.h->cfg.channels;
+    GemmParams q = conv_params(p.h, p.s.tdnn2[i], p.H2, C, p.H3, C, p.M, p.h->T);
+    q.act1 = ACT_GELU;
+    q.colsum = p.cs_base; q.colsum_stride = p.h->colsum_region;
+    return q;
+}
+
+// mfa; its epilogue leaves the column sums and sums of squares of the ASP statistics where its kernel can
+static GemmParams ec_mfa_params(const EcPass& p) {
+    const int C3 = 3 * p.h->cfg.channels;
+    GemmParams q = conv_params(p.h, p.s.mfa, p.CAT, C3, p.MFA, C3, p.M, p.h->T);
+    q.act1 = ACT_GELU;
+    q.colsum = p.cs_base; q.colsum_sq = 1; q.colsum_stride = p.h->colsum_region;
+    return q;
+}
+
+// EcPass::s32_only: do tdnn1 of blocks 2 and 3 and mfa (with its column sums) all take the split operand at this batch size?
+static bool ec_s32_only(const EcPass& p) {
+    svhip_handle* h = p.h;
+    const int C = h->cfg.channels, C3 = 3 * C;
+    if (!p.cat32) return false;
+    const GemmParams pm = ec_mfa_params(p);
+    const GemmPlan gm = conv_plan(h, p.s.mfa, pm, p.cat32, C3);
+    return conv_plan(h, p.s.tdnn1[1], ec_tdnn1_params(p, 1, nullptr, C3), p.cat32, C3).x3 &&
+           conv_plan(h, p.s.tdnn1[2], ec_tdnn1_params(p, 2, nullptr, C3), p.cat32 + (size_t)C * 4, C3).x3 && gm.x3 && (gm.colsum_groups || !pm.colsum) &&
+           !h->opt.x3_keep_f32;
+}
+
+// F32X3: step j (1..7) of block i's Res2Net chain on gemm_pw3's step form; it reads U_j = c_j + y_{j-1} (S32) and writes y_j (S32, into
+// the chain output) and U_{j+1}; no fp32 copy of the chain exists
+static GemmParams ec_r2_step_params(const EcPass& p, int i, int j) {
+    const int C = p.h->cfg.channels, C8 = C / 8;
+    const ConvLayer& L = p.s.res2[i][j - 1];
+    GemmParams q = conv_params(p.h, L, p.us[(j - 1) & 1], C8, p.h2s + (size_t)j * C8 * 4, C, p.M, p.h->T);
+    q.W = L.Ws32; q.Wrows = L.N; q.x3 = 2; q.act1 = ACT_RELU;
+    if (j < 7) { q.R = static_cast<const float*>(p.H1) + (size_t)(j + 1) * C8; q.ldr = C; q.Y2 = p.us[j & 1]; q.lda2 = C8; }
+    return q;
+}
+
+// the Res2Net route of block i: seven launches of a split step kernel (F32X3), the bf16 chain in one launch, or seven per-layer GEMMs
+// (C / 8 = 128: the dedicated 128 x 128 step kernel, two workgroups per CU, any batch size; C / 8 = 64, or SVHIP_R2_BIG=1: the R2 form
+//  of the persistent 256 x 256 kernel)
+enum EcRes2 { RES2_STEP, RES2_PW3R2, RES2_CHAIN, RES2_LAYERS };
+static bool ec_res2_split(EcRes2 r) { return r == RES2_STEP || r == RES2_PW3R2; }
+static EcRes2 ec_res2_plan(const EcPass& p, int i) {
+    svhip_handle* h = p.h;
+    const int C = h->cfg.channels;
+    const ConvLayer& L = p.s.res2[i][0];
+    if (h->x3 && p.h2s && p.us[0] && p.us[1] && L.Ws32) {
+        const GemmParams q1 = ec_r2_step_params(p, i, 1);
+        if (!h->opt.r2_big && r2_step_supported(q1) &&
+            conv_plan(h, p.s.tdnn2[i], ec_tdnn2_params(p, i), p.h2s, C).x3)      // (tdnn2 must be able to read the chain output in the split layout)
+            return RES2_STEP;
+        if (gemm_pw3r2_supported(q1)) return RES2_PW3R2;
+    }
+    return h->bf16 && res2net_chain_supported(C, h->T, L.dil, L.Kp) ? RES2_CHAIN : RES2_LAYERS;
+}
+
+// the attention-head route.  bf16: 16 waves per CU, lane-local online softmax (asp_x3.hip's bf16 form: 0.195 against 0.264 ms at
+// B = 256, any T); the one-wave-per-SIMD kernel keeps the channel counts that are not multiples of 256 (and SVHIP_ASP_V1=1: the tests
+// compare the two).  F32X3: asp_x3.  Otherwise the asp.conv GEMM and asp_pool
+enum EcHead { HEAD_BF16, HEAD_FUSED, HEAD_X3, HEAD_POOL };
+static EcHead ec_head_plan(const EcPass& p) {
+    svhip_handle* h = p.h;
+    const auto& s = p.s;
+    const int T = h->T, C3 = 3 * h->cfg.channels;
+    if (h->bf16 && C3 % 256 == 0 && s.asp_tdnn.N == 128 && s.asp_conv.Kp == 128 && !h->opt.asp_v1) return HEAD_BF16;
+    if (h->bf16 && asp_fused_supported(T, C3, s.asp_tdnn.N, s.asp_conv.Kp)) return HEAD_FUSED;
+    if (h->x3 && s.asp_conv.Ws32 && asp_x3_supported(T, C3, s.asp_tdnn.N, s.asp_conv.K)) return HEAD_X3;
+    return HEAD_POOL;
+}
+
+// the front-end: the prologue (unless the fused fbank wrote X_in), then blocks.0 on the conv-gather split kernel or on conv_gemm
+static int ec_front(EcPass& p) {
+    svhip_handle* h = p.h;
+    auto& s = p.s;
+    const svhip_config& c = h->cfg;
+    const int T = h->T, M = p.M, C = c.channels;
+    const ConvLayer& L = s.blocks0;
+    float* xscale = p.xscale;
+    bool b0_cv = false;
+    GemmParams q;
+    int rc;
+    if (h->x3 && L.Wcv && h->s32_buf) {
         // F32X3: blocks.0 on the persistent kernel's conv-gather form: the features go to the S32 layout with rows zero-padded to
         // cv_cin channels (one small pass), the im2col view is formed by the operand DMAs
-        const ConvLayer& L = s.blocks0;
-        GemmParams& q = q0;
-        q = conv_params(h, L, h->s32_buf, L.cv_cin, X0, C, M, T);
+        q = conv_params(h, L, h->s32_buf, L.cv_cin, p.X0, C, M, T);
         q.W = L.Wcv; q.Wrows = L.N; q.x3 = 2; q.K = L.taps * L.cv_cin; q.Kp = L.cv_Kp; q.cin = L.cv_cin; q.act1 = ACT_GELU;
         // (with s32_only and tdnn1 of the first block on the X3 kernel, X0 itself is written in the split layout: no conversion pass,
         //  block 1's residual is read as hi + lo, svhip_get_stage rebuilds the fp32 view)
-        q.y_s32 = (s32_only && conv_plan(h, s.tdnn1[0], tdnn1_params(0, nullptr, C), X0, C).x3) ? 1 : 0;
+        q.y_s32 = (p.s32_only && conv_plan(h, s.tdnn1[0], ec_tdnn1_params(p, 0, nullptr, C), p.X0, C).x3) ? 1 : 0;
         q.in_scale = xscale;
         b0_cv = gemm_pw3cv_supported(q);
     }
     // the prologue's range guard (F32X3: half-precision planes carry |x| <= 65504): with the scaled first convolution only a non-finite
     // input is reported — a finite one of any magnitude is brought into the planes' range by an exact power of two (round 6)
     if (!s.xin_ready && (rc = run(h, "prologue", 0, [&]() {
-             return launch_prologue(d_feat, X_in, bf, B, c.n_mels, T, c.log_input, h->in_w, h->in_b, d_pstats, st,
+             return launch_prologue(p.feat, p.X_in, h->bf16, p.B, c.n_mels, T, c.log_input, h->in_w, h->in_b, p.d_pstats, p.st,
                                     h->x3 ? h->d_status : nullptr, h->host_flag_dev, (b0_cv && xscale) ? 3.0e38f : 65504.0f);
          }))) return rc;
     if (b0_cv) {
-        const ConvLayer& L = s.blocks0;
         if (xscale && (rc = run(h, "in_scale", 0, [&]() {
-                 return launch_in_scale(static_cast<const float*>(X_in), (int64_t)M * c.n_mels, reinterpret_cast<uint32_t*>(xscale + 4), xscale, st, L.cv_wscale);
+                 return launch_in_scale(static_cast<const float*>(p.X_in), (int64_t)M * c.n_mels, reinterpret_cast<uint32_t*>(xscale + 4), xscale, p.st, L.cv_wscale);
              }))) return rc;
-        if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(X_in), c.n_mels, h->s32_buf, M, L.cv_cin, st, L.cv_cin, c.n_mels, xscale); }))) return rc;
-        if ((rc = run(h, "gemm_pw3cv", (double)M * L.flops_per_row, [&]() { return launch_gemm_pw3cv(q0, st); }))) return rc;
-        b0_done = true;
-        x0_s32 = q0.y_s32 != 0;
-    }
-    if (!b0_done) {
-        GemmParams p = conv_params(h, s.blocks0, X_in, c.n_mels, X0, C, M, T);
-        p.act1 = ACT_GELU;
-        if ((rc = conv_gemm(h, s.blocks0, p))) return rc;
-    }
-    s.x0_is_s32 = x0_s32;
-    const void* xin = x0_s32 ? nullptr : X0;
-    int ldin = C;
-    const void* xin32 = x0_s32 ? X0 : nullptr;
-    int ldin32 = C;
-    for (int i = 0; i < 3; ++i) {
-        // F32X3: seven launches of gemm_pw3's Res2Net step form; step j reads U_j = c_j + y_{j-1} (S32) and writes y_j (S32, into the
-        // chain output) and U_{j+1}; no fp32 copy of the chain exists
-        char* h2s = s.h2_s32 ? static_cast<char*>(s.h2_s32) + r0 * C * 4 : nullptr;
-        char* us[2] = {s.u_s32[0] ? static_cast<char*>(s.u_s32[0]) + r0 * C8 * 4 : nullptr, s.u_s32[1] ? static_cast<char*>(s.u_s32[1]) + r0 * C8 * 4 : nullptr};
-        auto step_params = [&](int j) {
-            const ConvLayer& L = s.res2[i][j - 1];
-            GemmParams q = conv_params(h, L, us[(j - 1) & 1], C8, h2s + (size_t)j * C8 * 4, C, M, T);
-            q.W = L.Ws32; q.Wrows = L.N; q.x3 = 2; q.act1 = ACT_RELU;
-            if (j < 7) { q.R = static_cast<const float*>(H1) + (size_t)(j + 1) * C8; q.ldr = C; q.Y2 = us[j & 1]; q.lda2 = C8; }
-            return q;
-        };
-        // tdnn2; its epilogue also leaves per-utterance column sums (the SE squeeze) when the pw2 kernel runs
-        GemmParams p2 = conv_params(h, s.tdnn2[i], H2, C, H3, C, M, T);
-        p2.act1 = ACT_GELU;
-        p2.colsum = cs_base; p2.colsum_stride = h->colsum_region;
-        // (C / 8 = 128: the dedicated 128 x 128 kernel, two workgroups per CU, any batch size; C / 8 = 64, or SVHIP_R2_BIG=1: the R2 form
-        //  of the persistent 256 x 256 kernel)
-        const bool r2_small = h->x3 && h2s && us[0] && us[1] && s.res2[i][0].Ws32 && !h->opt.r2_big && r2_step_supported(step_params(1)) &&
-                              conv_plan(h, s.tdnn2[i], p2, h2s, C).x3;      // (tdnn2 must be able to read the chain output in the split layout)
-        const bool r2_plan = r2_small || (h->x3 && h2s && us[0] && us[1] && s.res2[i][0].Ws32 && gemm_pw3r2_supported(step_params(1)));
-        GemmParams p1 = tdnn1_params(i, (s32_only && (i > 0 || x0_s32)) ? nullptr : xin, ldin);
-        if (r2_plan) {      // tdnn1 writes the pass-through chunk and the first step's input in the split layout itself (when it takes the X3 kernel)
-            p1.side_a = h2s; p1.side_lda = C; p1.side_b = us[0]; p1.side_ldb = C8; p1.side_c = C8;
-        }
-        GemmPlan g1;
-        if ((rc = conv_gemm(h, s.tdnn1[i], p1, xin32, ldin32, &g1))) return rc;
-        if (i == 2) { s.h2_is_s32 = r2_plan; s.h1_split = r2_plan && g1.side; }      // (what svhip_get_stage can read back of block 3)
-        if (r2_plan) {
-            if (!g1.side) {
-                if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(H1), C, h2s, M, C8, st, C); }))) return rc;
-                if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(H1) + C8, C, us[0], M, C8, st, C8); }))) return rc;
-            }
-            for (int j = 1; j < 8; ++j) {
-                const GemmParams q = step_params(j);
-                if (r2_small) {
-                    if ((rc = run(h, "r2_step", (double)M * s.res2[i][j - 1].flops_per_row, [&]() { return launch_r2_step(q, st); }))) return rc;
-                } else if ((rc = run(h, "gemm_pw3r2", (double)M * s.res2[i][j - 1].flops_per_row, [&]() { return launch_gemm_pw3r2(q, st); }))) return rc;
-            }
-            p2.A = nullptr;      // (tdnn2 reads the chain output in the S32 layout only)
-        } else if (bf && res2net_chain_supported(C, T, s.res2[i][0].dil, s.res2[i][0].Kp)) {
-            Res2Params rp;
-            rp.H1 = H1; rp.H2 = H2; rp.ld = C; rp.T = T; rp.dil = s.res2[i][0].dil; rp.Kp = s.res2[i][0].Kp;
-            // small batches (the reference's per-file calls: B = num_eval crops): time slices, so that the chip is not left to B workgroups
-            rp.slices = h->opt.r2_slices >= 0 ? std::max(1, h->opt.r2_slices) : res2net_chain_slices(B, C, T, rp.dil, h->num_cu);
-            double fl = 0;
-            for (int j = 0; j < 7; ++j) {
-                rp.W[j] = s.res2[i][j].W; rp.bias[j] = s.res2[i][j].bias;
-                rp.scale[j] = s.res2[i][j].scale; rp.shift[j] = s.res2[i][j].shift;
-                fl += (double)M * s.res2[i][j].flops_per_row;
-            }
-            if ((rc = run(h, rp.slices > 1 ? "res2net_slices" : "res2net_chain", fl, [&]() { return launch_res2net_chain(rp, B, C, st); }))) return rc;
-        } else {
-            if ((rc = run(h, "copy_cols", 0, [&]() { return launch_copy_cols(H1, C, H2, C, bf, M, C8, st); }))) return rc;
-            for (int j = 1; j < 8; ++j) {
-                GemmParams p = conv_params(h, s.res2[i][j - 1], off(H1, (size_t)j * C8, e), C, off(H2, (size_t)j * C8, e), C, M, T);
-                p.act1 = ACT_RELU;
-                p.A2 = j >= 2 ? off(H2, (size_t)(j - 1) * C8, e) : nullptr; p.lda2 = C;
-                if ((rc = conv_gemm(h, s.res2[i][j - 1], p))) return rc;
-            }
-        }
-        GemmPlan g2;
-        if ((rc = conv_gemm(h, s.tdnn2[i], p2, r2_plan ? h2s : nullptr, C, &g2))) return rc;
-        const bool from_part = g2.colsum_groups != 0;      // the squeeze comes straight from the GEMM's column-sum partials
-        if (!from_part) {
-            if ((rc = run(h, "se_mean", 0, [&]() { return launch_colmean(H3, bf, C, B, T, C, d_mean, st); }))) return rc;
-        }
-        if ((rc = run(h, "se_mlp", 4.0 * B * 128 * C, [&]() {
-                 return launch_se_mlp(from_part ? nullptr : d_mean, from_part ? cs_base : nullptr, T,
-                                      bf ? (const void*)s.se1_bf[i] : (const void*)s.se1[i].W, s.se1[i].bias,
-                                      bf ? (const void*)s.se2T_bf[i] : (const void*)s.se2T[i], s.se2[i].bias, d_s2, bf, B, C, 128, st,
-                                      from_part ? g2.colsum_groups : 8);      // (8: any count the kernel takes; no partials are read)
-             }))) return rc;
-        void* xout = off(CAT, (size_t)i * C, e);
-        void* xout32 = cat32 ? cat32 + (size_t)i * C * 4 : nullptr;
-        if ((rc = run(h, "se_apply", 0, [&]() {
-                 return launch_se_apply(H3, C, d_s2, xin, ldin, s32_only ? nullptr : xout, C3, bf, B, T, C, st, xout32, C3,
-                                        s32_only && (i > 0 || x0_s32) ? xin32 : nullptr, ldin32);
-             })))
-            return rc;
-        xin = xout;
-        xin32 = xout32;
-        ldin = C3;
-        ldin32 = C3;
-    }
-    if (s32_only) pm.A = nullptr;
-    if ((rc = conv_gemm(h, s.mfa, pm, cat32, C3, &gm))) return rc;
-    if (gm.colsum_groups) {
-        if ((rc = run(h, "colsum_finalize", 0, [&]() { return launch_colsum_finalize(cs_base, h->colsum_region, true, B, T, C3, M, d_gstats, 1e-12f, st, gm.colsum_groups); }))) return rc;
+        if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(p.X_in), c.n_mels, h->s32_buf, M, L.cv_cin, p.st, L.cv_cin, c.n_mels, xscale); }))) return rc;
+        if ((rc = run(h, "gemm_pw3cv", (double)M * L.flops_per_row, [&]() { return launch_gemm_pw3cv(q, p.st); }))) return rc;
+        p.x0_s32 = q.y_s32 != 0;
     } else {
-        if ((rc = run(h, "asp_gstats", 0, [&]() { return launch_colstats(MFA, bf, C3, B, T, C3, d_gstats, 1e-12f, st); }))) return rc;
+        GemmParams g = conv_params(h, L, p.X_in, c.n_mels, p.X0, C, M, T);
+        g.act1 = ACT_GELU;
+        if ((rc = conv_gemm(h, L, g))) return rc;
     }
-    if ((rc = run(h, "asp_ctx", 2.0 * B * 128 * 2 * C3, [&]() {
-             return launch_rowvec_linear(d_gstats, 2 * C3, s.asp_ctx.W, s.asp_ctx.bias, d_ctx, 128, B, 128, 2 * C3, ACT_NONE, st, h->d_lin_part + (size_t)b0 * h->lin_part_per_utt);
-         }))) return rc;
-    GemmParams pa = conv_params(h, s.asp_tdnn, MFA, C3, ATT, 128, M, T);
-    pa.act1 = ACT_RELU; pa.act2 = ACT_TANH;
-    pa.bias_utt = d_ctx; pa.ld_bu = 128;
-    if ((rc = conv_gemm(h, s.asp_tdnn, pa))) return rc;
-    // bf16: 16 waves per CU, lane-local online softmax (asp_x3.hip's bf16 form: 0.195 against 0.264 ms at B = 256, any T); the
-    // one-wave-per-SIMD kernel keeps the channel counts that are not multiples of 256 (and SVHIP_ASP_V1=1: the tests compare the two)
-    const bool asp_v2 = bf && C3 % 256 == 0 && s.asp_tdnn.N == 128 && s.asp_conv.Kp == 128 && !h->opt.asp_v1;
-    if (asp_v2 || (bf && asp_fused_supported(T, C3, s.asp_tdnn.N, s.asp_conv.Kp))) {
-        AspFusedParams ap;
-        ap.att = ATT; ap.W = s.asp_conv.W; ap.Kp = s.asp_conv.Kp; ap.bias = s.asp_conv.bias;
-        ap.X = MFA; ap.ldx = C3; ap.T = T; ap.C = C3;
-        ap.bn_scale = s.aspbn_scale; ap.bn_shift = s.aspbn_shift;
-        ap.pooled_raw = d_pool_raw; ap.pooled_bn = d_pool_bn; ap.eps = 1e-12f;
-        if (asp_v2) {
-            if ((rc = run(h, "asp_bf16", (double)M * s.asp_conv.flops_per_row, [&]() { return launch_asp_bf16(ap, d_gstats, 2 * C3, B, st); }))) return rc;
-        } else
-        if ((rc = run(h, "asp_fused", (double)M * s.asp_conv.flops_per_row, [&]() { return launch_asp_fused(ap, B, st); }))) return rc;
-    } else if (h->x3 && s.asp_conv.Ws32 && asp_x3_supported(T, C3, s.asp_tdnn.N, s.asp_conv.K)) {
-        AspX3Params ap;
-        ap.att = (const float*)ATT; ap.Ws32 = s.asp_conv.Ws32; ap.X = (const float*)MFA; ap.ldx = C3; ap.T = T; ap.C = C3;
-        ap.mref = d_gstats; ap.mref_ld = 2 * C3;                  // [mean | std] per utterance: the means
-        ap.bn_scale = s.aspbn_scale; ap.bn_shift = s.aspbn_shift;
-        ap.pooled_raw = d_pool_raw; ap.pooled_bn = d_pool_bn; ap.eps = 1e-12f;
-        if ((rc = run(h, "asp_x3", (double)M * s.asp_conv.flops_per_row, [&]() { return launch_asp_x3(ap, B, st); }))) return rc;
-    } else {
-        GemmParams p = conv_params(h, s.asp_conv, ATT, 128, LOGITS, C3, M, T);
-        p.out_f32 = 1;
-        if ((rc = conv_gemm(h, s.asp_conv, p))) return rc;
-        if ((rc = run(h, "asp_pool", 0, [&]() {
-                 return launch_asp_pool(LOGITS, MFA, bf, C3, B, T, C3, s.aspbn_scale, s.aspbn_shift, d_pool_raw, d_pool_bn, 1e-12f, 0.0f, st);
-             }))) return rc;
-    }
-    if ((rc = run(h, "fc", 2.0 * B * s.fc.N * s.fc.K, [&]() {
-             return launch_rowvec_linear(d_pool_bn, 2 * C3, s.fc.W, s.fc.bias, d_emb, c.embed_dim, B, c.embed_dim, 2 * C3, ACT_NONE, st, h->d_lin_part + (size_t)b0 * h->lin_part_per_utt);
-         }))) return rc;
+    s.x0_is_s32 = p.x0_s32;
+    p.xin = p.x0_s32 ? nullptr : p.X0;
+    p.xin32 = p.x0_s32 ? p.X0 : nullptr;
+    p.ldin = p.ldin32 = C;
     return SVHIP_OK;
+}
+
+// block i's Res2Net: H1 -> H2, or on the split routes the S32 chain output h2s (tdnn1_side: tdnn1 already wrote the pass-through
+// chunk and the first step's input in the split layout)
+static int ec_res2(EcPass& p, int i, EcRes2 route, bool tdnn1_side) {
+    svhip_handle* h = p.h;
+    auto& s = p.s;
+    const int T = h->T, M = p.M, C = h->cfg.channels, C8 = C / 8, e = h->esz;
+    const bool bf = h->bf16;
+    int rc;
+    if (route == RES2_CHAIN) {
+        Res2Params rp;
+        rp.H1 = p.H1; rp.H2 = p.H2; rp.ld = C; rp.T = T; rp.dil = s.res2[i][0].dil; rp.Kp = s.res2[i][0].Kp;
+        // small batches (the reference's per-file calls: B = num_eval crops): time slices, so that the chip is not left to B workgroups
+        rp.slices = h->opt.r2_slices >= 0 ? std::max(1, h->opt.r2_slices) : res2net_chain_slices(p.B, C, T, rp.dil, h->num_cu);
+        double fl = 0;
+        for (int j = 0; j < 7; ++j) {
+            rp.W[j] = s.res2[i][j].W; rp.bias[j] = s.res2[i][j].bias;
+            rp.scale[j] = s.res2[i][j].scale; rp.shift[j] = s.res2[i][j].shift;
+            fl += (double)M * s.res2[i][j].flops_per_row;
+        }
+        return run(h, rp.slices > 1 ? "res2net_slices" : "res2net_chain", fl, [&]() { return launch_res2net_chain(rp, p.B, C, p.st); });
+    }
+    if (route == RES2_LAYERS) {
+        if ((rc = run(h, "copy_cols", 0, [&]() { return launch_copy_cols(p.H1, C, p.H2, C, bf, M, C8, p.st); }))) return rc;
+        for (int j = 1; j < 8; ++j) {
+            GemmParams q = conv_params(h, s.res2[i][j - 1], off(p.H1, (size_t)j * C8, e), C, off(p.H2, (size_t)j * C8, e), C, M, T);
+            q.act1 = ACT_RELU;
+            q.A2 = j >= 2 ? off(p.H2, (size_t)(j - 1) * C8, e) : nullptr; q.lda2 = C;
+            if ((rc = conv_gemm(h, s.res2[i][j - 1], q))) return rc;
+        }
+        return SVHIP_OK;
+    }
+    if (!tdnn1_side) {
+        if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(p.H1), C, p.h2s, M, C8, p.st, C); }))) return rc;
+        if ((rc = run(h, "split_s32", 0, [&]() { return launch_split_s32(static_cast<const float*>(p.H1) + C8, C, p.us[0], M, C8, p.st, C8); }))) return rc;
+    }
+    for (int j = 1; j < 8; ++j) {
+        const GemmParams q = ec_r2_step_params(p, i, j);
+        if ((rc = run(h, route == RES2_STEP ? "r2_step" : "gemm_pw3r2", (double)M * s.res2[i][j - 1].flops_per_row, [&]() {
+                 return route == RES2_STEP ? launch_r2_step(q, p.st) : launch_gemm_pw3r2(q, p.st);
+             }))) return rc;
+    }
+    return SVHIP_OK;
+}
+
+// SE-Res2Net block i: tdnn1 (with its side outputs), the Res2Net, tdnn2 (with its column sums), the SE squeeze, gate and residual;
+// the cursor moves on to the block's output in CAT
+static int ec_block(EcPass& p, int i) {
+    svhip_handle* h = p.h;
+    auto& s = p.s;
+    const int T = h->T, B = p.B, C = h->cfg.channels, C3 = 3 * C, C8 = C / 8, e = h->esz;
+    const bool bf = h->bf16;
+    const EcRes2 route = ec_res2_plan(p, i);
+    const bool split = ec_res2_split(route);
+    GemmParams p1 = ec_tdnn1_params(p, i, p.xin, p.ldin), p2 = ec_tdnn2_params(p, i);
+    GemmPlan g1, g2;
+    int rc;
+    if (split) {
+        // tdnn1 writes the pass-through chunk and the first step's input in the split layout itself (when it takes the X3 kernel)
+        p1.side_a = p.h2s; p1.side_lda = C; p1.side_b = p.us[0]; p1.side_ldb = C8; p1.side_c = C8;
+        p2.A = nullptr;      // (tdnn2 reads the chain output in the S32 layout only)
+    }
+    if ((rc = conv_gemm(h, s.tdnn1[i], p1, p.xin32, p.ldin32, &g1))) return rc;
+    if (i == 2) { s.h2_is_s32 = split; s.h1_split = split && g1.side; }      // (what svhip_get_stage can read back of block 3)
+    if ((rc = ec_res2(p, i, route, g1.side))) return rc;
+    if ((rc = conv_gemm(h, s.tdnn2[i], p2, split ? p.h2s : nullptr, C, &g2))) return rc;
+    const bool from_part = g2.colsum_groups != 0;      // the squeeze comes straight from the GEMM's column-sum partials
+    if (!from_part) {
+        if ((rc = run(h, "se_mean", 0, [&]() { return launch_colmean(p.H3, bf, C, B, T, C, p.d_mean, p.st); }))) return rc;
+    }
+    if ((rc = run(h, "se_mlp", 4.0 * B * 128 * C, [&]() {
+             return launch_se_mlp(from_part ? nullptr : p.d_mean, from_part ? p.cs_base : nullptr, T,
+                                  bf ? (const void*)s.se1_bf[i] : (const void*)s.se1[i].W, s.se1[i].bias,
+                                  bf ? (const void*)s.se2T_bf[i] : (const void*)s.se2T[i], s.se2[i].bias, p.d_s2, bf, B, C, 128, p.st,
+                                  from_part ? g2.colsum_groups : 8);      // (8: any count the kernel takes; no partials are read)
+         }))) return rc;
+    void* xout = p.s32_only ? nullptr : off(p.CAT, (size_t)i * C, e);
+    void* xout32 = p.cat32 ? p.cat32 + (size_t)i * C * 4 : nullptr;
+    // (the residual is read in the split layout only where the input has no copy in the handle's type)
+    if ((rc = run(h, "se_apply", 0, [&]() {
+             return launch_se_apply(p.H3, C, p.d_s2, p.xin, p.ldin, xout, C3, bf, B, T, C, p.st, xout32, C3, p.xin ? nullptr : p.xin32, p.ldin32);
+         }))) return rc;
+    p.xin = xout;
+    p.xin32 = xout32;
+    p.ldin = p.ldin32 = C3;
+    return SVHIP_OK;
+}
+
+// mfa over the three block outputs, and the ASP statistics [mean | std] per utterance: from mfa's column sums, or by their own kernel
+static int ec_mfa(EcPass& p) {
+    svhip_handle* h = p.h;
+    const int T = h->T, B = p.B, C3 = 3 * h->cfg.channels;
+    GemmParams pm = ec_mfa_params(p);
+    GemmPlan gm;
+    int rc;
+    if (p.s32_only) pm.A = nullptr;
+    if ((rc = conv_gemm(h, p.s.mfa, pm, p.cat32, C3, &gm))) return rc;
+    if (gm.colsum_groups)
+        return run(h, "colsum_finalize", 0, [&]() { return launch_colsum_finalize(p.cs_base, h->colsum_region, true, B, T, C3, p.M, p.d_gstats, 1e-12f, p.st, gm.colsum_groups); });
+    return run(h, "asp_gstats", 0, [&]() { return launch_colstats(p.MFA, h->bf16, C3, B, T, C3, p.d_gstats, 1e-12f, p.st); });
+}
+
+// the attention head: asp.tdnn (the time-constant columns of its input as the per-utterance bias asp_ctx), asp.conv, softmax over
+// time and the weighted statistics, asp_bn — on the route of ec_head_plan
+static int ec_head(EcPass& p) {
+    svhip_handle* h = p.h;
+    auto& s = p.s;
+    const int T = h->T, B = p.B, M = p.M, C3 = 3 * h->cfg.channels;
+    int rc;
+    if ((rc = run(h, "asp_ctx", 2.0 * B * 128 * 2 * C3, [&]() {
+             return launch_rowvec_linear(p.d_gstats, 2 * C3, s.asp_ctx.W, s.asp_ctx.bias, p.d_ctx, 128, B, 128, 2 * C3, ACT_NONE, p.st, p.lin_part);
+         }))) return rc;
+    GemmParams pa = conv_params(h, s.asp_tdnn, p.MFA, C3, p.ATT, 128, M, T);
+    pa.act1 = ACT_RELU; pa.act2 = ACT_TANH;
+    pa.bias_utt = p.d_ctx; pa.ld_bu = 128;
+    if ((rc = conv_gemm(h, s.asp_tdnn, pa))) return rc;
+    const EcHead head = ec_head_plan(p);
+    const double fl = (double)M * s.asp_conv.flops_per_row;
+    if (head == HEAD_BF16 || head == HEAD_FUSED) {
+        AspFusedParams ap;
+        ap.att = p.ATT; ap.W = s.asp_conv.W; ap.Kp = s.asp_conv.Kp; ap.bias = s.asp_conv.bias;
+        ap.X = p.MFA; ap.ldx = C3; ap.T = T; ap.C = C3;
+        ap.bn_scale = s.aspbn_scale; ap.bn_shift = s.aspbn_shift;
+        ap.pooled_raw = p.d_pool_raw; ap.pooled_bn = p.d_pool_bn; ap.eps = 1e-12f;
+        if (head == HEAD_BF16) return run(h, "asp_bf16", fl, [&]() { return launch_asp_bf16(ap, p.d_gstats, 2 * C3, B, p.st); });
+        return run(h, "asp_fused", fl, [&]() { return launch_asp_fused(ap, B, p.st); });
+    }
+    if (head == HEAD_X3) {
+        AspX3Params ap;
+        ap.att = (const float*)p.ATT; ap.Ws32 = s.asp_conv.Ws32; ap.X = (const float*)p.MFA; ap.ldx = C3; ap.T = T; ap.C = C3;
+        ap.mref = p.d_gstats; ap.mref_ld = 2 * C3;                  // [mean | std] per utterance: the means
+        ap.bn_scale = s.aspbn_scale; ap.bn_shift = s.aspbn_shift;
+        ap.pooled_raw = p.d_pool_raw; ap.pooled_bn = p.d_pool_bn; ap.eps = 1e-12f;
+        return run(h, "asp_x3", fl, [&]() { return launch_asp_x3(ap, B, p.st); });
+    }
+    GemmParams pl = conv_params(h, s.asp_conv, p.ATT, 128, p.LOGITS, C3, M, T);
+    pl.out_f32 = 1;
+    if ((rc = conv_gemm(h, s.asp_conv, pl))) return rc;
+    return run(h, "asp_pool", 0, [&]() {
+        return launch_asp_pool(p.LOGITS, p.MFA, h->bf16, C3, B, T, C3, s.aspbn_scale, s.aspbn_shift, p.d_pool_raw, p.d_pool_bn, 1e-12f, 0.0f, p.st);
+    });
+}
+
+static int ec_fc(EcPass& p) {
+    svhip_handle* h = p.h;
+    const LinearLayer& fc = p.s.fc;
+    const int E = h->cfg.embed_dim, K = 2 * 3 * h->cfg.channels;      // [mean | std] of 3C channels
+    return run(h, "fc", 2.0 * p.B * fc.N * fc.K, [&]() {
+        return launch_rowvec_linear(p.d_pool_bn, K, fc.W, fc.bias, p.d_emb, E, p.B, E, K, ACT_NONE, p.st, p.lin_part);
+    });
+}
+
+// utterances [b0, b0 + B) of the call, enqueued on h->cur: front-end, the three SE-Res2Net blocks, mfa, attention head, fc
+static int ecapa_forward_part(svhip_handle* h, const float* d_feat_all, int b0, int B) {
+    auto& s = S(h);
+    const svhip_config& c = h->cfg;
+    const int T = h->T, C = c.channels, C3 = 3 * C, C8 = C / 8, e = h->esz;
+    const size_t r0 = (size_t)b0 * T;                       // first activation row of the slice
+    EcPass p{h, s};
+    p.b0 = b0; p.B = B; p.M = B * T; p.st = h->cur;
+    p.feat = d_feat_all + (size_t)b0 * c.n_mels * T;
+    p.X_in = off(h->X_in, r0 * c.n_mels, e);
+    p.X0 = off(s.X0, r0 * C, e);
+    p.H1 = off(s.H1, r0 * C, e); p.H2 = off(s.H2, r0 * C, e); p.H3 = off(s.H3, r0 * C, e);
+    p.CAT = off(s.CAT, r0 * C3, e); p.MFA = off(s.MFA, r0 * C3, e);
+    p.ATT = off(s.ATT, r0 * 128, e);
+    p.LOGITS = s.LOGITS + r0 * C3;
+    p.d_pstats = h->d_pstats + (size_t)b0 * c.n_mels * 2;
+    p.d_mean = s.d_mean + (size_t)b0 * C; p.d_s2 = s.d_s2 + (size_t)b0 * C;
+    p.d_gstats = s.d_gstats + (size_t)b0 * 2 * C3;
+    p.d_ctx = s.d_ctx + (size_t)b0 * 128;
+    p.d_pool_raw = s.d_pool_raw + (size_t)b0 * 2 * C3; p.d_pool_bn = s.d_pool_bn + (size_t)b0 * 2 * C3;
+    p.d_emb = h->d_emb + (size_t)b0 * c.embed_dim;
+    p.cs_base = ((h->bf16 || h->x3) && h->d_colsum) ? h->d_colsum + (b0 ? 2 * h->colsum_region : 0) : nullptr;
+    p.xscale = h->d_xscale ? h->d_xscale + (b0 ? 4 + 256 : 0) : nullptr;
+    p.lin_part = h->d_lin_part + (size_t)b0 * h->lin_part_per_utt;
+    p.cat32 = s.cat_s32 ? static_cast<char*>(s.cat_s32) + r0 * C3 * 4 : nullptr;
+    p.h2s = s.h2_s32 ? static_cast<char*>(s.h2_s32) + r0 * C * 4 : nullptr;
+    for (int k = 0; k < 2; ++k) p.us[k] = s.u_s32[k] ? static_cast<char*>(s.u_s32[k]) + r0 * C8 * 4 : nullptr;
+    p.s32_only = ec_s32_only(p);
+    if (p.s32_only) s.cat_f32_stale = true;      // (svhip_get_stage converts on demand)
+    int rc;
+    if ((rc = ec_front(p))) return rc;
+    for (int i = 0; i < 3; ++i)
+        if ((rc = ec_block(p, i))) return rc;
+    if ((rc = ec_mfa(p)) || (rc = ec_head(p))) return rc;
+    return ec_fc(p);
 }
 
 // whole batch: one lane, or two half-batches on two streams so that kernel tails, launch gaps and the
@@ -430,8 +554,8 @@ static const RagRule kEcapaRag = {1, ecapa_rag_frames, true};
 // ECAPA_TDNN.forward over the packed rows of a ragged batch (features at pk.in + pk.off[u]; tables on the device).  One slice on
 // the handle's stream.  Every GEMM goes to the generic kernel (launch_gemm_ragged: one kernel at every row count, so that a row's sums
 // do not depend on the pack); the convolutions gather through the segment table; the reductions over time are ragged.hip's.
-// It stays apart from ecapa_forward_part: that one is mostly route decisions (F32X3 planes, the Res2Net step kernels, fused attention
-// heads, two lanes) that this one has none of, and what the two share is too little to pay for one walk.
+// It stays apart from the steps of ecapa_forward_part (ec_front .. ec_fc): those are mostly route decisions (F32X3 planes, the Res2Net
+// step kernels, fused attention heads, two lanes) that this one has none of, and what the two share is too little to pay for one walk.
 static int ecapa_forward_ragged(svhip_handle* h, const RagPack& pk) {
     auto& s = S(h);
     const svhip_config& c = h->cfg;
