@@ -291,6 +291,7 @@ int svhip_rawnet2_ragged_check(const svhip_config* cfg, const int32_t* lengths, 
  * BATCH INVARIANCE as above: bit-for-bit the same embedding and stages whatever the pack; to the precision of the compute type against
  * a fixed-length call.  A non-finite input gives NaN for its own utterance only, and SVHIP_ERR_NONFINITE.
  * STAGES after a ragged call: cf_in, cf_attn0, cf_block0, cf_last (sum T'_i, 256), rows packed in utterance order; cf_pool (n, 512);
+ * with option cf_keep also cf_b<i>_ff1 | _qkv | _ctx | _att | _pw1 | _dw | _conv | _ff2 | _out and cf_logits (sum T'_i rows), cf_pool_raw (n, 512);
  * "input" (sum T_i, n_mels). */
 int svhip_conformer_embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
                                  int32_t flags, int32_t is_wave);
@@ -491,7 +492,13 @@ int svhip_synth_waveforms(svhip_handle* h, uint64_t seed, int64_t first_utt, int
  *                  "tn_prolog" (B T, H), "tn_dw0" (block 0's first depthwise output, its bias included), "tn_mega_last" (the last
  *                  mega-block's output), "tn_enc" (B T, 1536) and "tn_pool" (B, 3072, after BN) of SVHIP_MODEL_TITANET;
  *                  "cf_in" (B T', 256: the input projection), "cf_block0", "cf_attn0" (block 0's per-head attention context before
- *                  out_proj), "cf_last" (the last block's output) and "cf_pool" (B, 512, after attention_norm) of SVHIP_MODEL_CONFORMER;
+ *                  out_proj), "cf_last" (the last block's output) and "cf_pool" (B, 512, after attention_norm) of SVHIP_MODEL_CONFORMER,
+ *                  and with option "cf_keep" what its forward stored on its way: per block i = 0 .. 5 "cf_b<i>_ff1" (B T', 256: after
+ *                  the first half-step), "cf_b<i>_qkv" (B T', 768), "cf_b<i>_ctx" (the attention context), "cf_b<i>_att" (after
+ *                  out_proj and its residual), "cf_b<i>_pw1" (B T', 512), "cf_b<i>_dw" (GLU, depthwise conv, BN, Swish),
+ *                  "cf_b<i>_conv" (after pw2 and its residual), "cf_b<i>_ff2" (after the second half-step), "cf_b<i>_out" (the
+ *                  block's LayerNorm), then "cf_logits" (B T', 256 fp32: the pooling's logits) and "cf_pool_raw" (B, 512 fp32:
+ *                  [mean | std] before attention_norm) — SVHIP_ERR_STATE without the option;
  *                  "rs_stem" (B P Q, 32: channels-last, P frames x Q mel rows), "rs_layer1" .. "rs_layer4" (each stage's output, B P' Q' x C)
  *                  and "rs_pool" (B, 512 n_mels / 8 fp32: [mean | std], feature q 256 + c) of SVHIP_MODEL_RESNETSE.
  *                  Returns the element count through *count (out may be NULL to query).
@@ -510,7 +517,7 @@ double svhip_workload_flops(const svhip_handle* h);
  * "pw3_cus" (cap of the persistent GEMM grids; 0: off), "rn_unfused", "asp_v1", "r2_big", "x3_keep_f32",
  * "asnorm_slab", "asnorm_f32mfma", "asnorm_norefit", "score_f32mfma", "score_tiled", "fbank32", "fbank_unfused", "rn_sinc_full", "cv_off",
  * "pw3_tail_off", "n128_off", "r2_slices", "rn_tail_big", "rn_sinc_f32", "rn_step_off", "rn_pool_off", "layer_labels", "rn_conv_unfused",
- * "rn_keep".
+ * "rn_keep", "cf_keep".
  * Unknown names: SVHIP_ERR_INVALID. */
 int svhip_set_option(svhip_handle* h, const char* name, int32_t value);
 /* Free the scoring / metrics scratch slots of the handle (grown on demand, otherwise kept until svhip_destroy). */

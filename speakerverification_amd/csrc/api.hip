@@ -51,6 +51,7 @@ const DevOptRow kDevOpts[] = {
     SV_OPT(r2_slices, "SVHIP_R2_SLICES", OPT_NUM, -1),
     SV_OPT(rn_conv_unfused, "SVHIP_RN_CONV_UNFUSED", OPT_IS1, 0),
     SV_OPT(rn_keep, "SVHIP_RN_KEEP", OPT_IS1, 0),
+    SV_OPT(cf_keep, "SVHIP_CF_KEEP", OPT_IS1, 0),
 };
 #undef SV_OPT
 
@@ -127,6 +128,40 @@ void prof_collect(svhip_handle* h) {
 }
 
 int unknown_stage(svhip_handle* h, const std::string& name) { SV_FAIL(h, SVHIP_ERR_INVALID, "unknown stage %s", name.c_str()); }
+
+int keep_stage(svhip_handle* h, KeptStages& ks, hipStream_t st, const std::string& name, const void* src, int kind, size_t rows, bool packed,
+               size_t cap_rows, int cols, size_t row0, size_t nrows, int utts) {
+    const bool f32 = kind != KEEP_DT || !h->bf16;
+    const size_t es = f32 ? 4 : 2, need = cap_rows * cols * es;
+    KeptStages::Kept& k = ks.kept[name];
+    if (!k.buf || k.cap < need) {
+        void* q = nullptr;
+        SV_HIP(h, hipMalloc(&q, need));
+        h->allocs.push_back(q);
+        k.buf = q; k.cap = need; k.epoch = 0;
+    }
+    // (the first copy of a forward, or another shape than the earlier slices': what the buffer held does not count)
+    if (k.epoch != ks.epoch || k.rows != rows || k.cols != (size_t)cols || k.f32 != f32 || k.packed != packed) {
+        k.rows = rows; k.cols = cols; k.f32 = f32; k.packed = packed; k.epoch = ks.epoch; k.utts = 0;
+    }
+    void* dst = static_cast<char*>(k.buf) + row0 * cols * es;
+    if (kind == KEEP_S32) SV_HIP(h, launch_unsplit_s32(src, cols, static_cast<float*>(dst), cols, (int64_t)nrows, cols, st));
+    else SV_HIP(h, hipMemcpyAsync(dst, src, nrows * cols * es, hipMemcpyDeviceToDevice, st));
+    k.utts += utts;
+    return SVHIP_OK;
+}
+
+int kept_view(svhip_handle* h, const KeptStages& ks, const std::string& name, int B, const char* option, bool option_on, StageView& v) {
+    const auto it = ks.kept.find(name);
+    if (it == ks.kept.end() || it->second.epoch != ks.epoch || it->second.utts != B) {
+        if (option_on) SV_FAIL(h, SVHIP_ERR_STATE, "stage %s: the route of the last forward never stored it", name.c_str());
+        SV_FAIL(h, SVHIP_ERR_STATE, "stage %s: option %s was not set", name.c_str(), option);
+    }
+    const KeptStages::Kept& k = it->second;
+    // (a pack's rows are those of the stage's level, counted when it was kept; a fixed-length forward has `rows` per utterance)
+    v.src = k.buf; v.rows = k.packed ? k.rows : (size_t)B * k.rows; v.cols = v.ld = k.cols; v.f32 = k.f32;
+    return SVHIP_OK;
+}
 
 // A whole-batch forward: one slice on the handle's stream, or `lanes` slices of `per` utterances (the last one takes the rest) on the
 // lane streams, forked from and joined back into the handle's stream.

@@ -68,6 +68,7 @@ struct ConformerState : ModelState {
     void* last = nullptr;                 // the last block's output
     float* logits = nullptr;              // (Bmax T', 256) fp32 attention logits of the pooling
     float *pool_raw = nullptr, *pool = nullptr;         // (Bmax, 512) [mean | std], after attention_norm
+    KeptStages keep;                      // option cf_keep: copies of what the walk stored, by stage name (keep_stage fills them)
     // ragged packs (allocated by the first ragged call; the row buffers above hold rows_cap >= floor((Bmax T - 3) / 4) rows for them)
     size_t rows_cap = 0;
     std::vector<std::vector<float>> pe_host, wpos_host;   // kept from finalize: each layer's pos_proj weight; pe_host[pe_of[i]] is layer
@@ -416,6 +417,15 @@ static int conformer_walk(svhip_handle* h, const float* d_feat, int B, const Rag
     hipStream_t st = h->cur;
     int rc;
     auto gemm = [&](const ConvLayer& L, const GemmParams& p) { return g ? cf_rag_gemm(h, L, p) : conv_gemm(h, L, p); };
+    // option cf_keep: the M x cols tensor block i has just stored (i < 0: the pooling's; `utt_rows`: one row per utterance), copied on st
+    ++s.keep.epoch;
+    auto keep = [&](int i, const char* what, const void* src, int cols, bool f32 = false, bool utt_rows = false) -> int {
+        if (!h->opt.cf_keep) return SVHIP_OK;
+        const std::string name = i < 0 ? std::string("cf_") + what : "cf_b" + std::to_string(i) + "_" + what;
+        const int kind = f32 ? KEEP_F32 : KEEP_DT;
+        if (utt_rows) return keep_stage(h, s.keep, st, name, src, kind, g ? (size_t)B : 1, g != nullptr, (size_t)c.max_batch, cols, 0, (size_t)B, B);
+        return keep_stage(h, s.keep, st, name, src, kind, g ? (size_t)M : (size_t)T, g != nullptr, s.rows_cap, cols, 0, (size_t)M, B);
+    };
     // relative-position attention of block i over hid = q | k | v -> ctx; a pack's P: rows 0 .. the longest T'_u seen (conformer_ragged_pos)
     auto attn = [&](int i, void* ctx) {
         const CfBlock& K = s.blocks[i];
@@ -446,21 +456,21 @@ static int conformer_walk(svhip_handle* h, const float* d_feat, int B, const Rag
         if ((rc = gemm(K.ff1[0], f1))) return rc;
         GemmParams f2 = conv_params(h, K.ff2[0], s.hid, 4 * D, s.r, D, M, T);
         f2.scale = s.half; f2.shift = h->d_zeros; f2.R = x; f2.ldr = D;
-        if ((rc = gemm(K.ff2[0], f2))) return rc;
+        if ((rc = gemm(K.ff2[0], f2)) || (rc = keep(i, "ff1", s.r, D))) return rc;
         // xo = r + out_proj(attention(LN(r)))                                                        attention.py:75-159
         if ((rc = cf_ln(h, s.r, s.ln, K.att_g, K.att_b, M))) return rc;
-        if ((rc = gemm(K.qkv, conv_params(h, K.qkv, s.ln, D, s.hid, 3 * D, M, T)))) return rc;
-        if ((rc = attn(i, ctx))) return rc;
+        if ((rc = gemm(K.qkv, conv_params(h, K.qkv, s.ln, D, s.hid, 3 * D, M, T))) || (rc = keep(i, "qkv", s.hid, 3 * D))) return rc;
+        if ((rc = attn(i, ctx)) || (rc = keep(i, "ctx", ctx, D))) return rc;
         GemmParams po = conv_params(h, K.out, ctx, D, xo, D, M, T);
         po.R = s.r; po.ldr = D;
-        if ((rc = gemm(K.out, po))) return rc;
+        if ((rc = gemm(K.out, po)) || (rc = keep(i, "att", xo, D))) return rc;
         // r = xo + pw2(swish(BN(dw15(GLU(pw1(LN(xo)))))))                                             convolution.py:108-149
         if ((rc = cf_ln(h, xo, s.ln, K.cv_g, K.cv_b, M))) return rc;
-        if ((rc = gemm(K.pw1, conv_params(h, K.pw1, s.ln, D, s.hid, 2 * D, M, T)))) return rc;
-        if ((rc = glu_dw(K))) return rc;
+        if ((rc = gemm(K.pw1, conv_params(h, K.pw1, s.ln, D, s.hid, 2 * D, M, T))) || (rc = keep(i, "pw1", s.hid, 2 * D))) return rc;
+        if ((rc = glu_dw(K)) || (rc = keep(i, "dw", s.ctx, D))) return rc;
         GemmParams pw = conv_params(h, K.pw2, s.ctx, D, s.r, D, M, T);
         pw.R = xo; pw.ldr = D;
-        if ((rc = gemm(K.pw2, pw))) return rc;
+        if ((rc = gemm(K.pw2, pw)) || (rc = keep(i, "conv", s.r, D))) return rc;
         // ln2 = r + 0.5 FF'(r); xo = LN(ln2), and the next block's LN(xo) in the same pass
         if ((rc = cf_ln(h, s.r, s.ln, K.ff_g[1], K.ff_b[1], M))) return rc;
         GemmParams g1 = conv_params(h, K.ff1[1], s.ln, D, s.hid, 4 * D, M, T);
@@ -468,10 +478,11 @@ static int conformer_walk(svhip_handle* h, const float* d_feat, int B, const Rag
         if ((rc = gemm(K.ff1[1], g1))) return rc;
         GemmParams g2 = conv_params(h, K.ff2[1], s.hid, 4 * D, s.ln2, D, M, T);
         g2.scale = s.half; g2.shift = h->d_zeros; g2.R = s.r; g2.ldr = D;
-        if ((rc = gemm(K.ff2[1], g2))) return rc;
+        if ((rc = gemm(K.ff2[1], g2)) || (rc = keep(i, "ff2", s.ln2, D))) return rc;
         const CfBlock* nx = i + 1 < nb ? &s.blocks[i + 1] : nullptr;
         if ((rc = cf_ln(h, s.ln2, xo, K.fin_g, K.fin_b, M, nx ? s.ln : nullptr, nx ? nx->ff_g[0] : nullptr, nx ? nx->ff_b[0] : nullptr)))
             return rc;
+        if ((rc = keep(i, "out", xo, D))) return rc;
         x = xo;
     }
     // attentive statistics pooling (Conformer.py:130-142)
@@ -480,11 +491,12 @@ static int conformer_walk(svhip_handle* h, const float* d_feat, int B, const Rag
     if ((rc = gemm(s.att0, pa))) return rc;
     GemmParams pl = conv_params(h, s.att3, s.hid, 128, s.logits, D, M, T);
     pl.out_f32 = 1;
-    if ((rc = gemm(s.att3, pl))) return rc;
+    if ((rc = gemm(s.att3, pl)) || (rc = keep(-1, "logits", s.logits, D, true))) return rc;
     if ((rc = run(h, g ? "rag_asp_pool" : "cf_asp_pool", 0, [&]() {
              return g ? launch_rag_asp_pool(s.logits, x, bf, D, g->row0, B, D, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-4f, st, 1e4f)
                       : launch_asp_pool(s.logits, x, bf, D, B, T, D, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-4f, 1e4f, st);
          }))) return rc;
+    if ((rc = keep(-1, "pool_raw", s.pool_raw, 2 * D, true, true))) return rc;
     // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the ReLU epilogues would have dropped it): its
     // own row only
     if ((rc = run(h, "cf_in_check", 0, [&]() {
@@ -569,7 +581,16 @@ int conformer_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool 
     return SVHIP_OK;
 }
 
-int conformer_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // cf_in, cf_block0, cf_attn0, cf_last, cf_pool
+// the stages of option cf_keep: cf_logits, cf_pool_raw, cf_b<block>_ff1 | _qkv | _ctx | _att | _pw1 | _dw | _conv | _ff2 | _out
+static bool cf_keep_name(const std::string& n) {
+    if (n == "cf_logits" || n == "cf_pool_raw") return true;
+    if (n.size() < 7 || n.compare(0, 4, "cf_b") != 0 || n[4] < '0' || n[4] >= '0' + CF_LAYERS || n[5] != '_') return false;
+    const std::string w = n.substr(6);
+    for (const char* q : {"ff1", "qkv", "ctx", "att", "pw1", "dw", "conv", "ff2", "out"}) if (w == q) return true;
+    return false;
+}
+
+int conformer_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // cf_in, cf_block0, cf_attn0, cf_last, cf_pool; option cf_keep's
     auto& s = S(h);
     v.rows = h->rag_levels ? (size_t)h->rag_rows[1] : (size_t)h->lastB * s.Tp; v.cols = v.ld = CF_D;      // (a ragged forward: the packed rows)
     if (n == "cf_in") v.src = s.in;
@@ -577,6 +598,7 @@ int conformer_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {
     else if (n == "cf_attn0") v.src = s.attn0;
     else if (n == "cf_last") v.src = s.last;
     else if (n == "cf_pool") { v.src = s.pool; v.rows = h->lastB; v.cols = v.ld = 2 * CF_D; v.f32 = true; }
+    else if (cf_keep_name(n)) return kept_view(h, s.keep, n, h->lastB, "cf_keep", h->opt.cf_keep != 0, v);
     else return unknown_stage(h, n);
     return SVHIP_OK;
 }

@@ -54,12 +54,7 @@ struct RawNet2State : ModelState {
     float *stats = nullptr, *mean = nullptr, *gate = nullptr, *logits = nullptr, *pooled = nullptr;
     float* part = nullptr;             // fused 128-channel blocks: per-tile column sums (B, ntiles, 128)
     int T1 = 0;
-    // option rn_keep (the helper of the same name fills them): copies of what the forward stored, by stage name, `rows` per utterance or,
-    // after a ragged forward, the packed rows of all its utterances (`packed`); `cap`: the buffer's bytes.  A stage counts as kept when
-    // every utterance of the last forward (`epoch`) wrote it.
-    struct Kept { void* buf = nullptr; size_t rows = 0, cols = 0; bool f32 = false; uint64_t epoch = 0; int utts = 0; bool packed = false; size_t cap = 0; };
-    std::map<std::string, Kept> kept;
-    uint64_t epoch = 0;
+    KeptStages keep;                   // option rn_keep: copies of what the forward stored, by stage name (keep_stage fills them)
     // ragged packs of the 'conv' model: all allocated by the first ragged call, each under its own null check
     RagTables rag;                     // the tables of a call (seven levels) and the staging buffer of host waveforms
     int* rag_slice0 = nullptr;         // (RAG_LEVELS, max_batch + 1): the first slice of every utterance at every level (rn_rag_slices)
@@ -385,14 +380,7 @@ int rawnet2_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {
         if (!s.gru_in) SV_FAIL(h, SVHIP_ERR_STATE, "stage rn_gru_in: the last forward ran as several batch slices (SVHIP_LANES)");
         v.src = s.gru_in; v.rows = (size_t)B * s.gru_T; v.cols = v.ld = 512;
     }
-    else if (rn_keep_name(n)) {
-        const auto it = s.kept.find(n);
-        if (it == s.kept.end() || it->second.epoch != s.epoch || it->second.utts != B)
-            SV_FAIL(h, SVHIP_ERR_STATE, "stage %s: %s", n.c_str(), h->opt.rn_keep ? "the route of the last forward never stored it" : "option rn_keep was not set");
-        const RawNet2State::Kept& k = it->second;
-        // (a pack's rows are those of the stage's level, counted when it was kept; a fixed-length forward has `rows` per utterance)
-        v.src = k.buf; v.rows = k.packed ? k.rows : (size_t)B * k.rows; v.cols = v.ld = k.cols; v.f32 = k.f32;
-    }
+    else if (rn_keep_name(n)) return kept_view(h, s.keep, n, B, "rn_keep", h->opt.rn_keep != 0, v);
     else return unknown_stage(h, n);
     return SVHIP_OK;
 }
@@ -405,33 +393,10 @@ static GemmParams conv2sc_params(svhip_handle* h, const RnBlock& K, const void* 
     return p;
 }
 
-// Option rn_keep, for both forwards: copy `nrows` x `cols` values the forward has just stored — in the handle's type, in fp32 (KEEP_F32)
-// or in the S32 layout (KEEP_S32, kept as fp32) — to rows [row0, row0 + nrows) of stage `name`, on the forward's stream, for `utts`
-// utterances.  A fixed-length forward counts `rows` per utterance and fills a buffer of max_batch utterances slice by slice; a ragged
-// one (`packed`) keeps the `rows` packed rows of a level at once.  The buffer holds `cap_rows` rows and grows when a call needs more.
-// Nothing else reads the option: the kernels enqueued, their operands and their routes are those of a forward without it.
-enum { KEEP_DT, KEEP_F32, KEEP_S32 };
+// Option rn_keep, for both forwards: keep_stage (handle.h) on this model's stages
 static int rn_keep(svhip_handle* h, hipStream_t st, const std::string& name, const void* src, int kind, size_t rows, bool packed, size_t cap_rows,
                    int cols, size_t row0, size_t nrows, int utts) {
-    auto& s = S(h);
-    const bool f32 = kind != KEEP_DT || !h->bf16;
-    const size_t es = f32 ? 4 : 2, need = cap_rows * cols * es;
-    RawNet2State::Kept& k = s.kept[name];
-    if (!k.buf || k.cap < need) {
-        void* q = nullptr;
-        SV_HIP(h, hipMalloc(&q, need));
-        h->allocs.push_back(q);
-        k.buf = q; k.cap = need; k.epoch = 0;
-    }
-    // (the first copy of a forward, or another shape than the earlier slices': what the buffer held does not count)
-    if (k.epoch != s.epoch || k.rows != rows || k.cols != (size_t)cols || k.f32 != f32 || k.packed != packed) {
-        k.rows = rows; k.cols = cols; k.f32 = f32; k.packed = packed; k.epoch = s.epoch; k.utts = 0;
-    }
-    void* dst = static_cast<char*>(k.buf) + row0 * cols * es;
-    if (kind == KEEP_S32) SV_HIP(h, launch_unsplit_s32(src, cols, static_cast<float*>(dst), cols, (int64_t)nrows, cols, st));
-    else SV_HIP(h, hipMemcpyAsync(dst, src, nrows * cols * es, hipMemcpyDeviceToDevice, st));
-    k.utts += utts;
-    return SVHIP_OK;
+    return keep_stage(h, S(h).keep, st, name, src, kind, rows, packed, cap_rows, cols, row0, nrows, utts);
 }
 static std::string blk(int i, const char* what) { return "rn_b" + std::to_string(i) + "_" + what; }
 
@@ -763,7 +728,7 @@ static int rawnet2_forward_part(svhip_handle* h, const float* d_wav_all, int b0,
 // blocks are grids of 86 - 400 workgroups, the AFMS passes are latency-bound) run beside the big ones of another
 int rawnet2_forward(svhip_handle* h, const float* d_wav, int B) {
     const int lanes = (h->lanes > 1 && B >= 16 * h->lanes) ? h->lanes : 1;
-    ++S(h).epoch;
+    ++S(h).keep.epoch;
     const int rc = forward_lanes(h, rawnet2_forward_part, d_wav, B, lanes, ((B + lanes - 1) / lanes + 3) & ~3);
     if (lanes > 1) S(h).gru_in = nullptr;          // the slices' GRU inputs are not one (B T, 512) block
     return rc;
@@ -831,7 +796,7 @@ static int rawnet2_rag_walk(svhip_handle* h, const RagPack& pk) {
     h->cur = h->stream;
     hipStream_t st = h->cur;
     int rc;
-    ++s.epoch;
+    ++s.keep.epoch;
     // option rn_keep: a packed tensor the forward has just stored (level `lvl` rows; lvl < 0: one row per utterance)
     auto keep = [&](const std::string& name, const void* src, int lvl, int cols, bool f32) -> int {
         if (!h->opt.rn_keep) return SVHIP_OK;

@@ -95,6 +95,7 @@ struct svhip_handle {
         int r2_slices;            // bf16 Res2Net chain: time slices per utterance (-1: by batch size, 0 / 1: whole utterances, n: forced)
         int rn_conv_unfused;      // 16-bit RawNet2 'conv' handles: rn_conv3_front + plain rn_block128 instead of block 0 reading the waveform (tests, A/B)
         int rn_keep;              // RawNet2: copy what the forward stores (block inputs, outputs, gates, logits) for svhip_get_stage; the kernels enqueued stay the same (tests)
+        int cf_keep;              // Conformer: the same for every block's steps, the pooling logits and the pooled vector before attention_norm (tests)
     } opt;
     bool bf16 = false;                        // 16-bit storage handle: bf16, or fp16 when `f16` is set (the flag keeps its round-1 name)
     bool f16 = false;                         // SVHIP_F16: the 16-bit type is IEEE half (RawNet2)
@@ -296,6 +297,26 @@ struct ModelOps {
     RaggedEmbedFn* embed_ragged;
 };
 int unknown_stage(svhip_handle* h, const std::string& name);         // SVHIP_ERR_INVALID "unknown stage <name>"
+
+// api.hip: the options that keep what a forward stored on its way (rn_keep, cf_keep).  A model's state holds one KeptStages: copies of
+// what the forward stored, by stage name, `rows` per utterance or, after a ragged forward, the packed rows of all its utterances
+// (`packed`); `cap`: the buffer's bytes.  A stage counts as kept when every utterance of the last forward (`epoch`, which the forward
+// advances before its first copy) wrote it.
+struct KeptStages {
+    struct Kept { void* buf = nullptr; size_t rows = 0, cols = 0; bool f32 = false; uint64_t epoch = 0; int utts = 0; bool packed = false; size_t cap = 0; };
+    std::map<std::string, Kept> kept;
+    uint64_t epoch = 0;
+};
+// Copy `nrows` x `cols` values the forward has just stored — in the handle's type, in fp32 (KEEP_F32) or in the S32 layout (KEEP_S32,
+// kept as fp32) — to rows [row0, row0 + nrows) of stage `name`, on the forward's stream, for `utts` utterances.  A fixed-length forward
+// counts `rows` per utterance and fills a buffer of max_batch utterances slice by slice; a ragged one (`packed`) keeps the `rows`
+// packed rows of a level at once.  The buffer holds `cap_rows` rows and grows when a call needs more.  The caller reads its option
+// first; nothing else does: the kernels enqueued, their operands and their routes are those of a forward without it.
+enum { KEEP_DT, KEEP_F32, KEEP_S32 };
+int keep_stage(svhip_handle* h, KeptStages& ks, hipStream_t st, const std::string& name, const void* src, int kind, size_t rows, bool packed,
+               size_t cap_rows, int cols, size_t row0, size_t nrows, int utts);
+// svhip_get_stage of a kept stage after a forward of B utterances; option / option_on: the model's option, for SVHIP_ERR_STATE's text
+int kept_view(svhip_handle* h, const KeptStages& ks, const std::string& name, int B, const char* option, bool option_on, StageView& v);
 
 // api_ragged.hip: what the ragged calls of the models share on the host
 int refuse(std::string& err, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));      // err = the text; returns code
