@@ -553,7 +553,7 @@ static const RagRule kEcapaRag = {1, ecapa_rag_frames, true};
 
 // ECAPA_TDNN.forward over the packed rows of a ragged batch (features at pk.in + pk.off[u]; tables on the device).  One slice on
 // the handle's stream.  Every GEMM goes to the generic kernel (launch_gemm_ragged: one kernel at every row count, so that a row's sums
-// do not depend on the pack); the convolutions gather through the segment table; the reductions over time are ragged.hip's.
+// do not depend on the pack); the convolutions gather through the segment table; the reductions over time are the fixed kernels' RAG instances (launch_rag_*).
 // It stays apart from the steps of ecapa_forward_part (ec_front .. ec_fc): those are mostly route decisions (F32X3 planes, the Res2Net
 // step kernels, fused attention heads, two lanes) that this one has none of, and what the two share is too little to pay for one walk.
 static int ecapa_forward_ragged(svhip_handle* h, const RagPack& pk) {

@@ -15,7 +15,7 @@
 // (Seg).  The buffers are the fixed-length ones: a pack holds at most max_batch * T0 level-0 rows, hence at most a fifth of that at
 // level 1 and floor(max_batch * T0 / 15) at level 2, which is what CAT and the logits are sized for (the sum of T0_u / 15 can pass
 // max_batch * T2 by a few rows).  Every GEMM goes to launch_gemm_ragged and every small linear to launch_rag_linear — one kernel at
-// every row count — and the reductions over time are the per-utterance kernels of rawnet3.hip / ragged.hip, so an utterance's values
+// every row count — and the reductions over time are the per-utterance kernels of rawnet3.hip and the launch_rag_* forms, so an utterance's values
 // do not depend on the pack.
 #include <algorithm>
 #include <cmath>

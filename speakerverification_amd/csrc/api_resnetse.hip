@@ -19,7 +19,7 @@
 // back in utterance order in the buffers above, one row0 / utt table per level (RagRule: four levels).  resnetse_walk is the one walk of
 // the layers: for a pack the convolutions run on the packed form of rs_conv (every utterance tiled by rs_conv_plan of its own image, the
 // padding at its own first and last frame), the stem, the SE gate and the block tail in their segment-table forms, the two attention
-// convolutions on launch_gemm_ragged and the pooling, the input test and fc on ragged.hip's kernels, so no value of an utterance depends
+// convolutions on launch_gemm_ragged and the pooling, the input test and fc on the launch_rag_* forms, so no value of an utterance depends
 // on what it is packed with, and its stages are bit for bit those of a fixed-length handle of its length at B = 1.
 // CAPACITY of a pack: 1 <= n <= max_batch and sum_u 8 ceil(T_u / 8) <= max_batch T.  The subsampling rounds up, so sum T_u <= max_batch T
 // alone does not protect the deeper levels (max_batch = 4, T = 40, frames 37 + 41 + 41 + 41 = 160, but 19 + 21 + 21 + 21 = 82 > 4 * 20 rows

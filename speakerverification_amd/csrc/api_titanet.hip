@@ -18,7 +18,7 @@
 // network has no subsampling, so the pack has one frame level and one row0 table.  titanet_walk is the one walk of the layers: for a
 // pack every GEMM goes through launch_gemm_ragged (the prolog's three taps zero-padded at each utterance's own ends), the depthwise
 // convs and the block tail run in their segment-table forms, and the SE squeeze, the pooling, the input test and the last linear layer
-// are ragged.hip's: no value of an utterance depends on what it is packed with.
+// are the fixed kernels' RAG instances (launch_rag_*): no value of an utterance depends on what it is packed with.
 #include <cmath>
 #include <cstdlib>
 

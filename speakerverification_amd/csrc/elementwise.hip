@@ -10,16 +10,26 @@ namespace {
 
 // ---- mean / std over the T rows of each utterance ---------------------------------------------
 // grid (ceil(C / (64*VEC)), B), block 256: wave w takes frames t = w, w+4, ...; lane owns VEC channels.
-template <typename T, bool STD>
+// RAG (a pack, B = n): utterance b owns the rows [rag_row0[b], rag_row0[b + 1]) and Tn is its own length.  Every kernel below with this
+// flag differs between its two instances in these first lines alone: the sums run over the utterance's own frames in an order fixed by the
+// frame index, so a packed utterance gets the arithmetic — and the error bars — of a fixed-length batch of its length.
+template <typename T, bool STD, bool RAG>
 __global__ __launch_bounds__(256) void colstats_kernel(const T* __restrict__ X, int ldx, int Tn, int C,
-                                                       float* __restrict__ out, int ld_out, float eps) {
+                                                       float* __restrict__ out, int ld_out, float eps, const int* __restrict__ rag_row0) {
     constexpr int VEC = Vec16<T>::N;
     __shared__ float red[4][64 * VEC];
     const int b = blockIdx.y;
+    int64_t row0;
+    if constexpr (RAG) {
+        row0 = rag_row0[b];
+        Tn = rag_row0[b + 1] - (int)row0;
+    } else {
+        row0 = (int64_t)b * Tn;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c0 = (blockIdx.x * 64 + lane) * VEC;
     const bool ok = c0 < C;
-    const T* __restrict__ base = X + (int64_t)b * Tn * ldx + c0;
+    const T* __restrict__ base = X + row0 * ldx + c0;
     float s[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) s[j] = 0.0f;
@@ -505,18 +515,27 @@ __global__ __launch_bounds__(256) void copy_cols_kernel(const T* __restrict__ sr
 // doubled its bytes): online softmax (running max, rescaled sums) with the weighted mean and the weighted sum of squared
 // deviations kept in West's incremental form (mean += (w / W) d, M2 += w d (x - mean)): as stable as the two-pass
 // form, one exp and one division per element.  The four waves' partial states are merged with the pairwise update.
-template <typename T>
+// RAG: the rows and Tn of utterance b from the segment table (colstats_kernel above).
+template <typename T, bool RAG>
 __global__ __launch_bounds__(256) void asp_pool_kernel(const float* __restrict__ logits, const T* __restrict__ X, int ldx,
                                                        int Tn, int C, const float* __restrict__ bn_scale,
                                                        const float* __restrict__ bn_shift, float* __restrict__ pooled_raw,
-                                                       float* __restrict__ pooled_bn, float eps, float var_max) {
+                                                       float* __restrict__ pooled_bn, float eps, float var_max,
+                                                       const int* __restrict__ rag_row0) {
     __shared__ float smx[4][64], sse[4][64], smean[4][64], sm2[4][64];
     const int b = blockIdx.y;
+    int64_t row0;
+    if constexpr (RAG) {
+        row0 = rag_row0[b];
+        Tn = rag_row0[b + 1] - (int)row0;
+    } else {
+        row0 = (int64_t)b * Tn;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + lane;
     const bool ok = c < C;
-    const float* __restrict__ lg = logits + (int64_t)b * Tn * C + c;
-    const T* __restrict__ xp = X + (int64_t)b * Tn * ldx + c;
+    const float* __restrict__ lg = logits + row0 * C + c;
+    const T* __restrict__ xp = X + row0 * ldx + c;
     float mx = -INFINITY, se = 0.0f, mean = 0.0f, m2 = 0.0f;
     if (ok) {
         // four frames' loads in flight per lane
@@ -600,6 +619,8 @@ __global__ __launch_bounds__(256) void crop_pcm16_kernel(const int16_t* __restri
     }
 }
 
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 inline int grid_for(int64_t work_items) {
     int64_t g = (work_items + 255) / 256;
     const int64_t cap = 256 * 8;
@@ -625,9 +646,9 @@ hipError_t launch_colmean(const void* X, int dt, int ldx, int B, int T, int C, f
         return hipGetLastError();
     }
     dim3 grid((C + 64 * vec - 1) / (64 * vec), B), block(256);
-    if (dt == DT_F16) hipLaunchKernelGGL((colstats_kernel<f16_t, false>), grid, block, 0, stream, (const f16_t*)X, ldx, T, C, mean, C, 0.f);
-    else if (bf16) hipLaunchKernelGGL((colstats_kernel<bf16_t, false>), grid, block, 0, stream, (const bf16_t*)X, ldx, T, C, mean, C, 0.f);
-    else hipLaunchKernelGGL((colstats_kernel<float, false>), grid, block, 0, stream, (const float*)X, ldx, T, C, mean, C, 0.f);
+    if (dt == DT_F16) hipLaunchKernelGGL((colstats_kernel<f16_t, false, false>), grid, block, 0, stream, (const f16_t*)X, ldx, T, C, mean, C, 0.f, nullptr);
+    else if (bf16) hipLaunchKernelGGL((colstats_kernel<bf16_t, false, false>), grid, block, 0, stream, (const bf16_t*)X, ldx, T, C, mean, C, 0.f, nullptr);
+    else hipLaunchKernelGGL((colstats_kernel<float, false, false>), grid, block, 0, stream, (const float*)X, ldx, T, C, mean, C, 0.f, nullptr);
     return hipGetLastError();
 }
 
@@ -635,8 +656,23 @@ hipError_t launch_colstats(const void* X, bool bf16, int ldx, int B, int T, int 
     const int vec = bf16 ? 8 : 4;
     if (C % vec != 0 || ldx % vec != 0) return hipErrorInvalidValue;
     dim3 grid((C + 64 * vec - 1) / (64 * vec), B), block(256);
-    if (bf16) hipLaunchKernelGGL((colstats_kernel<bf16_t, true>), grid, block, 0, stream, (const bf16_t*)X, ldx, T, C, stats, 2 * C, eps);
-    else hipLaunchKernelGGL((colstats_kernel<float, true>), grid, block, 0, stream, (const float*)X, ldx, T, C, stats, 2 * C, eps);
+    if (bf16) hipLaunchKernelGGL((colstats_kernel<bf16_t, true, false>), grid, block, 0, stream, (const bf16_t*)X, ldx, T, C, stats, 2 * C, eps, nullptr);
+    else hipLaunchKernelGGL((colstats_kernel<float, true, false>), grid, block, 0, stream, (const float*)X, ldx, T, C, stats, 2 * C, eps, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_rag_colstats(const void* X, bool bf16, int ldx, const int* row0, int n, int C, float* out, bool with_std, float eps,
+                               hipStream_t stream) {
+    const int vec = bf16 ? 8 : 4;
+    if (!X || !row0 || !out || n <= 0 || C % vec != 0 || ldx % vec != 0 || !aligned16(X)) return hipErrorInvalidValue;
+    const dim3 grid((C + 64 * vec - 1) / (64 * vec), n), block(256);
+    if (with_std) {
+        if (bf16) hipLaunchKernelGGL((colstats_kernel<bf16_t, true, true>), grid, block, 0, stream, (const bf16_t*)X, ldx, 0, C, out, 2 * C, eps, row0);
+        else hipLaunchKernelGGL((colstats_kernel<float, true, true>), grid, block, 0, stream, (const float*)X, ldx, 0, C, out, 2 * C, eps, row0);
+    } else {
+        if (bf16) hipLaunchKernelGGL((colstats_kernel<bf16_t, false, true>), grid, block, 0, stream, (const bf16_t*)X, ldx, 0, C, out, C, eps, row0);
+        else hipLaunchKernelGGL((colstats_kernel<float, false, true>), grid, block, 0, stream, (const float*)X, ldx, 0, C, out, C, eps, row0);
+    }
     return hipGetLastError();
 }
 
@@ -690,6 +726,15 @@ hipError_t launch_rowvec_linear(const float* in, int ld_in, const float* W, cons
     }
     dim3 grid((N + 7) / 8, (B + 7) / 8), block(256);
     hipLaunchKernelGGL(rowvec_linear_kernel, grid, block, 0, stream, in, ld_in, W, bias, out, ld_out, B, N, K, act);
+    return hipGetLastError();
+}
+
+// a pack: rowvec_linear_small_kernel at EVERY n — each output has its own accumulator, so a row's sum is the same whatever rides in the
+// other three slots of its workgroup, where launch_rowvec_linear's choice of kernel by batch size would change the order of the sum
+hipError_t launch_rag_linear(const float* in, int ld_in, const float* W, const float* bias, float* out, int ld_out, int n, int N, int K,
+                             int act, hipStream_t stream) {
+    if (!in || !W || !out || K <= 0 || N <= 0 || n <= 0 || K % 4 != 0 || ld_in % 4 != 0 || !aligned16(in) || !aligned16(W)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rowvec_linear_small_kernel, dim3((N + 7) / 8, (n + 3) / 4), dim3(1024), 0, stream, in, ld_in, W, bias, out, ld_out, n, N, K, act);
     return hipGetLastError();
 }
 
@@ -874,8 +919,17 @@ hipError_t launch_asp_pool(const float* logits, const void* X, bool bf16, int ld
                            const float* bn_scale, const float* bn_shift, float* pooled_raw, float* pooled_bn,
                            float eps, float var_max, hipStream_t stream) {
     dim3 grid((C + 63) / 64, B), block(256);
-    if (bf16) hipLaunchKernelGGL(asp_pool_kernel<bf16_t>, grid, block, 0, stream, logits, (const bf16_t*)X, ldx, T, C, bn_scale, bn_shift, pooled_raw, pooled_bn, eps, var_max);
-    else hipLaunchKernelGGL(asp_pool_kernel<float>, grid, block, 0, stream, logits, (const float*)X, ldx, T, C, bn_scale, bn_shift, pooled_raw, pooled_bn, eps, var_max);
+    if (bf16) hipLaunchKernelGGL((asp_pool_kernel<bf16_t, false>), grid, block, 0, stream, logits, (const bf16_t*)X, ldx, T, C, bn_scale, bn_shift, pooled_raw, pooled_bn, eps, var_max, nullptr);
+    else hipLaunchKernelGGL((asp_pool_kernel<float, false>), grid, block, 0, stream, logits, (const float*)X, ldx, T, C, bn_scale, bn_shift, pooled_raw, pooled_bn, eps, var_max, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_rag_asp_pool(const float* logits, const void* X, bool bf16, int ldx, const int* row0, int n, int C, const float* bn_scale,
+                               const float* bn_shift, float* pooled_raw, float* pooled_bn, float eps, hipStream_t stream, float var_max) {
+    if (!logits || !X || !row0 || !bn_scale || !bn_shift || !pooled_bn || n <= 0 || C <= 0) return hipErrorInvalidValue;
+    const dim3 grid((C + 63) / 64, n), block(256);
+    if (bf16) hipLaunchKernelGGL((asp_pool_kernel<bf16_t, true>), grid, block, 0, stream, logits, (const bf16_t*)X, ldx, 0, C, bn_scale, bn_shift, pooled_raw, pooled_bn, eps, var_max, row0);
+    else hipLaunchKernelGGL((asp_pool_kernel<float, true>), grid, block, 0, stream, logits, (const float*)X, ldx, 0, C, bn_scale, bn_shift, pooled_raw, pooled_bn, eps, var_max, row0);
     return hipGetLastError();
 }
 

@@ -641,13 +641,10 @@ __global__ __launch_bounds__(256) void fbank_norm_kernel(const float* __restrict
 }
 
 // per (b, mel): mean of log(x + 1e-6) over T (and biased variance of the normalised signal when
-// instance norm is on).  stats[(b*n_mels + m)*2 + {0,1}] = {shift, scale}: y = (v - shift) * scale.
-__global__ __launch_bounds__(256) void prologue_stats_kernel(const float* __restrict__ feat, float* __restrict__ stats,
-                                                             int rows, int T, int log_input, int inorm) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + wave;
-    if (row >= rows) return;
-    const float* __restrict__ x = feat + (int64_t)row * T;
+// instance norm is on).  st[{0,1}] = {shift, scale} of the row x[0 .. T): y = (v - shift) * scale.  One wave per row, lane l takes
+// t = l, l + 64, ..  The one body of the fixed and the packed entry below: they differ only in where the row starts and how long it is.
+__device__ __forceinline__ void prologue_stats_row(const float* __restrict__ x, int T, int log_input, int inorm, float* __restrict__ st) {
+    const int lane = threadIdx.x & 63;
     float s = 0.0f;
     for (int t = lane; t < T; t += 64) {
         float v = x[t];
@@ -670,25 +667,43 @@ __global__ __launch_bounds__(256) void prologue_stats_kernel(const float* __rest
         shift = shift + mu;
         scale = 1.0f / sqrtf(var + 1e-5f);
     }
-    if (lane == 0) { stats[2 * row] = shift; stats[2 * row + 1] = scale; }
+    if (lane == 0) { st[0] = shift; st[1] = scale; }
 }
 
-// (B, n_mels, T) -> (B, T, n_mels) with log / shift / scale / affine applied; 32-frame LDS transpose tile.
+// fixed: grid ceil(rows / 4) over the rows = B n_mels rows of T frames; stats[(b*n_mels + m)*2 + {0,1}]
+__global__ __launch_bounds__(256) void prologue_stats_kernel(const float* __restrict__ feat, float* __restrict__ stats,
+                                                             int rows, int T, int log_input, int inorm) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    prologue_stats_row(feat + (int64_t)row * T, T, log_input, inorm, stats + 2 * row);
+}
+
+// a pack: grid (ceil(n_mels / 4), n); utterance u is a (n_mels, T_u) block at feat + feat_off[u], T_u from the segment table
+__global__ __launch_bounds__(256) void prologue_stats_pack_kernel(const float* __restrict__ feat, const int64_t* __restrict__ feat_off,
+                                                                  const int* __restrict__ row0, float* __restrict__ stats, int n_mels,
+                                                                  int log_input, int inorm) {
+    const int u = blockIdx.y, m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= n_mels) return;
+    const int T = row0[u + 1] - row0[u];
+    prologue_stats_row(feat + feat_off[u] + (int64_t)m * T, T, log_input, inorm, stats + 2 * ((int64_t)u * n_mels + m));
+}
+
+// (n_mels, T) block x of utterance b -> the rows r0 .. r0 + T of out (rows, n_mels) with log / shift / scale / affine applied; one
+// 32-frame LDS transpose tile from frame t0.  The one body of the fixed and the packed entry below.
 template <typename T_>
-__global__ __launch_bounds__(256) void prologue_apply_kernel(const float* __restrict__ feat, const float* __restrict__ stats,
-                                                             T_* __restrict__ out, int n_mels, int T, int log_input,
-                                                             const float* __restrict__ in_w, const float* __restrict__ in_b,
-                                                             uint32_t* __restrict__ status, volatile uint32_t* __restrict__ host_flag, float limit) {
+__device__ __forceinline__ void prologue_apply_tile(const float* __restrict__ x, const float* __restrict__ stats, T_* __restrict__ out,
+                                                    int n_mels, int T, int log_input, const float* __restrict__ in_w,
+                                                    const float* __restrict__ in_b, uint32_t* __restrict__ status,
+                                                    volatile uint32_t* __restrict__ host_flag, float limit, int b, int t0, int64_t r0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* tile = reinterpret_cast<float*>(smem);      // [n_mels][33]
-    const int b = blockIdx.y, t0 = blockIdx.x * 32;
     bool bad = false;
     for (int idx = threadIdx.x; idx < n_mels * 32; idx += 256) {
         const int i = idx & 31, m = idx >> 5;
         const int t = t0 + i;
         float v = 0.0f;
         if (t < T) {
-            v = feat[((int64_t)b * n_mels + m) * T + t];
+            v = x[(int64_t)m * T + t];
             if (log_input) v = logf(v + 1e-6f);
             const float sh = stats[2 * (b * n_mels + m)], sc = stats[2 * (b * n_mels + m) + 1];
             v = (v - sh) * sc;
@@ -712,8 +727,32 @@ __global__ __launch_bounds__(256) void prologue_apply_kernel(const float* __rest
     for (int idx = threadIdx.x; idx < n_mels * 32; idx += 256) {
         const int m = idx % n_mels, i = idx / n_mels;
         const int t = t0 + i;
-        if (t < T) out[((int64_t)b * T + t) * n_mels + m] = from_f32<T_>(tile[m * 33 + i]);
+        if (t < T) out[(r0 + t) * n_mels + m] = from_f32<T_>(tile[m * 33 + i]);
     }
+}
+
+// fixed: (B, n_mels, T) -> (B, T, n_mels); grid (ceil(T / 32), B)
+template <typename T_>
+__global__ __launch_bounds__(256) void prologue_apply_kernel(const float* __restrict__ feat, const float* __restrict__ stats,
+                                                             T_* __restrict__ out, int n_mels, int T, int log_input,
+                                                             const float* __restrict__ in_w, const float* __restrict__ in_b,
+                                                             uint32_t* __restrict__ status, volatile uint32_t* __restrict__ host_flag, float limit) {
+    const int b = blockIdx.y;
+    prologue_apply_tile<T_>(feat + (int64_t)b * n_mels * T, stats, out, n_mels, T, log_input, in_w, in_b, status, host_flag, limit, b,
+                            blockIdx.x * 32, (int64_t)b * T);
+}
+
+// a pack: (n_mels, T_u) blocks -> packed (M, n_mels) rows; grid (ceil(maxT / 32), n), the tiles past an utterance's last frame leave at
+// once.  No status words and an infinite limit (a pack has no F32X3 handles): constants here, so the guard folds away.
+template <typename T_>
+__global__ __launch_bounds__(256) void prologue_apply_pack_kernel(const float* __restrict__ feat, const int64_t* __restrict__ feat_off,
+                                                                  const int* __restrict__ row0, const float* __restrict__ stats,
+                                                                  T_* __restrict__ out, int n_mels, int log_input,
+                                                                  const float* __restrict__ in_w, const float* __restrict__ in_b) {
+    const int u = blockIdx.y, t0 = blockIdx.x * 32;
+    const int r0 = row0[u], T = row0[u + 1] - r0;
+    if (t0 >= T) return;
+    prologue_apply_tile<T_>(feat + feat_off[u], stats, out, n_mels, T, log_input, in_w, in_b, nullptr, nullptr, INFINITY, u, t0, r0);
 }
 
 }  // namespace
@@ -793,6 +832,23 @@ hipError_t launch_prologue(const float* feat, void* out, bool out_bf16, int B, i
     else
         hipLaunchKernelGGL(prologue_apply_kernel<float>, grid, dim3(256), lds, stream, feat, stats,
                            reinterpret_cast<float*>(out), n_mels, T, log_input, in_w, in_b, status, host_flag, limit);
+    return hipGetLastError();
+}
+
+hipError_t launch_rag_prologue(const float* feat, const int64_t* feat_off, const int* row0, int n, int maxT, void* out, bool out_bf16,
+                               int n_mels, int log_input, const float* in_w, const float* in_b, float* stats, hipStream_t stream) {
+    if (!feat || !feat_off || !row0 || !out || !stats || n <= 0 || maxT <= 0 || n_mels <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(prologue_stats_pack_kernel, dim3((n_mels + 3) / 4, n), dim3(256), 0, stream, feat, feat_off, row0, stats, n_mels, log_input,
+                       in_w != nullptr ? 1 : 0);
+    const dim3 grid((maxT + 31) / 32, n);
+    const size_t lds = (size_t)n_mels * 33 * sizeof(float);
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    if (out_bf16)
+        hipLaunchKernelGGL(prologue_apply_pack_kernel<bf16_t>, grid, dim3(256), lds, stream, feat, feat_off, row0, stats, reinterpret_cast<bf16_t*>(out),
+                           n_mels, log_input, in_w, in_b);
+    else
+        hipLaunchKernelGGL(prologue_apply_pack_kernel<float>, grid, dim3(256), lds, stream, feat, feat_off, row0, stats, reinterpret_cast<float*>(out),
+                           n_mels, log_input, in_w, in_b);
     return hipGetLastError();
 }
 

@@ -174,9 +174,11 @@ int gemm_colsum_groups(const GemmParams& p, bool bf16);
 hipError_t launch_gemm_ragged(const GemmParams& p, bool bf16, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
-// Ragged batches (ragged.hip): n utterances of T_u frames packed back to back; row0 (n + 1 ints) holds each utterance's first row
-// and the total, utt (M ints) the utterance of every row.  Every reduction over time is one workgroup per (utterance, channel
-// block) that walks the utterance's own frames in an order fixed by the frame index: a value never depends on the neighbours.
+// Ragged batches: n utterances of T_u frames packed back to back; row0 (n + 1 ints) holds each utterance's first row
+// and the total, utt (M ints) the utterance of every row (ragged.hip).  Every reduction over time is one workgroup per (utterance, channel
+// block) that walks the utterance's own frames in an order fixed by the frame index: a value never depends on the neighbours.  These
+// launch the fixed-length kernels' own bodies (RAG instances in elementwise.hip, packed entries in fbank.hip), so the two forms cannot
+// drift apart.
 // ---------------------------------------------------------------------------------------------
 hipError_t launch_rag_rows(const int* row0, int n, int maxT, int* utt, hipStream_t stream);
 // features: utterance u is a (n_mels, T_u) fp32 block at feat + feat_off[u] -> rows row0[u] .. of out (M, n_mels) in the compute type:

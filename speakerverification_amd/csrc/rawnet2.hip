@@ -803,15 +803,29 @@ __global__ __launch_bounds__(256) void rn_afms_apply_kernel(const T* __restrict_
     }
 }
 
-// one thread per (b, c): softmax over the Tn (= 14) frames of the fp32 logits, weighted mean / std of x
-template <typename T>
+// one thread per (b, c): softmax over the Tn (= 14) frames of the fp32 logits, weighted mean / std of x, the frames in index order.
+// RAG (a pack, grid (ceil(C / 256), n)): utterance b = blockIdx.y owns the rows [rag_row0[b], rag_row0[b + 1]) and Tn is its own length
+// (one frame is the common short case: its std is sqrt(1e-5)).
+template <typename T, bool RAG>
 __global__ __launch_bounds__(256) void rn_attn_pool_kernel(const float* __restrict__ logits, const T* __restrict__ x, int Tn, int C,
-                                                           float* __restrict__ out, int B) {
-    const int id = blockIdx.x * 256 + threadIdx.x;
-    if (id >= B * C) return;
-    const int b = id / C, c = id - b * C;
-    const float* lg = logits + (int64_t)b * Tn * C + c;
-    const T* xp = x + (int64_t)b * Tn * C + c;
+                                                           float* __restrict__ out, int B, const int* __restrict__ rag_row0) {
+    int b, c;
+    int64_t row0;
+    if constexpr (RAG) {
+        b = blockIdx.y;
+        c = blockIdx.x * 256 + threadIdx.x;
+        if (c >= C) return;
+        row0 = rag_row0[b];
+        Tn = rag_row0[b + 1] - (int)row0;
+    } else {
+        const int id = blockIdx.x * 256 + threadIdx.x;
+        if (id >= B * C) return;
+        b = id / C;
+        c = id - b * C;
+        row0 = (int64_t)b * Tn;
+    }
+    const float* lg = logits + row0 * C + c;
+    const T* xp = x + row0 * C + c;
     float mx = -INFINITY;
     for (int t = 0; t < Tn; ++t) mx = fmaxf(mx, lg[(int64_t)t * C]);
     float se = 0.0f;
@@ -1260,9 +1274,20 @@ hipError_t launch_rn_tail(const void* x, void* y, void* pre, int dt, bool pool, 
 
 hipError_t launch_rn_attn_pool(const float* logits, const void* x, int dt, int B, int T, int C, float* out, hipStream_t stream) {
     const int n = B * C;
-    if (dt == DT_F16) hipLaunchKernelGGL(rn_attn_pool_kernel<f16_t>, dim3((n + 255) / 256), dim3(256), 0, stream, logits, (const f16_t*)x, T, C, out, B);
-    else if (dt == DT_BF16) hipLaunchKernelGGL(rn_attn_pool_kernel<bf16_t>, dim3((n + 255) / 256), dim3(256), 0, stream, logits, (const bf16_t*)x, T, C, out, B);
-    else hipLaunchKernelGGL(rn_attn_pool_kernel<float>, dim3((n + 255) / 256), dim3(256), 0, stream, logits, (const float*)x, T, C, out, B);
+    if (dt == DT_F16) hipLaunchKernelGGL((rn_attn_pool_kernel<f16_t, false>), dim3((n + 255) / 256), dim3(256), 0, stream, logits, (const f16_t*)x, T, C, out, B, nullptr);
+    else if (dt == DT_BF16) hipLaunchKernelGGL((rn_attn_pool_kernel<bf16_t, false>), dim3((n + 255) / 256), dim3(256), 0, stream, logits, (const bf16_t*)x, T, C, out, B, nullptr);
+    else hipLaunchKernelGGL((rn_attn_pool_kernel<float, false>), dim3((n + 255) / 256), dim3(256), 0, stream, logits, (const float*)x, T, C, out, B, nullptr);
+    return hipGetLastError();
+}
+
+// the pooling of a ragged pack (the rest of its kernels: rn_ragged.hip)
+hipError_t launch_rn_rag_attn_pool(const float* logits, const void* x, int dt, const int* row0, int n, int C, float* out, hipStream_t stream) {
+    if (!logits || !x || !row0 || !out || n <= 0 || C <= 0) return hipErrorInvalidValue;
+    const dim3 grid((C + 255) / 256, n), block(256);
+    if (dt == DT_F16) hipLaunchKernelGGL((rn_attn_pool_kernel<f16_t, true>), grid, block, 0, stream, logits, (const f16_t*)x, 0, C, out, n, row0);
+    else if (dt == DT_BF16) hipLaunchKernelGGL((rn_attn_pool_kernel<bf16_t, true>), grid, block, 0, stream, logits, (const bf16_t*)x, 0, C, out, n, row0);
+    else if (dt == DT_F32) hipLaunchKernelGGL((rn_attn_pool_kernel<float, true>), grid, block, 0, stream, logits, (const float*)x, 0, C, out, n, row0);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

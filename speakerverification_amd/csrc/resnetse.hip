@@ -21,7 +21,7 @@
 //           TP x TQ <= 128 positions of one utterance; it finds the utterance in a tile prefix built on the device from the level's row0
 //           table (rs_rag_tiles_kernel), takes that utterance's own tile and frame counts, and runs the same body: an utterance's values
 //           and tile sums are those of the fixed form on it alone.  The grid is the pack's tiles, no more.  The stem, the SE gate and the
-//           block tail have segment-table forms next to their fixed ones.
+//           block tail carry the same flag: their RAG instances read the utterance from the level's tables and run the fixed text.
 // Every ReLU here is x < 0 ? 0 : x, which keeps a NaN (fmaxf would drop it): a NaN input reaches the embedding of its own utterance.
 #include "common.h"
 #include "kernels.h"
@@ -246,10 +246,12 @@ hipError_t rs_conv_t(const RsConvParams& p, hipStream_t stream) {
 
 // ---- stem: Conv2d(1, 32, 3, padding 1) + bias -> ReLU -> BatchNorm on the normalised (B, P, Q) fp32 input ------------------------
 // One thread = one position x 8 channels (four threads per position write 16 / 32 consecutive bytes each); w tap-major [9][32].
-template <typename T>
+// RAG (a pack: B counts its M frames and the P argument is not read): the frame's utterance from the level's utt table, the image's
+// first frame and its P from row0, so the zero padding sits at each utterance's own first and last frame.
+template <typename T, bool RAG>
 __global__ __launch_bounds__(256) void rs_stem_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                       const float* __restrict__ scale, const float* __restrict__ shift, T* __restrict__ y,
-                                                      int B, int P, int Q) {
+                                                      int B, int P, int Q, const int* __restrict__ rag_row0, const int* __restrict__ rag_utt) {
     __shared__ float sw[9 * 32 + 3 * 32];
     for (int i = threadIdx.x; i < 9 * 32; i += 256) sw[i] = w[i];
     if (threadIdx.x < 32) {
@@ -260,12 +262,23 @@ __global__ __launch_bounds__(256) void rs_stem_kernel(const float* __restrict__ 
     __syncthreads();
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t pos = idx >> 2;
-    if (pos >= (int64_t)B * P * Q) return;
+    if (pos >= (int64_t)B * (RAG ? 1 : P) * Q) return;
     const int cg = (int)(idx & 3) * 8;
     const int q = (int)(pos % Q);
-    const int64_t bp = pos / Q;
-    const int pp = (int)(bp % P);
-    const float* __restrict__ xb = x + (bp - pp) * Q;          // the utterance's (P, Q) image
+    const int64_t bp = pos / Q;                                // the frame: row b P + pp of the batch, row bp of a pack
+    int pp;
+    const float* __restrict__ xb;                              // the utterance's (P, Q) image
+    if constexpr (RAG) {
+        const int m = (int)bp;
+        const int u = rag_utt[m];
+        const int r0 = rag_row0[u];
+        P = rag_row0[u + 1] - r0;
+        pp = m - r0;
+        xb = x + (int64_t)r0 * Q;
+    } else {
+        pp = (int)(bp % P);
+        xb = x + (bp - pp) * Q;
+    }
     float in[9];
 #pragma unroll
     for (int dp = 0; dp < 3; ++dp)
@@ -288,139 +301,24 @@ __global__ __launch_bounds__(256) void rs_stem_kernel(const float* __restrict__ 
 
 // ---- SE gate from the per-tile sums: gate[b, c] = sigmoid(W2 relu(W1 mean + b1) + b2), 16 hidden units ---------------------------
 // One workgroup per utterance; the tiles are added in index order.  w1 [16][C], w2 [C][16], fp32.
+// RAG (a pack): utterance b has its own tiles [rag_tile0[b], rag_tile0[b + 1]) and its own P_b Q positions (P_b from the level's row0).
+template <bool RAG>
 __global__ __launch_bounds__(256) void rs_se_gate_kernel(const float* __restrict__ part, int ntiles, int C, float inv_n, const float* __restrict__ w1,
                                                          const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
-                                                         float* __restrict__ gate) {
+                                                         float* __restrict__ gate, const int* __restrict__ rag_tile0, const int* __restrict__ rag_row0,
+                                                         int Q) {
     __shared__ float mean[256], hid[16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t tile_first;
+    if constexpr (RAG) {
+        tile_first = rag_tile0[b];
+        ntiles = rag_tile0[b + 1] - (int)tile_first;
+        inv_n = 1.0f / (float)((rag_row0[b + 1] - rag_row0[b]) * Q);
+    } else {
+        tile_first = (int64_t)b * ntiles;
+    }
     if (tid < C) {
-        const float* __restrict__ pp = part + (int64_t)b * ntiles * C + tid;
-        float s = 0.0f;
-        for (int t = 0; t < ntiles; ++t) s += pp[(int64_t)t * C];
-        mean[tid] = s * inv_n;
-    }
-    __syncthreads();
-    for (int j = wave * 4; j < wave * 4 + 4; ++j) {
-        float s = 0.0f;
-        for (int c = lane; c < C; c += 64) s = fmaf(w1[j * C + c], mean[c], s);
-        s = wave_sum(s) + b1[j];
-        if (lane == 0) hid[j] = s < 0.0f ? 0.0f : s;
-    }
-    __syncthreads();
-    if (tid < C) {
-        float s = b2[tid];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) s = fmaf(w2[tid * 16 + j], hid[j], s);
-        gate[(int64_t)b * C + tid] = 1.0f / (1.0f + expf(-s));
-    }
-}
-
-// ---- out = relu(res + y * gate[b, :]); res = relu(x) (the identity residual: the block's in-place ReLU has already overwritten x,
-// ResNetBlocks.py:230-231) or the downsample output as it is ---------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void rs_se_apply_kernel(const T* __restrict__ y, const T* __restrict__ res, const float* __restrict__ gate,
-                                                          T* __restrict__ out, int64_t nvec, int per_utt_vec, int cvec, int res_relu) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nvec) return;
-    constexpr int N = Vec16<T>::N;
-    const int b = (int)(i / per_utt_vec);
-    const int c0 = (int)(i % cvec) * N;
-    const Vec16<T> yv = ld_nt(y + i * N), rv = ld_nt(res + i * N);
-    const float* __restrict__ g = gate + (int64_t)b * cvec * N + c0;
-    Vec16<T> o;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        float r = rv.get(k);
-        if (res_relu) r = r < 0.0f ? 0.0f : r;
-        const float v = fmaf(yv.get(k), g[k], r);
-        o.set(k, v < 0.0f ? 0.0f : v);
-    }
-    *reinterpret_cast<decltype(o.v)*>(out + i * N) = o.v;
-}
-
-// ---- the same three over a ragged pack, and the tile tables of its convolutions -----------------------------------------------------
-// tile0 / plan of one convolution of a pack from the input level's row0: thread u plans utterance u's output image (rs_tile_of, the
-// function the host counts with), thread 0 adds the counts up in utterance order.  One workgroup; n > 256 runs in rounds of 256.
-__global__ __launch_bounds__(256) void rs_rag_tiles_kernel(const int* __restrict__ row0_in, int n, int Q, int stride, int ks, int* __restrict__ tile0,
-                                                           int* __restrict__ plan) {
-    __shared__ int cnt[256];
-    __shared__ int base;
-    if (threadIdx.x == 0) base = 0;
-    const int Qo = (Q - 1) / stride + 1;          // rs_out_size
-    for (int u0 = 0; u0 < n; u0 += 256) {
-        const int u = u0 + threadIdx.x;
-        if (u < n) {
-            const int Po = (row0_in[u + 1] - row0_in[u] - 1) / stride + 1;
-            int TP, TQ;
-            rs_tile_of(Po, Qo, stride, ks, TP, TQ);
-            plan[u] = TP | TQ << 8;
-            cnt[threadIdx.x] = ((Po + TP - 1) / TP) * ((Qo + TQ - 1) / TQ);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int t = base;
-            const int m = min(256, n - u0);
-            for (int i = 0; i < m; ++i) { tile0[u0 + i] = t; t += cnt[i]; }
-            base = t;
-            if (u0 + m == n) tile0[n] = t;
-        }
-        __syncthreads();
-    }
-}
-
-// rs_stem_kernel with the frame's utterance taken from the level's tables: M frames of Q positions
-template <typename T>
-__global__ __launch_bounds__(256) void rs_stem_rag_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                          const float* __restrict__ scale, const float* __restrict__ shift, T* __restrict__ y,
-                                                          const int* __restrict__ row0, const int* __restrict__ utt, int M, int Q) {
-    __shared__ float sw[9 * 32 + 3 * 32];
-    for (int i = threadIdx.x; i < 9 * 32; i += 256) sw[i] = w[i];
-    if (threadIdx.x < 32) {
-        sw[288 + threadIdx.x] = bias[threadIdx.x];
-        sw[320 + threadIdx.x] = scale[threadIdx.x];
-        sw[352 + threadIdx.x] = shift[threadIdx.x];
-    }
-    __syncthreads();
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t pos = idx >> 2;
-    if (pos >= (int64_t)M * Q) return;
-    const int cg = (int)(idx & 3) * 8;
-    const int q = (int)(pos % Q);
-    const int m = (int)(pos / Q);
-    const int u = utt[m];
-    const int r0 = row0[u], P = row0[u + 1] - r0;
-    const int pp = m - r0;
-    const float* __restrict__ xb = x + (int64_t)r0 * Q;        // the utterance's (P, Q) image
-    float in[9];
-#pragma unroll
-    for (int dp = 0; dp < 3; ++dp)
-#pragma unroll
-        for (int dq = 0; dq < 3; ++dq) {
-            const int ip = pp + dp - 1, iq = q + dq - 1;
-            in[dp * 3 + dq] = (ip >= 0 && ip < P && iq >= 0 && iq < Q) ? xb[(int64_t)ip * Q + iq] : 0.0f;
-        }
-    T* __restrict__ yo = y + pos * 32 + cg;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int c = cg + k;
-        float v = sw[288 + c];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) v = fmaf(sw[t * 32 + c], in[t], v);
-        v = v < 0.0f ? 0.0f : v;
-        yo[k] = from_f32<T>(fmaf(v, sw[320 + c], sw[352 + c]));
-    }
-}
-
-// rs_se_gate_kernel of utterance u = blockIdx.x over its own tiles [tile0[u], tile0[u + 1]) and its own P_u Q positions
-__global__ __launch_bounds__(256) void rs_se_gate_rag_kernel(const float* __restrict__ part, const int* __restrict__ tile0, const int* __restrict__ row0,
-                                                             int C, int Q, const float* __restrict__ w1, const float* __restrict__ b1,
-                                                             const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ gate) {
-    __shared__ float mean[256], hid[16];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int t0 = tile0[b], ntiles = tile0[b + 1] - t0;
-    const float inv_n = 1.0f / (float)((row0[b + 1] - row0[b]) * Q);
-    if (tid < C) {
-        const float* __restrict__ pp = part + (int64_t)t0 * C + tid;
+        const float* __restrict__ pp = part + tile_first * C + tid;
         float s = 0.0f;
         int t = 0;
         for (; t + 8 <= ntiles; t += 8) {          // eight loads in flight, added in index order (a 20 s file has 2500 tiles at level 0)
@@ -449,15 +347,18 @@ __global__ __launch_bounds__(256) void rs_se_gate_rag_kernel(const float* __rest
     }
 }
 
-// rs_se_apply_kernel with the gate row of the frame's utterance: per_frame_vec = Q C / N vectors in a frame
-template <typename T>
-__global__ __launch_bounds__(256) void rs_se_apply_rag_kernel(const T* __restrict__ y, const T* __restrict__ res, const float* __restrict__ gate,
-                                                              T* __restrict__ out, const int* __restrict__ utt, int64_t nvec, int per_frame_vec, int cvec,
-                                                              int res_relu) {
+// ---- out = relu(res + y * gate[b, :]); res = relu(x) (the identity residual: the block's in-place ReLU has already overwritten x,
+// ResNetBlocks.py:230-231) or the downsample output as it is ---------------------------------------------------------------------------
+// RAG (a pack): per_utt_vec counts the vectors of one FRAME (Q C / N), and the gate row is that of the frame's utterance
+template <typename T, bool RAG>
+__global__ __launch_bounds__(256) void rs_se_apply_kernel(const T* __restrict__ y, const T* __restrict__ res, const float* __restrict__ gate,
+                                                          T* __restrict__ out, int64_t nvec, int per_utt_vec, int cvec, int res_relu,
+                                                          const int* __restrict__ rag_utt) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nvec) return;
     constexpr int N = Vec16<T>::N;
-    const int b = utt[(int)(i / per_frame_vec)];
+    int b = (int)(i / per_utt_vec);
+    if constexpr (RAG) b = rag_utt[b];
     const int c0 = (int)(i % cvec) * N;
     const Vec16<T> yv = ld_nt(y + i * N), rv = ld_nt(res + i * N);
     const float* __restrict__ g = gate + (int64_t)b * cvec * N + c0;
@@ -470,6 +371,36 @@ __global__ __launch_bounds__(256) void rs_se_apply_rag_kernel(const T* __restric
         o.set(k, v < 0.0f ? 0.0f : v);
     }
     *reinterpret_cast<decltype(o.v)*>(out + i * N) = o.v;
+}
+
+// ---- the tile tables of a ragged pack's convolutions ---------------------------------------------------------------------------------
+// tile0 / plan of one convolution of a pack from the input level's row0: thread u plans utterance u's output image (rs_tile_of, the
+// function the host counts with), thread 0 adds the counts up in utterance order.  One workgroup; n > 256 runs in rounds of 256.
+__global__ __launch_bounds__(256) void rs_rag_tiles_kernel(const int* __restrict__ row0_in, int n, int Q, int stride, int ks, int* __restrict__ tile0,
+                                                           int* __restrict__ plan) {
+    __shared__ int cnt[256];
+    __shared__ int base;
+    if (threadIdx.x == 0) base = 0;
+    const int Qo = (Q - 1) / stride + 1;          // rs_out_size
+    for (int u0 = 0; u0 < n; u0 += 256) {
+        const int u = u0 + threadIdx.x;
+        if (u < n) {
+            const int Po = (row0_in[u + 1] - row0_in[u] - 1) / stride + 1;
+            int TP, TQ;
+            rs_tile_of(Po, Qo, stride, ks, TP, TQ);
+            plan[u] = TP | TQ << 8;
+            cnt[threadIdx.x] = ((Po + TP - 1) / TP) * ((Qo + TQ - 1) / TQ);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int t = base;
+            const int m = min(256, n - u0);
+            for (int i = 0; i < m; ++i) { tile0[u0 + i] = t; t += cnt[i]; }
+            base = t;
+            if (u0 + m == n) tile0[n] = t;
+        }
+        __syncthreads();
+    }
 }
 
 template <typename T, int BN, int KS>
@@ -517,15 +448,15 @@ hipError_t launch_rs_stem(const float* x, const float* w, const float* bias, con
     if (dt != DT_F32 && dt != DT_BF16) return hipErrorInvalidValue;
     const int64_t n = (int64_t)B * P * Q * 4;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (dt == DT_F32) hipLaunchKernelGGL(rs_stem_kernel<float>, grid, block, 0, stream, x, w, bias, scale, shift, (float*)y, B, P, Q);
-    else hipLaunchKernelGGL(rs_stem_kernel<bf16_t>, grid, block, 0, stream, x, w, bias, scale, shift, (bf16_t*)y, B, P, Q);
+    if (dt == DT_F32) hipLaunchKernelGGL((rs_stem_kernel<float, false>), grid, block, 0, stream, x, w, bias, scale, shift, (float*)y, B, P, Q, nullptr, nullptr);
+    else hipLaunchKernelGGL((rs_stem_kernel<bf16_t, false>), grid, block, 0, stream, x, w, bias, scale, shift, (bf16_t*)y, B, P, Q, nullptr, nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_rs_se_gate(const float* part, int ntiles, int B, int C, int positions, const float* w1, const float* b1, const float* w2, const float* b2,
                              float* gate, hipStream_t stream) {
     if (C > 256 || C % 32 != 0 || ntiles <= 0 || positions <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rs_se_gate_kernel, dim3(B), dim3(256), 0, stream, part, ntiles, C, 1.0f / (float)positions, w1, b1, w2, b2, gate);
+    hipLaunchKernelGGL(rs_se_gate_kernel<false>, dim3(B), dim3(256), 0, stream, part, ntiles, C, 1.0f / (float)positions, w1, b1, w2, b2, gate, nullptr, nullptr, 0);
     return hipGetLastError();
 }
 
@@ -539,10 +470,11 @@ hipError_t launch_rs_se_apply(const void* y, const void* res, const float* gate,
     if (per > 0x7fffffffLL) return hipErrorInvalidValue;
     dim3 grid((unsigned)((nvec + 255) / 256)), block(256);
     if (dt == DT_F32)
-        hipLaunchKernelGGL(rs_se_apply_kernel<float>, grid, block, 0, stream, (const float*)y, (const float*)res, gate, (float*)out, nvec, (int)per, cvec, res_relu ? 1 : 0);
+        hipLaunchKernelGGL((rs_se_apply_kernel<float, false>), grid, block, 0, stream, (const float*)y, (const float*)res, gate, (float*)out, nvec, (int)per, cvec,
+                           res_relu ? 1 : 0, nullptr);
     else
-        hipLaunchKernelGGL(rs_se_apply_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)y, (const bf16_t*)res, gate, (bf16_t*)out, nvec, (int)per, cvec,
-                           res_relu ? 1 : 0);
+        hipLaunchKernelGGL((rs_se_apply_kernel<bf16_t, false>), grid, block, 0, stream, (const bf16_t*)y, (const bf16_t*)res, gate, (bf16_t*)out, nvec, (int)per, cvec,
+                           res_relu ? 1 : 0, nullptr);
     return hipGetLastError();
 }
 
@@ -587,15 +519,15 @@ hipError_t launch_rs_stem_ragged(const float* x, const float* w, const float* bi
     if ((dt != DT_F32 && dt != DT_BF16) || !row0 || !utt || M <= 0 || Q <= 0) return hipErrorInvalidValue;
     const int64_t n = (int64_t)M * Q * 4;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (dt == DT_F32) hipLaunchKernelGGL(rs_stem_rag_kernel<float>, grid, block, 0, stream, x, w, bias, scale, shift, (float*)y, row0, utt, M, Q);
-    else hipLaunchKernelGGL(rs_stem_rag_kernel<bf16_t>, grid, block, 0, stream, x, w, bias, scale, shift, (bf16_t*)y, row0, utt, M, Q);
+    if (dt == DT_F32) hipLaunchKernelGGL((rs_stem_kernel<float, true>), grid, block, 0, stream, x, w, bias, scale, shift, (float*)y, M, 0, Q, row0, utt);
+    else hipLaunchKernelGGL((rs_stem_kernel<bf16_t, true>), grid, block, 0, stream, x, w, bias, scale, shift, (bf16_t*)y, M, 0, Q, row0, utt);
     return hipGetLastError();
 }
 
 hipError_t launch_rs_se_gate_ragged(const float* part, const int* tile0, const int* row0, int n, int C, int Q, const float* w1, const float* b1,
                                     const float* w2, const float* b2, float* gate, hipStream_t stream) {
     if (C > 256 || C % 32 != 0 || n <= 0 || Q <= 0 || !part || !tile0 || !row0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rs_se_gate_rag_kernel, dim3(n), dim3(256), 0, stream, part, tile0, row0, C, Q, w1, b1, w2, b2, gate);
+    hipLaunchKernelGGL(rs_se_gate_kernel<true>, dim3(n), dim3(256), 0, stream, part, 0, C, 0.0f, w1, b1, w2, b2, gate, tile0, row0, Q);
     return hipGetLastError();
 }
 
@@ -609,11 +541,11 @@ hipError_t launch_rs_se_apply_ragged(const void* y, const void* res, const float
     if (per > 0x7fffffffLL) return hipErrorInvalidValue;
     dim3 grid((unsigned)((nvec + 255) / 256)), block(256);
     if (dt == DT_F32)
-        hipLaunchKernelGGL(rs_se_apply_rag_kernel<float>, grid, block, 0, stream, (const float*)y, (const float*)res, gate, (float*)out, utt, nvec, (int)per, cvec,
-                           res_relu ? 1 : 0);
+        hipLaunchKernelGGL((rs_se_apply_kernel<float, true>), grid, block, 0, stream, (const float*)y, (const float*)res, gate, (float*)out, nvec, (int)per, cvec,
+                           res_relu ? 1 : 0, utt);
     else
-        hipLaunchKernelGGL(rs_se_apply_rag_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)y, (const bf16_t*)res, gate, (bf16_t*)out, utt, nvec, (int)per,
-                           cvec, res_relu ? 1 : 0);
+        hipLaunchKernelGGL((rs_se_apply_kernel<bf16_t, true>), grid, block, 0, stream, (const bf16_t*)y, (const bf16_t*)res, gate, (bf16_t*)out, nvec, (int)per,
+                           cvec, res_relu ? 1 : 0, utt);
     return hipGetLastError();
 }
 

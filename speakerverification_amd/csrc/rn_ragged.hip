@@ -2,7 +2,8 @@
 //
 // n utterances are packed back to back at seven frame levels (the conv front-end's T1_u = len_u / 3 frames, then what each of the six
 // max_pool1d(3) stages leaves); level l's row0 table (n + 1 ints) holds each utterance's first row and the row count.  The GEMMs run on
-// launch_gemm_ragged; here are the front-end, the block tail and the attentive pooling.
+// launch_gemm_ragged and the attentive pooling is the RAG instance of rn_attn_pool_kernel (rawnet2.hip); here are the front-end and the
+// block tail.
 //
 // The block tail is rawnet2.hip's small-batch form (rn_tail_part -> rn_afms_gate -> rn_tail_apply) on a segment table: an utterance of Tn_u
 // pooled frames is cut into ceil(Tn_u / RN_RAG_SLICE) slices of a CONSTANT RN_RAG_SLICE frames (uncapped: a 20 s file has 35 555 pooled
@@ -223,31 +224,6 @@ __global__ __launch_bounds__(RR_THREADS) void rn_rag_tail_apply_kernel(const T* 
     }
 }
 
-// rn_attn_pool_kernel over an utterance's own frames: one thread per (utterance, channel), the frames in index order; the variance
-// around the mean, clamped at 1e-5 (one frame is the common short case: its std is sqrt(1e-5)).  grid (ceil(C / 256), n)
-template <typename T>
-__global__ __launch_bounds__(RR_THREADS) void rn_rag_attn_pool_kernel(const float* __restrict__ logits, const T* __restrict__ x,
-                                                                      const int* __restrict__ row0, int C, float* __restrict__ out) {
-    const int u = blockIdx.y, c = blockIdx.x * RR_THREADS + threadIdx.x;
-    if (c >= C) return;
-    const int r0 = row0[u], Tn = row0[u + 1] - r0;
-    const float* lg = logits + (int64_t)r0 * C + c;
-    const T* xp = x + (int64_t)r0 * C + c;
-    float mx = -INFINITY;
-    for (int t = 0; t < Tn; ++t) mx = fmaxf(mx, lg[(int64_t)t * C]);
-    float se = 0.0f;
-    for (int t = 0; t < Tn; ++t) se += expf(lg[(int64_t)t * C] - mx);
-    float m = 0.0f;
-    for (int t = 0; t < Tn; ++t) m = fmaf(to_f32<T>(xp[(int64_t)t * C]), expf(lg[(int64_t)t * C] - mx) / se, m);
-    float v = 0.0f;
-    for (int t = 0; t < Tn; ++t) {
-        const float d = to_f32<T>(xp[(int64_t)t * C]) - m;
-        v = fmaf(d * d, expf(lg[(int64_t)t * C] - mx) / se, v);
-    }
-    out[(int64_t)u * 2 * C + c] = m;
-    out[(int64_t)u * 2 * C + C + c] = sqrtf(fmaxf(v, 1e-5f));
-}
-
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // the shapes the tail kernels are cut for: whole 16-byte chunks, a row of chunks divides the workgroup, the mean fits its LDS array
@@ -312,16 +288,6 @@ hipError_t launch_rn_rag_tail_apply(const void* x, int dt, bool pool, const int*
     else if (dt == DT_F32) { if (pool) SV_APPLY(float, true); else SV_APPLY(float, false); }
     else return hipErrorInvalidValue;
 #undef SV_APPLY
-    return hipGetLastError();
-}
-
-hipError_t launch_rn_rag_attn_pool(const float* logits, const void* x, int dt, const int* row0, int n, int C, float* out, hipStream_t stream) {
-    if (!logits || !x || !row0 || !out || n <= 0 || C <= 0) return hipErrorInvalidValue;
-    const dim3 grid((C + RR_THREADS - 1) / RR_THREADS, n), block(RR_THREADS);
-    if (dt == DT_F16) hipLaunchKernelGGL(rn_rag_attn_pool_kernel<f16_t>, grid, block, 0, stream, logits, (const f16_t*)x, row0, C, out);
-    else if (dt == DT_BF16) hipLaunchKernelGGL(rn_rag_attn_pool_kernel<bf16_t>, grid, block, 0, stream, logits, (const bf16_t*)x, row0, C, out);
-    else if (dt == DT_F32) hipLaunchKernelGGL(rn_rag_attn_pool_kernel<float>, grid, block, 0, stream, logits, (const float*)x, row0, C, out);
-    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

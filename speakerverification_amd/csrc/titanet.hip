@@ -157,23 +157,19 @@ hipError_t launch_by_k(int k, const void* x, const void* skip, const void* h3, c
 }
 
 // rows[b, 0:n) = NaN for every utterance b whose input (per_utt floats from x + b per_utt) holds an inf / NaN: the ReLU epilogues
-// (fmaxf) would turn such a value into 0, where the reference's forward propagates it to the embedding
-__global__ __launch_bounds__(256) void tn_nonfinite_rows_kernel(const float* __restrict__ x, int64_t per_utt, float* __restrict__ rows, int ld, int n) {
+// (fmaxf) would turn such a value into 0, where the reference's forward propagates it to the embedding.
+// RAG (a pack): utterance b's values start at x + rag_off[b] and number (rag_row0[b + 1] - rag_row0[b]) * per_utt, per_utt counting one ROW
+template <bool RAG>
+__global__ __launch_bounds__(256) void tn_nonfinite_rows_kernel(const float* __restrict__ x, int64_t per_utt, float* __restrict__ rows, int ld, int n,
+                                                                const int64_t* __restrict__ rag_off, const int* __restrict__ rag_row0) {
     const int b = blockIdx.x;
-    const uint32_t* __restrict__ p = reinterpret_cast<const uint32_t*>(x + (int64_t)b * per_utt);
-    int bad = 0;
-    for (int64_t i = threadIdx.x; i < per_utt; i += 256) bad |= (p[i] & 0x7f800000u) == 0x7f800000u;
-    bad = __syncthreads_or(bad);
-    if (bad)
-        for (int i = threadIdx.x; i < n; i += 256) rows[(int64_t)b * ld + i] = __builtin_nanf("");
-}
-
-// the same test over a pack: utterance b's values start at x + off[b] and number (row0[b + 1] - row0[b]) * per_row
-__global__ __launch_bounds__(256) void tn_nonfinite_rows_rag_kernel(const float* __restrict__ x, const int64_t* __restrict__ off,
-                                                                    const int* __restrict__ row0, int per_row, float* __restrict__ rows, int ld, int n) {
-    const int b = blockIdx.x;
-    const uint32_t* __restrict__ p = reinterpret_cast<const uint32_t*>(x + off[b]);
-    const int64_t per_utt = (int64_t)(row0[b + 1] - row0[b]) * per_row;
+    const uint32_t* __restrict__ p;
+    if constexpr (RAG) {
+        p = reinterpret_cast<const uint32_t*>(x + rag_off[b]);
+        per_utt *= rag_row0[b + 1] - rag_row0[b];
+    } else {
+        p = reinterpret_cast<const uint32_t*>(x + (int64_t)b * per_utt);
+    }
     int bad = 0;
     for (int64_t i = threadIdx.x; i < per_utt; i += 256) bad |= (p[i] & 0x7f800000u) == 0x7f800000u;
     bad = __syncthreads_or(bad);
@@ -193,14 +189,14 @@ bool shape_ok(int dt, int k, int B, int Tn, int C) {
 
 hipError_t launch_tn_nonfinite_rows(const float* x, int64_t per_utt, int B, float* rows, int ld, int n, hipStream_t stream) {
     if (!x || !rows || B <= 0 || per_utt <= 0 || n <= 0 || ld < n) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tn_nonfinite_rows_kernel, dim3(B), dim3(256), 0, stream, x, per_utt, rows, ld, n);
+    hipLaunchKernelGGL(tn_nonfinite_rows_kernel<false>, dim3(B), dim3(256), 0, stream, x, per_utt, rows, ld, n, nullptr, nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_tn_nonfinite_rows_ragged(const float* x, const int64_t* off, const int* row0, int per_row, int B, float* rows, int ld, int n,
                                            hipStream_t stream) {
     if (!x || !off || !row0 || !rows || B <= 0 || per_row <= 0 || n <= 0 || ld < n) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tn_nonfinite_rows_rag_kernel, dim3(B), dim3(256), 0, stream, x, off, row0, per_row, rows, ld, n);
+    hipLaunchKernelGGL(tn_nonfinite_rows_kernel<true>, dim3(B), dim3(256), 0, stream, x, (int64_t)per_row, rows, ld, n, off, row0);
     return hipGetLastError();
 }
 
