@@ -377,6 +377,17 @@ int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, con
  *                  embeddings only: svhip_asnorm_last_refit()), they exist only as <= 2 GiB slabs.  svhip_asnorm_last_fallback():
  *                  how many embeddings of the last call took the slab path after the fused kernel (-1: the whole call did).
  *   asnorm_pairs : out[p] = 0.5*((s-mu[a])/sd[a] + (s-mu[b])/sd[b]), s = E[a].E[b] (utils.py:148-160).
+ *   score_topk   : 1:N identification (what the `predict` branch of the reference's driver asks, src/inference.py:254-327): per row of Q
+ *                  the k largest entries of Q @ G^T and the gallery rows they belong to, best first, without the N x M matrix.  Order:
+ *                  score descending; equal scores by the lower gallery index; a NaN score below every number (-inf included), NaNs among
+ *                  themselves by the lower index; +inf first.  A row's result depends on that row of Q and on G only - not on N, on the
+ *                  row's place in Q or on how the gallery is sliced.  1 <= k <= 128, k <= M <= 2^31 - 1, D >= 1 (else SVHIP_ERR_INVALID,
+ *                  the message names the value; nothing is launched); N = 0 is SVHIP_OK.  fp32-grade on every handle: a returned score
+ *                  of L2-normalised rows lies within 1e-6 of the float64 inner product of the row it names.  D in {192, 256} with
+ *                  16-byte aligned operands: the fused kernel (csrc/score_topk.hip, exact fp32 MFMA, any finite magnitude; profile
+ *                  labels "score_topk", "score_topk_merge") - no score reaches memory.  Every other width: slabs of query rows through
+ *                  score_matrix's GEMM (its magnitude contract; at most 2 GiB, at least 128 rows: M <= 4 194 304, beyond it
+ *                  SVHIP_ERR_UNSUPPORTED) and a row kernel ("score_topk_gemm", "score_topk_rows").
  * Pointers follow `flags` (indices are int32, device or host like the other inputs). */
 int svhip_l2norm(svhip_handle* h, float* E, int64_t N, int32_t D, int32_t flags);
 int svhip_score_pairs(svhip_handle* h, const float* E, int64_t N, int32_t D,
@@ -385,6 +396,10 @@ int svhip_score_matrix(svhip_handle* h, const float* A, int64_t Na, const float*
                        int32_t D, float* out, int32_t flags);
 int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, const float* cohort,
                        int32_t K, int32_t top, float* mu, float* sigma, int32_t flags);
+/* out_score (N, k), out_index (N, k): per row of Q the k largest entries of Q @ G^T (np.inner, as score_matrix) and the
+ * gallery rows they belong to, best first.  Pointers follow `flags`. */
+int svhip_score_topk(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, int32_t k,
+                     float* out_score, int32_t* out_index, int32_t flags);
 int svhip_asnorm_pairs(svhip_handle* h, const float* E, int64_t N, int32_t D, const float* mu,
                        const float* sigma, const int32_t* ia, const int32_t* ib, int64_t P,
                        float* out, int32_t flags);

@@ -26,7 +26,7 @@ int scratch(svhip_handle* h, int slot, size_t bytes, void** out) {
     *out = h->scr[slot];
     return SVHIP_OK;
 }
-// Scratch retention policy: the slab of the AS-norm slab path (up to 2 GiB) and the staging copies of HOST-pointer calls
+// Scratch retention policy: the slab of the AS-norm / top-k slab paths (up to 2 GiB), the top-k lists and the staging copies of HOST-pointer calls
 // (N x D x 4 bytes for the embedding matrix) are released at the end of the call once they exceed 256 MiB — they would otherwise sit
 // beside the model engines' workspaces for the life of the process-wide scoring handle.  The slots of the device-resident fast path
 // (candidate lists, cohort planes: re-used every call) stay; svhip_trim_scratch frees everything.
@@ -41,6 +41,7 @@ void release_big_scratch(svhip_handle* h, bool staged_host) {
         }
     };
     drop(svhip_handle::SCR_SLAB);
+    drop(svhip_handle::SCR_TOPK);
     if (staged_host)
         for (int s_ : {svhip_handle::SCR_IN0, svhip_handle::SCR_IN1, svhip_handle::SCR_IN2, svhip_handle::SCR_IN3, svhip_handle::SCR_IN4,
                        svhip_handle::SCR_OUT0, svhip_handle::SCR_OUT1, svhip_handle::SCR_OUT2, svhip_handle::SCR_SPLIT}) drop(s_);
@@ -431,6 +432,108 @@ int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, co
         release_big_scratch(h, !din || !dout);
     }
     return SVHIP_OK;
+}
+
+// ---- 1:N identification: the k best gallery rows per query (score_topk.hip) ---------------------------------------------------------------
+// The route is decided from the shape and the pointers alone:
+//   fused  D = 192 / 256, 16-byte aligned operands: no score reaches memory.  Queries go in chunks of 16 384; the whole 128-query tiles of a
+//          chunk run the shared-block form of the kernel, a last tile of at most 32 queries the form whose waves walk different gallery
+//          blocks; each launch cuts the gallery into enough slices to fill the chip (within 256 MiB of list scratch) and is followed by its merge
+//   slab   every other width: score_gemm writes slabs of query rows (at most 2 GiB, at least 128 rows, as asnorm_stats_slab), a row kernel selects
+static int topk_fused_part(svhip_handle* h, const float* dQ, int64_t rows, const float* dG, int64_t M, int D, int k, bool few, float* dS, int32_t* dI) {
+    const int cap = score_topk_cap(k);
+    const int64_t nb_all = (M + 31) / 32;
+    const int64_t tiles = few ? 1 : (rows + 127) / 128;
+    const int per_slice_lists = few ? 8 : 2;
+    const int cu = h->num_cu > 0 ? h->num_cu : 256;
+    // two workgroups per CU; few: one, since every wave of it keeps lists of its own for the merge to read (8 per slice)
+    int64_t slices = ((few ? 1 : 2) * (int64_t)cu + tiles - 1) / tiles;
+    const int64_t min_blocks = few ? 16 : 8;                      // gallery blocks a workgroup should at least walk
+    slices = std::min(slices, (nb_all + min_blocks - 1) / min_blocks);
+    const int64_t slice_bytes = rows * per_slice_lists * ((int64_t)cap * 8 + 4);
+    slices = std::min(slices, std::max<int64_t>(1, ((int64_t)256 << 20) / slice_bytes));
+    slices = std::max<int64_t>(1, std::min<int64_t>(slices, 65535));
+    const int64_t per = (nb_all + slices - 1) / slices;
+    slices = (nb_all + per - 1) / per;
+    ScoreTopkParams p;
+    p.Q = dQ; p.N = rows; p.G = dG; p.M = M; p.k = k; p.cap = cap; p.per = (int)per; p.nlists = (int)slices * per_slice_lists;
+    void* s = nullptr;
+    const size_t list_bytes = (size_t)rows * p.nlists * cap * 8;
+    if (int rc = scratch(h, svhip_handle::SCR_TOPK, list_bytes + (size_t)rows * p.nlists * 4, &s)) return rc;
+    p.lists = reinterpret_cast<uint2*>(s);
+    p.cnt = reinterpret_cast<int32_t*>((char*)s + list_bytes);
+    if (int rc = run(h, "score_topk", 2.0 * rows * M * D, [&]() { return launch_score_topk(p, D, few, (int)slices, h->stream); })) return rc;
+    return run(h, "score_topk_merge", 0, [&]() { return launch_score_topk_merge(p.lists, p.cnt, rows, p.nlists, cap, k, dS, dI, h->stream); });
+}
+
+static int topk_slab(svhip_handle* h, const float* dQ, int64_t N, const float* dG, int64_t M, int D, int k, float* dS, int32_t* dI) {
+    const int64_t ldk = (M + 3) & ~(int64_t)3;                    // row stride of the slab (16-byte rows for the DMA GEMM)
+    const int64_t max_m = (((int64_t)1 << 31) / (128 * 4)) & ~(int64_t)3;
+    if (ldk > max_m)
+        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "score_topk: D = %d takes the slab route, whose 128-row slab holds at most M = %lld gallery rows (M = %lld)", D,
+                (long long)max_m, (long long)M);
+    const int64_t slab_rows = std::min<int64_t>(N, std::max<int64_t>(128, ((int64_t)1 << 31) / (ldk * 4)));
+    void* gsplit = nullptr;
+    void* slab = nullptr;
+    int rc;
+    const ScoreRoute route = score_route(h, dQ, slab_rows, dG, M, D);       // (every slab starts r0 * D * 4 bytes into Q: the same alignment)
+    if ((rc = split_b(h, route, dG, M, D, &gsplit))) return rc;
+    if ((rc = scratch(h, svhip_handle::SCR_SLAB, (size_t)slab_rows * ldk * 4, &slab))) return rc;
+    for (int64_t r0 = 0; r0 < N; r0 += slab_rows) {
+        const int64_t rows = std::min(slab_rows, N - r0);
+        rc = score_gemm(h, "score_topk_gemm", dQ + r0 * D, rows, dG, M, D, (float*)slab, ldk, route, gsplit);
+        if (!rc) rc = run(h, "score_topk_rows", 0, [&]() { return launch_score_topk_rows((const float*)slab, rows, M, ldk, k, dS + r0 * k, dI + r0 * k, h->stream); });
+        if (rc) return rc;
+    }
+    return SVHIP_OK;
+}
+
+int svhip_score_topk(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, int32_t k, float* out_score,
+                     int32_t* out_index, int32_t flags) {
+    if (!h) return SVHIP_ERR_INVALID;
+    if (k < 1 || k > SCORE_TOPK_MAX_K) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: k = %d is outside [1, %d]", (int)k, SCORE_TOPK_MAX_K);
+    if (M < 1 || M > (int64_t)INT32_MAX) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: M = %lld is outside [1, 2^31 - 1]", (long long)M);
+    if (k > M) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: k = %d exceeds the gallery's M = %lld rows", (int)k, (long long)M);
+    if (D < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: D = %d must be at least 1", (int)D);
+    if (N < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: N = %lld is negative", (long long)N);
+    if (N == 0) return SVHIP_OK;
+    if (!Q || !G || !out_score || !out_index) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: NULL pointer");
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
+    TempBuf tQ{h, svhip_handle::SCR_IN0}, tG{h, svhip_handle::SCR_IN1}, tS{h, svhip_handle::SCR_OUT0}, tI{h, svhip_handle::SCR_OUT1};
+    const void *dQ, *dG;
+    void *dS, *dI;
+    int rc;
+    if ((rc = tQ.in(Q, (size_t)N * D * 4, din, &dQ))) return rc;
+    if ((rc = tG.in(G, (size_t)M * D * 4, din, &dG))) return rc;
+    if ((rc = tS.out(out_score, (size_t)N * k * 4, dout, &dS))) return rc;
+    if ((rc = tI.out(out_index, (size_t)N * k * 4, dout, &dI))) return rc;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dG)) & 15) == 0;
+    if (score_topk_fused_supported(D) && aligned) {
+        constexpr int64_t CHUNK = 16384;
+        for (int64_t r0 = 0; r0 < N && !rc; r0 += CHUNK) {
+            const int64_t rows = std::min(CHUNK, N - r0);
+            const int64_t tail = rows % 128;
+            const int64_t n_few = (tail >= 1 && tail <= 32) ? tail : 0, n_many = rows - n_few;
+            const float* q = (const float*)dQ + r0 * D;
+            if (n_many) rc = topk_fused_part(h, q, n_many, (const float*)dG, M, D, k, false, (float*)dS + r0 * k, (int32_t*)dI + r0 * k);
+            if (!rc && n_few)
+                rc = topk_fused_part(h, q + n_many * D, n_few, (const float*)dG, M, D, k, true, (float*)dS + (r0 + n_many) * k, (int32_t*)dI + (r0 + n_many) * k);
+        }
+    } else {
+        rc = topk_slab(h, (const float*)dQ, N, (const float*)dG, M, D, k, (float*)dS, (int32_t*)dI);
+    }
+    if (!rc && !dout) {
+        hipError_t e = hipMemcpyAsync(out_score, dS, (size_t)N * k * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(out_index, dI, (size_t)N * k * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e != hipSuccess) { h->err = std::string("score_topk: copy of the results failed: ") + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
+    }
+    if (rc || !(din && dout && (flags & SVHIP_ASYNC))) {
+        const hipError_t e = hipStreamSynchronize(h->stream);
+        if (!rc && e != hipSuccess) { h->err = std::string("score_topk: ") + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
+        release_big_scratch(h, !din || !dout);
+    }
+    return rc;
 }
 
 int64_t svhip_asnorm_last_fallback(const svhip_handle* h) { return h ? h->last_asnorm_flagged : -1; }

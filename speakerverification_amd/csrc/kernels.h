@@ -692,6 +692,31 @@ hipError_t launch_asnorm_refit_init(const int32_t* ids, const int32_t* info, int
 hipError_t launch_asnorm_refit_next(const float* in, int n_in, const int32_t* pos, const int32_t* info, int left, float target, float* out, hipStream_t stream);
 hipError_t launch_scatter_stats(const float* m, const float* s, const int32_t* ids, int n, float* mu, float* sigma, hipStream_t stream);
 
+// 1:N identification (score_topk.hip): per row of Q the k best rows of G by score, ties to the lower index, NaN last — without the N x M
+// matrix.  The grid is query tiles x gallery slices; every lane of the fused kernel keeps the k best of the gallery rows it saw as a list of
+// (score bits, index) pairs in `lists`, score_topk_merge orders the `nlists` lists of a query.
+struct ScoreTopkParams {
+    const float* Q = nullptr;       // (N, D) queries of this launch
+    int64_t N = 0;
+    const float* G = nullptr;       // (M, D) gallery
+    int64_t M = 0;
+    int k = 0;
+    int cap = 0;                    // slots per list (score_topk_cap)
+    int per = 0;                    // blocks of 32 gallery rows per slice
+    int nlists = 0;                 // lists per query: 2 per slice (8 where the waves of a workgroup walk different blocks: `few`)
+    uint2* lists = nullptr;         // (N, nlists, cap)
+    int32_t* cnt = nullptr;         // (N, nlists) entries each list holds (<= k when the kernel has ended)
+};
+constexpr int SCORE_TOPK_MAX_K = 128;
+bool score_topk_fused_supported(int D);
+int score_topk_cap(int k);
+// few: the launch's queries fit one wave (N <= 32): the four waves of a workgroup take different gallery blocks of the slice
+hipError_t launch_score_topk(const ScoreTopkParams& p, int D, bool few, int slices, hipStream_t stream);
+hipError_t launch_score_topk_merge(const uint2* lists, const int32_t* cnt, int64_t rows, int nlists, int cap, int k, float* out_score,
+                                   int32_t* out_index, hipStream_t stream);
+// the slab route: the k best of each row of S (rows x M, row stride ld), same order
+hipError_t launch_score_topk_rows(const float* S, int64_t rows, int64_t M, int64_t ld, int k, float* out_score, int32_t* out_index, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // Verification metrics (metrics.hip): one workspace of metrics_workspace_bytes(P) holds the sorted trial list
 // ---------------------------------------------------------------------------------------------

@@ -508,6 +508,32 @@ class Engine:
                                              (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
         return out
 
+    def score_topk(self, Q, G, k, out=None):
+        """1:N identification (``svhip_score_topk``): per row of Q (N, D) the k best rows of the gallery G (M, D) by inner product ->
+        ``(scores (N, k) float32, index (N, k) int32)``, best first; equal scores go to the lower gallery index, NaN scores last.
+        ``out``: a preallocated ``(scores, index)`` pair in the inputs' memory space."""
+        N, D = Q.shape
+        M = G.shape[0]
+        if G.shape[1] != D:
+            raise ValueError(f"queries are {D} wide, the gallery {G.shape[1]}")
+        k = int(k)
+        if out is None:
+            shape = (N, max(k, 0))
+            if _is_torch(Q) and Q.is_cuda:
+                out = (torch.empty(shape, dtype=torch.float32, device=Q.device), torch.empty(shape, dtype=torch.int32, device=Q.device))
+            else:
+                out = (np.empty(shape, np.float32), np.empty(shape, np.int32))
+        scores, index = out
+        q, g = _Buf(Q, np.float32), _Buf(G, np.float32)
+        s, i = _Buf(scores, np.float32, writable=True), _Buf(index, np.int32, writable=True)
+        if s.nbytes != N * max(k, 0) * 4 or i.nbytes != s.nbytes:
+            raise ValueError(f"out must be a ({N}, {k}) float32 and a ({N}, {k}) int32 array")
+        dev = self._same_space(q, g, s, i)
+        self._ck(self.lib.svhip_score_topk(self.h, q.ptr, N, g.ptr, M, D, k, s.ptr, i.ptr,
+                                           (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
+        _count([q, g], [s, i])
+        return scores, index
+
     # ---- verification metrics (host arrays in / out; the trial list is small next to the embeddings) --------------------
     def _scores_labels(self, scores, labels):
         if _is_torch(scores):

@@ -510,6 +510,63 @@ class ModelHandling:
                 return mean_embed
         raise NotImplementedError
 
+    # ---- 1:N identification -------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _gallery(embeds, classes):
+        """the three forms of an enrolled gallery -> ((n_class, nOut) float32 crop-mean rows, {index: name} or None)"""
+        if isinstance(embeds, (str, Path)):
+            d = Path(embeds)
+            if classes is None and (d / "classes.npy").exists():
+                classes = np.load(str(d / "classes.npy"), allow_pickle=True).item()
+            embeds = torch.load(d / "embeds.pt")
+        g = np.array(_host(embeds), dtype=np.float32)      # (a copy: the rows are normalised in place later)
+        if g.ndim == 3:                                  # prepare('embed'): (num_eval, nOut, n_class)
+            g = g.mean(axis=0).T
+        elif g.ndim != 2:
+            raise ValueError(f"embeds must be (num_eval, nOut, n_class) or (n_class, nOut), not {g.shape}")
+        if classes is not None and not isinstance(classes, dict):
+            classes = dict(enumerate(np.asarray(classes).tolist()))
+        if classes is not None and len(classes) != g.shape[0]:
+            raise ValueError(f"{len(classes)} class names for {g.shape[0]} enrolled classes")
+        return np.ascontiguousarray(g), classes
+
+    def identify(self, source, embeds, classes=None, top=1, num_eval=10):
+        """Whose voice is this?  The ``top`` best enrolled classes of every file of ``source`` (what ``_embed_files`` takes: a list of
+        paths / arrays, or one of them) against a gallery: the directory ``prepare('embed')`` wrote (``embeds.pt``, ``classes.npy``),
+        a ``(num_eval, nOut, n_class)`` tensor in that layout, or an ``(n_class, nOut)`` array.
+
+        Rule: each crop embedding is L2-normalised when the loss sets ``test_normalize``; the crops are averaged; the mean is
+        L2-normalised.  The gallery is treated the same way (mean over its crop axis, then L2-normalised), and the score is the cosine
+        of the two.  (The reference's ``predict`` loop, src/inference.py:254-327, averages per-crop L2 distances d and reports
+        1 - d^2 / 2: the same cosine for one crop of unit vectors; for several crops this project averages embeddings, as its AS-norm
+        path does.)  Files are embedded in batches (whole files through the ragged path with ``num_eval=0``) and searched in ONE
+        ``score_topk`` call.
+
+        Returns ``(scores (n_files, top) float32, index (n_files, top) int32)``, best first, and as a third item the class names
+        (a list of ``top`` names per file) when ``classes`` is given ({index: name} or a sequence) or the directory holds ``classes.npy``."""
+        self.__model__.eval()
+        files = list(source) if isinstance(source, (list, tuple)) else [source]
+        if not files:
+            raise ValueError("Please provide appropriate source!")
+        gal, classes = self._gallery(embeds, classes)
+        top = int(top)
+        if top < 1 or top > gal.shape[0]:
+            raise ValueError(f"top = {top} must lie in [1, n_class = {gal.shape[0]}]")
+        eng = scoring.scoring_engine(self.gpu)
+        feats = np.asarray(_host(self._embed_files(files, num_eval)), dtype=np.float32)       # (n_files, n_crops, nOut)
+        if feats.shape[-1] != gal.shape[1]:
+            raise ValueError(f"the model embeds to {feats.shape[-1]} values, the gallery holds {gal.shape[1]}")
+        flat = np.ascontiguousarray(feats.reshape(-1, feats.shape[-1]))
+        if self.__model__.module.test_normalize:
+            eng.l2norm_(flat)
+        q = np.ascontiguousarray(flat.reshape(feats.shape).mean(axis=1))
+        eng.l2norm_(q)
+        eng.l2norm_(gal)
+        scores, index = scoring.score_topk(q, gal, top, device=self.gpu)
+        if classes is None:
+            return scores, index
+        return scores, index, [[classes[int(i)] for i in row] for row in np.asarray(_host(index))]
+
     # ---- checkpoints ------------------------------------------------------------------------------------------------------
     def saveParameters(self, path):
         torch.save(self.__model__.module.state_dict(), path)

@@ -1,7 +1,7 @@
 """Scoring counterparts of the reference's ``src/utils.py:126-169``.
 
 ``similarity_measure(method, ref, com, **kw)`` keeps the per-trial signature for compatibility; the
-batched entry points (``score_pairs``, ``score_matrix``, ``asnorm_stats``, ``asnorm_pairs``,
+batched entry points (``score_pairs``, ``score_matrix``, ``score_topk``, ``asnorm_stats``, ``asnorm_pairs``,
 ``score_trials``) are what ``ModelHandling.evaluateFromList`` uses: one kernel launch per trial LIST
 instead of three host<->device crossings per trial.
 """
@@ -51,6 +51,11 @@ def score_pairs(E, ia, ib, device=0):
 
 def score_matrix(A, B, device=0):
     return scoring_engine(device).score_matrix(A, B)
+
+
+def score_topk(Q, G, k, device=0):
+    """per row of Q the k best rows of the gallery G by inner product -> (scores (N, k), int32 index (N, k)), best first"""
+    return scoring_engine(device).score_topk(Q, G, k)
 
 
 def asnorm_stats(E, cohort, top=200, device=0):
