@@ -313,7 +313,8 @@ int svhip_conformer_ragged_check(const svhip_config* cfg, const int32_t* lengths
  * both computes); to the precision of the compute type against a fixed-length call, which stays bit for bit what it was.  A non-finite
  * input gives NaN for its own utterance only, and SVHIP_ERR_NONFINITE.
  * STAGES after a ragged call: tn_prolog, tn_dw0, tn_mega_last (sum T_i, H) and tn_enc (sum T_i, 1536), rows packed in utterance order;
- * tn_pool (n, 3072); "mel" the packed (n_mels, T_i) blocks. */
+ * tn_pool (n, 3072); with option tn_keep also tn_b<i>_skip | _dw0 | _pw0 | _dw1 | _pw1 | _dw2 | _pw2 | _out, tn_att and tn_logits (sum T_i rows),
+ * tn_b<i>_mean, tn_b<i>_gate and tn_pool_raw (n rows); "mel" the packed (n_mels, T_i) blocks. */
 int svhip_titanet_embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
                                int32_t flags, int32_t is_wave);
 /* lengths[i] are samples (is_wave != 0) or frames.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is svhip_last_error(NULL). */
@@ -505,7 +506,13 @@ int svhip_synth_waveforms(svhip_handle* h, uint64_t seed, int64_t first_utt, int
  *                  "rn_b<i>_pre", "rn_b<i>_x", "rn_b<i>_o", "rn_b<i>_c2", "rn_b<i>_pool", "rn_b<i>_gate", "rn_agg_in", "rn_logits") — SVHIP_ERR_STATE
  *                  where the route taken never stored the tensor;
  *                  "tn_prolog" (B T, H), "tn_dw0" (block 0's first depthwise output, its bias included), "tn_mega_last" (the last
- *                  mega-block's output), "tn_enc" (B T, 1536) and "tn_pool" (B, 3072, after BN) of SVHIP_MODEL_TITANET;
+ *                  mega-block's output), "tn_enc" (B T, 1536) and "tn_pool" (B, 3072, after BN) of SVHIP_MODEL_TITANET, and with option
+ *                  "tn_keep" what its forward stored on its way: per mega-block i "tn_b<i>_skip" (B T, H: the 1 x 1 skip + BN),
+ *                  "tn_b<i>_dw0" | "_pw0" | "_dw1" | "_pw1" | "_dw2" | "_pw2" (the three depthwise and pointwise outputs; dw0 of block 0 is
+ *                  tn_dw's, of a later block the previous block tail's), "tn_b<i>_out" (the block's output), "tn_b<i>_gate" (B, H fp32:
+ *                  the SE gate) and "tn_b<i>_mean" (B, H fp32: the SE squeeze, only where the squeeze kernel ran — SVHIP_ERR_STATE
+ *                  where the gate came from the GEMM's column sums), then "tn_att" (B T, 128), "tn_logits" (B T, 1536 fp32) and
+ *                  "tn_pool_raw" (B, 3072 fp32: [mean | std] before BN) — SVHIP_ERR_STATE without the option;
  *                  "cf_in" (B T', 256: the input projection), "cf_block0", "cf_attn0" (block 0's per-head attention context before
  *                  out_proj), "cf_last" (the last block's output) and "cf_pool" (B, 512, after attention_norm) of SVHIP_MODEL_CONFORMER,
  *                  and with option "cf_keep" what its forward stored on its way: per block i = 0 .. 5 "cf_b<i>_ff1" (B T', 256: after
@@ -532,7 +539,7 @@ double svhip_workload_flops(const svhip_handle* h);
  * "pw3_cus" (cap of the persistent GEMM grids; 0: off), "rn_unfused", "asp_v1", "r2_big", "x3_keep_f32",
  * "asnorm_slab", "asnorm_f32mfma", "asnorm_norefit", "score_f32mfma", "score_tiled", "fbank32", "fbank_unfused", "rn_sinc_full", "cv_off",
  * "pw3_tail_off", "n128_off", "r2_slices", "rn_tail_big", "rn_sinc_f32", "rn_step_off", "rn_pool_off", "layer_labels", "rn_conv_unfused",
- * "rn_keep", "cf_keep".
+ * "rn_keep", "cf_keep", "tn_keep".
  * Unknown names: SVHIP_ERR_INVALID. */
 int svhip_set_option(svhip_handle* h, const char* name, int32_t value);
 /* Free the scoring / metrics scratch slots of the handle (grown on demand, otherwise kept until svhip_destroy). */

@@ -56,6 +56,7 @@ struct TitaNetState : ModelState {
     float *pool_raw = nullptr, *pool = nullptr;              // (Bmax, 3072) pooled [mean | std], after BN
     // ragged packs (allocated by the first ragged call; the buffers above already hold Bmax T rows)
     RagTables rag;                        // the tables of a call (one level: mel frames, Bmax T rows) and the waveform staging buffer
+    KeptStages keep;                      // option tn_keep: copies of what the walk stored, by stage name (keep_stage fills them)
 };
 
 TitaNetState& S(svhip_handle* h) { return static_cast<TitaNetState&>(*h->model); }
@@ -240,6 +241,15 @@ static int titanet_walk(svhip_handle* h, const float* d_feat, int B, const RagPa
     void *PRO = s.buf[0], *X = s.buf[1], *D0 = s.buf[2], *D = s.buf[3], *Sb = s.buf[4], *K = s.buf[5];
     float* cs = !g && bf ? h->d_colsum : nullptr;       // the third pointwise GEMM's column-sum partials (fixed form, bf16)
     int rc;
+    // option tn_keep: the M x cols tensor block i has just stored (i < 0: the pooling's; `utt_rows`: one row per utterance), copied on st
+    ++s.keep.epoch;
+    auto keep = [&](int i, const std::string& what, const void* src, int cols, bool f32 = false, bool utt_rows = false) -> int {
+        if (!h->opt.tn_keep) return SVHIP_OK;
+        const std::string name = i < 0 ? "tn_" + what : "tn_b" + std::to_string(i) + "_" + what;
+        const int kind = f32 ? KEEP_F32 : KEEP_DT;
+        if (utt_rows) return keep_stage(h, s.keep, st, name, src, kind, g ? (size_t)B : 1, g != nullptr, (size_t)c.max_batch, cols, 0, (size_t)B, B);
+        return keep_stage(h, s.keep, st, name, src, kind, g ? (size_t)M : (size_t)T, g != nullptr, (size_t)c.max_batch * h->T, cols, 0, (size_t)M, B);
+    };
     auto gemm = [&](const ConvLayer& L, GemmParams p, GemmPlan* plan = nullptr) {
         if (!g) return conv_gemm(h, L, p, nullptr, 0, plan);
         p.rag_utt = g->utt; p.rag_row0 = g->row0;
@@ -280,30 +290,31 @@ static int titanet_walk(svhip_handle* h, const float* d_feat, int B, const RagPa
     const void* x = PRO;
     for (int i = 0; i < nb; ++i) {
         const TnBlock& Bk = s.blocks[i];
-        if ((rc = gemm(Bk.skip, conv_params(h, Bk.skip, x, H, K, H, M, T)))) return rc;
-        if (i == 0 && (rc = dw(x, D0, Bk.dw_w[0], Bk.dw_b[0]))) return rc;
+        if ((rc = gemm(Bk.skip, conv_params(h, Bk.skip, x, H, K, H, M, T))) || (rc = keep(i, "skip", K, H))) return rc;
+        if (i == 0 && ((rc = dw(x, D0, Bk.dw_w[0], Bk.dw_b[0])) || (rc = keep(0, "dw0", D0, H)))) return rc;
         const void* d = i == 0 ? D0 : D;
         GemmPlan g3;
         for (int j = 0; j < 3; ++j) {
             GemmParams p = conv_params(h, Bk.pw[j], d, H, Sb, H, M, T);
             p.act1 = ACT_RELU;
             if (j == 2 && !g) { p.colsum = cs; p.colsum_stride = h->colsum_region; }
-            if ((rc = gemm(Bk.pw[j], p, &g3))) return rc;
+            if ((rc = gemm(Bk.pw[j], p, &g3)) || (rc = keep(i, "pw" + std::to_string(j), Sb, H))) return rc;
             if (j < 2) {
-                if ((rc = dw(Sb, D, Bk.dw_w[j + 1], Bk.dw_b[j + 1]))) return rc;
+                if ((rc = dw(Sb, D, Bk.dw_w[j + 1], Bk.dw_b[j + 1])) || (rc = keep(i, "dw" + std::to_string(j + 1), D, H))) return rc;
                 d = D;
             }
         }
         // squeeze-excitation (titanet_blocks.py:162-192): the squeeze from the GEMM's column sums when its kernel wrote them (never for a
         // pack: launch_gemm_ragged leaves g3 as it is)
         const bool from_part = g3.colsum_groups != 0;
-        if (!from_part && (rc = squeeze())) return rc;
+        if (!from_part && ((rc = squeeze()) || (rc = keep(i, "mean", s.mean, H, true, true)))) return rc;
         if ((rc = run(h, "tn_se_mlp", 4.0 * B * (H / 16) * H, [&]() {
                  return launch_se_mlp(from_part ? nullptr : s.mean, from_part ? cs : nullptr, T, bf ? Bk.se1_bf : (const void*)Bk.se1, h->d_zeros,
                                       bf ? Bk.se2T_bf : (const void*)Bk.se2T, h->d_zeros, s.gate, bf, B, H, H / 16, st, from_part ? g3.colsum_groups : 8);
-             }))) return rc;
+             })) || (rc = keep(i, "gate", s.gate, H, true, true))) return rc;
         // relu(skip + SE(sub_blocks(x))) and the next block's first depthwise conv                     TitaNet.py:306-318
-        if ((rc = tail(i + 1 < nb ? &s.blocks[i + 1] : nullptr))) return rc;
+        if ((rc = tail(i + 1 < nb ? &s.blocks[i + 1] : nullptr)) || (rc = keep(i, "out", X, H))) return rc;
+        if (i + 1 < nb && (rc = keep(i + 1, "dw0", D, H))) return rc;
         x = X;
     }
     // epilog: relu(BN(conv1x1(x)))                                                   TitaNet.py:244-245
@@ -314,14 +325,14 @@ static int titanet_walk(svhip_handle* h, const float* d_feat, int B, const RagPa
     // sqrt(clamp(var, 1e-6)) (the variance in the centred form), then decoder.pool.1
     GemmParams pa = conv_params(h, s.att_in, s.enc, E, s.att, 128, M, T);
     pa.act2 = ACT_TANH;
-    if ((rc = gemm(s.att_in, pa))) return rc;
+    if ((rc = gemm(s.att_in, pa)) || (rc = keep(-1, "att", s.att, 128))) return rc;
     GemmParams pl = conv_params(h, s.att_out, s.att, 128, s.logits, E, M, T);
     pl.out_f32 = 1;
-    if ((rc = gemm(s.att_out, pl))) return rc;
+    if ((rc = gemm(s.att_out, pl)) || (rc = keep(-1, "logits", s.logits, E, true))) return rc;
     if ((rc = run(h, g ? "rag_asp_pool" : "tn_asp_pool", 0, [&]() {
              return g ? launch_rag_asp_pool(s.logits, s.enc, bf, E, g->row0, B, E, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-6f, st)
                       : launch_asp_pool(s.logits, s.enc, bf, E, B, T, E, s.pbn_scale, s.pbn_shift, s.pool_raw, s.pool, 1e-6f, 0.0f, st);
-         }))) return rc;
+         })) || (rc = keep(-1, "pool_raw", s.pool_raw, 2 * E, true, true))) return rc;
     // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the ReLU epilogues would have dropped it): its
     // own row only
     if ((rc = run(h, "tn_in_check", 0, [&]() {
@@ -357,8 +368,20 @@ int titanet_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool is
     return SVHIP_OK;
 }
 
+// the stages of option tn_keep: tn_att, tn_logits, tn_pool_raw, tn_b<block>_skip | _dw0 | _pw0 | _dw1 | _pw1 | _dw2 | _pw2 | _mean | _gate | _out
+static bool tn_keep_name(const std::string& n) {
+    if (n == "tn_att" || n == "tn_logits" || n == "tn_pool_raw") return true;
+    if (n.compare(0, 4, "tn_b") != 0) return false;
+    size_t i = 4;
+    while (i < n.size() && n[i] >= '0' && n[i] <= '9') ++i;
+    if (i == 4 || i > 6 || i >= n.size() || n[i] != '_' || atoi(n.c_str() + 4) >= SVHIP_TITANET_MAX_BLOCKS) return false;
+    const std::string w = n.substr(i + 1);
+    for (const char* q : {"skip", "dw0", "pw0", "dw1", "pw1", "dw2", "pw2", "mean", "gate", "out"}) if (w == q) return true;
+    return false;
+}
+
 // (after a ragged forward the (rows, H) stages and tn_enc are the packed sum T_i rows: svhip_get_stage sets them from rag_rows)
-int titanet_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // tn_prolog, tn_dw0, tn_mega_last, tn_enc, tn_pool
+int titanet_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {      // tn_prolog, tn_dw0, tn_mega_last, tn_enc, tn_pool; option tn_keep's
     auto& s = S(h);
     const int H = h->cfg.channels;
     if (n == "tn_prolog") { v.src = s.buf[0]; v.cols = v.ld = H; }
@@ -366,6 +389,7 @@ int titanet_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {  
     else if (n == "tn_dw0") { v.src = s.buf[2]; v.cols = v.ld = H; }
     else if (n == "tn_enc") { v.src = s.enc; v.cols = v.ld = 1536; }
     else if (n == "tn_pool") { v.src = s.pool; v.rows = h->lastB; v.cols = v.ld = 3072; v.f32 = true; }
+    else if (tn_keep_name(n)) return kept_view(h, s.keep, n, h->lastB, "tn_keep", h->opt.tn_keep != 0, v);
     else return unknown_stage(h, n);
     return SVHIP_OK;
 }
