@@ -341,7 +341,9 @@ int svhip_titanet_ragged_check(const svhip_config* cfg, const int32_t* lengths, 
  * handle of its length at B = 1, and the embedding agrees with it to the precision of the compute type.  The fixed-length call stays bit
  * for bit what it was.  A non-finite input gives NaN for its own utterance only, and SVHIP_ERR_NONFINITE.
  * STAGES after a ragged call: rs_stem, rs_layer1 .. rs_layer4 (sum_i P_l,i * Q_l, C_l), the images packed in utterance order; rs_pool
- * (n, 2 F); "mel" the packed (n_mels, T_i) blocks. */
+ * (n, 2 F); with option rs_keep also rs_xin (sum T_i rows), rs_b<i>_conv1 | _conv2 | _down | _out (the packed images of the block's
+ * level), rs_b<i>_part (the pack's tiles in pack order: utterance by utterance, each in its own tile order), rs_b<i>_gate and
+ * rs_pool_raw (n rows), rs_att and rs_logits (sum_i P_4,i rows); "mel" the packed (n_mels, T_i) blocks. */
 int svhip_resnetse_embed_ragged(svhip_handle* h, const float* in, const int64_t* offsets, const int32_t* lengths, int32_t n, float* emb_out,
                                 int32_t flags, int32_t is_wave);
 /* lengths[i] are samples (is_wave != 0) or frames.  SVHIP_OK, SVHIP_ERR_INVALID or SVHIP_ERR_UNSUPPORTED; the message is svhip_last_error(NULL). */
@@ -522,7 +524,14 @@ int svhip_synth_waveforms(svhip_handle* h, uint64_t seed, int64_t first_utt, int
  *                  block's LayerNorm), then "cf_logits" (B T', 256 fp32: the pooling's logits) and "cf_pool_raw" (B, 512 fp32:
  *                  [mean | std] before attention_norm) — SVHIP_ERR_STATE without the option;
  *                  "rs_stem" (B P Q, 32: channels-last, P frames x Q mel rows), "rs_layer1" .. "rs_layer4" (each stage's output, B P' Q' x C)
- *                  and "rs_pool" (B, 512 n_mels / 8 fp32: [mean | std], feature q 256 + c) of SVHIP_MODEL_RESNETSE.
+ *                  and "rs_pool" (B, 512 n_mels / 8 fp32: [mean | std], feature q 256 + c) of SVHIP_MODEL_RESNETSE, and with option
+ *                  "rs_keep" what its forward stored on its way: "rs_xin" (B T, n_mels fp32: the normalised input), per block
+ *                  i = 0 .. 15 "rs_b<i>_conv1" | "_conv2" | "_out" (B P' Q', C: conv1 + bn1 + ReLU, conv2 + bn2, the block's output),
+ *                  "rs_b<i>_down" (the downsample + BN; blocks 3, 7, 13), "rs_b<i>_part" (B ntp ntq, C fp32: the SE sums of conv2's
+ *                  fp32 values over each tile's positions inside the image, tiles in the order tp ntq + tq) and "rs_b<i>_gate"
+ *                  (B, C fp32), then "rs_att" (B P4, 128), "rs_logits" (B P4, 256 n_mels / 8 fp32) and "rs_pool_raw" (B, 512
+ *                  n_mels / 8 fp32: [mean | std] before the pooling's affine, the identity here) — SVHIP_ERR_STATE without the
+ *                  option; "rs_layer<s>" is bit for bit the "_out" of the stage's last block.
  *                  Returns the element count through *count (out may be NULL to query).
  *   profile_*    : when enabled every kernel launch is bracketed by HIP events on the handle's
  *                  stream; profile_get returns accumulated milliseconds / launch count per kernel
@@ -539,7 +548,7 @@ double svhip_workload_flops(const svhip_handle* h);
  * "pw3_cus" (cap of the persistent GEMM grids; 0: off), "rn_unfused", "asp_v1", "r2_big", "x3_keep_f32",
  * "asnorm_slab", "asnorm_f32mfma", "asnorm_norefit", "score_f32mfma", "score_tiled", "fbank32", "fbank_unfused", "rn_sinc_full", "cv_off",
  * "pw3_tail_off", "n128_off", "r2_slices", "rn_tail_big", "rn_sinc_f32", "rn_step_off", "rn_pool_off", "layer_labels", "rn_conv_unfused",
- * "rn_keep", "cf_keep", "tn_keep".
+ * "rn_keep", "cf_keep", "tn_keep", "rs_keep".
  * Unknown names: SVHIP_ERR_INVALID. */
 int svhip_set_option(svhip_handle* h, const char* name, int32_t value);
 /* Free the scoring / metrics scratch slots of the handle (grown on demand, otherwise kept until svhip_destroy). */

@@ -53,6 +53,7 @@ const DevOptRow kDevOpts[] = {
     SV_OPT(rn_keep, "SVHIP_RN_KEEP", OPT_IS1, 0),
     SV_OPT(cf_keep, "SVHIP_CF_KEEP", OPT_IS1, 0),
     SV_OPT(tn_keep, "SVHIP_TN_KEEP", OPT_IS1, 0),
+    SV_OPT(rs_keep, "SVHIP_RS_KEEP", OPT_IS1, 0),
 };
 #undef SV_OPT
 

@@ -68,6 +68,7 @@ struct ResNetSEState : ModelState {
     int* rag_tiles = nullptr;             // RS_RAG_KINDS x (tile0 (Bmax + 1) | plan (Bmax)): the tile tables of a pack's convolutions
     float* rag_part = nullptr;            // the SE tile sums of a pack: rag_part_floats (rs_rag_part_floats) of them
     size_t rag_part_floats = 0;
+    KeptStages keep;                      // option rs_keep: copies of what the walk stored, by stage name (keep_stage fills them)
 };
 
 ResNetSEState& S(svhip_handle* h) { return static_cast<ResNetSEState&>(*h->model); }
@@ -329,6 +330,24 @@ static int resnetse_walk(svhip_handle* h, const float* d_feat, int B, const RagP
         }
     }
     float* part = g ? s.rag_part : s.part;
+    // option rs_keep: what block i has just stored (i < 0: outside the blocks), copied on st.  `rows` x cols per utterance of a fixed-length
+    // batch (`cap_rows` per utterance at most), or the `rag_rows` packed rows of a pack; utt_rows: one row per utterance
+    ++s.keep.epoch;
+    auto keep = [&](int i, const std::string& what, const void* src, size_t rows, size_t rag_rows, size_t cap_rows, int cols, bool f32 = false,
+                    bool utt_rows = false) -> int {
+        if (!h->opt.rs_keep) return SVHIP_OK;
+        const std::string name = i < 0 ? "rs_" + what : "rs_b" + std::to_string(i) + "_" + what;
+        const int kind = f32 ? KEEP_F32 : KEEP_DT;
+        if (utt_rows) return keep_stage(h, s.keep, st, name, src, kind, g ? (size_t)B : 1, g != nullptr, (size_t)Bmax, cols, 0, (size_t)B, B);
+        // (a pack of short utterances can have more tiles than max_batch fixed images: keep_stage grows the buffer then)
+        return keep_stage(h, s.keep, st, name, src, kind, g ? rag_rows : rows, g != nullptr, std::max(rag_rows, (size_t)Bmax * cap_rows), cols, 0,
+                          g ? rag_rows : (size_t)B * rows, B);
+    };
+    // an activation of level lv (0: the stem's image; 1 .. 4: a stage's) or of frame level lv - 1 of a pack
+    auto keep_act = [&](int i, const std::string& what, const void* src, int lv) {
+        const size_t q = s.Q[lv];
+        return keep(i, what, src, (size_t)s.P[lv] * q, g ? (size_t)g[lv ? lv - 1 : 0].M * q : 0, (size_t)s.P[lv] * q, s.C[lv]);
+    };
     // one convolution L of the block that writes level `lv` (= its stage), x -> y
     auto conv = [&](const char* label, const RsConv& L, const void* x, void* y, int P, int Q, int lv, bool relu_in, bool relu_out, float* pt,
                     RsConvParams& p) {
@@ -347,6 +366,7 @@ static int resnetse_walk(svhip_handle* h, const float* d_feat, int B, const RagP
     } else if ((rc = run(h, "prologue", 0, [&]() {
                     return launch_prologue(d_feat, s.xin, false, B, c.n_mels, h->T, c.log_input, h->d_ones, h->d_zeros, h->d_pstats, st);
                 }))) return rc;
+    if ((rc = keep(-1, "xin", s.xin, s.P[0], g ? (size_t)g[0].M : 0, s.P[0], s.Q[0], true))) return rc;
     // conv1 (with bias) -> ReLU -> bn1                                                       ResNetBaseline.py:260-262
     if ((rc = run(h, g ? "rs_stem_rag" : "rs_stem", 2.0 * 9 * s.C[0] * (g ? (double)g[0].M : (double)B * s.P[0]) * s.Q[0], [&]() {
              return g ? launch_rs_stem_ragged(s.xin, s.stem_w, s.stem_b, s.stem_scale, s.stem_shift, s.out[0], dt, g[0].row0, g[0].utt, g[0].M, s.Q[0], st)
@@ -361,21 +381,25 @@ static int resnetse_walk(svhip_handle* h, const float* d_feat, int B, const RagP
         const bool last = (int)i + 1 == s.stage_end[stage];
         void* out = last ? s.out[stage + 1] : s.tmp[pp];
         RsConvParams p1, p2, pd;
-        if ((rc = conv(kConvLabel[stage], K.c1, x, s.tmp[2], P, Q, stage, true, true, nullptr, p1))) return rc;
-        if ((rc = conv(kConvLabel[stage], K.c2, s.tmp[2], s.tmp[3], p1.Po, p1.Qo, stage, false, false, part, p2))) return rc;
+        const int bi = (int)i, lv = stage + 1;
+        if ((rc = conv(kConvLabel[stage], K.c1, x, s.tmp[2], P, Q, stage, true, true, nullptr, p1)) || (rc = keep_act(bi, "conv1", s.tmp[2], lv))) return rc;
+        if ((rc = conv(kConvLabel[stage], K.c2, s.tmp[2], s.tmp[3], p1.Po, p1.Qo, stage, false, false, part, p2)) ||
+            (rc = keep_act(bi, "conv2", s.tmp[3], lv))) return rc;
+        // the tile sums: ntp ntq rows per utterance, or the pack's tiles in pack order
+        if ((rc = keep(bi, "part", part, (size_t)p2.ntp * p2.ntq, g ? (size_t)rk[stage].ntiles : 0, (size_t)p2.ntp * p2.ntq, K.c2.cout, true))) return rc;
         if ((rc = run(h, g ? "rs_se_gate_rag" : "rs_se_gate", 0, [&]() {
                  return g ? launch_rs_se_gate_ragged(part, rk[stage].tile0, g[stage].row0, B, K.c2.cout, p2.Qo, K.se_w1, K.se_b1, K.se_w2, K.se_b2, s.gate, st)
                           : launch_rs_se_gate(part, p2.ntp * p2.ntq, B, K.c2.cout, p2.Po * p2.Qo, K.se_w1, K.se_b1, K.se_w2, K.se_b2, s.gate, st);
-             }))) return rc;
+             })) || (rc = keep(bi, "gate", s.gate, 1, 0, 1, K.c2.cout, true, true))) return rc;
         const void* res = x;
         if (K.has_down) {
-            if ((rc = conv("rs_down", K.down, x, s.tmp[4], P, Q, stage, true, false, nullptr, pd))) return rc;
+            if ((rc = conv("rs_down", K.down, x, s.tmp[4], P, Q, stage, true, false, nullptr, pd)) || (rc = keep_act(bi, "down", s.tmp[4], lv))) return rc;
             res = s.tmp[4];
         }
         if ((rc = run(h, g ? "rs_se_apply_rag" : "rs_se_apply", 0, [&]() {
                  return g ? launch_rs_se_apply_ragged(s.tmp[3], res, s.gate, out, dt, g[stage].utt, g[stage].M, p2.Qo, K.c2.cout, !K.has_down, st)
                           : launch_rs_se_apply(s.tmp[3], res, s.gate, out, dt, B, p2.Po * p2.Qo, K.c2.cout, !K.has_down, st);
-             }))) return rc;
+             })) || (rc = keep_act(bi, "out", out, lv))) return rc;
         x = out;
         P = p1.Po; Q = p1.Qo;
         if (!last) pp ^= 1;
@@ -390,14 +414,14 @@ static int resnetse_walk(svhip_handle* h, const float* d_feat, int B, const RagP
     };
     GemmParams pa = conv_params(h, s.att0, x, F, s.att, 128, M, Tg);
     pa.act1 = ACT_RELU;
-    if ((rc = gemm(s.att0, pa))) return rc;
+    if ((rc = gemm(s.att0, pa)) || (rc = keep(-1, "att", s.att, s.P[4], (size_t)M, s.P[4], 128))) return rc;
     GemmParams pl = conv_params(h, s.att3, s.att, 128, s.logits, F, M, Tg);
     pl.out_f32 = 1;
-    if ((rc = gemm(s.att3, pl))) return rc;
+    if ((rc = gemm(s.att3, pl)) || (rc = keep(-1, "logits", s.logits, s.P[4], (size_t)M, s.P[4], F, true))) return rc;
     if ((rc = run(h, g ? "rag_asp_pool" : "rs_asp_pool", 0, [&]() {
              return g ? launch_rag_asp_pool(s.logits, x, bf, F, g[3].row0, B, F, s.pool_one, s.pool_zero, s.pool_raw, s.pool, 1e-5f, st)
                       : launch_asp_pool(s.logits, x, bf, F, B, P, F, s.pool_one, s.pool_zero, s.pool_raw, s.pool, 1e-5f, 0.0f, st);
-         }))) return rc;
+         })) || (rc = keep(-1, "pool_raw", s.pool_raw, 1, 0, 1, 2 * F, true, true))) return rc;
     // an utterance with a non-finite input value gets a NaN embedding, as in the reference (the GEMM's ReLU epilogue would have dropped it):
     // its own row only
     if ((rc = run(h, "rs_in_check", 0, [&]() {
@@ -447,7 +471,20 @@ int resnetse_embed_ragged(svhip_handle* h, const float* in, bool in_host, bool i
     return SVHIP_OK;
 }
 
-// rs_stem, rs_layer1 .. rs_layer4 (B P Q, C), rs_pool (B, 2 F); after a ragged forward the packed rows (sum_u P_l,u Q_l, C_l) in utterance order
+// the stages of option rs_keep: rs_xin, rs_att, rs_logits, rs_pool_raw, rs_b<block>_conv1 | _conv2 | _part | _gate | _down | _out
+static bool rs_keep_name(const std::string& n) {
+    if (n == "rs_xin" || n == "rs_att" || n == "rs_logits" || n == "rs_pool_raw") return true;
+    if (n.compare(0, 4, "rs_b") != 0) return false;
+    size_t i = 4;
+    while (i < n.size() && n[i] >= '0' && n[i] <= '9') ++i;
+    if (i == 4 || i > 6 || i >= n.size() || n[i] != '_') return false;
+    const std::string w = n.substr(i + 1);
+    for (const char* q : {"conv1", "conv2", "part", "gate", "down", "out"}) if (w == q) return true;
+    return false;
+}
+
+// rs_stem, rs_layer1 .. rs_layer4 (B P Q, C), rs_pool (B, 2 F); after a ragged forward the packed rows (sum_u P_l,u Q_l, C_l) in utterance order;
+// option rs_keep's
 int resnetse_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {
     auto& s = S(h);
     int sg = -1;
@@ -458,6 +495,7 @@ int resnetse_stage(svhip_handle* h, const std::string& n, bool, StageView& v) {
         v.src = s.out[sg]; v.rows = frames * s.Q[sg]; v.cols = v.ld = s.C[sg];
     }
     else if (n == "rs_pool") { v.src = s.pool; v.rows = h->lastB; v.cols = v.ld = 2 * (size_t)s.C[4] * s.Q[4]; v.f32 = true; }
+    else if (rs_keep_name(n)) return kept_view(h, s.keep, n, h->lastB, "rs_keep", h->opt.rs_keep != 0, v);
     else return unknown_stage(h, n);
     return SVHIP_OK;
 }

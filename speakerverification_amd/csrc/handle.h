@@ -97,6 +97,7 @@ struct svhip_handle {
         int rn_keep;              // RawNet2: copy what the forward stores (block inputs, outputs, gates, logits) for svhip_get_stage; the kernels enqueued stay the same (tests)
         int cf_keep;              // Conformer: the same for every block's steps, the pooling logits and the pooled vector before attention_norm (tests)
         int tn_keep;              // TitaNet: the same for every mega-block's steps, its SE squeeze and gate, the attention layer, the logits and the pooled vector before BN (tests)
+        int rs_keep;              // ResNetSE: the same for the normalised input, every block's two convolutions, SE tile sums, gate, downsample and output, the attention layer, the logits and the pooled vector (tests)
     } opt;
     bool bf16 = false;                        // 16-bit storage handle: bf16, or fp16 when `f16` is set (the flag keeps its round-1 name)
     bool f16 = false;                         // SVHIP_F16: the 16-bit type is IEEE half (RawNet2)
@@ -299,7 +300,7 @@ struct ModelOps {
 };
 int unknown_stage(svhip_handle* h, const std::string& name);         // SVHIP_ERR_INVALID "unknown stage <name>"
 
-// api.hip: the options that keep what a forward stored on its way (rn_keep, cf_keep, tn_keep).  A model's state holds one KeptStages: copies of
+// api.hip: the options that keep what a forward stored on its way (rn_keep, cf_keep, tn_keep, rs_keep).  A model's state holds one KeptStages: copies of
 // what the forward stored, by stage name, `rows` per utterance or, after a ragged forward, the packed rows of all its utterances
 // (`packed`); `cap`: the buffer's bytes.  A stage counts as kept when every utterance of the last forward (`epoch`, which the forward
 // advances before its first copy) wrote it.

@@ -7,9 +7,8 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-from oracle import fbank as o_fbank
+from oracle import fbank as o_fbank, resnetse as o_resnetse
 from speakerverification_amd import _lib, checkpoint, synth
 from speakerverification_amd.models import ResNetSE34V2
 
@@ -37,55 +36,22 @@ def checksum(t):
 
 
 def ref64(sd, mel, features="melspectrogram", encoder_type="ASP", residual_relu=True):
-    """float64 restatement of ResNetSE.forward with SEBasicBlockV2 (ResNetBaseline.py:250-301, ResNetBlocks.py:229-246,303-307): returns the
-    stages in the reference's (B, C, n_mels', T') layout and the embedding.  residual_relu=False takes the identity residual from x, as
+    """float64 restatement of ResNetSE.forward with SEBasicBlockV2 (ResNetBaseline.py:250-301, ResNetBlocks.py:229-246,303-307;
+    oracle/resnetse.py, one utterance at a time): returns the stages in the reference's (B, C, n_mels', T') layout and the embedding.  residual_relu=False takes the identity residual from x, as
     the block would WITHOUT its in-place ReLU (only the first block's input has negative values)."""
-    t = {n: torch.from_numpy(np.asarray(v)).double() for n, v in sd.items() if np.asarray(v).dtype != np.int64}
-    x = torch.from_numpy(np.asarray(mel)).double()
-
-    def bn(y, p):
-        s = t[p + ".weight"] / torch.sqrt(t[p + ".running_var"] + 1e-5)
-        sh = t[p + ".bias"] - t[p + ".running_mean"] * s
-        shape = (1, -1) + (1,) * (y.ndim - 2)
-        return y * s.view(shape) + sh.view(shape)
-
-    if features == "melspectrogram":
-        x = torch.log(x + 1e-6)
-        x = x - x.mean(-1, keepdim=True)
-    x = (x - x.mean(-1, keepdim=True)) / torch.sqrt(x.var(-1, unbiased=False, keepdim=True) + 1e-5)     # InstanceNorm1d, no affine
-    x = x.unsqueeze(1)
-    st = {}
-    x = bn(F.relu(F.conv2d(x, t["conv1.weight"], t["conv1.bias"], padding=1)), "bn1")
-    st["rs_stem"] = x
-    for s in range(1, 5):
-        j = 0
-        while f"layer{s}.{j}.conv1.weight" in t:
-            p = f"layer{s}.{j}."
-            stride = 2 if (s > 1 and j == 0) else 1
-            r = F.relu(x)                                    # self.relu(x) is in place: x itself is relu(x) from here on
-            o = F.relu(bn(F.conv2d(r, t[p + "conv1.weight"], stride=stride, padding=1), p + "bn1"))
-            o = bn(F.conv2d(o, t[p + "conv2.weight"], padding=1), p + "bn2")
-            g = torch.sigmoid(F.relu(o.mean((2, 3)) @ t[p + "se.fc.0.weight"].T + t[p + "se.fc.0.bias"]) @ t[p + "se.fc.2.weight"].T
-                              + t[p + "se.fc.2.bias"])
-            res = r if residual_relu else x
-            if p + "downsample.0.weight" in t:
-                res = bn(F.conv2d(r, t[p + "downsample.0.weight"], stride=2), p + "downsample.1")
-            x = F.relu(o * g[:, :, None, None] + res)
-            j += 1
-        st[f"rs_layer{s}"] = x
-    x = x.reshape(x.shape[0], -1, x.shape[-1])
-    a = F.conv1d(x, t["attention.0.weight"], t["attention.0.bias"])
-    a = F.conv1d(bn(F.relu(a), "attention.2"), t["attention.3.weight"], t["attention.3.bias"])
-    w = torch.softmax(a, dim=2)
-    mu = (x * w).sum(2)
-    if encoder_type == "ASP":
-        sg = torch.sqrt(((x ** 2 * w).sum(2) - mu ** 2).clamp(min=1e-5))
-        pool = torch.cat([mu, sg], 1)
-    else:
-        pool = mu
-    st["rs_pool"] = pool
-    emb = pool @ t["fc.weight"].T + t["fc.bias"]
-    return {k: v.numpy() for k, v in st.items()}, emb.numpy()
+    t = o_resnetse.to_torch_sd(sd)
+    last = [i for i, p in enumerate(o_resnetse.block_names(t)) if p.endswith(".0.")][1:] + [len(o_resnetse.block_names(t))]
+    names = dict([("rs_stem", "stem")] + [(f"rs_layer{s + 1}", f"b{i - 1}_out") for s, i in enumerate(last)])
+    F_ = t["attention.3.weight"].shape[0]
+    st, emb = {n: [] for n in list(names) + ["rs_pool"]}, []
+    with torch.no_grad():
+        for m in torch.from_numpy(np.asarray(mel)).double():
+            s = {}
+            emb.append(o_resnetse.forward(m, t, log_input=features == "melspectrogram", residual_relu=residual_relu, stages=s).numpy())
+            for n, k in names.items():
+                st[n].append(s[k].permute(2, 1, 0).numpy())          # (P, Q, C) -> (C, Q, P)
+            st["rs_pool"].append(s["pool"].numpy()[:2 * F_ if encoder_type == "ASP" else F_])
+    return {k: np.stack(v) for k, v in st.items()}, np.stack(emb)
 
 
 def _rel(a, b):
