@@ -130,7 +130,9 @@ typedef struct svhip_config {
     int32_t samples;        /* L: samples per utterance (32000); fixes T = L/hop + 1 of the fixed-length calls and the row capacity max_batch * T of the ragged ones */
     int32_t log_input;      /* ECAPA: 1 = features=='melspectrogram' -> log(x+1e-6) - mean_t (ECAPA_TDNN.py:473-476) */
     int32_t input_norm;     /* ECAPA: InstanceNorm1d(n_mels, affine) (ECAPA_TDNN.py:406-409,477-478) */
-    /* mel front-end — defaults of models/FeatureExtraction/feature.py:66-71 */
+    /* mel front-end — defaults of models/FeatureExtraction/feature.py:66-71.  Served: an even n_fft <= 574, win_length % 8 == 0,
+       win_length <= n_fft, hop_length % 4 == 0 and a hop whose 32-frame tile (31 hops + one window of samples) fits a workgroup's
+       LDS; anything else is refused by svhip_create (SVHIP_ERR_UNSUPPORTED, the geometry in the message), never at a launch */
     int32_t fb_sr;          /* 8000 */
     int32_t n_fft;          /* 512 */
     int32_t win_length;     /* 200 */

@@ -62,6 +62,10 @@ int build_fbank_tables(svhip_handle* h) {
     fb.preemph = c.preemph;
     if (c.win_length % 8 != 0 || c.hop_length % 4 != 0 || fb.n_pairs > 9 || c.win_length > c.n_fft)
         SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "fbank geometry n_fft=%d win=%d hop=%d not supported", c.n_fft, c.win_length, c.hop_length);
+    // an odd n_fft: the reference pads n_fft / 2 samples on both sides, one sample less than a frame in all, and so has (L - 1) / hop + 1
+    // frames where every buffer of the library is sized for L / hop + 1
+    if (c.n_fft % 2 != 0)
+        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "fbank geometry n_fft=%d win=%d hop=%d not supported: n_fft must be even", c.n_fft, c.win_length, c.hop_length);
     const double PI = 3.14159265358979323846;
     // periodic Hamming (scipy get_window('hamming', win, fftbins=True)), cast to float32
     std::vector<float> win(c.win_length);
@@ -190,6 +194,13 @@ int build_fbank_tables(svhip_handle* h) {
     fb.mel_max_bin = 0;
     for (int i = 0; i < nm; ++i) fb.mel_max_bin = std::max(fb.mel_max_bin, mstart[i] + mlen[i] - 1);
     fb.basis = d_basis; fb.mel_w = d_mw; fb.mel_start = d_ms; fb.mel_len = d_ml; fb.mel_off = d_mo;
+    // the kernels' sample buffer grows with the hop: what launch_fbank will ask for must fit one workgroup's LDS on this device
+    int dev_lds = 0;
+    if (hipDeviceGetAttribute(&dev_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, c.device) != hipSuccess) dev_lds = 64 * 1024;
+    const size_t need = fbank_lds_needed(fb), have = std::min((size_t)dev_lds, fbank_lds_limit());
+    if (need > have)
+        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "fbank geometry n_fft=%d win=%d hop=%d n_mels=%d not supported: its tile needs %zu bytes of LDS, a workgroup has %zu",
+                c.n_fft, c.win_length, c.hop_length, c.n_mels, need, have);
     return SVHIP_OK;
 }
 

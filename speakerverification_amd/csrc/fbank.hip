@@ -24,6 +24,8 @@
 // 12 MFMAs instead of 3) is the open lead.
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -755,38 +757,77 @@ __global__ __launch_bounds__(256) void prologue_apply_pack_kernel(const float* _
     prologue_apply_tile<T_>(feat + feat_off[u], stats, out, n_mels, T, log_input, in_w, in_b, nullptr, nullptr, INFINITY, u, t0, r0);
 }
 
+// The dynamic LDS of the two kernels depends on the geometry (the sample buffer holds 31 or 63 hops + one window).  A launch above the
+// runtime's default of 64 KiB per workgroup needs the kernel's limit raised first; FB_LDS_MAX / F2_LDS_MAX are what the limits are
+// raised to.  The 64-frame kernel is only chosen where its tile fits F2_LDS_MAX (two workgroups per CU); the 32-frame kernel serves
+// every other geometry, so a geometry whose 32-frame tile exceeds a workgroup's LDS is refused at create (fbank_lds_needed).
+constexpr size_t FB_LDS_DEFAULT = 64 * 1024;
+constexpr size_t FB_LDS_MAX = 160 * 1024;      // one workgroup's LDS on gfx950
+constexpr size_t F2_LDS_MAX = 80 * 1024;
+
+size_t fbank32_lds(const FbankTables& tb) {
+    const int ns = (FB_FRAMES - 1) * tb.hop + tb.win_length;
+    const int ns_pad = ((ns + 15) & ~15) + 16;
+    return (size_t)(ns_pad + FB_FRAMES * FB_PT_STRIDE + tb.n_melw) * sizeof(float);
+}
+
+bool fbank_x6(const FbankTables& tb) { return tb.split6 && tb.basis_hi && tb.basis_lo && tb.basis_l3 && tb.hop % 8 == 0; }
+
+size_t fbank64_lds(const FbankTables& tb) {
+    const int ns2 = (F2_FRAMES - 1) * tb.hop + tb.win_length;
+    const int ns2_pad = ((ns2 + 15) & ~15) + 16;
+    return (size_t)(32 * F2_PT_STRIDE + tb.n_melw) * sizeof(float) + (size_t)ns2_pad * (fbank_x6(tb) ? 6 : 4);
+}
+
+// 64-frame kernel: needs the mel bank to stop below the Nyquist bin (eight pairs = 256 bins) and its tile in F2_LDS_MAX of LDS
+bool fbank64_eligible(const FbankTables& tb) { return tb.mel_max_bin < 256 && tb.n_pairs >= 8 && fbank64_lds(tb) <= F2_LDS_MAX; }
+
+hipError_t raise_lds(DeviceOnce& once, const void* fn, size_t lds, size_t cap) {
+    if (lds > cap) return hipErrorInvalidValue;
+    return lds > FB_LDS_DEFAULT ? set_max_dynamic_lds(once, fn, (int)cap) : hipSuccess;
+}
+
 }  // namespace
+
+// the largest dynamic LDS a launch_fbank of this bank sends (option fbank32 may ask for the 32-frame kernel at any time), and the
+// most launch_fbank can be given: build_fbank_tables refuses a geometry above either this or the device's own limit
+size_t fbank_lds_needed(const FbankTables& tb) { return std::max(fbank32_lds(tb), fbank64_eligible(tb) ? fbank64_lds(tb) : (size_t)0); }
+size_t fbank_lds_limit() { return FB_LDS_MAX; }
 
 hipError_t launch_fbank(const FbankTables& tb, const float* wav, int B, int L, int T, float* mel, hipStream_t stream) {
     if (tb.win_length % 8 != 0 || tb.hop % 4 != 0 || tb.n_pairs > 3 * FB_PAIRS_PER_WAVE ||
         tb.n_bins > 32 * tb.n_pairs || tb.n_q * 8 != tb.win_length || L < tb.n_fft || B <= 0)
         return hipErrorInvalidValue;
-    const int ns = (FB_FRAMES - 1) * tb.hop + tb.win_length;
-    const int ns_pad = ((ns + 15) & ~15) + 16;
-    const size_t lds = (size_t)(ns_pad + FB_FRAMES * FB_PT_STRIDE + tb.n_melw) * sizeof(float);
+    const size_t lds = fbank32_lds(tb);
     dim3 grid((T + FB_FRAMES - 1) / FB_FRAMES, B), block(FB_THREADS);
     if (tb.split_bf16 && (!tb.basis_hi || !tb.basis_lo || tb.hop % 8 != 0)) return hipErrorInvalidValue;
-    // 64-frame kernel: needs the mel bank to stop below the Nyquist bin (eight pairs = 256 bins) and its tile in 64 KiB of LDS
-    const int ns2 = (F2_FRAMES - 1) * tb.hop + tb.win_length;
-    const int ns2_pad = ((ns2 + 15) & ~15) + 16;
-    const bool x6 = tb.split6 && tb.basis_hi && tb.basis_lo && tb.basis_l3 && tb.hop % 8 == 0;
-    const size_t lds2 = (size_t)(32 * F2_PT_STRIDE + tb.n_melw) * sizeof(float) + (size_t)ns2_pad * (x6 ? 6 : 4);
-    if (tb.mel_max_bin < 256 && tb.n_pairs >= 8 && lds2 <= 80 * 1024 && !tb.force32) {
+    if (fbank64_eligible(tb) && !tb.force32) {
+        const size_t lds2 = fbank64_lds(tb);
         dim3 grid2((T + F2_FRAMES - 1) / F2_FRAMES, B);
-        if (x6) {
+        if (fbank_x6(tb)) {
             static DeviceOnce attr6;
-            if (hipError_t e = set_max_dynamic_lds(attr6, reinterpret_cast<const void*>(fbank64_kernel<2>), 80 * 1024)) return e;
+            if (hipError_t e = set_max_dynamic_lds(attr6, reinterpret_cast<const void*>(fbank64_kernel<2>), (int)F2_LDS_MAX)) return e;
             hipLaunchKernelGGL(fbank64_kernel<2>, grid2, dim3(F2_THREADS), lds2, stream, tb, wav, L, T, mel);
-        } else if (tb.split_bf16)
+        } else if (tb.split_bf16) {
+            static DeviceOnce attr1;
+            if (hipError_t e = raise_lds(attr1, reinterpret_cast<const void*>(fbank64_kernel<1>), lds2, F2_LDS_MAX)) return e;
             hipLaunchKernelGGL(fbank64_kernel<1>, grid2, dim3(F2_THREADS), lds2, stream, tb, wav, L, T, mel);
-        else
+        } else {
+            static DeviceOnce attr0;
+            if (hipError_t e = raise_lds(attr0, reinterpret_cast<const void*>(fbank64_kernel<0>), lds2, F2_LDS_MAX)) return e;
             hipLaunchKernelGGL(fbank64_kernel<0>, grid2, dim3(F2_THREADS), lds2, stream, tb, wav, L, T, mel);
+        }
         return hipGetLastError();
     }
-    if (tb.split_bf16)
+    if (tb.split_bf16) {
+        static DeviceOnce attr;
+        if (hipError_t e = raise_lds(attr, reinterpret_cast<const void*>(fbank_kernel<true>), lds, FB_LDS_MAX)) return e;
         hipLaunchKernelGGL(fbank_kernel<true>, grid, block, lds, stream, tb, wav, L, T, mel);
-    else
+    } else {
+        static DeviceOnce attr;
+        if (hipError_t e = raise_lds(attr, reinterpret_cast<const void*>(fbank_kernel<false>), lds, FB_LDS_MAX)) return e;
         hipLaunchKernelGGL(fbank_kernel<false>, grid, block, lds, stream, tb, wav, L, T, mel);
+    }
     return hipGetLastError();
 }
 

@@ -248,6 +248,10 @@ struct FbankTables {           // device pointers, built once per handle
 };
 // wav (B, L) fp32 -> mel power (B, n_mels, T) fp32
 hipError_t launch_fbank(const FbankTables& tb, const float* wav, int B, int L, int T, float* mel, hipStream_t stream);
+// the largest dynamic LDS launch_fbank sends for these (complete) tables, and the most its kernels are allowed: a geometry above the
+// limit, or above what the device offers one workgroup, is refused when the handle is created, never at its first launch
+size_t fbank_lds_needed(const FbankTables& tb);
+size_t fbank_lds_limit();
 
 // round 6, bf16 handles: wav (B, L) -> the 16-bit frame-major operand of blocks.0 (log-mel minus its time mean) in two launches
 bool fbank_fused_supported(const FbankTables& tb, int L);

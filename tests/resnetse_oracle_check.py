@@ -57,6 +57,7 @@ import torch
 
 from oracle import fbank as o_fbank, resnetse as orr
 from speakerverification_amd import synth
+from tests import fbank_emulation
 from tests.conformer_oracle_check import KSTEP, frame_errs, gain_err  # noqa: F401
 from tests.ecapa_oracle_check import bias_err, local_err, nearer_err, rel_err  # noqa: F401
 from tests.titanet_oracle_check import mel_emulated
@@ -177,37 +178,10 @@ def samples_of(T):
 
 
 def mel_emulated_split(wave):
-    """(L,) samples -> (80, T) mel power in fp32 as the front-end of a BF16 handle adds it up (fbank.hip, the bf16x3 form): the
-    pre-emphasised samples and the windowed DFT basis split into bf16 hi + lo parts, per k step of 16 taps the products lo hi, hi lo and
-    hi hi added to one fp32 accumulator per bin, |X|^2 as re^2 + im^2, each mel filter as a chain of fused multiply-adds over its bins.
-    The dropped lo lo term is 2^-16 of a product: after the log, 1e-4 of xin in a mel bin with little energy, where an f32 handle
-    (titanet_oracle_check.mel_emulated) keeps 1e-6"""
-    p = o_fbank.FBANK_DEFAULTS
-    n_fft, win, hop = p["n_fft"], p["win_length"], p["hop_length"]
-    lo = (n_fft - win) // 2
-    y = o_fbank.pre_emphasis(torch.as_tensor(wave, dtype=torch.float32)[None])
-    yp = torch.nn.functional.pad(y.unsqueeze(1), (n_fft // 2, n_fft // 2), mode="reflect")[0, 0]
-    fr = yp.unfold(0, n_fft, hop)[:, lo:lo + win].contiguous()                          # (T, 200)
-    fh = orr.bf16_round(fr)
-    fl = orr.bf16_round(fr - fh)
-    out = []
-    for k in o_fbank.fourier_kernels(n_fft, win, p["window"])[::-1]:                       # cos, sin
-        b = torch.from_numpy(np.ascontiguousarray(k[:, lo:lo + win].T))
-        bh = orr.bf16_round(b)
-        bl = orr.bf16_round(b - bh)
-        acc = torch.zeros(fr.shape[0], b.shape[1])
-        for k0 in range(0, win, 16):
-            sl = slice(k0, k0 + 16)
-            acc.addmm_(fl[:, sl], bh[sl])
-            acc.addmm_(fh[:, sl], bl[sl])
-            acc.addmm_(fh[:, sl], bh[sl])
-        out.append(acc)
-    power = out[0] * out[0] + out[1] * out[1]
-    mb = torch.from_numpy(o_fbank.mel_basis(p["sr"], n_fft, p["n_mels"], p["fmin"], p["fmax"]))
-    acc = power.new_zeros(power.shape[0], mb.shape[0])
-    for k in range(mb.shape[1]):
-        acc = orr._fma(mb[:, k], power[:, k:k + 1], acc)
-    return acc.T.contiguous()
+    """(L,) samples -> (80, T) mel power in fp32 as the front-end of a BF16 handle adds it up (fbank.hip, the bf16x3 form) at the default
+    geometry: tests/fbank_emulation.py states the sums and takes any geometry.  The dropped lo lo term is 2^-16 of a product: after the
+    log, 1e-4 of xin in a mel bin with little energy, where an f32 handle (titanet_oracle_check.mel_emulated) keeps 1e-6"""
+    return fbank_emulation.mel_emulated_split(wave)
 
 
 def engine_kw(T):

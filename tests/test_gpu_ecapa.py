@@ -564,3 +564,37 @@ def test_ecapa_reports_a_nonfinite_input(compute):
         assert np.isfinite(got[[0, 2]]).all()
     assert eng.lib.svhip_embed_features(eng.h, mel.ctypes.data, B, T, got.ctypes.data, 0) == 0 and np.array_equal(got, clean)
     eng.close()
+
+
+@pytest.mark.parametrize("compute", ["f32", "bf16"])
+def test_plugin_waveform_path_on_another_front_end(compute):
+    """The plug-in forwards the front-end keywords of a config to the engine (tests/test_host_logic.py shows them arrive): here the
+    handle they build runs.  16 kHz, n_fft = win = 400 (7 bin pairs: the 32-frame fbank kernel, lpad = 0), hop 160, a band-limited
+    bank, no pre-emphasis, from a waveform, against the float64 oracle of the network on the float64 oracle of the front-end at the
+    same keywords: f32 at the end-to-end bar of this file (1e-4 of the embedding scale, 1e-4 on the normalised embeddings), bf16 by
+    cosine at its bar of 0.999."""
+    from speakerverification_amd.models import ECAPA_TDNN
+    fe = dict(sr=16000, n_fft=400, win_length=400, hop_length=160, fmin=20.0, fmax=7600.0)
+    C, B, L = 512, 2, 16000
+    sd = synth.synth_state_dict(synth.ecapa_param_spec(C=C), seed=4)
+    m = ECAPA_TDNN.MainModel(nOut=192, channels=[C] * 4 + [3 * C], n_mels=80, features="melspectrogram", pre_emphasis=False,
+                             compute=compute, max_batch=B, **fe)
+    m.load_state_dict(sd)
+    wav = synth.synth_waveforms(B, L, seed=9)
+    out = np.asarray(m.embed_wave(wav), np.float64)
+    m._drop_engine()
+    from oracle import fbank as o_fbank
+    with torch.no_grad():
+        mel = o_fbank.melspectrogram(torch.from_numpy(wav).double(), pre_emph=False, **fe)
+        ref = o_ecapa.ecapa_forward(mel, o_ecapa.to_torch_sd(sd, torch.float64)).numpy()
+    assert out.shape == ref.shape == (B, 192) and mel.shape == (B, 80, L // 160 + 1)
+    scale = float(np.abs(ref).max())
+    err = float(np.abs(out - ref).max())
+    nrm = lambda a: a / np.linalg.norm(a, axis=1, keepdims=True)
+    err_n = float(np.abs(nrm(out) - nrm(ref)).max())
+    cos = np.sum(nrm(out) * nrm(ref), axis=1)
+    print(f"{compute}: max |d_emb| {err:.3e} of scale {scale:.1f}, normalised {err_n:.3e}, cos >= {cos.min():.6f}")
+    if compute == "f32":
+        assert err <= 1e-4 * max(1.0, scale) and err_n <= 1e-4
+    else:
+        assert np.isfinite(out).all() and float(cos.min()) >= 0.999

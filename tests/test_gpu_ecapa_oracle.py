@@ -32,8 +32,8 @@ def _num_cu():
     return torch.cuda.get_device_properties(0).multi_processor_count
 
 
-def _frames(L):
-    return L // 80 + 1
+def _frames(L, hop=80):
+    return L // hop + 1
 
 
 def _pw3_regime(M, N, num_cu):
@@ -73,14 +73,14 @@ def _sd(C, input_norm=False, n_mels=80):
     return _SD[key]
 
 
-def _oracle(x_row, C, wave, input_norm, n_fft, n_mels):
+def _oracle(x_row, C, wave, input_norm, fe, n_mels):
     """(the oracle's input features (1, n_mels, T), its embedding end to end) of one utterance, cached by input hash"""
-    key = hashlib.sha1(x_row.tobytes() + repr((C, wave, input_norm, n_fft, n_mels)).encode()).hexdigest()
+    key = hashlib.sha1(x_row.tobytes() + repr((C, wave, input_norm, sorted(fe.items()), n_mels)).encode()).hexdigest()
     if key not in _REF:
         _, sd64, _ = _sd(C, input_norm, n_mels)
         with torch.no_grad():
             x = torch.from_numpy(x_row).double()[None]
-            mel = o_fbank.melspectrogram(x, n_fft=n_fft, n_mels=n_mels) if wave else x
+            mel = o_fbank.melspectrogram(x, n_mels=n_mels, **fe) if wave else x
             feat = chk.features(mel, sd64, input_norm)
             _REF[key] = (feat, o_ecapa.ecapa_forward(feat, sd64, features="none").reshape(-1).numpy())
     return _REF[key]
@@ -101,14 +101,16 @@ def _stages(e, B, T, C):
 
 
 def run_case(compute, C, L, B, rows=None, wave=True, options=None, lanes=1, input_norm=False, n_fft=512, n_mels=80, tag="",
-             monkeypatch=None):
+             monkeypatch=None, front=None):
     """one forward, its stages against the oracle at `rows` (default _rows); returns (embeddings, kernel labels, the worst error of
-    every check).  Every error is printed; the bars are asserted after the whole case."""
-    T = _frames(L)
+    every check).  Every error is printed; the bars are asserted after the whole case.  front: the front-end keywords of the handle
+    and of the oracle (sr, n_fft, win_length, hop_length, fmin, fmax) where they are not the defaults."""
+    fe = dict(dict(n_fft=n_fft), **(front or {}))
+    T = _frames(L, fe.get("hop_length", 80))
     if lanes > 1:
         monkeypatch.setenv("SVHIP_LANES", str(lanes))
     sd, sd64, sdq = _sd(C, input_norm, n_mels)
-    e = Engine(model="ecapa", compute=compute, channels=C, max_batch=B, samples=L, input_norm=input_norm, n_fft=n_fft, n_mels=n_mels)
+    e = Engine(model="ecapa", compute=compute, channels=C, max_batch=B, samples=L, input_norm=input_norm, n_mels=n_mels, **fe)
     if lanes > 1:
         monkeypatch.delenv("SVHIP_LANES")
     e.load_state_dict(sd)
@@ -126,7 +128,7 @@ def run_case(compute, C, L, B, rows=None, wave=True, options=None, lanes=1, inpu
     e.close()
     worst, bad = {}, []
     for b in (_rows(B, T, lanes) if rows is None else rows):
-        feat, e2e = _oracle(x[b], C, wave, input_norm, n_fft, n_mels)
+        feat, e2e = _oracle(x[b], C, wave, input_norm, fe, n_mels)
         err = chk.layer_local(S, b, sdq if compute == "bf16" else sd64, ref_input=feat, emb=emb[b], e2e_ref=e2e,
                               bf16=compute == "bf16")
         print(f"{tag} {compute} C={C} T={T} B={B} b={b}: {chk.describe(err)}")
@@ -153,6 +155,7 @@ def _length_cases():
     return out
 
 
+FRONT_16K = dict(sr=16000, n_fft=512, win_length=400, hop_length=160)      # T = 201: the 64-frame fbank kernel at 76.9 KB of LDS
 OTHER_CASES = (
     ("C=512", "bf16", 512, 32000, 2, {}),
     ("C=512", "f32", 512, 32000, 2, {}),
@@ -165,6 +168,8 @@ OTHER_CASES = (
     ("per-file crops B=10", "bf16", 1024, 32000, 10, {}),
     ("per-file crops B=20", "bf16", 1024, 32000, 20, {}),
     ("two lanes B=64", "bf16", 1024, 32000, 64, dict(lanes=2)),
+    ("16 kHz front-end", "bf16", 512, 32000, 2, dict(front=FRONT_16K)),
+    ("16 kHz front-end", "f32", 512, 32000, 2, dict(front=FRONT_16K)),
 )
 FORCED = (
     ("pw3_cus=2", "bf16", dict(pw3_cus=2)),
@@ -221,6 +226,13 @@ def test_stages_at_edge_lengths(case, monkeypatch):
 @pytest.mark.parametrize("case", OTHER_CASES, ids=lambda c: f"{c[0]}-{c[1]}")
 def test_stages_on_other_geometries(case, monkeypatch):
     _case(case, monkeypatch)
+
+
+def test_another_front_end_takes_the_separate_kernels(monkeypatch):
+    """fbank_fused_supported takes the default window, FFT size and hop only: a bf16 handle at any other geometry runs fbank and the
+    prologue, and meets the same bars"""
+    labels = _case(next(c for c in OTHER_CASES if c[0] == "16 kHz front-end" and c[1] == "bf16"), monkeypatch)
+    assert "fbank" in labels and "prologue" in labels and "fbank_fused" not in labels, labels
 
 
 def test_stages_on_every_gemm_route(monkeypatch):

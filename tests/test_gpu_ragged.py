@@ -210,6 +210,43 @@ def test_ragged_against_the_library_itself(compute):
 
 
 @pytest.mark.parametrize("compute", ["f32", "bf16"])
+def test_ragged_pack_on_another_front_end(compute):
+    """the ragged waveform path at another window and hop (16 kHz, win 400, hop 160: per utterance the 64-frame fbank kernel at 76.9 KB
+    of LDS, on a bf16 handle the separate fbank + prologue kernels): three waveforms of different lengths in one call, each utterance's
+    mel rows and embedding against a fixed-length handle of its own length"""
+    C = 64
+    fe = dict(sr=16000, n_fft=512, win_length=400, hop_length=160)
+    Ts = [9, 65, 130]
+    wavs = _waves([(T - 1) * 160 + 37 for T in Ts], first=700)
+    e = Engine(model="ecapa", compute=compute, channels=C, max_batch=3, samples=32000, **fe)
+    e.load_state_dict(_sd(C)[0])
+    e.finalize()
+    emb = e.embed_wave_ragged(wavs)
+    assert emb.shape == (3, 192) and e.numeric_status() == 0 and np.isfinite(emb).all()
+    mel = e.get_stage("mel")
+    e.close()
+    assert mel.size == NMEL * sum(Ts)
+    pos = 0
+    for u, (w, T) in enumerate(zip(wavs, Ts)):
+        one = Engine(model="ecapa", compute=compute, channels=C, max_batch=1, samples=len(w), **fe)
+        one.load_state_dict(_sd(C)[0])
+        one.finalize()
+        alone = one.embed_wave(w[None])
+        mel1 = one.get_stage("mel")
+        one.close()
+        got = mel[pos:pos + NMEL * T]
+        pos += NMEL * T
+        with torch.no_grad():
+            ref = o_fbank.melspectrogram(torch.from_numpy(w).double()[None], n_mels=NMEL, **fe)[0].numpy()
+        e_mel = float(np.abs(got.reshape(NMEL, T) - ref).max() / np.abs(ref).max())
+        d_emb = chk.rel_err(emb[u], alone[0])[0]
+        print(f"{compute} u={u} T={T}: mel bit for bit {np.array_equal(got, mel1.reshape(-1))}, against the oracle {e_mel:.3g}; "
+              f"embedding bit for bit {np.array_equal(emb[u], alone[0])}, ragged vs alone {d_emb:.3g}")
+        assert mel1.size == NMEL * T and np.array_equal(got, mel1.reshape(-1)), (compute, u, T)
+        assert np.array_equal(emb[u], alone[0]), (compute, u, T, d_emb)
+
+
+@pytest.mark.parametrize("compute", ["f32", "bf16"])
 def test_batch_invariance_bit_for_bit(compute):
     """the same utterance first / last / between different neighbours / alone / in a pack of max_batch: its embedding and every stage
     are bit-for-bit the same"""

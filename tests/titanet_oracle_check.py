@@ -41,6 +41,7 @@ import torch
 
 from oracle import fbank as o_fbank, titanet as ot
 from speakerverification_amd import synth
+from tests import fbank_emulation
 from tests.conformer_oracle_check import KSTEP, frame_errs, gain_err  # noqa: F401
 from tests.ecapa_oracle_check import bias_err, local_err, nearer_err, rel_err  # noqa: F401
 
@@ -198,24 +199,9 @@ def mel_of(wave, dtype=torch.float64):
 
 
 def mel_emulated(wave, compute):
-    """(L,) samples -> (80, T) mel power in fp32 as the handle's front-end adds it up (fbank.hip): the windowed DFT over the 200 non-zero
-    taps as one accumulator per bin along the taps (chained_matmul: the MFMA's k-order; torch's blocked conv1d sums sat 2 x below the
-    chain's error at the prolog's gain), sqrt(re^2 + im^2) squared, each mel filter as a chain of fused multiply-adds over its bins"""
-    p = o_fbank.FBANK_DEFAULTS
-    n_fft, win, hop = p["n_fft"], p["win_length"], p["hop_length"]
-    lo = (n_fft - win) // 2
-    y = o_fbank.pre_emphasis(torch.as_tensor(wave, dtype=torch.float32)[None])
-    yp = torch.nn.functional.pad(y.unsqueeze(1), (n_fft // 2, n_fft // 2), mode="reflect")[0, 0]
-    fr = yp.unfold(0, n_fft, hop)[:, lo:lo + win].contiguous()                          # (T, 200)
-    wsin, wcos = (torch.from_numpy(np.ascontiguousarray(k[:, lo:lo + win].T)) for k in o_fbank.fourier_kernels(n_fft, win, p["window"]))
-    mm = ot.chained_matmul(KSTEP[compute])
-    re, im = mm(fr, wcos), mm(fr, wsin)
-    power = torch.sqrt(re * re + im * im) ** 2.0
-    mb = torch.from_numpy(o_fbank.mel_basis(p["sr"], n_fft, p["n_mels"], p["fmin"], p["fmax"]))
-    acc = power.new_zeros(power.shape[0], mb.shape[0])
-    for k in range(mb.shape[1]):
-        acc = ot._fma(mb[:, k], power[:, k:k + 1], acc)
-    return acc.T.contiguous()
+    """(L,) samples -> (80, T) mel power in fp32 as the handle's front-end adds it up (fbank.hip) at the default geometry: the DFT's
+    products added KSTEP[compute] at a time (tests/fbank_emulation.py states the sums and takes any geometry)"""
+    return fbank_emulation.mel_emulated(wave, kstep=KSTEP[compute])
 
 
 _FEATS = {}
