@@ -393,6 +393,24 @@ int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, con
  *                  labels "score_topk", "score_topk_merge") - no score reaches memory.  Every other width: slabs of query rows through
  *                  score_matrix's GEMM (its magnitude contract; at most 2 GiB, at least 128 rows: M <= 4 194 304, beyond it
  *                  SVHIP_ERR_UNSUPPORTED) and a row kernel ("score_topk_gemm", "score_topk_rows").
+ *   score_topk_norm : open-set 1:N identification: score_topk over adaptive-S-normalised scores, so that the best score can be compared
+ *                  with one threshold across speakers and channels.  Inputs: Q (N, D) with q_mu[N], q_sigma[N], G (M, D) with g_mu[M],
+ *                  g_sigma[M]; every statistic is fp32, as svhip_asnorm_stats writes them.  The coefficients are computed in fp32, one
+ *                  IEEE operation each,
+ *                      a = 0.5f / sigma          b = mu * a
+ *                  and the score is
+ *                      t(n, m) = fmaf( s(n, m), aq[n] + ag[m], -(bq[n] + bg[m]) )
+ *                  with s the fp32 inner product exactly as score_topk computes it on the same route: the algebraic
+ *                  0.5*((s-mu_q)/sd_q + (s-mu_g)/sd_g) of asnorm_pairs in a form with one rounding per step (exact on integer data).
+ *                  Result: per query the k largest t and their gallery rows, best first, in score_topk's order (t descending, ties to
+ *                  the lower index, NaN below every number, +inf first); out_score holds t.  Every gallery row has its own mean and
+ *                  deviation, so the ranking differs from the cosine ranking: the selection itself sees t.  No constraint is placed
+ *                  on the statistics: a zero, negative or non-finite sigma or mu gives whatever IEEE gives, and a NaN t sorts last.
+ *                  A row's result depends only on that row of Q, its two statistics, G and G's statistics - not on N, on the row's
+ *                  place in Q, on the gallery slicing or on which form of the kernel ran it: bit for bit.  Bounds, refusals, N = 0,
+ *                  pointer spaces and SVHIP_ASYNC as score_topk (messages start "score_topk_norm:"); a NULL statistic pointer is
+ *                  SVHIP_ERR_INVALID "NULL pointer".  Routes as score_topk; profile labels "score_topk_coef" (the coefficients, once per
+ *                  call), then "score_topk_norm", "score_topk_merge" (fused) or "score_topk_gemm", "score_topk_rows_norm" (slab).
  * Pointers follow `flags` (indices are int32, device or host like the other inputs). */
 int svhip_l2norm(svhip_handle* h, float* E, int64_t N, int32_t D, int32_t flags);
 int svhip_score_pairs(svhip_handle* h, const float* E, int64_t N, int32_t D,
@@ -405,6 +423,10 @@ int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, co
  * gallery rows they belong to, best first.  Pointers follow `flags`. */
 int svhip_score_topk(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, int32_t k,
                      float* out_score, int32_t* out_index, int32_t flags);
+/* as svhip_score_topk over t = fmaf(s, aq + ag, -(bq + bg)), a = 0.5f / sigma, b = mu * a (statement above); out_score holds t. */
+int svhip_score_topk_norm(svhip_handle* h, const float* Q, int64_t N, const float* q_mu, const float* q_sigma,
+                          const float* G, int64_t M, const float* g_mu, const float* g_sigma,
+                          int32_t D, int32_t k, float* out_score, int32_t* out_index, int32_t flags);
 int svhip_asnorm_pairs(svhip_handle* h, const float* E, int64_t N, int32_t D, const float* mu,
                        const float* sigma, const int32_t* ia, const int32_t* ib, int64_t P,
                        float* out, int32_t flags);

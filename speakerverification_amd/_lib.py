@@ -90,6 +90,7 @@ _SIGNATURES = {
     "svhip_score_pairs": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32]),
     "svhip_score_matrix": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_int32]),
     "svhip_score_topk": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
+    "svhip_score_topk_norm": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
     "svhip_asnorm_stats": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
     "svhip_asnorm_pairs": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, C.c_int32]),
     "svhip_asnorm_last_fallback": (C.c_int64, [_P]),

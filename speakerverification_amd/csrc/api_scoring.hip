@@ -42,9 +42,10 @@ void release_big_scratch(svhip_handle* h, bool staged_host) {
     };
     drop(svhip_handle::SCR_SLAB);
     drop(svhip_handle::SCR_TOPK);
+    drop(svhip_handle::SCR_COEF);
     if (staged_host)
         for (int s_ : {svhip_handle::SCR_IN0, svhip_handle::SCR_IN1, svhip_handle::SCR_IN2, svhip_handle::SCR_IN3, svhip_handle::SCR_IN4,
-                       svhip_handle::SCR_OUT0, svhip_handle::SCR_OUT1, svhip_handle::SCR_OUT2, svhip_handle::SCR_SPLIT}) drop(s_);
+                       svhip_handle::SCR_IN5, svhip_handle::SCR_OUT0, svhip_handle::SCR_OUT1, svhip_handle::SCR_OUT2, svhip_handle::SCR_SPLIT}) drop(s_);
 }
 struct TempBuf {      // device staging for host-pointer calls, in a scratch slot of the handle
     svhip_handle* h; int slot;
@@ -440,7 +441,10 @@ int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, co
 //          chunk run the shared-block form of the kernel, a last tile of at most 32 queries the form whose waves walk different gallery
 //          blocks; each launch cuts the gallery into enough slices to fill the chip (within 256 MiB of list scratch) and is followed by its merge
 //   slab   every other width: score_gemm writes slabs of query rows (at most 2 GiB, at least 128 rows, as asnorm_stats_slab), a row kernel selects
-static int topk_fused_part(svhip_handle* h, const float* dQ, int64_t rows, const float* dG, int64_t M, int D, int k, bool few, float* dS, int32_t* dI) {
+// The normalised call (svhip_score_topk_norm) takes the same routes with the same chunks, slices and slabs: `qc` / `gc` are its tables of
+// (a, b) pairs (score_topk_coef; qc already offset to the first row of dQ), both NULL for the plain call.
+static int topk_fused_part(svhip_handle* h, const float* dQ, int64_t rows, const float* dG, int64_t M, int D, int k, bool few, float* dS, int32_t* dI,
+                           const float2* qc, const float2* gc) {
     const int cap = score_topk_cap(k);
     const int64_t nb_all = (M + 31) / 32;
     const int64_t tiles = few ? 1 : (rows + 127) / 128;
@@ -462,15 +466,17 @@ static int topk_fused_part(svhip_handle* h, const float* dQ, int64_t rows, const
     if (int rc = scratch(h, svhip_handle::SCR_TOPK, list_bytes + (size_t)rows * p.nlists * 4, &s)) return rc;
     p.lists = reinterpret_cast<uint2*>(s);
     p.cnt = reinterpret_cast<int32_t*>((char*)s + list_bytes);
-    if (int rc = run(h, "score_topk", 2.0 * rows * M * D, [&]() { return launch_score_topk(p, D, few, (int)slices, h->stream); })) return rc;
+    p.qcoef = qc; p.gcoef = gc;
+    if (int rc = run(h, qc ? "score_topk_norm" : "score_topk", 2.0 * rows * M * D, [&]() { return launch_score_topk(p, D, few, (int)slices, h->stream); })) return rc;
     return run(h, "score_topk_merge", 0, [&]() { return launch_score_topk_merge(p.lists, p.cnt, rows, p.nlists, cap, k, dS, dI, h->stream); });
 }
 
-static int topk_slab(svhip_handle* h, const float* dQ, int64_t N, const float* dG, int64_t M, int D, int k, float* dS, int32_t* dI) {
+static int topk_slab(svhip_handle* h, const char* name, const float* dQ, int64_t N, const float* dG, int64_t M, int D, int k, float* dS, int32_t* dI,
+                     const float2* qc, const float2* gc) {
     const int64_t ldk = (M + 3) & ~(int64_t)3;                    // row stride of the slab (16-byte rows for the DMA GEMM)
     const int64_t max_m = (((int64_t)1 << 31) / (128 * 4)) & ~(int64_t)3;
     if (ldk > max_m)
-        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "score_topk: D = %d takes the slab route, whose 128-row slab holds at most M = %lld gallery rows (M = %lld)", D,
+        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "%s: D = %d takes the slab route, whose 128-row slab holds at most M = %lld gallery rows (M = %lld)", name, D,
                 (long long)max_m, (long long)M);
     const int64_t slab_rows = std::min<int64_t>(N, std::max<int64_t>(128, ((int64_t)1 << 31) / (ldk * 4)));
     void* gsplit = nullptr;
@@ -482,22 +488,27 @@ static int topk_slab(svhip_handle* h, const float* dQ, int64_t N, const float* d
     for (int64_t r0 = 0; r0 < N; r0 += slab_rows) {
         const int64_t rows = std::min(slab_rows, N - r0);
         rc = score_gemm(h, "score_topk_gemm", dQ + r0 * D, rows, dG, M, D, (float*)slab, ldk, route, gsplit);
-        if (!rc) rc = run(h, "score_topk_rows", 0, [&]() { return launch_score_topk_rows((const float*)slab, rows, M, ldk, k, dS + r0 * k, dI + r0 * k, h->stream); });
+        if (!rc)
+            rc = run(h, qc ? "score_topk_rows_norm" : "score_topk_rows", 0, [&]() {
+                return launch_score_topk_rows((const float*)slab, rows, M, ldk, k, dS + r0 * k, dI + r0 * k, h->stream, qc ? qc + r0 : nullptr, gc);
+            });
         if (rc) return rc;
     }
     return SVHIP_OK;
 }
 
-int svhip_score_topk(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, int32_t k, float* out_score,
-                     int32_t* out_index, int32_t flags) {
+// both entry points: `stats` = {q_mu, q_sigma, g_mu, g_sigma} for the normalised call, NULL for the plain one; `name` prefixes the messages
+static int score_topk_impl(svhip_handle* h, const char* name, const float* Q, int64_t N, const float* G, int64_t M, const float* const* stats,
+                           int32_t D, int32_t k, float* out_score, int32_t* out_index, int32_t flags) {
     if (!h) return SVHIP_ERR_INVALID;
-    if (k < 1 || k > SCORE_TOPK_MAX_K) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: k = %d is outside [1, %d]", (int)k, SCORE_TOPK_MAX_K);
-    if (M < 1 || M > (int64_t)INT32_MAX) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: M = %lld is outside [1, 2^31 - 1]", (long long)M);
-    if (k > M) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: k = %d exceeds the gallery's M = %lld rows", (int)k, (long long)M);
-    if (D < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: D = %d must be at least 1", (int)D);
-    if (N < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: N = %lld is negative", (long long)N);
+    if (k < 1 || k > SCORE_TOPK_MAX_K) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: k = %d is outside [1, %d]", name, (int)k, SCORE_TOPK_MAX_K);
+    if (M < 1 || M > (int64_t)INT32_MAX) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: M = %lld is outside [1, 2^31 - 1]", name, (long long)M);
+    if (k > M) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: k = %d exceeds the gallery's M = %lld rows", name, (int)k, (long long)M);
+    if (D < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: D = %d must be at least 1", name, (int)D);
+    if (N < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: N = %lld is negative", name, (long long)N);
     if (N == 0) return SVHIP_OK;
-    if (!Q || !G || !out_score || !out_index) SV_FAIL(h, SVHIP_ERR_INVALID, "score_topk: NULL pointer");
+    if (!Q || !G || !out_score || !out_index) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: NULL pointer", name);
+    if (stats && (!stats[0] || !stats[1] || !stats[2] || !stats[3])) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: NULL pointer", name);
     SV_HIP(h, hipSetDevice(h->cfg.device));
     const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
     TempBuf tQ{h, svhip_handle::SCR_IN0}, tG{h, svhip_handle::SCR_IN1}, tS{h, svhip_handle::SCR_OUT0}, tI{h, svhip_handle::SCR_OUT1};
@@ -508,6 +519,25 @@ int svhip_score_topk(svhip_handle* h, const float* Q, int64_t N, const float* G,
     if ((rc = tG.in(G, (size_t)M * D * 4, din, &dG))) return rc;
     if ((rc = tS.out(out_score, (size_t)N * k * 4, dout, &dS))) return rc;
     if ((rc = tI.out(out_index, (size_t)N * k * 4, dout, &dI))) return rc;
+    const float2 *qc = nullptr, *gc = nullptr;
+    if (stats) {
+        // the coefficient tables, once per call: [queries (N) | gallery (whole blocks of 32 rows), on a 16-byte boundary]
+        const int slot[4] = {svhip_handle::SCR_IN2, svhip_handle::SCR_IN3, svhip_handle::SCR_IN4, svhip_handle::SCR_IN5};
+        const void* d[4];
+        for (int i = 0; i < 4; ++i) {
+            TempBuf t{h, slot[i]};
+            if ((rc = t.in(stats[i], (size_t)(i < 2 ? N : M) * 4, din, &d[i]))) return rc;
+        }
+        const size_t q_bytes = ((size_t)N * 8 + 15) & ~(size_t)15;
+        void* c = nullptr;
+        if ((rc = scratch(h, svhip_handle::SCR_COEF, q_bytes + (size_t)score_topk_coef_rows(M) * 8, &c))) return rc;
+        float2* qcw = reinterpret_cast<float2*>(c);
+        float2* gcw = reinterpret_cast<float2*>((char*)c + q_bytes);
+        if ((rc = run(h, "score_topk_coef", 0, [&]() {
+                 return launch_score_topk_coef((const float*)d[0], (const float*)d[1], N, (const float*)d[2], (const float*)d[3], M, qcw, gcw, h->stream);
+             }))) return rc;
+        qc = qcw; gc = gcw;
+    }
     const bool aligned = ((reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dG)) & 15) == 0;
     if (score_topk_fused_supported(D) && aligned) {
         constexpr int64_t CHUNK = 16384;
@@ -516,24 +546,37 @@ int svhip_score_topk(svhip_handle* h, const float* Q, int64_t N, const float* G,
             const int64_t tail = rows % 128;
             const int64_t n_few = (tail >= 1 && tail <= 32) ? tail : 0, n_many = rows - n_few;
             const float* q = (const float*)dQ + r0 * D;
-            if (n_many) rc = topk_fused_part(h, q, n_many, (const float*)dG, M, D, k, false, (float*)dS + r0 * k, (int32_t*)dI + r0 * k);
+            const float2* qcr = qc ? qc + r0 : nullptr;
+            if (n_many) rc = topk_fused_part(h, q, n_many, (const float*)dG, M, D, k, false, (float*)dS + r0 * k, (int32_t*)dI + r0 * k, qcr, gc);
             if (!rc && n_few)
-                rc = topk_fused_part(h, q + n_many * D, n_few, (const float*)dG, M, D, k, true, (float*)dS + (r0 + n_many) * k, (int32_t*)dI + (r0 + n_many) * k);
+                rc = topk_fused_part(h, q + n_many * D, n_few, (const float*)dG, M, D, k, true, (float*)dS + (r0 + n_many) * k, (int32_t*)dI + (r0 + n_many) * k,
+                                     qc ? qcr + n_many : nullptr, gc);
         }
     } else {
-        rc = topk_slab(h, (const float*)dQ, N, (const float*)dG, M, D, k, (float*)dS, (int32_t*)dI);
+        rc = topk_slab(h, name, (const float*)dQ, N, (const float*)dG, M, D, k, (float*)dS, (int32_t*)dI, qc, gc);
     }
     if (!rc && !dout) {
         hipError_t e = hipMemcpyAsync(out_score, dS, (size_t)N * k * 4, hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(out_index, dI, (size_t)N * k * 4, hipMemcpyDeviceToHost, h->stream);
-        if (e != hipSuccess) { h->err = std::string("score_topk: copy of the results failed: ") + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
+        if (e != hipSuccess) { h->err = std::string(name) + ": copy of the results failed: " + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
     }
     if (rc || !(din && dout && (flags & SVHIP_ASYNC))) {
         const hipError_t e = hipStreamSynchronize(h->stream);
-        if (!rc && e != hipSuccess) { h->err = std::string("score_topk: ") + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
+        if (!rc && e != hipSuccess) { h->err = std::string(name) + ": " + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
         release_big_scratch(h, !din || !dout);
     }
     return rc;
+}
+
+int svhip_score_topk(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, int32_t k, float* out_score,
+                     int32_t* out_index, int32_t flags) {
+    return score_topk_impl(h, "score_topk", Q, N, G, M, nullptr, D, k, out_score, out_index, flags);
+}
+
+int svhip_score_topk_norm(svhip_handle* h, const float* Q, int64_t N, const float* q_mu, const float* q_sigma, const float* G, int64_t M,
+                          const float* g_mu, const float* g_sigma, int32_t D, int32_t k, float* out_score, int32_t* out_index, int32_t flags) {
+    const float* stats[4] = {q_mu, q_sigma, g_mu, g_sigma};
+    return score_topk_impl(h, "score_topk_norm", Q, N, G, M, stats, D, k, out_score, out_index, flags);
 }
 
 int64_t svhip_asnorm_last_fallback(const svhip_handle* h) { return h ? h->last_asnorm_flagged : -1; }

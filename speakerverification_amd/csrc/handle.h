@@ -167,7 +167,7 @@ struct svhip_handle {
     void* crop_pcm = nullptr; size_t crop_pcm_cap = 0;
     // scoring / metrics scratch: handle-owned slots, grown on demand (no hipMalloc / hipFree per call once warm)
     enum { SCR_IN0 = 0, SCR_IN1, SCR_IN2, SCR_IN3, SCR_IN4, SCR_OUT0, SCR_OUT1, SCR_OUT2, SCR_SLAB, SCR_SPLIT, SCR_CAND, SCR_CNT, SCR_MB,
-           SCR_FLAG, SCR_GATHER, SCR_WS, SCR_TOPK, SCR_COUNT };
+           SCR_FLAG, SCR_GATHER, SCR_WS, SCR_TOPK, SCR_IN5, SCR_COEF, SCR_COUNT };
     void* scr[SCR_COUNT] = {};
     size_t scr_cap[SCR_COUNT] = {};
     hipStream_t aux_stream = nullptr;         // second stream of the scoring entry points (candidate statistics under the next MFMA launch)

@@ -710,6 +710,9 @@ struct ScoreTopkParams {
     int nlists = 0;                 // lists per query: 2 per slice (8 where the waves of a workgroup walk different blocks: `few`)
     uint2* lists = nullptr;         // (N, nlists, cap)
     int32_t* cnt = nullptr;         // (N, nlists) entries each list holds (<= k when the kernel has ended)
+    // the normalised form (svhip_score_topk_norm): both tables or neither.  The lists then hold t = fmaf(s, aq + ag, -(bq + bg))
+    const float2* qcoef = nullptr;  // (N) pairs (a, b) of this launch's queries
+    const float2* gcoef = nullptr;  // (score_topk_coef_rows(M)) pairs of the gallery, 16-byte aligned
 };
 constexpr int SCORE_TOPK_MAX_K = 128;
 bool score_topk_fused_supported(int D);
@@ -719,7 +722,14 @@ hipError_t launch_score_topk(const ScoreTopkParams& p, int D, bool few, int slic
 hipError_t launch_score_topk_merge(const uint2* lists, const int32_t* cnt, int64_t rows, int nlists, int cap, int k, float* out_score,
                                    int32_t* out_index, hipStream_t stream);
 // the slab route: the k best of each row of S (rows x M, row stride ld), same order
-hipError_t launch_score_topk_rows(const float* S, int64_t rows, int64_t M, int64_t ld, int k, float* out_score, int32_t* out_index, hipStream_t stream);
+// (qcoef, gcoef: the normalised form — the pairs of the slab's rows and of the gallery; every read of a score goes through the fmaf)
+hipError_t launch_score_topk_rows(const float* S, int64_t rows, int64_t M, int64_t ld, int k, float* out_score, int32_t* out_index, hipStream_t stream,
+                                  const float2* qcoef = nullptr, const float2* gcoef = nullptr);
+// a = 0.5f / sigma, b = mu * a per query and per gallery row, interleaved; the gallery's table has score_topk_coef_rows(M) entries
+// (whole blocks of 32 rows, the last row repeated)
+int64_t score_topk_coef_rows(int64_t M);
+hipError_t launch_score_topk_coef(const float* q_mu, const float* q_sigma, int64_t N, const float* g_mu, const float* g_sigma, int64_t M,
+                                  float2* qcoef, float2* gcoef, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // Verification metrics (metrics.hip): one workspace of metrics_workspace_bytes(P) holds the sorted trial list

@@ -20,6 +20,8 @@
 //   score_topk_merge    one workgroup per query: the k largest composite keys of all its lists, in order (k rounds of a block-wide max
 //                       below the previous one).
 //   score_topk_rows     the slab route's row kernel: the same k rounds over one row of a score slab.
+//   score_topk_coef     svhip_score_topk_norm only: the (a, b) pairs of queries and gallery rows, once per call.  The NORM instances of
+//                       score_topk_kernel and score_topk_rows select on t = fmaf(s, aq + ag, -(bq + bg)) instead of s.
 #include "common.h"
 #include "kernels.h"
 #include "score_select.h"
@@ -90,7 +92,15 @@ __device__ __forceinline__ void compact_lists(unsigned long long need, uint2* lb
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 }
 
-template <int D, bool FEW>
+// NORM (svhip_score_topk_norm): the lists hold t = fmaf(s, aq + ag, -(bq + bg)) in place of s; (aq, bq) are two registers of the lane
+// (a lane holds one query), (ag, bg) come from the gallery's table of interleaved pairs, which score_topk_coef writes out to whole blocks
+// of 32 rows (the entries past M repeat row M - 1: the last block reads in bounds, and its rows past M are masked as before).  The 16
+// rows of a lane are four runs of four: rows 32 b + 8 g + 4 h + 0..3, 32 contiguous bytes per g.
+//   FEW   the pairs are loaded into registers with the A fragments of the block, ahead of its MFMAs
+//   MANY  256 bytes per block travel with the block's DMA image into a ring of four LDS slots (block b + 1 is written while block b - 1
+//         is still read, so two slots are not enough); process reads them from LDS, where the whole half wave reads one address
+// The NORM = false instances are the kernels of svhip_score_topk, instruction for instruction.
+template <int D, bool FEW, bool NORM>
 __global__ __launch_bounds__(256, 2) void score_topk_kernel(ScoreTopkParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int CH = D / 4;                       // 16-byte chunks per gallery row
@@ -106,6 +116,11 @@ __global__ __launch_bounds__(256, 2) void score_topk_kernel(ScoreTopkParams p) {
     const int64_t row = FEW ? (int64_t)blockIdx.x * 32 + j : (int64_t)blockIdx.x * 128 + wave * 32 + j;
     const bool valid = row < p.N;
     const float* __restrict__ qrow = p.Q + (valid ? row : p.N - 1) * D;
+    float aq = 0.0f, bq = 0.0f;
+    if (NORM) {
+        const float2 c = p.qcoef[valid ? row : p.N - 1];
+        aq = c.x; bq = c.y;
+    }
 
     // B operand: q[k], k = h * D/2 + s, for MFMA k-step s (both operands use the same k assignment)
     float eb[D / 2];
@@ -152,6 +167,23 @@ __global__ __launch_bounds__(256, 2) void score_topk_kernel(ScoreTopkParams p) {
             }
         }
     };
+    // NORM: the lane's 16 scores through the statement, one rounding per step (svhip.h): the sum of the two a, the sum of the two b, the
+    // fused multiply-add.  gc: the pairs of rows 8 g + 4 h + 0..3 of the block in gc[2 g], gc[2 g + 1]
+    // (normalise8: scores 8 half .. 8 half + 7 with gc[0 .. 3] = the pairs of g = 2 half, 2 half + 1)
+    auto normalise8 = [&](f32x16& t, const f32x16& a, const f32x4* gc, int half) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const f32x4 c = gc[r >> 1];
+            const float ag = (r & 1) ? c[2] : c[0], bg = (r & 1) ? c[3] : c[1];
+            t[8 * half + r] = __builtin_fmaf(a[8 * half + r], aq + ag, -(bq + bg));
+        }
+    };
+    auto normalised = [&](const f32x16& a, const f32x4* gc) {
+        f32x16 t;
+        normalise8(t, a, gc, 0);
+        normalise8(t, a, gc + 4, 1);
+        return t;
+    };
     auto mfma_step = [&](f32x16& acc, const f32x4& a4, int t) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u], eb[t * 4 + u], acc, 0, 0, 0);
@@ -166,12 +198,19 @@ __global__ __launch_bounds__(256, 2) void score_topk_kernel(ScoreTopkParams p) {
             f32x4 af[NG];
 #pragma unroll
             for (int t = 0; t < NG; ++t) af[t] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(arow) + t);
+            f32x4 gc[8];
+            if (NORM) {
+                const f32x4* __restrict__ src = reinterpret_cast<const f32x4*>(p.gcoef + r0 + 4 * h);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) { gc[2 * g] = src[4 * g]; gc[2 * g + 1] = src[4 * g + 1]; }
+            }
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
 #pragma unroll
             for (int t = 0; t < NG; ++t) mfma_step(acc, af[t], t);
-            process(acc, b);
+            if (NORM) process(normalised(acc, gc), b);
+            else process(acc, b);
         }
     } else {
         // per-lane source offsets of the NDMA chunks this lane moves per block (block-invariant: row within the block, swizzled chunk)
@@ -192,6 +231,21 @@ __global__ __launch_bounds__(256, 2) void score_topk_kernel(ScoreTopkParams p) {
                 const float* s = bb + min(srow[q], lim) * D + scol[q];
                 __builtin_amdgcn_global_load_lds((gbl_void*)s, (lds_void*)(smem + buf * BLK + (q * 256 + wave * 64) * 16), 16, 0, 0);
             }
+            if (NORM && wave == 0 && lane < 16)         // the block's 32 pairs: 16 lanes x 16 bytes, lane-linear like the image
+                __builtin_amdgcn_global_load_lds((gbl_void*)(p.gcoef + r0 + 2 * lane), (lds_void*)(smem + 2 * BLK + ((b - b_first) & 3) * 256), 16, 0, 0);
+        };
+        auto normalised_block = [&](const f32x16& a, int b) {      // with the pairs of block b from their LDS slot
+            const char* src = smem + 2 * BLK + ((b - b_first) & 3) * 256 + 32 * h;
+            f32x16 t;
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {                 // (two rounds of 16 registers: D = 256 has no 32 to spare here)
+                f32x4 gc[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) gc[u] = *reinterpret_cast<const f32x4*>(src + 128 * half + 64 * (u >> 1) + 16 * (u & 1));
+                normalise8(t, a, gc, half);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            return t;
         };
         auto rd = [&](int buf, int t) {
             return *reinterpret_cast<const f32x4*>(smem + buf * BLK + j * (D * 4) + (((h * NG + t) ^ (j & 15)) << 4));      // gallery row j of the block
@@ -224,11 +278,15 @@ __global__ __launch_bounds__(256, 2) void score_topk_kernel(ScoreTopkParams p) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // block b has landed (and the list stores of one block ago)
                 __syncthreads();                                       // ... for every wave; nobody still reads the other buffer
                 if (b + 1 < b_last) issue(b + 1, buf ^ 1);
-                if (b > b_first) process(accp, b - 1);                 // selection of the previous block
+                if (b > b_first) {                                     // selection of the previous block
+                    if (NORM) process(normalised_block(accp, b - 1), b - 1);
+                    else process(accp, b - 1);
+                }
                 __builtin_amdgcn_sched_barrier(0);
                 accp = mfma_block(buf);
             }
-            process(accp, b_last - 1);
+            if (NORM) process(normalised_block(accp, b_last - 1), b_last - 1);
+            else process(accp, b_last - 1);
         }
     }
     // what the merge reads: at most k entries per list
@@ -307,15 +365,35 @@ __global__ __launch_bounds__(256) void score_topk_merge_kernel(const uint2* __re
 // largest of those 256 maxima, T, is a lower bound of the row's k-th key (k <= min(M, 256) shares are not empty, and k keys are >= T).
 // Pass 2 (the row comes from L2): the keys >= T go to an LDS list — about 2 k of them on scores without structure — and the k rounds run
 // over that list in registers.  A row that fills the list (its large scores share a few threads' strides) takes the k rounds over the row.
+// NORM: every read of s[t] goes through the statement's fmaf with the row's (aq, bq) and the gallery's pair of column t, so all passes
+// see the identical value.
 constexpr int ROWS_CAND = 256 * MERGE_PER;
+template <bool NORM>
 __global__ __launch_bounds__(256) void score_topk_rows_kernel(const float* __restrict__ S, int64_t M, int64_t ld, int k, float* __restrict__ out_score,
-                                                              int32_t* __restrict__ out_index) {
+                                                              int32_t* __restrict__ out_index, const float2* __restrict__ qcoef,
+                                                              const float2* __restrict__ gcoef) {
     __shared__ unsigned long long sm[8];
     __shared__ unsigned long long cand[ROWS_CAND];
     __shared__ int ncand;
     const int64_t row = blockIdx.x;
     const int tid = threadIdx.x;
-    const float* __restrict__ s = S + row * ld;
+    const float* __restrict__ sraw = S + row * ld;
+    float aq = 0.0f, bq = 0.0f;
+    if (NORM) {
+        const float2 c = qcoef[row];
+        aq = c.x; bq = c.y;
+    }
+    struct Row {
+        const float* __restrict__ s;
+        const float2* __restrict__ g;
+        float aq, bq;
+        __device__ __forceinline__ float operator[](int64_t t) const {
+            if (!NORM) return s[t];
+            const float2 c = g[t];
+            return __builtin_fmaf(s[t], aq + c.x, -(bq + c.y));
+        }
+    };
+    const Row s{sraw, gcoef, aq, bq};
     unsigned long long mx = 0ull;
     for (int64_t t = tid; t < M; t += 256) {
         const unsigned long long x = composite(s[t], (uint32_t)t);
@@ -355,17 +433,50 @@ __global__ __launch_bounds__(256) void score_topk_rows_kernel(const float* __res
     }, sm, out_score + row * k, out_index + row * k);
 }
 
-template <int D, bool FEW>
+// the coefficients of the statement, one IEEE operation each: a = 0.5f / sigma, b = mu * a, as interleaved pairs per query and per
+// gallery row; the gallery's table runs to Mpad = whole blocks of 32 rows, the entries past M repeat row M - 1
+__global__ __launch_bounds__(256) void score_topk_coef_kernel(const float* __restrict__ q_mu, const float* __restrict__ q_sigma, int64_t N,
+                                                              const float* __restrict__ g_mu, const float* __restrict__ g_sigma, int64_t M,
+                                                              int64_t Mpad, float2* __restrict__ qcoef, float2* __restrict__ gcoef) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N + Mpad) return;
+    const bool isq = i < N;
+    const int64_t src = isq ? i : min(i - N, M - 1);
+    const float mu = isq ? q_mu[src] : g_mu[src], sigma = isq ? q_sigma[src] : g_sigma[src];
+    const float a = 0.5f / sigma;
+    const float b = mu * a;
+    (isq ? qcoef + i : gcoef + (i - N))[0] = make_float2(a, b);
+}
+
+template <int D, bool FEW, bool NORM>
 hipError_t launch_topk_d(const ScoreTopkParams& p, const dim3& grid, hipStream_t stream) {
     static DeviceOnce attr;
-    const int lds = FEW ? 0 : 2 * 32 * D * 4;
+    const int lds = FEW ? 0 : 2 * 32 * D * 4 + (NORM ? 4 * 256 : 0);
     if (!FEW)
-        if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(score_topk_kernel<D, FEW>), lds)) return e;
-    hipLaunchKernelGGL((score_topk_kernel<D, FEW>), grid, dim3(256), lds, stream, p);
+        if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(score_topk_kernel<D, FEW, NORM>), lds)) return e;
+    hipLaunchKernelGGL((score_topk_kernel<D, FEW, NORM>), grid, dim3(256), lds, stream, p);
     return hipGetLastError();
 }
 
+template <int D, bool NORM>
+hipError_t launch_topk_form(const ScoreTopkParams& p, bool few, const dim3& grid, hipStream_t stream) {
+    return few ? launch_topk_d<D, true, NORM>(p, grid, stream) : launch_topk_d<D, false, NORM>(p, grid, stream);
+}
+
 }  // namespace
+
+int64_t score_topk_coef_rows(int64_t M) { return (M + 31) / 32 * 32; }
+
+hipError_t launch_score_topk_coef(const float* q_mu, const float* q_sigma, int64_t N, const float* g_mu, const float* g_sigma, int64_t M,
+                                  float2* qcoef, float2* gcoef, hipStream_t stream) {
+    if (N <= 0) return hipSuccess;
+    if (!q_mu || !q_sigma || !g_mu || !g_sigma || !qcoef || !gcoef || M < 1 || M >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const int64_t Mpad = score_topk_coef_rows(M);
+    const int64_t blocks = (N + Mpad + 255) / 256;
+    if (blocks >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(score_topk_coef_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, q_mu, q_sigma, N, g_mu, g_sigma, M, Mpad, qcoef, gcoef);
+    return hipGetLastError();
+}
 
 bool score_topk_fused_supported(int D) { return D == 192 || D == 256; }
 
@@ -381,9 +492,11 @@ hipError_t launch_score_topk(const ScoreTopkParams& p, int D, bool few, int slic
     if (slices < 1 || slices > 65535 || p.per < 1 || (int64_t)slices * p.per * 32 < p.M) return hipErrorInvalidValue;      // every gallery block belongs to a slice
     if (p.nlists != slices * (few ? 8 : 2)) return hipErrorInvalidValue;
     if (few && p.N > 32) return hipErrorInvalidValue;
+    // the normalised form takes both tables (the gallery's is read in 16-byte pieces) or neither
+    if (!p.qcoef != !p.gcoef || (reinterpret_cast<uintptr_t>(p.gcoef) & 15)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(few ? 1 : (p.N + 127) / 128), (unsigned)slices);
-    if (D == 192) return few ? launch_topk_d<192, true>(p, grid, stream) : launch_topk_d<192, false>(p, grid, stream);
-    return few ? launch_topk_d<256, true>(p, grid, stream) : launch_topk_d<256, false>(p, grid, stream);
+    if (p.qcoef) return D == 192 ? launch_topk_form<192, true>(p, few, grid, stream) : launch_topk_form<256, true>(p, few, grid, stream);
+    return D == 192 ? launch_topk_form<192, false>(p, few, grid, stream) : launch_topk_form<256, false>(p, few, grid, stream);
 }
 
 hipError_t launch_score_topk_merge(const uint2* lists, const int32_t* cnt, int64_t rows, int nlists, int cap, int k, float* out_score,
@@ -396,10 +509,15 @@ hipError_t launch_score_topk_merge(const uint2* lists, const int32_t* cnt, int64
     return hipGetLastError();
 }
 
-hipError_t launch_score_topk_rows(const float* S, int64_t rows, int64_t M, int64_t ld, int k, float* out_score, int32_t* out_index, hipStream_t stream) {
+hipError_t launch_score_topk_rows(const float* S, int64_t rows, int64_t M, int64_t ld, int k, float* out_score, int32_t* out_index, hipStream_t stream,
+                                  const float2* qcoef, const float2* gcoef) {
     if (rows <= 0) return hipSuccess;
     if (!S || !out_score || !out_index || k < 1 || k > M || M >= ((int64_t)1 << 31) || ld < M || rows >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(score_topk_rows_kernel, dim3((unsigned)rows), dim3(256), 0, stream, S, M, ld, k, out_score, out_index);
+    if (!qcoef != !gcoef) return hipErrorInvalidValue;
+    if (qcoef)
+        hipLaunchKernelGGL(score_topk_rows_kernel<true>, dim3((unsigned)rows), dim3(256), 0, stream, S, M, ld, k, out_score, out_index, qcoef, gcoef);
+    else
+        hipLaunchKernelGGL(score_topk_rows_kernel<false>, dim3((unsigned)rows), dim3(256), 0, stream, S, M, ld, k, out_score, out_index, qcoef, gcoef);
     return hipGetLastError();
 }
 

@@ -534,6 +534,42 @@ class Engine:
         _count([q, g], [s, i])
         return scores, index
 
+    def score_topk_norm(self, Q, q_stats, G, g_stats, k, out=None):
+        """Open-set 1:N identification (``svhip_score_topk_norm``): ``score_topk`` over adaptive-S-normalised scores.  ``q_stats`` /
+        ``g_stats``: the ``(mu, sigma)`` pairs ``asnorm_stats`` returns for Q and for G, in the inputs' memory space.  The score of
+        query n against gallery row m is ``t = fmaf(s, aq + ag, -(bq + bg))`` with ``a = 0.5 / sigma``, ``b = mu * a`` in float32 —
+        ``asnorm_pairs``' ``0.5*((s-mu_q)/sd_q + (s-mu_g)/sd_g)`` — and the k best rows are selected ON t (every gallery row has its own
+        statistics, so the order differs from the cosine order).  Returns ``(t (N, k) float32, index (N, k) int32)``, best first,
+        in ``score_topk``'s order; ``out`` as there."""
+        N, D = Q.shape
+        M = G.shape[0]
+        if G.shape[1] != D:
+            raise ValueError(f"queries are {D} wide, the gallery {G.shape[1]}")
+        if q_stats is None or g_stats is None or len(q_stats) != 2 or len(g_stats) != 2:
+            raise ValueError("q_stats and g_stats must be (mu, sigma) pairs")
+        for what, st, n in (("q_stats", q_stats, N), ("g_stats", g_stats, M)):
+            for name, x in zip(("mu", "sigma"), st):
+                if x is None or tuple(x.shape) != (n,):
+                    raise ValueError(f"{what}: {name} must hold {n} values, not {None if x is None else tuple(x.shape)}")
+        k = int(k)
+        if out is None:
+            shape = (N, max(k, 0))
+            if _is_torch(Q) and Q.is_cuda:
+                out = (torch.empty(shape, dtype=torch.float32, device=Q.device), torch.empty(shape, dtype=torch.int32, device=Q.device))
+            else:
+                out = (np.empty(shape, np.float32), np.empty(shape, np.int32))
+        scores, index = out
+        q, g = _Buf(Q, np.float32), _Buf(G, np.float32)
+        st = [_Buf(x, np.float32) for x in (*q_stats, *g_stats)]
+        s, i = _Buf(scores, np.float32, writable=True), _Buf(index, np.int32, writable=True)
+        if s.nbytes != N * max(k, 0) * 4 or i.nbytes != s.nbytes:
+            raise ValueError(f"out must be a ({N}, {k}) float32 and a ({N}, {k}) int32 array")
+        dev = self._same_space(q, g, *st, s, i)
+        self._ck(self.lib.svhip_score_topk_norm(self.h, q.ptr, N, st[0].ptr, st[1].ptr, g.ptr, M, st[2].ptr, st[3].ptr, D, k, s.ptr, i.ptr,
+                                                (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
+        _count([q, g, *st], [s, i])
+        return scores, index
+
     # ---- verification metrics (host arrays in / out; the trial list is small next to the embeddings) --------------------
     def _scores_labels(self, scores, labels):
         if _is_torch(scores):

@@ -530,7 +530,8 @@ class ModelHandling:
             raise ValueError(f"{len(classes)} class names for {g.shape[0]} enrolled classes")
         return np.ascontiguousarray(g), classes
 
-    def identify(self, source, embeds, classes=None, top=1, num_eval=10):
+    def identify(self, source, embeds, classes=None, top=1, num_eval=10, scoring_mode="cosine", cohorts=None, cohorts_path=None,
+                 cohort_top=200, thresh_score=None):
         """Whose voice is this?  The ``top`` best enrolled classes of every file of ``source`` (what ``_embed_files`` takes: a list of
         paths / arrays, or one of them) against a gallery: the directory ``prepare('embed')`` wrote (``embeds.pt``, ``classes.npy``),
         a ``(num_eval, nOut, n_class)`` tensor in that layout, or an ``(n_class, nOut)`` array.
@@ -542,6 +543,17 @@ class ModelHandling:
         path does.)  Files are embedded in batches (whole files through the ragged path with ``num_eval=0``) and searched in ONE
         ``score_topk`` call.
 
+        ``scoring_mode="norm"`` (open-set identification): queries and gallery are prepared as above, the adaptive-S-norm statistics of
+        both are taken against a cohort — ``cohorts``, a ``(K, nOut)`` array, or ``cohorts_path``, the ``.npy`` file
+        ``prepare('cohorts')`` wrote, as ``evaluateFromList`` takes it — over each row's ``cohort_top`` largest cohort scores, and the
+        score of a file against a class is ``0.5 * ((s - mu_q) / sd_q + (s - mu_g) / sd_g)`` with s their cosine.  The ``top`` classes
+        are the best by THAT score (every class has its own statistics: the order differs from the cosine order), found in one
+        ``score_topk_norm`` call.  A missing cohort is refused.
+
+        ``thresh_score`` (either mode): an entry whose score is below it is not an identification — its index becomes -1 and its name
+        ``None``; the scores are returned as computed, and the entries stay in place (best first).  What the reference's ``predict``
+        does with ``args.test_threshold``; a threshold on ``"norm"`` scores carries across speakers and channels, one on cosines does not.
+
         Returns ``(scores (n_files, top) float32, index (n_files, top) int32)``, best first, and as a third item the class names
         (a list of ``top`` names per file) when ``classes`` is given ({index: name} or a sequence) or the directory holds ``classes.npy``."""
         self.__model__.eval()
@@ -552,6 +564,16 @@ class ModelHandling:
         top = int(top)
         if top < 1 or top > gal.shape[0]:
             raise ValueError(f"top = {top} must lie in [1, n_class = {gal.shape[0]}]")
+        if scoring_mode not in ("cosine", "norm"):
+            raise ValueError(f"unknown scoring_mode {scoring_mode}")
+        if scoring_mode == "norm":
+            if cohorts is None and cohorts_path is not None:
+                cohorts = np.load(str(cohorts_path))
+            if cohorts is None:
+                raise ValueError("scoring_mode 'norm' needs a cohort: cohorts (an array) or cohorts_path (an .npy file)")
+            cohorts = np.ascontiguousarray(_host(cohorts), dtype=np.float32)
+            if cohorts.ndim != 2 or cohorts.shape[1] != gal.shape[1]:
+                raise ValueError(f"the cohort must be (K, {gal.shape[1]}), not {cohorts.shape}")
         eng = scoring.scoring_engine(self.gpu)
         feats = np.asarray(_host(self._embed_files(files, num_eval)), dtype=np.float32)       # (n_files, n_crops, nOut)
         if feats.shape[-1] != gal.shape[1]:
@@ -562,10 +584,15 @@ class ModelHandling:
         q = np.ascontiguousarray(flat.reshape(feats.shape).mean(axis=1))
         eng.l2norm_(q)
         eng.l2norm_(gal)
-        scores, index = scoring.score_topk(q, gal, top, device=self.gpu)
+        if scoring_mode == "norm":
+            scores, index, _ = scoring.score_topk_norm(q, gal, top, cohorts, top=int(cohort_top), device=self.gpu)
+        else:
+            scores, index = scoring.score_topk(q, gal, top, device=self.gpu)
+        if thresh_score is not None:
+            index = np.where(np.asarray(_host(scores)) < thresh_score, np.int32(-1), np.asarray(_host(index))).astype(np.int32)
         if classes is None:
             return scores, index
-        return scores, index, [[classes[int(i)] for i in row] for row in np.asarray(_host(index))]
+        return scores, index, [[classes[int(i)] if i >= 0 else None for i in row] for row in np.asarray(_host(index))]
 
     # ---- checkpoints ------------------------------------------------------------------------------------------------------
     def saveParameters(self, path):

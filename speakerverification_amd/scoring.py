@@ -1,7 +1,7 @@
 """Scoring counterparts of the reference's ``src/utils.py:126-169``.
 
 ``similarity_measure(method, ref, com, **kw)`` keeps the per-trial signature for compatibility; the
-batched entry points (``score_pairs``, ``score_matrix``, ``score_topk``, ``asnorm_stats``, ``asnorm_pairs``,
+batched entry points (``score_pairs``, ``score_matrix``, ``score_topk``, ``score_topk_norm``, ``asnorm_stats``, ``asnorm_pairs``,
 ``score_trials``) are what ``ModelHandling.evaluateFromList`` uses: one kernel launch per trial LIST
 instead of three host<->device crossings per trial.
 """
@@ -56,6 +56,19 @@ def score_matrix(A, B, device=0):
 def score_topk(Q, G, k, device=0):
     """per row of Q the k best rows of the gallery G by inner product -> (scores (N, k), int32 index (N, k)), best first"""
     return scoring_engine(device).score_topk(Q, G, k)
+
+
+def score_topk_norm(Q, G, k, cohort, top=200, g_stats=None, device=0):
+    """``score_topk`` over adaptive-S-normalised scores (open-set identification: the best score can be held against one threshold).
+    The cohort statistics of Q, and of G unless ``g_stats = (mu, sigma)`` is given, come from ``asnorm_stats(., cohort, top)``;
+    the k best gallery rows per query are selected on the normalised score.  All arrays in one memory space.
+    -> (scores (N, k), int32 index (N, k), g_stats): keep ``g_stats`` with the gallery to skip its statistics next time."""
+    eng = scoring_engine(device)
+    if g_stats is None:
+        g_stats = eng.asnorm_stats(G, cohort, top)
+    q_stats = eng.asnorm_stats(Q, cohort, top)
+    scores, index = eng.score_topk_norm(Q, q_stats, G, g_stats, k)
+    return scores, index, tuple(g_stats)
 
 
 def asnorm_stats(E, cohort, top=200, device=0):
