@@ -366,21 +366,38 @@ int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, con
  * (src/model.py:415-448,526-553) and src/utils.py:126-169.
  *   l2norm       : F.normalize(p=2, dim=1) in place (src/model.py:421-423), eps 1e-12.
  *   score_pairs  : out[p] = | cos(E[ia[p]], E[ib[p]]) |, per-norm clamp 1e-5 (utils.py:163-164,
- *                  one crop per row).
+ *                  one crop per row).  Any D and any 4-byte aligned E: the pair kernels (asnorm_pairs too) read 16 bytes at a time only
+ *                  where D % 4 == 0 and E sits on a 16-byte boundary (the kernel looks at its base address), element by element otherwise.
  *   score_matrix : out (Na, Nb) = A @ B^T (np.inner, utils.py:150).  On every handle the product runs as three fp16 MFMAs on IEEE-half
  *                  hi | lo planes of the operands (fp32-grade: ~1e-7 of |a||b| from the float64 product); both operands are first scaled
  *                  by exact powers of two on the device (a row of A by its own max |x|, B by its global max |x|), so for D in {192, 256}
  *                  (the row-streaming kernel; 16-byte aligned operands) ANY finite magnitude is served, and an inf / NaN element stays in
- *                  its own row or column (non-finite elements are left out of the max |x| searches).  Other widths run a tiled split GEMM
- *                  without the scaling: |x| <= 65504 there (beyond it the scores come out inf / NaN).  Option score_f32mfma keeps the
- *                  exact fp32 MFMA (any magnitude, any width).
+ *                  its own row or column (non-finite elements are left out of the max |x| searches).  Every other multiple of 32, and
+ *                  D in {192, 256} with an operand that is not 16-byte aligned, takes the tiled route, WITHOUT the scaling: B is split
+ *                  into hi | lo half words (profile label "split_words"), and the GEMM runs the split form where both operands and the
+ *                  output are 16-byte aligned and the output rows are too (Nb % 4 == 0; the slabs of asnorm_stats and score_topk
+ *                  always are), the exact fp32 MFMA on the unsplit operands otherwise (the words are then not read).  That second form
+ *                  reads 16 bytes at a time from rows that are only 4-byte aligned: it relies on the unaligned global access of the
+ *                  hardware, which needs dword alignment only.  The served range of the route is that of its split form: rows of
+ *                  both operands with an L2 norm in [1, 30000] (L2-normalised embeddings and their sums over crops or
+ *                  enrolments; every |x| <= 65504), where a score lies within 1e-6 of |a||b| from the float64 product.  Below it the lo
+ *                  half of a component goes subnormal and the error grows as 1 / norm: 8e-7 of |a||b| at a norm of 0.1 against a row inside
+ *                  the range, 1.05e-6 with both at 0.1, 1e-5 at 0.01, 1e-4 at 1e-3 (measured on the MI355X, D = 64 .. 512); beyond
+ *                  |x| = 65504 the scores come out inf / NaN.  An inf / NaN element stays in its own row or column there too.  Option
+ *                  score_f32mfma keeps the exact fp32 MFMA on every width and at any magnitude (5.5e-7 of |a||b|, row norms 1e-6 .. 3e5)
+ *                  and is the way to score rows outside that range at those widths.  D % 32 != 0 is refused with SVHIP_ERR_UNSUPPORTED
+ *                  before anything is copied or launched.
  *   asnorm_stats : per row of E: S = cohort @ e (utils.py:142), top-`top` largest, population
  *                  mean / std (utils.py:143-146) -> mu[N], sigma[N].  For D in {192, 256}, top <= 256 and K >= 4 top the cohort
  *                  scores never reach memory (fused selection in the half-plane MFMA kernel, csrc/asnorm_fused.hip: the same three-MFMA
  *                  products and the same power-of-two operand scaling as score_matrix; option asnorm_f32mfma: exact fp32 MFMA); otherwise, and for
  *                  the embeddings that kernel cannot decide even with a threshold re-derived from its own counts (up to three more passes over those
  *                  embeddings only: svhip_asnorm_last_refit()), they exist only as <= 2 GiB slabs.  svhip_asnorm_last_fallback():
- *                  how many embeddings of the last call took the slab path after the fused kernel (-1: the whole call did).
+ *                  how many embeddings of the last call took the slab path after the fused kernel (-1: the whole call did).  The slab
+ *                  path serves every K and every top: its cohort GEMM is score_matrix's (its routes, its magnitude contract, D % 32 != 0
+ *                  refused with SVHIP_ERR_UNSUPPORTED before anything is launched; an operand that is not 16-byte aligned sends the whole
+ *                  call here), and the selection runs with the row in registers (K <= 6144), in LDS (K <= 37 888) or read from the slab
+ *                  (longer cohorts); profile labels "asnorm_cohort_gemm", then "asnorm_topk_reg8" | "_reg24" | "_lds" | "_global".
  *   asnorm_pairs : out[p] = 0.5*((s-mu[a])/sd[a] + (s-mu[b])/sd[b]), s = E[a].E[b] (utils.py:148-160).
  *   score_topk   : 1:N identification (what the `predict` branch of the reference's driver asks, src/inference.py:254-327): per row of Q
  *                  the k largest entries of Q @ G^T and the gallery rows they belong to, best first, without the N x M matrix.  Order:
@@ -391,8 +408,10 @@ int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, con
  *                  of L2-normalised rows lies within 1e-6 of the float64 inner product of the row it names.  D in {192, 256} with
  *                  16-byte aligned operands: the fused kernel (csrc/score_topk.hip, exact fp32 MFMA, any finite magnitude; profile
  *                  labels "score_topk", "score_topk_merge") - no score reaches memory.  Every other width: slabs of query rows through
- *                  score_matrix's GEMM (its magnitude contract; at most 2 GiB, at least 128 rows: M <= 4 194 304, beyond it
- *                  SVHIP_ERR_UNSUPPORTED) and a row kernel ("score_topk_gemm", "score_topk_rows").
+ *                  score_matrix's GEMM (its magnitude contract: the tiled route's served range of row norms, option score_f32mfma
+ *                  outside it; at most 2 GiB, at least 128 rows: M <= 4 194 304, beyond it SVHIP_ERR_UNSUPPORTED; D % 32 != 0 is
+ *                  SVHIP_ERR_UNSUPPORTED before anything is launched) and a row kernel ("score_topk_gemm", "score_topk_rows").  An
+ *                  operand that is not 16-byte aligned takes this route at D = 192 / 256 as well.
  *   score_topk_norm : open-set 1:N identification: score_topk over adaptive-S-normalised scores, so that the best score can be compared
  *                  with one threshold across speakers and channels.  Inputs: Q (N, D) with q_mu[N], q_sigma[N], G (M, D) with g_mu[M],
  *                  g_sigma[M]; every statistic is fp32, as svhip_asnorm_stats writes them.  The coefficients are computed in fp32, one

@@ -217,6 +217,7 @@ static int split_b(svhip_handle* h, ScoreRoute route, const float* dB, int64_t N
 
 int svhip_score_matrix(svhip_handle* h, const float* A, int64_t Na, const float* B, int64_t Nb, int32_t D, float* out, int32_t flags) {
     if (!h || !A || !B || !out || Na <= 0 || Nb <= 0 || D <= 0) return SVHIP_ERR_INVALID;
+    if (D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "score_matrix: embedding dim %d must be a multiple of 32", (int)D);      // before any copy or launch
     SV_HIP(h, hipSetDevice(h->cfg.device));
     const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
     TempBuf tA{h, svhip_handle::SCR_IN0}, tB{h, svhip_handle::SCR_IN1}, tO{h, svhip_handle::SCR_OUT0};
@@ -250,7 +251,12 @@ static int asnorm_stats_slab(svhip_handle* h, const float* dE, int64_t N, int D,
     for (int64_t r0 = 0; r0 < N; r0 += slab_rows) {
         const int64_t rows = std::min(slab_rows, N - r0);
         rc = score_gemm(h, "asnorm_cohort_gemm", dE + r0 * D, rows, dC, K, D, (float*)slab, ldk, route, csplit);
-        if (!rc) rc = run(h, "asnorm_topk", 0, [&]() { return launch_topk_stats((const float*)slab, rows, K, (int)ldk, top, dM + r0, dS + r0, h->stream); });
+        if (!rc) {
+            // the profile label names the form of the selection the launcher takes for this shape
+            static const char* const labels[4] = {"asnorm_topk_reg8", "asnorm_topk_reg24", "asnorm_topk_lds", "asnorm_topk_global"};
+            rc = run(h, labels[topk_stats_form((const float*)slab, K, (int)ldk)], 0,
+                     [&]() { return launch_topk_stats((const float*)slab, rows, K, (int)ldk, top, dM + r0, dS + r0, h->stream); });
+        }
         if (rc) return rc;
     }
     return SVHIP_OK;
@@ -263,6 +269,7 @@ int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, co
     if (top > K) top = K;
     if (top <= 0) SV_FAIL(h, SVHIP_ERR_INVALID, "top must select at least one cohort score");
     if (N >= ((int64_t)1 << 31)) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "at most 2^31 - 1 embeddings per call");
+    if (D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "asnorm_stats: embedding dim %d must be a multiple of 32", (int)D);      // before any copy or launch
     SV_HIP(h, hipSetDevice(h->cfg.device));
     const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
     TempBuf tE{h, svhip_handle::SCR_IN0}, tC{h, svhip_handle::SCR_IN1}, tM{h, svhip_handle::SCR_OUT0}, tS{h, svhip_handle::SCR_OUT1};
@@ -509,6 +516,7 @@ static int score_topk_impl(svhip_handle* h, const char* name, const float* Q, in
     if (N == 0) return SVHIP_OK;
     if (!Q || !G || !out_score || !out_index) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: NULL pointer", name);
     if (stats && (!stats[0] || !stats[1] || !stats[2] || !stats[3])) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: NULL pointer", name);
+    if (D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "%s: embedding dim %d must be a multiple of 32", name, (int)D);      // before any copy or launch
     SV_HIP(h, hipSetDevice(h->cfg.device));
     const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
     TempBuf tQ{h, svhip_handle::SCR_IN0}, tG{h, svhip_handle::SCR_IN1}, tS{h, svhip_handle::SCR_OUT0}, tI{h, svhip_handle::SCR_OUT1};

@@ -637,7 +637,12 @@ hipError_t launch_asnorm_pairs(const float* E, int D, const float* mu, const flo
 hipError_t launch_trial_crops(int mode, float pexp, const float* F, int n_crops, int D, const int32_t* ia, const int32_t* ib, int64_t P, float* out,
                               hipStream_t stream);
 hipError_t launch_mean_crops(const float* F, int64_t n_files, int n_crops, int D, float* out, hipStream_t stream);
-// S (rows x K, row stride ld) fp32 cohort scores -> mean / population std of the `top` largest per row
+// S (rows x K, row stride ld) fp32 cohort scores -> mean / population std of the `top` largest per row.  Every K is served, by one of
+// four forms of the same selection: the row in registers (K <= 2048 / 6144, 16-byte rows), in LDS (Kp <= 37 888, rows_per_wg rows per
+// workgroup) or read from the slab itself on every pass (longer rows).  topk_stats_form is the launcher's own choice for a shape, so a
+// caller can name it beforehand (rows_per_wg: the rows a workgroup of the LDS form holds, 4 for the others).
+enum TopkStatsForm { TOPK_STATS_REG8 = 0, TOPK_STATS_REG24 = 1, TOPK_STATS_LDS = 2, TOPK_STATS_GLOBAL = 3 };
+TopkStatsForm topk_stats_form(const float* S, int K, int ld, int* rows_per_wg = nullptr);
 hipError_t launch_topk_stats(const float* S, int64_t rows, int K, int ld, int top, float* mu, float* sigma, hipStream_t stream);
 
 // Fused AS-norm cohort statistics (asnorm_fused.hip): scores stay in the MFMA accumulators; per embedding two candidate lists of

@@ -4,7 +4,8 @@
 //   asnorm_pairs  : 0.5*((s-mu_a)/sd_a + (s-mu_b)/sd_b), s = E[a].E[b]  (src/utils.py:148-160)
 //   topk_stats    : per row of a (rows x K) cohort-score slab: mean / population std of the `top`
 //                   largest values                                       (src/utils.py:142-146)
-// Pair kernels use 16 lanes per pair (4 pairs per wavefront): each lane loads float4s of both rows
+// Pair kernels use 16 lanes per pair (4 pairs per wavefront): each lane loads float4s of both rows (D % 4 == 0 and a 16-byte
+// aligned E; single floats otherwise)
 // (whole-row gathers), partial dot products are reduced with 4 xor-shuffles.
 #include "common.h"
 #include "kernels.h"
@@ -44,7 +45,8 @@ __global__ __launch_bounds__(256) void pair_kernel(const float* __restrict__ E, 
     const float* __restrict__ ea = E + a * D;
     const float* __restrict__ eb = E + b * D;
     float dab = 0.f, daa = 0.f, dbb = 0.f;
-    if ((D & 3) == 0) {
+    // 16-byte loads need 16-byte rows: D % 4 == 0 AND a 16-byte aligned E (a view one float into a buffer is a legal input)
+    if ((D & 3) == 0 && (reinterpret_cast<uintptr_t>(E) & 15) == 0) {
         for (int k = sub * 4; k < D; k += 64) {
             const f32x4 x = *reinterpret_cast<const f32x4*>(ea + k);
             const f32x4 y = *reinterpret_cast<const f32x4*>(eb + k);
@@ -236,27 +238,47 @@ __global__ __launch_bounds__(256) void topk_stats_reg_kernel(const float* __rest
 // two moments keeps <= 512 candidates (expected ~2*top), which are compacted with wave ballots and
 // selected exactly in registers; tau is re-aimed at most 3 times.  Anything else (small K, unlucky
 // distributions) takes the exact 32-pass search over the whole row.  Both paths give the same answer.
+// IN_LDS = false: a row too long for the LDS (Kp > 37 888) stays in the slab and every pass reads it from there (the slab row is
+// at most a few hundred KiB: the passes after the first hit the L2); only the candidates take LDS.  Same moments, threshold,
+// ballots and search.
+template <bool IN_LDS>
 __global__ __launch_bounds__(256) void topk_stats_kernel(const float* __restrict__ S, int64_t rows, int K, int ld, int Kp, int top,
                                                          int rows_per_wg, float* __restrict__ mu, float* __restrict__ sigma) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t* keys = reinterpret_cast<uint32_t*>(smem) + (size_t)wave * (Kp + TOPK_CAP);
-    uint32_t* cand = keys + Kp;
+    uint32_t* keys = reinterpret_cast<uint32_t*>(smem) + (size_t)wave * ((IN_LDS ? Kp : 0) + TOPK_CAP);
+    uint32_t* cand = keys + (IN_LDS ? Kp : 0);
     const int64_t row = (int64_t)blockIdx.x * rows_per_wg + wave;
     const bool active = (wave < rows_per_wg) && (row < rows);
+    const float* __restrict__ s = S + (active ? row : 0) * ld;
     float s1 = 0.0f, s2 = 0.0f;
     if (active) {
-        const float* __restrict__ s = S + row * ld;
         for (int k = lane; k < Kp; k += 64) {
             const float v = (k < K) ? s[k] : 0.0f;
-            keys[k] = (k < K) ? fkey(v) : 0u;                                       // pad = smallest key
+            if (IN_LDS) keys[k] = (k < K) ? fkey(v) : 0u;                           // pad = smallest key
             if (k < K) { s1 += v; s2 = fmaf(v, v, s2); }
         }
     }
     __syncthreads();
     if (!active) return;
-    const u32x4* k4 = reinterpret_cast<const u32x4*>(keys);
     const int n4 = Kp >> 2;
+    // four keys of the row: from LDS, or made from the slab (16-byte loads where the rows are 16-byte aligned: a ragged tail reads row
+    // padding, ld >= Kp then; element loads otherwise)
+    const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(S) & 15) == 0;
+    auto key4 = [&](int i) -> u32x4 {
+        if (IN_LDS) return reinterpret_cast<const u32x4*>(keys)[i];
+        const int k0 = i * 4;
+        u32x4 r;
+        if (vec) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(s + k0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = (k0 + j < K) ? fkey(v[j]) : 0u;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = (k0 + j < K) ? fkey(s[k0 + j]) : 0u;
+        }
+        return r;
+    };
     float mean_out, sd_out;
     bool done = false;
     if (top <= 256 && K >= 4 * top) {
@@ -272,7 +294,7 @@ __global__ __launch_bounds__(256) void topk_stats_kernel(const float* __restrict
             int base = 0;
             for (int i = lane; i < n4 + 63 - ((n4 + 63) % 64) ; i += 64) {       // every lane runs the same trip count (ballots)
                 const bool in = i < n4;
-                const u32x4 v = in ? k4[i] : u32x4{0u, 0u, 0u, 0u};
+                const u32x4 v = in ? key4(i) : u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const bool pred = v[j] > tkey;
@@ -299,7 +321,7 @@ __global__ __launch_bounds__(256) void topk_stats_kernel(const float* __restrict
             const uint32_t c = prefix | (1u << bit);
             int cnt = 0;
             for (int i = lane; i < n4; i += 64) {
-                const u32x4 v = k4[i];
+                const u32x4 v = key4(i);
                 cnt += (v[0] >= c) + (v[1] >= c) + (v[2] >= c) + (v[3] >= c);
             }
             if (wave_isum(cnt) >= top) prefix = c;
@@ -308,7 +330,7 @@ __global__ __launch_bounds__(256) void topk_stats_kernel(const float* __restrict
         float sum = 0.0f;
         int cgt = 0;
         for (int i = lane; i < n4; i += 64) {
-            const u32x4 v = k4[i];
+            const u32x4 v = key4(i);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (v[j] > prefix) { sum += fkey_inv(v[j]); ++cgt; }
@@ -319,7 +341,7 @@ __global__ __launch_bounds__(256) void topk_stats_kernel(const float* __restrict
         const float mean = (sum + nt * vth) / (float)top;
         float sq = 0.0f;
         for (int i = lane; i < n4; i += 64) {
-            const u32x4 v = k4[i];
+            const u32x4 v = key4(i);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (v[j] > prefix) { const float d = fkey_inv(v[j]) - mean; sq = fmaf(d, d, sq); }
@@ -373,24 +395,41 @@ hipError_t launch_mean_crops(const float* F, int64_t n_files, int n_crops, int D
     return hipGetLastError();
 }
 
+// The form a shape takes.  Kp + TOPK_CAP words per row of the LDS form, 150 KiB of rows per workgroup: 4 rows up to Kp = 9088, 3 to
+// 12 288, 2 to 18 688, 1 to 37 888; a longer row is read from the slab.
+TopkStatsForm topk_stats_form(const float* S, int K, int ld, int* rows_per_wg) {
+    if (rows_per_wg) *rows_per_wg = 4;
+    if (ld % 4 == 0 && (reinterpret_cast<uintptr_t>(S) & 15) == 0 && K <= 256 * 24) return K <= 256 * 8 ? TOPK_STATS_REG8 : TOPK_STATS_REG24;
+    const int Kp = (K + 3) & ~3;
+    const size_t row_bytes = (size_t)(Kp + TOPK_CAP) * sizeof(uint32_t);
+    const int rpw = (int)((150 * 1024) / row_bytes);
+    if (rpw < 1) return TOPK_STATS_GLOBAL;
+    if (rows_per_wg) *rows_per_wg = rpw > 4 ? 4 : rpw;
+    return TOPK_STATS_LDS;
+}
+
 hipError_t launch_topk_stats(const float* S, int64_t rows, int K, int ld, int top, float* mu, float* sigma, hipStream_t stream) {
     if (rows <= 0) return hipSuccess;
     if (top <= 0 || top > K || ld < K) return hipErrorInvalidValue;
-    if (ld % 4 == 0 && (reinterpret_cast<uintptr_t>(S) & 15) == 0 && K <= 256 * 24) {      // register-resident rows
+    int rpw = 4;
+    const TopkStatsForm form = topk_stats_form(S, K, ld, &rpw);
+    if (form == TOPK_STATS_REG8 || form == TOPK_STATS_REG24) {                              // register-resident rows
         const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-        if (K <= 256 * 8) hipLaunchKernelGGL(topk_stats_reg_kernel<8>, grid, block, 0, stream, S, rows, K, ld, top, mu, sigma);
+        if (form == TOPK_STATS_REG8) hipLaunchKernelGGL(topk_stats_reg_kernel<8>, grid, block, 0, stream, S, rows, K, ld, top, mu, sigma);
         else hipLaunchKernelGGL(topk_stats_reg_kernel<24>, grid, block, 0, stream, S, rows, K, ld, top, mu, sigma);
         return hipGetLastError();
     }
     const int Kp = (K + 3) & ~3;
-    const size_t row_bytes = (size_t)(Kp + TOPK_CAP) * sizeof(uint32_t);
-    int rpw = (int)((150 * 1024) / row_bytes);
-    if (rpw < 1) return hipErrorInvalidValue;          // K > 38400: not supported by the LDS-resident selection
-    if (rpw > 4) rpw = 4;
-    const size_t lds = row_bytes * rpw;
+    const dim3 grid((unsigned)((rows + rpw - 1) / rpw)), block(256);
+    if (form == TOPK_STATS_GLOBAL) {                                                        // rows in the slab, the candidates in LDS
+        const size_t lds = (size_t)4 * TOPK_CAP * sizeof(uint32_t);
+        hipLaunchKernelGGL(topk_stats_kernel<false>, grid, block, lds, stream, S, rows, K, ld, Kp, top, rpw, mu, sigma);
+        return hipGetLastError();
+    }
+    const size_t lds = (size_t)(Kp + TOPK_CAP) * sizeof(uint32_t) * rpw;
     static DeviceOnce attr;
-    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(topk_stats_kernel), 160 * 1024)) return e;
-    hipLaunchKernelGGL(topk_stats_kernel, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(256), lds, stream, S, rows, K, ld, Kp, top, rpw, mu, sigma);
+    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(topk_stats_kernel<true>), 160 * 1024)) return e;
+    hipLaunchKernelGGL(topk_stats_kernel<true>, grid, block, lds, stream, S, rows, K, ld, Kp, top, rpw, mu, sigma);
     return hipGetLastError();
 }
 
