@@ -430,6 +430,41 @@ int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, con
  *                  pointer spaces and SVHIP_ASYNC as score_topk (messages start "score_topk_norm:"); a NULL statistic pointer is
  *                  SVHIP_ERR_INVALID "NULL pointer".  Routes as score_topk; profile labels "score_topk_coef" (the coefficients, once per
  *                  call), then "score_topk_norm", "score_topk_merge" (fused) or "score_topk_gemm", "score_topk_rows_norm" (slab).
+ *   score_above  : threshold search ("which enrolled speakers match at all?"): EVERY pair (n, m) of a row of Q (N, D) and a row of G (M, D)
+ *                  whose score reaches a threshold, however many or few there are, without the N x M matrix.  A pair is a HIT iff
+ *                  v(n, m) >= thr, with v = s, the fp32 inner product exactly as score_topk computes it on the same route, or - when the
+ *                  four statistic arrays are given - v = t exactly as score_topk_norm computes it (its statement above; the coefficients
+ *                  under the profile label "score_above_coef").  A NaN v is never a hit; thr = -inf makes every pair whose v is not NaN a
+ *                  hit, thr = +inf only the pairs whose v is +inf; a NaN thr is SVHIP_ERR_INVALID, refused before anything is launched.
+ *                  Result: CSR.  row_ptr[N + 1] int64 (row_ptr[0] = 0), index[total] int32 and score[total] fp32 (v; -0 is returned as
+ *                  +0, as score_topk does) with total = row_ptr[N]; the hits of query n are the entries row_ptr[n] .. row_ptr[n + 1] - 1,
+ *                  in ASCENDING gallery index.  A row's hits (indices and score bits) depend only on that row of Q, its two statistics,
+ *                  G, G's statistics and thr - not on N, on the row's place in Q, on how the gallery is sliced or on which form of the
+ *                  kernel ran: bit for bit; and the score bits of a hit are the bits score_topk / score_topk_norm returns for that pair
+ *                  on the same route.  `mode`: 0, or SVHIP_ABOVE_UPPER: keep a pair only if m > q_base + n - the self-join of one set,
+ *                  Q being the rows q_base .. q_base + N - 1 of G: every unordered pair appears once and no row matches itself; a long
+ *                  set is joined in query chunks, each with its own q_base (q_base >= 0; it is not looked at without the flag).
+ *                  Two calls, so that the caller owns the allocation and nothing overflows silently:
+ *                    svhip_score_above_count   out_count[n] = the number of hits of query n (int64[N]).  The caller takes the
+ *                                              exclusive prefix sum (row_ptr) and allocates index and score for row_ptr[N] entries.
+ *                    svhip_score_above_fill    the same arguments plus row_ptr: counts again, and only if row_ptr[0] = 0 and EVERY row's
+ *                                              recount equals row_ptr[n + 1] - row_ptr[n] writes the hits.  Otherwise (the inputs
+ *                                              changed between the two calls) SVHIP_ERR_INVALID, the message names the first such row, and
+ *                                              NOTHING is written: no entry outside [0, row_ptr[N]) is ever touched.
+ *                  All four statistic pointers NULL: the plain score; some but not all NULL: SVHIP_ERR_INVALID.  Bounds (1 <= M <=
+ *                  2^31 - 1, D >= 1, N >= 0), N = 0 (SVHIP_OK, nothing is read or written), pointer spaces (row_ptr is an input,
+ *                  out_count / out_index / out_score are outputs) as score_topk; messages start "score_above:".  SVHIP_ASYNC: count as
+ *                  score_topk; fill waits for its own recount on the host before it writes and skips only the final wait.  A device
+ *                  row_ptr is read on the handle's stream (row_ptr[N] first, for the size of the outputs): work enqueued there is
+ *                  waited for, a row_ptr produced on ANOTHER stream must be complete before the call, like every device input.
+ *                  Routes as score_topk.  D in {192, 256} with 16-byte aligned operands: the fused kernel (csrc/score_above.hip: the MFMA
+ *                  loop of score_topk's kernel, no score reaches memory), once to count ("score_above_count", then "score_above_scan":
+ *                  the per-row sums, in fill the offsets of a row's lists and the comparison with row_ptr) and once more to write
+ *                  ("score_above_fill": the two lanes that share the 32 rows of a gallery block for one query exchange their hit counts
+ *                  in registers, so a list is written in ascending index as it is met and no ordering pass follows).  Every other width
+ *                  or alignment: slabs of score_matrix's GEMM and a row kernel that counts, then compacts, a slab row in index order
+ *                  ("score_above_gemm", "score_above_rows"); the refusals of score_topk's slab route hold (D % 32 != 0 and
+ *                  M > 4 194 304: SVHIP_ERR_UNSUPPORTED before anything is launched), and so does its magnitude contract.
  * Pointers follow `flags` (indices are int32, device or host like the other inputs). */
 int svhip_l2norm(svhip_handle* h, float* E, int64_t N, int32_t D, int32_t flags);
 int svhip_score_pairs(svhip_handle* h, const float* E, int64_t N, int32_t D,
@@ -446,6 +481,16 @@ int svhip_score_topk(svhip_handle* h, const float* Q, int64_t N, const float* G,
 int svhip_score_topk_norm(svhip_handle* h, const float* Q, int64_t N, const float* q_mu, const float* q_sigma,
                           const float* G, int64_t M, const float* g_mu, const float* g_sigma,
                           int32_t D, int32_t k, float* out_score, int32_t* out_index, int32_t flags);
+/* threshold search (score_above above): count, then fill.  q_mu / q_sigma / g_mu / g_sigma: all NULL (plain score) or none; mode: 0 or
+ * SVHIP_ABOVE_UPPER (q_base then places Q inside G). */
+enum { SVHIP_ABOVE_UPPER = 1 };
+int svhip_score_above_count(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, float thr,
+                            const float* q_mu, const float* q_sigma, const float* g_mu, const float* g_sigma,
+                            int64_t q_base, int32_t mode, int64_t* out_count /* int64[N] */, int32_t flags);
+int svhip_score_above_fill(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, float thr,
+                           const float* q_mu, const float* q_sigma, const float* g_mu, const float* g_sigma,
+                           int64_t q_base, int32_t mode, const int64_t* row_ptr /* int64[N + 1] */,
+                           int32_t* out_index, float* out_score, int32_t flags);
 int svhip_asnorm_pairs(svhip_handle* h, const float* E, int64_t N, int32_t D, const float* mu,
                        const float* sigma, const int32_t* ia, const int32_t* ib, int64_t P,
                        float* out, int32_t flags);

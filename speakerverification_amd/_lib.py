@@ -26,6 +26,7 @@ MODEL_FUSION_HEAD = 9                      # the attention head of Raw_ECAPA_hyp
 F32, BF16, I64, F32X3, F16 = 0, 1, 2, 3, 4
 IN_DEVICE, OUT_DEVICE, ASYNC = 1, 2, 4
 TRIAL_COSINE, TRIAL_PNORM, TRIAL_PDIST = 0, 1, 2
+ABOVE_UPPER = 1                            # svhip_score_above_*: only the pairs with m > q_base + n (the self-join of one set)
 COMM_ID_BYTES = 128
 
 
@@ -91,6 +92,9 @@ _SIGNATURES = {
     "svhip_score_matrix": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_int32]),
     "svhip_score_topk": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
     "svhip_score_topk_norm": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
+    "svhip_score_above_count": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32]),
+    "svhip_score_above_fill": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P,
+                                         C.c_int32]),
     "svhip_asnorm_stats": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
     "svhip_asnorm_pairs": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, C.c_int32]),
     "svhip_asnorm_last_fallback": (C.c_int64, [_P]),

@@ -2,6 +2,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include "handle.h"
 
@@ -585,6 +587,228 @@ int svhip_score_topk_norm(svhip_handle* h, const float* Q, int64_t N, const floa
                           const float* g_mu, const float* g_sigma, int32_t D, int32_t k, float* out_score, int32_t* out_index, int32_t flags) {
     const float* stats[4] = {q_mu, q_sigma, g_mu, g_sigma};
     return score_topk_impl(h, "score_topk_norm", Q, N, G, M, stats, D, k, out_score, out_index, flags);
+}
+
+// ---- threshold search: every gallery row at or above a score, as CSR rows (score_above.hip) -----------------------------------------------
+// Routes, query chunks, the FEW / MANY split of a chunk and the slab sizes are score_topk's.  Both entry points count first (every launch of
+// the call, into one scratch: a few list counts per row); fill then reads ONE word back - the first row whose recount is not what row_ptr
+// says - and writes only if there is none, so no entry outside [0, row_ptr[N]) is ever touched.
+namespace {
+struct AboveArgs {
+    const float *dQ, *dG;
+    int64_t N, M;
+    int D;
+    float thr;
+    int upper;
+    int64_t q_base;
+    const float2 *qc, *gc;
+    int64_t* dCount;              // count
+    const int64_t* dRowPtr;       // fill
+    int32_t* dIndex;
+    float* dScore;
+    int64_t total;                // fill: row_ptr[N]
+};
+struct AbovePart { int64_t r0, rows; bool few; int slices, per, nl; size_t first; };      // first: its place in the list-count scratch
+
+// fill: the word the scan / row kernels lowered -> OK, or the refusal that names the row
+int above_guard(svhip_handle* h, const unsigned long long* bad) {
+    unsigned long long row = 0;
+    SV_HIP(h, hipMemcpyAsync(&row, bad, 8, hipMemcpyDeviceToHost, h->stream));
+    SV_HIP(h, hipStreamSynchronize(h->stream));
+    if (row != ~0ull)
+        SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: row %llu now holds another number of hits than row_ptr[%llu + 1] - row_ptr[%llu] (or row_ptr[0] is not 0): "
+                "the inputs changed between count and fill; nothing was written", row, row, row);
+    return SVHIP_OK;
+}
+
+int above_fused(svhip_handle* h, const AboveArgs& a) {
+    const bool fill = a.dRowPtr != nullptr;
+    const int64_t nb_all = (a.M + 31) / 32;
+    const int cu = h->num_cu > 0 ? h->num_cu : 256;
+    std::vector<AbovePart> parts;
+    size_t entries = 0;
+    auto add = [&](int64_t r0, int64_t rows, bool few) {
+        // as topk_fused_part: two workgroups per CU (few: one), and a workgroup walks at least 8 (16) gallery blocks
+        const int64_t tiles = few ? 1 : (rows + 127) / 128;
+        int64_t slices = ((few ? 1 : 2) * (int64_t)cu + tiles - 1) / tiles;
+        const int64_t min_blocks = few ? 16 : 8;
+        slices = std::max<int64_t>(1, std::min<int64_t>(std::min(slices, (nb_all + min_blocks - 1) / min_blocks), 65535));
+        const int64_t per = (nb_all + slices - 1) / slices;
+        slices = (nb_all + per - 1) / per;
+        parts.push_back({r0, rows, few, (int)slices, (int)per, (int)slices * (few ? 4 : 1), entries});
+        entries += (size_t)rows * parts.back().nl;
+    };
+    constexpr int64_t CHUNK = 16384;
+    for (int64_t r0 = 0; r0 < a.N; r0 += CHUNK) {
+        const int64_t rows = std::min(CHUNK, a.N - r0);
+        const int64_t tail = rows % 128;
+        const int64_t n_few = (tail >= 1 && tail <= 32) ? tail : 0, n_many = rows - n_few;
+        if (n_many) add(r0, n_many, false);
+        if (n_few) add(r0 + n_many, n_few, true);
+    }
+    // [the guard's word (256 bytes) | list counts (int32) | fill: list offsets (int64)]
+    const size_t cnt_bytes = (entries * 4 + 255) & ~(size_t)255;
+    void* s = nullptr;
+    if (int rc = scratch(h, svhip_handle::SCR_TOPK, 256 + cnt_bytes + (fill ? entries * 8 : 0), &s)) return rc;
+    unsigned long long* bad = reinterpret_cast<unsigned long long*>(s);
+    int32_t* lcnt = reinterpret_cast<int32_t*>((char*)s + 256);
+    int64_t* loff = reinterpret_cast<int64_t*>((char*)s + 256 + cnt_bytes);
+    if (fill) SV_HIP(h, hipMemsetAsync(bad, 0xff, 8, h->stream));
+    auto params = [&](const AbovePart& t) {
+        ScoreAboveParams p;
+        p.Q = a.dQ + t.r0 * a.D; p.N = t.rows; p.G = a.dG; p.M = a.M; p.thr = a.thr; p.upper = a.upper; p.row_base = a.q_base + t.r0;
+        p.per = t.per; p.nl = t.nl; p.lcnt = lcnt + t.first; p.loff = loff + t.first; p.out_index = a.dIndex; p.out_score = a.dScore;
+        p.qcoef = a.qc ? a.qc + t.r0 : nullptr; p.gcoef = a.gc;
+        return p;
+    };
+    for (const AbovePart& t : parts) {
+        const ScoreAboveParams p = params(t);
+        if (int rc = run(h, "score_above_count", 2.0 * t.rows * a.M * a.D, [&]() { return launch_score_above(p, a.D, t.few, t.slices, false, h->stream); })) return rc;
+        if (int rc = run(h, "score_above_scan", 0, [&]() {
+                return launch_score_above_scan(p.lcnt, t.rows, t.nl, fill ? nullptr : a.dCount + t.r0, fill ? a.dRowPtr + t.r0 : nullptr, t.r0,
+                                               fill ? loff + t.first : nullptr, fill ? bad : nullptr, h->stream);
+            })) return rc;
+    }
+    if (!fill) return SVHIP_OK;
+    if (int rc = above_guard(h, bad)) return rc;
+    if (a.total == 0) return SVHIP_OK;
+    for (const AbovePart& t : parts) {
+        const ScoreAboveParams p = params(t);
+        if (int rc = run(h, "score_above_fill", 2.0 * t.rows * a.M * a.D, [&]() { return launch_score_above(p, a.D, t.few, t.slices, true, h->stream); })) return rc;
+    }
+    return SVHIP_OK;
+}
+
+int above_slab(svhip_handle* h, const AboveArgs& a) {
+    const bool fill = a.dRowPtr != nullptr;
+    const int64_t ldk = (a.M + 3) & ~(int64_t)3;                  // row stride of the slab (16-byte rows for the DMA GEMM)
+    const int64_t max_m = (((int64_t)1 << 31) / (128 * 4)) & ~(int64_t)3;
+    if (ldk > max_m)
+        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "score_above: D = %d takes the slab route, whose 128-row slab holds at most M = %lld gallery rows (M = %lld)", a.D,
+                (long long)max_m, (long long)a.M);
+    const int64_t slab_rows = std::min<int64_t>(a.N, std::max<int64_t>(128, ((int64_t)1 << 31) / (ldk * 4)));
+    void *gsplit = nullptr, *slab = nullptr, *w = nullptr;
+    int rc;
+    const ScoreRoute route = score_route(h, a.dQ, slab_rows, a.dG, a.M, a.D);       // (every slab starts r0 * D * 4 bytes into Q: the same alignment)
+    if ((rc = split_b(h, route, a.dG, a.M, a.D, &gsplit))) return rc;
+    if ((rc = scratch(h, svhip_handle::SCR_SLAB, (size_t)slab_rows * ldk * 4, &slab))) return rc;
+    if ((rc = scratch(h, svhip_handle::SCR_TOPK, 256, &w))) return rc;
+    unsigned long long* bad = reinterpret_cast<unsigned long long*>(w);
+    if (fill) SV_HIP(h, hipMemsetAsync(bad, 0xff, 8, h->stream));
+    // one pass over the slabs: count, compare with row_ptr (check) or write
+    auto pass = [&](bool check, bool gemm) {
+        for (int64_t r0 = 0; r0 < a.N; r0 += slab_rows) {
+            const int64_t rows = std::min(slab_rows, a.N - r0);
+            if (gemm && (rc = score_gemm(h, "score_above_gemm", a.dQ + r0 * a.D, rows, a.dG, a.M, a.D, (float*)slab, ldk, route, gsplit))) return rc;
+            rc = run(h, "score_above_rows", 0, [&]() {
+                return launch_score_above_rows((const float*)slab, rows, a.M, ldk, a.thr, a.upper, a.q_base + r0, a.qc ? a.qc + r0 : nullptr, a.gc,
+                                               fill ? nullptr : a.dCount + r0, fill ? a.dRowPtr + r0 : nullptr, r0, check ? bad : nullptr,
+                                               fill && !check ? a.dIndex : nullptr, fill && !check ? a.dScore : nullptr, h->stream);
+            });
+            if (rc) return rc;
+        }
+        return (int)SVHIP_OK;
+    };
+    if (!fill) return pass(false, true);
+    if ((rc = pass(true, true))) return rc;
+    if ((rc = above_guard(h, bad))) return rc;
+    if (a.total == 0) return SVHIP_OK;
+    return pass(false, slab_rows < a.N);                            // (one slab: its scores are still there)
+}
+
+int score_above_impl(svhip_handle* h, bool fill, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, float thr, const float* const* stats,
+                     int64_t q_base, int32_t mode, int64_t* out_count, const int64_t* row_ptr, int32_t* out_index, float* out_score, int32_t flags) {
+    if (!h) return SVHIP_ERR_INVALID;
+    if (thr != thr) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: the threshold is NaN");
+    if (M < 1 || M > (int64_t)INT32_MAX) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: M = %lld is outside [1, 2^31 - 1]", (long long)M);
+    if (D < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: D = %d must be at least 1", (int)D);
+    if (N < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: N = %lld is negative", (long long)N);
+    if (mode & ~SVHIP_ABOVE_UPPER) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: unknown mode bits %d", (int)mode);
+    const int upper = mode & SVHIP_ABOVE_UPPER;
+    if (upper && q_base < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: q_base = %lld is negative", (long long)q_base);
+    const int n_stats = !!stats[0] + !!stats[1] + !!stats[2] + !!stats[3];
+    if (n_stats != 0 && n_stats != 4) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: %d of the four statistic arrays are NULL: give all four or none", 4 - n_stats);
+    if (N == 0) return SVHIP_OK;
+    if (!Q || !G || (fill ? !row_ptr : !out_count)) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: NULL pointer");
+    if (D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "score_above: embedding dim %d must be a multiple of 32", (int)D);      // before any copy or launch
+    SV_HIP(h, hipSetDevice(h->cfg.device));
+    const bool din = flags & SVHIP_IN_DEVICE, dout = flags & SVHIP_OUT_DEVICE;
+    AboveArgs a{};
+    a.N = N; a.M = M; a.D = D; a.thr = thr; a.upper = upper; a.q_base = upper ? q_base : 0;
+    TempBuf tQ{h, svhip_handle::SCR_IN0}, tG{h, svhip_handle::SCR_IN1}, tR{h, svhip_handle::SCR_OUT2}, tI{h, svhip_handle::SCR_OUT0}, tS{h, svhip_handle::SCR_OUT1};
+    const void *dQ, *dG;
+    int rc;
+    if ((rc = tQ.in(Q, (size_t)N * D * 4, din, &dQ))) return rc;
+    if ((rc = tG.in(G, (size_t)M * D * 4, din, &dG))) return rc;
+    a.dQ = (const float*)dQ; a.dG = (const float*)dG;
+    if (fill) {
+        const void* dR;
+        if ((rc = tR.in(row_ptr, (size_t)(N + 1) * 8, din, &dR))) return rc;
+        a.dRowPtr = (const int64_t*)dR;
+        if (din) {          // (on the handle's stream: a row_ptr produced there needs no wait by the caller)
+            SV_HIP(h, hipMemcpyAsync(&a.total, row_ptr + N, 8, hipMemcpyDeviceToHost, h->stream));
+            SV_HIP(h, hipStreamSynchronize(h->stream));
+        }
+        else a.total = row_ptr[N];
+        if (a.total < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: row_ptr[N] = %lld is negative", (long long)a.total);
+        if (a.total > 0 && (!out_index || !out_score)) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: NULL pointer");
+        void *dI = nullptr, *dS = nullptr;
+        if (a.total > 0 && ((rc = tI.out(out_index, (size_t)a.total * 4, dout, &dI)) || (rc = tS.out(out_score, (size_t)a.total * 4, dout, &dS)))) return rc;
+        a.dIndex = (int32_t*)dI; a.dScore = (float*)dS;
+    } else {
+        void* dC;
+        if ((rc = tI.out(out_count, (size_t)N * 8, dout, &dC))) return rc;
+        a.dCount = (int64_t*)dC;
+    }
+    if (n_stats) {
+        // the coefficient tables of score_topk_norm, once per call: [queries (N) | gallery (whole blocks of 32 rows), on a 16-byte boundary]
+        const int slot[4] = {svhip_handle::SCR_IN2, svhip_handle::SCR_IN3, svhip_handle::SCR_IN4, svhip_handle::SCR_IN5};
+        const void* d[4];
+        for (int i = 0; i < 4; ++i) {
+            TempBuf t{h, slot[i]};
+            if ((rc = t.in(stats[i], (size_t)(i < 2 ? N : M) * 4, din, &d[i]))) return rc;
+        }
+        const size_t q_bytes = ((size_t)N * 8 + 15) & ~(size_t)15;
+        void* c = nullptr;
+        if ((rc = scratch(h, svhip_handle::SCR_COEF, q_bytes + (size_t)score_topk_coef_rows(M) * 8, &c))) return rc;
+        float2* qcw = reinterpret_cast<float2*>(c);
+        float2* gcw = reinterpret_cast<float2*>((char*)c + q_bytes);
+        if ((rc = run(h, "score_above_coef", 0, [&]() {
+                 return launch_score_topk_coef((const float*)d[0], (const float*)d[1], N, (const float*)d[2], (const float*)d[3], M, qcw, gcw, h->stream);
+             }))) return rc;
+        a.qc = qcw; a.gc = gcw;
+    }
+    const bool aligned = ((reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dG)) & 15) == 0;
+    rc = score_topk_fused_supported(D) && aligned ? above_fused(h, a) : above_slab(h, a);
+    if (!rc && !dout) {
+        hipError_t e = hipSuccess;
+        if (!fill) e = hipMemcpyAsync(out_count, a.dCount, (size_t)N * 8, hipMemcpyDeviceToHost, h->stream);
+        else if (a.total > 0) {
+            e = hipMemcpyAsync(out_index, a.dIndex, (size_t)a.total * 4, hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(out_score, a.dScore, (size_t)a.total * 4, hipMemcpyDeviceToHost, h->stream);
+        }
+        if (e != hipSuccess) { h->err = std::string("score_above: copy of the results failed: ") + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
+    }
+    if (rc || !(din && dout && (flags & SVHIP_ASYNC))) {
+        const hipError_t e = hipStreamSynchronize(h->stream);
+        if (!rc && e != hipSuccess) { h->err = std::string("score_above: ") + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
+        release_big_scratch(h, !din || !dout);
+    }
+    return rc;
+}
+}  // namespace
+
+int svhip_score_above_count(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, float thr, const float* q_mu,
+                            const float* q_sigma, const float* g_mu, const float* g_sigma, int64_t q_base, int32_t mode, int64_t* out_count, int32_t flags) {
+    const float* stats[4] = {q_mu, q_sigma, g_mu, g_sigma};
+    return score_above_impl(h, false, Q, N, G, M, D, thr, stats, q_base, mode, out_count, nullptr, nullptr, nullptr, flags);
+}
+
+int svhip_score_above_fill(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, float thr, const float* q_mu,
+                           const float* q_sigma, const float* g_mu, const float* g_sigma, int64_t q_base, int32_t mode, const int64_t* row_ptr,
+                           int32_t* out_index, float* out_score, int32_t flags) {
+    const float* stats[4] = {q_mu, q_sigma, g_mu, g_sigma};
+    return score_above_impl(h, true, Q, N, G, M, D, thr, stats, q_base, mode, nullptr, row_ptr, out_index, out_score, flags);
 }
 
 int64_t svhip_asnorm_last_fallback(const svhip_handle* h) { return h ? h->last_asnorm_flagged : -1; }

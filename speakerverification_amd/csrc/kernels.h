@@ -736,6 +736,40 @@ int64_t score_topk_coef_rows(int64_t M);
 hipError_t launch_score_topk_coef(const float* q_mu, const float* q_sigma, int64_t N, const float* g_mu, const float* g_sigma, int64_t M,
                                   float2* qcoef, float2* gcoef, hipStream_t stream);
 
+// Threshold search (score_above.hip): every (query, gallery row) pair whose score v reaches `thr` (v = s, or t with the coefficient tables
+// of score_topk_coef), as CSR rows in ascending gallery index — without the N x M matrix.  The fused kernel is score_topk_kernel's MFMA loop
+// with another epilogue; the grid is query tiles x gallery slices as there.  A query's lists are CONTIGUOUS runs of gallery blocks in
+// ascending order: one per slice (`few`: four, each wave of the workgroup walks a quarter of the slice).  The count form adds up the hits
+// of a list, launch_score_above_scan sums the lists of a row (and places them inside the row's CSR segment), the fill form writes.
+struct ScoreAboveParams {
+    const float* Q = nullptr;       // (N, D) queries of this launch
+    int64_t N = 0;
+    const float* G = nullptr;       // (M, D) gallery
+    int64_t M = 0;
+    float thr = 0.0f;               // a hit: v >= thr (never NaN)
+    int upper = 0;                  // SVHIP_ABOVE_UPPER: only the pairs with m > row_base + n
+    int64_t row_base = 0;           // q_base + the place of this launch's first query in the call
+    int per = 0;                    // blocks of 32 gallery rows per slice
+    int nl = 0;                     // lists per query: slices (few: 4 slices)
+    int32_t* lcnt = nullptr;        // (N, nl) hits per list: written by the count form, the fill form's write bound
+    const int64_t* loff = nullptr;  // fill: (N, nl) where each list starts in out_index / out_score
+    int32_t* out_index = nullptr;   // fill
+    float* out_score = nullptr;     // fill
+    const float2* qcoef = nullptr;  // the normalised form: both tables or neither (ScoreTopkParams)
+    const float2* gcoef = nullptr;
+};
+hipError_t launch_score_above(const ScoreAboveParams& p, int D, bool few, int slices, bool fill, hipStream_t stream);
+// per row of a launch the sum of its nl list counts.  out_count (count): out_count[row] = the sum.  row_ptr (fill; both offset to the
+// launch's first row, row0 = that row's place in the call): loff[row, l] = row_ptr[row] + the hits of the lists before l, and a row whose
+// sum is not row_ptr[row + 1] - row_ptr[row] (or row 0 of the call with row_ptr[0] != 0) lowers *bad to its place in the call
+hipError_t launch_score_above_scan(const int32_t* lcnt, int64_t rows, int nl, int64_t* out_count, const int64_t* row_ptr, int64_t row0,
+                                   int64_t* loff, unsigned long long* bad, hipStream_t stream);
+// the slab route: one workgroup per row of S (rows x M, row stride ld % 4 == 0, 16-byte aligned).  Exactly one of: out_count (count),
+// bad (compare the count with row_ptr, as the scan does), out_index + out_score (write the row's hits at row_ptr[row], ascending)
+hipError_t launch_score_above_rows(const float* S, int64_t rows, int64_t M, int64_t ld, float thr, int upper, int64_t row_base, const float2* qcoef,
+                                   const float2* gcoef, int64_t* out_count, const int64_t* row_ptr, int64_t row0, unsigned long long* bad,
+                                   int32_t* out_index, float* out_score, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // Verification metrics (metrics.hip): one workspace of metrics_workspace_bytes(P) holds the sorted trial list
 // ---------------------------------------------------------------------------------------------

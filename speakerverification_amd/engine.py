@@ -570,6 +570,70 @@ class Engine:
         _count([q, g, *st], [s, i])
         return scores, index
 
+    @staticmethod
+    def _above_row_ptr(count, max_hits):
+        """``score_above``'s step between its two calls: the per-row hit counts -> ``(row_ptr, total)``, the exclusive prefix sum
+        (int64, N + 1 entries, in the counts' memory space) and its last entry.  A total above ``max_hits`` is a ``ValueError`` that
+        names it, raised before anything is allocated for the hits."""
+        if _is_torch(count):
+            row_ptr = torch.zeros(count.numel() + 1, dtype=torch.int64, device=count.device)
+            torch.cumsum(count, 0, out=row_ptr[1:])
+        else:
+            row_ptr = np.zeros(count.size + 1, np.int64)
+            np.cumsum(count, out=row_ptr[1:])
+        total = int(row_ptr[-1])
+        if total > max_hits:
+            raise ValueError(f"score_above: {total} hits exceed max_hits = {max_hits}; raise the threshold, query fewer rows per call or raise max_hits")
+        return row_ptr, total
+
+    def score_above(self, Q, G, thr, q_stats=None, g_stats=None, upper=False, q_base=0, max_hits=2 ** 28):
+        """Threshold search (``svhip_score_above_count`` / ``_fill``): EVERY pair of a row of Q (N, D) and a row of the gallery G (M, D)
+        whose score is at least ``thr``, as CSR -> ``(row_ptr (N + 1,) int64, index (total,) int32, score (total,) float32)``: the hits
+        of query n are ``index[row_ptr[n]:row_ptr[n + 1]]``, in ascending gallery index.  The score is the inner product as
+        ``score_topk`` computes it, or - with ``q_stats`` and ``g_stats``, the ``(mu, sigma)`` pairs of ``asnorm_stats`` - the
+        normalised score of ``score_topk_norm``; a NaN score is never a hit.  ``upper``: the self-join of one set - Q is the rows
+        ``q_base ..`` of G, and only the pairs with ``m > q_base + n`` are kept (every unordered pair once, no row with itself).
+        All arrays in one memory space; the results come back in it.  Runs the count, takes the prefix sum, allocates, fills;
+        more than ``max_hits`` hits in all are refused by a ``ValueError`` that names the total, before the allocation."""
+        N, D = Q.shape
+        M = G.shape[0]
+        if G.shape[1] != D:
+            raise ValueError(f"queries are {D} wide, the gallery {G.shape[1]}")
+        thr = float(thr)
+        if thr != thr:
+            raise ValueError("score_above: the threshold is NaN")
+        if (q_stats is None) != (g_stats is None):
+            raise ValueError("score_above: q_stats and g_stats go together: give both (normalised scores) or neither")
+        stats = ()
+        if q_stats is not None:
+            if len(q_stats) != 2 or len(g_stats) != 2:
+                raise ValueError("q_stats and g_stats must be (mu, sigma) pairs")
+            for what, st, n in (("q_stats", q_stats, N), ("g_stats", g_stats, M)):
+                for name, x in zip(("mu", "sigma"), st):
+                    if x is None or tuple(x.shape) != (n,):
+                        raise ValueError(f"{what}: {name} must hold {n} values, not {None if x is None else tuple(x.shape)}")
+            stats = (*q_stats, *g_stats)
+        on_dev = _is_torch(Q) and Q.is_cuda
+        empty = (lambda n, dt: torch.empty(n, dtype=getattr(torch, np.dtype(dt).name), device=Q.device)) if on_dev else np.empty
+        q, g = _Buf(Q, np.float32), _Buf(G, np.float32)
+        st = [_Buf(x, np.float32) for x in stats]
+        sp = [b.ptr for b in st] or [None] * 4
+        count = empty(N, np.int64)
+        c = _Buf(count, np.int64, writable=True)
+        dev = self._same_space(q, g, *st, c)
+        flags = (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0
+        mode = _lib.ABOVE_UPPER if upper else 0
+        self._ck(self.lib.svhip_score_above_count(self.h, q.ptr, N, g.ptr, M, D, thr, *sp, int(q_base), mode, c.ptr, flags))
+        _count([q, g, *st], [c])
+        row_ptr, total = self._above_row_ptr(count, max_hits)
+        index, score = empty(total, np.int32), empty(total, np.float32)
+        if total:
+            r, i, s = _Buf(row_ptr, np.int64), _Buf(index, np.int32, writable=True), _Buf(score, np.float32, writable=True)
+            self._order_after_torch(r)
+            self._ck(self.lib.svhip_score_above_fill(self.h, q.ptr, N, g.ptr, M, D, thr, *sp, int(q_base), mode, r.ptr, i.ptr, s.ptr, flags))
+            _count([q, g, *st, r], [i, s])
+        return row_ptr, index, score
+
     # ---- verification metrics (host arrays in / out; the trial list is small next to the embeddings) --------------------
     def _scores_labels(self, scores, labels):
         if _is_torch(scores):

@@ -530,6 +530,45 @@ class ModelHandling:
             raise ValueError(f"{len(classes)} class names for {g.shape[0]} enrolled classes")
         return np.ascontiguousarray(g), classes
 
+    def _cohort(self, scoring_mode, cohorts, cohorts_path, width):
+        """the cohort of ``scoring_mode="norm"`` as a (K, nOut) float32 array (None for "cosine"); a missing or mis-shaped one is refused"""
+        if scoring_mode not in ("cosine", "norm"):
+            raise ValueError(f"unknown scoring_mode {scoring_mode}")
+        if scoring_mode != "norm":
+            return None
+        if cohorts is None and cohorts_path is not None:
+            cohorts = np.load(str(cohorts_path))
+        if cohorts is None:
+            raise ValueError("scoring_mode 'norm' needs a cohort: cohorts (an array) or cohorts_path (an .npy file)")
+        cohorts = np.ascontiguousarray(_host(cohorts), dtype=np.float32)
+        if cohorts.ndim != 2 or cohorts.shape[1] != width:
+            raise ValueError(f"the cohort must be (K, {width}), not {cohorts.shape}")
+        return cohorts
+
+    def _search_operands(self, source, embeds, classes, num_eval, scoring_mode, cohorts, cohorts_path, check_gallery=None):
+        """What ``identify`` and ``matches`` search with, by ``identify``'s rule: the files' crop-mean embeddings and the gallery's class
+        rows, both L2-normalised -> ``(q (n_files, nOut), gal (n_class, nOut), classes or None, cohort or None)``.
+        ``check_gallery(gal)`` runs before any file is embedded."""
+        self.__model__.eval()
+        files = list(source) if isinstance(source, (list, tuple)) else [source]
+        if not files:
+            raise ValueError("Please provide appropriate source!")
+        gal, classes = self._gallery(embeds, classes)
+        if check_gallery is not None:
+            check_gallery(gal)
+        cohorts = self._cohort(scoring_mode, cohorts, cohorts_path, gal.shape[1])
+        eng = scoring.scoring_engine(self.gpu)
+        feats = np.asarray(_host(self._embed_files(files, num_eval)), dtype=np.float32)       # (n_files, n_crops, nOut)
+        if feats.shape[-1] != gal.shape[1]:
+            raise ValueError(f"the model embeds to {feats.shape[-1]} values, the gallery holds {gal.shape[1]}")
+        flat = np.ascontiguousarray(feats.reshape(-1, feats.shape[-1]))
+        if self.__model__.module.test_normalize:
+            eng.l2norm_(flat)
+        q = np.ascontiguousarray(flat.reshape(feats.shape).mean(axis=1))
+        eng.l2norm_(q)
+        eng.l2norm_(gal)
+        return q, gal, classes, cohorts
+
     def identify(self, source, embeds, classes=None, top=1, num_eval=10, scoring_mode="cosine", cohorts=None, cohorts_path=None,
                  cohort_top=200, thresh_score=None):
         """Whose voice is this?  The ``top`` best enrolled classes of every file of ``source`` (what ``_embed_files`` takes: a list of
@@ -556,34 +595,13 @@ class ModelHandling:
 
         Returns ``(scores (n_files, top) float32, index (n_files, top) int32)``, best first, and as a third item the class names
         (a list of ``top`` names per file) when ``classes`` is given ({index: name} or a sequence) or the directory holds ``classes.npy``."""
-        self.__model__.eval()
-        files = list(source) if isinstance(source, (list, tuple)) else [source]
-        if not files:
-            raise ValueError("Please provide appropriate source!")
-        gal, classes = self._gallery(embeds, classes)
         top = int(top)
-        if top < 1 or top > gal.shape[0]:
-            raise ValueError(f"top = {top} must lie in [1, n_class = {gal.shape[0]}]")
-        if scoring_mode not in ("cosine", "norm"):
-            raise ValueError(f"unknown scoring_mode {scoring_mode}")
-        if scoring_mode == "norm":
-            if cohorts is None and cohorts_path is not None:
-                cohorts = np.load(str(cohorts_path))
-            if cohorts is None:
-                raise ValueError("scoring_mode 'norm' needs a cohort: cohorts (an array) or cohorts_path (an .npy file)")
-            cohorts = np.ascontiguousarray(_host(cohorts), dtype=np.float32)
-            if cohorts.ndim != 2 or cohorts.shape[1] != gal.shape[1]:
-                raise ValueError(f"the cohort must be (K, {gal.shape[1]}), not {cohorts.shape}")
-        eng = scoring.scoring_engine(self.gpu)
-        feats = np.asarray(_host(self._embed_files(files, num_eval)), dtype=np.float32)       # (n_files, n_crops, nOut)
-        if feats.shape[-1] != gal.shape[1]:
-            raise ValueError(f"the model embeds to {feats.shape[-1]} values, the gallery holds {gal.shape[1]}")
-        flat = np.ascontiguousarray(feats.reshape(-1, feats.shape[-1]))
-        if self.__model__.module.test_normalize:
-            eng.l2norm_(flat)
-        q = np.ascontiguousarray(flat.reshape(feats.shape).mean(axis=1))
-        eng.l2norm_(q)
-        eng.l2norm_(gal)
+
+        def check_top(gal):
+            if top < 1 or top > gal.shape[0]:
+                raise ValueError(f"top = {top} must lie in [1, n_class = {gal.shape[0]}]")
+
+        q, gal, classes, cohorts = self._search_operands(source, embeds, classes, num_eval, scoring_mode, cohorts, cohorts_path, check_top)
         if scoring_mode == "norm":
             scores, index, _ = scoring.score_topk_norm(q, gal, top, cohorts, top=int(cohort_top), device=self.gpu)
         else:
@@ -593,6 +611,55 @@ class ModelHandling:
         if classes is None:
             return scores, index
         return scores, index, [[classes[int(i)] if i >= 0 else None for i in row] for row in np.asarray(_host(index))]
+
+    def matches(self, source, embeds, thresh_score, classes=None, num_eval=10, scoring_mode="cosine", cohorts=None, cohorts_path=None,
+                cohort_top=200):
+        """Which enrolled classes match at all?  For every file of ``source`` ALL classes of the gallery whose score is at least
+        ``thresh_score``, however many or few - where ``identify(top=k, thresh_score=...)`` stops at its k best.  Sources, gallery forms,
+        the preparation of both sides, ``scoring_mode`` and the cohort arguments are ``identify``'s, and so is every score (bit for bit);
+        the search is ONE ``score_above`` call, which writes no score below the threshold anywhere.
+
+        Returns ``(scores, index)``: per file a float32 array and an int32 array of its matches, best first (score descending, equal
+        scores by the lower class index: ``identify``'s order), empty for a file without a match; and as a third item the class names
+        (a list per file) when ``classes`` is given or the directory holds ``classes.npy``."""
+        q, gal, classes, cohorts = self._search_operands(source, embeds, classes, num_eval, scoring_mode, cohorts, cohorts_path)
+        row_ptr, index, score = scoring.score_above(q, gal, thresh_score, cohort=cohorts, top=int(cohort_top), device=self.gpu)
+        row_ptr, index, score = np.asarray(_host(row_ptr)), np.asarray(_host(index)), np.asarray(_host(score))
+        scores, found = [], []
+        for n in range(q.shape[0]):
+            seg = slice(int(row_ptr[n]), int(row_ptr[n + 1]))
+            order = np.argsort(-score[seg], kind="stable")              # (the segment is in ascending class index: ties keep it)
+            scores.append(score[seg][order])
+            found.append(index[seg][order])
+        if classes is None:
+            return scores, found
+        return scores, found, [[classes[int(i)] for i in row] for row in found]
+
+    def duplicates(self, embeds, thresh_score, classes=None, scoring_mode="cosine", cohorts=None, cohorts_path=None, cohort_top=200,
+                   chunk=65536):
+        """Who was enrolled twice?  The self-join of a gallery (``identify``'s three forms, prepared the same way): every pair of
+        classes ``i < j`` whose score is at least ``thresh_score``, each once, no class with itself.  The gallery is joined ``chunk``
+        query rows at a time (``score_above`` with ``upper=True``), so no N x N matrix exists.
+
+        Returns ``(i, j, score)``: int32, int32 and float32 arrays of equal length, ordered by i, then j; and as a fourth item the
+        pairs of class names when ``classes`` is given or the directory holds ``classes.npy``."""
+        gal, classes = self._gallery(embeds, classes)
+        cohorts = self._cohort(scoring_mode, cohorts, cohorts_path, gal.shape[1])
+        eng = scoring.scoring_engine(self.gpu)
+        eng.l2norm_(gal)
+        g_stats = None if cohorts is None else eng.asnorm_stats(gal, cohorts, int(cohort_top))
+        ii, jj, ss = [], [], []
+        for base in range(0, gal.shape[0], int(chunk)):
+            rows = gal[base:base + int(chunk)]
+            row_ptr, index, score = scoring.score_above(rows, gal, thresh_score, cohort=cohorts, top=int(cohort_top), g_stats=g_stats, upper=True,
+                                                        q_base=base, device=self.gpu)
+            ii.append(np.repeat(np.arange(base, base + rows.shape[0], dtype=np.int32), np.diff(np.asarray(_host(row_ptr)))))
+            jj.append(np.asarray(_host(index)))
+            ss.append(np.asarray(_host(score)))
+        i, j, s = (np.concatenate(x) for x in (ii, jj, ss))
+        if classes is None:
+            return i, j, s
+        return i, j, s, [(classes[int(a)], classes[int(b)]) for a, b in zip(i, j)]
 
     # ---- checkpoints ------------------------------------------------------------------------------------------------------
     def saveParameters(self, path):

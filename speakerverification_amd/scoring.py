@@ -1,8 +1,8 @@
 """Scoring counterparts of the reference's ``src/utils.py:126-169``.
 
 ``similarity_measure(method, ref, com, **kw)`` keeps the per-trial signature for compatibility; the
-batched entry points (``score_pairs``, ``score_matrix``, ``score_topk``, ``score_topk_norm``, ``asnorm_stats``, ``asnorm_pairs``,
-``score_trials``) are what ``ModelHandling.evaluateFromList`` uses: one kernel launch per trial LIST
+batched entry points (``score_pairs``, ``score_matrix``, ``score_topk``, ``score_topk_norm``, ``score_above``, ``asnorm_stats``,
+``asnorm_pairs``, ``score_trials``) are what ``ModelHandling.evaluateFromList`` uses: one kernel launch per trial LIST
 instead of three host<->device crossings per trial.
 """
 from __future__ import annotations
@@ -69,6 +69,24 @@ def score_topk_norm(Q, G, k, cohort, top=200, g_stats=None, device=0):
     q_stats = eng.asnorm_stats(Q, cohort, top)
     scores, index = eng.score_topk_norm(Q, q_stats, G, g_stats, k)
     return scores, index, tuple(g_stats)
+
+
+def score_above(Q, G, thr, cohort=None, top=200, g_stats=None, upper=False, q_base=0, max_hits=2 ** 28, device=0):
+    """every (row of Q, row of G) pair whose score is at least ``thr`` -> CSR ``(row_ptr (N + 1,) int64, index int32, score float32)``,
+    a row's hits in ascending gallery index (``Engine.score_above``).  With a ``cohort`` the score is the adaptive-S-normalised one of
+    ``score_topk_norm``: the statistics of Q, and of G unless ``g_stats = (mu, sigma)`` is given, come from
+    ``asnorm_stats(., cohort, top)``.  ``upper`` / ``q_base``: the self-join of one set, every unordered pair once."""
+    if float(thr) != float(thr):
+        raise ValueError("score_above: the threshold is NaN")
+    eng = scoring_engine(device)
+    if cohort is None:
+        if g_stats is not None:
+            raise ValueError("score_above: g_stats without a cohort (the queries' statistics need it)")
+        return eng.score_above(Q, G, thr, upper=upper, q_base=q_base, max_hits=max_hits)
+    if g_stats is None:
+        g_stats = eng.asnorm_stats(G, cohort, top)
+    q_stats = eng.asnorm_stats(Q, cohort, top)
+    return eng.score_above(Q, G, thr, q_stats, g_stats, upper=upper, q_base=q_base, max_hits=max_hits)
 
 
 def asnorm_stats(E, cohort, top=200, device=0):
