@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -238,30 +239,53 @@ int svhip_score_matrix(svhip_handle* h, const float* A, int64_t Na, const float*
     return rc;
 }
 
+// The slab route of asnorm_stats, score_topk and score_above: A @ B^T goes through an HBM scratch (SCR_SLAB) in slabs of A's rows - at most
+// 2 GiB, at least 128 rows, row stride ldk - and a row kernel consumes each slab.  open() decides everything once per call, pass() walks.
+namespace {
+struct SlabWalk {
+    svhip_handle* h;
+    const float* dA; int64_t N;
+    const float* dB; int64_t M;
+    int D;
+    int64_t ldk = 0, slab_rows = 0;
+    ScoreRoute route = SCORE_F32MFMA;
+    void *bsplit = nullptr, *slab = nullptr;
+    // name: the call that refuses, in its own words, an M no 128-row slab holds (NULL: no refusal, as asnorm_stats always ran)
+    int open(const char* name) {
+        ldk = (M + 3) & ~(int64_t)3;                                  // row stride of the slab (16-byte rows for the DMA GEMM)
+        const int64_t max_m = (((int64_t)1 << 31) / (128 * 4)) & ~(int64_t)3;
+        if (name && ldk > max_m)
+            SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "%s: D = %d takes the slab route, whose 128-row slab holds at most M = %lld gallery rows (M = %lld)", name, D,
+                    (long long)max_m, (long long)M);
+        slab_rows = std::min<int64_t>(N, std::max<int64_t>(128, ((int64_t)1 << 31) / (ldk * 4)));
+        route = score_route(h, dA, slab_rows, dB, M, D);              // (every slab starts r0 * D * 4 bytes into A: the same alignment)
+        if (int rc = split_b(h, route, dB, M, D, &bsplit)) return rc;
+        return scratch(h, svhip_handle::SCR_SLAB, (size_t)slab_rows * ldk * 4, &slab);
+    }
+    // per slab: score_gemm under `label` (gemm = false: the call's one slab still holds its scores), then rows_fn(r0, rows, slab, ldk)
+    int pass(const char* label, bool gemm, const std::function<int(int64_t, int64_t, const float*, int64_t)>& rows_fn) {
+        for (int64_t r0 = 0; r0 < N; r0 += slab_rows) {
+            const int64_t rows = std::min(slab_rows, N - r0);
+            if (gemm)
+                if (int rc = score_gemm(h, label, dA + r0 * D, rows, dB, M, D, (float*)slab, ldk, route, bsplit)) return rc;
+            if (int rc = rows_fn(r0, rows, (const float*)slab, ldk)) return rc;
+        }
+        return SVHIP_OK;
+    }
+};
+}  // namespace
+
 // the slab path: cohort scores of `rows` embeddings into an HBM scratch (rows x K fp32), slab by slab, reduced per row.
 // Used for shapes the fused kernel does not take (small cohorts, top > 256, other embedding widths, F32X3 handles) and for
 // the embeddings the fused kernel flags.
 static int asnorm_stats_slab(svhip_handle* h, const float* dE, int64_t N, int D, const float* dC, int K, int top, float* dM, float* dS) {
-    const int64_t ldk = (K + 3) & ~3;                             // row stride of the slab (16-byte rows for the DMA GEMM)
-    const int64_t slab_rows = std::min<int64_t>(N, std::max<int64_t>(128, ((int64_t)1 << 31) / (ldk * 4)));
-    void* csplit = nullptr;
-    void* slab = nullptr;
-    int rc;
-    const ScoreRoute route = score_route(h, dE, slab_rows, dC, K, D);       // (every slab starts r0 * D * 4 bytes into E: the same alignment)
-    if ((rc = split_b(h, route, dC, K, D, &csplit))) return rc;
-    if ((rc = scratch(h, svhip_handle::SCR_SLAB, (size_t)slab_rows * ldk * 4, &slab))) return rc;
-    for (int64_t r0 = 0; r0 < N; r0 += slab_rows) {
-        const int64_t rows = std::min(slab_rows, N - r0);
-        rc = score_gemm(h, "asnorm_cohort_gemm", dE + r0 * D, rows, dC, K, D, (float*)slab, ldk, route, csplit);
-        if (!rc) {
-            // the profile label names the form of the selection the launcher takes for this shape
-            static const char* const labels[4] = {"asnorm_topk_reg8", "asnorm_topk_reg24", "asnorm_topk_lds", "asnorm_topk_global"};
-            rc = run(h, labels[topk_stats_form((const float*)slab, K, (int)ldk)], 0,
-                     [&]() { return launch_topk_stats((const float*)slab, rows, K, (int)ldk, top, dM + r0, dS + r0, h->stream); });
-        }
-        if (rc) return rc;
-    }
-    return SVHIP_OK;
+    SlabWalk w{h, dE, N, dC, K, D};
+    if (int rc = w.open(nullptr)) return rc;
+    return w.pass("asnorm_cohort_gemm", true, [&](int64_t r0, int64_t rows, const float* slab, int64_t ldk) {
+        // the profile label names the form of the selection the launcher takes for this shape
+        static const char* const labels[4] = {"asnorm_topk_reg8", "asnorm_topk_reg24", "asnorm_topk_lds", "asnorm_topk_global"};
+        return run(h, labels[topk_stats_form(slab, K, (int)ldk)], 0, [&]() { return launch_topk_stats(slab, rows, K, (int)ldk, top, dM + r0, dS + r0, h->stream); });
+    });
 }
 
 int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, const float* cohort, int32_t K, int32_t top,
@@ -444,66 +468,101 @@ int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, co
     return SVHIP_OK;
 }
 
-// ---- 1:N identification: the k best gallery rows per query (score_topk.hip) ---------------------------------------------------------------
-// The route is decided from the shape and the pointers alone:
-//   fused  D = 192 / 256, 16-byte aligned operands: no score reaches memory.  Queries go in chunks of 16 384; the whole 128-query tiles of a
-//          chunk run the shared-block form of the kernel, a last tile of at most 32 queries the form whose waves walk different gallery
-//          blocks; each launch cuts the gallery into enough slices to fill the chip (within 256 MiB of list scratch) and is followed by its merge
-//   slab   every other width: score_gemm writes slabs of query rows (at most 2 GiB, at least 128 rows, as asnorm_stats_slab), a row kernel selects
-// The normalised call (svhip_score_topk_norm) takes the same routes with the same chunks, slices and slabs: `qc` / `gc` are its tables of
-// (a, b) pairs (score_topk_coef; qc already offset to the first row of dQ), both NULL for the plain call.
-static int topk_fused_part(svhip_handle* h, const float* dQ, int64_t rows, const float* dG, int64_t M, int D, int k, bool few, float* dS, int32_t* dI,
+// ---- the search calls: top-k (score_topk.hip) and threshold search (score_above.hip) over one gallery walk (score_walk.h) ----------------
+// Both decide their route from the shape and the pointers alone:
+//   fused  D = 192 / 256, 16-byte aligned operands: no score reaches memory.  fused_plan cuts the call into launches
+//   slab   every other width: SlabWalk writes slabs of query rows, a row kernel selects
+// and the calls with statistics take the same routes with the same parts and slabs: `qc` / `gc` are their tables of (a, b) pairs.
+namespace {
+// One launch of the fused route: queries [r0, r0 + rows) of the call, `slices` gallery slices of `per` blocks of 32 rows.
+struct FusedPart { int64_t r0, rows; bool few; int slices, per; };
+
+// Queries go in chunks of 16 384; the whole 128-query tiles of a chunk run the shared-block form of the walk (MANY), a last tile of at most
+// 32 queries the form whose waves walk different gallery blocks (FEW).  Each launch cuts the gallery into enough slices to fill the chip:
+// two workgroups per CU (FEW: one, since every wave of it keeps lists of its own), a workgroup walks at least 8 (FEW: 16) gallery blocks.
+// slice_bytes[few]: the scratch a launch needs per (query, slice), held within 256 MiB per launch (0: the caller's scratch has no such cap).
+void fused_plan(int64_t N, int64_t M, int num_cu, const int64_t (&slice_bytes)[2], std::vector<FusedPart>& parts) {
+    constexpr int64_t CHUNK = 16384;
+    const int64_t nb_all = (M + 31) / 32;
+    const int cu = num_cu > 0 ? num_cu : 256;
+    auto add = [&](int64_t r0, int64_t rows, bool few) {
+        const int64_t tiles = few ? 1 : (rows + 127) / 128;
+        int64_t slices = ((few ? 1 : 2) * (int64_t)cu + tiles - 1) / tiles;
+        const int64_t min_blocks = few ? 16 : 8;
+        slices = std::min(slices, (nb_all + min_blocks - 1) / min_blocks);
+        if (slice_bytes[few]) slices = std::min(slices, std::max<int64_t>(1, ((int64_t)256 << 20) / (rows * slice_bytes[few])));
+        slices = std::max<int64_t>(1, std::min<int64_t>(slices, 65535));
+        const int64_t per = (nb_all + slices - 1) / slices;
+        parts.push_back({r0, rows, few, (int)((nb_all + per - 1) / per), (int)per});
+    };
+    for (int64_t r0 = 0; r0 < N; r0 += CHUNK) {
+        const int64_t rows = std::min(CHUNK, N - r0);
+        const int64_t tail = rows % 128;
+        const int64_t n_few = (tail >= 1 && tail <= 32) ? tail : 0, n_many = rows - n_few;
+        if (n_many) add(r0, n_many, false);
+        if (n_few) add(r0 + n_many, n_few, true);
+    }
+}
+
+// The coefficient tables of a call with statistics ({q_mu, q_sigma, g_mu, g_sigma}), once per call, in SCR_COEF:
+// [queries (N) | gallery (whole blocks of 32 rows), on a 16-byte boundary]
+int coef_tables(svhip_handle* h, const char* label, const float* const* stats, int64_t N, int64_t M, bool din, const float2** qc, const float2** gc) {
+    const int slot[4] = {svhip_handle::SCR_IN2, svhip_handle::SCR_IN3, svhip_handle::SCR_IN4, svhip_handle::SCR_IN5};
+    const void* d[4];
+    for (int i = 0; i < 4; ++i) {
+        TempBuf t{h, slot[i]};
+        if (int rc = t.in(stats[i], (size_t)(i < 2 ? N : M) * 4, din, &d[i])) return rc;
+    }
+    const size_t q_bytes = ((size_t)N * 8 + 15) & ~(size_t)15;
+    void* c = nullptr;
+    if (int rc = scratch(h, svhip_handle::SCR_COEF, q_bytes + (size_t)score_topk_coef_rows(M) * 8, &c)) return rc;
+    float2* qcw = reinterpret_cast<float2*>(c);
+    float2* gcw = reinterpret_cast<float2*>((char*)c + q_bytes);
+    *qc = qcw; *gc = gcw;
+    return run(h, label, 0, [&]() {
+        return launch_score_topk_coef((const float*)d[0], (const float*)d[1], N, (const float*)d[2], (const float*)d[3], M, qcw, gcw, h->stream);
+    });
+}
+
+// The end of a call whose results are enqueued (rc: what the call came to so far): wait unless the call is asynchronous, report what the
+// stream reports under the call's name, and release the scratch that is not kept between calls.
+int search_end(svhip_handle* h, const char* name, int rc, bool din, bool dout, int32_t flags) {
+    if (rc || !(din && dout && (flags & SVHIP_ASYNC))) {
+        const hipError_t e = hipStreamSynchronize(h->stream);
+        if (!rc && e != hipSuccess) { h->err = std::string(name) + ": " + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
+        release_big_scratch(h, !din || !dout);
+    }
+    return rc;
+}
+}  // namespace
+
+// one part of score_topk's fused route: its lists (SCR_TOPK, sized for this launch alone), the launch, its merge.  dQ, dS, dI, qc: the call's
+static int topk_fused_part(svhip_handle* h, const FusedPart& t, const float* dQ, const float* dG, int64_t M, int D, int k, float* dS, int32_t* dI,
                            const float2* qc, const float2* gc) {
     const int cap = score_topk_cap(k);
-    const int64_t nb_all = (M + 31) / 32;
-    const int64_t tiles = few ? 1 : (rows + 127) / 128;
-    const int per_slice_lists = few ? 8 : 2;
-    const int cu = h->num_cu > 0 ? h->num_cu : 256;
-    // two workgroups per CU; few: one, since every wave of it keeps lists of its own for the merge to read (8 per slice)
-    int64_t slices = ((few ? 1 : 2) * (int64_t)cu + tiles - 1) / tiles;
-    const int64_t min_blocks = few ? 16 : 8;                      // gallery blocks a workgroup should at least walk
-    slices = std::min(slices, (nb_all + min_blocks - 1) / min_blocks);
-    const int64_t slice_bytes = rows * per_slice_lists * ((int64_t)cap * 8 + 4);
-    slices = std::min(slices, std::max<int64_t>(1, ((int64_t)256 << 20) / slice_bytes));
-    slices = std::max<int64_t>(1, std::min<int64_t>(slices, 65535));
-    const int64_t per = (nb_all + slices - 1) / slices;
-    slices = (nb_all + per - 1) / per;
     ScoreTopkParams p;
-    p.Q = dQ; p.N = rows; p.G = dG; p.M = M; p.k = k; p.cap = cap; p.per = (int)per; p.nlists = (int)slices * per_slice_lists;
+    p.Q = dQ + t.r0 * D; p.N = t.rows; p.G = dG; p.M = M; p.k = k; p.cap = cap; p.per = t.per; p.nlists = t.slices * (t.few ? 8 : 2);
     void* s = nullptr;
-    const size_t list_bytes = (size_t)rows * p.nlists * cap * 8;
-    if (int rc = scratch(h, svhip_handle::SCR_TOPK, list_bytes + (size_t)rows * p.nlists * 4, &s)) return rc;
+    const size_t list_bytes = (size_t)t.rows * p.nlists * cap * 8;
+    if (int rc = scratch(h, svhip_handle::SCR_TOPK, list_bytes + (size_t)t.rows * p.nlists * 4, &s)) return rc;
     p.lists = reinterpret_cast<uint2*>(s);
     p.cnt = reinterpret_cast<int32_t*>((char*)s + list_bytes);
-    p.qcoef = qc; p.gcoef = gc;
-    if (int rc = run(h, qc ? "score_topk_norm" : "score_topk", 2.0 * rows * M * D, [&]() { return launch_score_topk(p, D, few, (int)slices, h->stream); })) return rc;
-    return run(h, "score_topk_merge", 0, [&]() { return launch_score_topk_merge(p.lists, p.cnt, rows, p.nlists, cap, k, dS, dI, h->stream); });
+    p.qcoef = qc ? qc + t.r0 : nullptr; p.gcoef = gc;
+    if (int rc = run(h, qc ? "score_topk_norm" : "score_topk", 2.0 * t.rows * M * D, [&]() { return launch_score_topk(p, D, t.few, t.slices, h->stream); })) return rc;
+    return run(h, "score_topk_merge", 0, [&]() {
+        return launch_score_topk_merge(p.lists, p.cnt, t.rows, p.nlists, cap, k, dS + t.r0 * k, dI + t.r0 * k, h->stream);
+    });
 }
 
 static int topk_slab(svhip_handle* h, const char* name, const float* dQ, int64_t N, const float* dG, int64_t M, int D, int k, float* dS, int32_t* dI,
                      const float2* qc, const float2* gc) {
-    const int64_t ldk = (M + 3) & ~(int64_t)3;                    // row stride of the slab (16-byte rows for the DMA GEMM)
-    const int64_t max_m = (((int64_t)1 << 31) / (128 * 4)) & ~(int64_t)3;
-    if (ldk > max_m)
-        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "%s: D = %d takes the slab route, whose 128-row slab holds at most M = %lld gallery rows (M = %lld)", name, D,
-                (long long)max_m, (long long)M);
-    const int64_t slab_rows = std::min<int64_t>(N, std::max<int64_t>(128, ((int64_t)1 << 31) / (ldk * 4)));
-    void* gsplit = nullptr;
-    void* slab = nullptr;
-    int rc;
-    const ScoreRoute route = score_route(h, dQ, slab_rows, dG, M, D);       // (every slab starts r0 * D * 4 bytes into Q: the same alignment)
-    if ((rc = split_b(h, route, dG, M, D, &gsplit))) return rc;
-    if ((rc = scratch(h, svhip_handle::SCR_SLAB, (size_t)slab_rows * ldk * 4, &slab))) return rc;
-    for (int64_t r0 = 0; r0 < N; r0 += slab_rows) {
-        const int64_t rows = std::min(slab_rows, N - r0);
-        rc = score_gemm(h, "score_topk_gemm", dQ + r0 * D, rows, dG, M, D, (float*)slab, ldk, route, gsplit);
-        if (!rc)
-            rc = run(h, qc ? "score_topk_rows_norm" : "score_topk_rows", 0, [&]() {
-                return launch_score_topk_rows((const float*)slab, rows, M, ldk, k, dS + r0 * k, dI + r0 * k, h->stream, qc ? qc + r0 : nullptr, gc);
-            });
-        if (rc) return rc;
-    }
-    return SVHIP_OK;
+    SlabWalk w{h, dQ, N, dG, M, D};
+    if (int rc = w.open(name)) return rc;
+    return w.pass("score_topk_gemm", true, [&](int64_t r0, int64_t rows, const float* slab, int64_t ldk) {
+        return run(h, qc ? "score_topk_rows_norm" : "score_topk_rows", 0, [&]() {
+            return launch_score_topk_rows(slab, rows, M, ldk, k, dS + r0 * k, dI + r0 * k, h->stream, qc ? qc + r0 : nullptr, gc);
+        });
+    });
 }
 
 // both entry points: `stats` = {q_mu, q_sigma, g_mu, g_sigma} for the normalised call, NULL for the plain one; `name` prefixes the messages
@@ -530,38 +589,14 @@ static int score_topk_impl(svhip_handle* h, const char* name, const float* Q, in
     if ((rc = tS.out(out_score, (size_t)N * k * 4, dout, &dS))) return rc;
     if ((rc = tI.out(out_index, (size_t)N * k * 4, dout, &dI))) return rc;
     const float2 *qc = nullptr, *gc = nullptr;
-    if (stats) {
-        // the coefficient tables, once per call: [queries (N) | gallery (whole blocks of 32 rows), on a 16-byte boundary]
-        const int slot[4] = {svhip_handle::SCR_IN2, svhip_handle::SCR_IN3, svhip_handle::SCR_IN4, svhip_handle::SCR_IN5};
-        const void* d[4];
-        for (int i = 0; i < 4; ++i) {
-            TempBuf t{h, slot[i]};
-            if ((rc = t.in(stats[i], (size_t)(i < 2 ? N : M) * 4, din, &d[i]))) return rc;
-        }
-        const size_t q_bytes = ((size_t)N * 8 + 15) & ~(size_t)15;
-        void* c = nullptr;
-        if ((rc = scratch(h, svhip_handle::SCR_COEF, q_bytes + (size_t)score_topk_coef_rows(M) * 8, &c))) return rc;
-        float2* qcw = reinterpret_cast<float2*>(c);
-        float2* gcw = reinterpret_cast<float2*>((char*)c + q_bytes);
-        if ((rc = run(h, "score_topk_coef", 0, [&]() {
-                 return launch_score_topk_coef((const float*)d[0], (const float*)d[1], N, (const float*)d[2], (const float*)d[3], M, qcw, gcw, h->stream);
-             }))) return rc;
-        qc = qcw; gc = gcw;
-    }
+    if (stats && (rc = coef_tables(h, "score_topk_coef", stats, N, M, din, &qc, &gc))) return rc;
     const bool aligned = ((reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dG)) & 15) == 0;
     if (score_topk_fused_supported(D) && aligned) {
-        constexpr int64_t CHUNK = 16384;
-        for (int64_t r0 = 0; r0 < N && !rc; r0 += CHUNK) {
-            const int64_t rows = std::min(CHUNK, N - r0);
-            const int64_t tail = rows % 128;
-            const int64_t n_few = (tail >= 1 && tail <= 32) ? tail : 0, n_many = rows - n_few;
-            const float* q = (const float*)dQ + r0 * D;
-            const float2* qcr = qc ? qc + r0 : nullptr;
-            if (n_many) rc = topk_fused_part(h, q, n_many, (const float*)dG, M, D, k, false, (float*)dS + r0 * k, (int32_t*)dI + r0 * k, qcr, gc);
-            if (!rc && n_few)
-                rc = topk_fused_part(h, q + n_many * D, n_few, (const float*)dG, M, D, k, true, (float*)dS + (r0 + n_many) * k, (int32_t*)dI + (r0 + n_many) * k,
-                                     qc ? qcr + n_many : nullptr, gc);
-        }
+        const int64_t list_bytes = (int64_t)score_topk_cap(k) * 8 + 4;      // a list and its count; 2 lists per slice, FEW 8
+        std::vector<FusedPart> parts;
+        fused_plan(N, M, h->num_cu, {2 * list_bytes, 8 * list_bytes}, parts);
+        for (const FusedPart& t : parts)
+            if ((rc = topk_fused_part(h, t, (const float*)dQ, (const float*)dG, M, D, k, (float*)dS, (int32_t*)dI, qc, gc))) break;
     } else {
         rc = topk_slab(h, name, (const float*)dQ, N, (const float*)dG, M, D, k, (float*)dS, (int32_t*)dI, qc, gc);
     }
@@ -570,12 +605,7 @@ static int score_topk_impl(svhip_handle* h, const char* name, const float* Q, in
         if (e == hipSuccess) e = hipMemcpyAsync(out_index, dI, (size_t)N * k * 4, hipMemcpyDeviceToHost, h->stream);
         if (e != hipSuccess) { h->err = std::string(name) + ": copy of the results failed: " + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
     }
-    if (rc || !(din && dout && (flags & SVHIP_ASYNC))) {
-        const hipError_t e = hipStreamSynchronize(h->stream);
-        if (!rc && e != hipSuccess) { h->err = std::string(name) + ": " + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
-        release_big_scratch(h, !din || !dout);
-    }
-    return rc;
+    return search_end(h, name, rc, din, dout, flags);
 }
 
 int svhip_score_topk(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, int32_t k, float* out_score,
@@ -590,9 +620,9 @@ int svhip_score_topk_norm(svhip_handle* h, const float* Q, int64_t N, const floa
 }
 
 // ---- threshold search: every gallery row at or above a score, as CSR rows (score_above.hip) -----------------------------------------------
-// Routes, query chunks, the FEW / MANY split of a chunk and the slab sizes are score_topk's.  Both entry points count first (every launch of
-// the call, into one scratch: a few list counts per row); fill then reads ONE word back - the first row whose recount is not what row_ptr
-// says - and writes only if there is none, so no entry outside [0, row_ptr[N]) is ever touched.
+// Routes, fused_plan's parts and the slabs are score_topk's.  Both entry points count first (every launch of the call, into one scratch: a
+// few list counts per row); fill then reads ONE word back - the first row whose recount is not what row_ptr says - and writes only if there
+// is none, so no entry outside [0, row_ptr[N]) is ever touched.
 namespace {
 struct AboveArgs {
     const float *dQ, *dG;
@@ -608,7 +638,6 @@ struct AboveArgs {
     float* dScore;
     int64_t total;                // fill: row_ptr[N]
 };
-struct AbovePart { int64_t r0, rows; bool few; int slices, per, nl; size_t first; };      // first: its place in the list-count scratch
 
 // fill: the word the scan / row kernels lowered -> OK, or the refusal that names the row
 int above_guard(svhip_handle* h, const unsigned long long* bad) {
@@ -623,28 +652,14 @@ int above_guard(svhip_handle* h, const unsigned long long* bad) {
 
 int above_fused(svhip_handle* h, const AboveArgs& a) {
     const bool fill = a.dRowPtr != nullptr;
-    const int64_t nb_all = (a.M + 31) / 32;
-    const int cu = h->num_cu > 0 ? h->num_cu : 256;
-    std::vector<AbovePart> parts;
+    std::vector<FusedPart> parts;
+    fused_plan(a.N, a.M, h->num_cu, {0, 0}, parts);
+    auto nl = [](const FusedPart& t) { return t.slices * (t.few ? 4 : 1); };      // lists per query
+    std::vector<size_t> first;                                                    // a part's place in the list-count scratch
     size_t entries = 0;
-    auto add = [&](int64_t r0, int64_t rows, bool few) {
-        // as topk_fused_part: two workgroups per CU (few: one), and a workgroup walks at least 8 (16) gallery blocks
-        const int64_t tiles = few ? 1 : (rows + 127) / 128;
-        int64_t slices = ((few ? 1 : 2) * (int64_t)cu + tiles - 1) / tiles;
-        const int64_t min_blocks = few ? 16 : 8;
-        slices = std::max<int64_t>(1, std::min<int64_t>(std::min(slices, (nb_all + min_blocks - 1) / min_blocks), 65535));
-        const int64_t per = (nb_all + slices - 1) / slices;
-        slices = (nb_all + per - 1) / per;
-        parts.push_back({r0, rows, few, (int)slices, (int)per, (int)slices * (few ? 4 : 1), entries});
-        entries += (size_t)rows * parts.back().nl;
-    };
-    constexpr int64_t CHUNK = 16384;
-    for (int64_t r0 = 0; r0 < a.N; r0 += CHUNK) {
-        const int64_t rows = std::min(CHUNK, a.N - r0);
-        const int64_t tail = rows % 128;
-        const int64_t n_few = (tail >= 1 && tail <= 32) ? tail : 0, n_many = rows - n_few;
-        if (n_many) add(r0, n_many, false);
-        if (n_few) add(r0 + n_many, n_few, true);
+    for (const FusedPart& t : parts) {
+        first.push_back(entries);
+        entries += (size_t)t.rows * nl(t);
     }
     // [the guard's word (256 bytes) | list counts (int32) | fill: list offsets (int64)]
     const size_t cnt_bytes = (entries * 4 + 255) & ~(size_t)255;
@@ -654,26 +669,29 @@ int above_fused(svhip_handle* h, const AboveArgs& a) {
     int32_t* lcnt = reinterpret_cast<int32_t*>((char*)s + 256);
     int64_t* loff = reinterpret_cast<int64_t*>((char*)s + 256 + cnt_bytes);
     if (fill) SV_HIP(h, hipMemsetAsync(bad, 0xff, 8, h->stream));
-    auto params = [&](const AbovePart& t) {
+    auto params = [&](size_t i) {
+        const FusedPart& t = parts[i];
         ScoreAboveParams p;
         p.Q = a.dQ + t.r0 * a.D; p.N = t.rows; p.G = a.dG; p.M = a.M; p.thr = a.thr; p.upper = a.upper; p.row_base = a.q_base + t.r0;
-        p.per = t.per; p.nl = t.nl; p.lcnt = lcnt + t.first; p.loff = loff + t.first; p.out_index = a.dIndex; p.out_score = a.dScore;
+        p.per = t.per; p.nl = nl(t); p.lcnt = lcnt + first[i]; p.loff = loff + first[i]; p.out_index = a.dIndex; p.out_score = a.dScore;
         p.qcoef = a.qc ? a.qc + t.r0 : nullptr; p.gcoef = a.gc;
         return p;
     };
-    for (const AbovePart& t : parts) {
-        const ScoreAboveParams p = params(t);
+    for (size_t i = 0; i < parts.size(); ++i) {
+        const FusedPart& t = parts[i];
+        const ScoreAboveParams p = params(i);
         if (int rc = run(h, "score_above_count", 2.0 * t.rows * a.M * a.D, [&]() { return launch_score_above(p, a.D, t.few, t.slices, false, h->stream); })) return rc;
         if (int rc = run(h, "score_above_scan", 0, [&]() {
-                return launch_score_above_scan(p.lcnt, t.rows, t.nl, fill ? nullptr : a.dCount + t.r0, fill ? a.dRowPtr + t.r0 : nullptr, t.r0,
-                                               fill ? loff + t.first : nullptr, fill ? bad : nullptr, h->stream);
+                return launch_score_above_scan(p.lcnt, t.rows, p.nl, fill ? nullptr : a.dCount + t.r0, fill ? a.dRowPtr + t.r0 : nullptr, t.r0,
+                                               fill ? loff + first[i] : nullptr, fill ? bad : nullptr, h->stream);
             })) return rc;
     }
     if (!fill) return SVHIP_OK;
     if (int rc = above_guard(h, bad)) return rc;
     if (a.total == 0) return SVHIP_OK;
-    for (const AbovePart& t : parts) {
-        const ScoreAboveParams p = params(t);
+    for (size_t i = 0; i < parts.size(); ++i) {
+        const FusedPart& t = parts[i];
+        const ScoreAboveParams p = params(i);
         if (int rc = run(h, "score_above_fill", 2.0 * t.rows * a.M * a.D, [&]() { return launch_score_above(p, a.D, t.few, t.slices, true, h->stream); })) return rc;
     }
     return SVHIP_OK;
@@ -681,39 +699,28 @@ int above_fused(svhip_handle* h, const AboveArgs& a) {
 
 int above_slab(svhip_handle* h, const AboveArgs& a) {
     const bool fill = a.dRowPtr != nullptr;
-    const int64_t ldk = (a.M + 3) & ~(int64_t)3;                  // row stride of the slab (16-byte rows for the DMA GEMM)
-    const int64_t max_m = (((int64_t)1 << 31) / (128 * 4)) & ~(int64_t)3;
-    if (ldk > max_m)
-        SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "score_above: D = %d takes the slab route, whose 128-row slab holds at most M = %lld gallery rows (M = %lld)", a.D,
-                (long long)max_m, (long long)a.M);
-    const int64_t slab_rows = std::min<int64_t>(a.N, std::max<int64_t>(128, ((int64_t)1 << 31) / (ldk * 4)));
-    void *gsplit = nullptr, *slab = nullptr, *w = nullptr;
+    SlabWalk w{h, a.dQ, a.N, a.dG, a.M, a.D};
+    void* word = nullptr;
     int rc;
-    const ScoreRoute route = score_route(h, a.dQ, slab_rows, a.dG, a.M, a.D);       // (every slab starts r0 * D * 4 bytes into Q: the same alignment)
-    if ((rc = split_b(h, route, a.dG, a.M, a.D, &gsplit))) return rc;
-    if ((rc = scratch(h, svhip_handle::SCR_SLAB, (size_t)slab_rows * ldk * 4, &slab))) return rc;
-    if ((rc = scratch(h, svhip_handle::SCR_TOPK, 256, &w))) return rc;
-    unsigned long long* bad = reinterpret_cast<unsigned long long*>(w);
+    if ((rc = w.open("score_above"))) return rc;
+    if ((rc = scratch(h, svhip_handle::SCR_TOPK, 256, &word))) return rc;
+    unsigned long long* bad = reinterpret_cast<unsigned long long*>(word);
     if (fill) SV_HIP(h, hipMemsetAsync(bad, 0xff, 8, h->stream));
     // one pass over the slabs: count, compare with row_ptr (check) or write
     auto pass = [&](bool check, bool gemm) {
-        for (int64_t r0 = 0; r0 < a.N; r0 += slab_rows) {
-            const int64_t rows = std::min(slab_rows, a.N - r0);
-            if (gemm && (rc = score_gemm(h, "score_above_gemm", a.dQ + r0 * a.D, rows, a.dG, a.M, a.D, (float*)slab, ldk, route, gsplit))) return rc;
-            rc = run(h, "score_above_rows", 0, [&]() {
-                return launch_score_above_rows((const float*)slab, rows, a.M, ldk, a.thr, a.upper, a.q_base + r0, a.qc ? a.qc + r0 : nullptr, a.gc,
+        return w.pass("score_above_gemm", gemm, [&](int64_t r0, int64_t rows, const float* slab, int64_t ldk) {
+            return run(h, "score_above_rows", 0, [&]() {
+                return launch_score_above_rows(slab, rows, a.M, ldk, a.thr, a.upper, a.q_base + r0, a.qc ? a.qc + r0 : nullptr, a.gc,
                                                fill ? nullptr : a.dCount + r0, fill ? a.dRowPtr + r0 : nullptr, r0, check ? bad : nullptr,
                                                fill && !check ? a.dIndex : nullptr, fill && !check ? a.dScore : nullptr, h->stream);
             });
-            if (rc) return rc;
-        }
-        return (int)SVHIP_OK;
+        });
     };
     if (!fill) return pass(false, true);
     if ((rc = pass(true, true))) return rc;
     if ((rc = above_guard(h, bad))) return rc;
     if (a.total == 0) return SVHIP_OK;
-    return pass(false, slab_rows < a.N);                            // (one slab: its scores are still there)
+    return pass(false, w.slab_rows < a.N);                          // (one slab: its scores are still there)
 }
 
 int score_above_impl(svhip_handle* h, bool fill, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, float thr, const float* const* stats,
@@ -760,24 +767,7 @@ int score_above_impl(svhip_handle* h, bool fill, const float* Q, int64_t N, cons
         if ((rc = tI.out(out_count, (size_t)N * 8, dout, &dC))) return rc;
         a.dCount = (int64_t*)dC;
     }
-    if (n_stats) {
-        // the coefficient tables of score_topk_norm, once per call: [queries (N) | gallery (whole blocks of 32 rows), on a 16-byte boundary]
-        const int slot[4] = {svhip_handle::SCR_IN2, svhip_handle::SCR_IN3, svhip_handle::SCR_IN4, svhip_handle::SCR_IN5};
-        const void* d[4];
-        for (int i = 0; i < 4; ++i) {
-            TempBuf t{h, slot[i]};
-            if ((rc = t.in(stats[i], (size_t)(i < 2 ? N : M) * 4, din, &d[i]))) return rc;
-        }
-        const size_t q_bytes = ((size_t)N * 8 + 15) & ~(size_t)15;
-        void* c = nullptr;
-        if ((rc = scratch(h, svhip_handle::SCR_COEF, q_bytes + (size_t)score_topk_coef_rows(M) * 8, &c))) return rc;
-        float2* qcw = reinterpret_cast<float2*>(c);
-        float2* gcw = reinterpret_cast<float2*>((char*)c + q_bytes);
-        if ((rc = run(h, "score_above_coef", 0, [&]() {
-                 return launch_score_topk_coef((const float*)d[0], (const float*)d[1], N, (const float*)d[2], (const float*)d[3], M, qcw, gcw, h->stream);
-             }))) return rc;
-        a.qc = qcw; a.gc = gcw;
-    }
+    if (n_stats && (rc = coef_tables(h, "score_above_coef", stats, N, M, din, &a.qc, &a.gc))) return rc;
     const bool aligned = ((reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dG)) & 15) == 0;
     rc = score_topk_fused_supported(D) && aligned ? above_fused(h, a) : above_slab(h, a);
     if (!rc && !dout) {
@@ -789,12 +779,7 @@ int score_above_impl(svhip_handle* h, bool fill, const float* Q, int64_t N, cons
         }
         if (e != hipSuccess) { h->err = std::string("score_above: copy of the results failed: ") + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
     }
-    if (rc || !(din && dout && (flags & SVHIP_ASYNC))) {
-        const hipError_t e = hipStreamSynchronize(h->stream);
-        if (!rc && e != hipSuccess) { h->err = std::string("score_above: ") + hipGetErrorString(e); rc = SVHIP_ERR_HIP; }
-        release_big_scratch(h, !din || !dout);
-    }
-    return rc;
+    return search_end(h, "score_above", rc, din, dout, flags);
 }
 }  // namespace
 

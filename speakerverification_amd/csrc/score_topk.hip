@@ -4,19 +4,15 @@
 // compare ONE composite key, (okey(score) << 32) | ~index, with okey an order-preserving map of the floats in which NaN is the smallest
 // key and -0 is +0: a total order, no tie case anywhere.
 //
-//   score_topk_kernel   the MFMA loop of asnorm_fused_kernel (a wave owns 32 queries as the B operand of v_mfma_f32_32x32x2_f32, exact
-//                       fp32; gallery blocks of 32 rows are the A operand, so a lane's 16 accumulators are 16 gallery scores of ONE query
-//                       and the selection is lane-local).  Grid: query tiles x gallery slices.  Every lane keeps the k best of the rows it
-//                       saw in a list of (score bits, index) pairs in handle-owned scratch (L2): a score above the lane's threshold is
-//                       appended; when a list cannot take another block the wave selects that list's k-th key (32-step bitwise search),
-//                       compacts the list to k entries in place and raises the threshold.  A lane meets its rows in ascending index order
-//                       and the compaction is stable, so "equal score, later" is always "equal score, higher index": the threshold test
-//                       is on the score alone, strict, and nothing at or above a list's own k-th composite key is ever dropped.
-//                       MANY form: a workgroup holds 128 queries, its four waves share each gallery block through the double-buffered,
-//                       XOR-swizzled 16-byte LDS-DMA image.  FEW form (a launch of at most 32 queries): nothing is shared, so the four
-//                       waves walk DIFFERENT blocks of the slice and read their A fragments straight from global memory (every byte of
-//                       the gallery is read once either way).  Both forms issue the same MFMAs on the same operands in the same order:
-//                       a score depends on its query row and its gallery row only, bit for bit.
+//   score_topk_kernel   the gallery walk of score_walk.h (shared with score_above.hip: a lane is handed 16 gallery scores of ONE query per
+//                       block of 32 gallery rows, in ascending index; grid: query tiles x gallery slices) with the selection as its
+//                       epilogue, which is lane-local.  Every lane keeps the k best of the rows it saw in a list of (score bits, index)
+//                       pairs in handle-owned scratch (L2): a score above the lane's threshold is appended; when a list cannot take
+//                       another block the wave selects that list's k-th key (32-step bitwise search), compacts the list to k entries in
+//                       place and raises the threshold.  A lane meets its rows in ascending index order and the compaction is stable, so
+//                       "equal score, later" is always "equal score, higher index": the threshold test is on the score alone, strict,
+//                       and nothing at or above a list's own k-th composite key is ever dropped.  FEW deals the slice's blocks to the
+//                       four waves round robin: each wave has lists of its own, their order does not matter to the merge.
 //   score_topk_merge    one workgroup per query: the k largest composite keys of all its lists, in order (k rounds of a block-wide max
 //                       below the previous one).
 //   score_topk_rows     the slab route's row kernel: the same k rounds over one row of a score slab.
@@ -25,13 +21,11 @@
 #include "common.h"
 #include "kernels.h"
 #include "score_select.h"
+#include "score_walk.h"
 
 namespace svhip {
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
 
 // order-preserving key of a score: NaN -> 1 (below every number), numbers -> fkey + 1 (>= 0x00800000); 0 is no score at all
 __device__ __forceinline__ uint32_t okey(float v) { return v != v ? 1u : fkey(v + 0.0f) + 1u; }
@@ -92,57 +86,21 @@ __device__ __forceinline__ void compact_lists(unsigned long long need, uint2* lb
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 }
 
-// NORM (svhip_score_topk_norm): the lists hold t = fmaf(s, aq + ag, -(bq + bg)) in place of s; (aq, bq) are two registers of the lane
-// (a lane holds one query), (ag, bg) come from the gallery's table of interleaved pairs, which score_topk_coef writes out to whole blocks
-// of 32 rows (the entries past M repeat row M - 1: the last block reads in bounds, and its rows past M are masked as before).  The 16
-// rows of a lane are four runs of four: rows 32 b + 8 g + 4 h + 0..3, 32 contiguous bytes per g.
-//   FEW   the pairs are loaded into registers with the A fragments of the block, ahead of its MFMAs
-//   MANY  256 bytes per block travel with the block's DMA image into a ring of four LDS slots (block b + 1 is written while block b - 1
-//         is still read, so two slots are not enough); process reads them from LDS, where the whole half wave reads one address
-// The NORM = false instances are the kernels of svhip_score_topk, instruction for instruction.
+// The walk's epilogue (score_walk.h): a lane keeps the k best of the scores it is handed in its list.  NORM: the lists hold t in place of s.
 template <int D, bool FEW, bool NORM>
 __global__ __launch_bounds__(256, 2) void score_topk_kernel(ScoreTopkParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int CH = D / 4;                       // 16-byte chunks per gallery row
-    constexpr int BLK = 32 * D * 4;                 // one block of 32 gallery rows
-    constexpr int NDMA = 32 * CH / 256;             // DMA instructions per thread per block
-    constexpr int NG = CH / 2;                      // 16-byte A fragments per lane per block
-    static_assert(D % 64 == 0 && (32 * CH) % 256 == 0, "block image must be whole 4 KiB DMA rounds with 16-aligned chunk groups");
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 31, h = lane >> 5;         // query within the wave's 32 / half of the k range (and of the gallery rows of a block)
-    const int64_t row = FEW ? (int64_t)blockIdx.x * 32 + j : (int64_t)blockIdx.x * 128 + wave * 32 + j;
-    const bool valid = row < p.N;
-    const float* __restrict__ qrow = p.Q + (valid ? row : p.N - 1) * D;
-    float aq = 0.0f, bq = 0.0f;
-    if (NORM) {
-        const float2 c = p.qcoef[valid ? row : p.N - 1];
-        aq = c.x; bq = c.y;
-    }
-
-    // B operand: q[k], k = h * D/2 + s, for MFMA k-step s (both operands use the same k assignment)
-    float eb[D / 2];
-#pragma unroll
-    for (int t = 0; t < D / 8; ++t) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(qrow + h * (D / 2) + t * 4);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) eb[t * 4 + u] = v[u];
-    }
-
-    const int nb_all = (int)((p.M + 31) / 32);
-    const int b_first = min((int64_t)nb_all, (int64_t)blockIdx.y * p.per);
-    const int b_last = (int)min((int64_t)nb_all, (int64_t)b_first + p.per);
+    const ScoreLane g(FEW, p.N);
+    const int lane = g.lane, h = g.h;
+    const bool valid = g.valid;
 
     // this lane's list: one per (slice, [wave,] half) of its query
-    const int lid = FEW ? ((int)blockIdx.y * 4 + wave) * 2 + h : (int)blockIdx.y * 2 + h;
-    const int64_t lslot = (valid ? row : 0) * p.nlists + lid;
+    const int lid = FEW ? ((int)blockIdx.y * 4 + g.wave) * 2 + h : (int)blockIdx.y * 2 + h;
+    const int64_t lslot = (valid ? g.row : 0) * p.nlists + lid;
     uint2* lbase = p.lists + lslot * p.cap;
     int cnt = 0;
     uint32_t thr = 0;                               // a score is appended while its key is above thr (0: fewer than k seen, everything is)
 
-    // acc[r] = score of gallery row 32 b + (r & 3) + 8 (r >> 2) + 4 h against query j: ascending in r
     auto compact = [&](unsigned long long need) {
         if (p.cap <= 64) compact_lists<1>(need, lbase, cnt, thr, p.k, lane);
         else compact_lists<TK_NQ>(need, lbase, cnt, thr, p.k, lane);
@@ -167,128 +125,7 @@ __global__ __launch_bounds__(256, 2) void score_topk_kernel(ScoreTopkParams p) {
             }
         }
     };
-    // NORM: the lane's 16 scores through the statement, one rounding per step (svhip.h): the sum of the two a, the sum of the two b, the
-    // fused multiply-add.  gc: the pairs of rows 8 g + 4 h + 0..3 of the block in gc[2 g], gc[2 g + 1]
-    // (normalise8: scores 8 half .. 8 half + 7 with gc[0 .. 3] = the pairs of g = 2 half, 2 half + 1)
-    auto normalise8 = [&](f32x16& t, const f32x16& a, const f32x4* gc, int half) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const f32x4 c = gc[r >> 1];
-            const float ag = (r & 1) ? c[2] : c[0], bg = (r & 1) ? c[3] : c[1];
-            t[8 * half + r] = __builtin_fmaf(a[8 * half + r], aq + ag, -(bq + bg));
-        }
-    };
-    auto normalised = [&](const f32x16& a, const f32x4* gc) {
-        f32x16 t;
-        normalise8(t, a, gc, 0);
-        normalise8(t, a, gc + 4, 1);
-        return t;
-    };
-    auto mfma_step = [&](f32x16& acc, const f32x4& a4, int t) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u], eb[t * 4 + u], acc, 0, 0, 0);
-    };
-
-    if (FEW) {
-        // nothing to share: wave w takes blocks b_first + w, + 4, ..; a lane reads the half row it multiplies (rows past M repeat row M - 1)
-        for (int b = b_first + wave; b < b_last; b += 4) {
-            const int64_t r0 = (int64_t)b * 32;
-            const int lim = (int)min((int64_t)31, p.M - 1 - r0);
-            const float* __restrict__ arow = p.G + (r0 + min(j, lim)) * D + h * (D / 2);
-            f32x4 af[NG];
-#pragma unroll
-            for (int t = 0; t < NG; ++t) af[t] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(arow) + t);
-            f32x4 gc[8];
-            if (NORM) {
-                const f32x4* __restrict__ src = reinterpret_cast<const f32x4*>(p.gcoef + r0 + 4 * h);
-#pragma unroll
-                for (int g = 0; g < 4; ++g) { gc[2 * g] = src[4 * g]; gc[2 * g + 1] = src[4 * g + 1]; }
-            }
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-#pragma unroll
-            for (int t = 0; t < NG; ++t) mfma_step(acc, af[t], t);
-            if (NORM) process(normalised(acc, gc), b);
-            else process(acc, b);
-        }
-    } else {
-        // per-lane source offsets of the NDMA chunks this lane moves per block (block-invariant: row within the block, swizzled chunk)
-        int srow[NDMA], scol[NDMA];
-#pragma unroll
-        for (int q = 0; q < NDMA; ++q) {
-            const int pidx = q * 256 + tid;
-            const int i = pidx / CH, cs = pidx - i * CH;
-            srow[q] = i;
-            scol[q] = (cs ^ (i & 15)) * 4;            // the image is lane-linear: the swizzle goes on the source
-        }
-        auto issue = [&](int b, int buf) {
-            const int64_t r0 = (int64_t)b * 32;
-            const int lim = (int)min((int64_t)31, p.M - 1 - r0);       // the gallery's last block clamps its rows
-            const float* bb = p.G + r0 * D;
-#pragma unroll
-            for (int q = 0; q < NDMA; ++q) {
-                const float* s = bb + min(srow[q], lim) * D + scol[q];
-                __builtin_amdgcn_global_load_lds((gbl_void*)s, (lds_void*)(smem + buf * BLK + (q * 256 + wave * 64) * 16), 16, 0, 0);
-            }
-            if (NORM && wave == 0 && lane < 16)         // the block's 32 pairs: 16 lanes x 16 bytes, lane-linear like the image
-                __builtin_amdgcn_global_load_lds((gbl_void*)(p.gcoef + r0 + 2 * lane), (lds_void*)(smem + 2 * BLK + ((b - b_first) & 3) * 256), 16, 0, 0);
-        };
-        auto normalised_block = [&](const f32x16& a, int b) {      // with the pairs of block b from their LDS slot
-            const char* src = smem + 2 * BLK + ((b - b_first) & 3) * 256 + 32 * h;
-            f32x16 t;
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {                 // (two rounds of 16 registers: D = 256 has no 32 to spare here)
-                f32x4 gc[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) gc[u] = *reinterpret_cast<const f32x4*>(src + 128 * half + 64 * (u >> 1) + 16 * (u & 1));
-                normalise8(t, a, gc, half);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            return t;
-        };
-        auto rd = [&](int buf, int t) {
-            return *reinterpret_cast<const f32x4*>(smem + buf * BLK + j * (D * 4) + (((h * NG + t) ^ (j & 15)) << 4));      // gallery row j of the block
-        };
-        auto mfma_block = [&](int buf) {
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-            f32x4 a4 = rd(buf, 0);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int t = 0; t < NG; ++t) {
-                f32x4 nx = a4;
-                if (t + 1 < NG) nx = rd(buf, t + 1);       // one fragment ahead of its MFMAs, fenced (asnorm_fused.hip)
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_step(acc, a4, t);
-                __builtin_amdgcn_sched_barrier(0);
-                a4 = nx;
-            }
-            __builtin_amdgcn_s_setprio(0);
-            return acc;
-        };
-        if (b_first < b_last) {                                    // (workgroup-uniform)
-            issue(b_first, 0);
-            f32x16 accp;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) accp[r] = 0.0f;
-            for (int b = b_first; b < b_last; ++b) {
-                const int buf = (b - b_first) & 1;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // block b has landed (and the list stores of one block ago)
-                __syncthreads();                                       // ... for every wave; nobody still reads the other buffer
-                if (b + 1 < b_last) issue(b + 1, buf ^ 1);
-                if (b > b_first) {                                     // selection of the previous block
-                    if (NORM) process(normalised_block(accp, b - 1), b - 1);
-                    else process(accp, b - 1);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                accp = mfma_block(buf);
-            }
-            if (NORM) process(normalised_block(accp, b_last - 1), b_last - 1);
-            else process(accp, b_last - 1);
-        }
-    }
+    score_walk<D, FEW, NORM, false>(g, p.Q, p.N, p.G, p.M, p.per, p.qcoef, p.gcoef, smem, process);
     // what the merge reads: at most k entries per list
     const unsigned long long over = __ballot(valid && cnt > p.k);
     if (over) compact(over);
@@ -451,7 +288,7 @@ __global__ __launch_bounds__(256) void score_topk_coef_kernel(const float* __res
 template <int D, bool FEW, bool NORM>
 hipError_t launch_topk_d(const ScoreTopkParams& p, const dim3& grid, hipStream_t stream) {
     static DeviceOnce attr;
-    const int lds = FEW ? 0 : 2 * 32 * D * 4 + (NORM ? 4 * 256 : 0);
+    constexpr int lds = score_walk_lds_bytes(D, FEW, NORM);
     if (!FEW)
         if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(score_topk_kernel<D, FEW, NORM>), lds)) return e;
     hipLaunchKernelGGL((score_topk_kernel<D, FEW, NORM>), grid, dim3(256), lds, stream, p);
@@ -485,16 +322,12 @@ int score_topk_cap(int k) { return (2 * k + 32 + 63) / 64 * 64; }
 
 hipError_t launch_score_topk(const ScoreTopkParams& p, int D, bool few, int slices, hipStream_t stream) {
     if (p.N <= 0) return hipSuccess;
-    if (!score_topk_fused_supported(D) || !p.Q || !p.G || !p.lists || !p.cnt) return hipErrorInvalidValue;
-    if ((reinterpret_cast<uintptr_t>(p.Q) | reinterpret_cast<uintptr_t>(p.G)) & 15) return hipErrorInvalidValue;
-    if (p.k < 1 || p.k > SCORE_TOPK_MAX_K || p.k > p.M || p.M >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    if (!p.lists || !p.cnt) return hipErrorInvalidValue;
+    if (p.k < 1 || p.k > SCORE_TOPK_MAX_K || p.k > p.M) return hipErrorInvalidValue;
     if (p.cap != score_topk_cap(p.k) || p.cap > 64 * TK_NQ || p.cap < p.k + 17) return hipErrorInvalidValue;
-    if (slices < 1 || slices > 65535 || p.per < 1 || (int64_t)slices * p.per * 32 < p.M) return hipErrorInvalidValue;      // every gallery block belongs to a slice
     if (p.nlists != slices * (few ? 8 : 2)) return hipErrorInvalidValue;
-    if (few && p.N > 32) return hipErrorInvalidValue;
-    // the normalised form takes both tables (the gallery's is read in 16-byte pieces) or neither
-    if (!p.qcoef != !p.gcoef || (reinterpret_cast<uintptr_t>(p.gcoef) & 15)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)(few ? 1 : (p.N + 127) / 128), (unsigned)slices);
+    dim3 grid;
+    if (hipError_t e = score_walk_launch(D, p.Q, p.N, p.G, p.M, p.per, p.qcoef, p.gcoef, few, slices, &grid)) return e;
     if (p.qcoef) return D == 192 ? launch_topk_form<192, true>(p, few, grid, stream) : launch_topk_form<256, true>(p, few, grid, stream);
     return D == 192 ? launch_topk_form<192, false>(p, few, grid, stream) : launch_topk_form<256, false>(p, few, grid, stream);
 }

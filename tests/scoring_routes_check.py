@@ -36,7 +36,7 @@ LDS_MAX_ROWS = 4
 FAST_MAX_TOP = 256                    # score.hip: the threshold fast path runs for top <= 256 and K >= 4 top
 FUSED_WIDTHS = (192, 256)             # asnorm_fused.hip::asnorm_fused_supported, score_h3w_supported
 FUSED_MIN_K = 64
-SLAB_BYTES, SLAB_MIN_ROWS = 1 << 31, 128              # api_scoring.hip::asnorm_stats_slab
+SLAB_BYTES, SLAB_MIN_ROWS = 1 << 31, 128              # api_scoring.hip::SlabWalk
 BIG_SCRATCH = 256 << 20               # api_scoring.hip::release_big_scratch
 ERR_UNSUPPORTED = -5                  # include/svhip.h
 FORMS = ("reg8", "reg24", "lds", "global")
@@ -99,7 +99,7 @@ def score_route(D, Na, Nb, aligned=True, f32mfma=False, tiled=False):
 
 
 def slab_rows(N, K):
-    """api_scoring.hip::asnorm_stats_slab"""
+    """api_scoring.hip::SlabWalk::open"""
     return min(N, max(SLAB_MIN_ROWS, SLAB_BYTES // (kp(K) * 4)))
 
 

@@ -13,7 +13,7 @@ import torch
 from speakerverification_amd import _lib, synth
 from speakerverification_amd.engine import Engine
 from speakerverification_amd.model import ModelHandling, SpeakerEncoder, WrappedModel
-from tests.test_gpu_topk_norm import EPS, _coef, _statement, _stats64
+from tests.test_gpu_topk_norm import EPS, _chunk_data, _coef, _statement, _stats64
 
 pytestmark = pytest.mark.gpu
 
@@ -97,6 +97,21 @@ def test_exact_sets_on_integer_data(eng, D, N):
     a gallery shorter than a block; 33, 1000, 4100: a last block that runs past M; 4100 = 129 blocks: several gallery slices."""
     hits, ties = _exact_sets(eng, D, N, (1, 31, 33, 1000, 4100))
     assert hits > 0 and ties > 0                # pairs exactly AT the threshold were there: >= includes them
+
+
+@pytest.mark.parametrize("norm", [False, True])
+def test_more_than_one_query_chunk(eng, norm):
+    """N = 16 384 + 148, M = 1 283, D = 192: three launches of the fused route (tests/test_gpu_topk_norm.py, _chunk_data), each with its
+    own place in the list-count scratch, its own rows of row_ptr and of the coefficient table.  The threshold is a value that occurs,
+    with about three hits a row at or above it."""
+    d = _chunk_data()
+    V = d["T"] if norm else d["S"]
+    thr = _occurring(V[:512], 1.0 - 3.0 / V.shape[1])
+    keep = V >= np.float32(thr)
+    per_row = keep.sum(axis=1)
+    assert (per_row == 0).any() and (per_row >= 3).any() and 1.0 <= per_row.mean() <= 6.0 and int((V == np.float32(thr)).sum()) > 0
+    got = eng.score_above(d["Q"], d["G"], thr, *((d["q_stats"], d["g_stats"]) if norm else ()))
+    assert _equal(got, _csr(keep, V))
 
 
 # ---- 2. edge values -----------------------------------------------------------------------------------------------------------------------------

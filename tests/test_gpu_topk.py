@@ -64,6 +64,16 @@ def test_exact_order_on_integer_data(eng, D, N):
         assert crossing > 0     # rows whose k-th and (k + 1)-th score tie: the tie rule was exercised
 
 
+def test_more_than_one_query_chunk(eng):
+    """N = 16 384 + 148, M = 1 283, D = 192, k = 5: three launches of the fused route with three list strides (_chunk_data)"""
+    from tests.test_gpu_topk_norm import _chunk_data
+    d = _chunk_data()
+    sc, ix = eng.score_topk(d["Q"], d["G"], 5)
+    order, want = _reference(d["S"], 5)
+    assert np.array_equal(ix, order)
+    assert np.array_equal(sc.view(np.uint32), want.view(np.uint32))
+
+
 @pytest.mark.parametrize("D", [192, 320])
 def test_planted_rows_on_block_and_slice_edges(eng, D):
     """the unique best row at index 0, at M - 1 and at a multiple of 32; duplicate gallery rows across 32-row boundaries"""

@@ -97,6 +97,40 @@ def test_exact_order_on_integer_data(eng, D, N):
         assert crossing > 0     # rows whose k-th and (k + 1)-th t tie: the tie rule was exercised
 
 
+_CHUNK = {}
+
+
+def _chunk_data():
+    """A call of more than one query chunk, shared with tests/test_gpu_topk.py and tests/test_gpu_above.py: N = 16 384 + 148 queries, so
+    the fused route (csrc/api_scoring.hip, fused_plan) runs three launches - a full chunk of 128 MANY tiles, and from the second chunk
+    one MANY tile of 128 queries and a FEW launch of 20 - each with its own offset into the queries, the coefficient table and the
+    outputs.  M = 1 283 is 41 gallery blocks with a ragged last one: on a 256-CU chip 4, 5 and 3 slices, so the three launches have
+    three different list strides.  _int_data's generators at D = 192; S and t are exact in fp32 and kept as fp32 (85 MB each)."""
+    if not _CHUNK:
+        rng = np.random.default_rng(16384 + 148)
+        N, M, D = 16384 + 148, 1283, 192
+        G = rng.integers(-4, 5, (M, D)).astype(np.float32)
+        Q = rng.integers(-4, 5, (N, D)).astype(np.float32)
+        sig = np.array([0.25, 0.5, 1.0, 2.0], np.float32)
+        q_stats = (rng.integers(-8, 9, N).astype(np.float32), sig[rng.integers(0, 4, N)])
+        g_stats = (rng.integers(-8, 9, M).astype(np.float32), sig[rng.integers(0, 4, M)])
+        S64 = Q.astype(np.float64) @ G.astype(np.float64).T
+        T64 = _statement(S64, q_stats, g_stats)
+        S, T = S64.astype(np.float32), T64.astype(np.float32)
+        assert np.array_equal(S, S64) and np.array_equal(T, T64)                # (nothing was rounded)
+        _CHUNK.update(Q=Q, G=G, q_stats=q_stats, g_stats=g_stats, S=S, T=T)
+    return _CHUNK
+
+
+def test_more_than_one_query_chunk(eng):
+    d = _chunk_data()
+    k = 5
+    sc, ix = eng.score_topk_norm(d["Q"], d["q_stats"], d["G"], d["g_stats"], k)
+    order, want = _reference(d["T"], k)
+    assert np.array_equal(ix, order)
+    assert np.array_equal(sc.view(np.uint32), want.view(np.uint32))
+
+
 # ---- 2. the coefficients alone order the gallery ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("N", [20, 129])
 @pytest.mark.parametrize("D", [192, 320])

@@ -52,9 +52,13 @@ def test_route_predicates_restate_the_api_and_the_fused_kernels():
     assert ("bool score_h3w_supported(int D, int64_t Na, int64_t Nb) { return (D == 192 || D == 256) && Na > 0 && Nb > 0 && "
             "Nb < ((int64_t)1 << 30) && Na < ((int64_t)1 << 31); }") in fused
     api = _src("speakerverification_amd", "csrc", "api_scoring.hip")
+    # the slab geometry is SlabWalk's, with asnorm_stats_slab's cohort of K rows as its B operand of M rows
+    walk = _body(api, "struct SlabWalk {", "\n};\n")
+    assert "const float* dA; int64_t N;\n    const float* dB; int64_t M;\n    int D;\n" in walk
+    assert "ldk = (M + 3) & ~(int64_t)3;" in walk
+    assert "slab_rows = std::min<int64_t>(N, std::max<int64_t>(128, ((int64_t)1 << 31) / (ldk * 4)));" in walk
     slab = _body(api, "static int asnorm_stats_slab(")
-    assert "const int64_t ldk = (K + 3) & ~3;" in slab
-    assert "std::min<int64_t>(N, std::max<int64_t>(128, ((int64_t)1 << 31) / (ldk * 4)))" in slab
+    assert "SlabWalk w{h, dE, N, dC, K, D};" in slab and "w.open(nullptr)" in slab
     assert re.findall(r'"(asnorm_topk_\w+)"', slab)[:4] == [chk.LABEL[f] for f in chk.FORMS]
     assert "const size_t cap = (size_t)256 << 20;" in _body(api, "void release_big_scratch(") and chk.BIG_SCRATCH == 256 << 20
     route = _flat(_body(api, "static ScoreRoute score_route("))
