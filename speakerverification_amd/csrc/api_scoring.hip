@@ -178,7 +178,7 @@ int svhip_mean_crops(svhip_handle* h, const float* F, int64_t n_files, int32_t n
 }
 
 // out (Na, Nb) = A @ B^T.  The route is decided ONCE (split_b and score_gemm used to re-derive it from different predicates):
-//   SCORE_H3W     rows of A in registers, B streamed past them as half planes (asnorm_fused.hip: score_h3w; D = 192 / 256, aligned operands);
+//   SCORE_H3W     rows of A in registers, B streamed past them as half planes (score_h3w.hip; D = 192 / 256, aligned operands);
 //                 the kernel's launcher fills the planes itself (and scales both operands by exact powers of two)
 //   SCORE_WORDS   the tiled GEMM with B as (hi half << 16 | lo half) words, A split in registers (gemm_pw's x3 form)
 //   SCORE_F32MFMA the exact fp32 MFMA GEMM (option score_f32mfma, or shapes gemm_pw's split form does not take)
@@ -339,7 +339,7 @@ int svhip_asnorm_stats(svhip_handle* h, const float* E, int64_t N, int32_t D, co
             void* planes = (char*)mb + mb_bytes + mom_bytes;
             fp.planes = planes;
             fp.nlists = 4;                  // the 16-wide-MFMA kernel: four lists per embedding
-            // the kernel scales its operands by exact powers of two (asnorm_fused.hip, "operand scaling"): the cohort's max |x| goes to
+            // the kernel scales its operands by exact powers of two (split_planes.hip, "operand scaling"): the cohort's max |x| goes to
             // a device word behind the two planes (the buffer is sized for three)
             uint32_t* pscale = reinterpret_cast<uint32_t*>((char*)planes + (size_t)2 * (D + 32 + K) * D * 2);
             if ((rc = run(h, "asnorm_planes", 0, [&]() { return launch_asnorm_planes((const float*)mb, (const float*)dC, K, D, planes, h->stream, pscale); }))) return rc;

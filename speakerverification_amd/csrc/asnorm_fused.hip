@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "h3w_walk.h"
 #include "kernels.h"
 #include "score_select.h"
 
@@ -87,15 +88,11 @@ __global__ __launch_bounds__(256, 2) void asnorm_fused_kernel(AsnormFusedParams 
     };
     // A fragments (16-byte reads: four k-steps each) are requested NG1 groups ahead of their MFMAs (left alone hipcc issues each
     // ds_read right in front of the wait of the four MFMAs that use it).
-    // Read-ahead depth, measured on one box with two builds (tools/build_variant.sh -DAF_NG1=n; 1.2 M x 5 994, ms end to end):
+    // Read-ahead depth NG1, measured on one box with two builds (1.2 M x 5 994, ms end to end):
     // none 26.1 - 26.4 (another box), 1 group 26.7 - 26.9, half a block (12) 27.5 - 29.3: the partner wave already covers the LDS
     // latency, and the deeper variants only cost registers.  PMC of this kernel (profiles/r03_asnorm_pmc.txt): matrix pipe busy
     // 0.80 of the CU cycles at 2.13 - 2.23 GHz, no LDS bank conflicts, LDS array 5 % active.
-#ifdef AF_NG1
-    constexpr int NG = CH / 2, NG1 = AF_NG1;
-#else
     constexpr int NG = CH / 2, NG1 = 1;
-#endif
     f32x4 af[NG];
     auto rd = [&](int buf, int t) {
         return *reinterpret_cast<const f32x4*>(smem + buf * BLK + j * (D * 4) + (((h * NG + t) ^ (j & 15)) << 4));      // cohort row j of the block (A: row = lane & 31)
@@ -151,9 +148,7 @@ __global__ __launch_bounds__(256, 2) void asnorm_fused_kernel(AsnormFusedParams 
         }
     };
 
-#ifdef AF_STAGGER
-    if ((blockIdx.x >> 8) & 1) __builtin_amdgcn_s_sleep(AF_STAGGER);      // developer A/B: co-resident workgroups half a block apart (measured: +-0)
-#endif
+    // (co-resident workgroups started half a block apart, by a sleep in every other one, measured +-0)
     issue(0, 0);
     f32x16 accp;
 #pragma unroll
@@ -171,51 +166,11 @@ __global__ __launch_bounds__(256, 2) void asnorm_fused_kernel(AsnormFusedParams 
     if (valid) p.cnt[row * 2 + h] = cnt;
 }
 
-// ---- operand scaling of the half-plane forms (round 5) --------------------------------------------------------------------------
-// IEEE-half planes have fp16's exponent range: a component beyond 65504 overflows, one below 2^-14 loses bits of its hi part, and lo is a
-// subnormal (2^-24 absolute) below 2^-3.  Embeddings are not always unit vectors (the reference scores raw embeddings when `normalize` is
-// off: src/model.py:421, utils.py:142-150), so every operand is brought to a fixed magnitude by an EXACT power of two before it is split:
-// a row of the register operand by its own max |x| (found in the kernel, per row), the streamed operand by the max |x| of the whole matrix
-// (absmax_bits_kernel -> a device word the split pass and the kernels read: no host round trip).  max |x| lands in [64, 128): hi is exact
-// to 11 bits and lo a normal half for every component down to 2^-10 of the largest; squares (the AS-norm moment rows) stay below 2^14.
-// Products and sums are formed on the scaled values — binary floating point is scale-invariant, so the fp32 accumulation rounds exactly
-// as it would have — and the result is multiplied back by the exact inverse.  Zero rows keep scale 1; inf / NaN stay inf / NaN.
-// (pow2_scale_of_bits, pow2_inverse, finite_abs_bits: common.h — round 6: the F32X3 network input uses them too)
-// max |x| over the FINITE elements of a matrix as the bit pattern of a non-negative float (ordered like an unsigned integer): ABSMAX_WGS
-// workgroups leave one partial each in part[0 .. ABSMAX_WGS) (no atomics, no zero-fill launch); the consumer's first kernel folds them
-// (absmax_fold: 256 loads per workgroup) and its workgroup 0 publishes the result in part[-1] = *pscale for the kernels after it
-constexpr int ABSMAX_WGS = 256;
-__global__ __launch_bounds__(256) void absmax_bits_kernel(const float* __restrict__ X, int64_t n, uint32_t* __restrict__ part) {
-    __shared__ uint32_t wm[4];
-    uint32_t m = 0;
-    const int64_t n4 = n >> 2;
-    const u32x4* __restrict__ X4 = reinterpret_cast<const u32x4*>(X);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        const u32x4 v = X4[i];
-        m = max(max(m, finite_abs_bits(v[0])), max(max(finite_abs_bits(v[1]), finite_abs_bits(v[2])), finite_abs_bits(v[3])));
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) m = max(m, finite_abs_bits(__float_as_uint(X[(n4 << 2) + threadIdx.x])));
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = max(max(wm[0], wm[1]), max(wm[2], wm[3]));
-}
-// (called by every thread of a 256-thread workgroup)
-__device__ __forceinline__ uint32_t absmax_fold(const uint32_t* __restrict__ part) {
-    __shared__ uint32_t fm[4];
-    uint32_t m = part[threadIdx.x];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    if ((threadIdx.x & 63) == 0) fm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    return max(max(fm[0], fm[1]), max(fm[2], fm[3]));
-}
-
 // ---- the same kernel on two IEEE-half planes and three fp16 MFMAs per product block ("h3w", round 4, the default) ----------------------
 // Same structure as asnorm_fused_kernel (embeddings = B operand in registers, cohort blocks through LDS, lane-local selection, exact moments as
 // leading pseudo-cohort blocks); the cohort image (pseudo rows first, then the K cohort rows) is split into two half planes once per call
-// (split2_planes_kernel), and a product block is hi.hi + hi.lo + lo.hi with fp32 accumulation.  A half plane carries 11 significant bits, so
+// (split_planes.hip), and a product block is hi.hi + hi.lo + lo.hi with fp32 accumulation — the machinery of h3w_walk.h, shared with the
+// dense score kernel (score_h3w.hip); this kernel keeps its block loop and the selection.  A half plane carries 11 significant bits, so
 // hi + lo holds 22 (2^-23 relative) while lo is a normal half, and below |v| = 2^-3 — where the components of unit embeddings live — lo is a
 // subnormal half with an ABSOLUTE quantum of 2^-24: a component is represented to 3e-8 absolute, a score of unit vectors to ~4e-8 (measured
 // against the float64 oracle: tests).  That is the class of round 3's six-bf16-MFMA form (three exact bf16 parts per value, 1.5e-8 from the
@@ -229,130 +184,28 @@ __device__ __forceinline__ uint32_t absmax_fold(const uint32_t* __restrict__ par
 template <int D>
 __global__ __launch_bounds__(256, 2) void asnorm_h3w_kernel(AsnormFusedParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int CH = D / 8;                       // 16-byte chunks (8 values) per row of a plane
-    constexpr int PL = 32 * D * 2;                  // one plane of a block of 32 rows
-    constexpr int BLK = 2 * PL;
-    constexpr int NDMA = 2 * 32 * CH / 256;         // DMA instructions per thread per block
+    typedef H3wWalk<D> Walk;
+    typedef typename Walk::acc_t acc_t;
     constexpr int NP = D / 32 + 1;                  // pseudo-cohort blocks: rows of M, then cbar
-    constexpr int NS = D / 32;                      // MFMA k steps (32 wide) per block
     constexpr int CAPQ = AF_CAPL / 2;               // candidate slots per (embedding, q)
-    static_assert(D % 64 == 0 && (2 * 32 * CH) % 256 == 0 && CH % 8 == 0, "block image: whole DMA rounds, chunk groups of 8");
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 15, q = lane >> 4;
-    const int64_t row0 = (int64_t)blockIdx.x * 128 + wave * 32 + c;            // embedding of group 0 (group 1: + 16)
-    bool valid[2];
+    Walk w(smem, p.N);
+    const int c = w.c, q = w.q;
+    const int64_t row0 = w.row0;                                               // embedding of group 0 (group 1: + 16)
+    const bool (&valid)[2] = w.valid;
+    const float (&se)[2] = w.se;
     uint32_t eoff[2];                                                          // < 2^31 elements per launch (host check)
 #pragma unroll
-    for (int eg = 0; eg < 2; ++eg) {
-        const int64_t r = row0 + 16 * eg;
-        valid[eg] = r < p.N;
-        eoff[eg] = (uint32_t)((valid[eg] ? r : p.N - 1) * D);
-    }
+    for (int eg = 0; eg < 2; ++eg) eoff[eg] = (uint32_t)((valid[eg] ? row0 + 16 * eg : p.N - 1) * D);
 
-    // B operand: embedding (16 eg + c), k = 32 s + 8 q .. + 7, as half hi | lo parts of the row SCALED by a power of two (its max |x| in
-    // [64, 128): "operand scaling" above).  With p.pscale the planes are scaled too (cohort and mean row by sC, moment rows by sC^2): every
-    // score of this kernel lives in the scaled domain — the threshold is formed and compared there, the candidates are stored there — and
-    // the candidate kernel multiplies a row's mean and deviation back by p.rowscale[row] (exact).
-    bf16x8 bh[2][NS], bl[2][NS];
-    float se[2] = {1.0f, 1.0f}, unscale[2] = {1.0f, 1.0f};
-#pragma unroll
-    for (int eg = 0; eg < 2; ++eg) {
-        if (p.pscale) {
-            uint32_t m = 0;
-#pragma unroll
-            for (int s_ = 0; s_ < NS; ++s_) {
-                const u32x4 w0 = *reinterpret_cast<const u32x4*>(p.E + eoff[eg] + 32 * s_ + 8 * q);
-                const u32x4 w1 = *reinterpret_cast<const u32x4*>(p.E + eoff[eg] + 32 * s_ + 8 * q + 4);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) m = max(m, max(finite_abs_bits(w0[u]), finite_abs_bits(w1[u])));
-            }
-            m = max(m, (uint32_t)__shfl_xor((int)m, 16, 64));
-            m = max(m, (uint32_t)__shfl_xor((int)m, 32, 64));
-            se[eg] = pow2_scale_of_bits(m);
-            unscale[eg] = pow2_inverse(se[eg]) * pow2_inverse(pow2_scale_of_bits(*p.pscale));
-        }
-#pragma unroll
-        for (int s_ = 0; s_ < NS; ++s_) {
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(p.E + eoff[eg] + 32 * s_ + 8 * q);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(p.E + eoff[eg] + 32 * s_ + 8 * q + 4);
-            f16x8 a8, b8;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float v = (u < 4 ? v0[u] : v1[u - 4]) * se[eg];
-                const f16_t a = static_cast<f16_t>(v);
-                a8[u] = a;
-                b8[u] = static_cast<f16_t>(v - static_cast<float>(a));
-            }
-            bh[eg][s_] = __builtin_bit_cast(bf16x8, a8);
-            bl[eg][s_] = __builtin_bit_cast(bf16x8, b8);
-        }
-    }
+    // B operand: embedding (16 eg + c), scaled by se ("operand scaling", split_planes.hip).  With p.pscale the planes are scaled too (cohort
+    // and mean row by sC, moment rows by sC^2): every score of this kernel lives in the scaled domain — the threshold is formed and compared
+    // there, the candidates are stored there — and the candidate kernel multiplies a row's mean and deviation back by p.rowscale[row] (exact).
+    w.load_operand([&](int eg) { return p.E + eoff[eg]; }, p.pscale);
 
     const int rows_total = NP * 32 + p.K;
     const int nb = (rows_total + 31) / 32;
-    const char* planes = reinterpret_cast<const char*>(p.planes);
-    const int64_t plane_bytes = (int64_t)rows_total * D * 2;
-    // the image is lane-linear (16 bytes per lane): position -> (plane, row, chunk slot); the swizzle goes on the source chunk
-    auto issue = [&](int b, int buf) {
-        const int r0 = b * 32;
-        const int limit = rows_total - 1 - r0;          // the last block clamps its rows
-#pragma unroll
-        for (int qq = 0; qq < NDMA; ++qq) {
-            const int pidx = qq * 256 + tid;
-            const int pl = pidx / (32 * CH), rem = pidx - pl * (32 * CH);
-            const int i = rem / CH, cs = rem - i * CH;
-            const int cc = (cs & ~7) | ((cs ^ (i >> 1)) & 7);
-            const char* src = planes + pl * plane_bytes + ((int64_t)(r0 + min(i, limit)) * D + cc * 8) * 2;
-            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(smem + buf * BLK + (qq * 256 + wave * 64) * 16), 16, 0, 0);
-        }
-    };
-    // A fragment: cohort row 16 rg + c of the block, k = 32 s + 8 q .. + 7 (chunk 4 s + q of the row).  The 16 lanes of one q read 16 rows at
-    // one logical chunk: 8 keys x even / odd row (row stride 384 B = 1.5 bank periods at D = 192): 16 distinct 16-byte slots, no conflict
-    auto rd = [&](int buf, int pl, int rg, int s_) {
-        const int i = 16 * rg + c, cs = 4 * s_ + q;
-        return *reinterpret_cast<const bf16x8*>(smem + buf * BLK + pl * PL + i * (D * 2) + (((cs & ~7) | ((cs ^ (i >> 1)) & 7)) << 4));
-    };
-    typedef f32x4 acc_t[2][2];
-    auto mfma_block = [&](int buf, acc_t& acc) {
-#pragma unroll
-        for (int rg = 0; rg < 2; ++rg)
-#pragma unroll
-            for (int eg = 0; eg < 2; ++eg) acc[rg][eg] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // A fragments are read ONE k step ahead of their MFMAs, fenced (left alone hipcc issues each ds_read right in front of the wait
-        // of the MFMAs that use it, and a wave then sits out the LDS latency every k step whenever its SIMD partner is not in its own MFMA
-        // phase: matrix pipe busy 0.58 in round 3's form)
-        bf16x8 ah[2] = {rd(buf, 0, 0, 0), rd(buf, 0, 1, 0)}, al[2] = {rd(buf, 1, 0, 0), rd(buf, 1, 1, 0)};
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s_ = 0; s_ < NS; ++s_) {
-            bf16x8 nh[2] = {ah[0], ah[1]}, nl[2] = {al[0], al[1]};
-            if (s_ + 1 < NS) {
-#pragma unroll
-                for (int rg = 0; rg < 2; ++rg) { nh[rg] = rd(buf, 0, rg, s_ + 1); nl[rg] = rd(buf, 1, rg, s_ + 1); }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // small terms first; the four accumulators of a term are independent
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg)
-#pragma unroll
-                for (int eg = 0; eg < 2; ++eg) acc[rg][eg] = Half16<f16_t>::mfma16(al[rg], bh[eg][s_], acc[rg][eg]);
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg)
-#pragma unroll
-                for (int eg = 0; eg < 2; ++eg) acc[rg][eg] = Half16<f16_t>::mfma16(ah[rg], bl[eg][s_], acc[rg][eg]);
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg)
-#pragma unroll
-                for (int eg = 0; eg < 2; ++eg) acc[rg][eg] = Half16<f16_t>::mfma16(ah[rg], bh[eg][s_], acc[rg][eg]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg) { ah[rg] = nh[rg]; al[rg] = nl[rg]; }
-        }
-        __builtin_amdgcn_s_setprio(0);
-    };
+    w.stream(p.planes, rows_total);
 
     float second[2] = {0.0f, 0.0f}, tau[2] = {0.0f, 0.0f};
     // A lane's candidate list.  The four lists of an embedding (one per q) are INTERLEAVED in its 4 * CAPQ-float region: element k of list q at
@@ -423,7 +276,7 @@ __global__ __launch_bounds__(256, 2) void asnorm_h3w_kernel(AsnormFusedParams p)
         }
     };
 
-    issue(0, 0);
+    w.issue(0, 0);
     acc_t accp;
 #pragma unroll
     for (int rg = 0; rg < 2; ++rg)
@@ -432,242 +285,20 @@ __global__ __launch_bounds__(256, 2) void asnorm_h3w_kernel(AsnormFusedParams p)
     for (int b = 0; b < nb; ++b) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // block b has landed (and the candidate stores of one block ago, long since)
         __syncthreads();                                       // ... for every wave; nobody still reads the other buffer
-        if (b + 1 < nb) issue(b + 1, (b + 1) & 1);
+        if (b + 1 < nb) w.issue(b + 1, (b + 1) & 1);
         // the selection of the PREVIOUS block goes first: its candidate stores are then a whole MFMA phase old at the next wait
         // (issued after the MFMAs they sat right in front of that wait: 18.8 ms for 1.2 M embeddings)
         if (b > 0) process(accp, b - 1);
         __builtin_amdgcn_sched_barrier(0);
-        mfma_block(b & 1, accp);
+        w.mfma_block(b & 1, accp);
     }
     process(accp, nb - 1);
 #pragma unroll
     for (int eg = 0; eg < 2; ++eg)
         if (valid[eg]) {
             p.cnt[(row0 + 16 * eg) * 4 + q] = (int32_t)((pos[eg] - (coff[eg] << 2)) >> 4);      // every hit counted, stored or not
-            if (q == 0 && p.rowscale) p.rowscale[row0 + 16 * eg] = unscale[eg];
+            if (q == 0 && p.rowscale) p.rowscale[row0 + 16 * eg] = w.unscale[eg];
         }
-}
-
-// ---- dense score matrix on the same machinery: out[i][j] = A_i . B_j (svhip_score_matrix, the slab path's cohort GEMM) --------------------
-// K = D = 192 / 256 is six / eight k steps: as a tiled GEMM (gemm_pw's split form, 256 x 128 tiles) the kernel spent its time fetching fp32
-// operands (43 FLOP per byte) — 152 TFLOP/s, 0.68 ms for 16 384 x 16 384.  Here a wave keeps 32 rows of A in registers as half hi | lo parts
-// and streams B (pre-split half planes, blocks of 32 rows through the LDS image of the AS-norm kernel) past them: three fp16 MFMAs per
-// product block on v_mfma_f32_16x16x32_f16, scores stored straight from the accumulators (lane = 4 consecutive columns of one row: 16-byte
-// stores, a 128-byte line per row per block).  Grid (row panels of 128, column slices): every workgroup walks `per` blocks of B.
-#ifndef SCORE_ABL
-#define SCORE_ABL 0          // tools only: 1 = stores straight from the accumulators (round 5's form)
-#endif
-template <int D>
-__global__ __launch_bounds__(256, 2) void score_h3w_kernel(ScoreH3Params p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int CH = D / 8;
-    constexpr int PL = 32 * D * 2;
-    constexpr int BLK = 2 * PL;
-    constexpr int NDMA = 2 * 32 * CH / 256;
-    constexpr int NS = D / 32;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 15, q = lane >> 4;
-    const int64_t row0 = (int64_t)blockIdx.x * 128 + wave * 32 + c;
-    bool valid[2];
-    int64_t arow[2];
-#pragma unroll
-    for (int eg = 0; eg < 2; ++eg) {
-        arow[eg] = row0 + 16 * eg;
-        valid[eg] = arow[eg] < p.Na;
-    }
-    bf16x8 bh[2][NS], bl[2][NS];
-    float unscale[2] = {1.0f, 1.0f};            // per row of A: 1 / (its own scale * the scale of the B planes), exact powers of two
-#pragma unroll
-    for (int eg = 0; eg < 2; ++eg) {
-        const float* src = p.A + (valid[eg] ? arow[eg] : p.Na - 1) * D;
-        float sa = 1.0f;
-        if (p.pscale) {                         // "operand scaling" above: the row by its own max |x|, the planes by the matrix's
-            uint32_t m = 0;
-#pragma unroll
-            for (int s_ = 0; s_ < NS; ++s_) {
-                const u32x4 w0 = *reinterpret_cast<const u32x4*>(src + 32 * s_ + 8 * q);
-                const u32x4 w1 = *reinterpret_cast<const u32x4*>(src + 32 * s_ + 8 * q + 4);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) m = max(m, max(finite_abs_bits(w0[u]), finite_abs_bits(w1[u])));
-            }
-            m = max(m, (uint32_t)__shfl_xor((int)m, 16, 64));
-            m = max(m, (uint32_t)__shfl_xor((int)m, 32, 64));
-            sa = pow2_scale_of_bits(m);
-            unscale[eg] = pow2_inverse(sa) * pow2_inverse(pow2_scale_of_bits(*p.pscale));
-        }
-#pragma unroll
-        for (int s_ = 0; s_ < NS; ++s_) {
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(src + 32 * s_ + 8 * q);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(src + 32 * s_ + 8 * q + 4);
-            f16x8 a8, b8;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float v = (u < 4 ? v0[u] : v1[u - 4]) * sa;
-                const f16_t a = static_cast<f16_t>(v);
-                a8[u] = a;
-                b8[u] = static_cast<f16_t>(v - static_cast<float>(a));
-            }
-            bh[eg][s_] = __builtin_bit_cast(bf16x8, a8);
-            bl[eg][s_] = __builtin_bit_cast(bf16x8, b8);
-        }
-    }
-    const int nb_all = (p.Nb + 31) / 32;
-    const int b_first = blockIdx.y * p.per, b_last = min(nb_all, b_first + p.per);
-    if (b_first >= b_last) return;                                                  // workgroup-uniform
-    const char* planes = reinterpret_cast<const char*>(p.planes);
-    const int64_t plane_bytes = (int64_t)p.Nb * D * 2;
-    auto issue = [&](int b, int buf) {
-        const int r0 = b * 32;
-        const int limit = p.Nb - 1 - r0;            // the last block clamps its rows
-#pragma unroll
-        for (int qq = 0; qq < NDMA; ++qq) {
-            const int pidx = qq * 256 + tid;
-            const int pl = pidx / (32 * CH), rem = pidx - pl * (32 * CH);
-            const int i = rem / CH, cs = rem - i * CH;
-            const int cc = (cs & ~7) | ((cs ^ (i >> 1)) & 7);
-            const char* src = planes + pl * plane_bytes + ((int64_t)(r0 + min(i, limit)) * D + cc * 8) * 2;
-            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(smem + buf * BLK + (qq * 256 + wave * 64) * 16), 16, 0, 0);
-        }
-    };
-    auto rd = [&](int buf, int pl, int rg, int s_) {
-        const int i = 16 * rg + c, cs = 4 * s_ + q;
-        return *reinterpret_cast<const bf16x8*>(smem + buf * BLK + pl * PL + i * (D * 2) + (((cs & ~7) | ((cs ^ (i >> 1)) & 7)) << 4));
-    };
-    const bool vec_ok = (p.ldo & 3) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0;
-    // a wave whose 32 rows are all inside A issues exactly four 16-byte store instructions per interior block, AFTER the next block's DMAs:
-    // the wait for block b may then leave those four (the newest entries of the in-order counter) in flight instead of draining them
-    const bool rows_full = vec_ok && ((int64_t)blockIdx.x * 128 + wave * 32 + 32 <= p.Na);      // wave-uniform
-    bool four_stores_behind = false;
-    // Round 6: stored straight from the accumulators a wave instruction writes sixteen 64-byte row pieces (2.8 TB/s of
-    // output at 16 384^2; plain stores of 256 contiguous bytes per row run at 6 TB/s: MI355X_MICROARCH.md).  Where the LDS has room beside
-    // the two operand blocks (D = 192: 48 KiB + 4 x 8 KiB = 80 KiB, still two workgroups per CU) a wave keeps the scores of TWO blocks — 32
-    // rows x 64 columns — in a private 8 KiB image (16-byte slot s of row r at s ^ (r & 15): conflict-free both ways) and writes them as
-    // four rows x 256 contiguous bytes per instruction.  No barrier: the image is the wave's own, and a wave's LDS operations run in order.
-    constexpr bool STAGED = D == 192 && !(SCORE_ABL & 1);
-    char* stg = smem + 2 * BLK + wave * 8192;
-    const bool stage = STAGED && vec_ok;
-    int stores_behind = 0;                      // stores this wave issued behind the next block's DMAs (-1: not known)
-    issue(b_first, 0);
-    for (int b = b_first; b < b_last; ++b) {
-        const int buf = (b - b_first) & 1;
-        if (stage) {
-            if (stores_behind == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else if (four_stores_behind) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");      // block b has landed; the previous block's stores may still fly
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        four_stores_behind = rows_full && (32 * b + 32 <= p.Nb);
-        __syncthreads();
-        if (b + 1 < b_last) issue(b + 1, buf ^ 1);
-        f32x4 acc[2][2];
-#pragma unroll
-        for (int rg = 0; rg < 2; ++rg)
-#pragma unroll
-            for (int eg = 0; eg < 2; ++eg) acc[rg][eg] = f32x4{0.f, 0.f, 0.f, 0.f};
-        bf16x8 ah[2] = {rd(buf, 0, 0, 0), rd(buf, 0, 1, 0)}, al[2] = {rd(buf, 1, 0, 0), rd(buf, 1, 1, 0)};
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s_ = 0; s_ < NS; ++s_) {
-            bf16x8 nh[2] = {ah[0], ah[1]}, nl[2] = {al[0], al[1]};
-            if (s_ + 1 < NS) {
-#pragma unroll
-                for (int rg = 0; rg < 2; ++rg) { nh[rg] = rd(buf, 0, rg, s_ + 1); nl[rg] = rd(buf, 1, rg, s_ + 1); }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg)
-#pragma unroll
-                for (int eg = 0; eg < 2; ++eg) acc[rg][eg] = Half16<f16_t>::mfma16(al[rg], bh[eg][s_], acc[rg][eg]);
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg)
-#pragma unroll
-                for (int eg = 0; eg < 2; ++eg) acc[rg][eg] = Half16<f16_t>::mfma16(ah[rg], bl[eg][s_], acc[rg][eg]);
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg)
-#pragma unroll
-                for (int eg = 0; eg < 2; ++eg) acc[rg][eg] = Half16<f16_t>::mfma16(ah[rg], bh[eg][s_], acc[rg][eg]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg) { ah[rg] = nh[rg]; al[rg] = nl[rg]; }
-        }
-        __builtin_amdgcn_s_setprio(0);
-        // acc[rg][eg][e] = A row (16 eg + c of the wave) . B row 32 b + 16 rg + 4 q + e
-        if (stage) {
-            const int hb = (b - b_first) & 1;           // which half of the image this block fills
-#pragma unroll
-            for (int eg = 0; eg < 2; ++eg)
-#pragma unroll
-                for (int rg = 0; rg < 2; ++rg) {
-                    const int slot = hb * 8 + rg * 4 + q;
-                    *reinterpret_cast<f32x4*>(stg + (16 * eg + c) * 256 + ((slot ^ c) << 4)) = acc[rg][eg] * unscale[eg];
-                }
-            stores_behind = 0;
-            if (hb == 1 || b + 1 == b_last) {
-                asm volatile("" ::: "memory");
-                const int jb = 32 * (b - hb);           // first column of the image
-                const int t = lane & 15;
-                const int64_t wrow0 = (int64_t)blockIdx.x * 128 + wave * 32;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int R = 4 * k + (lane >> 4);
-                    const f32x4 o4 = *reinterpret_cast<const f32x4*>(stg + R * 256 + ((t ^ (R & 15)) << 4));
-                    const int j0 = jb + 4 * t;
-                    if (wrow0 + R < p.Na && t < 8 * (hb + 1)) {
-                        float* orow = p.out + (wrow0 + R) * p.ldo;
-                        if (j0 + 4 <= p.Nb) {
-                            __builtin_nontemporal_store(o4, reinterpret_cast<f32x4*>(orow + j0));
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if (j0 + e < p.Nb) orow[j0 + e] = o4[e];
-                        }
-                    }
-                }
-                // (exactly eight 16-byte store instructions when every row is inside A and both blocks are whole)
-                stores_behind = (rows_full && hb == 1 && jb + 64 <= p.Nb) ? 8 : -1;
-            }
-            continue;
-        }
-#pragma unroll
-        for (int eg = 0; eg < 2; ++eg) {
-            if (!valid[eg]) continue;
-            float* orow = p.out + arow[eg] * p.ldo;
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg) {
-                const int j0 = 32 * b + 16 * rg + 4 * q;
-                const f32x4 o4 = acc[rg][eg] * unscale[eg];
-                if (vec_ok && j0 + 4 <= p.Nb) {
-                    __builtin_nontemporal_store(o4, reinterpret_cast<f32x4*>(orow + j0));      // (written once, read by a later kernel at best)
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (j0 + e < p.Nb) orow[j0 + e] = o4[e];
-                }
-            }
-        }
-    }
-}
-
-// fp32 rows -> two half planes [2][rows_total][D] (hi, lo): rows [0, n0) from A (the pseudo-cohort rows MB), the rest from B (the cohort)
-// `pscale` (optional): the max-|x| word of B (absmax_bits_kernel): every row is multiplied by s = pow2_scale_of_bits(*pscale), the first
-// `sq_rows` rows of A (second-moment rows: products of two cohort values) by s^2
-__global__ __launch_bounds__(256) void split2_planes_kernel(const float* __restrict__ A, int n0, const float* __restrict__ B, int n1, int D,
-                                                            f16_t* __restrict__ planes, uint32_t* __restrict__ pscale, int sq_rows) {
-    const int64_t n = (int64_t)(n0 + n1) * D;
-    float sc = 1.0f;
-    if (pscale) {           // pscale[1 ..] = the partials of absmax_bits_kernel; pscale[0] <- their maximum, for the kernels behind this one
-        const uint32_t bits = absmax_fold(pscale + 1);
-        if (blockIdx.x == 0 && threadIdx.x == 0) *pscale = bits;
-        sc = pow2_scale_of_bits(bits);
-    }
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int64_t r = i / D;
-        const float v = (r < n0 ? A[i] : B[i - (int64_t)n0 * D]) * (r < sq_rows ? sc * sc : sc);
-        const f16_t a = static_cast<f16_t>(v);
-        planes[i] = a;
-        planes[n + i] = static_cast<f16_t>(v - static_cast<float>(a));
-    }
 }
 
 // one wave per embedding: exact statistics of the top-`top` of its candidates; rows that cannot be decided are flagged.
@@ -792,15 +423,6 @@ __global__ __launch_bounds__(256) void scatter_stats_kernel(const float* __restr
     sigma[ids[i]] = s[i];
 }
 
-template <int D>
-hipError_t launch_fused_d(const AsnormFusedParams& p, hipStream_t stream) {
-    static DeviceOnce attr;
-    const int lds = 2 * 32 * D * 4;
-    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(asnorm_fused_kernel<D>), lds)) return e;
-    hipLaunchKernelGGL((asnorm_fused_kernel<D>), dim3((unsigned)((p.N + 127) / 128)), dim3(256), lds, stream, p);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 bool asnorm_fused_supported(int D, int K, int top) {
@@ -829,12 +451,8 @@ size_t asnorm_planes_bytes(int D, int K) { return (size_t)3 * (D + 32 + K) * D *
 
 hipError_t launch_asnorm_planes(const float* MB, const float* cohort, int K, int D, void* planes, hipStream_t stream, uint32_t* pscale) {
     if (!MB || !cohort || !planes || K <= 0 || D % 32 != 0) return hipErrorInvalidValue;
-    const int64_t n = (int64_t)(D + 32 + K) * D;
-    const int64_t g = (n + 255) / 256;
-    if (pscale)             // the cohort's max |x| -> pscale[1 ..] (partials; the split pass folds them into pscale[0]); cohort rows and the mean row are scaled by s, the D moment rows by s^2
-        hipLaunchKernelGGL(absmax_bits_kernel, dim3(ABSMAX_WGS), dim3(256), 0, stream, cohort, (int64_t)K * D, pscale + 1);
-    hipLaunchKernelGGL(split2_planes_kernel, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, stream, MB, D + 32, cohort, K, D, reinterpret_cast<f16_t*>(planes), pscale, D);
-    return hipGetLastError();
+    // (with pscale: cohort rows and the mean row are scaled by s, the D moment rows by s^2)
+    return launch_split_planes(MB, D + 32, cohort, K, D, planes, pscale, D, stream);
 }
 
 hipError_t launch_asnorm_fused(const AsnormFusedParams& p, int D, hipStream_t stream) {
@@ -842,28 +460,16 @@ hipError_t launch_asnorm_fused(const AsnormFusedParams& p, int D, hipStream_t st
     if (!asnorm_fused_supported(D, p.K, 1) || !p.E || !p.cohort || !p.MB || !p.cand || !p.cnt) return hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(p.E) | reinterpret_cast<uintptr_t>(p.cohort) | reinterpret_cast<uintptr_t>(p.MB)) & 15) return hipErrorInvalidValue;
     if (p.nlists != (p.planes ? 4 : 2)) return hipErrorInvalidValue;      // (four lists: the half-plane kernel; two: the fp32-MFMA kernel)
-    if (p.planes) {                                       // the split form: three fp16 MFMAs on two half planes
+    const dim3 grid((unsigned)((p.N + 127) / 128));       // (D is 192 or 256: asnorm_fused_supported)
+    if (p.planes) {                                      // the split form: three fp16 MFMAs on two half planes
         if ((D != 192 && D != 256) || (reinterpret_cast<uintptr_t>(p.planes) & 15) || p.N > (int64_t)1 << 21) return hipErrorInvalidValue;      // (32-bit lane offsets)
         if (p.N * 2 * ASNORM_CAND_PER_LANE * 4 >= (int64_t)1 << 32) return hipErrorInvalidValue;      // (32-bit byte offsets into the candidate lists)
         if (p.pscale && !p.rowscale) return hipErrorInvalidValue;                                       // (scaled planes: the row factors go with them)
-        const dim3 grid((unsigned)((p.N + 127) / 128));
-#define SV_H3W(DD)                                                                                                          \
-        {                                                                                                                   \
-            static DeviceOnce attrw;                                                                                        \
-            constexpr int ldsw = 2 * 2 * 32 * DD * 2;                                                                       \
-            if (hipError_t e = set_max_dynamic_lds(attrw, reinterpret_cast<const void*>(asnorm_h3w_kernel<DD>), ldsw)) return e; \
-            hipLaunchKernelGGL((asnorm_h3w_kernel<DD>), grid, dim3(256), ldsw, stream, p);                                  \
-            return hipGetLastError();                                                                                       \
-        }
-        if (D == 192) SV_H3W(192)
-        SV_H3W(256)
-#undef SV_H3W
+        if (D == 192) return launch_max_lds<AsnormFusedParams, asnorm_h3w_kernel<192>>(grid, h3w_lds_bytes(192), p, stream);
+        return launch_max_lds<AsnormFusedParams, asnorm_h3w_kernel<256>>(grid, h3w_lds_bytes(256), p, stream);
     }
-    switch (D) {
-        case 192: return launch_fused_d<192>(p, stream);
-        case 256: return launch_fused_d<256>(p, stream);
-        default: return hipErrorInvalidValue;
-    }
+    if (D == 192) return launch_max_lds<AsnormFusedParams, asnorm_fused_kernel<192>>(grid, 2 * 32 * 192 * 4, p, stream);
+    return launch_max_lds<AsnormFusedParams, asnorm_fused_kernel<256>>(grid, 2 * 32 * 256 * 4, p, stream);
 }
 
 hipError_t launch_asnorm_cand_stats(const float* cand, const int32_t* cnt, int64_t rows, int top, float* mu, float* sigma, int64_t row_base,
@@ -942,43 +548,6 @@ hipError_t launch_scatter_stats(const float* m, const float* s, const int32_t* i
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(scatter_stats_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, m, s, ids, n, mu, sigma);
     return hipGetLastError();
-}
-
-bool score_h3w_supported(int D, int64_t Na, int64_t Nb) { return (D == 192 || D == 256) && Na > 0 && Nb > 0 && Nb < ((int64_t)1 << 30) && Na < ((int64_t)1 << 31); }
-size_t score_h3w_planes_bytes(int D, int64_t Nb) { return (size_t)2 * Nb * D * 2 + 2048; }      // two half planes + the scale word of B and its 256 partials behind them
-
-// out (Na, ldo) = A (Na, D) . B (Nb, D)^T; `planes` = score_h3w_planes_bytes of scratch (filled here with the half parts of B)
-hipError_t launch_score_h3w(const float* A, int64_t Na, const float* B, int64_t Nb, int D, float* out, int64_t ldo, void* planes, int num_cu,
-                            hipStream_t stream) {
-    if (!score_h3w_supported(D, Na, Nb) || !A || !B || !out || !planes || ldo < Nb) return hipErrorInvalidValue;
-    if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(planes)) & 15) return hipErrorInvalidValue;
-    const int64_t n = Nb * D;
-    const int64_t g = (n + 255) / 256;
-    uint32_t* pscale = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(planes) + (size_t)2 * Nb * D * 2);      // (16-byte aligned: Nb * D * 4 bytes in)
-    hipLaunchKernelGGL(absmax_bits_kernel, dim3(ABSMAX_WGS), dim3(256), 0, stream, B, n, pscale + 1);
-    hipLaunchKernelGGL(split2_planes_kernel, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, stream, B, 0, B, (int)Nb, D, reinterpret_cast<f16_t*>(planes), pscale, 0);
-    ScoreH3Params p;
-    p.A = A; p.Na = Na; p.planes = planes; p.Nb = (int)Nb; p.out = out; p.ldo = ldo; p.pscale = pscale;
-    const int panels = (int)((Na + 127) / 128), nb_all = (int)((Nb + 31) / 32);
-    // column slices: enough workgroups for ~4 per CU, at least 8 blocks per slice
-    int slices = (4 * (num_cu > 0 ? num_cu : 256) + panels - 1) / panels;
-    if (slices > (nb_all + 7) / 8) slices = (nb_all + 7) / 8;
-    if (slices < 1) slices = 1;
-    if (slices > 65535) slices = 65535;
-    p.per = (nb_all + slices - 1) / slices;
-    slices = (nb_all + p.per - 1) / p.per;
-    const dim3 grid((unsigned)panels, (unsigned)slices);
-#define SV_SC(DD)                                                                                                           \
-    {                                                                                                                       \
-        static DeviceOnce attr;                                                                                             \
-        constexpr int lds = 2 * 2 * 32 * DD * 2 + (DD == 192 ? 4 * 8192 : 0);     /* + the waves' store images (score_h3w_kernel) */ \
-        if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(score_h3w_kernel<DD>), lds)) return e;    \
-        hipLaunchKernelGGL((score_h3w_kernel<DD>), grid, dim3(256), lds, stream, p);                                        \
-        return hipGetLastError();                                                                                           \
-    }
-    if (D == 192) SV_SC(192)
-    SV_SC(256)
-#undef SV_SC
 }
 
 }  // namespace svhip

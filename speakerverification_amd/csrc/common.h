@@ -168,7 +168,7 @@ __device__ __forceinline__ void x3_split2(float a, float b, uint32_t& hd, uint32
     ld = __builtin_bit_cast(uint32_t, x3x2_t{x3_lo(a, ha), x3_lo(b, hb)});
 }
 
-// ---- exact power-of-two operand scaling of the half-plane forms (asnorm_fused.hip "operand scaling"; elementwise.hip / gemm_pw3.hip: the
+// ---- exact power-of-two operand scaling of the half-plane forms (split_planes.hip "operand scaling"; elementwise.hip / gemm_pw3.hip: the
 // network input of F32X3 handles, round 6) ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float pow2_scale_of_bits(uint32_t bits) {      // s = 2^k with (max |x|) * s in [64, 128)
     const int e = (int)((bits >> 23) & 255u);

@@ -28,6 +28,14 @@ inline hipError_t set_max_dynamic_lds(DeviceOnce& once, const void* fn, int byte
     if (e == hipSuccess) once.mark(dev);
     return e;
 }
+// a 256-thread kernel over one parameter struct that needs `lds` bytes of dynamic LDS: raise its limit once per device, launch
+template <class P, void (*Kernel)(P)>
+hipError_t launch_max_lds(const dim3& grid, int lds, const P& p, hipStream_t stream) {
+    static DeviceOnce attr;         // (one per kernel: a static of the template instance)
+    if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(Kernel), lds)) return e;
+    hipLaunchKernelGGL(Kernel, grid, dim3(256), lds, stream, p);
+    return hipGetLastError();
+}
 
 // ---------------------------------------------------------------------------------------------
 // Tiled MFMA GEMM with fused conv-gather prologue and bias/activation/BN epilogue.
@@ -667,7 +675,12 @@ struct AsnormFusedParams {
                                     // domain) back to scores: asnorm_cand_stats multiplies mu and sigma by it
     const uint32_t* pscale = nullptr;   // the 16-wide half-plane kernel: max-|x| word of the cohort the planes were scaled by (launch_asnorm_planes)
 };
-// dense score matrix on half planes / 16x16x32 fp16 MFMAs (asnorm_fused.hip): out (Na, ldo) = A (Na, D) . B (Nb, D)^T, D = 192 / 256
+// The streamed operand of the half-plane kernels (split_planes.hip): rows [0, n0) of A, then the n1 rows of B, as two half planes
+// [2][n0 + n1][D] (hi, lo).  With pscale — 257 device words — the max |x| of B goes to pscale[0] (its partials behind it) and every row is
+// multiplied by the exact power of two that brings that maximum into [64, 128), the first sq_rows rows by its square ("operand scaling")
+hipError_t launch_split_planes(const float* A, int n0, const float* B, int n1, int D, void* planes, uint32_t* pscale, int sq_rows,
+                               hipStream_t stream);
+// dense score matrix on half planes / 16x16x32 fp16 MFMAs (score_h3w.hip): out (Na, ldo) = A (Na, D) . B (Nb, D)^T, D = 192 / 256
 struct ScoreH3Params {
     const float* A = nullptr;
     int64_t Na = 0;
@@ -676,7 +689,7 @@ struct ScoreH3Params {
     float* out = nullptr;
     int64_t ldo = 0;
     int per = 0;                    // blocks of 32 rows of B per workgroup (column slice)
-    const uint32_t* pscale = nullptr;   // max-|x| word of B: the planes hold B * 2^k (asnorm_fused.hip, "operand scaling")
+    const uint32_t* pscale = nullptr;   // max-|x| word of B: the planes hold B * 2^k (split_planes.hip, "operand scaling")
 };
 bool score_h3w_supported(int D, int64_t Na, int64_t Nb);
 size_t score_h3w_planes_bytes(int D, int64_t Nb);

@@ -11,7 +11,7 @@ ROUTES (restated below, each with the function it restates)
                        four forms of the selection (score.hip::topk_stats_form): reg8 (K <= 2048), reg24 (K <= 6144), lds (Kp <= 37 888,
                        4 / 3 / 2 / 1 rows per workgroup) and global (longer rows, read from the slab on every pass).
   svhip_score_matrix   option score_f32mfma first; the row-streaming kernel for D in {192, 256} with 16-byte aligned operands
-                       (asnorm_fused.hip::score_h3w_supported, api_scoring.hip::score_route); the tiled split GEMM otherwise.
+                       (score_h3w.hip::score_h3w_supported, api_scoring.hip::score_route); the tiled split GEMM otherwise.
   pair kernels         16-byte loads when D % 4 == 0 and E is 16-byte aligned, element loads otherwise (score.hip::pair_kernel).
 
 BARS.  None is taken from what the kernels give.
@@ -34,7 +34,7 @@ REG8_MAX_K, REG24_MAX_K = 256 * 8, 256 * 24           # score.hip::topk_stats_fo
 LDS_ROW_BUDGET = 150 * 1024           # score.hip::topk_stats_form: bytes of rows per workgroup of the LDS form
 LDS_MAX_ROWS = 4
 FAST_MAX_TOP = 256                    # score.hip: the threshold fast path runs for top <= 256 and K >= 4 top
-FUSED_WIDTHS = (192, 256)             # asnorm_fused.hip::asnorm_fused_supported, score_h3w_supported
+FUSED_WIDTHS = (192, 256)             # asnorm_fused.hip::asnorm_fused_supported, score_h3w.hip::score_h3w_supported
 FUSED_MIN_K = 64
 SLAB_BYTES, SLAB_MIN_ROWS = 1 << 31, 128              # api_scoring.hip::SlabWalk
 BIG_SCRATCH = 256 << 20               # api_scoring.hip::release_big_scratch
@@ -87,7 +87,7 @@ def asnorm_route(D, K, top, aligned=True, slab_option=False):
 
 
 def score_h3w_supported(D, Na, Nb):
-    """asnorm_fused.hip::score_h3w_supported"""
+    """score_h3w.hip::score_h3w_supported"""
     return D in FUSED_WIDTHS and Na > 0 and 0 < Nb < (1 << 30) and Na < (1 << 31)
 
 

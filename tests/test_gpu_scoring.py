@@ -118,12 +118,15 @@ def test_score_matrix(eng):
     assert float(np.abs(got - want).max()) <= 1e-6
 
 
-@pytest.mark.parametrize("Na,Nb,D", [(300, 517, 192), (1, 5, 192), (129, 64, 256), (1000, 4096, 192), (260, 33, 256), (70, 130, 64)])
+@pytest.mark.parametrize("Na,Nb,D", [(300, 517, 192), (1, 5, 192), (129, 64, 256), (1000, 4096, 192), (260, 33, 256), (70, 130, 64),
+                                      (130, 637, 192), (130, 637, 256)])
 def test_score_matrix_row_streaming_kernel_against_the_tiled_one(Na, Nb, D):
     """Round 4: D = 192 / 256 score matrices run on score_h3w (rows of A in registers as half hi | lo parts, B streamed past them as half
     planes, three fp16 16x16x32 MFMAs per product block, scores stored from the accumulators); option score_tiled keeps the tiled split
     GEMM.  Both against the float64 product: ragged sizes (single rows, Nb not a multiple of 4 or 32, several column slices), host and
-    device operands; D = 64 takes the tiled kernel either way."""
+    device operands; D = 64 takes the tiled kernel either way.  130 x 637: 20 blocks of B, the last one ragged, in 3 column slices of
+    7, 7 and 6 on any chip ((20 + 7) / 8 caps the count) — the first two slices of the staged D = 192 form end on a half-filled store image
+    that is not the matrix's last block — and a wave with two rows inside A."""
     import torch
     eng = Engine(model="none", max_batch=1)
     rng = np.random.Generator(np.random.PCG64(Na * 7 + Nb))
@@ -321,7 +324,7 @@ def test_half_plane_score_kernels_take_operands_of_any_magnitude(sa, sb, D):
     """since round 4 the dense score GEMMs and the AS-norm kernel carry their operands as IEEE-half hi | lo planes — on
     every handle, the 'exact' scoring handle included — and the reference scores RAW embeddings when `normalize` is off.  Round 4 clamped
     |x| > 65504 silently and lost the low bits of components below 2^-3.  Round 5 scales every operand by an exact power of two first
-    (a row by its own max |x|, the streamed matrix by its global max |x|; asnorm_fused.hip "operand scaling"): embeddings of norm 3e5,
+    (a row by its own max |x|, the streamed matrix by its global max |x|; split_planes.hip "operand scaling"): embeddings of norm 3e5,
     1e-6, 7e6 x 2e-7 ... against the float64 statement, relative to |a| |b| — the bar of the unit-vector test, 2e-7.  One row holds a
     component 2^-20 of its largest (it must not vanish), one is all zeros."""
     eng = Engine(model="none", max_batch=1)

@@ -50,7 +50,7 @@ def test_route_predicates_restate_the_api_and_the_fused_kernels():
     fused = _src("speakerverification_amd", "csrc", "asnorm_fused.hip")
     assert "return (D == 192 || D == 256) && top >= 1 && top <= 256 && K >= 4 * top && K >= 64;" in _body(fused, "bool asnorm_fused_supported(")
     assert ("bool score_h3w_supported(int D, int64_t Na, int64_t Nb) { return (D == 192 || D == 256) && Na > 0 && Nb > 0 && "
-            "Nb < ((int64_t)1 << 30) && Na < ((int64_t)1 << 31); }") in fused
+            "Nb < ((int64_t)1 << 30) && Na < ((int64_t)1 << 31); }") in _src("speakerverification_amd", "csrc", "score_h3w.hip")
     api = _src("speakerverification_amd", "csrc", "api_scoring.hip")
     # the slab geometry is SlabWalk's, with asnorm_stats_slab's cohort of K rows as its B operand of M rows
     walk = _body(api, "struct SlabWalk {", "\n};\n")
