@@ -465,6 +465,34 @@ int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, con
  *                  or alignment: slabs of score_matrix's GEMM and a row kernel that counts, then compacts, a slab row in index order
  *                  ("score_above_gemm", "score_above_rows"); the refusals of score_topk's slab route hold (D % 32 != 0 and
  *                  M > 4 194 304: SVHIP_ERR_UNSUPPORTED before anything is launched), and so does its magnitude contract.
+ *   group_audit  : dataset audit ("which files of a speaker folder do not sound like the rest of it?", the label-noise audit of the
+ *                  reference's src/benchmark/benchmark_dataset.py:32-84): per file the number of files of its OWN group it does not match.
+ *                  Inputs: F (n_files, n_crops, D) fp32 crop embeddings, the files sorted by group; group_ptr[n_groups + 1] int64, ALWAYS
+ *                  a host pointer whatever `flags` say, group_ptr[0] = 0, non-decreasing, group_ptr[n_groups] = n_files: group g is the
+ *                  files group_ptr[g] .. group_ptr[g + 1] - 1 (empty groups and groups of one file are legal); cut, a float.  For two
+ *                  files i, j of the SAME group
+ *                      s(i, j) = ( sum_c | dot(F[i,c], F[j,c]) / (max(sqrt(|F[i,c]|^2), 1e-5f) * max(sqrt(|F[j,c]|^2), 1e-5f)) | ) / (float)n_crops
+ *                  - SVHIP_TRIAL_COSINE's statement (utils.py:163-164), the crops added in index order, one final division.  (i, j) is a
+ *                  MISMATCH iff s(i, j) <= cut; a NaN score is never a mismatch (the reference's check_matching turns it into a match).
+ *                  out_miss[i] (int32[n_files]) = the number of files j != i of i's group that i mismatches (the reference's
+ *                  imposters[file]).  out_score is optional (NULL: not wanted): the dense per-group score blocks back to back, block g
+ *                  starting at the sum of n_h^2 over the groups h < g, row-major n_g x n_g, both (i, j) and (j, i) written, the diagonal
+ *                  written as computed and never counted; the caller allocates sum n_g^2 floats.  Promises, on each route: s(i, j) and
+ *                  s(j, i) are the same bits; a file's count and its row of scores depend only on the rows of its own group and on cut -
+ *                  not on the other groups, on the group's place in F, on n_files or n_groups or on the launch geometry: bit for bit; a
+ *                  NaN / inf element changes only scores of its own file.  n_files = 0 or n_groups = 0: SVHIP_OK, nothing is read or
+ *                  written.  SVHIP_ERR_INVALID before any copy or launch (messages start "group_audit:"): n_crops < 1, D < 1, a NULL F,
+ *                  group_ptr or out_miss, group_ptr[0] != 0, a decrease, group_ptr[n_groups] != n_files; more than 2^31 - 1 files:
+ *                  SVHIP_ERR_UNSUPPORTED.  Pointer spaces (F in, out_miss / out_score out) and SVHIP_ASYNC as score_topk;
+ *                  group_ptr has been read when the call returns (its device copy is waited for, so an asynchronous call also waits
+ *                  for what the handle's stream held before it).
+ *                  Routes, from D and the alignment of the device F alone.  D % 32 == 0, D <= 1024, 16-byte aligned: the MFMA kernel
+ *                  (csrc/group_audit.hip: 64 x 64 tiles on the file axis, small groups share a tile under a block-diagonal mask, exact
+ *                  fp32 v_mfma_f32_32x32x2_f32, the upper triangle of the join computed once and counted for both files with integer
+ *                  atomics, the norms from the tile's own loads; profile labels "group_audit_tables", "group_audit"): within (2 D + n_crops + 16) * 2^-24
+ *                  of the float64 statement on unit rows.  Every other width or alignment: chunks of 2^21 within-group pairs are
+ *                  enumerated on the device, scored by score_trials' kernel and counted ("group_audit_tables", then per chunk
+ *                  "group_audit_pairs", "score_trials", "group_audit_count"): a score's bits are svhip_score_trials(SVHIP_TRIAL_COSINE)'s.
  * Pointers follow `flags` (indices are int32, device or host like the other inputs). */
 int svhip_l2norm(svhip_handle* h, float* E, int64_t N, int32_t D, int32_t flags);
 int svhip_score_pairs(svhip_handle* h, const float* E, int64_t N, int32_t D,
@@ -491,6 +519,10 @@ int svhip_score_above_fill(svhip_handle* h, const float* Q, int64_t N, const flo
                            const float* q_mu, const float* q_sigma, const float* g_mu, const float* g_sigma,
                            int64_t q_base, int32_t mode, const int64_t* row_ptr /* int64[N + 1] */,
                            int32_t* out_index, float* out_score, int32_t flags);
+/* dataset audit (group_audit above): group_ptr is always a HOST array; out_score may be NULL. */
+int svhip_group_audit(svhip_handle* h, const float* F, int64_t n_files, int32_t n_crops, int32_t D,
+                      const int64_t* group_ptr /* host, int64[n_groups + 1] */, int64_t n_groups, float cut,
+                      int32_t* out_miss /* int32[n_files] */, float* out_score /* sum n_g^2 floats, or NULL */, int32_t flags);
 int svhip_asnorm_pairs(svhip_handle* h, const float* E, int64_t N, int32_t D, const float* mu,
                        const float* sigma, const int32_t* ia, const int32_t* ib, int64_t P,
                        float* out, int32_t flags);

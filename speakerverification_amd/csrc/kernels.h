@@ -783,6 +783,35 @@ hipError_t launch_score_above_rows(const float* S, int64_t rows, int64_t M, int6
                                    const float2* gcoef, int64_t* out_count, const int64_t* row_ptr, int64_t row0, unsigned long long* bad,
                                    int32_t* out_index, float* out_score, hipStream_t stream);
 
+// Dataset audit (group_audit.hip): files sorted by group; s(i, j) = mean_c | cos(F[i, c], F[j, c]) | (launch_trial_crops mode 0's
+// statement) for the files of one group, a mismatch iff s <= cut; miss[i] counts the files j != i of i's group that i mismatches.
+// Per-file tables (launch_group_audit_tables, from the device copy of group_ptr): gs / ge = where the file's group starts / ends,
+// sbase = where its group's n_g x n_g score block starts (sq[g] = the sum of n_h^2 over the groups before g; only with scores).
+// Both routes compute the pairs j >= i once and count / write them for both files; `miss` must be zero before the first launch.
+struct GroupAuditParams {
+    const float* F = nullptr;       // (n_files, n_crops, D), 16-byte aligned
+    int64_t n_files = 0;
+    int n_crops = 0, D = 0;
+    const int32_t* gs = nullptr;
+    const int32_t* ge = nullptr;
+    const int64_t* sbase = nullptr; // with score
+    float cut = 0.0f;
+    int32_t* miss = nullptr;
+    float* score = nullptr;         // optional: the dense per-group blocks, back to back
+};
+bool group_audit_mfma_supported(int D);      // D % 32 == 0, D <= 1024 (and a 16-byte aligned F: the caller's check)
+hipError_t launch_group_audit_tables(const int64_t* gp, int64_t n_groups, const int64_t* sq, int64_t n_files, int32_t* gs, int32_t* ge, int64_t* sbase,
+                                     hipStream_t stream);
+// the MFMA route: 64 x 64 tiles on the file axis; max_cols = the most column tiles any row tile meets (a bound is enough: a workgroup
+// whose column tile starts past its row tile's last group exits at once)
+hipError_t launch_group_audit(const GroupAuditParams& p, int64_t max_cols, hipStream_t stream);
+// the plain route: pairs [p0, p0 + P) of the call's list of within-group pairs j >= i (pp[g] = the pairs before group g, n_groups + 1
+// entries) -> ia / ib; then launch_trial_crops(mode 0); then the comparison, the counts and the scatter of the scores
+hipError_t launch_group_audit_pairs(const int64_t* gp, const int64_t* pp, int64_t n_groups, int64_t p0, int64_t P, int32_t* ia, int32_t* ib,
+                                    hipStream_t stream);
+hipError_t launch_group_audit_count(const float* sc, const int32_t* ia, const int32_t* ib, int64_t P, float cut, const int32_t* gs, const int32_t* ge,
+                                    const int64_t* sbase, int32_t* miss, float* score, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // Verification metrics (metrics.hip): one workspace of metrics_workspace_bytes(P) holds the sorted trial list
 // ---------------------------------------------------------------------------------------------

@@ -634,6 +634,61 @@ class Engine:
             _count([q, g, *st, r], [i, s])
         return row_ptr, index, score
 
+    @staticmethod
+    def _audit_group_ptr(group_ptr, n_files):
+        """``group_audit``'s group table as a contiguous host int64 array, checked by the C ABI's rules (a bad one is a
+        ``ValueError`` that names the entry, raised before anything is allocated or launched)"""
+        if _is_torch(group_ptr):
+            group_ptr = group_ptr.detach().cpu().numpy()
+        gp = np.ascontiguousarray(np.asarray(group_ptr).ravel(), dtype=np.int64)
+        if gp.size < 1:
+            raise ValueError("group_audit: group_ptr needs at least one entry (n_groups + 1)")
+        if gp[0] != 0:
+            raise ValueError(f"group_audit: group_ptr[0] = {int(gp[0])} is not 0")
+        down = np.nonzero(np.diff(gp) < 0)[0]
+        if down.size:
+            g = int(down[0]) + 1
+            raise ValueError(f"group_audit: group_ptr decreases at entry {g} ({int(gp[g])} after {int(gp[g - 1])})")
+        if gp[-1] != n_files:
+            raise ValueError(f"group_audit: group_ptr[n_groups] = {int(gp[-1])} is not n_files = {n_files}")
+        return gp
+
+    def group_audit(self, F, group_ptr, cut, scores=False):
+        """Dataset audit (``svhip_group_audit``): F (n_files, n_crops, D) crop embeddings, the files sorted by group; ``group_ptr``
+        (n_groups + 1, a host array whatever F is): group g is the files ``group_ptr[g]:group_ptr[g + 1]``.  The score of two files of
+        one group is ``score_trials(mode="cosine")``'s mean |cos| over the aligned crops; they MISMATCH iff it is ``<= cut`` (a NaN
+        score never is).  Returns ``miss`` (n_files,) int32: per file the number of OTHER files of its group it mismatches.  With
+        ``scores=True``: ``(miss, score, score_ptr)``, ``score[score_ptr[g]:score_ptr[g + 1]]`` being the row-major n_g x n_g score
+        block of group g (symmetric bit for bit; the diagonal is written and never counted).  numpy in, numpy out; a CUDA tensor in,
+        CUDA tensors out (``score_ptr`` is always a host int64 array)."""
+        if F.ndim != 3:
+            raise ValueError(f"group_audit: F must be (n_files, n_crops, D), not {tuple(F.shape)}")
+        n_files, n_crops, D = (int(x) for x in F.shape)
+        gp = self._audit_group_ptr(group_ptr, n_files)
+        if n_crops < 1 or D < 1:
+            raise ValueError(f"group_audit: n_crops = {n_crops} and D = {D} must be at least 1")
+        n_groups = gp.size - 1
+        sizes = np.diff(gp)
+        score_ptr = np.zeros(n_groups + 1, np.int64)
+        np.cumsum(sizes * sizes, out=score_ptr[1:])
+        on_dev = _is_torch(F) and F.is_cuda
+        empty = (lambda n, dt: torch.empty(n, dtype=getattr(torch, np.dtype(dt).name), device=F.device)) if on_dev else np.empty
+        miss = empty(n_files, np.int32)
+        score = empty(int(score_ptr[-1]), np.float32) if scores else None
+        if n_files and n_groups:
+            f, m = _Buf(F, np.float32), _Buf(miss, np.int32, writable=True)
+            bufs = [f, m]
+            s = None
+            if scores and score_ptr[-1]:
+                s = _Buf(score, np.float32, writable=True)
+                bufs.append(s)
+            dev = self._same_space(*bufs)
+            self._ck(self.lib.svhip_group_audit(self.h, f.ptr, n_files, n_crops, D, gp.ctypes.data, n_groups, float(cut), m.ptr,
+                                                s.ptr if s is not None else None, (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
+            TRANSFER_STATS["h2d_bytes"] += gp.nbytes
+            _count([f], bufs[1:])
+        return (miss, score, score_ptr) if scores else miss
+
     # ---- verification metrics (host arrays in / out; the trial list is small next to the embeddings) --------------------
     def _scores_labels(self, scores, labels):
         if _is_torch(scores):

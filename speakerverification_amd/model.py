@@ -661,6 +661,78 @@ class ModelHandling:
             return i, j, s
         return i, j, s, [(classes[int(a)], classes[int(b)]) for a, b in zip(i, j)]
 
+    # ---- dataset audit ----------------------------------------------------------------------------------------------------
+    def audit(self, source, thresh_score, num_eval=20, save_file=None, max_files=65536):
+        """Which files of a speaker folder do not sound like the rest of it?  The reference's label-noise audit
+        (src/benchmark/benchmark_dataset.py:32-84): every file is embedded as ``embed_utterance(num_eval, normalize=True)`` does, ALL
+        pairs of files of a folder are scored with ``similarity_measure('cosine')`` (the mean over the crops of |cos|, crop c against
+        crop c) and a file's count is the number of partners it does not match under the reference's rule at ``thresh_score``
+        (``scoring.audit_cut``).
+
+        ``source``: a directory whose sub-directories are speakers (found as ``prepare('embed')`` finds them, ``*.wav`` inside), or
+        ``{name: [files]}``.  Whole folders are collected up to ``max_files`` files (a larger folder goes alone); each collection is
+        embedded in one ``_embed_files`` call (``num_eval=0``: whole files through the ragged path, one crop), every crop row is
+        L2-normalised, and ONE ``group_audit`` call counts - no pair list, no score leaves the device.
+
+        Returns, per folder in order, ``(folder, n_files, [(file, count), ...])`` with the files whose count is > 0, sorted by path.
+        ``save_file``: the reference's report text is appended to it, for the folders with at least one such file."""
+        self.__model__.eval()
+        if isinstance(source, dict):
+            folders = [(str(k), [str(f) for f in v]) for k, v in source.items()]
+        elif isinstance(source, (str, Path)):
+            folders = [(str(d), [str(f) for f in d.glob("*.wav")]) for d in Path(source).iterdir() if d.is_dir()]
+        else:
+            raise ValueError("Please provide appropriate source!")
+        max_files = int(max_files)
+        if max_files < 1:
+            raise ValueError(f"max_files = {max_files} must be at least 1")
+        on_dev = self._feats_on_device()
+        eng = scoring.scoring_engine(self.gpu)
+        counts = [None] * len(folders)
+
+        def run(batch):
+            files = [f for g in batch for f in folders[g][1]]
+            if not files:
+                for g in batch:
+                    counts[g] = np.zeros(0, np.int32)
+                return
+            feats = self._embed_files(files, num_eval, on_device=on_dev)
+            if _is_torch(feats) and feats.is_cuda:
+                feats = feats.contiguous()
+                eng.l2norm_(feats.view(-1, feats.shape[-1]))                 # embed_utterance(normalize=True)
+            else:
+                flat = np.ascontiguousarray(np.asarray(_host(feats), np.float32).reshape(-1, feats.shape[-1]))
+                eng.l2norm_(flat)
+                feats = flat.reshape(feats.shape)
+            group_ptr = np.zeros(len(batch) + 1, np.int64)
+            np.cumsum([len(folders[g][1]) for g in batch], out=group_ptr[1:])
+            miss = np.asarray(_host(scoring.group_audit(feats, group_ptr, thresh_score, device=self.gpu)))
+            for k, g in enumerate(batch):
+                counts[g] = miss[group_ptr[k]:group_ptr[k + 1]]
+
+        batch, held = [], 0
+        for g, (_, fl) in enumerate(folders):
+            if batch and held + len(fl) > max_files:
+                run(batch)
+                batch, held = [], 0
+            batch.append(g)
+            held += len(fl)
+        if batch:
+            run(batch)
+
+        result = []
+        for (folder, fl), c in zip(folders, counts):
+            result.append((folder, len(fl), sorted((f, int(n)) for f, n in zip(fl, c) if n > 0)))
+        if save_file:
+            with open(save_file, "a+") as fh:
+                for folder, n, found in result:
+                    if found:
+                        fh.write(f"Folder:{folder}\n")
+                        for f, cnt in found:
+                            fh.write(f"[{cnt}/{n}] - {f}\n")
+                        fh.write("//================//\n")
+        return result
+
     # ---- checkpoints ------------------------------------------------------------------------------------------------------
     def saveParameters(self, path):
         torch.save(self.__model__.module.state_dict(), path)

@@ -1,7 +1,7 @@
 """Scoring counterparts of the reference's ``src/utils.py:126-169``.
 
 ``similarity_measure(method, ref, com, **kw)`` keeps the per-trial signature for compatibility; the
-batched entry points (``score_pairs``, ``score_matrix``, ``score_topk``, ``score_topk_norm``, ``score_above``, ``asnorm_stats``,
+batched entry points (``score_pairs``, ``score_matrix``, ``score_topk``, ``score_topk_norm``, ``score_above``, ``group_audit``, ``asnorm_stats``,
 ``asnorm_pairs``, ``score_trials``) are what ``ModelHandling.evaluateFromList`` uses: one kernel launch per trial LIST
 instead of three host<->device crossings per trial.
 """
@@ -87,6 +87,43 @@ def score_above(Q, G, thr, cohort=None, top=200, g_stats=None, upper=False, q_ba
         g_stats = eng.asnorm_stats(G, cohort, top)
     q_stats = eng.asnorm_stats(Q, cohort, top)
     return eng.score_above(Q, G, thr, q_stats, g_stats, upper=upper, q_base=q_base, max_hits=max_hits)
+
+
+def audit_cut(threshold):
+    """The largest float32 score the reference's audit rule (src/benchmark/benchmark_dataset.py:24-29) calls a MISMATCH: with
+    ``ratio = threshold / 0.5`` a pair matches iff ``min(score / ratio, 1) > 0.5``, the float32 score divided in float64 (what numpy
+    1.x made of a float32 scalar over a Python float).  ``group_audit`` counts ``score <= audit_cut(threshold)``."""
+    threshold = float(threshold)
+    if not (threshold > 0.0 and np.isfinite(threshold)):
+        raise ValueError(f"audit_cut: the threshold must be a positive finite number, not {threshold}")
+    ratio = threshold / 0.5
+
+    def mismatch(s):
+        return not (min(float(s) / ratio, 1.0) > 0.5)
+
+    s = np.float32(threshold)
+    inf = np.float32(np.inf)
+    while not mismatch(s):
+        s = np.nextafter(s, -inf)
+    while mismatch(np.nextafter(s, inf)):
+        s = np.nextafter(s, inf)
+    return np.float32(s)
+
+
+def group_audit(feats, group_ptr, threshold, scores=False, device=0):
+    """The reference's label-noise audit (benchmark_dataset.py:32-84) over many folders at once.  ``feats``: (n_files, n_crops, D)
+    float32 crop embeddings (numpy, or a CUDA tensor that stays where it is), the files sorted by folder; ``group_ptr``: the folders'
+    boundaries (n_folders + 1).  Returns per file the number of files of its own folder it does not match under the reference's rule at
+    ``threshold`` (``audit_cut``); with ``scores=True`` also the per-folder score blocks (``Engine.group_audit``)."""
+    on_dev = _is_torch(feats) and feats.is_cuda
+    if not on_dev:
+        feats = np.ascontiguousarray(_np(feats), dtype=np.float32)
+    else:
+        feats = feats.contiguous()
+    if feats.ndim == 2:
+        feats = feats[:, None, :]
+    Engine._audit_group_ptr(group_ptr, int(feats.shape[0]))           # (refused here: before an engine is even created)
+    return scoring_engine(device).group_audit(feats, group_ptr, audit_cut(threshold), scores=scores)
 
 
 def asnorm_stats(E, cohort, top=200, device=0):
