@@ -1,7 +1,8 @@
 // api.hip — C ABI of libsvhip: handle lifetime, developer options, weight loading, embedding, staging, stages and profiling
 // (see include/svhip.h).  The handle is in handle.h; what the models share when weights are loaded in api_weights.hip, the conv-layer
 // GEMM in api_gemm.hip, what the ragged calls share in api_ragged.hip, each model's own host code and state in its api_<model>.hip
-// (kModels below lists them), scoring and metrics in api_scoring.hip.
+// (kModels below lists them); the scoring side in api_scoring.hip (what its calls share, the simple calls), api_asnorm.hip, api_search.hip,
+// api_audit.hip and api_metrics.hip, over scoring_host.h.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>

@@ -1,0 +1,304 @@
+// api_search.hip — the search calls of libsvhip (see include/svhip.h): top-k (score_topk.hip) and threshold search (score_above.hip)
+// over one gallery walk (score_walk.h).  Both decide their route from the shape and the pointers alone:
+//   fused  D = 192 / 256, 16-byte aligned operands: no score reaches memory.  fused_plan cuts the call into launches
+//   slab   every other width: SlabWalk writes slabs of query rows, a row kernel selects
+// and the calls with statistics take the same routes with the same parts and slabs: `qc` / `gc` are their tables of (a, b) pairs.
+#include <vector>
+
+#include "scoring_host.h"
+
+using namespace svhip;
+
+namespace {
+// One launch of the fused route: queries [r0, r0 + rows) of the call, `slices` gallery slices of `per` blocks of 32 rows.
+struct FusedPart { int64_t r0, rows; bool few; int slices, per; };
+
+// Queries go in chunks of 16 384; the whole 128-query tiles of a chunk run the shared-block form of the walk (MANY), a last tile of at most
+// 32 queries the form whose waves walk different gallery blocks (FEW).  Each launch cuts the gallery into enough slices to fill the chip:
+// two workgroups per CU (FEW: one, since every wave of it keeps lists of its own), a workgroup walks at least 8 (FEW: 16) gallery blocks.
+// slice_bytes[few]: the scratch a launch needs per (query, slice), held within 256 MiB per launch (0: the caller's scratch has no such cap).
+void fused_plan(int64_t N, int64_t M, int num_cu, const int64_t (&slice_bytes)[2], std::vector<FusedPart>& parts) {
+    constexpr int64_t CHUNK = 16384;
+    const int64_t nb_all = (M + 31) / 32;
+    const int cu = num_cu > 0 ? num_cu : 256;
+    auto add = [&](int64_t r0, int64_t rows, bool few) {
+        const int64_t tiles = few ? 1 : (rows + 127) / 128;
+        int64_t slices = ((few ? 1 : 2) * (int64_t)cu + tiles - 1) / tiles;
+        const int64_t min_blocks = few ? 16 : 8;
+        slices = std::min(slices, (nb_all + min_blocks - 1) / min_blocks);
+        if (slice_bytes[few]) slices = std::min(slices, std::max<int64_t>(1, ((int64_t)256 << 20) / (rows * slice_bytes[few])));
+        slices = std::max<int64_t>(1, std::min<int64_t>(slices, 65535));
+        const int64_t per = (nb_all + slices - 1) / slices;
+        parts.push_back({r0, rows, few, (int)((nb_all + per - 1) / per), (int)per});
+    };
+    for (int64_t r0 = 0; r0 < N; r0 += CHUNK) {
+        const int64_t rows = std::min(CHUNK, N - r0);
+        const int64_t tail = rows % 128;
+        const int64_t n_few = (tail >= 1 && tail <= 32) ? tail : 0, n_many = rows - n_few;
+        if (n_many) add(r0, n_many, false);
+        if (n_few) add(r0 + n_many, n_few, true);
+    }
+}
+
+// The coefficient tables of a call with statistics ({q_mu, q_sigma, g_mu, g_sigma}), once per call, in SCR_COEF:
+// [queries (N) | gallery (whole blocks of 32 rows), on a 16-byte boundary]
+int coef_tables(Staged& s, const char* label, const float* const* stats, int64_t N, int64_t M, const float2** qc, const float2** gc) {
+    svhip_handle* h = s.h;
+    const int slot[4] = {svhip_handle::SCR_IN2, svhip_handle::SCR_IN3, svhip_handle::SCR_IN4, svhip_handle::SCR_IN5};
+    const float* d[4];
+    for (int i = 0; i < 4; ++i) d[i] = s.in(slot[i], stats[i], (size_t)(i < 2 ? N : M) * 4);
+    if (s.rc) return s.rc;
+    Bump b;
+    const size_t o_q = b.take((size_t)N * 8), o_g = b.take((size_t)score_topk_coef_rows(M) * 8, 16);
+    void* c = nullptr;
+    if (int rc = scratch(h, svhip_handle::SCR_COEF, b.size, &c)) return rc;
+    float2* qcw = at<float2>(c, o_q);
+    float2* gcw = at<float2>(c, o_g);
+    *qc = qcw; *gc = gcw;
+    return run(h, label, 0, [&]() { return launch_score_topk_coef(d[0], d[1], N, d[2], d[3], M, qcw, gcw, h->stream); });
+}
+}  // namespace
+
+extern "C" {
+
+// one part of score_topk's fused route: its lists (SCR_TOPK, sized for this launch alone), the launch, its merge.  dQ, dS, dI, qc: the call's
+static int topk_fused_part(svhip_handle* h, const FusedPart& t, const float* dQ, const float* dG, int64_t M, int D, int k, float* dS, int32_t* dI,
+                           const float2* qc, const float2* gc) {
+    const int cap = score_topk_cap(k);
+    ScoreTopkParams p;
+    p.Q = dQ + t.r0 * D; p.N = t.rows; p.G = dG; p.M = M; p.k = k; p.cap = cap; p.per = t.per; p.nlists = t.slices * (t.few ? 8 : 2);
+    void* s = nullptr;
+    Bump b;
+    const size_t o_lists = b.take((size_t)t.rows * p.nlists * cap * 8), o_cnt = b.take((size_t)t.rows * p.nlists * 4);
+    if (int rc = scratch(h, svhip_handle::SCR_TOPK, b.size, &s)) return rc;
+    p.lists = at<uint2>(s, o_lists);
+    p.cnt = at<int32_t>(s, o_cnt);
+    p.qcoef = qc ? qc + t.r0 : nullptr; p.gcoef = gc;
+    if (int rc = run(h, qc ? "score_topk_norm" : "score_topk", 2.0 * t.rows * M * D, [&]() { return launch_score_topk(p, D, t.few, t.slices, h->stream); })) return rc;
+    return run(h, "score_topk_merge", 0, [&]() {
+        return launch_score_topk_merge(p.lists, p.cnt, t.rows, p.nlists, cap, k, dS + t.r0 * k, dI + t.r0 * k, h->stream);
+    });
+}
+
+static int topk_slab(svhip_handle* h, const char* name, const float* dQ, int64_t N, const float* dG, int64_t M, int D, int k, float* dS, int32_t* dI,
+                     const float2* qc, const float2* gc) {
+    SlabWalk w{h, dQ, N, dG, M, D};
+    if (int rc = w.open(name)) return rc;
+    return w.pass("score_topk_gemm", true, [&](int64_t r0, int64_t rows, const float* slab, int64_t ldk) {
+        return run(h, qc ? "score_topk_rows_norm" : "score_topk_rows", 0, [&]() {
+            return launch_score_topk_rows(slab, rows, M, ldk, k, dS + r0 * k, dI + r0 * k, h->stream, qc ? qc + r0 : nullptr, gc);
+        });
+    });
+}
+
+// both entry points: `stats` = {q_mu, q_sigma, g_mu, g_sigma} for the normalised call, NULL for the plain one; `name` prefixes the messages
+static int score_topk_impl(svhip_handle* h, const char* name, const float* Q, int64_t N, const float* G, int64_t M, const float* const* stats,
+                           int32_t D, int32_t k, float* out_score, int32_t* out_index, int32_t flags) {
+    if (!h) return SVHIP_ERR_INVALID;
+    if (k < 1 || k > SCORE_TOPK_MAX_K) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: k = %d is outside [1, %d]", name, (int)k, SCORE_TOPK_MAX_K);
+    if (M < 1 || M > (int64_t)INT32_MAX) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: M = %lld is outside [1, 2^31 - 1]", name, (long long)M);
+    if (k > M) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: k = %d exceeds the gallery's M = %lld rows", name, (int)k, (long long)M);
+    if (D < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: D = %d must be at least 1", name, (int)D);
+    if (N < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: N = %lld is negative", name, (long long)N);
+    if (N == 0) return SVHIP_OK;
+    if (!Q || !G || !out_score || !out_index) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: NULL pointer", name);
+    if (stats && (!stats[0] || !stats[1] || !stats[2] || !stats[3])) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: NULL pointer", name);
+    if (D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "%s: embedding dim %d must be a multiple of 32", name, (int)D);      // before any copy or launch
+    Staged s(h, flags);
+    const float* dQ = s.in(svhip_handle::SCR_IN0, Q, (size_t)N * D * 4);
+    const float* dG = s.in(svhip_handle::SCR_IN1, G, (size_t)M * D * 4);
+    float* dS = s.out(svhip_handle::SCR_OUT0, out_score, (size_t)N * k * 4);
+    int32_t* dI = s.out(svhip_handle::SCR_OUT1, out_index, (size_t)N * k * 4);
+    if (s.rc) return s.rc;
+    int rc;
+    const float2 *qc = nullptr, *gc = nullptr;
+    if (stats && (rc = coef_tables(s, "score_topk_coef", stats, N, M, &qc, &gc))) return rc;
+    if (score_topk_fused_supported(D) && aligned16(dQ, dG)) {
+        const int64_t list_bytes = (int64_t)score_topk_cap(k) * 8 + 4;      // a list and its count; 2 lists per slice, FEW 8
+        std::vector<FusedPart> parts;
+        fused_plan(N, M, h->num_cu, {2 * list_bytes, 8 * list_bytes}, parts);
+        for (const FusedPart& t : parts)
+            if ((rc = topk_fused_part(h, t, dQ, dG, M, D, k, dS, dI, qc, gc))) break;
+    } else {
+        rc = topk_slab(h, name, dQ, N, dG, M, D, k, dS, dI, qc, gc);
+    }
+    return s.finish(name, rc, true);
+}
+
+int svhip_score_topk(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, int32_t k, float* out_score,
+                     int32_t* out_index, int32_t flags) {
+    return score_topk_impl(h, "score_topk", Q, N, G, M, nullptr, D, k, out_score, out_index, flags);
+}
+
+int svhip_score_topk_norm(svhip_handle* h, const float* Q, int64_t N, const float* q_mu, const float* q_sigma, const float* G, int64_t M,
+                          const float* g_mu, const float* g_sigma, int32_t D, int32_t k, float* out_score, int32_t* out_index, int32_t flags) {
+    const float* stats[4] = {q_mu, q_sigma, g_mu, g_sigma};
+    return score_topk_impl(h, "score_topk_norm", Q, N, G, M, stats, D, k, out_score, out_index, flags);
+}
+
+// ---- threshold search: every gallery row at or above a score, as CSR rows (score_above.hip) -----------------------------------------------
+// Routes, fused_plan's parts and the slabs are score_topk's.  Both entry points count first (every launch of the call, into one scratch: a
+// few list counts per row); fill then reads ONE word back - the first row whose recount is not what row_ptr says - and writes only if there
+// is none, so no entry outside [0, row_ptr[N]) is ever touched.
+namespace {
+struct AboveArgs {
+    const float *dQ, *dG;
+    int64_t N, M;
+    int D;
+    float thr;
+    int upper;
+    int64_t q_base;
+    const float2 *qc, *gc;
+    int64_t* dCount;              // count
+    const int64_t* dRowPtr;       // fill
+    int32_t* dIndex;
+    float* dScore;
+    int64_t total;                // fill: row_ptr[N]
+};
+
+constexpr size_t ABOVE_GUARD_BYTES = 256;      // SCR_TOPK of both routes starts with the guard's word (the slab route holds nothing else there)
+// fill: the word the scan / row kernels lowered -> OK, or the refusal that names the row
+int above_guard(svhip_handle* h, const unsigned long long* bad) {
+    unsigned long long row = 0;
+    SV_HIP(h, hipMemcpyAsync(&row, bad, 8, hipMemcpyDeviceToHost, h->stream));
+    SV_HIP(h, hipStreamSynchronize(h->stream));
+    if (row != ~0ull)
+        SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: row %llu now holds another number of hits than row_ptr[%llu + 1] - row_ptr[%llu] (or row_ptr[0] is not 0): "
+                "the inputs changed between count and fill; nothing was written", row, row, row);
+    return SVHIP_OK;
+}
+
+int above_fused(svhip_handle* h, const AboveArgs& a) {
+    const bool fill = a.dRowPtr != nullptr;
+    std::vector<FusedPart> parts;
+    fused_plan(a.N, a.M, h->num_cu, {0, 0}, parts);
+    auto nl = [](const FusedPart& t) { return t.slices * (t.few ? 4 : 1); };      // lists per query
+    std::vector<size_t> first;                                                    // a part's place in the list-count scratch
+    size_t entries = 0;
+    for (const FusedPart& t : parts) {
+        first.push_back(entries);
+        entries += (size_t)t.rows * nl(t);
+    }
+    // [the guard's word | list counts (int32) | fill: list offsets (int64), on a 256-byte boundary]
+    Bump b;
+    const size_t o_bad = b.take(ABOVE_GUARD_BYTES), o_cnt = b.take(entries * 4), o_off = b.take(fill ? entries * 8 : 0, 256);
+    void* s = nullptr;
+    if (int rc = scratch(h, svhip_handle::SCR_TOPK, b.size, &s)) return rc;
+    unsigned long long* bad = at<unsigned long long>(s, o_bad);
+    int32_t* lcnt = at<int32_t>(s, o_cnt);
+    int64_t* loff = at<int64_t>(s, o_off);
+    if (fill) SV_HIP(h, hipMemsetAsync(bad, 0xff, 8, h->stream));
+    auto params = [&](size_t i) {
+        const FusedPart& t = parts[i];
+        ScoreAboveParams p;
+        p.Q = a.dQ + t.r0 * a.D; p.N = t.rows; p.G = a.dG; p.M = a.M; p.thr = a.thr; p.upper = a.upper; p.row_base = a.q_base + t.r0;
+        p.per = t.per; p.nl = nl(t); p.lcnt = lcnt + first[i]; p.loff = loff + first[i]; p.out_index = a.dIndex; p.out_score = a.dScore;
+        p.qcoef = a.qc ? a.qc + t.r0 : nullptr; p.gcoef = a.gc;
+        return p;
+    };
+    for (size_t i = 0; i < parts.size(); ++i) {
+        const FusedPart& t = parts[i];
+        const ScoreAboveParams p = params(i);
+        if (int rc = run(h, "score_above_count", 2.0 * t.rows * a.M * a.D, [&]() { return launch_score_above(p, a.D, t.few, t.slices, false, h->stream); })) return rc;
+        if (int rc = run(h, "score_above_scan", 0, [&]() {
+                return launch_score_above_scan(p.lcnt, t.rows, p.nl, fill ? nullptr : a.dCount + t.r0, fill ? a.dRowPtr + t.r0 : nullptr, t.r0,
+                                               fill ? loff + first[i] : nullptr, fill ? bad : nullptr, h->stream);
+            })) return rc;
+    }
+    if (!fill) return SVHIP_OK;
+    if (int rc = above_guard(h, bad)) return rc;
+    if (a.total == 0) return SVHIP_OK;
+    for (size_t i = 0; i < parts.size(); ++i) {
+        const FusedPart& t = parts[i];
+        const ScoreAboveParams p = params(i);
+        if (int rc = run(h, "score_above_fill", 2.0 * t.rows * a.M * a.D, [&]() { return launch_score_above(p, a.D, t.few, t.slices, true, h->stream); })) return rc;
+    }
+    return SVHIP_OK;
+}
+
+int above_slab(svhip_handle* h, const AboveArgs& a) {
+    const bool fill = a.dRowPtr != nullptr;
+    SlabWalk w{h, a.dQ, a.N, a.dG, a.M, a.D};
+    void* word = nullptr;
+    int rc;
+    if ((rc = w.open("score_above"))) return rc;
+    if ((rc = scratch(h, svhip_handle::SCR_TOPK, ABOVE_GUARD_BYTES, &word))) return rc;
+    unsigned long long* bad = reinterpret_cast<unsigned long long*>(word);
+    if (fill) SV_HIP(h, hipMemsetAsync(bad, 0xff, 8, h->stream));
+    // one pass over the slabs: count, compare with row_ptr (check) or write
+    auto pass = [&](bool check, bool gemm) {
+        return w.pass("score_above_gemm", gemm, [&](int64_t r0, int64_t rows, const float* slab, int64_t ldk) {
+            return run(h, "score_above_rows", 0, [&]() {
+                return launch_score_above_rows(slab, rows, a.M, ldk, a.thr, a.upper, a.q_base + r0, a.qc ? a.qc + r0 : nullptr, a.gc,
+                                               fill ? nullptr : a.dCount + r0, fill ? a.dRowPtr + r0 : nullptr, r0, check ? bad : nullptr,
+                                               fill && !check ? a.dIndex : nullptr, fill && !check ? a.dScore : nullptr, h->stream);
+            });
+        });
+    };
+    if (!fill) return pass(false, true);
+    if ((rc = pass(true, true))) return rc;
+    if ((rc = above_guard(h, bad))) return rc;
+    if (a.total == 0) return SVHIP_OK;
+    return pass(false, w.slab_rows < a.N);                          // (one slab: its scores are still there)
+}
+
+int score_above_impl(svhip_handle* h, bool fill, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, float thr, const float* const* stats,
+                     int64_t q_base, int32_t mode, int64_t* out_count, const int64_t* row_ptr, int32_t* out_index, float* out_score, int32_t flags) {
+    if (!h) return SVHIP_ERR_INVALID;
+    if (thr != thr) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: the threshold is NaN");
+    if (M < 1 || M > (int64_t)INT32_MAX) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: M = %lld is outside [1, 2^31 - 1]", (long long)M);
+    if (D < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: D = %d must be at least 1", (int)D);
+    if (N < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: N = %lld is negative", (long long)N);
+    if (mode & ~SVHIP_ABOVE_UPPER) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: unknown mode bits %d", (int)mode);
+    const int upper = mode & SVHIP_ABOVE_UPPER;
+    if (upper && q_base < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: q_base = %lld is negative", (long long)q_base);
+    const int n_stats = !!stats[0] + !!stats[1] + !!stats[2] + !!stats[3];
+    if (n_stats != 0 && n_stats != 4) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: %d of the four statistic arrays are NULL: give all four or none", 4 - n_stats);
+    if (N == 0) return SVHIP_OK;
+    if (!Q || !G || (fill ? !row_ptr : !out_count)) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: NULL pointer");
+    if (D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "score_above: embedding dim %d must be a multiple of 32", (int)D);      // before any copy or launch
+    Staged s(h, flags);
+    AboveArgs a{};
+    a.N = N; a.M = M; a.D = D; a.thr = thr; a.upper = upper; a.q_base = upper ? q_base : 0;
+    a.dQ = s.in(svhip_handle::SCR_IN0, Q, (size_t)N * D * 4);
+    a.dG = s.in(svhip_handle::SCR_IN1, G, (size_t)M * D * 4);
+    if (fill) {
+        a.dRowPtr = s.in(svhip_handle::SCR_OUT2, row_ptr, (size_t)(N + 1) * 8);
+        if (s.rc) return s.rc;
+        // row_ptr[N] is read mid-call: it sizes the outputs
+        if (s.din) {          // (on the handle's stream: a row_ptr produced there needs no wait by the caller)
+            SV_HIP(h, hipMemcpyAsync(&a.total, row_ptr + N, 8, hipMemcpyDeviceToHost, h->stream));
+            SV_HIP(h, hipStreamSynchronize(h->stream));
+        }
+        else a.total = row_ptr[N];
+        if (a.total < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: row_ptr[N] = %lld is negative", (long long)a.total);
+        if (a.total > 0 && (!out_index || !out_score)) SV_FAIL(h, SVHIP_ERR_INVALID, "score_above: NULL pointer");
+        if (a.total > 0) {
+            a.dIndex = s.out(svhip_handle::SCR_OUT0, out_index, (size_t)a.total * 4);
+            a.dScore = s.out(svhip_handle::SCR_OUT1, out_score, (size_t)a.total * 4);
+        }
+    } else {
+        a.dCount = s.out(svhip_handle::SCR_OUT0, out_count, (size_t)N * 8);
+    }
+    if (s.rc) return s.rc;
+    int rc;
+    if (n_stats && (rc = coef_tables(s, "score_above_coef", stats, N, M, &a.qc, &a.gc))) return rc;
+    rc = score_topk_fused_supported(D) && aligned16(a.dQ, a.dG) ? above_fused(h, a) : above_slab(h, a);
+    return s.finish("score_above", rc, true);
+}
+}  // namespace
+
+int svhip_score_above_count(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, float thr, const float* q_mu,
+                            const float* q_sigma, const float* g_mu, const float* g_sigma, int64_t q_base, int32_t mode, int64_t* out_count, int32_t flags) {
+    const float* stats[4] = {q_mu, q_sigma, g_mu, g_sigma};
+    return score_above_impl(h, false, Q, N, G, M, D, thr, stats, q_base, mode, out_count, nullptr, nullptr, nullptr, flags);
+}
+
+int svhip_score_above_fill(svhip_handle* h, const float* Q, int64_t N, const float* G, int64_t M, int32_t D, float thr, const float* q_mu,
+                           const float* q_sigma, const float* g_mu, const float* g_sigma, int64_t q_base, int32_t mode, const int64_t* row_ptr,
+                           int32_t* out_index, float* out_score, int32_t flags) {
+    const float* stats[4] = {q_mu, q_sigma, g_mu, g_sigma};
+    return score_above_impl(h, true, Q, N, G, M, D, thr, stats, q_base, mode, nullptr, row_ptr, out_index, out_score, flags);
+}
+
+}  // extern "C"

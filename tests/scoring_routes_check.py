@@ -6,7 +6,7 @@ References are float64 throughout: oracle/scoring.py::asnorm_stats on float64 in
 
 ROUTES (restated below, each with the function it restates)
   svhip_asnorm_stats   fused kernel for D in {192, 256}, top <= 256, K >= 4 top, K >= 64, 16-byte aligned operands and no option asnorm_slab
-                       (asnorm_fused.hip::asnorm_fused_supported, api_scoring.hip::svhip_asnorm_stats); everything else, and the rows
+                       (asnorm_fused.hip::asnorm_fused_supported, api_asnorm.hip::svhip_asnorm_stats); everything else, and the rows
                        the fused kernel cannot decide, takes the slab path: a cohort GEMM into slabs of slab_rows rows, then one of the
                        four forms of the selection (score.hip::topk_stats_form): reg8 (K <= 2048), reg24 (K <= 6144), lds (Kp <= 37 888,
                        4 / 3 / 2 / 1 rows per workgroup) and global (longer rows, read from the slab on every pass).
@@ -36,11 +36,11 @@ LDS_MAX_ROWS = 4
 FAST_MAX_TOP = 256                    # score.hip: the threshold fast path runs for top <= 256 and K >= 4 top
 FUSED_WIDTHS = (192, 256)             # asnorm_fused.hip::asnorm_fused_supported, score_h3w.hip::score_h3w_supported
 FUSED_MIN_K = 64
-SLAB_BYTES, SLAB_MIN_ROWS = 1 << 31, 128              # api_scoring.hip::SlabWalk
+SLAB_BYTES, SLAB_MIN_ROWS = 1 << 31, 128              # api_scoring.hip::SlabWalk::open
 BIG_SCRATCH = 256 << 20               # api_scoring.hip::release_big_scratch
 ERR_UNSUPPORTED = -5                  # include/svhip.h
 FORMS = ("reg8", "reg24", "lds", "global")
-LABEL = {f: "asnorm_topk_" + f for f in FORMS}        # api_scoring.hip::asnorm_stats_slab
+LABEL = {f: "asnorm_topk_" + f for f in FORMS}        # api_asnorm.hip::asnorm_stats_slab
 
 
 def kp(K):
@@ -60,7 +60,7 @@ def topk_form(K, ld=None, aligned=True):
 
 
 def resolve_top(K, top):
-    """api_scoring.hip::svhip_asnorm_stats: python slice semantics of S[:top]"""
+    """api_asnorm.hip::svhip_asnorm_stats: python slice semantics of S[:top]"""
     top = K + top if top < 0 else top
     return min(top, K)
 
@@ -82,7 +82,7 @@ def is_aligned(*ptrs):
 
 
 def asnorm_route(D, K, top, aligned=True, slab_option=False):
-    """api_scoring.hip::svhip_asnorm_stats on a default (not f32x3) handle"""
+    """api_asnorm.hip::svhip_asnorm_stats on a default (not f32x3) handle"""
     return "fused" if aligned and asnorm_fused_supported(D, K, resolve_top(K, top)) and not slab_option else "slab"
 
 

@@ -263,7 +263,7 @@ def test_score_bits_are_score_topks(eng, D):
 @pytest.mark.parametrize("D", [192, 256])
 def test_rows_do_not_depend_on_the_launch(eng, D, norm):
     """The same 20 rows alone (N = 20: the FEW form) and at places 70 .. 89 of a 130-query call (the MANY form), on a long and on a short
-    gallery.  More than one gallery slice: the launch rule (csrc/api_scoring.hip, above_fused, as score_topk's) cuts the gallery so that
+    gallery.  More than one gallery slice: the launch rule (csrc/api_search.hip, above_fused, as score_topk's) cuts the gallery so that
     a workgroup walks at least 8 blocks of 32 rows (FEW: 16) while there are fewer workgroups than twice the CUs; M = 4100 is 129
     blocks: 9 slices for the FEW launch and 17 for the one-tile MANY launch on any chip with more than 16 CUs, while M = 250 is 8
     blocks: ONE slice in both.  The hits below index 250 of the long-gallery calls must be the short-gallery calls' hits."""

@@ -102,7 +102,7 @@ _CHUNK = {}
 
 def _chunk_data():
     """A call of more than one query chunk, shared with tests/test_gpu_topk.py and tests/test_gpu_above.py: N = 16 384 + 148 queries, so
-    the fused route (csrc/api_scoring.hip, fused_plan) runs three launches - a full chunk of 128 MANY tiles, and from the second chunk
+    the fused route (csrc/api_search.hip, fused_plan) runs three launches - a full chunk of 128 MANY tiles, and from the second chunk
     one MANY tile of 128 queries and a FEW launch of 20 - each with its own offset into the queries, the coefficient table and the
     outputs.  M = 1 283 is 41 gallery blocks with a ragged last one: on a 256-CU chip 4, 5 and 3 slices, so the three launches have
     three different list strides.  _int_data's generators at D = 192; S and t are exact in fp32 and kept as fp32 (85 MB each)."""

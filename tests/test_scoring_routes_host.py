@@ -51,30 +51,36 @@ def test_route_predicates_restate_the_api_and_the_fused_kernels():
     assert "return (D == 192 || D == 256) && top >= 1 && top <= 256 && K >= 4 * top && K >= 64;" in _body(fused, "bool asnorm_fused_supported(")
     assert ("bool score_h3w_supported(int D, int64_t Na, int64_t Nb) { return (D == 192 || D == 256) && Na > 0 && Nb > 0 && "
             "Nb < ((int64_t)1 << 30) && Na < ((int64_t)1 << 31); }") in _src("speakerverification_amd", "csrc", "score_h3w.hip")
+    host = _src("speakerverification_amd", "csrc", "scoring_host.h")
     api = _src("speakerverification_amd", "csrc", "api_scoring.hip")
+    asnorm = _src("speakerverification_amd", "csrc", "api_asnorm.hip")
+    search = _src("speakerverification_amd", "csrc", "api_search.hip")
     # the slab geometry is SlabWalk's, with asnorm_stats_slab's cohort of K rows as its B operand of M rows
-    walk = _body(api, "struct SlabWalk {", "\n};\n")
-    assert "const float* dA; int64_t N;\n    const float* dB; int64_t M;\n    int D;\n" in walk
+    assert "const float* dA; int64_t N;\n    const float* dB; int64_t M;\n    int D;\n" in _body(host, "struct SlabWalk {", "\n};\n")
+    walk = _body(api, "int SlabWalk::open(")
     assert "ldk = (M + 3) & ~(int64_t)3;" in walk
     assert "slab_rows = std::min<int64_t>(N, std::max<int64_t>(128, ((int64_t)1 << 31) / (ldk * 4)));" in walk
-    slab = _body(api, "static int asnorm_stats_slab(")
+    slab = _body(asnorm, "static int asnorm_stats_slab(")
     assert "SlabWalk w{h, dE, N, dC, K, D};" in slab and "w.open(nullptr)" in slab
     assert re.findall(r'"(asnorm_topk_\w+)"', slab)[:4] == [chk.LABEL[f] for f in chk.FORMS]
     assert "const size_t cap = (size_t)256 << 20;" in _body(api, "void release_big_scratch(") and chk.BIG_SCRATCH == 256 << 20
-    route = _flat(_body(api, "static ScoreRoute score_route("))
+    # the one alignment predicate of the routes: both pointers on 16 bytes
+    assert ("inline bool aligned16(const void* a, const void* b = nullptr) { return ((reinterpret_cast<uintptr_t>(a) | "
+            "reinterpret_cast<uintptr_t>(b)) & 15) == 0; }") in host
+    route = _flat(_body(api, "ScoreRoute score_route("))
     assert route.index("if (h->opt.score_f32mfma && !h->x3) return SCORE_F32MFMA;") < route.index("score_h3w_supported(D, Na, Nb)")
-    assert "(reinterpret_cast<uintptr_t>(dA) | reinterpret_cast<uintptr_t>(dB)) & 15) == 0) return SCORE_H3W;" in route
-    stats = _flat(_body(api, "int svhip_asnorm_stats("))
-    assert "const bool aligned = ((reinterpret_cast<uintptr_t>(dE) | reinterpret_cast<uintptr_t>(dC)) & 15) == 0;" in stats
+    assert "score_h3w_supported(D, Na, Nb) && aligned16(dA, dB)) return SCORE_H3W;" in route
+    stats = _flat(_body(asnorm, "int svhip_asnorm_stats("))
+    assert "const bool aligned = aligned16(dE, dC);" in stats
     assert "if (!h->x3 && aligned && asnorm_fused_supported(D, K, top) && !h->opt.asnorm_slab) {" in stats
     # the multiple-of-32 rule stands before the first staging copy of all three entry points
-    for fn in ("int svhip_score_matrix(", "int svhip_asnorm_stats(", "static int score_topk_impl("):
-        body = _body(api, fn)
-        assert body.index("D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED") < body.index("TempBuf"), fn
+    for src, fn in ((api, "int svhip_score_matrix("), (asnorm, "int svhip_asnorm_stats("), (search, "static int score_topk_impl(")):
+        body = _body(src, fn)
+        assert body.index("D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED") < body.index("Staged"), fn
     header = _src("include", "svhip.h")
     assert int(re.search(r"SVHIP_ERR_UNSUPPORTED = (-\d+)", header).group(1)) == chk.ERR_UNSUPPORTED
     # the split form inside the tiled route: where gemm_pw takes the shape
-    assert "if (route == SCORE_WORDS && dBsplit && gemm_pw_supported(p, false)) { p.W = dBsplit; p.x3 = 1; }" in _body(api, "static int score_gemm(")
+    assert "if (route == SCORE_WORDS && dBsplit && gemm_pw_supported(p, false)) { p.W = dBsplit; p.x3 = 1; }" in _body(api, "\nint score_gemm(")
     pw = _body(_src("speakerverification_amd", "csrc", "gemm_pw.hip"), "bool gemm_pw_supported(")
     assert "if (p.ldy % 4 != 0 || p.ldy < ((p.N + 3) & ~3)) return false;" in pw
     assert "if ((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.W) | reinterpret_cast<uintptr_t>(p.Y)) & 15) return false;" in pw
