@@ -465,6 +465,28 @@ int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, con
  *                  or alignment: slabs of score_matrix's GEMM and a row kernel that counts, then compacts, a slab row in index order
  *                  ("score_above_gemm", "score_above_rows"); the refusals of score_topk's slab route hold (D % 32 != 0 and
  *                  M > 4 194 304: SVHIP_ERR_UNSUPPORTED before anything is launched), and so does its magnitude contract.
+ *   cluster_above: speaker clustering ("which rows are the same speaker?"): the connected components of the threshold graph of ONE set,
+ *                  without an edge list and without the N x N matrix.  Input: E (N, D) and a threshold thr.  Rows i < j are LINKED iff
+ *                  v(i, j) >= thr, v being the inner product exactly as score_above computes it for Q = G = E on the same route, or -
+ *                  with mu[N] and sigma[N], the rows' AS-norm statistics - t = fmaf(s, a_i + a_j, -(b_i + b_j)) as score_topk_norm /
+ *                  score_above compute it (a = 0.5f / sigma, b = mu * a; profile label "cluster_coef").  A NaN v links nothing; thr =
+ *                  -inf links every pair whose v is not NaN.  A CLUSTER is a connected component of that graph (single linkage).
+ *                  Outputs: out_root[i] (int32[N]) = the smallest row index in i's cluster; out_cluster[i] (int32[N], optional: NULL =
+ *                  not wanted) = the dense id, clusters numbered 0 .. C - 1 in order of their smallest member; *out_n_clusters
+ *                  (int64) = C.  The result is a function of the data only: the same bits on every run, whatever order the hardware
+ *                  meets the links in, and by definition the components of the pair set score_above(E, E, thr, SVHIP_ABOVE_UPPER)
+ *                  returns.  SVHIP_ERR_INVALID before any copy or launch (messages start "cluster_above:"): a NaN thr, D < 1, N < 0,
+ *                  N > 2^31 - 1, mu without sigma or sigma without mu, a NULL E, out_root or out_n_clusters; D % 32 != 0:
+ *                  SVHIP_ERR_UNSUPPORTED; the outputs are then untouched.  N = 0: SVHIP_OK, *out_n_clusters = 0.  Pointer spaces (E, mu,
+ *                  sigma in; out_root, out_cluster, out_n_clusters out) and SVHIP_ASYNC as score_topk.
+ *                  Routes as score_above.  D in {192, 256} with a 16-byte aligned E: ONE pass of the fused walk per part of the launch
+ *                  plan ("cluster_link"; csrc/score_cluster.hip): each surviving pair is unioned at once in a lock-free disjoint-set
+ *                  forest held in out_root (parent[x] <= x, the larger root hooked under the smaller by compare-and-swap), and a
+ *                  workgroup whose gallery slice lies at or below its query rows returns before the walk.  Every other width or
+ *                  alignment: slabs of score_matrix's GEMM and a row kernel that links a slab row's hits above the diagonal
+ *                  ("cluster_gemm", "cluster_link_rows"; score_topk's slab refusals and magnitude contract hold).  Both: "cluster_init"
+ *                  before, "cluster_flatten" and "cluster_ids" (a hand-written scan of the root flags) behind.  Scratch is O(N) plus
+ *                  the slab: no buffer's size depends on the number of links.
  *   group_audit  : dataset audit ("which files of a speaker folder do not sound like the rest of it?", the label-noise audit of the
  *                  reference's src/benchmark/benchmark_dataset.py:32-84): per file the number of files of its OWN group it does not match.
  *                  Inputs: F (n_files, n_crops, D) fp32 crop embeddings, the files sorted by group; group_ptr[n_groups + 1] int64, ALWAYS
@@ -519,6 +541,10 @@ int svhip_score_above_fill(svhip_handle* h, const float* Q, int64_t N, const flo
                            const float* q_mu, const float* q_sigma, const float* g_mu, const float* g_sigma,
                            int64_t q_base, int32_t mode, const int64_t* row_ptr /* int64[N + 1] */,
                            int32_t* out_index, float* out_score, int32_t flags);
+/* speaker clustering (cluster_above above): mu / sigma both NULL (plain score) or both given; out_cluster may be NULL. */
+int svhip_cluster_above(svhip_handle* h, const float* E, int64_t N, int32_t D, float thr, const float* mu, const float* sigma,
+                        int32_t* out_root /* int32[N] */, int32_t* out_cluster /* int32[N], or NULL */,
+                        int64_t* out_n_clusters, int32_t flags);
 /* dataset audit (group_audit above): group_ptr is always a HOST array; out_score may be NULL. */
 int svhip_group_audit(svhip_handle* h, const float* F, int64_t n_files, int32_t n_crops, int32_t D,
                       const int64_t* group_ptr /* host, int64[n_groups + 1] */, int64_t n_groups, float cut,

@@ -1,5 +1,5 @@
-// api_search.hip — the search calls of libsvhip (see include/svhip.h): top-k (score_topk.hip) and threshold search (score_above.hip)
-// over one gallery walk (score_walk.h).  Both decide their route from the shape and the pointers alone:
+// api_search.hip — the search calls of libsvhip (see include/svhip.h): top-k (score_topk.hip), threshold search (score_above.hip) and
+// clustering (score_cluster.hip) over one gallery walk (score_walk.h).  All decide their route from the shape and the pointers alone:
 //   fused  D = 192 / 256, 16-byte aligned operands: no score reaches memory.  fused_plan cuts the call into launches
 //   slab   every other width: SlabWalk writes slabs of query rows, a row kernel selects
 // and the calls with statistics take the same routes with the same parts and slabs: `qc` / `gc` are their tables of (a, b) pairs.
@@ -299,6 +299,92 @@ int svhip_score_above_fill(svhip_handle* h, const float* Q, int64_t N, const flo
                            int32_t* out_index, float* out_score, int32_t flags) {
     const float* stats[4] = {q_mu, q_sigma, g_mu, g_sigma};
     return score_above_impl(h, true, Q, N, G, M, D, thr, stats, q_base, mode, nullptr, row_ptr, out_index, out_score, flags);
+}
+
+// ---- speaker clustering: the components of the self-join's pair set, without the pair set (score_cluster.hip) ---------------------------
+// Routes, fused_plan's parts and the slabs are score_above's for Q = G = E in UPPER mode; the forest lives in out_root.  ONE link launch per
+// part (or per slab) and no second MFMA pass; the scratch is O(N): the coefficient tables and the per-block root counts of the dense ids.
+namespace {
+struct ClusterArgs {
+    const float* dE;
+    int64_t N;
+    int D;
+    float thr;
+    const float2 *qc, *gc;
+    int32_t* dRoot;
+};
+
+int cluster_fused(svhip_handle* h, const ClusterArgs& a) {
+    // The plan as for four chips' worth of CUs: four times the slices, so the workgroups under the diagonal, which return at once, leave
+    // their places to walking ones instead of leaving the launch as long as one whole walk (slices still hold >= 8 / 16 gallery blocks).
+    std::vector<FusedPart> parts;
+    fused_plan(a.N, a.N, 4 * (h->num_cu > 0 ? h->num_cu : 256), {0, 0}, parts);
+    for (const FusedPart& t : parts) {
+        ClusterLinkParams p;
+        p.Q = a.dE + t.r0 * a.D; p.N = t.rows; p.G = a.dE; p.M = a.N; p.thr = a.thr; p.row_base = t.r0; p.per = t.per; p.parent = a.dRoot;
+        p.qcoef = a.qc ? a.qc + t.r0 : nullptr; p.gcoef = a.gc;
+        // the profile's flops: the (query tile, gallery slice) workgroups that walk - the kernel's own diagonal skip leaves the others out
+        const int64_t tile = t.few ? 32 : 128, span = (int64_t)t.per * 32;
+        double pairs = 0;
+        for (int64_t q0 = 0; q0 < t.rows; q0 += tile)
+            for (int64_t y = (t.r0 + q0) / span; y < t.slices; ++y)      // (the first slice that ends above the tile's first row)
+                pairs += (double)std::min(tile, t.rows - q0) * std::min(span, a.N - y * span);
+        if (int rc = run(h, "cluster_link", 2.0 * pairs * a.D, [&]() { return launch_cluster_link(p, a.D, t.few, t.slices, h->stream); })) return rc;
+    }
+    return SVHIP_OK;
+}
+
+int cluster_slab(svhip_handle* h, const ClusterArgs& a) {
+    SlabWalk w{h, a.dE, a.N, a.dE, a.N, a.D};
+    if (int rc = w.open("cluster_above")) return rc;
+    return w.pass("cluster_gemm", true, [&](int64_t r0, int64_t rows, const float* slab, int64_t ldk) {
+        return run(h, "cluster_link_rows", 0, [&]() {
+            return launch_cluster_link_rows(slab, rows, a.N, ldk, a.thr, r0, a.qc ? a.qc + r0 : nullptr, a.gc, a.dRoot, h->stream);
+        });
+    });
+}
+
+int cluster_above_impl(svhip_handle* h, const float* E, int64_t N, int32_t D, float thr, const float* mu, const float* sigma, int32_t* out_root,
+                       int32_t* out_cluster, int64_t* out_n_clusters, int32_t flags) {
+    if (!h) return SVHIP_ERR_INVALID;
+    if (thr != thr) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: the threshold is NaN");
+    if (D < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: D = %d must be at least 1", (int)D);
+    if (N < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: N = %lld is negative", (long long)N);
+    if (N > (int64_t)INT32_MAX) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: N = %lld is outside [0, 2^31 - 1]", (long long)N);
+    if (!mu != !sigma) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: %s is NULL: give mu and sigma or neither", mu ? "sigma" : "mu");
+    if (!out_n_clusters || (N > 0 && (!E || !out_root))) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: NULL pointer");
+    if (D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "cluster_above: embedding dim %d must be a multiple of 32", (int)D);      // before any copy or launch
+    Staged s(h, flags);
+    if (N == 0) {
+        int64_t* dN = s.out(svhip_handle::SCR_OUT2, out_n_clusters, 8);
+        if (s.rc) return s.rc;
+        SV_HIP(h, hipMemsetAsync(dN, 0, 8, h->stream));
+        return s.finish("cluster_above", SVHIP_OK, false);
+    }
+    ClusterArgs a{};
+    a.N = N; a.D = D; a.thr = thr;
+    a.dE = s.in(svhip_handle::SCR_IN0, E, (size_t)N * D * 4);
+    a.dRoot = s.out(svhip_handle::SCR_OUT0, out_root, (size_t)N * 4);
+    int32_t* dCluster = out_cluster ? s.out(svhip_handle::SCR_OUT1, out_cluster, (size_t)N * 4) : nullptr;
+    int64_t* dN = s.out(svhip_handle::SCR_OUT2, out_n_clusters, 8);
+    if (s.rc) return s.rc;
+    int rc;
+    // the rows are queries and gallery at once: both coefficient tables come from the one (mu, sigma) pair
+    const float* stats[4] = {mu, sigma, mu, sigma};
+    if (mu && (rc = coef_tables(s, "cluster_coef", stats, N, N, &a.qc, &a.gc))) return rc;
+    void* bcnt = nullptr;
+    if ((rc = scratch(h, svhip_handle::SCR_TOPK, (size_t)cluster_id_blocks(N) * 4, &bcnt))) return rc;
+    rc = run(h, "cluster_init", 0, [&]() { return launch_cluster_init(a.dRoot, N, h->stream); });
+    if (!rc) rc = score_topk_fused_supported(D) && aligned16(a.dE) ? cluster_fused(h, a) : cluster_slab(h, a);
+    if (!rc) rc = run(h, "cluster_flatten", 0, [&]() { return launch_cluster_flatten(a.dRoot, N, h->stream); });
+    if (!rc) rc = run(h, "cluster_ids", 0, [&]() { return launch_cluster_ids(a.dRoot, N, static_cast<int32_t*>(bcnt), dCluster, dN, h->stream); });
+    return s.finish("cluster_above", rc, true);
+}
+}  // namespace
+
+int svhip_cluster_above(svhip_handle* h, const float* E, int64_t N, int32_t D, float thr, const float* mu, const float* sigma, int32_t* out_root,
+                        int32_t* out_cluster, int64_t* out_n_clusters, int32_t flags) {
+    return cluster_above_impl(h, E, N, D, thr, mu, sigma, out_root, out_cluster, out_n_clusters, flags);
 }
 
 }  // extern "C"

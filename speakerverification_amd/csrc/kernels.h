@@ -783,6 +783,33 @@ hipError_t launch_score_above_rows(const float* S, int64_t rows, int64_t M, int6
                                    const float2* gcoef, int64_t* out_count, const int64_t* row_ptr, int64_t row0, unsigned long long* bad,
                                    int32_t* out_index, float* out_score, hipStream_t stream);
 
+// Speaker clustering (score_cluster.hip): the connected components of "rows i < j of ONE set are linked iff v(i, j) >= thr" (v as threshold
+// search computes it in UPPER mode), without an edge list.  `parent` (M int32, the call's out_root) holds a lock-free disjoint-set forest
+// with parent[x] <= x: launch_cluster_init, then one launch_cluster_link per part of the fused plan (or one launch_cluster_link_rows per
+// slab), then launch_cluster_flatten: parent[i] = the smallest row of i's component.
+struct ClusterLinkParams {
+    const float* Q = nullptr;       // (N, D) the rows row_base .. row_base + N - 1 of G: the queries of this launch
+    int64_t N = 0;
+    const float* G = nullptr;       // (M, D) the whole set
+    int64_t M = 0;
+    float thr = 0.0f;               // a link: v >= thr (never NaN)
+    int64_t row_base = 0;           // the place of this launch's first query in the set
+    int per = 0;                    // blocks of 32 gallery rows per slice
+    int32_t* parent = nullptr;      // (M) the forest
+    const float2* qcoef = nullptr;  // the normalised form: both tables or neither (ScoreTopkParams)
+    const float2* gcoef = nullptr;
+};
+hipError_t launch_cluster_init(int32_t* parent, int64_t N, hipStream_t stream);
+hipError_t launch_cluster_link(const ClusterLinkParams& p, int D, bool few, int slices, hipStream_t stream);
+// the slab route: one workgroup per row of S (rows x M, row stride ld % 4 == 0, 16-byte aligned), row r being row row_base + r of the set
+hipError_t launch_cluster_link_rows(const float* S, int64_t rows, int64_t M, int64_t ld, float thr, int64_t row_base, const float2* qcoef,
+                                    const float2* gcoef, int32_t* parent, hipStream_t stream);
+hipError_t launch_cluster_flatten(int32_t* root, int64_t N, hipStream_t stream);
+// dense ids from flattened roots: *out_n = the number of roots; cluster (optional) [i] = the roots below root[i].  bcnt: cluster_id_blocks(N)
+// int32 of scratch (per-block root counts, scanned in place by one workgroup)
+int64_t cluster_id_blocks(int64_t N);
+hipError_t launch_cluster_ids(const int32_t* root, int64_t N, int32_t* bcnt, int32_t* cluster, int64_t* out_n, hipStream_t stream);
+
 // Dataset audit (group_audit.hip): files sorted by group; s(i, j) = mean_c | cos(F[i, c], F[j, c]) | (launch_trial_crops mode 0's
 // statement) for the files of one group, a mismatch iff s <= cut; miss[i] counts the files j != i of i's group that i mismatches.
 // Per-file tables (launch_group_audit_tables, from the device copy of group_ptr): gs / ge = where the file's group starts / ends,

@@ -1,0 +1,298 @@
+// score_cluster.hip — speaker clustering: the connected components of the graph "rows i < j are linked iff v(i, j) >= thr" over ONE set of
+// rows, WITHOUT an edge list and without the N x N score matrix (gfx950; svhip.h, svhip_cluster_above).
+//
+//   cluster_init        parent[i] = i
+//   cluster_link        the gallery walk of score_walk.h (Q = G = E, the masks of score_above_kernel in UPPER mode, so v has the bits
+//                       score_above gives the pair) with a third epilogue: every surviving pair is unioned at once in a lock-free
+//                       disjoint-set forest that lives in the out_root buffer itself.  One MFMA pass over the upper half plane: a
+//                       workgroup whose gallery slice ends at or below its first query row returns before the walk (no pair j > i lies
+//                       there; workgroup-uniform, and no score's bits change).
+//   cluster_link_rows   the slab route: one workgroup per row of a score slab, four columns per thread, the columns above the row's own index
+//   cluster_flatten     root[i] = the representative of i, in place, behind the kernel boundary
+//   cluster_count / _scan / _rank / _assign   dense ids: the roots are flagged (root[i] == i), counted per block of 1024 rows, ONE block
+//                       scans the block counts, the roots take their rank, every other row takes its root's: clusters are numbered in
+//                       order of their smallest member.  Integers only: the ids depend on root[] alone.
+//
+// The forest (the ECL-CC / Jayanti-Tarjan scheme).  parent[x] <= x always; x is a ROOT while parent[x] == x.  To link (u, v): climb from both
+// to nodes that look like roots; if they are one node, done; otherwise hook the LARGER under the smaller with
+// atomicCAS(&parent[hi], hi, lo).  The CAS succeeds only while hi really is a root; when it fails it returns the value that was there,
+// which is strictly smaller than hi, and the link goes on from it: every step moves to a smaller index, so the loop ends without waiting
+// for any other wave.  While climbing, a node's parent may be lowered to its grandparent (atomicMin): the only other write there is.
+//   Invariant.  Rows form SETS (the unions made so far).  A set has exactly one root, which is its smallest member (a hook puts the root
+//   of one set under a member lo < hi of the other, whose root is <= lo: the smaller of the two minima stays root), and every value ever
+//   stored in parent[x] is a member of x's set that is <= x (a hook stores a member of the merged set; atomicMin stores what was read as
+//   the parent of the parent: sets only ever grow).
+//   Staleness.  Per-XCD L2s and per-CU L1s are not coherent, so inside cluster_link every access to parent[] is an agent-scope atomic:
+//   atomicCAS to hook, __hip_atomic_load(relaxed, agent) to climb, atomicMin to shorten; there is no plain store to it.  Even so a load
+//   may return an OLDER value of parent[x].  That is harmless by construction: an older value is x itself or a member of x's set below x
+//   (the invariant), so a climb through stale values still ends at a member of the start's set, and a node that only LOOKS like a root
+//   is caught by the CAS, which is the arbiter: it compares with the value memory holds.  Two climbs that meet in one node started in one
+//   set, whatever they read on the way.  When the kernel has ended every link (u, v) has either met or hooked, so u and v are in one set;
+//   no two rows without a chain of links ever are.  The root of every set is then the smallest index of its component, whatever order the
+//   hardware met the links in: the result is a function of the data only.
+// No spin-waits, no cross-lane operation inside the divergent link loop, no inline assembly: plain C++ and HIP atomics.
+#include "common.h"
+#include "kernels.h"
+#include "score_walk.h"
+
+namespace svhip {
+
+namespace {
+
+__device__ __forceinline__ int32_t forest_load(const int32_t* parent, int32_t x) {
+    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a node above x that looks like a root; on the way a node's parent is lowered to its grandparent
+__device__ __forceinline__ int32_t forest_climb(int32_t* parent, int32_t x) {
+    int32_t p = forest_load(parent, x);
+    while (p != x) {
+        const int32_t g = forest_load(parent, p);
+        if (g != p) atomicMin(parent + x, g);       // (x is no root: its parent only ever moves down inside its set)
+        x = p;
+        p = g;
+    }
+    return x;
+}
+
+__device__ __forceinline__ void forest_link(int32_t* parent, int32_t u, int32_t v) {
+    for (;;) {
+        u = forest_climb(parent, u);
+        v = forest_climb(parent, v);
+        if (u == v) return;
+        const int32_t hi = u > v ? u : v, lo = u > v ? v : u;
+        const int32_t was = atomicCAS(parent + hi, hi, lo);
+        if (was == hi) return;
+        u = was;                                    // hi was hooked meanwhile: go on below it (was < hi)
+        v = lo;
+    }
+}
+
+template <int D, bool FEW, bool NORM>
+__global__ __launch_bounds__(256, 2) void cluster_link_kernel(ClusterLinkParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    // the diagonal skip: the slice's last gallery row lies at or below the workgroup's first query row (workgroup-uniform)
+    const int64_t tile_first_row = FEW ? 0 : (int64_t)blockIdx.x * 128;
+    if (((int64_t)blockIdx.y + 1) * p.per * 32 <= p.row_base + tile_first_row) return;
+    const ScoreLane g(FEW, p.N);
+    const int h = g.h;
+    // a link's gallery index lies in [lo, M): score_above_kernel's UPPER mask
+    const int64_t first = p.row_base + g.row + 1;
+    const uint32_t lo = g.valid && first < (int64_t)0xffffffffu ? (uint32_t)first : 0xffffffffu, hi = (uint32_t)p.M;
+    const int32_t me = (int32_t)(p.row_base + (g.valid ? g.row : 0));
+
+    auto process = [&](const f32x16& a, int b) {
+        const uint32_t kb = (uint32_t)b * 32u + 4u * h;
+        uint32_t hits = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const uint32_t i = kb + (r & 3) + 8 * (r >> 2);
+            if (i >= lo && i < hi && a[r] >= p.thr) hits |= 1u << r;                    // (a NaN score links nothing)
+        }
+        while (hits) {                                                                  // (divergent: most lanes hold no hit)
+            const int r = __ffs(hits) - 1;
+            hits &= hits - 1;
+            forest_link(p.parent, me, (int32_t)(kb + (r & 3) + 8 * (r >> 2)));
+        }
+    };
+    score_walk<D, FEW, NORM, true>(g, p.Q, p.N, p.G, p.M, p.per, p.qcoef, p.gcoef, smem, process);
+}
+
+// The slab route: one workgroup per row of a score slab, four consecutive columns per thread and round (score_above_rows_kernel's reads),
+// from the round that holds the first column above the row's own index.
+template <bool NORM>
+__global__ __launch_bounds__(256) void cluster_link_rows_kernel(const float* __restrict__ S, int64_t M, int64_t ld, float thr, int64_t row_base,
+                                                                const float2* __restrict__ qcoef, const float2* __restrict__ gcoef, int32_t* parent) {
+    const int64_t row = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float* __restrict__ s = S + row * ld;
+    float aq = 0.0f, bq = 0.0f;
+    if (NORM) {
+        const float2 c = qcoef[row];
+        aq = c.x; bq = c.y;
+    }
+    const int64_t above = row_base + row;
+    for (int64_t c0 = (above + 1) & ~(int64_t)1023; c0 < M; c0 += 1024) {
+        const int64_t t0 = c0 + 4 * tid;
+        if (t0 >= M) continue;                                         // (ld % 4 == 0: the four columns lie inside the row's stride)
+        const f32x4 x = *reinterpret_cast<const f32x4*>(s + t0);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float v = x[u];
+            if (NORM && t0 + u < M) {
+                const float2 g = gcoef[t0 + u];
+                v = __builtin_fmaf(x[u], aq + g.x, -(bq + g.y));
+            }
+            if (t0 + u < M && t0 + u > above && v >= thr) forest_link(parent, (int32_t)above, (int32_t)(t0 + u));
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void cluster_init_kernel(int32_t* __restrict__ parent, int64_t N) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < N) parent[i] = (int32_t)i;
+}
+
+// In place: a row climbs to its root and stores it.  Rows are rewritten while others still climb through them: what a climb reads is an
+// older or a newer ancestor, and a root is never rewritten to anything but itself - the accesses stay agent-scope atomics all the same.
+__global__ __launch_bounds__(256) void cluster_flatten_kernel(int32_t* root, int64_t N) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    int32_t x = (int32_t)i, p = forest_load(root, x);
+    if (p == x) return;
+    while (p != x) {
+        x = p;
+        p = forest_load(root, x);
+    }
+    __hip_atomic_store(root + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- dense ids: blocks of 1024 rows, four consecutive rows per thread ------------------------------------------------------------------
+constexpr int CLUSTER_BLOCK = 1024;
+
+// the roots among the thread's four rows, as a mask
+__device__ __forceinline__ uint32_t root_flags(const int32_t* __restrict__ root, int64_t N, int64_t i0) {
+    uint32_t f = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        if (i0 + u < N && root[i0 + u] == (int32_t)(i0 + u)) f |= 1u << u;
+    return f;
+}
+
+// exclusive prefix of `n` over the 256 threads of a workgroup (ws: 4 ints of LDS); *all = the workgroup's sum
+__device__ __forceinline__ int block_exclusive(int n, int* ws, int* all) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = n;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    __syncthreads();                                                   // (ws may still be read from the round before)
+    if (lane == 63) ws[wave] = incl;
+    __syncthreads();
+    int before = 0, sum = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int x = ws[w];
+        if (w < wave) before += x;
+        sum += x;
+    }
+    *all = sum;
+    return before + incl - n;
+}
+
+__global__ __launch_bounds__(256) void cluster_count_kernel(const int32_t* __restrict__ root, int64_t N, int32_t* __restrict__ bcnt) {
+    __shared__ int ws[4];
+    int all;
+    block_exclusive(__popc(root_flags(root, N, (int64_t)blockIdx.x * CLUSTER_BLOCK + 4 * threadIdx.x)), ws, &all);
+    if (threadIdx.x == 0) bcnt[blockIdx.x] = all;
+}
+
+// ONE workgroup: bcnt[b] <- the roots of the blocks before b, 256 blocks a round; *out_n = the number of roots
+__global__ __launch_bounds__(256) void cluster_scan_kernel(int32_t* __restrict__ bcnt, int64_t nb, int64_t* __restrict__ out_n) {
+    __shared__ int ws[4];
+    int64_t carry = 0;
+    for (int64_t b0 = 0; b0 < nb; b0 += 256) {
+        const int64_t b = b0 + threadIdx.x;
+        const int n = b < nb ? bcnt[b] : 0;
+        int all;
+        const int before = block_exclusive(n, ws, &all);
+        if (b < nb) bcnt[b] = (int32_t)(carry + before);               // (fewer than 2^31 rows: fewer roots)
+        carry += all;
+    }
+    if (threadIdx.x == 0) *out_n = carry;
+}
+
+// a root's id: the roots before it
+__global__ __launch_bounds__(256) void cluster_rank_kernel(const int32_t* __restrict__ root, int64_t N, const int32_t* __restrict__ boff,
+                                                           int32_t* __restrict__ cluster) {
+    __shared__ int ws[4];
+    const int64_t i0 = (int64_t)blockIdx.x * CLUSTER_BLOCK + 4 * threadIdx.x;
+    const uint32_t f = root_flags(root, N, i0);
+    int all;
+    int rank = boff[blockIdx.x] + block_exclusive(__popc(f), ws, &all);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        if ((f >> u) & 1u) cluster[i0 + u] = rank++;
+}
+
+// every other row: its root's id (the roots' entries were written by the launch before and are not written here)
+__global__ __launch_bounds__(256) void cluster_assign_kernel(const int32_t* __restrict__ root, int64_t N, int32_t* cluster) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const int32_t r = root[i];
+    if (r != (int32_t)i) cluster[i] = cluster[r];
+}
+
+template <int D, bool FEW, bool NORM>
+hipError_t launch_link_d(const ClusterLinkParams& p, const dim3& grid, hipStream_t stream) {
+    static DeviceOnce attr;
+    constexpr int lds = score_walk_lds_bytes(D, FEW, NORM);
+    if (!FEW)
+        if (hipError_t e = set_max_dynamic_lds(attr, reinterpret_cast<const void*>(cluster_link_kernel<D, FEW, NORM>), lds)) return e;
+    hipLaunchKernelGGL((cluster_link_kernel<D, FEW, NORM>), grid, dim3(256), lds, stream, p);
+    return hipGetLastError();
+}
+
+template <int D>
+hipError_t launch_link_form(const ClusterLinkParams& p, bool few, const dim3& grid, hipStream_t stream) {
+    if (p.qcoef) return few ? launch_link_d<D, true, true>(p, grid, stream) : launch_link_d<D, false, true>(p, grid, stream);
+    return few ? launch_link_d<D, true, false>(p, grid, stream) : launch_link_d<D, false, false>(p, grid, stream);
+}
+
+inline unsigned blocks_of(int64_t N, int per) { return (unsigned)((N + per - 1) / per); }
+
+}  // namespace
+
+hipError_t launch_cluster_init(int32_t* parent, int64_t N, hipStream_t stream) {
+    if (N <= 0) return hipSuccess;
+    if (!parent || N >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cluster_init_kernel, dim3(blocks_of(N, 256)), dim3(256), 0, stream, parent, N);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_link(const ClusterLinkParams& p, int D, bool few, int slices, hipStream_t stream) {
+    if (p.N <= 0) return hipSuccess;
+    // every index a link touches lies in [0, M): the queries of the launch are the rows row_base .. row_base + N - 1 of the gallery
+    if (!p.parent || p.thr != p.thr || p.row_base < 0 || p.row_base + p.N > p.M) return hipErrorInvalidValue;
+    dim3 grid;
+    if (hipError_t e = score_walk_launch(D, p.Q, p.N, p.G, p.M, p.per, p.qcoef, p.gcoef, few, slices, &grid)) return e;
+    return D == 192 ? launch_link_form<192>(p, few, grid, stream) : launch_link_form<256>(p, few, grid, stream);
+}
+
+hipError_t launch_cluster_link_rows(const float* S, int64_t rows, int64_t M, int64_t ld, float thr, int64_t row_base, const float2* qcoef,
+                                    const float2* gcoef, int32_t* parent, hipStream_t stream) {
+    if (rows <= 0) return hipSuccess;
+    if (!S || !parent || thr != thr || M < 1 || M >= ((int64_t)1 << 31) || ld < M || (ld & 3) || (reinterpret_cast<uintptr_t>(S) & 15) ||
+        row_base < 0 || row_base + rows > M)
+        return hipErrorInvalidValue;
+    if (!qcoef != !gcoef) return hipErrorInvalidValue;
+    if (qcoef) hipLaunchKernelGGL(cluster_link_rows_kernel<true>, dim3((unsigned)rows), dim3(256), 0, stream, S, M, ld, thr, row_base, qcoef, gcoef, parent);
+    else hipLaunchKernelGGL(cluster_link_rows_kernel<false>, dim3((unsigned)rows), dim3(256), 0, stream, S, M, ld, thr, row_base, qcoef, gcoef, parent);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_flatten(int32_t* root, int64_t N, hipStream_t stream) {
+    if (N <= 0) return hipSuccess;
+    if (!root || N >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cluster_flatten_kernel, dim3(blocks_of(N, 256)), dim3(256), 0, stream, root, N);
+    return hipGetLastError();
+}
+
+int64_t cluster_id_blocks(int64_t N) { return (N + CLUSTER_BLOCK - 1) / CLUSTER_BLOCK; }
+
+hipError_t launch_cluster_ids(const int32_t* root, int64_t N, int32_t* bcnt, int32_t* cluster, int64_t* out_n, hipStream_t stream) {
+    if (N <= 0) return hipSuccess;
+    if (!root || !bcnt || !out_n || N >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const int64_t nb = cluster_id_blocks(N);
+    hipLaunchKernelGGL(cluster_count_kernel, dim3((unsigned)nb), dim3(256), 0, stream, root, N, bcnt);
+    hipLaunchKernelGGL(cluster_scan_kernel, dim3(1), dim3(256), 0, stream, bcnt, nb, out_n);
+    if (cluster) {
+        hipLaunchKernelGGL(cluster_rank_kernel, dim3((unsigned)nb), dim3(256), 0, stream, root, N, bcnt, cluster);
+        hipLaunchKernelGGL(cluster_assign_kernel, dim3(blocks_of(N, 256)), dim3(256), 0, stream, root, N, cluster);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace svhip

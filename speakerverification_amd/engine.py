@@ -634,6 +634,36 @@ class Engine:
             _count([q, g, *st, r], [i, s])
         return row_ptr, index, score
 
+    def cluster_above(self, E, thr, stats=None):
+        """Speaker clustering (``svhip_cluster_above``): rows ``i < j`` of E (N, D) are linked iff their score is at least ``thr``, and
+        a cluster is a connected component of that graph - by definition the components of the pair set
+        ``score_above(E, E, thr, upper=True)`` returns, found in one pass and without the pair list.  The score is the inner product
+        as ``score_above`` computes it, or - with ``stats``, the ``(mu, sigma)`` pair of ``asnorm_stats`` for E - the normalised score
+        of ``score_topk_norm``; a NaN score links nothing.  Returns ``(root (N,) int32, cluster (N,) int32, n_clusters)``: the smallest
+        row of each row's cluster, the dense id (clusters numbered in order of their smallest member) and the number of clusters.
+        numpy in, numpy out (``n_clusters`` an int); a CUDA tensor in, CUDA tensors out (``n_clusters`` a 0-d int64 tensor)."""
+        N, D = (int(x) for x in E.shape)
+        thr = float(thr)
+        if thr != thr:
+            raise ValueError("cluster_above: the threshold is NaN")
+        if stats is not None:
+            if len(stats) != 2:
+                raise ValueError("stats must be a (mu, sigma) pair")
+            for name, x in zip(("mu", "sigma"), stats):
+                if x is None or tuple(x.shape) != (N,):
+                    raise ValueError(f"stats: {name} must hold {N} values, not {None if x is None else tuple(x.shape)}")
+        on_dev = _is_torch(E) and E.is_cuda
+        empty = (lambda n, dt: torch.empty(n, dtype=getattr(torch, np.dtype(dt).name), device=E.device)) if on_dev else np.empty
+        root, cluster, count = empty(N, np.int32), empty(N, np.int32), empty(1, np.int64)
+        e = _Buf(E, np.float32)
+        st = [_Buf(x, np.float32) for x in (stats or ())]
+        sp = [b.ptr for b in st] or [None] * 2
+        r, c, n = _Buf(root, np.int32, writable=True), _Buf(cluster, np.int32, writable=True), _Buf(count, np.int64, writable=True)
+        dev = self._same_space(e, *st, r, c, n)
+        self._ck(self.lib.svhip_cluster_above(self.h, e.ptr, N, D, thr, *sp, r.ptr, c.ptr, n.ptr, (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
+        _count([e, *st], [r, c, n])
+        return root, cluster, (count[0] if on_dev else int(count[0]))
+
     @staticmethod
     def _audit_group_ptr(group_ptr, n_files):
         """``group_audit``'s group table as a contiguous host int64 array, checked by the C ABI's rules (a bad one is a

@@ -661,6 +661,62 @@ class ModelHandling:
             return i, j, s
         return i, j, s, [(classes[int(a)], classes[int(b)]) for a, b in zip(i, j)]
 
+    def cluster(self, source=None, embeds=None, thresh_score=None, classes=None, num_eval=10, scoring_mode="cosine", cohorts=None,
+                cohorts_path=None, cohort_top=200, min_size=1):
+        """Which of these are the same speaker?  Groups unlabelled files, or the classes of a carelessly enrolled gallery: two rows are
+        linked when their score is at least ``thresh_score``, and a cluster is a connected component of those links - by definition
+        the components of the pair set ``duplicates`` returns on the same rows, found by ONE ``cluster_above`` call per set: one pass
+        over the upper half of the self-join, no pair list, one int per row.
+
+        Exactly one of ``source`` and ``embeds`` is given.  ``source``: files (what ``_embed_files`` takes), embedded and prepared as
+        ``identify`` prepares its queries (crops L2-normalised when the loss sets ``test_normalize``, averaged, the mean L2-normalised).
+        ``embeds``: a gallery in ``identify``'s three forms, prepared as ``duplicates`` prepares it.  ``scoring_mode`` and the cohort
+        arguments are ``identify``'s: with ``"norm"`` a row's statistics are taken against the cohort and the link score is the
+        adaptive-S-normalised one.
+
+        This is SINGLE linkage, and single linkage chains: one borderline pair joins two speakers, and a string of them joins many.
+        ``scoring_mode="norm"``, whose threshold carries across speakers and channels, and ``min_size``, which drops the clusters too
+        small to trust, are the mitigations on offer; average or complete linkage is not.
+
+        Returns ``(labels, groups)``.  ``labels`` (n,) int32: the dense cluster id of every row, clusters numbered in order of their
+        smallest member; rows of clusters with fewer than ``min_size`` members get -1 and the remaining clusters are renumbered in the
+        same order.  ``groups``: per kept cluster the list of its members in index order - the files of ``source``, the class names
+        when ``classes`` is given or the directory holds ``classes.npy``, else the row indices."""
+        if (source is None) == (embeds is None):
+            raise ValueError("cluster: give exactly one of source (files) and embeds (a gallery)")
+        if thresh_score is None:
+            raise ValueError("cluster: thresh_score is required")
+        min_size = int(min_size)
+        if min_size < 1:
+            raise ValueError(f"cluster: min_size = {min_size} must be at least 1")
+        eng = scoring.scoring_engine(self.gpu)
+        if source is not None:
+            self.__model__.eval()
+            names = list(source) if isinstance(source, (list, tuple)) else [source]
+            if not names:
+                raise ValueError("Please provide appropriate source!")
+            feats = np.asarray(_host(self._embed_files(names, num_eval)), dtype=np.float32)       # (n_files, n_crops, nOut)
+            flat = np.ascontiguousarray(feats.reshape(-1, feats.shape[-1]))
+            if self.__model__.module.test_normalize:
+                eng.l2norm_(flat)
+            rows = np.ascontiguousarray(flat.reshape(feats.shape).mean(axis=1))
+        else:
+            rows, classes = self._gallery(embeds, classes)
+            names = [classes[i] for i in range(rows.shape[0])] if classes is not None else list(range(rows.shape[0]))
+        cohorts = self._cohort(scoring_mode, cohorts, cohorts_path, rows.shape[1])
+        eng.l2norm_(rows)
+        _, ids, _ = scoring.cluster(rows, thresh_score, cohort=cohorts, top=int(cohort_top), device=self.gpu)
+        ids = np.asarray(_host(ids))
+        sizes = np.bincount(ids, minlength=0)
+        keep = sizes >= min_size
+        renumber = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
+        labels = renumber[ids] if ids.size else np.zeros(0, np.int32)
+        groups = [[] for _ in range(int(keep.sum()))]
+        for i, c in enumerate(labels):
+            if c >= 0:
+                groups[c].append(names[i])
+        return labels, groups
+
     # ---- dataset audit ----------------------------------------------------------------------------------------------------
     def audit(self, source, thresh_score, num_eval=20, save_file=None, max_files=65536):
         """Which files of a speaker folder do not sound like the rest of it?  The reference's label-noise audit

@@ -1,7 +1,7 @@
 """Scoring counterparts of the reference's ``src/utils.py:126-169``.
 
 ``similarity_measure(method, ref, com, **kw)`` keeps the per-trial signature for compatibility; the
-batched entry points (``score_pairs``, ``score_matrix``, ``score_topk``, ``score_topk_norm``, ``score_above``, ``group_audit``, ``asnorm_stats``,
+batched entry points (``score_pairs``, ``score_matrix``, ``score_topk``, ``score_topk_norm``, ``score_above``, ``cluster``, ``group_audit``, ``asnorm_stats``,
 ``asnorm_pairs``, ``score_trials``) are what ``ModelHandling.evaluateFromList`` uses: one kernel launch per trial LIST
 instead of three host<->device crossings per trial.
 """
@@ -87,6 +87,20 @@ def score_above(Q, G, thr, cohort=None, top=200, g_stats=None, upper=False, q_ba
         g_stats = eng.asnorm_stats(G, cohort, top)
     q_stats = eng.asnorm_stats(Q, cohort, top)
     return eng.score_above(Q, G, thr, q_stats, g_stats, upper=upper, q_base=q_base, max_hits=max_hits)
+
+
+def cluster(E, thr, cohort=None, top=200, stats=None, device=0):
+    """which rows of E are the same speaker?  Rows ``i < j`` are linked iff their score is at least ``thr``; a cluster is a connected
+    component -> ``(root (N,) int32, cluster (N,) int32, n_clusters)`` (``Engine.cluster_above``).  With a ``cohort`` the score is the
+    adaptive-S-normalised one of ``score_topk_norm``: the rows' statistics come from ``asnorm_stats(E, cohort, top)``; ``stats =
+    (mu, sigma)``, kept from an earlier call, is used as it is.  The clusters are the components of the pair set ``score_above(E, E, thr, ..., upper=True)``
+    returns, found in one pass over the upper half plane and without that pair list."""
+    if float(thr) != float(thr):
+        raise ValueError("cluster: the threshold is NaN")
+    eng = scoring_engine(device)
+    if stats is None and cohort is not None:
+        stats = eng.asnorm_stats(E, cohort, top)
+    return eng.cluster_above(E, thr, stats)
 
 
 def audit_cut(threshold):
