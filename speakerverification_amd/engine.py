@@ -28,15 +28,6 @@ def _is_torch(x) -> bool:
 TRANSFER_STATS = {"h2d_bytes": 0, "d2h_bytes": 0}
 
 
-def _count(inputs=(), outputs=()):
-    for b in inputs:
-        if not b.device:
-            TRANSFER_STATS["h2d_bytes"] += b.nbytes
-    for b in outputs:
-        if not b.device:
-            TRANSFER_STATS["d2h_bytes"] += b.nbytes
-
-
 def to_device(a, device=0):
     """host array -> CUDA tensor (torch owns the memory: plumbing), counted as PCIe traffic"""
     t = torch.from_numpy(np.ascontiguousarray(a)).to(f"cuda:{device}")
@@ -78,6 +69,74 @@ class _Buf:
             self.device = False
             self.ptr = a.ctypes.data
             self.nbytes = a.nbytes
+
+
+class _Call:
+    """The arrays of ONE library call: ``inp`` / ``out`` / ``inout`` register an array and return its pointer, ``host`` a host table
+    that travels beside the arrays.  ``run(export, *args)`` works the flags word out from what was registered and appends it to the
+    arguments (where every C signature has it), orders the call after torch, makes it, checks the return code and counts the host
+    buffers into TRANSFER_STATS (once, after the call returned).
+    ``same_space`` (scoring calls): all arrays live in one memory space, or ``run`` refuses.  Otherwise (forward calls) the first
+    input and the output say where the data lives, each for itself; a call without an input array has no input on the device.
+    ``ins``: the registered inputs of an earlier call that this one takes again."""
+    __slots__ = ("eng", "same_space", "async_", "ordered", "ins", "outs", "h2d")
+
+    def __init__(self, eng, same_space=False, async_=False, ordered=False, ins=()):
+        self.eng = eng
+        self.same_space = same_space
+        self.async_ = async_
+        self.ordered = ordered
+        self.ins = list(ins)
+        self.outs = []
+        self.h2d = 0
+
+    def inp(self, x, dtype=np.float32):
+        b = _Buf(x, dtype)
+        self.ins.append(b)
+        return b.ptr
+
+    def out(self, x, dtype=np.float32):
+        b = _Buf(x, dtype, writable=True)
+        self.outs.append(b)
+        return b.ptr
+
+    def inout(self, x, dtype=np.float32):
+        """an array the call rewrites in place: it travels both ways"""
+        b = _Buf(x, dtype, writable=True)
+        self.ins.append(b)
+        self.outs.append(b)
+        return b.ptr
+
+    def host(self, a):
+        """a contiguous host numpy table (offsets, lengths, group boundaries) that is copied up whatever space the arrays live in"""
+        self.h2d += a.nbytes
+        return a.ctypes.data
+
+    def run(self, export, *args, tail=()):
+        """export(*args, flags, *tail): ``tail`` is what a ragged export takes after the flags"""
+        ins, outs = self.ins, self.outs
+        h2d, d2h, n_dev = self.h2d, 0, 0
+        for b in ins:
+            if b.device:
+                n_dev += 1
+            else:
+                h2d += b.nbytes
+        for b in outs:
+            if b.device:
+                n_dev += 1
+            else:
+                d2h += b.nbytes
+        if n_dev:
+            if self.same_space and n_dev != len(ins) + len(outs):
+                raise ValueError("all arrays of one scoring call must live in the same memory space")
+            if not self.ordered:                            # (ordered: the caller has already waited for torch's stream)
+                self.eng._order_after_torch(self.async_)
+            flags = (_lib.IN_DEVICE if ins and ins[0].device else 0) | (_lib.OUT_DEVICE if outs[0].device else 0)
+        else:
+            flags = 0
+        self.eng._ck(export(*args, (flags | _lib.ASYNC) if self.async_ else flags, *tail))
+        TRANSFER_STATS["h2d_bytes"] += h2d
+        TRANSFER_STATS["d2h_bytes"] += d2h
 
 
 # The ragged exports of the library per model kind, as data: the waveform export and the feature export (None: a waveform model), each a
@@ -152,12 +211,10 @@ class Engine:
         self.h = h
         self._stream = int(stream) if stream else None
 
-    def _order_after_torch(self, *bufs, async_=False, ordered=False):
+    def _order_after_torch(self, async_):
         """Device tensors handed in by torch may still be in flight on torch's current stream.  When the
         handle runs on that same stream the order is already right; otherwise wait for torch's stream
         on the host before the library touches the data (and refuse async calls, which would race)."""
-        if ordered or torch is None or not any(b.device for b in bufs):
-            return                                  # (ordered: the caller has already waited for torch's stream)
         cur = torch.cuda.current_stream(self.device)
         if self._stream is not None and cur.cuda_stream == self._stream:
             return
@@ -223,27 +280,20 @@ class Engine:
         self._ck(self.lib.svhip_load_blob(self.h, str(path).encode()))
 
     # ---- forward ------------------------------------------------------------------------------------------
-    def _out(self, like, shape):
-        if _is_torch(like) and like.is_cuda:
-            return torch.empty(shape, dtype=torch.float32, device=like.device)
-        return np.empty(shape, dtype=np.float32)
-
-    @staticmethod
-    def _flags(i: _Buf, o: _Buf, async_=False):
-        f = (_lib.IN_DEVICE if i.device else 0) | (_lib.OUT_DEVICE if o.device else 0)
-        if async_:
-            f |= _lib.ASYNC
-        return f
+    def _out(self, like, shape, dtype=np.float32):
+        """an uninitialised output where ``like`` lives: a CUDA tensor beside a CUDA tensor, else a numpy array"""
+        if torch is not None and isinstance(like, torch.Tensor) and like.is_cuda:
+            return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=like.device)
+        return np.empty(shape, dtype)
 
     def fbank(self, wav, out=None, async_=False):
         """(B, L) fp32 waveforms -> (B, n_mels, T) mel power (numpy in -> numpy out, CUDA tensor in -> CUDA tensor out)."""
         B, L = wav.shape
         if out is None:
             out = self._out(wav, (B, self.n_mels, self.frames))
-        i, o = _Buf(wav, np.float32), _Buf(out, np.float32, writable=True)
-        self._order_after_torch(i, o, async_=async_)
-        _count([i], [o])
-        self._ck(self.lib.svhip_fbank(self.h, i.ptr, B, L, o.ptr, self._flags(i, o, async_)))
+        c = _Call(self, async_=async_)
+        i, o = c.inp(wav), c.out(out)
+        c.run(self.lib.svhip_fbank, self.h, i, B, L, o)
         return out
 
     def embed_features(self, feat, out=None, async_=False):
@@ -252,10 +302,9 @@ class Engine:
             raise ValueError(f"expected {self.n_mels} feature channels, got {nm}")
         if out is None:
             out = self._out(feat, (B, self.embed_dim))
-        i, o = _Buf(feat, np.float32), _Buf(out, np.float32, writable=True)
-        self._order_after_torch(i, o, async_=async_)
-        _count([i], [o])
-        self._ck(self.lib.svhip_embed_features(self.h, i.ptr, B, T, o.ptr, self._flags(i, o, async_)))
+        c = _Call(self, async_=async_)
+        i, o = c.inp(feat), c.out(out)
+        c.run(self.lib.svhip_embed_features, self.h, i, B, T, o)
         return out
 
     def embed_wave(self, wav, out=None, async_=False, ordered=False):
@@ -264,10 +313,9 @@ class Engine:
         B, L = wav.shape
         if out is None:
             out = self._out(wav, (B, self.embed_dim))
-        i, o = _Buf(wav, np.float32), _Buf(out, np.float32, writable=True)
-        self._order_after_torch(i, o, async_=async_, ordered=ordered)
-        _count([i], [o])
-        self._ck(self.lib.svhip_embed_wave(self.h, i.ptr, B, L, o.ptr, self._flags(i, o, async_)))
+        c = _Call(self, async_=async_, ordered=ordered)
+        i, o = c.inp(wav), c.out(out)
+        c.run(self.lib.svhip_embed_wave, self.h, i, B, L, o)
         return out
 
     def fusion_head(self, e1, e2, out=None, async_=False, ordered=False):
@@ -279,12 +327,11 @@ class Engine:
             raise ValueError(f"the branch embeddings have {B} and {B2} rows")
         if out is None:
             out = self._out(e1, (B, self.embed_dim))
-        i1, i2, o = _Buf(e1, np.float32), _Buf(e2, np.float32), _Buf(out, np.float32, writable=True)
-        if i1.device != i2.device:
+        c = _Call(self, async_=async_, ordered=ordered)
+        i1, i2, o = c.inp(e1), c.inp(e2), c.out(out)
+        if c.ins[0].device != c.ins[1].device:
             raise ValueError("both branch embeddings must live in the same memory space")
-        self._order_after_torch(i1, i2, o, async_=async_, ordered=ordered)
-        _count([i1, i2], [o])
-        self._ck(self.lib.svhip_fusion_head(self.h, i1.ptr, d1, i2.ptr, d2, B, o.ptr, self._flags(i1, o, async_)))
+        c.run(self.lib.svhip_fusion_head, self.h, i1, d1, i2, d2, B, o)
         return out
 
     # ---- ragged batches: utterances of different lengths in one call (_RAGGED names the model's exports) ----
@@ -330,10 +377,9 @@ class Engine:
         n = int(lens.shape[0])
         if out is None:
             out = self._out(packed, (n, self.embed_dim))
-        i, o = _Buf(packed, np.float32), _Buf(out, np.float32, writable=True)
-        self._order_after_torch(i, o, async_=async_, ordered=ordered)
-        _count([i], [o])
-        self._ck(getattr(self.lib, export[0])(self.h, i.ptr, offs.ctypes.data, lens.ctypes.data, n, o.ptr, self._flags(i, o, async_), *export[1:]))
+        c = _Call(self, async_=async_, ordered=ordered)
+        i, o = c.inp(packed), c.out(out)
+        c.run(getattr(self.lib, export[0]), self.h, i, offs.ctypes.data, lens.ctypes.data, n, o, tail=export[1:])   # (the tables are not counted)
         return out
 
     def embed_wave_ragged(self, wavs, offsets=None, lengths=None, out=None, async_=False, ordered=False):
@@ -369,8 +415,9 @@ class Engine:
         offsets / lengths; async_=True (device `out` only) returns once the copy and the crop kernel are enqueued."""
         offs = np.ascontiguousarray(offs, dtype=np.int64)
         lens = np.ascontiguousarray(lens, dtype=np.int32)
-        p = _Buf(pcm, np.int16)
-        if p.device:
+        c = _Call(self, async_=async_)
+        p = c.inp(pcm, np.int16)
+        if c.ins[0].device:
             raise ValueError("packed PCM lives on the host (device PCM: call the C ABI with SVHIP_IN_DEVICE)")
         n_files = int(lens.shape[0])
         n = n_files * num_eval
@@ -378,15 +425,10 @@ class Engine:
             out = np.empty((n, L), dtype=np.float32)
         elif tuple(out.shape) != (n, L):
             raise ValueError(f"out must be ({n}, {L})")
-        o = _Buf(out, np.float32, writable=True)
-        if async_ and not o.device:
+        o = c.out(out)
+        if async_ and not c.outs[0].device:
             raise ValueError("async_ needs a device output tensor")
-        self._order_after_torch(o, async_=async_)
-        TRANSFER_STATS["h2d_bytes"] += p.nbytes + offs.nbytes + lens.nbytes
-        _count([], [o])
-        flags = (_lib.OUT_DEVICE if o.device else 0) | (_lib.ASYNC if async_ else 0)
-        self._ck(self.lib.svhip_crop_pcm16(self.h, p.ptr, p.nbytes // 2, offs.ctypes.data, lens.ctypes.data, n_files,
-                                           int(num_eval), int(L), o.ptr, flags))
+        c.run(self.lib.svhip_crop_pcm16, self.h, p, c.ins[0].nbytes // 2, c.host(offs), c.host(lens), n_files, int(num_eval), int(L), o)
         return out
 
     def synth_waveforms(self, seed, first_utt, B, L=None, out=None, async_=False):
@@ -394,11 +436,9 @@ class Engine:
         L = int(L or self.samples)
         if out is None:
             out = np.empty((B, L), dtype=np.float32)
-        o = _Buf(out, np.float32, writable=True)
-        self._order_after_torch(o, async_=async_)
-        _count([], [o])
-        flags = (_lib.OUT_DEVICE if o.device else 0) | (_lib.ASYNC if async_ else 0)
-        self._ck(self.lib.svhip_synth_waveforms(self.h, int(seed), int(first_utt), int(B), L, o.ptr, flags))
+        c = _Call(self, async_=async_)                       # (no input array: only the output says where the data lives)
+        o = c.out(out)
+        c.run(self.lib.svhip_synth_waveforms, self.h, int(seed), int(first_utt), int(B), L, o)
         return out
 
     # ---- multi-GPU exchange (RCCL under the C ABI) -------------------------------------------------------------
@@ -431,40 +471,29 @@ class Engine:
             raise RuntimeError("comm_init has not been called on this Engine")
         if out is None:
             out = self._out(local, (world * rows, D))
-        i, o = _Buf(local, np.float32), _Buf(out, np.float32, writable=True)
+        c = _Call(self, async_=async_)
+        i, o = c.inp(local), c.out(out)
         if tuple(out.shape) != (world * rows, D):
             raise ValueError(f"out must be ({world * rows}, {D})")
-        self._order_after_torch(i, o, async_=async_)
-        _count([i], [o])
-        self._ck(self.lib.svhip_allgather_rows(self.h, i.ptr, rows, D, o.ptr, self._flags(i, o, async_)))
+        c.run(self.lib.svhip_allgather_rows, self.h, i, rows, D, o)
         return out
 
     # ---- scoring ---------------------------------------------------------------------------------------------
     def l2norm_(self, E):
         N, D = E.shape
-        b = _Buf(E, np.float32, writable=True)
-        self._order_after_torch(b)
-        self._ck(self.lib.svhip_l2norm(self.h, b.ptr, N, D, _lib.IN_DEVICE | _lib.OUT_DEVICE if b.device else 0))
-        _count([b], [b])
+        c = _Call(self, same_space=True)
+        e = c.inout(E)
+        c.run(self.lib.svhip_l2norm, self.h, e, N, D)
         return E
-
-    def _same_space(self, *bufs):
-        dev = {b.device for b in bufs}
-        if len(dev) != 1:
-            raise ValueError("all arrays of one scoring call must live in the same memory space")
-        self._order_after_torch(*bufs)
-        return dev.pop()
 
     def score_pairs(self, E, ia, ib, out=None):
         N, D = E.shape
         P = int(ia.shape[0])
         if out is None:
             out = self._out(E, (P,))
-        e, a, b, o = _Buf(E, np.float32), _Buf(ia, np.int32), _Buf(ib, np.int32), _Buf(out, np.float32, writable=True)
-        dev = self._same_space(e, a, b, o)
-        self._ck(self.lib.svhip_score_pairs(self.h, e.ptr, N, D, a.ptr, b.ptr, P, o.ptr,
-                                            (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
-        _count([e, a, b], [o])
+        c = _Call(self, same_space=True)
+        e, a, b, o = c.inp(E), c.inp(ia, np.int32), c.inp(ib, np.int32), c.out(out)
+        c.run(self.lib.svhip_score_pairs, self.h, e, N, D, a, b, P, o)
         return out
 
     TRIAL_MODES = {"cosine": _lib.TRIAL_COSINE, "pnorm": _lib.TRIAL_PNORM, "pdist": _lib.TRIAL_PDIST}
@@ -476,14 +505,12 @@ class Engine:
         P = int(ia.shape[0])
         if out is None:
             out = self._out(F, (P,))
-        f, a, b, o = _Buf(F, np.float32), _Buf(ia, np.int32), _Buf(ib, np.int32), _Buf(out, np.float32, writable=True)
-        dev = self._same_space(f, a, b, o)
-        fl = (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0
+        c = _Call(self, same_space=True)
+        f, a, b, o = c.inp(F), c.inp(ia, np.int32), c.inp(ib, np.int32), c.out(out)
         if mode == "pnorm" and float(p) != 2.0:
-            self._ck(self.lib.svhip_score_trials_pnorm(self.h, float(p), f.ptr, n_files, n_crops, D, a.ptr, b.ptr, P, o.ptr, fl))
+            c.run(self.lib.svhip_score_trials_pnorm, self.h, float(p), f, n_files, n_crops, D, a, b, P, o)
         else:
-            self._ck(self.lib.svhip_score_trials(self.h, self.TRIAL_MODES[mode], f.ptr, n_files, n_crops, D, a.ptr, b.ptr, P, o.ptr, fl))
-        _count([f, a, b], [o])
+            c.run(self.lib.svhip_score_trials, self.h, self.TRIAL_MODES[mode], f, n_files, n_crops, D, a, b, P, o)
         return out
 
     def mean_crops(self, F, out=None):
@@ -491,10 +518,9 @@ class Engine:
         n_files, n_crops, D = F.shape
         if out is None:
             out = self._out(F, (n_files, D))
-        f, o = _Buf(F, np.float32), _Buf(out, np.float32, writable=True)
-        dev = self._same_space(f, o)
-        self._ck(self.lib.svhip_mean_crops(self.h, f.ptr, n_files, n_crops, D, o.ptr, (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
-        _count([f], [o])
+        c = _Call(self, same_space=True)
+        f, o = c.inp(F), c.out(out)
+        c.run(self.lib.svhip_mean_crops, self.h, f, n_files, n_crops, D, o)
         return out
 
     def score_matrix(self, A, B, out=None):
@@ -502,11 +528,30 @@ class Engine:
         Nb = B.shape[0]
         if out is None:
             out = self._out(A, (Na, Nb))
-        a, b, o = _Buf(A, np.float32), _Buf(B, np.float32), _Buf(out, np.float32, writable=True)
-        dev = self._same_space(a, b, o)
-        self._ck(self.lib.svhip_score_matrix(self.h, a.ptr, Na, b.ptr, Nb, D, o.ptr,
-                                             (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
+        c = _Call(self, same_space=True)
+        a, b, o = c.inp(A), c.inp(B), c.out(out)
+        c.run(self.lib.svhip_score_matrix, self.h, a, Na, b, Nb, D, o)
         return out
+
+    @staticmethod
+    def _stat_pair(what, pair, n):
+        """``what``'s ``(mu, sigma)`` pair of ``asnorm_stats`` for n rows, checked -> the pair"""
+        if pair is None or len(pair) != 2:
+            raise ValueError("stats must be a (mu, sigma) pair" if what == "stats" else "q_stats and g_stats must be (mu, sigma) pairs")
+        for name, x in zip(("mu", "sigma"), pair):
+            if x is None or tuple(x.shape) != (n,):
+                raise ValueError(f"{what}: {name} must hold {n} values, not {None if x is None else tuple(x.shape)}")
+        return tuple(pair)
+
+    def _topk_out(self, c, like, N, k, out):
+        """the ``(scores, index)`` pair of a top-k call: allocated where ``like`` lives, or ``out`` checked; registered as c's outputs
+        -> ``(scores, index, their pointers)``"""
+        shape = (N, max(k, 0))
+        scores, index = out if out is not None else (self._out(like, shape), self._out(like, shape, np.int32))
+        s, i = c.out(scores), c.out(index, np.int32)
+        if c.outs[0].nbytes != N * max(k, 0) * 4 or c.outs[1].nbytes != c.outs[0].nbytes:
+            raise ValueError(f"out must be a ({N}, {k}) float32 and a ({N}, {k}) int32 array")
+        return scores, index, s, i
 
     def score_topk(self, Q, G, k, out=None):
         """1:N identification (``svhip_score_topk``): per row of Q (N, D) the k best rows of the gallery G (M, D) by inner product ->
@@ -517,21 +562,10 @@ class Engine:
         if G.shape[1] != D:
             raise ValueError(f"queries are {D} wide, the gallery {G.shape[1]}")
         k = int(k)
-        if out is None:
-            shape = (N, max(k, 0))
-            if _is_torch(Q) and Q.is_cuda:
-                out = (torch.empty(shape, dtype=torch.float32, device=Q.device), torch.empty(shape, dtype=torch.int32, device=Q.device))
-            else:
-                out = (np.empty(shape, np.float32), np.empty(shape, np.int32))
-        scores, index = out
-        q, g = _Buf(Q, np.float32), _Buf(G, np.float32)
-        s, i = _Buf(scores, np.float32, writable=True), _Buf(index, np.int32, writable=True)
-        if s.nbytes != N * max(k, 0) * 4 or i.nbytes != s.nbytes:
-            raise ValueError(f"out must be a ({N}, {k}) float32 and a ({N}, {k}) int32 array")
-        dev = self._same_space(q, g, s, i)
-        self._ck(self.lib.svhip_score_topk(self.h, q.ptr, N, g.ptr, M, D, k, s.ptr, i.ptr,
-                                           (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
-        _count([q, g], [s, i])
+        c = _Call(self, same_space=True)
+        scores, index, s, i = self._topk_out(c, Q, N, k, out)
+        q, g = c.inp(Q), c.inp(G)
+        c.run(self.lib.svhip_score_topk, self.h, q, N, g, M, D, k, s, i)
         return scores, index
 
     def score_topk_norm(self, Q, q_stats, G, g_stats, k, out=None):
@@ -545,29 +579,13 @@ class Engine:
         M = G.shape[0]
         if G.shape[1] != D:
             raise ValueError(f"queries are {D} wide, the gallery {G.shape[1]}")
-        if q_stats is None or g_stats is None or len(q_stats) != 2 or len(g_stats) != 2:
-            raise ValueError("q_stats and g_stats must be (mu, sigma) pairs")
-        for what, st, n in (("q_stats", q_stats, N), ("g_stats", g_stats, M)):
-            for name, x in zip(("mu", "sigma"), st):
-                if x is None or tuple(x.shape) != (n,):
-                    raise ValueError(f"{what}: {name} must hold {n} values, not {None if x is None else tuple(x.shape)}")
+        stats = self._stat_pair("q_stats", q_stats, N) + self._stat_pair("g_stats", g_stats, M)
         k = int(k)
-        if out is None:
-            shape = (N, max(k, 0))
-            if _is_torch(Q) and Q.is_cuda:
-                out = (torch.empty(shape, dtype=torch.float32, device=Q.device), torch.empty(shape, dtype=torch.int32, device=Q.device))
-            else:
-                out = (np.empty(shape, np.float32), np.empty(shape, np.int32))
-        scores, index = out
-        q, g = _Buf(Q, np.float32), _Buf(G, np.float32)
-        st = [_Buf(x, np.float32) for x in (*q_stats, *g_stats)]
-        s, i = _Buf(scores, np.float32, writable=True), _Buf(index, np.int32, writable=True)
-        if s.nbytes != N * max(k, 0) * 4 or i.nbytes != s.nbytes:
-            raise ValueError(f"out must be a ({N}, {k}) float32 and a ({N}, {k}) int32 array")
-        dev = self._same_space(q, g, *st, s, i)
-        self._ck(self.lib.svhip_score_topk_norm(self.h, q.ptr, N, st[0].ptr, st[1].ptr, g.ptr, M, st[2].ptr, st[3].ptr, D, k, s.ptr, i.ptr,
-                                                (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
-        _count([q, g, *st], [s, i])
+        c = _Call(self, same_space=True)
+        scores, index, s, i = self._topk_out(c, Q, N, k, out)
+        q, g = c.inp(Q), c.inp(G)
+        mq, sq, mg, sg = (c.inp(x) for x in stats)
+        c.run(self.lib.svhip_score_topk_norm, self.h, q, N, mq, sq, g, M, mg, sg, D, k, s, i)
         return scores, index
 
     @staticmethod
@@ -604,34 +622,18 @@ class Engine:
             raise ValueError("score_above: the threshold is NaN")
         if (q_stats is None) != (g_stats is None):
             raise ValueError("score_above: q_stats and g_stats go together: give both (normalised scores) or neither")
-        stats = ()
-        if q_stats is not None:
-            if len(q_stats) != 2 or len(g_stats) != 2:
-                raise ValueError("q_stats and g_stats must be (mu, sigma) pairs")
-            for what, st, n in (("q_stats", q_stats, N), ("g_stats", g_stats, M)):
-                for name, x in zip(("mu", "sigma"), st):
-                    if x is None or tuple(x.shape) != (n,):
-                        raise ValueError(f"{what}: {name} must hold {n} values, not {None if x is None else tuple(x.shape)}")
-            stats = (*q_stats, *g_stats)
-        on_dev = _is_torch(Q) and Q.is_cuda
-        empty = (lambda n, dt: torch.empty(n, dtype=getattr(torch, np.dtype(dt).name), device=Q.device)) if on_dev else np.empty
-        q, g = _Buf(Q, np.float32), _Buf(G, np.float32)
-        st = [_Buf(x, np.float32) for x in stats]
-        sp = [b.ptr for b in st] or [None] * 4
-        count = empty(N, np.int64)
-        c = _Buf(count, np.int64, writable=True)
-        dev = self._same_space(q, g, *st, c)
-        flags = (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0
-        mode = _lib.ABOVE_UPPER if upper else 0
-        self._ck(self.lib.svhip_score_above_count(self.h, q.ptr, N, g.ptr, M, D, thr, *sp, int(q_base), mode, c.ptr, flags))
-        _count([q, g, *st], [c])
+        stats = () if q_stats is None else self._stat_pair("q_stats", q_stats, N) + self._stat_pair("g_stats", g_stats, M)
+        c = _Call(self, same_space=True)
+        q, g = c.inp(Q), c.inp(G)
+        sp = [c.inp(x) for x in stats] or [None] * 4
+        count = self._out(Q, N, np.int64)
+        search = (self.h, q, N, g, M, D, thr, *sp, int(q_base), _lib.ABOVE_UPPER if upper else 0)
+        c.run(self.lib.svhip_score_above_count, *search, c.out(count, np.int64))
         row_ptr, total = self._above_row_ptr(count, max_hits)
-        index, score = empty(total, np.int32), empty(total, np.float32)
+        index, score = self._out(Q, total, np.int32), self._out(Q, total)
         if total:
-            r, i, s = _Buf(row_ptr, np.int64), _Buf(index, np.int32, writable=True), _Buf(score, np.float32, writable=True)
-            self._order_after_torch(r)
-            self._ck(self.lib.svhip_score_above_fill(self.h, q.ptr, N, g.ptr, M, D, thr, *sp, int(q_base), mode, r.ptr, i.ptr, s.ptr, flags))
-            _count([q, g, *st, r], [i, s])
+            c = _Call(self, same_space=True, ins=c.ins)                  # (the same operands again, and row_ptr)
+            c.run(self.lib.svhip_score_above_fill, *search, c.inp(row_ptr, np.int64), c.out(index, np.int32), c.out(score))
         return row_ptr, index, score
 
     def cluster_above(self, E, thr, stats=None):
@@ -646,23 +648,14 @@ class Engine:
         thr = float(thr)
         if thr != thr:
             raise ValueError("cluster_above: the threshold is NaN")
-        if stats is not None:
-            if len(stats) != 2:
-                raise ValueError("stats must be a (mu, sigma) pair")
-            for name, x in zip(("mu", "sigma"), stats):
-                if x is None or tuple(x.shape) != (N,):
-                    raise ValueError(f"stats: {name} must hold {N} values, not {None if x is None else tuple(x.shape)}")
-        on_dev = _is_torch(E) and E.is_cuda
-        empty = (lambda n, dt: torch.empty(n, dtype=getattr(torch, np.dtype(dt).name), device=E.device)) if on_dev else np.empty
-        root, cluster, count = empty(N, np.int32), empty(N, np.int32), empty(1, np.int64)
-        e = _Buf(E, np.float32)
-        st = [_Buf(x, np.float32) for x in (stats or ())]
-        sp = [b.ptr for b in st] or [None] * 2
-        r, c, n = _Buf(root, np.int32, writable=True), _Buf(cluster, np.int32, writable=True), _Buf(count, np.int64, writable=True)
-        dev = self._same_space(e, *st, r, c, n)
-        self._ck(self.lib.svhip_cluster_above(self.h, e.ptr, N, D, thr, *sp, r.ptr, c.ptr, n.ptr, (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
-        _count([e, *st], [r, c, n])
-        return root, cluster, (count[0] if on_dev else int(count[0]))
+        stats = () if stats is None else self._stat_pair("stats", stats, N)
+        root, cluster, count = self._out(E, N, np.int32), self._out(E, N, np.int32), self._out(E, 1, np.int64)
+        c = _Call(self, same_space=True)
+        e = c.inp(E)
+        sp = [c.inp(x) for x in stats] or [None] * 2
+        r, cl, n = c.out(root, np.int32), c.out(cluster, np.int32), c.out(count, np.int64)
+        c.run(self.lib.svhip_cluster_above, self.h, e, N, D, thr, *sp, r, cl, n)
+        return root, cluster, (count[0] if _is_torch(count) else int(count[0]))
 
     @staticmethod
     def _audit_group_ptr(group_ptr, n_files):
@@ -701,22 +694,13 @@ class Engine:
         sizes = np.diff(gp)
         score_ptr = np.zeros(n_groups + 1, np.int64)
         np.cumsum(sizes * sizes, out=score_ptr[1:])
-        on_dev = _is_torch(F) and F.is_cuda
-        empty = (lambda n, dt: torch.empty(n, dtype=getattr(torch, np.dtype(dt).name), device=F.device)) if on_dev else np.empty
-        miss = empty(n_files, np.int32)
-        score = empty(int(score_ptr[-1]), np.float32) if scores else None
+        miss = self._out(F, n_files, np.int32)
+        score = self._out(F, int(score_ptr[-1])) if scores else None
         if n_files and n_groups:
-            f, m = _Buf(F, np.float32), _Buf(miss, np.int32, writable=True)
-            bufs = [f, m]
-            s = None
-            if scores and score_ptr[-1]:
-                s = _Buf(score, np.float32, writable=True)
-                bufs.append(s)
-            dev = self._same_space(*bufs)
-            self._ck(self.lib.svhip_group_audit(self.h, f.ptr, n_files, n_crops, D, gp.ctypes.data, n_groups, float(cut), m.ptr,
-                                                s.ptr if s is not None else None, (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
-            TRANSFER_STATS["h2d_bytes"] += gp.nbytes
-            _count([f], bufs[1:])
+            c = _Call(self, same_space=True)
+            f, m = c.inp(F), c.out(miss, np.int32)
+            s = c.out(score) if scores and score_ptr[-1] else None
+            c.run(self.lib.svhip_group_audit, self.h, f, n_files, n_crops, D, c.host(gp), n_groups, float(cut), m, s)
         return (miss, score, score_ptr) if scores else miss
 
     # ---- verification metrics (host arrays in / out; the trial list is small next to the embeddings) --------------------
@@ -764,11 +748,9 @@ class Engine:
         N, D = E.shape
         K = cohort.shape[0]
         mu, sd = self._out(E, (N,)), self._out(E, (N,))
-        e, c, m, s = _Buf(E, np.float32), _Buf(cohort, np.float32), _Buf(mu, np.float32, True), _Buf(sd, np.float32, True)
-        dev = self._same_space(e, c, m, s)
-        self._ck(self.lib.svhip_asnorm_stats(self.h, e.ptr, N, D, c.ptr, K, int(top), m.ptr, s.ptr,
-                                             (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
-        _count([e, c], [m, s])
+        c = _Call(self, same_space=True)
+        e, co, m, s = c.inp(E), c.inp(cohort), c.out(mu), c.out(sd)
+        c.run(self.lib.svhip_asnorm_stats, self.h, e, N, D, co, K, int(top), m, s)
         return mu, sd
 
     @property
@@ -780,9 +762,8 @@ class Engine:
     def asnorm_last_refit(self):
         """(rows, passes): embeddings of the last asnorm_stats call that the fused kernel decided with a threshold re-derived from its own
         counts (non-Gaussian cohort scores), and the extra passes over them that took"""
-        import ctypes
-        n = ctypes.c_int32(0)
-        rows = int(self.lib.svhip_asnorm_last_refit(self.h, ctypes.byref(n)))
+        n = C.c_int32(0)
+        rows = int(self.lib.svhip_asnorm_last_refit(self.h, C.byref(n)))
         return rows, int(n.value)
 
     def asnorm_pairs(self, E, mu, sigma, ia, ib, out=None):
@@ -790,12 +771,9 @@ class Engine:
         P = int(ia.shape[0])
         if out is None:
             out = self._out(E, (P,))
-        e, m, s = _Buf(E, np.float32), _Buf(mu, np.float32), _Buf(sigma, np.float32)
-        a, b, o = _Buf(ia, np.int32), _Buf(ib, np.int32), _Buf(out, np.float32, writable=True)
-        dev = self._same_space(e, m, s, a, b, o)
-        self._ck(self.lib.svhip_asnorm_pairs(self.h, e.ptr, N, D, m.ptr, s.ptr, a.ptr, b.ptr, P, o.ptr,
-                                             (_lib.IN_DEVICE | _lib.OUT_DEVICE) if dev else 0))
-        _count([e, m, s, a, b], [o])
+        c = _Call(self, same_space=True)
+        e, m, s, a, b, o = c.inp(E), c.inp(mu), c.inp(sigma), c.inp(ia, np.int32), c.inp(ib, np.int32), c.out(out)
+        c.run(self.lib.svhip_asnorm_pairs, self.h, e, N, D, m, s, a, b, P, o)
         return out
 
     # ---- introspection ------------------------------------------------------------------------------------------

@@ -323,19 +323,32 @@ class ModelHandling:
         return torch.from_numpy(emb) if torch is not None else emb
 
     # ---- evaluation ----------------------------------------------------------------------------------------------
+    def _l2norm_crops(self, feats):
+        """L2-normalise every crop row of an (n_files, n_crops, D) block where it lives (F.normalize(p=2, dim=1), model.py:421-423;
+        embed_utterance(normalize=True)): a CUDA tensor in place through a view, a host array in a contiguous float32 copy"""
+        eng = scoring.scoring_engine(self.gpu)
+        if _is_torch(feats) and feats.is_cuda:
+            feats = feats.contiguous()
+            eng.l2norm_(feats.view(-1, feats.shape[-1]))
+            return feats
+        flat = np.ascontiguousarray(np.asarray(_host(feats), np.float32).reshape(-1, feats.shape[-1]))
+        eng.l2norm_(flat)
+        return flat.reshape(feats.shape)
+
+    def _crop_mean_rows(self, files, num_eval):
+        """identify's preparation of its queries, up to the last step: the files' crop embeddings, L2-normalised when the loss sets
+        ``test_normalize``, averaged -> (n_files, nOut) host rows (the caller normalises the means)"""
+        feats = np.ascontiguousarray(_host(self._embed_files(files, num_eval)), dtype=np.float32)       # (n_files, n_crops, nOut)
+        if self.__model__.module.test_normalize:
+            feats = self._l2norm_crops(feats)
+        return np.ascontiguousarray(feats.mean(axis=1))
+
     def _score(self, feats, ia, ib, scoring_mode, cohorts, cohorts_path):
         """(n_files, n_crops, D) embeddings (numpy, or a CUDA tensor that stays where it is) + trial indices -> P float32 scores
         on the host.  Normalisation and every scoring mode are library kernels; with device embeddings the PCIe traffic is the
         index lists up, the P scores down (and the cohort up, for 'norm')."""
-        on_dev = _is_torch(feats) and feats.is_cuda
-        if self.__model__.module.test_normalize:                            # F.normalize(p=2, dim=1), model.py:421-423
-            if on_dev:
-                feats = feats.contiguous()
-                scoring.scoring_engine(self.gpu).l2norm_(feats.view(-1, feats.shape[-1]))
-            else:
-                flat = np.ascontiguousarray(np.asarray(feats, np.float32).reshape(-1, feats.shape[-1]))
-                scoring.scoring_engine(self.gpu).l2norm_(flat)
-                feats = flat.reshape(feats.shape)
+        if self.__model__.module.test_normalize:
+            feats = self._l2norm_crops(feats)
         if cohorts_path is None:
             # model.py:425-431: F.pairwise_distance(ref (n,D,1), com (1,D,n)) takes the 2-norm over the LAST axis of the
             # broadcast (n, D, n) difference, i.e. over the crops j of `com`; score = -mean.  One kernel over the trial list
@@ -477,10 +490,7 @@ class ModelHandling:
                 for pth in paths[:n_emb_per_spk]:
                     files.append(pth)
                     owner.append(si)
-            feats = self._embed_files(files, num_eval)                              # (n_files, n_crops, D)
-            flat = np.ascontiguousarray(feats.reshape(-1, feats.shape[-1]))
-            scoring.scoring_engine(self.gpu).l2norm_(flat)                          # embed_utterance(normalize=True)
-            feats = flat.reshape(feats.shape)
+            feats = self._l2norm_crops(self._embed_files(files, num_eval))          # (n_files, n_crops, D), as embed_utterance(normalize=True)
             owner = np.asarray(owner)
             cohort = np.vstack([feats[owner == si].reshape(-1, feats.shape[-1]).mean(axis=0, keepdims=True)
                                 for si in range(len(spk_files))])
@@ -558,13 +568,9 @@ class ModelHandling:
             check_gallery(gal)
         cohorts = self._cohort(scoring_mode, cohorts, cohorts_path, gal.shape[1])
         eng = scoring.scoring_engine(self.gpu)
-        feats = np.asarray(_host(self._embed_files(files, num_eval)), dtype=np.float32)       # (n_files, n_crops, nOut)
-        if feats.shape[-1] != gal.shape[1]:
-            raise ValueError(f"the model embeds to {feats.shape[-1]} values, the gallery holds {gal.shape[1]}")
-        flat = np.ascontiguousarray(feats.reshape(-1, feats.shape[-1]))
-        if self.__model__.module.test_normalize:
-            eng.l2norm_(flat)
-        q = np.ascontiguousarray(flat.reshape(feats.shape).mean(axis=1))
+        q = self._crop_mean_rows(files, num_eval)
+        if q.shape[1] != gal.shape[1]:
+            raise ValueError(f"the model embeds to {q.shape[1]} values, the gallery holds {gal.shape[1]}")
         eng.l2norm_(q)
         eng.l2norm_(gal)
         return q, gal, classes, cohorts
@@ -695,11 +701,7 @@ class ModelHandling:
             names = list(source) if isinstance(source, (list, tuple)) else [source]
             if not names:
                 raise ValueError("Please provide appropriate source!")
-            feats = np.asarray(_host(self._embed_files(names, num_eval)), dtype=np.float32)       # (n_files, n_crops, nOut)
-            flat = np.ascontiguousarray(feats.reshape(-1, feats.shape[-1]))
-            if self.__model__.module.test_normalize:
-                eng.l2norm_(flat)
-            rows = np.ascontiguousarray(flat.reshape(feats.shape).mean(axis=1))
+            rows = self._crop_mean_rows(names, num_eval)
         else:
             rows, classes = self._gallery(embeds, classes)
             names = [classes[i] for i in range(rows.shape[0])] if classes is not None else list(range(rows.shape[0]))
@@ -743,7 +745,6 @@ class ModelHandling:
         if max_files < 1:
             raise ValueError(f"max_files = {max_files} must be at least 1")
         on_dev = self._feats_on_device()
-        eng = scoring.scoring_engine(self.gpu)
         counts = [None] * len(folders)
 
         def run(batch):
@@ -752,14 +753,7 @@ class ModelHandling:
                 for g in batch:
                     counts[g] = np.zeros(0, np.int32)
                 return
-            feats = self._embed_files(files, num_eval, on_device=on_dev)
-            if _is_torch(feats) and feats.is_cuda:
-                feats = feats.contiguous()
-                eng.l2norm_(feats.view(-1, feats.shape[-1]))                 # embed_utterance(normalize=True)
-            else:
-                flat = np.ascontiguousarray(np.asarray(_host(feats), np.float32).reshape(-1, feats.shape[-1]))
-                eng.l2norm_(flat)
-                feats = flat.reshape(feats.shape)
+            feats = self._l2norm_crops(self._embed_files(files, num_eval, on_device=on_dev))     # embed_utterance(normalize=True)
             group_ptr = np.zeros(len(batch) + 1, np.int64)
             np.cumsum([len(folders[g][1]) for g in batch], out=group_ptr[1:])
             miss = np.asarray(_host(scoring.group_audit(feats, group_ptr, thresh_score, device=self.gpu)))

@@ -43,6 +43,20 @@ def _np(x):
     return x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x)
 
 
+def _feature_block(feats):
+    """crop embeddings as the engine takes them: contiguous float32 where they live, (n_files, n_crops, D) - 2-D is one crop per file"""
+    on_dev = _is_torch(feats) and feats.is_cuda
+    feats = feats.contiguous() if on_dev else np.ascontiguousarray(_np(feats), dtype=np.float32)
+    return feats[:, None, :] if feats.ndim == 2 else feats
+
+
+def _cohort_stats(eng, cohort, top, G, g_stats=None, Q=None):
+    """AS-norm statistics against ``cohort`` -> ``(q_stats, g_stats)``: the gallery's first, unless given; then the queries' (None without Q)"""
+    if g_stats is None:
+        g_stats = eng.asnorm_stats(G, cohort, top)
+    return (None if Q is None else eng.asnorm_stats(Q, cohort, top)), g_stats
+
+
 # ---- batched API ---------------------------------------------------------------------------------------
 def score_pairs(E, ia, ib, device=0):
     """|cos(E[ia], E[ib])| (utils.py:163-164 with one crop per row)."""
@@ -64,9 +78,7 @@ def score_topk_norm(Q, G, k, cohort, top=200, g_stats=None, device=0):
     the k best gallery rows per query are selected on the normalised score.  All arrays in one memory space.
     -> (scores (N, k), int32 index (N, k), g_stats): keep ``g_stats`` with the gallery to skip its statistics next time."""
     eng = scoring_engine(device)
-    if g_stats is None:
-        g_stats = eng.asnorm_stats(G, cohort, top)
-    q_stats = eng.asnorm_stats(Q, cohort, top)
+    q_stats, g_stats = _cohort_stats(eng, cohort, top, G, g_stats, Q)
     scores, index = eng.score_topk_norm(Q, q_stats, G, g_stats, k)
     return scores, index, tuple(g_stats)
 
@@ -83,9 +95,7 @@ def score_above(Q, G, thr, cohort=None, top=200, g_stats=None, upper=False, q_ba
         if g_stats is not None:
             raise ValueError("score_above: g_stats without a cohort (the queries' statistics need it)")
         return eng.score_above(Q, G, thr, upper=upper, q_base=q_base, max_hits=max_hits)
-    if g_stats is None:
-        g_stats = eng.asnorm_stats(G, cohort, top)
-    q_stats = eng.asnorm_stats(Q, cohort, top)
+    q_stats, g_stats = _cohort_stats(eng, cohort, top, G, g_stats, Q)
     return eng.score_above(Q, G, thr, q_stats, g_stats, upper=upper, q_base=q_base, max_hits=max_hits)
 
 
@@ -98,8 +108,8 @@ def cluster(E, thr, cohort=None, top=200, stats=None, device=0):
     if float(thr) != float(thr):
         raise ValueError("cluster: the threshold is NaN")
     eng = scoring_engine(device)
-    if stats is None and cohort is not None:
-        stats = eng.asnorm_stats(E, cohort, top)
+    if cohort is not None:
+        stats = _cohort_stats(eng, cohort, top, E, stats)[1]
     return eng.cluster_above(E, thr, stats)
 
 
@@ -129,13 +139,7 @@ def group_audit(feats, group_ptr, threshold, scores=False, device=0):
     float32 crop embeddings (numpy, or a CUDA tensor that stays where it is), the files sorted by folder; ``group_ptr``: the folders'
     boundaries (n_folders + 1).  Returns per file the number of files of its own folder it does not match under the reference's rule at
     ``threshold`` (``audit_cut``); with ``scores=True`` also the per-folder score blocks (``Engine.group_audit``)."""
-    on_dev = _is_torch(feats) and feats.is_cuda
-    if not on_dev:
-        feats = np.ascontiguousarray(_np(feats), dtype=np.float32)
-    else:
-        feats = feats.contiguous()
-    if feats.ndim == 2:
-        feats = feats[:, None, :]
+    feats = _feature_block(feats)
     Engine._audit_group_ptr(group_ptr, int(feats.shape[0]))           # (refused here: before an engine is even created)
     return scoring_engine(device).group_audit(feats, group_ptr, audit_cut(threshold), scores=scores)
 
@@ -158,11 +162,8 @@ def score_trials(feats, ia, ib, mode="cosine", cohorts=None, top=200, device=0):
       pdist : -mean pairwise distance over the (n, D, n) broadcast               (model.py:425-431, cohorts_path=None)
     Every mode is a device kernel (svhip_score_trials / svhip_mean_crops + svhip_asnorm_*)."""
     from . import engine as _engine
-    on_dev = _is_torch(feats) and feats.is_cuda
-    if not on_dev:
-        feats = np.ascontiguousarray(_np(feats), dtype=np.float32)
-    if feats.ndim == 2:
-        feats = feats[:, None, :]
+    feats = _feature_block(feats)
+    on_dev = _is_torch(feats)                 # (a CUDA tensor: anything else came back as a numpy array)
     ia = np.ascontiguousarray(ia, dtype=np.int32)
     ib = np.ascontiguousarray(ib, dtype=np.int32)
     eng = scoring_engine(device)
@@ -176,7 +177,6 @@ def score_trials(feats, ia, ib, mode="cosine", cohorts=None, top=200, device=0):
     if int(ia.min()) < 0 or int(ib.min()) < 0 or int(ia.max()) >= n_files or int(ib.max()) >= n_files:
         raise ValueError(f"trial indexes outside [0, {n_files})")
     if on_dev:                                # indices follow the embeddings into HBM (8 P bytes over PCIe)
-        feats = feats.contiguous()
         ia, ib = _engine.to_device(ia, feats.device.index), _engine.to_device(ib, feats.device.index)
     if mode in ("cosine", "pnorm", "pdist"):
         return eng.score_trials(feats, ia, ib, mode)

@@ -57,3 +57,31 @@ def fake_embedder(dim=16):
                       (c[:, 1:] * c[:, :-1]).mean(1), np.ones(len(c), np.float32)], 1)
         return f @ P
     return embed
+
+
+class FakeS:
+    def eval(self): return self
+    def state_dict(self): return {}
+
+
+def unit(a):
+    return a / np.maximum(np.linalg.norm(a, axis=-1, keepdims=True), 1e-12)
+
+
+def fake_model_handling(tmp_path, dim=16, **kw):
+    """a ModelHandling over fake_embedder instead of a network -> (handler, the embedder, its audio spec).  device_feats=False unless
+    asked otherwise: the host path, whose numpy blocks the CPU fakes can score, also when the box has a GPU"""
+    from speakerverification_amd import model as sv_model
+    enc = sv_model.SpeakerEncoder.__new__(sv_model.SpeakerEncoder)
+    enc.model = {"name": "ECAPA_TDNN", "nOut": dim}
+    enc.criterion = {"name": "AAmSoftmaxAP"}
+    enc.test_normalize = True
+    enc.features = "melspectrogram"
+    enc.__S__ = FakeS()
+    emb = fake_embedder(dim)
+    enc.forward = lambda data, label=None: emb(data.reshape(-1, data.shape[-1]))
+    net = sv_model.WrappedModel(enc)
+    net.forward = lambda x, label=None: enc.forward(x)
+    spec = {"sample_rate": 16000, "channels": 1, "sentence_len": 2.0, "win_len": 0.025, "hop_len": 0.01}
+    mh = sv_model.ModelHandling(net, audio_spec=spec, save_folder=str(tmp_path), **{"embed_batch": 5, "device_feats": False, **kw})
+    return mh, emb, spec

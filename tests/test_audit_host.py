@@ -74,11 +74,6 @@ def test_wrappers_refuse_a_bad_group_ptr_before_any_launch():
         eng.group_audit(F, [0, 2, 2, 5], 0.5)
 
 
-class _FakeS:
-    def eval(self): return self
-    def state_dict(self): return {}
-
-
 @pytest.fixture
 def handler(monkeypatch, tmp_path):
     eng = fakes.FakeScoringEngine()
@@ -90,19 +85,7 @@ def handler(monkeypatch, tmp_path):
         return st.numpy_group_audit(feats, group_ptr, threshold, **kw)
 
     monkeypatch.setattr(scoring, "group_audit", audit)
-    dim = 16
-    enc = sv_model.SpeakerEncoder.__new__(sv_model.SpeakerEncoder)
-    enc.model = {"name": "ECAPA_TDNN", "nOut": dim}
-    enc.criterion = {"name": "AAmSoftmaxAP"}
-    enc.test_normalize = True
-    enc.features = "melspectrogram"
-    enc.__S__ = _FakeS()
-    emb = fakes.fake_embedder(dim)
-    enc.forward = lambda data, label=None: emb(data.reshape(-1, data.shape[-1]))
-    net = sv_model.WrappedModel(enc)
-    net.forward = lambda x, label=None: enc.forward(x)
-    spec = {"sample_rate": 16000, "channels": 1, "sentence_len": 2.0, "win_len": 0.025, "hop_len": 0.01}
-    mh = sv_model.ModelHandling(net, audio_spec=spec, save_folder=str(tmp_path), embed_batch=5, device_feats=False)
+    mh = fakes.fake_model_handling(tmp_path)[0]
     return mh, calls
 
 

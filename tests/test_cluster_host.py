@@ -188,33 +188,12 @@ class _ClusterEngine(fakes.FakeScoringEngine):
         return cs.statement(E, thr, stats)
 
 
-class _FakeS:
-    def eval(self): return self
-    def state_dict(self): return {}
-
-
 @pytest.fixture
 def handler(monkeypatch, tmp_path):
     eng = _ClusterEngine()
     monkeypatch.setattr(scoring, "scoring_engine", lambda device=0: eng)
-    dim = 16
-    enc = sv_model.SpeakerEncoder.__new__(sv_model.SpeakerEncoder)
-    enc.model = {"name": "ECAPA_TDNN", "nOut": dim}
-    enc.criterion = {"name": "AAmSoftmaxAP"}
-    enc.test_normalize = True
-    enc.features = "melspectrogram"
-    enc.__S__ = _FakeS()
-    emb = fakes.fake_embedder(dim)
-    enc.forward = lambda data, label=None: emb(data.reshape(-1, data.shape[-1]))
-    net = sv_model.WrappedModel(enc)
-    net.forward = lambda x, label=None: enc.forward(x)
-    spec = {"sample_rate": 16000, "channels": 1, "sentence_len": 2.0, "win_len": 0.025, "hop_len": 0.01}
-    mh = sv_model.ModelHandling(net, audio_spec=spec, save_folder=str(tmp_path), embed_batch=5, device_feats=False)
+    mh = fakes.fake_model_handling(tmp_path)[0]
     return mh, eng
-
-
-def _unit(a):
-    return a / np.maximum(np.linalg.norm(a, axis=-1, keepdims=True), 1e-12)
 
 
 def test_model_cluster_argument_rules(handler):
@@ -262,17 +241,17 @@ def test_model_cluster_groups_and_min_size(handler, tmp_path):
     assert mh.cluster(embeds=three, thresh_score=0.5)[0].tolist() == [0, 1, 2, 0, 1, 0, 3]
     # norm mode: the rows' statistics come from the cohort, once, and go into the one call
     eng.calls.clear()
-    cohort = _unit(np.random.default_rng(3).standard_normal((12, 16))).astype(np.float32)
+    cohort = fakes.unit(np.random.default_rng(3).standard_normal((12, 16))).astype(np.float32)
     labels, _ = mh.cluster(embeds=gal, thresh_score=-50.0, scoring_mode="norm", cohorts=cohort, cohort_top=5)
     assert len(eng.calls) == 1 and eng.calls[0][2] is not None and eng.calls[0][2][0].shape == (7,)
-    assert labels.tolist() == cs.statement(_unit(gal), -50.0, eng.calls[0][2])[1].tolist()
+    assert labels.tolist() == cs.statement(fakes.unit(gal), -50.0, eng.calls[0][2])[1].tolist()
 
 
 def test_model_cluster_from_files(handler, tmp_path):
     mh, eng = handler
     files, _, _ = make_e2e_files(str(tmp_path))
     num_eval = 3
-    q = _unit(np.stack([_unit(mh.embed_utterance(f, num_eval=num_eval, normalize=False).numpy().astype(np.float64)).mean(axis=0) for f in files]))
+    q = fakes.unit(np.stack([fakes.unit(mh.embed_utterance(f, num_eval=num_eval, normalize=False).numpy().astype(np.float64)).mean(axis=0) for f in files]))
     S = q @ q.T
     v = np.sort(S[np.triu_indices(len(files), 1)])
     k = int(np.argmax(np.diff(v)))

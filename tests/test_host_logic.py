@@ -59,28 +59,6 @@ def test_score_trials_equals_reference_per_trial_loop(fake_engine, golden_dir):
     assert abs(scoring.similarity_measure("zt_norm", Rn[0], Cn[0], cohorts=g["cohort"], top=int(g["top"])) - g["zt_norm"][0]) < 1e-4
 
 
-class _FakeS:
-    def eval(self): return self
-    def state_dict(self): return {}
-
-
-def _make_handler(tmp_path, dim=16):
-    enc = sv_model.SpeakerEncoder.__new__(sv_model.SpeakerEncoder)
-    enc.model = {"name": "ECAPA_TDNN", "nOut": dim}
-    enc.criterion = {"name": "AAmSoftmaxAP"}
-    enc.test_normalize = True
-    enc.features = "melspectrogram"
-    enc.__S__ = _FakeS()
-    emb = fakes.fake_embedder(dim)
-    enc.forward = lambda data, label=None: emb(data.reshape(-1, data.shape[-1]))
-    net = sv_model.WrappedModel(enc)
-    net.forward = lambda x, label=None: enc.forward(x)
-    spec = {"sample_rate": 16000, "channels": 1, "sentence_len": 2.0, "win_len": 0.025, "hop_len": 0.01}
-    # device_feats=False: the host path, whose numpy blocks the CPU fakes can score, also when the box has a GPU
-    mh = sv_model.ModelHandling(net, audio_spec=spec, save_folder=str(tmp_path), embed_batch=5, device_feats=False)
-    return mh, emb, spec
-
-
 def _expected_scores(files, lines, emb, spec, num_eval):
     feats = {}
     for f in files:
@@ -91,7 +69,7 @@ def _expected_scores(files, lines, emb, spec, num_eval):
 
 def test_evaluate_from_list_plumbing(fake_engine, tmp_path):
     files, trial_path, lines = make_e2e_files(str(tmp_path))
-    mh, emb, spec = _make_handler(tmp_path)
+    mh, emb, spec = fakes.fake_model_handling(tmp_path)
     for ne in (1, 3):
         sc, lab, tr = mh.evaluateFromList(listfilename=trial_path, distributed=False, dataloader_options={"num_workers": 0},
                                           cohorts_path="unused", num_eval=ne, scoring_mode="cosine")
@@ -105,7 +83,7 @@ def test_evaluate_from_list_plumbing(fake_engine, tmp_path):
 
 def test_test_from_list_and_prepare(fake_engine, tmp_path):
     files, _, _ = make_e2e_files(str(tmp_path))
-    mh, emb, spec = _make_handler(tmp_path)
+    mh, emb, spec = fakes.fake_model_handling(tmp_path)
     csv_path = tmp_path / "pairs.txt"
     csv_path.write_text("audio_1,audio_2\n" + "".join(f"{files[i]},{files[i + 1]}\n" for i in range(4)))
     res = mh.testFromList(test_list=str(csv_path), thresh_score=0.5, cohorts_path=None, num_eval=2, scoring_mode="cosine",
@@ -129,7 +107,7 @@ def test_pairwise_distance_scoring_goes_through_the_trial_kernel(fake_engine, tm
     normalises, then hands the whole trial list to ONE scoring call in mode 'pdist' (svhip_score_trials on a GPU; here the
     stand-in engine, which evaluates the reference's own per-trial expression) — no (P, n, D, n) temporary on the host."""
     import torch.nn.functional as F
-    mh, emb, spec = _make_handler(tmp_path)
+    mh, emb, spec = fakes.fake_model_handling(tmp_path)
     rng = np.random.Generator(np.random.PCG64(5))
     n_files, n, D = 40, 10, 192
     feats = rng.standard_normal((n_files, n, D)).astype(np.float32)
@@ -184,7 +162,7 @@ def _gloo_worker(rank, world, port, tmp, q):
         ok1 = bool(torch.equal(full, torch.arange(n, dtype=torch.float32)[:, None] * torch.ones(1, 3)))
         # 2. evaluateFromList shards files over ranks and scores on rank 0
         files, trial_path, lines = make_e2e_files(os.path.join(tmp, f"r{rank}"))
-        mh, emb, spec = _make_handler(tmp)
+        mh, emb, spec = fakes.fake_model_handling(tmp)
         sc, lab, tr = mh.evaluateFromList(listfilename=trial_path, distributed=True, dataloader_options={}, cohorts_path="x",
                                           num_eval=2, scoring_mode="cosine")
         # 3. row-sharded scoring: every rank scores the trials of its enrol block, rank 0 assembles them
@@ -219,7 +197,7 @@ def test_two_rank_gloo_sharded_evaluation(tmp_path):
     files, trial_path, lines = make_e2e_files(str(tmp_path / "single"))  if os.makedirs(tmp_path / "single", exist_ok=True) is None else None
     eng = fakes.FakeScoringEngine()
     scoring.scoring_engine = lambda device=0: eng
-    mh, emb, spec = _make_handler(tmp_path)
+    mh, emb, spec = fakes.fake_model_handling(tmp_path)
     sc, _, _ = mh.evaluateFromList(listfilename=trial_path, distributed=False, dataloader_options={}, cohorts_path="x",
                                    num_eval=2, scoring_mode="cosine")
     assert np.abs(np.array(sc) - np.array(res[0][1])).max() < 1e-6

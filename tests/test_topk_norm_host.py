@@ -64,11 +64,6 @@ def _numpy_topk(Q, G, k, device=0):
     return np.take_along_axis(S, order, axis=1).astype(np.float32), order.astype(np.int32)
 
 
-class _FakeS:
-    def eval(self): return self
-    def state_dict(self): return {}
-
-
 @pytest.fixture
 def handler(monkeypatch, tmp_path):
     eng = fakes.FakeScoringEngine()
@@ -85,24 +80,8 @@ def handler(monkeypatch, tmp_path):
 
     monkeypatch.setattr(scoring, "score_topk", topk)
     monkeypatch.setattr(scoring, "score_topk_norm", topk_norm)
-    dim = 16
-    enc = sv_model.SpeakerEncoder.__new__(sv_model.SpeakerEncoder)
-    enc.model = {"name": "ECAPA_TDNN", "nOut": dim}
-    enc.criterion = {"name": "AAmSoftmaxAP"}
-    enc.test_normalize = True
-    enc.features = "melspectrogram"
-    enc.__S__ = _FakeS()
-    emb = fakes.fake_embedder(dim)
-    enc.forward = lambda data, label=None: emb(data.reshape(-1, data.shape[-1]))
-    net = sv_model.WrappedModel(enc)
-    net.forward = lambda x, label=None: enc.forward(x)
-    spec = {"sample_rate": 16000, "channels": 1, "sentence_len": 2.0, "win_len": 0.025, "hop_len": 0.01}
-    mh = sv_model.ModelHandling(net, audio_spec=spec, save_folder=str(tmp_path), embed_batch=5, device_feats=False)
+    mh = fakes.fake_model_handling(tmp_path)[0]
     return mh, calls
-
-
-def _unit(a):
-    return a / np.maximum(np.linalg.norm(a, axis=-1, keepdims=True), 1e-12)
 
 
 def test_identify_norm_host_logic(handler, tmp_path):
@@ -112,9 +91,9 @@ def test_identify_norm_host_logic(handler, tmp_path):
     per_file = [mh.embed_utterance(f, num_eval=num_eval, normalize=True).numpy() for f in files]
     embeds = np.stack([np.stack(per_file[2 * c:2 * c + 2], 0).mean(axis=0) for c in range(n_class)], -1).astype(np.float32)
     names = [f"spk{c}" for c in range(n_class)]
-    cohort = _unit(np.random.default_rng(3).standard_normal((12, 16))).astype(np.float32)
-    gal = _unit(embeds.astype(np.float64).mean(axis=0).T)
-    q = _unit(np.stack([_unit(mh.embed_utterance(f, num_eval=num_eval, normalize=False).numpy().astype(np.float64)).mean(axis=0)
+    cohort = fakes.unit(np.random.default_rng(3).standard_normal((12, 16))).astype(np.float32)
+    gal = fakes.unit(embeds.astype(np.float64).mean(axis=0).T)
+    q = fakes.unit(np.stack([fakes.unit(mh.embed_utterance(f, num_eval=num_eval, normalize=False).numpy().astype(np.float64)).mean(axis=0)
                         for f in files]))
     want_s, want_i, _ = _numpy_topk_norm(q, gal, 2, cohort, top_c)
 
