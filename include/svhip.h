@@ -487,6 +487,46 @@ int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, con
  *                  ("cluster_gemm", "cluster_link_rows"; score_topk's slab refusals and magnitude contract hold).  Both: "cluster_init"
  *                  before, "cluster_flatten" and "cluster_ids" (a hand-written scan of the root flags) behind.  Scratch is O(N) plus
  *                  the slab: no buffer's size depends on the number of links.
+ *   cluster_linkage: speaker clustering that does not chain: AVERAGE or COMPLETE linkage cut at thr, without the N x N matrix.  Every
+ *                  merge of either linkage at a level >= thr needs one pair with v >= thr, so every such cluster lies inside ONE
+ *                  component of cluster_above(E, thr, mu, sigma): the COMPONENTS are cluster_above's (its kernels, its routes, its
+ *                  bits), and the agglomeration runs inside each component alone, one workgroup per component.
+ *                  Scores inside a component: v(i, j) = ONE fp32 chain fmaf(E[i][d], E[j][d], v) over d = 0 .. D - 1 from +0 - the
+ *                  exact fp32 inner product of exactly representable data, within (D + 1) 2^-24 sum|e_i e_j| of the float64 one, NOT
+ *                  bound to the bits of score_above's MFMA order - or, with mu / sigma, t = fmaf(v, a_i + a_j, -(b_i + b_j)) from
+ *                  cluster_above's coefficients.  v(i, j) and v(j, i) are the same bits (the pair is computed once); a NaN v is
+ *                  taken as -inf.  Inside a component every row starts as its own cluster.  L(A, B) = the sum (average) or the
+ *                  minimum (complete) of v(a, b) over a in A, b in B, kept per pair of clusters and updated by L(A u B, C) = L(A, C) +
+ *                  L(B, C) (one fp32 add) or fminf of the two; g(A, B) = L / (float)(|A| |B|) (average: one fp32 division) or L
+ *                  (complete).  Repeat: among all pairs of current clusters of the component take the largest g, equal values going
+ *                  to the smallest (min A, min B) with min A < min B; if g >= thr merge, otherwise stop (a NaN g is never taken).
+ *                  Outputs: out_root[i] = the smallest row of i's final cluster; out_cluster / *out_n_clusters as cluster_above's
+ *                  (dense ids in order of the smallest member); *out_n_unrefined (int64, optional: NULL = not wanted) = the number
+ *                  of components of more than SVHIP_LINKAGE_MAX_ROWS rows: one workgroup owns a component, so such a component is
+ *                  NOT refined and stays one cluster (the cap is a measured value: one component of 256 / 512 / 1 024 rows
+ *                  takes 2.2 / 7.0 / 25 ms on an MI355X whatever else the call holds, 2 048 / 4 096 rows took 104 / 450 ms).
+ *                  The result is a function of the data only, the same bits on every run, and
+ *                  a row's cluster depends only on the rows of its own component: not on N, the component's place, the other
+ *                  components or the launch.  `linkage`: SVHIP_LINKAGE_AVERAGE or SVHIP_LINKAGE_COMPLETE, anything else
+ *                  SVHIP_ERR_INVALID.  Refusals as cluster_above's, messages starting "cluster_linkage:", before any copy or launch,
+ *                  outputs untouched.  N = 0: SVHIP_OK, both counts 0.  thr = -inf is legal (everything whose v is not NaN is one
+ *                  component, and merges down to one cluster).  Pointer spaces and SVHIP_ASYNC as cluster_above.
+ *                  Device side (csrc/score_linkage.hip).  "linkage_table": per component its size (integer atomics on the dense id),
+ *                  an exclusive scan to offsets (cluster_ids' hand-written block scan), the member list through an atomic cursor
+ *                  (the owning workgroup sorts it ascending) and three work lists by size.  "linkage_agglo": one workgroup per
+ *                  component of >= 2 rows builds the m x m matrix with plain FMAs and agglomerates in place - per row the best partner
+ *                  above it is cached, a merge is one argmax over the caches, the row / column update of the surviving slot (the
+ *                  cluster's smallest member) and a rescan of the rows whose cached partner was merged.  m <= 64 and m <=
+ *                  SVHIP_LINKAGE_LDS_ROWS (option "linkage_lds_rows" lowers it; tests) keep the matrix in LDS; larger components keep
+ *                  it in a pool of scratch of min(2^24, N min(N, SVHIP_LINKAGE_MAX_ROWS)) floats - 64 MiB at most, the fixed budget;
+ *                  the handle's scratch slots grow by half again, so up to 96 MiB are held.  The pool exists whenever N exceeds the
+ *                  LDS cap, whether or not a component needs it, in the slot of the slab route's slab: where it is larger than the
+ *                  slab the slot is reallocated behind a stream synchronise, in an SVHIP_ASYNC call too.  One thread packs those
+ *                  components into rounds whose matrices fit the pool, and one launch per round the host cannot rule out follows
+ *                  ("linkage_agglo_pool": 2 floor(N min(N, SVHIP_LINKAGE_MAX_ROWS) / pool) + 1 launches, 33 at 262 144 rows; an empty
+ *                  round returns at once); both homes run one body and give the same bits.  No
+ *                  host round trip: the sizes never leave the device.  Then "cluster_ids" over the refined roots.  Nothing's size
+ *                  depends on the number of links.
  *   group_audit  : dataset audit ("which files of a speaker folder do not sound like the rest of it?", the label-noise audit of the
  *                  reference's src/benchmark/benchmark_dataset.py:32-84): per file the number of files of its OWN group it does not match.
  *                  Inputs: F (n_files, n_crops, D) fp32 crop embeddings, the files sorted by group; group_ptr[n_groups + 1] int64, ALWAYS
@@ -545,6 +585,13 @@ int svhip_score_above_fill(svhip_handle* h, const float* Q, int64_t N, const flo
 int svhip_cluster_above(svhip_handle* h, const float* E, int64_t N, int32_t D, float thr, const float* mu, const float* sigma,
                         int32_t* out_root /* int32[N] */, int32_t* out_cluster /* int32[N], or NULL */,
                         int64_t* out_n_clusters, int32_t flags);
+/* average / complete linkage inside cluster_above's components (cluster_linkage above); out_cluster and out_n_unrefined may be NULL. */
+enum { SVHIP_LINKAGE_AVERAGE = 1, SVHIP_LINKAGE_COMPLETE = 2 };
+#define SVHIP_LINKAGE_MAX_ROWS 1024
+#define SVHIP_LINKAGE_LDS_ROWS 176      /* the largest component whose matrix lives in LDS */
+int svhip_cluster_linkage(svhip_handle* h, const float* E, int64_t N, int32_t D, float thr, const float* mu, const float* sigma,
+                          int32_t linkage, int32_t* out_root /* int32[N] */, int32_t* out_cluster /* int32[N], or NULL */,
+                          int64_t* out_n_clusters, int64_t* out_n_unrefined /* or NULL */, int32_t flags);
 /* dataset audit (group_audit above): group_ptr is always a HOST array; out_score may be NULL. */
 int svhip_group_audit(svhip_handle* h, const float* F, int64_t n_files, int32_t n_crops, int32_t D,
                       const int64_t* group_ptr /* host, int64[n_groups + 1] */, int64_t n_groups, float cut,
@@ -694,7 +741,9 @@ double svhip_workload_flops(const svhip_handle* h);
  * "pw3_cus" (cap of the persistent GEMM grids; 0: off), "rn_unfused", "asp_v1", "r2_big", "x3_keep_f32",
  * "asnorm_slab", "asnorm_f32mfma", "asnorm_norefit", "score_f32mfma", "score_tiled", "fbank32", "fbank_unfused", "rn_sinc_full", "cv_off",
  * "pw3_tail_off", "n128_off", "r2_slices", "rn_tail_big", "rn_sinc_f32", "rn_step_off", "rn_pool_off", "layer_labels", "rn_conv_unfused",
- * "rn_keep", "cf_keep", "tn_keep", "rs_keep".
+ * "rn_keep", "cf_keep", "tn_keep", "rs_keep", "linkage_lds_rows" (cluster_linkage: the largest component held in LDS, 2 ..
+ * SVHIP_LINKAGE_LDS_ROWS; anything else: the default), "linkage_fill_only" (cluster_linkage builds the score matrices and merges
+ * nothing: every row stays its own cluster; measurements).
  * Unknown names: SVHIP_ERR_INVALID. */
 int svhip_set_option(svhip_handle* h, const char* name, int32_t value);
 /* Free the scoring / metrics scratch slots of the handle (grown on demand, otherwise kept until svhip_destroy). */

@@ -27,6 +27,8 @@ F32, BF16, I64, F32X3, F16 = 0, 1, 2, 3, 4
 IN_DEVICE, OUT_DEVICE, ASYNC = 1, 2, 4
 TRIAL_COSINE, TRIAL_PNORM, TRIAL_PDIST = 0, 1, 2
 ABOVE_UPPER = 1                            # svhip_score_above_*: only the pairs with m > q_base + n (the self-join of one set)
+LINKAGE_AVERAGE, LINKAGE_COMPLETE = 1, 2    # svhip_cluster_linkage
+LINKAGE_MAX_ROWS, LINKAGE_LDS_ROWS = 1024, 176      # a larger component is not refined / leaves LDS for scratch (include/svhip.h)
 COMM_ID_BYTES = 128
 
 
@@ -96,6 +98,7 @@ _SIGNATURES = {
     "svhip_score_above_fill": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P,
                                          C.c_int32]),
     "svhip_cluster_above": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P, _P, _P, C.c_int32]),
+    "svhip_cluster_linkage": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32]),
     "svhip_group_audit": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, C.c_float, _P, _P, C.c_int32]),
     "svhip_asnorm_stats": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
     "svhip_asnorm_pairs": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, C.c_int32]),

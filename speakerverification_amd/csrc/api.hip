@@ -55,6 +55,8 @@ const DevOptRow kDevOpts[] = {
     SV_OPT(cf_keep, "SVHIP_CF_KEEP", OPT_IS1, 0),
     SV_OPT(tn_keep, "SVHIP_TN_KEEP", OPT_IS1, 0),
     SV_OPT(rs_keep, "SVHIP_RS_KEEP", OPT_IS1, 0),
+    SV_OPT(linkage_lds_rows, "SVHIP_LINKAGE_LDS_ROWS", OPT_NUM, 0),
+    SV_OPT(linkage_fill_only, nullptr, OPT_NO_ENV, 0),
 };
 #undef SV_OPT
 

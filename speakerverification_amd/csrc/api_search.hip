@@ -344,22 +344,27 @@ int cluster_slab(svhip_handle* h, const ClusterArgs& a) {
     });
 }
 
-int cluster_above_impl(svhip_handle* h, const float* E, int64_t N, int32_t D, float thr, const float* mu, const float* sigma, int32_t* out_root,
-                       int32_t* out_cluster, int64_t* out_n_clusters, int32_t flags) {
+// both entry points: linkage = 0 is cluster_above (single linkage: the components themselves), else svhip_cluster_linkage's enum; `name`
+// prefixes the messages.  With a linkage the components' dense ids go to scratch, the table and the agglomeration (score_linkage.hip)
+// rewrite out_root inside each component, and cluster_ids runs once more over the refined roots.
+int cluster_impl(svhip_handle* h, const char* name, int32_t linkage, const float* E, int64_t N, int32_t D, float thr, const float* mu,
+                 const float* sigma, int32_t* out_root, int32_t* out_cluster, int64_t* out_n_clusters, int64_t* out_n_unrefined, int32_t flags) {
     if (!h) return SVHIP_ERR_INVALID;
-    if (thr != thr) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: the threshold is NaN");
-    if (D < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: D = %d must be at least 1", (int)D);
-    if (N < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: N = %lld is negative", (long long)N);
-    if (N > (int64_t)INT32_MAX) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: N = %lld is outside [0, 2^31 - 1]", (long long)N);
-    if (!mu != !sigma) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: %s is NULL: give mu and sigma or neither", mu ? "sigma" : "mu");
-    if (!out_n_clusters || (N > 0 && (!E || !out_root))) SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_above: NULL pointer");
-    if (D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "cluster_above: embedding dim %d must be a multiple of 32", (int)D);      // before any copy or launch
+    if (thr != thr) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: the threshold is NaN", name);
+    if (D < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: D = %d must be at least 1", name, (int)D);
+    if (N < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: N = %lld is negative", name, (long long)N);
+    if (N > (int64_t)INT32_MAX) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: N = %lld is outside [0, 2^31 - 1]", name, (long long)N);
+    if (!mu != !sigma) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: %s is NULL: give mu and sigma or neither", name, mu ? "sigma" : "mu");
+    if (!out_n_clusters || (N > 0 && (!E || !out_root))) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: NULL pointer", name);
+    if (D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "%s: embedding dim %d must be a multiple of 32", name, (int)D);      // before any copy or launch
     Staged s(h, flags);
     if (N == 0) {
         int64_t* dN = s.out(svhip_handle::SCR_OUT2, out_n_clusters, 8);
+        int64_t* dU = out_n_unrefined ? s.out(svhip_handle::SCR_CNT, out_n_unrefined, 8) : nullptr;
         if (s.rc) return s.rc;
         SV_HIP(h, hipMemsetAsync(dN, 0, 8, h->stream));
-        return s.finish("cluster_above", SVHIP_OK, false);
+        if (dU) SV_HIP(h, hipMemsetAsync(dU, 0, 8, h->stream));
+        return s.finish(name, SVHIP_OK, false);
     }
     ClusterArgs a{};
     a.N = N; a.D = D; a.thr = thr;
@@ -367,24 +372,59 @@ int cluster_above_impl(svhip_handle* h, const float* E, int64_t N, int32_t D, fl
     a.dRoot = s.out(svhip_handle::SCR_OUT0, out_root, (size_t)N * 4);
     int32_t* dCluster = out_cluster ? s.out(svhip_handle::SCR_OUT1, out_cluster, (size_t)N * 4) : nullptr;
     int64_t* dN = s.out(svhip_handle::SCR_OUT2, out_n_clusters, 8);
+    int64_t* dU = out_n_unrefined ? s.out(svhip_handle::SCR_CNT, out_n_unrefined, 8) : nullptr;
     if (s.rc) return s.rc;
     int rc;
     // the rows are queries and gallery at once: both coefficient tables come from the one (mu, sigma) pair
     const float* stats[4] = {mu, sigma, mu, sigma};
     if (mu && (rc = coef_tables(s, "cluster_coef", stats, N, N, &a.qc, &a.gc))) return rc;
-    void* bcnt = nullptr;
-    if ((rc = scratch(h, svhip_handle::SCR_TOPK, (size_t)cluster_id_blocks(N) * 4, &bcnt))) return rc;
+    // [per-block root counts | linkage: the components' dense ids | the component table | the unrefined count where the caller wants none]
+    Bump b;
+    const size_t o_bcnt = b.take((size_t)cluster_id_blocks(N) * 4);
+    const size_t o_comp = b.take(linkage ? (size_t)N * 4 : 0, 4), o_table = b.take(linkage ? linkage_table_ints(N) * 4 : 0, 4), o_unref = b.take(linkage ? 8 : 0, 8);
+    void* sc = nullptr;
+    if ((rc = scratch(h, svhip_handle::SCR_TOPK, b.size, &sc))) return rc;
+    int32_t* bcnt = at<int32_t>(sc, o_bcnt);
     rc = run(h, "cluster_init", 0, [&]() { return launch_cluster_init(a.dRoot, N, h->stream); });
     if (!rc) rc = score_topk_fused_supported(D) && aligned16(a.dE) ? cluster_fused(h, a) : cluster_slab(h, a);
     if (!rc) rc = run(h, "cluster_flatten", 0, [&]() { return launch_cluster_flatten(a.dRoot, N, h->stream); });
-    if (!rc) rc = run(h, "cluster_ids", 0, [&]() { return launch_cluster_ids(a.dRoot, N, static_cast<int32_t*>(bcnt), dCluster, dN, h->stream); });
-    return s.finish("cluster_above", rc, true);
+    if (!rc && linkage) {
+        int32_t* comp = at<int32_t>(sc, o_comp);
+        int32_t* ti = at<int32_t>(sc, o_table);
+        LinkageParams p;
+        p.E = a.dE; p.N = N; p.D = D; p.thr = thr; p.linkage = linkage; p.coef = a.qc; p.root = a.dRoot;
+        LinkageTable& t = p.t;
+        t.work_stride = N / 2 + 1;
+        t.cnt = ti; t.off = ti + N; t.cursor = ti + 2 * N; t.members = ti + 3 * N; t.bsum = ti + 4 * N;
+        t.work = t.bsum + cluster_id_blocks(N); t.round = t.work + 3 * t.work_stride; t.place = t.round + t.work_stride; t.n_work = t.place + t.work_stride;
+        unsigned long long* unref = reinterpret_cast<unsigned long long*>(dU ? dU : at<int64_t>(sc, o_unref));
+        int lds_rows = h->opt.linkage_lds_rows;
+        if (lds_rows < 2 || lds_rows > LINKAGE_LDS_ROWS) lds_rows = LINKAGE_LDS_ROWS;
+        // the matrices of the components beyond LDS: a pool of 64 MiB at most (the slab, if there was one, is done with)
+        void* pool = nullptr;
+        rc = scratch(h, svhip_handle::SCR_SLAB, N > lds_rows ? (size_t)linkage_pool_floats(N) * 4 : 256, &pool);
+        p.pool = static_cast<float*>(pool);
+        if (!rc) rc = run(h, "cluster_ids", 0, [&]() { return launch_cluster_ids(a.dRoot, N, bcnt, comp, dN, h->stream); });
+        if (!rc) rc = run(h, "linkage_table", 0, [&]() { return launch_linkage_table(comp, N, lds_rows, t, unref, h->stream); });
+        p.fill_only = h->opt.linkage_fill_only;
+        if (!rc) rc = run(h, "linkage_agglo", 0, [&]() { return launch_linkage_agglo(p, lds_rows, false, h->num_cu, h->stream); });
+        if (!rc && N > lds_rows) rc = run(h, "linkage_agglo_pool", 0, [&]() { return launch_linkage_agglo(p, lds_rows, true, h->num_cu, h->stream); });
+    }
+    if (!rc) rc = run(h, "cluster_ids", 0, [&]() { return launch_cluster_ids(a.dRoot, N, bcnt, dCluster, dN, h->stream); });
+    return s.finish(name, rc, true);
 }
 }  // namespace
 
 int svhip_cluster_above(svhip_handle* h, const float* E, int64_t N, int32_t D, float thr, const float* mu, const float* sigma, int32_t* out_root,
                         int32_t* out_cluster, int64_t* out_n_clusters, int32_t flags) {
-    return cluster_above_impl(h, E, N, D, thr, mu, sigma, out_root, out_cluster, out_n_clusters, flags);
+    return cluster_impl(h, "cluster_above", 0, E, N, D, thr, mu, sigma, out_root, out_cluster, out_n_clusters, nullptr, flags);
+}
+
+int svhip_cluster_linkage(svhip_handle* h, const float* E, int64_t N, int32_t D, float thr, const float* mu, const float* sigma, int32_t linkage,
+                          int32_t* out_root, int32_t* out_cluster, int64_t* out_n_clusters, int64_t* out_n_unrefined, int32_t flags) {
+    if (h && linkage != SVHIP_LINKAGE_AVERAGE && linkage != SVHIP_LINKAGE_COMPLETE)
+        SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_linkage: linkage = %d is neither SVHIP_LINKAGE_AVERAGE nor SVHIP_LINKAGE_COMPLETE", (int)linkage);
+    return cluster_impl(h, "cluster_linkage", linkage, E, N, D, thr, mu, sigma, out_root, out_cluster, out_n_clusters, out_n_unrefined, flags);
 }
 
 }  // extern "C"

@@ -98,6 +98,8 @@ struct svhip_handle {
         int cf_keep;              // Conformer: the same for every block's steps, the pooling logits and the pooled vector before attention_norm (tests)
         int tn_keep;              // TitaNet: the same for every mega-block's steps, its SE squeeze and gate, the attention layer, the logits and the pooled vector before BN (tests)
         int rs_keep;              // ResNetSE: the same for the normalised input, every block's two convolutions, SE tile sums, gate, downsample and output, the attention layer, the logits and the pooled vector (tests)
+        int linkage_lds_rows;     // cluster_linkage: the largest component whose matrix lives in LDS (2 .. SVHIP_LINKAGE_LDS_ROWS; else the default) (tests)
+        int linkage_fill_only;    // cluster_linkage: build the score matrices and make no merge - every row stays its own cluster (measurements: the fill's share)
     } opt;
     bool bf16 = false;                        // 16-bit storage handle: bf16, or fp16 when `f16` is set (the flag keeps its round-1 name)
     bool f16 = false;                         // SVHIP_F16: the 16-bit type is IEEE half (RawNet2)

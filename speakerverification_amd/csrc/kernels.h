@@ -3,8 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <atomic>
 
+#include "../../include/svhip.h"
 #include "common.h"
 
 namespace svhip {
@@ -809,6 +811,52 @@ hipError_t launch_cluster_flatten(int32_t* root, int64_t N, hipStream_t stream);
 // int32 of scratch (per-block root counts, scanned in place by one workgroup)
 int64_t cluster_id_blocks(int64_t N);
 hipError_t launch_cluster_ids(const int32_t* root, int64_t N, int32_t* bcnt, int32_t* cluster, int64_t* out_n, hipStream_t stream);
+
+// Average / complete linkage inside the components (score_linkage.hip; svhip.h, cluster_linkage).  The component table, all int32 and all
+// on the device (no size ever reaches the host): per dense component id c its rows cnt[c], the start off[c] of its member list, the
+// list itself (filled through cursor[c], sorted by the workgroup that owns the component), and three work lists of component ids by size:
+//   0: 2 .. min(64, lds_rows) rows   1: .. lds_rows rows (both: the matrix in LDS)   2: .. LINKAGE_MAX_ROWS rows (the matrix in scratch)
+// The matrices of work list 2 live in a POOL of scratch, at most LINKAGE_POOL_FLOATS (64 MiB: sixteen matrices of LINKAGE_MAX_ROWS rows):
+// one thread packs the list into rounds that fit the pool (round[w], place[w]), and the host enqueues one launch per round it cannot rule
+// out - a launch whose round is empty returns at once.
+constexpr int LINKAGE_MAX_ROWS = SVHIP_LINKAGE_MAX_ROWS, LINKAGE_LDS_ROWS = SVHIP_LINKAGE_LDS_ROWS, LINKAGE_SMALL_ROWS = 64;
+constexpr int64_t LINKAGE_POOL_FLOATS = (int64_t)16 << 20;
+struct LinkageTable {
+    int32_t* cnt = nullptr;         // [N], zero behind the last component
+    int32_t* off = nullptr;         // [N]
+    int32_t* cursor = nullptr;      // [N]
+    int32_t* members = nullptr;     // [N]
+    int32_t* bsum = nullptr;        // [cluster_id_blocks(N)]
+    int32_t* work = nullptr;        // [3][work_stride]
+    int32_t* n_work = nullptr;      // [4]: the lengths of the three lists, the rounds of list 2
+    int32_t* round = nullptr;       // [work_stride] per entry of list 2: its round ...
+    int32_t* place = nullptr;       // [work_stride] ... and where its matrix starts in the pool
+    int64_t work_stride = 0;        // N / 2 + 1: the components of at least two rows
+};
+inline size_t linkage_table_ints(int64_t N) { return (size_t)4 * N + (size_t)cluster_id_blocks(N) + 5 * (size_t)(N / 2 + 1) + 4; }
+// The pool of a call over N rows, and the rounds it may take.  The matrices of list 2 hold at most T = N min(N, LINKAGE_MAX_ROWS) floats in
+// all (sum m <= N, m <= min(N, LINKAGE_MAX_ROWS)).  pool == T: everything fits in round 0.  Otherwise a round is closed only when the next
+// matrix does not fit, so a closed round and the first matrix of the round behind it hold more than the pool together: every PAIR of
+// consecutive rounds holds more than the pool, there are at most floor(T / pool) disjoint such pairs, hence at most 2 floor(T / pool) + 1 rounds.
+inline int64_t linkage_pool_floats(int64_t N) { return std::min<int64_t>(LINKAGE_POOL_FLOATS, N * std::min<int64_t>(N, LINKAGE_MAX_ROWS)); }
+inline int64_t linkage_max_rounds(int64_t N) { return 2 * (N * std::min<int64_t>(N, LINKAGE_MAX_ROWS) / linkage_pool_floats(N)) + 1; }
+// comp: the dense component id of every row (cluster_ids' output); *n_unrefined <- the components of more than LINKAGE_MAX_ROWS rows
+hipError_t launch_linkage_table(const int32_t* comp, int64_t N, int lds_rows, const LinkageTable& t, unsigned long long* n_unrefined,
+                                hipStream_t stream);
+struct LinkageParams {
+    const float* E = nullptr;       // (N, D)
+    int64_t N = 0;
+    int D = 0;
+    float thr = 0.0f;
+    int linkage = 0;                // SVHIP_LINKAGE_AVERAGE / _COMPLETE
+    const float2* coef = nullptr;   // the normalised form: (a, b) per row (cluster_above's query table), or NULL
+    LinkageTable t;
+    int32_t* root = nullptr;        // [N]: holds the component roots, receives the refined ones
+    float* pool = nullptr;          // linkage_pool_floats(N) floats: the matrices of work list 2, round by round
+    int fill_only = 0;              // option linkage_fill_only: the matrices are built and no merge is made (a measurement's switch)
+};
+// the launches of linkage_agglo_kernel: one per LDS work list (pool = false), or one per round of list 2 that N cannot rule out (pool = true)
+hipError_t launch_linkage_agglo(const LinkageParams& p, int lds_rows, bool pool, int num_cu, hipStream_t stream);
 
 // Dataset audit (group_audit.hip): files sorted by group; s(i, j) = mean_c | cos(F[i, c], F[j, c]) | (launch_trial_crops mode 0's
 // statement) for the files of one group, a mismatch iff s <= cut; miss[i] counts the files j != i of i's group that i mismatches.

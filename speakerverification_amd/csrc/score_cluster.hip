@@ -31,6 +31,7 @@
 //   no two rows without a chain of links ever are.  The root of every set is then the smallest index of its component, whatever order the
 //   hardware met the links in: the result is a function of the data only.
 // No spin-waits, no cross-lane operation inside the divergent link loop, no inline assembly: plain C++ and HIP atomics.
+#include "block_scan.h"
 #include "common.h"
 #include "kernels.h"
 #include "score_walk.h"
@@ -159,28 +160,7 @@ __device__ __forceinline__ uint32_t root_flags(const int32_t* __restrict__ root,
     return f;
 }
 
-// exclusive prefix of `n` over the 256 threads of a workgroup (ws: 4 ints of LDS); *all = the workgroup's sum
-__device__ __forceinline__ int block_exclusive(int n, int* ws, int* all) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = n;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    __syncthreads();                                                   // (ws may still be read from the round before)
-    if (lane == 63) ws[wave] = incl;
-    __syncthreads();
-    int before = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const int x = ws[w];
-        if (w < wave) before += x;
-        sum += x;
-    }
-    *all = sum;
-    return before + incl - n;
-}
+// (block_exclusive, the workgroup scan of the kernels below: block_scan.h)
 
 __global__ __launch_bounds__(256) void cluster_count_kernel(const int32_t* __restrict__ root, int64_t N, int32_t* __restrict__ bcnt) {
     __shared__ int ws[4];

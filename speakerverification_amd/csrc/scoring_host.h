@@ -35,7 +35,7 @@ struct Staged {
     svhip_handle* h;
     bool din, dout, async;
     int rc;
-    struct Out { void* host; void* dev; size_t bytes; } outs[3] = {};     // (three: the most outputs a call has; no allocation on the call path)
+    struct Out { void* host; void* dev; size_t bytes; } outs[4] = {};     // (four: the most outputs a call has; no allocation on the call path)
     int n_outs = 0;
     Staged(svhip_handle* hh, int32_t flags);
     int stage(int slot, size_t bytes, const void* host_src, void** dev);      // the slot at `bytes`; host_src: copied into it

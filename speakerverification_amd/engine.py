@@ -657,6 +657,35 @@ class Engine:
         c.run(self.lib.svhip_cluster_above, self.h, e, N, D, thr, *sp, r, cl, n)
         return root, cluster, (count[0] if _is_torch(count) else int(count[0]))
 
+    _LINKAGES = {"average": _lib.LINKAGE_AVERAGE, "complete": _lib.LINKAGE_COMPLETE}
+
+    def cluster_linkage(self, E, thr, stats=None, linkage="average"):
+        """Speaker clustering that does not chain (``svhip_cluster_linkage``): average or complete linkage cut at ``thr``, run inside
+        each component of ``cluster_above(E, thr, stats)`` - every merge of either linkage at a level of at least ``thr`` needs one pair
+        that scores at least ``thr``, so no cluster leaves its component, and no N x N matrix is built.  Inside a component every row
+        starts alone; the two clusters with the largest link value - the mean (``"average"``) or the minimum (``"complete"``) of the
+        scores between them - are merged while that value is at least ``thr``, ties going to the pair with the smallest rows.  Returns
+        ``(root, cluster, n_clusters, n_unrefined)``: the first three as ``cluster_above``; ``n_unrefined`` counts the components of
+        more than ``_lib.LINKAGE_MAX_ROWS`` rows, which one workgroup cannot own and which stay one cluster each.  numpy in, numpy out
+        (the counts ints); a CUDA tensor in, CUDA tensors out (the counts 0-d int64 tensors)."""
+        N, D = (int(x) for x in E.shape)
+        thr = float(thr)
+        if thr != thr:
+            raise ValueError("cluster_linkage: the threshold is NaN")
+        if linkage not in self._LINKAGES:
+            raise ValueError(f"cluster_linkage: linkage = {linkage!r} is neither 'average' nor 'complete'")
+        stats = () if stats is None else self._stat_pair("stats", stats, N)
+        root, cluster = self._out(E, N, np.int32), self._out(E, N, np.int32)
+        count, unrefined = self._out(E, 1, np.int64), self._out(E, 1, np.int64)
+        c = _Call(self, same_space=True)
+        e = c.inp(E)
+        sp = [c.inp(x) for x in stats] or [None] * 2
+        r, cl, n, u = c.out(root, np.int32), c.out(cluster, np.int32), c.out(count, np.int64), c.out(unrefined, np.int64)
+        c.run(self.lib.svhip_cluster_linkage, self.h, e, N, D, thr, *sp, self._LINKAGES[linkage], r, cl, n, u)
+        if _is_torch(count):
+            return root, cluster, count[0], unrefined[0]
+        return root, cluster, int(count[0]), int(unrefined[0])
+
     @staticmethod
     def _audit_group_ptr(group_ptr, n_files):
         """``group_audit``'s group table as a contiguous host int64 array, checked by the C ABI's rules (a bad one is a

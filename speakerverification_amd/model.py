@@ -21,10 +21,12 @@ import csv
 import importlib
 import itertools
 import os
+import warnings
 from pathlib import Path
 
 import numpy as np
 
+from . import _lib
 from . import distributed as sv_dist
 from . import scoring
 from .audio import loadWAV, read_pcm16
@@ -668,7 +670,7 @@ class ModelHandling:
         return i, j, s, [(classes[int(a)], classes[int(b)]) for a, b in zip(i, j)]
 
     def cluster(self, source=None, embeds=None, thresh_score=None, classes=None, num_eval=10, scoring_mode="cosine", cohorts=None,
-                cohorts_path=None, cohort_top=200, min_size=1):
+                cohorts_path=None, cohort_top=200, min_size=1, linkage="single"):
         """Which of these are the same speaker?  Groups unlabelled files, or the classes of a carelessly enrolled gallery: two rows are
         linked when their score is at least ``thresh_score``, and a cluster is a connected component of those links - by definition
         the components of the pair set ``duplicates`` returns on the same rows, found by ONE ``cluster_above`` call per set: one pass
@@ -680,9 +682,14 @@ class ModelHandling:
         arguments are ``identify``'s: with ``"norm"`` a row's statistics are taken against the cohort and the link score is the
         adaptive-S-normalised one.
 
-        This is SINGLE linkage, and single linkage chains: one borderline pair joins two speakers, and a string of them joins many.
+        ``linkage``: ``"single"`` (the default) is exactly the above, and single linkage chains: one borderline pair joins two
+        speakers, and a string of them joins many.  ``"average"`` and ``"complete"`` do not: inside each of those components every row
+        starts alone, and the two clusters whose mean (average) or smallest (complete) score is largest are merged while that value
+        is at least ``thresh_score`` - two speakers that one bridge file has joined come apart again.  Both run on the device,
+        component by component, without the n x n matrix (``Engine.cluster_linkage``).  A component of more than
+        ``_lib.LINKAGE_MAX_ROWS`` rows is left as one cluster, and a ``RuntimeWarning`` names how many there were.
         ``scoring_mode="norm"``, whose threshold carries across speakers and channels, and ``min_size``, which drops the clusters too
-        small to trust, are the mitigations on offer; average or complete linkage is not.
+        small to trust, help with every linkage.
 
         Returns ``(labels, groups)``.  ``labels`` (n,) int32: the dense cluster id of every row, clusters numbered in order of their
         smallest member; rows of clusters with fewer than ``min_size`` members get -1 and the remaining clusters are renumbered in the
@@ -692,6 +699,8 @@ class ModelHandling:
             raise ValueError("cluster: give exactly one of source (files) and embeds (a gallery)")
         if thresh_score is None:
             raise ValueError("cluster: thresh_score is required")
+        if linkage not in scoring.LINKAGES:
+            raise ValueError(f"cluster: linkage = {linkage!r} is not one of {scoring.LINKAGES}")
         min_size = int(min_size)
         if min_size < 1:
             raise ValueError(f"cluster: min_size = {min_size} must be at least 1")
@@ -707,7 +716,13 @@ class ModelHandling:
             names = [classes[i] for i in range(rows.shape[0])] if classes is not None else list(range(rows.shape[0]))
         cohorts = self._cohort(scoring_mode, cohorts, cohorts_path, rows.shape[1])
         eng.l2norm_(rows)
-        _, ids, _ = scoring.cluster(rows, thresh_score, cohort=cohorts, top=int(cohort_top), device=self.gpu)
+        if linkage == "single":
+            _, ids, _ = scoring.cluster(rows, thresh_score, cohort=cohorts, top=int(cohort_top), device=self.gpu)
+        else:
+            _, ids, _, unrefined = scoring.cluster(rows, thresh_score, cohort=cohorts, top=int(cohort_top), device=self.gpu, linkage=linkage)
+            if int(unrefined) > 0:
+                warnings.warn(f"cluster: {int(unrefined)} component(s) of more than {_lib.LINKAGE_MAX_ROWS} rows were not refined by "
+                              f"{linkage} linkage and stay one cluster each; raise thresh_score", RuntimeWarning, stacklevel=2)
         ids = np.asarray(_host(ids))
         sizes = np.bincount(ids, minlength=0)
         keep = sizes >= min_size

@@ -99,18 +99,29 @@ def score_above(Q, G, thr, cohort=None, top=200, g_stats=None, upper=False, q_ba
     return eng.score_above(Q, G, thr, q_stats, g_stats, upper=upper, q_base=q_base, max_hits=max_hits)
 
 
-def cluster(E, thr, cohort=None, top=200, stats=None, device=0):
+LINKAGES = ("single", "average", "complete")
+
+
+def cluster(E, thr, cohort=None, top=200, stats=None, device=0, linkage="single"):
     """which rows of E are the same speaker?  Rows ``i < j`` are linked iff their score is at least ``thr``; a cluster is a connected
     component -> ``(root (N,) int32, cluster (N,) int32, n_clusters)`` (``Engine.cluster_above``).  With a ``cohort`` the score is the
     adaptive-S-normalised one of ``score_topk_norm``: the rows' statistics come from ``asnorm_stats(E, cohort, top)``; ``stats =
     (mu, sigma)``, kept from an earlier call, is used as it is.  The clusters are the components of the pair set ``score_above(E, E, thr, ..., upper=True)``
-    returns, found in one pass over the upper half plane and without that pair list."""
+    returns, found in one pass over the upper half plane and without that pair list.
+
+    ``linkage``: ``"single"`` is the above.  ``"average"`` / ``"complete"`` agglomerate inside each of those components until no two
+    clusters' mean / smallest score reaches ``thr`` (``Engine.cluster_linkage``) and return a fourth value, ``n_unrefined``: the
+    components too large to refine, which stay one cluster each."""
     if float(thr) != float(thr):
         raise ValueError("cluster: the threshold is NaN")
+    if linkage not in LINKAGES:
+        raise ValueError(f"cluster: linkage = {linkage!r} is not one of {LINKAGES}")
     eng = scoring_engine(device)
     if cohort is not None:
         stats = _cohort_stats(eng, cohort, top, E, stats)[1]
-    return eng.cluster_above(E, thr, stats)
+    if linkage == "single":
+        return eng.cluster_above(E, thr, stats)
+    return eng.cluster_linkage(E, thr, stats, linkage)
 
 
 def audit_cut(threshold):
