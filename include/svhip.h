@@ -487,6 +487,41 @@ int svhip_crop_pcm16(svhip_handle* h, const int16_t* pcm, int64_t n_samples, con
  *                  ("cluster_gemm", "cluster_link_rows"; score_topk's slab refusals and magnitude contract hold).  Both: "cluster_init"
  *                  before, "cluster_flatten" and "cluster_ids" (a hand-written scan of the root flags) behind.  Scratch is O(N) plus
  *                  the slab: no buffer's size depends on the number of links.
+ *   cluster_join : two-set clustering ("which clusters do these NEW rows belong to?"): joins the rows B (NB, D) to a set A (NA, D) that
+ *                  may already be clustered, without walking A x A again.  The rows are numbered jointly: A's are 0 .. NA - 1, B's
+ *                  NA .. NA + NB - 1.  The graph has three kinds of edges.  SEED links: where root_a (int32[NA]) is given, A's own
+ *                  pairs are NOT scored; row i of A is linked to row root_a[i].  Any array with 0 <= root_a[i] <= i is legal -
+ *                  cluster_above's out_root, or any parent-pointer forest whose pointers go downwards; an entry outside [0, i] is
+ *                  read as i (the row starts alone).  root_b (int32[NB]) likewise, in B's own numbering 0 .. NB - 1.  INTERNAL links
+ *                  of a side whose root_x is NULL: its pairs i < j are scored and linked exactly as cluster_above does on that side
+ *                  alone.  CROSS links, always walked: every pair (a in A, b in B) with v(a, b) >= thr.  v(a, b) is the score
+ *                  score_above returns for the query row a and the gallery row b (the lower joint index is the query, as in
+ *                  cluster_above), or - with the four statistic arrays a_mu[NA], a_sigma[NA], b_mu[NB], b_sigma[NB], all or none -
+ *                  t = fmaf(s, a_a + a_b, -(b_a + b_b)) from the two sides' coefficients ("cluster_join_coef").  A NaN v links
+ *                  nothing; thr = -inf links every pair whose v is not NaN.  Outputs as cluster_above's over the NA + NB joint rows:
+ *                  out_root[i] = the smallest joint index of i's cluster, out_cluster (optional) the dense ids in order of the
+ *                  smallest member, *out_n_clusters their number.  The result is a function of the data only, the same bits on
+ *                  every run.  The components of a graph do not depend on the order its edges are met in, and a score depends only
+ *                  on its two rows, so: both seeds NULL; root_a = cluster_above(A)'s out_root with root_b NULL; and root_a, root_b
+ *                  = cluster_above's out_root of A and of B - all three give cluster_above([A; B]), exactly.  A new row may bridge
+ *                  two old clusters: out_root[i] != root_a[i] for the absorbed cluster's rows is the answer, not an error.
+ *                  Refusals are cluster_above's, before any copy or launch, outputs untouched, messages starting "cluster_join:".
+ *                  SVHIP_ERR_INVALID: a NaN thr, D < 1, a negative NA or NB, NA + NB > 2^31 - 1, some but not all of the four
+ *                  statistic pointers, a NULL A where NA > 0 (likewise B), a NULL out_root where NA + NB > 0, a NULL
+ *                  out_n_clusters; D % 32 != 0: SVHIP_ERR_UNSUPPORTED.  Seeds handed over as HOST arrays are checked on the host too:
+ *                  an entry outside [0, i] is SVHIP_ERR_INVALID and names the first offending index (device seeds get the
+ *                  read-as-i rule).  NA + NB = 0: SVHIP_OK, *out_n_clusters = 0.  NA = 0 or NB = 0 is legal: one side alone, seeded
+ *                  (no MFMA pass at all) or walked.  Pointer spaces (A, B, root_a, root_b and the statistics in; the three outputs
+ *                  out) and SVHIP_ASYNC as cluster_above.
+ *                  Device side (csrc/score_cluster.hip).  "cluster_seed" writes the joint forest (the clamp above is one function,
+ *                  shared with the host check and exercised by svhip_selftest: the forest's climbs end only because parent[x] <= x).
+ *                  Fused route (D in {192, 256}, A and B 16-byte aligned): one link launch per part of the plan over queries = A,
+ *                  gallery = B - or the other way round where B is the smaller side: on this route v(a, b) and v(b, a) are the same
+ *                  bits ("cluster_join_link": cluster_link's body with an index offset per side and no mask); an unseeded
+ *                  side's self-join runs cluster_above's plan behind the side's offset ("cluster_join_self").  Every other width or
+ *                  alignment: slabs and a row kernel ("cluster_join_gemm" / "cluster_join_rows", "cluster_join_self_gemm" /
+ *                  "cluster_join_self_rows"; score_topk's slab refusals hold, for NB as the gallery and for an unseeded side).  Then
+ *                  "cluster_flatten" and "cluster_ids" over NA + NB rows.  Scratch is O(NA + NB) plus the slab.
  *   cluster_linkage: speaker clustering that does not chain: AVERAGE or COMPLETE linkage cut at thr, without the N x N matrix.  Every
  *                  merge of either linkage at a level >= thr needs one pair with v >= thr, so every such cluster lies inside ONE
  *                  component of cluster_above(E, thr, mu, sigma): the COMPONENTS are cluster_above's (its kernels, its routes, its
@@ -585,6 +620,13 @@ int svhip_score_above_fill(svhip_handle* h, const float* Q, int64_t N, const flo
 int svhip_cluster_above(svhip_handle* h, const float* E, int64_t N, int32_t D, float thr, const float* mu, const float* sigma,
                         int32_t* out_root /* int32[N] */, int32_t* out_cluster /* int32[N], or NULL */,
                         int64_t* out_n_clusters, int32_t flags);
+/* two-set clustering (cluster_join above): B's rows joined to A's; root_a / root_b: a known grouping of that side, or NULL (the side is
+ * walked); the four statistic arrays all or none; out_cluster may be NULL.  Joint rows: A's 0 .. NA - 1, B's NA .. NA + NB - 1. */
+int svhip_cluster_join(svhip_handle* h, const float* A, int64_t NA, const int32_t* root_a /* int32[NA] or NULL */,
+                       const float* B, int64_t NB, const int32_t* root_b /* int32[NB] or NULL */, int32_t D, float thr,
+                       const float* a_mu, const float* a_sigma, const float* b_mu, const float* b_sigma,
+                       int32_t* out_root /* int32[NA + NB] */, int32_t* out_cluster /* int32[NA + NB], or NULL */,
+                       int64_t* out_n_clusters, int32_t flags);
 /* average / complete linkage inside cluster_above's components (cluster_linkage above); out_cluster and out_n_unrefined may be NULL. */
 enum { SVHIP_LINKAGE_AVERAGE = 1, SVHIP_LINKAGE_COMPLETE = 2 };
 #define SVHIP_LINKAGE_MAX_ROWS 1024

@@ -98,6 +98,7 @@ _SIGNATURES = {
     "svhip_score_above_fill": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P,
                                          C.c_int32]),
     "svhip_cluster_above": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P, _P, _P, C.c_int32]),
+    "svhip_cluster_join": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, _P, _P, _P, _P, _P, _P, _P, C.c_int32]),
     "svhip_cluster_linkage": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32]),
     "svhip_group_audit": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, C.c_float, _P, _P, C.c_int32]),
     "svhip_asnorm_stats": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32]),

@@ -796,6 +796,21 @@ int svhip_selftest(void) {
     if (!once.done(5) || !once.done(63) || once.done(64) || once.done(-3) || once.done(4)) return 3;
     once.mark(0);
     if (!once.done(0) || once.mask.load() != ((1ull << 0) | (1ull << 5) | (1ull << 63))) return 4;
+    // cluster_join's seed clamp (kernels.h): whatever the entry, the result lies in [0, i] - the forest's climbs end on nothing else -
+    // and a legal entry comes back as it is
+    const int32_t entries[] = {INT32_MIN, INT32_MIN + 1, -2, -1, 0, 1, 2, 31, 32, 33, 1 << 20, INT32_MAX - 1, INT32_MAX};
+    const int64_t places[] = {0, 1, 2, 31, 32, 33, 1 << 20, (int64_t)INT32_MAX - 1};
+    for (int64_t i : places)
+        for (int32_t v : entries) {
+            const int32_t got = svhip::cluster_seed_parent(v, i);
+            if (got < 0 || got > i) return 5;
+            if (got != ((v >= 0 && v <= i) ? v : (int32_t)i)) return 6;
+        }
+    for (int64_t i = 0; i < 300; ++i)
+        for (int32_t v = -3; v < 304; ++v) {
+            const int32_t got = svhip::cluster_seed_parent(v, i);
+            if (got < 0 || got > i || (v >= 0 && v <= i && got != v) || ((v < 0 || v > i) && got != i)) return 7;
+        }
     return 0;
 }
 

@@ -43,7 +43,7 @@ void release_big_scratch(svhip_handle* h, bool staged_host) {
     drop(svhip_handle::SCR_COEF);
     if (staged_host)
         for (int s_ : {svhip_handle::SCR_IN0, svhip_handle::SCR_IN1, svhip_handle::SCR_IN2, svhip_handle::SCR_IN3, svhip_handle::SCR_IN4,
-                       svhip_handle::SCR_IN5, svhip_handle::SCR_OUT0, svhip_handle::SCR_OUT1, svhip_handle::SCR_OUT2, svhip_handle::SCR_SPLIT}) drop(s_);
+                       svhip_handle::SCR_IN5, svhip_handle::SCR_IN6, svhip_handle::SCR_IN7, svhip_handle::SCR_OUT0, svhip_handle::SCR_OUT1, svhip_handle::SCR_OUT2, svhip_handle::SCR_SPLIT}) drop(s_);
 }
 
 static int select_device(svhip_handle* h) {

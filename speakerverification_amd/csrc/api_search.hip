@@ -312,6 +312,8 @@ struct ClusterArgs {
     float thr;
     const float2 *qc, *gc;
     int32_t* dRoot;
+    // cluster_join: the set is one side of a joint forest of `forest` rows and starts at its row `off` (forest = 0: cluster_above itself)
+    int64_t off, forest;
 };
 
 int cluster_fused(svhip_handle* h, const ClusterArgs& a) {
@@ -329,17 +331,22 @@ int cluster_fused(svhip_handle* h, const ClusterArgs& a) {
         for (int64_t q0 = 0; q0 < t.rows; q0 += tile)
             for (int64_t y = (t.r0 + q0) / span; y < t.slices; ++y)      // (the first slice that ends above the tile's first row)
                 pairs += (double)std::min(tile, t.rows - q0) * std::min(span, a.N - y * span);
-        if (int rc = run(h, "cluster_link", 2.0 * pairs * a.D, [&]() { return launch_cluster_link(p, a.D, t.few, t.slices, h->stream); })) return rc;
+        if (int rc = run(h, a.forest ? "cluster_join_self" : "cluster_link", 2.0 * pairs * a.D, [&]() {
+                return a.forest ? launch_cluster_join_link(p, a.D, t.few, t.slices, CLUSTER_LINK_SIDE, a.off, a.off, a.forest, h->stream)
+                                : launch_cluster_link(p, a.D, t.few, t.slices, h->stream);
+            })) return rc;
     }
     return SVHIP_OK;
 }
 
 int cluster_slab(svhip_handle* h, const ClusterArgs& a) {
     SlabWalk w{h, a.dE, a.N, a.dE, a.N, a.D};
-    if (int rc = w.open("cluster_above")) return rc;
-    return w.pass("cluster_gemm", true, [&](int64_t r0, int64_t rows, const float* slab, int64_t ldk) {
-        return run(h, "cluster_link_rows", 0, [&]() {
-            return launch_cluster_link_rows(slab, rows, a.N, ldk, a.thr, r0, a.qc ? a.qc + r0 : nullptr, a.gc, a.dRoot, h->stream);
+    if (int rc = w.open(a.forest ? "cluster_join" : "cluster_above")) return rc;
+    return w.pass(a.forest ? "cluster_join_self_gemm" : "cluster_gemm", true, [&](int64_t r0, int64_t rows, const float* slab, int64_t ldk) {
+        return run(h, a.forest ? "cluster_join_self_rows" : "cluster_link_rows", 0, [&]() {
+            const float2* qc = a.qc ? a.qc + r0 : nullptr;
+            return a.forest ? launch_cluster_join_rows(slab, rows, a.N, ldk, a.thr, r0, qc, a.gc, a.dRoot, CLUSTER_LINK_SIDE, a.off, a.off, a.forest, h->stream)
+                            : launch_cluster_link_rows(slab, rows, a.N, ldk, a.thr, r0, qc, a.gc, a.dRoot, h->stream);
         });
     });
 }
@@ -413,6 +420,136 @@ int cluster_impl(svhip_handle* h, const char* name, int32_t linkage, const float
     if (!rc) rc = run(h, "cluster_ids", 0, [&]() { return launch_cluster_ids(a.dRoot, N, bcnt, dCluster, dN, h->stream); });
     return s.finish(name, rc, true);
 }
+
+// ---- two-set clustering: rows B joined to an already clustered (or not yet clustered) set A (svhip_cluster_join) -------------------------
+// The joint forest over NA + NB rows is seeded (cluster_seed), then takes the links of up to three walks in any order: the rectangle A x B
+// (always), and the self-join of every side that brought no seed - cluster_above's own plan and kernels behind the side's offset.  The
+// components of a graph do not depend on the order its edges are met in, so the result is cluster_above's on [A; B] whenever the seeds
+// are cluster_above's on their sides.
+struct JoinSide {
+    const float* d;               // (n, D)
+    int64_t n, off;               // rows, the side's first joint row
+    const int32_t* seed;          // int32[n] on the device, or NULL
+    bool seeded;                  // the caller gave a seed (an empty side has no array to show for it): the side's own pairs are not walked
+    const float2 *qc, *gc;        // its coefficient tables in the query and in the gallery layout, or NULL
+};
+
+// The rectangle on the fused route.  The SMALLER side is the query side (A where they are equal): the queries sit in registers and the
+// gallery streams past them, so a long gallery gives every workgroup a long walk and the call few launches - at 1 048 576 x 64 one
+// launch over A instead of 64 launches of two-block walks.  That is free on this route: both operands of the walk use one k assignment
+// and one accumulation order, and a * b == b * a, so v(a, b) has the same bits whichever row is the query (asserted on the GPU:
+// tests/test_gpu_cluster_join.py), and the normalised score adds its coefficients commutatively.
+int join_cross_fused(svhip_handle* h, const JoinSide& a, const JoinSide& b, int D, float thr, int32_t* dRoot) {
+    const bool swap = b.n < a.n;
+    const JoinSide &q = swap ? b : a, &g = swap ? a : b;
+    std::vector<FusedPart> parts;
+    fused_plan(q.n, g.n, h->num_cu, {0, 0}, parts);
+    for (const FusedPart& t : parts) {
+        ClusterLinkParams p;
+        p.Q = q.d + t.r0 * D; p.N = t.rows; p.G = g.d; p.M = g.n; p.thr = thr; p.row_base = t.r0; p.per = t.per; p.parent = dRoot;
+        p.qcoef = q.qc ? q.qc + t.r0 : nullptr; p.gcoef = q.qc ? g.gc : nullptr;
+        if (int rc = run(h, "cluster_join_link", 2.0 * t.rows * g.n * D, [&]() {
+                return launch_cluster_join_link(p, D, t.few, t.slices, CLUSTER_LINK_CROSS, q.off, g.off, a.n + b.n, h->stream);
+            })) return rc;
+    }
+    return SVHIP_OK;
+}
+
+// the slab route keeps the definitional orientation (the row of A is the query): its GEMM's bits are not promised to be symmetric
+int join_cross_slab(svhip_handle* h, const JoinSide& a, const JoinSide& b, int D, float thr, int32_t* dRoot) {
+    SlabWalk w{h, a.d, a.n, b.d, b.n, D};
+    if (int rc = w.open("cluster_join")) return rc;
+    return w.pass("cluster_join_gemm", true, [&](int64_t r0, int64_t rows, const float* slab, int64_t ldk) {
+        return run(h, "cluster_join_rows", 0, [&]() {
+            return launch_cluster_join_rows(slab, rows, b.n, ldk, thr, r0, a.qc ? a.qc + r0 : nullptr, a.qc ? b.gc : nullptr, dRoot, CLUSTER_LINK_CROSS,
+                                            a.off, b.off, a.n + b.n, h->stream);
+        });
+    });
+}
+
+// a HOST seed array against the rule of cluster_seed_parent (kernels.h): the first entry the seed kernel would not take as it is, or -1
+int64_t first_bad_seed(const int32_t* seed, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (cluster_seed_parent(seed[i], i) != seed[i]) return i;
+    return -1;
+}
+
+int cluster_join_impl(svhip_handle* h, const float* A, int64_t NA, const int32_t* root_a, const float* B, int64_t NB, const int32_t* root_b, int32_t D,
+                      float thr, const float* const* stats, int32_t* out_root, int32_t* out_cluster, int64_t* out_n_clusters, int32_t flags) {
+    if (!h) return SVHIP_ERR_INVALID;
+    const char* name = "cluster_join";
+    if (thr != thr) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: the threshold is NaN", name);
+    if (D < 1) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: D = %d must be at least 1", name, (int)D);
+    if (NA < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: NA = %lld is negative", name, (long long)NA);
+    if (NB < 0) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: NB = %lld is negative", name, (long long)NB);
+    if (NA > (int64_t)INT32_MAX || NB > (int64_t)INT32_MAX || NA + NB > (int64_t)INT32_MAX)
+        SV_FAIL(h, SVHIP_ERR_INVALID, "%s: NA + NB = %lld + %lld is outside [0, 2^31 - 1]", name, (long long)NA, (long long)NB);
+    const int n_stats = !!stats[0] + !!stats[1] + !!stats[2] + !!stats[3];
+    if (n_stats != 0 && n_stats != 4) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: %d of the four statistic arrays are NULL: give all four or none", name, 4 - n_stats);
+    const int64_t N = NA + NB;
+    if (!out_n_clusters || (NA > 0 && !A) || (NB > 0 && !B) || (N > 0 && !out_root)) SV_FAIL(h, SVHIP_ERR_INVALID, "%s: NULL pointer", name);
+    if (D % 32 != 0) SV_FAIL(h, SVHIP_ERR_UNSUPPORTED, "%s: embedding dim %d must be a multiple of 32", name, (int)D);      // before any copy or launch
+    if (!(flags & SVHIP_IN_DEVICE)) {          // host seeds are checked where they are read; device seeds are clamped by the seed kernel
+        int64_t bad;
+        if (root_a && (bad = first_bad_seed(root_a, NA)) >= 0)
+            SV_FAIL(h, SVHIP_ERR_INVALID, "%s: root_a[%lld] = %d is outside [0, %lld]", name, (long long)bad, (int)root_a[bad], (long long)bad);
+        if (root_b && (bad = first_bad_seed(root_b, NB)) >= 0)
+            SV_FAIL(h, SVHIP_ERR_INVALID, "%s: root_b[%lld] = %d is outside [0, %lld]", name, (long long)bad, (int)root_b[bad], (long long)bad);
+    }
+    Staged s(h, flags);
+    if (N == 0) {
+        int64_t* dN = s.out(svhip_handle::SCR_OUT2, out_n_clusters, 8);
+        if (s.rc) return s.rc;
+        SV_HIP(h, hipMemsetAsync(dN, 0, 8, h->stream));
+        return s.finish(name, SVHIP_OK, false);
+    }
+    JoinSide a{}, b{};
+    a.n = NA; a.off = 0; a.seeded = root_a != nullptr;
+    b.n = NB; b.off = NA; b.seeded = root_b != nullptr;
+    a.d = NA ? s.in(svhip_handle::SCR_IN0, A, (size_t)NA * D * 4) : nullptr;
+    b.d = NB ? s.in(svhip_handle::SCR_IN1, B, (size_t)NB * D * 4) : nullptr;
+    a.seed = root_a && NA ? s.in(svhip_handle::SCR_IN6, root_a, (size_t)NA * 4) : nullptr;
+    b.seed = root_b && NB ? s.in(svhip_handle::SCR_IN7, root_b, (size_t)NB * 4) : nullptr;
+    int32_t* dRoot = s.out(svhip_handle::SCR_OUT0, out_root, (size_t)N * 4);
+    int32_t* dCluster = out_cluster ? s.out(svhip_handle::SCR_OUT1, out_cluster, (size_t)N * 4) : nullptr;
+    int64_t* dN = s.out(svhip_handle::SCR_OUT2, out_n_clusters, 8);
+    if (s.rc) return s.rc;
+    int rc = SVHIP_OK;
+    if (n_stats) {
+        // per side ONE (mu, sigma) pair and both of score_topk_coef's layouts of it: the side's rows are queries (of the rectangle, of its
+        // own self-join) and gallery rows (B: of the rectangle; both: of their self-join) - cluster_above's tables, side by side
+        const int slot[4] = {svhip_handle::SCR_IN2, svhip_handle::SCR_IN3, svhip_handle::SCR_IN4, svhip_handle::SCR_IN5};
+        const float* d[4];
+        for (int i = 0; i < 4; ++i) d[i] = s.in(slot[i], stats[i], (size_t)(i < 2 ? NA : NB) * 4);
+        if (s.rc) return s.rc;
+        Bump bt;
+        const size_t o_qa = bt.take((size_t)NA * 8, 16), o_ga = bt.take(NA ? (size_t)score_topk_coef_rows(NA) * 8 : 0, 16);
+        const size_t o_qb = bt.take((size_t)NB * 8, 16), o_gb = bt.take(NB ? (size_t)score_topk_coef_rows(NB) * 8 : 0, 16);
+        void* c = nullptr;
+        if ((rc = scratch(h, svhip_handle::SCR_COEF, bt.size, &c))) return rc;
+        float2 *qa = at<float2>(c, o_qa), *ga = at<float2>(c, o_ga), *qb = at<float2>(c, o_qb), *gb = at<float2>(c, o_gb);
+        if (NA) { a.qc = qa; a.gc = ga; }
+        if (NB) { b.qc = qb; b.gc = gb; }
+        if (NA) rc = run(h, "cluster_join_coef", 0, [&]() { return launch_score_topk_coef(d[0], d[1], NA, d[0], d[1], NA, qa, ga, h->stream); });
+        if (!rc && NB) rc = run(h, "cluster_join_coef", 0, [&]() { return launch_score_topk_coef(d[2], d[3], NB, d[2], d[3], NB, qb, gb, h->stream); });
+        if (rc) return rc;
+    }
+    void* sc = nullptr;
+    if ((rc = scratch(h, svhip_handle::SCR_TOPK, (size_t)cluster_id_blocks(N) * 4, &sc))) return rc;
+    int32_t* bcnt = static_cast<int32_t*>(sc);
+    const bool fused = score_topk_fused_supported(D) && aligned16(a.d, b.d);      // (an empty side's pointer is NULL here)
+    rc = run(h, "cluster_seed", 0, [&]() { return launch_cluster_seed(a.seed, NA, b.seed, NB, dRoot, h->stream); });
+    if (!rc && NA && NB) rc = fused ? join_cross_fused(h, a, b, D, thr, dRoot) : join_cross_slab(h, a, b, D, thr, dRoot);
+    for (const JoinSide* side : {&a, &b}) {
+        if (rc || !side->n || side->seeded) continue;      // a seeded side is trusted, not rescored
+        ClusterArgs ca{};
+        ca.dE = side->d; ca.N = side->n; ca.D = D; ca.thr = thr; ca.qc = side->qc; ca.gc = side->gc; ca.dRoot = dRoot; ca.off = side->off; ca.forest = N;
+        rc = fused ? cluster_fused(h, ca) : cluster_slab(h, ca);
+    }
+    if (!rc) rc = run(h, "cluster_flatten", 0, [&]() { return launch_cluster_flatten(dRoot, N, h->stream); });
+    if (!rc) rc = run(h, "cluster_ids", 0, [&]() { return launch_cluster_ids(dRoot, N, bcnt, dCluster, dN, h->stream); });
+    return s.finish(name, rc, true);
+}
 }  // namespace
 
 int svhip_cluster_above(svhip_handle* h, const float* E, int64_t N, int32_t D, float thr, const float* mu, const float* sigma, int32_t* out_root,
@@ -425,6 +562,13 @@ int svhip_cluster_linkage(svhip_handle* h, const float* E, int64_t N, int32_t D,
     if (h && linkage != SVHIP_LINKAGE_AVERAGE && linkage != SVHIP_LINKAGE_COMPLETE)
         SV_FAIL(h, SVHIP_ERR_INVALID, "cluster_linkage: linkage = %d is neither SVHIP_LINKAGE_AVERAGE nor SVHIP_LINKAGE_COMPLETE", (int)linkage);
     return cluster_impl(h, "cluster_linkage", linkage, E, N, D, thr, mu, sigma, out_root, out_cluster, out_n_clusters, out_n_unrefined, flags);
+}
+
+int svhip_cluster_join(svhip_handle* h, const float* A, int64_t NA, const int32_t* root_a, const float* B, int64_t NB, const int32_t* root_b, int32_t D,
+                       float thr, const float* a_mu, const float* a_sigma, const float* b_mu, const float* b_sigma, int32_t* out_root,
+                       int32_t* out_cluster, int64_t* out_n_clusters, int32_t flags) {
+    const float* stats[4] = {a_mu, a_sigma, b_mu, b_sigma};
+    return cluster_join_impl(h, A, NA, root_a, B, NB, root_b, D, thr, stats, out_root, out_cluster, out_n_clusters, flags);
 }
 
 }  // extern "C"

@@ -170,7 +170,7 @@ struct svhip_handle {
     // scoring / metrics scratch: handle-owned slots, grown on demand (no hipMalloc / hipFree per call once warm).  The scoring files
     // (api_scoring.hip, api_asnorm.hip, api_search.hip, api_audit.hip, api_metrics.hip) reach them through scoring_host.h
     enum { SCR_IN0 = 0, SCR_IN1, SCR_IN2, SCR_IN3, SCR_IN4, SCR_OUT0, SCR_OUT1, SCR_OUT2, SCR_SLAB, SCR_SPLIT, SCR_CAND, SCR_CNT, SCR_MB,
-           SCR_FLAG, SCR_GATHER, SCR_WS, SCR_TOPK, SCR_IN5, SCR_COEF, SCR_COUNT };
+           SCR_FLAG, SCR_GATHER, SCR_WS, SCR_TOPK, SCR_IN5, SCR_COEF, SCR_IN6, SCR_IN7, SCR_COUNT };
     void* scr[SCR_COUNT] = {};
     size_t scr_cap[SCR_COUNT] = {};
     hipStream_t aux_stream = nullptr;         // second stream of the scoring entry points (candidate statistics under the next MFMA launch)

@@ -807,6 +807,23 @@ hipError_t launch_cluster_link(const ClusterLinkParams& p, int D, bool few, int 
 hipError_t launch_cluster_link_rows(const float* S, int64_t rows, int64_t M, int64_t ld, float thr, int64_t row_base, const float2* qcoef,
                                     const float2* gcoef, int32_t* parent, hipStream_t stream);
 hipError_t launch_cluster_flatten(int32_t* root, int64_t N, hipStream_t stream);
+// Two-set clustering (svhip_cluster_join): A's rows are 0 .. NA - 1 of the joint forest, B's NA .. NA + NB - 1.
+// The clamp of a seed entry, written once for the seed kernel and for the host check of host seeds: row i of a side may point at any row
+// of [0, i] of that side; every other value is read as i, so the row starts alone.  The forest's climbs end only because parent[x] <= x
+// holds everywhere (score_cluster.hip): whatever a seed array holds, what this returns keeps that.
+__host__ __device__ inline int32_t cluster_seed_parent(int32_t seed, int64_t i) { return seed >= 0 && (int64_t)seed <= i ? seed : (int32_t)i; }
+// parent[i] = root_a[i] clamped (NULL: i); parent[NA + j] = NA + root_b[j] clamped (NULL: NA + j)
+hipError_t launch_cluster_seed(const int32_t* root_a, int64_t NA, const int32_t* root_b, int64_t NB, int32_t* parent, hipStream_t stream);
+// The link launches with an index offset on either side: a link is (q_off + row_base + the query's place in the launch, g_off + the
+// gallery row), and every such index must lie below `forest`, the size of `parent`.
+//   CLUSTER_LINK_SET    cluster_above's own launch (launch_cluster_link / _rows: no offsets)
+//   CLUSTER_LINK_SIDE   the self-join of one side: the masks of CLUSTER_LINK_SET, q_off == g_off == the side's first joint row
+//   CLUSTER_LINK_CROSS  the rectangle: every (query, gallery row) pair, no mask
+enum { CLUSTER_LINK_SET = 0, CLUSTER_LINK_SIDE = 1, CLUSTER_LINK_CROSS = 2 };
+hipError_t launch_cluster_join_link(const ClusterLinkParams& p, int D, bool few, int slices, int form, int64_t q_off, int64_t g_off, int64_t forest,
+                                    hipStream_t stream);
+hipError_t launch_cluster_join_rows(const float* S, int64_t rows, int64_t M, int64_t ld, float thr, int64_t row_base, const float2* qcoef,
+                                    const float2* gcoef, int32_t* parent, int form, int64_t q_off, int64_t g_off, int64_t forest, hipStream_t stream);
 // dense ids from flattened roots: *out_n = the number of roots; cluster (optional) [i] = the roots below root[i].  bcnt: cluster_id_blocks(N)
 // int32 of scratch (per-block root counts, scanned in place by one workgroup)
 int64_t cluster_id_blocks(int64_t N);

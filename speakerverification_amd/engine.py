@@ -657,6 +657,41 @@ class Engine:
         c.run(self.lib.svhip_cluster_above, self.h, e, N, D, thr, *sp, r, cl, n)
         return root, cluster, (count[0] if _is_torch(count) else int(count[0]))
 
+    def cluster_join(self, A, B, thr, root_a=None, root_b=None, a_stats=None, b_stats=None):
+        """Two-set clustering (``svhip_cluster_join``): joins the rows B (NB, D) to a set A (NA, D) that may already be clustered,
+        without scoring A against itself again.  The rows are numbered jointly - A's are ``0 .. NA - 1``, B's ``NA .. NA + NB - 1`` -
+        and the clusters are the connected components of: the seed links of a side whose ``root_x`` is given (row i is linked to row
+        ``root_x[i]`` of its side, ``0 <= root_x[i] <= i``: ``cluster_above``'s ``root``, or any downward parent-pointer forest; the
+        side's own pairs are then NOT scored); the pairs ``i < j`` of a side without a seed, scored as ``cluster_above`` scores them;
+        and every pair (row of A, row of B) whose score is at least ``thr``.  The score is ``score_above``'s for the query row of A
+        and the gallery row of B, or - with ``a_stats`` and ``b_stats``, the ``(mu, sigma)`` pairs of ``asnorm_stats``, both or
+        neither - the normalised score.  With seeds that are ``cluster_above``'s roots of their sides (or none) the result is exactly
+        ``cluster_above`` of the concatenation.  A host seed with an entry outside ``[0, i]`` is refused by index; on the device such
+        an entry is read as ``i``.  Returns ``(root (NA + NB,) int32, cluster (NA + NB,) int32, n_clusters)`` as ``cluster_above``
+        does, in the inputs' memory space (all arrays in one)."""
+        NA, D = (int(x) for x in A.shape)
+        NB = int(B.shape[0])
+        if int(B.shape[1]) != D:
+            raise ValueError(f"cluster_join: A is {D} wide, B {int(B.shape[1])}")
+        thr = float(thr)
+        if thr != thr:
+            raise ValueError("cluster_join: the threshold is NaN")
+        if (a_stats is None) != (b_stats is None):
+            raise ValueError("cluster_join: a_stats and b_stats go together: give both (normalised scores) or neither")
+        stats = () if a_stats is None else self._stat_pair("a_stats", a_stats, NA) + self._stat_pair("b_stats", b_stats, NB)
+        for name, seed, n in (("root_a", root_a, NA), ("root_b", root_b, NB)):
+            if seed is not None and tuple(seed.shape) != (n,):
+                raise ValueError(f"cluster_join: {name} must hold {n} values, not {tuple(seed.shape)}")
+        N = NA + NB
+        root, cluster, count = self._out(A, N, np.int32), self._out(A, N, np.int32), self._out(A, 1, np.int64)
+        c = _Call(self, same_space=True)
+        a, b = c.inp(A), c.inp(B)
+        ra, rb = (None if x is None else c.inp(x, np.int32) for x in (root_a, root_b))
+        sp = [c.inp(x) for x in stats] or [None] * 4
+        r, cl, n = c.out(root, np.int32), c.out(cluster, np.int32), c.out(count, np.int64)
+        c.run(self.lib.svhip_cluster_join, self.h, a, NA, ra, b, NB, rb, D, thr, *sp, r, cl, n)
+        return root, cluster, (count[0] if _is_torch(count) else int(count[0]))
+
     _LINKAGES = {"average": _lib.LINKAGE_AVERAGE, "complete": _lib.LINKAGE_COMPLETE}
 
     def cluster_linkage(self, E, thr, stats=None, linkage="average"):

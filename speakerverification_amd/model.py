@@ -734,6 +734,58 @@ class ModelHandling:
                 groups[c].append(names[i])
         return labels, groups
 
+    def cluster_extend(self, base_embeds, base_labels=None, source=None, embeds=None, thresh_score=None, num_eval=10, scoring_mode="cosine",
+                       cohorts=None, cohorts_path=None, cohort_top=200):
+        """Which of the clusters I already have do these NEW files belong to?  Joins new rows to a base set that was clustered before
+        (by ``cluster``, by a person, or not at all) in ONE ``cluster_join`` call: the base rows are not scored against each other
+        again, so the cost grows with (base x new + new^2 / 2) pairs, not with the square of everything ever ingested.
+
+        ``base_embeds``: the base set in ``identify``'s three gallery forms, prepared as ``cluster(embeds=)`` prepares it.
+        ``base_labels``: its known grouping as any integer labelling (an equal label means the same cluster; ``cluster``'s ``labels``
+        with ``min_size=1``, or labels a person has corrected) - it is trusted, not rescored; ``None``: every base row is a cluster of
+        its own (an enrolled gallery).  The new rows: exactly one of ``source`` (files) and ``embeds`` (a gallery), prepared as
+        ``cluster`` prepares them; their own pairs are scored.  ``scoring_mode`` and the cohort arguments are ``identify``'s.
+
+        Only SINGLE linkage is served: a cluster is a connected component of the links, and with ``base_labels = cluster(base)``'s
+        labels the result is exactly ``cluster`` of base and new rows together.  A new row may join a base cluster, start a new one,
+        or bridge two base clusters, which then come back as one.
+
+        Returns ``(base_ids (NA,) int32, new_ids (NB,) int32, merged)``: the dense ids of the joint clustering, numbered in order of
+        each cluster's smallest member (base rows first), and ``merged``: the groups of DISTINCT input base labels that ended in one
+        cluster, each a sorted list, in order of the cluster's id - empty when no new row bridged anything."""
+        if (source is None) == (embeds is None):
+            raise ValueError("cluster_extend: give exactly one of source (files) and embeds (a gallery)")
+        if thresh_score is None:
+            raise ValueError("cluster_extend: thresh_score is required")
+        base, _ = self._gallery(base_embeds, None)
+        if base_labels is None:
+            base_labels = np.arange(base.shape[0], dtype=np.int64)
+        base_labels = np.asarray(_host(base_labels)).reshape(-1)
+        if base_labels.shape[0] != base.shape[0]:
+            raise ValueError(f"cluster_extend: {base_labels.shape[0]} base labels for {base.shape[0]} base rows")
+        cohorts = self._cohort(scoring_mode, cohorts, cohorts_path, base.shape[1])
+        eng = scoring.scoring_engine(self.gpu)
+        if source is not None:
+            self.__model__.eval()
+            names = list(source) if isinstance(source, (list, tuple)) else [source]
+            if not names:
+                raise ValueError("Please provide appropriate source!")
+            rows = self._crop_mean_rows(names, num_eval)
+        else:
+            rows, _ = self._gallery(embeds, None)
+        if rows.shape[1] != base.shape[1]:
+            raise ValueError(f"the new rows are {rows.shape[1]} wide, the base set {base.shape[1]}")
+        eng.l2norm_(base)
+        eng.l2norm_(rows)
+        _, ids, _ = scoring.cluster_join(base, rows, thresh_score, labels_a=base_labels, cohort=cohorts, top=int(cohort_top), device=self.gpu)
+        ids = np.asarray(_host(ids)).astype(np.int32, copy=False)
+        base_ids, new_ids = ids[:base.shape[0]], ids[base.shape[0]:]
+        seen = {}
+        for c, lab in zip(base_ids.tolist(), base_labels.tolist()):
+            seen.setdefault(c, set()).add(lab)
+        merged = [sorted(labs) for c, labs in sorted(seen.items()) if len(labs) > 1]
+        return base_ids, new_ids, merged
+
     # ---- dataset audit ----------------------------------------------------------------------------------------------------
     def audit(self, source, thresh_score, num_eval=20, save_file=None, max_files=65536):
         """Which files of a speaker folder do not sound like the rest of it?  The reference's label-noise audit

@@ -1,7 +1,7 @@
 """Scoring counterparts of the reference's ``src/utils.py:126-169``.
 
 ``similarity_measure(method, ref, com, **kw)`` keeps the per-trial signature for compatibility; the
-batched entry points (``score_pairs``, ``score_matrix``, ``score_topk``, ``score_topk_norm``, ``score_above``, ``cluster``, ``group_audit``, ``asnorm_stats``,
+batched entry points (``score_pairs``, ``score_matrix``, ``score_topk``, ``score_topk_norm``, ``score_above``, ``cluster``, ``cluster_join``, ``group_audit``, ``asnorm_stats``,
 ``asnorm_pairs``, ``score_trials``) are what ``ModelHandling.evaluateFromList`` uses: one kernel launch per trial LIST
 instead of three host<->device crossings per trial.
 """
@@ -122,6 +122,56 @@ def cluster(E, thr, cohort=None, top=200, stats=None, device=0, linkage="single"
     if linkage == "single":
         return eng.cluster_above(E, thr, stats)
     return eng.cluster_linkage(E, thr, stats, linkage)
+
+
+def _first_rows_torch(lab):
+    """``labels_to_roots`` for a 1-D integer tensor, where it lives (plumbing: unique, then the smallest row of each label)"""
+    _, inv = torch.unique(lab, return_inverse=True)
+    first = torch.full((int(inv.max()) + 1 if inv.numel() else 0,), lab.numel(), dtype=torch.int64, device=lab.device)
+    first.scatter_reduce_(0, inv, torch.arange(lab.numel(), device=lab.device), "amin")
+    return first[inv].to(torch.int32)
+
+
+def labels_to_roots(labels, n=None, what="labels"):
+    """any integer labelling (an equal label means the same cluster) -> the root form ``cluster_join`` takes as a seed: per row the
+    FIRST row that carries its label (int32, ``root[i] <= i``); on the host, or on the device for a CUDA tensor.  ``n``: the length
+    the labelling must have."""
+    on_dev = _is_torch(labels) and labels.is_cuda
+    lab = _np(labels).reshape(-1) if not on_dev else labels.reshape(-1)
+    if n is not None and int(lab.shape[0]) != int(n):
+        raise ValueError(f"cluster_join: {what} must hold {int(n)} values, not {int(lab.shape[0])}")
+    if on_dev:
+        if lab.dtype.is_floating_point or lab.dtype == torch.bool:
+            raise ValueError(f"cluster_join: {what} must be integers, not {lab.dtype}")
+        return _first_rows_torch(lab)
+    if lab.dtype.kind not in "iu":
+        raise ValueError(f"cluster_join: {what} must be integers, not {lab.dtype}")
+    _, first, inv = np.unique(lab, return_index=True, return_inverse=True)
+    return first[inv.reshape(-1)].astype(np.int32) if lab.size else np.zeros(0, np.int32)
+
+
+def cluster_join(A, B, thr, labels_a=None, labels_b=None, cohort=None, top=200, a_stats=None, b_stats=None, device=0):
+    """which clusters do the new rows B belong to?  Joins B (NB, D) to a set A (NA, D) without scoring A against itself again ->
+    ``(root (NA + NB,) int32, cluster (NA + NB,) int32, n_clusters)`` over the joint rows, A's first (``Engine.cluster_join``).
+    ``labels_a`` / ``labels_b``: a known grouping of that side as ANY integer labelling - an equal label means the same cluster -
+    which is trusted, not rescored; ``None``: the side's own pairs are scored as ``cluster`` scores them.  Every pair (row of A, row
+    of B) whose score is at least ``thr`` is linked, so a new row may join an old cluster, start its own, or bridge two old ones.
+    With ``labels_a = cluster(A, thr)[1]`` the result is exactly ``cluster`` of the concatenation (single linkage).  With a
+    ``cohort`` the score is the adaptive-S-normalised one: the statistics of each side come from ``asnorm_stats(., cohort, top)``
+    unless ``a_stats`` / ``b_stats = (mu, sigma)``, kept from an earlier call, are given.  All arrays in one memory space."""
+    if float(thr) != float(thr):
+        raise ValueError("cluster_join: the threshold is NaN")
+    if cohort is None and (a_stats is None) != (b_stats is None):
+        raise ValueError("cluster_join: a_stats and b_stats go together without a cohort: give both or neither")
+    root_a = None if labels_a is None else labels_to_roots(labels_a, A.shape[0], "labels_a")
+    root_b = None if labels_b is None else labels_to_roots(labels_b, B.shape[0], "labels_b")
+    eng = scoring_engine(device)
+    if cohort is not None:
+        if a_stats is None:
+            a_stats = eng.asnorm_stats(A, cohort, top)
+        if b_stats is None:
+            b_stats = eng.asnorm_stats(B, cohort, top)
+    return eng.cluster_join(A, B, thr, root_a, root_b, a_stats, b_stats)
 
 
 def audit_cut(threshold):
